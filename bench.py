@@ -12,8 +12,14 @@ per GPU, weak scaling (every rank its own piles).  `--workload c4` makes BASELIN
 config 4 the headline instead: 1024 independent 64-body ensembles (fp32, 50
 sweeps), SHARDED over the ranks (eggshell_amd.dist.shard_range), strong scaling.
 
-On one GPU the same JSON line carries every other BASELINE configuration and
-the kernels the north star names, each with the physical bound that applies:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up the headline workload, warms up, times
+exactly K steps and prints the one JSON line: `value`, `ms_per_step` and the headline's bounds, which come
+from the timed launches themselves and the committed profiles/.  `--dump-outputs DIR` also writes what the
+last timed step computed (DIR/lambda.npy, DIR/velocity.npy; inputs are seeded, so two builds can be
+compared output for output).
+
+With `--full`, on one GPU the same JSON line also carries every other BASELINE configuration, the CPU
+baselines and the kernels the north star names, each with the physical bound that applies:
   single_pile   one C3 pile (the dependency chain of a pile: latency)
   matvec        the stand-alone block-sparse J M^-1 J^T product on C3 x batch
                 (the one kernel of the path that streams: HBM roofline)
@@ -25,7 +31,8 @@ the kernels the north star names, each with the physical bound that applies:
   c5            dense direct LCP, N = 2048 (MFMA fp64), CPU dense oracle beside it
   cpu_baseline  the CPU port of the same step on the host cores
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full [--legs LEG,... --cpu-seconds S]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...          (no launcher: bench.py starts its own N ranks)
@@ -361,6 +368,23 @@ def run_piles(ctx, workload, seeds, method, steps, warmup, torch=None, tdist=Non
     hbm = hbm_roofline_from_counters(kname, kernel_ms, m, case) or hbm
     return dict(elapsed=elapsed, n=sc["p"].shape[0], m=m, sweeps=sweeps, prec=prec, dt=dt, stats=st, t_plan=t_plan,
                 roofline=valu, roofline_hbm=hbm, latency_model=lat, shape=(nx, ny, nz), problem=pr, scene=sc, piles=len(piles))
+
+
+DUMP_BYTES_MAX = 60 * 10**6     # --dump-outputs: at most this many bytes of arrays in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path computed in its last step, as `path`/<name>.npy in float64.
+    Above DUMP_BYTES_MAX in all, every array is cut to a fixed sample of its flattened elements (indices drawn by
+    numpy default_rng(0), sorted): the same elements from run to run, so two builds compare element by element."""
+    os.makedirs(path, exist_ok=True)
+    total = 8 * sum(a.size for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if total > DUMP_BYTES_MAX:
+            keep = a.size * DUMP_BYTES_MAX // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def leg_from_run(r, steps, unit="pile-steps/s", note=None):
@@ -844,14 +868,25 @@ def main():
     ap.add_argument("--batch", type=int, default=24, help="C3: independent piles resident per GPU (24 x 1024 columns = two full rounds of 3 tiles per CU)")
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c4"], help="the headline workload (`value`)")
     ap.add_argument("--method", default="gs", choices=["gs", "sor"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip every CPU leg)")
-    ap.add_argument("--legs", default="all", help="'all', 'none' or a comma list of single_pile,matvec,c1,c2,c4,coupled,c5,lcp_batch,literal,stopping_loop,world (1 GPU only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the other legs (--legs) and the CPU baselines "
+                    "(--cpu-seconds); a plain run times the headline workload only")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="with --full: CPU baseline budget (default 12; 0 = skip every CPU leg)")
+    ap.add_argument("--legs", default=None, help="with --full: 'all' (default), 'none' or a comma list of single_pile,matvec,c1,c2,c4,"
+                    "coupled,c5,lcp_batch,literal,stopping_loop,world (1 GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0's "
+                    "lambda and body velocities) as DIR/<name>.npy, float64")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo only to rehearse N>1 on a 1-GPU box")
     ap.add_argument("--share-device0", action="store_true", help="rehearsal: every rank uses GPU 0")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / sharding / statistics reduction only, no GPU "
                     "work (CPU test of the N > 1 plumbing; the line says dry_run)")
     args = ap.parse_args()
+    if not args.full and ((args.legs or "none") != "none" or (args.cpu_seconds or 0.0) > 0):
+        ap.error("--legs and --cpu-seconds select what --full measures besides the headline: add --full")
+    if args.legs is None:
+        args.legs = "all" if args.full else "none"
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 12.0 if args.full else 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher (nothing has touched the GPU yet)
@@ -877,7 +912,10 @@ def main():
         seeds, scaling, unit = c4_shard_seeds(rank, world), "strong", "ensemble-steps/s"
     else:                         # every rank its own piles; seeds differ per rank and pile
         seeds, scaling, unit = [rank * args.batch + b + 1 for b in range(args.batch)], "weak", "pile-steps/s"
-    r = run_piles(ctx, args.workload, seeds, method, args.steps, args.warmup, torch, tdist, world)
+    # one rank: ctx.synchronize() alone closes the timed region (torch's own device context is never started)
+    r = run_piles(ctx, args.workload, seeds, method, args.steps, args.warmup, torch if world > 1 else None, tdist, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"lambda": r["problem"].lambda_(), "velocity": r["problem"].velocity()})
     st, m, sweeps = r["stats"], r["m"], r["sweeps"]
     el, units, citers, resid, failed = egs_dist.reduce_stats(
         r["elapsed"], len(seeds) * args.steps, float(m) * sweeps * args.steps, st.residual, st.status != capi.OK,

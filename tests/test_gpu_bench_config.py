@@ -70,3 +70,32 @@ def test_wres_elementwise_small(ctx):
         # same mathematics, different rounding
         assert np.abs(w - (orc.fast_matvec(s, lam, orc.MV_FULL, 0.02) - rhs)).max() < 1e-11 * scale
         pr.close()
+
+
+def test_plain_bench_run_dumps_its_last_step(ctx, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (2 piles): one result line with the headline keys and none
+    of --full's legs, and the dumped arrays are what the same steps leave in a problem built here."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "2", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = lines[0]
+    assert out["metric"] == "constraint_solve_steps_per_sec" and out["unit"] == "pile-steps/s" and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not out["failed"]
+    assert not any(k in out for k in ("single_pile", "matvec", "c5", "cpu_baseline", "world_step"))
+    nx, ny, nz, sweeps, prec, dt = bench.WORKLOADS["c3"]
+    sc = scenes.concat([scenes.box_stack(nx, ny, nz, jitter=1e-3, seed=k + 1, origin=(0.0, 100.0 * k)) for k in range(2)])
+    pr, _ = bench.build_problem(ctx, sc, capi.F64)
+    prm = capi.params(method=capi.GAUSS_SEIDEL, max_iters=sweeps, tol=0.0, cfm=0.01)
+    for _ in range(1 + 3):
+        pr.step(dt, 0.2, prm)
+    lam, vel = np.load(tmp_path / "lambda.npy"), np.load(tmp_path / "velocity.npy")
+    assert lam.dtype == np.float64 and np.array_equal(lam, pr.lambda_())
+    assert vel.dtype == np.float64 and np.array_equal(vel, pr.velocity())
+    pr.close()

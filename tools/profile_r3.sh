@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun).  Per-leg evidence for bench.py's rooflines, one workload per run so that a
 # kernel name maps to ONE problem size:
-#   stats:<leg>   rocprofv3 --kernel-trace --stats of `bench.py --legs <leg>` (leg = none | single_pile | c4 | ...)
+#   stats:<leg>   rocprofv3 --kernel-trace --stats of `bench.py --full --legs <leg>` (leg = none | single_pile | c4 | ...)
 #   <case>        four counter-only passes over tools/pmc_case.py <case> (tile | quad | c4 | coupled | matvec | c2):
 #                 SQ pass 1, SQ pass 2, FETCH_SIZE, WRITE_SIZE -- separate runs, --pmc only (no trace domains)
 # then tools/profile_summary.py folds everything under OUTDIR into counters.json + kernel_stats_<leg>.csv.
@@ -18,7 +18,7 @@ for c in "$@"; do
   case "$c" in
     stats:*)
       leg="${c#stats:}"
-      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$leg" -o kt -- python3 "$R/bench.py" --steps 20 --warmup 5 --cpu-seconds 0 --legs "$leg" > "$OUT/kt_$leg.log" 2>&1 || echo "stats $leg failed"
+      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_$leg" -o kt -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --cpu-seconds 0 --legs "$leg" > "$OUT/kt_$leg.log" 2>&1 || echo "stats $leg failed"
       echo "stats $leg done"
       ;;
     *)
