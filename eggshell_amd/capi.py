@@ -31,7 +31,7 @@ EXPORTS = [
     "egs_problem_get_stats", "egs_mixed_constraints_solve", "egs_debug_plan", "egs_debug_plan_slots",
     "egs_update_contacts", "egs_update_contacts_joints", "egs_world_create", "egs_world_destroy", "egs_world_set_bodies",
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
-    "egs_world_get_lambda", "egs_world_info",
+    "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
@@ -506,11 +506,36 @@ def debug_plan_timetable(n_bodies, body0, body1, tile_size=256):
 class World:
     """Ensemble::Step resident on the device (collide -> solve -> integrate)."""
 
-    def __init__(self, ctx, n_bodies, precision=F64):
+    def __init__(self, ctx, n_bodies, precision=F64, _handle=None):
         self.ctx, self.n = ctx, int(n_bodies)
-        self.h = C.c_void_p()
-        ctx.check(load().egs_world_create(ctx.h, C.c_int32(self.n), C.c_int32(precision), C.byref(self.h)))
+        self.n_ensembles = 1
+        if _handle is None:
+            self.h = C.c_void_p()
+            ctx.check(load().egs_world_create(ctx.h, C.c_int32(self.n), C.c_int32(precision), C.byref(self.h)))
+        else:
+            self.h = _handle
         ctx._children.add(self)
+
+    @classmethod
+    def batch(cls, ctx, n_bodies, precision=F64):
+        """E independent ensembles in one world (egs_world_create_batch): n_bodies [E].
+        Returns (world, body_offset [E+1]); body arrays are the ensembles' concatenated."""
+        nb = _i32(n_bodies)
+        off = np.zeros(nb.shape[0] + 1, np.int32)
+        h = C.c_void_p()
+        ctx.check(load().egs_world_create_batch(ctx.h, C.c_int32(nb.shape[0]), _p(nb), C.c_int32(precision),
+                                                C.byref(h), _p(off)))
+        w = cls(ctx, int(off[-1]), precision, _handle=h)
+        w.n_ensembles = int(nb.shape[0])
+        return w, off
+
+    def batch_info(self):
+        """Per-ensemble figures: joint_offset / contact_offset [E+1], iterations / residual [E] of the last solve."""
+        E = self.n_ensembles
+        jo = np.zeros(E + 1, np.int32); co = np.zeros(E + 1, np.int32)
+        it = np.zeros(E, np.int32); res = np.zeros(E)
+        self.ctx.check(load().egs_world_batch_info(self.h, C.c_int32(E), _p(jo), _p(co), _p(it), _p(res)))
+        return dict(joint_offset=jo, contact_offset=co, iterations=it, residual=res)
 
     def close(self):
         if self.h:

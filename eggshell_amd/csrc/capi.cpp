@@ -643,6 +643,57 @@ void fill_history_args(egs_problem *p, SolveArgs<REAL> &a, REAL cfm) {
   a.m = p->m; a.n_bodies = p->n; a.cfm = cfm;
 }
 
+// ---- the stopping loop's schedule (tol > 0), shared by do_solve and do_solve_batch ----------------
+// With recorded chunks the residual of x0 is not waited for: its partial sums ride on the first chunk's
+// read-back and the chunk is launched at once (EGS_DEFER_RESIDUAL=0: read on its own).
+bool defer_first_residual(const egs_solve_params *prm) {
+  const char *e = std::getenv("EGS_DEFER_RESIDUAL");
+  return prm->max_iters > 1 && !(e && std::atoi(e) == 0);
+}
+// Fast form, same result: sweeps run in chunks while the kernels record x and the per-body accumulators
+// after every sweep ... on every schedule, oversize islands on the patch kernels or the all-global kernel
+// included.  Only Jacobi on oversize islands, which is a launch per sweep anyway, takes the plain loop.
+bool use_history(egs_problem *p, const egs_solve_params *prm) {
+  const bool quad = p->use_quad && prm->method != EGS_JACOBI;
+  if (!quad) ensure_tile_plan(p);
+  return (quad || p->plan.global.empty() || prm->method != EGS_JACOBI) && prm->max_iters > 1;
+}
+// Up to 256 recorded sweeps per launch within 2 GiB of snapshots (24 C3 piles: 14 MB per sweep).  The first
+// launch records at most 64 and every further one twice as many as the one before: a solve that converges
+// early wastes little, a long one pays the timetable's fill and the read-back once per 256 sweeps.
+struct ChunkSchedule {
+  int K = 1, cur = 1;
+  ChunkSchedule(const egs_problem *p, const egs_solve_params *prm) {
+    const size_t rs = p->real_size(), m = (size_t)p->m, n = (size_t)(p->n > 0 ? p->n : 1);
+    const size_t per_sweep = (3 * m + 6 * n) * rs;
+    K = (int)std::min<size_t>(256, std::max<size_t>(1, (size_t(2048) << 20) / per_sweep));
+    K = std::min(K, prm->max_iters);
+    cur = std::min(K, 64);
+  }
+  int next(int left) {
+    const int chunk = std::min(cur, left);
+    cur = std::min(2 * cur, K);
+    return chunk;
+  }
+};
+// snapshot buffers for K sweeps; bodies without constraints never get a snapshot written: theirs stays zero
+void prepare_history(egs_problem *p, int K) {
+  const size_t rs = p->real_size(), m = (size_t)p->m, n = (size_t)(p->n > 0 ? p->n : 1);
+  p->hist_x.alloc((size_t)K * 3 * m * rs);
+  p->hist_acc.alloc((size_t)K * 6 * n * rs);
+  HIPCHK(hipMemsetAsync(p->hist_acc.p, 0, (size_t)K * 6 * n * rs, p->ctx->stream));
+}
+// the snapshots are scratch of ONE call: a problem object that once ran a tolerance-terminated solve on a large
+// system must not keep up to 2 GiB of HBM (and the page-locked mirror) for the rest of its life.  Small ones stay
+// (a converging Chain re-solves every step); the stream-ordered free waits for the kernels above.
+void release_large_history(egs_problem *p) {
+  static const size_t keep_mb = [] { const char *e = std::getenv("EGS_HIST_KEEP_MB"); return e ? (size_t)std::atol(e) : (size_t)256; }();
+  if (p->hist_x.bytes() + p->hist_acc.bytes() > (keep_mb << 20)) {
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    p->hist_x.release(); p->hist_acc.release(); p->hist_out.release();
+  }
+}
+
 // The solve driver: sparse_iterations.cc:148-226.
 egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats) {
   egs_context *ctx = p->ctx;
@@ -691,36 +742,21 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
   int it = 0, flag = 0;
   launch_solve(p, *prm, 0, 0);
   launch_residual(p);
-  // With recorded chunks (below) the residual of x0 is not waited for: its partial sums ride on the first chunk's
-  // read-back and the chunk is launched at once.  Should x0 already satisfy the test (it never does in practice: the
-  // reference starts from x0 = rhs) its state is simply produced again.
-  const bool defer_first = prm->max_iters > 1 && !(std::getenv("EGS_DEFER_RESIDUAL") && std::atoi(std::getenv("EGS_DEFER_RESIDUAL")) == 0);
+  // Should x0 already satisfy the test when its residual is deferred (it never does in practice: the reference
+  // starts from x0 = rhs) its state is simply produced again.
+  const bool defer_first = defer_first_residual(prm);
   double err = 0.0;
-  // Fast form, same result: sweeps run in chunks of up to 64 per launch while the kernels
-  // record x and the per-body accumulators after every sweep; one more kernel evaluates the
-  // stopping test of every recorded sweep and ONE read-back per chunk finds the first sweep
-  // that satisfies it.
-  const bool quad = p->use_quad && prm->method != EGS_JACOBI;
-  // ... and oversize islands on the patch kernels or the all-global kernel.  Only Jacobi on
-  // oversize islands, which is a launch per sweep anyway, takes the plain loop below.
-  if (!quad) ensure_tile_plan(p);
-  const bool history = (quad || p->plan.global.empty() || prm->method != EGS_JACOBI) && prm->max_iters > 1;
+  // one more kernel evaluates the stopping test of every recorded sweep and ONE read-back per chunk finds the
+  // first sweep that satisfies it (use_history)
+  const bool history = use_history(p, prm);
   const bool deferred = history && defer_first;
   if (!deferred) err = read_residual(p, &flag);
   if (history) {
-    const size_t rs = p->real_size(), m = (size_t)p->m, n = (size_t)(p->n > 0 ? p->n : 1);
-    const size_t per_sweep = (3 * m + 6 * n) * rs;
-    // up to 256 recorded sweeps per launch within 2 GiB of snapshots (24 C3 piles: 14 MB per sweep).  The first
-    // launch records at most 64 and every further one twice as many as the one before: a solve that converges
-    // early wastes little, a long one pays the timetable's fill and the read-back once per 256 sweeps
-    int K = (int)std::min<size_t>(256, std::max<size_t>(1, (size_t(2048) << 20) / per_sweep));
-    K = std::min(K, prm->max_iters);
-    int k_cur = std::min(K, 64);
-    p->hist_x.alloc((size_t)K * 3 * m * rs);
-    p->hist_acc.alloc((size_t)K * 6 * n * rs);
+    const size_t rs = p->real_size(), m = (size_t)p->m;
+    ChunkSchedule sched(p, prm);
+    const int K = sched.K;
+    prepare_history(p, K);
     p->hist_out.alloc((size_t)K * kResidualBlocks * 4);
-    // bodies without constraints never get a snapshot written: theirs stays zero
-    HIPCHK(hipMemsetAsync(p->hist_acc.p, 0, (size_t)K * 6 * n * rs, ctx->stream));
     // read-backs land in page-locked memory: a pageable destination makes each of the two copies per launch a
     // synchronous bounce through the runtime's staging buffer
     const size_t part_len = (size_t)K * kResidualBlocks * 4, first_len = (size_t)kResidualBlocks * 4;
@@ -738,8 +774,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
       err = std::numeric_limits<double>::infinity();
     }
     while (!flag && err > prm->tol && it < prm->max_iters) {
-      const int chunk = std::min(k_cur, prm->max_iters - it);
-      k_cur = std::min(2 * k_cur, K);
+      const int chunk = sched.next(prm->max_iters - it);
       p->hist_sweeps = chunk;
       launch_solve(p, *prm, chunk, 1);
       p->hist_sweeps = 0;
@@ -802,14 +837,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
       if (stop == chunk) break;   // the launch's own epilogue state is the answer
     }
     p->residual_pending = it > 0;   // res_partials still hold the sums of x0; x / wres are final
-    // the snapshots are scratch of THIS call: a problem object that once ran a tolerance-terminated solve on a large
-    // system must not keep up to 2 GiB of HBM (and the page-locked mirror) for the rest of its life.  Small ones stay
-    // (a converging Chain re-solves every step); the stream-ordered free waits for the kernels above.
-    static const size_t keep_mb = [] { const char *e = std::getenv("EGS_HIST_KEEP_MB"); return e ? (size_t)std::atol(e) : (size_t)256; }();
-    if (p->hist_x.bytes() + p->hist_acc.bytes() > (keep_mb << 20)) {
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      p->hist_x.release(); p->hist_acc.release(); p->hist_out.release();
-    }
+    release_large_history(p);
   } else {
     while (!flag && err > prm->tol && it < prm->max_iters) {
       const int chunk = std::min(every, prm->max_iters - it);
@@ -827,6 +855,162 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     fill_stats(p, stats);
   }
   if (flag) return fail(ctx, EGS_ERR_STALL, "device ordering wait timed out");
+  return EGS_OK;
+}
+
+// ---- batched worlds: the per-ensemble stopping rule ----------------------------
+// A world of E > 1 independent ensembles (egs_world_create_batch) solves them in one system, and each
+// ensemble must end with the lambda, sweep count and residual of a world holding only it.  Sweeps
+// never cross ensembles, so every ensemble is swept until the last one stops; the stopping test runs
+// per ensemble on the device (launch_seg_residual / launch_seg_select, kernels.h) and copies each
+// ensemble's chosen state into fin_x / fin_acc, which become x / acc at the end.
+struct BatchSolveState {
+  EnsembleSegs segs;               // device tables (owned by the world)
+  DevBuf<int32_t> ints;            // running [E], iterations [E], n_running
+  DevBuf<double> res;              // residual [E]
+  DevBuf<double> err;              // [sweeps][E] of the last evaluation
+  DevBuf<unsigned char> fin_x, fin_acc;
+  int32_t *h_ints = nullptr;       // page-locked: iterations [E], n_running, stall flag
+  double *h_res = nullptr;         // page-locked: residual [E]
+  int h_cap = -1;
+  int max_iterations = 0;          // of the last solve, for egs_solve_stats
+  double max_residual = 0.0;
+  ~BatchSolveState() {
+    if (h_ints) (void)hipHostFree(h_ints);
+    if (h_res) (void)hipHostFree(h_res);
+  }
+  EnsembleStop stop() {
+    const size_t E = (size_t)segs.n_ens;
+    return EnsembleStop{ints.p, ints.p + E, res.p, ints.p + 2 * E};
+  }
+  void ensure(int E) {
+    ints.alloc(2 * (size_t)E + 1);
+    res.alloc((size_t)E);
+    if (h_cap < E) {
+      if (h_ints) (void)hipHostFree(h_ints);
+      if (h_res) (void)hipHostFree(h_res);
+      h_ints = nullptr; h_res = nullptr; h_cap = -1;
+      HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_ints), ((size_t)E + 2) * sizeof(int32_t), hipHostMallocDefault));
+      HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_res), (size_t)(E > 0 ? E : 1) * sizeof(double), hipHostMallocDefault));
+      h_cap = E;
+    }
+  }
+};
+
+template <typename REAL>
+void batch_residual(egs_problem *p, BatchSolveState &B, double cfm, const int32_t *running, const void *xs, const void *as,
+                    const void *ws, int sweeps) {
+  SolveArgs<REAL> a{};
+  fill_history_args(p, a, (REAL)cfm);
+  launch_seg_residual<REAL>(a, B.segs, running, static_cast<const REAL *>(xs), static_cast<const REAL *>(as),
+                            static_cast<const REAL *>(ws), sweeps, B.err.p, p->ctx->stream);
+}
+
+// the stopping test over B.err for the states xs / as (strides in elements per entry)
+void batch_select(egs_problem *p, BatchSolveState &B, const egs_solve_params *prm, int sweeps, int first, int all_checked,
+                  int init, const void *xs, size_t xstride, const void *as, size_t astride) {
+  hipStream_t s = p->ctx->stream;
+  HIPCHK(hipMemsetAsync(B.stop().n_running, 0, sizeof(int32_t), s));
+  if (p->precision == EGS_F32)
+    launch_seg_select<float>(B.segs, B.stop(), B.err.p, sweeps, first, prm->max_iters, prm->check_every, prm->tol, all_checked,
+                             init, static_cast<const float *>(xs), xstride, static_cast<const float *>(as), astride,
+                             reinterpret_cast<float *>(B.fin_x.p), reinterpret_cast<float *>(B.fin_acc.p), s);
+  else
+    launch_seg_select<double>(B.segs, B.stop(), B.err.p, sweeps, first, prm->max_iters, prm->check_every, prm->tol, all_checked,
+                              init, static_cast<const double *>(xs), xstride, static_cast<const double *>(as), astride,
+                              reinterpret_cast<double *>(B.fin_x.p), reinterpret_cast<double *>(B.fin_acc.p), s);
+}
+
+// ONE read-back: the number of ensembles still running and the stall flag (cleared once seen).  Synchronises.
+int batch_read_running(egs_problem *p, BatchSolveState &B, int *flag) {
+  hipStream_t s = p->ctx->stream;
+  const int E = B.segs.n_ens;
+  HIPCHK(hipMemcpyAsync(B.h_ints + E, B.stop().n_running, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(B.h_ints + E + 1, p->error_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *flag = B.h_ints[E + 1];
+  if (*flag) HIPCHK(hipMemsetAsync(p->error_flag.p, 0, sizeof(int32_t), s));
+  return B.h_ints[E];
+}
+
+// The solve of a batched world: do_solve's loops, each ensemble stopping on its own (sparse_iterations.cc:204-221).
+// Enqueues the copy of the per-ensemble results into B.h_ints / B.h_res; the caller synchronises before reading them.
+egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolveState &B) {
+  egs_context *ctx = p->ctx;
+  hipStream_t s = ctx->stream;
+  if (egs_status st = validate_params(ctx, prm)) return st;
+  if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
+  const int E = B.segs.n_ens;
+  const size_t rs = p->real_size(), m = (size_t)p->m, n = (size_t)(p->n > 0 ? p->n : 1);
+  auto finish = [&]() {
+    HIPCHK(hipMemcpyAsync(B.h_ints, B.stop().iterations, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(B.h_res, B.stop().residual, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s));
+  };
+  B.err.alloc((size_t)E);
+  if (!(prm->tol > 0)) {   // fixed sweep count: do_solve as it is, then every ensemble's residual of the final state
+    if (egs_status st = do_solve(p, prm, nullptr)) return st;
+    if (p->precision == EGS_F32) batch_residual<float>(p, B, prm->cfm, nullptr, p->x.p, nullptr, p->wres.p, 1);
+    else batch_residual<double>(p, B, prm->cfm, nullptr, p->x.p, nullptr, p->wres.p, 1);
+    launch_seg_fixed(B.segs, B.stop(), B.err.p, prm->max_iters, s);
+    HIPCHK(hipGetLastError());
+    finish();
+    return EGS_OK;
+  }
+  ensure_minv_real(p);
+  if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
+  if (stall_seen(p)) return report_stall(p);
+  // the schedule of do_solve: same recorded-chunk decision, chunk sizes and deferred residual of x0
+  const bool defer_first = defer_first_residual(prm);
+  const bool history = use_history(p, prm);
+  ChunkSchedule sched(p, prm);
+  const int K = sched.K;
+  // before the first launch: a growing DevBuf frees the old one
+  B.err.alloc((size_t)std::max(K, 1) * E);
+  B.fin_x.alloc(3 * m * rs);
+  B.fin_acc.alloc(6 * n * rs);
+  auto residual = [&](const int32_t *running, const void *xs, const void *as, const void *ws, int sweeps) {
+    if (p->precision == EGS_F32) batch_residual<float>(p, B, prm->cfm, running, xs, as, ws, sweeps);
+    else batch_residual<double>(p, B, prm->cfm, running, xs, as, ws, sweeps);
+  };
+  // x0 = rhs: every ensemble's residual before iterating; those that already pass stop at 0 sweeps
+  launch_solve(p, *prm, 0, 0);
+  residual(nullptr, p->x.p, nullptr, p->wres.p, 1);
+  batch_select(p, B, prm, 1, 0, 1, 1, p->x.p, 0, p->acc.p, 0);
+  int it = 0, flag = 0;
+  // as do_solve: with recorded chunks the count of x0 rides on the first chunk's read-back
+  int running = (history && defer_first) ? E : batch_read_running(p, B, &flag);
+  const int32_t *d_running = B.stop().running;
+  if (history) {
+    prepare_history(p, K);
+    while (!flag && running > 0 && it < prm->max_iters) {
+      const int chunk = sched.next(prm->max_iters - it);
+      p->hist_sweeps = chunk;
+      launch_solve(p, *prm, chunk, 1);
+      p->hist_sweeps = 0;
+      residual(d_running, p->hist_x.p, p->hist_acc.p, nullptr, chunk);
+      batch_select(p, B, prm, chunk, it + 1, 0, 0, p->hist_x.p, 3 * m, p->hist_acc.p, 6 * n);
+      running = batch_read_running(p, B, &flag);
+      it += chunk;
+    }
+    release_large_history(p);
+  } else {
+    while (!flag && running > 0 && it < prm->max_iters) {
+      const int chunk = std::min(prm->check_every > 0 ? prm->check_every : 1, prm->max_iters - it);
+      launch_solve(p, *prm, chunk, 1);
+      it += chunk;
+      residual(d_running, p->x.p, nullptr, p->wres.p, 1);
+      batch_select(p, B, prm, 1, it, 1, 0, p->x.p, 0, p->acc.p, 0);
+      running = batch_read_running(p, B, &flag);
+    }
+  }
+  if (flag) return fail(ctx, EGS_ERR_STALL, "device ordering wait timed out");
+  // every ensemble has stopped: its state is in fin_x / fin_acc
+  if (m > 0) HIPCHK(hipMemcpyAsync(p->x.p, B.fin_x.p, 3 * m * rs, hipMemcpyDeviceToDevice, s));
+  if (p->n > 0) HIPCHK(hipMemcpyAsync(p->acc.p, B.fin_acc.p, 6 * (size_t)p->n * rs, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipGetLastError());
+  p->last_iterations = it;
+  p->residual_pending = false;
+  finish();
   return EGS_OK;
 }
 
@@ -1966,6 +2150,12 @@ struct egs_world {
   int m_contacts = 0;
   int replans = 0;
   bool have_bodies = false;
+  // batched world (egs_world_create_batch, n_ens > 1): bodies, joints and contacts are grouped by ensemble
+  int n_ens = 1;
+  std::vector<int32_t> body_off, joint_off;   // [n_ens + 1]
+  DevBuf<int32_t> d_ens, d_boff, d_joff;       // body -> ensemble [n], body and joint offsets [n_ens + 1]
+  DevBuf<int32_t> d_coff;                      // contact offsets [n_ens + 1], written by the collider
+  BatchSolveState batch;
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
   double t_phase[5] = {0, 0, 0, 0, 0};   // collide, topology D2H + compare, re-plan, solve + integrate (enqueue), steps
@@ -2051,9 +2241,69 @@ egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R
   });
 }
 
+egs_status egs_world_create_batch(egs_context *ctx, int32_t n_ensembles, const int32_t *n_bodies, int32_t precision,
+                                  egs_world **out, int32_t *body_offset) {
+  if (!ctx || !out) return EGS_ERR_INVALID;
+  *out = nullptr;
+  if (n_ensembles < 1 || !n_bodies) return fail(ctx, EGS_ERR_INVALID, "bad ensemble count / NULL size table");
+  std::vector<int32_t> off((size_t)n_ensembles + 1, 0);
+  long nb = 0;
+  for (int e = 0; e < n_ensembles; ++e) {
+    if (n_bodies[e] < 0) return fail(ctx, EGS_ERR_INVALID, "negative ensemble size");
+    nb += n_bodies[e];
+    if (nb > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "batch too large for 32-bit indices");
+    off[(size_t)e + 1] = (int32_t)nb;
+  }
+  if (body_offset) std::copy(off.begin(), off.end(), body_offset);
+  egs_status st = egs_world_create(ctx, (int32_t)nb, precision, out);
+  if (st != EGS_OK || n_ensembles == 1) return st;   // one ensemble: the plain world, nothing else
+  egs_world *w = *out;
+  st = guarded(ctx, [&]() -> egs_status {
+    const size_t E = (size_t)n_ensembles;
+    w->n_ens = n_ensembles;
+    w->body_off = off;
+    w->joint_off.assign(E + 1, 0);
+    std::vector<int32_t> ens((size_t)(nb > 0 ? nb : 1), 0);
+    for (size_t e = 0; e < E; ++e)
+      for (int32_t b = off[e]; b < off[e + 1]; ++b) ens[(size_t)b] = (int32_t)e;
+    w->d_ens.alloc(ens.size()); upload(w->d_ens, ens.data(), ens.size(), ctx->stream);
+    w->d_boff.alloc(E + 1); upload(w->d_boff, off.data(), E + 1, ctx->stream);
+    w->d_joff.alloc(E + 1); upload(w->d_joff, w->joint_off.data(), E + 1, ctx->stream);
+    w->d_coff.alloc(E + 1); upload(w->d_coff, w->joint_off.data(), E + 1, ctx->stream);   // no contacts yet
+    w->batch.segs = EnsembleSegs{n_ensembles, 0, w->d_joff.p, w->d_coff.p, w->d_boff.p};
+    w->batch.ensure(n_ensembles);
+    std::fill(w->batch.h_ints, w->batch.h_ints + E + 2, 0);
+    std::fill(w->batch.h_res, w->batch.h_res + E, 0.0);
+    w->col.set_ensembles(n_ensembles, w->d_ens.p, w->d_boff.p, w->d_coff.p);
+    return EGS_OK;
+  });
+  if (st != EGS_OK) { egs_world_destroy(w); *out = nullptr; }
+  return st;
+}
+
 egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
                                 const double *data) {
   if (!w || m_joints < 0 || (m_joints > 0 && (!body0 || !body1 || !data))) return EGS_ERR_INVALID;
+  std::vector<int32_t> joint_off;
+  if (w->n_ens > 1) {   // every joint inside one ensemble, the joints grouped by ensemble (order within kept)
+    joint_off.assign((size_t)w->n_ens + 1, 0);
+    auto ens_of = [&](int32_t b) {
+      return (int)(std::upper_bound(w->body_off.begin(), w->body_off.end(), b) - w->body_off.begin()) - 1;
+    };
+    int last = 0;
+    for (int i = 0; i < m_joints; ++i) {
+      const int32_t a = body0[i], b = body1[i];
+      if (a < -1 || a >= w->n || b < -1 || b >= w->n || (a < 0 && b < 0))
+        return fail(w->ctx, EGS_ERR_INVALID, "joint body index out of range");
+      const int ea = a >= 0 ? ens_of(a) : -1, eb = b >= 0 ? ens_of(b) : -1;
+      if (ea >= 0 && eb >= 0 && ea != eb) return fail(w->ctx, EGS_ERR_INVALID, "joint between two ensembles");
+      const int e = ea >= 0 ? ea : eb;
+      if (e < last) return fail(w->ctx, EGS_ERR_INVALID, "joints not grouped by ensemble");
+      last = e;
+      ++joint_off[(size_t)e + 1];
+    }
+    for (int e = 0; e < w->n_ens; ++e) joint_off[(size_t)e + 1] += joint_off[(size_t)e];
+  }
   w->jb0.assign(body0, body0 + m_joints);
   w->jb1.assign(body1, body1 + m_joints);
   w->jdata.assign(data, data + (size_t)m_joints * 7);
@@ -2066,6 +2316,13 @@ egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *b
     }
     world_make_problem(w, w->jb0.data(), w->jb1.data(), m_joints);   // contacts are re-detected by the next step
     w->m_contacts = 0;
+    if (w->n_ens > 1) {
+      const size_t E1 = (size_t)w->n_ens + 1;
+      w->joint_off = joint_off;
+      upload(w->d_joff, joint_off.data(), E1, w->ctx->stream);
+      HIPCHK(hipMemsetAsync(w->d_coff.p, 0, E1 * sizeof(int32_t), w->ctx->stream));
+      w->batch.segs.mj = m_joints;
+    }
     return EGS_OK;
   });
 }
@@ -2114,18 +2371,32 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
       w->m_contacts = mc;
     }
     egs_problem *p = w->prob;
+    const bool batched = w->n_ens > 1;
     if (p->m > 0) {
       do_assemble(p, dt, erp);
-      egs_status st = do_solve(p, params, stats);
+      egs_status st = batched ? do_solve_batch(p, params, w->batch) : do_solve(p, params, stats);
       if (st != EGS_OK) return st;
       // the body state must not be advanced with a lambda that came out of a timed-out ordering
       // wait: look at the flag before integrating (one 4-byte read-back per step)
       HIPCHK(hipStreamSynchronize(s));
       if (stall_seen(p)) return report_stall(p);
+      if (batched && stats) {   // the slowest ensemble's sweep count and the largest residual
+        std::memset(stats, 0, sizeof *stats);
+        fill_stats(p, stats);
+        for (int e = 0; e < w->n_ens; ++e) {
+          stats->iterations = std::max(stats->iterations, w->batch.h_ints[e]);
+          const double r = w->batch.h_res[e];
+          if (!std::isnan(stats->residual) && (std::isnan(r) || r > stats->residual)) stats->residual = r;   // NaN wins
+        }
+      }
     } else {  // no constraints: v_dot = M^-1 f (ensembles.cc:504-505)
       if (egs_status st = validate_params(w->ctx, params)) return st;
       HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * p->real_size(), s));
       if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
+      if (batched) {
+        std::fill(w->batch.h_ints, w->batch.h_ints + w->n_ens, 0);
+        std::fill(w->batch.h_res, w->batch.h_res + w->n_ens, 0.0);
+      }
     }
     do_velocity(p, dt);
     launch_advance(p->n, p->pos.p, p->R.p, p->v.p, p->w.p, p->v6.p, dt, s);
@@ -2162,6 +2433,36 @@ egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_ou
   if (3 * w->prob->m > max_rows) return fail(w->ctx, EGS_ERR_INVALID, "max_rows too small");
   if (w->prob->m == 0) return EGS_OK;
   return egs_problem_get_lambda(w->prob, lambda);
+}
+
+egs_status egs_world_batch_info(egs_world *w, int32_t n_ensembles, int32_t *joint_offset, int32_t *contact_offset,
+                                int32_t *iterations, double *residual) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  const size_t E = (size_t)w->n_ens;
+  if (w->n_ens > 1) {
+    if (joint_offset) std::copy(w->joint_off.begin(), w->joint_off.end(), joint_offset);
+    return guarded(w->ctx, [&]() -> egs_status {
+      if (contact_offset) {
+        HIPCHK(hipMemcpyAsync(contact_offset, w->d_coff.p, (E + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, w->ctx->stream));
+        HIPCHK(hipStreamSynchronize(w->ctx->stream));
+      }
+      if (iterations) std::copy(w->batch.h_ints, w->batch.h_ints + E, iterations);
+      if (residual) std::copy(w->batch.h_res, w->batch.h_res + E, residual);
+      return EGS_OK;
+    });
+  }
+  // one ensemble: the plain world's own figures
+  if (joint_offset) { joint_offset[0] = 0; joint_offset[1] = (int32_t)w->jb0.size(); }
+  if (contact_offset) { contact_offset[0] = 0; contact_offset[1] = w->m_contacts; }
+  if (!iterations && !residual) return EGS_OK;
+  egs_solve_stats st{};
+  if (w->prob) {
+    if (egs_status r = egs_problem_get_stats(w->prob, &st)) return r;
+  }
+  if (iterations) iterations[0] = st.iterations;
+  if (residual) residual[0] = st.residual;
+  return EGS_OK;
 }
 
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans) {

@@ -32,6 +32,11 @@ class Collider {
   const int32_t *body0() const;
   const int32_t *body1() const;
   const double *data() const;
+  // Batched world (egs_world_create_batch): n_ens > 0 ensembles, ens [n] = each body's ensemble and
+  // eoff [n_ens + 1] = body offsets, device arrays the caller keeps alive.  Pairs across ensembles are
+  // never candidates; the list is, ensemble by ensemble, its ground contacts then its pairs i < j, and
+  // run() writes each ensemble's first contact to contact_off [n_ens + 1] (device).  n_ens = 0: off.
+  void set_ensembles(int n_ens, const int32_t *ens, const int32_t *eoff, int32_t *contact_off);
   int n_ground() const { return n_ground_; }
   int n_pairs() const { return n_pairs_; }
 
@@ -39,6 +44,9 @@ class Collider {
   struct Impl;
   Impl *impl_;
   int n_ground_ = 0, n_pairs_ = 0;
+  int n_ens_ = 0;
+  const int32_t *ens_ = nullptr, *eoff_ = nullptr;
+  int32_t *contact_off_ = nullptr;
 };
 
 }  // namespace egs

@@ -318,27 +318,33 @@ __device__ int collide_boxes(const double *c1, const double *R1, const double *s
 }
 
 // ---- kernels ---------------------------------------------------------------
+// Batched worlds (ens != NULL): body b's ground contacts follow the pair contacts of the ensembles before
+// its own, ebase[2e] of them (ens_base_kernel).
 __global__ void __launch_bounds__(256) ground_kernel(int n, const double *pos, const double *R, const double *side,
-                                                     const int *off, int *count, int *b0, int *b1, double *data) {
+                                                     const int *off, int *count, int *b0, int *b1, double *data,
+                                                     const int *ens = nullptr, const int *ebase = nullptr) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n) return;
   double buf[8 * 7];
   const int c = ground_contacts(pos + 3 * (size_t)b, R + 9 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
   if (!off) { count[b] = c; return; }
+  const size_t shift = ens ? (size_t)ebase[2 * ens[b]] : 0;
   for (int k = 0; k < c; ++k) {
-    const size_t o = (size_t)off[b] + k;
+    const size_t o = (size_t)off[b] + shift + k;
     b0[o] = -1; b1[o] = b;  // contact.h:13-15: ground contacts are (null, body)
     for (int q = 0; q < 7; ++q) data[o * 7 + q] = buf[7 * k + q];
   }
 }
 
 // One wavefront per body i: candidates j > i whose bounding spheres overlap, in
-// ascending j (ballot keeps the order).
+// ascending j (ballot keeps the order).  In a batched world (ens != NULL) j stops at the end
+// of body i's ensemble: no cross-ensemble pair, O(sum n_e^2) instead of O(n^2).
 __global__ void __launch_bounds__(64) cand_kernel(int n, const double *pos, const double *side, int *cand, int *count,
-                                                  int *overflow) {
+                                                  int *overflow, const int *ens = nullptr, const int *eoff = nullptr) {
   const int i = blockIdx.x, lane = threadIdx.x;
   const double ci[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
   const double ri = 0.5 * sqrt(dot3(side + 3 * (size_t)i, side + 3 * (size_t)i));
+  if (ens) n = eoff[ens[i] + 1];
   int found = 0;
   for (int base = i + 1; base < n; base += 64) {
     const int j = base + lane;
@@ -367,10 +373,12 @@ __global__ void __launch_bounds__(64) cand_kernel(int n, const double *pos, cons
 // body i at off[i] in ascending j -- the order of the capped kernels, so the contact list is unchanged.
 template <bool FILL>
 __global__ void __launch_bounds__(64) cand_all_kernel(int n, const double *pos, const double *side, const int *off,
-                                                      int *count, int *pi, int *pj) {
+                                                      int *count, int *pi, int *pj, const int *ens = nullptr,
+                                                      const int *eoff = nullptr) {
   const int i = blockIdx.x, lane = threadIdx.x;
   const double ci[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
   const double ri = 0.5 * sqrt(dot3(side + 3 * (size_t)i, side + 3 * (size_t)i));
+  if (ens) n = eoff[ens[i] + 1];
   int found = 0;
   for (int base = i + 1; base < n; base += 64) {
     const int j = base + lane;
@@ -400,8 +408,10 @@ __global__ void __launch_bounds__(64) cand_all_kernel(int n, const double *pos, 
 // the all-pairs kernel's.
 constexpr int kCellClamp = 1 << 20;
 
-__device__ __forceinline__ unsigned cell_hash(int x, int y, int z) {
-  return (unsigned)x * 73856093u ^ (unsigned)y * 19349663u ^ (unsigned)z * 83492791u;
+// e: the body's ensemble in a batched world (0 otherwise, which leaves the hash as it was): co-located
+// ensembles never share a cell, so the KMAX limit and the spill path count same-ensemble candidates only
+__device__ __forceinline__ unsigned cell_hash(int x, int y, int z, int e = 0) {
+  return (unsigned)x * 73856093u ^ (unsigned)y * 19349663u ^ (unsigned)z * 83492791u ^ (unsigned)e * 2654435761u;
 }
 
 __global__ void __launch_bounds__(1024) cell_size_kernel(int n, const double *side, double *cell) {
@@ -415,7 +425,8 @@ __global__ void __launch_bounds__(1024) cell_size_kernel(int n, const double *si
 }
 
 __global__ void __launch_bounds__(256) cell_bin_kernel(int n, const double *pos, const double *cell, int table_mask,
-                                                       int *coords, int *bucket_of, int *arrival, int *tcount) {
+                                                       int *coords, int *bucket_of, int *arrival, int *tcount,
+                                                       const int *ens = nullptr) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n) return;
   const double c = cell[0];
@@ -426,7 +437,7 @@ __global__ void __launch_bounds__(256) cell_bin_kernel(int n, const double *pos,
     q[k] = (int)f;
     coords[3 * (size_t)b + k] = q[k];
   }
-  const int bkt = (int)(cell_hash(q[0], q[1], q[2]) & (unsigned)table_mask);
+  const int bkt = (int)(cell_hash(q[0], q[1], q[2], ens ? ens[b] : 0) & (unsigned)table_mask);
   bucket_of[b] = bkt;
   arrival[b] = atomicAdd(&tcount[bkt], 1);   // order inside a bucket is irrelevant: candidates are sorted later
 }
@@ -439,16 +450,18 @@ __global__ void __launch_bounds__(256) cell_fill_kernel(int n, const int *bucket
 
 __global__ void __launch_bounds__(64) cand_grid_kernel(int n, const double *pos, const double *side, const int *coords,
                                                        int table_mask, const int *toff, const int *tcount,
-                                                       const int *sorted, int *cand, int *count, int *overflow) {
+                                                       const int *sorted, int *cand, int *count, int *overflow,
+                                                       const int *ens = nullptr) {
   __shared__ int list[KMAX];
   const int i = blockIdx.x, lane = threadIdx.x;
+  const int ei = ens ? ens[i] : 0;
   const double ci[3] = {pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]};
   const double ri = 0.5 * sqrt(dot3(side + 3 * (size_t)i, side + 3 * (size_t)i));
   const int cx = coords[3 * (size_t)i], cy = coords[3 * (size_t)i + 1], cz = coords[3 * (size_t)i + 2];
   int found = 0;
   for (int nb = 0; nb < 27; ++nb) {
     const int x = cx + nb % 3 - 1, y = cy + (nb / 3) % 3 - 1, z = cz + nb / 9 - 1;
-    const int bkt = (int)(cell_hash(x, y, z) & (unsigned)table_mask);
+    const int bkt = (int)(cell_hash(x, y, z, ei) & (unsigned)table_mask);
     const int beg = toff[bkt], cnt = tcount[bkt];
     for (int base = 0; base < cnt; base += 64) {
       const int k = base + lane;
@@ -457,7 +470,8 @@ __global__ void __launch_bounds__(64) cand_grid_kernel(int n, const double *pos,
       if (k < cnt) {
         j = sorted[beg + k];
         // exact cell match: a bucket shared by two cells (hash collision) is never counted twice
-        if (j > i && coords[3 * (size_t)j] == x && coords[3 * (size_t)j + 1] == y && coords[3 * (size_t)j + 2] == z) {
+        if (j > i && coords[3 * (size_t)j] == x && coords[3 * (size_t)j + 1] == y && coords[3 * (size_t)j + 2] == z &&
+            (!ens || ens[j] == ei)) {
           const double d[3] = {pos[3 * (size_t)j] - ci[0], pos[3 * (size_t)j + 1] - ci[1], pos[3 * (size_t)j + 2] - ci[2]};
           const double rj = 0.5 * sqrt(dot3(side + 3 * (size_t)j, side + 3 * (size_t)j));
           const double rr = (ri + rj) * 1.0000001 + 1e-12;
@@ -501,7 +515,8 @@ struct JointList { int mj; const int *b0, *b1; const double *data; };
 template <bool EMIT>
 __global__ void __launch_bounds__(64) narrow_kernel(int npairs, const int *pi, const int *pj, const double *pos,
                                                     const double *R, const double *side, const int *off, int base,
-                                                    int *count, int *b0, int *b1, double *data, JointList jl) {
+                                                    int *count, int *b0, int *b1, double *data, JointList jl,
+                                                    const int *ens = nullptr, const int *ebase = nullptr) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= npairs) return;
   const int i = pi[t], j = pj[t];
@@ -529,14 +544,35 @@ __global__ void __launch_bounds__(64) narrow_kernel(int npairs, const int *pi, c
       if (sqrt(dot3(d, d)) < 1e-6) del = true;
     }
     if (del) continue;
-    if (EMIT) {
-      const size_t o = (size_t)base + off[t] + kept;
+    if (EMIT) {   // batched: after the ground contacts of ensembles 0..e, ebase[2e + 1] of them
+      const size_t o = (size_t)(ens ? ebase[2 * ens[i] + 1] : base) + off[t] + kept;
       b0[o] = i; b1[o] = j;
       for (int q = 0; q < 7; ++q) data[o * 7 + q] = cs[7 * a + q];
     }
     ++kept;
   }
   if (!EMIT) count[t] = kept;
+}
+
+// Batched world: where each ensemble's contacts go.  The list is, ensemble by ensemble, its ground
+// contacts then its pairs; goff / coff / poff are the exclusive scans over ALL bodies / pairs and
+// totals = {-, G, C, P}.  ebase[2e] = pair contacts of the ensembles before e, ebase[2e + 1] = ground
+// contacts of ensembles 0..e; contact_off[e] (e <= E) = first contact of ensemble e.
+__global__ void __launch_bounds__(256) ens_base_kernel(int E, int n, const int *eoff, const int *goff, const int *coff,
+                                                       const int *poff, const int *totals, int *ebase, int *contact_off) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e > E) return;
+  const int G = totals[1], C = totals[2], P = totals[3];
+  const int b = eoff[e];
+  const int g_before = b < n ? goff[b] : G;
+  const int c_first = b < n ? coff[b] : C;
+  const int p_before = c_first < C ? poff[c_first] : P;
+  contact_off[e] = g_before + p_before;
+  if (e < E) {
+    const int b1 = eoff[e + 1];
+    ebase[2 * e] = p_before;
+    ebase[2 * e + 1] = b1 < n ? goff[b1] : G;
+  }
 }
 
 // Copies the contact topology into device-visible (page-locked host) memory: a
@@ -648,6 +684,7 @@ struct Collider::Impl {
   };
   G<int> gcount, goff, ccount, coff, cand, flags, blocks, pi, pj, pcount, poff, blocks2, b0, b1;
   G<int> coords, bucket_of, arrival, tcount, toff, sorted, blocks3, scratch;   // uniform grid
+  G<int> ebase;                                                                 // batched worlds
   G<double> data, cell;
 };
 
@@ -656,13 +693,20 @@ Collider::~Collider() { delete impl_; }
 const int32_t *Collider::body0() const { return impl_->b0.p; }
 const int32_t *Collider::body1() const { return impl_->b1.p; }
 const double *Collider::data() const { return impl_->data.p; }
+void Collider::set_ensembles(int n_ens, const int32_t *ens, const int32_t *eoff, int32_t *contact_off) {
+  n_ens_ = n_ens; ens_ = ens; eoff_ = eoff; contact_off_ = contact_off;
+}
 
 int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, const double *dside, int mj,
                   const int32_t *djb0, const int32_t *djb1, const double *djdata) {
   const JointList jl{mj, djb0, djb1, djdata};
   Impl &I = *impl_;
   n_ground_ = 0; n_pairs_ = 0;
-  if (n <= 0) return 0;
+  const int *ens = n_ens_ > 0 ? ens_ : nullptr, *eoff = n_ens_ > 0 ? eoff_ : nullptr;
+  if (n <= 0) {
+    if (ens) HIPCHK(hipMemsetAsync(contact_off_, 0, (size_t)(n_ens_ + 1) * sizeof(int32_t), s));
+    return 0;
+  }
   const size_t nn = (size_t)n;
   I.gcount.need(nn); I.goff.need(nn); I.ccount.need(nn); I.coff.need(nn); I.cand.need(nn * KMAX); I.flags.need(4);
   I.blocks.need((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8); I.blocks2.need((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
@@ -681,13 +725,13 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
     HIPCHK(hipMemsetAsync(I.tcount.p, 0, (size_t)table * sizeof(int), s));
     hipLaunchKernelGGL(cell_size_kernel, dim3(1), dim3(1024), 0, s, n, dside, I.cell.p);
     hipLaunchKernelGGL(cell_bin_kernel, dim3(gb), dim3(256), 0, s, n, dpos, I.cell.p, table - 1, I.coords.p, I.bucket_of.p,
-                       I.arrival.p, I.tcount.p);
+                       I.arrival.p, I.tcount.p, ens);
     exclusive_scan_async(s, table, I.tcount.p, I.toff.p, I.blocks3.p, I.scratch.p);
     hipLaunchKernelGGL(cell_fill_kernel, dim3(gb), dim3(256), 0, s, n, I.bucket_of.p, I.arrival.p, I.toff.p, I.sorted.p);
     hipLaunchKernelGGL(cand_grid_kernel, dim3(n), dim3(64), 0, s, n, dpos, dside, I.coords.p, table - 1, I.toff.p,
-                       I.tcount.p, I.sorted.p, I.cand.p, I.ccount.p, I.flags.p);
+                       I.tcount.p, I.sorted.p, I.cand.p, I.ccount.p, I.flags.p, ens);
   } else {
-    hipLaunchKernelGGL(cand_kernel, dim3(n), dim3(64), 0, s, n, dpos, dside, I.cand.p, I.ccount.p, I.flags.p);
+    hipLaunchKernelGGL(cand_kernel, dim3(n), dim3(64), 0, s, n, dpos, dside, I.cand.p, I.ccount.p, I.flags.p, ens, eoff);
   }
   exclusive_scan_async(s, n, I.ccount.p, I.coff.p, I.blocks2.p, I.flags.p + 2);
   int totals[4] = {0, 0, 0, 0};   // ONE read-back for overflow, G and C
@@ -696,14 +740,15 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   const bool spill = totals[0] != 0;   // some body has more than KMAX partners: uncapped count -> scan -> fill
   if (spill) {
     hipLaunchKernelGGL((cand_all_kernel<false>), dim3(n), dim3(64), 0, s, n, dpos, dside, (const int *)nullptr, I.ccount.p,
-                       (int *)nullptr, (int *)nullptr);
+                       (int *)nullptr, (int *)nullptr, ens, eoff);
     totals[2] = exclusive_scan(s, n, I.ccount.p, I.coff.p, I.blocks2.p, I.flags.p + 2);
   }
   const int G = totals[1], C = totals[2];
   int P = 0;
   if (C > 0) {
     I.pi.need(C); I.pj.need(C); I.pcount.need(C); I.poff.need(C); I.blocks2.need(((size_t)C + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
-    if (spill) hipLaunchKernelGGL((cand_all_kernel<true>), dim3(n), dim3(64), 0, s, n, dpos, dside, I.coff.p, (int *)nullptr, I.pi.p, I.pj.p);
+    if (spill) hipLaunchKernelGGL((cand_all_kernel<true>), dim3(n), dim3(64), 0, s, n, dpos, dside, I.coff.p, (int *)nullptr, I.pi.p, I.pj.p,
+                                  ens, eoff);
     else
     hipLaunchKernelGGL(flatten_kernel, dim3(gb), dim3(256), 0, s, n, I.cand.p, I.ccount.p, I.coff.p, I.pi.p, I.pj.p);
     hipLaunchKernelGGL((narrow_kernel<false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
@@ -712,13 +757,18 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   }
   const int m = G + P;
   n_ground_ = G; n_pairs_ = C;
+  if (ens) {   // per-ensemble order: ground contacts then pairs, ensemble by ensemble
+    I.ebase.need((size_t)n_ens_ * 2);
+    hipLaunchKernelGGL(ens_base_kernel, dim3(n_ens_ / 256 + 1), dim3(256), 0, s, n_ens_, n, eoff, I.goff.p, I.coff.p, I.poff.p,
+                       I.flags.p, I.ebase.p, contact_off_);
+  }
   if (m == 0) return 0;
   I.b0.need(m); I.b1.need(m); I.data.need((size_t)m * 7);
   hipLaunchKernelGGL(ground_kernel, dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
-                     I.b1.p, I.data.p);
+                     I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr);
   if (C > 0)
     hipLaunchKernelGGL((narrow_kernel<true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
-                       I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl);
+                       I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr);
   HIPCHK(hipGetLastError());
   return m;
 }

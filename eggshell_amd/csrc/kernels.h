@@ -143,6 +143,41 @@ void launch_velocity(int n, const double *v, const double *w, const double *Wf, 
 // chunk: out [sweeps][blocks][4].  write_sweep >= 1 also stores that sweep's w into wres.
 template <typename REAL>
 void launch_hist_residual(const SolveArgs<REAL> &a, int sweeps, int blocks, double *out, int write_sweep, hipStream_t s);
+// ---- batched worlds (egs_world_create_batch): the per-ensemble stopping rule ----
+// Ensemble e owns the constraints [jo[e], jo[e+1]) (its joints) and [mj + co[e], mj + co[e+1]) (its
+// contacts), i.e. its own 3 m_e rows in two ranges, and the bodies [bo[e], bo[e+1]).  Device arrays.
+struct EnsembleSegs {
+  int32_t n_ens = 0, mj = 0;
+  const int32_t *jo = nullptr, *co = nullptr, *bo = nullptr;
+};
+// Per-ensemble state of a tolerance-terminated solve, device arrays [n_ens]: still running, sweeps taken,
+// residual (the last one checked while running); n_running counts the ensembles left after a selection.
+struct EnsembleStop {
+  int32_t *running = nullptr, *iterations = nullptr;
+  double *residual = nullptr;
+  int32_t *n_running = nullptr;
+};
+// err [sweeps][n_ens]: the residual of sparse_iterations.cc:51-69 of every ensemble after every recorded
+// sweep, bit for bit what a world holding only that ensemble computes -- its own 3 m_e rows blocked as
+// residual_partials_kernel blocks them (kResidualBlocks x 256 threads), the partial sums combined in
+// read_residual's order, the square roots on the device.  w from the snapshots (xs / as, strides
+// 3m and 6n per sweep, the w of hist_residual_kernel) or, if ws != NULL, read from it (sweeps = 1).
+// Ensembles with running[e] == 0 are skipped (running == NULL: none).
+template <typename REAL>
+void launch_seg_residual(const SolveArgs<REAL> &a, const EnsembleSegs &S, const int32_t *running, const REAL *xs,
+                         const REAL *as, const REAL *ws, int sweeps, double *err, hipStream_t s);
+// The reference's stopping test per running ensemble over err [sweeps][n_ens], entry k being the state after
+// `first + k` sweeps: the first checked entry (all_checked, or a multiple of `every`, or max_iters) with
+// !(err > tol) stops it; an ensemble still running at max_iters takes the last entry.  A stopping ensemble
+// gets its sweep count and residual and its lambda rows / body accumulators copied from entry k of xs / as
+// into fin_x / fin_acc.  init = 1: every ensemble counts as running (the test of x0).
+template <typename REAL>
+void launch_seg_select(const EnsembleSegs &S, const EnsembleStop &T, const double *err, int sweeps, int first,
+                       int max_iters, int every, double tol, int all_checked, int init, const REAL *xs, size_t xstride,
+                       const REAL *as, size_t astride, REAL *fin_x, REAL *fin_acc, hipStream_t s);
+// fixed sweep count: iterations[e] = sweeps (0 for an ensemble without constraints), residual[e] = err[e]
+void launch_seg_fixed(const EnsembleSegs &S, const EnsembleStop &T, const double *err, int sweeps, hipStream_t s);
+
 template <typename REAL>
 void launch_convert_minv(int count, const double *src, REAL *dst, hipStream_t s);
 // *flag (preset to 1) is cleared unless every 6x6 block is exactly diag(a, a, a, b, b, b)

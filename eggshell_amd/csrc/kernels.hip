@@ -323,6 +323,114 @@ __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL
 }
 
 // --------------------------------------------------------------------------
+// Batched worlds: the residual of each ensemble on its own (kernels.h, launch_seg_residual).  One
+// workgroup per (ensemble, sweep) replays the stand-alone reduction: local row lr of the ensemble is
+// added by thread lr % 256 of block (lr / 256) % kResidualBlocks in ascending lr, each block reduces as
+// residual_partials_kernel does, and the block sums are added in block order as read_residual adds them.
+// Blocks beyond the ensemble's rows would contribute +0.0 to sums that are >= 0 (or NaN): skipped.
+template <typename REAL>
+__global__ void __launch_bounds__(256) seg_residual_kernel(const SolveArgs<REAL> A, const EnsembleSegs S, const int32_t *running,
+                                                           const REAL *xs, const REAL *as, const REAL *ws, double *err) {
+  __shared__ double red[4][256];
+  const int e = blockIdx.x, sweep = blockIdx.y, t = threadIdx.x;
+  if (running && !running[e]) return;
+  const int j0 = S.jo[e], mje = S.jo[e + 1] - j0;
+  const int c0 = S.mj + S.co[e], mce = S.co[e + 1] - S.co[e];
+  const int rows = 3 * (mje + mce), jrows = 3 * mje;
+  const REAL *hx = xs + (size_t)sweep * A.m * 3;
+  const REAL *ha = ws ? nullptr : as + (size_t)sweep * A.n_bodies * 6;
+  const int nblk = min(kResidualBlocks, (rows + 255) / 256);
+  double sum[4] = {0, 0, 0, 0};
+  for (int blk = 0; blk < nblk; ++blk) {
+    double acc[4] = {0, 0, 0, 0};
+    for (int lr = blk * 256 + t; lr < rows; lr += kResidualBlocks * 256) {
+      const int r = lr < jrows ? 3 * j0 + lr : 3 * c0 + (lr - jrows);
+      const REAL xv = hx[r], l = A.lo[r], h = A.hi[r];
+      double w;
+      if (ws) {
+        w = (double)ws[r];
+      } else {   // hist_residual_kernel's expression
+        const int i = r / 3, rr = r - 3 * i;
+        const int b0 = A.body0[i], b1 = A.body1[i];
+        REAL j0v[6], j1v[6], a0[6], a1[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          j0v[k] = b0 >= 0 ? A.J0[(size_t)i * 18 + 6 * rr + k] : REAL(0);
+          j1v[k] = b1 >= 0 ? A.J1[(size_t)i * 18 + 6 * rr + k] : REAL(0);
+          a0[k] = b0 >= 0 ? ha[(size_t)b0 * 6 + k] : REAL(0);
+          a1[k] = b1 >= 0 ? ha[(size_t)b1 * 6 + k] : REAL(0);
+        }
+        w = (double)(tfma(A.cfm, xv, row_dot(j0v, a0, j1v, a1)) - A.rhs[r]);
+      }
+      if (A.is_eq[r]) acc[0] += w * w;
+      else {
+        if (xv == l && w < 0) acc[1] += w * w;
+        if (xv == h && w > 0) acc[2] += w * w;
+        if (xv > l && xv < h) acc[3] += w * w;
+      }
+    }
+    __syncthreads();   // thread 0 has read the previous block's sums
+    red[0][t] = acc[0]; red[1][t] = acc[1]; red[2][t] = acc[2]; red[3][t] = acc[3];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (t < s)
+        for (int k = 0; k < 4; ++k) red[k][t] += red[k][t + s];
+      __syncthreads();
+    }
+    if (t == 0)
+      for (int k = 0; k < 4; ++k) sum[k] += red[k][0];
+  }
+  if (t == 0) err[(size_t)sweep * S.n_ens + e] = sqrt(sum[0]) + (sqrt(sum[1]) + sqrt(sum[2]) + sqrt(sum[3]));
+}
+
+// One workgroup per ensemble: the stopping test (thread 0), then the chosen state's rows (all threads).
+// Only thread 0 reads or writes the ensemble's state; the other threads learn the outcome from s_pick
+// after the barrier (-1: still running or already stopped, nothing to copy).
+template <typename REAL>
+__global__ void __launch_bounds__(256) seg_select_kernel(const EnsembleSegs S, const EnsembleStop T, const double *err, int sweeps,
+                                                         int first, int max_iters, int every, double tol, int all_checked,
+                                                         int init, const REAL *xs, size_t xstride, const REAL *as,
+                                                         size_t astride, REAL *fin_x, REAL *fin_acc) {
+  __shared__ int s_pick;
+  const int e = blockIdx.x, t = threadIdx.x;
+  if (t == 0) s_pick = -1;
+  if (t == 0 && (init || T.running[e])) {
+    int pick = -1;
+    double res = init ? 0.0 : T.residual[e];
+    for (int k = 0; k < sweeps; ++k) {
+      const int sw = first + k;
+      if (!(all_checked || sw % every == 0 || sw == max_iters)) continue;
+      res = err[(size_t)k * S.n_ens + e];
+      if (!(res > tol)) { pick = k; break; }   // as the reference's loop condition: NaN stops too
+    }
+    if (pick < 0 && first + sweeps - 1 >= max_iters) pick = sweeps - 1;
+    T.residual[e] = res;
+    if (pick >= 0) { T.iterations[e] = first + pick; T.running[e] = 0; }
+    else { T.running[e] = 1; atomicAdd(T.n_running, 1); }
+    s_pick = pick;
+  }
+  __syncthreads();
+  const int pick = s_pick;
+  if (pick < 0) return;
+  const REAL *x = xs + (size_t)pick * xstride, *a = as + (size_t)pick * astride;
+  const size_t jb = (size_t)3 * S.jo[e], jn = (size_t)3 * (S.jo[e + 1] - S.jo[e]);
+  const size_t cb = (size_t)3 * (S.mj + S.co[e]), cn = (size_t)3 * (S.co[e + 1] - S.co[e]);
+  const size_t bb = (size_t)6 * S.bo[e], bn = (size_t)6 * (S.bo[e + 1] - S.bo[e]);
+  for (size_t r = t; r < jn; r += 256) fin_x[jb + r] = x[jb + r];
+  for (size_t r = t; r < cn; r += 256) fin_x[cb + r] = x[cb + r];
+  for (size_t q = t; q < bn; q += 256) fin_acc[bb + q] = a[bb + q];
+}
+
+__global__ void __launch_bounds__(256) seg_fixed_kernel(const EnsembleSegs S, const EnsembleStop T, const double *err, int sweeps) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= S.n_ens) return;
+  const bool any = S.jo[e + 1] > S.jo[e] || S.co[e + 1] > S.co[e];
+  T.iterations[e] = any ? sweeps : 0;   // a world without constraints does not solve (sparse_iterations.cc:152-154)
+  T.residual[e] = err[e];
+  T.running[e] = 0;
+}
+
+// --------------------------------------------------------------------------
 // K9: v_new = v + dt (W f_ext + a)        (ensembles.cc:535, 572)
 template <typename REAL>
 __global__ void __launch_bounds__(256) velocity_kernel(int n, const double *v, const double *w, const double *Wf,
@@ -925,6 +1033,27 @@ void launch_hist_residual(const SolveArgs<REAL> &a, int sweeps, int blocks, doub
 }
 
 template <typename REAL>
+void launch_seg_residual(const SolveArgs<REAL> &a, const EnsembleSegs &S, const int32_t *running, const REAL *xs,
+                         const REAL *as, const REAL *ws, int sweeps, double *err, hipStream_t s) {
+  if (S.n_ens <= 0 || sweeps <= 0) return;
+  hipLaunchKernelGGL((seg_residual_kernel<REAL>), dim3(S.n_ens, sweeps), dim3(256), 0, s, a, S, running, xs, as, ws, err);
+}
+
+template <typename REAL>
+void launch_seg_select(const EnsembleSegs &S, const EnsembleStop &T, const double *err, int sweeps, int first, int max_iters,
+                       int every, double tol, int all_checked, int init, const REAL *xs, size_t xstride, const REAL *as,
+                       size_t astride, REAL *fin_x, REAL *fin_acc, hipStream_t s) {
+  if (S.n_ens <= 0) return;
+  hipLaunchKernelGGL((seg_select_kernel<REAL>), dim3(S.n_ens), dim3(256), 0, s, S, T, err, sweeps, first, max_iters,
+                     every > 0 ? every : 1, tol, all_checked, init, xs, xstride, as, astride, fin_x, fin_acc);
+}
+
+void launch_seg_fixed(const EnsembleSegs &S, const EnsembleStop &T, const double *err, int sweeps, hipStream_t s) {
+  if (S.n_ens <= 0) return;
+  hipLaunchKernelGGL(seg_fixed_kernel, dim3((S.n_ens + 255) / 256), dim3(256), 0, s, S, T, err, sweeps);
+}
+
+template <typename REAL>
 void launch_velocity(int n, const double *v, const double *w, const double *Wf, const REAL *acc, double dt, double *v6,
                      hipStream_t s) {
   if (n <= 0) return;
@@ -1021,7 +1150,12 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
                                       double *, hipStream_t);                          \
   template void launch_convert_minv<REAL>(int, const double *, REAL *, hipStream_t);                         \
   template void launch_minv_iso<REAL>(int, const REAL *, int *, hipStream_t);                               \
-  template void launch_hist_residual<REAL>(const SolveArgs<REAL> &, int, int, double *, int, hipStream_t);
+  template void launch_hist_residual<REAL>(const SolveArgs<REAL> &, int, int, double *, int, hipStream_t);   \
+  template void launch_seg_residual<REAL>(const SolveArgs<REAL> &, const EnsembleSegs &, const int32_t *, const REAL *, \
+                                          const REAL *, const REAL *, int, double *, hipStream_t);                      \
+  template void launch_seg_select<REAL>(const EnsembleSegs &, const EnsembleStop &, const double *, int, int, int, int,  \
+                                        double, int, int, const REAL *, size_t, const REAL *, size_t, REAL *, REAL *,   \
+                                        hipStream_t);
 EGS_INSTANTIATE(double)
 EGS_INSTANTIATE(float)
 

@@ -357,6 +357,37 @@ egs_status egs_world_get_contacts(egs_world *w, int32_t max_contacts, int32_t *m
 egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_out, double *lambda);
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans);
 
+/* ---- many ensembles in one world ------------------------------------------
+ * The reference steps every Ensemble of a frame in turn (model.cc:37-70:
+ * SimulationStep() calls Step() on each).  A batched world holds E
+ * independent ensembles and steps them all in one device pipeline; after
+ * every step each ensemble holds exactly the bits a world created for it
+ * alone would hold: bodies, contact list (order included), lambda, sweep
+ * count and residual.
+ *   - n_bodies [E] (>= 0 each, E >= 1); body_offset [E+1] (may be NULL)
+ *     receives where ensemble e's bodies start in the concatenated arrays
+ *     that egs_world_set_bodies / get_bodies take.
+ *   - egs_world_set_joints keeps global body indices; a joint may not join
+ *     two ensembles (the world, -1, is allowed) and the joints must be
+ *     grouped by non-decreasing ensemble: EGS_ERR_INVALID otherwise.
+ *   - Contacts never join two ensembles; the contact list (get_contacts) is,
+ *     ensemble by ensemble, its ground contacts then its body pairs i < j.
+ *   - With tol > 0 each ensemble stops on its own residual, as its own
+ *     Step() would; egs_solve_stats from egs_world_step then reports the
+ *     largest sweep count and the largest residual over the ensembles.
+ * E = 1 is egs_world_create(ctx, n_bodies[0], ...) itself.                   */
+egs_status egs_world_create_batch(egs_context *ctx, int32_t n_ensembles, const int32_t *n_bodies,
+                                  int32_t precision, egs_world **out, int32_t *body_offset);
+/* Per-ensemble figures of a world (n_ensembles must be the world's; a plain
+ * world is one ensemble).  joint_offset / contact_offset [E+1]: ensemble e's
+ * joints are constraints [joint_offset[e], joint_offset[e+1]) and its contacts
+ * [contact_offset[e], contact_offset[e+1]) of get_contacts, i.e. constraint
+ * mj + k of get_lambda's rows (joints first).  iterations / residual [E]: the
+ * last step's solve of each ensemble (model.cc:37-70, one Step() each).
+ * Any pointer may be NULL.                                                   */
+egs_status egs_world_batch_info(egs_world *w, int32_t n_ensembles, int32_t *joint_offset,
+                                int32_t *contact_offset, int32_t *iterations, double *residual);
+
 /* Replaces lcp::SolveLCP_BoxDantzig (toolkit/lcp.cc:444-619; reached from lcp::SolveLCP with
  * Settings.algorithm = COTTLE_DANTZIG, box_lcp = true, schur_complement = false, toolkit/lcp.cc:776-779):
  * Cottle-Dantzig principal pivoting on A x = b + w with lo <= x <= hi, the Cholesky factor of the active
