@@ -36,6 +36,7 @@ EXPORTS = [
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
+    "egs_world_step_dense", "egs_world_dense_info",
 ]
 
 
@@ -563,6 +564,24 @@ class World:
                                              C.c_int32(1 if detect_contacts else 0),
                                              C.byref(st) if want_stats else None))
         return st
+
+    def step_dense(self, dt, erp=0.2, cfm=0.01, use_bounds=0, detect_contacts=True):
+        """Ensemble::Step through the reference's dense path for every ensemble (egs_world_step_dense): cfm is
+        kCfmCoeff, added where cond(J M^-1 J^T) >= 1e7.  Returns how many ensembles failed to solve (then no body
+        moved; dense_info() tells which); any other error raises."""
+        nf = C.c_int32(0)
+        st = load().egs_world_step_dense(self.h, C.c_double(dt), C.c_double(erp), C.c_double(cfm), C.c_int32(use_bounds),
+                                         C.c_int32(1 if detect_contacts else 0), C.byref(nf))
+        if st not in (OK, ERR_LCP_FAILED):
+            self.ctx.check(st)
+        return nf.value
+
+    def dense_info(self):
+        """Per-ensemble figures of the last step_dense: condition estimate, cfm added, pivots, ok [E]."""
+        E = self.n_ensembles
+        cond = np.zeros(E); cfm = np.zeros(E); piv = np.zeros(E, np.int32); ok = np.zeros(E, np.int32)
+        self.ctx.check(load().egs_world_dense_info(self.h, C.c_int32(E), _p(cond), _p(cfm), _p(piv), _p(ok)))
+        return dict(condition=cond, cfm=cfm, pivots=piv, ok=ok.astype(bool))
 
     def bodies(self):
         pos = np.zeros((self.n, 3)); R = np.zeros((self.n, 9)); v = np.zeros((self.n, 3)); w = np.zeros((self.n, 3))

@@ -19,6 +19,7 @@
 #include "../../include/eggshell_amd.h"
 #include "collide.h"
 #include "dense_lcp.h"
+#include "dense_world.h"
 #include "kernels.h"
 #include "matvec.h"
 #include "plan.h"
@@ -2156,6 +2157,24 @@ struct egs_world {
   DevBuf<int32_t> d_ens, d_boff, d_joff;       // body -> ensemble [n], body and joint offsets [n_ens + 1]
   DevBuf<int32_t> d_coff;                      // contact offsets [n_ens + 1], written by the collider
   BatchSolveState batch;
+  // egs_world_step_dense: each ensemble's dense row space (its joints, then its contacts, as its own Ensemble lists
+  // them), built on the first dense step after a re-plan; the figures of the last dense step
+  int dense_plan_replans = -1;           // w->replans the tables below were built for
+  std::vector<int32_t> dn_start;         // [E + 1] into dn_cons (host copy)
+  std::vector<int64_t> dn_off;           // [E] workspace offsets (host copy)
+  std::vector<int32_t> dn_class[3], dn_big;   // ensembles per fused size class; above the fused cap
+  int dn_max_m = 0;
+  DevBuf<int32_t> dn_cons, dn_cstart, dn_lists;
+  DevBuf<int64_t> dn_wsoff;
+  DevBuf<double> dn_ws;
+  DevBuf<DenseEnsStatus> dn_status;
+  std::vector<uint8_t> dn_big_C;         // C / lo / hi of the ensembles above the cap, read back once per re-plan
+  std::vector<double> dn_big_lo, dn_big_hi;
+  bool dn_big_rows_valid = false;
+  PinnedArena dn_pinned;
+  DenseEnsStatus *h_dn_status = nullptr;
+  std::vector<DenseEnsStatus> dn_info;   // [E] of the last dense step
+  bool last_dense = false;               // the last step was egs_world_step_dense (batch_info reports its pivots)
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
   double t_phase[5] = {0, 0, 0, 0, 0};   // collide, topology D2H + compare, re-plan, solve + integrate (enqueue), steps
@@ -2189,6 +2208,87 @@ void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int 
   np->h_rows_valid = false;
   w->topo_b0.assign(b0, b0 + m); w->topo_b1.assign(b1, b1 + m);
   ++w->replans;
+}
+
+// UpdateContacts + pruning on the device (ensembles.cc:393-394), the topology read-back, and a re-plan only when the
+// constraint topology changed: the front of egs_world_step and egs_world_step_dense.
+template <typename LAP>
+void world_update_contacts(egs_world *w, LAP &&lap) {
+  hipStream_t s = w->ctx->stream;
+  const int mj = (int)w->jb0.size();
+  const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, mj, w->djb0.p, w->djb1.p, w->djdata.p);
+  lap(0);
+  const size_t mt = (size_t)mj + (size_t)mc;
+  if (mt > w->h_cap) {   // grow-only; the stream is idle here (col.run synchronised)
+    w->topo_pinned.reset();
+    w->h_cap = mt + mt / 4 + 64;
+    w->h_b0 = static_cast<int32_t *>(w->topo_pinned.take(2 * w->h_cap * sizeof(int32_t)));
+    w->h_b1 = w->h_b0 + w->h_cap;
+  }
+  std::copy(w->jb0.begin(), w->jb0.end(), w->h_b0);
+  std::copy(w->jb1.begin(), w->jb1.end(), w->h_b1);
+  if (mc > 0) {   // the GPU writes the 8 bytes per contact straight into page-locked host memory
+    w->col.export_topology(s, mc, w->h_b0 + mj, w->h_b1 + mj);
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  const bool changed = mt != w->topo_b0.size() || (mt > 0 && (
+                       std::memcmp(w->h_b0, w->topo_b0.data(), mt * sizeof(int32_t)) != 0 ||
+                       std::memcmp(w->h_b1, w->topo_b1.data(), mt * sizeof(int32_t)) != 0));
+  lap(1);
+  if (changed) world_make_problem(w, w->h_b0, w->h_b1, (int)mt);  // host plan only on topology change
+  lap(2);
+  if (mc > 0)
+    HIPCHK(hipMemcpyAsync(w->prob->data.p + (size_t)mj * 7, w->col.data(), (size_t)mc * 7 * sizeof(double),
+                          hipMemcpyDeviceToDevice, s));
+  w->m_contacts = mc;
+}
+
+// The dense row space of every ensemble (egs_world_step_dense): ensemble e's constraints in the order its own
+// Ensemble would list them -- its joints, then its contacts (ensembles.cc:234-239) -- which decides the Murty loop's
+// first offender and the Schur partition; workspace offsets; the fused kernel's size classes.  Host tables only:
+// building them is not a re-plan.
+void world_dense_plan(egs_world *w) {
+  const egs_problem *p = w->prob;
+  const int E = w->n_ens, m = p->m;
+  std::vector<int32_t> ens((size_t)(m > 0 ? m : 1), 0), count((size_t)E, 0);
+  for (int c = 0; c < m; ++c) {
+    const int32_t b = p->h_body0[(size_t)c] >= 0 ? p->h_body0[(size_t)c] : p->h_body1[(size_t)c];
+    const int e = E == 1 ? 0 : (int)(std::upper_bound(w->body_off.begin(), w->body_off.end(), b) - w->body_off.begin()) - 1;
+    ens[(size_t)c] = e;
+    ++count[(size_t)e];
+  }
+  w->dn_start.assign((size_t)E + 1, 0);
+  w->dn_off.assign((size_t)E, 0);
+  w->dn_max_m = 0;
+  for (auto &l : w->dn_class) l.clear();
+  w->dn_big.clear();
+  int64_t off = 0;
+  for (int e = 0; e < E; ++e) {
+    const int me = count[(size_t)e], N = 3 * me;
+    w->dn_start[(size_t)e + 1] = w->dn_start[(size_t)e] + me;
+    w->dn_off[(size_t)e] = off;
+    off += (int64_t)dense_ws_size((size_t)N);
+    w->dn_max_m = std::max(w->dn_max_m, me);
+    if (N == 0) continue;   // v_dot = M^-1 f (ensembles.cc:504-505): nothing to solve
+    if (N <= kDenseClassRows[0]) w->dn_class[0].push_back(e);
+    else if (N <= kDenseClassRows[1]) w->dn_class[1].push_back(e);
+    else if (N <= kFusedDenseMax) w->dn_class[2].push_back(e);
+    else w->dn_big.push_back(e);
+  }
+  // a stable bucket sort: the world lists joints (grouped by ensemble) before contacts (grouped by ensemble)
+  std::vector<int32_t> cons((size_t)(m > 0 ? m : 1), 0), next(w->dn_start.begin(), w->dn_start.end() - 1);
+  for (int c = 0; c < m; ++c) cons[(size_t)next[(size_t)ens[(size_t)c]]++] = c;
+  std::vector<int32_t> lists;
+  for (const auto &l : w->dn_class) lists.insert(lists.end(), l.begin(), l.end());
+  if (lists.empty()) lists.push_back(0);
+  stage(w->ctx, w->dn_cons, cons);
+  stage(w->ctx, w->dn_cstart, w->dn_start);
+  stage(w->ctx, w->dn_wsoff, w->dn_off);
+  stage(w->ctx, w->dn_lists, lists);
+  w->dn_ws.alloc((size_t)(off > 0 ? off : 1));
+  w->dn_status.alloc((size_t)E);
+  w->dn_big_rows_valid = false;
+  w->dense_plan_replans = w->replans;
 }
 
 }  // namespace
@@ -2332,9 +2432,9 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
   if (!w) return EGS_ERR_INVALID;
   if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
   if (!(dt > 0)) return fail(w->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  w->last_dense = false;
   return guarded(w->ctx, [&]() -> egs_status {
     hipStream_t s = w->ctx->stream;
-    const int mj = (int)w->jb0.size();
     using clk = std::chrono::steady_clock;
     auto t0 = clk::now();
     auto lap = [&](int k) {
@@ -2343,33 +2443,7 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
       w->t_phase[k] += std::chrono::duration<double, std::micro>(t1 - t0).count();
       t0 = t1;
     };
-    if (detect_contacts) {  // UpdateContacts + pruning on the device (ensembles.cc:393-394)
-      const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, mj, w->djb0.p, w->djb1.p, w->djdata.p);
-      lap(0);
-      const size_t mt = (size_t)mj + (size_t)mc;
-      if (mt > w->h_cap) {   // grow-only; the stream is idle here (col.run synchronised)
-        w->topo_pinned.reset();
-        w->h_cap = mt + mt / 4 + 64;
-        w->h_b0 = static_cast<int32_t *>(w->topo_pinned.take(2 * w->h_cap * sizeof(int32_t)));
-        w->h_b1 = w->h_b0 + w->h_cap;
-      }
-      std::copy(w->jb0.begin(), w->jb0.end(), w->h_b0);
-      std::copy(w->jb1.begin(), w->jb1.end(), w->h_b1);
-      if (mc > 0) {   // the GPU writes the 8 bytes per contact straight into page-locked host memory
-        w->col.export_topology(s, mc, w->h_b0 + mj, w->h_b1 + mj);
-        HIPCHK(hipStreamSynchronize(s));
-      }
-      const bool changed = mt != w->topo_b0.size() || (mt > 0 && (
-                           std::memcmp(w->h_b0, w->topo_b0.data(), mt * sizeof(int32_t)) != 0 ||
-                           std::memcmp(w->h_b1, w->topo_b1.data(), mt * sizeof(int32_t)) != 0));
-      lap(1);
-      if (changed) world_make_problem(w, w->h_b0, w->h_b1, (int)mt);  // host plan only on topology change
-      lap(2);
-      if (mc > 0)
-        HIPCHK(hipMemcpyAsync(w->prob->data.p + (size_t)mj * 7, w->col.data(), (size_t)mc * 7 * sizeof(double),
-                              hipMemcpyDeviceToDevice, s));
-      w->m_contacts = mc;
-    }
+    if (detect_contacts) world_update_contacts(w, lap);
     egs_problem *p = w->prob;
     const bool batched = w->n_ens > 1;
     if (p->m > 0) {
@@ -2404,6 +2478,142 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
     if (w->trace) { HIPCHK(hipStreamSynchronize(s)); lap(3); w->t_phase[4] += 1; }
     return EGS_OK;
   });
+}
+
+egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_coeff, int32_t use_bounds,
+                                int32_t detect_contacts, int32_t *n_failed) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_failed) *n_failed = 0;
+  if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
+  if (!(dt > 0)) return fail(w->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  if (w->precision != EGS_F64) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense path is fp64 (the reference's is)");
+  if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
+  w->last_dense = false;
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    if (detect_contacts) world_update_contacts(w, [](int) {});
+    egs_problem *p = w->prob;
+    const int E = w->n_ens;
+    if (!w->h_dn_status) w->h_dn_status = static_cast<DenseEnsStatus *>(w->dn_pinned.take((size_t)E * sizeof(DenseEnsStatus)));
+    w->dn_info.assign((size_t)E, DenseEnsStatus{1.0, 0.0, 1, 0});   // contact-free ensembles: solved, no pivots
+    std::string big_msg;
+    if (p->m > 0) {
+      do_assemble(p, dt, erp);                                       // J, err, bounds, rhs (ensembles.cc:565-570)
+      if (w->dense_plan_replans != w->replans) world_dense_plan(w);
+      DenseWorldArgs a;
+      a.cons = w->dn_cons.p; a.cstart = w->dn_cstart.p; a.ws_off = w->dn_wsoff.p;
+      a.body0 = p->body0.p; a.body1 = p->body1.p;
+      a.J0 = reinterpret_cast<const double *>(p->J0.p); a.J1 = reinterpret_cast<const double *>(p->J1.p);
+      a.Minv = p->Minv_d.p;
+      a.rhs = reinterpret_cast<const double *>(p->rhs.p);
+      a.lo = reinterpret_cast<const double *>(p->lo.p); a.hi = reinterpret_cast<const double *>(p->hi.p);
+      a.is_eq = p->is_eq.p;
+      a.ws = w->dn_ws.p; a.x = reinterpret_cast<double *>(p->x.p); a.status = w->dn_status.p;
+      a.cfm_coeff = cfm_coeff; a.use_bounds = use_bounds;
+      launch_dense_world_system(a, E, w->dn_max_m, s);               // A_e = J M^-1 J^T (ensembles.cc:510)
+      int at = 0;
+      for (int c = 0; c < 3; ++c) {                                  // the rest of ComputeVDot, one workgroup each
+        launch_dense_world_fused(a, w->dn_lists.p + at, (int)w->dn_class[c].size(), c, s);
+        at += (int)w->dn_class[c].size();
+      }
+      HIPCHK(hipGetLastError());
+      // above the fused cap: the multi-launch path on each ensemble's workspace slice, one after another
+      if (!w->dn_big.empty()) {
+        if (!w->dn_big_rows_valid) {
+          size_t rows = 0;
+          for (int e : w->dn_big) rows += (size_t)3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]);
+          std::vector<double> c4(rows * 3);
+          size_t r0 = 0;
+          for (int e : w->dn_big) {
+            const size_t N = (size_t)3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]);
+            const double *vb = w->dn_ws.p + w->dn_off[(size_t)e] + dense_ws_vec(N);
+            HIPCHK(hipMemcpyAsync(c4.data() + 3 * r0, vb + N, 3 * N * sizeof(double), hipMemcpyDeviceToHost, s));   // lo, hi, C
+            r0 += N;
+          }
+          HIPCHK(hipStreamSynchronize(s));
+          w->dn_big_C.resize(rows); w->dn_big_lo.resize(rows); w->dn_big_hi.resize(rows);
+          r0 = 0;
+          for (int e : w->dn_big) {
+            const size_t N = (size_t)3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]);
+            for (size_t k = 0; k < N; ++k) {
+              w->dn_big_lo[r0 + k] = c4[3 * r0 + k];
+              w->dn_big_hi[r0 + k] = c4[3 * r0 + N + k];
+              w->dn_big_C[r0 + k] = c4[3 * r0 + 2 * N + k] != 0.0 ? 1 : 0;
+            }
+            r0 += N;
+          }
+          w->dn_big_rows_valid = true;
+        }
+        size_t r0 = 0;
+        for (int e : w->dn_big) {
+          const int N = 3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]);
+          double *A = w->dn_ws.p + w->dn_off[(size_t)e];
+          double *vb = A + dense_ws_vec((size_t)N), *xs = vb + 4 * (size_t)N;
+          DenseEnsStatus &st = w->dn_info[(size_t)e];
+          bool spd = true;
+          st.condition = dense_condition_estimate(s, N, A, &spd);    // ensembles.cc:513-521
+          st.cfm = st.condition < 1e7 ? 0.0 : cfm_coeff;
+          if (st.cfm != 0.0) launch_dense_world_add_diag(A, N, st.cfm, s);
+          int piv = 0;
+          std::string msg;
+          const bool good = dense_mixed_constraints_device(s, N, A, vb, w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
+                                                           w->dn_big_hi.data() + r0, use_bounds != 0, false, 0, 0.0, nullptr,
+                                                           nullptr, xs, &piv, &msg);
+          st.ok = good ? 1 : 0;
+          st.pivots = piv;
+          if (good) launch_dense_world_scatter(w->dn_cons.p + w->dn_start[(size_t)e], N, xs, a.x, s);
+          else if (big_msg.empty()) big_msg = msg;
+          r0 += (size_t)N;
+        }
+        HIPCHK(hipGetLastError());
+      }
+      // one read-back of the fused ensembles' figures
+      if (at > 0) {
+        HIPCHK(hipMemcpyAsync(w->h_dn_status, w->dn_status.p, (size_t)E * sizeof(DenseEnsStatus), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (const auto &l : w->dn_class)
+          for (int e : l) w->dn_info[(size_t)e] = w->h_dn_status[e];
+      }
+    }
+    int nf = 0, first = -1, max_piv = 0;
+    for (int e = 0; e < E; ++e) {
+      const DenseEnsStatus &st = w->dn_info[(size_t)e];
+      if (!st.ok && first < 0) first = e;
+      nf += st.ok ? 0 : 1;
+      max_piv = std::max(max_piv, (int)st.pivots);
+      if (E > 1) { w->batch.h_ints[e] = st.pivots; w->batch.h_res[e] = std::numeric_limits<double>::quiet_NaN(); }
+    }
+    p->last_iterations = max_piv;
+    w->last_dense = true;
+    if (n_failed) *n_failed = nf;
+    if (nf > 0) {   // the reference Panics (ensembles.cc:531-534): no body is advanced
+      std::string msg = "ensemble " + std::to_string(first) + ": MixedConstraintsSolver did not reach a solution";
+      if (!big_msg.empty()) msg += " (" + big_msg + ")";
+      if (nf > 1) msg += "; " + std::to_string(nf) + " of " + std::to_string(E) + " ensembles failed";
+      return fail(w->ctx, EGS_ERR_LCP_FAILED, msg);
+    }
+    if (p->m > 0) accumulators_from_lambda(p);                    // a = M^-1 J^T lambda
+    else HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * p->real_size(), s));
+    do_velocity(p, dt);                                           // ensembles.cc:535, 572
+    launch_advance(p->n, p->pos.p, p->R.p, p->v.p, p->w.p, p->v6.p, dt, s);   // StepPositions_ODE
+    HIPCHK(hipGetLastError());
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm, int32_t *pivots,
+                                int32_t *ok) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  if (w->dn_info.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_step_dense yet");
+  for (int e = 0; e < w->n_ens; ++e) {
+    const DenseEnsStatus &st = w->dn_info[(size_t)e];
+    if (condition) condition[e] = st.condition;
+    if (cfm) cfm[e] = st.cfm;
+    if (pivots) pivots[e] = st.pivots;
+    if (ok) ok[e] = st.ok;
+  }
+  return EGS_OK;
 }
 
 egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v, double *wv) {
@@ -2457,11 +2667,11 @@ egs_status egs_world_batch_info(egs_world *w, int32_t n_ensembles, int32_t *join
   if (contact_offset) { contact_offset[0] = 0; contact_offset[1] = w->m_contacts; }
   if (!iterations && !residual) return EGS_OK;
   egs_solve_stats st{};
-  if (w->prob) {
+  if (w->prob && !w->last_dense) {
     if (egs_status r = egs_problem_get_stats(w->prob, &st)) return r;
   }
-  if (iterations) iterations[0] = st.iterations;
-  if (residual) residual[0] = st.residual;
+  if (iterations) iterations[0] = w->last_dense ? w->dn_info[0].pivots : st.iterations;
+  if (residual) residual[0] = w->last_dense ? std::numeric_limits<double>::quiet_NaN() : st.residual;
   return EGS_OK;
 }
 

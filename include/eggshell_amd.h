@@ -388,6 +388,32 @@ egs_status egs_world_create_batch(egs_context *ctx, int32_t n_ensembles, const i
 egs_status egs_world_batch_info(egs_world *w, int32_t n_ensembles, int32_t *joint_offset,
                                 int32_t *contact_offset, int32_t *iterations, double *residual);
 
+/* Ensemble::Step(dt, OPEN_DYNAMICS_ENGINE) on the reference's live path (kSparseImplementation = false,
+ * ensembles.cc:390-427, 498-538, 563-591), for every ensemble of a world (plain or batched).  Per ensemble,
+ * on its own constraint list in the reference's order (its joints, then its contacts):
+ * A = J M^-1 J^T; cond(A) < 1e7 ? A : A + cfm_coeff*I; Lcp::MixedConstraintsSolver(A, rhs, C, lo, hi);
+ * velocity update; midpoint positions.  use_bounds: 0 = the reference (quirk Q3), 1 = true box problem.
+ * fp64 worlds only (EGS_ERR_UNSUPPORTED otherwise).  If any ensemble's solve fails (the reference Panics,
+ * ensembles.cc:531-534), the call returns EGS_ERR_LCP_FAILED, egs_last_error names the first failing
+ * ensemble and NO body of the world is advanced.  *n_failed (may be NULL) = how many failed.
+ *   - Contact detection, pruning and re-planning are those of egs_world_step; the two steps may alternate on
+ *     one world (they share the bodies, the contact list, get_lambda and batch_info's offsets), and switching
+ *     between them does not re-plan.  After a dense step batch_info reports iterations[e] = principal pivots
+ *     and residual[e] = NaN.
+ *   - An ensemble of at most 112 rows (3 per constraint) is solved by one fused kernel, a workgroup per
+ *     ensemble, the whole ComputeVDot in LDS (size classes of <= 32, <= 64 and <= 112 rows; the class depends
+ *     on the ensemble's own size only, so its bits do not depend on the rest of the batch).  Larger ensembles
+ *     are solved one after another inside the same call by the multi-launch path of egs_problem_step_dense
+ *     (the condition estimate of egs_problem_dense_condition, then the dense mixed solver).
+ *   - An ensemble without constraints gets v_dot = M^-1 f (ensembles.cc:504-505), ok = 1, pivots = 0.   */
+egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_coeff, int32_t use_bounds,
+                                int32_t detect_contacts, int32_t *n_failed);
+/* Per-ensemble figures of the last egs_world_step_dense ([E] each, any may be NULL): the condition estimate
+ * (+inf when A is not positive definite), the cfm actually added (0 or cfm_coeff), the principal pivots,
+ * and ok (1 = solved).  n_ensembles must be the world's; EGS_ERR_INVALID before the first dense step.    */
+egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm,
+                                int32_t *pivots, int32_t *ok);
+
 /* Replaces lcp::SolveLCP_BoxDantzig (toolkit/lcp.cc:444-619; reached from lcp::SolveLCP with
  * Settings.algorithm = COTTLE_DANTZIG, box_lcp = true, schur_complement = false, toolkit/lcp.cc:776-779):
  * Cottle-Dantzig principal pivoting on A x = b + w with lo <= x <= hi, the Cholesky factor of the active
