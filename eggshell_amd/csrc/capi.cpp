@@ -218,6 +218,10 @@ struct egs_problem {
   int last_lean = 0;           // ... in its 128-VGPR form (lean_solve.hip)
   bool lin_antisym = false;    // J1_lin == -J0_lin on every two-body constraint (device assembly: by construction;
                                // egs_problem_set_blocks: checked on the host), what lean_step_kernel relies on
+  bool lin_neg = false;        // ... bit for bit, signed zeros included (device assembly: contacts only, note_kinds)
+  bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
+  int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
+  int last_linsym = 0;         // the last tile launch used step_solve_kernel's LINSYM form
   int oversize = 2;            // OversizeSchedule
   int global_max_blocks = 1;
   DevBuf<LaneDesc> q_lanes;
@@ -328,8 +332,13 @@ void download_real(egs_problem *p, const DevBuf<unsigned char> &src, double *dst
   }
 }
 
+void decide_linsym_bodies(egs_problem *p);
+
 void ensure_minv_real(egs_problem *p) {
-  if (p->minv_r_valid) return;
+  if (p->minv_r_valid) {
+    if (p->linsym_bodies < 0) decide_linsym_bodies(p);
+    return;
+  }
   const int count = p->n * 36;
   if (p->precision == EGS_F32)
     launch_convert_minv<float>(count, p->Minv_d.p, reinterpret_cast<float *>(p->Minv_r.p), p->ctx->stream);
@@ -351,6 +360,34 @@ void ensure_minv_real(egs_problem *p) {
     if (iso != p->minv_iso) p->tile_plan_ready = false;   // the preferred tile size depends on it
     p->minv_iso = iso;
   }
+  decide_linsym_bodies(p);
+}
+
+// Once per M^-1 upload or topology change (4 bytes back): may the fp64 isotropic timetable sweep keep one linear block
+// for both sides (step_solve.hip: LINSYM)?  The body half of the preconditions -- every constraint has a body on
+// side 1, and where it has one on side 0 as well, the same linear weight -- is decided here, on the device; the
+// Jacobian half (lin_neg) where the blocks are made.  EGS_ISO_LINSYM=0 disables the form.
+void decide_linsym_bodies(egs_problem *p) {
+  p->linsym_bodies = 0;
+  const char *le = std::getenv("EGS_ISO_LINSYM");
+  if (le && std::atoi(le) == 0) return;
+  if (p->precision != EGS_F64 || !p->minv_iso || p->m <= 0) return;
+  hipStream_t s = p->ctx->stream;
+  int one = 1, flag = 0;
+  int32_t *scratch = p->error_flag.p + 1;
+  HIPCHK(hipMemcpyAsync(scratch, &one, sizeof(int), hipMemcpyHostToDevice, s));
+  launch_linsym_bodies<double>(p->m, p->body0.p, p->body1.p, reinterpret_cast<const double *>(p->Minv_r.p), scratch, s);
+  HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  p->linsym_bodies = flag != 0 ? 1 : 0;
+}
+
+// Ball joints that join two bodies are assembled with +0 in J1_lin where J0_lin holds +0 (joints.cc:17-31): their
+// J1_lin is -J0_lin in value but not in bits.  Contacts are [-Rn, ..] / [Rn, ..], negated bit for bit.
+void note_kinds(egs_problem *p, const int32_t *kind) {
+  bool jp = false;
+  for (int i = 0; i < p->m && !jp; ++i) jp = kind[i] == EGS_JOINT_BALL && p->h_body0[i] >= 0 && p->h_body1[i] >= 0;
+  p->joint_pairs = jp;
 }
 
 // ---- the sticky stall flag ---------------------------------------------------
@@ -435,6 +472,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     }
     p->last_iso = quad ? 0 : a.iso;
     p->last_lean = 0;
+    p->last_linsym = 0;
     if (quad) {
       launch_cons_prepare<REAL>(a, ctx->stream);
       if (use_static_timetable(p->planq, sweeps)) {
@@ -460,7 +498,12 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
                a.hist_x == nullptr && !a.runs;
         if (lean) { a.iso = 1; launch_lean_solve(a, method, p->plan.n_tiles, p->plan.block, ctx->stream); p->last_iso = 1; }
       }
-      if (!lean) launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream);
+      if (!lean) {
+        // one linear block for both sides (step_solve.hip: LINSYM): fp64 isotropic sweep, not for the snapshots
+        if constexpr (sizeof(REAL) == 8)
+          a.linsym = (a.iso && a.hist_x == nullptr && p->lin_neg && p->linsym_bodies == 1) ? 1 : 0;
+        p->last_linsym = launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream) ? 1 : 0;
+      }
       p->last_static = 1;
       p->last_lean = lean ? 1 : 0;
     } else {
@@ -626,7 +669,8 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_tiles = pl.n_tiles;
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
-  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_iso ? EGS_SCHED_ISO : 0) | (p->last_static ? EGS_SCHED_STATIC : 0) | (p->last_lean ? EGS_SCHED_LEAN : 0);
+  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_iso ? EGS_SCHED_ISO : 0) | (p->last_static ? EGS_SCHED_STATIC : 0) | (p->last_lean ? EGS_SCHED_LEAN : 0) |
+                (p->last_linsym ? EGS_SCHED_LINSYM : 0);
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;
@@ -1038,6 +1082,7 @@ void do_assemble(egs_problem *p, double dt, double erp) {
   HIPCHK(hipGetLastError());
   p->have_blocks = true;
   p->lin_antisym = true;     // joints.cc:17-31 and contact.cc:66-99 build [X, ..] / [-X, ..]
+  p->lin_neg = !p->joint_pairs;
 }
 
 void do_velocity(egs_problem *p, double dt) {
@@ -1341,6 +1386,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->h_body0.assign(body0, body0 + m);
   p->h_body1.assign(body1, body1 + m);
   p->tile_plan_ready = false;
+  p->linsym_bodies = -1;
   p->mv_ready = false;
   p->dense_cfm = -1.0;
   p->h_rows_valid = false;
@@ -1506,13 +1552,18 @@ egs_status egs_problem_set_blocks(egs_problem *p, const double *Minv, const doub
     if (J0 || J1) {
       // lean_step_kernel keeps ONE linear block per constraint: allowed only if J1_lin = -J0_lin wherever both sides exist
       bool anti = J0 && J1 && p->precision == EGS_F64 && p->h_body0.size() == m && p->h_body1.size() == m;
+      bool neg = anti;   // step_solve_kernel's LINSYM form: the same, bit for bit
       for (size_t i = 0; anti && i < m; ++i) {
         if (p->h_body0[i] < 0 || p->h_body1[i] < 0) continue;
         for (int r = 0; r < 3 && anti; ++r)
-          for (int k = 0; k < 3; ++k)
-            if (!(J0[i * 18 + 6 * r + k] == -J1[i * 18 + 6 * r + k])) { anti = false; break; }
+          for (int k = 0; k < 3; ++k) {
+            const double a = J0[i * 18 + 6 * r + k], b = -J1[i * 18 + 6 * r + k];
+            if (!(a == b)) { anti = false; break; }
+            neg = neg && std::memcmp(&a, &b, sizeof a) == 0;
+          }
       }
       p->lin_antisym = anti;
+      p->lin_neg = anti && neg;
     }
     if (is_eq && m) upload(p->is_eq, is_eq, m * 3, p->ctx->stream);
     upload_real(p, p->lo, lo, m * 3);
@@ -1587,6 +1638,7 @@ egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, cons
   return guarded(p->ctx, [&]() -> egs_status {
     upload(p->kind, kind, (size_t)p->m, p->ctx->stream);
     upload(p->data, data, (size_t)p->m * 7, p->ctx->stream);
+    note_kinds(p, kind);
     p->have_constraints = true;
     p->h_rows_valid = false;
     return EGS_OK;
@@ -2202,6 +2254,7 @@ void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int 
   if (m > 0) {
     kind.resize((size_t)m);
     stage(w->ctx, np->kind, kind);   // through the pinned arena (reset only after a synchronise): no wait here
+    note_kinds(np, kind.data());
     if (mj > 0) upload(np->data, w->jdata.data(), (size_t)mj * 7, s);
   }
   np->have_constraints = true;

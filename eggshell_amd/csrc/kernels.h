@@ -39,6 +39,8 @@ struct SolveArgs {
   int32_t runs = 0;            // the timetable counts groups of four constraints (plan.h: Plan::runs)
   int32_t patch_runs = 0;      // body patches: the lanes come in chunks of four quads (Plan::patch_runs, quad_solve.hip)
   int iso = 0;              // 1: every M^-1 block is diag(a,a,a,b,b,b): B is formed on the fly (tile kernel)
+  int linsym = 0;           // 1 (with iso, fp64, GROUP = 1): J1_lin = -J0_lin and wl0 = wl1 bit for bit on every
+                            // two-body constraint: step_solve_kernel keeps one linear block (step_solve.hip: LINSYM)
   // Per-sweep history (tolerance-terminated solves): x after sweep s and each body's
   // accumulator once its last constraint of sweep s has run, s = 1..sweeps of this launch.
   // hist_residual then evaluates the reference's per-iteration stopping test for the
@@ -96,7 +98,7 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
                        int block, hipStream_t s);
 // the same GS / SOR sweep on the plan's static timetable: one workgroup barrier per time step, no tickets
 template <typename REAL>
-void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s);
+bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s);   // true: LINSYM form ran
 // the same timetable in 128 VGPRs (lean_solve.hip): fp64, isotropic bodies, 256-constraint tiles, J1_lin = -J0_lin
 void launch_lean_solve(const SolveArgs<double> &a, int method, int n_tiles, int block, hipStream_t s);
 int occupancy_lean_solve(int block, int max_slots);
@@ -183,6 +185,10 @@ void launch_convert_minv(int count, const double *src, REAL *dst, hipStream_t s)
 // *flag (preset to 1) is cleared unless every 6x6 block is exactly diag(a, a, a, b, b, b)
 template <typename REAL>
 void launch_minv_iso(int n, const REAL *W, int *flag, hipStream_t s);
+// clears *flag unless every constraint has a body on side 1 and, where it also has one on side 0, both bodies carry
+// the same linear weight W[0] bit for bit (the body preconditions of step_solve_kernel's LINSYM form)
+template <typename REAL>
+void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, const REAL *W, int *flag, hipStream_t s);
 
 // A = J M^-1 J^T + cfm I, [3m][3m] row-major fp64 on the device (ensembles.cc:510, 513-521)
 void launch_dense_system(int m, const int32_t *body0, const int32_t *body1, const double *J0, const double *J1,

@@ -514,6 +514,21 @@ __global__ void __launch_bounds__(256) minv_iso_kernel(int n, const REAL *W, int
   if (!iso) atomicAnd(flag, 0);
 }
 
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+
+template <typename REAL>
+__global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t *body0, const int32_t *body1, const REAL *W, int *flag) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool ok = true;
+  if (i < m) {
+    const int b0 = body0[i], b1 = body1[i];
+    ok = b1 >= 0;
+    if (ok && b0 >= 0) ok = same_bits(W[(size_t)b0 * 36], W[(size_t)b1 * 36]);
+  }
+  if (!ok) atomicAnd(flag, 0);
+}
+
 // --------------------------------------------------------------------------
 // K1-K4 assembly.  Operation order mirrors oracle/model.c.
 __device__ __forceinline__ double d3(const double *a, const double *b) {
@@ -1082,6 +1097,12 @@ void launch_minv_iso(int n, const REAL *W, int *flag, hipStream_t s) {
   hipLaunchKernelGGL((minv_iso_kernel<REAL>), dim3((n + 255) / 256), dim3(256), 0, s, n, W, flag);
 }
 
+template <typename REAL>
+void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, const REAL *W, int *flag, hipStream_t s) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL((linsym_bodies_kernel<REAL>), dim3((m + 255) / 256), dim3(256), 0, s, m, body0, body1, W, flag);
+}
+
 
 template <typename REAL>
 int occupancy_global_solve() {
@@ -1150,6 +1171,7 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
                                       double *, hipStream_t);                          \
   template void launch_convert_minv<REAL>(int, const double *, REAL *, hipStream_t);                         \
   template void launch_minv_iso<REAL>(int, const REAL *, int *, hipStream_t);                               \
+  template void launch_linsym_bodies<REAL>(int, const int32_t *, const int32_t *, const REAL *, int *, hipStream_t);                               \
   template void launch_hist_residual<REAL>(const SolveArgs<REAL> &, int, int, double *, int, hipStream_t);   \
   template void launch_seg_residual<REAL>(const SolveArgs<REAL> &, const EnsembleSegs &, const int32_t *, const REAL *, \
                                           const REAL *, const REAL *, int, double *, hipStream_t);                      \

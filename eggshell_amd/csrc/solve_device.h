@@ -112,7 +112,7 @@ __device__ __forceinline__ void acc_add_side1(REAL *a, const Cons<REAL> &c, cons
   if (ISO) acc_add_iso(a, c.J1, c.wl1, c.wa1, d); else acc_add(a, c.B1, d);
 }
 
-template <typename REAL, bool ISO = false>
+template <typename REAL, bool ISO = false, bool LINSYM = false>
 __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bool has0, bool has1,
                                           int body0, int body1, Cons<REAL> &c) {
 #pragma unroll
@@ -137,6 +137,19 @@ __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bo
         for (int k = 1; k < 6; ++k) d1 = tfma(c.J1[6 * r + k], (k < 3 ? c.wl1 : c.wa1) * c.J1[6 * q + k], d1);
         c.D[3 * r + q] = d0 + d1;
       }
+    // LINSYM (step_solve.hip): every lane has side 1, J0_lin = -J1_lin and wl0 = wl1 where it has side 0.  One linear
+    // block Jl = -J1_lin in J0_lin's registers (side 1 takes -Jl) and Bl = wl1 Jl in J1_lin's.  A side-1-only lane
+    // reads the world slot (zeros) on side 0, where the +-0 products sum to the +0 of the plain form.
+    if (LINSYM) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const REAL j = -c.J1[6 * r + k];
+          c.J0[6 * r + k] = j;
+          c.J1[6 * r + k] = c.wl1 * j;
+        }
+    }
   } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) { c.B0[k] = REAL(0); c.B1[k] = REAL(0); }

@@ -22,12 +22,58 @@
 // and in a regular tile the due wavefront is the same in every tile.  Sharing the barrier and
 // rotating the lane -> wavefront assignment by the tile's number inside the group puts the GROUP
 // passes of a time step on GROUP different SIMDs.
+//
+// LINSYM: the isotropic fp64 sweep when every two-body constraint has J1_lin = -J0_lin bit for bit and both bodies
+// the same linear weight wl (a pile of equal boxes: contact.cc:66-99 builds [-Rn, ..] / [Rn, ..]), and every
+// constraint has a body on side 1.  Then wl0 J0_lin = -(wl1 J1_lin) exactly (negation commutes with rounding), so
+// load_cons leaves ONE linear block Jl = -J1_lin in J0_lin's registers and Bl = wl1 Jl, precomputed, in J1_lin's:
+// side 1's linear residual products take -Jl and the linear accumulator updates take +Bl (side 0) / -Bl (side 1), all
+// as source negations, which cost nothing.  An update forms only the 18 angular products w J on the fly instead of
+// 36.  Same roundings in the same order as the plain kernel: the same bits (capi.cpp decides the preconditions).
 #include "kernels.h"
 #include "solve_device.h"
 
 namespace egs {
 
 namespace {
+
+// row_dot of row r with side 1's linear products taken as -Jl (dot3h's order, row_dot's sum order)
+template <typename REAL>
+__device__ __forceinline__ REAL linsym_row_dot(const Cons<REAL> &c, int r, const REAL *a0, const REAL *a1) {
+  const REAL *j = c.J0 + 6 * r;
+  const REAL p0 = dot3h(j, a0), p1 = dot3h(j + 3, a0 + 3);
+  REAL p2 = (-j[0]) * a1[0];
+  p2 = tfma(-j[1], a1[1], p2);
+  p2 = tfma(-j[2], a1[2], p2);
+  const REAL p3 = dot3h(c.J1 + 6 * r + 3, a1 + 3);
+  return (p0 + p1) + (p2 + p3);
+}
+// row_residuals on the LINSYM registers
+template <typename REAL>
+__device__ __forceinline__ void linsym_residuals(const Cons<REAL> &c, const REAL *a0, const REAL *a1, const REAL *x,
+                                                 REAL cfm, REAL *res) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) res[r] = c.rhs[r] - tfma(cfm, x[r], linsym_row_dot(c, r, a0, a1));
+}
+
+// acc_add_iso with the linear half from +-Bl (NEG: side 1) and the angular half w J formed on the fly.  wa is the
+// loop-carried register itself, made opaque by the caller: no copy per update.
+template <bool NEG, typename REAL>
+__device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, const REAL *Ja, REAL wa, const REAL *d) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const REAL *B = c.J1 + k;   // Bl[r][k] at B[6 r]
+    REAL t = tfma(NEG ? -B[0] : B[0], d[0], a[k]);
+    t = tfma(NEG ? -B[6] : B[6], d[1], t);
+    a[k] = tfma(NEG ? -B[12] : B[12], d[2], t);
+  }
+#pragma unroll
+  for (int k = 3; k < 6; ++k) {
+    REAL t = tfma(wa * Ja[k], d[0], a[k]);
+    t = tfma(wa * Ja[6 + k], d[1], t);
+    a[k] = tfma(wa * Ja[12 + k], d[2], t);
+  }
+}
 
 template <int METHOD>
 __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int resume) {
@@ -36,7 +82,7 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
   return n_phases >= 1 ? depth + P * (n_phases - 1) : 0;
 }
 
-template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST>
+template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WAVES = BLOCK / 64;
@@ -67,7 +113,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
   if (active) {
-    load_cons<REAL, ISO>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+    load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
     for (int r = 0; r < 3; ++r) x[r] = A.resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
@@ -100,11 +146,19 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
         for (int r = 0; r < 3; ++r) dx[r] = x[r];
       } else {
         REAL res[3];
-        row_residuals(c, a0, a1, x, A.cfm, res);
+        if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
+        else row_residuals(c, a0, a1, x, A.cfm, res);
         update_rows<REAL, METHOD>(c, res, x, dx);
       }
-      if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
-      if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
+      if (LINSYM) {
+        // opaque to the optimiser in place: the products wa J stay in the update (not hoisted into 36 registers)
+        asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
+        if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
+        if (has1) { linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx); store6(ac1, a1); }
+      } else {
+        if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
+        if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
+      }
       if (hist && sweep >= 1) {
         REAL *hx = A.hist_x + ((size_t)(sweep - 1) * A.m + d.cidx) * 3;
         hx[0] = x[0]; hx[1] = x[1]; hx[2] = x[2];
@@ -134,7 +188,8 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
     lds_load6(s_acc + slot1 * 6, a1);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      REAL w = tfma(A.cfm, x[r], row_dot(c.J0 + 6 * r, a0, c.J1 + 6 * r, a1)) - c.rhs[r];
+      const REAL ax = LINSYM ? linsym_row_dot(c, r, a0, a1) : row_dot(c.J0 + 6 * r, a0, c.J1 + 6 * r, a1);
+      REAL w = tfma(A.cfm, x[r], ax) - c.rhs[r];
       A.x[(size_t)d.cidx * 3 + r] = x[r];
       A.wres[(size_t)d.cidx * 3 + r] = w;
     }
@@ -157,17 +212,17 @@ int step_group_env(int dflt) {
 }  // namespace
 
 template <typename REAL>
-void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s) {
-  if (n_tiles <= 0) return;
+bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s) {
+  if (n_tiles <= 0) return false;
   SolveArgs<REAL> b = a;
   b.n_tiles = n_tiles;
-#define EGS_LAUNCH_S(BLK, ISO, GRP) EGS_LAUNCH_SH(BLK, ISO, GRP, !ISO)
-#define EGS_LAUNCH_SH(BLK, ISO, GRP, HIST)                                                                     \
+#define EGS_LAUNCH_S(BLK, ISO, GRP) EGS_LAUNCH_SH(BLK, ISO, GRP, !ISO, false)
+#define EGS_LAUNCH_SH(BLK, ISO, GRP, HIST, LINSYM)                                                             \
   {                                                                                                            \
     const size_t lds = (size_t)b.max_slots * 6 * sizeof(REAL) * GRP;                                           \
     const dim3 g((n_tiles + GRP - 1) / GRP), t(BLK * GRP);                                                     \
-    auto k1 = step_solve_kernel<REAL, BLK, 1, ISO, GRP, HIST>;                                                 \
-    auto k2 = step_solve_kernel<REAL, BLK, 2, ISO, GRP, HIST>;                                                 \
+    auto k1 = step_solve_kernel<REAL, BLK, 1, ISO, GRP, HIST, LINSYM>;                                         \
+    auto k2 = step_solve_kernel<REAL, BLK, 2, ISO, GRP, HIST, LINSYM>;                                         \
     if (lds > 48 * 1024) {                                                                                     \
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2),                            \
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
@@ -180,13 +235,17 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
     // pays for the four fp32 tiles (C4: 0.281 ms against 0.368); with three fp64 tiles the 12-wavefront
     // barrier costs more than the collisions it avoids (C3 x 24: 1.06 ms against 0.95), so fp64 keeps GROUP = 1
     const int grp = step_group_env(sizeof(REAL) == 4 ? 4 : 1);
-    if (b.hist_x != nullptr) EGS_LAUNCH_SH(256, true, 1, true)      // per-sweep snapshots of the stopping loop (kernels.h)
+    if (b.hist_x != nullptr) EGS_LAUNCH_SH(256, true, 1, true, false)      // per-sweep snapshots of the stopping loop (kernels.h)
     else if constexpr (sizeof(REAL) == 4) {
       if (grp >= 4) EGS_LAUNCH_S(256, true, 4)
       else if (grp >= 2) EGS_LAUNCH_S(256, true, 2)
       else EGS_LAUNCH_S(256, true, 1)
     } else {
       if (grp >= 3) EGS_LAUNCH_S(256, true, 3)
+      else if (b.linsym) {   // one linear block for both sides (LINSYM above)
+        EGS_LAUNCH_SH(256, true, 1, false, true)
+        return true;
+      }
       else EGS_LAUNCH_S(256, true, 1)
     }
   }
@@ -196,9 +255,10 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
   else EGS_LAUNCH_S(512, false, 1)
 #undef EGS_LAUNCH_S
 #undef EGS_LAUNCH_SH
+  return false;
 }
 
-template void launch_step_solve<double>(const SolveArgs<double> &, int, int, int, hipStream_t);
-template void launch_step_solve<float>(const SolveArgs<float> &, int, int, int, hipStream_t);
+template bool launch_step_solve<double>(const SolveArgs<double> &, int, int, int, hipStream_t);
+template bool launch_step_solve<float>(const SolveArgs<float> &, int, int, int, hipStream_t);
 
 }  // namespace egs
