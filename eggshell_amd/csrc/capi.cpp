@@ -222,6 +222,8 @@ struct egs_problem {
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
   int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
   int last_linsym = 0;         // the last tile launch used step_solve_kernel's LINSYM form
+  int last_fused = 0;          // ... and assembled the system in its prologue (egs_problem_step: fused_assembly_applies)
+  const AssembleArgs *fused_asm = nullptr;   // set by egs_problem_step for the next launch: assemble in its prologue
   int oversize = 2;            // OversizeSchedule
   int global_max_blocks = 1;
   DevBuf<LaneDesc> q_lanes;
@@ -418,6 +420,18 @@ void record_kernel_event(egs_context *ctx, bool begin) {
 
 void ensure_tile_plan(egs_problem *p);
 
+// SolveArgs::iso of a launch on the tile plan (quad = false) or the 4-lane plan
+int tile_iso(const egs_problem *p, bool quad, int method, int sweeps) {
+  int iso = (p->minv_iso && !quad && p->plan.block == 256 && iso_schedule_pays(p->m, p->ctx->cu_count, p->precision)) ? 1 : 0;
+  // the ticket kernel's isotropic variant has no registers to spare for the snapshots; the timetable
+  // kernel has an instantiation of its own for them
+  if (p->hist_sweeps > 0 && !(method != EGS_JACOBI && !quad && use_static_timetable(p->plan, sweeps))) iso = 0;
+  const char *ie = std::getenv("EGS_ISO");   // 2: force the variant wherever the bodies allow it (experiments)
+  if (ie && std::atoi(ie) == 2 && p->minv_iso && !quad && p->plan.block == 256 &&
+      (p->hist_sweeps == 0 || (method != EGS_JACOBI && use_static_timetable(p->plan, sweeps)))) iso = 1;
+  return iso;
+}
+
 template <typename REAL>
 void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweeps, int resume) {
   egs_context *ctx = p->ctx;
@@ -456,23 +470,16 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     a.resume = resume;
     a.max_slots = quad ? p->planq.max_slots : p->plan.max_slots;
     a.spin_limit = spin_limit();
-    a.iso = (p->minv_iso && !quad && p->plan.block == 256 && iso_schedule_pays(p->m, ctx->cu_count, p->precision)) ? 1 : 0;
+    a.iso = tile_iso(p, quad, method, sweeps);
     a.n_bodies = p->n;
     if (p->hist_sweeps > 0) {
       a.hist_x = reinterpret_cast<REAL *>(p->hist_x.p);
       a.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p);
-      // the ticket kernel's isotropic variant has no registers to spare for the snapshots; the timetable
-      // kernel has an instantiation of its own for them
-      if (!(method != EGS_JACOBI && !quad && use_static_timetable(p->plan, sweeps))) a.iso = 0;
-    }
-    {
-      const char *ie = std::getenv("EGS_ISO");   // 2: force the variant wherever the bodies allow it (experiments)
-      if (ie && std::atoi(ie) == 2 && p->minv_iso && !quad && p->plan.block == 256 &&
-          (p->hist_sweeps == 0 || (method != EGS_JACOBI && use_static_timetable(p->plan, sweeps)))) a.iso = 1;
     }
     p->last_iso = quad ? 0 : a.iso;
     p->last_lean = 0;
     p->last_linsym = 0;
+    p->last_fused = 0;
     if (quad) {
       launch_cons_prepare<REAL>(a, ctx->stream);
       if (use_static_timetable(p->planq, sweeps)) {
@@ -494,15 +501,25 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
         // (DESIGN.md section 5); EGS_LEAN=1 selects it wherever its preconditions hold.  Never for the
         // snapshot-recording launches of the stopping loop.
         const char *le = std::getenv("EGS_LEAN");
-        lean = le && std::atoi(le) != 0 && p->minv_iso && (p->plan.block == 256 || p->plan.block == 512) && p->lin_antisym &&
+        lean = !p->fused_asm && le && std::atoi(le) != 0 && p->minv_iso && (p->plan.block == 256 || p->plan.block == 512) && p->lin_antisym &&
                a.hist_x == nullptr && !a.runs;
         if (lean) { a.iso = 1; launch_lean_solve(a, method, p->plan.n_tiles, p->plan.block, ctx->stream); p->last_iso = 1; }
       }
       if (!lean) {
         // one linear block for both sides (step_solve.hip: LINSYM): fp64 isotropic sweep, not for the snapshots
-        if constexpr (sizeof(REAL) == 8)
+        if constexpr (sizeof(REAL) == 8) {
           a.linsym = (a.iso && a.hist_x == nullptr && p->lin_neg && p->linsym_bodies == 1) ? 1 : 0;
-        p->last_linsym = launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream) ? 1 : 0;
+          if (p->fused_asm) {   // ... with the assembly in its prologue (egs_problem_step, fused_assembly_applies)
+            if (resume || !a.linsym || !step_solve_takes_linsym(a, p->plan.block))
+              throw std::logic_error("fused assembly chosen for a launch that is not a fresh LINSYM launch");
+            a.assemble = *p->fused_asm;
+            p->fused_asm = nullptr;
+            launch_step_solve_assemble(a, method, p->plan.n_tiles, ctx->stream);
+            p->last_linsym = p->last_fused = 1;
+          }
+        }
+        if (!p->last_fused)
+          p->last_linsym = launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream) ? 1 : 0;
       }
       p->last_static = 1;
       p->last_lean = lean ? 1 : 0;
@@ -607,6 +624,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
   }
   record_kernel_event(ctx, false);
   HIPCHK(hipGetLastError());
+  if (p->fused_asm) throw std::logic_error("fused assembly chosen, but the launch did not take it");
 }
 
 void launch_solve(egs_problem *p, const egs_solve_params &prm, int sweeps, int resume) {
@@ -670,7 +688,7 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
   st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_iso ? EGS_SCHED_ISO : 0) | (p->last_static ? EGS_SCHED_STATIC : 0) | (p->last_lean ? EGS_SCHED_LEAN : 0) |
-                (p->last_linsym ? EGS_SCHED_LINSYM : 0);
+                (p->last_linsym ? EGS_SCHED_LINSYM : 0) | (p->last_fused ? EGS_SCHED_FUSED_ASSEMBLY : 0);
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;
@@ -739,6 +757,14 @@ void release_large_history(egs_problem *p) {
   }
 }
 
+// The longest launch of a fixed-sweep solve: tickets are 32-bit counters that advance by cnt per sweep, and the static
+// timetable counts time steps in a 32-bit int (see do_solve)
+int fixed_chunk_max(const Plan &pl_used) {
+  const int64_t by_ticket = (int64_t)0xF0000000u / (int64_t)std::max(1, pl_used.max_cnt) - 2;
+  const int64_t by_clock = ((int64_t)0x7fffffff - 2 * (int64_t)std::max(1, pl_used.max_depth) - 2) / (int64_t)std::max(1, pl_used.max_period) - 2;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_ticket, by_clock), 0x7fffffff));
+}
+
 // The solve driver: sparse_iterations.cc:148-226.
 egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats) {
   egs_context *ctx = p->ctx;
@@ -757,10 +783,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     // are cut into resumed launches so they cannot wrap
     // ... and the static timetable counts time steps in a 32-bit int (t_end = depth + period x sweeps,
     // step_solve.hip / quad_solve.hip): the chunk also keeps that below INT_MAX.  64-bit arithmetic, then the clamp.
-    const Plan &pl_used = p->use_quad ? p->planq : p->plan;
-    const int64_t by_ticket = (int64_t)0xF0000000u / (int64_t)std::max(1, pl_used.max_cnt) - 2;
-    const int64_t by_clock = ((int64_t)0x7fffffff - 2 * (int64_t)std::max(1, pl_used.max_depth) - 2) / (int64_t)std::max(1, pl_used.max_period) - 2;
-    const int chunk_max = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_ticket, by_clock), 0x7fffffff));
+    const int chunk_max = fixed_chunk_max(p->use_quad ? p->planq : p->plan);
     int done = 0;
     do {
       const int chunk = std::min(chunk_max, prm->max_iters - done);
@@ -1066,7 +1089,7 @@ void ensure_wf(egs_problem *p) {
   p->wf_valid = true;
 }
 
-void do_assemble(egs_problem *p, double dt, double erp) {
+AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
   AssembleArgs a;
   a.n = p->n; a.m = p->m;
   a.pos = p->pos.p; a.R = p->R.p; a.v = p->v.p; a.w = p->w.p;
@@ -1077,12 +1100,51 @@ void do_assemble(egs_problem *p, double dt, double erp) {
   a.dt = dt; a.erp = erp;
   a.J0 = p->J0.p; a.J1 = p->J1.p; a.lo = p->lo.p; a.hi = p->hi.p; a.rhs = p->rhs.p;
   a.err = p->err.p; a.is_eq = p->is_eq.p;
-  if (p->precision == EGS_F32) launch_assemble<float>(a, p->ctx->stream);
-  else launch_assemble<double>(a, p->ctx->stream);
-  HIPCHK(hipGetLastError());
+  return a;
+}
+
+// what the device assembly tells about the blocks it makes
+void note_assembled(egs_problem *p) {
   p->have_blocks = true;
   p->lin_antisym = true;     // joints.cc:17-31 and contact.cc:66-99 build [X, ..] / [-X, ..]
   p->lin_neg = !p->joint_pairs;
+}
+
+void do_assemble(egs_problem *p, double dt, double erp) {
+  const AssembleArgs a = assemble_args(p, dt, erp);
+  if (p->precision == EGS_F32) launch_assemble<float>(a, p->ctx->stream);
+  else launch_assemble<double>(a, p->ctx->stream);
+  HIPCHK(hipGetLastError());
+  note_assembled(p);
+}
+
+// egs_problem_step assembles in the prologue of the solve launch (step_solve.hip: ASSEMBLE) exactly when do_solve is
+// about to make ONE launch of the LINSYM timetable kernel: fp64, a fixed sweep count in one chunk, GS or SOR on the
+// 1-lane tile plan with every constraint in a tile (no oversize islands), the isotropic variant and LINSYM's
+// preconditions for assembled blocks (no two-body ball joint, equal linear weights).  Anything else -- tol > 0, fp32,
+// mixed masses, ball joints between bodies, the 4-lane or lean kernels -- keeps assemble_kernel.  launch_solve_t
+// checks the choice again at the launch.  EGS_FUSED_ASSEMBLY=0 disables the fused form.
+bool fused_assembly_applies(egs_problem *p, const egs_solve_params *prm) {
+  const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
+  if (fe && std::atoi(fe) == 0) return false;
+  if (p->precision != EGS_F64 || p->m <= 0 || p->joint_pairs) return false;
+  if (!prm || prm->tol > 0 || !(prm->method == EGS_GAUSS_SEIDEL || prm->method == EGS_SOR)) return false;
+  if (prm->method == EGS_SOR && !(prm->omega > 0 && prm->omega < 2)) return false;   // do_solve refuses it
+  if (prm->max_iters < 0) return false;
+  const char *le = std::getenv("EGS_LEAN");
+  if (le && std::atoi(le) != 0) return false;
+  ensure_minv_real(p);   // what do_solve does first: isotropy, LINSYM's body check, hence the tile plan
+  if (p->use_quad) return false;
+  ensure_tile_plan(p);
+  const Plan &pl = p->plan;
+  if (pl.n_tiles <= 0 || !pl.global.empty() || pl.n_patch_tiles > 0 || pl.block != 256) return false;
+  if (p->hist_sweeps != 0 || prm->max_iters > fixed_chunk_max(pl) || !use_static_timetable(pl, prm->max_iters)) return false;
+  if (p->linsym_bodies != 1) return false;
+  SolveArgs<double> a;
+  a.iso = tile_iso(p, false, prm->method, prm->max_iters);
+  a.hist_x = nullptr;
+  a.linsym = a.iso;
+  return step_solve_takes_linsym(a, pl.block);
 }
 
 void do_velocity(egs_problem *p, double dt) {
@@ -1659,7 +1721,18 @@ egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_sol
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
   return guarded(p->ctx, [&]() -> egs_status {
     if (stall_seen(p)) return report_stall(p);   // an earlier (asynchronous) step timed out
-    do_assemble(p, dt, erp);
+    AssembleArgs fa;
+    struct Pending {   // the fused assembly is offered to this step's solve launch only
+      egs_problem *p;
+      ~Pending() { p->fused_asm = nullptr; }
+    } pending{p};
+    if (fused_assembly_applies(p, params)) {
+      fa = assemble_args(p, dt, erp);
+      note_assembled(p);
+      p->fused_asm = &fa;
+    } else {
+      do_assemble(p, dt, erp);
+    }
     egs_status st = do_solve(p, params, stats);
     if (st != EGS_OK) return st;
     do_velocity(p, dt);

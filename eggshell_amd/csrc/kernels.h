@@ -8,6 +8,18 @@
 
 namespace egs {
 
+struct AssembleArgs {
+  int32_t n, m;
+  const double *pos, *R, *v, *w;                 // body state, fp64
+  const double *Wf;                              // [n][6] M^-1 f_ext (launch_mass_times_force)
+  const int32_t *kind, *body0, *body1;
+  const double *data;                            // [m][7]
+  double dt, erp;
+  void *J0, *J1, *lo, *hi, *rhs;                 // REAL outputs
+  double *err;                                   // [3m] fp64
+  uint8_t *is_eq;
+};
+
 // Flat system + tile plan, all device pointers.
 template <typename REAL>
 struct SolveArgs {
@@ -41,6 +53,9 @@ struct SolveArgs {
   int iso = 0;              // 1: every M^-1 block is diag(a,a,a,b,b,b): B is formed on the fly (tile kernel)
   int linsym = 0;           // 1 (with iso, fp64, GROUP = 1): J1_lin = -J0_lin and wl0 = wl1 bit for bit on every
                             // two-body constraint: step_solve_kernel keeps one linear block (step_solve.hip: LINSYM)
+  // step_solve_kernel's ASSEMBLE form (launch_step_solve_assemble): every lane assembles its constraint from this
+  // body state in the prologue and also leaves the blocks where assemble_kernel would (J0 .. is_eq above point there)
+  AssembleArgs assemble{};
   // Per-sweep history (tolerance-terminated solves): x after sweep s and each body's
   // accumulator once its last constraint of sweep s has run, s = 1..sweeps of this launch.
   // hist_residual then evaluates the reference's per-iteration stopping test for the
@@ -78,17 +93,6 @@ struct GlobalArgs {
   REAL *hist_x = nullptr, *hist_acc = nullptr;
 };
 
-struct AssembleArgs {
-  int32_t n, m;
-  const double *pos, *R, *v, *w;                 // body state, fp64
-  const double *Wf;                              // [n][6] M^-1 f_ext (launch_mass_times_force)
-  const int32_t *kind, *body0, *body1;
-  const double *data;                            // [m][7]
-  double dt, erp;
-  void *J0, *J1, *lo, *hi, *rhs;                 // REAL outputs
-  double *err;                                   // [3m] fp64
-  uint8_t *is_eq;
-};
 
 // Wf[b] = M_b^-1 f_ext,b: both frozen at Init (Q5), so assembly and the velocity update read
 // these 48 B per body instead of the 288 B block and the force (same expression, same bits).
@@ -99,6 +103,11 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
 // the same GS / SOR sweep on the plan's static timetable: one workgroup barrier per time step, no tickets
 template <typename REAL>
 bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s);   // true: LINSYM form ran
+// would launch_step_solve<double> take the LINSYM form for these arguments?
+bool step_solve_takes_linsym(const SolveArgs<double> &a, int block);
+// the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles): assemble_kernel
+// and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s);
 // the same timetable in 128 VGPRs (lean_solve.hip): fp64, isotropic bodies, 256-constraint tiles, J1_lin = -J0_lin
 void launch_lean_solve(const SolveArgs<double> &a, int method, int n_tiles, int block, hipStream_t s);
 int occupancy_lean_solve(int block, int max_slots);

@@ -25,6 +25,7 @@
 // that can run; consecutive sweeps pipeline through an island as a wavefront.
 #include "kernels.h"
 #include "solve_device.h"
+#include "assemble_device.h"
 
 #ifndef EGS_POLL_SLEEP
 #define EGS_POLL_SLEEP 32  // s_sleep units (64 cycles) of a wavefront none of whose lanes is ready; s_wakeup ends it early
@@ -530,72 +531,7 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
 }
 
 // --------------------------------------------------------------------------
-// K1-K4 assembly.  Operation order mirrors oracle/model.c.
-__device__ __forceinline__ double d3(const double *a, const double *b) {
-  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-__device__ __forceinline__ void mv3(const double *A, const double *v, double *o) {
-  o[0] = (A[0] * v[0] + A[1] * v[1]) + A[2] * v[2];
-  o[1] = (A[3] * v[0] + A[4] * v[1]) + A[5] * v[2];
-  o[2] = (A[6] * v[0] + A[7] * v[1]) + A[8] * v[2];
-}
-__device__ __forceinline__ void mm3(const double *A, const double *B, double *O) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      O[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
-}
-__device__ __forceinline__ void crossmat(const double *a, double *m) {  // utils.cc:16-24
-  m[0] = 0;     m[1] = -a[2]; m[2] = a[1];
-  m[3] = a[2];  m[4] = 0;     m[5] = -a[0];
-  m[6] = -a[1]; m[7] = a[0];  m[8] = 0;
-}
-__device__ __forceinline__ void quat_to_R(double w, double x, double y, double z, double *R) {
-  double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  double twx = tx * w, twy = ty * w, twz = tz * w;
-  double txx = tx * x, txy = ty * x, txz = tz * x;
-  double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
-  R[3] = txy + twz;         R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
-}
-// utils.cc:233-237 (Eigen FromTwoVectors(a, z).toRotationMatrix()); for the
-// antiparallel case see DESIGN.md (deterministic axis instead of Eigen's SVD).
-__device__ void align_to_z(const double *a, double *Rout) {
-  double v0[3];
-  const double na = d3(a, a);
-  if (na > 0) { const double s = sqrt(na); v0[0] = a[0] / s; v0[1] = a[1] / s; v0[2] = a[2] / s; }
-  else { v0[0] = a[0]; v0[1] = a[1]; v0[2] = a[2]; }
-  const double v1[3] = {0.0 / 1.0, 0.0 / 1.0, 1.0 / 1.0};
-  double c = d3(v1, v0);
-  double qw, q[3];
-  if (c < -1.0 + 1e-12) {
-    if (c < -1.0) c = -1.0;
-    const double ax = fabs(v0[0]), ay = fabs(v0[1]), az = fabs(v0[2]);
-    double e[3] = {0, 0, 0};
-    if (ax <= ay && ax <= az) e[0] = 1; else if (ay <= az) e[1] = 1; else e[2] = 1;
-    double axis[3] = {v0[1] * e[2] - v0[2] * e[1], v0[2] * e[0] - v0[0] * e[2], v0[0] * e[1] - v0[1] * e[0]};
-    const double n = sqrt(d3(axis, axis));
-    axis[0] /= n; axis[1] /= n; axis[2] /= n;
-    const double w2 = (1.0 + c) * 0.5;
-    qw = sqrt(w2);
-    const double sv = sqrt(1.0 - w2);
-    q[0] = axis[0] * sv; q[1] = axis[1] * sv; q[2] = axis[2] * sv;
-  } else {
-    const double axis[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
-    const double s = sqrt((1.0 + c) * 2.0);
-    const double invs = 1.0 / s;
-    q[0] = axis[0] * invs; q[1] = axis[1] * invs; q[2] = axis[2] * invs;
-    qw = s * 0.5;
-  }
-  quat_to_R(qw, q[0], q[1], q[2], Rout);
-}
-
-__device__ __forceinline__ double dot6p(const double *a, const double *b) {
-  return ((((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]) + a[4] * b[4]) + a[5] * b[5];
-}
-
+// K1-K4 assembly: the per-constraint body lives in assemble_device.h.
 template <typename REAL>
 __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
@@ -604,98 +540,9 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
   const int i_raw = blockIdx.x * 256 + threadIdx.x;
   const bool live = i_raw < A.m;
   const int i = live ? i_raw : A.m - 1;   // the tail lanes recompute the last constraint and store nothing
-  const int b0 = A.body0[i], b1 = A.body1[i];
-  double d[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) d[k] = A.data[(size_t)i * 7 + k];
-  double j0[18], j1[18], e[3], lo[3], hi[3];
+  double j0[18], j1[18], e[3], lo[3], hi[3], u0[6], u1[6];
   bool eq;
-#pragma unroll
-  for (int k = 0; k < 18; ++k) { j0[k] = 0.0; j1[k] = 0.0; }
-  if (A.kind[i] == 0) {  // joints.cc:3-35
-    double R0[9], rc0[3], cm[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
-    mv3(R0, d, rc0);
-    crossmat(rc0, cm);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      j0[6 * r + r] = 1.0;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) j0[6 * r + 3 + c] = -1.0 * cm[3 * r + c];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) e[k] = A.pos[(size_t)b0 * 3 + k] + rc0[k];
-    if (b1 >= 0) {
-      double R1[9], rc1[3];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R1[k] = A.R[(size_t)b1 * 9 + k];
-      mv3(R1, d + 3, rc1);
-      crossmat(rc1, cm);
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        j1[6 * r + r] = -1.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) j1[6 * r + 3 + c] = cm[3 * r + c];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) e[k] = (e[k] - A.pos[(size_t)b1 * 3 + k]) - rc1[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) e[k] = e[k] - d[3 + k];
-    }
-    eq = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = 0.0; hi[k] = 0.0; }
-  } else {  // contact.cc:14-117, FrictionModel::BOX
-    double Rn[9];
-    align_to_z(d + 3, Rn);
-    if (b0 >= 0) {
-      double rel[3], cm[9], rw[9];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) rel[k] = d[k] - A.pos[(size_t)b0 * 3 + k];
-      crossmat(rel, cm);
-      mm3(Rn, cm, rw);
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { j0[6 * r + c] = -Rn[3 * r + c]; j0[6 * r + 3 + c] = rw[3 * r + c]; }
-    }
-    if (b1 >= 0) {
-      double rel[3], cm[9], rw[9];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) rel[k] = d[k] - A.pos[(size_t)b1 * 3 + k];
-      crossmat(rel, cm);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) cm[k] = -1.0 * cm[k];
-      mm3(Rn, cm, rw);
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { j1[6 * r + c] = Rn[3 * r + c]; j1[6 * r + 3 + c] = rw[3 * r + c]; }
-    }
-    e[0] = 0.0; e[1] = 0.0; e[2] = -d[6];
-    eq = false;
-    lo[0] = -1.0; lo[1] = -1.0; lo[2] = 0.0;
-    hi[0] = 1.0; hi[1] = 1.0; hi[2] = INFINITY;
-  }
-  // rhs = -(erp/dt^2) err - J (v/dt + W f)      ensembles.cc:569-570
-  double u0[6] = {0, 0, 0, 0, 0, 0}, u1[6] = {0, 0, 0, 0, 0, 0};
-  if (b0 >= 0) {
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const double vel = r < 3 ? A.v[(size_t)b0 * 3 + r] : A.w[(size_t)b0 * 3 + r - 3];
-      u0[r] = vel / A.dt + A.Wf[(size_t)b0 * 6 + r];
-    }
-  }
-  if (b1 >= 0) {
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const double vel = r < 3 ? A.v[(size_t)b1 * 3 + r] : A.w[(size_t)b1 * 3 + r - 3];
-      u1[r] = vel / A.dt + A.Wf[(size_t)b1 * 6 + r];
-    }
-  }
-  const double kk = -A.erp / A.dt / A.dt;
+  assemble_one(A, i, j0, j1, e, lo, hi, eq, u0, u1);
   REAL *J0o = reinterpret_cast<REAL *>(A.J0), *J1o = reinterpret_cast<REAL *>(A.J1);
   REAL *loo = reinterpret_cast<REAL *>(A.lo), *hio = reinterpret_cast<REAL *>(A.hi);
   REAL *rhso = reinterpret_cast<REAL *>(A.rhs);
@@ -715,8 +562,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
   if (!live) return;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const double ju = dot6p(j0 + 6 * r, u0) + dot6p(j1 + 6 * r, u1);
-    rhso[(size_t)i * 3 + r] = (REAL)(kk * e[r] - ju);
+    rhso[(size_t)i * 3 + r] = (REAL)assemble_rhs(A, j0, j1, e, u0, u1, r);
     A.err[(size_t)i * 3 + r] = e[r];
     loo[(size_t)i * 3 + r] = (REAL)lo[r];
     hio[(size_t)i * 3 + r] = (REAL)hi[r];

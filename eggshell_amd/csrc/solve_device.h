@@ -112,13 +112,15 @@ __device__ __forceinline__ void acc_add_side1(REAL *a, const Cons<REAL> &c, cons
   if (ISO) acc_add_iso(a, c.J1, c.wl1, c.wa1, d); else acc_add(a, c.B1, d);
 }
 
-template <typename REAL, bool ISO = false, bool LINSYM = false>
+// ASSEMBLED (step_solve_kernel's ASSEMBLE form): c.J0 / c.J1, rhs, lo, hi and eq are in c already, from the assembly's
+// registers; only what is derived from them is formed here.
+template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false>
 __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bool has0, bool has1,
                                           int body0, int body1, Cons<REAL> &c) {
 #pragma unroll
   for (int k = 0; k < 18; ++k) {
-    c.J0[k] = has0 ? A.J0[(size_t)cidx * 18 + k] : REAL(0);
-    c.J1[k] = has1 ? A.J1[(size_t)cidx * 18 + k] : REAL(0);
+    c.J0[k] = has0 ? (ASSEMBLED ? c.J0[k] : A.J0[(size_t)cidx * 18 + k]) : REAL(0);
+    c.J1[k] = has1 ? (ASSEMBLED ? c.J1[k] : A.J1[(size_t)cidx * 18 + k]) : REAL(0);
   }
   c.wl0 = c.wa0 = c.wl1 = c.wa1 = REAL(0);
   if (ISO) {
@@ -191,10 +193,12 @@ __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bo
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     c.inv[r] = REAL(1) / ((c.D[4 * r] + A.cfm) * A.kscale);
-    c.rhs[r] = A.rhs[(size_t)cidx * 3 + r];
-    c.lo[r] = A.lo[(size_t)cidx * 3 + r];
-    c.hi[r] = A.hi[(size_t)cidx * 3 + r];
-    c.eq[r] = A.is_eq[(size_t)cidx * 3 + r] != 0;
+    if (!ASSEMBLED) {
+      c.rhs[r] = A.rhs[(size_t)cidx * 3 + r];
+      c.lo[r] = A.lo[(size_t)cidx * 3 + r];
+      c.hi[r] = A.hi[(size_t)cidx * 3 + r];
+      c.eq[r] = A.is_eq[(size_t)cidx * 3 + r] != 0;
+    }
     clamp_bounds(c.eq[r], c.lo[r], c.hi[r]);
   }
 }

@@ -30,8 +30,20 @@
 // side 1's linear residual products take -Jl and the linear accumulator updates take +Bl (side 0) / -Bl (side 1), all
 // as source negations, which cost nothing.  An update forms only the 18 angular products w J on the fly instead of
 // 36.  Same roundings in the same order as the plain kernel: the same bits (capi.cpp decides the preconditions).
+//
+// ASSEMBLE (LINSYM only): the prologue assembles the lane's constraint itself (assemble_device.h, the body of
+// assemble_kernel) instead of reading back what assemble_kernel wrote: the blocks go from the assembly's registers into
+// Cons, and load_cons (ASSEMBLED) finishes them.  The lane also stores J0, J1 (staged through LDS, stage_blocks), rhs,
+// lo, hi, err and is_eq where assemble_kernel puts them, with the same bits, for whatever reads the system after the
+// solve (get_blocks, the residual, matvec, later solves).  Nothing waits for these stores: they drain while the
+// timetable runs.  Every constraint of the problem is a lane of some tile (capi.cpp: no oversize islands), so all of
+// them are written.
+#include <algorithm>
+#include <stdexcept>
+
 #include "kernels.h"
 #include "solve_device.h"
+#include "assemble_device.h"
 
 namespace egs {
 
@@ -75,6 +87,56 @@ __device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, con
   }
 }
 
+// The ASSEMBLE prologue of one lane: K1-K4 for constraint cidx (J0 / J1 into c, for stage_blocks and load_cons), rhs,
+// err, lo, hi and is_eq to global memory where assemble_kernel puts them (24 B per lane and array: a few lines per
+// store instruction), rhs, lo, hi and eq into c.
+__device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, Cons<double> &c) {
+  double e[3], lo[3], hi[3], u0[6], u1[6];
+  bool eq;
+  assemble_one(G, cidx, c.J0, c.J1, e, lo, hi, eq, u0, u1);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    c.rhs[r] = assemble_rhs(G, c.J0, c.J1, e, u0, u1, r);
+    reinterpret_cast<double *>(G.rhs)[(size_t)cidx * 3 + r] = c.rhs[r];
+    G.err[(size_t)cidx * 3 + r] = e[r];
+    reinterpret_cast<double *>(G.lo)[(size_t)cidx * 3 + r] = lo[r];
+    reinterpret_cast<double *>(G.hi)[(size_t)cidx * 3 + r] = hi[r];
+    G.is_eq[(size_t)cidx * 3 + r] = eq ? 1 : 0;
+    c.lo[r] = lo[r];
+    c.hi[r] = hi[r];
+    c.eq[r] = eq;
+  }
+}
+
+// LDS per wavefront for stage_blocks: 64 rows of 18 doubles at a stride of 19 (conflict-free column walks)
+constexpr int kStageWave = 64 * 19;
+
+// J0 and J1 of the wavefront's lanes to global memory in assemble_kernel's layout, through LDS: stored from the lanes'
+// registers, one instruction writes 64 rows 144 B apart, 64 cache lines; staged, lane l stores elements l, l + 64, ..
+// of the wavefront's 64 x 18 block, about four whole rows per instruction.  The whole wavefront takes part (the
+// inactive lanes store nothing); the staging area is the tile's LDS before the accumulators are set up.
+__device__ __forceinline__ void stage_blocks(const AssembleArgs &G, double *stg, int lane, int cidx, bool active,
+                                             const Cons<double> &c) {
+#pragma unroll
+  for (int side = 0; side < 2; ++side) {
+    const double *J = side ? c.J1 : c.J0;
+    double *out = reinterpret_cast<double *>(side ? G.J1 : G.J0);
+    if (active) {
+#pragma unroll
+      for (int k = 0; k < 18; ++k) stg[lane * 19 + k] = J[k];
+    }
+    asm volatile("" ::: "memory");   // the wavefront's LDS operations run in order: no wait, only no reordering
+#pragma unroll
+    for (int it = 0; it < 18; ++it) {
+      const int e = it * 64 + lane, row = e / 18, k = e - 18 * row;
+      const double v = stg[row * 19 + k];
+      const int ci = __shfl(cidx, row);
+      if (ci >= 0) out[(size_t)ci * 18 + k] = v;
+    }
+    asm volatile("" ::: "memory");
+  }
+}
+
 template <int METHOD>
 __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int resume) {
   if (METHOD == 2) return (resume ? 0 : depth) + (sweeps >= 1 ? depth + P * (sweeps - 1) : 0);
@@ -82,7 +144,7 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
   return n_phases >= 1 ? depth + P * (n_phases - 1) : 0;
 }
 
-template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false>
+template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WAVES = BLOCK / 64;
@@ -92,14 +154,17 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   const int tid = (GROUP > 1 && WAVES > 1) ? (((phys >> 6) + sub) % WAVES) * 64 + (phys & 63) : phys;
   const int tile = blockIdx.x * GROUP + sub;
   const bool valid = GROUP == 1 || tile < A.n_tiles;
+  const int resume = ASSEMBLE ? 0 : A.resume;   // the ASSEMBLE form starts a solve (launch_step_solve_assemble)
   REAL *s_acc = reinterpret_cast<REAL *>(smem) + (size_t)sub * A.max_slots * 6;
 
   const int nslots = valid ? A.tile_nslots[tile] : 0;
   const int32_t *slot_body = A.slot_body + (valid ? A.tile_slot_off[tile] : 0);
-  for (int s = tid; s < nslots; s += BLOCK) {
-    const int body = slot_body[s];
+  if constexpr (!ASSEMBLE) {   // the ASSEMBLE form stages its blocks in this LDS first (below)
+    for (int s = tid; s < nslots; s += BLOCK) {
+      const int body = slot_body[s];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = (A.resume && body >= 0) ? A.acc[(size_t)body * 6 + k] : REAL(0);
+      for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = (resume && body >= 0) ? A.acc[(size_t)body * 6 + k] : REAL(0);
+    }
   }
   LaneDesc d;
   d.cidx = -1;
@@ -112,10 +177,20 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
 
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
-  if (active) {
-    load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+  if constexpr (ASSEMBLE) {
+    if (active) assemble_lane(A.assemble, d.cidx, c);
+    stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
+    __syncthreads();   // every wavefront has read its staging area back
+    for (int s = tid; s < nslots; s += BLOCK) {   // a fresh solve: the accumulators start from zero
 #pragma unroll
-    for (int r = 0; r < 3; ++r) x[r] = A.resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
+      for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = REAL(0);
+    }
+  }
+  if (active) {
+    if constexpr (ASSEMBLE) load_cons<REAL, true, true, true>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+    else load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) x[r] = resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
   const unsigned ac0 = lds_addr(s_acc + slot0 * 6), ac1 = lds_addr(s_acc + slot1 * 6);
   // snapshots for the per-sweep stopping test (kernels.h): is this lane the last update of its body in a sweep?
@@ -127,14 +202,14 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
 #pragma unroll
   for (int k = 0; k < GROUP; ++k) {
     const int tk = blockIdx.x * GROUP + k;
-    if (GROUP == 1 || tk < A.n_tiles) t_end = max(t_end, timetable_end<METHOD>(A.tile_depth[tk], A.tile_period[tk], A.sweeps, A.resume));
+    if (GROUP == 1 || tk < A.n_tiles) t_end = max(t_end, timetable_end<METHOD>(A.tile_depth[tk], A.tile_period[tk], A.sweeps, resume));
   }
   __syncthreads();
 
   // the timetable: `due` = the step of this lane's next update, `sweep` = which sweep that is (0 = accumulation)
-  int sweep = A.resume ? 1 : 0;
-  const int t0 = (METHOD == 2 && !A.resume) ? depth : 0;       // backward sweeps start after the forward accumulation
-  int due = (METHOD == 2 && A.resume) ? depth - 1 - level : level;
+  int sweep = resume ? 1 : 0;
+  const int t0 = (METHOD == 2 && !resume) ? depth : 0;       // backward sweeps start after the forward accumulation
+  int due = (METHOD == 2 && resume) ? depth - 1 - level : level;
   if (!active || sweep > A.sweeps) due = 0x7fffffff;
   for (int t = 0; t < t_end; ++t) {
     if (due == t) {
@@ -256,6 +331,24 @@ bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 #undef EGS_LAUNCH_S
 #undef EGS_LAUNCH_SH
   return false;
+}
+
+bool step_solve_takes_linsym(const SolveArgs<double> &a, int block) {
+  return block == 256 && a.iso && a.hist_x == nullptr && step_group_env(1) < 3 && a.linsym;
+}
+
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s) {
+  if (n_tiles <= 0 || a.resume || !step_solve_takes_linsym(a, 256))
+    throw std::logic_error("launch_step_solve_assemble: not a fresh LINSYM launch");
+  SolveArgs<double> b = a;
+  b.n_tiles = n_tiles;
+  const size_t lds = std::max((size_t)b.max_slots * 6 * sizeof(double), (size_t)4 * kStageWave * sizeof(double));
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true>;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
+  else hipLaunchKernelGGL(k2, dim3(n_tiles), dim3(256), lds, s, b);
 }
 
 template bool launch_step_solve<double>(const SolveArgs<double> &, int, int, int, hipStream_t);

@@ -95,8 +95,10 @@ typedef enum {
                                   its static timetable (one workgroup barrier per time step) instead of tickets */
   EGS_SCHED_LEAN = 64,         /* lean_step_kernel: the timetable sweep in 128 VGPRs (one linear block for both sides,
                                   constants parked in LDS): four 256-constraint tiles per CU (fp64, isotropic bodies) */
-  EGS_SCHED_LINSYM = 128       /* step_solve_kernel's LINSYM form: the fp64 isotropic timetable sweep with one linear
+  EGS_SCHED_LINSYM = 128,      /* step_solve_kernel's LINSYM form: the fp64 isotropic timetable sweep with one linear
                                   block for both sides (J1_lin = -J0_lin and equal linear weights, bit for bit) */
+  EGS_SCHED_FUSED_ASSEMBLY = 256   /* egs_problem_step assembled the Jacobian in the LINSYM launch's prologue
+                                      (no separate assembly kernel; the same blocks, bit for bit) */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
