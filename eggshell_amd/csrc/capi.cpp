@@ -99,11 +99,7 @@ constexpr int kBigTileMinConstraints = 196608;   // 768 tiles of 256: from here 
 // depth + (largest per-body count) x sweeps updates long.  Regular islands (piles of columns) have
 // P = the per-body count and the timetable wins (every lane due at a step shares ONE pass); an
 // irregular island can have spans far beyond its counts, then the tickets win.
-// EGS_STEP=0 / 1 forces one or the other.
-inline bool use_static_timetable(const Plan &pl, int sweeps) {
-  if (!pl.levels_ok || pl.n_tiles <= 0) return false;
-  const char *e = std::getenv("EGS_STEP");
-  if (e) return std::atoi(e) != 0;
+inline bool timetable_pays(const Plan &pl, int sweeps) {
   const double grp = pl.runs ? 4.0 : 1.0;     // with runs the timetable counts groups of four updates (plan.h)
   const double fixed = grp * ((double)pl.max_depth + (double)pl.max_period * sweeps);
   const double ticket = grp * (double)pl.max_depth + (double)pl.max_cnt * sweeps;
@@ -210,20 +206,14 @@ struct egs_problem {
   // used for GS/SOR when the problem is small and every island fits a tile
   Plan planq;
   bool use_quad = false;
+  uint32_t last_sched = 0;     // SweepSchedule::flags() of the last solve launch
+  bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
+                               // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
+  bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
+  int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
   // which kernel takes the oversize islands of a GS / SOR solve (choose_oversize_schedule; EGS_PATCH=0
   // forces the all-global kernel, EGS_QUAD_PATCH=0 the 1-lane patches) and how many workgroups the
   // all-global kernel's persistent grid may have: both from the runtime's occupancy of the kernels
-  int last_iso = 0;            // the last tile launch used the isotropic-body variant
-  int last_static = 0;         // ... ran on the static timetable (step_solve.hip)
-  int last_lean = 0;           // ... in its 128-VGPR form (lean_solve.hip)
-  bool lin_antisym = false;    // J1_lin == -J0_lin on every two-body constraint (device assembly: by construction;
-                               // egs_problem_set_blocks: checked on the host), what lean_step_kernel relies on
-  bool lin_neg = false;        // ... bit for bit, signed zeros included (device assembly: contacts only, note_kinds)
-  bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
-  int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
-  int last_linsym = 0;         // the last tile launch used step_solve_kernel's LINSYM form
-  int last_fused = 0;          // ... and assembled the system in its prologue (egs_problem_step: fused_assembly_applies)
-  const AssembleArgs *fused_asm = nullptr;   // set by egs_problem_step for the next launch: assemble in its prologue
   int oversize = 2;            // OversizeSchedule
   int global_max_blocks = 1;
   DevBuf<LaneDesc> q_lanes;
@@ -368,11 +358,9 @@ void ensure_minv_real(egs_problem *p) {
 // Once per M^-1 upload or topology change (4 bytes back): may the fp64 isotropic timetable sweep keep one linear block
 // for both sides (step_solve.hip: LINSYM)?  The body half of the preconditions -- every constraint has a body on
 // side 1, and where it has one on side 0 as well, the same linear weight -- is decided here, on the device; the
-// Jacobian half (lin_neg) where the blocks are made.  EGS_ISO_LINSYM=0 disables the form.
+// Jacobian half (lin_neg) where the blocks are made.
 void decide_linsym_bodies(egs_problem *p) {
   p->linsym_bodies = 0;
-  const char *le = std::getenv("EGS_ISO_LINSYM");
-  if (le && std::atoi(le) == 0) return;
   if (p->precision != EGS_F64 || !p->minv_iso || p->m <= 0) return;
   hipStream_t s = p->ctx->stream;
   int one = 1, flag = 0;
@@ -420,139 +408,162 @@ void record_kernel_event(egs_context *ctx, bool begin) {
 
 void ensure_tile_plan(egs_problem *p);
 
-// SolveArgs::iso of a launch on the tile plan (quad = false) or the 4-lane plan
-int tile_iso(const egs_problem *p, bool quad, int method, int sweeps) {
-  int iso = (p->minv_iso && !quad && p->plan.block == 256 && iso_schedule_pays(p->m, p->ctx->cu_count, p->precision)) ? 1 : 0;
-  // the ticket kernel's isotropic variant has no registers to spare for the snapshots; the timetable
-  // kernel has an instantiation of its own for them
-  if (p->hist_sweeps > 0 && !(method != EGS_JACOBI && !quad && use_static_timetable(p->plan, sweeps))) iso = 0;
-  const char *ie = std::getenv("EGS_ISO");   // 2: force the variant wherever the bodies allow it (experiments)
-  if (ie && std::atoi(ie) == 2 && p->minv_iso && !quad && p->plan.block == 256 &&
-      (p->hist_sweeps == 0 || (method != EGS_JACOBI && use_static_timetable(p->plan, sweeps)))) iso = 1;
-  return iso;
+// Which kernels one solve launch runs.  Every policy switch of the sweep is read here, once per launch (tests change
+// them between calls in one process), and nowhere else; launch_solve_t dispatches on the answer.
+struct SweepSchedule {
+  bool quad = false;        // 4 lanes per constraint (planq) instead of 1 (plan)
+  bool timetable = false;   // the plan's static timetable (step_solve.hip, quad_solve.hip) instead of tickets
+  int iso = 0;              // SolveArgs::iso: the isotropic-body variant of the 1-lane tile kernels
+  int group = 1;            // tiles per workgroup of step_solve_kernel
+  bool linsym = false;      // step_solve_kernel's LINSYM form
+  bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
+  int oversize = -1;        // OversizeSchedule of the launch's oversize islands, -1: it has none
+  // the bits of the kernels that ran (egs_schedule_flags); fill_stats adds those of the problem's plans
+  uint32_t flags() const {
+    return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
+           (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0);
+  }
+};
+
+// hist: the launch records per-sweep snapshots; resume: it continues the previous launch; offer_assembly: the caller
+// has not assembled the system and hands the assembly to the launch if its kernel can take it.
+SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bool resume, bool offer_assembly) {
+  SweepSchedule s;
+  s.quad = p->use_quad && method != EGS_JACOBI;
+  if (!s.quad) ensure_tile_plan(p);
+  const Plan &pl = s.quad ? p->planq : p->plan;
+  const char *se = std::getenv("EGS_STEP");   // 0 / 1: tickets / the timetable wherever the plan has levels
+  s.timetable = method != EGS_JACOBI && pl.levels_ok && pl.n_tiles > 0 && (se ? std::atoi(se) != 0 : timetable_pays(pl, sweeps));
+  if (s.quad) return s;
+  if (!pl.global.empty()) s.oversize = method == EGS_JACOBI ? kAllGlobal : p->oversize;
+  if (pl.n_tiles > 0 && p->minv_iso && pl.block == 256) {
+    const char *ie = std::getenv("EGS_ISO");   // 2: the variant wherever the bodies allow it (experiments)
+    // the ticket kernel's isotropic variant has no registers to spare for the snapshots; the timetable kernel has an
+    // instantiation of its own for them
+    s.iso = (!hist || s.timetable) && ((ie && std::atoi(ie) == 2) || iso_schedule_pays(p->m, p->ctx->cu_count, p->precision));
+  }
+  if (!s.timetable || !s.iso || hist) return s;
+  // The CU holds three fp64 (168 VGPRs) resp. four fp32 (128) isotropic tiles.  Walking them on one clock pays for
+  // the four fp32 tiles (C4: 0.281 ms against 0.368); with three fp64 tiles the 12-wavefront barrier costs more than
+  // the collisions it avoids (C3 x 24: 1.06 ms against 0.95), so fp64 keeps GROUP = 1.  EGS_STEP_GROUP=k forces k.
+  const bool f32 = p->precision == EGS_F32;
+  const char *ge = std::getenv("EGS_STEP_GROUP");
+  const int g = ge && std::atoi(ge) >= 1 ? std::atoi(ge) : f32 ? 4 : 1;
+  s.group = f32 ? (g >= 4 ? 4 : g >= 2 ? 2 : 1) : (g >= 3 ? 3 : 1);
+  // one linear block for both sides (step_solve.hip: LINSYM); EGS_ISO_LINSYM=0 disables the form
+  const char *le = std::getenv("EGS_ISO_LINSYM");
+  s.linsym = !f32 && s.group == 1 && p->lin_neg && p->linsym_bodies == 1 && !(le && std::atoi(le) == 0);
+  // ... with the assembly in its prologue: a fresh launch in which every constraint is a lane of some tile.
+  // EGS_FUSED_ASSEMBLY=0 keeps assemble_kernel.
+  const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
+  s.assemble = offer_assembly && s.linsym && !resume && pl.global.empty() && !(fe && std::atoi(fe) == 0);
+  return s;
+}
+
+// The problem's system, solution and accumulators as the solve and residual kernels read them (kernels.h); hist: the
+// per-sweep snapshots too.  The plan's fields are the launch's.
+template <typename REAL>
+SolveArgs<REAL> solve_args(const egs_problem *p, REAL cfm, bool hist) {
+  SolveArgs<REAL> a{};
+  a.body0 = p->body0.p; a.body1 = p->body1.p; a.m = p->m; a.n_bodies = p->n;
+  a.Minv = reinterpret_cast<const REAL *>(p->Minv_r.p);
+  a.J0 = reinterpret_cast<const REAL *>(p->J0.p); a.J1 = reinterpret_cast<const REAL *>(p->J1.p);
+  a.is_eq = p->is_eq.p;
+  a.lo = reinterpret_cast<const REAL *>(p->lo.p); a.hi = reinterpret_cast<const REAL *>(p->hi.p);
+  a.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
+  a.x = reinterpret_cast<REAL *>(p->x.p); a.acc = reinterpret_cast<REAL *>(p->acc.p);
+  a.wres = reinterpret_cast<REAL *>(p->wres.p);
+  a.error_flag = p->error_flag.p;
+  a.cfm = cfm; a.spin_limit = spin_limit();
+  if (hist) { a.hist_x = reinterpret_cast<REAL *>(p->hist_x.p); a.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p); }
+  return a;
+}
+
+// ... and as the all-global kernels read them, on the tile plan's oversize islands
+template <typename REAL>
+GlobalArgs<REAL> global_args(const egs_problem *p, REAL cfm, bool hist) {
+  GlobalArgs<REAL> g{};
+  g.cons = p->gcons.p; g.mg = (int)p->plan.global.size(); g.per_lane = 1;
+  g.n_bodies = p->n; g.m = p->m;
+  g.Minv = reinterpret_cast<const REAL *>(p->Minv_r.p);
+  g.J0 = reinterpret_cast<const REAL *>(p->J0.p); g.J1 = reinterpret_cast<const REAL *>(p->J1.p);
+  g.is_eq = p->is_eq.p;
+  g.lo = reinterpret_cast<const REAL *>(p->lo.p); g.hi = reinterpret_cast<const REAL *>(p->hi.p);
+  g.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
+  g.x = reinterpret_cast<REAL *>(p->x.p); g.acc = reinterpret_cast<REAL *>(p->acc.p);
+  g.wres = reinterpret_cast<REAL *>(p->wres.p);
+  g.B0 = reinterpret_cast<REAL *>(p->gB0.p); g.B1 = reinterpret_cast<REAL *>(p->gB1.p);
+  g.D = reinterpret_cast<REAL *>(p->gD.p); g.den = reinterpret_cast<REAL *>(p->gden.p);
+  g.dx = reinterpret_cast<REAL *>(p->gdx.p);
+  g.tickets = p->gtickets.p;
+  g.error_flag = p->error_flag.p;
+  g.cfm = cfm; g.spin_limit = spin_limit();
+  if (hist) { g.hist_x = reinterpret_cast<REAL *>(p->hist_x.p); g.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p); }
+  return g;
 }
 
 template <typename REAL>
-void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweeps, int resume) {
+void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweeps, int resume, const AssembleArgs *assemble) {
   egs_context *ctx = p->ctx;
-  const bool quad = p->use_quad && method != EGS_JACOBI;
-  p->last_static = 0;
-  if (!quad) ensure_tile_plan(p);
-  const bool patch = !quad && method != EGS_JACOBI && p->plan.n_patch_tiles > 0 && p->oversize != kAllGlobal;
+  const bool hist = p->hist_sweeps > 0;
+  const SweepSchedule sc = choose_sweep(p, method, sweeps, hist, resume, assemble != nullptr);
+  if (assemble && !sc.assemble)   // egs_problem_step asked choose_sweep for this launch before it skipped assemble_kernel
+    throw std::logic_error("fused assembly offered to a launch that does not take it");
+  p->last_sched = sc.flags();
   record_kernel_event(ctx, true);
   // oversize islands accumulate in global memory (all bodies on the all-global kernel, shared
   // bodies of patches): from zero, unless this launch continues the previous one
-  if (!quad && !p->plan.global.empty() && !resume)
+  if (sc.oversize >= 0 && !resume)
     HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * sizeof(REAL), ctx->stream));
-  if (quad || p->plan.n_tiles > 0) {
-    SolveArgs<REAL> a;
-    a.lanes = quad ? p->q_lanes.p : p->lanes.p;
-    a.tile_nslots = quad ? p->q_tile_nslots.p : p->tile_nslots.p;
-    a.tile_slot_off = quad ? p->q_tile_slot_off.p : p->tile_slot_off.p;
-    a.slot_body = quad ? p->q_slot_body.p : p->slot_body.p;
+  if (sc.quad || p->plan.n_tiles > 0) {
+    SolveArgs<REAL> a = solve_args(p, cfm, hist);
+    a.lanes = sc.quad ? p->q_lanes.p : p->lanes.p;
+    a.tile_nslots = sc.quad ? p->q_tile_nslots.p : p->tile_nslots.p;
+    a.tile_slot_off = sc.quad ? p->q_tile_slot_off.p : p->tile_slot_off.p;
+    a.slot_body = sc.quad ? p->q_slot_body.p : p->slot_body.p;
     a.wsB0 = reinterpret_cast<REAL *>(p->wsB0.p); a.wsB1 = reinterpret_cast<REAL *>(p->wsB1.p);
     a.wsD = reinterpret_cast<REAL *>(p->wsD.p); a.wsInv = reinterpret_cast<REAL *>(p->wsInv.p);
-    a.body0 = p->body0.p; a.body1 = p->body1.p; a.m = p->m;
-    a.Minv = reinterpret_cast<const REAL *>(p->Minv_r.p);
-    a.J0 = reinterpret_cast<const REAL *>(p->J0.p);
-    a.J1 = reinterpret_cast<const REAL *>(p->J1.p);
-    a.is_eq = p->is_eq.p;
-    a.lo = reinterpret_cast<const REAL *>(p->lo.p);
-    a.hi = reinterpret_cast<const REAL *>(p->hi.p);
-    a.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
-    a.x = reinterpret_cast<REAL *>(p->x.p);
-    a.acc = reinterpret_cast<REAL *>(p->acc.p);
-    a.wres = reinterpret_cast<REAL *>(p->wres.p);
-    a.error_flag = p->error_flag.p;
-    a.cfm = cfm;
     a.kscale = kscale;
     a.sweeps = sweeps;
     a.resume = resume;
-    a.max_slots = quad ? p->planq.max_slots : p->plan.max_slots;
-    a.spin_limit = spin_limit();
-    a.iso = tile_iso(p, quad, method, sweeps);
-    a.n_bodies = p->n;
-    if (p->hist_sweeps > 0) {
-      a.hist_x = reinterpret_cast<REAL *>(p->hist_x.p);
-      a.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p);
-    }
-    p->last_iso = quad ? 0 : a.iso;
-    p->last_lean = 0;
-    p->last_linsym = 0;
-    p->last_fused = 0;
-    if (quad) {
+    a.max_slots = sc.quad ? p->planq.max_slots : p->plan.max_slots;
+    a.iso = sc.iso;
+    a.linsym = sc.linsym;
+    if (sc.quad) {
       launch_cons_prepare<REAL>(a, ctx->stream);
-      if (use_static_timetable(p->planq, sweeps)) {
+      if (sc.timetable) {
         a.lane_level = p->q_lane_level.p; a.tile_period = p->q_tile_period.p; a.tile_depth = p->q_tile_depth.p;
         a.runs = p->planq.runs ? 1 : 0;
         launch_step_quad<REAL>(a, method, p->planq.n_tiles, p->planq.block, ctx->stream);
-        p->last_static = 1;
       } else {
         launch_quad_solve<REAL>(a, method, p->planq.n_tiles, p->planq.block, ctx->stream);
-        p->last_static = 0;
       }
-    } else if (method != EGS_JACOBI && use_static_timetable(p->plan, sweeps)) {
+    } else if (sc.timetable) {
       a.lane_level = p->lane_level.p; a.tile_period = p->tile_period.p; a.tile_depth = p->tile_depth.p;
       a.runs = p->plan.runs ? 1 : 0;
-      bool lean = false;
-      if constexpr (sizeof(REAL) == 8) {
-        // the 128-VGPR form (lean_solve.hip): an experiment switch, off by default -- measured on MI355X it buys residency
-        // (1024 instead of 768 constraints per CU) with a longer update and ends level with the 164-VGPR kernel
-        // (DESIGN.md section 5); EGS_LEAN=1 selects it wherever its preconditions hold.  Never for the
-        // snapshot-recording launches of the stopping loop.
-        const char *le = std::getenv("EGS_LEAN");
-        lean = !p->fused_asm && le && std::atoi(le) != 0 && p->minv_iso && (p->plan.block == 256 || p->plan.block == 512) && p->lin_antisym &&
-               a.hist_x == nullptr && !a.runs;
-        if (lean) { a.iso = 1; launch_lean_solve(a, method, p->plan.n_tiles, p->plan.block, ctx->stream); p->last_iso = 1; }
-      }
-      if (!lean) {
-        // one linear block for both sides (step_solve.hip: LINSYM): fp64 isotropic sweep, not for the snapshots
+      if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
-          a.linsym = (a.iso && a.hist_x == nullptr && p->lin_neg && p->linsym_bodies == 1) ? 1 : 0;
-          if (p->fused_asm) {   // ... with the assembly in its prologue (egs_problem_step, fused_assembly_applies)
-            if (resume || !a.linsym || !step_solve_takes_linsym(a, p->plan.block))
-              throw std::logic_error("fused assembly chosen for a launch that is not a fresh LINSYM launch");
-            a.assemble = *p->fused_asm;
-            p->fused_asm = nullptr;
-            launch_step_solve_assemble(a, method, p->plan.n_tiles, ctx->stream);
-            p->last_linsym = p->last_fused = 1;
-          }
+          a.assemble = *assemble;
+          launch_step_solve_assemble(a, method, p->plan.n_tiles, ctx->stream);
         }
-        if (!p->last_fused)
-          p->last_linsym = launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream) ? 1 : 0;
+      } else {
+        launch_step_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, sc.group, sc.linsym, ctx->stream);
       }
-      p->last_static = 1;
-      p->last_lean = lean ? 1 : 0;
     } else {
       launch_tile_solve<REAL>(a, method, p->plan.n_tiles, p->plan.block, ctx->stream);
-      p->last_static = 0;
     }
   }
+  const bool patch = sc.oversize == kQuadPatches || sc.oversize == kLanePatches;
   if (patch && p->plan.block != 256)   // patch lanes are laid out for 256-thread workgroups
     throw std::logic_error("patch schedule built with a tile size other than 256");
   if (patch) {
-    SolveArgs<REAL> a;
+    SolveArgs<REAL> a = solve_args(p, cfm, hist);
     a.lanes = p->p_lanes.p; a.tile_nslots = p->p_tile_nslots.p; a.tile_slot_off = p->p_tile_slot_off.p;
     a.slot_body = p->p_slot_body.p;
-    a.wsB0 = a.wsB1 = a.wsD = a.wsInv = nullptr;
-    a.body0 = p->body0.p; a.body1 = p->body1.p; a.m = p->m;
-    a.Minv = reinterpret_cast<const REAL *>(p->Minv_r.p);
-    a.J0 = reinterpret_cast<const REAL *>(p->J0.p); a.J1 = reinterpret_cast<const REAL *>(p->J1.p);
-    a.is_eq = p->is_eq.p;
-    a.lo = reinterpret_cast<const REAL *>(p->lo.p); a.hi = reinterpret_cast<const REAL *>(p->hi.p);
-    a.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
-    a.x = reinterpret_cast<REAL *>(p->x.p); a.acc = reinterpret_cast<REAL *>(p->acc.p);
-    a.wres = reinterpret_cast<REAL *>(p->wres.p);
-    a.error_flag = p->error_flag.p;
-    a.cfm = cfm; a.kscale = kscale; a.sweeps = sweeps; a.resume = resume;
-    a.max_slots = p->plan.patch_max_slots; a.spin_limit = spin_limit();
+    a.kscale = kscale; a.sweeps = sweeps; a.resume = resume;
+    a.max_slots = p->plan.patch_max_slots;
     HIPCHK(hipMemsetAsync(p->gtickets.p, 0, sizeof(uint32_t) * (size_t)(p->n > 0 ? p->n : 1), ctx->stream));
-    a.n_bodies = p->n;
-    if (p->hist_sweeps > 0) {
-      a.hist_x = reinterpret_cast<REAL *>(p->hist_x.p);
-      a.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p);
-    }
-    if (p->oversize == kQuadPatches) {
+    if (sc.oversize == kQuadPatches) {
       {   // hand-offs between patches as data-tagged granules (EGS_GRANULES=0: payload + flag, the round-2 protocol)
         const char *ge = std::getenv("EGS_GRANULES");
         if (!(ge && std::atoi(ge) == 0)) {
@@ -585,56 +596,27 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     } else {
       launch_patch_solve<REAL>(a, method, p->plan.n_patch_tiles, p->gtickets.p, ctx->stream);
     }
-    GlobalArgs<REAL> g{};
-    g.cons = p->gcons.p; g.mg = (int)p->plan.global.size();
-    g.J0 = a.J0; g.J1 = a.J1; g.rhs = a.rhs; g.x = a.x; g.acc = a.acc; g.wres = a.wres; g.cfm = cfm;
-    launch_global_wres<REAL>(g, ctx->stream);
-  } else if (!quad && !p->plan.global.empty()) {
-    GlobalArgs<REAL> g;
-    g.cons = p->gcons.p;
-    g.mg = (int)p->plan.global.size();
-    g.n_bodies = p->n; g.pad0 = 0; g.per_lane = 1; g.mode = 0;
-    g.B0 = reinterpret_cast<REAL *>(p->gB0.p); g.B1 = reinterpret_cast<REAL *>(p->gB1.p);
-    g.D = reinterpret_cast<REAL *>(p->gD.p); g.den = reinterpret_cast<REAL *>(p->gden.p);
-    g.dx = reinterpret_cast<REAL *>(p->gdx.p);
-    g.Minv = reinterpret_cast<const REAL *>(p->Minv_r.p);
-    g.J0 = reinterpret_cast<const REAL *>(p->J0.p);
-    g.J1 = reinterpret_cast<const REAL *>(p->J1.p);
-    g.is_eq = p->is_eq.p;
-    g.lo = reinterpret_cast<const REAL *>(p->lo.p);
-    g.hi = reinterpret_cast<const REAL *>(p->hi.p);
-    g.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
-    g.x = reinterpret_cast<REAL *>(p->x.p);
-    g.acc = reinterpret_cast<REAL *>(p->acc.p);
-    g.wres = reinterpret_cast<REAL *>(p->wres.p);
-    g.tickets = p->gtickets.p;
-    g.error_flag = p->error_flag.p;
-    g.cfm = cfm;
+    launch_global_wres<REAL>(global_args(p, cfm, false), ctx->stream);
+  } else if (sc.oversize == kAllGlobal) {
+    GlobalArgs<REAL> g = global_args(p, cfm, hist && method != EGS_JACOBI);
     g.kscale = kscale;
     g.sweeps = sweeps;
     g.resume = resume;
     g.method = method;
-    g.spin_limit = spin_limit();
-    g.m = p->m;
-    if (p->hist_sweeps > 0 && method != EGS_JACOBI) {
-      g.hist_x = reinterpret_cast<REAL *>(p->hist_x.p);
-      g.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p);
-    }
     launch_global_solve<REAL>(g, p->global_max_blocks, ctx->stream);
   }
   record_kernel_event(ctx, false);
   HIPCHK(hipGetLastError());
-  if (p->fused_asm) throw std::logic_error("fused assembly chosen, but the launch did not take it");
 }
 
-void launch_solve(egs_problem *p, const egs_solve_params &prm, int sweeps, int resume) {
+void launch_solve(egs_problem *p, const egs_solve_params &prm, int sweeps, int resume, const AssembleArgs *assemble = nullptr) {
   ensure_minv_real(p);
   if (p->precision == EGS_F32) {
     const float ks = prm.method == EGS_SOR ? 1.0f / (float)prm.omega : 1.0f;
-    launch_solve_t<float>(p, prm.method, (float)prm.cfm, ks, sweeps, resume);
+    launch_solve_t<float>(p, prm.method, (float)prm.cfm, ks, sweeps, resume, assemble);
   } else {
     const double ks = prm.method == EGS_SOR ? 1.0 / prm.omega : 1.0;
-    launch_solve_t<double>(p, prm.method, prm.cfm, ks, sweeps, resume);
+    launch_solve_t<double>(p, prm.method, prm.cfm, ks, sweeps, resume, assemble);
   }
 }
 
@@ -687,23 +669,10 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_tiles = pl.n_tiles;
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
-  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_iso ? EGS_SCHED_ISO : 0) | (p->last_static ? EGS_SCHED_STATIC : 0) | (p->last_lean ? EGS_SCHED_LEAN : 0) |
-                (p->last_linsym ? EGS_SCHED_LINSYM : 0) | (p->last_fused ? EGS_SCHED_FUSED_ASSEMBLY : 0);
+  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | p->last_sched;
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;
-}
-
-template <typename REAL>
-void fill_history_args(egs_problem *p, SolveArgs<REAL> &a, REAL cfm) {
-  a.J0 = reinterpret_cast<const REAL *>(p->J0.p); a.J1 = reinterpret_cast<const REAL *>(p->J1.p);
-  a.body0 = p->body0.p; a.body1 = p->body1.p;
-  a.is_eq = p->is_eq.p;
-  a.lo = reinterpret_cast<const REAL *>(p->lo.p); a.hi = reinterpret_cast<const REAL *>(p->hi.p);
-  a.rhs = reinterpret_cast<const REAL *>(p->rhs.p);
-  a.wres = reinterpret_cast<REAL *>(p->wres.p);
-  a.hist_x = reinterpret_cast<REAL *>(p->hist_x.p); a.hist_acc = reinterpret_cast<REAL *>(p->hist_acc.p);
-  a.m = p->m; a.n_bodies = p->n; a.cfm = cfm;
 }
 
 // ---- the stopping loop's schedule (tol > 0), shared by do_solve and do_solve_batch ----------------
@@ -765,8 +734,9 @@ int fixed_chunk_max(const Plan &pl_used) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(by_ticket, by_clock), 0x7fffffff));
 }
 
-// The solve driver: sparse_iterations.cc:148-226.
-egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats) {
+// The solve driver: sparse_iterations.cc:148-226.  assemble: egs_problem_step hands the assembly to the first launch
+// (step_fuses_assembly).
+egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats, const AssembleArgs *assemble = nullptr) {
   egs_context *ctx = p->ctx;
   if (egs_status st = validate_params(ctx, prm)) return st;
   if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
@@ -787,7 +757,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     int done = 0;
     do {
       const int chunk = std::min(chunk_max, prm->max_iters - done);
-      launch_solve(p, *prm, chunk, done > 0 ? 1 : 0);
+      launch_solve(p, *prm, chunk, done > 0 ? 1 : 0, done > 0 ? nullptr : assemble);
       done += chunk;
     } while (done < prm->max_iters);
     p->last_iterations = prm->max_iters;
@@ -847,15 +817,10 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
       launch_solve(p, *prm, chunk, 1);
       p->hist_sweeps = 0;
       auto residual_pass = [&](int write_sweep) {
-        if (p->precision == EGS_F32) {
-          SolveArgs<float> a{};
-          fill_history_args(p, a, (float)prm->cfm);
-          launch_hist_residual<float>(a, chunk, kResidualBlocks, p->hist_out.p, write_sweep, ctx->stream);
-        } else {
-          SolveArgs<double> a{};
-          fill_history_args(p, a, prm->cfm);
-          launch_hist_residual<double>(a, chunk, kResidualBlocks, p->hist_out.p, write_sweep, ctx->stream);
-        }
+        if (p->precision == EGS_F32)
+          launch_hist_residual<float>(solve_args(p, (float)prm->cfm, true), chunk, kResidualBlocks, p->hist_out.p, write_sweep, ctx->stream);
+        else
+          launch_hist_residual<double>(solve_args(p, prm->cfm, true), chunk, kResidualBlocks, p->hist_out.p, write_sweep, ctx->stream);
       };
       residual_pass(0);
       HIPCHK(hipMemcpyAsync(part, p->hist_out.p, (size_t)chunk * kResidualBlocks * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -968,9 +933,7 @@ struct BatchSolveState {
 template <typename REAL>
 void batch_residual(egs_problem *p, BatchSolveState &B, double cfm, const int32_t *running, const void *xs, const void *as,
                     const void *ws, int sweeps) {
-  SolveArgs<REAL> a{};
-  fill_history_args(p, a, (REAL)cfm);
-  launch_seg_residual<REAL>(a, B.segs, running, static_cast<const REAL *>(xs), static_cast<const REAL *>(as),
+  launch_seg_residual<REAL>(solve_args(p, (REAL)cfm, true), B.segs, running, static_cast<const REAL *>(xs), static_cast<const REAL *>(as),
                             static_cast<const REAL *>(ws), sweeps, B.err.p, p->ctx->stream);
 }
 
@@ -1106,8 +1069,7 @@ AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
 // what the device assembly tells about the blocks it makes
 void note_assembled(egs_problem *p) {
   p->have_blocks = true;
-  p->lin_antisym = true;     // joints.cc:17-31 and contact.cc:66-99 build [X, ..] / [-X, ..]
-  p->lin_neg = !p->joint_pairs;
+  p->lin_neg = !p->joint_pairs;   // contact.cc:66-99 builds [-Rn, ..] / [Rn, ..]; two-body ball joints: note_kinds
 }
 
 void do_assemble(egs_problem *p, double dt, double erp) {
@@ -1119,32 +1081,12 @@ void do_assemble(egs_problem *p, double dt, double erp) {
 }
 
 // egs_problem_step assembles in the prologue of the solve launch (step_solve.hip: ASSEMBLE) exactly when do_solve is
-// about to make ONE launch of the LINSYM timetable kernel: fp64, a fixed sweep count in one chunk, GS or SOR on the
-// 1-lane tile plan with every constraint in a tile (no oversize islands), the isotropic variant and LINSYM's
-// preconditions for assembled blocks (no two-body ball joint, equal linear weights).  Anything else -- tol > 0, fp32,
-// mixed masses, ball joints between bodies, the 4-lane or lean kernels -- keeps assemble_kernel.  launch_solve_t
-// checks the choice again at the launch.  EGS_FUSED_ASSEMBLY=0 disables the fused form.
-bool fused_assembly_applies(egs_problem *p, const egs_solve_params *prm) {
-  const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
-  if (fe && std::atoi(fe) == 0) return false;
-  if (p->precision != EGS_F64 || p->m <= 0 || p->joint_pairs) return false;
-  if (!prm || prm->tol > 0 || !(prm->method == EGS_GAUSS_SEIDEL || prm->method == EGS_SOR)) return false;
-  if (prm->method == EGS_SOR && !(prm->omega > 0 && prm->omega < 2)) return false;   // do_solve refuses it
-  if (prm->max_iters < 0) return false;
-  const char *le = std::getenv("EGS_LEAN");
-  if (le && std::atoi(le) != 0) return false;
+// about to make ONE launch -- a fixed sweep count in one chunk -- and choose_sweep hands that launch the assembly.
+// Anything else -- tol > 0, invalid parameters, more sweeps than one launch takes -- keeps assemble_kernel.
+bool step_fuses_assembly(egs_problem *p, const egs_solve_params *prm) {
+  if (p->m <= 0 || validate_params(nullptr, prm) != EGS_OK || prm->tol > 0) return false;
   ensure_minv_real(p);   // what do_solve does first: isotropy, LINSYM's body check, hence the tile plan
-  if (p->use_quad) return false;
-  ensure_tile_plan(p);
-  const Plan &pl = p->plan;
-  if (pl.n_tiles <= 0 || !pl.global.empty() || pl.n_patch_tiles > 0 || pl.block != 256) return false;
-  if (p->hist_sweeps != 0 || prm->max_iters > fixed_chunk_max(pl) || !use_static_timetable(pl, prm->max_iters)) return false;
-  if (p->linsym_bodies != 1) return false;
-  SolveArgs<double> a;
-  a.iso = tile_iso(p, false, prm->method, prm->max_iters);
-  a.hist_x = nullptr;
-  a.linsym = a.iso;
-  return step_solve_takes_linsym(a, pl.block);
+  return choose_sweep(p, prm->method, prm->max_iters, false, false, true).assemble && prm->max_iters <= fixed_chunk_max(p->plan);
 }
 
 void do_velocity(egs_problem *p, double dt) {
@@ -1612,20 +1554,18 @@ egs_status egs_problem_set_blocks(egs_problem *p, const double *Minv, const doub
     upload_real(p, p->J0, J0, m * 18);
     upload_real(p, p->J1, J1, m * 18);
     if (J0 || J1) {
-      // lean_step_kernel keeps ONE linear block per constraint: allowed only if J1_lin = -J0_lin wherever both sides exist
-      bool anti = J0 && J1 && p->precision == EGS_F64 && p->h_body0.size() == m && p->h_body1.size() == m;
-      bool neg = anti;   // step_solve_kernel's LINSYM form: the same, bit for bit
-      for (size_t i = 0; anti && i < m; ++i) {
+      // step_solve_kernel's LINSYM form keeps ONE linear block per constraint: J1_lin = -J0_lin wherever both sides
+      // exist, equal in value (a NaN refuses it) and bit for bit
+      bool neg = J0 && J1 && p->precision == EGS_F64 && p->h_body0.size() == m && p->h_body1.size() == m;
+      for (size_t i = 0; neg && i < m; ++i) {
         if (p->h_body0[i] < 0 || p->h_body1[i] < 0) continue;
-        for (int r = 0; r < 3 && anti; ++r)
-          for (int k = 0; k < 3; ++k) {
+        for (int r = 0; r < 3 && neg; ++r)
+          for (int k = 0; k < 3 && neg; ++k) {
             const double a = J0[i * 18 + 6 * r + k], b = -J1[i * 18 + 6 * r + k];
-            if (!(a == b)) { anti = false; break; }
-            neg = neg && std::memcmp(&a, &b, sizeof a) == 0;
+            neg = a == b && std::memcmp(&a, &b, sizeof a) == 0;
           }
       }
-      p->lin_antisym = anti;
-      p->lin_neg = anti && neg;
+      p->lin_neg = neg;
     }
     if (is_eq && m) upload(p->is_eq, is_eq, m * 3, p->ctx->stream);
     upload_real(p, p->lo, lo, m * 3);
@@ -1721,19 +1661,15 @@ egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_sol
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
   return guarded(p->ctx, [&]() -> egs_status {
     if (stall_seen(p)) return report_stall(p);   // an earlier (asynchronous) step timed out
-    AssembleArgs fa;
-    struct Pending {   // the fused assembly is offered to this step's solve launch only
-      egs_problem *p;
-      ~Pending() { p->fused_asm = nullptr; }
-    } pending{p};
-    if (fused_assembly_applies(p, params)) {
-      fa = assemble_args(p, dt, erp);
-      note_assembled(p);
-      p->fused_asm = &fa;
+    note_assembled(p);   // what choose_sweep reads of the blocks this step makes
+    egs_status st;
+    if (step_fuses_assembly(p, params)) {
+      const AssembleArgs a = assemble_args(p, dt, erp);
+      st = do_solve(p, params, stats, &a);
     } else {
       do_assemble(p, dt, erp);
+      st = do_solve(p, params, stats);
     }
-    egs_status st = do_solve(p, params, stats);
     if (st != EGS_OK) return st;
     do_velocity(p, dt);
     return EGS_OK;

@@ -100,17 +100,15 @@ void launch_mass_times_force(int n, const double *Minv, const double *f_ext, dou
 template <typename REAL>
 void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
                        int block, hipStream_t s);
-// the same GS / SOR sweep on the plan's static timetable: one workgroup barrier per time step, no tickets
+// the same GS / SOR sweep on the plan's static timetable: one workgroup barrier per time step, no tickets.  With
+// a.iso on 256-constraint tiles: `group` tiles per workgroup (fp32: 1, 2 or 4; fp64: 1 or 3) and, fp64 with group 1,
+// the LINSYM form if `linsym`; the per-sweep snapshots (a.hist_x) always take group 1 without LINSYM.  The caller
+// decides both (capi.cpp: choose_sweep).
 template <typename REAL>
-bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s);   // true: LINSYM form ran
-// would launch_step_solve<double> take the LINSYM form for these arguments?
-bool step_solve_takes_linsym(const SolveArgs<double> &a, int block);
-// the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles): assemble_kernel
-// and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit
+void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, int group, bool linsym, hipStream_t s);
+// the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles, no snapshots):
+// assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit
 void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s);
-// the same timetable in 128 VGPRs (lean_solve.hip): fp64, isotropic bodies, 256-constraint tiles, J1_lin = -J0_lin
-void launch_lean_solve(const SolveArgs<double> &a, int method, int n_tiles, int block, hipStream_t s);
-int occupancy_lean_solve(int block, int max_slots);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);

@@ -39,7 +39,6 @@
 // timetable runs.  Every constraint of the problem is a lane of some tile (capi.cpp: no oversize islands), so all of
 // them are written.
 #include <algorithm>
-#include <stdexcept>
 
 #include "kernels.h"
 #include "solve_device.h"
@@ -277,18 +276,11 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   }
 }
 
-int step_group_env(int dflt) {
-  const char *e = std::getenv("EGS_STEP_GROUP");
-  if (!e) return dflt;
-  const int g = std::atoi(e);
-  return g >= 1 ? g : dflt;
-}
-
 }  // namespace
 
 template <typename REAL>
-bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, hipStream_t s) {
-  if (n_tiles <= 0) return false;
+void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, int group, bool linsym, hipStream_t s) {
+  if (n_tiles <= 0) return;
   SolveArgs<REAL> b = a;
   b.n_tiles = n_tiles;
 #define EGS_LAUNCH_S(BLK, ISO, GRP) EGS_LAUNCH_SH(BLK, ISO, GRP, !ISO, false)
@@ -306,21 +298,14 @@ bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
     else hipLaunchKernelGGL(k2, g, t, lds, s, b);                                                              \
   }
   if (block == 256 && a.iso) {
-    // the CU holds three fp64 (168 VGPRs) resp. four fp32 (128) isotropic tiles.  Walking them on one clock
-    // pays for the four fp32 tiles (C4: 0.281 ms against 0.368); with three fp64 tiles the 12-wavefront
-    // barrier costs more than the collisions it avoids (C3 x 24: 1.06 ms against 0.95), so fp64 keeps GROUP = 1
-    const int grp = step_group_env(sizeof(REAL) == 4 ? 4 : 1);
     if (b.hist_x != nullptr) EGS_LAUNCH_SH(256, true, 1, true, false)      // per-sweep snapshots of the stopping loop (kernels.h)
     else if constexpr (sizeof(REAL) == 4) {
-      if (grp >= 4) EGS_LAUNCH_S(256, true, 4)
-      else if (grp >= 2) EGS_LAUNCH_S(256, true, 2)
+      if (group == 4) EGS_LAUNCH_S(256, true, 4)
+      else if (group == 2) EGS_LAUNCH_S(256, true, 2)
       else EGS_LAUNCH_S(256, true, 1)
     } else {
-      if (grp >= 3) EGS_LAUNCH_S(256, true, 3)
-      else if (b.linsym) {   // one linear block for both sides (LINSYM above)
-        EGS_LAUNCH_SH(256, true, 1, false, true)
-        return true;
-      }
+      if (group == 3) EGS_LAUNCH_S(256, true, 3)
+      else if (linsym) EGS_LAUNCH_SH(256, true, 1, false, true)   // one linear block for both sides (LINSYM above)
       else EGS_LAUNCH_S(256, true, 1)
     }
   }
@@ -330,16 +315,9 @@ bool launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
   else EGS_LAUNCH_S(512, false, 1)
 #undef EGS_LAUNCH_S
 #undef EGS_LAUNCH_SH
-  return false;
-}
-
-bool step_solve_takes_linsym(const SolveArgs<double> &a, int block) {
-  return block == 256 && a.iso && a.hist_x == nullptr && step_group_env(1) < 3 && a.linsym;
 }
 
 void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s) {
-  if (n_tiles <= 0 || a.resume || !step_solve_takes_linsym(a, 256))
-    throw std::logic_error("launch_step_solve_assemble: not a fresh LINSYM launch");
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
   const size_t lds = std::max((size_t)b.max_slots * 6 * sizeof(double), (size_t)4 * kStageWave * sizeof(double));
@@ -351,7 +329,7 @@ void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_ti
   else hipLaunchKernelGGL(k2, dim3(n_tiles), dim3(256), lds, s, b);
 }
 
-template bool launch_step_solve<double>(const SolveArgs<double> &, int, int, int, hipStream_t);
-template bool launch_step_solve<float>(const SolveArgs<float> &, int, int, int, hipStream_t);
+template void launch_step_solve<double>(const SolveArgs<double> &, int, int, int, int, bool, hipStream_t);
+template void launch_step_solve<float>(const SolveArgs<float> &, int, int, int, int, bool, hipStream_t);
 
 }  // namespace egs

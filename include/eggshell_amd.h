@@ -93,8 +93,7 @@ typedef enum {
   EGS_SCHED_ALL_GLOBAL = 16,   /* oversize islands: the all-global kernel */
   EGS_SCHED_STATIC = 32,       /* step_solve_kernel / step_quad_kernel (with EGS_SCHED_QUAD): the plan's sweep on
                                   its static timetable (one workgroup barrier per time step) instead of tickets */
-  EGS_SCHED_LEAN = 64,         /* lean_step_kernel: the timetable sweep in 128 VGPRs (one linear block for both sides,
-                                  constants parked in LDS): four 256-constraint tiles per CU (fp64, isotropic bodies) */
+  EGS_SCHED_LEAN = 64,         /* reserved, never reported: a retired 128-VGPR form of the timetable sweep */
   EGS_SCHED_LINSYM = 128,      /* step_solve_kernel's LINSYM form: the fp64 isotropic timetable sweep with one linear
                                   block for both sides (J1_lin = -J0_lin and equal linear weights, bit for bit) */
   EGS_SCHED_FUSED_ASSEMBLY = 256   /* egs_problem_step assembled the Jacobian in the LINSYM launch's prologue
