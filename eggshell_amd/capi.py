@@ -20,6 +20,7 @@ MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
 SCHED_LINSYM = 128
 SCHED_FUSED_ASSEMBLY = 256
+STABILIZE_INIT, STABILIZE_POST = 0, 1
 
 # every symbol include/eggshell_amd.h declares
 EXPORTS = [
@@ -38,7 +39,7 @@ EXPORTS = [
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
-    "egs_world_step_dense", "egs_world_dense_info",
+    "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
 ]
 
 
@@ -584,6 +585,23 @@ class World:
         cond = np.zeros(E); cfm = np.zeros(E); piv = np.zeros(E, np.int32); ok = np.zeros(E, np.int32)
         self.ctx.check(load().egs_world_dense_info(self.h, C.c_int32(E), _p(cond), _p(cfm), _p(piv), _p(ok)))
         return dict(condition=cond, cfm=cfm, pivots=piv, ok=ok.astype(bool))
+
+    def stabilize(self, mode, max_steps=0, detect_contacts=True, params=None):
+        """Ensemble::InitStabilize (mode STABILIZE_INIT) or PostStabilize(max_steps) (STABILIZE_POST) for every
+        ensemble (egs_world_stabilize); max_steps = 0 is the reference's 100 / 500, params None the adapter's
+        relaxation solve.  Returns how many ensembles ended with err_sq > 1e-9; stabilize_info() has the figures."""
+        nu = C.c_int32(0)
+        self.ctx.check(load().egs_world_stabilize(self.h, C.c_int32(mode), C.c_int32(max_steps),
+                                                  C.c_int32(1 if detect_contacts else 0),
+                                                  C.byref(params) if params is not None else None, C.byref(nu)))
+        return nu.value
+
+    def stabilize_info(self):
+        """Per-ensemble figures of the last stabilize: relaxation steps and the final err_sq [E]."""
+        E = self.n_ensembles
+        steps = np.zeros(E, np.int32); err_sq = np.zeros(E)
+        self.ctx.check(load().egs_world_stabilize_info(self.h, C.c_int32(E), _p(steps), _p(err_sq)))
+        return dict(steps=steps, err_sq=err_sq)
 
     def bodies(self):
         pos = np.zeros((self.n, 3)); R = np.zeros((self.n, 9)); v = np.zeros((self.n, 3)); w = np.zeros((self.n, 3))

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "matvec.h"
 #include "plan.h"
+#include "stabilize.h"
 
 using namespace egs;
 
@@ -966,7 +967,10 @@ int batch_read_running(egs_problem *p, BatchSolveState &B, int *flag) {
 
 // The solve of a batched world: do_solve's loops, each ensemble stopping on its own (sparse_iterations.cc:204-221).
 // Enqueues the copy of the per-ensemble results into B.h_ints / B.h_res; the caller synchronises before reading them.
-egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolveState &B) {
+// active [E] (device, may be NULL): only these ensembles run the stopping test; the others are not checked and no
+// state of theirs is selected (egs_world_stabilize's finished ensembles).  The sweeps still cover every ensemble, as
+// they do for an ensemble that has stopped (section 4c of DESIGN.md); a fixed sweep count ignores active.
+egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolveState &B, const int32_t *active = nullptr) {
   egs_context *ctx = p->ctx;
   hipStream_t s = ctx->stream;
   if (egs_status st = validate_params(ctx, prm)) return st;
@@ -1007,6 +1011,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   launch_solve(p, *prm, 0, 0);
   residual(nullptr, p->x.p, nullptr, p->wres.p, 1);
   batch_select(p, B, prm, 1, 0, 1, 1, p->x.p, 0, p->acc.p, 0);
+  if (active) launch_stab_seed_running(E, active, B.stop().running, B.stop().n_running, s);
   int it = 0, flag = 0;
   // as do_solve: with recorded chunks the count of x0 rides on the first chunk's read-back
   int running = (history && defer_first) ? E : batch_read_running(p, B, &flag);
@@ -2236,6 +2241,22 @@ struct egs_world {
   DenseEnsStatus *h_dn_status = nullptr;
   std::vector<DenseEnsStatus> dn_info;   // [E] of the last dense step
   bool last_dense = false;               // the last step was egs_world_step_dense (batch_info reports its pivots)
+  // egs_world_stabilize, all made on its first call: the relaxation system (the world's topology with M^-1 = I, every
+  // row an equality, rhs = err; re-topologised when the world re-plans), its batched stopping state, and per ensemble
+  // active [E], steps [E], err_sq [E]; a plain world's row offsets jo / co [2] each
+  egs_problem *rx = nullptr;
+  int rx_replans = -1;                   // w->replans rx's topology was set for
+  BatchSolveState rx_batch;
+  DevBuf<int32_t> rx_ints;               // active [E] | steps [E] | n_active | jo [2] | co [2]
+  DevBuf<double> rx_err_sq;              // [E]
+  DevBuf<uint8_t> rx_eq_scratch;         // the assembly's row types, not used (every relaxation row is an equality)
+  int32_t *h_rx = nullptr;               // page-locked (hipHostMalloc, 8 words): n_active, stall flag, jo [2], co [2]
+  // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_stabilize's passes, printed by egs_world_destroy
+  double t_stab[6] = {0, 0, 0, 0, 0, 0};   // detection + world re-plan, relaxation re-topology, assembly + test + count
+                                           // read-back, solve, J^T y + stall check + relaxation step; passes
+  std::vector<int32_t> st_steps;         // [E] of the last egs_world_stabilize (empty: none yet)
+  std::vector<double> st_err_sq;
+  bool lambda_stale = false;             // a stabilise call changed bodies / contacts since the last step's solve
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
   double t_phase[5] = {0, 0, 0, 0, 0};   // collide, topology D2H + compare, re-plan, solve + integrate (enqueue), steps
@@ -2353,6 +2374,54 @@ void world_dense_plan(egs_world *w) {
   w->dense_plan_replans = w->replans;
 }
 
+// The relaxation system of egs_world_stabilize (the solve of CalculateVelocityRelaxation, ensembles.cc:659-666, as the
+// adapter's stabilize.cpp sets it up): the world problem's constraint topology with M^-1 = I, every row an equality
+// and rhs = err.  Made on the first stabilise call, re-topologised only when the world has re-planned since; its plan
+// follows from the identity masses (isotropic: the ISO / LINSYM forms of choose_sweep may apply).
+void world_relax_system(egs_world *w) {
+  if (w->rx && w->rx_replans == w->replans) return;
+  hipStream_t s = w->ctx->stream;
+  const int m = w->prob->m;
+  const int32_t *b0 = w->topo_b0.data(), *b1 = w->topo_b1.data();
+  if (!w->rx) {
+    egs_problem *created = nullptr;
+    if (egs_problem_create(w->ctx, w->n, m, b0, b1, EGS_F64, &created) != EGS_OK)
+      throw HipError(std::string("world: relaxation system: ") + egs_last_error(w->ctx));
+    w->rx = created;
+    std::vector<double> eye((size_t)(w->n > 0 ? w->n : 1) * 36, 0.0);
+    for (int b = 0; b < w->n; ++b)
+      for (int k = 0; k < 6; ++k) eye[(size_t)b * 36 + 7 * k] = 1.0;
+    upload(w->rx->Minv_d, eye.data(), (size_t)w->n * 36, s);
+    w->rx->minv_r_valid = false;   // the first solve converts the blocks and finds them isotropic
+    w->rx->have_state = true;
+  } else {
+    problem_set_topology(w->rx, m, b0, b1, /*fresh=*/false);
+  }
+  egs_problem *rx = w->rx;
+  const size_t rows = (size_t)(m > 0 ? m : 1) * 3;
+  HIPCHK(hipMemsetAsync(rx->is_eq.p, 1, rows, s));
+  w->rx_eq_scratch.alloc(rows);
+  rx->joint_pairs = w->prob->joint_pairs;
+  rx->have_constraints = true;
+  w->rx_replans = w->replans;
+}
+
+// J and err of the world's constraint list at the current body state, the blocks straight into the relaxation
+// system and err as its rhs (the assembly's rhs, lo, hi and row types are not used by the relaxation).
+void world_relax_assemble(egs_world *w) {
+  egs_problem *p = w->prob, *rx = w->rx;
+  AssembleArgs a = assemble_args(p, 1.0, 0.2);
+  a.J0 = rx->J0.p; a.J1 = rx->J1.p;
+  a.lo = rx->lo.p; a.hi = rx->hi.p;   // read by no equality row
+  a.rhs = rx->wres.p;                  // scratch: the solve writes w there
+  a.err = reinterpret_cast<double *>(rx->rhs.p);
+  a.is_eq = w->rx_eq_scratch.p;
+  launch_assemble<double>(a, w->ctx->stream);
+  HIPCHK(hipGetLastError());
+  rx->have_blocks = true;
+  rx->lin_neg = !rx->joint_pairs;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2382,7 +2451,15 @@ void egs_world_destroy(egs_world *w) {
     std::fprintf(stderr, "egs_world trace (%d steps, %d re-plans), us/step: collide %.1f  topology %.1f  re-plan %.1f  solve+integrate %.1f\n",
                  (int)w->t_phase[4], w->replans, w->t_phase[0] * k, w->t_phase[1] * k, w->t_phase[2] * k, w->t_phase[3] * k);
   }
+  if (w->trace && w->t_stab[5] > 0) {
+    const double k = 1.0 / w->t_stab[5];
+    std::fprintf(stderr, "egs_world stabilize trace (%d passes), us/pass: detect+re-plan %.1f  relaxation re-topology %.1f  "
+                 "assemble+test %.1f  solve %.1f  J^T y+relax %.1f\n", (int)w->t_stab[5], w->t_stab[0] * k, w->t_stab[1] * k,
+                 w->t_stab[2] * k, w->t_stab[3] * k, w->t_stab[4] * k);
+  }
   if (w->prob) egs_problem_destroy(w->prob);
+  if (w->rx) egs_problem_destroy(w->rx);
+  if (w->h_rx) (void)hipHostFree(w->h_rx);
   delete w;
 }
 
@@ -2516,6 +2593,7 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
       // wait: look at the flag before integrating (one 4-byte read-back per step)
       HIPCHK(hipStreamSynchronize(s));
       if (stall_seen(p)) return report_stall(p);
+      w->lambda_stale = false;   // x holds this step's lambda for the current list
       if (batched && stats) {   // the slowest ensemble's sweep count and the largest residual
         std::memset(stats, 0, sizeof *stats);
         fill_stats(p, stats);
@@ -2527,6 +2605,7 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
       }
     } else {  // no constraints: v_dot = M^-1 f (ensembles.cc:504-505)
       if (egs_status st = validate_params(w->ctx, params)) return st;
+      w->lambda_stale = false;
       HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * p->real_size(), s));
       if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
       if (batched) {
@@ -2654,6 +2733,7 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
       if (nf > 1) msg += "; " + std::to_string(nf) + " of " + std::to_string(E) + " ensembles failed";
       return fail(w->ctx, EGS_ERR_LCP_FAILED, msg);
     }
+    w->lambda_stale = false;   // every ensemble solved: x holds this step's lambda for the current list
     if (p->m > 0) accumulators_from_lambda(p);                    // a = M^-1 J^T lambda
     else HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * p->real_size(), s));
     do_velocity(p, dt);                                           // ensembles.cc:535, 572
@@ -2702,6 +2782,8 @@ egs_status egs_world_get_contacts(egs_world *w, int32_t max_contacts, int32_t *m
 egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_out, double *lambda) {
   if (!w || !w->prob || !rows_out) return EGS_ERR_INVALID;
   *rows_out = 3 * w->prob->m;
+  if (w->lambda_stale)
+    return fail(w->ctx, EGS_ERR_INVALID, "no step lambda for the constraint list egs_world_stabilize left: step first");
   if (3 * w->prob->m > max_rows) return fail(w->ctx, EGS_ERR_INVALID, "max_rows too small");
   if (w->prob->m == 0) return EGS_OK;
   return egs_problem_get_lambda(w->prob, lambda);
@@ -2742,6 +2824,118 @@ egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_conta
   if (n_constraints) *n_constraints = w->prob ? w->prob->m : 0;
   if (n_contacts) *n_contacts = w->m_contacts;
   if (replans) *replans = w->replans;
+  return EGS_OK;
+}
+
+
+egs_status egs_world_stabilize(egs_world *w, int32_t mode, int32_t max_steps, int32_t detect_contacts,
+                               const egs_solve_params *params, int32_t *n_unsettled) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_unsettled) *n_unsettled = 0;
+  if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
+  if (mode != EGS_STABILIZE_INIT && mode != EGS_STABILIZE_POST)
+    return fail(w->ctx, EGS_ERR_INVALID, "mode must be EGS_STABILIZE_INIT or EGS_STABILIZE_POST");
+  if (max_steps < 0) return fail(w->ctx, EGS_ERR_INVALID, "max_steps must be >= 0");
+  if (w->precision != EGS_F64) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "stabilisation is fp64 (the reference's is)");
+  // stabilize.cpp's relaxation solve: SOR, omega 1.5, cfm 0, tol 1e-11, at most 20000 sweeps, checked every 10
+  egs_solve_params prm;
+  egs_default_params(&prm);
+  prm.method = EGS_SOR; prm.cfm = 0.0; prm.tol = 1e-11; prm.max_iters = 20000; prm.check_every = 10;
+  if (params) prm = *params;
+  if (egs_status st = validate_params(w->ctx, &prm)) return st;
+  constexpr double kAllowNumericalError = 1e-9, kSimTimeStep = 0.001;   // constants.h:5-6
+  const bool post = mode == EGS_STABILIZE_POST;
+  const int cap = max_steps > 0 ? max_steps : post ? 500 : 100;         // ensembles.cc:606, PostStabilize(500)
+  const double h = post ? kSimTimeStep * 100 : kSimTimeStep * 500;      // ensembles.cc:614, 638
+  const bool detect = !post && detect_contacts != 0;                     // PostStabilize never detects
+  const int E = w->n_ens;
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    w->lambda_stale = true;
+    w->st_steps.clear(); w->st_err_sq.clear();
+    w->rx_ints.alloc(2 * (size_t)E + 5);
+    w->rx_err_sq.alloc((size_t)E);
+    if (!w->h_rx) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&w->h_rx), 8 * sizeof(int32_t), hipHostMallocDefault));
+    int32_t *d_active = w->rx_ints.p, *d_steps = d_active + E, *d_count = d_steps + E, *d_jo = d_count + 1, *d_co = d_jo + 2;
+    if (E > 1) {
+      w->rx_batch.segs = w->batch.segs;
+      w->rx_batch.ensure(E);
+    }
+    using clk = std::chrono::steady_clock;
+    auto t0 = clk::now();
+    auto lap = [&](int k) {   // host wall time per phase (EGS_WORLD_TRACE=1); synchronises first
+      if (!w->trace) return;
+      HIPCHK(hipStreamSynchronize(s));
+      const auto t1 = clk::now();
+      w->t_stab[k] += std::chrono::duration<double, std::micro>(t1 - t0).count();
+      t0 = t1;
+    };
+    for (int pass = 0;; ++pass) {
+      if (detect) world_update_contacts(w, [](int) {});                  // ensembles.cc:603, 616 (pruning included)
+      lap(0);
+      world_relax_system(w);
+      lap(1);
+      egs_problem *p = w->prob, *rx = w->rx;
+      if (p->m > 0) world_relax_assemble(w);
+      StabErrArgs ea;
+      if (E > 1) {
+        ea.jo = w->d_joff.p; ea.co = w->d_coff.p;
+      } else {   // the plain world's one ensemble: its joints, then its contacts
+        w->h_rx[2] = 0; w->h_rx[3] = (int32_t)w->jb0.size(); w->h_rx[4] = 0; w->h_rx[5] = w->m_contacts;
+        HIPCHK(hipMemcpyAsync(d_jo, w->h_rx + 2, 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        ea.jo = d_jo; ea.co = d_co;
+      }
+      ea.mj = (int32_t)w->jb0.size();
+      ea.err = reinterpret_cast<const double *>(rx->rhs.p);
+      ea.active = d_active; ea.steps = d_steps; ea.err_sq = w->rx_err_sq.p; ea.n_active = d_count;
+      ea.first = pass == 0 ? 1 : 0; ea.max_steps = cap; ea.threshold = kAllowNumericalError;
+      HIPCHK(hipMemsetAsync(d_count, 0, sizeof(int32_t), s));
+      launch_stab_err(ea, E, s);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(w->h_rx, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      lap(2);
+      if (w->trace) w->t_stab[5] += 1;
+      if (w->h_rx[0] == 0) break;
+      // (J J^T) y = err and the list-order J^T y (ensembles.cc:659-666).  A finished ensemble is not tested and none of
+      // its states is selected; the sweeps still cover it (ensembles share no body), its rows are never read.
+      egs_status st = E > 1 ? do_solve_batch(rx, &prm, w->rx_batch, d_active) : do_solve(rx, &prm, nullptr);
+      if (st != EGS_OK) return st;
+      lap(3);
+      accumulators_from_lambda(rx);
+      // a lambda out of a timed-out ordering wait moves no body (egs_world_step's rule)
+      HIPCHK(hipMemcpyAsync(w->h_rx + 1, rx->error_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (w->h_rx[1] != 0) return report_stall(rx);
+      StabRelaxArgs ra;
+      ra.n = w->n; ra.post = post ? 1 : 0;
+      ra.ens = E > 1 ? w->d_ens.p : nullptr; ra.active = d_active;
+      ra.acc = reinterpret_cast<const double *>(rx->acc.p);
+      ra.scale = -1.0 * 0.2; ra.h = h;                                   // CalculateVelocityRelaxation(0.2)
+      ra.pos = p->pos.p; ra.R = p->R.p; ra.v = p->v.p; ra.w = p->w.p;
+      launch_stab_relax(ra, s);
+      HIPCHK(hipGetLastError());
+      lap(4);
+    }
+    w->st_steps.resize((size_t)E); w->st_err_sq.resize((size_t)E);
+    HIPCHK(hipMemcpyAsync(w->st_steps.data(), d_steps, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(w->st_err_sq.data(), w->rx_err_sq.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n_unsettled) {
+      int u = 0;
+      for (double e2 : w->st_err_sq) u += !(e2 <= kAllowNumericalError) ? 1 : 0;   // NaN counts as unsettled
+      *n_unsettled = u;
+    }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_stabilize_info(egs_world *w, int32_t n_ensembles, int32_t *steps, double *err_sq) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  if (w->st_steps.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_stabilize yet");
+  if (steps) std::copy(w->st_steps.begin(), w->st_steps.end(), steps);
+  if (err_sq) std::copy(w->st_err_sq.begin(), w->st_err_sq.end(), err_sq);
   return EGS_OK;
 }
 

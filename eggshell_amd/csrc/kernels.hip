@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "solve_device.h"
 #include "assemble_device.h"
+#include "rotation_device.h"
 
 #ifndef EGS_POLL_SLEEP
 #define EGS_POLL_SLEEP 32  // s_sleep units (64 cycles) of a wavefront none of whose lanes is ready; s_wakeup ends it early
@@ -467,27 +468,7 @@ __global__ void __launch_bounds__(256) advance_kernel(int n, double *pos, double
     pos[(size_t)b * 3 + k] = pos[(size_t)b * 3 + k] + dt * vm;
     wm[k] = (w[(size_t)b * 3 + k] + v6[(size_t)b * 6 + 3 + k]) / 2.0;
   }
-  const double n2 = (wm[0] * wm[0] + wm[1] * wm[1]) + wm[2] * wm[2];
-  const double nrm = sqrt(n2);
-  double ax[3] = {wm[0], wm[1], wm[2]};
-  if (n2 > 0) { ax[0] = wm[0] / nrm; ax[1] = wm[1] / nrm; ax[2] = wm[2] / nrm; }
-  const double half = 0.5 * (nrm * dt);
-  const double sn = sin(half), cs = cos(half);
-  const double qw = cs, qx = sn * ax[0], qy = sn * ax[1], qz = sn * ax[2];
-  const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
-  const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  const double Q[9] = {1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx,
-                       txz - twy, tyz + twx, 1.0 - (txx + tyy)};
-  double Ro[9], Rn[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) Ro[k] = R[(size_t)b * 9 + k];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Q[3 * i] * Ro[j] + Q[3 * i + 1] * Ro[3 + j]) + Q[3 * i + 2] * Ro[6 + j];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[(size_t)b * 9 + k] = Rn[k];
+  rotate_by_w(wm, dt, R + (size_t)b * 9);
 #pragma unroll
   for (int k = 0; k < 3; ++k) { v[(size_t)b * 3 + k] = v6[(size_t)b * 6 + k]; w[(size_t)b * 3 + k] = v6[(size_t)b * 6 + 3 + k]; }
 }

@@ -12,6 +12,8 @@ collision.cc bit for bit.  Nothing here runs on the GPU.
     `gap` so side faces never touch.  Contacts are listed in the order
     Ensemble::UpdateContacts produces (ensembles.cc:445-480): all ground
     contacts by body, then body pairs i<j.
+  * cairn(n)               -- a column of seeded, randomly rotated boxes that
+    overlap each other and the ground (InitStabilize's input); bodies only.
 """
 import math
 
@@ -143,6 +145,27 @@ def brick_wall(nx, nz, sink=1e-3):
     n = p.shape[0]
     return dict(p=p, R=np.tile(np.eye(3).reshape(9), (n, 1)), v=np.zeros((n, 3)),
                 w=np.zeros((n, 3)), mass=np.ones(n),
+                I_body=np.tile((np.eye(3) * 0.1).reshape(9), (n, 1)))
+
+
+def cairn(n, overlap=0.03, tilt=0.2, seed=0, origin=(0.0, 0.0)):
+    """A column of n boxes (side 0.3, mass 1, I = 0.1*I3) with seeded random rotations (axis uniform, angle up to
+    `tilt` rad) and lateral offsets up to 0.02, each resting `overlap` into the one below and the lowest `overlap`
+    into the ground: rocks that interpenetrate, what Ensemble::InitStabilize relaxes apart.  Bodies only; the
+    contacts come from the caller's collision routine."""
+    rng = np.random.default_rng(seed)
+    h = SIDE / 2
+    p = np.zeros((n, 3))
+    R = np.zeros((n, 9))
+    for k in range(n):
+        ax = rng.normal(size=3)
+        ax = ax / np.linalg.norm(ax)
+        ang = tilt * rng.uniform()
+        s = math.sin(ang / 2)
+        R[k] = _quat_to_R(math.cos(ang / 2), s * ax[0], s * ax[1], s * ax[2])
+        dx, dy = rng.uniform(-0.02, 0.02, size=2)
+        p[k] = [origin[0] + dx, origin[1] + dy, (h - overlap) + k * (SIDE - overlap)]
+    return dict(p=p, R=R, v=np.zeros((n, 3)), w=np.zeros((n, 3)), mass=np.ones(n),
                 I_body=np.tile((np.eye(3) * 0.1).reshape(9), (n, 1)))
 
 

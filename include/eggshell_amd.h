@@ -417,6 +417,34 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
 egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm,
                                 int32_t *pivots, int32_t *ok);
 
+/* Ensemble::InitStabilize (mode EGS_STABILIZE_INIT, ensembles.cc:602-622) or Ensemble::PostStabilize(max_steps)
+ * (EGS_STABILIZE_POST, ensembles.cc:624-646) for every ensemble of a world (plain or batched).  Per ensemble, on its
+ * own constraint list in the reference's order (its joints, then its contacts): err_sq = sum err_i^2; while
+ * err_sq > 1e-9 (constants.h:5) and steps < max_steps: solve (J J^T) y = err, v_r = -0.2 J^T y (J^T y summed per body
+ * in list order), p += h v_r[0:3], R = WtoR(v_r[3:6], h) R (StepPositions_ExplicitEuler, ensembles.cc:553-561),
+ * then err_sq again.  INIT: h = 0.5, velocities untouched.  POST: h = 0.1, then v += v_r[0:3], w += v_r[3:6].
+ * max_steps = 0: the reference's 100 (INIT) / 500 (POST); hitting it is not an error.  fp64 worlds only
+ * (EGS_ERR_UNSUPPORTED otherwise).  *n_unsettled (may be NULL) = ensembles that ended with err_sq > 1e-9 (or NaN).
+ *   - INIT with detect_contacts = 1 detects and prunes contacts as egs_world_step does, once before the first test
+ *     and after every position step (InitStabilize's UpdateContacts); POST never detects.
+ *   - The solve is the adapter's (stabilize.cpp): the matrix-free sweep with M^-1 = I, every row an equality; params
+ *     NULL = SOR, omega 1.5, cfm 0, tol 1e-11, at most 20000 sweeps, checked every 10.  Each ensemble stops on its
+ *     own test; a stopped ensemble is frozen (bodies, contacts, steps, err_sq) while the others go on, so each
+ *     ensemble of a batch ends with the bits a world holding it alone ends with.  An ensemble without constraints
+ *     takes 0 steps (err_sq = 0).
+ *   - A stall of the relaxation solve returns EGS_ERR_STALL; that pass moves no body.
+ *   - Afterwards get_contacts / batch_info describe the final contact list and egs_world_get_lambda returns
+ *     EGS_ERR_INVALID until the next egs_world_step / egs_world_step_dense (there is no step lambda for that list).
+ *   - EGS_ERR_INVALID, nothing moved: before egs_world_set_bodies, an unknown mode, max_steps < 0.
+ *   - The first call allocates the relaxation system; egs_world_step allocates and launches nothing for it.   */
+#define EGS_STABILIZE_INIT 0   /* Ensemble::InitStabilize, ensembles.cc:602-622 */
+#define EGS_STABILIZE_POST 1   /* Ensemble::PostStabilize(max_steps), ensembles.cc:624-646 */
+egs_status egs_world_stabilize(egs_world *w, int32_t mode, int32_t max_steps, int32_t detect_contacts,
+                               const egs_solve_params *params, int32_t *n_unsettled);
+/* Per-ensemble figures of the last egs_world_stabilize ([E] each, any may be NULL): relaxation steps taken and the
+ * final err_sq.  n_ensembles must be the world's; EGS_ERR_INVALID before the first stabilise call.              */
+egs_status egs_world_stabilize_info(egs_world *w, int32_t n_ensembles, int32_t *steps, double *err_sq);
+
 /* Replaces lcp::SolveLCP_BoxDantzig (toolkit/lcp.cc:444-619; reached from lcp::SolveLCP with
  * Settings.algorithm = COTTLE_DANTZIG, box_lcp = true, schur_complement = false, toolkit/lcp.cc:776-779):
  * Cottle-Dantzig principal pivoting on A x = b + w with lo <= x <= hi, the Cholesky factor of the active
