@@ -1,0 +1,231 @@
+// dense.cpp -- the dense and LCP entries of the C ABI: the dense system of a problem and a step solved on it
+// (egs_problem_dense_*, egs_problem_step_dense), and the stateless solvers on host matrices (egs_dense_*,
+// egs_mixed_constraints_*, egs_box_lcp_*) over dense_lcp.h.
+#include "dense_lcp.h"
+#include "problem.h"
+
+using namespace egs;
+
+namespace {
+
+// The dense system of Ensemble::ComputeVDot (ensembles.cc:510, 513-521) from the blocks the problem holds.
+egs_status build_dense_system(egs_problem *p, double cfm) {
+  egs_context *ctx = p->ctx;
+  if (p->precision != EGS_F64) return fail(ctx, EGS_ERR_UNSUPPORTED, "the dense path is fp64 (the reference's is)");
+  if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
+  if ((size_t)p->m * 3 > 46340) return fail(ctx, EGS_ERR_INVALID, "dense system too large (more than 2^31 entries)");
+  const size_t N = (size_t)p->m * 3;
+  p->dense_A.alloc(N * N > 0 ? N * N : 1);
+  launch_dense_system(p->m, p->body0.p, p->body1.p, real<double>(p->J0), real<double>(p->J1), p->Minv_d.p, cfm,
+                      p->dense_A.p, ctx->stream);
+  HIPCHK(hipGetLastError());
+  p->dense_cfm = cfm;
+  return EGS_OK;
+}
+
+// the outcome of a direct solver, as every LCP entry reports it
+egs_status lcp_result(egs_context *ctx, bool good, int piv, const std::string &msg, const char *what, int32_t *ok, int32_t *pivots) {
+  if (ok) *ok = good ? 1 : 0;
+  if (pivots) *pivots = piv;
+  if (!good) return fail(ctx, EGS_ERR_LCP_FAILED, msg.empty() ? what : msg);
+  return EGS_OK;
+}
+
+egs_status box_lcp_incremental_entry(egs_context *ctx, int algorithm, int32_t n, double *A, const double *b, const double *lo,
+                                     const double *hi, int32_t max_steps, double *x, double *w, int32_t *perm, int32_t *ok,
+                                     int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (ok) *ok = 0;
+  if (n < 1 || n > kIncrementalMaxRows) return fail(ctx, EGS_ERR_INVALID, "incremental box LCP: 1 <= n <= 1024");
+  if (!A || !b || !lo || !hi || !x || !w) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    int piv = 0;
+    std::string msg;
+    const bool good = box_lcp_incremental(ctx->stream, algorithm, n, A, b, lo, hi, x, w, perm, max_steps, 0.0, &piv, &msg);
+    return lcp_result(ctx, good, piv, msg, "the box LCP solver did not reach a solution", ok, pivots);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+egs_status egs_problem_dense_system(egs_problem *p, double cfm, double *A) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (egs_status st = build_dense_system(p, cfm)) return st;
+    const size_t N = (size_t)p->m * 3;
+    if (A && N) {
+      HIPCHK(hipMemcpyAsync(A, p->dense_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+      HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_dense_condition(egs_problem *p, double cfm, double *estimate) {
+  if (!p || !estimate) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (egs_status st = build_dense_system(p, cfm)) return st;
+    bool spd = true;
+    *estimate = dense_condition_estimate(p->ctx->stream, 3 * p->m, p->dense_A.p, &spd);
+    return EGS_OK;   // not positive definite: +inf, i.e. "ill-conditioned" to the caller (ensembles.cc:514)
+  });
+}
+
+egs_status egs_dense_iterate(egs_context *ctx, int32_t N, const double *A, const double *b, const uint8_t *C, const double *lo,
+                             const double *hi, const egs_solve_params *params, double *x, egs_solve_stats *stats) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (egs_status st = validate_params(ctx, params)) return st;
+  if (N < 0 || (N > 0 && (!A || !b || !x))) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (N > 0 && (C || lo || hi) && !(C && lo && hi)) return fail(ctx, EGS_ERR_INVALID, "C, lo and hi come together (or all NULL: every row an equality)");
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<uint8_t> all_eq;
+    std::vector<double> zeros;
+    if (!C) { all_eq.assign((size_t)std::max(N, 1), 1); zeros.assign((size_t)std::max(N, 1), 0.0); }   // sparse_iterations.cc:229-233
+    int it = 0;
+    double res = 0.0;
+    dense_iterate(ctx->stream, N, A, b, C ? C : all_eq.data(), lo ? lo : zeros.data(), hi ? hi : zeros.data(), params->method,
+                  params->omega, params->max_iters, params->tol, x, &it, &res);
+    if (stats) {
+      std::memset(stats, 0, sizeof *stats);
+      stats->iterations = it;
+      stats->residual = res;
+      stats->status = EGS_OK;
+    }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_dense_condition(egs_context *ctx, int32_t N, const double *A, double *estimate, double *pivot_bound) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (N < 0 || !estimate || (N > 0 && !A)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf<double> dA;
+    dA.alloc((size_t)N * N);
+    if (N) HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    bool spd = true;
+    double pb = 1.0;
+    *estimate = dense_condition_estimate(ctx->stream, N, dA.p, &spd, &pb);
+    if (pivot_bound) *pivot_bound = spd ? pb : *estimate;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double cfm, int32_t use_bounds, int32_t *ok,
+                                  int32_t *pivots) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
+  if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  if (ok) *ok = 0;
+  return guarded(p->ctx, [&]() -> egs_status {
+    egs_context *ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    if (stall_seen(p)) return report_stall(p);
+    do_assemble(p, dt, erp);                                  // J, err, bounds, rhs (ensembles.cc:565-570)
+    if (p->m == 0) {                                           // v_dot = M^-1 f (ensembles.cc:504-505)
+      zero_accumulators(p);
+      do_velocity(p, dt);
+      if (ok) *ok = 1;
+      return EGS_OK;
+    }
+    if (egs_status st = build_dense_system(p, cfm)) return st;   // ensembles.cc:510, 513-521
+    const size_t rows = (size_t)p->m * 3;
+    if (!p->h_rows_valid || p->h_rows_eq.size() != rows) {
+      p->h_rows_eq.resize(rows); p->h_rows_lo.resize(rows); p->h_rows_hi.resize(rows);
+      HIPCHK(hipMemcpyAsync(p->h_rows_eq.data(), p->is_eq.p, rows, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(p->h_rows_lo.data(), p->lo.p, rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(p->h_rows_hi.data(), p->hi.p, rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      p->h_rows_valid = true;
+    }
+    const std::vector<uint8_t> &C = p->h_rows_eq;
+    const std::vector<double> &lo = p->h_rows_lo, &hi = p->h_rows_hi;
+    int piv = 0;
+    std::string msg;
+    // Lcp::MixedConstraintsSolver (ensembles.cc:531) on the device matrix; lambda lands in the problem's x
+    const bool good = dense_mixed_constraints_device(s, (int)rows, p->dense_A.p, real<double>(p->rhs), C.data(),
+                                                     lo.data(), hi.data(), (use_bounds & 1) != 0, (use_bounds & 2) != 0, 0, 0.0,
+                                                     nullptr, nullptr, real<double>(p->x), &piv, &msg);
+    if (pivots) *pivots = piv;
+    if (!good) return fail(ctx, EGS_ERR_LCP_FAILED, msg.empty() ? "MixedConstraintsSolver did not reach a solution" : msg);
+    if (ok) *ok = 1;
+    p->last_iterations = piv;
+    accumulators_from_lambda(p);                              // a = M^-1 J^T lambda
+    do_velocity(p, dt);                                       // ensembles.cc:535, 572
+    return EGS_OK;
+  });
+}
+
+egs_status egs_mixed_constraints_solve(egs_context *ctx, int32_t N, const double *A, const double *b,
+                                       const uint8_t *C, const double *lo, const double *hi, int32_t use_bounds,
+                                       double *x, double *w, int32_t *ok, int32_t *pivots) {
+  return egs_mixed_constraints_solve_limits(ctx, N, A, b, C, lo, hi, use_bounds, 0, 0.0, x, w, ok, pivots);
+}
+
+egs_status egs_mixed_constraints_solve_limits(egs_context *ctx, int32_t N, const double *A, const double *b,
+                                              const uint8_t *C, const double *lo, const double *hi, int32_t use_bounds,
+                                              int32_t max_pivots, double max_seconds, double *x, double *w, int32_t *ok,
+                                              int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (N < 0 || (N > 0 && (!A || !b || !C || !lo || !hi || !x || !w))) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (ok) *ok = 0;
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    int piv = 0;
+    std::string msg;
+    const bool good = dense_mixed_constraints(ctx->stream, N, A, b, C, lo, hi, (use_bounds & 1) != 0,
+                                              (use_bounds & 2) != 0, x, w, &piv, &msg, max_pivots, max_seconds);
+    return lcp_result(ctx, good, piv, msg, "MixedConstraintsSolver did not reach a solution", ok, pivots);
+  });
+}
+
+egs_status egs_box_lcp_dantzig(egs_context *ctx, int32_t n, double *A, const double *b, const double *lo, const double *hi,
+                               int32_t max_steps, double *x, double *w, int32_t *perm, int32_t *ok, int32_t *pivots) {
+  return box_lcp_incremental_entry(ctx, 1, n, A, b, lo, hi, max_steps, x, w, perm, ok, pivots);
+}
+egs_status egs_box_lcp_murty(egs_context *ctx, int32_t n, double *A, const double *b, const double *lo, const double *hi,
+                             int32_t max_iterations, double *x, double *w, int32_t *perm, int32_t *ok, int32_t *iterations) {
+  return box_lcp_incremental_entry(ctx, 0, n, A, b, lo, hi, max_iterations, x, w, perm, ok, iterations);
+}
+
+egs_status egs_box_lcp_batch(egs_context *ctx, int32_t algorithm, int32_t count, const int32_t *n, double *A, const double *b,
+                             const double *lo, const double *hi, int32_t max_steps, double max_seconds, double *x, double *w,
+                             int32_t *perm, int32_t *ok, int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (count < 0 || (count > 0 && (!n || !A || !b || !lo || !hi || !x || !w || !ok))) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (algorithm != 0 && algorithm != 1) return fail(ctx, EGS_ERR_INVALID, "algorithm: 0 (Murty) or 1 (Cottle-Dantzig)");
+  for (int k = 0; k < count; ++k) {
+    ok[k] = 0;
+    if (n[k] < 1 || n[k] > kIncrementalMaxRows) return fail(ctx, EGS_ERR_INVALID, "incremental box LCP: 1 <= n <= 1024");
+  }
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    box_lcp_incremental_batch(ctx->stream, algorithm, count, n, A, b, lo, hi, max_steps, max_seconds, x, w, perm, ok, pivots, nullptr);
+    return EGS_OK;     // per-problem outcome in ok[]
+  });
+}
+
+egs_status egs_box_lcp_schur(egs_context *ctx, int32_t n, double *A, const double *b, const double *lo, const double *hi,
+                             int32_t algorithm, int32_t nub, int32_t reference_quirks, int32_t max_iterations, double max_seconds,
+                             double *x, double *w, int32_t *perm, int32_t *ok, int32_t *nub_out, int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (ok) *ok = 0;
+  if (n < 1 || nub > n) return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: n >= 1, nub <= n");
+  if (!A || !b || !lo || !hi || !x || !w) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (algorithm != 0 && algorithm != 1) return fail(ctx, EGS_ERR_INVALID, "algorithm: 0 (Murty) or 1 (Cottle-Dantzig)");
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    int piv = 0, nub_found = 0;
+    std::string msg;
+    const bool good = box_lcp_schur(ctx->stream, n, A, b, lo, hi, algorithm, nub, reference_quirks != 0, max_iterations, max_seconds,
+                                    x, w, perm, &nub_found, &piv, &msg);
+    if (nub_out) *nub_out = nub_found;
+    return lcp_result(ctx, good, piv, msg, "SolveLCP_BoxSchur did not reach a solution", ok, pivots);
+  });
+}
+
+}  // extern "C"

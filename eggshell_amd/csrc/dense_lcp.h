@@ -13,7 +13,7 @@ namespace egs {
 // block_pivoting = true replaces the reference's single-index rule by block
 // principal pivoting (same solution, far fewer factorisations, no 1000-pivot cap).
 // Returns the reference's bool; *pivots = number of principal pivots (solves).
-// Throws std::invalid_argument / the HIP error type of capi.cpp's hip_check.
+// Throws std::invalid_argument / the HIP error type of runtime.h's hip_check.
 // max_pivots > 0 / max_seconds > 0: give up (return false) after that many principal pivots / that
 // much wall time (lcp::Settings::max_iterations, max_time; toolkit/lcp.h:161-167).
 bool dense_mixed_constraints(hipStream_t stream, int N, const double *A, const double *b, const uint8_t *C,

@@ -103,7 +103,7 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
 // the same GS / SOR sweep on the plan's static timetable: one workgroup barrier per time step, no tickets.  With
 // a.iso on 256-constraint tiles: `group` tiles per workgroup (fp32: 1, 2 or 4; fp64: 1 or 3) and, fp64 with group 1,
 // the LINSYM form if `linsym`; the per-sweep snapshots (a.hist_x) always take group 1 without LINSYM.  The caller
-// decides both (capi.cpp: choose_sweep).
+// decides both (solve.cpp: choose_sweep).
 template <typename REAL>
 void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, int group, bool linsym, hipStream_t s);
 // the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles, no snapshots):

@@ -1,0 +1,66 @@
+// policy.h -- the host-side schedule policy: which plan and which kernel family a problem of a given shape gets.
+// Pure functions of sizes, plan figures and the precision; no HIP, so the plan-inspection entries (plan_debug.cpp)
+// can use them without a device.  choose_sweep (solve.cpp) and ensure_tile_plan (problem.cpp) apply them.
+#pragma once
+
+#include <algorithm>
+
+#include "../../include/eggshell_amd.h"
+#include "plan.h"
+
+namespace egs {
+
+// The 4-lane schedule is the faster one while its tiles are all resident at once (one round): 5 x 64
+// constraints per CU in fp64 (94 VGPRs), 8 x 64 in fp32 -- hipOccupancyMaxActiveBlocksPerMultiprocessor
+// of the instantiation decides (C3 fp64: 4 piles 0.33 ms against 0.41 on the 1-lane schedule, 6 piles
+// 0.53 against 0.45).  No 4-lane plan is built at all beyond the register file's 5 (fp64) / 8 (fp32)
+// tiles per CU.
+inline int quad_tiles_per_cu_max(int precision) { return precision == EGS_F32 ? 8 : 5; }
+constexpr int kBigTileMinConstraints = 196608;   // 768 tiles of 256: from here 512-constraint tiles
+// The tile plan's GS / SOR sweep on its static timetable (step_solve.hip) or on tickets
+// (tile_solve_kernel)?  The timetable takes depth + P x sweeps barrier steps, P = the largest level
+// span of a body in a tile; the ticket sweep follows the true dependency chains, about
+// depth + (largest per-body count) x sweeps updates long.  Regular islands (piles of columns) have
+// P = the per-body count and the timetable wins (every lane due at a step shares ONE pass); an
+// irregular island can have spans far beyond its counts, then the tickets win.
+inline bool timetable_pays(const Plan &pl, int sweeps) {
+  const double grp = pl.runs ? 4.0 : 1.0;     // with runs the timetable counts groups of four updates (plan.h)
+  const double fixed = grp * ((double)pl.max_depth + (double)pl.max_period * sweeps);
+  const double ticket = grp * (double)pl.max_depth + (double)pl.max_cnt * sweeps;
+  return fixed <= 1.15 * ticket;
+}
+
+// Which kernel takes the oversize islands of a GS / SOR solve.  Patches wait on each other, so
+// all of a launch's patches must be co-resident: the limits are occupancy (workgroups per CU of
+// the exact kernel instantiation, queried from the runtime) x CUs, never above what was
+// measured on MI355X -- one 1024-thread patch (4 lanes per constraint) or two 256-thread
+// patches (232 VGPRs) per CU.  A kernel change that lowers occupancy lowers the limit and the
+// island falls through to the next schedule instead of stalling.
+enum OversizeSchedule { kQuadPatches = 0, kLanePatches = 1, kAllGlobal = 2 };
+inline OversizeSchedule choose_oversize_schedule(int n_patch_tiles, int quad_per_cu, int patch_per_cu, int cu_count,
+                                                 bool patches_enabled, bool quad_patches_enabled) {
+  if (n_patch_tiles <= 0 || !patches_enabled) return kAllGlobal;
+  const long quad_cap = (long)std::min(quad_per_cu, 1) * cu_count, lane_cap = (long)std::min(patch_per_cu, 2) * cu_count;
+  if (quad_patches_enabled && n_patch_tiles <= quad_cap) return kQuadPatches;
+  if (n_patch_tiles <= lane_cap) return kLanePatches;
+  return kAllGlobal;
+}
+
+// Isotropic bodies, batched work: the register-light tile kernel (no stored B, three
+// 256-constraint tiles per CU in fp64, four in fp32) against the regular one (fp64:
+// 512-constraint tiles, one per CU; fp32: three 256-constraint tiles).
+// Tiles are dispatched in rounds of 3C resp. C, so the better choice depends on how the
+// tile count quantises; per-round times (ms, C3 columns, 100 sweeps) measured on MI355X.
+inline bool iso_schedule_pays(long m, int cu, int precision) {
+  const long t = (m + 255) / 256;                       // 256-constraint tiles
+  if (precision == EGS_F32) return t > 3L * cu;         // fp32: 4 instead of 3 tiles per CU (C4: +7 %)
+  if (t < 2L * cu) return false;                       // fewer than two tiles per CU: registers are not the limit
+  const long full3 = t / (3L * cu), rem3 = t % (3L * cu);
+  // (timetable kernels: one / two / three isotropic tiles per CU walk a launch in 0.435 / 0.462 / 0.50 ms, a round of
+  //  512-constraint regular tiles in 0.415 ms; the ticket kernels' figures were 0.45 / 0.57 / 0.66 and 0.53 -- same choices)
+  const double iso = 0.50 * full3 + (rem3 == 0 ? 0.0 : rem3 <= cu ? 0.435 : rem3 <= 2L * cu ? 0.462 : 0.50);
+  const double regular = 0.415 * ((t / 2 + cu - 1) / cu);
+  return iso < regular;
+}
+
+}  // namespace egs

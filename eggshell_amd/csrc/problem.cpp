@@ -1,0 +1,721 @@
+// problem.cpp -- the device-resident problem: its topology and plans (problem_set_topology, ensure_tile_plan),
+// mass blocks, the sticky stall flag, assembly and velocity update, the stand-alone mat-vec, and the egs_problem_*
+// entries of the C ABI with the stateless egs_solve_blocks / egs_matvec_blocks on top of them.
+#include <chrono>
+
+#include "matvec.h"
+#include "policy.h"
+#include "problem.h"
+
+using namespace egs;
+
+namespace {
+
+// host double <-> the problem's REAL: fp32 problems convert on the host, through a temporary
+void upload_real(egs_problem *p, DevBuf<unsigned char> &dst, const double *src, size_t count) {
+  if (!src || count == 0) return;
+  hipStream_t s = p->ctx->stream;
+  std::vector<float> tmp;
+  const void *h = src;
+  if (p->precision == EGS_F32) {
+    tmp.resize(count);
+    for (size_t i = 0; i < count; ++i) tmp[i] = (float)src[i];
+    h = tmp.data();
+  }
+  HIPCHK(hipMemcpyAsync(dst.p, h, count * p->real_size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+}
+
+void download_real(egs_problem *p, const DevBuf<unsigned char> &src, double *dst, size_t count) {
+  if (!dst || count == 0) return;
+  hipStream_t s = p->ctx->stream;
+  const bool f32 = p->precision == EGS_F32;
+  std::vector<float> tmp(f32 ? count : 0);
+  HIPCHK(hipMemcpyAsync(f32 ? (void *)tmp.data() : (void *)dst, src.p, count * p->real_size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  for (size_t i = 0; f32 && i < count; ++i) dst[i] = (double)tmp[i];
+}
+
+// Once per M^-1 upload or topology change (4 bytes back): may the fp64 isotropic timetable sweep keep one linear block
+// for both sides (step_solve.hip: LINSYM)?  The body half of the preconditions -- every constraint has a body on
+// side 1, and where it has one on side 0 as well, the same linear weight -- is decided here, on the device; the
+// Jacobian half (lin_neg) where the blocks are made.
+void decide_linsym_bodies(egs_problem *p) {
+  p->linsym_bodies = 0;
+  if (p->precision != EGS_F64 || !p->minv_iso || p->m <= 0) return;
+  hipStream_t s = p->ctx->stream;
+  int one = 1, flag = 0;
+  int32_t *scratch = p->error_flag.p + 1;
+  HIPCHK(hipMemcpyAsync(scratch, &one, sizeof(int), hipMemcpyHostToDevice, s));
+  launch_linsym_bodies<double>(p->m, p->body0.p, p->body1.p, real<double>(p->Minv_r), scratch, s);
+  HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  p->linsym_bodies = flag != 0 ? 1 : 0;
+}
+
+void ensure_wf(egs_problem *p) {
+  if (p->wf_valid) return;
+  p->Wf.alloc((size_t)(p->n > 0 ? p->n : 1) * 6);
+  launch_mass_times_force(p->n, p->Minv_d.p, p->f_ext.p, p->Wf.p, p->ctx->stream);
+  p->wf_valid = true;
+}
+
+// The schedule of the stand-alone products (matvec_plan.h), built on first use.
+void ensure_matvec_plan(egs_problem *p) {
+  if (p->mv_ready) return;
+  // 128 constraints per tile: 37 KB of LDS, four workgroups per CU keep loads in flight while others
+  // compute (measured on 1 M contacts: 5.2-5.4 TB/s against 4.9-5.0 with 256).  EGS_MV_TILE=256 for experiments.
+  const char *te = std::getenv("EGS_MV_TILE");
+  const int forced = te ? std::atoi(te) : 0;
+  p->mvplan = build_matvec_plan(p->n, p->m, p->h_body0.data(), p->h_body1.data(), forced == 256 ? 256 : 128);
+  const MatvecPlan &pl = p->mvplan;
+  stage(p->ctx, p->mv_lanes, pl.lanes);
+  stage(p->ctx, p->mv_tiles, pl.tiles);
+  stage(p->ctx, p->mv_slots, pl.slots);
+  stage(p->ctx, p->mv_ents, pl.ents);
+  stage(p->ctx, p->mv_boundary, pl.boundary);
+  const size_t rs = p->real_size(), mm = (size_t)(p->m > 0 ? p->m : 1);
+  p->mv_T.alloc((size_t)(pl.n_shared_entries > 0 ? pl.n_shared_entries : 1) * 6 * rs);
+  p->mv_x.alloc(mm * 3 * rs);
+  p->mv_y.alloc(mm * 3 * rs);
+  HIPCHK(hipStreamSynchronize(p->ctx->stream));
+  p->mv_ready = true;
+}
+
+template <typename REAL>
+void launch_matvec_t(egs_problem *p, int parts, REAL eps, REAL scale, const REAL *x) {
+  const MatvecPlan &pl = p->mvplan;
+  MatvecArgs<REAL> a;
+  a.lanes = p->mv_lanes.p; a.tiles = p->mv_tiles.p; a.slots = p->mv_slots.p; a.ents = p->mv_ents.p;
+  a.boundary = p->mv_boundary.p; a.n_boundary = (int32_t)pl.boundary.size();
+  a.max_slots = pl.max_slots;
+  a.Minv = real<REAL>(p->Minv_r);
+  a.J0 = real<REAL>(p->J0); a.J1 = real<REAL>(p->J1);
+  a.x = x; a.y = real<REAL>(p->mv_y); a.T = real<REAL>(p->mv_T);
+  a.eps = eps; a.scale = scale; a.accumulate = 0;
+  { const char *ne = std::getenv("EGS_MV_NT"); a.stream_nt = ne ? (std::atoi(ne) != 0) : 1; }   // +2-8 % measured
+  record_kernel_event(p->ctx, true);
+  if (parts == EGS_MV_FULL) {
+    launch_matvec<REAL>(a, 8, pl.n_tiles, pl.block, p->ctx->stream);
+  } else {   // Lx + Ux, Ux + Dx, Lx + Dx as the reference adds them (sparse_iterations_utils.cc:563-569, 606-622)
+    for (int bit = 1; bit <= 4; bit <<= 1) {
+      if (!(parts & bit)) continue;
+      launch_matvec<REAL>(a, bit, pl.n_tiles, pl.block, p->ctx->stream);
+      a.accumulate = 1;
+    }
+  }
+  record_kernel_event(p->ctx, false);
+  HIPCHK(hipGetLastError());
+}
+
+egs_status do_matvec(egs_problem *p, int32_t parts, double eps, double scale, const double *x, double *y) {
+  egs_context *ctx = p->ctx;
+  if (!(parts == EGS_MV_FULL || (parts >= 1 && parts <= 7)))
+    return fail(ctx, EGS_ERR_INVALID, "parts must be EGS_MV_FULL or a combination of LOWER / UPPER / DIAG");
+  if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
+  if (p->m == 0) return EGS_OK;
+  ensure_minv_real(p);
+  ensure_matvec_plan(p);
+  if (x) upload_real(p, p->mv_x, x, (size_t)p->m * 3);
+  // x = NULL: the device-resident lambda of the last solve
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    launch_matvec_t<REAL>(p, parts, (REAL)eps, (REAL)scale, real<REAL>(x ? p->mv_x : p->x));
+  });
+  if (y) download_real(p, p->mv_y, y, (size_t)p->m * 3);
+  return EGS_OK;
+}
+
+// egs_solve_blocks / egs_matvec_blocks are stateless for their caller; the context keeps the
+// last problem (schedule + device buffers) and reuses it while the constraint graph is unchanged.
+egs_status oneshot_problem(egs_context *ctx, int32_t n, int32_t m, const int32_t *body0, const int32_t *body1,
+                           int32_t precision, egs_problem **out) {
+  egs_problem *p = ctx->oneshot;
+  const bool reuse = p && p->n == n && p->m == m && p->precision == precision &&
+                     (m == 0 || (std::memcmp(p->h_body0.data(), body0, (size_t)m * sizeof(int32_t)) == 0 &&
+                                 std::memcmp(p->h_body1.data(), body1, (size_t)m * sizeof(int32_t)) == 0));
+  if (!reuse) {
+    if (p) { egs_problem_destroy(p); ctx->oneshot = nullptr; }
+    egs_status st = egs_problem_create(ctx, n, m, body0, body1, precision, &p);
+    if (st != EGS_OK) return st;
+    ctx->oneshot = p;
+  }
+  *out = p;
+  return EGS_OK;
+}
+}  // namespace
+
+namespace egs {
+
+void ensure_minv_real(egs_problem *p) {
+  if (p->minv_r_valid) {
+    if (p->linsym_bodies < 0) decide_linsym_bodies(p);
+    return;
+  }
+  const int count = p->n * 36;
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    launch_convert_minv<REAL>(count, p->Minv_d.p, real<REAL>(p->Minv_r), p->ctx->stream);
+  });
+  p->minv_r_valid = true;
+  // isotropy of the blocks, checked once per upload (4 bytes back)
+  const char *ie = std::getenv("EGS_ISO");
+  if (p->n > 0 && !(ie && std::atoi(ie) == 0)) {
+    hipStream_t s = p->ctx->stream;
+    int one = 1, flag = 0;
+    int32_t *scratch = p->error_flag.p + 1;
+    HIPCHK(hipMemcpyAsync(scratch, &one, sizeof(int), hipMemcpyHostToDevice, s));
+    with_real(p, [&](auto r) { using REAL = decltype(r); launch_minv_iso<REAL>(p->n, real<REAL>(p->Minv_r), scratch, s); });
+    HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const bool iso = flag != 0;
+    if (iso != p->minv_iso) p->tile_plan_ready = false;   // the preferred tile size depends on it
+    p->minv_iso = iso;
+  }
+  decide_linsym_bodies(p);
+}
+
+// Ball joints that join two bodies are assembled with +0 in J1_lin where J0_lin holds +0 (joints.cc:17-31): their
+// J1_lin is -J0_lin in value but not in bits.  Contacts are [-Rn, ..] / [Rn, ..], negated bit for bit.
+void note_kinds(egs_problem *p, const int32_t *kind) {
+  bool jp = false;
+  for (int i = 0; i < p->m && !jp; ++i) jp = kind[i] == EGS_JOINT_BALL && p->h_body0[i] >= 0 && p->h_body1[i] >= 0;
+  p->joint_pairs = jp;
+}
+
+// ---- the sticky stall flag ---------------------------------------------------
+// asynchronous refresh of the page-locked copy (4 bytes), enqueued behind a solve
+void post_flag_copy(egs_problem *p) {
+  HIPCHK(hipMemcpyAsync(p->h_flag.p, p->error_flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, p->ctx->stream));
+}
+
+// A stall was seen: clear it (it is being reported now) and fail.  Synchronises.
+egs_status report_stall(egs_problem *p) {
+  hipStream_t s = p->ctx->stream;
+  HIPCHK(hipMemsetAsync(p->error_flag.p, 0, sizeof(int32_t), s));
+  HIPCHK(hipStreamSynchronize(s));
+  *p->h_flag.p = 0;
+  p->ctx->error = "device ordering wait timed out";
+  return EGS_ERR_STALL;
+}
+
+AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
+  AssembleArgs a;
+  a.n = p->n; a.m = p->m;
+  a.pos = p->pos.p; a.R = p->R.p; a.v = p->v.p; a.w = p->w.p;
+  ensure_wf(p);
+  a.Wf = p->Wf.p;
+  a.kind = p->kind.p; a.body0 = p->body0.p; a.body1 = p->body1.p;
+  a.data = p->data.p;
+  a.dt = dt; a.erp = erp;
+  a.J0 = p->J0.p; a.J1 = p->J1.p; a.lo = p->lo.p; a.hi = p->hi.p; a.rhs = p->rhs.p;
+  a.err = p->err.p; a.is_eq = p->is_eq.p;
+  return a;
+}
+
+// what the device assembly tells about the blocks it makes
+void note_assembled(egs_problem *p) {
+  p->have_blocks = true;
+  p->lin_neg = !p->joint_pairs;   // contact.cc:66-99 builds [-Rn, ..] / [Rn, ..]; two-body ball joints: note_kinds
+}
+
+void do_assemble(egs_problem *p, double dt, double erp) {
+  const AssembleArgs a = assemble_args(p, dt, erp);
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->ctx->stream); });
+  HIPCHK(hipGetLastError());
+  note_assembled(p);
+}
+
+void do_velocity(egs_problem *p, double dt) {
+  ensure_wf(p);
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    launch_velocity<REAL>(p->n, p->v.p, p->w.p, p->Wf.p, real<REAL>(p->acc), dt, p->v6.p, p->ctx->stream);
+  });
+  HIPCHK(hipGetLastError());
+}
+
+// no constraints: v_dot = M^-1 f (ensembles.cc:504-505), the accumulators the velocity update reads are zero
+void zero_accumulators(egs_problem *p) {
+  HIPCHK(hipMemsetAsync(p->acc.p, 0, (size_t)(p->n > 0 ? p->n : 1) * 6 * p->real_size(), p->ctx->stream));
+}
+
+// The 1-lane-per-constraint schedule (tile / patch / global kernels).  Built on
+// demand: a problem that runs on the quad schedule only needs it for Jacobi.
+void ensure_tile_plan(egs_problem *p) {
+  if (p->tile_plan_ready) return;
+  hipStream_t s = p->ctx->stream;
+  const int n = p->n, m = p->m;
+  {
+    // 256 constraints per tile; 512 once there are enough tiles to give every CU two
+    // anyway (all 64 lanes of the working wavefront busy: +3-4 % on 16 batched C3 piles) --
+    // but not for isotropic bodies, whose register-light kernel fits THREE 256-thread tiles per CU.
+    // Oversize islands (patch / global kernels) always use 256 -- unless 512 makes every island fit.
+    const char *te = std::getenv("EGS_TILE");   // experiment knob: 64/128/256/512 constraints per tile
+    const int forced = te ? std::atoi(te) : 0;
+    int tile = (forced == 64 || forced == 128 || forced == 256 || forced == 512) ? forced : (m >= kBigTileMinConstraints && p->precision == EGS_F64 && !(p->minv_iso && iso_schedule_pays(m, p->ctx->cu_count, p->precision)) ? 512 : 256);
+    p->plan = build_plan(n, m, p->h_body0.data(), p->h_body1.data(), tile);
+    if (!p->plan.global.empty()) {
+      if (tile == 256 && !forced) {   // islands of 257..512 constraints: one 512-thread workgroup, all hand-offs in LDS
+        Plan big = build_plan(n, m, p->h_body0.data(), p->h_body1.data(), 512);
+        if (big.global.empty()) p->plan = std::move(big);
+      } else if (tile != 256) {       // the patch kernels are 256-constraint workgroups, forced size or not
+        p->plan = build_plan(n, m, p->h_body0.data(), p->h_body1.data(), 256);
+      }
+    }
+  }
+  const Plan &pl = p->plan;
+  p->tile.stage(p->ctx, pl);
+  stage(p->ctx, p->gcons, pl.global);
+  if (pl.n_patch_tiles > 0) p->patch.stage(p->ctx, pl);
+  {
+    const char *pe = std::getenv("EGS_PATCH"), *qp = std::getenv("EGS_QUAD_PATCH");
+    const size_t lds = (size_t)pl.patch_max_slots * (6 * p->real_size() + sizeof(unsigned));
+    int occ_quad = 0, occ_lane = 0, occ_glob = 1;
+    with_real(p, [&](auto r) {
+      using REAL = decltype(r);
+      if (pl.n_patch_tiles > 0) { occ_quad = occupancy_quad_patch_solve<REAL>(lds); occ_lane = occupancy_patch_solve<REAL>(lds); }
+      if (!pl.global.empty()) occ_glob = occupancy_global_solve<REAL>();
+    });
+    p->oversize = choose_oversize_schedule(pl.n_patch_tiles, occ_quad, occ_lane, p->ctx->cu_count, !(pe && std::atoi(pe) == 0),
+                                           pl.block == 256 && !(qp && std::atoi(qp) == 0));
+    // (a patch plan with runs is for the 4-lane kernel only: plan.cpp builds it when that kernel will take it; should it
+    //  not -- no LDS left for a resident workgroup -- the island goes the all-global way rather than to a kernel that
+    //  does not know the placeholders)
+    if (pl.patch_runs && p->oversize == kLanePatches) p->oversize = kAllGlobal;
+    p->global_max_blocks = std::max(1, std::min(occ_glob, 1) * p->ctx->cu_count);
+    if (p->oversize == kQuadPatches) {
+      const size_t rsz = p->real_size(), mm2 = (size_t)m;
+      p->wsB0.alloc(mm2 * 18 * rsz); p->wsB1.alloc(mm2 * 18 * rsz); p->wsD.alloc(mm2 * 9 * rsz); p->wsInv.alloc(mm2 * 3 * rsz);
+    }
+  }
+  const size_t mg = pl.global.size(), rsz = p->real_size();
+  p->gB0.alloc(mg * 18 * rsz); p->gB1.alloc(mg * 18 * rsz); p->gD.alloc(mg * 9 * rsz);
+  p->gden.alloc(mg * 3 * rsz); p->gdx.alloc(mg * 3 * rsz);
+  HIPCHK(hipStreamSynchronize(s));
+  p->tile_plan_ready = true;
+}
+
+// (Re)build everything that depends on the constraint topology.  Body state
+// (pos, R, v, w, M^-1, f_ext) is kept when n is unchanged; buffers only grow.
+void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const int32_t *body1, bool fresh) {
+  egs_context *ctx = p->ctx;
+  const int n = p->n;
+  hipStream_t s = ctx->stream;
+  const auto t_top0 = std::chrono::steady_clock::now();
+  HIPCHK(hipStreamSynchronize(s));   // nothing may still read the pinned arena
+  ctx->pinned.reset();
+  p->m = m;
+  p->h_body0.assign(body0, body0 + m);
+  p->h_body1.assign(body1, body1 + m);
+  p->tile_plan_ready = false;
+  p->linsym_bodies = -1;
+  p->mv_ready = false;
+  p->dense_cfm = -1.0;
+  p->h_rows_valid = false;
+  p->use_quad = false;
+  p->have_blocks = false;
+  p->have_constraints = false;
+  p->last_iterations = 0;
+  {  // quad schedule: small problems whose islands all fit 64-constraint tiles
+    const char *env = std::getenv("EGS_QUAD");
+    const int force = env ? std::atoi(env) : -1;
+    if (m > 0 && force != 0 && (force == 1 || (long)m <= 64L * quad_tiles_per_cu_max(p->precision) * p->ctx->cu_count)) {
+      const char *qe = std::getenv("EGS_QUAD_TILE");   // experiment knob: force 64 or 256
+      const int qt = qe ? std::atoi(qe) : 0;
+      // 64-constraint tiles when every island fits, else 1024-thread tiles of 256
+      // runs (plan.h) while there is about one tile per CU
+      const auto t_pl0 = std::chrono::steady_clock::now();
+      p->planq = build_plan(n, m, body0, body1, (qt == 64 || qt == 128 || qt == 256) ? qt : kAutoQuadBlock, &p->planq,
+                            p->ctx->cu_count);
+      if (std::getenv("EGS_PLAN_TRACE"))
+        std::fprintf(stderr, "plan trace: build_plan(quad) %.1f us for %d constraints\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_pl0).count(), m);
+      bool one_round = true;
+      if (force != 1 && p->planq.global.empty()) {
+        const size_t qlds = (size_t)p->planq.max_slots * 6 * p->real_size();
+        const int occ = with_real(p, [&](auto r) { return occupancy_step_quad<decltype(r)>(p->planq.block, qlds); });
+        one_round = (long)p->planq.n_tiles <= (long)occ * p->ctx->cu_count;
+      }
+      if (p->planq.global.empty() && one_round) {
+        p->use_quad = true;
+        p->quad.stage(p->ctx, p->planq);
+        const size_t rsz = p->real_size(), mm2 = (size_t)m;
+        p->wsB0.alloc(mm2 * 18 * rsz); p->wsB1.alloc(mm2 * 18 * rsz); p->wsD.alloc(mm2 * 9 * rsz); p->wsInv.alloc(mm2 * 3 * rsz);
+      }
+    }
+  }
+  stage(p->ctx, p->body0, p->h_body0);
+  stage(p->ctx, p->body1, p->h_body1);
+  const size_t rs = p->real_size();
+  const size_t nn = (size_t)(n > 0 ? n : 1), mm = (size_t)(m > 0 ? m : 1);
+  p->kind.alloc(mm); p->data.alloc(mm * 7);
+  p->err.alloc(mm * 3);
+  p->J0.alloc(mm * 18 * rs); p->J1.alloc(mm * 18 * rs);
+  p->lo.alloc(mm * 3 * rs); p->hi.alloc(mm * 3 * rs); p->rhs.alloc(mm * 3 * rs);
+  p->x.alloc(mm * 3 * rs); p->wres.alloc(mm * 3 * rs);
+  p->is_eq.alloc(mm * 3);
+  HIPCHK(hipMemsetAsync(p->acc.p, 0, nn * 6 * rs, s));
+  if (fresh) {   // a re-planned world overwrites both in its next solve; a new problem reads as zeros
+    HIPCHK(hipMemsetAsync(p->x.p, 0, mm * 3 * rs, s));
+    HIPCHK(hipMemsetAsync(p->wres.p, 0, mm * 3 * rs, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  if (std::getenv("EGS_PLAN_TRACE"))
+    std::fprintf(stderr, "plan trace: problem_set_topology %.1f us in all\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_top0).count());
+  // the 1-lane schedule is built at the first solve that needs it (ensure_tile_plan):
+  // its tile size depends on the mass blocks, which arrive after the topology
+}
+
+egs_status check_topology(egs_context *ctx, int32_t n, int32_t m, const int32_t *body0, const int32_t *body1) {
+  if (n < 0 || m < 0 || (m > 0 && (!body0 || !body1))) return fail(ctx, EGS_ERR_INVALID, "bad sizes / NULL topology");
+  for (int i = 0; i < m; ++i) {
+    // (the schedule builder checks the range too, but the 1-lane schedule is built lazily)
+    if (body0[i] < -1 || body0[i] >= n || body1[i] < -1 || body1[i] >= n)
+      return fail(ctx, EGS_ERR_INVALID, "body index out of range");
+    if (body0[i] >= 0 && body0[i] == body1[i])
+      return fail(ctx, EGS_ERR_INVALID, "constraint with the same body on both sides");
+  }
+  return EGS_OK;
+}
+}  // namespace egs
+
+extern "C" {
+
+egs_status egs_problem_create(egs_context *ctx, int32_t n, int32_t m, const int32_t *body0,
+                              const int32_t *body1, int32_t precision, egs_problem **out) {
+  if (!ctx || !out) return EGS_ERR_INVALID;
+  *out = nullptr;
+  if (egs_status st = check_topology(ctx, n, m, body0, body1)) return st;
+  if (precision != EGS_F64 && precision != EGS_F32) return fail(ctx, EGS_ERR_INVALID, "unknown precision");
+  egs_problem *p = new (std::nothrow) egs_problem;
+  if (!p) return fail(ctx, EGS_ERR_HIP, "host allocation failed");
+  p->ctx = ctx; p->n = n; p->m = m; p->precision = precision;
+  egs_status st = guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t rs = p->real_size(), nn = (size_t)(n > 0 ? n : 1);
+    p->gtickets.alloc(nn);
+    p->pos.alloc(nn * 3); p->R.alloc(nn * 9); p->v.alloc(nn * 3); p->w.alloc(nn * 3);
+    p->Minv_d.alloc(nn * 36); p->f_ext.alloc(nn * 6); p->v6.alloc(nn * 6);
+    p->res_partials.alloc(4 * kResidualBlocks);
+    p->Minv_r.alloc(nn * 36 * rs);
+    p->acc.alloc(nn * 6 * rs);
+    p->error_flag.alloc(2);
+    HIPCHK(hipMemsetAsync(p->error_flag.p, 0, 2 * sizeof(int32_t), ctx->stream));
+    p->h_flag.alloc(16);   // 64 bytes
+    *p->h_flag.p = 0;
+    problem_set_topology(p, m, body0, body1);
+    return EGS_OK;
+  });
+  if (st != EGS_OK) { delete p; return st; }
+  *out = p;
+  return EGS_OK;
+}
+
+egs_status egs_problem_create_batch(egs_context *ctx, int32_t n_ensembles, const int32_t *n_bodies,
+                                    const int32_t *n_constraints, const int32_t *body0, const int32_t *body1,
+                                    int32_t precision, egs_problem **out, int32_t *body_offset,
+                                    int32_t *constraint_offset) {
+  if (!ctx || !out) return EGS_ERR_INVALID;
+  *out = nullptr;
+  if (n_ensembles < 0 || (n_ensembles > 0 && (!n_bodies || !n_constraints)))
+    return fail(ctx, EGS_ERR_INVALID, "bad ensemble count / NULL size tables");
+  long nb = 0, nc = 0;
+  for (int e = 0; e < n_ensembles; ++e) {
+    if (n_bodies[e] < 0 || n_constraints[e] < 0) return fail(ctx, EGS_ERR_INVALID, "negative ensemble size");
+    nb += n_bodies[e]; nc += n_constraints[e];
+  }
+  if (nb > INT32_MAX || nc > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "batch too large for 32-bit indices");
+  if (nc > 0 && (!body0 || !body1)) return fail(ctx, EGS_ERR_INVALID, "NULL topology");
+  std::vector<int32_t> g0, g1;
+  try {
+    g0.resize((size_t)nc); g1.resize((size_t)nc);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, EGS_ERR_HIP, "host allocation failed");
+  }
+  long bo = 0, co = 0;
+  for (int e = 0; e < n_ensembles; ++e) {
+    if (body_offset) body_offset[e] = (int32_t)bo;
+    if (constraint_offset) constraint_offset[e] = (int32_t)co;
+    for (int i = 0; i < n_constraints[e]; ++i) {
+      const int32_t a = body0[co + i], b = body1[co + i];
+      if (a < -1 || a >= n_bodies[e] || b < -1 || b >= n_bodies[e])
+        return fail(ctx, EGS_ERR_INVALID, "ensemble-local body index out of range");
+      g0[(size_t)(co + i)] = a < 0 ? -1 : (int32_t)(bo + a);
+      g1[(size_t)(co + i)] = b < 0 ? -1 : (int32_t)(bo + b);
+    }
+    bo += n_bodies[e]; co += n_constraints[e];
+  }
+  if (body_offset) body_offset[n_ensembles] = (int32_t)bo;
+  if (constraint_offset) constraint_offset[n_ensembles] = (int32_t)co;
+  return egs_problem_create(ctx, (int32_t)nb, (int32_t)nc, g0.data(), g1.data(), precision, out);
+}
+
+void egs_problem_destroy(egs_problem *p) {
+  if (!p) return;
+  if (p->ctx && p->ctx->stream) (void)hipStreamSynchronize(p->ctx->stream);
+  delete p;
+}
+
+egs_status egs_problem_set_blocks(egs_problem *p, const double *Minv, const double *J0, const double *J1,
+                                  const uint8_t *is_eq, const double *lo, const double *hi, const double *rhs) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t n = p->n, m = p->m;
+    if (Minv && n) { upload(p->Minv_d, Minv, n * 36, p->ctx->stream); p->minv_r_valid = false; p->wf_valid = false; }
+    upload_real(p, p->J0, J0, m * 18);
+    upload_real(p, p->J1, J1, m * 18);
+    if (J0 || J1) {
+      // step_solve_kernel's LINSYM form keeps ONE linear block per constraint: J1_lin = -J0_lin wherever both sides
+      // exist, equal in value (a NaN refuses it) and bit for bit
+      bool neg = J0 && J1 && p->precision == EGS_F64 && p->h_body0.size() == m && p->h_body1.size() == m;
+      for (size_t i = 0; neg && i < m; ++i) {
+        if (p->h_body0[i] < 0 || p->h_body1[i] < 0) continue;
+        for (int r = 0; r < 3 && neg; ++r)
+          for (int k = 0; k < 3 && neg; ++k) {
+            const double a = J0[i * 18 + 6 * r + k], b = -J1[i * 18 + 6 * r + k];
+            neg = a == b && std::memcmp(&a, &b, sizeof a) == 0;
+          }
+      }
+      p->lin_neg = neg;
+    }
+    if (is_eq && m) upload(p->is_eq, is_eq, m * 3, p->ctx->stream);
+    upload_real(p, p->lo, lo, m * 3);
+    upload_real(p, p->hi, hi, m * 3);
+    upload_real(p, p->rhs, rhs, m * 3);
+    p->have_blocks = true;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_solve(egs_problem *p, const egs_solve_params *params, egs_solve_stats *stats) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status { return do_solve(p, params, stats); });
+}
+
+egs_status egs_problem_get_lambda(egs_problem *p, double *x) {
+  if (!p || !x) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    download_real(p, p->x, x, (size_t)p->m * 3);
+    return stall_seen(p) ? report_stall(p) : EGS_OK;   // the download synchronised: every earlier solve is accounted for
+  });
+}
+
+egs_status egs_problem_get_accumulators(egs_problem *p, double *a) {
+  if (!p || !a) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    download_real(p, p->acc, a, (size_t)p->n * 6);
+    return stall_seen(p) ? report_stall(p) : EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_state(egs_problem *p, const double *pos, const double *R, const double *v,
+                                 const double *w, const double *Minv, const double *f_ext) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t n = p->n;
+    hipStream_t s = p->ctx->stream;
+    if (pos) upload(p->pos, pos, n * 3, s);
+    if (R) upload(p->R, R, n * 9, s);
+    if (v) upload(p->v, v, n * 3, s);
+    if (w) upload(p->w, w, n * 3, s);
+    if (Minv) { upload(p->Minv_d, Minv, n * 36, s); p->minv_r_valid = false; p->wf_valid = false; }
+    if (f_ext) { upload(p->f_ext, f_ext, n * 6, s); p->wf_valid = false; }
+    p->have_state = true;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_mass(egs_problem *p, const double *inv_mass, const double *inv_inertia) {
+  if (!p) return EGS_ERR_INVALID;
+  if (p->n > 0 && (!inv_mass || !inv_inertia)) return fail(p->ctx, EGS_ERR_INVALID, "NULL mass arrays");
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t n = (size_t)p->n;
+    std::vector<double> blocks(n * 36, 0.0);
+    for (size_t b = 0; b < n; ++b) {
+      double *W = blocks.data() + b * 36;
+      for (int k = 0; k < 3; ++k) W[7 * k] = inv_mass[b];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) W[6 * (3 + r) + 3 + c] = inv_inertia[b * 9 + 3 * r + c];
+    }
+    if (n) { upload(p->Minv_d, blocks.data(), n * 36, p->ctx->stream); p->minv_r_valid = false; p->wf_valid = false; }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, const double *data) {
+  if (!p) return EGS_ERR_INVALID;
+  if (p->m > 0 && (!kind || !data)) return fail(p->ctx, EGS_ERR_INVALID, "NULL constraint descriptors");
+  for (int i = 0; i < p->m; ++i)
+    if (kind[i] != EGS_JOINT_BALL && kind[i] != EGS_CONTACT_BOX)
+      return fail(p->ctx, EGS_ERR_INVALID, "unknown constraint kind");
+  return guarded(p->ctx, [&]() -> egs_status {
+    upload(p->kind, kind, (size_t)p->m, p->ctx->stream);
+    upload(p->data, data, (size_t)p->m * 7, p->ctx->stream);
+    note_kinds(p, kind);
+    p->have_constraints = true;
+    p->h_rows_valid = false;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_assemble(egs_problem *p, double dt, double erp) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
+  if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  return guarded(p->ctx, [&]() -> egs_status { do_assemble(p, dt, erp); return EGS_OK; });
+}
+
+egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_solve_params *params,
+                            egs_solve_stats *stats) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
+  if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (stall_seen(p)) return report_stall(p);   // an earlier (asynchronous) step timed out
+    note_assembled(p);   // what choose_sweep reads of the blocks this step makes
+    egs_status st;
+    if (step_fuses_assembly(p, params)) {
+      const AssembleArgs a = assemble_args(p, dt, erp);
+      st = do_solve(p, params, stats, &a);
+    } else {
+      do_assemble(p, dt, erp);
+      st = do_solve(p, params, stats);
+    }
+    if (st != EGS_OK) return st;
+    do_velocity(p, dt);
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_get_blocks(egs_problem *p, double *J0, double *J1, uint8_t *is_eq, double *lo,
+                                  double *hi, double *rhs, double *err) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t m = p->m;
+    download_real(p, p->J0, J0, m * 18);
+    download_real(p, p->J1, J1, m * 18);
+    download_real(p, p->lo, lo, m * 3);
+    download_real(p, p->hi, hi, m * 3);
+    download_real(p, p->rhs, rhs, m * 3);
+    hipStream_t s = p->ctx->stream;
+    if (is_eq && m) HIPCHK(hipMemcpyAsync(is_eq, p->is_eq.p, m * 3, hipMemcpyDeviceToHost, s));
+    if (err && m) HIPCHK(hipMemcpyAsync(err, p->err.p, m * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_get_velocity(egs_problem *p, double *v6) {
+  if (!p || !v6) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (p->n) HIPCHK(hipMemcpyAsync(v6, p->v6.p, (size_t)p->n * 6 * sizeof(double), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    return stall_seen(p) ? report_stall(p) : EGS_OK;
+  });
+}
+
+egs_status egs_problem_advance(egs_problem *p, double dt) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!p->have_state) return fail(p->ctx, EGS_ERR_INVALID, "set_state and step first");
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (stall_seen(p)) return report_stall(p);   // do not integrate a lambda that came out of a timed-out wait
+    launch_advance(p->n, p->pos.p, p->R.p, p->v.p, p->w.p, p->v6.p, dt, p->ctx->stream);
+    HIPCHK(hipGetLastError());
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_get_state(egs_problem *p, double *pos, double *R, double *v, double *w) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t n = p->n;
+    hipStream_t s = p->ctx->stream;
+    if (pos && n) HIPCHK(hipMemcpyAsync(pos, p->pos.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (R && n) HIPCHK(hipMemcpyAsync(R, p->R.p, n * 9 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (v && n) HIPCHK(hipMemcpyAsync(v, p->v.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (w && n) HIPCHK(hipMemcpyAsync(w, p->w.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return stall_seen(p) ? report_stall(p) : EGS_OK;
+  });
+}
+
+egs_status egs_problem_get_stats(egs_problem *p, egs_solve_stats *stats) {
+  if (!p || !stats) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    std::memset(stats, 0, sizeof *stats);
+    fill_stats(p, stats);
+    stats->iterations = p->last_iterations;
+    if (p->m == 0) return EGS_OK;
+    int flag = 0;
+    if (p->residual_pending) { launch_residual(p); p->residual_pending = false; }
+    stats->residual = read_residual(p, &flag);
+    stats->status = flag ? EGS_ERR_STALL : EGS_OK;
+    return flag ? fail(p->ctx, EGS_ERR_STALL, "device ordering wait timed out") : EGS_OK;
+  });
+}
+
+egs_status egs_solve_blocks(egs_context *ctx, int32_t n, const double *Minv, int32_t m, const int32_t *body0,
+                            const int32_t *body1, const double *J0, const double *J1, const uint8_t *is_eq,
+                            const double *lo, const double *hi, const double *rhs, const egs_solve_params *params,
+                            int32_t precision, double *x, egs_solve_stats *stats) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (m > 0 && (!Minv || !body0 || !body1 || !J0 || !J1 || !is_eq || !lo || !hi || !rhs || !x))
+    return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  egs_problem *p = nullptr;
+  egs_status st = oneshot_problem(ctx, n, m, body0, body1, precision, &p);
+  if (st != EGS_OK) return st;
+  st = egs_problem_set_blocks(p, Minv, J0, J1, is_eq, lo, hi, rhs);
+  egs_solve_stats local;
+  if (st == EGS_OK) st = egs_problem_solve(p, params, stats ? stats : &local);
+  if (st == EGS_OK && m > 0) st = egs_problem_get_lambda(p, x);
+  return st;
+}
+
+egs_status egs_problem_matvec(egs_problem *p, int32_t parts, double eps, double scale, const double *x, double *y) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status { return do_matvec(p, parts, eps, scale, x, y); });
+}
+
+egs_status egs_problem_get_matvec(egs_problem *p, double *y) {
+  if (!p || !y) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (!p->mv_ready) return fail(p->ctx, EGS_ERR_INVALID, "egs_problem_matvec first");
+    download_real(p, p->mv_y, y, (size_t)p->m * 3);
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_get_wres(egs_problem *p, double *w) {
+  if (!p || !w) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    download_real(p, p->wres, w, (size_t)p->m * 3);
+    return stall_seen(p) ? report_stall(p) : EGS_OK;
+  });
+}
+
+egs_status egs_matvec_blocks(egs_context *ctx, int32_t n, const double *Minv, int32_t m, const int32_t *body0,
+                             const int32_t *body1, const double *J0, const double *J1, int32_t parts, double eps,
+                             double scale, int32_t precision, const double *x, double *y) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (m > 0 && (!Minv || !body0 || !body1 || !J0 || !J1 || !x || !y)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  egs_problem *p = nullptr;
+  egs_status st = oneshot_problem(ctx, n, m, body0, body1, precision, &p);
+  if (st != EGS_OK) return st;
+  st = egs_problem_set_blocks(p, Minv, J0, J1, nullptr, nullptr, nullptr, nullptr);
+  if (st == EGS_OK) st = egs_problem_matvec(p, parts, eps, scale, x, y);
+  return st;
+}
+
+egs_status egs_problem_debug_trace(egs_problem *p, uint64_t *out, int64_t count, int32_t *sweeps) {
+  if (!p || !out) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (sweeps) *sweeps = p->trace_sweeps;
+    const int64_t have = (int64_t)p->trace_sweeps * p->m;
+    if (have <= 0 || count < have) return fail(p->ctx, EGS_ERR_INVALID, "no trace recorded (EGS_TRACE_UPDATES=1, an island on 4-lane patches) or buffer too small");
+    HIPCHK(hipMemcpyAsync(out, p->trace.p, (size_t)have * sizeof(uint64_t), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    return EGS_OK;
+  });
+}
+
+}  // extern "C"

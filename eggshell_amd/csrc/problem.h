@@ -1,0 +1,179 @@
+// problem.h -- the device-resident problem (struct egs_problem) and what the host units call on it: topology and
+// plan (problem.cpp), assembly and velocity update (problem.cpp), the solve driver (solve.cpp).  The dense and world
+// units use a problem through this header only.
+#pragma once
+
+#include "kernels.h"
+#include "matvec_plan.h"
+#include "plan.h"
+#include "runtime.h"
+
+namespace egs {
+
+// A plan's seven schedule tables on the device: lanes, the static timetable (plan.h), the tiles' body slots.
+struct DevicePlan {
+  DevBuf<LaneDesc> lanes;
+  DevBuf<uint16_t> lane_level;
+  DevBuf<int32_t> tile_period, tile_depth;
+  DevBuf<int32_t> tile_nslots, tile_slot_off, slot_body;
+  void stage(egs_context *ctx, const Plan &pl) {
+    egs::stage(ctx, lanes, pl.lanes);
+    egs::stage(ctx, lane_level, pl.lane_level);
+    egs::stage(ctx, tile_period, pl.tile_period);
+    egs::stage(ctx, tile_depth, pl.tile_depth);
+    egs::stage(ctx, tile_nslots, pl.tile_nslots);
+    egs::stage(ctx, tile_slot_off, pl.tile_slot_off);
+    egs::stage(ctx, slot_body, pl.slot_body);
+  }
+};
+// ... and the four of its oversize islands' body patches (ticket kernels: no timetable)
+struct DevicePatches {
+  DevBuf<LaneDesc> lanes;
+  DevBuf<int32_t> tile_nslots, tile_slot_off, slot_body;
+  void stage(egs_context *ctx, const Plan &pl) {
+    egs::stage(ctx, lanes, pl.patch_lanes);
+    egs::stage(ctx, tile_nslots, pl.patch_tile_nslots);
+    egs::stage(ctx, tile_slot_off, pl.patch_tile_slot_off);
+    egs::stage(ctx, slot_body, pl.patch_slot_body);
+  }
+};
+
+}  // namespace egs
+
+struct egs_problem {
+  egs_context *ctx = nullptr;
+  int n = 0, m = 0, precision = EGS_F64;
+  egs::Plan plan;                     // 1 lane per constraint (built lazily when the quad schedule applies)
+  bool tile_plan_ready = false;
+  std::vector<int32_t> h_body0, h_body1;
+  egs::DevicePlan tile;          // plan's tables
+  // latency-optimised schedule (4 lanes per constraint, 64-constraint tiles);
+  // used for GS/SOR when the problem is small and every island fits a tile
+  egs::Plan planq;
+  bool use_quad = false;
+  uint32_t last_sched = 0;     // SweepSchedule::flags() of the last solve launch
+  bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
+                               // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
+  bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
+  int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
+  // which kernel takes the oversize islands of a GS / SOR solve (choose_oversize_schedule; EGS_PATCH=0
+  // forces the all-global kernel, EGS_QUAD_PATCH=0 the 1-lane patches) and how many workgroups the
+  // all-global kernel's persistent grid may have: both from the runtime's occupancy of the kernels
+  int oversize = 2;            // OversizeSchedule
+  int global_max_blocks = 1;
+  egs::DevicePlan quad;          // planq's tables
+  egs::DevBuf<unsigned char> wsB0, wsB1, wsD, wsInv;
+  egs::DevBuf<egs::GlobalDesc> gcons;
+  egs::DevBuf<uint32_t> gtickets;
+  egs::DevBuf<unsigned long long> trace;   // EGS_TRACE_UPDATES=1: [sweeps][m] completion times of the last patch launch
+  int trace_sweeps = 0;
+  egs::DevBuf<unsigned char> ggran;   // [n][6] x 16 B: data-tagged granules of the 4-lane body patches (quad_solve.hip)
+  uint32_t gran_epoch = 0;
+  // oversize islands as body patches (GS/SOR): LDS for private bodies, global for shared
+  egs::DevicePatches patch;
+  // topology + state (fp64)
+  egs::DevBuf<int32_t> body0, body1, kind;
+  egs::DevBuf<double> pos, R, v, w, Minv_d, f_ext, data, err, v6, res_partials;
+  egs::DevBuf<double> Wf;            // M^-1 f_ext per body, rebuilt when either is re-uploaded
+  bool wf_valid = false;
+  // solver arrays, REAL = double or float (byte buffers)
+  egs::DevBuf<unsigned char> Minv_r, J0, J1, lo, hi, rhs, x, acc, wres;
+  egs::DevBuf<unsigned char> gB0, gB1, gD, gden, gdx;  // cross-workgroup workspace
+  egs::DevBuf<uint8_t> is_eq;
+  // [0]: device-side ordering wait timed out (EGS_ERR_STALL).  STICKY: the solve kernels OR into
+  // it and only reporting it clears it, so a stall in any step of an asynchronous run is seen.
+  // [1]: scratch word of the isotropy check.
+  egs::DevBuf<int32_t> error_flag;
+  egs::PinnedBuf<int32_t> h_flag;   // page-locked copy of [0] (64 bytes), refreshed by an async copy after every solve
+  egs::PinnedBuf<double> h_hist;    // page-locked landing area of the stopping loop's per-sweep residual sums (+ the flag)
+  // per-sweep history of a chunk of sweeps (tolerance-terminated solves, see kernels.h)
+  egs::DevBuf<unsigned char> hist_x, hist_acc;
+  egs::DevBuf<double> hist_out;
+  int hist_sweeps = 0;        // 0: off for the next launch; k: record k sweeps
+  bool residual_pending = false;   // wres/x hold a finished solve whose residual sums were not reduced yet
+  bool have_blocks = false, have_state = false, have_constraints = false, minv_r_valid = false;
+  // stand-alone mat-vec (matvec_plan.h): schedule built at the first product after a topology change
+  egs::MatvecPlan mvplan;
+  bool mv_ready = false;
+  egs::DevBuf<egs::MvLane> mv_lanes;
+  egs::DevBuf<egs::MvTile> mv_tiles;
+  egs::DevBuf<egs::MvSlot> mv_slots;
+  egs::DevBuf<uint16_t> mv_ents;
+  egs::DevBuf<egs::MvBoundary> mv_boundary;
+  egs::DevBuf<unsigned char> mv_T, mv_x, mv_y;
+  egs::DevBuf<unsigned char> tmp_rows;   // [3m] REAL scratch
+  egs::DevBuf<double> dense_A;        // J M^-1 J^T + cfm I of the dense path (egs_problem_dense_system), [3m][3m]
+  double dense_cfm = -1.0;       // the cfm dense_A was built with (< 0: not built)
+  // row types and bounds of the assembled system on the host (the dense path partitions by them): they depend on the
+  // constraint kinds only (joints.cc:13-35, contact.cc:103-113), so they are read back once per set of kinds
+  std::vector<uint8_t> h_rows_eq;
+  std::vector<double> h_rows_lo, h_rows_hi;
+  bool h_rows_valid = false;
+  bool minv_iso = false;       // every M^-1 block is diag(a,a,a,b,b,b): the tile kernel keeps no B (EGS_ISO=0 disables)
+  int last_iterations = 0;
+  size_t real_size() const { return precision == EGS_F32 ? sizeof(float) : sizeof(double); }
+};
+
+namespace egs {
+
+// The precision of a problem's solver arrays as a type: f(float{}) or f(double{}).  The one place that turns
+// egs_problem::precision into a template argument; a callable that differs by precision in more than the type
+// (conversions, scale factors) does that inside.
+template <typename F>
+auto with_real(const egs_problem *p, F &&f) {
+  if (p->precision == EGS_F32) return f(float{});
+  return f(double{});
+}
+// a solver array (byte buffer) as the REAL array it holds
+template <typename REAL>
+REAL *real(const DevBuf<unsigned char> &b) { return reinterpret_cast<REAL *>(b.p); }
+
+// ---- problem.cpp ---------------------------------------------------------------------------------------------------
+egs_status check_topology(egs_context *ctx, int32_t n, int32_t m, const int32_t *body0, const int32_t *body1);
+void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const int32_t *body1, bool fresh = true);
+void ensure_tile_plan(egs_problem *p);
+void ensure_minv_real(egs_problem *p);
+void note_kinds(egs_problem *p, const int32_t *kind);
+void note_assembled(egs_problem *p);
+AssembleArgs assemble_args(egs_problem *p, double dt, double erp);
+void do_assemble(egs_problem *p, double dt, double erp);
+void do_velocity(egs_problem *p, double dt);
+void zero_accumulators(egs_problem *p);
+void post_flag_copy(egs_problem *p);
+egs_status report_stall(egs_problem *p);
+// Non-blocking look at the page-locked copy: true once the copy behind a stalled solve has
+// landed.  Entry points that enqueue more work call it first; entry points that have just
+// synchronised see every earlier solve.
+inline bool stall_seen(const egs_problem *p) { return p->h_flag.p && *static_cast<volatile int32_t *>(p->h_flag.p) != 0; }
+
+// ---- solve.cpp -----------------------------------------------------------------------------------------------------
+egs_status validate_params(egs_context *ctx, const egs_solve_params *prm);
+void fill_stats(egs_problem *p, egs_solve_stats *st);
+void launch_residual(egs_problem *p);
+double read_residual(egs_problem *p, int *err_flag);
+egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats, const AssembleArgs *assemble = nullptr);
+bool step_fuses_assembly(egs_problem *p, const egs_solve_params *prm);
+void accumulators_from_lambda(egs_problem *p);
+
+struct BatchSolveState {
+  EnsembleSegs segs;               // device tables (owned by the world)
+  DevBuf<int32_t> ints;            // running [E], iterations [E], n_running
+  DevBuf<double> res;              // residual [E]
+  DevBuf<double> err;              // [sweeps][E] of the last evaluation
+  DevBuf<unsigned char> fin_x, fin_acc;
+  PinnedBuf<int32_t> h_ints;       // page-locked: iterations [E], n_running, stall flag
+  PinnedBuf<double> h_res;         // page-locked: residual [E]
+  EnsembleStop stop() {
+    const size_t E = (size_t)segs.n_ens;
+    return EnsembleStop{ints.p, ints.p + E, res.p, ints.p + 2 * E};
+  }
+  void ensure(int E) {
+    ints.alloc(2 * (size_t)E + 1);
+    res.alloc((size_t)E);
+    h_ints.alloc((size_t)E + 2);
+    h_res.alloc((size_t)(E > 0 ? E : 1));
+  }
+};
+egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolveState &B, const int32_t *active = nullptr);
+
+}  // namespace egs

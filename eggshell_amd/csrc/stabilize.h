@@ -35,7 +35,7 @@ struct StabRelaxArgs {
 };
 void launch_stab_relax(const StabRelaxArgs &a, hipStream_t s);
 
-// Seeds a batched tolerance-terminated solve (capi.cpp: do_solve_batch) after its test of x0: an ensemble with
+// Seeds a batched tolerance-terminated solve (solve.cpp: do_solve_batch) after its test of x0: an ensemble with
 // active[e] == 0 stops running and leaves the count n_running (integer atomics only).  It is no longer tested and no
 // state of it is selected; the sweeps still cover it, as they cover every ensemble until the last one stops.
 void launch_stab_seed_running(int n_ens, const int32_t *active, int32_t *running, int32_t *n_running, hipStream_t s);

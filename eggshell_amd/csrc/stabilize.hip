@@ -1,6 +1,6 @@
 // stabilize.hip -- Ensemble::InitStabilize / PostStabilize (ensembles.cc:602-666) for every ensemble of a world
 // (egs_world_stabilize): the per-ensemble stopping test and the relaxation step.  The relaxation solve and the
-// list-order J^T y are the solve kernels' own (capi.cpp drives the loop).
+// list-order J^T y are the solve kernels' own (world.cpp drives the loop).
 #include "stabilize.h"
 
 #include "rotation_device.h"

@@ -29,14 +29,14 @@
 // load_cons leaves ONE linear block Jl = -J1_lin in J0_lin's registers and Bl = wl1 Jl, precomputed, in J1_lin's:
 // side 1's linear residual products take -Jl and the linear accumulator updates take +Bl (side 0) / -Bl (side 1), all
 // as source negations, which cost nothing.  An update forms only the 18 angular products w J on the fly instead of
-// 36.  Same roundings in the same order as the plain kernel: the same bits (capi.cpp decides the preconditions).
+// 36.  Same roundings in the same order as the plain kernel: the same bits (solve.cpp decides the preconditions).
 //
 // ASSEMBLE (LINSYM only): the prologue assembles the lane's constraint itself (assemble_device.h, the body of
 // assemble_kernel) instead of reading back what assemble_kernel wrote: the blocks go from the assembly's registers into
 // Cons, and load_cons (ASSEMBLED) finishes them.  The lane also stores J0, J1 (staged through LDS, stage_blocks), rhs,
 // lo, hi, err and is_eq where assemble_kernel puts them, with the same bits, for whatever reads the system after the
 // solve (get_blocks, the residual, matvec, later solves).  Nothing waits for these stores: they drain while the
-// timetable runs.  Every constraint of the problem is a lane of some tile (capi.cpp: no oversize islands), so all of
+// timetable runs.  Every constraint of the problem is a lane of some tile (solve.cpp: no oversize islands), so all of
 // them are written.
 #include <algorithm>
 
