@@ -37,7 +37,7 @@ EXPORTS = [
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
-    "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
+    "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
 ]
@@ -102,6 +102,35 @@ def debug_plan_patches(n_bodies, body0, body1):
     if st != OK:
         raise RuntimeError("egs_debug_plan_patches failed: %d" % st)
     return npat.value, cp, cl, r0, r1
+
+
+def lcp_batch_offsets(ns):
+    """Offsets of the packed batch layout of egs_box_lcp_batch / egs_box_lcp_schur_batch: problem k's vectors start at
+    vo[k] = sum_{j<k} n_j, its row-major matrix at ao[k] = sum_{j<k} n_j^2 (both int64, count + 1 entries)."""
+    ns = np.asarray(ns, np.int64)
+    return np.concatenate([[0], np.cumsum(ns)]).astype(np.int64), np.concatenate([[0], np.cumsum(ns * ns)]).astype(np.int64)
+
+
+def pack_lcp_batch(As, bs, los, his):
+    """Lists of matrices and vectors -> ns, A, b, lo, hi in the packed batch layout (host only)."""
+    ns = np.array([np.shape(b)[0] for b in bs], np.int32)
+    for k, a in enumerate(As):
+        if np.shape(a) != (ns[k], ns[k]):
+            raise ValueError("problem %d: matrix %s for %d rows" % (k, np.shape(a), ns[k]))
+    cat = lambda vs: np.concatenate([_f64(v).reshape(-1) for v in vs]) if len(vs) else np.zeros(0)
+    return ns, cat(As), cat(bs), cat(los), cat(his)
+
+
+def unpack_lcp_batch(ns, A=None, *vectors):
+    """The inverse of pack_lcp_batch: a list of n_k x n_k views of A (if given), then a list of n_k views per vector."""
+    vo, ao = lcp_batch_offsets(ns)
+    cnt = len(ns)
+    out = []
+    if A is not None:
+        out.append([A[ao[k]:ao[k + 1]].reshape(ns[k], ns[k]) for k in range(cnt)])
+    for v in vectors:
+        out.append([v[vo[k]:vo[k + 1]] for k in range(cnt)])
+    return out
 
 
 def params(method=GAUSS_SEIDEL, max_iters=500, tol=1e-9, cfm=0.0, omega=1.5, check_every=1):
@@ -289,6 +318,35 @@ class Context:
         if st not in (OK, ERR_LCP_FAILED):
             self.check(st)
         return bool(ok.value), x, w, A, perm, nub_out.value, piv.value
+
+
+    def box_lcp_schur_batch_packed(self, ns, A, b, lo, hi, algorithm=0, nubs=None, reference_quirks=True, max_iterations=0,
+                                   max_seconds=0.0):
+        """egs_box_lcp_schur_batch on packed arrays (see lcp_batch_offsets): returns ok, x, w, A (permuted in place, a
+        copy), perm of the partitions, nub, inner pivots -- packed the same way."""
+        ns = _i32(ns)
+        A = _f64(A).copy()
+        b, lo, hi = map(_f64, (b, lo, hi))
+        nubs = _i32(nubs)
+        tot, cnt = int(ns.sum()), len(ns)
+        if A.size != int((ns.astype(np.int64) ** 2).sum()) or any(v.size != tot for v in (b, lo, hi)) or (nubs is not None and nubs.size != cnt):
+            raise ValueError("packed arrays do not match the sizes")
+        x = np.zeros(tot); w = np.zeros(tot); perm = np.zeros(tot, np.int32)
+        ok = np.zeros(cnt, np.int32); nub_out = np.zeros(cnt, np.int32); piv = np.zeros(cnt, np.int32)
+        self.check(load().egs_box_lcp_schur_batch(self.h, C.c_int32(algorithm), C.c_int32(cnt), _p(ns), _p(A), _p(b), _p(lo), _p(hi),
+                                                  _p(nubs), C.c_int32(1 if reference_quirks else 0), C.c_int32(max_iterations),
+                                                  C.c_double(max_seconds), _p(x), _p(w), _p(perm), _p(ok), _p(nub_out), _p(piv)))
+        return ok, x, w, A, perm, nub_out, piv
+
+    def box_lcp_schur_batch(self, As, bs, los, his, algorithm=0, nubs=None, reference_quirks=True, max_iterations=0, max_seconds=0.0):
+        """lcp::SolveLCP under its default Settings (SolveLCP_BoxSchur) on `len(As)` independent problems in one call:
+        those of n <= 96 rows in one fused launch, larger ones one after another.  Returns lists ok, x, w, A (permuted in
+        place), perm, nub, pivots -- problem k's entries are those of box_lcp_schur on it."""
+        ns, A, b, lo, hi = pack_lcp_batch(As, bs, los, his)
+        ok, x, w, A, perm, nub, piv = self.box_lcp_schur_batch_packed(ns, A, b, lo, hi, algorithm, nubs, reference_quirks,
+                                                                      max_iterations, max_seconds)
+        Al, xl, wl, pl = unpack_lcp_batch(ns, A, x, w, perm)
+        return [bool(v) for v in ok], xl, wl, Al, pl, [int(v) for v in nub], [int(v) for v in piv]
 
 
 class Problem:

@@ -15,9 +15,13 @@
 // reference's element order on all lanes at once, so the pivot sequence -- and with it the permutation left in
 // A -- is the sequential algorithm's.  Every loop has an exit: a step cap (the caller's, else 20 n + 1000) and
 // an optional wall-clock limit (lcp::Settings::max_iterations / max_time, toolkit/lcp.h:161-167).
+// The solver bodies are __device__ functions (dantzig_solve, murty_solve) shared by these kernels and by
+// box_schur_kernel below: lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747) fused into one launch for a batch of
+// problems of n <= 96 rows (egs_box_lcp_schur_batch).
 #include "dense_lcp.h"
 
 #include <algorithm>
+#include <cstring>
 #include <stdexcept>
 #include <vector>
 
@@ -223,26 +227,36 @@ struct LcpView {
   }
 };
 
-// SolveLCP_BoxDantzig, toolkit/lcp.cc:444-619.
-template <int NT, bool GLOBAL>
-__global__ void __launch_bounds__(NT) box_dantzig_kernel(const LcpSet S) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = threadIdx.x;
-  const LcpView<NT, GLOBAL> V(S, smem, lane);
-  const int n = V.n;
-  double *A = V.A, *L = V.L;
-  double *x = V.vec, *w = x + n, *lo = w + n, *hi = lo + n, *b = hi + n, *dxS = b + n, *dwNS = dxS + n,
-         *limit = dwNS + n, *v = limit + n, *wq = v + n, *temp = wq + n;
-  int *perm = reinterpret_cast<int *>(temp + n), *flag = perm + 2 * n;
-  const double *gb = S.b + V.v_off, *glo = S.lo + V.v_off, *ghi = S.hi + V.v_off;
-  for (int k = lane; k < n * n; k += NT) { if (!GLOBAL) A[k] = V.gA[k]; L[k] = 0.0; }
-  for (int k = lane; k < n; k += NT) { x[k] = 0.0; w[k] = 0.0; lo[k] = glo[k]; hi[k] = ghi[k]; b[k] = gb[k]; perm[k] = k; }
-  wsync();
-  const int max_steps = S.max_steps > 0 ? S.max_steps : 20 * n + 1000;
-  const long long t0 = (long long)wall_clock64();
-  int reason = 0;
+// The LDS vectors of one inner solve: x, w, the bounds and right-hand side, six work vectors, the permutation(s)
+// and the clock flag.  The stand-alone kernels carve them from one block; the fused Schur kernel points lo / hi / b
+// at the vectors it already holds.
+struct LcpWork {
+  double *x, *w, *lo, *hi, *b, *s0, *s1, *s2, *s3, *s4, *s5;
+  int *perm, *iperm, *flag;
+};
+__device__ __forceinline__ LcpWork carve_work(double *vec, int n) {
+  LcpWork W;
+  W.x = vec; W.w = W.x + n; W.lo = W.w + n; W.hi = W.lo + n; W.b = W.hi + n; W.s0 = W.b + n; W.s1 = W.s0 + n; W.s2 = W.s1 + n;
+  W.s3 = W.s2 + n; W.s4 = W.s3 + n; W.s5 = W.s4 + n;
+  W.perm = reinterpret_cast<int *>(W.s5 + n); W.iperm = W.perm + n; W.flag = W.perm + 2 * n;
+  return W;
+}
 
-  int index = 0, steps = 0;
+// SolveLCP_BoxDantzig, toolkit/lcp.cc:444-619, on an n x n matrix (leading dimension n) the workgroup can write.
+// On entry: L = 0, x = w = 0, lo / hi / b loaded, perm = identity, everything visible.  On return x, w, lo, hi are in
+// the pivoting order perm describes (perm[k] = original index of final row k).
+template <int NT>
+__device__ bool dantzig_solve(double *A, double *L, int n, const LcpWork &W, int max_steps_arg, long long max_ticks, int lane,
+                              int &steps, int &reason) {
+  double *x = W.x, *w = W.w, *lo = W.lo, *hi = W.hi, *b = W.b, *dxS = W.s0, *dwNS = W.s1, *limit = W.s2, *v = W.s3, *wq = W.s4,
+         *temp = W.s5;
+  int *perm = W.perm, *flag = W.flag;
+  const int max_steps = max_steps_arg > 0 ? max_steps_arg : 20 * n + 1000;
+  const long long t0 = (long long)wall_clock64();
+  reason = 0;
+
+  int index = 0;
+  steps = 0;
   bool ok = true;
   for (int i = 0; i < n && ok; ++i) {
     double s = 0.0;
@@ -261,7 +275,7 @@ __global__ void __launch_bounds__(NT) box_dantzig_kernel(const LcpSet S) {
     const double delta_xi = dir;
     while (true) {
       if (++steps > max_steps) { ok = false; reason = 1; break; }
-      if (out_of_time(t0, S.max_ticks, flag, lane)) { ok = false; reason = 3; break; }
+      if (out_of_time(t0, max_ticks, flag, lane)) { ok = false; reason = 3; break; }
       // delta_w on the rows outside the set, one lane per row, the row's products in column order
       for (int r = index + lane; r < i; r += NT) {
         double t = 0.0;
@@ -335,6 +349,25 @@ __global__ void __launch_bounds__(NT) box_dantzig_kernel(const LcpSet S) {
     }
   }
   wsync();
+  return ok;
+}
+
+template <int NT, bool GLOBAL>
+__global__ void __launch_bounds__(NT) box_dantzig_kernel(const LcpSet S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const LcpView<NT, GLOBAL> V(S, smem, lane);
+  const int n = V.n;
+  double *A = V.A, *L = V.L;
+  const LcpWork W = carve_work(V.vec, n);
+  double *x = W.x, *w = W.w, *lo = W.lo, *hi = W.hi, *b = W.b;
+  int *perm = W.perm;
+  const double *gb = S.b + V.v_off, *glo = S.lo + V.v_off, *ghi = S.hi + V.v_off;
+  for (int k = lane; k < n * n; k += NT) { if (!GLOBAL) A[k] = V.gA[k]; L[k] = 0.0; }
+  for (int k = lane; k < n; k += NT) { x[k] = 0.0; w[k] = 0.0; lo[k] = glo[k]; hi[k] = ghi[k]; b[k] = gb[k]; perm[k] = k; }
+  wsync();
+  int steps, reason;
+  const bool ok = dantzig_solve<NT>(A, L, n, W, S.max_steps, S.max_ticks, lane, steps, reason);
   for (int k = lane; k < n; k += NT) { S.x[V.v_off + perm[k]] = x[k]; S.w[V.v_off + perm[k]] = w[k]; if (S.perm) S.perm[V.v_off + k] = perm[k]; }
   if (!GLOBAL)
     for (int k = lane; k < n * n; k += NT) {
@@ -365,37 +398,26 @@ __device__ bool cholesky(double *L, int n, int lane) {
 }
 
 // SolveLCP_BoxMurty on a LinearReducer (toolkit/lcp.cc:213-328, 380-442); SolveLCP_Murty (:333-378) is the same loop
-// with lo = 0, hi = +inf.
-template <int NT, bool GLOBAL>
-__global__ void __launch_bounds__(NT) box_murty_kernel(const LcpSet S) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = threadIdx.x;
-  const LcpView<NT, GLOBAL> V(S, smem, lane);
-  const int n = V.n;
-  double *A = V.A, *L = V.L;
-  double *x = V.vec, *w = x + n, *lo = w + n, *hi = lo + n, *b = hi + n, *xs = b + n, *c = xs + n, *c2 = c + n,
-         *t = c2 + n, *wq = t + n, *temp = wq + n;
-  int *perm = reinterpret_cast<int *>(temp + n), *iperm = perm + n, *flag = iperm + n;
-  const double *gb = S.b + V.v_off, *glo = S.lo + V.v_off, *ghi = S.hi + V.v_off;
-  for (int k = lane; k < n * n; k += NT) {
-    const int r = k / n, q = k - r * n;
-    const double a = V.gA[k];
-    if (!GLOBAL) A[k] = a;
-    L[k] = (q <= r) ? a : 0.0;
-  }
-  for (int k = lane; k < n; k += NT) { x[k] = 0.0; w[k] = 0.0; lo[k] = glo[k]; hi[k] = ghi[k]; b[k] = gb[k]; xs[k] = gb[k]; c[k] = 0.0; perm[k] = k; iperm[k] = k; }
-  wsync();
-  const int max_iterations = S.max_steps > 0 ? S.max_steps : 20 * n + 1000;
+// with lo = 0, hi = +inf.  On entry: L = the lower triangle of A (0 above it), x = w = 0, lo / hi / b loaded, s0 (xs) = b,
+// s1 (c) = 0, perm = iperm = identity.  x and w come back in the caller's order; returns "no factor broke down",
+// solved = the loop ended on a solution.
+template <int NT>
+__device__ bool murty_solve(double *A, double *L, int n, const LcpWork &W, int max_steps_arg, long long max_ticks, int lane,
+                            int &it, int &reason, bool &solved) {
+  double *x = W.x, *w = W.w, *lo = W.lo, *hi = W.hi, *b = W.b, *xs = W.s0, *c = W.s1, *c2 = W.s2, *t = W.s3, *wq = W.s4, *temp = W.s5;
+  int *perm = W.perm, *iperm = W.iperm, *flag = W.flag;
+  const int max_iterations = max_steps_arg > 0 ? max_steps_arg : 20 * n + 1000;
   const long long t0 = (long long)wall_clock64();
-  int reason = 0;
+  reason = 0;
   // LinearReducer::LinearReducer (:213-224): factor all of A, xs = A^-1 b
   bool ok = cholesky<NT>(L, n, lane);
   if (!ok) reason = 2;
   if (ok) lltsolve<NT>(L, n, n, xs, lane);
-  int index = n, it = 0;
-  bool solved = false;
+  int index = n;
+  it = 0;
+  solved = false;
   for (; ok && it < max_iterations; ++it) {
-    if (out_of_time(t0, S.max_ticks, flag, lane)) { ok = false; reason = 3; break; }
+    if (out_of_time(t0, max_ticks, flag, lane)) { ok = false; reason = 3; break; }
     // SubSolve (:245-296)
     wsync();
     if (index == 0) {
@@ -459,6 +481,31 @@ __global__ void __launch_bounds__(NT) box_murty_kernel(const LcpSet S) {
     wsync();
   }
   wsync();
+  return ok;
+}
+
+template <int NT, bool GLOBAL>
+__global__ void __launch_bounds__(NT) box_murty_kernel(const LcpSet S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const LcpView<NT, GLOBAL> V(S, smem, lane);
+  const int n = V.n;
+  double *A = V.A, *L = V.L;
+  const LcpWork W = carve_work(V.vec, n);
+  double *x = W.x, *w = W.w, *lo = W.lo, *hi = W.hi, *b = W.b, *xs = W.s0, *c = W.s1;
+  int *perm = W.perm, *iperm = W.iperm;
+  const double *gb = S.b + V.v_off, *glo = S.lo + V.v_off, *ghi = S.hi + V.v_off;
+  for (int k = lane; k < n * n; k += NT) {
+    const int r = k / n, q = k - r * n;
+    const double a = V.gA[k];
+    if (!GLOBAL) A[k] = a;
+    L[k] = (q <= r) ? a : 0.0;
+  }
+  for (int k = lane; k < n; k += NT) { x[k] = 0.0; w[k] = 0.0; lo[k] = glo[k]; hi[k] = ghi[k]; b[k] = gb[k]; xs[k] = gb[k]; c[k] = 0.0; perm[k] = k; iperm[k] = k; }
+  wsync();
+  int it, reason;
+  bool solved;
+  const bool ok = murty_solve<NT>(A, L, n, W, S.max_steps, S.max_ticks, lane, it, reason, solved);
   for (int k = lane; k < n; k += NT) { S.x[V.v_off + k] = x[k]; S.w[V.v_off + k] = w[k]; if (S.perm) S.perm[V.v_off + k] = perm[k]; }
   if (!GLOBAL)
     for (int k = lane; k < n * n; k += NT) {
@@ -470,6 +517,164 @@ __global__ void __launch_bounds__(NT) box_murty_kernel(const LcpSet S) {
     r.ok = (ok && solved) ? 1 : 0; r.pivots = it; r.reason = (ok && solved) ? 0 : (ok ? 1 : reason); r.pad = 0;
     S.res[V.prob] = r;
   }
+}
+
+// ---- lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747), fused: one workgroup (one wavefront) per problem of
+// n <= kDantzigMaxRows rows does the partition, the elimination of the unbounded rows, the box LCP on the Schur
+// complement and the back-substitution, all in LDS.  The operation order is the column-oriented one of the plain
+// restatement the tests check against: one accumulation chain per entry, terms in increasing k.
+struct SchurSet {
+  const int32_t *n;
+  const int64_t *a_off, *v_off;         // in doubles, per problem of this launch
+  double *A;                            // lower triangles permuted in place
+  const double *b, *lo, *hi;
+  const int32_t *nub;                   // >= 0: the reference's test hook, < 0: scan the bounds
+  double *x, *w;
+  int32_t *perm;                        // the partition's permutation
+  LcpResult *res;                       // pad = nub
+  int q6, max_steps;
+  long long max_ticks;
+};
+
+// LDS of a problem of n rows: 2 n^2 doubles of matrices (L_Z nub^2 + Q nub ni + R ni^2 + the inner factor ni^2 for any
+// split nub + ni = n; A and its factor when nub = 0), 7 n outer and 8 n inner vectors, 4 n + 4 ints.
+constexpr int kSchurVectors = 15;
+__host__ __device__ constexpr size_t schur_lds_bytes(int n) {
+  return (2 * (size_t)n * n + kSchurVectors * (size_t)n) * sizeof(double) + (4 * (size_t)n + 4) * sizeof(int);
+}
+
+template <int ALG>      // 0 = SolveLCP_BoxMurty inside, 1 = SolveLCP_BoxDantzig
+__global__ void __launch_bounds__(64) box_schur_kernel(const SchurSet S) {
+  constexpr int NT = 64;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x, prob = blockIdx.x;
+  const int n = S.n[prob];
+  double *gA = S.A + S.a_off[prob];
+  const long long vo = S.v_off[prob];
+  double *M = reinterpret_cast<double *>(smem);
+  double *ob = M + 2 * (size_t)n * n, *olo = ob + n, *ohi = olo + n, *t = ohi + n, *rhs = t + n, *z = rhs + n, *zw = z + n;
+  LcpWork W;
+  W.x = zw + n; W.w = W.x + n; W.s0 = W.w + n; W.s1 = W.s0 + n; W.s2 = W.s1 + n; W.s3 = W.s2 + n; W.s4 = W.s3 + n; W.s5 = W.s4 + n;
+  int *operm = reinterpret_cast<int *>(W.s5 + n);
+  W.perm = operm + n; W.iperm = W.perm + n; W.flag = W.iperm + n;
+  const double big = 1.7976931348623157e308, inf = __builtin_huge_val();
+
+  for (int k = lane; k < n; k += NT) { ob[k] = S.b[vo + k]; olo[k] = S.lo[vo + k]; ohi[k] = S.hi[vo + k]; operm[k] = k; }
+  wsync();
+  // the partition (:652-683): every lane walks the two pointers, the swaps are shared out
+  int nub = S.nub[prob];
+  if (nub < 0) {
+    nub = 0;
+    int nb = n - 1;
+    while (true) {
+      for (; nub <= nb; ++nub) if (S.q6 ? (olo[nub] > -big || ohi[nub] < -big) : (olo[nub] > -big || ohi[nub] < big)) break;
+      for (; nb >= nub; --nb) if (S.q6 ? (olo[nb] <= -big && ohi[nb] >= -big) : (olo[nb] <= -big && ohi[nb] >= big)) break;
+      if (nub > nb) break;
+      swap_rows_and_columns<NT>(gA, n, nub, nb, operm, lane);
+      swap_entry(ob, nub, nb, lane); swap_entry(olo, nub, nb, lane); swap_entry(ohi, nub, nb, lane);
+      wsync();
+    }
+  }
+  const int ni = n - nub;
+  // "infinity" is DBL_MAX or the real one (toolkit/lcp.h:149-150): the inner solver sees the real one
+  for (int k = nub + lane; k < n; k += NT) { if (olo[k] <= -big) olo[k] = -inf; if (ohi[k] >= big) ohi[k] = inf; }
+  for (int k = lane; k < n; k += NT) { S.perm[vo + k] = operm[k]; z[k] = 0.0; zw[k] = 0.0; }
+  W.lo = olo + nub; W.hi = ohi + nub; W.b = (nub == 0) ? ob : rhs;
+  for (int k = lane; k < ni; k += NT) { W.x[k] = 0.0; W.w[k] = 0.0; W.perm[k] = k; W.iperm[k] = k; }
+  wsync();
+
+  int steps = 0, reason = 0;
+  bool ok = true;
+  double *A = M, *L = M + (size_t)n * n;      // the inner solver's matrix and factor; reseated below when 0 < nub < n
+  if (nub == n) {
+    // x = A.llt().solve(b), w = 0 (:687-692)
+    for (int k = lane; k < n * n; k += NT) { const int r = k / n, q = k - r * n; M[k] = (q <= r) ? gA[k] : 0.0; }
+    for (int k = lane; k < n; k += NT) z[k] = ob[k];
+    wsync();
+    ok = cholesky<NT>(M, n, lane);
+    if (ok) lltsolve<NT>(M, n, n, z, lane);
+    else reason = 2;
+  } else {
+    if (nub == 0) {
+      for (int k = lane; k < n * n; k += NT) A[k] = gA[k];
+    } else {
+      double *LZ = M, *Q = LZ + (size_t)nub * nub, *R = Q + (size_t)nub * ni;
+      A = R; L = R + (size_t)ni * ni;
+      for (int k = lane; k < nub * nub; k += NT) { const int r = k / nub, q = k - r * nub; LZ[k] = (q <= r) ? gA[(size_t)r * n + q] : 0.0; }
+      wsync();
+      ok = cholesky<NT>(LZ, nub, lane);                          // L L' = Z
+      if (!ok) reason = 2;
+      if (ok) {
+        for (int j = lane; j < ni; j += NT) {                    // Q = L^-1 B', a lane per column of B' (row of B)
+          const double *brow = gA + (size_t)(nub + j) * n;
+          for (int k = 0; k < nub; ++k) Q[k * ni + j] = brow[k];
+          for (int c = 0; c < nub; ++c) {
+            const double xc = Q[c * ni + j] / LZ[c * nub + c];
+            Q[c * ni + j] = xc;
+            for (int k = c + 1; k < nub; ++k) Q[k * ni + j] = Q[k * ni + j] - LZ[k * nub + c] * xc;
+          }
+        }
+        for (int k = lane; k < nub; k += NT) t[k] = ob[k];
+        wsync();
+        for (int e = lane; e < ni * ni; e += NT) {               // R = C - Q'Q, lower triangle (:717-719)
+          const int i = e / ni, j = e - i * ni;
+          double r = 0.0;
+          if (j <= i) {
+            double sum = 0.0;
+            for (int k = 0; k < nub; ++k) sum = sum + Q[k * ni + i] * Q[k * ni + j];
+            r = gA[(size_t)(nub + i) * n + nub + j] - sum;
+          }
+          R[e] = r;
+        }
+        lltsolve<NT>(LZ, nub, nub, t, lane);                     // t = Z^-1 c
+        for (int i = lane; i < ni; i += NT) {                    // rhs = d - B t
+          const double *brow = gA + (size_t)(nub + i) * n;
+          double sum = 0.0;
+          for (int k = 0; k < nub; ++k) sum = sum + brow[k] * t[k];
+          rhs[i] = ob[nub + i] - sum;
+        }
+        wsync();
+      }
+    }
+    if (ok) {
+      if (ALG == 1) {
+        for (int k = lane; k < ni * ni; k += NT) L[k] = 0.0;
+        wsync();
+        ok = dantzig_solve<NT>(A, L, ni, W, S.max_steps, S.max_ticks, lane, steps, reason);
+        if (ok) for (int k = lane; k < ni; k += NT) { z[W.perm[k]] = W.x[k]; zw[W.perm[k]] = W.w[k]; }
+      } else {
+        for (int k = lane; k < ni * ni; k += NT) { const int r = k / ni, q = k - r * ni; L[k] = (q <= r) ? A[k] : 0.0; }
+        for (int k = lane; k < ni; k += NT) { W.s0[k] = W.b[k]; W.s1[k] = 0.0; }
+        wsync();
+        bool solved = false;
+        ok = murty_solve<NT>(A, L, ni, W, S.max_steps, S.max_ticks, lane, steps, reason, solved);
+        if (ok && !solved) { ok = false; reason = 1; }
+        if (ok || nub == 0) for (int k = lane; k < ni; k += NT) { z[k] = W.x[k]; zw[k] = W.w[k]; }
+      }
+      wsync();
+      if (nub == 0) {
+        // entirely an LCP (:695-700): the inner solver's pivoting order stays in the caller's lower triangle
+        for (int k = lane; k < n * n; k += NT) { const int r = k / n, q = k - r * n; if (q <= r) gA[k] = A[k]; }
+      } else if (ok) {
+        for (int k = lane; k < nub; k += NT) {                   // y = Z^-1 (c - B' z)
+          double sum = 0.0;
+          for (int i = 0; i < ni; ++i) sum = sum + gA[(size_t)(nub + i) * n + k] * z[i];
+          t[k] = ob[k] - sum;
+        }
+        wsync();
+        lltsolve<NT>(M, nub, nub, t, lane);
+      }
+    }
+  }
+  wsync();
+  // Unpermute (:741-744); a problem that failed after the partition reports zeros
+  if (nub == n) {
+    for (int k = lane; k < n; k += NT) { S.x[vo + k] = z[k]; S.w[vo + k] = 0.0; }
+  } else {
+    for (int k = lane; k < nub; k += NT) { S.x[vo + operm[k]] = ok ? t[k] : 0.0; S.w[vo + operm[k]] = 0.0; }
+    for (int k = lane; k < ni; k += NT) { S.x[vo + operm[nub + k]] = z[k]; S.w[vo + operm[nub + k]] = zw[k]; }
+  }
+  if (lane == 0) { LcpResult r; r.ok = ok ? 1 : 0; r.pivots = steps; r.reason = ok ? 0 : reason; r.pad = nub; S.res[prob] = r; }
 }
 
 #undef AT
@@ -601,6 +806,80 @@ void box_lcp_incremental_batch(hipStream_t stream, int algorithm, int count, con
     if (ok) ok[k] = r[k].ok;
     if (pivots) pivots[k] = r[k].pivots;
     if (reason) reason[k] = r[k].reason;
+  }
+}
+
+void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algorithm, int count, const int32_t *sel, const int32_t *n,
+                         const int64_t *a_off, const int64_t *v_off, double *A, const double *b, const double *lo, const double *hi,
+                         const int32_t *nub, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm,
+                         int32_t *ok, int32_t *nub_out, int32_t *pivots) {
+  if (algorithm != 0 && algorithm != 1) throw std::invalid_argument("SolveLCP_BoxSchur: algorithm 0 (Murty) or 1 (Cottle-Dantzig)");
+  if (count <= 0) return;
+  // one packed block, the same layout on both sides:  x w perm res | A | b lo hi a_off v_off n nub
+  // read back: everything up to the end of A; uploaded: everything from A on
+  size_t at = 0, vt = 0;
+  int n_max = 0;
+  for (int k = 0; k < count; ++k) {
+    const int nk = n[sel[k]];
+    if (nk < 1 || nk > kDantzigMaxRows) throw std::invalid_argument("SolveLCP_BoxSchur, fused: 1 <= n <= 96");
+    at += (size_t)nk * nk; vt += nk; n_max = std::max(n_max, nk);
+  }
+  const auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
+  const size_t o_x = 0, o_w = o_x + vt * 8, o_perm = o_w + vt * 8, o_res = up8(o_perm + vt * 4), o_A = o_res + (size_t)count * sizeof(LcpResult),
+               o_b = o_A + at * 8, o_lo = o_b + vt * 8, o_hi = o_lo + vt * 8, o_aoff = o_hi + vt * 8, o_voff = o_aoff + (size_t)count * 8,
+               o_n = o_voff + (size_t)count * 8, o_nub = o_n + (size_t)count * 4, total = o_nub + (size_t)count * 4;
+  char *h = static_cast<char *>(hooks.take(hooks.self, total));
+  double *hA = reinterpret_cast<double *>(h + o_A), *hb = reinterpret_cast<double *>(h + o_b), *hlo = reinterpret_cast<double *>(h + o_lo),
+         *hhi = reinterpret_cast<double *>(h + o_hi);
+  int64_t *haoff = reinterpret_cast<int64_t *>(h + o_aoff), *hvoff = reinterpret_cast<int64_t *>(h + o_voff);
+  int32_t *hn = reinterpret_cast<int32_t *>(h + o_n), *hnub = reinterpret_cast<int32_t *>(h + o_nub);
+  size_t ap = 0, vp = 0;
+  for (int k = 0; k < count; ++k) {
+    const int j = sel[k], nk = n[j];
+    std::memcpy(hA + ap, A + a_off[j], (size_t)nk * nk * sizeof(double));
+    std::memcpy(hb + vp, b + v_off[j], nk * sizeof(double));
+    std::memcpy(hlo + vp, lo + v_off[j], nk * sizeof(double));
+    std::memcpy(hhi + vp, hi + v_off[j], nk * sizeof(double));
+    haoff[k] = (int64_t)ap; hvoff[k] = (int64_t)vp; hn[k] = nk; hnub[k] = nub ? nub[j] : -1;
+    ap += (size_t)nk * nk; vp += nk;
+  }
+  DBuf<char> d(total);
+  HIPCHK(hipMemcpyAsync(d.p + o_A, h + o_A, total - o_A, hipMemcpyHostToDevice, stream));
+  SchurSet S{};
+  S.n = reinterpret_cast<int32_t *>(d.p + o_n); S.nub = reinterpret_cast<int32_t *>(d.p + o_nub);
+  S.a_off = reinterpret_cast<int64_t *>(d.p + o_aoff); S.v_off = reinterpret_cast<int64_t *>(d.p + o_voff);
+  S.A = reinterpret_cast<double *>(d.p + o_A); S.b = reinterpret_cast<double *>(d.p + o_b);
+  S.lo = reinterpret_cast<double *>(d.p + o_lo); S.hi = reinterpret_cast<double *>(d.p + o_hi);
+  S.x = reinterpret_cast<double *>(d.p + o_x); S.w = reinterpret_cast<double *>(d.p + o_w);
+  S.perm = reinterpret_cast<int32_t *>(d.p + o_perm); S.res = reinterpret_cast<LcpResult *>(d.p + o_res);
+  S.q6 = q6 ? 1 : 0; S.max_steps = max_steps;
+  S.max_ticks = max_seconds > 0 ? (long long)(max_seconds * 1e8) + 1 : 0;
+  const size_t lds = schur_lds_bytes(n_max);
+  auto km = box_schur_kernel<0>;
+  auto kd = box_schur_kernel<1>;
+  const void *fn = algorithm == 1 ? reinterpret_cast<const void *>(kd) : reinterpret_cast<const void *>(km);
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (hooks.mark) hooks.mark(hooks.self, true);
+  if (algorithm == 1) hipLaunchKernelGGL(kd, dim3(count), dim3(64), lds, stream, S);
+  else hipLaunchKernelGGL(km, dim3(count), dim3(64), lds, stream, S);
+  HIPCHK(hipGetLastError());
+  if (hooks.mark) hooks.mark(hooks.self, false);
+  HIPCHK(hipMemcpyAsync(h, d.p, o_A + at * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  const double *hx = reinterpret_cast<double *>(h + o_x), *hw = reinterpret_cast<double *>(h + o_w);
+  const int32_t *hperm = reinterpret_cast<int32_t *>(h + o_perm);
+  const LcpResult *hres = reinterpret_cast<LcpResult *>(h + o_res);
+  for (int k = 0; k < count; ++k) {
+    const int j = sel[k], nk = n[j];
+    double *Ak = A + a_off[j];
+    const double *Hk = hA + haoff[k];
+    for (int r = 0; r < nk; ++r) std::memcpy(Ak + (size_t)r * nk, Hk + (size_t)r * nk, (size_t)(r + 1) * sizeof(double));   // the lower triangle only
+    std::memcpy(x + v_off[j], hx + hvoff[k], nk * sizeof(double));
+    std::memcpy(w + v_off[j], hw + hvoff[k], nk * sizeof(double));
+    if (perm) std::memcpy(perm + v_off[j], hperm + hvoff[k], nk * sizeof(int32_t));
+    ok[j] = hres[k].ok;
+    if (nub_out) nub_out[j] = hres[k].pad;
+    if (pivots) pivots[j] = hres[k].pivots;
   }
 }
 

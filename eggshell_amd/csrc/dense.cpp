@@ -4,6 +4,8 @@
 #include "dense_lcp.h"
 #include "problem.h"
 
+#include <limits>
+
 using namespace egs;
 
 namespace {
@@ -225,6 +227,66 @@ egs_status egs_box_lcp_schur(egs_context *ctx, int32_t n, double *A, const doubl
                                     x, w, perm, &nub_found, &piv, &msg);
     if (nub_out) *nub_out = nub_found;
     return lcp_result(ctx, good, piv, msg, "SolveLCP_BoxSchur did not reach a solution", ok, pivots);
+  });
+}
+
+egs_status egs_box_lcp_schur_batch(egs_context *ctx, int32_t algorithm, int32_t count, const int32_t *n, double *A, const double *b,
+                                   const double *lo, const double *hi, const int32_t *nub, int32_t reference_quirks,
+                                   int32_t max_iterations, double max_seconds, double *x, double *w, int32_t *perm, int32_t *ok,
+                                   int32_t *nub_out, int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (count < 0 || (count > 0 && (!n || !A || !b || !lo || !hi || !x || !w || !ok))) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (algorithm != 0 && algorithm != 1) return fail(ctx, EGS_ERR_INVALID, "algorithm: 0 (Murty) or 1 (Cottle-Dantzig)");
+  if (count == 0) return EGS_OK;
+  // everything is checked before anything is written
+  const double big = std::numeric_limits<double>::max();
+  const bool q6 = reference_quirks != 0;
+  std::vector<int64_t> a_off(count), v_off(count);
+  std::vector<int32_t> fused, single;
+  int64_t at = 0, vt = 0;
+  for (int k = 0; k < count; ++k) {
+    const int nk = n[k];
+    if (nk < 1 || (nub && nub[k] > nk)) return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: n >= 1, nub <= n");
+    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: n too large");
+    a_off[k] = at; v_off[k] = vt;
+    const double *lk = lo + vt, *hk = hi + vt;
+    const int hook = nub ? nub[k] : -1;
+    for (int i = 0; i < nk; ++i) {
+      // the rows the partition leaves behind the unbounded ones (toolkit/lcp.cc:660-669) go to the inner solver
+      const bool bounded = hook >= 0 ? i >= hook : (q6 ? (lk[i] > -big || hk[i] < -big) : (lk[i] > -big || hk[i] < big));
+      if (!bounded) continue;
+      // lo <= 0 <= hi (toolkit/lcp.h:134); Dantzig also needs lo < hi (toolkit/lcp.cc:448-450)
+      if (!(lk[i] <= 0.0) || !(hk[i] >= 0.0) || (algorithm == 1 && !(lk[i] < hk[i])))
+        return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: the bounded rows need lo <= 0 <= hi (and lo < hi for Cottle-Dantzig)");
+    }
+    (nk <= kDantzigMaxRows ? fused : single).push_back(k);
+    at += (int64_t)nk * nk; vt += nk;
+  }
+  for (int k = 0; k < count; ++k) ok[k] = 0;
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    LaunchHooks hooks;
+    hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
+    hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
+    hooks.self = ctx;
+    if (!fused.empty()) {
+      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
+      ctx->pinned.reset();
+      box_lcp_schur_fused(ctx->stream, hooks, algorithm, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, lo, hi,
+                          nub, q6, max_iterations, max_seconds, x, w, perm, ok, nub_out, pivots);
+    }
+    // beyond the fused size: the single-problem path, one problem after another
+    for (const int k : single) {
+      int piv = 0, nub_found = 0;
+      std::string msg;
+      const bool good = box_lcp_schur(ctx->stream, n[k], A + a_off[k], b + v_off[k], lo + v_off[k], hi + v_off[k], algorithm,
+                                      nub ? nub[k] : -1, q6, max_iterations, max_seconds, x + v_off[k], w + v_off[k],
+                                      perm ? perm + v_off[k] : nullptr, &nub_found, &piv, &msg);
+      ok[k] = good ? 1 : 0;
+      if (nub_out) nub_out[k] = nub_found;
+      if (pivots) pivots[k] = piv;
+    }
+    return EGS_OK;     // per-problem outcome in ok[]
   });
 }
 

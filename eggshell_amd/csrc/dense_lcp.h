@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <string>
 
@@ -65,6 +66,23 @@ bool box_lcp_incremental_device(hipStream_t stream, int algorithm, int n, double
 bool box_lcp_schur(hipStream_t stream, int n, double *A, const double *b, const double *lo, const double *hi, int algorithm,
                    int nub_arg, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm, int *nub_out,
                    int *pivots, std::string *msg);
+
+// `count` SolveLCP_BoxSchur problems of n <= kDantzigMaxRows rows in ONE launch, a workgroup per problem with the
+// partition, the elimination, the inner box LCP and the back-substitution all on chip (dantzig.hip).  sel[k] = the
+// problem's number in the caller's packed arrays (n, nub, ok, nub_out, pivots indexed by it; its matrix at A +
+// a_off[sel[k]], its vectors at v_off[sel[k]]).  One upload, one launch, one read-back through page-locked memory
+// that `hooks.take` hands out (valid until the call returns); hooks.mark(begin) brackets the launch for the caller's
+// kernel timer (may be NULL).  The bounds must already satisfy lo <= 0 <= hi on the bounded rows.  Problems with more
+// rows are NOT fused: they go through box_lcp_schur one at a time.
+struct LaunchHooks {
+  void *(*take)(void *self, size_t bytes);
+  void (*mark)(void *self, bool begin);
+  void *self;
+};
+void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algorithm, int count, const int32_t *sel, const int32_t *n,
+                         const int64_t *a_off, const int64_t *v_off, double *A, const double *b, const double *lo, const double *hi,
+                         const int32_t *nub, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm,
+                         int32_t *ok, int32_t *nub_out, int32_t *pivots);
 
 // sparse::{Jacobi,GaussSeidel,SOR}Iteration on an explicit dense matrix (sparse_iterations.cc:72-144; dense_iter.hip):
 // A row-major n x n (n <= 1024), C / lo / hi as the reference's 5-argument overloads (all-equality for the 2-argument

@@ -227,6 +227,13 @@ struct Settings {
 int LastSolvePivots();             // principal pivots of the most recent SolveLCP
 bool SolveLCP(const Settings &settings, MatrixXd &A, const VectorXd &b, const VectorXd &lo, const VectorXd &hi,
               VectorXd *x, VectorXd *w);
+// SolveLCP on many independent problems in one library call, with the same dispatch and refusals applied to the
+// whole batch: default settings -> egs_box_lcp_schur_batch (problems of up to 96 rows fused into one launch, a
+// workgroup per problem; larger ones one after another inside the call), schur_complement = false ->
+// egs_box_lcp_batch.  Each (*A)[k] is left as SolveLCP leaves it; returns SolveLCP's bool per problem.
+std::vector<bool> SolveLCPBatch(const Settings &settings, std::vector<MatrixXd> *A, const std::vector<VectorXd> &b,
+                                const std::vector<VectorXd> &lo, const std::vector<VectorXd> &hi, std::vector<VectorXd> *x,
+                                std::vector<VectorXd> *w);
 }  // namespace lcp
 
 class Ensemble {  // ensembles.h:25-186

@@ -168,3 +168,78 @@ bool lcp::SolveLCP(const Settings &settings, MatrixXd &A, const VectorXd &b, con
   if (st != EGS_OK && st != EGS_ERR_LCP_FAILED) throw egs::Error(st, egs_last_error(egs::DefaultContext()));
   return ok != 0;
 }
+
+// The dispatch of toolkit/lcp.cc:752-785 applied to a whole batch: one library call for all the problems.
+std::vector<bool> lcp::SolveLCPBatch(const Settings &settings, std::vector<MatrixXd> *A, const std::vector<VectorXd> &b,
+                                     const std::vector<VectorXd> &lo, const std::vector<VectorXd> &hi, std::vector<VectorXd> *x,
+                                     std::vector<VectorXd> *w) {
+  if (!A || !x || !w || b.size() != A->size() || lo.size() != A->size() || hi.size() != A->size())
+    throw egs::Error(EGS_ERR_INVALID, "SolveLCPBatch: one A, b, lo and hi per problem");
+  if (settings.schur_complement && !settings.box_lcp)
+    throw egs::Error(EGS_ERR_INVALID, "Schur complement solver only available for box LCP");
+  if (!settings.schur_complement && settings.algorithm == COTTLE_DANTZIG && !settings.box_lcp)
+    throw egs::Error(EGS_ERR_INVALID, "Cottle Dantzig solver only available for box LCP");
+  if (settings.algorithm != MURTY && settings.algorithm != COTTLE_DANTZIG) throw egs::Error(EGS_ERR_INVALID, "Unknown LCP solver selection");
+  const int count = (int)A->size();
+  std::vector<int32_t> n(count);
+  size_t at = 0, vt = 0;
+  bool beyond = false;      // a problem the incremental solvers do not take (schur_complement = false only)
+  for (int k = 0; k < count; ++k) {
+    const MatrixXd &Ak = (*A)[k];
+    const int N = b[k].size();
+    if (Ak.rows() != Ak.cols() || Ak.rows() <= 0 || Ak.rows() != N || lo[k].size() != N || hi[k].size() != N)
+      throw egs::Error(EGS_ERR_INVALID, "SolveLCPBatch: A must be square and non-empty, b / lo / hi of its size");
+    n[k] = N; at += (size_t)N * N; vt += N;
+    if (N > 1024) beyond = true;
+  }
+  x->assign(count, VectorXd()); w->assign(count, VectorXd());
+  std::vector<bool> result(count, false);
+  if (count == 0) return result;
+  if (!settings.schur_complement && beyond) {      // SolveLCP's own route beyond 1024 rows, problem by problem
+    for (int k = 0; k < count; ++k) result[k] = SolveLCP(settings, (*A)[k], b[k], lo[k], hi[k], &(*x)[k], &(*w)[k]);
+    return result;
+  }
+  const double inf = std::numeric_limits<double>::infinity();
+  const int max_it = settings.max_iterations >= __INT_MAX__ ? 0 : std::max(settings.max_iterations, 1);
+  const double max_sec = settings.max_time >= __DBL_MAX__ ? 0.0 : settings.max_time;
+  const int algorithm = settings.algorithm == COTTLE_DANTZIG ? 1 : 0;
+  // the packed layout of the batch entries: matrices back to back, vectors back to back
+  std::vector<double> pA(at), pb(vt), plo(vt), phi(vt), px(vt), pw(vt);
+  std::vector<int32_t> ok(count, 0), pivots(count, 0);
+  at = vt = 0;
+  for (int k = 0; k < count; ++k) {
+    const int N = n[k];
+    std::copy((*A)[k].data(), (*A)[k].data() + (size_t)N * N, pA.begin() + at);
+    for (int i = 0; i < N; ++i) {
+      pb[vt + i] = b[k](i);
+      double l = lo[k](i), h = hi[k](i);
+      if (!settings.schur_complement) {
+        if (!settings.box_lcp) { l = 0.0; h = inf; }     // toolkit/lcp.h:152-154
+        if (l <= -__DBL_MAX__) l = -inf;                 // "infinity" is DBL_MAX or the real one (toolkit/lcp.h:149-150)
+        if (h >= __DBL_MAX__) h = inf;
+      }
+      plo[vt + i] = l; phi[vt + i] = h;
+    }
+    at += (size_t)N * N; vt += N;
+  }
+  egs_context *ctx = egs::DefaultContext();
+  const egs_status st = settings.schur_complement
+      ? egs_box_lcp_schur_batch(ctx, algorithm, count, n.data(), pA.data(), pb.data(), plo.data(), phi.data(), /*nub: scan*/ nullptr,
+                                settings.reference_quirks ? 1 : 0, max_it, max_sec, px.data(), pw.data(), nullptr, ok.data(), nullptr,
+                                pivots.data())
+      : egs_box_lcp_batch(ctx, algorithm, count, n.data(), pA.data(), pb.data(), plo.data(), phi.data(), max_it, max_sec, px.data(),
+                          pw.data(), nullptr, ok.data(), pivots.data());
+  if (st != EGS_OK) throw egs::Error(st, egs_last_error(ctx));
+  at = vt = 0;
+  for (int k = 0; k < count; ++k) {
+    const int N = n[k];
+    for (int r = 0; r < N; ++r)      // only the lower triangle is ever written (toolkit/lcp.h:73)
+      for (int c = 0; c <= r; ++c) (*A)[k](r, c) = pA[at + (size_t)r * N + c];
+    (*x)[k].resize(N); (*w)[k].resize(N);
+    for (int i = 0; i < N; ++i) { (*x)[k](i) = px[vt + i]; (*w)[k](i) = pw[vt + i]; }
+    result[k] = ok[k] != 0;
+    at += (size_t)N * N; vt += N;
+  }
+  g_last_lcp_pivots = count ? pivots[count - 1] : 0;
+  return result;
+}

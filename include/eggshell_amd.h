@@ -501,6 +501,25 @@ egs_status egs_box_lcp_schur(egs_context *ctx, int32_t n, double *A, const doubl
                              int32_t max_iterations, double max_seconds, double *x, double *w, int32_t *perm,
                              int32_t *ok, int32_t *nub_out, int32_t *pivots);
 
+/* egs_box_lcp_schur on `count` independent problems -- what a batch of ensembles hands lcp::SolveLCP under its
+ * DEFAULT Settings.  Packing as egs_box_lcp_batch: problem k has n[k] rows, its matrix at A + sum_{j<k} n[j]^2,
+ * its vectors (b, lo, hi, x, w, perm) at sum_{j<k} n[j].  Per problem the semantics are exactly those of
+ * egs_box_lcp_schur: only the lower triangle is read or written, perm is the partition's permutation, pivots[k] the
+ * inner solver's steps, nub_out[k] = test_nub_from_SolveLCP_BoxSchur; nub[k] >= 0 is the test hook, nub = NULL (or
+ * nub[k] < 0) scans the bounds.  reference_quirks, max_iterations and max_seconds hold for every problem of the call.
+ * Problems of n <= 96 rows are FUSED: one upload, ONE launch with a workgroup per problem (partition, Z = L L',
+ * the Schur complement, the inner box LCP and the back-substitution all in LDS, in the operation order of the plain
+ * column-oriented algorithm), one read-back, through page-locked staging of the context.  Problems with more rows
+ * are not fused: they run inside the same call, one after another, on the egs_box_lcp_schur path.
+ * Returns EGS_OK when every problem was run -- outcomes in ok[k] (0: the inner solver gave up or Z is not
+ * positive definite; x and w of such a problem are not meaningful).  EGS_ERR_INVALID, nothing written: a size < 1,
+ * nub[k] > n[k], or a bounded row that breaks lo <= 0 <= hi (lo < hi for Dantzig).  count = 0 is EGS_OK.
+ * perm, nub_out, pivots may be NULL.                                                                          */
+egs_status egs_box_lcp_schur_batch(egs_context *ctx, int32_t algorithm, int32_t count, const int32_t *n, double *A,
+                                   const double *b, const double *lo, const double *hi, const int32_t *nub,
+                                   int32_t reference_quirks, int32_t max_iterations, double max_seconds, double *x,
+                                   double *w, int32_t *perm, int32_t *ok, int32_t *nub_out, int32_t *pivots);
+
 /* ---- diagnostics (host only, needs no GPU) -------------------------------
  * The schedule the solver derives from the constraint graph: islands, the
  * workgroup tile each constraint lands in (-1 = cross-workgroup path) and the
