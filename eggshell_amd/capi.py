@@ -40,6 +40,7 @@ EXPORTS = [
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
+    "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
 ]
 
 
@@ -226,6 +227,17 @@ class Context:
         self.check(load().egs_update_contacts(self.h, C.c_int32(n), _p(pos), _p(R), _p(side), C.c_int32(cap),
                                               C.byref(m), _p(b0), _p(b1), _p(data)))
         return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
+
+    def relax_blocks_direct(self, n_bodies, body0, body1, J0, J1, err, rank_tol=0.0):
+        """(J J^T) y = err by the rank-revealing LDL^T of the direct relaxation route (egs_relax_blocks_direct):
+        y [3m] (0 on the rows the truncation left) and the rank."""
+        body0, body1 = _i32(body0), _i32(body1)
+        J0, J1, err = _f64(J0), _f64(J1), _f64(err)
+        m = body0.shape[0]
+        y = np.zeros(3 * m); rank = C.c_int32(0)
+        self.check(load().egs_relax_blocks_direct(self.h, C.c_int32(n_bodies), C.c_int32(m), _p(body0), _p(body1), _p(J0),
+                                                  _p(J1), _p(err), C.c_double(rank_tol), _p(y), C.byref(rank)))
+        return y, rank.value
 
     def mixed_constraints_solve(self, A, b, Ceq, lo, hi, use_bounds=0, max_pivots=0, max_seconds=0.0):
         A, b, lo, hi = map(_f64, (A, b, lo, hi))
@@ -653,6 +665,23 @@ class World:
                                                   C.c_int32(1 if detect_contacts else 0),
                                                   C.byref(params) if params is not None else None, C.byref(nu)))
         return nu.value
+
+    def stabilize_direct(self, mode, max_steps=0, detect_contacts=True, rank_tol=0.0):
+        """stabilize() with the relaxation system solved directly on the device, a workgroup per ensemble
+        (egs_world_stabilize_direct): a pivoted LDL^T truncated at the first pivot <= rank_tol * |first pivot|
+        (0: 1e-10).  Returns how many ensembles ended with err_sq > 1e-9; stabilize_info() / stabilize_rank()."""
+        nu = C.c_int32(0)
+        self.ctx.check(load().egs_world_stabilize_direct(self.h, C.c_int32(mode), C.c_int32(max_steps),
+                                                         C.c_int32(1 if detect_contacts else 0), C.c_double(rank_tol),
+                                                         C.byref(nu)))
+        return nu.value
+
+    def stabilize_rank(self):
+        """Per-ensemble figures of the last stabilize_direct: rows of the system and the rank of the last pass solved [E]."""
+        E = self.n_ensembles
+        rows = np.zeros(E, np.int32); rank = np.zeros(E, np.int32)
+        self.ctx.check(load().egs_world_stabilize_rank(self.h, C.c_int32(E), _p(rows), _p(rank)))
+        return dict(rows=rows, rank=rank)
 
     def stabilize_info(self):
         """Per-ensemble figures of the last stabilize: relaxation steps and the final err_sq [E]."""

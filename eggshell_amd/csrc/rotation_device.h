@@ -1,6 +1,6 @@
 // rotation_device.h -- R <- WtoR(w, dt) R on the device (utils.cc:82-89: the quaternion of the rotation by |w| dt
 // about w, as a matrix), the arithmetic of the CPU oracle's orc_w_to_R and quat_to_R.  Shared by the integrators:
-// advance_kernel (StepPositions_ODE, kernels.hip) and stab_relax_kernel (StepPositions_ExplicitEuler, stabilize.hip).
+// advance_kernel (StepPositions_ODE, kernels.hip) and stab_relax_body (StepPositions_ExplicitEuler, stabilize_device.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

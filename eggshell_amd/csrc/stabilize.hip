@@ -3,7 +3,7 @@
 // list-order J^T y are the solve kernels' own (world.cpp drives the loop).
 #include "stabilize.h"
 
-#include "rotation_device.h"
+#include "stabilize_device.h"
 
 namespace egs {
 
@@ -48,18 +48,11 @@ __global__ void __launch_bounds__(256) stab_relax_kernel(StabRelaxArgs a) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.n) return;
   if (!a.active[a.ens ? a.ens[b] : 0]) return;
-  double vr[6];
+  double acc[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) vr[k] = a.acc[(size_t)b * 6 + k] * a.scale;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) a.pos[(size_t)b * 3 + k] = a.pos[(size_t)b * 3 + k] + a.h * vr[k];
-  rotate_by_w(vr + 3, a.h, a.R + (size_t)b * 9);
-  if (!a.post) return;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    a.v[(size_t)b * 3 + k] = a.v[(size_t)b * 3 + k] + vr[k];
-    a.w[(size_t)b * 3 + k] = a.w[(size_t)b * 3 + k] + vr[3 + k];
-  }
+  for (int k = 0; k < 6; ++k) acc[k] = a.acc[(size_t)b * 6 + k];
+  stab_relax_body(acc, a.scale, a.h, a.post, a.pos + (size_t)b * 3, a.R + (size_t)b * 9, a.v + (size_t)b * 3,
+                  a.w + (size_t)b * 3);
 }
 
 __global__ void __launch_bounds__(256) stab_seed_running_kernel(int n_ens, const int32_t *active, int32_t *running,

@@ -1,6 +1,7 @@
 // world.cpp -- struct egs_world and the egs_world_* entries of the C ABI, with the stateless egs_update_contacts[_joints]:
 // Ensemble::Step (ensembles.cc:390-427) resident on the device, for one ensemble or a batch of them, on the sparse
-// sweeps (egs_world_step), the dense path (egs_world_step_dense) and the stabilisation passes (egs_world_stabilize).
+// sweeps (egs_world_step), the dense path (egs_world_step_dense) and the stabilisation passes (egs_world_stabilize,
+// egs_world_stabilize_direct), and the one-shot egs_relax_blocks_direct.
 // The world works on its egs_problem through problem.h.
 #include <chrono>
 #include <cmath>
@@ -11,6 +12,7 @@
 #include "dense_world.h"
 #include "problem.h"
 #include "stabilize.h"
+#include "stabilize_direct.h"
 
 using namespace egs;
 
@@ -75,6 +77,18 @@ struct egs_world {
                                            // read-back, solve, J^T y + stall check + relaxation step; passes
   std::vector<int32_t> st_steps;         // [E] of the last egs_world_stabilize (empty: none yet)
   std::vector<double> st_err_sq;
+  // egs_world_stabilize_direct, all made on its first call: every ensemble's constraint list in its own order and
+  // the size-class lists (stabilize_direct.h; host tables rebuilt after a re-plan), the global class's workspace, and
+  // per ensemble active [E], steps [E], rank [E], then n_active
+  int dr_replans = -1;                   // w->replans the tables below were built for
+  int dr_max_rows = 0;
+  std::vector<int32_t> dr_rows;          // [E] rows of each ensemble
+  int dr_count[kDirectClasses] = {0, 0, 0};
+  DevBuf<int32_t> dr_cons, dr_cstart, dr_lists, dr_ints;
+  DevBuf<int64_t> dr_wsoff;
+  DevBuf<double> dr_ws, dr_err_sq;
+  PinnedBuf<int32_t> h_dr;               // page-locked: n_active
+  std::vector<int32_t> st_rank, st_rows; // [E] of the last egs_world_stabilize_direct (empty: none yet)
   bool lambda_stale = false;             // a stabilise call changed bodies / contacts since the last step's solve
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
@@ -241,6 +255,56 @@ void world_relax_assemble(egs_world *w) {
   rx->lin_neg = !rx->joint_pairs;
 }
 
+// Every ensemble's constraint list in the order its own Ensemble holds it (its joints, then its contacts), the size
+// class of each (stabilize_direct.h) and the workspace of the global class: the tables of egs_world_stabilize_direct.
+// Host work only, redone after a re-plan.  EGS_ERR_UNSUPPORTED, with nothing staged, if an ensemble is above the limit.
+egs_status world_direct_plan(egs_world *w) {
+  auto verdict = [&]() {
+    return w->dr_max_rows > kDirectMaxRows
+        ? fail(w->ctx, EGS_ERR_UNSUPPORTED, "an ensemble has " + std::to_string(w->dr_max_rows) + " rows: the direct relaxation takes at most " +
+                                             std::to_string(kDirectMaxRows))
+        : EGS_OK;
+  };
+  if (w->dr_replans == w->replans) return verdict();
+  const egs_problem *p = w->prob;
+  const int E = w->n_ens, m = p->m;
+  std::vector<int32_t> ens((size_t)(m > 0 ? m : 1), 0), start((size_t)E + 1, 0);
+  for (int c = 0; c < m; ++c) {
+    const int32_t b = p->h_body0[(size_t)c] >= 0 ? p->h_body0[(size_t)c] : p->h_body1[(size_t)c];
+    const int e = E == 1 ? 0 : (int)(std::upper_bound(w->body_off.begin(), w->body_off.end(), b) - w->body_off.begin()) - 1;
+    ens[(size_t)c] = e;
+    ++start[(size_t)e + 1];
+  }
+  w->dr_rows.assign((size_t)E, 0);
+  w->dr_max_rows = 0;
+  std::vector<int32_t> cls[kDirectClasses];
+  std::vector<int64_t> off((size_t)E, 0);
+  int64_t total = 0;
+  for (int e = 0; e < E; ++e) {
+    const int rows = 3 * start[(size_t)e + 1];
+    start[(size_t)e + 1] += start[(size_t)e];
+    w->dr_rows[(size_t)e] = rows;
+    w->dr_max_rows = std::max(w->dr_max_rows, rows);
+    cls[direct_class(rows)].push_back(e);   // an ensemble without constraints too: its err_sq = 0 ends it
+    off[(size_t)e] = total;
+    total += (int64_t)direct_ws_size((size_t)rows);
+  }
+  w->dr_replans = w->replans;
+  if (w->dr_max_rows > kDirectMaxRows) return verdict();
+  // a stable bucket sort: the world lists joints (grouped by ensemble) before contacts (grouped by ensemble)
+  std::vector<int32_t> cons((size_t)(m > 0 ? m : 1), 0), next(start.begin(), start.end() - 1), lists;
+  for (int c = 0; c < m; ++c) cons[(size_t)next[(size_t)ens[(size_t)c]]++] = c;
+  for (int c = 0; c < kDirectClasses; ++c) {
+    w->dr_count[c] = (int)cls[c].size();
+    lists.insert(lists.end(), cls[c].begin(), cls[c].end());
+  }
+  stage(w->ctx, w->dr_cons, cons);
+  stage(w->ctx, w->dr_cstart, start);
+  stage(w->ctx, w->dr_lists, lists);
+  stage(w->ctx, w->dr_wsoff, off);
+  w->dr_ws.alloc((size_t)(total > 0 ? total : 1));
+  return EGS_OK;
+}
 
 // "bodies set, dt > 0, fp64" of the stepping entries, in that order; fp64_what = NULL: either precision will do
 egs_status world_step_guard(egs_world *w, double dt, const char *fp64_what) {
@@ -798,10 +862,125 @@ egs_status egs_world_stabilize(egs_world *w, int32_t mode, int32_t max_steps, in
 egs_status egs_world_stabilize_info(egs_world *w, int32_t n_ensembles, int32_t *steps, double *err_sq) {
   if (!w) return EGS_ERR_INVALID;
   if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
-  if (w->st_steps.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_stabilize yet");
+  if (w->st_steps.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_stabilize / egs_world_stabilize_direct yet");
   if (steps) std::copy(w->st_steps.begin(), w->st_steps.end(), steps);
   if (err_sq) std::copy(w->st_err_sq.begin(), w->st_err_sq.end(), err_sq);
   return EGS_OK;
+}
+
+egs_status egs_world_stabilize_direct(egs_world *w, int32_t mode, int32_t max_steps, int32_t detect_contacts, double rank_tol,
+                                      int32_t *n_unsettled) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_unsettled) *n_unsettled = 0;
+  if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
+  if (mode != EGS_STABILIZE_INIT && mode != EGS_STABILIZE_POST)
+    return fail(w->ctx, EGS_ERR_INVALID, "mode must be EGS_STABILIZE_INIT or EGS_STABILIZE_POST");
+  if (max_steps < 0) return fail(w->ctx, EGS_ERR_INVALID, "max_steps must be >= 0");
+  if (std::isnan(rank_tol) || rank_tol >= 1.0) return fail(w->ctx, EGS_ERR_INVALID, "rank_tol must be below 1 (<= 0: 1e-10)");
+  if (w->precision != EGS_F64) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "stabilisation is fp64 (the reference's is)");
+  constexpr double kAllowNumericalError = 1e-9, kSimTimeStep = 0.001;   // constants.h:5-6
+  const bool post = mode == EGS_STABILIZE_POST;
+  const bool detect = !post && detect_contacts != 0;                     // PostStabilize never detects
+  const int E = w->n_ens;
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    if (!detect)   // the list the call works on is known now: refuse before anything changes
+      if (egs_status st = world_direct_plan(w)) return st;
+    w->lambda_stale = true;
+    w->st_steps.clear(); w->st_err_sq.clear(); w->st_rank.clear(); w->st_rows.clear();
+    w->dr_ints.alloc(3 * (size_t)E + 1);
+    w->dr_err_sq.alloc((size_t)E);
+    w->h_dr.alloc(16);
+    StabDirectArgs a;
+    a.active = w->dr_ints.p; a.steps = a.active + E; a.rank = a.steps + E; a.n_active = a.rank + E;
+    a.err_sq = w->dr_err_sq.p;
+    a.loop = detect ? 0 : 1; a.post = post ? 1 : 0;
+    a.max_steps = max_steps > 0 ? max_steps : post ? 500 : 100;           // ensembles.cc:606, PostStabilize(500)
+    a.threshold = kAllowNumericalError;
+    a.rank_tol = rank_tol > 0 ? rank_tol : 1e-10;
+    a.scale = -1.0 * 0.2;                                                 // CalculateVelocityRelaxation(0.2)
+    a.h = post ? kSimTimeStep * 100 : kSimTimeStep * 500;                 // ensembles.cc:614, 638
+    for (int pass = 0;; ++pass) {
+      if (detect) {                                                       // ensembles.cc:603, 616 (pruning included)
+        world_update_contacts(w, [](int) {});
+        if (egs_status st = world_direct_plan(w)) return st;              // over the limit: this pass moves no body
+      }
+      egs_problem *p = w->prob;
+      a.as = assemble_args(p, 1.0, 0.2);
+      a.pos = p->pos.p; a.R = p->R.p; a.v = p->v.p; a.w = p->w.p;
+      a.cons = w->dr_cons.p; a.cstart = w->dr_cstart.p;
+      a.bo = E > 1 ? w->d_boff.p : nullptr;
+      a.ws_off = w->dr_wsoff.p; a.ws = w->dr_ws.p;
+      a.first = pass == 0 ? 1 : 0;
+      HIPCHK(hipMemsetAsync(a.n_active, 0, sizeof(int32_t), s));
+      int at = 0;
+      for (int c = 0; c < kDirectClasses; ++c) {
+        launch_stab_direct(a, w->dr_lists.p + at, w->dr_count[c], c, s);
+        at += w->dr_count[c];
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(w->h_dr.p, a.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (!detect || w->h_dr.p[0] == 0) break;
+    }
+    w->st_steps.resize((size_t)E); w->st_err_sq.resize((size_t)E); w->st_rank.resize((size_t)E);
+    HIPCHK(hipMemcpyAsync(w->st_steps.data(), a.steps, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(w->st_rank.data(), a.rank, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(w->st_err_sq.data(), a.err_sq, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    w->st_rows = w->dr_rows;
+    if (n_unsettled) {
+      int u = 0;
+      for (double e2 : w->st_err_sq) u += !(e2 <= kAllowNumericalError) ? 1 : 0;   // NaN counts as unsettled
+      *n_unsettled = u;
+    }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_stabilize_rank(egs_world *w, int32_t n_ensembles, int32_t *rows, int32_t *rank) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  if (w->st_rank.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_stabilize_direct yet");
+  if (rows) std::copy(w->st_rows.begin(), w->st_rows.end(), rows);
+  if (rank) std::copy(w->st_rank.begin(), w->st_rank.end(), rank);
+  return EGS_OK;
+}
+
+egs_status egs_relax_blocks_direct(egs_context *ctx, int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                   const double *J0, const double *J1, const double *err, double rank_tol, double *y,
+                                   int32_t *rank) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (!rank || (m > 0 && (!J0 || !J1 || !err || !y))) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (std::isnan(rank_tol) || rank_tol >= 1.0) return fail(ctx, EGS_ERR_INVALID, "rank_tol must be below 1 (<= 0: 1e-10)");
+  if (egs_status st = check_topology(ctx, n_bodies, m, body0, body1)) return st;
+  if (3 * (int64_t)m > kDirectMaxRows) return fail(ctx, EGS_ERR_UNSUPPORTED, "the direct relaxation takes at most 1024 rows");
+  *rank = 0;
+  if (m == 0) return EGS_OK;
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t mm = (size_t)m;
+    DevBuf<int32_t> db, dr;
+    DevBuf<double> dJ, dv, dws;
+    db.alloc(2 * mm); dr.alloc(1); dJ.alloc(36 * mm); dv.alloc(6 * mm);
+    dws.alloc(std::max<size_t>(direct_ws_size(3 * mm), 1));
+    HIPCHK(hipMemcpyAsync(db.p, body0, mm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(db.p + mm, body1, mm * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dJ.p, J0, 18 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dJ.p + 18 * mm, J1, 18 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dv.p, err, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+    RelaxDirectArgs a;
+    a.m = m; a.body0 = db.p; a.body1 = db.p + mm; a.J0 = dJ.p; a.J1 = dJ.p + 18 * mm; a.err = dv.p;
+    a.rank_tol = rank_tol > 0 ? rank_tol : 1e-10;
+    a.ws = dws.p; a.y = dv.p + 3 * mm; a.rank = dr.p;
+    launch_relax_direct(a, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(y, a.y, 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(rank, dr.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return EGS_OK;
+  });
 }
 
 }  // extern "C"

@@ -251,6 +251,12 @@ class Ensemble {  // ensembles.h:25-186
   // positions AND velocities back to the constraint manifold (ensembles.cc:624-646).
   void InitStabilize();
   void PostStabilize(int max_steps = 500);
+  // How CalculateVelocityRelaxation solves (J J^T) y = err.  Sweep (the default): the matrix-free SOR sweep.  Direct:
+  // egs_relax_blocks_direct, the pivoted LDL^T the reference's ldlt() is, truncated at the first pivot
+  // <= 1e-10 * |first pivot| (J J^T is singular with redundant contact points; J^T y is the same for every solution).
+  enum struct RelaxationSolver { Sweep = 0, Direct };
+  void SetRelaxationSolver(RelaxationSolver solver) { relaxation_solver_ = solver; }
+  int last_relaxation_rank = -1;         // rank of the last Direct solve (-1: none yet)
   const MatrixXd &M_inverse() const { return M_inverse_; }
   const ConstraintsList constraints() const { return CombineConstraintsLists(); }
   const ComponentsList &components() const { return components_; }
@@ -303,6 +309,7 @@ class Ensemble {  // ensembles.h:25-186
   void StepPositions_ExplicitEuler(double dt, const VectorXd &v);          // ensembles.cc:553-561
   void StepPositionRelaxation(double dt, double step_scale = 0.2);         // ensembles.cc:648-651
   void StepPostStabilization(double dt, double step_scale = 0.2);          // ensembles.cc:653-658
+  RelaxationSolver relaxation_solver_ = RelaxationSolver::Sweep;
   egs_world *world_ = nullptr;
   int world_joints_ = -1;
   std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds

@@ -4,7 +4,8 @@
 // goes through the matrix-free GPU sweep (entry 1 of the C ABI) with M^-1 = I
 // and all rows equalities.  J J^T is only positive SEMI-definite when contacts
 // are redundant; the correction J^T y is unique whenever err is consistent, and
-// the sweep converges to it.
+// the sweep converges to it.  SetRelaxationSolver(Direct) takes the device's
+// rank-revealing LDL^T instead (egs_relax_blocks_direct).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -36,13 +37,21 @@ VectorXd Ensemble::CalculateVelocityRelaxation(double step_scale) const {  // en
       for (int c = 0; c < 6; ++c) { J0[(size_t)i * 18 + 6 * r + c] = j0(r, c); J1[(size_t)i * 18 + 6 * r + c] = j1(r, c); }
   }
   const VectorXd err = ComputePositionConstraintError();
-  egs_solve_params prm;
-  egs_default_params(&prm);
-  prm.method = EGS_SOR; prm.cfm = 0.0; prm.tol = 1e-11; prm.max_iters = 20000; prm.check_every = 10;
-  egs_solve_stats st;
-  egs_status rc = egs_solve_blocks(egs::DefaultContext(), n_, Minv.data(), m, b0.data(), b1.data(), J0.data(), J1.data(),
-                                   is_eq.data(), lo.data(), hi.data(), err.data(), &prm, EGS_F64, x.data(), &st);
-  if (rc != EGS_OK) throw egs::Error(rc, egs_last_error(egs::DefaultContext()));
+  if (relaxation_solver_ == RelaxationSolver::Direct) {
+    int32_t rank = 0;
+    egs_status rc = egs_relax_blocks_direct(egs::DefaultContext(), n_, m, b0.data(), b1.data(), J0.data(), J1.data(), err.data(),
+                                            /*rank_tol: the default*/ 0.0, x.data(), &rank);
+    if (rc != EGS_OK) throw egs::Error(rc, egs_last_error(egs::DefaultContext()));
+    const_cast<Ensemble *>(this)->last_relaxation_rank = rank;
+  } else {
+    egs_solve_params prm;
+    egs_default_params(&prm);
+    prm.method = EGS_SOR; prm.cfm = 0.0; prm.tol = 1e-11; prm.max_iters = 20000; prm.check_every = 10;
+    egs_solve_stats st;
+    egs_status rc = egs_solve_blocks(egs::DefaultContext(), n_, Minv.data(), m, b0.data(), b1.data(), J0.data(), J1.data(),
+                                     is_eq.data(), lo.data(), hi.data(), err.data(), &prm, EGS_F64, x.data(), &st);
+    if (rc != EGS_OK) throw egs::Error(rc, egs_last_error(egs::DefaultContext()));
+  }
   for (int i = 0; i < m; ++i)
     for (int side = 0; side < 2; ++side) {
       const int b = side ? b1[i] : b0[i];

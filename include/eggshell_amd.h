@@ -445,6 +445,45 @@ egs_status egs_world_stabilize(egs_world *w, int32_t mode, int32_t max_steps, in
  * final err_sq.  n_ensembles must be the world's; EGS_ERR_INVALID before the first stabilise call.              */
 egs_status egs_world_stabilize_info(egs_world *w, int32_t n_ensembles, int32_t *steps, double *err_sq);
 
+/* egs_world_stabilize with the relaxation solve done directly: the same loops, the same mode, max_steps (0 = 100 /
+ * 500), freezing of stopped ensembles, *n_unsettled, and the same state of get_contacts / get_lambda afterwards;
+ * egs_world_stabilize_info reports steps / err_sq of whichever of the two ran last.  One workgroup per ensemble does a
+ * whole pass on chip: assembly, err_sq, the lower triangle of A = J J^T, its factorisation, the solve, the list-order
+ * J^T y and the position step.  With a fixed constraint list (POST, or INIT with detect_contacts = 0) ALL passes run
+ * inside one launch, with one read-back per call; INIT with detection takes one launch per pass between the world's
+ * collide / prune / re-plan-on-change steps.
+ *   - The factorisation is the LDL^T with symmetric diagonal pivoting that ldlt() (ensembles.cc:662) is (largest
+ *     |diagonal|, lowest index on ties), but it STOPS at the first pivot <= rank_tol * |first pivot| and takes y = 0
+ *     on the rows left; rank_tol <= 0 means 1e-10.  Redundant contact points make J J^T singular (a 2x2x2 box stack:
+ *     96 rows, rank 48): dividing by its rounding-noise pivots gives |y| ~ 3e14 and a correction wrong by 5x its own
+ *     size, while err is consistent, so every solution has the same J^T y and the truncated one equals the least
+ *     squares correction to 3e-16.  Where J J^T is positive definite nothing is truncated and the result is ldlt()'s.
+ *     Where err is NOT consistent (the contacts of tilted boxes over-determine the bodies: a 5-box cairn has 84 rows
+ *     of rank 30) the rows left carry a residual rho, and the leading block is solved for
+ *     L1^-1 b1 + (W^T W)^-1 L2^T rho instead of L1^-1 b1 (W = [L1; L2], the truncated unit lower factor): a small
+ *     positive definite solve that makes J^T y the least-squares correction J^T (J J^T)^+ err, which the sweep
+ *     route converges to.  With consistent err rho = 0 and nothing changes.
+ *   - Ensembles of up to 126 rows (42 constraints) live in LDS (<= 48 rows: one wavefront; above: four); larger ones,
+ *     up to 1024 rows, keep the matrices and the Jacobian in a per-ensemble device workspace.  The class depends on the
+ *     ensemble's own rows only, so each ensemble of a batch ends with the bits a world holding it alone ends with.
+ *   - EGS_ERR_UNSUPPORTED: an fp32 world; an ensemble above 1024 rows (if detection pushes one over the limit in
+ *     mid-call, that pass moves no body and egs_world_stabilize_info has nothing to report).  EGS_ERR_INVALID:
+ *     before egs_world_set_bodies, an unknown mode, max_steps < 0, rank_tol NaN or >= 1.  Nothing is moved then.
+ *   - The first call allocates its tables; egs_world_stabilize, egs_world_step and egs_world_step_dense allocate and
+ *     launch nothing for it.                                                                                      */
+egs_status egs_world_stabilize_direct(egs_world *w, int32_t mode, int32_t max_steps, int32_t detect_contacts,
+                                      double rank_tol, int32_t *n_unsettled);
+/* Per-ensemble figures of the last egs_world_stabilize_direct ([E] each, any may be NULL): the rows of the ensemble's
+ * system (3 per constraint, on the final list) and the rank of the last pass it solved (0: none).  n_ensembles must
+ * be the world's; EGS_ERR_INVALID before the first direct call.                                                   */
+egs_status egs_world_stabilize_rank(egs_world *w, int32_t n_ensembles, int32_t *rows, int32_t *rank);
+/* One-shot: (J J^T) y = err for one constraint list by the same device code, one workgroup.  J0 / J1 [m][18]
+ * row-major blocks (zero for a world side, body index -1), err and y [3m]; y = 0 on the rows the truncation left,
+ * *rank = pivots taken; rank_tol as above.  3m <= 1024 (EGS_ERR_UNSUPPORTED above).                              */
+egs_status egs_relax_blocks_direct(egs_context *ctx, int32_t n_bodies, int32_t m, const int32_t *body0,
+                                   const int32_t *body1, const double *J0, const double *J1, const double *err,
+                                   double rank_tol, double *y, int32_t *rank);
+
 /* Replaces lcp::SolveLCP_BoxDantzig (toolkit/lcp.cc:444-619; reached from lcp::SolveLCP with
  * Settings.algorithm = COTTLE_DANTZIG, box_lcp = true, schur_complement = false, toolkit/lcp.cc:776-779):
  * Cottle-Dantzig principal pivoting on A x = b + w with lo <= x <= hi, the Cholesky factor of the active
