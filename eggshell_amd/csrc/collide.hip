@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "collide.h"
+#include "runtime.h"
 
 namespace egs {
 
@@ -37,21 +38,6 @@ namespace {
 
 constexpr int KMAX = 64;      // candidate partners j > i per body
 constexpr int MAXC = 16;      // contacts per pair before pruning
-
-struct HipErr : std::runtime_error { using std::runtime_error::runtime_error; };
-void chk(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipErr(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(call) chk((call), #call)
-
-template <typename T>
-struct Buf {
-  T *p = nullptr;
-  explicit Buf(size_t n) { if (n) HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T))); }
-  ~Buf() { if (p) (void)hipFree(p); }
-  Buf(const Buf &) = delete;
-  Buf &operator=(const Buf &) = delete;
-};
 
 struct Box { double c[3]; double R[9]; double h[3]; };
 struct V2 { double x, y; };
@@ -668,24 +654,11 @@ bool use_grid(int n) {
 }  // namespace
 
 struct Collider::Impl {
-  // growable device buffers
-  template <typename T>
-  struct G {
-    T *p = nullptr;
-    size_t cap = 0;
-    void need(size_t n) {
-      if (n <= cap) return;
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = n + n / 4 + 64;
-      HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), cap * sizeof(T)));
-    }
-    ~G() { if (p) (void)hipFree(p); }
-  };
-  G<int> gcount, goff, ccount, coff, cand, flags, blocks, pi, pj, pcount, poff, blocks2, b0, b1;
-  G<int> coords, bucket_of, arrival, tcount, toff, sorted, blocks3, scratch;   // uniform grid
-  G<int> ebase;                                                                 // batched worlds
-  G<double> data, cell;
+  // grow-only: a world runs the collider every step
+  DevBuf<int> gcount, goff, ccount, coff, cand, flags, blocks, pi, pj, pcount, poff, blocks2, b0, b1;
+  DevBuf<int> coords, bucket_of, arrival, tcount, toff, sorted, blocks3, scratch;   // uniform grid
+  DevBuf<int> ebase;                                                                 // batched worlds
+  DevBuf<double> data, cell;
 };
 
 Collider::Collider() : impl_(new Impl) {}
@@ -708,8 +681,8 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
     return 0;
   }
   const size_t nn = (size_t)n;
-  I.gcount.need(nn); I.goff.need(nn); I.ccount.need(nn); I.coff.need(nn); I.cand.need(nn * KMAX); I.flags.need(4);
-  I.blocks.need((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8); I.blocks2.need((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
+  I.gcount.alloc(nn); I.goff.alloc(nn); I.ccount.alloc(nn); I.coff.alloc(nn); I.cand.alloc(nn * KMAX); I.flags.alloc(4);
+  I.blocks.alloc((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8); I.blocks2.alloc((nn + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
   // flags: [0] candidate overflow, [1] ground contacts, [2] candidate pairs, [3] pair contacts
   HIPCHK(hipMemsetAsync(I.flags.p, 0, 4 * sizeof(int), s));
   const int gb = (n + 255) / 256;
@@ -719,9 +692,9 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   if (use_grid(n)) {
     int table = 1024;
     while (table < 2 * n) table <<= 1;
-    I.cell.need(1); I.coords.need(nn * 3); I.bucket_of.need(nn); I.arrival.need(nn); I.sorted.need(nn);
-    I.tcount.need((size_t)table); I.toff.need((size_t)table); I.blocks3.need((size_t)table / SCAN_CHUNK + 8);
-    I.scratch.need(1);
+    I.cell.alloc(1); I.coords.alloc(nn * 3); I.bucket_of.alloc(nn); I.arrival.alloc(nn); I.sorted.alloc(nn);
+    I.tcount.alloc((size_t)table); I.toff.alloc((size_t)table); I.blocks3.alloc((size_t)table / SCAN_CHUNK + 8);
+    I.scratch.alloc(1);
     HIPCHK(hipMemsetAsync(I.tcount.p, 0, (size_t)table * sizeof(int), s));
     hipLaunchKernelGGL(cell_size_kernel, dim3(1), dim3(1024), 0, s, n, dside, I.cell.p);
     hipLaunchKernelGGL(cell_bin_kernel, dim3(gb), dim3(256), 0, s, n, dpos, I.cell.p, table - 1, I.coords.p, I.bucket_of.p,
@@ -746,7 +719,7 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   const int G = totals[1], C = totals[2];
   int P = 0;
   if (C > 0) {
-    I.pi.need(C); I.pj.need(C); I.pcount.need(C); I.poff.need(C); I.blocks2.need(((size_t)C + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
+    I.pi.alloc(C); I.pj.alloc(C); I.pcount.alloc(C); I.poff.alloc(C); I.blocks2.alloc(((size_t)C + SCAN_CHUNK - 1) / SCAN_CHUNK + 8);
     if (spill) hipLaunchKernelGGL((cand_all_kernel<true>), dim3(n), dim3(64), 0, s, n, dpos, dside, I.coff.p, (int *)nullptr, I.pi.p, I.pj.p,
                                   ens, eoff);
     else
@@ -758,12 +731,12 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   const int m = G + P;
   n_ground_ = G; n_pairs_ = C;
   if (ens) {   // per-ensemble order: ground contacts then pairs, ensemble by ensemble
-    I.ebase.need((size_t)n_ens_ * 2);
+    I.ebase.alloc((size_t)n_ens_ * 2);
     hipLaunchKernelGGL(ens_base_kernel, dim3(n_ens_ / 256 + 1), dim3(256), 0, s, n_ens_, n, eoff, I.goff.p, I.coff.p, I.poff.p,
                        I.flags.p, I.ebase.p, contact_off_);
   }
   if (m == 0) return 0;
-  I.b0.need(m); I.b1.need(m); I.data.need((size_t)m * 7);
+  I.b0.alloc(m); I.b1.alloc(m); I.data.alloc((size_t)m * 7);
   hipLaunchKernelGGL(ground_kernel, dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
                      I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr);
   if (C > 0)
@@ -787,12 +760,12 @@ int update_contacts(hipStream_t s, int n, const double *pos, const double *R, co
   if (n_pairs) *n_pairs = 0;
   if (n <= 0) return 0;
   const size_t nn = (size_t)n;
-  Buf<double> dpos(nn * 3), dR(nn * 9), dside(nn * 3);
+  ScopedDevBuf<double> dpos(nn * 3), dR(nn * 9), dside(nn * 3);
   HIPCHK(hipMemcpyAsync(dpos.p, pos, nn * 3 * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dR.p, R, nn * 9 * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(dside.p, side, nn * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-  Buf<int> djb0((size_t)mj), djb1((size_t)mj);
-  Buf<double> djdata((size_t)mj * 7);
+  ScopedDevBuf<int> djb0((size_t)mj), djb1((size_t)mj);
+  ScopedDevBuf<double> djdata((size_t)mj * 7);
   if (mj > 0) {
     HIPCHK(hipMemcpyAsync(djb0.p, jb0, (size_t)mj * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(djb1.p, jb1, (size_t)mj * sizeof(int), hipMemcpyHostToDevice, s));

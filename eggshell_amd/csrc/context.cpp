@@ -1,5 +1,6 @@
 // context.cpp -- the context entries of the C ABI: egs_default_params, egs_context_*, egs_last_error, the stream
-// timer and the per-launch kernel-time events.  A context owns the stream every other unit enqueues on.
+// timer and the per-launch kernel-time events.  A context owns the stream every other unit enqueues on, and with it
+// everything that work on that stream uses between calls: the staging arena, the dense workspace, the one-shot problem.
 #include "plan.h"
 #include "runtime.h"
 
@@ -34,6 +35,7 @@ egs_status egs_context_create(int device_index, egs_context **out) {
     if (prop.multiProcessorCount > 0) ctx->cu_count = prop.multiProcessorCount;
     set_patch_workgroups(ctx->cu_count);
     HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    ctx->dense.stream = ctx->stream;
     HIPCHK(hipEventCreate(&ctx->t0));
     HIPCHK(hipEventCreate(&ctx->t1));
     ctx->kev.resize(2 * kEventPairs, nullptr);
@@ -52,6 +54,8 @@ void egs_context_destroy(egs_context *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->dense.side) (void)hipStreamSynchronize(ctx->dense.side);
+  ctx->dense.release();     // while its streams still exist and are idle
   if (ctx->oneshot) { egs_problem_destroy(ctx->oneshot); ctx->oneshot = nullptr; }
   for (auto e : ctx->kev) if (e) (void)hipEventDestroy(e);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);

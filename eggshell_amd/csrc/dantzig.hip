@@ -19,6 +19,7 @@
 // box_schur_kernel below: lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747) fused into one launch for a batch of
 // problems of n <= 96 rows (egs_box_lcp_schur_batch).
 #include "dense_lcp.h"
+#include "runtime.h"
 
 #include <algorithm>
 #include <cstring>
@@ -679,24 +680,6 @@ __global__ void __launch_bounds__(64) box_schur_kernel(const SchurSet S) {
 
 #undef AT
 
-struct HipErr : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-void chk(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipErr(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(call) chk((call), #call)
-
-template <typename T>
-struct DBuf {      // plain hipMalloc / hipFree on purpose: with a stream-ordered pool allocation (hipMallocAsync /
-  T *p = nullptr;  // hipFreeAsync) back-to-back calls that got the same block back saw stale lines of the previous
-                   // call's matrix on this stack (ROCm 7.2; tests/test_gpu_dantzig.py::test_repeated_calls_are_independent)
-  explicit DBuf(size_t n) { if (n) HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T))); }
-  ~DBuf() { if (p) (void)hipFree(p); }
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-};
-
 size_t lds_bytes(int n, bool global) {
   return ((global ? 0 : 2 * (size_t)n * n) + 11 * (size_t)n) * sizeof(double) + (3 * (size_t)n + 4) * sizeof(int);
 }
@@ -726,9 +709,9 @@ void solve_set(hipStream_t stream, int algorithm, int count, const int32_t *hn, 
     else { large.push_back(k); n_large = std::max(n_large, (int)hn[k]); }
     a_total = std::max(a_total, ha[k] + (int64_t)hn[k] * hn[k]);
   }
-  DBuf<int32_t> d_n(count), d_ids(count);
-  DBuf<int64_t> d_off(2 * (size_t)count);
-  DBuf<double> d_L(large.empty() ? 0 : (size_t)a_total);
+  ScopedDevBuf<int32_t> d_n(count), d_ids(count);
+  ScopedDevBuf<int64_t> d_off(2 * (size_t)count);
+  ScopedDevBuf<double> d_L(large.empty() ? 0 : (size_t)a_total);
   std::vector<int32_t> ids(small);
   ids.insert(ids.end(), large.begin(), large.end());
   HIPCHK(hipMemcpyAsync(d_n.p, hn, count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -779,9 +762,9 @@ void box_lcp_incremental_batch(hipStream_t stream, int algorithm, int count, con
     check_problem(algorithm, n[k], lo + vt, hi + vt);
     at += (int64_t)n[k] * n[k]; vt += n[k];
   }
-  DBuf<double> dA((size_t)at), dv(5 * (size_t)vt);
-  DBuf<int32_t> dperm((size_t)vt);
-  DBuf<LcpResult> dres(count);
+  ScopedDevBuf<double> dA((size_t)at), dv(5 * (size_t)vt);
+  ScopedDevBuf<int32_t> dperm((size_t)vt);
+  ScopedDevBuf<LcpResult> dres(count);
   double *db = dv.p, *dlo = dv.p + vt, *dhi = dv.p + 2 * vt, *dx = dv.p + 3 * vt, *dw = dv.p + 4 * vt;
   HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)at * sizeof(double), hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemcpyAsync(db, b, (size_t)vt * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -843,7 +826,7 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
     haoff[k] = (int64_t)ap; hvoff[k] = (int64_t)vp; hn[k] = nk; hnub[k] = nub ? nub[j] : -1;
     ap += (size_t)nk * nk; vp += nk;
   }
-  DBuf<char> d(total);
+  ScopedDevBuf<char> d(total);
   HIPCHK(hipMemcpyAsync(d.p + o_A, h + o_A, total - o_A, hipMemcpyHostToDevice, stream));
   SchurSet S{};
   S.n = reinterpret_cast<int32_t *>(d.p + o_n); S.nub = reinterpret_cast<int32_t *>(d.p + o_nub);
@@ -897,7 +880,7 @@ bool box_lcp_incremental_device(hipStream_t stream, int algorithm, int n, double
                                 double *dx, double *dw, int *pivots, std::string *msg) {
   if (algorithm != 0 && algorithm != 1) throw std::invalid_argument("incremental box LCP: algorithm 0 (Murty) or 1 (Cottle-Dantzig)");
   check_problem(algorithm, n, h_lo, h_hi);
-  DBuf<LcpResult> dres(1);
+  ScopedDevBuf<LcpResult> dres(1);
   const int32_t hn = n;
   const int64_t zero = 0;
   solve_set(stream, algorithm, 1, &hn, &zero, &zero, dA, db, dlo, dhi, max_steps, max_seconds, dx, dw, nullptr, dres.p);

@@ -71,7 +71,7 @@ egs_status egs_problem_dense_condition(egs_problem *p, double cfm, double *estim
   return guarded(p->ctx, [&]() -> egs_status {
     if (egs_status st = build_dense_system(p, cfm)) return st;
     bool spd = true;
-    *estimate = dense_condition_estimate(p->ctx->stream, 3 * p->m, p->dense_A.p, &spd);
+    *estimate = dense_condition_estimate(p->ctx->dense, 3 * p->m, p->dense_A.p, &spd);
     return EGS_OK;   // not positive definite: +inf, i.e. "ill-conditioned" to the caller (ensembles.cc:514)
   });
 }
@@ -111,7 +111,7 @@ egs_status egs_dense_condition(egs_context *ctx, int32_t N, const double *A, dou
     if (N) HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     bool spd = true;
     double pb = 1.0;
-    *estimate = dense_condition_estimate(ctx->stream, N, dA.p, &spd, &pb);
+    *estimate = dense_condition_estimate(ctx->dense, N, dA.p, &spd, &pb);
     if (pivot_bound) *pivot_bound = spd ? pb : *estimate;
     return EGS_OK;
   });
@@ -149,7 +149,7 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
     int piv = 0;
     std::string msg;
     // Lcp::MixedConstraintsSolver (ensembles.cc:531) on the device matrix; lambda lands in the problem's x
-    const bool good = dense_mixed_constraints_device(s, (int)rows, p->dense_A.p, real<double>(p->rhs), C.data(),
+    const bool good = dense_mixed_constraints_device(ctx->dense, (int)rows, p->dense_A.p, real<double>(p->rhs), C.data(),
                                                      lo.data(), hi.data(), (use_bounds & 1) != 0, (use_bounds & 2) != 0, 0, 0.0,
                                                      nullptr, nullptr, real<double>(p->x), &piv, &msg);
     if (pivots) *pivots = piv;
@@ -179,7 +179,7 @@ egs_status egs_mixed_constraints_solve_limits(egs_context *ctx, int32_t N, const
     HIPCHK(hipSetDevice(ctx->device));
     int piv = 0;
     std::string msg;
-    const bool good = dense_mixed_constraints(ctx->stream, N, A, b, C, lo, hi, (use_bounds & 1) != 0,
+    const bool good = dense_mixed_constraints(ctx->dense, N, A, b, C, lo, hi, (use_bounds & 1) != 0,
                                               (use_bounds & 2) != 0, x, w, &piv, &msg, max_pivots, max_seconds);
     return lcp_result(ctx, good, piv, msg, "MixedConstraintsSolver did not reach a solution", ok, pivots);
   });
@@ -223,7 +223,7 @@ egs_status egs_box_lcp_schur(egs_context *ctx, int32_t n, double *A, const doubl
     HIPCHK(hipSetDevice(ctx->device));
     int piv = 0, nub_found = 0;
     std::string msg;
-    const bool good = box_lcp_schur(ctx->stream, n, A, b, lo, hi, algorithm, nub, reference_quirks != 0, max_iterations, max_seconds,
+    const bool good = box_lcp_schur(ctx->dense, n, A, b, lo, hi, algorithm, nub, reference_quirks != 0, max_iterations, max_seconds,
                                     x, w, perm, &nub_found, &piv, &msg);
     if (nub_out) *nub_out = nub_found;
     return lcp_result(ctx, good, piv, msg, "SolveLCP_BoxSchur did not reach a solution", ok, pivots);
@@ -279,7 +279,7 @@ egs_status egs_box_lcp_schur_batch(egs_context *ctx, int32_t algorithm, int32_t 
     for (const int k : single) {
       int piv = 0, nub_found = 0;
       std::string msg;
-      const bool good = box_lcp_schur(ctx->stream, n[k], A + a_off[k], b + v_off[k], lo + v_off[k], hi + v_off[k], algorithm,
+      const bool good = box_lcp_schur(ctx->dense, n[k], A + a_off[k], b + v_off[k], lo + v_off[k], hi + v_off[k], algorithm,
                                       nub ? nub[k] : -1, q6, max_iterations, max_seconds, x + v_off[k], w + v_off[k],
                                       perm ? perm + v_off[k] : nullptr, &nub_found, &piv, &msg);
       ok[k] = good ? 1 : 0;

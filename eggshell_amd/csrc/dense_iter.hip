@@ -24,6 +24,7 @@
 #include <stdexcept>
 
 #include "dense_lcp.h"
+#include "runtime.h"
 
 namespace egs {
 
@@ -119,14 +120,6 @@ __global__ void __launch_bounds__(1024) dense_iterate_kernel(int n, const double
   if (tid == 0) { out->residual = err; out->iterations = it; out->pad = 0; }
 }
 
-struct HipErr2 : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-void chk2(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipErr2(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK2(call) chk2((call), #call)
-
 }  // namespace
 
 void dense_iterate(hipStream_t s, int n, const double *A, const double *b, const uint8_t *C, const double *lo, const double *hi,
@@ -139,34 +132,23 @@ void dense_iterate(hipStream_t s, int n, const double *A, const double *b, const
   if (n == 0) return;                      // sparse_iterations.cc:79-81
   for (int i = 0; i < n; ++i)
     if (A[(size_t)i * n + i] == 0.0) throw std::invalid_argument("dense iteration: zero on the diagonal (the reference CHECKs det != 0)");
-  double *dA = nullptr, *dv = nullptr;
-  uint8_t *dC = nullptr;
-  DenseIterOut *dout = nullptr;
-  const size_t nn = (size_t)n * n;
-  HIPCHK2(hipMalloc(reinterpret_cast<void **>(&dA), nn * sizeof(double)));
-  HIPCHK2(hipMalloc(reinterpret_cast<void **>(&dv), 4 * (size_t)n * sizeof(double)));
-  HIPCHK2(hipMalloc(reinterpret_cast<void **>(&dC), (size_t)n));
-  HIPCHK2(hipMalloc(reinterpret_cast<void **>(&dout), sizeof(DenseIterOut)));
-  try {
-    double *db = dv, *dlo = dv + n, *dhi = dv + 2 * n, *dx = dv + 3 * n;
-    HIPCHK2(hipMemcpyAsync(dA, A, nn * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK2(hipMemcpyAsync(db, b, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK2(hipMemcpyAsync(dlo, lo, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK2(hipMemcpyAsync(dhi, hi, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK2(hipMemcpyAsync(dC, C, (size_t)n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(dense_iterate_kernel, dim3(1), dim3(1024), 0, s, n, dA, db, dC, dlo, dhi, method, 1.0 / omega, max_iters, tol, dx, dout);
-    HIPCHK2(hipGetLastError());
-    DenseIterOut o{};
-    HIPCHK2(hipMemcpyAsync(x, dx, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK2(hipMemcpyAsync(&o, dout, sizeof o, hipMemcpyDeviceToHost, s));
-    HIPCHK2(hipStreamSynchronize(s));
-    if (iterations) *iterations = o.iterations;
-    if (residual) *residual = o.residual;
-  } catch (...) {
-    (void)hipFree(dA); (void)hipFree(dv); (void)hipFree(dC); (void)hipFree(dout);
-    throw;
-  }
-  (void)hipFree(dA); (void)hipFree(dv); (void)hipFree(dC); (void)hipFree(dout);
+  ScopedDevBuf<double> dA((size_t)n * n), dv(4 * (size_t)n);
+  ScopedDevBuf<uint8_t> dC(n);
+  ScopedDevBuf<DenseIterOut> dout(1);
+  double *db = dv.p, *dlo = dv.p + n, *dhi = dv.p + 2 * n, *dx = dv.p + 3 * n;
+  HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(db, b, n * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dlo, lo, n * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dhi, hi, n * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dC.p, C, (size_t)n, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(dense_iterate_kernel, dim3(1), dim3(1024), 0, s, n, dA.p, db, dC.p, dlo, dhi, method, 1.0 / omega, max_iters, tol, dx, dout.p);
+  HIPCHK(hipGetLastError());
+  DenseIterOut o{};
+  HIPCHK(hipMemcpyAsync(x, dx, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&o, dout.p, sizeof o, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (iterations) *iterations = o.iterations;
+  if (residual) *residual = o.residual;
 }
 
 }  // namespace egs

@@ -9,20 +9,24 @@
 
 namespace egs {
 
+// The scratch, pinned records and side stream of the entries below that need any, and the stream they enqueue on
+// (runtime.h): a context owns one.  The pure-Dantzig entries and dense_iterate need none and take the stream itself.
+struct DenseWorkspace;
+
 // A [N][N] row-major symmetric, b, C, lo, hi [N] on the host; x, w [N] out.
 // use_bounds = false reproduces the reference (Murty on [0, inf), quirk Q3).
 // block_pivoting = true replaces the reference's single-index rule by block
 // principal pivoting (same solution, far fewer factorisations, no 1000-pivot cap).
 // Returns the reference's bool; *pivots = number of principal pivots (solves).
-// Throws std::invalid_argument / the HIP error type of runtime.h's hip_check.
+// Throws std::invalid_argument for a bad argument and egs::HipError (runtime.h) for a failed HIP call, as every entry here.
 // max_pivots > 0 / max_seconds > 0: give up (return false) after that many principal pivots / that
 // much wall time (lcp::Settings::max_iterations, max_time; toolkit/lcp.h:161-167).
-bool dense_mixed_constraints(hipStream_t stream, int N, const double *A, const double *b, const uint8_t *C,
+bool dense_mixed_constraints(DenseWorkspace &ws, int N, const double *A, const double *b, const uint8_t *C,
                              const double *lo, const double *hi, bool use_bounds, bool block_pivoting, double *x,
                              double *w, int *pivots, std::string *msg, int max_pivots = 0, double max_seconds = 0.0);
 // The same with A (row-major, symmetric: the lower triangle is read) and b already on the device.
 // x / w (host, [N]) may be NULL; dx_out (device, [N]) receives the solution if not NULL.
-bool dense_mixed_constraints_device(hipStream_t stream, int N, const double *dA, const double *db, const uint8_t *C,
+bool dense_mixed_constraints_device(DenseWorkspace &ws, int N, const double *dA, const double *db, const uint8_t *C,
                                     const double *lo, const double *hi, bool use_bounds, bool block_pivoting,
                                     int max_pivots, double max_seconds, double *x, double *w, double *dx_out,
                                     int *pivots, std::string *msg);
@@ -31,7 +35,7 @@ bool dense_mixed_constraints_device(hipStream_t stream, int N, const double *dA,
 // Cholesky factor (N <= 1024; 60 iterations each, accurate to a few per cent unless the extreme eigenvalues are
 // clustered, and never above the true value).  *pivot_bound (may be NULL) = (max L_ii / min L_ii)^2, the cheap lower
 // bound, which is also what is returned beyond 1024 rows.  *spd = false (and +inf) if the factorisation breaks down.
-double dense_condition_estimate(hipStream_t stream, int N, const double *dA, bool *spd, double *pivot_bound = nullptr);
+double dense_condition_estimate(DenseWorkspace &ws, int N, const double *dA, bool *spd, double *pivot_bound = nullptr);
 
 // lcp::SolveLCP_BoxDantzig / SolveLCP_BoxMurty with the incremental Cholesky factor of toolkit/lcp.cc (dantzig.hip):
 // one workgroup per problem.  n <= kDantzigMaxRows: one wavefront, everything in LDS; up to kIncrementalMaxRows:
@@ -63,7 +67,7 @@ bool box_lcp_incremental_device(hipStream_t stream, int algorithm, int n, double
 // principal pivoting), then y = Z^-1 (c - B' z).  nub_arg >= 0 is the reference's test hook (:623-626), -1 scans the
 // bounds; q6 keeps the reference's literal classification test.  A: host, row-major, only the
 // lower triangle is read or written.
-bool box_lcp_schur(hipStream_t stream, int n, double *A, const double *b, const double *lo, const double *hi, int algorithm,
+bool box_lcp_schur(DenseWorkspace &ws, int n, double *A, const double *b, const double *lo, const double *hi, int algorithm,
                    int nub_arg, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm, int *nub_out,
                    int *pivots, std::string *msg);
 

@@ -26,6 +26,7 @@
 // + cfm I and for the reference's own tests); otherwise the call reports
 // failure instead of a wrong answer.
 #include "dense_lcp.h"
+#include "runtime.h"
 
 #include <algorithm>
 #include <chrono>
@@ -44,14 +45,6 @@ namespace egs {
 namespace {
 
 constexpr int NB = 64;    // block size = wavefront size
-
-struct HipErr : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-void chk(hipError_t e, const char *what) {
-  if (e != hipSuccess) throw HipErr(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(call) chk((call), #call)
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -468,14 +461,14 @@ __global__ void __launch_bounds__(1024) back_solve_kernel(const double *T, int l
   for (int i = tid; i < nreal; i += 1024) out[map ? map[i] : i] = xs[i];
 }
 
-void launch_back_solve(hipStream_t s, const double *T, int ld, int nf, int yrow, int nreal, const int *map, double *out, double *xs,
+void launch_back_solve(DenseWorkspace &ws, const double *T, int ld, int nf, int yrow, int nreal, const int *map, double *out, double *xs,
                        const double *inv) {
+  hipStream_t s = ws.stream;
   if (nf <= kBackSolveLdsRows) {
-    static bool attr_set = false;
-    if (!attr_set) {
+    if (!ws.back_solve_lds) {
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(back_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)(kBackSolveLdsRows * sizeof(double))));
-      attr_set = true;
+      ws.back_solve_lds = true;
     }
     hipLaunchKernelGGL(back_solve_kernel<true>, dim3(1), dim3(1024), (size_t)nf * sizeof(double), s, T, ld, nf, yrow, nreal, map, out, xs, inv);
   } else {
@@ -1264,48 +1257,18 @@ __global__ void __launch_bounds__(256) murty_small_kernel(int n, const double *A
   if (tid == 0) { res->solved = solved; res->pivots = pivots; res->not_spd = s_fail; res->pad = 0; }
 }
 
-// Device scratch of the dense solvers.  A solve takes some twenty-five buffers; hipMalloc + hipFree for each of them
-// (hipFree synchronises the device) cost more than a millisecond per call at N = 2048.  Freed blocks therefore go to a
-// small per-host-thread cache and the next request of at most that size reuses them; the cache holds at most 256 MB
-// (beyond that a released block is really freed).
-struct ScratchCache {
-  struct Block { void *p; size_t bytes; };
-  std::vector<Block> free_blocks;
-  size_t held = 0;
-  ~ScratchCache() { for (auto &b : free_blocks) (void)hipFree(b.p); }
-  void *take(size_t &bytes) {      // in: wanted, out: the block's real size
-    int best = -1;
-    for (int i = 0; i < (int)free_blocks.size(); ++i)
-      if (free_blocks[i].bytes >= bytes && free_blocks[i].bytes <= 2 * bytes + 4096 && (best < 0 || free_blocks[i].bytes < free_blocks[best].bytes)) best = i;
-    if (best >= 0) {
-      void *p = free_blocks[best].p;
-      bytes = free_blocks[best].bytes;
-      held -= bytes;
-      free_blocks.erase(free_blocks.begin() + best);
-      return p;
-    }
-    void *p = nullptr;
-    HIPCHK(hipMalloc(&p, bytes));
-    return p;
-  }
-  void give(void *p, size_t bytes) {
-    if (held + bytes > (size_t(256) << 20)) { (void)hipFree(p); return; }
-    free_blocks.push_back({p, bytes});
-    held += bytes;
-  }
-};
-thread_local ScratchCache g_scratch;
-
+// A block of the workspace's cache (DenseWorkspace::take, runtime.h), rounded up to 256 bytes.
 template <typename T>
 struct Buf {
+  DenseWorkspace &ws;
   T *p = nullptr;
   size_t bytes = 0;
-  explicit Buf(size_t n) {
-    if (n) { bytes = ((n * sizeof(T) + 255) / 256) * 256; p = static_cast<T *>(g_scratch.take(bytes)); }
+  Buf(DenseWorkspace &w, size_t n) : ws(w) {
+    if (n) { bytes = ((n * sizeof(T) + 255) / 256) * 256; p = static_cast<T *>(ws.take(bytes)); }
   }
-  // a block goes back to the cache while kernels that use it may still be queued: the next user enqueues on the same
-  // stream (one context = one stream = one host thread), so the stream's order keeps them apart
-  ~Buf() { if (p) g_scratch.give(p, bytes); }
+  // a block goes back to the cache while kernels that use it may still be queued: the next taker enqueues on the same
+  // context's stream, so the stream's order keeps them apart
+  ~Buf() { if (p) ws.give(p, bytes); }
   Buf(const Buf &) = delete;
   Buf &operator=(const Buf &) = delete;
 };
@@ -1431,31 +1394,24 @@ __global__ void merge_factor_kernel(double *T, const double *Tl, int ld, int nro
   }
 }
 
-// work area of the factorisation (the second array), kept per host thread, grow-only
-struct FactorWork {
-  double *p = nullptr;
-  size_t cap = 0;
-};
-thread_local FactorWork g_fwork;
-
 // the diagonal-tile kernel needs 110 KB of LDS: opt in once
-void launch_diag(hipStream_t s, const double *T, double *Tout, int ld, int k0, double *inv, int *fail) {
-  static bool attr_set = false;
-  if (!attr_set) {
+void launch_diag(DenseWorkspace &ws, const double *T, double *Tout, int ld, int k0, double *inv, int *fail) {
+  if (!ws.diag_lds) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(chol_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDiagLdsBytes));
-    attr_set = true;
+    ws.diag_lds = true;
   }
-  hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(kDiagThreads), kDiagLdsBytes, s, T, Tout, ld, k0, inv, fail);
+  hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(kDiagThreads), kDiagLdsBytes, ws.stream, T, Tout, ld, k0, inv, fail);
 }
 
 // Blocked Cholesky of the first nf (multiple of 64) columns of T; inv receives
 // the nf/64 inverted diagonal blocks (64x64 each).
-void factor_launches(hipStream_t s, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase) {
+void factor_launches(DenseWorkspace &ws, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase) {
+  hipStream_t s = ws.stream;
   const int iend = ibase >= 0 ? ibase + nf : -1;
   if (ibase < 0) ibase = 1 << 30;
   for (int k0 = 0; k0 < nf; k0 += NB) {
     double *inv_k = inv + (size_t)(k0 / NB) * NB * NB;
-    launch_diag(s, T, T, ld, k0, inv_k, fail);
+    launch_diag(ws, T, T, ld, k0, inv_k, fail);
     const int slabs = (nrows - (k0 + NB) + NB - 1) / NB;
     if (slabs > 0) hipLaunchKernelGGL(chol_trsm_kernel, dim3(slabs), dim3(256), 0, s, T, T, ld, nrows, k0, inv_k, ibase, iend);
     const int tr = (nrows - (k0 + NB) + NB - 1) / NB, tc = (ld - (k0 + NB) + NB - 1) / NB;
@@ -1469,27 +1425,27 @@ void factor_launches(hipStream_t s, double *T, int ld, int nrows, int nf, int *f
 // (inverse_rows_solve_kernel) instead of a block-by-block back substitution in a single workgroup, which one CU's
 // memory bandwidth bounds (the strips of L are n^2 / 2 doubles: 34 us at n = 512, 105 us at n = 1088).  The extra
 // tiles run on other CUs in the shadow of the diagonal tile's chain.
-void factor(hipStream_t s, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase = -1) {
+void factor(DenseWorkspace &ws, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase = -1) {
   if (nf <= 0) return;
+  hipStream_t s = ws.stream;
   static const bool fused = [] { const char *e = std::getenv("EGS_CHOL_FUSED"); return !(e && std::atoi(e) == 0); }();
-  if (!fused || nf <= NB) { factor_launches(s, T, ld, nrows, nf, fail, inv, ibase); return; }
+  if (!fused || nf <= NB) { factor_launches(ws, T, ld, nrows, nf, fail, inv, ibase); return; }
   const int iend = ibase >= 0 ? ibase + nf : -1;
   if (ibase < 0) ibase = 1 << 30;
   const size_t need = (size_t)nrows * ld;
-  if (g_fwork.cap < need) {
-    if (g_fwork.p) { HIPCHK(hipStreamSynchronize(s)); (void)hipFree(g_fwork.p); g_fwork.p = nullptr; g_fwork.cap = 0; }
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&g_fwork.p), (need + need / 4) * sizeof(double)));
-    g_fwork.cap = need + need / 4;
+  if (ws.factor_work.cap < need) {      // the second array: grow-only, a quarter of head-room from the start
+    if (ws.factor_work.p) HIPCHK(hipStreamSynchronize(s));
+    ws.factor_work.release();
+    ws.factor_work.alloc(need + need / 4);
   }
-  double *Tl = g_fwork.p;
+  double *Tl = ws.factor_work.p;
   const size_t lds = (size_t)(3 * NB * kStageLd + 32 * kTileQs + NB) * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
+  if (!ws.panel_lds) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(chol_panel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
+    ws.panel_lds = true;
   }
   // the first diagonal block has no update before it
-  launch_diag(s, T, Tl, ld, 0, inv, fail);
+  launch_diag(ws, T, Tl, ld, 0, inv, fail);
   for (int k0 = 0; k0 < nf; k0 += NB) {
     double *inv_k = inv + (size_t)(k0 / NB) * NB * NB;
     const int tr = (nrows - (k0 + NB) + NB - 1) / NB, tc = (ld - (k0 + NB) + NB - 1) / NB;
@@ -1505,6 +1461,23 @@ void factor(hipStream_t s, double *T, int ld, int nrows, int nf, int *fail, doub
   hipLaunchKernelGGL(merge_factor_kernel, dim3(grid1((size_t)nrows * nf)), dim3(256), 0, s, T, Tl, ld, nrows, nf);
 }
 
+}  // namespace
+
+// The workspace's page-locked records: murty_advance_kernel writes `step` and the host reads it after the sync;
+// `words` is the landing area of the deferred checks (a line of its own: the host polls step.seq while copies land here).
+struct HostWords { unsigned long long sym[2]; int fail; int pad; };
+struct DensePinned { alignas(64) MurtyStep step; alignas(64) HostWords words; };
+
+namespace {
+
+DensePinned *pinned_records(DenseWorkspace &ws) {
+  if (!ws.pinned.p) {
+    ws.pinned.alloc(1);
+    std::memset(ws.pinned.p, 0, sizeof(DensePinned));
+  }
+  return ws.pinned.p;
+}
+
 // Murty on (A n x n device, b device).  Mirrors lcp.cc:157-274; box_fix as in
 // the oracle (true box problem: solve once before the first check).
 //
@@ -1514,57 +1487,13 @@ void factor(hipStream_t s, double *T, int ld, int nrows, int nf, int *fail, doub
 // safeguard that guarantees termination.  Same unique solution for SPD A, in
 // tens of factorisations instead of hundreds -- and no min(1000, 2^n) cap, which
 // the reference's single-index rule exhausts for n >~ 600.
-// One pinned (host-coherent) record per host thread: murty_advance_kernel writes it, the host reads it after the sync.
-MurtyStep *pinned_step() {
-  struct Holder {
-    MurtyStep *p = nullptr;
-    ~Holder() { if (p) (void)hipHostFree(p); }
-  };
-  thread_local Holder h;
-  if (!h.p) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h.p), sizeof(MurtyStep), hipHostMallocDefault));
-    std::memset(h.p, 0, sizeof(MurtyStep));
-  }
-  return h.p;
-}
-
-// a second stream (and an event) per host thread for work that overlaps the main stream's
-hipStream_t side_stream() {
-  struct Holder {
-    hipStream_t q = nullptr;
-    ~Holder() { if (q) (void)hipStreamDestroy(q); }
-  };
-  thread_local Holder h;
-  if (!h.q) HIPCHK(hipStreamCreateWithFlags(&h.q, hipStreamNonBlocking));
-  return h.q;
-}
-hipEvent_t side_event() {
-  struct Holder {
-    hipEvent_t e = nullptr;
-    ~Holder() { if (e) (void)hipEventDestroy(e); }
-  };
-  thread_local Holder h;
-  if (!h.e) HIPCHK(hipEventCreateWithFlags(&h.e, hipEventDisableTiming));
-  return h.e;
-}
-
-struct HostWords { unsigned long long sym[2]; int fail; int pad; };   // pinned landing area of the deferred checks
-HostWords *pinned_words() {
-  struct Holder {
-    HostWords *p = nullptr;
-    ~Holder() { if (p) (void)hipHostFree(p); }
-  };
-  thread_local Holder h;
-  if (!h.p) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h.p), sizeof(HostWords), hipHostMallocDefault));
-  return h.p;
-}
-
 // extra_fail: a device flag of the caller's own factorisation, folded into the record's `fail`; after_first_sync: run
 // once after the first synchronisation (the caller's deferred checks ride on it instead of synchronising themselves).
-bool murty_device(hipStream_t s, int n, const double *dA, const double *db, const std::vector<double> &lo,
+bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db, const std::vector<double> &lo,
                   const std::vector<double> &hi, bool box_fix, bool block, int max_pivots, double max_seconds, double *dx,
                   double *dw, int *pivots_out, std::string *msg, const int *extra_fail = nullptr,
                   const std::function<void()> *after_first_sync = nullptr) {
+  hipStream_t s = ws.stream;
   const auto t_start = std::chrono::steady_clock::now();
   for (int i = 0; i < n; ++i)   // lcp.cc:161-164; the box variant also admits hi == 0 (toolkit/lcp.h:129)
     if (!(lo[i] < hi[i]) || !(lo[i] <= 0) || !(box_fix ? hi[i] >= 0 : hi[i] > 0)) { if (msg) *msg = "bounds must satisfy lo <= 0 < hi (lcp.cc:161-164)"; return false; }
@@ -1575,8 +1504,8 @@ bool murty_device(hipStream_t s, int n, const double *dA, const double *db, cons
   // the caller's own cap (lcp::Settings::max_iterations, toolkit/lcp.h:161-164): give up and return false
   if (max_pivots > 0 && max_pivots < max_iterations) max_iterations = max_pivots;
   if (n <= kSmallMurtyMax && !block) {   // the whole loop in one workgroup, one read-back
-    Buf<double> lo_s(n), hi_s(n);
-    Buf<SmallMurtyResult> res_d(1);
+    Buf<double> lo_s(ws, n), hi_s(ws, n);
+    Buf<SmallMurtyResult> res_d(ws, 1);
     SmallMurtyResult res{};
     HIPCHK(hipMemcpyAsync(lo_s.p, lo.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(hi_s.p, hi.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1592,23 +1521,23 @@ bool murty_device(hipStream_t s, int n, const double *dA, const double *db, cons
     return res.solved != 0;
   }
   const int npad_max = (n + NB - 1) / NB * NB;
-  Buf<double> T((size_t)(2 * npad_max + 1) * npad_max), lohi_d(2 * (size_t)n), Cb(n), beff(n), r(n), bx(n), bw(n), xs(npad_max), dinv((size_t)npad_max * NB);
-  Buf<uint8_t> S_d(n);
-  Buf<int> idx_d(n), fail_d(1);
-  Buf<MurtyState> st_d(1);
+  Buf<double> T(ws, (size_t)(2 * npad_max + 1) * npad_max), lohi_d(ws, 2 * (size_t)n), Cb(ws, n), beff(ws, n), r(ws, n), bx(ws, n), bw(ws, n), xs(ws, npad_max), dinv(ws, (size_t)npad_max * NB);
+  Buf<uint8_t> S_d(ws, n);
+  Buf<int> idx_d(ws, n), fail_d(ws, 1);
+  Buf<MurtyState> st_d(ws, 1);
   // bordered pivots (see border_* kernels): the base set of the last factorisation and the work arrays
   static const bool border_on = [] { const char *e = std::getenv("EGS_DENSE_BORDER"); return !(e && std::atoi(e) == 0); }();
   static const bool start_guess = [] { const char *e = std::getenv("EGS_DENSE_GUESS"); return !(e && std::atoi(e) == 0); }();
   const bool track_base = border_on && n <= 2048;      // (the forward product keeps n / 64 partial copies of Y)
-  Buf<int> pos0(track_base ? n : 0), idx0(track_base ? npad_max : 0), Dl(track_base ? kBorderMax : 0), Rl(track_base ? kBorderMax : 0);
-  Buf<double> Um(track_base ? (size_t)npad_max * kBorderStride : 0), Ym(track_base ? (size_t)npad_max * kBorderStride : 0),
-      Cpart(track_base ? (size_t)(npad_max / NB) * kBorderStride * kBorderStride : 0), zz(track_base ? kBorderStride : 0), vv(track_base ? npad_max : 0),
-      Yp(track_base ? (size_t)(npad_max / NB) * npad_max * kBorderStride : 0);
+  Buf<int> pos0(ws, track_base ? n : 0), idx0(ws, track_base ? npad_max : 0), Dl(ws, track_base ? kBorderMax : 0), Rl(ws, track_base ? kBorderMax : 0);
+  Buf<double> Um(ws, track_base ? (size_t)npad_max * kBorderStride : 0), Ym(ws, track_base ? (size_t)npad_max * kBorderStride : 0),
+      Cpart(ws, track_base ? (size_t)(npad_max / NB) * kBorderStride * kBorderStride : 0), zz(ws, track_base ? kBorderStride : 0), vv(ws, track_base ? npad_max : 0),
+      Yp(ws, track_base ? (size_t)(npad_max / NB) * npad_max * kBorderStride : 0);
   int base_n0 = -1;      // |S0|, or -1 while nothing is factored
   if (track_base) HIPCHK(hipMemsetAsync(pos0.p, 0xff, (size_t)n * sizeof(int), s));
   const double *lo_d = lohi_d.p, *hi_d = lohi_d.p + n;
-  MurtyStep *rec = pinned_step();
-  int seq = rec->seq;      // continues across calls (the record is per host thread)
+  MurtyStep *rec = &pinned_records(ws)->step;
+  int seq = rec->seq;      // continues across calls (the record is the workspace's)
   {
     std::vector<double> lohi(2 * (size_t)n);
     std::copy(lo.begin(), lo.end(), lohi.begin());
@@ -1680,7 +1609,7 @@ bool murty_device(hipStream_t s, int n, const double *dA, const double *db, cons
       last_bordered = false;
       hipLaunchKernelGGL(build_pivot_kernel, dim3(grid1((size_t)(2 * nspad + 1) * nspad)), dim3(256), 0, s, dA, n, idx_d.p, ns,
                          nspad, beff.p, T.p, 1, track_base ? pos0.p : (int *)nullptr, idx0.p);
-      factor(s, T.p, nspad, 2 * nspad + 1, nspad, fail_d.p, dinv.p, nspad);
+      factor(ws, T.p, nspad, 2 * nspad + 1, nspad, fail_d.p, dinv.p, nspad);
       hipLaunchKernelGGL(inverse_rows_solve_kernel, dim3((ns + 3) / 4), dim3(256), 0, s, T.p, nspad, nspad, nspad,
                          T.p + (size_t)2 * nspad * nspad, ns, idx_d.p, dx, (const uint8_t *)nullptr);
       if (track_base) base_n0 = ns;      // (build_pivot_kernel recorded the set: the base of the bordered pivots that may follow)
@@ -1724,19 +1653,20 @@ namespace {
 // The host entry uploads the lower block trapezoids of A first and hands the rest over as `upload_rest`: the Schur stage
 // (which reads the lower triangle only) is enqueued before the host pushes the remainder on a second stream, where the
 // symmetry check then runs; `side` is that stream.
-bool dense_mixed_impl(hipStream_t s, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
+bool dense_mixed_impl(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
                       bool use_bounds, bool block_pivoting, int max_pivots, double max_seconds, double *x, double *w, double *dx_out,
                       int *pivots, std::string *msg, const std::function<void()> *upload_rest, hipStream_t side);
 }  // namespace
 
-bool dense_mixed_constraints(hipStream_t s, int N, const double *A, const double *b, const uint8_t *C, const double *lo,
+bool dense_mixed_constraints(DenseWorkspace &ws, int N, const double *A, const double *b, const uint8_t *C, const double *lo,
                              const double *hi, bool use_bounds, bool block_pivoting, double *x, double *w, int *pivots,
                              std::string *msg, int max_pivots, double max_seconds) {
   if (pivots) *pivots = 0;
   if (N == 0) return true;
+  hipStream_t s = ws.stream;
   const bool trace = std::getenv("EGS_DENSE_TRACE") != nullptr;
   const auto t_a = std::chrono::steady_clock::now();
-  Buf<double> dA((size_t)N * N), db(N);
+  Buf<double> dA(ws, (size_t)N * N), db(ws, N);
   const auto t_b = std::chrono::steady_clock::now();
   // (a pageable source: ROCm 7.2 moves these 33.6 MB in 0.6 ms on MI355X's host; a hand-made threaded staging copy took 0.9).
   // From N = 1024 on the lower block trapezoids go first (62 % of the bytes with four blocks of rows, 0.41 ms) -- all the
@@ -1750,13 +1680,13 @@ bool dense_mixed_constraints(hipStream_t s, int N, const double *A, const double
   } side_guard{&side};
   std::function<void()> rest;
   if (chunk) {
-    side = side_stream();
+    side = ws.side_stream();
     for (int r0 = 0; r0 < N; r0 += chunk) {
       const int r1 = std::min(N, r0 + chunk);
       HIPCHK(hipMemcpy2DAsync(dA.p + (size_t)r0 * N, (size_t)N * sizeof(double), A + (size_t)r0 * N, (size_t)N * sizeof(double),
                               (size_t)r1 * sizeof(double), (size_t)(r1 - r0), hipMemcpyHostToDevice, s));
     }
-    hipEvent_t ev = side_event();
+    hipEvent_t ev = ws.side_event();
     HIPCHK(hipEventRecord(ev, s));
     HIPCHK(hipStreamWaitEvent(side, ev, 0));      // (the symmetry check on the side stream reads the lower part too)
     rest = [&, chunk, side]() {
@@ -1776,7 +1706,7 @@ bool dense_mixed_constraints(hipStream_t s, int N, const double *A, const double
                  std::chrono::duration<double, std::milli>(t_c - t_b).count());
   }
   HIPCHK(hipMemcpyAsync(db.p, b, N * sizeof(double), hipMemcpyHostToDevice, s));
-  return dense_mixed_impl(s, N, dA.p, db.p, C, lo, hi, use_bounds, block_pivoting, max_pivots, max_seconds, x, w, nullptr, pivots, msg,
+  return dense_mixed_impl(ws, N, dA.p, db.p, C, lo, hi, use_bounds, block_pivoting, max_pivots, max_seconds, x, w, nullptr, pivots, msg,
                           chunk ? &rest : nullptr, side);
 }
 
@@ -1911,20 +1841,21 @@ __global__ void __launch_bounds__(1024) cond_iterations_kernel(const double *A, 
   if (tid == 0) { out[0] = lmax; out[1] = mu; }
 }
 
-double dense_condition_estimate(hipStream_t s, int N, const double *dA, bool *spd, double *pivot_bound) {
+double dense_condition_estimate(DenseWorkspace &ws, int N, const double *dA, bool *spd, double *pivot_bound) {
   if (spd) *spd = true;
   if (pivot_bound) *pivot_bound = 1.0;
   if (N == 0) return 1.0;
+  hipStream_t s = ws.stream;
   const int npad = (N + NB - 1) / NB * NB;
-  Buf<double> T((size_t)(npad + 1) * npad), dinv((size_t)npad * NB), zero(N), mm(4);
-  Buf<int> idx_d(N), fail_d(1);
+  Buf<double> T(ws, (size_t)(npad + 1) * npad), dinv(ws, (size_t)npad * NB), zero(ws, N), mm(ws, 4);
+  Buf<int> idx_d(ws, N), fail_d(ws, 1);
   std::vector<int> idx(N);
   for (int i = 0; i < N; ++i) idx[i] = i;
   HIPCHK(hipMemcpyAsync(idx_d.p, idx.data(), N * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(zero.p, 0, N * sizeof(double), s));
   HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
   hipLaunchKernelGGL(build_pivot_kernel, dim3(grid1((size_t)(npad + 1) * npad)), dim3(256), 0, s, dA, N, idx_d.p, N, npad, zero.p, T.p, 0, (int *)nullptr, (int *)nullptr);
-  factor(s, T.p, npad, npad + 1, npad, fail_d.p, dinv.p);
+  factor(ws, T.p, npad, npad + 1, npad, fail_d.p, dinv.p);
   hipLaunchKernelGGL(diag_minmax_kernel, dim3(1), dim3(256), 0, s, T.p, npad, N, mm.p);
   double h[4] = {1, 1, 0, 0};
   int fail = 0;
@@ -1943,27 +1874,28 @@ double dense_condition_estimate(hipStream_t s, int N, const double *dA, bool *sp
   return est > r * r ? est : r * r;          // two lower bounds: the larger one
 }
 
-bool dense_mixed_constraints_device(hipStream_t s, int N, const double *dA_in, const double *db_in, const uint8_t *C,
+bool dense_mixed_constraints_device(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C,
                                     const double *lo, const double *hi, bool use_bounds, bool block_pivoting, int max_pivots,
                                     double max_seconds, double *x, double *w, double *dx_out, int *pivots, std::string *msg) {
-  return dense_mixed_impl(s, N, dA_in, db_in, C, lo, hi, use_bounds, block_pivoting, max_pivots, max_seconds, x, w, dx_out, pivots, msg,
+  return dense_mixed_impl(ws, N, dA_in, db_in, C, lo, hi, use_bounds, block_pivoting, max_pivots, max_seconds, x, w, dx_out, pivots, msg,
                           nullptr, nullptr);
 }
 
 namespace {
-bool dense_mixed_impl(hipStream_t s, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
+bool dense_mixed_impl(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
                       bool use_bounds, bool block_pivoting, int max_pivots, double max_seconds, double *x, double *w, double *dx_out,
                       int *pivots, std::string *msg, const std::function<void()> *upload_rest, hipStream_t side) {
   if (pivots) *pivots = 0;
   if (N == 0) return true;
+  hipStream_t s = ws.stream;
   const auto t_dev0 = std::chrono::steady_clock::now();
   std::vector<int> E, I;
   for (int i = 0; i < N; ++i) (C[i] ? E : I).push_back(i);
   const int ne = (int)E.size(), ni = (int)I.size();
   const int nepad = (ne + NB - 1) / NB * NB;
   const int ld = nepad + ni, rows = nepad + ni + 1;
-  Buf<double> T((size_t)rows * (ld > 0 ? ld : 1)), lhs((size_t)ni * ni), rhs(ni), xi(ni), wi(ni), xe(ne), xs(nepad), dinv((size_t)nepad * NB);
-  Buf<int> dEI(N), fail_d(1);
+  Buf<double> T(ws, (size_t)rows * (ld > 0 ? ld : 1)), lhs(ws, (size_t)ni * ni), rhs(ws, ni), xi(ws, ni), wi(ws, ni), xe(ws, ne), xs(ws, nepad), dinv(ws, (size_t)nepad * NB);
+  Buf<int> dEI(ws, N), fail_d(ws, 1);
   int *const dE_p = dEI.p, *const dI_p = dEI.p + ne;
   struct { const double *p; } dA{dA_in}, db{db_in};
   {
@@ -1974,8 +1906,8 @@ bool dense_mixed_impl(hipStream_t s, int N, const double *dA_in, const double *d
   HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
   // A must be symmetric: the factorisations read its lower triangle only.  The verdict (and the Schur factorisation's
   // failure flag) is read at the first synchronisation the pivot loop makes anyway, not at one of its own.
-  Buf<unsigned long long> sym_d(2);
-  HostWords *host = pinned_words();
+  Buf<unsigned long long> sym_d(ws, 2);
+  HostWords *host = &pinned_records(ws)->words;
   auto check_symmetry = [&](hipStream_t q) {
     HIPCHK(hipMemsetAsync(sym_d.p, 0, 2 * sizeof(unsigned long long), q));
     hipLaunchKernelGGL(symmetry_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, q, dA.p, N, sym_d.p);
@@ -1985,7 +1917,7 @@ bool dense_mixed_impl(hipStream_t s, int N, const double *dA_in, const double *d
   // Schur stage: factor the E columns of [A_ee A_ei; A_ie A_ii; b^T]   (lcp.cc:286-294)
   hipLaunchKernelGGL(build_schur_kernel, dim3(grid1((size_t)rows * ld)), dim3(256), 0, s, dA.p, db.p, N, dE_p, ne, nepad, dI_p, ni, T.p,
                      upload_rest ? 1 : 0);
-  factor(s, T.p, ld, rows, nepad, fail_d.p, dinv.p);
+  factor(ws, T.p, ld, rows, nepad, fail_d.p, dinv.p);
   if (ni) hipLaunchKernelGGL(extract_schur_kernel, dim3(grid1((size_t)ni * ni)), dim3(256), 0, s, T.p, nepad, ni, lhs.p, rhs.p);
   HIPCHK(hipMemcpyAsync(&host->fail, fail_d.p, sizeof(int), hipMemcpyDeviceToHost, s));
   if (upload_rest) {      // the device is busy with the Schur stage: now the rest of A, then the symmetry check, on the side stream
@@ -2013,19 +1945,19 @@ bool dense_mixed_impl(hipStream_t s, int N, const double *dA_in, const double *d
   const std::function<void()> once = [&]() { if (!deferred_ran) { deferred_ran = true; deferred(); } };
   bool ok = true;
   if (ni > 0) {
-    ok = murty_device(s, ni, lhs.p, rhs.p, l2, h2, use_bounds, block_pivoting, max_pivots, max_seconds, xi.p, wi.p, &piv, msg, fail_d.p, &once);
+    ok = murty_device(ws, ni, lhs.p, rhs.p, l2, h2, use_bounds, block_pivoting, max_pivots, max_seconds, xi.p, wi.p, &piv, msg, fail_d.p, &once);
     once();     // (paths of the pivot loop that return without its first synchronisation hook have synchronised all the same)
     if (schur_failed) { if (msg) *msg = "A_ee is not positive definite"; return false; }
   }
   if (pivots) *pivots = piv;
   if (!ok) return false;
   // x_e = A_ee^-1 (b_e - A_ei x_i) = L^-T (L^-1 b_e - (L^-1 A_ei) x_i)   (lcp.cc:317)
-  Buf<double> xw((size_t)2 * N);      // x and w in the caller's order: one copy back
+  Buf<double> xw(ws, (size_t)2 * N);      // x and w in the caller's order: one copy back
   std::vector<double> xwh((size_t)2 * N);
   HIPCHK(hipMemsetAsync(xw.p, 0, (size_t)2 * N * sizeof(double), s));     // w = 0 on the equality rows, lcp.cc:332-333
   if (ne) {
     hipLaunchKernelGGL(xe_rhs_kernel, dim3(nepad / NB), dim3(1024), 0, s, T.p, nepad, ni, xi.p);
-    launch_back_solve(s, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p,
+    launch_back_solve(ws, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p,
                        dinv.p);
     hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ne)), dim3(256), 0, s, ne, dE_p, xe.p, xw.p);
   }
@@ -2066,12 +1998,13 @@ __global__ void symmetrize_lower_kernel(double *A, int n) {    // A(r, c) = A(c,
 }
 }  // namespace
 
-bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const double *lo_arg, const double *hi_arg, int algorithm,
+bool box_lcp_schur(DenseWorkspace &ws, int n, double *A, const double *b_arg, const double *lo_arg, const double *hi_arg, int algorithm,
                    int nub_arg, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm_out, int *nub_out,
                    int *pivots, std::string *msg) {
   if (pivots) *pivots = 0;
   if (n <= 0) throw std::invalid_argument("SolveLCP_BoxSchur: n >= 1");
   if (nub_arg > n) throw std::invalid_argument("SolveLCP_BoxSchur: nub <= n");
+  hipStream_t s = ws.stream;
   const double big = std::numeric_limits<double>::max();
   const double inf = std::numeric_limits<double>::infinity();
   std::vector<double> b(b_arg, b_arg + n), lo(lo_arg, lo_arg + n), hi(hi_arg, hi_arg + n);
@@ -2098,7 +2031,7 @@ bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const d
   std::vector<double> l2(ni), h2(ni);
   for (int k = 0; k < ni; ++k) { l2[k] = lo[nub + k] <= -big ? -inf : lo[nub + k]; h2[k] = hi[nub + k] >= big ? inf : hi[nub + k]; }
 
-  Buf<double> dA((size_t)n * n), db(n);
+  Buf<double> dA(ws, (size_t)n * n), db(ws, n);
   if (ne == 0) {
     // entirely an LCP (toolkit/lcp.cc:695-700): the inner solver works on A itself and leaves its pivoting order there
     if (n <= kIncrementalMaxRows) {
@@ -2112,9 +2045,9 @@ bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const d
     HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(db.p, b.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(symmetrize_lower_kernel, dim3(grid1((size_t)n * n)), dim3(256), 0, s, dA.p, n);
-    Buf<double> dx(n), dw(n);
+    Buf<double> dx(ws, n), dw(ws, n);
     int piv = 0;
-    const bool good = murty_device(s, n, dA.p, db.p, l2, h2, true, true, max_steps, max_seconds, dx.p, dw.p, &piv, msg);
+    const bool good = murty_device(ws, n, dA.p, db.p, l2, h2, true, true, max_steps, max_seconds, dx.p, dw.p, &piv, msg);
     if (pivots) *pivots = piv;
     if (!good) return false;
     HIPCHK(hipMemcpyAsync(x, dx.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2127,13 +2060,13 @@ bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const d
   HIPCHK(hipMemcpyAsync(db.p, b_arg, n * sizeof(double), hipMemcpyHostToDevice, s));
   const int nepad = (ne + NB - 1) / NB * NB;
   const int ld = nepad + ni, rows = nepad + ni + 1;
-  Buf<double> T((size_t)rows * ld), lhs((size_t)ni * ni), rhs(ni), xi(ni), wi(ni), xe(ne), xs(nepad), dinv((size_t)nepad * NB), dl2(ni), dh2(ni);
-  Buf<int> dE(ne), dI(ni), fail_d(1);
+  Buf<double> T(ws, (size_t)rows * ld), lhs(ws, (size_t)ni * ni), rhs(ws, ni), xi(ws, ni), wi(ws, ni), xe(ws, ne), xs(ws, nepad), dinv(ws, (size_t)nepad * NB), dl2(ws, ni), dh2(ws, ni);
+  Buf<int> dE(ws, ne), dI(ws, ni), fail_d(ws, 1);
   HIPCHK(hipMemcpyAsync(dE.p, perm.data(), ne * sizeof(int), hipMemcpyHostToDevice, s));
   if (ni) HIPCHK(hipMemcpyAsync(dI.p, perm.data() + ne, ni * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
   hipLaunchKernelGGL(build_schur_kernel, dim3(grid1((size_t)rows * ld)), dim3(256), 0, s, dA.p, db.p, n, dE.p, ne, nepad, dI.p, ni, T.p, 1);
-  factor(s, T.p, ld, rows, nepad, fail_d.p, dinv.p);            // L L' = Z, Q = L^-1 B', R = C - Q'Q, rhs = d - B Z^-1 c
+  factor(ws, T.p, ld, rows, nepad, fail_d.p, dinv.p);            // L L' = Z, Q = L^-1 B', R = C - Q'Q, rhs = d - B Z^-1 c
   if (ni) hipLaunchKernelGGL(extract_schur_kernel, dim3(grid1((size_t)ni * ni)), dim3(256), 0, s, T.p, nepad, ni, lhs.p, rhs.p);
   // meanwhile the host applies the partition to the caller's lower triangle, as the reference leaves it
   for (const auto &sw : swaps) swap_rows_and_columns_lower(A, n, sw.first, sw.second);
@@ -2149,7 +2082,7 @@ bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const d
       HIPCHK(hipMemcpyAsync(dh2.p, h2.data(), ni * sizeof(double), hipMemcpyHostToDevice, s));
       good = box_lcp_incremental_device(s, algorithm, ni, lhs.p, rhs.p, dl2.p, dh2.p, l2.data(), h2.data(), max_steps, max_seconds, xi.p, wi.p, &piv, msg);
     } else {
-      good = murty_device(s, ni, lhs.p, rhs.p, l2, h2, true, true, max_steps, max_seconds, xi.p, wi.p, &piv, msg);
+      good = murty_device(ws, ni, lhs.p, rhs.p, l2, h2, true, true, max_steps, max_seconds, xi.p, wi.p, &piv, msg);
     }
     if (pivots) *pivots = piv;
     if (!good) return false;
@@ -2157,7 +2090,7 @@ bool box_lcp_schur(hipStream_t s, int n, double *A, const double *b_arg, const d
   // y = Z^-1 (c - B' z) = L^-T (L^-1 c - Q z)
   std::vector<double> xih(ni), wih(ni), xeh(ne);
   hipLaunchKernelGGL(xe_rhs_kernel, dim3(nepad / NB), dim3(1024), 0, s, T.p, nepad, ni, xi.p);
-  launch_back_solve(s, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p, dinv.p);
+  launch_back_solve(ws, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p, dinv.p);
   HIPCHK(hipMemcpyAsync(xeh.data(), xe.p, ne * sizeof(double), hipMemcpyDeviceToHost, s));
   if (ni) {
     HIPCHK(hipMemcpyAsync(xih.data(), xi.p, ni * sizeof(double), hipMemcpyDeviceToHost, s));

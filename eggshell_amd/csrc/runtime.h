@@ -1,5 +1,6 @@
 // runtime.h -- what every host unit of the C ABI (include/eggshell_amd.h) shares: the context, HIP error handling,
-// device and page-locked buffers, staged uploads, and the try / catch boundary of an entry point.  Internal to the
+// device and page-locked buffers, the dense solvers' workspace, staged uploads, and the try / catch boundary of an
+// entry point.  Internal to the
 // library; the plan-inspection entries (plan_debug.cpp) do without it, they make no HIP call.
 #pragma once
 
@@ -57,6 +58,20 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// Sized once, freed at scope exit: the working arrays of one call.  Plain hipMalloc / hipFree on purpose, and it must
+// not become stream-ordered or cached: with a stream-ordered pool allocation (hipMallocAsync / hipFreeAsync)
+// back-to-back calls that got the same block back saw stale lines of the previous call's matrix on this stack (ROCm
+// 7.2; tests/test_gpu_dantzig.py::test_repeated_calls_are_independent).  The Dantzig, batch and fused-Schur paths
+// therefore stay on this type and off the block cache of DenseWorkspace.
+template <typename T>
+struct ScopedDevBuf {
+  T *p = nullptr;
+  explicit ScopedDevBuf(size_t n) { if (n) HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T))); }
+  ~ScopedDevBuf() { if (p) (void)hipFree(p); }
+  ScopedDevBuf(const ScopedDevBuf &) = delete;
+  ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+};
+
 // The page-locked counterpart: grow-only, freed with its owner.  The caller sees to it that the stream no longer
 // writes to a buffer it regrows.
 template <typename T>
@@ -77,6 +92,75 @@ struct PinnedBuf {
   ~PinnedBuf() { release(); }
 };
 
+// What the dense solvers (dense_lcp.hip) keep between calls.  A context owns one: everything in it is used only by
+// work enqueued on that context's stream, under that context's device, and all of it is created on first use.
+struct DensePinned;      // dense_lcp.hip: the records the device writes for the host (pivot step, deferred checks)
+struct DenseWorkspace {
+  hipStream_t stream = nullptr;      // the owning context's
+  // Device scratch.  A solve takes some twenty-five buffers; hipMalloc + hipFree for each of them (hipFree synchronises
+  // the device) cost more than a millisecond per call at N = 2048.  Freed blocks therefore go to a small cache and the
+  // next request of at most that size reuses them; the cache holds at most 256 MB (beyond that a released block is
+  // really freed).
+  struct Block { void *p; size_t bytes; };
+  std::vector<Block> free_blocks;
+  size_t held = 0;
+  void *take(size_t &bytes) {      // in: wanted, out: the block's real size
+    int best = -1;
+    for (int i = 0; i < (int)free_blocks.size(); ++i)
+      if (free_blocks[i].bytes >= bytes && free_blocks[i].bytes <= 2 * bytes + 4096 && (best < 0 || free_blocks[i].bytes < free_blocks[best].bytes)) best = i;
+    if (best >= 0) {
+      void *p = free_blocks[best].p;
+      bytes = free_blocks[best].bytes;
+      held -= bytes;
+      free_blocks.erase(free_blocks.begin() + best);
+      return p;
+    }
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {      // no memory while blocks sit idle here: hand them back and try once more
+      (void)hipGetLastError();
+      drop_blocks();
+      HIPCHK(hipMalloc(&p, bytes));
+    }
+    return p;
+  }
+  void give(void *p, size_t bytes) {
+    if (held + bytes > (size_t(256) << 20)) { (void)hipFree(p); return; }
+    free_blocks.push_back({p, bytes});
+    held += bytes;
+  }
+  void drop_blocks() {
+    for (auto &b : free_blocks) (void)hipFree(b.p);
+    free_blocks.clear();
+    held = 0;
+  }
+  DevBuf<double> factor_work;        // the second array of the fused factorisation, grow-only
+  PinnedBuf<DensePinned> pinned;
+  // a second stream (and an event) for work that overlaps the main stream's
+  hipStream_t side = nullptr;
+  hipEvent_t side_done = nullptr;
+  hipStream_t side_stream() {
+    if (!side) HIPCHK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    return side;
+  }
+  hipEvent_t side_event() {
+    if (!side_done) HIPCHK(hipEventCreateWithFlags(&side_done, hipEventDisableTiming));
+    return side_done;
+  }
+  // the kernels whose dynamic LDS limit has been raised on this context's device
+  bool back_solve_lds = false, diag_lds = false, panel_lds = false;
+  // with the device set and both streams idle
+  void release() {
+    drop_blocks();
+    factor_work.release();
+    pinned.release();
+    if (side_done) (void)hipEventDestroy(side_done);
+    if (side) (void)hipStreamDestroy(side);
+    side_done = nullptr;
+    side = nullptr;
+  }
+  ~DenseWorkspace() { release(); }
+};
+
 // Page-locked staging for host->device uploads of plan tables and device->host
 // reads of the contact topology: pageable std::vector memory makes every
 // hipMemcpyAsync a synchronous bounce through the runtime's own staging buffer.
@@ -88,8 +172,7 @@ struct PinnedArena {
     if (blocks.empty() || used + bytes > blocks.back().second) {
       const size_t want = std::max(bytes, blocks.empty() ? size_t(1) << 20 : 2 * blocks.back().second);
       char *p = nullptr;
-      if (hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) != hipSuccess)
-        throw std::runtime_error("hipHostMalloc failed");
+      HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault));
       blocks.emplace_back(p, want);
       used = 0;
     }
@@ -118,6 +201,7 @@ inline uint32_t spin_limit() {
 
 struct egs_context {
   egs::PinnedArena pinned;
+  egs::DenseWorkspace dense;   // (its stream is `stream` below)
   int device = 0;
   int cu_count = 256;   // co-residency caps of the cross-workgroup kernels scale with it
   hipStream_t stream = nullptr;

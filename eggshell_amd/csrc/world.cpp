@@ -377,12 +377,12 @@ void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double 
     double *vb = A + dense_ws_vec((size_t)N), *xs = vb + 4 * (size_t)N;
     DenseEnsStatus &st = w->dn_info[(size_t)e];
     bool spd = true;
-    st.condition = dense_condition_estimate(s, N, A, &spd);    // ensembles.cc:513-521
+    st.condition = dense_condition_estimate(w->ctx->dense, N, A, &spd);    // ensembles.cc:513-521
     st.cfm = st.condition < 1e7 ? 0.0 : cfm_coeff;
     if (st.cfm != 0.0) launch_dense_world_add_diag(A, N, st.cfm, s);
     int piv = 0;
     std::string msg;
-    const bool good = dense_mixed_constraints_device(s, N, A, vb, w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
+    const bool good = dense_mixed_constraints_device(w->ctx->dense, N, A, vb, w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
                                                      w->dn_big_hi.data() + r0, use_bounds != 0, false, 0, 0.0, nullptr,
                                                      nullptr, xs, &piv, &msg);
     st.ok = good ? 1 : 0;
