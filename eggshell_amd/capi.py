@@ -20,6 +20,7 @@ MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
 SCHED_LINSYM = 128
 SCHED_FUSED_ASSEMBLY = 256
+SCHED_DEFERRED_SYSTEM = 512
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
 # every symbol include/eggshell_amd.h declares

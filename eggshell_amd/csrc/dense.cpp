@@ -17,6 +17,7 @@ egs_status build_dense_system(egs_problem *p, double cfm) {
   if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
   if ((size_t)p->m * 3 > 46340) return fail(ctx, EGS_ERR_INVALID, "dense system too large (more than 2^31 entries)");
   const size_t N = (size_t)p->m * 3;
+  ensure_system(p);
   p->dense_A.alloc(N * N > 0 ? N * N : 1);
   launch_dense_system(p->m, p->body0.p, p->body1.p, real<double>(p->J0), real<double>(p->J1), p->Minv_d.p, cfm,
                       p->dense_A.p, ctx->stream);

@@ -107,8 +107,9 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
 template <typename REAL>
 void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, int group, bool linsym, hipStream_t s);
 // the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles, no snapshots):
-// assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s);
+// assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit.
+// store_system = false: J0, J1, rhs, lo, hi, err and is_eq are not written (the caller defers them: problem.h)
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);
@@ -201,8 +202,12 @@ void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, con
 void launch_dense_system(int m, const int32_t *body0, const int32_t *body1, const double *J0, const double *J1,
                          const double *Minv, double cfm, double *A, hipStream_t s);
 
-void launch_advance(int n, double *pos, double *R, double *v, double *w, const double *v6, double dt,
-                    hipStream_t s);
+// the four state arrays are read from *_in and written to *_out (the same arrays, or four others: a body's lane reads
+// all of its inputs before it writes)
+struct BodyState {
+  double *pos, *R, *v, *w;
+};
+void launch_advance(int n, const BodyState &in, const BodyState &out, const double *v6, double dt, hipStream_t s);
 
 constexpr int kResidualBlocks = 64;
 

@@ -457,20 +457,25 @@ __global__ void __launch_bounds__(256) mass_times_force_kernel(int n, const doub
 // StepPositions_ODE (ensembles.cc:577-591): p += dt (v + v_new)/2,
 // R = Q(dt (w + w_new)/2) R with Q = WtoQ (utils.cc:82-89); then the new
 // velocities become the body state for the next step.
-__global__ void __launch_bounds__(256) advance_kernel(int n, double *pos, double *R, double *v, double *w,
-                                                      const double *v6, double dt) {
+// The state is read from `in` and written to `out`: the same arrays (in place), or a second set, which leaves the state
+// the step started from intact (egs_problem_advance after a step whose system is deferred).
+__global__ void __launch_bounds__(256) advance_kernel(int n, const BodyState in, const BodyState out, const double *v6, double dt) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n) return;
-  double wm[3];
+  double wm[3], Rb[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Rb[k] = in.R[(size_t)b * 9 + k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const double vm = (v[(size_t)b * 3 + k] + v6[(size_t)b * 6 + k]) / 2.0;
-    pos[(size_t)b * 3 + k] = pos[(size_t)b * 3 + k] + dt * vm;
-    wm[k] = (w[(size_t)b * 3 + k] + v6[(size_t)b * 6 + 3 + k]) / 2.0;
+    const double vm = (in.v[(size_t)b * 3 + k] + v6[(size_t)b * 6 + k]) / 2.0;
+    out.pos[(size_t)b * 3 + k] = in.pos[(size_t)b * 3 + k] + dt * vm;
+    wm[k] = (in.w[(size_t)b * 3 + k] + v6[(size_t)b * 6 + 3 + k]) / 2.0;
   }
-  rotate_by_w(wm, dt, R + (size_t)b * 9);
+  rotate_by_w(wm, dt, Rb);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { v[(size_t)b * 3 + k] = v6[(size_t)b * 6 + k]; w[(size_t)b * 3 + k] = v6[(size_t)b * 6 + 3 + k]; }
+  for (int k = 0; k < 9; ++k) out.R[(size_t)b * 9 + k] = Rb[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { out.v[(size_t)b * 3 + k] = v6[(size_t)b * 6 + k]; out.w[(size_t)b * 3 + k] = v6[(size_t)b * 6 + 3 + k]; }
 }
 
 template <typename REAL>
@@ -907,9 +912,9 @@ void launch_mass_times_force(int n, const double *Minv, const double *f_ext, dou
   hipLaunchKernelGGL(mass_times_force_kernel, dim3((6 * n + 255) / 256), dim3(256), 0, s, n, Minv, f_ext, Wf);
 }
 
-void launch_advance(int n, double *pos, double *R, double *v, double *w, const double *v6, double dt, hipStream_t s) {
+void launch_advance(int n, const BodyState &in, const BodyState &out, const double *v6, double dt, hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, pos, R, v, w, v6, dt);
+  hipLaunchKernelGGL(advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, in, out, v6, dt);
 }
 
 template <typename REAL>

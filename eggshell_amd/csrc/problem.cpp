@@ -53,6 +53,14 @@ void decide_linsym_bodies(egs_problem *p) {
   p->linsym_bodies = flag != 0 ? 1 : 0;
 }
 
+// two device buffers change places (DevBuf owns its allocation: members, not objects, are exchanged)
+template <typename T>
+void swap_buffers(DevBuf<T> &a, DevBuf<T> &b) {
+  std::swap(a.p, b.p);
+  std::swap(a.count, b.count);
+  std::swap(a.cap, b.cap);
+}
+
 void ensure_wf(egs_problem *p) {
   if (p->wf_valid) return;
   p->Wf.alloc((size_t)(p->n > 0 ? p->n : 1) * 6);
@@ -114,6 +122,7 @@ egs_status do_matvec(egs_problem *p, int32_t parts, double eps, double scale, co
     return fail(ctx, EGS_ERR_INVALID, "parts must be EGS_MV_FULL or a combination of LOWER / UPPER / DIAG");
   if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
   if (p->m == 0) return EGS_OK;
+  ensure_system(p);
   ensure_minv_real(p);
   ensure_matvec_plan(p);
   if (x) upload_real(p, p->mv_x, x, (size_t)p->m * 3);
@@ -224,6 +233,17 @@ void do_assemble(egs_problem *p, double dt, double erp) {
   with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->ctx->stream); });
   HIPCHK(hipGetLastError());
   note_assembled(p);
+  p->sys_deferred = false;   // every array is written: a deferred system is superseded
+}
+
+// The deferred step's system, now: assemble_kernel on the state that step read, with its dt and erp.
+void ensure_system(egs_problem *p) {
+  if (!p->sys_deferred) return;
+  AssembleArgs a = assemble_args(p, p->deferred_dt, p->deferred_erp);
+  if (p->deferred_prev) { a.pos = p->prev_pos.p; a.R = p->prev_R.p; a.v = p->prev_v.p; a.w = p->prev_w.p; }
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->ctx->stream); });
+  HIPCHK(hipGetLastError());
+  p->sys_deferred = false;
 }
 
 void do_velocity(egs_problem *p, double dt) {
@@ -315,6 +335,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->h_rows_valid = false;
   p->use_quad = false;
   p->have_blocks = false;
+  p->sys_deferred = false;
   p->have_constraints = false;
   p->last_iterations = 0;
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
@@ -461,6 +482,7 @@ egs_status egs_problem_set_blocks(egs_problem *p, const double *Minv, const doub
   if (!p) return EGS_ERR_INVALID;
   return guarded(p->ctx, [&]() -> egs_status {
     const size_t n = p->n, m = p->m;
+    ensure_system(p);   // the arrays not given here keep the deferred step's values; M^-1 is one of its inputs
     if (Minv && n) { upload(p->Minv_d, Minv, n * 36, p->ctx->stream); p->minv_r_valid = false; p->wf_valid = false; }
     upload_real(p, p->J0, J0, m * 18);
     upload_real(p, p->J1, J1, m * 18);
@@ -514,6 +536,7 @@ egs_status egs_problem_set_state(egs_problem *p, const double *pos, const double
   return guarded(p->ctx, [&]() -> egs_status {
     const size_t n = p->n;
     hipStream_t s = p->ctx->stream;
+    ensure_system(p);   // before its inputs change
     if (pos) upload(p->pos, pos, n * 3, s);
     if (R) upload(p->R, R, n * 9, s);
     if (v) upload(p->v, v, n * 3, s);
@@ -537,6 +560,7 @@ egs_status egs_problem_set_mass(egs_problem *p, const double *inv_mass, const do
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) W[6 * (3 + r) + 3 + c] = inv_inertia[b * 9 + 3 * r + c];
     }
+    ensure_system(p);   // before its inputs change
     if (n) { upload(p->Minv_d, blocks.data(), n * 36, p->ctx->stream); p->minv_r_valid = false; p->wf_valid = false; }
     return EGS_OK;
   });
@@ -549,6 +573,7 @@ egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, cons
     if (kind[i] != EGS_JOINT_BALL && kind[i] != EGS_CONTACT_BOX)
       return fail(p->ctx, EGS_ERR_INVALID, "unknown constraint kind");
   return guarded(p->ctx, [&]() -> egs_status {
+    ensure_system(p);   // before its inputs change
     upload(p->kind, kind, (size_t)p->m, p->ctx->stream);
     upload(p->data, data, (size_t)p->m * 7, p->ctx->stream);
     note_kinds(p, kind);
@@ -592,6 +617,7 @@ egs_status egs_problem_get_blocks(egs_problem *p, double *J0, double *J1, uint8_
   if (!p) return EGS_ERR_INVALID;
   return guarded(p->ctx, [&]() -> egs_status {
     const size_t m = p->m;
+    ensure_system(p);
     download_real(p, p->J0, J0, m * 18);
     download_real(p, p->J1, J1, m * 18);
     download_real(p, p->lo, lo, m * 3);
@@ -619,7 +645,21 @@ egs_status egs_problem_advance(egs_problem *p, double dt) {
   if (!p->have_state) return fail(p->ctx, EGS_ERR_INVALID, "set_state and step first");
   return guarded(p->ctx, [&]() -> egs_status {
     if (stall_seen(p)) return report_stall(p);   // do not integrate a lambda that came out of a timed-out wait
-    launch_advance(p->n, p->pos.p, p->R.p, p->v.p, p->w.p, p->v6.p, dt, p->ctx->stream);
+    // a second advance would overwrite the one old state set that is kept
+    if (p->sys_deferred && p->deferred_prev) ensure_system(p);
+    const BodyState cur{p->pos.p, p->R.p, p->v.p, p->w.p};
+    if (!p->sys_deferred) {
+      launch_advance(p->n, cur, cur, p->v6.p, dt, p->ctx->stream);
+    } else {
+      // the deferred system is assembled from the state the step read: the new state goes to the other set of buffers
+      // and the sets change places (no copy, no extra launch)
+      const size_t nn = (size_t)(p->n > 0 ? p->n : 1);
+      p->prev_pos.alloc(nn * 3); p->prev_R.alloc(nn * 9); p->prev_v.alloc(nn * 3); p->prev_w.alloc(nn * 3);
+      launch_advance(p->n, cur, BodyState{p->prev_pos.p, p->prev_R.p, p->prev_v.p, p->prev_w.p}, p->v6.p, dt, p->ctx->stream);
+      swap_buffers(p->pos, p->prev_pos); swap_buffers(p->R, p->prev_R);
+      swap_buffers(p->v, p->prev_v); swap_buffers(p->w, p->prev_w);
+      p->deferred_prev = true;
+    }
     HIPCHK(hipGetLastError());
     return EGS_OK;
   });

@@ -76,6 +76,15 @@ struct egs_problem {
   egs::DevBuf<double> pos, R, v, w, Minv_d, f_ext, data, err, v6, res_partials;
   egs::DevBuf<double> Wf;            // M^-1 f_ext per body, rebuilt when either is re-uploaded
   bool wf_valid = false;
+  // The deferred system.  A step whose launch assembled in its prologue without storing (step_solve.hip:
+  // STORE_SYSTEM = false) leaves J0, J1, rhs, lo, hi, err and is_eq NOT materialised: sys_deferred is set and
+  // {deferred_dt, deferred_erp} is what assemble_kernel needs to make them (ensure_system: the same bits).  Every
+  // reader of those arrays calls ensure_system first, and so does every writer of an assembly input -- except
+  // egs_problem_advance, the writer of the step loop: it writes the new state into the second set (prev_*) and swaps
+  // the sets, so the state the step read stays intact in prev_* (deferred_prev) until the next step or advance.
+  bool sys_deferred = false, deferred_prev = false;
+  double deferred_dt = 0.0, deferred_erp = 0.0;
+  egs::DevBuf<double> prev_pos, prev_R, prev_v, prev_w;
   // solver arrays, REAL = double or float (byte buffers)
   egs::DevBuf<unsigned char> Minv_r, J0, J1, lo, hi, rhs, x, acc, wres;
   egs::DevBuf<unsigned char> gB0, gB1, gD, gden, gdx;  // cross-workgroup workspace
@@ -137,6 +146,8 @@ void note_kinds(egs_problem *p, const int32_t *kind);
 void note_assembled(egs_problem *p);
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp);
 void do_assemble(egs_problem *p, double dt, double erp);
+// J0, J1, rhs, lo, hi, err and is_eq are materialised after this (a no-op unless the last step deferred them)
+void ensure_system(egs_problem *p);
 void do_velocity(egs_problem *p, double dt);
 void zero_accumulators(egs_problem *p);
 void post_flag_copy(egs_problem *p);

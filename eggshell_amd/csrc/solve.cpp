@@ -21,11 +21,12 @@ struct SweepSchedule {
   int group = 1;            // tiles per workgroup of step_solve_kernel
   bool linsym = false;      // step_solve_kernel's LINSYM form
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
+  bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
   int oversize = -1;        // OversizeSchedule of the launch's oversize islands, -1: it has none
   // the bits of the kernels that ran (egs_schedule_flags); fill_stats adds those of the problem's plans
   uint32_t flags() const {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
-           (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0);
+           (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0);
   }
 };
 
@@ -61,6 +62,9 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   // EGS_FUSED_ASSEMBLY=0 keeps assemble_kernel.
   const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
   s.assemble = offer_assembly && s.linsym && !resume && pl.global.empty() && !(fe && std::atoi(fe) == 0);
+  // ... which stores no system (problem.h: ensure_system).  EGS_STEP_DEFER_SYSTEM=0 keeps the eager stores.
+  const char *de = std::getenv("EGS_STEP_DEFER_SYSTEM");
+  s.defer = s.assemble && !(de && std::atoi(de) == 0);
   return s;
 }
 
@@ -142,7 +146,11 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          launch_step_solve_assemble(a, method, pl.n_tiles, ctx->stream);
+          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, ctx->stream);
+          // the system this launch assembled: stored, or the problem's to make on demand from the state it read
+          p->sys_deferred = sc.defer;
+          p->deferred_prev = false;
+          p->deferred_dt = assemble->dt; p->deferred_erp = assemble->erp;
         }
       } else {
         launch_step_solve<REAL>(a, method, pl.n_tiles, pl.block, sc.group, sc.linsym, ctx->stream);
@@ -322,6 +330,7 @@ int batch_read_running(egs_problem *p, BatchSolveState &B, int *flag) {
 }  // namespace
 
 void launch_residual(egs_problem *p) {
+  ensure_system(p);   // the metric sorts the rows by lo, hi and is_eq
   const int rows = 3 * p->m;
   hipStream_t s = p->ctx->stream;
   with_real(p, [&](auto r) {
@@ -381,6 +390,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
     return EGS_OK;
   }
+  if (!assemble) ensure_system(p);   // this solve reads the stored system
   ensure_minv_real(p);   // also decides the isotropic fast path, hence the tile size
   if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
   if (stall_seen(p)) return report_stall(p);   // an earlier asynchronous solve timed out
@@ -537,6 +547,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   if (!p->have_blocks) return fail(ctx, EGS_ERR_INVALID, "no system uploaded (set_blocks or assemble first)");
   const int E = B.segs.n_ens;
   const size_t rs = p->real_size(), m = (size_t)p->m, n = (size_t)(p->n > 0 ? p->n : 1);
+  ensure_system(p);
   auto finish = [&]() {
     HIPCHK(hipMemcpyAsync(B.h_ints.p, B.stop().iterations, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(B.h_res.p, B.stop().residual, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -625,6 +636,7 @@ void accumulators_from_lambda(egs_problem *p) {
   egs_default_params(&prm);
   prm.method = EGS_GAUSS_SEIDEL; prm.tol = 0.0; prm.max_iters = 0;
   hipStream_t s = p->ctx->stream;
+  ensure_system(p);
   const size_t bytes = (size_t)p->m * 3 * p->real_size();
   p->tmp_rows.alloc(bytes > 0 ? bytes : 1);
   HIPCHK(hipMemcpyAsync(p->tmp_rows.p, p->rhs.p, bytes, hipMemcpyDeviceToDevice, s));

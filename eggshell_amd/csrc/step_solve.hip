@@ -38,6 +38,8 @@
 // solve (get_blocks, the residual, matvec, later solves).  Nothing waits for these stores: they drain while the
 // timetable runs.  Every constraint of the problem is a lane of some tile (solve.cpp: no oversize islands), so all of
 // them are written.
+// STORE_SYSTEM = false: none of that is stored -- a step reads none of it (the sweeps run from registers) -- and the
+// problem remembers that its system is not materialised (problem.h: ensure_system runs assemble_kernel on demand).
 #include <algorithm>
 
 #include "kernels.h"
@@ -88,7 +90,8 @@ __device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, con
 
 // The ASSEMBLE prologue of one lane: K1-K4 for constraint cidx (J0 / J1 into c, for stage_blocks and load_cons), rhs,
 // err, lo, hi and is_eq to global memory where assemble_kernel puts them (24 B per lane and array: a few lines per
-// store instruction), rhs, lo, hi and eq into c.
+// store instruction), rhs, lo, hi and eq into c.  STORE = false: into c only.
+template <bool STORE>
 __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, Cons<double> &c) {
   double e[3], lo[3], hi[3], u0[6], u1[6];
   bool eq;
@@ -96,11 +99,13 @@ __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, C
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     c.rhs[r] = assemble_rhs(G, c.J0, c.J1, e, u0, u1, r);
-    reinterpret_cast<double *>(G.rhs)[(size_t)cidx * 3 + r] = c.rhs[r];
-    G.err[(size_t)cidx * 3 + r] = e[r];
-    reinterpret_cast<double *>(G.lo)[(size_t)cidx * 3 + r] = lo[r];
-    reinterpret_cast<double *>(G.hi)[(size_t)cidx * 3 + r] = hi[r];
-    G.is_eq[(size_t)cidx * 3 + r] = eq ? 1 : 0;
+    if constexpr (STORE) {
+      reinterpret_cast<double *>(G.rhs)[(size_t)cidx * 3 + r] = c.rhs[r];
+      G.err[(size_t)cidx * 3 + r] = e[r];
+      reinterpret_cast<double *>(G.lo)[(size_t)cidx * 3 + r] = lo[r];
+      reinterpret_cast<double *>(G.hi)[(size_t)cidx * 3 + r] = hi[r];
+      G.is_eq[(size_t)cidx * 3 + r] = eq ? 1 : 0;
+    }
     c.lo[r] = lo[r];
     c.hi[r] = hi[r];
     c.eq[r] = eq;
@@ -143,7 +148,8 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
   return n_phases >= 1 ? depth + P * (n_phases - 1) : 0;
 }
 
-template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false>
+template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
+          bool STORE_SYSTEM = true>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WAVES = BLOCK / 64;
@@ -177,9 +183,11 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
   if constexpr (ASSEMBLE) {
-    if (active) assemble_lane(A.assemble, d.cidx, c);
-    stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
-    __syncthreads();   // every wavefront has read its staging area back
+    if (active) assemble_lane<STORE_SYSTEM>(A.assemble, d.cidx, c);
+    if constexpr (STORE_SYSTEM) {
+      stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
+      __syncthreads();   // every wavefront has read its staging area back
+    }
     for (int s = tid; s < nslots; s += BLOCK) {   // a fresh solve: the accumulators start from zero
 #pragma unroll
       for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = REAL(0);
@@ -317,16 +325,26 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 #undef EGS_LAUNCH_SH
 }
 
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, hipStream_t s) {
-  SolveArgs<double> b = a;
-  b.n_tiles = n_tiles;
-  const size_t lds = std::max((size_t)b.max_slots * 6 * sizeof(double), (size_t)4 * kStageWave * sizeof(double));
-  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true>;
-  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true>;
+namespace {
+template <bool STORE_SYSTEM>
+void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
+  // the accumulators; the storing form stages its blocks in the same LDS first
+  size_t lds = (size_t)b.max_slots * 6 * sizeof(double);
+  if (STORE_SYSTEM) lds = std::max(lds, (size_t)4 * kStageWave * sizeof(double));
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
   else hipLaunchKernelGGL(k2, dim3(n_tiles), dim3(256), lds, s, b);
+}
+}  // namespace
+
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, hipStream_t s) {
+  SolveArgs<double> b = a;
+  b.n_tiles = n_tiles;
+  if (store_system) launch_step_solve_assemble_t<true>(b, method, n_tiles, s);
+  else launch_step_solve_assemble_t<false>(b, method, n_tiles, s);
 }
 
 template void launch_step_solve<double>(const SolveArgs<double> &, int, int, int, int, bool, hipStream_t);

@@ -318,7 +318,8 @@ egs_status world_step_guard(egs_world *w, double dt, const char *fp64_what) {
 void world_integrate(egs_world *w, double dt) {
   egs_problem *p = w->prob;
   do_velocity(p, dt);
-  launch_advance(p->n, p->pos.p, p->R.p, p->v.p, p->w.p, p->v6.p, dt, w->ctx->stream);
+  const BodyState state{p->pos.p, p->R.p, p->v.p, p->w.p};
+  launch_advance(p->n, state, state, p->v6.p, dt, w->ctx->stream);
   HIPCHK(hipGetLastError());
 }
 

@@ -96,8 +96,13 @@ typedef enum {
   EGS_SCHED_LEAN = 64,         /* reserved, never reported: a retired 128-VGPR form of the timetable sweep */
   EGS_SCHED_LINSYM = 128,      /* step_solve_kernel's LINSYM form: the fp64 isotropic timetable sweep with one linear
                                   block for both sides (J1_lin = -J0_lin and equal linear weights, bit for bit) */
-  EGS_SCHED_FUSED_ASSEMBLY = 256   /* egs_problem_step assembled the Jacobian in the LINSYM launch's prologue
+  EGS_SCHED_FUSED_ASSEMBLY = 256,  /* egs_problem_step assembled the Jacobian in the LINSYM launch's prologue
                                       (no separate assembly kernel; the same blocks, bit for bit) */
+  EGS_SCHED_DEFERRED_SYSTEM = 512  /* ... and that launch stored no system: J0, J1, rhs, lo, hi, err and is_eq are
+                                      made on demand, by the first call that reads them (the same bits): one
+                                      assembly launch, what the step saved.  Readers: get_blocks, matvec, a solve or
+                                      a step that does not fuse, the dense entries, and the residual -- so a step
+                                      asked for statistics, or get_stats after one, pays for it too */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
