@@ -4,6 +4,7 @@ Plumbing only: numpy arrays in, numpy arrays out.  There is NO CPU fallback;
 if the library is missing or no gfx950 device is usable the calls raise.
 """
 import ctypes as C
+import ctypes as _ct   # for the methods that call an argument C, as the reference does
 import os
 import weakref
 
@@ -38,7 +39,7 @@ EXPORTS = [
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
-    "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_debug_plan_patches", "egs_problem_debug_trace",
+    "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
     "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
@@ -116,11 +117,23 @@ def lcp_batch_offsets(ns):
 def pack_lcp_batch(As, bs, los, his):
     """Lists of matrices and vectors -> ns, A, b, lo, hi in the packed batch layout (host only)."""
     ns = np.array([np.shape(b)[0] for b in bs], np.int32)
+    if len(As) != len(bs):
+        raise ValueError("%d matrices for %d right-hand sides" % (len(As), len(bs)))
     for k, a in enumerate(As):
         if np.shape(a) != (ns[k], ns[k]):
             raise ValueError("problem %d: matrix %s for %d rows" % (k, np.shape(a), ns[k]))
     cat = lambda vs: np.concatenate([_f64(v).reshape(-1) for v in vs]) if len(vs) else np.zeros(0)
     return ns, cat(As), cat(bs), cat(los), cat(his)
+
+
+def pack_batch_vectors(ns, vs, dtype=np.float64, what="vector"):
+    """A list of per-problem vectors -> one packed array in the batch layout; every vector must have its problem's size."""
+    if len(vs) != len(ns):
+        raise ValueError("%d %ss for %d problems" % (len(vs), what, len(ns)))
+    for k, v in enumerate(vs):
+        if np.shape(v) != (ns[k],):
+            raise ValueError("problem %d: %s %s for %d rows" % (k, what, np.shape(v), ns[k]))
+    return np.concatenate([np.ascontiguousarray(v, dtype=dtype) for v in vs]) if len(vs) else np.zeros(0, dtype)
 
 
 def unpack_lcp_batch(ns, A=None, *vectors):
@@ -133,6 +146,28 @@ def unpack_lcp_batch(ns, A=None, *vectors):
     for v in vectors:
         out.append([v[vo[k]:vo[k + 1]] for k in range(cnt)])
     return out
+
+
+def check_dense_iterate_batch(ns, A, b, C=None, lo=None, hi=None):
+    """The size checks of Context.dense_iterate_batch_packed (host only): the packed arrays must hold exactly what the
+    sizes ask for, and C, lo and hi come together.  Returns ns, A, b, C, lo, hi as the C ABI takes them.  (A size outside
+    0..1024 is the library's to refuse; it counts as no rows here.)"""
+    ns = np.asarray(ns)
+    if ns.ndim != 1 or (ns.size and not np.issubdtype(ns.dtype, np.integer)):
+        raise ValueError("ns: a list of integer sizes")
+    ns = np.ascontiguousarray(ns, dtype=np.int32)
+    rows = np.maximum(ns, 0).astype(np.int64)
+    tot = int(rows.sum())
+    A, b, lo, hi = map(_f64, (A, b, lo, hi))
+    C = _u8(C)
+    if A.size != int((rows ** 2).sum()) or b.size != tot:
+        raise ValueError("packed arrays do not match the sizes")
+    given = [v is not None for v in (C, lo, hi)]
+    if any(given) and not all(given):
+        raise ValueError("C, lo and hi come together (or all None: every row an equality)")
+    if all(given) and any(v.size != tot for v in (C, lo, hi)):
+        raise ValueError("packed arrays do not match the sizes")
+    return ns, A.reshape(-1), b.reshape(-1), C, lo, hi
 
 
 def params(method=GAUSS_SEIDEL, max_iters=500, tol=1e-9, cfm=0.0, omega=1.5, check_every=1):
@@ -266,6 +301,33 @@ class Context:
             args = (_p(c8), _p(l8), _p(h8))
         self.check(load().egs_dense_iterate(self.h, C.c_int32(n), _p(A), _p(b), args[0], args[1], args[2], C.byref(prm), _p(x), C.byref(st)))
         return x, st
+
+    def dense_iterate_batch_packed(self, ns, A, b, prm, C=None, lo=None, hi=None, history=False):
+        """egs_dense_iterate_batch on packed arrays (see lcp_batch_offsets): x (packed), iterations [count], residual
+        [count] and, with history=True, the residual after every sweep, [count][max_iters + 1] (NaN beyond iterations)."""
+        ns, A, b, c8, lo, hi = check_dense_iterate_batch(ns, A, b, C, lo, hi)
+        cnt = len(ns)
+        x = np.zeros(int(np.maximum(ns, 0).sum())); it = np.zeros(cnt, np.int32); res = np.zeros(cnt)
+        hist = np.zeros((cnt, max(int(prm.max_iters), 0) + 1)) if history else None
+        self.check(load().egs_dense_iterate_batch(self.h, _ct.c_int32(cnt), _p(ns), _p(A), _p(b), _p(c8), _p(lo), _p(hi), _ct.byref(prm),
+                                                  _p(x), _p(it), _p(res), _p(hist)))
+        return (x, it, res, hist) if history else (x, it, res)
+
+    def dense_iterate_batch(self, As, bs, prm, Cs=None, los=None, his=None, history=False):
+        """sparse::{Jacobi,GaussSeidel,SOR}Iteration(A, b[, C, x_lo, x_hi]) on `len(As)` independent systems in one call:
+        lists x, iterations, residual[, history] -- problem k's entries are those of dense_iterate on it."""
+        given = [v is not None for v in (Cs, los, his)]
+        if any(given) and not all(given):
+            raise ValueError("Cs, los and his come together (or all None: every row an equality)")
+        ns, A, b, _, _ = pack_lcp_batch(As, bs, [], [])
+        Cp = lo = hi = None
+        if all(given):
+            Cp = pack_batch_vectors(ns, Cs, np.uint8, "C")
+            lo, hi = pack_batch_vectors(ns, los, what="lo"), pack_batch_vectors(ns, his, what="hi")
+        out = self.dense_iterate_batch_packed(ns, A, b, prm, Cp, lo, hi, history)
+        xl, = unpack_lcp_batch(ns, None, out[0])
+        res = (xl, [int(v) for v in out[1]], [float(v) for v in out[2]])
+        return res + ([out[3][k] for k in range(len(ns))],) if history else res
 
     def dense_condition(self, A):
         """GetConditionNumber of a symmetric positive definite matrix (utils.cc:256-261) on the device: (estimate, pivot bound)."""

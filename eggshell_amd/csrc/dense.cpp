@@ -102,6 +102,38 @@ egs_status egs_dense_iterate(egs_context *ctx, int32_t N, const double *A, const
   });
 }
 
+egs_status egs_dense_iterate_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A, const double *b, const uint8_t *C,
+                                   const double *lo, const double *hi, const egs_solve_params *params, double *x, int32_t *iterations,
+                                   double *residual, double *residual_history) {
+  if (!ctx) return EGS_ERR_INVALID;
+  if (egs_status st = validate_params(ctx, params)) return st;
+  if (count < 0) return fail(ctx, EGS_ERR_INVALID, "dense iteration batch: count < 0");
+  if (count == 0) return EGS_OK;
+  if (!n) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  int64_t rows = 0;
+  for (int k = 0; k < count; ++k) {
+    if (n[k] < 0 || n[k] > 1024) return fail(ctx, EGS_ERR_INVALID, "dense iteration batch: 0 <= n <= 1024, problem " + std::to_string(k));
+    rows += n[k];
+  }
+  if (rows > 0 && (!A || !b || !x)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  if (rows > 0 && (C || lo || hi) && !(C && lo && hi)) return fail(ctx, EGS_ERR_INVALID, "C, lo and hi come together (or all NULL: every row an equality)");
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    LaunchHooks hooks;
+    hooks.take = [](void *self, size_t bytes) {
+      egs_context *c = static_cast<egs_context *>(self);
+      HIPCHK(hipStreamSynchronize(c->stream));     // nothing may still be reading the staging memory
+      c->pinned.reset();
+      return c->pinned.take(bytes);
+    };
+    hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
+    hooks.self = ctx;
+    dense_iterate_batch(ctx->stream, hooks, count, n, A, b, C, lo, hi, params->method, params->omega, params->max_iters, params->tol, x,
+                        iterations, residual, residual_history);
+    return EGS_OK;
+  });
+}
+
 egs_status egs_dense_condition(egs_context *ctx, int32_t N, const double *A, double *estimate, double *pivot_bound) {
   if (!ctx) return EGS_ERR_INVALID;
   if (N < 0 || !estimate || (N > 0 && !A)) return fail(ctx, EGS_ERR_INVALID, "NULL array");

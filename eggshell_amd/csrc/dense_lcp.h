@@ -95,4 +95,17 @@ void dense_iterate(hipStream_t stream, int n, const double *A, const double *b, 
                    const double *hi, int method, double omega, int max_iters, double tol, double *x, int *iterations,
                    double *residual);
 
+// `count` such systems in one pipeline (dense_iter.hip): packed as the LCP batches, problem k's matrix at A + sum_{j<k}
+// n_j^2 and its vectors at sum_{j<k} n_j; C, lo and hi all NULL = every row an equality.  Problems of up to
+// kDantzigMaxRows rows go to one launch (a wavefront each, the matrix in LDS), larger ones (up to 1024 rows) to a second
+// (dense_iterate's workgroup each); n_k = 0 is allowed.  One upload, one read-back and one synchronisation through
+// page-locked memory that `hooks.take` hands out; hooks.mark brackets the launches.  iterations / residual [count] are
+// what dense_iterate reports for each problem alone; history (may be NULL) is [count][max_iters + 1]: entry s = the
+// error after sweep s (entry 0: of x0 = b), NaN beyond the problem's sweep count.  Throws std::invalid_argument, before
+// anything is launched or written, for a size outside 0..1024, a method or omega dense_iterate refuses, max_iters < 0,
+// or a zero on a diagonal (the message names the first such problem).
+void dense_iterate_batch(hipStream_t stream, const LaunchHooks &hooks, int count, const int32_t *n, const double *A, const double *b,
+                         const uint8_t *C, const double *lo, const double *hi, int method, double omega, int max_iters, double tol,
+                         double *x, int32_t *iterations, double *residual, double *history);
+
 }  // namespace egs

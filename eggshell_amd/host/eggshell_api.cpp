@@ -240,6 +240,78 @@ VectorXd sparse::SORIteration(const MatrixXd &A, const VectorXd &b, const ArrayX
   return IterateDense(A, b, &C, &lo, &hi, EGS_SOR);
 }
 
+// ---- ... and on many explicit matrices in one library call (egs_dense_iterate_batch) -------------
+namespace {
+std::vector<VectorXd> IterateDenseBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> *C,
+                                        const std::vector<VectorXd> *x_lo, const std::vector<VectorXd> *x_hi, int method) {
+  const size_t count = A.size();
+  if (b.size() != count || (C && (C->size() != count || x_lo->size() != count || x_hi->size() != count)))
+    throw egs::Error(EGS_ERR_INVALID, "IterationBatch: one A, b (and C, x_lo, x_hi) per problem");
+  std::vector<int32_t> n(count);
+  size_t rows = 0, entries = 0;
+  for (size_t k = 0; k < count; ++k) {
+    // CHECK(A.rows() == A.cols() && A.rows() == b.size()) (:77), per problem
+    if (A[k].rows() != A[k].cols() || A[k].rows() != b[k].size()) throw egs::Error(EGS_ERR_INVALID, "BaseIteration: A must be square, b of its size");
+    if (C && ((*C)[k].size() != b[k].size() || (*x_lo)[k].size() != b[k].size() || (*x_hi)[k].size() != b[k].size()))
+      throw egs::Error(EGS_ERR_INVALID, "BaseIteration: C, x_lo, x_hi of b's size");
+    n[k] = b[k].size();
+    rows += (size_t)n[k]; entries += (size_t)n[k] * n[k];
+  }
+  std::vector<double> pA(entries), pb(rows), plo(C ? rows : 0), phi(C ? rows : 0), px(rows);
+  std::vector<uint8_t> pC(C ? rows : 0);
+  size_t at = 0, vt = 0;
+  for (size_t k = 0; k < count; ++k) {
+    const size_t nk = (size_t)n[k];
+    std::copy(A[k].data(), A[k].data() + nk * nk, pA.begin() + at);
+    std::copy(b[k].data(), b[k].data() + nk, pb.begin() + vt);
+    if (C) {
+      std::copy((*C)[k].data(), (*C)[k].data() + nk, pC.begin() + vt);
+      std::copy((*x_lo)[k].data(), (*x_lo)[k].data() + nk, plo.begin() + vt);
+      std::copy((*x_hi)[k].data(), (*x_hi)[k].data() + nk, phi.begin() + vt);
+    }
+    at += nk * nk; vt += nk;
+  }
+  egs_solve_params prm;
+  egs_default_params(&prm);                       // omega 1.5, 500 sweeps, tol 1e-9: sparse_iterations.cc:15-19, constants.h:5
+  prm.method = method;
+  std::vector<int32_t> its(count);
+  std::vector<double> res(count);
+  egs_status rc = egs_dense_iterate_batch(egs::DefaultContext(), (int32_t)count, n.data(), pA.data(), pb.data(), C ? pC.data() : nullptr,
+                                          C ? plo.data() : nullptr, C ? phi.data() : nullptr, &prm, px.data(), its.data(), res.data(), nullptr);
+  if (rc != EGS_OK) throw egs::Error(rc, egs_last_error(egs::DefaultContext()));
+  std::vector<VectorXd> x(count);
+  vt = 0;
+  for (size_t k = 0; k < count; ++k) {
+    x[k].resize(n[k]);
+    std::copy(px.begin() + vt, px.begin() + vt + n[k], x[k].data());
+    vt += (size_t)n[k];
+  }
+  if (count) g_last = sparse::LastSolve{its[count - 1], res[count - 1], 0, 0, 0};   // of the last problem
+  return x;
+}
+}  // namespace
+std::vector<VectorXd> sparse::JacobiIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b) {
+  return IterateDenseBatch(A, b, nullptr, nullptr, nullptr, EGS_JACOBI);
+}
+std::vector<VectorXd> sparse::JacobiIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                                   const std::vector<VectorXd> &lo, const std::vector<VectorXd> &hi) {
+  return IterateDenseBatch(A, b, &C, &lo, &hi, EGS_JACOBI);
+}
+std::vector<VectorXd> sparse::GaussSeidelIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b) {
+  return IterateDenseBatch(A, b, nullptr, nullptr, nullptr, EGS_GAUSS_SEIDEL);
+}
+std::vector<VectorXd> sparse::GaussSeidelIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                                        const std::vector<VectorXd> &lo, const std::vector<VectorXd> &hi) {
+  return IterateDenseBatch(A, b, &C, &lo, &hi, EGS_GAUSS_SEIDEL);
+}
+std::vector<VectorXd> sparse::SORIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b) {
+  return IterateDenseBatch(A, b, nullptr, nullptr, nullptr, EGS_SOR);
+}
+std::vector<VectorXd> sparse::SORIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                                const std::vector<VectorXd> &lo, const std::vector<VectorXd> &hi) {
+  return IterateDenseBatch(A, b, &C, &lo, &hi, EGS_SOR);
+}
+
 // ---- sparse_iterations_utils.cc:427-695 ------------------------------------------
 namespace {
 VectorXd Product(const ConstraintsList &constraints, const MatrixXd &M_inverse, const VectorXd &x, int32_t parts,

@@ -150,6 +150,19 @@ VectorXd GaussSeidelIteration(const MatrixXd &A, const VectorXd &b);
 VectorXd GaussSeidelIteration(const MatrixXd &A, const VectorXd &b, const ArrayXb &C, const VectorXd &x_lo, const VectorXd &x_hi);
 VectorXd SORIteration(const MatrixXd &A, const VectorXd &b);
 VectorXd SORIteration(const MatrixXd &A, const VectorXd &b, const ArrayXb &C, const VectorXd &x_lo, const VectorXd &x_hi);
+// The same on many independent systems in one library call (egs_dense_iterate_batch: one upload, a workgroup per
+// system, one read-back), named like lcp::SolveLCPBatch: x[k] is, bit for bit, what the call above returns for A[k],
+// b[k] (and C[k], x_lo[k], x_hi[k]).  Sizes may differ from system to system (0..1024 rows); GetLastSolve() reports the
+// last system's count and residual.
+std::vector<VectorXd> JacobiIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b);
+std::vector<VectorXd> JacobiIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                           const std::vector<VectorXd> &x_lo, const std::vector<VectorXd> &x_hi);
+std::vector<VectorXd> GaussSeidelIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b);
+std::vector<VectorXd> GaussSeidelIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                                const std::vector<VectorXd> &x_lo, const std::vector<VectorXd> &x_hi);
+std::vector<VectorXd> SORIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b);
+std::vector<VectorXd> SORIterationBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b, const std::vector<ArrayXb> &C,
+                                        const std::vector<VectorXd> &x_lo, const std::vector<VectorXd> &x_hi);
 // matrix-free, on an ensemble's constraints (sparse_iterations.h:26-34)
 VectorXd JacobiIteration(const ConstraintsList &constraints, const MatrixXd &M_inverse, const VectorXd &rhs,
                          double cfm = 0.0);

@@ -284,6 +284,26 @@ egs_status egs_dense_iterate(egs_context *ctx, int32_t N, const double *A, const
                              const double *lo, const double *hi, const egs_solve_params *params, double *x,
                              egs_solve_stats *stats);
 
+/* The same on `count` independent systems in one device pipeline: the iterative twin of egs_box_lcp_batch, for the
+ * sizes the reference's own study of the three iterations runs them on (3..50 rows, sparse_iterations.cc:355-513)
+ * and a contact patch hands a projected iteration (8 contacts x 3 = 24 rows), where one call of egs_dense_iterate is
+ * all launch and copy.  Packing as egs_box_lcp_batch: problem k has n[k] rows (0 <= n[k] <= 1024; 0 gives
+ * iterations 0, residual 0, sparse_iterations.cc:79-81), its row-major matrix (general, non-zero diagonal) at
+ * A + sum_{j<k} n[j]^2, its vectors (b, C, lo, hi, x) at sum_{j<k} n[j]; C / lo / hi all NULL = every row of every
+ * problem an equality (the 2-argument form).  params: method, omega, max_iters, tol, shared by the batch, as for
+ * egs_dense_iterate.  One upload, at most two launches (problems of up to 96 rows: a wavefront each with the matrix
+ * in LDS; larger ones: the single call's workgroup each), one read-back, one synchronisation; no workgroup waits on
+ * another.  iterations[k] / residual[k] (either may be NULL) and x are, bit for bit, what egs_dense_iterate reports
+ * for problem k alone.  residual_history (may be NULL): [count][max_iters + 1], the convergence curve the reference
+ * computes and only prints in a commented-out line (:134-137): entry 0 = the error of x0 = b (:124-126), entry s =
+ * the error after sweep s (:131-133), NaN beyond iterations[k].  count = 0 is EGS_OK.  EGS_ERR_INVALID, with nothing
+ * launched and no output written: count < 0, a size outside 0..1024, a method or omega egs_dense_iterate refuses,
+ * max_iters < 0, a zero on some diagonal (egs_last_error names the first such problem). */
+egs_status egs_dense_iterate_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A, const double *b,
+                                   const uint8_t *C, const double *lo, const double *hi,
+                                   const egs_solve_params *params, double *x, int32_t *iterations, double *residual,
+                                   double *residual_history);
+
 /* ---- the dense front half of Ensemble::ComputeVDot (ensembles.cc:498-538) on
  *      the device, for the sizes the reference's dense solver is meant for
  *      (Chain, Cairn): the problem's blocks (assemble or set_blocks) -> dense
