@@ -40,7 +40,7 @@ EXPORTS = [
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
     "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
-    "egs_mixed_constraints_solve_limits", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
+    "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
     "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
 ]
@@ -76,6 +76,10 @@ def load():
                 LIB_PATH + " is missing: run __graft_entry__.build() (there is no CPU fallback)")
         _lib = C.CDLL(LIB_PATH)
         _lib.egs_last_error.restype = C.c_char_p
+        if hasattr(_lib, "egs_mixed_constraints_solve_batch"):      # (a timing tool may load an older build with --lib)
+            # ctx, count, n, A, b, C, lo, hi, use_bounds, max_pivots, x, w, ok, pivots
+            _lib.egs_mixed_constraints_solve_batch.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 2 + [C.c_void_p] * 4
+            _lib.egs_mixed_constraints_solve_batch.restype = C.c_int
     return _lib
 
 
@@ -168,6 +172,25 @@ def check_dense_iterate_batch(ns, A, b, C=None, lo=None, hi=None):
     if all(given) and any(v.size != tot for v in (C, lo, hi)):
         raise ValueError("packed arrays do not match the sizes")
     return ns, A.reshape(-1), b.reshape(-1), C, lo, hi
+
+
+def check_mixed_batch(ns, A, b, C, lo, hi):
+    """The size checks of Context.mixed_constraints_solve_batch_packed (host only): the packed arrays must hold exactly
+    what the sizes ask for.  Returns ns, A, b, C, lo, hi as the C ABI takes them.  (A negative size is the library's to
+    refuse; it counts as no rows here.)"""
+    ns = np.asarray(ns)
+    if ns.ndim != 1 or (ns.size and not np.issubdtype(ns.dtype, np.integer)):
+        raise ValueError("ns: a list of integer sizes")
+    ns = np.ascontiguousarray(ns, dtype=np.int32)
+    rows = np.maximum(ns, 0).astype(np.int64)
+    tot = int(rows.sum())
+    if any(v is None for v in (A, b, C, lo, hi)):
+        raise ValueError("A, b, C, lo and hi are all required")
+    A, b, lo, hi = map(_f64, (A, b, lo, hi))
+    C = _u8(C)
+    if A.size != int((rows ** 2).sum()) or any(v.size != tot for v in (b, C, lo, hi)):
+        raise ValueError("packed arrays do not match the sizes")
+    return ns, A.reshape(-1), b.reshape(-1), C.reshape(-1), lo.reshape(-1), hi.reshape(-1)
 
 
 def params(method=GAUSS_SEIDEL, max_iters=500, tol=1e-9, cfm=0.0, omega=1.5, check_every=1):
@@ -287,6 +310,27 @@ class Context:
             self.check(st)
         return bool(ok.value), x, w, piv.value
 
+
+    def mixed_constraints_solve_batch_packed(self, ns, A, b, C, lo, hi, use_bounds=0, max_pivots=0):
+        """egs_mixed_constraints_solve_batch on packed arrays (see lcp_batch_offsets): ok [count] (bool), x, w (packed),
+        pivots [count].  A failed problem shows in ok[k], not as an exception."""
+        ns, A, b, c8, lo, hi = check_mixed_batch(ns, A, b, C, lo, hi)
+        cnt = len(ns)
+        tot = int(np.maximum(ns, 0).sum())
+        x = np.zeros(tot); w = np.zeros(tot); ok = np.zeros(cnt, np.int32); piv = np.zeros(cnt, np.int32)
+        self.check(load().egs_mixed_constraints_solve_batch(self.h, cnt, _p(ns), _p(A), _p(b), _p(c8), _p(lo), _p(hi), int(use_bounds),
+                                                            int(max_pivots), _p(x), _p(w), _p(ok), _p(piv)))
+        return ok.astype(bool), x, w, piv
+
+    def mixed_constraints_solve_batch(self, As, bs, Cs, los, his, use_bounds=0, max_pivots=0):
+        """Lcp::MixedConstraintsSolver(A, b, C, x_lo, x_hi, x, w) on `len(As)` independent problems in one call: lists ok, x,
+        w, pivots -- problem k's entries are those of mixed_constraints_solve on it."""
+        ns, A, b, _, _ = pack_lcp_batch(As, bs, [], [])
+        Cp = pack_batch_vectors(ns, Cs, np.uint8, "C")
+        lo, hi = pack_batch_vectors(ns, los, what="lo"), pack_batch_vectors(ns, his, what="hi")
+        ok, x, w, piv = self.mixed_constraints_solve_batch_packed(ns, A, b, Cp, lo, hi, use_bounds, max_pivots)
+        xl, wl = unpack_lcp_batch(ns, None, x, w)
+        return [bool(v) for v in ok], xl, wl, [int(v) for v in piv]
 
     def dense_iterate(self, A, b, prm, Ceq=None, lo=None, hi=None):
         """sparse::{Jacobi,GaussSeidel,SOR}Iteration(A, b[, C, x_lo, x_hi]) on an explicit matrix: x, stats."""

@@ -2,8 +2,10 @@
 // (egs_problem_dense_*, egs_problem_step_dense), and the stateless solvers on host matrices (egs_dense_*,
 // egs_mixed_constraints_*, egs_box_lcp_*) over dense_lcp.h.
 #include "dense_lcp.h"
+#include "dense_world.h"
 #include "problem.h"
 
+#include <cmath>
 #include <limits>
 
 using namespace egs;
@@ -215,6 +217,71 @@ egs_status egs_mixed_constraints_solve_limits(egs_context *ctx, int32_t N, const
     const bool good = dense_mixed_constraints(ctx->dense, N, A, b, C, lo, hi, (use_bounds & 1) != 0,
                                               (use_bounds & 2) != 0, x, w, &piv, &msg, max_pivots, max_seconds);
     return lcp_result(ctx, good, piv, msg, "MixedConstraintsSolver did not reach a solution", ok, pivots);
+  });
+}
+
+egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A, const double *b,
+                                             const uint8_t *C, const double *lo, const double *hi, int32_t use_bounds, int32_t max_pivots,
+                                             double *x, double *w, int32_t *ok, int32_t *pivots) {
+  if (!ctx) return EGS_ERR_INVALID;
+  // everything is checked before anything is launched or written
+  if (count < 0) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: count < 0");
+  if (use_bounds < 0 || use_bounds > 3) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: use_bounds is a mask of bits 0 and 1");
+  if (max_pivots < 0) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: max_pivots < 0");
+  if (count == 0) return EGS_OK;
+  if (!n || !ok) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  std::vector<int64_t> a_off(count), v_off(count);
+  std::vector<int32_t> fused, single;
+  const bool block_pivoting = (use_bounds & 2) != 0;
+  int64_t at = 0, vt = 0;
+  for (int k = 0; k < count; ++k) {
+    const int nk = n[k];
+    if (nk < 0) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: n < 0, problem " + std::to_string(k));
+    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: n too large, problem " + std::to_string(k));
+    a_off[k] = at; v_off[k] = vt;
+    if (nk > 0) (nk <= kFusedDenseMax && !block_pivoting ? fused : single).push_back(k);
+    at += (int64_t)nk * nk; vt += nk;
+  }
+  if (vt > 0 && (!A || !b || !C || !lo || !hi || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  for (int k = 0; k < count; ++k) {     // the rule of the single entry's symmetry check (dense_lcp.hip)
+    const int nk = n[k];
+    const double *Ak = A + a_off[k];
+    double amax = 0.0, asym = 0.0;
+    for (int i = 1; i < nk; ++i)
+      for (int j = 0; j < i; ++j) {
+        const double v = Ak[(size_t)i * nk + j];
+        amax = std::fmax(amax, std::fabs(v));
+        asym = std::fmax(asym, std::fabs(v - Ak[(size_t)j * nk + i]));
+      }
+    if (asym > 1e-10 * std::max(amax, 1e-300))
+      return fail(ctx, EGS_ERR_INVALID, "A must be symmetric (J M^-1 J^T + cfm I is): problem " + std::to_string(k));
+  }
+  for (int k = 0; k < count; ++k) {
+    ok[k] = n[k] == 0 ? 1 : 0;
+    if (pivots) pivots[k] = 0;
+  }
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!fused.empty()) {
+      LaunchHooks hooks;
+      hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
+      hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
+      hooks.self = ctx;
+      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
+      ctx->pinned.reset();
+      mixed_constraints_fused(ctx->dense, hooks, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo, hi,
+                              (use_bounds & 1) != 0, max_pivots, x, w, ok, pivots);
+    }
+    // beyond the fused size, or with block pivoting: the single-problem path, one problem after another
+    for (const int k : single) {
+      int piv = 0;
+      const bool good = dense_mixed_constraints(ctx->dense, n[k], A + a_off[k], b + v_off[k], C + v_off[k], lo + v_off[k], hi + v_off[k],
+                                                (use_bounds & 1) != 0, block_pivoting, x + v_off[k], w + v_off[k], &piv, nullptr, max_pivots,
+                                                0.0);
+      ok[k] = good ? 1 : 0;
+      if (pivots) pivots[k] = piv;
+    }
+    return EGS_OK;     // per-problem outcome in ok[]
   });
 }
 

@@ -88,6 +88,19 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
                          const int32_t *nub, bool q6, int max_steps, double max_seconds, double *x, double *w, int32_t *perm,
                          int32_t *ok, int32_t *nub_out, int32_t *pivots);
 
+// `count` Lcp::MixedConstraintsSolver problems of at most kFusedDenseMax (112, dense_world.h) rows each in ONE pipeline
+// (mixed_batch.hip): a workgroup per problem runs the partition, the Cholesky of A_ee, the Schur complement, the
+// reference's Murty loop and the back-substitution of dense_world_fused_kernel on the caller's packed matrix.  sel[f] =
+// the problem's number in the caller's packed arrays (n, ok, pivots indexed by it; its full row-major matrix at A +
+// a_off[sel[f]], its vectors at v_off[sel[f]]); A is read only.  One page-locked block from `hooks.take`, one device
+// allocation, one upload, at most one launch per size class (32 / 64 / 112 rows), one read-back, one synchronisation.
+// use_bounds = false is the reference (quirk Q3); max_pivots > 0 tightens its cap min(1000, 2^n_i).  ok[k] = the
+// reference's bool, x / w of a failed problem are zero.  The matrices must already have passed the symmetry check.
+void mixed_constraints_fused(DenseWorkspace &ws, const LaunchHooks &hooks, int count, const int32_t *sel, const int32_t *n,
+                             const int64_t *a_off, const int64_t *v_off, const double *A, const double *b, const uint8_t *C,
+                             const double *lo, const double *hi, bool use_bounds, int max_pivots, double *x, double *w, int32_t *ok,
+                             int32_t *pivots);
+
 // sparse::{Jacobi,GaussSeidel,SOR}Iteration on an explicit dense matrix (sparse_iterations.cc:72-144; dense_iter.hip):
 // A row-major n x n (n <= 1024), C / lo / hi as the reference's 5-argument overloads (all-equality for the 2-argument
 // ones), method 0 / 1 / 2, omega = 1.5 in the reference (:15), max_iters = 500 (:19), tol = 1e-9 (constants.h:5).

@@ -9,12 +9,11 @@
 #include <cstdint>
 
 #include "dense_world.h"
+#include "mixed_solve_device.h"
 
 namespace egs {
 
 namespace {
-
-__device__ __forceinline__ int dtri(int r, int c) { return r * (r + 1) / 2 + c; }   // c <= r
 
 // Kernel 1: pair (i, j) of ensemble blockIdx.y's constraints -> the 3x3 block of A_e at (3i, 3j), the arithmetic of
 // dense_system_kernel (kernels.hip) on the world's blocks.  The lane of pair (i, 0) also gathers constraint i's rows.
@@ -80,18 +79,12 @@ __global__ void __launch_bounds__(256) dense_world_system_kernel(DenseWorldArgs 
 template <int MAXN, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs a, const int32_t *list) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double *T = sm;                                   // packed lower triangle: Cholesky factors of A, A_ee, A(S,S)
-  double *x = T + MAXN * (MAXN + 1) / 2;
-  double *w = x + MAXN, *r = w + MAXN, *Cv = r + MAXN, *lo = Cv + MAXN;
-  double *hi = lo + MAXN, *b = hi + MAXN, *y = b + MAXN, *bx = y + MAXN;
-  double *bw = bx + MAXN, *y2 = bw + MAXN;
-  __shared__ int idx[MAXN], idxE[MAXN], idxI[MAXN];
-  __shared__ unsigned char S[MAXN];
-  __shared__ int s_first, s_oob, s_wbad, s_ns, s_state, s_fail, s_ne, s_ni, s_badb;
-  __shared__ double s_resid2, s_good, s_best, s_diag[2];
+  const MixedSolveLds L(sm, MAXN);                  // the packed triangle (Cholesky factors of A, A_ee, A(S,S)) and the vectors
+  double *T = L.T, *x = L.x, *w = L.w, *r = L.r, *y = L.y, *y2 = L.y2;
+  __shared__ MixedSolveShared<MAXN> sh;
+  __shared__ double s_diag[2];
   __shared__ double s_red[BLOCK / 64][6];
   const int tid = threadIdx.x;
-  const int NONE = 0x7fffffff;
   const int e = list[blockIdx.x];
   const int c0 = a.cstart[e];
   const int N = 3 * (a.cstart[e + 1] - c0);
@@ -116,57 +109,16 @@ __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs
       __syncthreads();
     }
   };
-  // right-looking Cholesky of the packed n x n triangle in T, in place; yv (may be NULL) rides along as an extra
-  // row, so L z = yv is solved by the same column steps.  s_fail = 1 on a non-positive pivot.
-  auto cholesky = [&](int n, double *yv) {
-    for (int j = 0; j < n; ++j) {
-      const double d = T[dtri(j, j)];
-      if (!(d > 0.0)) { if (tid == 0) s_fail = 1; }
-      const double rt = sqrt(d > 0.0 ? d : 1.0);
-      for (int i = j + 1 + tid; i < n; i += BLOCK) T[dtri(i, j)] /= rt;
-      if (yv && tid == BLOCK - 1) yv[j] /= rt;
-      __syncthreads();
-      if (tid == 0) T[dtri(j, j)] = rt;
-      const int tx = tid & 15, ty = tid >> 4;
-      for (int i = j + 1 + ty; i < n; i += BLOCK / 16) {
-        const double lij = T[dtri(i, j)];
-        for (int k = j + 1 + tx; k <= i; k += 16) T[dtri(i, k)] = __builtin_fma(-lij, T[dtri(k, j)], T[dtri(i, k)]);
-      }
-      if (yv) {
-        const double yj = yv[j];
-        for (int i = j + 1 + tid; i < n; i += BLOCK) yv[i] = __builtin_fma(-T[dtri(i, j)], yj, yv[i]);
-      }
-      __syncthreads();
-    }
-  };
-  // L^T v = z for the factor in T, in ONE wavefront (no workgroup barrier per step)
-  auto back_solve = [&](int n, double *yv) {
-    if (tid < 64) {
-      for (int j = n - 1; j >= 0; --j) {
-        if (tid == (j & 63)) yv[j] = yv[j] / T[dtri(j, j)];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double yj = yv[j];
-        for (int i = tid; i < j; i += 64) yv[i] = __builtin_fma(-T[dtri(j, i)], yj, yv[i]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-    }
-    __syncthreads();
-  };
-
   // ---- CheckMatrixCondition (ensembles.cc:513-521): cond_2(A) < 1e7 ?  A is positive definite here or singular.
-  if (tid == 0) { s_fail = 0; s_state = 0; s_badb = 0; }
+  if (tid == 0) sh.fail = 0;
   for (int q = tid; q < N * N; q += BLOCK) {
     const int rr = q / N, cc = q - rr * N;
     if (cc <= rr) T[dtri(rr, cc)] = A[q];
   }
   __syncthreads();
-  cholesky(N, nullptr);
+  packed_cholesky<BLOCK>(T, N, nullptr, &sh.fail);
   double condition = INFINITY;
-  if (!s_fail) {
+  if (!sh.fail) {
     if (tid == 0) {
       double mx = 0.0, mn = 1e300;
       for (int k = 0; k < N; ++k) { const double d = T[dtri(k, k)]; mx = d > mx ? d : mx; mn = d < mn ? d : mn; }
@@ -232,207 +184,13 @@ __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs
   const double cfm = condition < 1e7 ? 0.0 : a.cfm_coeff;
   if (cfm != 0.0)
     for (int i = tid; i < N; i += BLOCK) A[(size_t)i * N + i] += cfm;
-  __syncthreads();   // (every thread has read s_fail and A before they change)
+  __syncthreads();   // (every thread has read sh.fail and A before they change)
 
-  // ---- Lcp::MixedConstraintsSolver (lcp.cc:276-336): partition, Schur complement over the equality rows
-  if (tid == 0) {
-    int ne = 0, ni = 0;
-    for (int i = 0; i < N; ++i) {
-      if (vc[i] != 0.0) idxE[ne++] = i;
-      else idxI[ni++] = i;
-    }
-    s_ne = ne; s_ni = ni; s_fail = 0;
-  }
-  __syncthreads();
-  const int ne = s_ne, ni = s_ni, ni1 = ni + 1;
-  if (ne > 0) {
-    for (int q = tid; q < ne * ne; q += BLOCK) {
-      const int rr = q / ne, cc = q - rr * ne;
-      if (cc <= rr) T[dtri(rr, cc)] = A[(size_t)idxE[rr] * N + idxE[cc]];
-    }
-    // Z = [A_ei | b_e], ne x (ni + 1)
-    for (int q = tid; q < ne * ni1; q += BLOCK) {
-      const int rr = q / ni1, cc = q - rr * ni1;
-      Z[q] = cc < ni ? A[(size_t)idxE[rr] * N + idxI[cc]] : vb[idxE[rr]];
-    }
-    __syncthreads();
-    cholesky(ne, nullptr);
-    // Z = L^-1 Z (forward substitution on all columns at once)
-    for (int j = 0; j < ne; ++j) {
-      const double d = T[dtri(j, j)];
-      for (int c = tid; c < ni1; c += BLOCK) Z[(size_t)j * ni1 + c] /= d;
-      __syncthreads();
-      for (int q = tid; q < (ne - j - 1) * ni1; q += BLOCK) {
-        const int i = j + 1 + q / ni1, c = q % ni1;
-        Z[(size_t)i * ni1 + c] = __builtin_fma(-T[dtri(i, j)], Z[(size_t)j * ni1 + c], Z[(size_t)i * ni1 + c]);
-      }
-      __syncthreads();
-    }
-  }
-  // lhs = A_ii - A_ie A_ee^-1 A_ei, its rhs = b_i - A_ie A_ee^-1 b_e   (lcp.cc:293-294)
-  for (int q = tid; q < ni * ni1; q += BLOCK) {
-    const int rr = q / ni1, cc = q - rr * ni1;
-    double s = 0.0;
-    for (int k = 0; k < ne; ++k) s = __builtin_fma(Z[(size_t)k * ni1 + rr], Z[(size_t)k * ni1 + cc], s);
-    if (cc < ni) Lh[(size_t)rr * ni + cc] = A[(size_t)idxI[rr] * N + idxI[cc]] - s;
-    else b[rr] = vb[idxI[rr]] - s;
-  }
-  // the inequality rows' bounds: the reference calls the no-bounds overload (lcp.cc:298, quirk Q3)
-  const bool box_fix = a.use_bounds != 0;
-  for (int k = tid; k < ni; k += BLOCK) {
-    lo[k] = box_fix ? vlo[idxI[k]] : 0.0;
-    hi[k] = box_fix ? vhi[idxI[k]] : INFINITY;
-    if (!(lo[k] < hi[k]) || !(lo[k] <= 0) || !(box_fix ? hi[k] >= 0 : hi[k] > 0)) s_badb = 1;   // lcp.cc:161-164
-  }
-  __syncthreads();
-  const bool schur_failed = s_fail != 0;
-  int solved = (!schur_failed && !s_badb) ? 1 : 0;
-  int pivots = 0;
-
-  // ---- MurtyPrincipalPivot on lhs (lcp.cc:157-274), the loop of murty_small_kernel
-  if (solved && ni > 0) {
-    const int n = ni;
-    const double *M = Lh;
-    const double p2 = pow(2.0, n);
-    const int max_iterations = p2 > 1000 ? 1000 : (int)p2;   // lcp.cc:168
-    for (int i = tid; i < n; i += BLOCK) {
-      S[i] = 1; Cv[i] = lo[i];
-      x[i] = 0.0; w[i] = -b[i]; r[i] = -b[i];   // lcp.cc:184-185
-      bx[i] = 0.0; bw[i] = -b[i];
-    }
-    __syncthreads();
-    auto check = [&]() {     // CheckMurtySolution (lcp.cc:20-103) + goodness (lcp.cc:107-113)
-      if (tid == 0) { s_first = NONE; s_oob = 0; s_wbad = 0; }
-      __syncthreads();
-      for (int i = tid; i < n; i += BLOCK) {
-        const double xi = x[i], wi = w[i];
-        bool off;
-        if (S[i]) off = (xi < lo[i]) || (xi > hi[i]);
-        else off = (Cv[i] == lo[i] && wi < 0) || (Cv[i] == hi[i] && wi > 0);
-        if (off) atomicMin(&s_first, i);
-        if (xi < lo[i] || xi > hi[i]) s_oob = 1;
-        if ((xi == lo[i] && wi < 0) || (xi == hi[i] && wi > 0)) s_wbad = 1;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double res2 = 0.0, good = 0.0;
-        for (int i = 0; i < n; ++i) {
-          const double d = r[i] - w[i];
-          res2 += d * d;
-          if (!(x[i] > 0)) good += x[i];
-          if (!(w[i] > 0)) good += w[i];
-        }
-        s_resid2 = res2; s_good = good;
-      }
-      __syncthreads();
-    };
-    auto is_solution = [&](double tol) { return s_first == NONE && !s_oob && !s_wbad && sqrt(s_resid2) <= tol; };
-    // r = M x - b: two threads per row (even / odd columns), four independent chains each
-    auto residual_vector = [&]() {
-      const int half = tid & 1;
-      for (int i = tid >> 1; i < n; i += BLOCK / 2) {
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-        const double *row = M + (size_t)i * n;
-        int c = half;
-        for (; c + 6 < n; c += 8) {
-          p0 = __builtin_fma(row[c], x[c], p0);
-          p1 = __builtin_fma(row[c + 2], x[c + 2], p1);
-          p2 = __builtin_fma(row[c + 4], x[c + 4], p2);
-          p3 = __builtin_fma(row[c + 6], x[c + 6], p3);
-        }
-        for (; c < n; c += 2) p0 = __builtin_fma(row[c], x[c], p0);
-        const double part = (p0 + p1) + (p2 + p3);
-        if (half) y2[i] = part;
-        else r[i] = part;
-      }
-      __syncthreads();
-      for (int i = tid; i < n; i += BLOCK) r[i] = (r[i] + y2[i]) - b[i];
-      __syncthreads();
-    };
-
-    check();
-    if (tid == 0) s_best = s_good;
-    __syncthreads();
-    int iter = 0;
-    bool force = box_fix;
-    while (iter < max_iterations) {
-      if (!force) {
-        if (is_solution(1e-9)) { if (tid == 0) s_state = 1; __syncthreads(); break; }
-        if (tid == 0 && s_first != NONE) {             // lcp.cc:36-62: flip the first offender
-          const int i = s_first;
-          if (S[i]) { S[i] = 0; Cv[i] = (x[i] < lo[i]) ? lo[i] : hi[i]; }
-          else S[i] = 1;
-        }
-        __syncthreads();
-      }
-      force = false;
-      if (tid == 0) {                                  // index list of S
-        int ns = 0;
-        for (int i = 0; i < n; ++i) if (S[i]) idx[ns++] = i;
-        s_ns = ns;
-      }
-      for (int i = tid; i < n; i += BLOCK) x[i] = S[i] ? 0.0 : Cv[i];   // x = x_clamped
-      __syncthreads();
-      const int ns = s_ns;
-      // right-hand side: b(S), minus M(S,!S) x(!S) for the true box problem (lcp.cc:199-216)
-      if (box_fix) {
-        residual_vector();                              // r = M x_clamped - b
-        for (int k = tid; k < ns; k += BLOCK) y[k] = -r[idx[k]];
-      } else {
-        for (int k = tid; k < ns; k += BLOCK) y[k] = b[idx[k]];
-      }
-      for (int q = tid; q < ns * ns; q += BLOCK) {      // gather M(S,S), lower triangle
-        const int rr = q / ns, cc = q - rr * ns;
-        if (cc <= rr) T[dtri(rr, cc)] = M[(size_t)idx[rr] * n + idx[cc]];
-      }
-      __syncthreads();
-      cholesky(ns, y);
-      back_solve(ns, y);
-      for (int k = tid; k < ns; k += BLOCK) x[idx[k]] = y[k];
-      __syncthreads();
-      residual_vector();                               // r = M x - b
-      for (int i = tid; i < n; i += BLOCK) w[i] = S[i] ? 0.0 : r[i];     // lcp.cc:219-223
-      __syncthreads();
-      ++pivots;
-      check();
-      if (s_good > s_best) {                           // lcp.cc:125-137 (uniform: shared value)
-        for (int i = tid; i < n; i += BLOCK) { bx[i] = x[i]; bw[i] = w[i]; }
-        __syncthreads();
-        if (tid == 0) s_best = s_good;
-        __syncthreads();
-      }
-      ++iter;
-      if (s_fail) break;
-    }
-    solved = (s_state == 1);
-    if (!solved && !s_fail) {
-      // capped: the best-seen iterate (reference rule only), re-checked at the looser 1e-8 (lcp.cc:241-246)
-      if (!box_fix) {
-        for (int i = tid; i < n; i += BLOCK) { x[i] = bx[i]; w[i] = bw[i]; }
-        __syncthreads();
-      }
-      residual_vector();
-      check();
-      solved = is_solution(1e-8) ? 1 : 0;
-    }
-  }
-
-  // ---- x_e = A_ee^-1 (b_e - A_ei x_i)   (lcp.cc:317); the factor of A_ee once more (the loop above reused T)
-  if (solved && ne > 0) {
-    for (int q = tid; q < ne * ne; q += BLOCK) {
-      const int rr = q / ne, cc = q - rr * ne;
-      if (cc <= rr) T[dtri(rr, cc)] = A[(size_t)idxE[rr] * N + idxE[cc]];
-    }
-    for (int k = tid; k < ne; k += BLOCK) {
-      double s = 0.0;
-      const double *row = A + (size_t)idxE[k] * N;
-      for (int c = 0; c < ni; ++c) s = __builtin_fma(row[idxI[c]], x[c], s);
-      y2[k] = vb[idxE[k]] - s;
-    }
-    __syncthreads();
-    cholesky(ne, y2);
-    back_solve(ne, y2);
-  }
+  // ---- Lcp::MixedConstraintsSolver (lcp.cc:276-336): the stage mixed_batch_kernel shares (mixed_solve_device.h)
+  mixed_partition(sh, N, [&](int i) { return vc[i] != 0.0; });
+  const MixedSolveResult res = mixed_solve_stage<MAXN, BLOCK>(sh, L, A, N, vb, vlo, vhi, Z, Lh, a.use_bounds, 0);
+  const int ne = sh.ne, ni = sh.ni, solved = res.solved, pivots = res.pivots;
+  const int *idxE = sh.idxE, *idxI = sh.idxI;
   if (solved) {     // lambda in the world's order
     for (int k = tid; k < ne; k += BLOCK) {
       const int row = idxE[k];
@@ -462,7 +220,7 @@ __global__ void scatter_rows_kernel(const int32_t *cons_e, int N, const double *
 
 template <int MAXN, int BLOCK>
 void launch_fused(const DenseWorldArgs &a, const int32_t *list, int count, hipStream_t s) {
-  const size_t lds = (size_t)(MAXN * (MAXN + 1) / 2 + 11 * MAXN) * sizeof(double);
+  const size_t lds = mixed_solve_lds_doubles(MAXN) * sizeof(double);
   hipLaunchKernelGGL((dense_world_fused_kernel<MAXN, BLOCK>), dim3(count), dim3(BLOCK), lds, s, a, list);
 }
 

@@ -371,6 +371,52 @@ bool Lcp::MixedConstraintsSolver(const MatrixXd &A, const VectorXd &b, const Arr
   return ok != 0;
 }
 
+std::vector<bool> Lcp::MixedConstraintsSolverBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b,
+                                                   const std::vector<ArrayXb> &C, const std::vector<VectorXd> &x_lo,
+                                                   const std::vector<VectorXd> &x_hi, std::vector<VectorXd> *x,
+                                                   std::vector<VectorXd> *w) {  // lcp.cc:276-336, per problem
+  const size_t count = A.size();
+  if (!x || !w || b.size() != count || C.size() != count || x_lo.size() != count || x_hi.size() != count)
+    throw egs::Error(EGS_ERR_INVALID, "MixedConstraintsSolverBatch: one A, b, C, x_lo and x_hi per problem");
+  std::vector<int32_t> n(count);
+  size_t rows = 0, entries = 0;
+  for (size_t k = 0; k < count; ++k) {
+    const auto N = b[k].size();
+    if (A[k].rows() != N || A[k].cols() != N || C[k].size() != N || x_lo[k].size() != N || x_hi[k].size() != N)
+      throw egs::Error(EGS_ERR_INVALID, "MixedConstraintsSolverBatch: dimension mismatch");
+    n[k] = (int32_t)N;
+    rows += (size_t)N; entries += (size_t)N * N;
+  }
+  std::vector<double> pA(entries), pb(rows), plo(rows), phi(rows), px(rows), pw(rows);
+  std::vector<uint8_t> pC(rows);
+  size_t at = 0, vt = 0;
+  for (size_t k = 0; k < count; ++k) {
+    const size_t nk = (size_t)n[k];
+    std::copy(A[k].data(), A[k].data() + nk * nk, pA.begin() + at);
+    std::copy(b[k].data(), b[k].data() + nk, pb.begin() + vt);
+    std::copy(C[k].data(), C[k].data() + nk, pC.begin() + vt);
+    std::copy(x_lo[k].data(), x_lo[k].data() + nk, plo.begin() + vt);
+    std::copy(x_hi[k].data(), x_hi[k].data() + nk, phi.begin() + vt);
+    at += nk * nk; vt += nk;
+  }
+  std::vector<int32_t> ok(count), pivots(count);
+  egs::check(egs_mixed_constraints_solve_batch(egs::DefaultContext(), (int32_t)count, n.data(), pA.data(), pb.data(), pC.data(),
+                                               plo.data(), phi.data(), /*use_bounds=*/0, /*max_pivots=*/0, px.data(), pw.data(),
+                                               ok.data(), pivots.data()));
+  x->assign(count, VectorXd());
+  w->assign(count, VectorXd());
+  std::vector<bool> good(count);
+  vt = 0;
+  for (size_t k = 0; k < count; ++k) {
+    (*x)[k].resize(n[k]); (*w)[k].resize(n[k]);
+    std::copy(px.begin() + vt, px.begin() + vt + n[k], (*x)[k].data());
+    std::copy(pw.begin() + vt, pw.begin() + vt + n[k], (*w)[k].data());
+    good[k] = ok[k] != 0;
+    vt += (size_t)n[k];
+  }
+  return good;
+}
+
 // ---- ensembles.cc ----------------------------------------------------------
 Ensemble::Ensemble() {
   egs_default_params(&solver_params);

@@ -199,6 +199,15 @@ LastSolve GetLastSolve();
 namespace Lcp {  // lcp.h:21-23
 bool MixedConstraintsSolver(const MatrixXd &A, const VectorXd &b, const ArrayXb &C, const VectorXd &x_lo,
                             const VectorXd &x_hi, VectorXd &x, VectorXd &w);
+// The same on many independent problems in one library call (egs_mixed_constraints_solve_batch: problems of up to 112
+// rows fused, one upload, a workgroup per problem, one read-back; larger ones one after another inside the call), named
+// like lcp::SolveLCPBatch and sparse::*IterationBatch: what the reference's own test of the function does one problem
+// after another (lcp.cc:412-528).  Returns MixedConstraintsSolver's bool per problem; (*x)[k] and (*w)[k] are its x and w
+// for A[k], b[k], C[k] (the bounds are ignored as there, quirk Q3).  Sizes may differ from problem to problem (0 rows
+// included).  A mismatched argument throws egs::Error(EGS_ERR_INVALID).
+std::vector<bool> MixedConstraintsSolverBatch(const std::vector<MatrixXd> &A, const std::vector<VectorXd> &b,
+                                              const std::vector<ArrayXb> &C, const std::vector<VectorXd> &x_lo,
+                                              const std::vector<VectorXd> &x_hi, std::vector<VectorXd> *x, std::vector<VectorXd> *w);
 }
 
 // toolkit/lcp.h:104-174 -- the "adjacent" solver family the north star names

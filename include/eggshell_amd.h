@@ -270,6 +270,32 @@ egs_status egs_mixed_constraints_solve_limits(egs_context *ctx, int32_t N, const
                                               int32_t use_bounds, int32_t max_pivots, double max_seconds,
                                               double *x, double *w, int32_t *ok, int32_t *pivots);
 
+/* Lcp::MixedConstraintsSolver (lcp.cc:276-336) on `count` independent problems in one call: what the reference's own
+ * test of the function does one problem after another (100 random 50 x 50 mixed problems, lcp.cc:412-528), a study of
+ * the condition / cfm rule, or an integrator that assembles its own J M^-1 J^T.  Packing as egs_box_lcp_batch /
+ * egs_dense_iterate_batch: problem k has n[k] >= 0 rows, its full row-major symmetric matrix at A + sum_{j<k} n[j]^2,
+ * its vectors (b, C, lo, hi, x, w) at sum_{j<k} n[j]; A is read only and never permuted.  use_bounds is the mask of
+ * egs_mixed_constraints_solve; max_pivots as in egs_mixed_constraints_solve_limits (0 = the reference's cap
+ * min(1000, 2^n_i)); there is no max_seconds, a fused kernel has no honest wall clock.
+ * Problems of n[k] <= 112 rows with bit 1 clear are fused: one packed page-locked block, one device allocation, one
+ * upload, at most one launch per size class (32 / 64 / 112 rows; a workgroup per problem runs the partition, the
+ * Cholesky of A_ee, the Schur complement, the reference's Murty loop and the back-substitution on chip), one read-back,
+ * one synchronisation; no workgroup waits on another.  Every other problem runs inside the same call, one after
+ * another, on the path of egs_mixed_constraints_solve.  A problem's path depends on its own n alone.
+ * Per problem, the single entry's semantics: w is exactly 0 on the equality rows, x holds A_ee^-1 (b_e - A_ei x_i)
+ * there; ok[k] = the reference's bool, pivots[k] (pivots may be NULL) = the Murty steps (0 without inequality rows);
+ * n[k] = 0 gives ok 1, pivots 0.  ok[k] = 0: A_ee or some A(S,S) is not positive definite, the cap was reached without
+ * a sensible solution, or (bit 0) the inequality bounds break lcp.cc:161-164; x and w of that problem are then not
+ * meaningful and its neighbours are untouched.
+ * Returns EGS_OK whenever every problem was run (outcomes in ok[]; not the single entry's EGS_ERR_LCP_FAILED);
+ * count = 0 is EGS_OK.  EGS_ERR_INVALID, with nothing launched and no output written: count < 0, some n[k] < 0,
+ * use_bounds outside 0..3, max_pivots < 0, a NULL among the required pointers when sum n > 0, or a matrix the single
+ * entry refuses as asymmetric (egs_last_error names the first such problem). */
+egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A,
+                                             const double *b, const uint8_t *C, const double *lo, const double *hi,
+                                             int32_t use_bounds, int32_t max_pivots, double *x, double *w, int32_t *ok,
+                                             int32_t *pivots);
+
 /* Replaces sparse::JacobiIteration / GaussSeidelIteration / SORIteration on an EXPLICIT matrix:
  *   VectorXd sparse::XIteration(const MatrixXd& A, const VectorXd& b)                                    sparse_iterations.h:13-24
  *   VectorXd sparse::XIteration(const MatrixXd& A, const VectorXd& b, const ArrayXb& C, x_lo, x_hi)
