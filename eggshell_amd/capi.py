@@ -43,6 +43,7 @@ EXPORTS = [
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
     "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
+    "egs_world_step_each", "egs_world_step_dense_each",
 ]
 
 
@@ -752,6 +753,38 @@ class World:
         nf = C.c_int32(0)
         st = load().egs_world_step_dense(self.h, C.c_double(dt), C.c_double(erp), C.c_double(cfm), C.c_int32(use_bounds),
                                          C.c_int32(1 if detect_contacts else 0), C.byref(nf))
+        if st not in (OK, ERR_LCP_FAILED):
+            self.ctx.check(st)
+        return nf.value
+
+    def _rates(self, dt, erp):
+        """dt [E] and erp (a scalar broadcasts) as two fp64 arrays of the world's length; ValueError otherwise."""
+        E = self.n_ensembles
+        dt = np.ascontiguousarray(np.atleast_1d(np.asarray(dt, np.float64)))
+        erp = np.asarray(erp, np.float64)
+        erp = np.ascontiguousarray(np.full(E, float(erp)) if erp.ndim == 0 else erp)
+        for name, a in (("dt", dt), ("erp", erp)):
+            if a.shape != (E,):
+                raise ValueError("%s has shape %s: the world has %d ensemble(s)" % (name, a.shape, E))
+        return dt, erp
+
+    def step_each(self, dt, erp, prm, detect_contacts=True, want_stats=False):
+        """step() with ensemble e stepped by dt[e] with erp[e] (egs_world_step_each): array-likes of length E, a scalar
+        erp broadcasts; dt[e] = 0 lets ensemble e sit the step out."""
+        dt, erp = self._rates(dt, erp)
+        st = SolveStats()
+        self.ctx.check(load().egs_world_step_each(self.h, C.c_int32(self.n_ensembles), _p(dt), _p(erp), C.byref(prm),
+                                                  C.c_int32(1 if detect_contacts else 0),
+                                                  C.byref(st) if want_stats else None))
+        return st
+
+    def step_dense_each(self, dt, erp, cfm=0.01, use_bounds=0, detect_contacts=True):
+        """step_dense() with ensemble e stepped by dt[e] with erp[e] (egs_world_step_dense_each); returns how many
+        ensembles failed to solve, as step_dense() does."""
+        dt, erp = self._rates(dt, erp)
+        nf = C.c_int32(0)
+        st = load().egs_world_step_dense_each(self.h, C.c_int32(self.n_ensembles), _p(dt), _p(erp), C.c_double(cfm),
+                                              C.c_int32(use_bounds), C.c_int32(1 if detect_contacts else 0), C.byref(nf))
         if st not in (OK, ERR_LCP_FAILED):
             self.ctx.check(st)
         return nf.value

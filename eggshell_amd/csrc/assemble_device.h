@@ -74,9 +74,12 @@ __device__ __forceinline__ double dot6p(const double *a, const double *b) {
 }
 
 // Constraint i: j0 / j1 (3x6 row-major, zero for a world side), e = err, lo / hi, eq (every row of a joint is an
-// equality row, no row of a contact is) and per side u = v/dt + W f (zero for a world side), what the rhs needs
-__device__ __forceinline__ void assemble_one(const AssembleArgs &A, int i, double *j0, double *j1, double *e, double *lo,
-                                             double *hi, bool &eq, double *u0, double *u1) {
+// equality row, no row of a contact is) and per side u = v/dt + W f (zero for a world side), what the rhs needs.
+// EACH: dt is the constraint's own time step, dt_each (constraint_rates); otherwise the launch's A.dt, read where the
+// scalar form has always read it
+template <bool EACH>
+__device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, double dt_each, double *j0, double *j1, double *e,
+                                               double *lo, double *hi, bool &eq, double *u0, double *u1) {
   const int b0 = A.body0[i], b1 = A.body1[i];
   double d[7];
 #pragma unroll
@@ -157,23 +160,40 @@ __device__ __forceinline__ void assemble_one(const AssembleArgs &A, int i, doubl
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       const double vel = r < 3 ? A.v[(size_t)b0 * 3 + r] : A.w[(size_t)b0 * 3 + r - 3];
-      u0[r] = vel / A.dt + A.Wf[(size_t)b0 * 6 + r];
+      u0[r] = vel / (EACH ? dt_each : A.dt) + A.Wf[(size_t)b0 * 6 + r];
     }
   }
   if (b1 >= 0) {
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       const double vel = r < 3 ? A.v[(size_t)b1 * 3 + r] : A.w[(size_t)b1 * 3 + r - 3];
-      u1[r] = vel / A.dt + A.Wf[(size_t)b1 * 6 + r];
+      u1[r] = vel / (EACH ? dt_each : A.dt) + A.Wf[(size_t)b1 * 6 + r];
     }
   }
 }
+__device__ __forceinline__ void assemble_one(const AssembleArgs &A, int i, double *j0, double *j1, double *e, double *lo,
+                                             double *hi, bool &eq, double *u0, double *u1) {
+  assemble_one_t<false>(A, i, 0.0, j0, j1, e, lo, hi, eq, u0, u1);
+}
 // row r of rhs = -(erp/dt^2) err - J (v/dt + W f)      ensembles.cc:569-570
-__device__ __forceinline__ double assemble_rhs(const AssembleArgs &A, const double *j0, const double *j1, const double *e,
-                                               const double *u0, const double *u1, int r) {
-  const double kk = -A.erp / A.dt / A.dt;
+template <bool EACH>
+__device__ __forceinline__ double assemble_rhs_t(const AssembleArgs &A, double dt_each, double erp_each, const double *j0,
+                                                 const double *j1, const double *e, const double *u0, const double *u1, int r) {
+  const double kk = EACH ? -erp_each / dt_each / dt_each : -A.erp / A.dt / A.dt;
   const double ju = dot6p(j0 + 6 * r, u0) + dot6p(j1 + 6 * r, u1);
   return kk * e[r] - ju;
+}
+__device__ __forceinline__ double assemble_rhs(const AssembleArgs &A, const double *j0, const double *j1, const double *e,
+                                               const double *u0, const double *u1, int r) {
+  return assemble_rhs_t<false>(A, 0.0, 0.0, j0, j1, e, u0, u1, r);
+}
+// the per-ensemble form's dt and erp of constraint i: its ensemble's (the ensemble of its first body)
+template <typename RATES>   // (instantiated for EnsembleRates only: the scalar form never calls it)
+__device__ __forceinline__ void constraint_rates(const AssembleArgs &A, const RATES &T, int i, double &dt, double &erp) {
+  const int b0 = A.body0[i];
+  const int en = T.body_ens[b0 >= 0 ? b0 : A.body1[i]];
+  dt = T.dt[en];
+  erp = T.erp[en];
 }
 
 }  // namespace

@@ -19,6 +19,14 @@ struct AssembleArgs {
   double *err;                                   // [3m] fp64
   uint8_t *is_eq;
 };
+// Per-ensemble rates of a step (egs_world_step_each), device tables: body -> ensemble [n], dt [n_ens], erp [n_ens].
+// A constraint takes its first body's ensemble's pair instead of AssembleArgs' dt / erp, a body its ensemble's dt.
+// dt[e] == 0: ensemble e sits the step out (rhs rows exactly 0, bodies left alone).  Kept out of AssembleArgs, which
+// is part of SolveArgs: the kernel arguments of the solve launches stay what they are.
+struct EnsembleRates {
+  const int32_t *body_ens = nullptr;
+  const double *dt = nullptr, *erp = nullptr;
+};
 
 // Flat system + tile plan, all device pointers.
 template <typename REAL>
@@ -139,6 +147,9 @@ template <typename REAL>
 void launch_quad_patch_solve(const SolveArgs<REAL> &a, int method, int n_tiles, uint32_t *tickets, hipStream_t s);
 template <typename REAL>
 void launch_assemble(const AssembleArgs &a, hipStream_t s);
+// ... with every constraint on its ensemble's rates (a.dt and a.erp are not read)
+template <typename REAL>
+void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStream_t s);
 // partial sums of squares by row category: out[4*blocks]
 template <typename REAL>
 void launch_residual_partials(int rows, const REAL *wres, const REAL *x,
@@ -148,6 +159,10 @@ void launch_residual_partials(int rows, const REAL *wres, const REAL *x,
 template <typename REAL>
 void launch_velocity(int n, const double *v, const double *w, const double *Wf, const REAL *acc,
                      double dt, double *v6, hipStream_t s);
+// body b takes dt_each[body_ens[b]]; a body whose ensemble sits the step out (dt 0) keeps its velocity: v6 = (v, w)
+template <typename REAL>
+void launch_velocity_each(int n, const double *v, const double *w, const double *Wf, const REAL *acc,
+                          const int32_t *body_ens, const double *dt_each, double *v6, hipStream_t s);
 // Residual partial sums (the 4 categories of sparse_iterations.cc:51-69, `blocks` partial
 // sums each, same reduction order as launch_residual_partials) for every sweep of a recorded
 // chunk: out [sweeps][blocks][4].  write_sweep >= 1 also stores that sweep's w into wres.
@@ -208,6 +223,9 @@ struct BodyState {
   double *pos, *R, *v, *w;
 };
 void launch_advance(int n, const BodyState &in, const BodyState &out, const double *v6, double dt, hipStream_t s);
+// in place, body b by dt_each[body_ens[b]]; a body whose ensemble sits the step out (dt 0) is neither read nor written
+void launch_advance_each(int n, const BodyState &state, const double *v6, const int32_t *body_ens, const double *dt_each,
+                         hipStream_t s);
 
 constexpr int kResidualBlocks = 64;
 

@@ -443,6 +443,18 @@ __global__ void __launch_bounds__(256) velocity_kernel(int n, const double *v, c
   const double vel = r < 3 ? v[(size_t)b * 3 + r] : w[(size_t)b * 3 + r - 3];
   v6[e] = vel + dt * (Wf[e] + (double)acc[e]);
 }
+// ... with each body's own dt (egs_world_step_each); a body that sits the step out keeps its velocity
+template <typename REAL>
+__global__ void __launch_bounds__(256) velocity_each_kernel(int n, const double *v, const double *w, const double *Wf,
+                                                            const REAL *acc, const int32_t *body_ens, const double *dt_each,
+                                                            double *v6) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= 6 * n) return;
+  const int b = e / 6, r = e - 6 * b;
+  const double vel = r < 3 ? v[(size_t)b * 3 + r] : w[(size_t)b * 3 + r - 3];
+  const double dt = dt_each[body_ens[b]];
+  v6[e] = dt == 0.0 ? vel : vel + dt * (Wf[e] + (double)acc[e]);
+}
 
 // Wf = M^-1 f_ext per body, the expression of ComputeVDot's M_inverse_ * external_force_torque_
 // restricted to the diagonal block (ensembles.cc:535)
@@ -459,9 +471,16 @@ __global__ void __launch_bounds__(256) mass_times_force_kernel(int n, const doub
 // velocities become the body state for the next step.
 // The state is read from `in` and written to `out`: the same arrays (in place), or a second set, which leaves the state
 // the step started from intact (egs_problem_advance after a step whose system is deferred).
-__global__ void __launch_bounds__(256) advance_kernel(int n, const BodyState in, const BodyState out, const double *v6, double dt) {
+// EACH: in place (in == out), body b by dt_each[body_ens[b]]; dt 0 = the body is left alone
+template <bool EACH>
+__device__ __forceinline__ void advance_body(int n, const BodyState &in, const BodyState &out, const double *v6, double dt,
+                                             const int32_t *body_ens, const double *dt_each) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n) return;
+  if (EACH) {
+    dt = dt_each[body_ens[b]];
+    if (dt == 0.0) return;
+  }
   double wm[3], Rb[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) Rb[k] = in.R[(size_t)b * 9 + k];
@@ -476,6 +495,13 @@ __global__ void __launch_bounds__(256) advance_kernel(int n, const BodyState in,
   for (int k = 0; k < 9; ++k) out.R[(size_t)b * 9 + k] = Rb[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) { out.v[(size_t)b * 3 + k] = v6[(size_t)b * 6 + k]; out.w[(size_t)b * 3 + k] = v6[(size_t)b * 6 + 3 + k]; }
+}
+__global__ void __launch_bounds__(256) advance_kernel(int n, const BodyState in, const BodyState out, const double *v6, double dt) {
+  advance_body<false>(n, in, out, v6, dt, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) advance_each_kernel(int n, const BodyState state, const double *v6,
+                                                           const int32_t *body_ens, const double *dt_each) {
+  advance_body<true>(n, state, state, v6, 0.0, body_ens, dt_each);
 }
 
 template <typename REAL>
@@ -518,8 +544,11 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
 
 // --------------------------------------------------------------------------
 // K1-K4 assembly: the per-constraint body lives in assemble_device.h.
-template <typename REAL>
-__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
+struct NoRates {};   // the scalar form's (empty) second argument
+// EACH: dt and erp per constraint from its ensemble's (T); an ensemble that sits the step out (dt 0) gets rhs rows of
+// exactly 0, its blocks, err, bounds and row types as always.
+template <typename REAL, bool EACH, typename RATES>
+__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
   // stores hit 64 lines per instruction; staged, the workgroup writes its 256 x 18 block contiguously
   __shared__ REAL stage[256 * 19];   // row stride 19: conflict-free column walks
@@ -528,7 +557,9 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
   const int i = live ? i_raw : A.m - 1;   // the tail lanes recompute the last constraint and store nothing
   double j0[18], j1[18], e[3], lo[3], hi[3], u0[6], u1[6];
   bool eq;
-  assemble_one(A, i, j0, j1, e, lo, hi, eq, u0, u1);
+  double dt = 0.0, erp = 0.0;   // EACH: the constraint's own; otherwise A.dt / A.erp where they are used
+  if constexpr (EACH) constraint_rates(A, T, i, dt, erp);
+  assemble_one_t<EACH>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
   REAL *J0o = reinterpret_cast<REAL *>(A.J0), *J1o = reinterpret_cast<REAL *>(A.J1);
   REAL *loo = reinterpret_cast<REAL *>(A.lo), *hio = reinterpret_cast<REAL *>(A.hi);
   REAL *rhso = reinterpret_cast<REAL *>(A.rhs);
@@ -548,7 +579,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A) {
   if (!live) return;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    rhso[(size_t)i * 3 + r] = (REAL)assemble_rhs(A, j0, j1, e, u0, u1, r);
+    rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_t<EACH>(A, dt, erp, j0, j1, e, u0, u1, r);
     A.err[(size_t)i * 3 + r] = e[r];
     loo[(size_t)i * 3 + r] = (REAL)lo[r];
     hio[(size_t)i * 3 + r] = (REAL)hi[r];
@@ -863,7 +894,13 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 template <typename REAL>
 void launch_assemble(const AssembleArgs &a, hipStream_t s) {
   if (a.m <= 0) return;
-  hipLaunchKernelGGL((assemble_kernel<REAL>), dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates>), dim3((a.m + 255) / 256), dim3(256), 0, s, a, NoRates{});
+}
+
+template <typename REAL>
+void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStream_t s) {
+  if (a.m <= 0) return;
+  hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates>), dim3((a.m + 255) / 256), dim3(256), 0, s, a, t);
 }
 
 template <typename REAL>
@@ -907,6 +944,14 @@ void launch_velocity(int n, const double *v, const double *w, const double *Wf, 
   hipLaunchKernelGGL((velocity_kernel<REAL>), dim3((6 * n + 255) / 256), dim3(256), 0, s, n, v, w, Wf, acc, dt, v6);
 }
 
+template <typename REAL>
+void launch_velocity_each(int n, const double *v, const double *w, const double *Wf, const REAL *acc, const int32_t *body_ens,
+                          const double *dt_each, double *v6, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL((velocity_each_kernel<REAL>), dim3((6 * n + 255) / 256), dim3(256), 0, s, n, v, w, Wf, acc, body_ens,
+                     dt_each, v6);
+}
+
 void launch_mass_times_force(int n, const double *Minv, const double *f_ext, double *Wf, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(mass_times_force_kernel, dim3((6 * n + 255) / 256), dim3(256), 0, s, n, Minv, f_ext, Wf);
@@ -915,6 +960,12 @@ void launch_mass_times_force(int n, const double *Minv, const double *f_ext, dou
 void launch_advance(int n, const BodyState &in, const BodyState &out, const double *v6, double dt, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, in, out, v6, dt);
+}
+
+void launch_advance_each(int n, const BodyState &state, const double *v6, const int32_t *body_ens, const double *dt_each,
+                         hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(advance_each_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, state, v6, body_ens, dt_each);
 }
 
 template <typename REAL>
@@ -997,10 +1048,13 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_cons_prepare<REAL>(const SolveArgs<REAL> &, hipStream_t);                             \
   template void launch_global_wres<REAL>(const GlobalArgs<REAL> &, hipStream_t);                            \
   template void launch_assemble<REAL>(const AssembleArgs &, hipStream_t);                                    \
+  template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, hipStream_t);        \
   template void launch_residual_partials<REAL>(int, const REAL *, const REAL *, const REAL *, const REAL *,  \
                                                const uint8_t *, double *, int, hipStream_t);                 \
   template void launch_velocity<REAL>(int, const double *, const double *, const double *, const REAL *, double,   \
                                       double *, hipStream_t);                          \
+  template void launch_velocity_each<REAL>(int, const double *, const double *, const double *, const REAL *,      \
+                                           const int32_t *, const double *, double *, hipStream_t);                 \
   template void launch_convert_minv<REAL>(int, const double *, REAL *, hipStream_t);                         \
   template void launch_minv_iso<REAL>(int, const REAL *, int *, hipStream_t);                               \
   template void launch_linsym_bodies<REAL>(int, const int32_t *, const int32_t *, const REAL *, int *, hipStream_t);                               \

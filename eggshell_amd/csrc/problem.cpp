@@ -236,6 +236,14 @@ void do_assemble(egs_problem *p, double dt, double erp) {
   p->sys_deferred = false;   // every array is written: a deferred system is superseded
 }
 
+void do_assemble_each(egs_problem *p, const EnsembleRates &r) {
+  const AssembleArgs a = assemble_args(p, 0.0, 0.0);   // the scalar pair is not read
+  with_real(p, [&](auto t) { launch_assemble_each<decltype(t)>(a, r, p->ctx->stream); });
+  HIPCHK(hipGetLastError());
+  note_assembled(p);
+  p->sys_deferred = false;
+}
+
 // The deferred step's system, now: assemble_kernel on the state that step read, with its dt and erp.
 void ensure_system(egs_problem *p) {
   if (!p->sys_deferred) return;
@@ -251,6 +259,15 @@ void do_velocity(egs_problem *p, double dt) {
   with_real(p, [&](auto r) {
     using REAL = decltype(r);
     launch_velocity<REAL>(p->n, p->v.p, p->w.p, p->Wf.p, real<REAL>(p->acc), dt, p->v6.p, p->ctx->stream);
+  });
+  HIPCHK(hipGetLastError());
+}
+
+void do_velocity_each(egs_problem *p, const EnsembleRates &r) {
+  ensure_wf(p);
+  with_real(p, [&](auto t) {
+    using REAL = decltype(t);
+    launch_velocity_each<REAL>(p->n, p->v.p, p->w.p, p->Wf.p, real<REAL>(p->acc), r.body_ens, r.dt, p->v6.p, p->ctx->stream);
   });
   HIPCHK(hipGetLastError());
 }

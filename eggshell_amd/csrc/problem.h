@@ -149,6 +149,9 @@ void do_assemble(egs_problem *p, double dt, double erp);
 // J0, J1, rhs, lo, hi, err and is_eq are materialised after this (a no-op unless the last step deferred them)
 void ensure_system(egs_problem *p);
 void do_velocity(egs_problem *p, double dt);
+// do_assemble / do_velocity with every constraint / body on its ensemble's rates (kernels.h: EnsembleRates)
+void do_assemble_each(egs_problem *p, const EnsembleRates &r);
+void do_velocity_each(egs_problem *p, const EnsembleRates &r);
 void zero_accumulators(egs_problem *p);
 void post_flag_copy(egs_problem *p);
 egs_status report_stall(egs_problem *p);

@@ -1,6 +1,7 @@
 // world.cpp -- struct egs_world and the egs_world_* entries of the C ABI, with the stateless egs_update_contacts[_joints]:
 // Ensemble::Step (ensembles.cc:390-427) resident on the device, for one ensemble or a batch of them, on the sparse
-// sweeps (egs_world_step), the dense path (egs_world_step_dense) and the stabilisation passes (egs_world_stabilize,
+// sweeps (egs_world_step), the dense path (egs_world_step_dense), either with a time step and an erp per ensemble
+// (egs_world_step_each, egs_world_step_dense_each), and the stabilisation passes (egs_world_stabilize,
 // egs_world_stabilize_direct), and the one-shot egs_relax_blocks_direct.
 // The world works on its egs_problem through problem.h.
 #include <chrono>
@@ -44,6 +45,15 @@ struct egs_world {
   DevBuf<int32_t> d_ens, d_boff, d_joff;       // body -> ensemble [n], body and joint offsets [n_ens + 1]
   DevBuf<int32_t> d_coff;                      // contact offsets [n_ens + 1], written by the collider
   BatchSolveState batch;
+  // egs_world_step_each / _dense_each: dt [E] | erp [E] on the device and the values last sent (an equal pair is not
+  // sent again); the page-locked block they go through -- dt, erp, then the E list words of a dense step with
+  // ensembles sitting out -- and the event behind the last copy out of it; that step's fused lists.  A plain world
+  // gets its body -> ensemble table (all 0) on its first such step.
+  DevBuf<double> d_rates;
+  std::vector<double> rates_sent;
+  PinnedBuf<double> h_each;
+  hipEvent_t each_ev = nullptr;
+  DevBuf<int32_t> dn_lists_step;
   // egs_world_step_dense: each ensemble's dense row space (its joints, then its contacts, as its own Ensemble lists
   // them), built on the first dense step after a re-plan; the figures of the last dense step
   int dense_plan_replans = -1;           // w->replans the tables below were built for
@@ -314,12 +324,64 @@ egs_status world_step_guard(egs_world *w, double dt, const char *fp64_what) {
   return EGS_OK;
 }
 
+// the arguments of the _each entries, in the scalar guard's order: bodies set, the tables and every dt[e] >= 0, fp64
+egs_status world_each_guard(egs_world *w, int32_t n_ensembles, const double *dt, const double *erp, const char *fp64_what) {
+  if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
+  if (!dt || !erp) return fail(w->ctx, EGS_ERR_INVALID, "NULL dt / erp table");
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  for (int e = 0; e < n_ensembles; ++e)
+    if (!(dt[e] >= 0)) return fail(w->ctx, EGS_ERR_INVALID, "dt[" + std::to_string(e) + "] must be >= 0 (0: the ensemble sits out)");
+  if (fp64_what && w->precision != EGS_F64) return fail(w->ctx, EGS_ERR_UNSUPPORTED, fp64_what);
+  return EGS_OK;
+}
+
+// the host may write the page-locked block of the _each entries again: the last copy out of it has been made
+void world_each_block(egs_world *w) {
+  const size_t E = (size_t)w->n_ens;
+  w->h_each.alloc(2 * E + (E + 1) / 2);   // once: E is the world's
+  if (!w->each_ev) HIPCHK(hipEventCreateWithFlags(&w->each_ev, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(w->each_ev));   // long past by the next step: no wait in practice
+}
+
+// dt [E] and erp [E] to the device through the page-locked block, no stream synchronisation; the tables of the step
+EnsembleRates world_send_rates(egs_world *w, const double *dt, const double *erp) {
+  hipStream_t s = w->ctx->stream;
+  const size_t E = (size_t)w->n_ens, bytes = E * sizeof(double);
+  if (!w->d_ens.p) {   // a plain world: every body in ensemble 0
+    w->d_ens.alloc((size_t)(w->n > 0 ? w->n : 1));
+    HIPCHK(hipMemsetAsync(w->d_ens.p, 0, w->d_ens.count * sizeof(int32_t), s));
+  }
+  const bool same = w->rates_sent.size() == 2 * E && std::memcmp(w->rates_sent.data(), dt, bytes) == 0 &&
+                    std::memcmp(w->rates_sent.data() + E, erp, bytes) == 0;
+  if (!same) {
+    world_each_block(w);
+    std::memcpy(w->h_each.p, dt, bytes);
+    std::memcpy(w->h_each.p + E, erp, bytes);
+    w->d_rates.alloc(2 * E);
+    HIPCHK(hipMemcpyAsync(w->d_rates.p, w->h_each.p, 2 * bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(w->each_ev, s));
+    w->rates_sent.assign(w->h_each.p, w->h_each.p + 2 * E);
+  }
+  return EnsembleRates{w->d_ens.p, w->d_rates.p, w->d_rates.p + E};
+}
+
+// the assembly of a step: J, err, bounds, rhs (ensembles.cc:565-570), on one dt / erp or on every ensemble's own
+void world_assemble(egs_world *w, double dt, double erp, const EnsembleRates *each) {
+  if (each) do_assemble_each(w->prob, *each);
+  else do_assemble(w->prob, dt, erp);
+}
+
 // the tail of a step: velocities from the accumulators (ensembles.cc:535, 572), then StepPositions_ODE
-void world_integrate(egs_world *w, double dt) {
+void world_integrate(egs_world *w, double dt, const EnsembleRates *each) {
   egs_problem *p = w->prob;
-  do_velocity(p, dt);
   const BodyState state{p->pos.p, p->R.p, p->v.p, p->w.p};
-  launch_advance(p->n, state, state, p->v6.p, dt, w->ctx->stream);
+  if (each) {
+    do_velocity_each(p, *each);
+    launch_advance_each(p->n, state, p->v6.p, each->body_ens, each->dt, w->ctx->stream);
+  } else {
+    do_velocity(p, dt);
+    launch_advance(p->n, state, state, p->v6.p, dt, w->ctx->stream);
+  }
   HIPCHK(hipGetLastError());
 }
 
@@ -342,8 +404,8 @@ struct PhaseTimer {
 
 // egs_world_step_dense's ensembles above the fused cap: the multi-launch path on each ensemble's workspace slice, one
 // after another (row types and bounds read back once per re-plan).  x: the world problem's lambda.  The first
-// failure's message goes to big_msg.
-void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double *x, std::string &big_msg) {
+// failure's message goes to big_msg.  dt_each [E] (host, may be NULL): an ensemble with dt 0 sits out, it is not solved.
+void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double *x, std::string &big_msg, const double *dt_each) {
   hipStream_t s = w->ctx->stream;
   auto rows_of = [&](int e) { return 3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]); };
   if (!w->dn_big_rows_valid) {
@@ -374,6 +436,7 @@ void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double 
   size_t r0 = 0;
   for (int e : w->dn_big) {
     const int N = rows_of(e);
+    if (dt_each && dt_each[e] == 0.0) { r0 += (size_t)N; continue; }
     double *A = w->dn_ws.p + w->dn_off[(size_t)e];
     double *vb = A + dense_ws_vec((size_t)N), *xs = vb + 4 * (size_t)N;
     DenseEnsStatus &st = w->dn_info[(size_t)e];
@@ -393,6 +456,144 @@ void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double 
     r0 += (size_t)N;
   }
   HIPCHK(hipGetLastError());
+}
+
+// egs_world_step (dt_each == NULL) and egs_world_step_each (dt_each / erp_each [E], host, validated) after their guards
+egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *dt_each, const double *erp_each,
+                             const egs_solve_params *params, int32_t detect_contacts, egs_solve_stats *stats) {
+  w->last_dense = false;
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    PhaseTimer lap{w, w->t_phase, /*sync=*/false};
+    EnsembleRates rates;
+    if (dt_each) rates = world_send_rates(w, dt_each, erp_each);
+    const EnsembleRates *each = dt_each ? &rates : nullptr;
+    if (detect_contacts) world_update_contacts(w, lap);
+    egs_problem *p = w->prob;
+    const bool batched = w->n_ens > 1;
+    if (p->m > 0) {
+      world_assemble(w, dt, erp, each);
+      egs_status st = batched ? do_solve_batch(p, params, w->batch) : do_solve(p, params, stats);
+      if (st != EGS_OK) return st;
+      // the body state must not be advanced with a lambda that came out of a timed-out ordering
+      // wait: look at the flag before integrating (one 4-byte read-back per step)
+      HIPCHK(hipStreamSynchronize(s));
+      if (stall_seen(p)) return report_stall(p);
+      w->lambda_stale = false;   // x holds this step's lambda for the current list
+      if (batched && stats) {   // the slowest ensemble's sweep count and the largest residual
+        std::memset(stats, 0, sizeof *stats);
+        fill_stats(p, stats);
+        for (int e = 0; e < w->n_ens; ++e) {
+          stats->iterations = std::max(stats->iterations, w->batch.h_ints.p[e]);
+          const double r = w->batch.h_res.p[e];
+          if (!std::isnan(stats->residual) && (std::isnan(r) || r > stats->residual)) stats->residual = r;   // NaN wins
+        }
+      }
+    } else {  // no constraints: v_dot = M^-1 f (ensembles.cc:504-505)
+      if (egs_status st = validate_params(w->ctx, params)) return st;
+      w->lambda_stale = false;
+      zero_accumulators(p);
+      if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
+      if (batched) {
+        std::fill(w->batch.h_ints.p, w->batch.h_ints.p + w->n_ens, 0);
+        std::fill(w->batch.h_res.p, w->batch.h_res.p + w->n_ens, 0.0);
+      }
+    }
+    world_integrate(w, dt, each);
+    if (w->trace) { HIPCHK(hipStreamSynchronize(s)); lap(3); w->t_phase[4] += 1; }
+    return EGS_OK;
+  });
+}
+
+// egs_world_step_dense (dt_each == NULL) and egs_world_step_dense_each (dt_each / erp_each [E], host, validated) after
+// their guards
+egs_status world_step_direct(egs_world *w, double dt, double erp, const double *dt_each, const double *erp_each,
+                             double cfm_coeff, int32_t use_bounds, int32_t detect_contacts, int32_t *n_failed) {
+  w->last_dense = false;
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    EnsembleRates rates;
+    if (dt_each) rates = world_send_rates(w, dt_each, erp_each);
+    const EnsembleRates *each = dt_each ? &rates : nullptr;
+    if (detect_contacts) world_update_contacts(w, [](int) {});
+    egs_problem *p = w->prob;
+    const int E = w->n_ens;
+    if (!w->h_dn_status) w->h_dn_status = static_cast<DenseEnsStatus *>(w->dn_pinned.take((size_t)E * sizeof(DenseEnsStatus)));
+    w->dn_info.assign((size_t)E, DenseEnsStatus{1.0, 0.0, 1, 0});   // contact-free ensembles: solved, no pivots
+    std::string big_msg;
+    bool sits_out = false;
+    for (int e = 0; dt_each && e < E; ++e) sits_out |= dt_each[e] == 0.0;
+    if (p->m > 0) {
+      world_assemble(w, dt, erp, each);                              // J, err, bounds, rhs (ensembles.cc:565-570)
+      if (w->dense_plan_replans != w->replans) world_dense_plan(w);
+      DenseWorldArgs a;
+      a.cons = w->dn_cons.p; a.cstart = w->dn_cstart.p; a.ws_off = w->dn_wsoff.p;
+      a.body0 = p->body0.p; a.body1 = p->body1.p;
+      a.J0 = real<double>(p->J0); a.J1 = real<double>(p->J1);
+      a.Minv = p->Minv_d.p;
+      a.rhs = real<double>(p->rhs);
+      a.lo = real<double>(p->lo); a.hi = real<double>(p->hi);
+      a.is_eq = p->is_eq.p;
+      a.ws = w->dn_ws.p; a.x = real<double>(p->x); a.status = w->dn_status.p;
+      a.cfm_coeff = cfm_coeff; a.use_bounds = use_bounds;
+      launch_dense_world_system(a, E, w->dn_max_m, s);               // A_e = J M^-1 J^T (ensembles.cc:510)
+      // ensembles sitting out (dt 0) are not solved: this step's fused lists go without them and their lambda rows are 0
+      const int32_t *lists = w->dn_lists.p;
+      int count[3] = {(int)w->dn_class[0].size(), (int)w->dn_class[1].size(), (int)w->dn_class[2].size()};
+      if (sits_out) {
+        world_each_block(w);
+        int32_t *h_lists = reinterpret_cast<int32_t *>(w->h_each.p + 2 * (size_t)E);
+        int k = 0;
+        for (int c = 0; c < 3; ++c) {
+          count[c] = 0;
+          for (int e : w->dn_class[c])
+            if (dt_each[e] != 0.0) { h_lists[k++] = e; ++count[c]; }
+        }
+        w->dn_lists_step.alloc((size_t)E);
+        if (k > 0) HIPCHK(hipMemcpyAsync(w->dn_lists_step.p, h_lists, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(w->each_ev, s));
+        lists = w->dn_lists_step.p;
+        HIPCHK(hipMemsetAsync(a.x, 0, (size_t)p->m * 3 * sizeof(double), s));
+      }
+      int at = 0;
+      for (int c = 0; c < 3; ++c) {                                  // the rest of ComputeVDot, one workgroup each
+        launch_dense_world_fused(a, lists + at, count[c], c, s);
+        at += count[c];
+      }
+      HIPCHK(hipGetLastError());
+      if (!w->dn_big.empty()) world_dense_big(w, cfm_coeff, use_bounds, a.x, big_msg, dt_each);   // above the fused cap
+      // one read-back of the fused ensembles' figures
+      if (at > 0) {
+        HIPCHK(hipMemcpyAsync(w->h_dn_status, w->dn_status.p, (size_t)E * sizeof(DenseEnsStatus), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (const auto &l : w->dn_class)
+          for (int e : l)
+            if (!(dt_each && dt_each[e] == 0.0)) w->dn_info[(size_t)e] = w->h_dn_status[e];
+      }
+    }
+    int nf = 0, first = -1, max_piv = 0;
+    for (int e = 0; e < E; ++e) {
+      const DenseEnsStatus &st = w->dn_info[(size_t)e];
+      if (!st.ok && first < 0) first = e;
+      nf += st.ok ? 0 : 1;
+      max_piv = std::max(max_piv, (int)st.pivots);
+      if (E > 1) { w->batch.h_ints.p[e] = st.pivots; w->batch.h_res.p[e] = std::numeric_limits<double>::quiet_NaN(); }
+    }
+    p->last_iterations = max_piv;
+    w->last_dense = true;
+    if (n_failed) *n_failed = nf;
+    if (nf > 0) {   // the reference Panics (ensembles.cc:531-534): no body is advanced
+      std::string msg = "ensemble " + std::to_string(first) + ": MixedConstraintsSolver did not reach a solution";
+      if (!big_msg.empty()) msg += " (" + big_msg + ")";
+      if (nf > 1) msg += "; " + std::to_string(nf) + " of " + std::to_string(E) + " ensembles failed";
+      return fail(w->ctx, EGS_ERR_LCP_FAILED, msg);
+    }
+    w->lambda_stale = false;   // every ensemble solved: x holds this step's lambda for the current list
+    if (p->m > 0) accumulators_from_lambda(p);                    // a = M^-1 J^T lambda
+    else zero_accumulators(p);
+    world_integrate(w, dt, each);
+    return EGS_OK;
+  });
 }
 
 }  // namespace
@@ -460,6 +661,7 @@ void egs_world_destroy(egs_world *w) {
   }
   if (w->prob) egs_problem_destroy(w->prob);
   if (w->rx) egs_problem_destroy(w->rx);
+  if (w->each_ev) (void)hipEventDestroy(w->each_ev);
   delete w;
 }
 
@@ -570,45 +772,14 @@ egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_p
                           int32_t detect_contacts, egs_solve_stats *stats) {
   if (!w) return EGS_ERR_INVALID;
   if (egs_status st = world_step_guard(w, dt, nullptr)) return st;
-  w->last_dense = false;
-  return guarded(w->ctx, [&]() -> egs_status {
-    hipStream_t s = w->ctx->stream;
-    PhaseTimer lap{w, w->t_phase, /*sync=*/false};
-    if (detect_contacts) world_update_contacts(w, lap);
-    egs_problem *p = w->prob;
-    const bool batched = w->n_ens > 1;
-    if (p->m > 0) {
-      do_assemble(p, dt, erp);
-      egs_status st = batched ? do_solve_batch(p, params, w->batch) : do_solve(p, params, stats);
-      if (st != EGS_OK) return st;
-      // the body state must not be advanced with a lambda that came out of a timed-out ordering
-      // wait: look at the flag before integrating (one 4-byte read-back per step)
-      HIPCHK(hipStreamSynchronize(s));
-      if (stall_seen(p)) return report_stall(p);
-      w->lambda_stale = false;   // x holds this step's lambda for the current list
-      if (batched && stats) {   // the slowest ensemble's sweep count and the largest residual
-        std::memset(stats, 0, sizeof *stats);
-        fill_stats(p, stats);
-        for (int e = 0; e < w->n_ens; ++e) {
-          stats->iterations = std::max(stats->iterations, w->batch.h_ints.p[e]);
-          const double r = w->batch.h_res.p[e];
-          if (!std::isnan(stats->residual) && (std::isnan(r) || r > stats->residual)) stats->residual = r;   // NaN wins
-        }
-      }
-    } else {  // no constraints: v_dot = M^-1 f (ensembles.cc:504-505)
-      if (egs_status st = validate_params(w->ctx, params)) return st;
-      w->lambda_stale = false;
-      zero_accumulators(p);
-      if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
-      if (batched) {
-        std::fill(w->batch.h_ints.p, w->batch.h_ints.p + w->n_ens, 0);
-        std::fill(w->batch.h_res.p, w->batch.h_res.p + w->n_ens, 0.0);
-      }
-    }
-    world_integrate(w, dt);
-    if (w->trace) { HIPCHK(hipStreamSynchronize(s)); lap(3); w->t_phase[4] += 1; }
-    return EGS_OK;
-  });
+  return world_step_sweeps(w, dt, erp, nullptr, nullptr, params, detect_contacts, stats);
+}
+
+egs_status egs_world_step_each(egs_world *w, int32_t n_ensembles, const double *dt, const double *erp,
+                               const egs_solve_params *params, int32_t detect_contacts, egs_solve_stats *stats) {
+  if (!w) return EGS_ERR_INVALID;
+  if (egs_status st = world_each_guard(w, n_ensembles, dt, erp, nullptr)) return st;
+  return world_step_sweeps(w, 0.0, 0.0, dt, erp, params, detect_contacts, stats);
 }
 
 egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_coeff, int32_t use_bounds,
@@ -617,67 +788,16 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
   if (n_failed) *n_failed = 0;
   if (egs_status st = world_step_guard(w, dt, "the dense path is fp64 (the reference's is)")) return st;
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
-  w->last_dense = false;
-  return guarded(w->ctx, [&]() -> egs_status {
-    hipStream_t s = w->ctx->stream;
-    if (detect_contacts) world_update_contacts(w, [](int) {});
-    egs_problem *p = w->prob;
-    const int E = w->n_ens;
-    if (!w->h_dn_status) w->h_dn_status = static_cast<DenseEnsStatus *>(w->dn_pinned.take((size_t)E * sizeof(DenseEnsStatus)));
-    w->dn_info.assign((size_t)E, DenseEnsStatus{1.0, 0.0, 1, 0});   // contact-free ensembles: solved, no pivots
-    std::string big_msg;
-    if (p->m > 0) {
-      do_assemble(p, dt, erp);                                       // J, err, bounds, rhs (ensembles.cc:565-570)
-      if (w->dense_plan_replans != w->replans) world_dense_plan(w);
-      DenseWorldArgs a;
-      a.cons = w->dn_cons.p; a.cstart = w->dn_cstart.p; a.ws_off = w->dn_wsoff.p;
-      a.body0 = p->body0.p; a.body1 = p->body1.p;
-      a.J0 = real<double>(p->J0); a.J1 = real<double>(p->J1);
-      a.Minv = p->Minv_d.p;
-      a.rhs = real<double>(p->rhs);
-      a.lo = real<double>(p->lo); a.hi = real<double>(p->hi);
-      a.is_eq = p->is_eq.p;
-      a.ws = w->dn_ws.p; a.x = real<double>(p->x); a.status = w->dn_status.p;
-      a.cfm_coeff = cfm_coeff; a.use_bounds = use_bounds;
-      launch_dense_world_system(a, E, w->dn_max_m, s);               // A_e = J M^-1 J^T (ensembles.cc:510)
-      int at = 0;
-      for (int c = 0; c < 3; ++c) {                                  // the rest of ComputeVDot, one workgroup each
-        launch_dense_world_fused(a, w->dn_lists.p + at, (int)w->dn_class[c].size(), c, s);
-        at += (int)w->dn_class[c].size();
-      }
-      HIPCHK(hipGetLastError());
-      if (!w->dn_big.empty()) world_dense_big(w, cfm_coeff, use_bounds, a.x, big_msg);   // above the fused cap
-      // one read-back of the fused ensembles' figures
-      if (at > 0) {
-        HIPCHK(hipMemcpyAsync(w->h_dn_status, w->dn_status.p, (size_t)E * sizeof(DenseEnsStatus), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (const auto &l : w->dn_class)
-          for (int e : l) w->dn_info[(size_t)e] = w->h_dn_status[e];
-      }
-    }
-    int nf = 0, first = -1, max_piv = 0;
-    for (int e = 0; e < E; ++e) {
-      const DenseEnsStatus &st = w->dn_info[(size_t)e];
-      if (!st.ok && first < 0) first = e;
-      nf += st.ok ? 0 : 1;
-      max_piv = std::max(max_piv, (int)st.pivots);
-      if (E > 1) { w->batch.h_ints.p[e] = st.pivots; w->batch.h_res.p[e] = std::numeric_limits<double>::quiet_NaN(); }
-    }
-    p->last_iterations = max_piv;
-    w->last_dense = true;
-    if (n_failed) *n_failed = nf;
-    if (nf > 0) {   // the reference Panics (ensembles.cc:531-534): no body is advanced
-      std::string msg = "ensemble " + std::to_string(first) + ": MixedConstraintsSolver did not reach a solution";
-      if (!big_msg.empty()) msg += " (" + big_msg + ")";
-      if (nf > 1) msg += "; " + std::to_string(nf) + " of " + std::to_string(E) + " ensembles failed";
-      return fail(w->ctx, EGS_ERR_LCP_FAILED, msg);
-    }
-    w->lambda_stale = false;   // every ensemble solved: x holds this step's lambda for the current list
-    if (p->m > 0) accumulators_from_lambda(p);                    // a = M^-1 J^T lambda
-    else zero_accumulators(p);
-    world_integrate(w, dt);
-    return EGS_OK;
-  });
+  return world_step_direct(w, dt, erp, nullptr, nullptr, cfm_coeff, use_bounds, detect_contacts, n_failed);
+}
+
+egs_status egs_world_step_dense_each(egs_world *w, int32_t n_ensembles, const double *dt, const double *erp,
+                                     double cfm_coeff, int32_t use_bounds, int32_t detect_contacts, int32_t *n_failed) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_failed) *n_failed = 0;
+  if (egs_status st = world_each_guard(w, n_ensembles, dt, erp, "the dense path is fp64 (the reference's is)")) return st;
+  if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
+  return world_step_direct(w, 0.0, 0.0, dt, erp, cfm_coeff, use_bounds, detect_contacts, n_failed);
 }
 
 egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm, int32_t *pivots,

@@ -787,6 +787,159 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
   StepPositions_ODE(dt, v, v_new);
 }
 
+// ---- EnsembleGroup: the frame (model.cc:37-70) through one batched world ------------------------------------------
+EnsembleGroup::EnsembleGroup(std::vector<Ensemble *> members) : members_(std::move(members)) {
+  if (members_.empty()) throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: no members");
+  const Ensemble *first = members_[0];
+  for (size_t i = 0; i < members_.size(); ++i) {
+    const Ensemble *m = members_[i];
+    const std::string who = "EnsembleGroup: member " + std::to_string(i);
+    if (!m) throw egs::Error(EGS_ERR_INVALID, who + " is a null pointer");
+    for (size_t k = 0; k < i; ++k)
+      if (members_[k] == m) throw egs::Error(EGS_ERR_INVALID, who + " is member " + std::to_string(k) + " again");
+    const egs_solve_params &a = first->solver_params, &b = m->solver_params;
+    if (a.method != b.method || a.max_iters != b.max_iters || a.check_every != b.check_every || a.omega != b.omega ||
+        a.cfm != b.cfm || a.tol != b.tol)
+      throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in solver_params");
+    if (m->cfm_coeff != first->cfm_coeff) throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in cfm_coeff");
+    if (m->use_dense_solver != first->use_dense_solver)
+      throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in use_dense_solver");
+    if (m->detect_contacts != first->detect_contacts)
+      throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in detect_contacts");
+    int32_t kind = 0;
+    double data[7];
+    for (size_t j = 0; j < m->joints_.size(); ++j)
+      if (!m->joints_[j]->Describe(&kind, data))
+        throw egs::Error(EGS_ERR_INVALID, who + ": joint " + std::to_string(j) + " cannot describe itself to the device");
+    if (!m->detect_contacts && !m->contacts_.empty())
+      throw egs::Error(EGS_ERR_INVALID, who + " carries caller-supplied contacts (detect_contacts = false)");
+  }
+}
+
+EnsembleGroup::~EnsembleGroup() {
+  if (world_) egs_world_destroy(world_);
+}
+
+int EnsembleGroup::world_ensembles() const {
+  const int32_t E = (int32_t)members_.size();
+  return world_ && egs_world_batch_info(world_, E, nullptr, nullptr, nullptr, nullptr) == EGS_OK ? E : 0;
+}
+
+void EnsembleGroup::Step(double dt) { Step(std::vector<double>(members_.size(), dt)); }
+
+void EnsembleGroup::Step(const std::vector<double> &dt) {
+  const size_t E = members_.size();
+  if (dt.size() != E)
+    throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup::Step: " + std::to_string(dt.size()) + " time steps for " +
+                                          std::to_string(E) + " members");
+  egs_context *ctx = egs::DefaultContext();
+  const bool first = !world_;
+  if (first) {
+    std::vector<int32_t> nb(E);
+    for (size_t i = 0; i < E; ++i) nb[i] = members_[i]->n_;
+    off_.assign(E + 1, 0);
+    egs::check(egs_world_create_batch(ctx, (int32_t)E, nb.data(), EGS_F64, &world_, off_.data()));
+    ++worlds_created_;
+    joints_sent_ = false;
+  }
+  const size_t n = (size_t)off_[E];
+  std::vector<double> pos(n * 3), R(n * 9), vl(n * 3), w(n * 3), Minv(first ? n * 36 : 0), side(first ? n * 3 : 0),
+      fext(first ? n * 6 : 0);
+  std::vector<int32_t> jb0, jb1;
+  std::vector<double> jdata;
+  for (size_t i = 0; i < E; ++i) {
+    const Ensemble *m = members_[i];
+    const size_t o = (size_t)off_[i];
+    if (m->n_ != off_[i + 1] - off_[i])
+      throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " changed its number of bodies");
+    for (int b = 0; b < m->n_; ++b) {
+      const Body &body = *m->components_[b];
+      const size_t g = o + (size_t)b;
+      for (int k = 0; k < 3; ++k) {
+        pos[3 * g + k] = body.p()[k]; vl[3 * g + k] = body.v()[k]; w[3 * g + k] = body.w_g()[k];
+      }
+      for (int k = 0; k < 9; ++k) R[9 * g + k] = body.R().d[k];
+      if (!first) continue;
+      const Vector3d sl = body.GetSideLengths();
+      for (int k = 0; k < 3; ++k) side[3 * g + k] = sl[k];
+      for (int k = 0; k < 6; ++k) fext[6 * g + k] = m->external_force_torque_(6 * b + k);
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) Minv[g * 36 + 6 * r + c] = m->M_inverse_(6 * b + r, 6 * b + c);
+    }
+    for (size_t j = 0; j < m->joints_.size(); ++j) {   // the world's joints: member by member, global body indices
+      int32_t kind = 0;
+      double d[7];
+      if (!m->joints_[j]->Describe(&kind, d))
+        throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + ": joint " + std::to_string(j) +
+                                              " cannot describe itself to the device");
+      const int a = m->joints_[j]->i0_, b = m->joints_[j]->i1_;
+      jb0.push_back(a >= 0 ? a + (int32_t)o : -1);
+      jb1.push_back(b >= 0 ? b + (int32_t)o : -1);
+      jdata.insert(jdata.end(), d, d + 7);
+    }
+  }
+  // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once
+  egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
+                                  first ? fext.data() : nullptr, first ? side.data() : nullptr));
+  if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {   // re-sent when edited
+    egs::check(egs_world_set_joints(world_, (int32_t)jb0.size(), jb0.data(), jb1.data(), jdata.data()));
+    joints_sent_ = true;
+    world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata;
+  }
+  const Ensemble *lead = members_[0];
+  const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
+  if (lead->use_dense_solver) {
+    egs::check(egs_world_step_dense_each(world_, (int32_t)E, dt.data(), erp.data(), lead->cfm_coeff, /*use_bounds=*/0,
+                                         lead->detect_contacts ? 1 : 0, nullptr));
+  } else {
+    egs_solve_params prm = lead->solver_params;
+    prm.cfm = lead->cfm_coeff;
+    egs_solve_stats st;
+    egs::check(egs_world_step_each(world_, (int32_t)E, dt.data(), erp.data(), &prm, lead->detect_contacts ? 1 : 0, &st));
+  }
+  egs::check(egs_world_get_bodies(world_, pos.data(), R.data(), vl.data(), w.data()));
+  int32_t mcons = 0, mc = 0, replans = 0;
+  egs::check(egs_world_info(world_, &mcons, &mc, &replans));
+  std::vector<int32_t> jo(E + 1), co(E + 1), cb0((size_t)mc), cb1((size_t)mc);
+  std::vector<double> cdata((size_t)mc * 7), lambda((size_t)mcons * 3);
+  egs::check(egs_world_batch_info(world_, (int32_t)E, jo.data(), co.data(), nullptr, nullptr));
+  if (mc > 0) {
+    int32_t got = 0;
+    egs::check(egs_world_get_contacts(world_, mc, &got, cb0.data(), cb1.data(), cdata.data()));
+  }
+  if (mcons > 0) {
+    int32_t rows = 0;
+    egs::check(egs_world_get_lambda(world_, 3 * mcons, &rows, lambda.data()));
+  }
+  const int mj = jo[E];
+  for (size_t i = 0; i < E; ++i) {
+    Ensemble *m = members_[i];
+    if (dt[i] == 0) continue;   // sat out: its bodies, contacts and last_lambda stay as they are
+    const int o = off_[i];
+    for (int b = 0; b < m->n_; ++b) {
+      const size_t g = (size_t)(o + b);
+      m->components_[b]->SetP(Vector3d(pos[3 * g], pos[3 * g + 1], pos[3 * g + 2]));
+      m->components_[b]->SetV(Vector3d(vl[3 * g], vl[3 * g + 1], vl[3 * g + 2]));
+      m->components_[b]->SetW_GlobalFrame(Vector3d(w[3 * g], w[3 * g + 1], w[3 * g + 2]));
+      Matrix3d Rm;
+      for (int k = 0; k < 9; ++k) Rm.d[k] = R[9 * g + k];
+      m->components_[b]->SetR(Rm);
+    }
+    m->contacts_.clear();   // the member's slice of the contact list the step used, in its own numbering
+    for (int k = co[i]; k < co[i + 1]; ++k) {
+      const double *d = &cdata[(size_t)k * 7];
+      const ContactGeometry cg(Vector3d(d[0], d[1], d[2]), Vector3d(d[3], d[4], d[5]), d[6]);
+      const int a = cb0[k] >= 0 ? cb0[k] - o : -1, b = cb1[k] - o;
+      if (a < 0) m->contacts_.push_back(std::make_shared<Contact>(m->components_[b], b, cg));
+      else m->contacts_.push_back(std::make_shared<Contact>(m->components_[a], a, m->components_[b], b, cg));
+    }
+    const int rj = 3 * (jo[i + 1] - jo[i]), rc = 3 * (co[i + 1] - co[i]);   // its joints' rows, then its contacts'
+    m->last_lambda.resize(rj + rc);
+    for (int r = 0; r < rj; ++r) m->last_lambda(r) = lambda[(size_t)(3 * jo[i] + r)];
+    for (int r = 0; r < rc; ++r) m->last_lambda(rj + r) = lambda[(size_t)(3 * (mj + co[i]) + r)];
+  }
+}
+
 Chain::Chain(int num_links, const Vector3d &anchor) {  // ensembles.cc:668-707
   if (num_links <= 0) throw egs::Error(EGS_ERR_INVALID, "num_links > 0");
   n_ = num_links;

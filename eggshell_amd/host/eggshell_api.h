@@ -317,6 +317,7 @@ class Ensemble {  // ensembles.h:25-186
   VectorXd external_force_torque_;
 
  private:
+  friend class EnsembleGroup;
   void ConstructMassInertiaMatrixInverse();                              // ensembles.cc:202-212
   void InitializeExternalForceTorqueVector();                            // ensembles.cc:214-222
   ConstraintsList CombineConstraintsLists() const;                       // ensembles.cc:234-239
@@ -358,6 +359,41 @@ class Cairn : public Ensemble {
  private:
   const double max_init_v_ = 1;
   const double max_init_w_ = 1;
+};
+
+// The frame of model.cc:37-70 -- SimulationStep() calls Step() on every Ensemble in turn -- as ONE batched device world
+// (egs_world_create_batch): Step does for every member what Ensemble::Step does for one on the device, with member i
+// stepped by dt[i] (egs_world_step_each; egs_world_step_dense_each when the members have use_dense_solver set), erp 0.2
+// as in Ensemble::Step.  After it every member's Body objects, contacts and last_lambda hold, bit for bit, what the
+// member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
+// egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
+//   - The members must agree in solver_params, cfm_coeff, use_dense_solver and detect_contacts, and each must be able to
+//     take the device step (joints that Describe themselves, no caller-supplied contacts); the list may not be empty or
+//     hold a pointer twice: the constructor throws egs::Error(EGS_ERR_INVALID) naming the offending member.
+//   - The members are not owned and must outlive the group; Init() them before the first Step (M^-1, the external
+//     force and the box sizes are sent once, quirk Q5).  A member may still be stepped on its own between group steps:
+//     its Body objects are the interface, they are pushed before and pulled after every step.  Joints are re-sent
+//     when edited.
+class EnsembleGroup {
+ public:
+  explicit EnsembleGroup(std::vector<Ensemble *> members);
+  ~EnsembleGroup();
+  EnsembleGroup(const EnsembleGroup &) = delete;
+  EnsembleGroup &operator=(const EnsembleGroup &) = delete;
+  void Step(const std::vector<double> &dt);   // dt[i] = 0: member i sits out; Integrator::OPEN_DYNAMICS_ENGINE
+  void Step(double dt);                       // every member
+  // how many ensembles the group's device world holds (0 before the first Step) and how many worlds it has made
+  int world_ensembles() const;
+  int worlds_created() const { return worlds_created_; }
+
+ private:
+  std::vector<Ensemble *> members_;
+  std::vector<int32_t> off_;                  // [E + 1] member i's bodies in the world
+  egs_world *world_ = nullptr;
+  int worlds_created_ = 0;
+  bool joints_sent_ = false;
+  std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds
+  std::vector<double> world_jdata_;
 };
 
 #endif

@@ -468,6 +468,36 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
 egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm,
                                 int32_t *pivots, int32_t *ok);
 
+/* ---- a time step and an erp per ensemble -----------------------------------------------------------------------
+ * The reference's frame steps its ensembles at different rates (model.cc:80, 108: the cairn with kSimTimeStep*5,
+ * the chain with kSimTimeStep).  egs_world_step_each is egs_world_step with ensemble e stepped by dt[e] with
+ * erp[e]; egs_world_step_dense_each is egs_world_step_dense likewise.  n_ensembles must be the world's (a plain
+ * world is one ensemble).  dt[e] > 0: the ensemble takes its Ensemble::Step(dt[e]).  dt[e] == 0: the ensemble sits
+ * this step out.  dt[e] < 0 or NaN, dt or erp NULL, wrong n_ensembles: EGS_ERR_INVALID and nothing moved.  All
+ * dt[e] == 0 is valid (nothing moves).  After the call every ensemble holds, bit for bit, what a world holding only
+ * it holds after the same call with that ensemble's dt and erp.
+ *   - An ensemble with dt[e] > 0: assembly, rhs (ensembles.cc:569-570), velocity update (:535, :572) and
+ *     StepPositions_ODE (:577-591) use dt[e] and erp[e] in the expressions, and in the order, of the scalar entries:
+ *     -erp / dt / dt, vel / dt + Wf, v + dt * (...), rotate by |w| dt.
+ *   - An ensemble with dt[e] == 0: its bodies (pos, R, v, w) are not touched, bit for bit (they are skipped, not
+ *     multiplied by zero).  Contact detection still runs over the whole world; it is a function of the poses alone,
+ *     so this ensemble's list comes out as it was.  Its rhs rows are exactly 0 (not computed through 1/dt), hence
+ *     its rows of egs_world_get_lambda are 0.  egs_world_batch_info reports residual 0 for it and, with tol > 0,
+ *     iterations 0; with a fixed sweep count it reports max_iters, as for every ensemble.  On the dense path it is
+ *     not solved: ok = 1, pivots = 0, condition 1, cfm 0 (batch_info's residual is NaN there, as for every
+ *     ensemble after a dense step).  A failure of another ensemble on the dense path still advances no body.
+ *   - All dt[e] equal and all erp[e] equal: the world is left bit-identical to what the scalar entry with that dt
+ *     and erp leaves, egs_world_batch_info and egs_solve_stats included.
+ *   - Everything else -- the stopping rule per ensemble, re-planning only on a topology change, get_lambda after a
+ *     stabilise call, stall handling, fp32 worlds on the sweeps and fp64 only on the dense path -- is as in the
+ *     scalar entries.  The _each forms may alternate freely with the scalar forms, with egs_world_stabilize* and
+ *     with each other on one world; none of that re-plans.  The 2 E rates reach the device without a stream
+ *     synchronisation, and only when they differ from the last call's.                                            */
+egs_status egs_world_step_each(egs_world *w, int32_t n_ensembles, const double *dt, const double *erp,
+                               const egs_solve_params *params, int32_t detect_contacts, egs_solve_stats *stats);
+egs_status egs_world_step_dense_each(egs_world *w, int32_t n_ensembles, const double *dt, const double *erp,
+                                     double cfm_coeff, int32_t use_bounds, int32_t detect_contacts, int32_t *n_failed);
+
 /* Ensemble::InitStabilize (mode EGS_STABILIZE_INIT, ensembles.cc:602-622) or Ensemble::PostStabilize(max_steps)
  * (EGS_STABILIZE_POST, ensembles.cc:624-646) for every ensemble of a world (plain or batched).  Per ensemble, on its
  * own constraint list in the reference's order (its joints, then its contacts): err_sq = sum err_i^2; while

@@ -9,7 +9,14 @@ phase, re-plan included, printed by egs_world_destroy).
 
 --pile 16 16 4 --ensembles 4 is the other shape: a few large ensembles, where every (ensemble, recorded sweep) of the
 segmented residual is one workgroup walking the ensemble's whole row set.  Under rocprofv3 --kernel-trace --stats it
-compares seg_residual_kernel with the separate worlds' hist_residual_kernel."""
+compares seg_residual_kernel with the separate worlds' hist_residual_kernel.
+
+  python tools/gpu_time_world_batch.py --each [--repeats 7] [--lib PATH/libeggshell_amd.so]
+
+times the batched world alone, co-located and spaced: egs_world_step against egs_world_step_each with equal rates (the
+same dt and erp for every ensemble: the same trajectory, bit for bit), each sample on a fresh world over the same
+steps, the two entries in turn; the median and the range of the samples.  --lib loads another build of the library
+(one without egs_world_step_each is timed on egs_world_step alone): the yardstick of a comparison across commits."""
 import argparse
 import os
 import sys
@@ -50,6 +57,38 @@ def timed(ctx, worlds, prm, warmup, steps):
     return ms / steps, sum(w.info()["replans"] for w in worlds) - r0
 
 
+def timed_entry(ctx, w, prm, warmup, steps, each):
+    E = w.n_ensembles
+    dt, erp = np.full(E, DT), np.full(E, ERP)
+    step = (lambda: w.step_each(dt, erp, prm)) if each else (lambda: w.step(DT, ERP, prm))
+    for _ in range(warmup):
+        step()
+    ctx.synchronize()
+    ctx.timer_start()
+    for _ in range(steps):
+        step()
+    return ctx.timer_stop() / steps
+
+
+def each_mode(ctx, a, prm):
+    have_each = hasattr(capi.load(), "egs_world_step_each")
+    for E in a.ensembles:
+        for spaced in (True, False):
+            ens = piles(E, spaced, a.pile)
+            samples = {False: [], True: []}
+            for _ in range(a.repeats):
+                for each in ((False, True) if have_each else (False,)):
+                    w = batched(ctx, ens)
+                    samples[each].append(timed_entry(ctx, w, prm, a.warmup, a.steps, each))
+                    w.close()
+            for each, name in ((False, "egs_world_step"), (True, "egs_world_step_each")):
+                t = np.array(samples[each])
+                if t.size:
+                    print("%dx%dx%d E=%4d %-10s %-20s median %8.3f ms/frame  min %8.3f  max %8.3f  (%d samples: %s)" %
+                          (*a.pile, E, "spaced" if spaced else "co-located", name, np.median(t), t.min(), t.max(), t.size,
+                           " ".join("%.3f" % x for x in t)), flush=True)
+
+
 def batched(ctx, ens):
     w, _ = capi.World.batch(ctx, [sc["p"].shape[0] for sc, _, _ in ens])
     cat = lambda k: np.concatenate([sc[k] for sc, _, _ in ens])
@@ -64,9 +103,18 @@ def main():
     ap.add_argument("--pile", type=int, nargs=3, default=[4, 4, 4], metavar=("NX", "NY", "NZ"))
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--each", action="store_true", help="egs_world_step against egs_world_step_each with equal rates")
+    ap.add_argument("--repeats", type=int, default=7, help="--each: samples per entry, each on a fresh world")
+    ap.add_argument("--lib", help="--each: another build of libeggshell_amd.so")
     a = ap.parse_args()
     prm = capi.params(method=capi.SOR, max_iters=500, tol=1e-9, cfm=0.01)
+    if a.lib:
+        capi.LIB_PATH = os.path.abspath(a.lib)
     ctx = capi.Context(0)
+    if a.each:
+        each_mode(ctx, a, prm)
+        ctx.close()
+        return
     for E in a.ensembles:
         for spaced in (True, False):
             ens = piles(E, spaced, a.pile)
