@@ -13,17 +13,22 @@ pytestmark = pytest.mark.gpu
 
 def reference_contacts(p, R, side=0.3):
     """Ensemble::UpdateContacts (ensembles.cc:445-480) then the contact-vs-contact
-    pruning of CheckAndCorrectEnsembleState (ensembles.cc:308-328) via the oracle."""
+    pruning of CheckAndCorrectEnsembleState (ensembles.cc:308-328) via the oracle.
+    side: one length for cubes, or [n][3].  All pairs, except those whose bounding
+    spheres are apart (these are separated, the oracle would return nothing)."""
     n = p.shape[0]
+    side = np.asarray(side, dtype=np.float64)
+    side = np.full((n, 3), float(side)) if side.ndim == 0 else side.reshape(n, 3)
+    reach = 0.5 * np.linalg.norm(side, axis=1)
     b0, b1, data = [], [], []
     for b in range(n):
-        for c in orc.collide_box_ground(p[b], R[b]):
+        for c in orc.collide_box_ground(p[b], R[b], side[b]):
             b0.append(-1); b1.append(b); data.append(c)
     for i in range(n):
         for j in range(i + 1, n):
-            if np.linalg.norm(p[i] - p[j]) > 0.53:
+            if np.linalg.norm(p[i] - p[j]) > (reach[i] + reach[j]) * (1 + 1e-9):
                 continue
-            cs, code = orc.collide_boxes(p[i], R[i], p[j], R[j])
+            cs, code = orc.collide_boxes(p[i], R[i], p[j], R[j], side[i], side[j])
             keep = []
             for a in range(len(cs)):
                 if not any(np.linalg.norm(cs[b][:3] - cs[a][:3]) < 1e-6 for b in range(a)):

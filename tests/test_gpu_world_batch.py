@@ -63,7 +63,7 @@ def mixed_batch():
 def single_world(ctx, e, precision):
     n = e["p"].shape[0]
     w = capi.World(ctx, n, precision)
-    w.set_bodies(e["p"], e["R"], e["v"], e["w"], e["Minv"], e["f_ext"])
+    w.set_bodies(e["p"], e["R"], e["v"], e["w"], e["Minv"], e["f_ext"], side=e.get("side"))
     if e["joints"] is not None:
         w.set_joints(*e["joints"])
     return w
@@ -72,7 +72,10 @@ def single_world(ctx, e, precision):
 def batch_world(ctx, ens, precision):
     w, off = capi.World.batch(ctx, [e["p"].shape[0] for e in ens], precision)
     cat = lambda k, d: np.concatenate([e[k].reshape(-1, d) for e in ens]) if off[-1] else np.zeros((0, d))
-    w.set_bodies(cat("p", 3), cat("R", 9), cat("v", 3), cat("w", 3), cat("Minv", 36), cat("f_ext", 6))
+    side = None
+    if any(e.get("side") is not None for e in ens):   # an ensemble without side lengths of its own: cubes of 0.3
+        side = np.concatenate([np.full((e["p"].shape[0], 3), 0.3) if e.get("side") is None else e["side"] for e in ens])
+    w.set_bodies(cat("p", 3), cat("R", 9), cat("v", 3), cat("w", 3), cat("Minv", 36), cat("f_ext", 6), side=side)
     b0, b1, data = [], [], []
     for e, o in zip(ens, off):
         if e["joints"] is not None:
