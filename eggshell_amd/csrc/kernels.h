@@ -61,6 +61,8 @@ struct SolveArgs {
   int iso = 0;              // 1: every M^-1 block is diag(a,a,a,b,b,b): B is formed on the fly (tile kernel)
   int linsym = 0;           // 1 (with iso, fp64, GROUP = 1): J1_lin = -J0_lin and wl0 = wl1 bit for bit on every
                             // two-body constraint: step_solve_kernel keeps one linear block (step_solve.hip: LINSYM)
+  int steady = 0;           // 1: step_solve_kernel (GROUP = 1, no snapshots) runs the steady-state loop between the
+                            // fill and the drain of its timetable (step_solve.hip)
   // step_solve_kernel's ASSEMBLE form (launch_step_solve_assemble): every lane assembles its constraint from this
   // body state in the prologue and also leaves the blocks where assemble_kernel would (J0 .. is_eq above point there)
   AssembleArgs assemble{};

@@ -22,6 +22,7 @@ struct SweepSchedule {
   bool linsym = false;      // step_solve_kernel's LINSYM form
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
+  int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
   int oversize = -1;        // OversizeSchedule of the launch's oversize islands, -1: it has none
   // the bits of the kernels that ran (egs_schedule_flags); fill_stats adds those of the problem's plans
   uint32_t flags() const {
@@ -40,6 +41,9 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   const char *se = std::getenv("EGS_STEP");   // 0 / 1: tickets / the timetable wherever the plan has levels
   s.timetable = method != EGS_JACOBI && pl.levels_ok && pl.n_tiles > 0 && (se ? std::atoi(se) != 0 : timetable_pays(pl, sweeps));
   if (s.quad) return s;
+  // the timetable kernel's steady-state loop, on wherever the kernel has it; EGS_STEP_STEADY=0 keeps the general loop
+  const char *ye = std::getenv("EGS_STEP_STEADY");
+  s.steady = s.timetable && !(ye && std::atoi(ye) == 0);
   if (!pl.global.empty()) s.oversize = method == EGS_JACOBI ? kAllGlobal : p->oversize;
   if (pl.n_tiles > 0 && p->minv_iso && pl.block == 256) {
     const char *ie = std::getenv("EGS_ISO");   // 2: the variant wherever the bodies allow it (experiments)
@@ -134,6 +138,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     a.max_slots = pl.max_slots;
     a.iso = sc.iso;
     a.linsym = sc.linsym;
+    a.steady = sc.steady;
     if (sc.quad) launch_cons_prepare<REAL>(a, ctx->stream);
     if (sc.timetable) {
       a.lane_level = dp.lane_level.p; a.tile_period = dp.tile_period.p; a.tile_depth = dp.tile_depth.p;

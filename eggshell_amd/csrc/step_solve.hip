@@ -38,6 +38,15 @@
 // solve (get_blocks, the residual, matvec, later solves).  Nothing waits for these stores: they drain while the
 // timetable runs.  Every constraint of the problem is a lane of some tile (solve.cpp: no oversize islands), so all of
 // them are written.
+// The steady-state loop (GROUP == 1, no snapshots, LINSYM or not ISO): between the first depth steps of a launch (the
+// fill: lanes still wait for their first turn, or run the accumulation) and its last ones (the drain: lanes have run
+// out of sweeps) every lane whose level matches the clock modulo P is due, in some sweep 1 .. sweeps.  There the
+// kernel walks a second loop without the per-lane timetable: the clock, its phase t mod P and the loop bounds are
+// scalar, a lane compares its phase with the clock's, and `due`, `sweep`, the accumulation branch and the history
+// test are gone from the pass.  The bounds are the same for every lane of the workgroup (the tile's depth and period,
+// the launch's sweeps): every wavefront meets the same barriers as in the single loop.  SolveArgs::steady = 0 (solve.cpp:
+// EGS_STEP_STEADY=0) keeps the single loop.  The arithmetic of an update is the same code: the same bits.
+//
 // STORE_SYSTEM = false: none of that is stored -- a step reads none of it (the sweeps run from registers) -- and the
 // problem remembers that its system is not materialised (problem.h: ensure_system runs assemble_kernel on demand).
 #include <algorithm>
@@ -218,49 +227,108 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   const int t0 = (METHOD == 2 && !resume) ? depth : 0;       // backward sweeps start after the forward accumulation
   int due = (METHOD == 2 && resume) ? depth - 1 - level : level;
   if (!active || sweep > A.sweeps) due = 0x7fffffff;
-  for (int t = 0; t < t_end; ++t) {
-    if (due == t) {
-      REAL a0[6], a1[6];
-      load12(ac0, ac1, a0, a1);
-      REAL dx[3] = {REAL(0), REAL(0), REAL(0)};
-      if (sweep == 0) {
+  // The steady window [t_s, t_e) (GROUP == 1, no snapshots; A.steady): with b = the step of the lane's first update on
+  // the sweeps' grid (forward: level, the accumulation being update 0 of a fresh solve; backward: t0 + depth - 1 -
+  // level) a lane is due at b + P k.  From t_s on every lane has b <= t, and on a fresh forward solve b + P <= t: the
+  // accumulation is behind it; before t_e = t0 + P * (updates on the grid) even a lane with b = t0 + (t mod P), the
+  // smallest b a tile can hold, has an update left, so a tile whose first level is not 0 only ends its sweeps later.
+  // In between, the due lanes are exactly the active ones with b = t (mod P), all in a sweep 1 .. A.sweeps.  The
+  // bounds come from the tile's depth and period and the launch's sweeps alone: every wavefront of the workgroup
+  // meets the same t_end barriers.
+  // The isotropic kernels without LINSYM sit at their register limit (168 / 128 VGPRs): a second loop would spill.
+  constexpr bool STEADY = GROUP == 1 && (LINSYM || !ISO);
+  const int grid_acc = (METHOD == 1 && !resume) ? 1 : 0;
+  int t_s = 0, t_e = 0, Ps = 1;
+  if constexpr (STEADY) {
+    // workgroup-uniform by construction; said so, the clock and its bounds live in scalar registers
+    t_end = __builtin_amdgcn_readfirstlane(t_end);
+    Ps = __builtin_amdgcn_readfirstlane(P);
+    if (A.steady && !hist && Ps > 0) {
+      const int ds = __builtin_amdgcn_readfirstlane(depth), t0s = (METHOD == 2 && !resume) ? ds : 0;
+      t_s = grid_acc ? ds : t0s + ds - 1;
+      t_e = min(t0s + Ps * (A.sweeps + grid_acc), t_end);
+      if (t_e <= t_s) t_s = t_e = 0;   // an empty window: the general loop alone
+    }
+  }
+  int t = 0, stop = t_e > t_s ? t_s : t_end;
+  for (;;) {
+    for (; t < stop; ++t) {
+      if (due == t) {
+        REAL a0[6], a1[6];
+        load12(ac0, ac1, a0, a1);
+        REAL dx[3] = {REAL(0), REAL(0), REAL(0)};
+        if (sweep == 0) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) dx[r] = x[r];
-      } else {
-        REAL res[3];
+          for (int r = 0; r < 3; ++r) dx[r] = x[r];
+        } else {
+          REAL res[3];
+          if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
+          else row_residuals(c, a0, a1, x, A.cfm, res);
+          update_rows<REAL, METHOD>(c, res, x, dx);
+        }
+        if (LINSYM) {
+          // opaque to the optimiser in place: the products wa J stay in the update (not hoisted into 36 registers)
+          asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
+          if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
+          if (has1) { linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx); store6(ac1, a1); }
+        } else {
+          if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
+          if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
+        }
+        if (hist && sweep >= 1) {
+          REAL *hx = A.hist_x + ((size_t)(sweep - 1) * A.m + d.cidx) * 3;
+          hx[0] = x[0]; hx[1] = x[1]; hx[2] = x[2];
+          if (has0 && last0) {
+            REAL *ha = A.hist_acc + ((size_t)(sweep - 1) * A.n_bodies + slot_body[slot0]) * 6;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) ha[k] = a0[k];
+          }
+          if (has1 && last1) {
+            REAL *ha = A.hist_acc + ((size_t)(sweep - 1) * A.n_bodies + slot_body[slot1]) * 6;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) ha[k] = a1[k];
+          }
+        }
+        // next: the first backward sweep starts at t0 and runs the list from its end
+        due = (METHOD == 2 && sweep == 0) ? t0 + (depth - 1 - level) : due + P;
+        if (++sweep > A.sweeps) due = 0x7fffffff;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wavefront's accumulator stores have landed
+      __builtin_amdgcn_s_barrier();
+    }
+    if (!STEADY || t >= t_end) break;
+    // steady: one compare of the lane's phase with the clock's (scalar), no `due`, no `sweep`, no accumulation branch
+    const int b = (METHOD == 2) ? t0 + depth - 1 - level : level;
+    const int phase = active ? b % Ps : -1;
+    int tp = t % Ps;
+    for (; t < t_e; ++t) {
+      if (phase == tp) {
+        REAL a0[6], a1[6], res[3], dx[3];
+        load12(ac0, ac1, a0, a1);
         if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
         else row_residuals(c, a0, a1, x, A.cfm, res);
         update_rows<REAL, METHOD>(c, res, x, dx);
-      }
-      if (LINSYM) {
-        // opaque to the optimiser in place: the products wa J stay in the update (not hoisted into 36 registers)
-        asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
-        if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
-        if (has1) { linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx); store6(ac1, a1); }
-      } else {
-        if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
-        if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
-      }
-      if (hist && sweep >= 1) {
-        REAL *hx = A.hist_x + ((size_t)(sweep - 1) * A.m + d.cidx) * 3;
-        hx[0] = x[0]; hx[1] = x[1]; hx[2] = x[2];
-        if (has0 && last0) {
-          REAL *ha = A.hist_acc + ((size_t)(sweep - 1) * A.n_bodies + slot_body[slot0]) * 6;
-#pragma unroll
-          for (int k = 0; k < 6; ++k) ha[k] = a0[k];
-        }
-        if (has1 && last1) {
-          REAL *ha = A.hist_acc + ((size_t)(sweep - 1) * A.n_bodies + slot_body[slot1]) * 6;
-#pragma unroll
-          for (int k = 0; k < 6; ++k) ha[k] = a1[k];
+        if (LINSYM) {
+          asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
+          if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
+          linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx);   // every active lane has side 1 (solve.cpp)
+          store6(ac1, a1);
+        } else {
+          if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
+          if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
         }
       }
-      // next: the first backward sweep starts at t0 and runs the list from its end
-      due = (METHOD == 2 && sweep == 0) ? t0 + (depth - 1 - level) : due + P;
-      if (++sweep > A.sweeps) due = 0x7fffffff;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      tp = tp + 1 == Ps ? 0 : tp + 1;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wavefront's accumulator stores have landed
-    __builtin_amdgcn_s_barrier();
+    // drain: the lane's next update at or after t_e, from its level (read again: not held through the window)
+    const int lv = A.lane_level[(size_t)tile * BLOCK + tid];
+    const int bd = (METHOD == 2) ? t0 + depth - 1 - lv : lv;
+    const int k = t_e > bd ? (t_e - bd + Ps - 1) / Ps : 0;
+    sweep = k + 1 - grid_acc;
+    due = (!active || sweep > A.sweeps) ? 0x7fffffff : bd + P * k;
+    stop = t_end;
   }
 
   // epilogue: lambda, w = A x - rhs, accumulators
