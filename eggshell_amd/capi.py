@@ -22,6 +22,8 @@ SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL,
 SCHED_LINSYM = 128
 SCHED_FUSED_ASSEMBLY = 256
 SCHED_DEFERRED_SYSTEM = 512
+SCHED_START = 1024
+START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
 # every symbol include/eggshell_amd.h declares
@@ -44,6 +46,7 @@ EXPORTS = [
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
     "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
     "egs_world_step_each", "egs_world_step_dense_each",
+    "egs_problem_set_start", "egs_match_contacts", "egs_world_set_warm_start", "egs_world_get_start",
 ]
 
 
@@ -287,6 +290,24 @@ class Context:
         self.check(load().egs_update_contacts(self.h, C.c_int32(n), _p(pos), _p(R), _p(side), C.c_int32(cap),
                                               C.byref(m), _p(b0), _p(b1), _p(data)))
         return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
+
+    def match_contacts(self, old_b0, old_b1, old_pos, old_lambda, old_off, valid, new_b0, new_b1, new_pos, new_rhs,
+                       new_off, radius):
+        """The start of a solve from the previous contact list's lambda (egs_match_contacts): x0 [3 m_new] and the old
+        index each new contact took its rows from (-1: none within the radius, x0 = 0; -2: its ensemble has no
+        history, x0 = rhs)."""
+        ob0, ob1, ooff, nb0, nb1, noff = map(_i32, (old_b0, old_b1, old_off, new_b0, new_b1, new_off))
+        opos, olam, npos, nrhs = map(_f64, (old_pos, old_lambda, new_pos, new_rhs))
+        valid = _u8(valid)
+        mo, mn = ob0.shape[0], nb0.shape[0]
+        if opos.size != 3 * mo or olam.size != 3 * mo or npos.size != 3 * mn or nrhs.size != 3 * mn or \
+                ooff.shape[0] != valid.shape[0] + 1 or noff.shape[0] != valid.shape[0] + 1:
+            raise ValueError("arrays do not match the list sizes")
+        x0 = np.zeros(3 * mn); src = np.zeros(mn, np.int32)
+        self.check(load().egs_match_contacts(self.h, C.c_int32(valid.shape[0]), C.c_int32(mo), _p(ob0), _p(ob1), _p(opos),
+                                             _p(olam), _p(ooff), _p(valid), C.c_int32(mn), _p(nb0), _p(nb1), _p(npos),
+                                             _p(nrhs), _p(noff), C.c_double(radius), _p(x0), _p(src)))
+        return x0, src
 
     def relax_blocks_direct(self, n_bodies, body0, body1, J0, J1, err, rank_tol=0.0):
         """(J J^T) y = err by the rank-revealing LDL^T of the direct relaxation route (egs_relax_blocks_direct):
@@ -555,6 +576,14 @@ class Problem:
         sw = C.c_int32(0)
         self.ctx.check(load().egs_problem_debug_trace(self.h, _p(buf), C.c_int64(buf.shape[0]), C.byref(sw)))
         return buf[:sw.value * self.m].reshape(sw.value, self.m)
+
+    def set_start(self, mode, x0=None):
+        """Where the following solves start (egs_problem_set_start): START_RHS (the reference, the default),
+        START_GIVEN with the 3m rows of x0, START_PREVIOUS (the last solve's lambda).  Sticky until changed."""
+        x0 = _f64(x0)
+        if x0 is not None and x0.size != 3 * self.m:
+            raise ValueError("x0: %d rows for %d constraints" % (x0.size, self.m))
+        self.ctx.check(load().egs_problem_set_start(self.h, C.c_int32(mode), _p(x0)))
 
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
@@ -845,6 +874,19 @@ class World:
         b0 = np.zeros(m, np.int32); b1 = np.zeros(m, np.int32); data = np.zeros((m, 7)); mo = C.c_int32(0)
         self.ctx.check(load().egs_world_get_contacts(self.h, C.c_int32(m), C.byref(mo), _p(b0), _p(b1), _p(data)))
         return b0, b1, data
+
+    def set_warm_start(self, enable, match_radius=0.01):
+        """Sweep steps start from the previous step's lambda (egs_world_set_warm_start): a contact takes the rows of the
+        nearest previous contact of its body pair within match_radius (metres, world frame), a joint its own."""
+        self.ctx.check(load().egs_world_set_warm_start(self.h, C.c_int32(1 if enable else 0), C.c_double(match_radius)))
+
+    def start(self):
+        """x0 [3m] and source [m] of the last warm-started step (egs_world_get_start): per constraint the previous
+        contact (joint) index its rows came from, -1: none within the radius (x0 = 0), -2: no history (x0 = rhs)."""
+        m = self.info()["n_constraints"]
+        x0 = np.zeros(3 * m); src = np.zeros(m, np.int32); ro = C.c_int32(0)
+        self.ctx.check(load().egs_world_get_start(self.h, C.c_int32(3 * m), C.byref(ro), _p(x0), _p(src)))
+        return x0, src
 
     def lambda_(self):
         rows = 3 * self.info()["n_constraints"]

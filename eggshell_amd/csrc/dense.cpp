@@ -191,6 +191,7 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
     if (!good) return fail(ctx, EGS_ERR_LCP_FAILED, msg.empty() ? "MixedConstraintsSolver did not reach a solution" : msg);
     if (ok) *ok = 1;
     p->last_iterations = piv;
+    p->have_lambda = true;
     accumulators_from_lambda(p);                              // a = M^-1 J^T lambda
     do_velocity(p, dt);                                       // ensembles.cc:535, 572
     return EGS_OK;

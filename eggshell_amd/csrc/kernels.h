@@ -80,6 +80,9 @@ struct SolveArgs {
   uint32_t gran_epoch = 0;
   // diagnostics (EGS_TRACE_UPDATES=1): completion time (100 MHz wall clock) of every update of the 4-lane patch kernel
   unsigned long long *trace = nullptr;   // [sweeps][m]
+  // the start of a fresh launch (!resume), [3m]; NULL: rhs, Q7.  Never aliases x.  step_solve_kernel's ASSEMBLE form
+  // does not read it: a started step assembles with assemble_kernel (solve.cpp: choose_sweep)
+  const REAL *x0 = nullptr;
 };
 
 template <typename REAL>
@@ -101,6 +104,7 @@ struct GlobalArgs {
   // per-sweep snapshots for tolerance-terminated solves, as in SolveArgs (NULL = off)
   int32_t m = 0, pad1 = 0;     // all constraints of the problem (hist_x stride)
   REAL *hist_x = nullptr, *hist_acc = nullptr;
+  const REAL *x0 = nullptr;    // the start of a fresh launch, as in SolveArgs (NULL: rhs, Q7)
 };
 
 

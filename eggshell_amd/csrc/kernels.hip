@@ -104,10 +104,11 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
 
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
+  const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
     load_cons<REAL, ISO>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) x[r] = A.resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
+    for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
   __syncthreads();
 
@@ -596,7 +597,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
 // workgroups: sc1 (write-through) payload stores -> s_waitcnt vmcnt(0) -> sc1
 // ticket store; sc1 ticket poll -> sc1 payload loads, all by the same lane.
 // Every wait is bounded.
-// B = W J^T, D, den per global constraint; x0 = rhs; dx workspace = x0.
+// B = W J^T, D, den per global constraint; x0 = rhs or the given start; dx workspace = x0.
 template <typename REAL>
 __global__ void __launch_bounds__(256) global_prepare_kernel(const GlobalArgs<REAL> A) {
   const int g = blockIdx.x * 256 + threadIdx.x;
@@ -614,8 +615,9 @@ __global__ void __launch_bounds__(256) global_prepare_kernel(const GlobalArgs<RE
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     A.den[(size_t)g * 3 + r] = c.inv[r];
-    if (!A.resume) A.x[(size_t)d.cidx * 3 + r] = c.rhs[r];
-    A.dx[(size_t)g * 3 + r] = A.resume ? REAL(0) : c.rhs[r];
+    const REAL x0 = A.x0 ? A.x0[(size_t)d.cidx * 3 + r] : c.rhs[r];   // a given start, or rhs (Q7)
+    if (!A.resume) A.x[(size_t)d.cidx * 3 + r] = x0;
+    A.dx[(size_t)g * 3 + r] = A.resume ? REAL(0) : x0;
   }
 }
 

@@ -48,10 +48,11 @@ __global__ void __launch_bounds__(256) patch_solve_kernel(const SolveArgs<REAL> 
 
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
+  const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
     load_cons(A, d.cidx, has0, has1, gb0, gb1, c);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) x[r] = A.resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
+    for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
   __syncthreads();
 

@@ -355,6 +355,9 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->sys_deferred = false;
   p->have_constraints = false;
   p->last_iterations = 0;
+  // the rows changed: x holds no lambda of this list, and a GIVEN start has the wrong length
+  p->have_lambda = false;
+  if (p->start_mode == EGS_START_GIVEN) p->start_mode = EGS_START_RHS;
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
     const int force = env ? std::atoi(env) : -1;
@@ -529,6 +532,27 @@ egs_status egs_problem_set_blocks(egs_problem *p, const double *Minv, const doub
 egs_status egs_problem_solve(egs_problem *p, const egs_solve_params *params, egs_solve_stats *stats) {
   if (!p) return EGS_ERR_INVALID;
   return guarded(p->ctx, [&]() -> egs_status { return do_solve(p, params, stats); });
+}
+
+egs_status egs_problem_set_start(egs_problem *p, int32_t mode, const double *x0) {
+  if (!p) return EGS_ERR_INVALID;
+  if (mode != EGS_START_RHS && mode != EGS_START_GIVEN && mode != EGS_START_PREVIOUS)
+    return fail(p->ctx, EGS_ERR_INVALID, "unknown start mode");
+  const size_t rows = (size_t)p->m * 3;
+  if (mode == EGS_START_GIVEN) {
+    if (!x0 && rows > 0) return fail(p->ctx, EGS_ERR_INVALID, "EGS_START_GIVEN needs the 3m rows of x0");
+    for (size_t i = 0; i < rows; ++i)
+      if (x0[i] != x0[i]) return fail(p->ctx, EGS_ERR_INVALID, "NaN in x0");
+  }
+  return guarded(p->ctx, [&]() -> egs_status {
+    if (mode == EGS_START_GIVEN) {
+      HIPCHK(hipStreamSynchronize(p->ctx->stream));   // a solve in flight may still read the old start
+      p->start.alloc((rows > 0 ? rows : 1) * p->real_size());
+      upload_real(p, p->start, x0, rows);
+    }
+    p->start_mode = mode;
+    return EGS_OK;
+  });
 }
 
 egs_status egs_problem_get_lambda(egs_problem *p, double *x) {

@@ -118,6 +118,13 @@ struct egs_problem {
   std::vector<uint8_t> h_rows_eq;
   std::vector<double> h_rows_lo, h_rows_hi;
   bool h_rows_valid = false;
+  // Where a solve starts (egs_problem_set_start).  start holds x0 [3m] REAL: uploaded once (GIVEN) or copied from x
+  // before a solve's first launch (PREVIOUS, while have_lambda).  start_active is set for the duration of a solve that
+  // takes it (solve.cpp: StartScope): launch_solve_t hands it to every fresh launch as SolveArgs::x0.
+  int start_mode = EGS_START_RHS;
+  egs::DevBuf<unsigned char> start;
+  bool have_lambda = false;    // x holds the lambda of a finished solve on the current constraint list
+  bool start_active = false;
   bool minv_iso = false;       // every M^-1 block is diag(a,a,a,b,b,b): the tile kernel keeps no B (EGS_ISO=0 disables)
   int last_iterations = 0;
   size_t real_size() const { return precision == EGS_F32 ? sizeof(float) : sizeof(double); }
@@ -167,6 +174,10 @@ void launch_residual(egs_problem *p);
 double read_residual(egs_problem *p, int *err_flag);
 egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats *stats, const AssembleArgs *assemble = nullptr);
 bool step_fuses_assembly(egs_problem *p, const egs_solve_params *prm);
+// the next solve starts from p->start instead of rhs: a GIVEN start, or PREVIOUS with a lambda to take
+inline bool solve_takes_start(const egs_problem *p) {
+  return p->start_mode == EGS_START_GIVEN || (p->start_mode == EGS_START_PREVIOUS && p->have_lambda);
+}
 void accumulators_from_lambda(egs_problem *p);
 
 struct BatchSolveState {

@@ -207,6 +207,7 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
   for (int k = 0; k < 9; ++k) { Jh[k] = REAL(0); Bh[k] = REAL(0); }
 #pragma unroll
   for (int r = 0; r < 3; ++r) { Dl[r] = inv[r] = rhs[r] = lo[r] = hi[r] = x[r] = REAL(0); eq[r] = true; }
+  const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
     const size_t c = (size_t)d.cidx;
     if (has) {
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
       hi[r] = A.hi[c * 3 + r];
       eq[r] = A.is_eq[c * 3 + r] != 0;
       clamp_bounds(eq[r], lo[r], hi[r]);
-      x[r] = A.resume ? A.x[c * 3 + r] : rhs[r];
+      x[r] = xs ? xs[c * 3 + r] : rhs[r];
     }
   }
   __syncthreads();
@@ -579,6 +580,7 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
   for (int k = 0; k < 9; ++k) { Jh[k] = REAL(0); Bh[k] = REAL(0); }
 #pragma unroll
   for (int r = 0; r < 3; ++r) { Dl[r] = inv[r] = rhs[r] = lo[r] = hi[r] = x[r] = REAL(0); eq[r] = true; }
+  const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
     const size_t c = (size_t)d.cidx;
     if (has) {
@@ -602,7 +604,7 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
       hi[r] = A.hi[c * 3 + r];
       eq[r] = A.is_eq[c * 3 + r] != 0;
       clamp_bounds(eq[r], lo[r], hi[r]);
-      x[r] = A.resume ? A.x[c * 3 + r] : rhs[r];
+      x[r] = xs ? xs[c * 3 + r] : rhs[r];
     }
   }
   // length of the tile's timetable (step_solve.hip: timetable_end)

@@ -22,12 +22,14 @@ struct SweepSchedule {
   bool linsym = false;      // step_solve_kernel's LINSYM form
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
+  bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
   int oversize = -1;        // OversizeSchedule of the launch's oversize islands, -1: it has none
   // the bits of the kernels that ran (egs_schedule_flags); fill_stats adds those of the problem's plans
   uint32_t flags() const {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
-           (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0);
+           (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
+           (started ? EGS_SCHED_START : 0);
   }
 };
 
@@ -35,6 +37,7 @@ struct SweepSchedule {
 // has not assembled the system and hands the assembly to the launch if its kernel can take it.
 SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bool resume, bool offer_assembly) {
   SweepSchedule s;
+  s.started = p->start_active;
   s.quad = p->use_quad && method != EGS_JACOBI;
   if (!s.quad) ensure_tile_plan(p);
   const Plan &pl = s.quad ? p->planq : p->plan;
@@ -63,9 +66,9 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   const char *le = std::getenv("EGS_ISO_LINSYM");
   s.linsym = !f32 && s.group == 1 && p->lin_neg && p->linsym_bodies == 1 && !(le && std::atoi(le) == 0);
   // ... with the assembly in its prologue: a fresh launch in which every constraint is a lane of some tile.
-  // EGS_FUSED_ASSEMBLY=0 keeps assemble_kernel.
+  // EGS_FUSED_ASSEMBLY=0 keeps assemble_kernel.  The ASSEMBLE form starts from rhs: a started solve is not offered it.
   const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
-  s.assemble = offer_assembly && s.linsym && !resume && pl.global.empty() && !(fe && std::atoi(fe) == 0);
+  s.assemble = offer_assembly && s.linsym && !resume && !solve_takes_start(p) && pl.global.empty() && !(fe && std::atoi(fe) == 0);
   // ... which stores no system (problem.h: ensure_system).  EGS_STEP_DEFER_SYSTEM=0 keeps the eager stores.
   const char *de = std::getenv("EGS_STEP_DEFER_SYSTEM");
   s.defer = s.assemble && !(de && std::atoi(de) == 0);
@@ -119,6 +122,8 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
   if (assemble && !sc.assemble)   // egs_problem_step asked choose_sweep for this launch before it skipped assemble_kernel
     throw std::logic_error("fused assembly offered to a launch that does not take it");
   p->last_sched = sc.flags();
+  // the start of a fresh launch: the problem's x0, or NULL: rhs (Q7)
+  const REAL *x0 = (p->start_active && !resume) ? real<REAL>(p->start) : nullptr;
   record_kernel_event(ctx, true);
   // oversize islands accumulate in global memory (all bodies on the all-global kernel, shared
   // bodies of patches): from zero, unless this launch continues the previous one
@@ -135,6 +140,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     a.kscale = kscale;
     a.sweeps = sweeps;
     a.resume = resume;
+    a.x0 = x0;
     a.max_slots = pl.max_slots;
     a.iso = sc.iso;
     a.linsym = sc.linsym;
@@ -172,6 +178,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     a.lanes = p->patch.lanes.p; a.tile_nslots = p->patch.tile_nslots.p; a.tile_slot_off = p->patch.tile_slot_off.p;
     a.slot_body = p->patch.slot_body.p;
     a.kscale = kscale; a.sweeps = sweeps; a.resume = resume;
+    a.x0 = x0;
     a.max_slots = p->plan.patch_max_slots;
     HIPCHK(hipMemsetAsync(p->gtickets.p, 0, sizeof(uint32_t) * (size_t)(p->n > 0 ? p->n : 1), ctx->stream));
     if (sc.oversize == kQuadPatches) {
@@ -213,6 +220,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
     g.kscale = kscale;
     g.sweeps = sweeps;
     g.resume = resume;
+    g.x0 = x0;
     g.method = method;
     launch_global_solve<REAL>(g, p->global_max_blocks, ctx->stream);
   }
@@ -288,6 +296,23 @@ void release_large_history(egs_problem *p) {
     p->hist_x.release(); p->hist_acc.release(); p->hist_out.release();
   }
 }
+
+// One solve's start (egs_problem_set_start): decided before the first launch, in force until the solve returns.
+// PREVIOUS takes its copy of x here, so x0 never aliases x; a problem without a lambda for its constraint list starts
+// from rhs.  Launches outside a solve (accumulators_from_lambda) never see a start.
+struct StartScope {
+  egs_problem *p;
+  explicit StartScope(egs_problem *q) : p(q) {
+    const bool take = p->m > 0 && solve_takes_start(p);
+    if (take && p->start_mode == EGS_START_PREVIOUS) {
+      const size_t bytes = (size_t)p->m * 3 * p->real_size();
+      p->start.alloc(bytes);
+      HIPCHK(hipMemcpyAsync(p->start.p, p->x.p, bytes, hipMemcpyDeviceToDevice, p->ctx->stream));
+    }
+    p->start_active = take;
+  }
+  ~StartScope() { p->start_active = false; }
+};
 
 // The longest launch of a fixed-sweep solve: tickets are 32-bit counters that advance by cnt per sweep, and the static
 // timetable counts time steps in a 32-bit int (see do_solve)
@@ -399,6 +424,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
   ensure_minv_real(p);   // also decides the isotropic fast path, hence the tile size
   if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
   if (stall_seen(p)) return report_stall(p);   // an earlier asynchronous solve timed out
+  const StartScope start(p);
   if (!(prm->tol > 0)) {
     // tickets are 32-bit counters that advance by cnt per sweep: very long runs
     // are cut into resumed launches so they cannot wrap
@@ -412,6 +438,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
       done += chunk;
     } while (done < prm->max_iters);
     p->last_iterations = prm->max_iters;
+    p->have_lambda = true;
     p->residual_pending = !stats;   // nobody is looking: the reduction runs when egs_problem_get_stats asks
     if (!stats) post_flag_copy(p);  // ... and a stall shows up at the next call or the next synchronising getter
     if (stats) {
@@ -425,14 +452,14 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     }
     return EGS_OK;
   }
-  // tol > 0: x0 = rhs, residual before iterating, then the reference's loop: one sweep,
+  // tol > 0: x0 = rhs (or the problem's start), residual before iterating, then the reference's loop: one sweep,
   // one residual, stop at the first err <= tol (sparse_iterations.cc:204-221).
   const int every = prm->check_every > 0 ? prm->check_every : 1;
   int it = 0, flag = 0;
   launch_solve(p, *prm, 0, 0);
   launch_residual(p);
-  // Should x0 already satisfy the test when its residual is deferred (it never does in practice: the reference
-  // starts from x0 = rhs) its state is simply produced again.
+  // Should x0 already satisfy the test when its residual is deferred (from x0 = rhs it never does in practice; a
+  // start taken from the previous step's lambda can) its state is simply produced again.
   const bool defer_first = defer_first_residual(prm);
   double err = 0.0;
   // one more kernel evaluates the stopping test of every recorded sweep and ONE read-back per chunk finds the
@@ -524,6 +551,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     }
   }
   p->last_iterations = it;
+  p->have_lambda = !flag;
   if (stats) {
     stats->residual = err;
     stats->iterations = it;
@@ -569,6 +597,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   ensure_minv_real(p);
   if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
   if (stall_seen(p)) return report_stall(p);
+  const StartScope start(p);
   // the schedule of do_solve: same recorded-chunk decision, chunk sizes and deferred residual of x0
   const bool defer_first = defer_first_residual(prm);
   const bool history = use_history(p, prm);
@@ -581,7 +610,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   auto residual = [&](const int32_t *running, const void *xs, const void *as, const void *ws, int sweeps) {
     batch_residual(p, B, prm->cfm, running, xs, as, ws, sweeps);
   };
-  // x0 = rhs: every ensemble's residual before iterating; those that already pass stop at 0 sweeps
+  // x0 = rhs (or the problem's start): every ensemble's residual before iterating; those that already pass stop at 0 sweeps
   launch_solve(p, *prm, 0, 0);
   residual(nullptr, p->x.p, nullptr, p->wres.p, 1);
   batch_select(p, B, prm, 1, 0, 1, 1, p->x.p, 0, p->acc.p, 0);
@@ -619,6 +648,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   if (p->n > 0) HIPCHK(hipMemcpyAsync(p->acc.p, B.fin_acc.p, 6 * (size_t)p->n * rs, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipGetLastError());
   p->last_iterations = it;
+  p->have_lambda = true;
   p->residual_pending = false;
   finish();
   return EGS_OK;

@@ -191,6 +191,8 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
 
   Cons<REAL> c;
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
+  // where x starts: the previous launch's x, a given start (A.x0), or NULL: rhs (Q7; always so in the ASSEMBLE form)
+  const REAL *xs = ASSEMBLE ? nullptr : resume ? A.x : A.x0;
   if constexpr (ASSEMBLE) {
     if (active) assemble_lane<STORE_SYSTEM>(A.assemble, d.cidx, c);
     if constexpr (STORE_SYSTEM) {
@@ -206,7 +208,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
     if constexpr (ASSEMBLE) load_cons<REAL, true, true, true>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
     else load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) x[r] = resume ? A.x[(size_t)d.cidx * 3 + r] : c.rhs[r];
+    for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
   const unsigned ac0 = lds_addr(s_acc + slot0 * 6), ac1 = lds_addr(s_acc + slot1 * 6);
   // snapshots for the per-sweep stopping test (kernels.h): is this lane the last update of its body in a sweep?

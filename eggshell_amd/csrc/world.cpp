@@ -2,7 +2,8 @@
 // Ensemble::Step (ensembles.cc:390-427) resident on the device, for one ensemble or a batch of them, on the sparse
 // sweeps (egs_world_step), the dense path (egs_world_step_dense), either with a time step and an erp per ensemble
 // (egs_world_step_each, egs_world_step_dense_each), and the stabilisation passes (egs_world_stabilize,
-// egs_world_stabilize_direct), and the one-shot egs_relax_blocks_direct.
+// egs_world_stabilize_direct), the warm start of the sweep steps (egs_world_set_warm_start: match, solve from x0,
+// snapshot; warm_start.h), and the one-shot egs_relax_blocks_direct.
 // The world works on its egs_problem through problem.h.
 #include <chrono>
 #include <cmath>
@@ -14,6 +15,7 @@
 #include "problem.h"
 #include "stabilize.h"
 #include "stabilize_direct.h"
+#include "warm_start.h"
 
 using namespace egs;
 
@@ -99,6 +101,18 @@ struct egs_world {
   DevBuf<double> dr_ws, dr_err_sq;
   PinnedBuf<int32_t> h_dr;               // page-locked: n_active
   std::vector<int32_t> st_rank, st_rows; // [E] of the last egs_world_stabilize_direct (empty: none yet)
+  // egs_world_set_warm_start: a step's solve starts from the previous step's lambda (warm_start.h).  The history is
+  // the list the last successful step solved -- its contacts' bodies and positions, every constraint's rows (joints
+  // first) in the world's precision, the contact offsets (batched) -- and valid [E]: has ensemble e a history?
+  // Dropped (valid = 0) wherever lambda_stale would be set, by set_bodies and by set_joints.  The step's x0 is the
+  // world's ws_x0, what the solve starts from the problem's start buffer; ws_source [m] says where each constraint's rows came from.
+  bool warm = false, last_warm = false;
+  double warm_radius = 0.0;
+  int ws_mj = 0, ws_mc = 0;              // the history's joints and contacts
+  DevBuf<int32_t> ws_b0, ws_b1, ws_coff, ws_source;
+  DevBuf<double> ws_pos;
+  DevBuf<unsigned char> ws_lambda, ws_x0;
+  DevBuf<uint8_t> ws_valid;
   bool lambda_stale = false;             // a stabilise call changed bodies / contacts since the last step's solve
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
@@ -385,6 +399,70 @@ void world_integrate(egs_world *w, double dt, const EnsembleRates *each) {
   HIPCHK(hipGetLastError());
 }
 
+// ---- warm start (egs_world_set_warm_start) ---------------------------------------------------------------------------
+// no ensemble has a history any more
+void world_drop_history(egs_world *w) {
+  if (!w->warm || !w->ws_valid.p) return;
+  HIPCHK(hipMemsetAsync(w->ws_valid.p, 0, (size_t)w->n_ens, w->ctx->stream));
+  w->ws_mj = w->ws_mc = 0;
+}
+
+// x0 of the assembled list from the history (REAL [3m]), sources into ws_source, and the solve's start into the
+// problem's start buffer: x0, but the rhs rows of an ensemble that sits the step out (dt_each, device, may be NULL)
+void world_warm_match(egs_world *w, const double *dt_each) {
+  egs_problem *p = w->prob;
+  hipStream_t s = w->ctx->stream;
+  const int mj = (int)w->jb0.size(), mc = p->m - mj;
+  const bool joints_kept = w->ws_mj == mj;   // (set_joints drops the history: a safeguard)
+  if (!joints_kept) world_drop_history(w);
+  p->start.alloc((size_t)p->m * 3 * p->real_size());
+  w->ws_x0.alloc((size_t)p->m * 3 * p->real_size());
+  w->ws_source.alloc((size_t)p->m);
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    MatchArgs<REAL> a;
+    a.n_ens = w->n_ens; a.mj = mj; a.m_old = w->ws_mc; a.m_new = mc;
+    if (w->n_ens > 1) { a.joint_off = w->d_joff.p; a.old_off = w->ws_coff.p; a.new_off = w->d_coff.p; }
+    a.valid = w->ws_valid.p;
+    a.old_b0 = w->ws_b0.p; a.old_b1 = w->ws_b1.p; a.old_pos = w->ws_pos.p; a.old_stride = 3;
+    a.old_lambda = real<REAL>(w->ws_lambda);
+    a.new_b0 = p->body0.p + mj; a.new_b1 = p->body1.p + mj;
+    a.new_pos = p->data.p + (size_t)mj * 7; a.new_stride = 7;
+    a.new_rhs = real<REAL>(p->rhs);
+    a.r2 = w->warm_radius * w->warm_radius;
+    a.x0 = real<REAL>(w->ws_x0); a.source = w->ws_source.p;
+    a.dt = dt_each; a.start = real<REAL>(p->start);
+    launch_match_contacts<REAL>(a, s);
+  });
+  HIPCHK(hipGetLastError());
+}
+
+// the list just solved becomes the history (x: its lambda); dt_each (device, may be NULL): who sat out
+void world_warm_snapshot(egs_world *w, const double *dt_each) {
+  egs_problem *p = w->prob;
+  hipStream_t s = w->ctx->stream;
+  const int mj = (int)w->jb0.size(), mc = p->m - mj;
+  const size_t rs = p->real_size(), mm = (size_t)(p->m > 0 ? p->m : 1), cc = (size_t)(mc > 0 ? mc : 1);
+  HIPCHK(hipStreamSynchronize(s));   // a growing buffer is freed: the match kernel has read it by now
+  w->ws_b0.alloc(cc); w->ws_b1.alloc(cc); w->ws_pos.alloc(cc * 3); w->ws_lambda.alloc(mm * 3 * rs);
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    SnapshotArgs<REAL> a;
+    a.n_ens = w->n_ens; a.mj = mj; a.mc = mc;
+    if (w->n_ens > 1) { a.joint_off = w->d_joff.p; a.contact_off = w->d_coff.p; }
+    a.dt = dt_each;
+    a.b0 = p->body0.p + mj; a.b1 = p->body1.p + mj; a.pos = p->data.p + (size_t)mj * 7; a.stride = 7;
+    a.x0 = real<REAL>(w->ws_x0); a.x = real<REAL>(p->x);
+    a.h_b0 = w->ws_b0.p; a.h_b1 = w->ws_b1.p; a.h_pos = w->ws_pos.p; a.h_lambda = real<REAL>(w->ws_lambda);
+    a.valid = w->ws_valid.p;
+    launch_warm_snapshot<REAL>(a, s);
+  });
+  HIPCHK(hipGetLastError());
+  if (w->n_ens > 1)
+    HIPCHK(hipMemcpyAsync(w->ws_coff.p, w->d_coff.p, ((size_t)w->n_ens + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  w->ws_mj = mj; w->ws_mc = mc;
+}
+
 // EGS_WORLD_TRACE=1: host wall time per phase of an entry, lap(k) adds the time since the last lap to acc[k].
 // sync: wait for the stream first (the stabilise passes; a step must not)
 struct PhaseTimer {
@@ -471,15 +549,29 @@ egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *
     if (detect_contacts) world_update_contacts(w, lap);
     egs_problem *p = w->prob;
     const bool batched = w->n_ens > 1;
+    w->last_warm = false;
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);
-      egs_status st = batched ? do_solve_batch(p, params, w->batch) : do_solve(p, params, stats);
+      // x0 from the history; an ensemble without one gets its rhs rows, the default start.  The problem takes the
+      // start for this solve only, also when the solve throws.
+      struct GivenStart {
+        egs_problem *p;
+        explicit GivenStart(egs_problem *q) : p(q) { if (p) p->start_mode = EGS_START_GIVEN; }
+        ~GivenStart() { if (p) p->start_mode = EGS_START_RHS; }
+      };
+      if (w->warm) world_warm_match(w, each ? each->dt : nullptr);
+      egs_status st;
+      {
+        const GivenStart given(w->warm ? p : nullptr);
+        st = batched ? do_solve_batch(p, params, w->batch) : do_solve(p, params, stats);
+      }
       if (st != EGS_OK) return st;
       // the body state must not be advanced with a lambda that came out of a timed-out ordering
       // wait: look at the flag before integrating (one 4-byte read-back per step)
       HIPCHK(hipStreamSynchronize(s));
       if (stall_seen(p)) return report_stall(p);
       w->lambda_stale = false;   // x holds this step's lambda for the current list
+      if (w->warm) { world_warm_snapshot(w, each ? each->dt : nullptr); w->last_warm = true; }
       if (batched && stats) {   // the slowest ensemble's sweep count and the largest residual
         std::memset(stats, 0, sizeof *stats);
         fill_stats(p, stats);
@@ -492,6 +584,7 @@ egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *
     } else {  // no constraints: v_dot = M^-1 f (ensembles.cc:504-505)
       if (egs_status st = validate_params(w->ctx, params)) return st;
       w->lambda_stale = false;
+      if (w->warm) world_warm_snapshot(w, each ? each->dt : nullptr);   // an empty list is a history too
       zero_accumulators(p);
       if (stats) { std::memset(stats, 0, sizeof *stats); fill_stats(p, stats); }
       if (batched) {
@@ -523,8 +616,11 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
     std::string big_msg;
     bool sits_out = false;
     for (int e = 0; dt_each && e < E; ++e) sits_out |= dt_each[e] == 0.0;
+    w->last_warm = false;
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);                              // J, err, bounds, rhs (ensembles.cc:565-570)
+      // the dense step takes no start; an ensemble sitting out keeps its history through the rows matched here
+      if (w->warm && sits_out) world_warm_match(w, each->dt);
       if (w->dense_plan_replans != w->replans) world_dense_plan(w);
       DenseWorldArgs a;
       a.cons = w->dn_cons.p; a.cstart = w->dn_cstart.p; a.ws_off = w->dn_wsoff.p;
@@ -589,6 +685,7 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
       return fail(w->ctx, EGS_ERR_LCP_FAILED, msg);
     }
     w->lambda_stale = false;   // every ensemble solved: x holds this step's lambda for the current list
+    if (w->warm) world_warm_snapshot(w, sits_out ? each->dt : nullptr);   // the history is the dense lambda
     if (p->m > 0) accumulators_from_lambda(p);                    // a = M^-1 J^T lambda
     else zero_accumulators(p);
     world_integrate(w, dt, each);
@@ -676,6 +773,7 @@ egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R
     if (!w->prob) world_make_problem(w, w->jb0.data(), w->jb1.data(), (int)w->jb0.size());
     egs_status st = egs_problem_set_state(w->prob, pos, R, v, wv, Minv, f_ext);
     if (st != EGS_OK) return st;
+    world_drop_history(w);
     if (side_lengths) upload(w->dside, side_lengths, (size_t)w->n * 3, w->ctx->stream);
     w->have_bodies = true;
     return EGS_OK;
@@ -757,6 +855,7 @@ egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *b
     }
     world_make_problem(w, w->jb0.data(), w->jb1.data(), m_joints);   // contacts are re-detected by the next step
     w->m_contacts = 0;
+    world_drop_history(w);
     if (w->n_ens > 1) {
       const size_t E1 = (size_t)w->n_ens + 1;
       w->joint_off = joint_off;
@@ -846,6 +945,42 @@ egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_ou
   return egs_problem_get_lambda(w->prob, lambda);
 }
 
+egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_radius) {
+  if (!w) return EGS_ERR_INVALID;
+  if (enable && !(match_radius >= 0)) return fail(w->ctx, EGS_ERR_INVALID, "match_radius must be >= 0");
+  return guarded(w->ctx, [&]() -> egs_status {
+    w->warm = enable != 0;
+    w->warm_radius = enable ? match_radius : 0.0;
+    w->last_warm = false;
+    if (w->warm) {   // switched on (or on again): no history
+      w->ws_valid.alloc((size_t)w->n_ens);
+      w->ws_coff.alloc((size_t)w->n_ens + 1);
+      HIPCHK(hipMemsetAsync(w->ws_coff.p, 0, ((size_t)w->n_ens + 1) * sizeof(int32_t), w->ctx->stream));
+      world_drop_history(w);
+    }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_get_start(egs_world *w, int32_t max_rows, int32_t *rows_out, double *x0, int32_t *source) {
+  if (!w || !w->prob || !rows_out) return EGS_ERR_INVALID;
+  *rows_out = 3 * w->prob->m;
+  if (!w->last_warm) return fail(w->ctx, EGS_ERR_INVALID, "the last step was not a warm-started sweep step");
+  if (3 * w->prob->m > max_rows) return fail(w->ctx, EGS_ERR_INVALID, "max_rows too small");
+  if (!x0) return fail(w->ctx, EGS_ERR_INVALID, "x0 is NULL");
+  return guarded(w->ctx, [&]() -> egs_status {
+    egs_problem *p = w->prob;
+    hipStream_t s = w->ctx->stream;
+    const size_t rows = (size_t)p->m * 3;
+    std::vector<float> tmp(p->precision == EGS_F32 ? rows : 0);
+    HIPCHK(hipMemcpyAsync(tmp.empty() ? (void *)x0 : (void *)tmp.data(), w->ws_x0.p, rows * p->real_size(), hipMemcpyDeviceToHost, s));
+    if (source) HIPCHK(hipMemcpyAsync(source, w->ws_source.p, (size_t)p->m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < tmp.size(); ++i) x0[i] = (double)tmp[i];
+    return EGS_OK;
+  });
+}
+
 egs_status egs_world_batch_info(egs_world *w, int32_t n_ensembles, int32_t *joint_offset, int32_t *contact_offset,
                                 int32_t *iterations, double *residual) {
   if (!w) return EGS_ERR_INVALID;
@@ -909,6 +1044,7 @@ egs_status egs_world_stabilize(egs_world *w, int32_t mode, int32_t max_steps, in
   return guarded(w->ctx, [&]() -> egs_status {
     hipStream_t s = w->ctx->stream;
     w->lambda_stale = true;
+    world_drop_history(w);
     w->st_steps.clear(); w->st_err_sq.clear();
     w->rx_ints.alloc(2 * (size_t)E + 5);
     w->rx_err_sq.alloc((size_t)E);
@@ -1008,6 +1144,7 @@ egs_status egs_world_stabilize_direct(egs_world *w, int32_t mode, int32_t max_st
     if (!detect)   // the list the call works on is known now: refuse before anything changes
       if (egs_status st = world_direct_plan(w)) return st;
     w->lambda_stale = true;
+    world_drop_history(w);
     w->st_steps.clear(); w->st_err_sq.clear(); w->st_rank.clear(); w->st_rows.clear();
     w->dr_ints.alloc(3 * (size_t)E + 1);
     w->dr_err_sq.alloc((size_t)E);

@@ -24,6 +24,23 @@ egs_context *DefaultContext() {
 static void check(egs_status st) {
   if (st != EGS_OK) throw Error(st, egs_last_error(DefaultContext()));
 }
+// pos, R, v, w of every body as one array, and whether a gathered state is that array bit for bit (SetWarmStart:
+// a state nobody touched since the last device step is not pushed again)
+static void keep_state(std::vector<double> &kept, const std::vector<double> &pos, const std::vector<double> &R,
+                       const std::vector<double> &v, const std::vector<double> &w) {
+  kept.clear();
+  for (const std::vector<double> *a : {&pos, &R, &v, &w}) kept.insert(kept.end(), a->begin(), a->end());
+}
+static bool same_state(const std::vector<double> &kept, const std::vector<double> &pos, const std::vector<double> &R,
+                       const std::vector<double> &v, const std::vector<double> &w) {
+  if (kept.empty() || kept.size() != pos.size() + R.size() + v.size() + w.size()) return false;
+  size_t at = 0;
+  for (const std::vector<double> *a : {&pos, &R, &v, &w}) {
+    if (!a->empty() && std::memcmp(kept.data() + at, a->data(), a->size() * sizeof(double)) != 0) return false;
+    at += a->size();
+  }
+  return true;
+}
 }  // namespace egs
 
 // ---- utils ---------------------------------------------------------------
@@ -694,6 +711,12 @@ void Ensemble::CheckAndCorrectEnsembleState() {
 // permanent constraint can describe itself (ball joints) -- contacts always can.
 // Body objects are the interface, so their state is pushed before and pulled
 // after the step; inside the step nothing but the contact topology leaves the GPU.
+void Ensemble::SetWarmStart(bool on, double match_radius) {
+  if (on && !(match_radius >= 0)) throw egs::Error(EGS_ERR_INVALID, "SetWarmStart: match_radius must be >= 0");
+  warm_start_ = on;
+  warm_radius_ = on ? match_radius : 0.0;
+}
+
 bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
@@ -722,9 +745,16 @@ bool Ensemble::StepOnDevice(double dt) {
     for (int r = 0; r < 6; ++r)
       for (int c = 0; c < 6; ++c) Minv[(size_t)i * 36 + 6 * r + c] = M_inverse_(6 * i + r, 6 * i + c);
   }
-  // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once
-  egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
-                                  first ? external_force_torque_.data() : nullptr, first ? side.data() : nullptr));
+  if (first || warm_start_ != world_warm_ || (warm_start_ && warm_radius_ != world_warm_radius_)) {
+    egs::check(egs_world_set_warm_start(world_, warm_start_ ? 1 : 0, warm_radius_));
+    world_warm_ = warm_start_; world_warm_radius_ = warm_radius_;
+    world_state_.clear();
+  }
+  // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state
+  // that is still what the last step left on the device is not pushed again: a push drops the world's history.
+  if (!(warm_start_ && egs::same_state(world_state_, pos, R, vl, w)))
+    egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
+                                    first ? external_force_torque_.data() : nullptr, first ? side.data() : nullptr));
   // joints are permanent in the reference (ensembles.cc:331-334); a caller that edits them all the same
   // (same count, other bodies or anchors) must not step against the stale device copy
   if (world_joints_ != mj || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {
@@ -735,8 +765,10 @@ bool Ensemble::StepOnDevice(double dt) {
   egs_solve_params prm = solver_params;
   prm.cfm = cfm_coeff;
   egs_solve_stats st;
+  world_state_.clear();   // (a step that throws leaves no state to trust)
   egs::check(egs_world_step(world_, dt, /*erp=*/0.2, &prm, detect_contacts ? 1 : 0, &st));
   egs::check(egs_world_get_bodies(world_, pos.data(), R.data(), vl.data(), w.data()));
+  if (warm_start_) egs::keep_state(world_state_, pos, R, vl, w);
   for (int i = 0; i < n_; ++i) {
     components_[i]->SetP(Vector3d(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]));
     components_[i]->SetV(Vector3d(vl[3 * i], vl[3 * i + 1], vl[3 * i + 2]));
@@ -806,6 +838,8 @@ EnsembleGroup::EnsembleGroup(std::vector<Ensemble *> members) : members_(std::mo
       throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in use_dense_solver");
     if (m->detect_contacts != first->detect_contacts)
       throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in detect_contacts");
+    if (m->warm_start_ != first->warm_start_ || m->warm_radius_ != first->warm_radius_)
+      throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in SetWarmStart");
     int32_t kind = 0;
     double data[7];
     for (size_t j = 0; j < m->joints_.size(); ++j)
@@ -878,15 +912,27 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
       jdata.insert(jdata.end(), d, d + 7);
     }
   }
-  // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once
-  egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
-                                  first ? fext.data() : nullptr, first ? side.data() : nullptr));
+  const Ensemble *lead = members_[0];
+  for (size_t i = 1; i < E; ++i)   // (the constructor's check, again: SetWarmStart may have been called since)
+    if (members_[i]->warm_start_ != lead->warm_start_ || members_[i]->warm_radius_ != lead->warm_radius_)
+      throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " differs from member 0 in SetWarmStart");
+  const bool warm = lead->warm_start_ && !lead->use_dense_solver;
+  if (first || warm != world_warm_ || (warm && lead->warm_radius_ != world_warm_radius_)) {
+    egs::check(egs_world_set_warm_start(world_, warm ? 1 : 0, lead->warm_radius_));
+    world_warm_ = warm; world_warm_radius_ = lead->warm_radius_;
+    world_state_.clear();
+  }
+  // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state
+  // that is still what the last step left on the device is not pushed again: a push drops the world's history.
+  if (!(warm && egs::same_state(world_state_, pos, R, vl, w)))
+    egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
+                                    first ? fext.data() : nullptr, first ? side.data() : nullptr));
+  world_state_.clear();
   if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {   // re-sent when edited
     egs::check(egs_world_set_joints(world_, (int32_t)jb0.size(), jb0.data(), jb1.data(), jdata.data()));
     joints_sent_ = true;
     world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata;
   }
-  const Ensemble *lead = members_[0];
   const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
   if (lead->use_dense_solver) {
     egs::check(egs_world_step_dense_each(world_, (int32_t)E, dt.data(), erp.data(), lead->cfm_coeff, /*use_bounds=*/0,
@@ -898,6 +944,7 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     egs::check(egs_world_step_each(world_, (int32_t)E, dt.data(), erp.data(), &prm, lead->detect_contacts ? 1 : 0, &st));
   }
   egs::check(egs_world_get_bodies(world_, pos.data(), R.data(), vl.data(), w.data()));
+  if (warm) egs::keep_state(world_state_, pos, R, vl, w);
   int32_t mcons = 0, mc = 0, replans = 0;
   egs::check(egs_world_info(world_, &mcons, &mc, &replans));
   std::vector<int32_t> jo(E + 1), co(E + 1), cb0((size_t)mc), cb1((size_t)mc);

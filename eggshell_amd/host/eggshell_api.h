@@ -304,6 +304,14 @@ class Ensemble {  // ensembles.h:25-186
   // solver parameters (compile-time constants in the reference)
   egs_solve_params solver_params;
   double cfm_coeff = 0.01;                                               // kCfmCoeff, ensembles.cc:14
+  // Not in the reference, off by default: the device step's sweeps start from the previous step's lambda instead of
+  // rhs (egs_world_set_warm_start: a contact takes the rows of the nearest previous contact of its body pair within
+  // match_radius, metres, world frame; a joint its own).  The history lives with the device world: a step after
+  // which no Body was touched continues it (the state is then not pushed again), a step after an edited Body, an
+  // edited joint or a stabilise call starts from rhs as ever.  Throws egs::Error(EGS_ERR_INVALID) if radius < 0.
+  void SetWarmStart(bool on, double match_radius = 0.01);
+  bool warm_start() const { return warm_start_; }
+  double warm_start_radius() const { return warm_radius_; }
   VectorXd last_lambda;
   int last_stabilize_steps = 0;
 
@@ -337,6 +345,9 @@ class Ensemble {  // ensembles.h:25-186
   int world_joints_ = -1;
   std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds
   std::vector<double> world_jdata_;
+  bool warm_start_ = false, world_warm_ = false;   // asked for; what the device world was last told
+  double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
+  std::vector<double> world_state_;              // pos, R, v, w as pulled after the last device step (warm start only)
   egs_problem *problem_ = nullptr;
   std::vector<int32_t> plan_b0_, plan_b1_;   // topology the cached device problem was planned for
 };
@@ -367,7 +378,7 @@ class Cairn : public Ensemble {
 // as in Ensemble::Step.  After it every member's Body objects, contacts and last_lambda hold, bit for bit, what the
 // member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
 // egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
-//   - The members must agree in solver_params, cfm_coeff, use_dense_solver and detect_contacts, and each must be able to
+//   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts and SetWarmStart, and each must be able to
 //     take the device step (joints that Describe themselves, no caller-supplied contacts); the list may not be empty or
 //     hold a pointer twice: the constructor throws egs::Error(EGS_ERR_INVALID) naming the offending member.
 //   - The members are not owned and must outlive the group; Init() them before the first Step (M^-1, the external
@@ -394,6 +405,9 @@ class EnsembleGroup {
   bool joints_sent_ = false;
   std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds
   std::vector<double> world_jdata_;
+  bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
+  double world_warm_radius_ = 0.0;
+  std::vector<double> world_state_;              // pos, R, v, w as pulled after the last step (warm start only)
 };
 
 #endif

@@ -9,6 +9,10 @@
 //                                        frame's p, R, v, w of all bodies and last_lambda (it must be exactly 0), the
 //                                        contact counts of both runs per frame, the group's world
 //   frame_demo --mismatch                a group of two members that differ in cfm_coeff: prints the refusal, exits 0
+//   frame_demo --warm [frames] [seed]    the same two runs with SetWarmStart(true, 0.01) on every Ensemble, and a third,
+//                                        cold copy stepped like the separate one: "differs_from_cold" counts the frames
+//                                        whose cairn lambda is not the cold run's (the history is in use)
+//   frame_demo --warm-mismatch           a group whose members differ in SetWarmStart: prints the refusal, exits 0
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -62,9 +66,10 @@ void print_list(const char *name, const std::vector<int> &v) {
   std::printf("]");
 }
 
-int mismatch() {
+int mismatch(bool warm) {
   Scene s(1);
-  s.cairn->cfm_coeff = 0.02;
+  if (warm) s.cairn->SetWarmStart(true, 0.01);
+  else s.cairn->cfm_coeff = 0.02;
   try {
     EnsembleGroup group({s.chain.get(), s.cairn.get()});
   } catch (const egs::Error &e) {
@@ -79,10 +84,16 @@ int mismatch() {
 
 int main(int argc, char **argv) {
   try {
-    if (argc > 1 && std::strcmp(argv[1], "--mismatch") == 0) return mismatch();
+    if (argc > 1 && std::strcmp(argv[1], "--mismatch") == 0) return mismatch(false);
+    if (argc > 1 && std::strcmp(argv[1], "--warm-mismatch") == 0) return mismatch(true);
+    const bool warm = argc > 1 && std::strcmp(argv[1], "--warm") == 0;
+    if (warm) { --argc; ++argv; }
     const int frames = argc > 1 ? std::atoi(argv[1]) : 3;
     const unsigned seed = argc > 2 ? (unsigned)std::atoi(argv[2]) : 1u;
-    Scene sep(seed), grp(seed);
+    Scene sep(seed), grp(seed), cold(seed);
+    if (warm)
+      for (Scene *s : {&sep, &grp}) { s->chain->SetWarmStart(true, 0.01); s->cairn->SetWarmStart(true, 0.01); }
+    int differs_from_cold = 0;
     const int chain_joints = 10;   // Chain(10): nine links' joints and the anchor
     EnsembleGroup group({grp.chain.get(), grp.cairn.get()});
     double diff = 0.0;
@@ -96,6 +107,12 @@ int main(int argc, char **argv) {
       for (int k = 0; k < 4; ++k) group.Step({1e-3, 0.0});
       compare(*sep.chain, *grp.chain, &diff);
       compare(*sep.cairn, *grp.cairn, &diff);
+      if (warm) {
+        cold.cairn->Step(5e-3);
+        double d = 0.0;
+        compare(*sep.cairn, *cold.cairn, &d);
+        differs_from_cold += d != 0.0 ? 1 : 0;
+      }
       chain_sep.push_back((int)sep.chain->constraints().size() - chain_joints);
       chain_grp.push_back((int)grp.chain->constraints().size() - chain_joints);
       cairn_sep.push_back((int)sep.cairn->constraints().size());
@@ -108,6 +125,7 @@ int main(int argc, char **argv) {
     print_list("chain_contacts_group", chain_grp); std::printf(", ");
     print_list("cairn_contacts_separate", cairn_sep); std::printf(", ");
     print_list("cairn_contacts_group", cairn_grp);
+    if (warm) std::printf(", \"differs_from_cold\": %d", differs_from_cold);
     std::printf(", \"world_ensembles\": %d, \"worlds_created\": %d}\n", group.world_ensembles(), group.worlds_created());
   } catch (const std::exception &e) {
     std::fprintf(stderr, "frame_demo: %s\n", e.what());

@@ -98,11 +98,12 @@ typedef enum {
                                   block for both sides (J1_lin = -J0_lin and equal linear weights, bit for bit) */
   EGS_SCHED_FUSED_ASSEMBLY = 256,  /* egs_problem_step assembled the Jacobian in the LINSYM launch's prologue
                                       (no separate assembly kernel; the same blocks, bit for bit) */
-  EGS_SCHED_DEFERRED_SYSTEM = 512  /* ... and that launch stored no system: J0, J1, rhs, lo, hi, err and is_eq are
+  EGS_SCHED_DEFERRED_SYSTEM = 512, /* ... and that launch stored no system: J0, J1, rhs, lo, hi, err and is_eq are
                                       made on demand, by the first call that reads them (the same bits): one
                                       assembly launch, what the step saved.  Readers: get_blocks, matvec, a solve or
                                       a step that does not fuse, the dense entries, and the residual -- so a step
                                       asked for statistics, or get_stats after one, pays for it too */
+  EGS_SCHED_START = 1024           /* the solve started from a given x0 (egs_problem_set_start), not from rhs */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -176,6 +177,23 @@ egs_status egs_problem_get_accumulators(egs_problem *p, double *a /*[n][6]*/);
 /* w = A lambda - rhs of the last solve, [3m]: what GetResidualError
  * (sparse_iterations.cc:51-69) reduces; written by the solve kernels' epilogue. */
 egs_status egs_problem_get_wres(egs_problem *p, double *w /*[3m]*/);
+
+/* ---- where a solve starts.  The reference starts every solve from x0 = rhs (quirk Q7, sparse_iterations.cc:202);
+ *      that is the default and nothing changes it unless this is called.  The mode is sticky until changed:
+ *        EGS_START_RHS       x0 = rhs.
+ *        EGS_START_GIVEN     x0 = the 3m rows passed with this call, uploaded once (converted to the problem's
+ *                            precision) and used by every following solve.
+ *        EGS_START_PREVIOUS  x0 = lambda of the last solve on this problem, copied on the device before each solve's
+ *                            first launch; a problem that holds no lambda yet starts that solve from rhs.
+ *      From x0 on the solve is the reference's: accumulators from x0 in list order, the sweeps, the stopping test
+ *      (x0 itself is tested first: iterations = 0 if it passes), w = A x - rhs with the true rhs.  A solve that
+ *      started from a given x0 reports EGS_SCHED_START.  egs_problem_step with a start in force assembles with the
+ *      assembly kernel (EGS_SCHED_FUSED_ASSEMBLY stays clear).  The dense steps take no start.
+ *      EGS_ERR_INVALID: an unknown mode, GIVEN with x0 = NULL, a NaN row.                                          */
+#define EGS_START_RHS      0
+#define EGS_START_GIVEN    1
+#define EGS_START_PREVIOUS 2
+egs_status egs_problem_set_start(egs_problem *p, int32_t mode, const double *x0 /*[3m], GIVEN only*/);
 
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
@@ -382,6 +400,25 @@ egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n_bodies,
                                       int32_t *m_out, int32_t *body0,
                                       int32_t *body1, double *data);
 
+/* ---- carrying lambda across a contact list that changes: the start (x0 of egs_problem_set_start's
+ *      EGS_START_GIVEN) of a solve on the new list from the lambda of the last solve on the old one.
+ * Both lists hold n_ens >= 1 ensembles back to back (offsets [n_ens + 1], from 0 to m), each in the order
+ * egs_update_contacts writes, i.e. ordered by (b0, b1) with the ground (-1) first; an old list that is not is
+ * refused.  pos = the contacts' positions [m][3], lambda / rhs = their rows [m][3].  For new contact c of ensemble e:
+ *   valid[e] == 0                       x0 = its rhs rows (the reference's start, Q7); source = -2
+ *   otherwise, among e's old contacts of the same ordered pair (b0, b1), the one whose position is nearest
+ *   (squared distance (dx^2 + dy^2) + dz^2 <= radius^2; a tie goes to the lowest old index):
+ *                                       x0 = its lambda rows, bit for bit; source = its old index
+ *   no such old contact                 x0 = 0; source = -1
+ * Two new contacts may take the same old one.  Positions are compared in the world frame: the radius must exceed
+ * what a contact point travels in one step.  One lane per new contact, a binary search for the pair's run in the
+ * ensemble's old segment and a scan of that run.  EGS_ERR_INVALID: radius < 0 or NaN, bad offsets, NULL arrays.   */
+egs_status egs_match_contacts(egs_context *ctx, int32_t n_ens,
+    int32_t m_old, const int32_t *old_b0, const int32_t *old_b1, const double *old_pos, const double *old_lambda,
+    const int32_t *old_off /*[n_ens+1]*/, const uint8_t *valid /*[n_ens]*/,
+    int32_t m_new, const int32_t *new_b0, const int32_t *new_b1, const double *new_pos, const double *new_rhs,
+    const int32_t *new_off, double radius, double *x0 /*[3 m_new]*/, int32_t *source /*[m_new]*/);
+
 /* ---- the whole Ensemble::Step on the device ------------------------------
  * Ensemble::Step(dt, OPEN_DYNAMICS_ENGINE) (ensembles.cc:390-427) with the
  * sparse switch on: UpdateContacts + contact pruning, StepVelocities_ODE
@@ -409,6 +446,28 @@ egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v,
 egs_status egs_world_get_contacts(egs_world *w, int32_t max_contacts, int32_t *m_out, int32_t *body0,
                                   int32_t *body1, double *data);
 egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_out, double *lambda);
+
+/* ---- warm start: a step's solve starts from the previous step's lambda instead of rhs (quirk Q7).  Off by default;
+ * off, nothing in a step changes.  On, egs_world_step and egs_world_step_each run
+ *   collide, re-plan on change, assemble, MATCH into x0, solve from x0, stall check, SNAPSHOT, integrate:
+ *   - a contact takes the lambda rows of the nearest contact of the same ordered body pair of the list the last step
+ *     solved, within match_radius (the rule of egs_match_contacts; none: 0), a joint its own previous rows;
+ *   - a step without history -- the first one, after egs_world_set_bodies, egs_world_set_joints or any
+ *     egs_world_stabilize* -- is the default step bit for bit (x0 = rhs rows, source -2) except that its
+ *     egs_solve_stats.schedule carries EGS_SCHED_START like every warm step's: the solve was handed a start, which
+ *     happens to be rhs; a stalled solve leaves the
+ *     history as it was; a step without constraints leaves an empty history (the next contacts start from 0);
+ *   - batched worlds: history, validity and offsets per ensemble, each ensemble the bits of a world holding only it.
+ *     An ensemble that sits a step out (dt[e] = 0) is solved from its rhs rows as ever (its lambda rows are 0) and
+ *     keeps the history it held;
+ *   - the dense steps take no start; after one the history is that step's lambda.
+ * Positions are matched in the world frame: match_radius (>= 0, metres) must exceed what a contact point travels in
+ * one step.
+ * egs_world_get_start: x0 [3m] of the last warm sweep step and, if asked, per constraint the index (among the
+ * previous list's contacts; a joint: its own index) its rows came from, -1 or -2 as egs_match_contacts reports;
+ * EGS_ERR_INVALID if the last step was not one.                                                                  */
+egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_radius);
+egs_status egs_world_get_start(egs_world *w, int32_t max_rows, int32_t *rows_out, double *x0, int32_t *source /*[m] or NULL*/);
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans);
 
 /* ---- many ensembles in one world ------------------------------------------
