@@ -135,6 +135,9 @@ int orc_fast_iterate_f32(int n, int m, const float *Minv, const int32_t *body0,
  * orc_fast_iterate_f64 returned: the expression of the solve kernels' epilogue. */
 void orc_fast_wres_f64(const orc_system *s, const double *rhs, double cfm, const double *x,
                        const double *a, double *w);
+/* the same in fp32, from the results of orc_fast_iterate_f32 */
+void orc_fast_wres_f32(int n, int m, const int32_t *body0, const int32_t *body1, const float *J0, const float *J1,
+                       const float *rhs, float cfm, const float *x, const float *a, float *w);
 
 /* O(nnz) twin of the matrix-free products CalculateSparse{Lx,Ux,Dx,LxUx,UxDx,LxDx,JMJtX}
  * (sparse_iterations_utils.cc:427-695) in the operation order of the HIP mat-vec

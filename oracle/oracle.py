@@ -265,6 +265,16 @@ def fast_iterate_f32(s, rhs, cfm, method, omega=1.5, max_iters=500, tol=0.0, che
     return x, a, it, res.value
 
 
+def fast_wres_f32(s, rhs, cfm, x, a):
+    """fast_wres in fp32, from the x and the accumulators fast_iterate_f32 returned."""
+    f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    J0, J1, rhs, x, a = f(s.J0), f(s.J1), f(rhs), f(x), f(a)
+    w = np.zeros(3 * s.m, np.float32)
+    lib().orc_fast_wres_f32(C.c_int(s.n), C.c_int(s.m), _p(s.body0), _p(s.body1), _p(J0), _p(J1), _p(rhs),
+                            C.c_float(cfm), _p(x), _p(a), _p(w))
+    return w
+
+
 MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 
 

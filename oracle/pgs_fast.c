@@ -86,3 +86,9 @@ void orc_fast_matvec_f32(int n, int m, const float *Minv, const int32_t *body0, 
 void orc_fast_wres_f64(const orc_system *s, const double *rhs, double cfm, const double *x, const double *a, double *w) {
   f64_wres(s->m, s->body0, s->body1, s->J0, s->J1, rhs, cfm, x, a, w);
 }
+
+void orc_fast_wres_f32(int n, int m, const int32_t *body0, const int32_t *body1, const float *J0, const float *J1,
+                       const float *rhs, float cfm, const float *x, const float *a, float *w) {
+  (void)n;
+  f32_wres(m, body0, body1, J0, J1, rhs, cfm, x, a, w);
+}
