@@ -186,10 +186,16 @@ void ensure_minv_real(egs_problem *p) {
 
 // Ball joints that join two bodies are assembled with +0 in J1_lin where J0_lin holds +0 (joints.cc:17-31): their
 // J1_lin is -J0_lin in value but not in bits.  Contacts are [-Rn, ..] / [Rn, ..], negated bit for bit.
+// A list without any joint holds contacts only: the fused step's sweep takes their bounds as literals (solve.cpp:
+// choose_sweep).
 void note_kinds(egs_problem *p, const int32_t *kind) {
-  bool jp = false;
-  for (int i = 0; i < p->m && !jp; ++i) jp = kind[i] == EGS_JOINT_BALL && p->h_body0[i] >= 0 && p->h_body1[i] >= 0;
+  bool jp = false, joint = false;
+  for (int i = 0; i < p->m && !jp; ++i) {
+    joint = joint || kind[i] == EGS_JOINT_BALL;
+    jp = kind[i] == EGS_JOINT_BALL && p->h_body0[i] >= 0 && p->h_body1[i] >= 0;
+  }
   p->joint_pairs = jp;
+  p->contacts_only = !joint;
 }
 
 // ---- the sticky stall flag ---------------------------------------------------

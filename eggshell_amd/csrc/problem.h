@@ -55,6 +55,7 @@ struct egs_problem {
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
+  bool contacts_only = false;  // no constraint is a joint (note_kinds): every row has a contact's bounds, (-1, -1, 0) .. (1, 1, +inf)
   int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
   // which kernel takes the oversize islands of a GS / SOR solve (choose_oversize_schedule; EGS_PATCH=0
   // forces the all-global kernel, EGS_QUAD_PATCH=0 the 1-lane patches) and how many workgroups the

@@ -67,8 +67,11 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   s.linsym = !f32 && s.group == 1 && p->lin_neg && p->linsym_bodies == 1 && !(le && std::atoi(le) == 0);
   // ... with the assembly in its prologue: a fresh launch in which every constraint is a lane of some tile.
   // EGS_FUSED_ASSEMBLY=0 keeps assemble_kernel.  The ASSEMBLE form starts from rhs: a started solve is not offered it.
+  // Its sweep projects with a contact's bounds as literals and reads no lo, hi or is_eq (step_solve.hip), so the
+  // list must hold no joint at all.  LINSYM already implies it (lin_neg: no two-body joint; linsym_bodies: a body on
+  // side 1, where a one-body joint has none), but the kernel depends on it, so it is required here by name.
   const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
-  s.assemble = offer_assembly && s.linsym && !resume && !solve_takes_start(p) && pl.global.empty() && !(fe && std::atoi(fe) == 0);
+  s.assemble = offer_assembly && s.linsym && p->contacts_only && !resume && !solve_takes_start(p) && pl.global.empty() && !(fe && std::atoi(fe) == 0);
   // ... which stores no system (problem.h: ensure_system).  EGS_STEP_DEFER_SYSTEM=0 keeps the eager stores.
   const char *de = std::getenv("EGS_STEP_DEFER_SYSTEM");
   s.defer = s.assemble && !(de && std::atoi(de) == 0);

@@ -50,6 +50,14 @@ __device__ __forceinline__ T project(T x, T lo, T hi) {
   r = (x < lo) ? lo : r;
   return r;
 }
+// project() with a contact's bounds as literals (assemble_device.h: lo = (-1, -1, 0), hi = (1, 1, +inf)): the same
+// value for every input, NaN, -0.0 and +-inf included.  Friction rows: x > 1 and x < -1 exclude each other, so the
+// two selects are one on |x| > 1 with the bound's sign taken from x.  Normal row: x > +inf holds for no x.
+template <typename T>
+__device__ __forceinline__ T project_contact(T x, int r) {
+  if (r < 2) return (__builtin_fabs(x) > T(1)) ? (T)__builtin_copysign(T(1), x) : x;
+  return (x < T(0)) ? T(0) : x;
+}
 template <typename T>
 __device__ __forceinline__ void clamp_bounds(bool eq, T &lo, T &hi) {
   if (eq) { lo = -__builtin_huge_val(); hi = __builtin_huge_val(); }
@@ -112,8 +120,9 @@ __device__ __forceinline__ void acc_add_side1(REAL *a, const Cons<REAL> &c, cons
   if (ISO) acc_add_iso(a, c.J1, c.wl1, c.wa1, d); else acc_add(a, c.B1, d);
 }
 
-// ASSEMBLED (step_solve_kernel's ASSEMBLE form): c.J0 / c.J1, rhs, lo, hi and eq are in c already, from the assembly's
-// registers; only what is derived from them is formed here.
+// ASSEMBLED (step_solve_kernel's ASSEMBLE form): c.J0 / c.J1 and rhs are in c already, from the assembly's registers;
+// only what is derived from them is formed here.  Every lane of that form is a contact (solve.cpp: choose_sweep), whose
+// bounds are literals in the sweep (project_contact): c.lo, c.hi and c.eq are not used.
 template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false>
 __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bool has0, bool has1,
                                           int body0, int body1, Cons<REAL> &c) {
@@ -198,8 +207,8 @@ __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bo
       c.lo[r] = A.lo[(size_t)cidx * 3 + r];
       c.hi[r] = A.hi[(size_t)cidx * 3 + r];
       c.eq[r] = A.is_eq[(size_t)cidx * 3 + r] != 0;
+      clamp_bounds(c.eq[r], c.lo[r], c.hi[r]);
     }
-    clamp_bounds(c.eq[r], c.lo[r], c.hi[r]);
   }
 }
 
@@ -214,8 +223,8 @@ __device__ __forceinline__ void row_residuals(const Cons<REAL> &c, const REAL *a
   }
 }
 
-// One projected update of the 3 rows of a constraint; returns dx.
-template <typename REAL, int METHOD>
+// One projected update of the 3 rows of a constraint; returns dx.  CONTACT: the bounds are a contact's, as literals.
+template <typename REAL, int METHOD, bool CONTACT = false>
 __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res, REAL *x, REAL *dx) {
   if (METHOD == 0) {  // Jacobi: no intra-block coupling
 #pragma unroll
@@ -230,7 +239,8 @@ __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res
       REAL t = res[r];
 #pragma unroll
       for (int l = 0; l < r; ++l) t = tfma(-c.D[3 * r + l], dx[l], t);
-      REAL xn = project(tfma(t, c.inv[r], x[r]), c.lo[r], c.hi[r]);
+      const REAL xu = tfma(t, c.inv[r], x[r]);
+      REAL xn = CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
       dx[r] = xn - x[r];
       x[r] = xn;
     }
@@ -240,7 +250,8 @@ __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res
       REAL t = res[r];
 #pragma unroll
       for (int l = 2; l > r; --l) t = tfma(-c.D[3 * r + l], dx[l], t);
-      REAL xn = project(tfma(t, c.inv[r], x[r]), c.lo[r], c.hi[r]);
+      const REAL xu = tfma(t, c.inv[r], x[r]);
+      REAL xn = CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
       dx[r] = xn - x[r];
       x[r] = xn;
     }

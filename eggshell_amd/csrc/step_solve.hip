@@ -38,6 +38,11 @@
 // solve (get_blocks, the residual, matvec, later solves).  Nothing waits for these stores: they drain while the
 // timetable runs.  Every constraint of the problem is a lane of some tile (solve.cpp: no oversize islands), so all of
 // them are written.
+// Every lane of this form is a contact (solve.cpp: choose_sweep requires a list without joints), so its sweep carries no
+// lo, hi or eq: the projection takes a contact's bounds as literals (solve_device.h: project_contact, the same value
+// as project() for every input).  The registers that frees hold side 0's nine angular products wa0 J0_ang, formed once
+// after load_cons with the multiply an update would use (AngProducts below): the same bits, nine multiplies less per
+// update.
 // The steady-state loop (GROUP == 1, no snapshots, LINSYM or not ISO): between the first depth steps of a launch (the
 // fill: lanes still wait for their first turn, or run the accumulation) and its last ones (the drain: lanes have run
 // out of sweeps) every lane whose level matches the clock modulo P is due, in some sweep 1 .. sweeps.  There the
@@ -78,10 +83,50 @@ __device__ __forceinline__ void linsym_residuals(const Cons<REAL> &c, const REAL
   for (int r = 0; r < 3; ++r) res[r] = c.rhs[r] - tfma(cfm, x[r], linsym_row_dot(c, r, a0, a1));
 }
 
-// acc_add_iso with the linear half from +-Bl (NEG: side 1) and the angular half w J formed on the fly.  wa is the
-// loop-carried register itself, made opaque by the caller: no copy per update.
-template <bool NEG, typename REAL>
-__device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, const REAL *Ja, REAL wa, const REAL *d) {
+// How many of the 18 angular products wa J_ang of an update an ASSEMBLE instantiation forms once, after load_cons, and
+// holds in registers through both loops (AngProducts): the largest count at which the instantiation keeps scratch 0
+// and at most 168 VGPRs (three wavefronts per SIMD), found by compiling every count.  The
+// registers are those the literal bounds of the contact projection freed (solve_device.h: project_contact).
+// Nine = all of side 0, after which wa0 is not live in the loops; ten spill 12 bytes in every one of the four.
+constexpr int kAngFree[2] = {9, 9};    // store-free (the headline): GS, backward SOR
+constexpr int kAngStore[2] = {9, 9};   // storing
+template <int METHOD, bool STORE_SYSTEM>
+constexpr int ang_products() {
+  return STORE_SYSTEM ? kAngStore[METHOD - 1] : kAngFree[METHOD - 1];
+}
+
+// Held products in the order side 0 then side 1, per side column-major as linsym_acc_add uses them: product i of a
+// side is wa J[6 (i % 3) + 3 + i / 3].  HELD = 0: nothing is held.
+template <typename REAL, int HELD>
+struct AngProducts {
+  REAL p[HELD > 0 ? HELD : 1];
+  template <int SIDE>
+  __device__ __forceinline__ void form(const REAL *J, REAL wa) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      if (9 * SIDE + i < HELD) {
+        p[9 * SIDE + i] = wa * J[6 * (i % 3) + 3 + i / 3];   // the one multiply of linsym_acc_add: the same rounding
+        asm volatile("" : "+v"(p[9 * SIDE + i]));             // opaque: held, not formed again where it is used
+      }
+    }
+  }
+};
+
+// The weights of the products formed on the fly, opaque to the optimiser in place: the products stay in the update
+// (not hoisted into registers of the compiler's choosing).  A side whose nine products are held needs no wa.
+template <int HELD, typename REAL>
+__device__ __forceinline__ void opaque_wa(Cons<REAL> &c) {
+  if constexpr (HELD < 9) asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
+  else if constexpr (HELD < 18) asm volatile("" : "+v"(c.wa1));
+}
+
+// acc_add_iso with the linear half from +-Bl (NEG: side 1) and the angular half w J formed on the fly, or taken from
+// the held products (SIDE's first of them).  wa is the loop-carried register itself, made opaque by the caller: no
+// copy per update.
+template <bool NEG, int HELD = 0, typename REAL>
+__device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, const REAL *Ja, REAL wa, const REAL *d,
+                                               const AngProducts<REAL, HELD> &h = AngProducts<REAL, HELD>()) {
+  constexpr int SIDE = NEG ? 1 : 0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const REAL *B = c.J1 + k;   // Bl[r][k] at B[6 r]
@@ -91,15 +136,17 @@ __device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, con
   }
 #pragma unroll
   for (int k = 3; k < 6; ++k) {
-    REAL t = tfma(wa * Ja[k], d[0], a[k]);
-    t = tfma(wa * Ja[6 + k], d[1], t);
-    a[k] = tfma(wa * Ja[12 + k], d[2], t);
+    const int i = 9 * SIDE + 3 * (k - 3);
+    REAL t = tfma(i < HELD ? h.p[i] : wa * Ja[k], d[0], a[k]);
+    t = tfma(i + 1 < HELD ? h.p[i + 1] : wa * Ja[6 + k], d[1], t);
+    a[k] = tfma(i + 2 < HELD ? h.p[i + 2] : wa * Ja[12 + k], d[2], t);
   }
 }
 
 // The ASSEMBLE prologue of one lane: K1-K4 for constraint cidx (J0 / J1 into c, for stage_blocks and load_cons), rhs,
 // err, lo, hi and is_eq to global memory where assemble_kernel puts them (24 B per lane and array: a few lines per
-// store instruction), rhs, lo, hi and eq into c.  STORE = false: into c only.
+// store instruction), rhs into c.  STORE = false: into c only.  The bounds do not go into c: the sweep of this form
+// projects with a contact's literals.
 template <bool STORE>
 __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, Cons<double> &c) {
   double e[3], lo[3], hi[3], u0[6], u1[6];
@@ -115,9 +162,6 @@ __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, C
       reinterpret_cast<double *>(G.hi)[(size_t)cidx * 3 + r] = hi[r];
       G.is_eq[(size_t)cidx * 3 + r] = eq ? 1 : 0;
     }
-    c.lo[r] = lo[r];
-    c.hi[r] = hi[r];
-    c.eq[r] = eq;
   }
 }
 
@@ -204,11 +248,19 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
       for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = REAL(0);
     }
   }
+  // ASSEMBLE: every lane is a contact (solve.cpp: choose_sweep), so the projection takes its bounds as literals, and
+  // some of the angular products of B are formed once, after load_cons
+  constexpr int HELD = ASSEMBLE ? ang_products<METHOD, STORE_SYSTEM>() : 0;
+  AngProducts<REAL, HELD> held;
   if (active) {
     if constexpr (ASSEMBLE) load_cons<REAL, true, true, true>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
     else load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
     for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
+    if constexpr (HELD > 0) {
+      held.template form<0>(c.J0, c.wa0);
+      held.template form<1>(c.J1, c.wa1);
+    }
   }
   const unsigned ac0 = lds_addr(s_acc + slot0 * 6), ac1 = lds_addr(s_acc + slot1 * 6);
   // snapshots for the per-sweep stopping test (kernels.h): is this lane the last update of its body in a sweep?
@@ -266,13 +318,12 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
           REAL res[3];
           if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
           else row_residuals(c, a0, a1, x, A.cfm, res);
-          update_rows<REAL, METHOD>(c, res, x, dx);
+          update_rows<REAL, METHOD, ASSEMBLE>(c, res, x, dx);
         }
         if (LINSYM) {
-          // opaque to the optimiser in place: the products wa J stay in the update (not hoisted into 36 registers)
-          asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
-          if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
-          if (has1) { linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx); store6(ac1, a1); }
+          opaque_wa<HELD>(c);
+          if (has0) { linsym_acc_add<false, HELD>(a0, c, c.J0, c.wa0, dx, held); store6(ac0, a0); }
+          if (has1) { linsym_acc_add<true, HELD>(a1, c, c.J1, c.wa1, dx, held); store6(ac1, a1); }
         } else {
           if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
           if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
@@ -309,11 +360,11 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
         load12(ac0, ac1, a0, a1);
         if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
         else row_residuals(c, a0, a1, x, A.cfm, res);
-        update_rows<REAL, METHOD>(c, res, x, dx);
+        update_rows<REAL, METHOD, ASSEMBLE>(c, res, x, dx);
         if (LINSYM) {
-          asm volatile("" : "+v"(c.wa0), "+v"(c.wa1));
-          if (has0) { linsym_acc_add<false>(a0, c, c.J0, c.wa0, dx); store6(ac0, a0); }
-          linsym_acc_add<true>(a1, c, c.J1, c.wa1, dx);   // every active lane has side 1 (solve.cpp)
+          opaque_wa<HELD>(c);
+          if (has0) { linsym_acc_add<false, HELD>(a0, c, c.J0, c.wa0, dx, held); store6(ac0, a0); }
+          linsym_acc_add<true, HELD>(a1, c, c.J1, c.wa1, dx, held);   // every active lane has side 1 (solve.cpp)
           store6(ac1, a1);
         } else {
           if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
