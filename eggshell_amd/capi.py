@@ -23,6 +23,7 @@ SCHED_LINSYM = 128
 SCHED_FUSED_ASSEMBLY = 256
 SCHED_DEFERRED_SYSTEM = 512
 SCHED_START = 1024
+SCHED_FRICTION = 2048
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
@@ -47,6 +48,7 @@ EXPORTS = [
     "egs_world_stabilize_direct", "egs_world_stabilize_rank", "egs_relax_blocks_direct",
     "egs_world_step_each", "egs_world_step_dense_each",
     "egs_problem_set_start", "egs_match_contacts", "egs_world_set_warm_start", "egs_world_get_start",
+    "egs_problem_set_friction", "egs_world_set_friction",
 ]
 
 
@@ -585,6 +587,14 @@ class Problem:
             raise ValueError("x0: %d rows for %d constraints" % (x0.size, self.m))
         self.ctx.check(load().egs_problem_set_start(self.h, C.c_int32(mode), _p(x0)))
 
+    def set_friction(self, mu=None):
+        """The Coulomb pyramid (egs_problem_set_friction): one coefficient per constraint, >= 0: the tangential rows are
+        bounded by +-mu x_n, < 0: the stored bounds.  None, or no coefficient >= 0, turns friction off."""
+        mu = _f64(mu)
+        if mu is not None and mu.size != self.m:
+            raise ValueError("mu: %d coefficients for %d constraints" % (mu.size, self.m))
+        self.ctx.check(load().egs_problem_set_friction(self.h, _p(mu)))
+
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
         w = np.zeros(3 * self.m)
@@ -874,6 +884,12 @@ class World:
         b0 = np.zeros(m, np.int32); b1 = np.zeros(m, np.int32); data = np.zeros((m, 7)); mo = C.c_int32(0)
         self.ctx.check(load().egs_world_get_contacts(self.h, C.c_int32(m), C.byref(mo), _p(b0), _p(b1), _p(data)))
         return b0, b1, data
+
+    def set_friction(self, mu):
+        """The Coulomb pyramid per ensemble (egs_world_set_friction): every contact of ensemble e takes mu[e] (a scalar
+        for a plain world), joints none; mu[e] < 0 keeps the reference's friction box."""
+        mu = np.atleast_1d(_f64(mu))
+        self.ctx.check(load().egs_world_set_friction(self.h, C.c_int32(mu.shape[0]), _p(mu)))
 
     def set_warm_start(self, enable, match_radius=0.01):
         """Sweep steps start from the previous step's lambda (egs_world_set_warm_start): a contact takes the rows of the

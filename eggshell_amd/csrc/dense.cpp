@@ -157,6 +157,7 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
   if (!p) return EGS_ERR_INVALID;
   if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
+  if (p->friction) return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (ok) *ok = 0;
   return guarded(p->ctx, [&]() -> egs_status {
     egs_context *ctx = p->ctx;

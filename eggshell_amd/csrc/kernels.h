@@ -83,6 +83,9 @@ struct SolveArgs {
   // the start of a fresh launch (!resume), [3m]; NULL: rhs, Q7.  Never aliases x.  step_solve_kernel's ASSEMBLE form
   // does not read it: a started step assembles with assemble_kernel (solve.cpp: choose_sweep)
   const REAL *x0 = nullptr;
+  // Coulomb pyramid: one coefficient per constraint [m], >= 0: rows 0 and 1 are bounded by +-mu x_n (solve_device.h:
+  // project_pyramid), < 0: the stored bounds.  NULL = friction off: the launch runs the instantiations without it.
+  const REAL *mu = nullptr;
 };
 
 template <typename REAL>
@@ -105,6 +108,7 @@ struct GlobalArgs {
   int32_t m = 0, pad1 = 0;     // all constraints of the problem (hist_x stride)
   REAL *hist_x = nullptr, *hist_acc = nullptr;
   const REAL *x0 = nullptr;    // the start of a fresh launch, as in SolveArgs (NULL: rhs, Q7)
+  const REAL *mu = nullptr;    // the friction coefficients, as in SolveArgs (NULL: off)
 };
 
 
@@ -156,11 +160,13 @@ void launch_assemble(const AssembleArgs &a, hipStream_t s);
 // ... with every constraint on its ensemble's rates (a.dt and a.erp are not read)
 template <typename REAL>
 void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStream_t s);
-// partial sums of squares by row category: out[4*blocks]
+// partial sums of squares by row category: out[4*blocks].  mu [rows / 3] (may be NULL: off): rows 0 and 1 of a
+// constraint with mu >= 0 are sorted by the pyramid's bounds, as in the kernels below that
+// take the coefficients from SolveArgs::mu.
 template <typename REAL>
 void launch_residual_partials(int rows, const REAL *wres, const REAL *x,
                               const REAL *lo, const REAL *hi,
-                              const uint8_t *is_eq, double *out, int blocks,
+                              const uint8_t *is_eq, const REAL *mu, double *out, int blocks,
                               hipStream_t s);
 template <typename REAL>
 void launch_velocity(int n, const double *v, const double *w, const double *Wf, const REAL *acc,
@@ -208,6 +214,13 @@ void launch_seg_select(const EnsembleSegs &S, const EnsembleStop &T, const doubl
                        const REAL *as, size_t astride, REAL *fin_x, REAL *fin_acc, hipStream_t s);
 // fixed sweep count: iterations[e] = sweeps (0 for an ensemble without constraints), residual[e] = err[e]
 void launch_seg_fixed(const EnsembleSegs &S, const EnsembleStop &T, const double *err, int sweeps, hipStream_t s);
+
+// The per-constraint friction coefficients of a world's list (egs_world_set_friction): constraint i < mj is a joint and
+// gets -1, a contact gets mu_ens[ensemble of its first body] (body_ens == NULL: a plain world, ensemble 0), rounded to
+// REAL.
+template <typename REAL>
+void launch_fill_friction(int m, int mj, const int32_t *body0, const int32_t *body1, const int32_t *body_ens,
+                          const double *mu_ens, REAL *mu, hipStream_t s);
 
 template <typename REAL>
 void launch_convert_minv(int count, const double *src, REAL *dst, hipStream_t s);

@@ -77,7 +77,8 @@ __device__ __forceinline__ bool ordered_accumulate(REAL *s_acc, unsigned *s_tick
 // entry and is formed on the fly instead of living in 72 VGPRs: 164 instead of 232 VGPRs,
 // three wavefronts per SIMD instead of two, i.e. 768 instead of 512 constraints resident
 // per CU.  Same products, same roundings, same bits.
-template <typename REAL, int BLOCK, int METHOD, bool ISO>
+// FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.
+template <typename REAL, int BLOCK, int METHOD, bool ISO, bool FRIC = false>
 __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) tile_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   REAL *s_acc = reinterpret_cast<REAL *>(smem);
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
   const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
-    load_cons<REAL, ISO>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+    load_cons<REAL, ISO, false, false, FRIC>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
     for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
@@ -130,7 +131,7 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
         lds_load6(s_acc + slot0 * 6, a0);
         lds_load6(s_acc + slot1 * 6, a1);
         row_residuals(c, a0, a1, x, A.cfm, res);
-        update_rows<REAL, 0>(c, res, x, dx);
+        update_rows<REAL, 0, false, FRIC>(c, res, x, dx);
       }
       __syncthreads();  // every lane has read the old accumulators
       ok &= ordered_accumulate<ISO>(s_acc, s_tick, c, dx, active, has0, has1, slot0, slot1,
@@ -174,7 +175,7 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
       if (ready) {
         REAL res[3], dx[3] = {REAL(0), REAL(0), REAL(0)};
         row_residuals(c, a0, a1, x, A.cfm, res);
-        update_rows<REAL, METHOD>(c, res, x, dx);
+        update_rows<REAL, METHOD, false, FRIC>(c, res, x, dx);
         if (has0) { acc_add_side0<ISO>(a0, c, dx); store6(ac0, a0); }
         if (has1) { acc_add_side1<ISO>(a1, c, dx); store6(ac1, a1); }
         if (has0) store_tick(tk0, want0 + 1);
@@ -233,16 +234,19 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
 // --------------------------------------------------------------------------
 // residual partial sums (sparse_iterations.cc:51-69): per block 4 sums of w^2
 // over {equality, at lo & w<0, at hi & w>0, strictly inside}.
-template <typename REAL>
+// FRIC: rows 0 and 1 of a constraint with mu >= 0 by the pyramid's rule (solve_device.h: pyramid_residual), the
+// normal multiplier being row 3i + 2 of the same x.  Without FRIC mu is not read.
+template <typename REAL, bool FRIC = false>
 __global__ void __launch_bounds__(256) residual_partials_kernel(int rows, const REAL *wres, const REAL *x,
                                                                 const REAL *lo, const REAL *hi,
-                                                                const uint8_t *is_eq, double *out) {
+                                                                const uint8_t *is_eq, double *out, const REAL *mu = nullptr) {
   __shared__ double red[4][256];
   double e = 0, a = 0, b = 0, c = 0;
   for (int r = blockIdx.x * 256 + threadIdx.x; r < rows; r += gridDim.x * 256) {
     const double w = (double)wres[r];
     const REAL xv = x[r], l = lo[r], h = hi[r];
-    if (is_eq[r]) e += w * w;
+    if (FRIC && r % 3 < 2 && mu[r / 3] >= REAL(0)) pyramid_residual(xv, w, mu[r / 3], x[r - r % 3 + 2], a, b, c);
+    else if (is_eq[r]) e += w * w;
     else {
       if (xv == l && w < 0) a += w * w;
       if (xv == h && w > 0) b += w * w;
@@ -267,7 +271,7 @@ __global__ void __launch_bounds__(256) residual_partials_kernel(int rows, const 
 // once and serve G sweeps (per sweep only lambda and the two accumulators change), instead of re-streaming
 // 300 B of J per row and sweep.  Per sweep every thread adds the same rows in the same order and the block
 // reduces them the same way as before, so the sums have the same bits.
-template <typename REAL, int G>
+template <typename REAL, int G, bool FRIC = false>
 __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL> A, double *out, int write_sweep, int sweeps) {
   __shared__ double red[4][256];
   const int s0 = blockIdx.y * G;          // first sweep of the group, 0-based
@@ -286,6 +290,7 @@ __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL
     }
     const REAL l = A.lo[r], h = A.hi[r], rhs = A.rhs[r];
     const bool eq = A.is_eq[r] != 0;
+    const REAL mu = (FRIC && rr < 2) ? A.mu[i] : REAL(-1);   // < 0: the stored bounds
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       const int sweep = s0 + g;
@@ -301,7 +306,11 @@ __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL
       const REAL wr = tfma(A.cfm, xv, row_dot(j0, a0, j1, a1)) - rhs;
       if (write_sweep == sweep + 1) A.wres[r] = wr;
       const double w = (double)wr;
-      if (eq) acc[g][0] += w * w;
+      if (FRIC && mu >= REAL(0)) {
+        double s_lo = 0, s_hi = 0, s_in = 0;
+        pyramid_residual(xv, w, mu, A.hist_x[(size_t)sweep * A.m * 3 + 3 * i + 2], s_lo, s_hi, s_in);
+        acc[g][1] += s_lo; acc[g][2] += s_hi; acc[g][3] += s_in;
+      } else if (eq) acc[g][0] += w * w;
       else {
         if (xv == l && w < 0) acc[g][1] += w * w;
         if (xv == h && w > 0) acc[g][2] += w * w;
@@ -331,7 +340,7 @@ __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL
 // added by thread lr % 256 of block (lr / 256) % kResidualBlocks in ascending lr, each block reduces as
 // residual_partials_kernel does, and the block sums are added in block order as read_residual adds them.
 // Blocks beyond the ensemble's rows would contribute +0.0 to sums that are >= 0 (or NaN): skipped.
-template <typename REAL>
+template <typename REAL, bool FRIC = false>
 __global__ void __launch_bounds__(256) seg_residual_kernel(const SolveArgs<REAL> A, const EnsembleSegs S, const int32_t *running,
                                                            const REAL *xs, const REAL *as, const REAL *ws, double *err) {
   __shared__ double red[4][256];
@@ -365,7 +374,11 @@ __global__ void __launch_bounds__(256) seg_residual_kernel(const SolveArgs<REAL>
         }
         w = (double)(tfma(A.cfm, xv, row_dot(j0v, a0, j1v, a1)) - A.rhs[r]);
       }
-      if (A.is_eq[r]) acc[0] += w * w;
+      if (FRIC && r % 3 < 2 && A.mu[r / 3] >= REAL(0)) {
+        double s_lo = 0, s_hi = 0, s_in = 0;
+        pyramid_residual(xv, w, A.mu[r / 3], hx[r - r % 3 + 2], s_lo, s_hi, s_in);
+        acc[1] += s_lo; acc[2] += s_hi; acc[3] += s_in;
+      } else if (A.is_eq[r]) acc[0] += w * w;
       else {
         if (xv == l && w < 0) acc[1] += w * w;
         if (xv == h && w > 0) acc[2] += w * w;
@@ -503,6 +516,15 @@ __global__ void __launch_bounds__(256) advance_kernel(int n, const BodyState in,
 __global__ void __launch_bounds__(256) advance_each_kernel(int n, const BodyState state, const double *v6,
                                                            const int32_t *body_ens, const double *dt_each) {
   advance_body<true>(n, state, state, v6, 0.0, body_ens, dt_each);
+}
+
+template <typename REAL>
+__global__ void __launch_bounds__(256) fill_friction_kernel(int m, int mj, const int32_t *body0, const int32_t *body1,
+                                                            const int32_t *body_ens, const double *mu_ens, REAL *mu) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const int b = body0[i] >= 0 ? body0[i] : body1[i];   // as constraint_rates: the first body's ensemble
+  mu[i] = i < mj ? REAL(-1) : (REAL)mu_ens[body_ens ? body_ens[b] : 0];
 }
 
 template <typename REAL>
@@ -644,7 +666,7 @@ __global__ void __launch_bounds__(256) cons_prepare_kernel(const SolveArgs<REAL>
   flush(c.inv, 3, A.wsInv);
 }
 
-template <typename REAL>
+template <typename REAL, bool FRIC = false>
 __device__ __forceinline__ void gload_cons(const GlobalArgs<REAL> &A, int g, const GlobalDesc &d, Cons<REAL> &c) {
   const bool has0 = d.body0 >= 0, has1 = d.body1 >= 0;
 #pragma unroll
@@ -665,9 +687,14 @@ __device__ __forceinline__ void gload_cons(const GlobalArgs<REAL> &A, int g, con
     c.eq[r] = A.is_eq[(size_t)d.cidx * 3 + r] != 0;
     clamp_bounds(c.eq[r], c.lo[r], c.hi[r]);
   }
+  if (FRIC) {
+    const REAL mu = A.mu[d.cidx];
+    c.pyr = mu >= REAL(0);
+    if (c.pyr) c.lo[0] = mu;
+  }
 }
 
-template <typename REAL, int METHOD>
+template <typename REAL, int METHOD, bool FRIC = false>
 __global__ void __launch_bounds__(256) global_solve_kernel(const GlobalArgs<REAL> A) {
   const int L = gridDim.x * 256, lane = blockIdx.x * 256 + threadIdx.x;
   const int per_lane = A.per_lane;
@@ -712,7 +739,7 @@ __global__ void __launch_bounds__(256) global_solve_kernel(const GlobalArgs<REAL
           a1[q] = has1 ? gld(A.acc + (size_t)d.body1 * 6 + q) : REAL(0);
         }
         Cons<REAL> c;
-        gload_cons(A, g, d, c);
+        gload_cons<REAL, FRIC>(A, g, d, c);
         if (p == 0) {
 #pragma unroll
           for (int r = 0; r < 3; ++r) dx[r] = A.dx[(size_t)g * 3 + r];
@@ -721,7 +748,7 @@ __global__ void __launch_bounds__(256) global_solve_kernel(const GlobalArgs<REAL
 #pragma unroll
           for (int r = 0; r < 3; ++r) { x[r] = A.x[(size_t)d.cidx * 3 + r]; dx[r] = REAL(0); }
           row_residuals(c, a0, a1, x, A.cfm, res);
-          update_rows<REAL, METHOD>(c, res, x, dx);
+          update_rows<REAL, METHOD, false, FRIC>(c, res, x, dx);
 #pragma unroll
           for (int r = 0; r < 3; ++r) A.x[(size_t)d.cidx * 3 + r] = x[r];
         }
@@ -770,13 +797,13 @@ __global__ void __launch_bounds__(256) global_solve_kernel(const GlobalArgs<REAL
 
 // Jacobi compute phase for the cross-workgroup path: x_new and dx from the
 // accumulators of the previous sweep (no ordering needed: read-only on acc).
-template <typename REAL>
+template <typename REAL, bool FRIC = false>
 __global__ void __launch_bounds__(256) global_jacobi_kernel(const GlobalArgs<REAL> A) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= A.mg) return;
   const GlobalDesc d = A.cons[g];
   Cons<REAL> c;
-  gload_cons(A, g, d, c);
+  gload_cons<REAL, FRIC>(A, g, d, c);
   REAL a0[6], a1[6], x[3], res[3], dx[3];
 #pragma unroll
   for (int q = 0; q < 6; ++q) {
@@ -786,7 +813,7 @@ __global__ void __launch_bounds__(256) global_jacobi_kernel(const GlobalArgs<REA
 #pragma unroll
   for (int r = 0; r < 3; ++r) x[r] = A.x[(size_t)d.cidx * 3 + r];
   row_residuals(c, a0, a1, x, A.cfm, res);
-  update_rows<REAL, 0>(c, res, x, dx);
+  update_rows<REAL, 0, false, FRIC>(c, res, x, dx);
 #pragma unroll
   for (int r = 0; r < 3; ++r) { A.x[(size_t)d.cidx * 3 + r] = x[r]; A.dx[(size_t)g * 3 + r] = dx[r]; }
 }
@@ -877,12 +904,14 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
   if (n_tiles <= 0) return;
   const size_t lds = (size_t)a.max_slots * (6 * sizeof(REAL) + sizeof(unsigned));
   const dim3 g(n_tiles), b(block);
-#define EGS_LAUNCH_T(BLK, ISO)                                                                        \
-  switch (method) {                                                                                   \
-    case 0: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 0, ISO>), g, b, lds, s, a); break;       \
-    case 1: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 1, ISO>), g, b, lds, s, a); break;       \
-    default: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 2, ISO>), g, b, lds, s, a); break;      \
+#define EGS_LAUNCH_TF(BLK, ISO, FRIC)                                                                     \
+  switch (method) {                                                                                       \
+    case 0: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 0, ISO, FRIC>), g, b, lds, s, a); break;     \
+    case 1: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 1, ISO, FRIC>), g, b, lds, s, a); break;     \
+    default: hipLaunchKernelGGL((tile_solve_kernel<REAL, BLK, 2, ISO, FRIC>), g, b, lds, s, a); break;    \
   }
+#define EGS_LAUNCH_T(BLK, ISO) \
+  if (a.mu != nullptr) { EGS_LAUNCH_TF(BLK, ISO, true) } else { EGS_LAUNCH_TF(BLK, ISO, false) }
 #define EGS_LAUNCH(BLK) EGS_LAUNCH_T(BLK, false)
   if (block == 256 && a.iso) { EGS_LAUNCH_T(256, true) }
   else if (block == 256) { EGS_LAUNCH(256) }
@@ -891,6 +920,7 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
   else { EGS_LAUNCH(512) }
 #undef EGS_LAUNCH
 #undef EGS_LAUNCH_T
+#undef EGS_LAUNCH_TF
 }
 
 template <typename REAL>
@@ -907,22 +937,26 @@ void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStre
 
 template <typename REAL>
 void launch_residual_partials(int rows, const REAL *wres, const REAL *x, const REAL *lo, const REAL *hi,
-                              const uint8_t *is_eq, double *out, int blocks, hipStream_t s) {
-  hipLaunchKernelGGL((residual_partials_kernel<REAL>), dim3(blocks), dim3(256), 0, s, rows, wres, x, lo, hi, is_eq, out);
+                              const uint8_t *is_eq, const REAL *mu, double *out, int blocks, hipStream_t s) {
+  if (mu) hipLaunchKernelGGL((residual_partials_kernel<REAL, true>), dim3(blocks), dim3(256), 0, s, rows, wres, x, lo, hi, is_eq, out, mu);
+  else hipLaunchKernelGGL((residual_partials_kernel<REAL>), dim3(blocks), dim3(256), 0, s, rows, wres, x, lo, hi, is_eq, out, mu);
 }
 
 template <typename REAL>
 void launch_hist_residual(const SolveArgs<REAL> &a, int sweeps, int blocks, double *out, int write_sweep, hipStream_t s) {
   if (sweeps <= 0 || a.m <= 0) return;
   constexpr int G = 8;   // recorded sweeps that share one pass over the J blocks
-  hipLaunchKernelGGL((hist_residual_kernel<REAL, G>), dim3(blocks, (sweeps + G - 1) / G), dim3(256), 0, s, a, out, write_sweep, sweeps);
+  const dim3 grid(blocks, (sweeps + G - 1) / G);
+  if (a.mu) hipLaunchKernelGGL((hist_residual_kernel<REAL, G, true>), grid, dim3(256), 0, s, a, out, write_sweep, sweeps);
+  else hipLaunchKernelGGL((hist_residual_kernel<REAL, G>), grid, dim3(256), 0, s, a, out, write_sweep, sweeps);
 }
 
 template <typename REAL>
 void launch_seg_residual(const SolveArgs<REAL> &a, const EnsembleSegs &S, const int32_t *running, const REAL *xs,
                          const REAL *as, const REAL *ws, int sweeps, double *err, hipStream_t s) {
   if (S.n_ens <= 0 || sweeps <= 0) return;
-  hipLaunchKernelGGL((seg_residual_kernel<REAL>), dim3(S.n_ens, sweeps), dim3(256), 0, s, a, S, running, xs, as, ws, err);
+  if (a.mu) hipLaunchKernelGGL((seg_residual_kernel<REAL, true>), dim3(S.n_ens, sweeps), dim3(256), 0, s, a, S, running, xs, as, ws, err);
+  else hipLaunchKernelGGL((seg_residual_kernel<REAL>), dim3(S.n_ens, sweeps), dim3(256), 0, s, a, S, running, xs, as, ws, err);
 }
 
 template <typename REAL>
@@ -971,6 +1005,13 @@ void launch_advance_each(int n, const BodyState &state, const double *v6, const 
 }
 
 template <typename REAL>
+void launch_fill_friction(int m, int mj, const int32_t *body0, const int32_t *body1, const int32_t *body_ens,
+                          const double *mu_ens, REAL *mu, hipStream_t s) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL((fill_friction_kernel<REAL>), dim3((m + 255) / 256), dim3(256), 0, s, m, mj, body0, body1, body_ens, mu_ens, mu);
+}
+
+template <typename REAL>
 void launch_convert_minv(int count, const double *src, REAL *dst, hipStream_t s) {
   if (count <= 0) return;
   hipLaunchKernelGGL((convert_kernel<REAL>), dim3((count + 255) / 256), dim3(256), 0, s, count, src, dst);
@@ -991,10 +1032,13 @@ void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, con
 
 template <typename REAL>
 int occupancy_global_solve() {
-  int a = 0, b = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, global_solve_kernel<REAL, 1>, 256, 0) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, global_solve_kernel<REAL, 2>, 256, 0) != hipSuccess) return 0;
-  return a < b ? a : b;
+  int best = 1 << 30, nb = 0;   // the friction forms included: the persistent grid is sized once for all of them
+#define EGS_OCC(M, F)                                                                                               \
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, global_solve_kernel<REAL, M, F>, 256, 0) != hipSuccess) return 0; \
+  best = nb < best ? nb : best;
+  EGS_OCC(1, false) EGS_OCC(2, false) EGS_OCC(1, true) EGS_OCC(2, true)
+#undef EGS_OCC
+  return best;
 }
 template int occupancy_global_solve<double>();
 template int occupancy_global_solve<float>();
@@ -1011,6 +1055,7 @@ void launch_global_solve(const GlobalArgs<REAL> &a0, int max_blocks, hipStream_t
   a.per_lane = (a.mg + grid * 256 - 1) / (grid * 256);
   const size_t tick_bytes = sizeof(uint32_t) * (size_t)(a.n_bodies > 0 ? a.n_bodies : 1);
   hipLaunchKernelGGL((global_prepare_kernel<REAL>), dim3(flat_blocks), dim3(256), 0, s, a);
+  const bool fric = a.mu != nullptr;   // the ordered accumulation (mode 1) projects nothing: it has no friction form
   if (a.method == 0) {
     if (!a.resume) {  // accumulators from x0
       a.mode = 1;
@@ -1018,7 +1063,8 @@ void launch_global_solve(const GlobalArgs<REAL> &a0, int max_blocks, hipStream_t
       hipLaunchKernelGGL((global_solve_kernel<REAL, 1>), dim3(grid), dim3(256), 0, s, a);
     }
     for (int it = 0; it < a.sweeps; ++it) {
-      hipLaunchKernelGGL((global_jacobi_kernel<REAL>), dim3(flat_blocks), dim3(256), 0, s, a);
+      if (fric) hipLaunchKernelGGL((global_jacobi_kernel<REAL, true>), dim3(flat_blocks), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((global_jacobi_kernel<REAL>), dim3(flat_blocks), dim3(256), 0, s, a);
       a.mode = 1;
       (void)hipMemsetAsync(a.tickets, 0, tick_bytes, s);
       hipLaunchKernelGGL((global_solve_kernel<REAL, 1>), dim3(grid), dim3(256), 0, s, a);
@@ -1026,7 +1072,9 @@ void launch_global_solve(const GlobalArgs<REAL> &a0, int max_blocks, hipStream_t
   } else {
     a.mode = 0;
     (void)hipMemsetAsync(a.tickets, 0, tick_bytes, s);
-    if (a.method == 1) hipLaunchKernelGGL((global_solve_kernel<REAL, 1>), dim3(grid), dim3(256), 0, s, a);
+    if (a.method == 1 && fric) hipLaunchKernelGGL((global_solve_kernel<REAL, 1, true>), dim3(grid), dim3(256), 0, s, a);
+    else if (a.method == 1) hipLaunchKernelGGL((global_solve_kernel<REAL, 1>), dim3(grid), dim3(256), 0, s, a);
+    else if (fric) hipLaunchKernelGGL((global_solve_kernel<REAL, 2, true>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((global_solve_kernel<REAL, 2>), dim3(grid), dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL((global_wres_kernel<REAL>), dim3(flat_blocks), dim3(256), 0, s, a);
@@ -1052,12 +1100,14 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_assemble<REAL>(const AssembleArgs &, hipStream_t);                                    \
   template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, hipStream_t);        \
   template void launch_residual_partials<REAL>(int, const REAL *, const REAL *, const REAL *, const REAL *,  \
-                                               const uint8_t *, double *, int, hipStream_t);                 \
+                                               const uint8_t *, const REAL *, double *, int, hipStream_t);   \
   template void launch_velocity<REAL>(int, const double *, const double *, const double *, const REAL *, double,   \
                                       double *, hipStream_t);                          \
   template void launch_velocity_each<REAL>(int, const double *, const double *, const double *, const REAL *,      \
                                            const int32_t *, const double *, double *, hipStream_t);                 \
   template void launch_convert_minv<REAL>(int, const double *, REAL *, hipStream_t);                         \
+  template void launch_fill_friction<REAL>(int, int, const int32_t *, const int32_t *, const int32_t *,      \
+                                           const double *, REAL *, hipStream_t);                             \
   template void launch_minv_iso<REAL>(int, const REAL *, int *, hipStream_t);                               \
   template void launch_linsym_bodies<REAL>(int, const int32_t *, const int32_t *, const REAL *, int *, hipStream_t);                               \
   template void launch_hist_residual<REAL>(const SolveArgs<REAL> &, int, int, double *, int, hipStream_t);   \

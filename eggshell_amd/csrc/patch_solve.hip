@@ -20,7 +20,8 @@ namespace {
 
 // HIST = true: records the per-sweep snapshots of SolveArgs::hist_x / hist_acc (tolerance-
 // terminated solves, kernels.h) -- a variant of its own so that the plain kernel keeps its registers.
-template <typename REAL, int METHOD, bool HIST>
+// FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.
+template <typename REAL, int METHOD, bool HIST, bool FRIC = false>
 __global__ void __launch_bounds__(256) patch_solve_kernel(const SolveArgs<REAL> A, uint32_t *g_tick) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   REAL *s_acc = reinterpret_cast<REAL *>(smem);
@@ -50,7 +51,7 @@ __global__ void __launch_bounds__(256) patch_solve_kernel(const SolveArgs<REAL> 
   REAL x[3] = {REAL(0), REAL(0), REAL(0)};
   const REAL *xs = A.resume ? A.x : A.x0;   // the previous launch's x, a given start, or NULL: rhs (Q7)
   if (active) {
-    load_cons(A, d.cidx, has0, has1, gb0, gb1, c);
+    load_cons<REAL, false, false, false, FRIC>(A, d.cidx, has0, has1, gb0, gb1, c);
 #pragma unroll
     for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
   }
@@ -105,7 +106,7 @@ __global__ void __launch_bounds__(256) patch_solve_kernel(const SolveArgs<REAL> 
       } else {
         REAL res[3];
         row_residuals(c, a0, a1, x, A.cfm, res);
-        update_rows<REAL, METHOD>(c, res, x, dx);
+        update_rows<REAL, METHOD, false, FRIC>(c, res, x, dx);
       }
       if (has0) {
         acc_add(a0, c.B0, dx);
@@ -187,10 +188,13 @@ void launch_patch_solve(const SolveArgs<REAL> &a, int method, int n_tiles, uint3
   if (n_tiles <= 0) return;
   const size_t lds = (size_t)a.max_slots * (6 * sizeof(REAL) + sizeof(unsigned));
   const bool hist = a.hist_x != nullptr;
-  if (method == 1 && hist) hipLaunchKernelGGL((patch_solve_kernel<REAL, 1, true>), dim3(n_tiles), dim3(256), lds, s, a, tickets);
-  else if (method == 1) hipLaunchKernelGGL((patch_solve_kernel<REAL, 1, false>), dim3(n_tiles), dim3(256), lds, s, a, tickets);
-  else if (hist) hipLaunchKernelGGL((patch_solve_kernel<REAL, 2, true>), dim3(n_tiles), dim3(256), lds, s, a, tickets);
-  else hipLaunchKernelGGL((patch_solve_kernel<REAL, 2, false>), dim3(n_tiles), dim3(256), lds, s, a, tickets);
+#define EGS_PLAUNCH(F)                                                                                                              \
+  if (method == 1 && hist) hipLaunchKernelGGL((patch_solve_kernel<REAL, 1, true, F>), dim3(n_tiles), dim3(256), lds, s, a, tickets);    \
+  else if (method == 1) hipLaunchKernelGGL((patch_solve_kernel<REAL, 1, false, F>), dim3(n_tiles), dim3(256), lds, s, a, tickets);     \
+  else if (hist) hipLaunchKernelGGL((patch_solve_kernel<REAL, 2, true, F>), dim3(n_tiles), dim3(256), lds, s, a, tickets);             \
+  else hipLaunchKernelGGL((patch_solve_kernel<REAL, 2, false, F>), dim3(n_tiles), dim3(256), lds, s, a, tickets);
+  if (a.mu != nullptr) { EGS_PLAUNCH(true) } else { EGS_PLAUNCH(false) }
+#undef EGS_PLAUNCH
 }
 
 // Workgroups of this kernel one CU keeps resident (the smallest over its instantiations):
@@ -200,6 +204,12 @@ int occupancy_patch_solve(size_t lds) {
   int best = 1 << 30, nb = 0;
 #define EGS_OCC(M, H)                                                                                              \
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, patch_solve_kernel<REAL, M, H>, 256, lds) != hipSuccess) return 0; \
+  best = nb < best ? nb : best;
+  EGS_OCC(1, true) EGS_OCC(1, false) EGS_OCC(2, true) EGS_OCC(2, false)
+#undef EGS_OCC
+  // ... the friction forms included: the grid is capped once for all of them
+#define EGS_OCC(M, H)                                                                                                    \
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, patch_solve_kernel<REAL, M, H, true>, 256, lds) != hipSuccess) return 0; \
   best = nb < best ? nb : best;
   EGS_OCC(1, true) EGS_OCC(1, false) EGS_OCC(2, true) EGS_OCC(2, false)
 #undef EGS_OCC

@@ -364,6 +364,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   // the rows changed: x holds no lambda of this list, and a GIVEN start has the wrong length
   p->have_lambda = false;
   if (p->start_mode == EGS_START_GIVEN) p->start_mode = EGS_START_RHS;
+  p->friction = false;   // the coefficients were those of the old list (the world refills them: world.cpp)
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
     const int force = env ? std::atoi(env) : -1;
@@ -557,6 +558,25 @@ egs_status egs_problem_set_start(egs_problem *p, int32_t mode, const double *x0)
       upload_real(p, p->start, x0, rows);
     }
     p->start_mode = mode;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_friction(egs_problem *p, const double *mu) {
+  if (!p) return EGS_ERR_INVALID;
+  const size_t m = (size_t)p->m;
+  bool any = false;
+  for (size_t i = 0; mu && i < m; ++i) {
+    if (mu[i] != mu[i]) return fail(p->ctx, EGS_ERR_INVALID, "NaN friction coefficient");
+    any |= mu[i] >= 0;
+  }
+  return guarded(p->ctx, [&]() -> egs_status {
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));   // a solve in flight may still read the old coefficients
+    if (any) {
+      p->mu.alloc(m * p->real_size());
+      upload_real(p, p->mu, mu, m);
+    }
+    p->friction = any;
     return EGS_OK;
   });
 }

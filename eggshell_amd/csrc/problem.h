@@ -126,6 +126,12 @@ struct egs_problem {
   egs::DevBuf<unsigned char> start;
   bool have_lambda = false;    // x holds the lambda of a finished solve on the current constraint list
   bool start_active = false;
+  // The Coulomb pyramid (egs_problem_set_friction, egs_world_set_friction): mu [m] REAL, one coefficient per constraint,
+  // >= 0: rows 0 and 1 are bounded by +-mu x_n, < 0: the stored bounds.  friction: some coefficient is >= 0 -- the
+  // solve launches and the residual take mu and run their friction forms (solve.cpp: choose_sweep); off, nothing reads
+  // mu.  A new topology turns it off: the coefficients belong to the list they were given for.
+  egs::DevBuf<unsigned char> mu;
+  bool friction = false;
   bool minv_iso = false;       // every M^-1 block is diag(a,a,a,b,b,b): the tile kernel keeps no B (EGS_ISO=0 disables)
   int last_iterations = 0;
   size_t real_size() const { return precision == EGS_F32 ? sizeof(float) : sizeof(double); }

@@ -152,7 +152,9 @@ __device__ __forceinline__ bool gran_poll3(const Gran *p, unsigned long long tag
 // every slot, see below), the accumulators go from member to member through the row (row_shr:4, backward row_shl:4)
 // and the slot at the end publishes the last member's ticket + 1.  Same updates, same order, same bits -- three of
 // four hand-offs on such a body no longer go through LDS.
-template <typename REAL, int METHOD, int QT, bool PATCH, bool HIST, bool RUNS = false>
+// FRIC = true: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL; the
+// four lanes of a quad hold all three x, so each clamps rows 0 and 1 against the same x[2].
+template <typename REAL, int METHOD, int QT, bool PATCH, bool HIST, bool RUNS = false, bool FRIC = false>
 __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL> A, uint32_t *g_tick) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   REAL *s_acc = reinterpret_cast<REAL *>(smem);
@@ -203,6 +205,7 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
 
   REAL Jh[9], Bh[9], Dl[3], inv[3], rhs[3], lo[3], hi[3], x[3];
   bool eq[3];
+  bool pyr = false;     // FRIC: the constraint's friction coefficient is >= 0, and lo[0] holds it (that bound is dead)
 #pragma unroll
   for (int k = 0; k < 9; ++k) { Jh[k] = REAL(0); Bh[k] = REAL(0); }
 #pragma unroll
@@ -232,6 +235,11 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
       eq[r] = A.is_eq[c * 3 + r] != 0;
       clamp_bounds(eq[r], lo[r], hi[r]);
       x[r] = xs ? xs[c * 3 + r] : rhs[r];
+    }
+    if (FRIC) {
+      const REAL mu = A.mu[c];
+      pyr = mu >= REAL(0);
+      if (pyr) lo[0] = mu;
     }
   }
   __syncthreads();
@@ -383,10 +391,10 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
           }
           if (METHOD == 1) {
             REAL t0 = res[0];
-            REAL xn = project(tfma(t0, inv[0], x[0]), lo[0], hi[0]);
+            REAL xn = FRIC ? project_pyramid(tfma(t0, inv[0], x[0]), lo[0], hi[0], pyr, lo[0], x[2]) : project(tfma(t0, inv[0], x[0]), lo[0], hi[0]);
             dx[0] = xn - x[0]; x[0] = xn;
             REAL t1 = tfma(-Dl[0], dx[0], res[1]);
-            xn = project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
+            xn = FRIC ? project_pyramid(tfma(t1, inv[1], x[1]), lo[1], hi[1], pyr, lo[0], x[2]) : project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
             dx[1] = xn - x[1]; x[1] = xn;
             REAL t2 = tfma(-Dl[1], dx[0], res[2]);
             t2 = tfma(-Dl[2], dx[1], t2);
@@ -397,11 +405,11 @@ __global__ void __launch_bounds__(4 * QT) quad_solve_kernel(const SolveArgs<REAL
             REAL xn = project(tfma(t2, inv[2], x[2]), lo[2], hi[2]);
             dx[2] = xn - x[2]; x[2] = xn;
             REAL t1 = tfma(-Dl[2], dx[2], res[1]);                 // D12
-            xn = project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
+            xn = FRIC ? project_pyramid(tfma(t1, inv[1], x[1]), lo[1], hi[1], pyr, lo[0], x[2]) : project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
             dx[1] = xn - x[1]; x[1] = xn;
             REAL t0 = tfma(-Dl[1], dx[2], res[0]);                 // D02
             t0 = tfma(-Dl[0], dx[1], t0);                          // D01
-            xn = project(tfma(t0, inv[0], x[0]), lo[0], hi[0]);
+            xn = FRIC ? project_pyramid(tfma(t0, inv[0], x[0]), lo[0], hi[0], pyr, lo[0], x[2]) : project(tfma(t0, inv[0], x[0]), lo[0], hi[0]);
             dx[0] = xn - x[0]; x[0] = xn;
           }
           if (has) {
@@ -547,7 +555,7 @@ __device__ __forceinline__ void load3(unsigned acc_addr, float (&a)[3]) {
 // per step, no tickets and no polling.  Same lane layout, same arithmetic and same bits as
 // quad_solve_kernel; what goes away is the ticket round trip through LDS on the critical path of a
 // dependent update (0.36 us -> see profiles/r02/microbench.json: chain_update_us_stepq_*).
-template <typename REAL, int METHOD, int QT, bool HIST, bool RUNS>
+template <typename REAL, int METHOD, int QT, bool HIST, bool RUNS, bool FRIC = false>
 __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   REAL *s_acc = reinterpret_cast<REAL *>(smem);
@@ -576,6 +584,7 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
 
   REAL Jh[9], Bh[9], Dl[3], inv[3], rhs[3], lo[3], hi[3], x[3];
   bool eq[3];
+  bool pyr = false;     // FRIC: the constraint's friction coefficient is >= 0, and lo[0] holds it (that bound is dead)
 #pragma unroll
   for (int k = 0; k < 9; ++k) { Jh[k] = REAL(0); Bh[k] = REAL(0); }
 #pragma unroll
@@ -605,6 +614,11 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
       eq[r] = A.is_eq[c * 3 + r] != 0;
       clamp_bounds(eq[r], lo[r], hi[r]);
       x[r] = xs ? xs[c * 3 + r] : rhs[r];
+    }
+    if (FRIC) {
+      const REAL mu = A.mu[c];
+      pyr = mu >= REAL(0);
+      if (pyr) lo[0] = mu;
     }
   }
   // length of the tile's timetable (step_solve.hip: timetable_end)
@@ -640,10 +654,10 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
       }
       if (METHOD == 1) {
         REAL t0r = res[0];
-        REAL xn = project(tfma(t0r, inv[0], x[0]), lo[0], hi[0]);
+        REAL xn = FRIC ? project_pyramid(tfma(t0r, inv[0], x[0]), lo[0], hi[0], pyr, lo[0], x[2]) : project(tfma(t0r, inv[0], x[0]), lo[0], hi[0]);
         dx[0] = xn - x[0]; x[0] = xn;
         REAL t1 = tfma(-Dl[0], dx[0], res[1]);
-        xn = project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
+        xn = FRIC ? project_pyramid(tfma(t1, inv[1], x[1]), lo[1], hi[1], pyr, lo[0], x[2]) : project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
         dx[1] = xn - x[1]; x[1] = xn;
         REAL t2 = tfma(-Dl[1], dx[0], res[2]);
         t2 = tfma(-Dl[2], dx[1], t2);
@@ -654,11 +668,11 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
         REAL xn = project(tfma(t2, inv[2], x[2]), lo[2], hi[2]);
         dx[2] = xn - x[2]; x[2] = xn;
         REAL t1 = tfma(-Dl[2], dx[2], res[1]);                 // D12
-        xn = project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
+        xn = FRIC ? project_pyramid(tfma(t1, inv[1], x[1]), lo[1], hi[1], pyr, lo[0], x[2]) : project(tfma(t1, inv[1], x[1]), lo[1], hi[1]);
         dx[1] = xn - x[1]; x[1] = xn;
         REAL t0r = tfma(-Dl[1], dx[2], res[0]);                // D02
         t0r = tfma(-Dl[0], dx[1], t0r);                        // D01
-        xn = project(tfma(t0r, inv[0], x[0]), lo[0], hi[0]);
+        xn = FRIC ? project_pyramid(tfma(t0r, inv[0], x[0]), lo[0], hi[0], pyr, lo[0], x[2]) : project(tfma(t0r, inv[0], x[0]), lo[0], hi[0]);
         dx[0] = xn - x[0]; x[0] = xn;
       }
     }
@@ -759,8 +773,11 @@ void launch_quad_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int ti
   const size_t lds = (size_t)a.max_slots * (6 * sizeof(REAL) + sizeof(unsigned));
   uint32_t *none = nullptr;
   const bool hist = a.hist_x != nullptr;
-#define EGS_QLAUNCH(METHOD, QT, HIST) \
-  hipLaunchKernelGGL((quad_solve_kernel<REAL, METHOD, QT, false, HIST>), dim3(n_tiles), dim3(4 * QT), lds, s, a, none)
+#define EGS_QLAUNCH(METHOD, QT, HIST)                                                                                              \
+  do {                                                                                                                             \
+    if (a.mu != nullptr) hipLaunchKernelGGL((quad_solve_kernel<REAL, METHOD, QT, false, HIST, false, true>), dim3(n_tiles), dim3(4 * QT), lds, s, a, none); \
+    else hipLaunchKernelGGL((quad_solve_kernel<REAL, METHOD, QT, false, HIST>), dim3(n_tiles), dim3(4 * QT), lds, s, a, none);      \
+  } while (0)
   if (tile_size == 64) {
     if (method == 1) { if (hist) EGS_QLAUNCH(1, 64, true); else EGS_QLAUNCH(1, 64, false); }
     else { if (hist) EGS_QLAUNCH(2, 64, true); else EGS_QLAUNCH(2, 64, false); }
@@ -786,7 +803,10 @@ void launch_quad_patch_solve(const SolveArgs<REAL> &a, int method, int n_tiles, 
   const bool hist = a.hist_x != nullptr;
 #define EGS_QPLAUNCH(M, H)                                                                                                      \
   do {                                                                                                                         \
-    if (a.patch_runs) hipLaunchKernelGGL((quad_solve_kernel<REAL, M, 256, true, H, true>), dim3(n_tiles), dim3(1024), lds, s, a, tickets); \
+    if (a.mu != nullptr) {                                                                                                     \
+      if (a.patch_runs) hipLaunchKernelGGL((quad_solve_kernel<REAL, M, 256, true, H, true, true>), dim3(n_tiles), dim3(1024), lds, s, a, tickets); \
+      else hipLaunchKernelGGL((quad_solve_kernel<REAL, M, 256, true, H, false, true>), dim3(n_tiles), dim3(1024), lds, s, a, tickets);             \
+    } else if (a.patch_runs) hipLaunchKernelGGL((quad_solve_kernel<REAL, M, 256, true, H, true>), dim3(n_tiles), dim3(1024), lds, s, a, tickets); \
     else hipLaunchKernelGGL((quad_solve_kernel<REAL, M, 256, true, H, false>), dim3(n_tiles), dim3(1024), lds, s, a, tickets);             \
   } while (0)
   if (method == 1) { if (hist) EGS_QPLAUNCH(1, true); else EGS_QPLAUNCH(1, false); }
@@ -801,6 +821,14 @@ int occupancy_quad_patch_solve(size_t lds) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, quad_solve_kernel<REAL, M, 256, true, H, false>, 1024, lds) != hipSuccess) return 0; \
   best = nb < best ? nb : best;                                                                           \
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, quad_solve_kernel<REAL, M, 256, true, H, true>, 1024, lds) != hipSuccess) return 0;  \
+  best = nb < best ? nb : best;
+  EGS_OCC(1, true) EGS_OCC(1, false) EGS_OCC(2, true) EGS_OCC(2, false)
+#undef EGS_OCC
+  // ... the friction forms included: the grid is capped once for all of them
+#define EGS_OCC(M, H)                                                                                     \
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, quad_solve_kernel<REAL, M, 256, true, H, false, true>, 1024, lds) != hipSuccess) return 0; \
+  best = nb < best ? nb : best;                                                                           \
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, quad_solve_kernel<REAL, M, 256, true, H, true, true>, 1024, lds) != hipSuccess) return 0;  \
   best = nb < best ? nb : best;
   EGS_OCC(1, true) EGS_OCC(1, false) EGS_OCC(2, true) EGS_OCC(2, false)
 #undef EGS_OCC
@@ -833,7 +861,10 @@ void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int til
   const bool hist = a.hist_x != nullptr;
 #define EGS_SQLAUNCH(METHOD, QT, HIST)                                                                           \
   do {                                                                                                           \
-    if (a.runs) hipLaunchKernelGGL((step_quad_kernel<REAL, METHOD, QT, HIST, true>), dim3(n_tiles), dim3(4 * QT), lds, s, a); \
+    if (a.mu != nullptr) {                                                                                       \
+      if (a.runs) hipLaunchKernelGGL((step_quad_kernel<REAL, METHOD, QT, HIST, true, true>), dim3(n_tiles), dim3(4 * QT), lds, s, a); \
+      else hipLaunchKernelGGL((step_quad_kernel<REAL, METHOD, QT, HIST, false, true>), dim3(n_tiles), dim3(4 * QT), lds, s, a);       \
+    } else if (a.runs) hipLaunchKernelGGL((step_quad_kernel<REAL, METHOD, QT, HIST, true>), dim3(n_tiles), dim3(4 * QT), lds, s, a); \
     else hipLaunchKernelGGL((step_quad_kernel<REAL, METHOD, QT, HIST, false>), dim3(n_tiles), dim3(4 * QT), lds, s, a);       \
   } while (0)
   if (tile_size == 64) {

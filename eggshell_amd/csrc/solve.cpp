@@ -23,13 +23,14 @@ struct SweepSchedule {
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
+  bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
   int oversize = -1;        // OversizeSchedule of the launch's oversize islands, -1: it has none
   // the bits of the kernels that ran (egs_schedule_flags); fill_stats adds those of the problem's plans
   uint32_t flags() const {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
-           (started ? EGS_SCHED_START : 0);
+           (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0);
   }
 };
 
@@ -38,6 +39,7 @@ struct SweepSchedule {
 SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bool resume, bool offer_assembly) {
   SweepSchedule s;
   s.started = p->start_active;
+  s.friction = p->friction;
   s.quad = p->use_quad && method != EGS_JACOBI;
   if (!s.quad) ensure_tile_plan(p);
   const Plan &pl = s.quad ? p->planq : p->plan;
@@ -70,8 +72,10 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   // Its sweep projects with a contact's bounds as literals and reads no lo, hi or is_eq (step_solve.hip), so the
   // list must hold no joint at all.  LINSYM already implies it (lin_neg: no two-body joint; linsym_bodies: a body on
   // side 1, where a one-body joint has none), but the kernel depends on it, so it is required here by name.
+  // A friction step is not offered it either: that form sits at 168 VGPRs with nothing spare for the coefficient
+  // (DESIGN.md section 4g), so the step runs assemble_kernel and the LINSYM friction sweep.
   const char *fe = std::getenv("EGS_FUSED_ASSEMBLY");
-  s.assemble = offer_assembly && s.linsym && p->contacts_only && !resume && !solve_takes_start(p) && pl.global.empty() && !(fe && std::atoi(fe) == 0);
+  s.assemble = offer_assembly && s.linsym && p->contacts_only && !s.friction && !resume && !solve_takes_start(p) && pl.global.empty() && !(fe && std::atoi(fe) == 0);
   // ... which stores no system (problem.h: ensure_system).  EGS_STEP_DEFER_SYSTEM=0 keeps the eager stores.
   const char *de = std::getenv("EGS_STEP_DEFER_SYSTEM");
   s.defer = s.assemble && !(de && std::atoi(de) == 0);
@@ -79,7 +83,8 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
 }
 
 // The problem's system, solution and accumulators as the solve and residual kernels read them (kernels.h; SolveArgs and
-// GlobalArgs name them alike); hist: the per-sweep snapshots too.
+// GlobalArgs name them alike); hist: the per-sweep snapshots too.  The friction coefficients go with them exactly while
+// friction is on, which is what selects the kernels' friction forms (choose_sweep reports it).
 template <typename ARGS, typename REAL>
 void system_args(ARGS &a, const egs_problem *p, REAL cfm, bool hist) {
   a.m = p->m; a.n_bodies = p->n;
@@ -91,6 +96,7 @@ void system_args(ARGS &a, const egs_problem *p, REAL cfm, bool hist) {
   a.x = real<REAL>(p->x); a.acc = real<REAL>(p->acc);
   a.wres = real<REAL>(p->wres);
   a.error_flag = p->error_flag.p;
+  a.mu = p->friction ? real<REAL>(p->mu) : nullptr;
   a.cfm = cfm; a.spin_limit = spin_limit();
   if (hist) { a.hist_x = real<REAL>(p->hist_x); a.hist_acc = real<REAL>(p->hist_acc); }
 }
@@ -369,7 +375,7 @@ void launch_residual(egs_problem *p) {
   with_real(p, [&](auto r) {
     using REAL = decltype(r);
     launch_residual_partials<REAL>(rows, real<REAL>(p->wres), real<REAL>(p->x), real<REAL>(p->lo), real<REAL>(p->hi), p->is_eq.p,
-                                   p->res_partials.p, kResidualBlocks, s);
+                                   p->friction ? real<REAL>(p->mu) : nullptr, p->res_partials.p, kResidualBlocks, s);
   });
 }
 

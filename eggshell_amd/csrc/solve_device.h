@@ -58,6 +58,29 @@ __device__ __forceinline__ T project_contact(T x, int r) {
   if (r < 2) return (__builtin_fabs(x) > T(1)) ? (T)__builtin_copysign(T(1), x) : x;
   return (x < T(0)) ? T(0) : x;
 }
+// The Coulomb pyramid.  A constraint with mu >= 0 projects its tangential rows 0 and 1 onto
+// [-b, b], b = fl(mu x_n) for the normal multiplier x_n the sweep holds at that moment (0 unless x_n > 0), whatever the
+// rows' stored type and bounds; mu < 0 (pyr false) keeps the stored bounds.  -ffp-contract=off: the product is rounded
+// once.  A pyramid lane's lo[0] is dead, so the sweeps keep mu there (Cons::pyr): no register more than without friction.
+template <typename T>
+__device__ __forceinline__ T project_pyramid(T x, T lo, T hi, bool pyr, T mu, T xn) {
+  const T b = (xn > T(0)) ? mu * xn : T(0);
+  return project(x, pyr ? -b : lo, pyr ? b : hi);
+}
+// ... and the residual metric's sort of such a row (x its multiplier, w its (A x - rhs), xn the normal multiplier of the
+// same iterate): inside the cone w must vanish, on a face it must point outward, outside the cone the distance to it
+// counts (a forward sweep clamps against the previous x_n), a row pinned at b = 0 adds nothing.
+template <typename T>
+__device__ __forceinline__ void pyramid_residual(T x, double w, T mu, T xn, double &at_lo, double &at_hi, double &inside) {
+  const T b = (xn > T(0)) ? mu * xn : T(0);
+  const T ax = __builtin_fabs(x);
+  if (ax < b) inside += w * w;
+  else if (ax > b) { const double v = (double)ax - (double)b; inside += v * v; }
+  else if (b > T(0)) {
+    if (x > T(0) && w > 0) at_hi += w * w;
+    if (x < T(0) && w < 0) at_lo += w * w;
+  }
+}
 template <typename T>
 __device__ __forceinline__ void clamp_bounds(bool eq, T &lo, T &hi) {
   if (eq) { lo = -__builtin_huge_val(); hi = __builtin_huge_val(); }
@@ -109,6 +132,7 @@ struct Cons {
   REAL inv[3];          // 1 / ((D_rr + cfm) * kscale)
   REAL rhs[3], lo[3], hi[3];
   bool eq[3];
+  bool pyr;             // friction instantiations only (load_cons: FRIC): mu >= 0, and lo[0] holds mu, not row 0's bound
 };
 
 template <bool ISO, typename REAL>
@@ -123,7 +147,8 @@ __device__ __forceinline__ void acc_add_side1(REAL *a, const Cons<REAL> &c, cons
 // ASSEMBLED (step_solve_kernel's ASSEMBLE form): c.J0 / c.J1 and rhs are in c already, from the assembly's registers;
 // only what is derived from them is formed here.  Every lane of that form is a contact (solve.cpp: choose_sweep), whose
 // bounds are literals in the sweep (project_contact): c.lo, c.hi and c.eq are not used.
-template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false>
+// FRIC: the lane also takes its friction coefficient (A.mu, not NULL in a friction launch).
+template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false, bool FRIC = false>
 __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bool has0, bool has1,
                                           int body0, int body1, Cons<REAL> &c) {
 #pragma unroll
@@ -210,6 +235,11 @@ __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bo
       clamp_bounds(c.eq[r], c.lo[r], c.hi[r]);
     }
   }
+  if (FRIC) {
+    const REAL mu = A.mu[cidx];
+    c.pyr = mu >= REAL(0);
+    if (c.pyr) c.lo[0] = mu;
+  }
 }
 
 // res_r = rhs_r - (J_r . a + cfm x_r)
@@ -224,12 +254,15 @@ __device__ __forceinline__ void row_residuals(const Cons<REAL> &c, const REAL *a
 }
 
 // One projected update of the 3 rows of a constraint; returns dx.  CONTACT: the bounds are a contact's, as literals.
-template <typename REAL, int METHOD, bool CONTACT = false>
+// FRIC: rows 0 and 1 take the pyramid's bounds from the x[2] held when they are projected (project_pyramid): the old
+// iterate's (Jacobi: row 2 is updated last), the previous sweep's (forward) or this sweep's (backward).
+template <typename REAL, int METHOD, bool CONTACT = false, bool FRIC = false>
 __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res, REAL *x, REAL *dx) {
   if (METHOD == 0) {  // Jacobi: no intra-block coupling
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      REAL xn = project(tfma(res[r], c.inv[r], x[r]), c.lo[r], c.hi[r]);
+      const REAL xu = tfma(res[r], c.inv[r], x[r]);
+      REAL xn = (FRIC && r < 2) ? project_pyramid(xu, c.lo[r], c.hi[r], c.pyr, c.lo[0], x[2]) : project(xu, c.lo[r], c.hi[r]);
       dx[r] = xn - x[r];
       x[r] = xn;
     }
@@ -240,7 +273,8 @@ __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res
 #pragma unroll
       for (int l = 0; l < r; ++l) t = tfma(-c.D[3 * r + l], dx[l], t);
       const REAL xu = tfma(t, c.inv[r], x[r]);
-      REAL xn = CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
+      REAL xn = (FRIC && r < 2) ? project_pyramid(xu, c.lo[r], c.hi[r], c.pyr, c.lo[0], x[2])
+                                : CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
       dx[r] = xn - x[r];
       x[r] = xn;
     }
@@ -251,7 +285,8 @@ __device__ __forceinline__ void update_rows(const Cons<REAL> &c, const REAL *res
 #pragma unroll
       for (int l = 2; l > r; --l) t = tfma(-c.D[3 * r + l], dx[l], t);
       const REAL xu = tfma(t, c.inv[r], x[r]);
-      REAL xn = CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
+      REAL xn = (FRIC && r < 2) ? project_pyramid(xu, c.lo[r], c.hi[r], c.pyr, c.lo[0], x[2])
+                                : CONTACT ? project_contact(xu, r) : project(xu, c.lo[r], c.hi[r]);
       dx[r] = xn - x[r];
       x[r] = xn;
     }

@@ -201,8 +201,10 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
   return n_phases >= 1 ? depth + P * (n_phases - 1) : 0;
 }
 
+// FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
+// ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
-          bool STORE_SYSTEM = true>
+          bool STORE_SYSTEM = true, bool FRIC = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WAVES = BLOCK / 64;
@@ -254,7 +256,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   AngProducts<REAL, HELD> held;
   if (active) {
     if constexpr (ASSEMBLE) load_cons<REAL, true, true, true>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
-    else load_cons<REAL, ISO, LINSYM>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
+    else load_cons<REAL, ISO, LINSYM, false, FRIC>(A, d.cidx, has0, has1, has0 ? slot_body[slot0] : 0, has1 ? slot_body[slot1] : 0, c);
 #pragma unroll
     for (int r = 0; r < 3; ++r) x[r] = xs ? xs[(size_t)d.cidx * 3 + r] : c.rhs[r];
     if constexpr (HELD > 0) {
@@ -318,7 +320,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
           REAL res[3];
           if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
           else row_residuals(c, a0, a1, x, A.cfm, res);
-          update_rows<REAL, METHOD, ASSEMBLE>(c, res, x, dx);
+          update_rows<REAL, METHOD, ASSEMBLE, FRIC>(c, res, x, dx);
         }
         if (LINSYM) {
           opaque_wa<HELD>(c);
@@ -360,7 +362,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
         load12(ac0, ac1, a0, a1);
         if (LINSYM) linsym_residuals(c, a0, a1, x, A.cfm, res);
         else row_residuals(c, a0, a1, x, A.cfm, res);
-        update_rows<REAL, METHOD, ASSEMBLE>(c, res, x, dx);
+        update_rows<REAL, METHOD, ASSEMBLE, FRIC>(c, res, x, dx);
         if (LINSYM) {
           opaque_wa<HELD>(c);
           if (has0) { linsym_acc_add<false, HELD>(a0, c, c.J0, c.wa0, dx, held); store6(ac0, a0); }
@@ -415,10 +417,15 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 #define EGS_LAUNCH_S(BLK, ISO, GRP) EGS_LAUNCH_SH(BLK, ISO, GRP, !ISO, false)
 #define EGS_LAUNCH_SH(BLK, ISO, GRP, HIST, LINSYM)                                                             \
   {                                                                                                            \
+    if (b.mu != nullptr) EGS_LAUNCH_SF(BLK, ISO, GRP, HIST, LINSYM, true)                                      \
+    else EGS_LAUNCH_SF(BLK, ISO, GRP, HIST, LINSYM, false)                                                     \
+  }
+#define EGS_LAUNCH_SF(BLK, ISO, GRP, HIST, LINSYM, FRIC)                                                       \
+  {                                                                                                            \
     const size_t lds = (size_t)b.max_slots * 6 * sizeof(REAL) * GRP;                                           \
     const dim3 g((n_tiles + GRP - 1) / GRP), t(BLK * GRP);                                                     \
-    auto k1 = step_solve_kernel<REAL, BLK, 1, ISO, GRP, HIST, LINSYM>;                                         \
-    auto k2 = step_solve_kernel<REAL, BLK, 2, ISO, GRP, HIST, LINSYM>;                                         \
+    auto k1 = step_solve_kernel<REAL, BLK, 1, ISO, GRP, HIST, LINSYM, false, true, FRIC>;                      \
+    auto k2 = step_solve_kernel<REAL, BLK, 2, ISO, GRP, HIST, LINSYM, false, true, FRIC>;                      \
     if (lds > 48 * 1024) {                                                                                     \
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2),                            \
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
@@ -444,6 +451,7 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
   else EGS_LAUNCH_S(512, false, 1)
 #undef EGS_LAUNCH_S
 #undef EGS_LAUNCH_SH
+#undef EGS_LAUNCH_SF
 }
 
 namespace {

@@ -113,6 +113,11 @@ struct egs_world {
   DevBuf<double> ws_pos;
   DevBuf<unsigned char> ws_lambda, ws_x0;
   DevBuf<uint8_t> ws_valid;
+  // egs_world_set_friction: the Coulomb pyramid, one coefficient per ensemble (< 0: the reference's box).  friction:
+  // some coefficient is >= 0; then every step fills the problem's per-constraint coefficients from the current list
+  // (world_fill_friction) before its solve.
+  bool friction = false;
+  DevBuf<double> d_fric;                 // [E]
   bool lambda_stale = false;             // a stabilise call changed bodies / contacts since the last step's solve
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
@@ -536,6 +541,22 @@ void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double 
   HIPCHK(hipGetLastError());
 }
 
+// The problem's friction coefficients for the list about to be solved: joints -1, every contact its ensemble's
+// coefficient (a batched world's body -> ensemble table; a plain world has one ensemble).
+void world_fill_friction(egs_world *w) {
+  egs_problem *p = w->prob;
+  p->friction = w->friction && p->m > 0;
+  if (!p->friction) return;
+  p->mu.alloc((size_t)p->m * p->real_size());
+  const int mj = (int)w->jb0.size();
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    launch_fill_friction<REAL>(p->m, mj, p->body0.p, p->body1.p, w->n_ens > 1 ? w->d_ens.p : nullptr, w->d_fric.p,
+                               real<REAL>(p->mu), w->ctx->stream);
+  });
+  HIPCHK(hipGetLastError());
+}
+
 // egs_world_step (dt_each == NULL) and egs_world_step_each (dt_each / erp_each [E], host, validated) after their guards
 egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *dt_each, const double *erp_each,
                              const egs_solve_params *params, int32_t detect_contacts, egs_solve_stats *stats) {
@@ -550,6 +571,7 @@ egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *
     egs_problem *p = w->prob;
     const bool batched = w->n_ens > 1;
     w->last_warm = false;
+    if (w->friction || p->friction) world_fill_friction(w);
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);
       // x0 from the history; an ensemble without one gets its rhs rows, the default start.  The problem takes the
@@ -886,6 +908,7 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
   if (!w) return EGS_ERR_INVALID;
   if (n_failed) *n_failed = 0;
   if (egs_status st = world_step_guard(w, dt, "the dense path is fp64 (the reference's is)")) return st;
+  if (w->friction) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
   return world_step_direct(w, dt, erp, nullptr, nullptr, cfm_coeff, use_bounds, detect_contacts, n_failed);
 }
@@ -895,6 +918,7 @@ egs_status egs_world_step_dense_each(egs_world *w, int32_t n_ensembles, const do
   if (!w) return EGS_ERR_INVALID;
   if (n_failed) *n_failed = 0;
   if (egs_status st = world_each_guard(w, n_ensembles, dt, erp, "the dense path is fp64 (the reference's is)")) return st;
+  if (w->friction) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
   return world_step_direct(w, 0.0, 0.0, dt, erp, cfm_coeff, use_bounds, detect_contacts, n_failed);
 }
@@ -958,6 +982,27 @@ egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_r
       HIPCHK(hipMemsetAsync(w->ws_coff.p, 0, ((size_t)w->n_ens + 1) * sizeof(int32_t), w->ctx->stream));
       world_drop_history(w);
     }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const double *mu) {
+  if (!w) return EGS_ERR_INVALID;
+  if (!mu) return fail(w->ctx, EGS_ERR_INVALID, "NULL friction table");
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  bool any = false;
+  for (int e = 0; e < n_ensembles; ++e) {
+    if (mu[e] != mu[e]) return fail(w->ctx, EGS_ERR_INVALID, "NaN friction coefficient");
+    any |= mu[e] >= 0;
+  }
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));   // a step in flight may still read the old table
+    w->d_fric.alloc((size_t)n_ensembles);
+    HIPCHK(hipMemcpyAsync(w->d_fric.p, mu, (size_t)n_ensembles * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));   // mu is the caller's
+    w->friction = any;
+    if (!any && w->prob) w->prob->friction = false;
     return EGS_OK;
   });
 }

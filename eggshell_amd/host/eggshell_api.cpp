@@ -717,6 +717,16 @@ void Ensemble::SetWarmStart(bool on, double match_radius) {
   warm_radius_ = on ? match_radius : 0.0;
 }
 
+void Ensemble::SetFriction(Contact::FrictionModel model, double mu) {
+  if (model != Contact::FrictionModel::BOX && model != Contact::FrictionModel::COULOMB_PYRAMID)
+    throw egs::Error(EGS_ERR_UNSUPPORTED, "SetFriction: NO_FRICTION and INFINITE have empty bodies in the reference (contact.cc:150-152) "
+                                          "and are not built; BOX and COULOMB_PYRAMID are");
+  if (model == Contact::FrictionModel::COULOMB_PYRAMID && !(mu >= 0))
+    throw egs::Error(EGS_ERR_INVALID, "SetFriction: COULOMB_PYRAMID needs mu >= 0");
+  friction_model_ = model;
+  friction_mu_ = model == Contact::FrictionModel::COULOMB_PYRAMID ? mu : 0.0;
+}
+
 bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
@@ -749,6 +759,11 @@ bool Ensemble::StepOnDevice(double dt) {
     egs::check(egs_world_set_warm_start(world_, warm_start_ ? 1 : 0, warm_radius_));
     world_warm_ = warm_start_; world_warm_radius_ = warm_radius_;
     world_state_.clear();
+  }
+  if (first) world_friction_ = -1.0;   // a fresh world has the reference's box
+  if (const double mu = device_friction(); mu != world_friction_) {
+    egs::check(egs_world_set_friction(world_, 1, &mu));
+    world_friction_ = mu;
   }
   // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state
   // that is still what the last step left on the device is not pushed again: a push drops the world's history.
@@ -812,6 +827,9 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
                      "Integrator::EXPLICIT_EULER panics in the reference (ComputeJDotV_Joints, ensembles.cc:94-97); "
                      "only Integrator::OPEN_DYNAMICS_ENGINE completes a step");
   if (StepOnDevice(dt)) return;   // collide -> solve -> integrate in one resident pipeline
+  if (friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID)
+    throw egs::Error(EGS_ERR_UNSUPPORTED, "COULOMB_PYRAMID steps on the device only: not with use_device_step = false, "
+                                          "use_dense_solver, caller-supplied contacts or a joint the device cannot take");
   const VectorXd v = GetVelocities();
   if (detect_contacts) UpdateContacts();
   CheckAndCorrectEnsembleState();   // ensembles.cc:394
@@ -921,6 +939,15 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     egs::check(egs_world_set_warm_start(world_, warm ? 1 : 0, lead->warm_radius_));
     world_warm_ = warm; world_warm_radius_ = lead->warm_radius_;
     world_state_.clear();
+  }
+  {   // the members' friction, each its own (a fresh world has the reference's box everywhere)
+    std::vector<double> mu(E);
+    for (size_t i = 0; i < E; ++i) mu[i] = members_[i]->device_friction();
+    if (first) world_friction_.assign(E, -1.0);
+    if (mu != world_friction_) {
+      egs::check(egs_world_set_friction(world_, (int32_t)E, mu.data()));
+      world_friction_ = mu;
+    }
   }
   // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state
   // that is still what the last step left on the device is not pushed again: a push drops the world's history.

@@ -123,6 +123,10 @@ struct ContactGeometry {  // collision.h:12-27
 
 class Contact : public Constraint {  // contact.h:11-56
  public:
+  // contact.h:21-25.  The reference implements BOX alone (tangential rows bounded by the constant 1, contact.cc:103-113)
+  // and leaves the other three with empty bodies; COULOMB_PYRAMID is built here (Ensemble::SetFriction), NO_FRICTION
+  // and INFINITE are not.
+  enum struct FrictionModel { NO_FRICTION, INFINITE, BOX, COULOMB_PYRAMID };
   Contact(std::shared_ptr<Body> b, int index, const ContactGeometry &cg)
       : Constraint(nullptr, -1, std::move(b), index), cg_(cg) {}
   Contact(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const ContactGeometry &cg)
@@ -310,6 +314,14 @@ class Ensemble {  // ensembles.h:25-186
   // which no Body was touched continues it (the state is then not pushed again), a step after an edited Body, an
   // edited joint or a stabilise call starts from rhs as ever.  Throws egs::Error(EGS_ERR_INVALID) if radius < 0.
   void SetWarmStart(bool on, double match_radius = 0.01);
+  // Not in the reference (Contact::FrictionModel::COULOMB_PYRAMID has empty bodies there), off by default: BOX is the
+  // reference's model; COULOMB_PYRAMID bounds every contact's two tangential multipliers by +-mu times its normal
+  // multiplier in the device step's sweeps (egs_world_set_friction).  Throws egs::Error: EGS_ERR_UNSUPPORTED for
+  // NO_FRICTION and INFINITE, EGS_ERR_INVALID for a pyramid with mu < 0 or NaN.  A pyramid ensemble steps on the
+  // device only: Step throws EGS_ERR_UNSUPPORTED where it would take the explicit or the dense path.
+  void SetFriction(Contact::FrictionModel model, double mu = 0);
+  Contact::FrictionModel friction_model() const { return friction_model_; }
+  double friction_mu() const { return friction_mu_; }
   bool warm_start() const { return warm_start_; }
   double warm_start_radius() const { return warm_radius_; }
   VectorXd last_lambda;
@@ -347,6 +359,9 @@ class Ensemble {  // ensembles.h:25-186
   std::vector<double> world_jdata_;
   bool warm_start_ = false, world_warm_ = false;   // asked for; what the device world was last told
   double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
+  Contact::FrictionModel friction_model_ = Contact::FrictionModel::BOX;
+  double friction_mu_ = 0.0, world_friction_ = -1.0;   // asked for; the coefficient the device world was last told (< 0: box)
+  double device_friction() const { return friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID ? friction_mu_ : -1.0; }
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last device step (warm start only)
   egs_problem *problem_ = nullptr;
   std::vector<int32_t> plan_b0_, plan_b1_;   // topology the cached device problem was planned for
@@ -378,6 +393,7 @@ class Cairn : public Ensemble {
 // as in Ensemble::Step.  After it every member's Body objects, contacts and last_lambda hold, bit for bit, what the
 // member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
 // egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
+//   - The members may differ in SetFriction: member i's contacts take its model and coefficient (egs_world_set_friction).
 //   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts and SetWarmStart, and each must be able to
 //     take the device step (joints that Describe themselves, no caller-supplied contacts); the list may not be empty or
 //     hold a pointer twice: the constructor throws egs::Error(EGS_ERR_INVALID) naming the offending member.
@@ -407,6 +423,7 @@ class EnsembleGroup {
   std::vector<double> world_jdata_;
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
+  std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last step (warm start only)
 };
 

@@ -103,7 +103,9 @@ typedef enum {
                                       assembly launch, what the step saved.  Readers: get_blocks, matvec, a solve or
                                       a step that does not fuse, the dense entries, and the residual -- so a step
                                       asked for statistics, or get_stats after one, pays for it too */
-  EGS_SCHED_START = 1024           /* the solve started from a given x0 (egs_problem_set_start), not from rhs */
+  EGS_SCHED_START = 1024,          /* the solve started from a given x0 (egs_problem_set_start), not from rhs */
+  EGS_SCHED_FRICTION = 2048        /* the launch ran the kernels' friction forms (egs_problem_set_friction,
+                                      egs_world_set_friction): tangential bounds +-mu x_n.  Clear with friction off */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -194,6 +196,24 @@ egs_status egs_problem_get_wres(egs_problem *p, double *w /*[3m]*/);
 #define EGS_START_GIVEN    1
 #define EGS_START_PREVIOUS 2
 egs_status egs_problem_set_start(egs_problem *p, int32_t mode, const double *x0 /*[3m], GIVEN only*/);
+
+/* ---- Coulomb friction pyramid.  The reference bounds a contact's two tangential rows by the constant 1 (the friction
+ *      box, contact.cc:103-113) and declares COULOMB_PYRAMID with empty bodies (contact.h:21-25); this is that model,
+ *      off unless asked for.  mu holds one coefficient per constraint (the whole list of a batch problem), converted
+ *      to the problem's precision.  mu[c] < 0: constraint c is solved as stored.  mu[c] >= 0: rows 0 and 1 of c are
+ *      inequality rows with the bounds [-b, +b], whatever type and bounds are stored for them,
+ *          b = x_n > 0 ? fl(mu[c] x_n) : 0,    x_n = the multiplier of row 2 (the normal row) held when the row is
+ *      projected: the old iterate's (Jacobi), the previous sweep's (Gauss-Seidel, rows run 0, 1, 2; in the first sweep
+ *      the start's, which may be negative), this sweep's (backward SOR, rows run 2, 1, 0).  Row 2 keeps its stored
+ *      type and bounds.  w = A x - rhs is unchanged.  The residual, stopping rule and reported value alike, sorts such
+ *      a row by the b of the iterate's own x_n: |x| < b adds w^2 to the strictly-inside sum; x = b > 0 with w > 0 to
+ *      the at-hi sum; x = -b < 0 with w < 0 to the at-lo sum; |x| > b adds (|x| - b)^2 to the strictly-inside sum (a
+ *      forward sweep clamps against the previous x_n); b = 0 = x adds nothing.
+ *      mu = NULL, or no coefficient >= 0, turns friction off: every result and schedule flag is then what it is
+ *      without this call.  On, the launches report EGS_SCHED_FRICTION, egs_problem_step does not fuse the assembly
+ *      (EGS_SCHED_FUSED_ASSEMBLY stays clear) and egs_problem_step_dense returns EGS_ERR_UNSUPPORTED.  Starts, mat-vec
+ *      and get_wres work alongside as they are.  EGS_ERR_INVALID: a NaN coefficient (nothing changes).              */
+egs_status egs_problem_set_friction(egs_problem *p, const double *mu /*[m] or NULL*/);
 
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
@@ -467,6 +487,13 @@ egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_ou
  * previous list's contacts; a joint: its own index) its rows came from, -1 or -2 as egs_match_contacts reports;
  * EGS_ERR_INVALID if the last step was not one.                                                                  */
 egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_radius);
+/* The friction pyramid of egs_problem_set_friction for a world: one coefficient per ensemble (n_ensembles must be the
+ * world's, 1 for a plain world).  Every contact of ensemble e takes mu[e], every joint -1; mu[e] < 0 keeps the
+ * reference's friction box for that ensemble.  The per-constraint coefficients are filled on the device from the
+ * current contact list at every step.  egs_world_step and egs_world_step_each solve with it; egs_world_step_dense and
+ * egs_world_step_dense_each return EGS_ERR_UNSUPPORTED while any coefficient is >= 0.  Warm start and stabilisation are
+ * untouched.  EGS_ERR_INVALID: mu NULL, a NaN, a wrong n_ensembles (nothing changes).                              */
+egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const double *mu /*[E]*/);
 egs_status egs_world_get_start(egs_world *w, int32_t max_rows, int32_t *rows_out, double *x0, int32_t *source /*[m] or NULL*/);
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans);
 
