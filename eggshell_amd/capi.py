@@ -17,6 +17,7 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STALL, ERR_UNSUPPORTED, ERR_LCP_FAI
 JACOBI, GAUSS_SEIDEL, SOR = 0, 1, 2
 F64, F32 = 0, 1
 JOINT_BALL, CONTACT_BOX = 0, 1
+SHAPE_BOX, SHAPE_SPHERE = 0, 1
 MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
 SCHED_LINSYM = 128
@@ -49,6 +50,7 @@ EXPORTS = [
     "egs_world_step_each", "egs_world_step_dense_each",
     "egs_problem_set_start", "egs_match_contacts", "egs_world_set_warm_start", "egs_world_get_start",
     "egs_problem_set_friction", "egs_world_set_friction",
+    "egs_update_contacts_shapes", "egs_world_set_shapes",
 ]
 
 
@@ -291,6 +293,21 @@ class Context:
         m = C.c_int32(0)
         self.check(load().egs_update_contacts(self.h, C.c_int32(n), _p(pos), _p(R), _p(side), C.c_int32(cap),
                                               C.byref(m), _p(b0), _p(b1), _p(data)))
+        return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
+
+    def update_contacts_shapes(self, pos, R, side, shape=None, max_contacts=None, joints=None):
+        """update_contacts with a shape per body (egs_update_contacts_shapes): SHAPE_BOX / SHAPE_SPHERE [n], a sphere's
+        side row being (d, d, d); shape None = all boxes.  joints as in update_contacts."""
+        pos, R, side, shape = _f64(pos), _f64(R), _f64(side), _i32(shape)
+        n = pos.reshape(-1, 3).shape[0]
+        jb0, jb1, jd = (_i32(joints[0]), _i32(joints[1]), _f64(joints[2])) if joints is not None else (None, None, None)
+        mj = 0 if jb0 is None else jb0.shape[0]
+        cap = int(max_contacts if max_contacts is not None else 64 * n + 64)
+        b0 = np.zeros(cap, np.int32); b1 = np.zeros(cap, np.int32); data = np.zeros((cap, 7))
+        m = C.c_int32(0)
+        self.check(load().egs_update_contacts_shapes(self.h, C.c_int32(n), _p(pos), _p(R), _p(side), C.c_int32(mj),
+                                                     _p(jb0), _p(jb1), _p(jd), _p(shape), C.c_int32(cap), C.byref(m),
+                                                     _p(b0), _p(b1), _p(data)))
         return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
 
     def match_contacts(self, old_b0, old_b1, old_pos, old_lambda, old_off, valid, new_b0, new_b1, new_pos, new_rhs,
@@ -773,6 +790,14 @@ class World:
         side = _f64(np.tile([0.3, 0.3, 0.3], (self.n, 1)) if side is None else side)
         a = [_f64(pos), _f64(R), _f64(v), _f64(w), _f64(Minv), _f64(f_ext), side]
         self.ctx.check(load().egs_world_set_bodies(self.h, *[_p(x) for x in a]))
+
+    def set_shapes(self, shape):
+        """A shape per body, SHAPE_BOX / SHAPE_SPHERE [n] (egs_world_set_shapes); None switches back to boxes.  A
+        sphere's side row is (d, d, d); its inertia is the caller's Minv."""
+        shape = _i32(shape)
+        if shape is not None and shape.shape != (self.n,):
+            raise ValueError("shape has shape %s: the world has %d bodies" % (shape.shape, self.n))
+        self.ctx.check(load().egs_world_set_shapes(self.h, _p(shape)))
 
     def set_joints(self, body0, body1, data):
         body0, body1, data = _i32(body0), _i32(body1), _f64(data)

@@ -6,14 +6,35 @@
 
 namespace egs {
 
+// ---- shapes (egs_shape in eggshell_amd.h; shape == NULL everywhere below means every body is a box) -----------
+// A SPHERE is a body whose side row is (d, d, d) with d > 0; r = d / 2 and its R is not read.  The conventions are
+// the box code's: contacts are (body0, body1) with body0 < body1 or body0 = -1 (ground), the normal points from
+// body0 towards body1, depth >= 0, an exactly touching pair (separation == 0) IS a contact, a ground contact needs
+// z < 0 strictly.
+//   sphere - ground   q = (c_x, c_y, c_z - r); contact iff q_z < 0: position q, normal (0, 0, 1), depth -q_z.
+//   sphere i - j      d = c_j - c_i, L = |d|, s = L - (r_i + r_j); contact iff s <= 0; n = d / L ((0, 0, 1) when
+//                     L == 0); depth = -s; position = c_i + n (r_i + L - r_j) / 2, the midpoint of the two surface
+//                     points on the centre line.
+//   sphere S - box B  p = R_B^T (c_S - c_B), h = side_B / 2, q_k = clamp(p_k, -h_k, h_k).
+//                     Centre outside (q != p): e = p - q, L = |e|; contact iff L - r <= 0; n_BS = R_B e / L,
+//                     depth = r - L; box point R_B q + c_B, sphere point c_S - r n_BS.
+//                     Centre inside or on the surface (q == p): k = argmin_k (h_k - |p_k|), lowest k on a tie;
+//                     n_BS = sgn(p_k) (column k of R_B), sgn(0) = +1; depth = (h_k - |p_k|) + r; box point = the
+//                     centre moved onto that face, sphere point c_S - r n_BS.
+//                     Position = the midpoint of the two points; the normal is n_BS if the box is body0, -n_BS if
+//                     the sphere is.
+// A pair with a sphere yields at most one contact, so only the joint-vs-contact pruning can remove it.  List order:
+// per ensemble the ground contacts by body, then the pairs i < j; box-box pairs emit what they emit without shapes.
+
 // pos [n][3], R [n][9] row-major, side [n][3] on the host.  Writes the contact
 // list in the reference's order (ground contacts by body, then pairs i < j):
 // body0/body1 [m], data [m][7] = position, normal, depth.  Returns m.
 // Throws std::invalid_argument if m > max_contacts or a body has more than 64
-// overlapping partners.
+// overlapping partners.  shape [n] (host, egs_shape) or NULL; the caller has checked its values and the spheres' sides.
 int update_contacts(hipStream_t s, int n, const double *pos, const double *R, const double *side, int max_contacts,
                     int32_t *body0, int32_t *body1, double *data, int *n_ground, int *n_pairs, int mj = 0,
-                    const int32_t *jb0 = nullptr, const int32_t *jb1 = nullptr, const double *jdata = nullptr);
+                    const int32_t *jb0 = nullptr, const int32_t *jb1 = nullptr, const double *jdata = nullptr,
+                    const int32_t *shape = nullptr);
 
 // Device-resident form: body state already on the device, the contact list stays
 // there (body0()/body1()/data() are device pointers valid until the next run()).
@@ -24,9 +45,11 @@ class Collider {
   Collider(const Collider &) = delete;
   Collider &operator=(const Collider &) = delete;
   // optional joints (device arrays, body-body only matter): contacts within 1e-6 of a
-  // joint between the same two bodies are dropped (ensembles.cc:296-306)
+  // joint between the same two bodies are dropped (ensembles.cc:296-306).
+  // dshape [n] (device, egs_shape) or NULL = all boxes, which takes the launches of a collider without shapes.
   int run(hipStream_t s, int n, const double *dpos, const double *dR, const double *dside, int mj = 0,
-          const int32_t *djb0 = nullptr, const int32_t *djb1 = nullptr, const double *djdata = nullptr);  // returns m
+          const int32_t *djb0 = nullptr, const int32_t *djb1 = nullptr, const double *djdata = nullptr,
+          const int32_t *dshape = nullptr);  // returns m
   // body0()/body1() of the last run() written to device-visible host memory (hipHostMalloc)
   void export_topology(hipStream_t s, int m, int32_t *mapped_b0, int32_t *mapped_b1) const;
   const int32_t *body0() const;

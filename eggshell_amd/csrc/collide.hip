@@ -15,8 +15,10 @@
 //      the candidates come from a hashed uniform grid instead of all pairs
 //      (cand_grid_kernel; same sphere test, same ascending order)
 //   2. flatten candidates (scan)      -> pair list in (i, j) order
-//   3. narrow_kernel<false>           per pair: SAT + clipping, count kept contacts
-//   4. scan, narrow_kernel<true> + ground emit  -> final arrays
+//   3. narrow_kernel<false, .>        per pair: SAT + clipping, count kept contacts
+//   4. scan, narrow_kernel<true, .> + ground emit  -> final arrays
+// With a shape array (egs_shape per body) the same pipeline runs the SHAPES = true instantiations, which
+// add sphere-ground, sphere-sphere and sphere-box beside the box code (collide.h has the geometry).
 // Arithmetic follows oracle/collision.c operation by operation (fp64,
 // -ffp-contract=off), so the contact set is bit-identical to the CPU oracle's.
 #include <hip/hip_runtime.h>
@@ -303,16 +305,109 @@ __device__ int collide_boxes(const double *c1, const double *R1, const double *s
   return n;
 }
 
+// ---- spheres (collide.h states the geometry) ---------------------------------
+// A sphere is a body whose side row is (d, d, d), r = d / 2; its R is not read.  Each function has ONE
+// operation order, written out below: fp64, one rounding per operation, sqrt and / only where the
+// definition has them.  tests/sphere_twin.py restates it in numpy and is matched bit for bit.
+constexpr int kShapeSphere = 1;   // EGS_SHAPE_SPHERE; every other value takes the box code (the ABI admits only 0)
+
+// r = side[0] * 0.5;  qz = c[2] - r;  contact iff qz < 0:  (c[0], c[1], qz), (0, 0, 1), -qz
+__device__ int ground_sphere(const double *c, const double *side, double *out) {
+  const double r = side[0] * 0.5;
+  const double qz = c[2] - r;
+  if (!(qz < 0)) return 0;
+  if (out) { out[0] = c[0]; out[1] = c[1]; out[2] = qz; out[3] = 0; out[4] = 0; out[5] = 1; out[6] = -qz; }
+  return 1;
+}
+
+// d = cj - ci;  L = sqrt((d0 d0 + d1 d1) + d2 d2);  s = L - (ri + rj);  contact iff s <= 0
+// n = d / L ((0, 0, 1) when L == 0);  t = ((ri + L) - rj) * 0.5;  position = ci + n * t;  depth = -s
+__device__ int collide_spheres(const double *ci, const double *si, const double *cj, const double *sj, double *out) {
+  const double ri = si[0] * 0.5, rj = sj[0] * 0.5;
+  const double d[3] = {cj[0] - ci[0], cj[1] - ci[1], cj[2] - ci[2]};
+  const double L = sqrt(dot3(d, d));
+  const double s = L - (ri + rj);
+  if (s > 0) return 0;
+  double n[3] = {0, 0, 1};
+  if (L != 0) { n[0] = d[0] / L; n[1] = d[1] / L; n[2] = d[2] / L; }
+  const double t = ((ri + L) - rj) * 0.5;
+  for (int k = 0; k < 3; ++k) { out[k] = ci[k] + n[k] * t; out[3 + k] = n[k]; }
+  out[6] = -s;
+  return 1;
+}
+
+// Sphere S against box B; flip = the sphere is body0, so the reported normal is -n_BS.
+//   r = sideS[0] * 0.5;  dc = cS - cB;  p_k = (R[k] dc0 + R[3 + k] dc1) + R[6 + k] dc2  (R^T dc)
+//   h_k = sideB[k] * 0.5;  q_k = min(max(p_k, -h_k), h_k);  e = p - q;  L = sqrt((e0 e0 + e1 e1) + e2 e2)
+//   L > 0 (centre outside; an e too small for its squares to be normal numbers counts as inside):
+//     contact iff L - r <= 0;  n = (R e) / L;  depth = r - L
+//   L == 0 (centre inside or on the surface):
+//     g_k = h_k - |p_k|;  k = argmin g (lowest k on a tie);  sg = sgn(p_k);  n = sg * column k of R
+//     depth = g_k + r;  q_k = sg * h_k (the centre moved onto that face)
+//   box point = R q + cB;  sphere point = cS - r * n;  position = (box point + sphere point) * 0.5
+__device__ int collide_sphere_box(const double *cS, const double *sideS, const double *cB, const double *RB,
+                                  const double *sideB, bool flip, double *out) {
+  const double r = sideS[0] * 0.5;
+  const double dc[3] = {cS[0] - cB[0], cS[1] - cB[1], cS[2] - cB[2]};
+  double p[3], h[3], q[3], e[3], n[3], depth;
+  for (int k = 0; k < 3; ++k) {
+    p[k] = (RB[k] * dc[0] + RB[3 + k] * dc[1]) + RB[6 + k] * dc[2];
+    h[k] = sideB[k] * 0.5;
+    q[k] = fmin(fmax(p[k], -h[k]), h[k]);
+    e[k] = p[k] - q[k];
+  }
+  const double L = sqrt(dot3(e, e));
+  if (L > 0) {
+    if (L - r > 0) return 0;
+    double w[3];
+    mat3_vec(RB, e, w);
+    for (int k = 0; k < 3; ++k) n[k] = w[k] / L;
+    depth = r - L;
+  } else {
+    const double g[3] = {h[0] - fabs(p[0]), h[1] - fabs(p[1]), h[2] - fabs(p[2])};
+    int k = 0;
+    if (g[1] < g[k]) k = 1;
+    if (g[2] < g[k]) k = 2;
+    const double sg = sgn(p[k]);
+    double col[3];
+    colv(RB, k, col);
+    for (int a = 0; a < 3; ++a) n[a] = sg * col[a];
+    depth = g[k] + r;
+    q[k] = sg * h[k];
+  }
+  double bq[3];
+  mat3_vec(RB, q, bq);
+  const double fs = flip ? -1.0 : 1.0;
+  for (int k = 0; k < 3; ++k) {
+    const double boxpt = bq[k] + cB[k];
+    const double sphpt = cS[k] - r * n[k];
+    out[k] = (boxpt + sphpt) * 0.5;
+    out[3 + k] = fs * n[k];
+  }
+  out[6] = depth;
+  return 1;
+}
+
 // ---- kernels ---------------------------------------------------------------
+// SHAPES = false is the all-box code, launched whenever no shape array is set; SHAPES = true reads
+// shape [n] (egs_shape) and dispatches per lane.  The broad phase below does not look at shapes: its
+// bounding radius 0.5 |side| is (sqrt(3) / 2) d >= r for a (d, d, d) sphere, so the candidate ball
+// contains the sphere and the candidate order (ascending j) is the box scene's.
 // Batched worlds (ens != NULL): body b's ground contacts follow the pair contacts of the ensembles before
 // its own, ebase[2e] of them (ens_base_kernel).
+template <bool SHAPES>
 __global__ void __launch_bounds__(256) ground_kernel(int n, const double *pos, const double *R, const double *side,
                                                      const int *off, int *count, int *b0, int *b1, double *data,
-                                                     const int *ens = nullptr, const int *ebase = nullptr) {
+                                                     const int *ens = nullptr, const int *ebase = nullptr,
+                                                     const int32_t *shape = nullptr) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= n) return;
   double buf[8 * 7];
-  const int c = ground_contacts(pos + 3 * (size_t)b, R + 9 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
+  int c;
+  if (SHAPES && shape[b] == kShapeSphere)
+    c = ground_sphere(pos + 3 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
+  else
+    c = ground_contacts(pos + 3 * (size_t)b, R + 9 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
   if (!off) { count[b] = c; return; }
   const size_t shift = ens ? (size_t)ebase[2 * ens[b]] : 0;
   for (int k = 0; k < c; ++k) {
@@ -498,17 +593,29 @@ __global__ void __launch_bounds__(256) flatten_kernel(int n, const int *cand, co
 // position (ensembles.cc:296-306; Joint::GetConstraintPosition, joints.cc:57-75).
 struct JointList { int mj; const int *b0, *b1; const double *data; };
 
-template <bool EMIT>
+template <bool EMIT, bool SHAPES>
 __global__ void __launch_bounds__(64) narrow_kernel(int npairs, const int *pi, const int *pj, const double *pos,
                                                     const double *R, const double *side, const int *off, int base,
                                                     int *count, int *b0, int *b1, double *data, JointList jl,
-                                                    const int *ens = nullptr, const int *ebase = nullptr) {
+                                                    const int *ens = nullptr, const int *ebase = nullptr,
+                                                    const int32_t *shape = nullptr) {
   const int t = blockIdx.x * 64 + threadIdx.x;
   if (t >= npairs) return;
   const int i = pi[t], j = pj[t];
   double cs[MAXC * 7];
-  const int nc = collide_boxes(pos + 3 * (size_t)i, R + 9 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j,
-                               R + 9 * (size_t)j, side + 3 * (size_t)j, cs);
+  int nc;
+  const bool si = SHAPES && shape[i] == kShapeSphere, sj = SHAPES && shape[j] == kShapeSphere;
+  if (si && sj)   // a sphere pair or sphere-box pair has one contact: only the joint test below can drop it
+    nc = collide_spheres(pos + 3 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j, side + 3 * (size_t)j, cs);
+  else if (si)
+    nc = collide_sphere_box(pos + 3 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j, R + 9 * (size_t)j,
+                            side + 3 * (size_t)j, /*flip=*/true, cs);
+  else if (sj)
+    nc = collide_sphere_box(pos + 3 * (size_t)j, side + 3 * (size_t)j, pos + 3 * (size_t)i, R + 9 * (size_t)i,
+                            side + 3 * (size_t)i, /*flip=*/false, cs);
+  else
+    nc = collide_boxes(pos + 3 * (size_t)i, R + 9 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j,
+                       R + 9 * (size_t)j, side + 3 * (size_t)j, cs);
   int kept = 0;
   for (int a = 0; a < nc; ++a) {
     bool del = false;
@@ -671,7 +778,7 @@ void Collider::set_ensembles(int n_ens, const int32_t *ens, const int32_t *eoff,
 }
 
 int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, const double *dside, int mj,
-                  const int32_t *djb0, const int32_t *djb1, const double *djdata) {
+                  const int32_t *djb0, const int32_t *djb1, const double *djdata, const int32_t *dshape) {
   const JointList jl{mj, djb0, djb1, djdata};
   Impl &I = *impl_;
   n_ground_ = 0; n_pairs_ = 0;
@@ -686,7 +793,12 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   // flags: [0] candidate overflow, [1] ground contacts, [2] candidate pairs, [3] pair contacts
   HIPCHK(hipMemsetAsync(I.flags.p, 0, 4 * sizeof(int), s));
   const int gb = (n + 255) / 256;
-  hipLaunchKernelGGL(ground_kernel, dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
+  // dshape == NULL: every body a box, the SHAPES = false instantiations (the launches of a world without shapes)
+  if (dshape)
+    hipLaunchKernelGGL((ground_kernel<true>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
+                       (int *)nullptr, (int *)nullptr, (double *)nullptr, (const int *)nullptr, (const int *)nullptr, dshape);
+  else
+  hipLaunchKernelGGL((ground_kernel<false>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
                      (int *)nullptr, (int *)nullptr, (double *)nullptr);
   exclusive_scan_async(s, n, I.gcount.p, I.goff.p, I.blocks.p, I.flags.p + 1);
   if (use_grid(n)) {
@@ -724,7 +836,12 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
                                   ens, eoff);
     else
     hipLaunchKernelGGL(flatten_kernel, dim3(gb), dim3(256), 0, s, n, I.cand.p, I.ccount.p, I.coff.p, I.pi.p, I.pj.p);
-    hipLaunchKernelGGL((narrow_kernel<false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+    if (dshape)
+      hipLaunchKernelGGL((narrow_kernel<false, true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+                         (const int *)nullptr, 0, I.pcount.p, (int *)nullptr, (int *)nullptr, (double *)nullptr, jl,
+                         (const int *)nullptr, (const int *)nullptr, dshape);
+    else
+    hipLaunchKernelGGL((narrow_kernel<false, false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                        (const int *)nullptr, 0, I.pcount.p, (int *)nullptr, (int *)nullptr, (double *)nullptr, jl);
     P = exclusive_scan(s, C, I.pcount.p, I.poff.p, I.blocks2.p, I.flags.p + 3);
   }
@@ -737,10 +854,17 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   }
   if (m == 0) return 0;
   I.b0.alloc(m); I.b1.alloc(m); I.data.alloc((size_t)m * 7);
-  hipLaunchKernelGGL(ground_kernel, dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
+  if (dshape)
+    hipLaunchKernelGGL((ground_kernel<true>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
+                       I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr, dshape);
+  else
+  hipLaunchKernelGGL((ground_kernel<false>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
                      I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr);
-  if (C > 0)
-    hipLaunchKernelGGL((narrow_kernel<true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+  if (C > 0 && dshape)
+    hipLaunchKernelGGL((narrow_kernel<true, true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+                       I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr, dshape);
+  else if (C > 0)
+    hipLaunchKernelGGL((narrow_kernel<true, false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                        I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr);
   HIPCHK(hipGetLastError());
   return m;
@@ -755,7 +879,7 @@ void Collider::export_topology(hipStream_t s, int m, int32_t *mapped_b0, int32_t
 
 int update_contacts(hipStream_t s, int n, const double *pos, const double *R, const double *side, int max_contacts,
                     int32_t *body0, int32_t *body1, double *data, int *n_ground, int *n_pairs, int mj,
-                    const int32_t *jb0, const int32_t *jb1, const double *jdata) {
+                    const int32_t *jb0, const int32_t *jb1, const double *jdata, const int32_t *shape) {
   if (n_ground) *n_ground = 0;
   if (n_pairs) *n_pairs = 0;
   if (n <= 0) return 0;
@@ -771,8 +895,10 @@ int update_contacts(hipStream_t s, int n, const double *pos, const double *R, co
     HIPCHK(hipMemcpyAsync(djb1.p, jb1, (size_t)mj * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(djdata.p, jdata, (size_t)mj * 7 * sizeof(double), hipMemcpyHostToDevice, s));
   }
+  ScopedDevBuf<int> dshape(shape ? nn : 0);
+  if (shape) HIPCHK(hipMemcpyAsync(dshape.p, shape, nn * sizeof(int), hipMemcpyHostToDevice, s));
   Collider col;
-  const int m = col.run(s, n, dpos.p, dR.p, dside.p, mj, djb0.p, djb1.p, djdata.p);
+  const int m = col.run(s, n, dpos.p, dR.p, dside.p, mj, djb0.p, djb1.p, djdata.p, shape ? dshape.p : nullptr);
   if (n_ground) *n_ground = col.n_ground();
   if (n_pairs) *n_pairs = col.n_pairs();
   if (m > max_contacts) throw std::invalid_argument("update_contacts: max_contacts too small (" + std::to_string(m) + " needed)");

@@ -29,6 +29,12 @@ struct egs_world {
   int n = 0, precision = EGS_F64;
   egs_problem *prob = nullptr;
   DevBuf<double> dside;
+  // egs_world_set_shapes: egs_shape per body on the device, handed to every Collider::run (shapes = false: NULL, the
+  // all-box launches); host copies of the shapes and the side lengths, for the check that a sphere's sides are (d, d, d)
+  bool shapes = false;
+  DevBuf<int32_t> dshape;
+  std::vector<int32_t> h_shape;
+  std::vector<double> h_side;
   Collider col;
   std::vector<int32_t> jb0, jb1;       // permanent constraints (joints), listed first (ensembles.cc:234-239)
   std::vector<double> jdata;
@@ -161,7 +167,8 @@ template <typename LAP>
 void world_update_contacts(egs_world *w, LAP &&lap) {
   hipStream_t s = w->ctx->stream;
   const int mj = (int)w->jb0.size();
-  const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, mj, w->djb0.p, w->djb1.p, w->djdata.p);
+  const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, mj, w->djb0.p, w->djb1.p, w->djdata.p,
+                            w->shapes ? w->dshape.p : nullptr);
   lap(0);
   const size_t mt = (size_t)mj + (size_t)mc;
   if (mt > w->h_cap) {   // grow-only; the stream is idle here (col.run synchronised)
@@ -715,20 +722,34 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
   });
 }
 
-}  // namespace
+// What is wrong with a shape array (nothing: an empty string): a value that is no egs_shape, or -- where the side lengths are
+// known (side != NULL) -- a sphere whose side row is not three equal positive numbers.
+std::string shapes_fault(int n, const int32_t *shape, const double *side) {
+  for (int b = 0; b < n; ++b) {
+    if (shape[b] != EGS_SHAPE_BOX && shape[b] != EGS_SHAPE_SPHERE)
+      return "body " + std::to_string(b) + ": unknown shape " + std::to_string(shape[b]);
+    if (shape[b] != EGS_SHAPE_SPHERE || !side) continue;
+    const double *d = side + 3 * (size_t)b;
+    if (!(d[0] > 0) || d[1] != d[0] || d[2] != d[0])
+      return "body " + std::to_string(b) + ": a sphere's side_lengths must be (d, d, d) with d > 0";
+  }
+  return std::string();
+}
 
-extern "C" {
-
-egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n, const double *pos, const double *R,
-                                      const double *side, int32_t m_joints, const int32_t *jb0, const int32_t *jb1,
-                                      const double *jdata, int32_t max_contacts, int32_t *m_out, int32_t *body0,
-                                      int32_t *body1, double *data) {
+egs_status update_contacts_entry(egs_context *ctx, int32_t n, const double *pos, const double *R, const double *side,
+                                 int32_t m_joints, const int32_t *jb0, const int32_t *jb1, const double *jdata,
+                                 const int32_t *shape, int32_t max_contacts, int32_t *m_out, int32_t *body0,
+                                 int32_t *body1, double *data) {
   if (!ctx) return EGS_ERR_INVALID;
   if (n < 0 || m_joints < 0 || !m_out || (n > 0 && (!pos || !R || !side)) || (m_joints > 0 && (!jb0 || !jb1 || !jdata)) ||
       (max_contacts > 0 && (!body0 || !body1 || !data)))
     return fail(ctx, EGS_ERR_INVALID, "NULL array");
   for (int q = 0; q < m_joints; ++q)
     if (jb0[q] < -1 || jb0[q] >= n || jb1[q] < -1 || jb1[q] >= n) return fail(ctx, EGS_ERR_INVALID, "joint body index out of range");
+  if (shape) {
+    const std::string fault = shapes_fault(n, shape, side);
+    if (!fault.empty()) return fail(ctx, EGS_ERR_INVALID, fault);
+  }
   *m_out = 0;
   // only body-body joints can prune (the pair scan never visits the ground, quirk Q4)
   std::vector<int32_t> b0, b1; std::vector<double> jd;
@@ -737,9 +758,27 @@ egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n, const double 
   return guarded(ctx, [&]() -> egs_status {
     HIPCHK(hipSetDevice(ctx->device));
     *m_out = update_contacts(ctx->stream, n, pos, R, side, max_contacts, body0, body1, data, nullptr, nullptr,
-                             (int)b0.size(), b0.data(), b1.data(), jd.data());
+                             (int)b0.size(), b0.data(), b1.data(), jd.data(), shape);
     return EGS_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n, const double *pos, const double *R,
+                                      const double *side, int32_t m_joints, const int32_t *jb0, const int32_t *jb1,
+                                      const double *jdata, int32_t max_contacts, int32_t *m_out, int32_t *body0,
+                                      int32_t *body1, double *data) {
+  return update_contacts_entry(ctx, n, pos, R, side, m_joints, jb0, jb1, jdata, nullptr, max_contacts, m_out, body0, body1, data);
+}
+
+egs_status egs_update_contacts_shapes(egs_context *ctx, int32_t n, const double *pos, const double *R,
+                                      const double *side, int32_t m_joints, const int32_t *jb0, const int32_t *jb1,
+                                      const double *jdata, const int32_t *shape, int32_t max_contacts, int32_t *m_out,
+                                      int32_t *body0, int32_t *body1, double *data) {
+  return update_contacts_entry(ctx, n, pos, R, side, m_joints, jb0, jb1, jdata, shape, max_contacts, m_out, body0, body1, data);
 }
 
 egs_status egs_update_contacts(egs_context *ctx, int32_t n, const double *pos, const double *R, const double *side,
@@ -791,13 +830,39 @@ egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R
   // are frozen at Init in the reference, Q5)
   if (w->n > 0 && !w->have_bodies && (!pos || !R || !v || !wv || !Minv || !f_ext || !side_lengths))
     return fail(w->ctx, EGS_ERR_INVALID, "NULL array on the first egs_world_set_bodies");
+  if (w->shapes && side_lengths) {   // new side lengths under the shapes in force: nothing changes if they do not fit
+    const std::string fault = shapes_fault(w->n, w->h_shape.data(), side_lengths);
+    if (!fault.empty()) return fail(w->ctx, EGS_ERR_INVALID, fault);
+  }
   return guarded(w->ctx, [&]() -> egs_status {
     if (!w->prob) world_make_problem(w, w->jb0.data(), w->jb1.data(), (int)w->jb0.size());
     egs_status st = egs_problem_set_state(w->prob, pos, R, v, wv, Minv, f_ext);
     if (st != EGS_OK) return st;
     world_drop_history(w);
-    if (side_lengths) upload(w->dside, side_lengths, (size_t)w->n * 3, w->ctx->stream);
+    if (side_lengths) {
+      upload(w->dside, side_lengths, (size_t)w->n * 3, w->ctx->stream);
+      w->h_side.assign(side_lengths, side_lengths + (size_t)w->n * 3);
+    }
     w->have_bodies = true;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape) {
+  if (!w) return EGS_ERR_INVALID;
+  if (shape) {   // against the side lengths if egs_world_set_bodies has given them, else there when it does
+    const std::string fault = shapes_fault(w->n, shape, w->h_side.empty() ? nullptr : w->h_side.data());
+    if (!fault.empty()) return fail(w->ctx, EGS_ERR_INVALID, fault);
+  }
+  return guarded(w->ctx, [&]() -> egs_status {
+    if (shape && w->n > 0) {
+      w->dshape.alloc((size_t)w->n);
+      upload(w->dshape, shape, (size_t)w->n, w->ctx->stream);
+      w->h_shape.assign(shape, shape + w->n);
+    }
+    w->shapes = shape && w->n > 0;
+    if (!w->shapes) w->h_shape.clear();
+    world_drop_history(w);
     return EGS_OK;
   });
 }

@@ -623,6 +623,16 @@ void Ensemble::StepPositions_ODE(double dt, const VectorXd &v, const VectorXd &v
   }
 }
 
+std::vector<int32_t> Ensemble::Shapes() const {
+  std::vector<int32_t> shape;
+  for (int i = 0; i < n_; ++i)
+    if (components_[i]->type() == Body::BodyType::Sphere) {
+      if (shape.empty()) shape.assign((size_t)n_, EGS_SHAPE_BOX);
+      shape[(size_t)i] = EGS_SHAPE_SPHERE;
+    }
+  return shape;
+}
+
 void Ensemble::UpdateContacts() {  // ensembles.cc:445-480 (+ :308-328)
   contacts_.clear();
   if (n_ == 0) return;
@@ -649,8 +659,10 @@ void Ensemble::UpdateContacts() {  // ensembles.cc:445-480 (+ :308-328)
     if (j->Describe(&kind, d7)) { jb0.push_back(j->i0_); jb1.push_back(j->i1_); jdata.insert(jdata.end(), d7, d7 + 7); }
     else host_joints.push_back(j);
   }
-  egs::check(egs_update_contacts_joints(egs::DefaultContext(), n_, pos.data(), R.data(), side.data(), (int32_t)jb0.size(),
-                                        jb0.data(), jb1.data(), jdata.data(), cap, &m, b0.data(), b1.data(), data.data()));
+  const std::vector<int32_t> shape = Shapes();   // empty: all boxes, egs_update_contacts_joints itself
+  egs::check(egs_update_contacts_shapes(egs::DefaultContext(), n_, pos.data(), R.data(), side.data(), (int32_t)jb0.size(),
+                                        jb0.data(), jb1.data(), jdata.data(), shape.empty() ? nullptr : shape.data(), cap, &m,
+                                        b0.data(), b1.data(), data.data()));
   for (int k = 0; k < m; ++k) {
     const double *d = &data[(size_t)k * 7];
     ContactGeometry cg(Vector3d(d[0], d[1], d[2]), Vector3d(d[3], d[4], d[5]), d[6]);
@@ -770,6 +782,8 @@ bool Ensemble::StepOnDevice(double dt) {
   if (!(warm_start_ && egs::same_state(world_state_, pos, R, vl, w)))
     egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
                                     first ? external_force_torque_.data() : nullptr, first ? side.data() : nullptr));
+  if (first)
+    if (const std::vector<int32_t> shape = Shapes(); !shape.empty()) egs::check(egs_world_set_shapes(world_, shape.data()));
   // joints are permanent in the reference (ensembles.cc:331-334); a caller that edits them all the same
   // (same count, other bodies or anchors) must not step against the stale device copy
   if (world_joints_ != mj || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {
@@ -826,6 +840,9 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
     throw egs::Error(EGS_ERR_UNSUPPORTED,
                      "Integrator::EXPLICIT_EULER panics in the reference (ComputeJDotV_Joints, ensembles.cc:94-97); "
                      "only Integrator::OPEN_DYNAMICS_ENGINE completes a step");
+  if (!detect_contacts && !Shapes().empty())
+    throw egs::Error(EGS_ERR_UNSUPPORTED, "an ensemble with a Sphere steps on contacts the device detects: not with "
+                                          "detect_contacts = false");
   if (StepOnDevice(dt)) return;   // collide -> solve -> integrate in one resident pipeline
   if (friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID)
     throw egs::Error(EGS_ERR_UNSUPPORTED, "COULOMB_PYRAMID steps on the device only: not with use_device_step = false, "
@@ -904,6 +921,9 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     const size_t o = (size_t)off_[i];
     if (m->n_ != off_[i + 1] - off_[i])
       throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " changed its number of bodies");
+    if (!m->detect_contacts && !m->Shapes().empty())
+      throw egs::Error(EGS_ERR_UNSUPPORTED, "EnsembleGroup: member " + std::to_string(i) + " holds a Sphere and steps on contacts "
+                                                "the device detects: not with detect_contacts = false");
     for (int b = 0; b < m->n_; ++b) {
       const Body &body = *m->components_[b];
       const size_t g = o + (size_t)b;
@@ -954,6 +974,15 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   if (!(warm && egs::same_state(world_state_, pos, R, vl, w)))
     egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
                                     first ? fext.data() : nullptr, first ? side.data() : nullptr));
+  if (first) {   // the members' shapes, with the side lengths; none sent when every Body of every member is a box
+    std::vector<int32_t> shape(n, EGS_SHAPE_BOX);
+    bool any = false;
+    for (size_t i = 0; i < E; ++i) {
+      const std::vector<int32_t> s = members_[i]->Shapes();
+      if (!s.empty()) { std::copy(s.begin(), s.end(), shape.begin() + off_[i]); any = true; }
+    }
+    if (any) egs::check(egs_world_set_shapes(world_, shape.data()));
+  }
   world_state_.clear();
   if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {   // re-sent when edited
     egs::check(egs_world_set_joints(world_, (int32_t)jb0.size(), jb0.data(), jb1.data(), jdata.data()));

@@ -60,7 +60,21 @@ class Body {  // body.h:13-96
   void SetV(const Vector3d &v) { v_ = v; }
   void SetR(const Matrix3d &R) { R_ = R; }
   void SetW_GlobalFrame(const Vector3d &w) { w_ = w; }
-  Vector3d GetSideLengths() const { return Vector3d(0.3, 0.3, 0.3); }  // body.h:91
+  // body.h:60: `enum struct BodyType { Box = 0 }` with the TODO "move this to a subclass when there are different
+  // types of Bodies".  Sphere is not in the reference: a ball of the given radius and mass, I = (2/5) m r^2 * 1,
+  // collided as a sphere on the device (EGS_SHAPE_SPHERE; its side lengths are the diameter three times).
+  enum struct BodyType { Box = 0, Sphere };
+  static Body Sphere(const Vector3d &p, const Vector3d &v, double radius, double m = 1.0) {
+    Body b(p, v, m, Matrix3d::Identity(), Vector3d::Zero(), Matrix3d::Identity() * (0.4 * m * radius * radius));
+    b.type_ = BodyType::Sphere;
+    b.radius_ = radius;
+    return b;
+  }
+  BodyType type() const { return type_; }
+  double radius() const { return radius_; }   // 0 for a box
+  Vector3d GetSideLengths() const {           // body.h:91 for a box
+    return type_ == BodyType::Sphere ? Vector3d(2 * radius_, 2 * radius_, 2 * radius_) : Vector3d(0.3, 0.3, 0.3);
+  }
 
  private:
   Vector3d p_, v_;
@@ -68,6 +82,8 @@ class Body {  // body.h:13-96
   Matrix3d R_;
   Vector3d w_;
   Matrix3d I_;
+  BodyType type_ = BodyType::Box;
+  double radius_ = 0.0;
   Matrix3d CalculateInertia(double m) const;  // body.cc:19-36
 };
 
@@ -345,6 +361,10 @@ class Ensemble {  // ensembles.h:25-186
   VectorXd StepVelocities_ODE(double dt, const VectorXd &v, double error_reduction_param = 0.2);  // :563-575
   void StepPositions_ODE(double dt, const VectorXd &v, const VectorXd &v_new);                    // :577-591
   bool StepOnDevice(double dt);
+  // egs_shape per component; empty when every Body is a box (the library then takes its all-box launches).  Shapes
+  // go to the device with the side lengths (frozen at Init(), Q5) and with every UpdateContacts().  A sphere ensemble
+  // needs the device's detection: Step throws egs::Error(EGS_ERR_UNSUPPORTED) with detect_contacts = false.
+  std::vector<int32_t> Shapes() const;
   // -step_scale * J^T (J J^T)^-1 err (ensembles.cc:659-666); the SPD(-semidefinite)
   // solve runs matrix-free on the GPU: the same projected sweep with M^-1 = I and
   // every row an equality.

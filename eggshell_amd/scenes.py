@@ -169,6 +169,20 @@ def cairn(n, overlap=0.03, tilt=0.2, seed=0, origin=(0.0, 0.0)):
                 I_body=np.tile((np.eye(3) * 0.1).reshape(9), (n, 1)))
 
 
+def ball_pile(nx, ny, nz, radius=0.15, sink=1e-3, gap=1e-2, mass=1.0, origin=(0.0, 0.0)):
+    """nx x ny columns of nz balls (radius, mass, I = (2/5) m r^2 * I3), the columns `gap` apart, each ball `sink`
+    into the one below and the lowest `sink` into the ground: marbles on a plate for nz = 1.  Bodies only, with
+    side = (2r, 2r, 2r) and shape = 1 (capi.SHAPE_SPHERE) per ball for World.set_bodies / set_shapes; the contacts
+    come from the device (Context.update_contacts_shapes or a world step)."""
+    d = 2.0 * radius
+    p = np.array([[origin[0] + i * (d + gap), origin[1] + j * (d + gap), (radius - sink) + k * (d - sink)]
+                  for i in range(nx) for j in range(ny) for k in range(nz)]).reshape(-1, 3)
+    n = p.shape[0]
+    return dict(p=p, R=np.tile(np.eye(3).reshape(9), (n, 1)), v=np.zeros((n, 3)), w=np.zeros((n, 3)),
+                mass=np.full(n, float(mass)), I_body=np.tile((np.eye(3) * (0.4 * mass * radius * radius)).reshape(9), (n, 1)),
+                side=np.full((n, 3), d), shape=np.ones(n, np.int32))
+
+
 def concat(scenes):
     """Batch independent ensembles into one system (body indices offset)."""
     out = {}

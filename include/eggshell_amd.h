@@ -420,6 +420,33 @@ egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n_bodies,
                                       int32_t *m_out, int32_t *body0,
                                       int32_t *body1, double *data);
 
+/* ---- shapes: spheres beside boxes.
+ * A sphere is a body whose side_lengths row is (d, d, d) with d > 0; r = d / 2 and its R is not read by the
+ * collider.  The conventions are the box code's: body0 < body1 or body0 = -1 (ground), the normal points from body0
+ * towards body1, depth >= 0, a pair exactly touching is a contact, a ground contact needs z < 0 strictly.
+ *   sphere - ground: q = (c_x, c_y, c_z - r); contact iff q_z < 0: (q, (0, 0, 1), -q_z).
+ *   sphere i - sphere j: d = c_j - c_i, L = |d|, s = L - (r_i + r_j); contact iff s <= 0; n = d / L ((0, 0, 1) when
+ *     L == 0), depth = -s, position = c_i + n (r_i + L - r_j) / 2.
+ *   sphere S - box B: p = R_B^T (c_S - c_B), h = side_B / 2, q_k = clamp(p_k, -h_k, h_k).  Centre outside (q != p):
+ *     e = p - q, L = |e|, contact iff L - r <= 0, n_BS = R_B e / L, depth = r - L, box point R_B q + c_B.  Centre
+ *     inside or on the surface: k = argmin_k (h_k - |p_k|) (lowest k on a tie), n_BS = sgn(p_k) (column k of R_B) with
+ *     sgn(0) = +1, depth = (h_k - |p_k|) + r, box point = the centre moved onto that face.  Sphere point
+ *     c_S - r n_BS; position = the midpoint of the two points; the normal is n_BS if the box is body0, else -n_BS.
+ * A pair with a sphere has at most one contact; the joint-vs-contact pruning applies to it unchanged.  The list order
+ * is unchanged and box-box pairs emit what they emit without shapes.  Inertia stays the caller's (Minv).           */
+typedef enum { EGS_SHAPE_BOX = 0, EGS_SHAPE_SPHERE = 1 } egs_shape;
+
+/* egs_update_contacts_joints with shape [n_bodies] (egs_shape values) or NULL.  NULL, or all EGS_SHAPE_BOX, gives the
+ * result of egs_update_contacts_joints bit for bit.  EGS_ERR_INVALID: an unknown shape value, a sphere whose
+ * side_lengths row is not three equal positive numbers.                                                           */
+egs_status egs_update_contacts_shapes(egs_context *ctx, int32_t n_bodies,
+                                      const double *pos, const double *R,
+                                      const double *side_lengths, int32_t m_joints,
+                                      const int32_t *jb0, const int32_t *jb1,
+                                      const double *jdata, const int32_t *shape,
+                                      int32_t max_contacts, int32_t *m_out,
+                                      int32_t *body0, int32_t *body1, double *data);
+
 /* ---- carrying lambda across a contact list that changes: the start (x0 of egs_problem_set_start's
  *      EGS_START_GIVEN) of a solve on the new list from the lambda of the last solve on the old one.
  * Both lists hold n_ens >= 1 ensembles back to back (offsets [n_ens + 1], from 0 to m), each in the order
@@ -457,6 +484,13 @@ void egs_world_destroy(egs_world *w);
 egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R, const double *v,
                                 const double *w_ang, const double *Minv, const double *f_ext,
                                 const double *side_lengths);
+/* shape [n_bodies] (egs_shape; global body indices in a batched world) for every entry that detects contacts:
+ * egs_world_step[_each], egs_world_step_dense[_each], egs_world_stabilize[_direct] with detect_contacts = 1.  NULL
+ * switches back to boxes.  Valid any time after the world is created; drops the warm-start history as
+ * egs_world_set_bodies does.  EGS_ERR_INVALID, with nothing changed: an unknown value; a sphere whose side_lengths row
+ * is not three equal positive numbers -- checked when both are known, i.e. here if egs_world_set_bodies has given the
+ * side lengths and in egs_world_set_bodies whenever it is given side_lengths while shapes are set.             */
+egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape);
 /* ball joints: body0/body1 [m], data [m][7] = c0, c1 (world point if body1 = -1), 0 */
 egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
                                 const double *data);
