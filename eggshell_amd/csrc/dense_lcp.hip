@@ -1570,7 +1570,7 @@ bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db,
     return rec->first_offender == 0x7fffffff && !rec->out_of_bounds && !rec->w_bad && std::sqrt(rec->resid2) <= tol;
   };
   int iter = 0, pivots = 0, bordered = 0;
-  bool last_bordered = false;
+  bool last_bordered = false, polished = false;
   bool force = box_fix, solved = false, timed_out = false;
   // the start iterate: its goodness opens the best-solution memory; a box problem solves once before the first flip,
   // the reference's loop (lcp.cc:196-198) checks and flips first
@@ -1583,16 +1583,24 @@ bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db,
       timed_out = true;   // lcp::Settings::max_time (toolkit/lcp.h:166-167)
       break;
     }
-    if (!force && is_solution(1e-9)) { solved = true; break; }
+    // The reference's rule starts from S = everything and moves one index per pivot, so its bordered pivots all stand on
+    // the factor of the FIRST set: an accepted x then carries the conditioning of that set (often the whole matrix), not
+    // of its own A(S,S) -- on a C5-recipe matrix of 113 rows a backward error of 112 u where a factorisation of the final
+    // set gives 1 u.  Such an iterate is solved once more on a fresh factor of its own set before
+    // it is accepted; that is no pivot of the rule (S does not change) and is not counted as one.  The block rule's
+    // bases lie next to its final set and measure like fresh factors, so it keeps its last bordered pivot.
+    const bool polish = !force && !block && last_bordered && !polished && is_solution(1e-9);
+    if (!force && !polish && is_solution(1e-9)) { solved = true; break; }
     // (no index to flip but not a solution -- residual / sign checks failed: the reference recomputes with unchanged S,
     //  and so does this)
     force = false;
+    polished = polished || polish;
     // new candidate: x(S) = A(S,S)^-1 (b(S) [- A(S,!S) x(!S)])   lcp.cc:199-216
     const int ns = rec->ns;
     const int nspad = (ns + NB - 1) / NB * NB;
     hipLaunchKernelGGL(murty_prep_kernel, dim3((n + 3) / 4), dim3(256), 0, s, dA, n, db, S_d.p, Cb.p, box_fix ? 1 : 0, beff.p, dx);
     const int nd = rec->nd, nr = rec->nr, mb = nd + nr;
-    if (track_base && base_n0 > 0 && nd >= 0 && mb <= kBorderMax && ns > 0) {
+    if (track_base && base_n0 > 0 && nd >= 0 && mb <= kBorderMax && ns > 0 && !polish) {
       // a few indexes away from the factored set: the bordered system on the old factor
       const int n0 = base_n0, n0pad = (n0 + NB - 1) / NB * NB, nblocks = n0pad / NB;
       hipLaunchKernelGGL(border_build_kernel, dim3(grid1((size_t)n0pad * kBorderStride)), dim3(256), 0, s, dA, n, beff.p, idx0.p, n0, n0pad,
@@ -1616,7 +1624,7 @@ bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db,
     }
     // r = A x - b; w(!S) = r.  (The reference, lcp.cc:219-221, uses x(S) only: x(!S) = lo = 0 there, so A x(S) == A x.)
     hipLaunchKernelGGL(murty_resid_kernel, dim3((n + 3) / 4), dim3(256), 0, s, dA, n, dx, db, S_d.p, r.p, dw);
-    ++pivots;
+    if (!polish) ++pivots;
     advance(flip_mode, 1e-9, 1);     // lcp.cc:125-137: the best iterate by "goodness" is kept by the kernel
     // resid2 is the squared residual of A(S,S) x(S) = b(S) (w is zero on S, r - w off it): a bordered solve that misses
     // the tolerance a solution must meet anyway is not built upon -- the next pivot factors afresh
@@ -1624,11 +1632,11 @@ bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db,
     if (trace) {
       const auto t_now = std::chrono::steady_clock::now();
       std::fprintf(stderr, "dense trace pivot %d: ns %d of %d (%s, +%d -%d against the factored set), %.3f ms, residual on S %.1e; then %d infeasible, %d flipped\n",
-                   pivots, ns, n, last_bordered ? "bordered" : "factored", nd, nr,
+                   pivots, ns, n, polish ? "accepted set factored afresh" : last_bordered ? "bordered" : "factored", nd, nr,
                    std::chrono::duration<double, std::milli>(t_now - t_prev).count(), std::sqrt(rec->resid2), rec->ninf, rec->flipped);
       t_prev = t_now;
     }
-    ++iter;
+    if (!polish) ++iter;
   }
   if (!solved && iter < max_iterations && !timed_out && !rec->fail) solved = is_solution(1e-9);
   if (trace) std::fprintf(stderr, "dense trace: %d pivots, %d of them bordered\n", pivots, bordered);

@@ -39,6 +39,7 @@ def test_mixed_no_bounds_vs_oracle(ctx, dim):
         assert piv == pivo
         scale = max(1.0, np.abs(xo).max())
         assert np.abs(x - xo).max() <= 1e-8 * scale and np.abs(w - wo).max() <= 1e-8 * scale
+        # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 def test_all_equality_and_all_inequality(ctx):
@@ -49,6 +50,7 @@ def test_all_equality_and_all_inequality(ctx):
     ok, x, w, piv = ctx.mixed_constraints_solve(A, b, np.ones(dim, np.uint8), np.zeros(dim), np.full(dim, INF))
     assert ok and piv == 0 and not w.any()
     assert np.abs(x - np.linalg.solve(A, b)).max() <= 1e-8 * max(1.0, np.abs(x).max())
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
     ok, x, w, piv = ctx.mixed_constraints_solve(A, b, np.zeros(dim, np.uint8), np.zeros(dim), np.full(dim, INF))
     oko, xo, wo, pivo = orc.murty(A, b)
     assert ok and oko and piv == pivo and np.abs(x - xo).max() < 1e-8
@@ -75,6 +77,7 @@ def test_bounds_ignored_like_reference_and_true_box(ctx):
     assert (w[ineq & (x == lo)] >= -1e-9).all() and (w[ineq & (x == hi)] <= 1e-9).all()
     oko, xo, wo, _ = orc.mixed_constraints(A, b, Ceq, lo, hi, use_bounds=1)
     assert oko and np.abs(x - xo).max() < 1e-8
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 def test_dense_on_ensemble_matrix(ctx):
@@ -89,6 +92,7 @@ def test_dense_on_ensemble_matrix(ctx):
     ok, x, w, piv = ctx.mixed_constraints_solve(A, rhs, s.is_eq, s.lo, s.hi)
     oko, xo, wo, _ = orc.mixed_constraints(A, rhs, s.is_eq, s.lo, s.hi)
     assert ok and oko and np.abs(x - xo).max() <= 1e-9 * max(1.0, np.abs(xo).max())
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 def test_not_positive_definite_reports_failure(ctx):
@@ -98,8 +102,10 @@ def test_not_positive_definite_reports_failure(ctx):
 
 
 def test_config5_size_properties(ctx):
-    """N = 1024 mixed problem (C5 is N = 2048; the bench tool reports it):
-    Ax = b + w and complementarity, no oracle at this size."""
+    """N = 1024 mixed problem (C5 is N = 2048; the bench tool reports it) under the reference's rule.  The oracle, run
+    once on this exact input (21 s on a CPU, so not in the suite), gives up at the reference's own cap of 1000 pivots
+    (lcp.cc:168): ok = false, 1000 pivots.  The device must report exactly that outcome; the block rule's answers at
+    this size are checked against the certified reference in test_gpu_lcp_reference.py."""
     rng = np.random.default_rng(8)
     N = 1024
     M = rng.uniform(-1, 1, (N, N))
@@ -107,13 +113,7 @@ def test_config5_size_properties(ctx):
     b = rng.uniform(-1, 1, N)
     Ceq = rng.integers(0, 2, N).astype(np.uint8)
     ok, x, w, piv = ctx.mixed_constraints_solve(A, b, Ceq, np.zeros(N), np.full(N, INF))
-    if ok:   # the reference's own cap (1000 pivots, lcp.cc:168) may bite at this size
-        assert np.linalg.norm(A @ x - b - w) < 1e-6 * np.linalg.norm(b) * 1e3
-        eq = Ceq.astype(bool)
-        assert (x[~eq] >= 0).all() and (w[~eq] >= -1e-8).all()
-        assert abs(x[~eq] @ w[~eq]) < 1e-6
-    else:
-        assert piv >= 1000
+    assert not ok and piv == 1000
 
 
 @pytest.mark.parametrize("dim", [2, 63, 111, 112, 113])
@@ -133,6 +133,7 @@ def test_single_workgroup_loop_boundary(ctx, dim):
     ok, x, w, piv = ctx.mixed_constraints_solve(A, b, none, lo, hi, use_bounds=1)
     oko, xo, wo, pivo = orc.mixed_constraints(A, b, none, lo, hi, use_bounds=1)
     assert ok and oko and piv == pivo and np.abs(x - xo).max() <= 1e-8 and np.abs(w - wo).max() <= 1e-8
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 def test_single_workgroup_loop_reports_indefinite_matrix(ctx):

@@ -32,6 +32,7 @@ def test_block_rule_same_solution_as_reference_rule(ctx, dim):
     ok, x, w, piv = ctx.mixed_constraints_solve(A2, b2, Ceq, np.full(dim, -0.3), np.full(dim, 0.4), use_bounds=3)
     oko, xo, wo, _ = orc.mixed_constraints(A2, b2, Ceq, np.full(dim, -0.3), np.full(dim, 0.4), use_bounds=1)
     assert ok and oko and np.abs(x - xo).max() <= 1e-8
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 def test_config5_n2048(ctx):
@@ -52,6 +53,7 @@ def test_config5_n2048(ctx):
     assert not w[eq].any()
     assert (x[~eq] >= 0).all() and (w[~eq] >= -1e-7).all()
     assert np.abs(x[~eq] * w[~eq]).max() < 1e-7
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 @pytest.mark.parametrize("N,mode", [(1100, 2), (1100, 3), (1350, 2)])
@@ -83,6 +85,7 @@ def test_block_rule_between_the_round_sizes(ctx, N, mode, monkeypatch):
     #  them set from outside -- tests/tools/env_matrix.sh does)
     ok2, x2, w2, _ = ctx.mixed_constraints_solve(A, b, Ceq, lo, hi, use_bounds=mode)
     assert ok2 and np.abs(x2 - x).max() <= 1e-8 * max(1.0, np.abs(x).max())
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
 
 
 @pytest.mark.parametrize("N,eq_frac", [(1200, 1.0), (1400, 0.9), (2300, 1.0)])
@@ -101,3 +104,4 @@ def test_many_equality_rows(ctx, N, eq_frac):
     assert not w[eq].any() and (x[~eq] >= -1e-9).all() and (w[~eq] >= -1e-7).all()
     if eq.all():
         assert np.abs(x - np.linalg.solve(A, b)).max() <= 1e-7 * max(1.0, np.abs(x).max())
+        # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's)
