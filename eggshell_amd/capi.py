@@ -25,6 +25,7 @@ SCHED_FUSED_ASSEMBLY = 256
 SCHED_DEFERRED_SYSTEM = 512
 SCHED_START = 1024
 SCHED_FRICTION = 2048
+SCHED_PAIR = 4096
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
@@ -42,7 +43,7 @@ EXPORTS = [
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
-    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
+    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
@@ -739,6 +740,16 @@ def debug_plan_timetable(n_bodies, body0, body1, tile_size=256):
     if st != OK:
         raise EgsError(st, "egs_debug_plan_timetable failed")
     return dict(level=out[0], period=out[1], depth=out[2], runs=bool(runs.value))
+
+
+def debug_plan_pairable(n_bodies, body0, body1):
+    """Host-only: does the 256-lane tile plan keep one timetable phase per half-wavefront (see egs_debug_plan_pairable)?"""
+    body0, body1 = _i32(body0), _i32(body1)
+    out = C.c_int32(0)
+    st = load().egs_debug_plan_pairable(C.c_int32(n_bodies), C.c_int32(body0.shape[0]), _p(body0), _p(body1), C.byref(out))
+    if st != OK:
+        raise EgsError(st, "egs_debug_plan_pairable failed")
+    return bool(out.value)
 
 
 class World:

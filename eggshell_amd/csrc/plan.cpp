@@ -354,7 +354,7 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
     plan = std::move(*recycle);
     plan.n_islands = plan.n_tiles = 0; plan.max_slots = 1; plan.max_cnt = 1;
     plan.lanes.clear(); plan.lane_level.clear(); plan.tile_period.clear(); plan.tile_depth.clear();
-    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false;
+    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false; plan.pairable = false;
     plan.tile_nslots.clear(); plan.tile_slot_off.clear(); plan.slot_body.clear();
     plan.global.clear();
     plan.n_patch_tiles = 0; plan.patch_max_slots = 1; plan.n_shared_bodies = 0; plan.patch_runs = false;
@@ -742,6 +742,19 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
     plan.max_period = std::max(plan.max_period, plan.tile_period[t]);
     plan.max_depth = std::max(plan.max_depth, plan.tile_depth[t]);
   }
+  // pairable (plan.h): in every wavefront of every tile each half (lanes 0-31, lanes 32-63) is idle or shares one
+  // phase, level mod the tile's period (the backward timetable mirrors the levels: equal phases stay equal)
+  plan.pairable = block == 256 && plan.n_tiles > 0 && plan.levels_ok && !plan.runs;
+  for (int t = 0; t < plan.n_tiles && plan.pairable; ++t)
+    for (int h = 0; h < block / 32 && plan.pairable; ++h) {
+      int phase = -1;
+      for (int l = 32 * h; l < 32 * h + 32; ++l) {
+        if (plan.lanes[(size_t)t * block + l].cidx < 0) continue;
+        const int ph = plan.lane_level[(size_t)t * block + l] % plan.tile_period[t];
+        if (phase < 0) phase = ph;
+        else if (ph != phase) plan.pairable = false;
+      }
+    }
   plan.slot_body.assign((size_t)off, -1);   // slot 0 of every tile = the world
   for (int b = 0; b < n_bodies; ++b)
     if (body_tile[b] >= 0) plan.slot_body[(size_t)plan.tile_slot_off[body_tile[b]] + body_slot[b]] = b;

@@ -57,6 +57,11 @@ struct Plan {
   // lane mod 4.  Only 4-lane plans built with max_run_tiles > 0, needing at most that many tiles, and with less than a quarter of padding (a chunk keeps
   // 1/4 of its wavefront's lanes busy: worth it where the chain latency sets the time, about one tile per CU).
   bool runs = false;
+  // Every half-wavefront of plan lanes (lanes 32 h .. 32 h + 31 of a 256-lane tile) is idle or holds constraints of
+  // ONE phase (level mod the tile's period): a time step's due lanes fill half-wavefronts, as in a pile of columns
+  // under the phase-major lane order.  That is where step_solve_kernel's PAIR form pays (step_solve.hip): it runs the
+  // update of lane 64 w + j on the thread pair (2 j, 2 j + 1) of wavefront w, and then that of lane 64 w + 32 + j.
+  bool pairable = false;
   std::vector<int32_t> tile_nslots;   // per tile, slots in use (slot 0 = world)
   std::vector<int32_t> tile_slot_off; // per tile, offset into slot_body
   std::vector<int32_t> slot_body;     // slot -> global body index (-1 for slot 0)

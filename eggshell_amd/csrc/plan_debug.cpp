@@ -147,4 +147,12 @@ egs_status egs_debug_plan_timetable(int32_t n, int32_t m, const int32_t *body0, 
   });
 }
 
+egs_status egs_debug_plan_pairable(int32_t n, int32_t m, const int32_t *body0, const int32_t *body1, int32_t *pairable) {
+  return plan_entry(n, m, body0, body1, [&]() -> egs_status {
+    const Plan pl = build_plan(n, m, body0, body1, 256);
+    if (pairable) *pairable = pl.pairable ? 1 : 0;
+    return EGS_OK;
+  });
+}
+
 }  // extern "C"

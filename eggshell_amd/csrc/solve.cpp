@@ -22,6 +22,7 @@ struct SweepSchedule {
   bool linsym = false;      // step_solve_kernel's LINSYM form
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
+  bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_solve.hip)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -30,7 +31,7 @@ struct SweepSchedule {
   uint32_t flags() const {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
-           (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0);
+           (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0);
   }
 };
 
@@ -79,6 +80,10 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   // ... which stores no system (problem.h: ensure_system).  EGS_STEP_DEFER_SYSTEM=0 keeps the eager stores.
   const char *de = std::getenv("EGS_STEP_DEFER_SYSTEM");
   s.defer = s.assemble && !(de && std::atoi(de) == 0);
+  // ... on a lane pair per update, where the plan's half-wavefronts each hold one phase (plan.h: pairable).
+  // EGS_STEP_PAIR=0 keeps one lane per constraint.
+  const char *pe = std::getenv("EGS_STEP_PAIR");
+  s.pair = s.assemble && pl.pairable && !(pe && std::atoi(pe) == 0);
   return s;
 }
 
@@ -166,7 +171,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, ctx->stream);
+          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, ctx->stream);
           // the system this launch assembled: stored, or the problem's to make on demand from the state it read
           p->sys_deferred = sc.defer;
           p->deferred_prev = false;

@@ -350,6 +350,17 @@ __device__ __forceinline__ void load12(unsigned ac0, unsigned ac1, float (&a0)[6
   a0[0] = u0.x; a0[1] = u0.y; a0[2] = u1.x; a0[3] = u1.y; a0[4] = u2.x; a0[5] = u2.y;
   a1[0] = v0.x; a1[1] = v0.y; a1[2] = v1.x; a1[3] = v1.y; a1[4] = v2.x; a1[5] = v2.y;
 }
+// one body's accumulator (step_solve.hip: the PAIR form, a lane holds one side of a constraint)
+__device__ __forceinline__ void load6(unsigned ac, double (&a)[6]) {
+  d2_t u0, u1, u2;
+  asm volatile(
+      "ds_read_b128 %0, %3\n\t"
+      "ds_read_b128 %1, %3 offset:16\n\t"
+      "ds_read_b128 %2, %3 offset:32\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(u0), "=&v"(u1), "=&v"(u2) : "v"(ac) : "memory");
+  a[0] = u0.x; a[1] = u0.y; a[2] = u1.x; a[3] = u1.y; a[4] = u2.x; a[5] = u2.y;
+}
 __device__ __forceinline__ void store6(unsigned ac, const double (&a)[6]) {
   d2_t u0 = {a[0], a[1]}, u1 = {a[2], a[3]}, u2 = {a[4], a[5]};
   asm volatile(
@@ -382,6 +393,18 @@ __device__ __forceinline__ double dpp(double v) {
   const int lo = dpp_i<CTRL>(__double2loint(v)), hi = dpp_i<CTRL>(__double2hiint(v));
   return __hiloint2double(hi, lo);
 }
+
+// The same move where every lane that executes it has its source lane executing too (a quad_perm among lanes that
+// take a branch together): no value for lanes without a source, so no register is set up for one.
+template <int CTRL>
+__device__ __forceinline__ double dpp_all(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+constexpr int kQuadSwap = 0xB1;    // quad_perm:[1,0,3,2]: the other lane of an even / odd lane pair
+constexpr int kQuadEven = 0xA0;    // quad_perm:[0,0,2,2]: the pair's even lane, in both
+constexpr int kQuadOdd = 0xF5;     // quad_perm:[1,1,3,3]: the pair's odd lane, in both
 
 template <typename T>
 __device__ __forceinline__ T gld(const T *p) {

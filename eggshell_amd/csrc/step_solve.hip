@@ -54,6 +54,9 @@
 //
 // STORE_SYSTEM = false: none of that is stored -- a step reads none of it (the sweeps run from registers) -- and the
 // problem remembers that its system is not materialised (problem.h: ensure_system runs assemble_kernel on demand).
+//
+// PAIR (ASSEMBLE only): an update runs on a lane pair, each lane holding one side of two constraints; described where
+// it is written, before the kernel.
 #include <algorithm>
 
 #include "kernels.h"
@@ -201,12 +204,251 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
   return n_phases >= 1 ? depth + P * (n_phases - 1) : 0;
 }
 
+// ---- PAIR (ASSEMBLE only): one update on a lane pair --------------------------------------------------------------
+// In a regular pile tile a time step has 32 due lanes, all in one wavefront, and a pass costs the same with 32 active
+// lanes as with 64.  Here thread l of wavefront w plays side s = l & 1 of TWO constraints, A = plan lane 64 w + (l >> 1)
+// and B = plan lane 64 w + 32 + (l >> 1): it holds side s's block J_s, weights and accumulator address of both, and the
+// even lane owns A's rhs, x, D and inv, the odd lane B's.  An update of A runs on both lanes of the pair: each forms its
+// side's half of the three row sums, the halves cross by DPP, the owner alone projects, dx goes back by DPP and each
+// lane updates and stores its own side's accumulator.  256 threads still hold 256 constraints, at the same registers.
+// Same bits: the row sum keeps (p0 + p1) + (p2 + p3) (the odd owner adds the halves the other way round: commutative);
+// side 1's linear terms take J1_lin itself, bit-equal to the -Jl of LINSYM, and its products wl1 J1_lin are -(wl1 Jl);
+// side 0's take J0_lin = Jl and wl0 = wl1 (LINSYM's preconditions); a side without a body holds zeros and reads the
+// world slot, whose half sums to the same +0.  The form is right for any plan; it pays where each half-wavefront of
+// plan lanes shares one phase (plan.h: Plan::pairable), which is where solve.cpp takes it.
+
+// How many of a side's 18 products w J (column-major as the accumulator update takes them: the nine linear first) a
+// lane holds per constraint: the largest count at which the instantiation keeps scratch 0 and at most 168 VGPRs, found
+// by compiling every count.  Six spill 12 to 20 bytes in every one of the four.
+constexpr int kPairHeldFree[2] = {5, 5};    // store-free: GS, backward SOR
+constexpr int kPairHeldStore[2] = {5, 5};   // storing
+template <int METHOD, bool STORE_SYSTEM>
+constexpr int pair_products() {
+  return STORE_SYSTEM ? kPairHeldStore[METHOD - 1] : kPairHeldFree[METHOD - 1];
+}
+
+// one side of one constraint, as its lane holds it
+template <int HELD>
+struct PairSide {
+  double J[18];   // 3x6 row-major; zeros where the constraint has no body on this side
+  double wl, wa;
+  double p[HELD > 0 ? HELD : 1];   // product i = w J[6 (i % 3) + i / 3]
+  __device__ __forceinline__ void form() {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) {
+      if (i < HELD) {
+        p[i] = (i < 9 ? wl : wa) * J[6 * (i % 3) + i / 3];   // the one multiply of acc_add_iso: the same rounding
+        asm volatile("" : "+v"(p[i]));
+      }
+    }
+  }
+  // acc_add_iso with the held products taken from registers; the weights opaque in place, as in linsym_acc_add
+  __device__ __forceinline__ void acc_add(double *a, const double *d) {
+    if constexpr (HELD < 9) asm volatile("" : "+v"(wl), "+v"(wa));
+    else if constexpr (HELD < 18) asm volatile("" : "+v"(wa));
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const double w = k < 3 ? wl : wa;
+      double t = tfma(3 * k < HELD ? p[3 * k] : w * J[k], d[0], a[k]);
+      t = tfma(3 * k + 1 < HELD ? p[3 * k + 1] : w * J[6 + k], d[1], t);
+      a[k] = tfma(3 * k + 2 < HELD ? p[3 * k + 2] : w * J[12 + k], d[2], t);
+    }
+  }
+  // this side's half of row r's sum: p0 + p1 resp. p2 + p3 of row_dot
+  __device__ __forceinline__ double half_dot(int r, const double *a) const {
+    return dot3h(J + 6 * r, a) + dot3h(J + 6 * r + 3, a + 3);
+  }
+};
+
+// One update of a pair's constraint on both lanes.  own: this lane holds the constraint's scalars (c, x); BCAST: the
+// quad_perm that hands the owner's value to both; GENERAL: the update may be the accumulation (sweep 0: dx = x).
+template <int METHOD, int BCAST, bool GENERAL, int HELD>
+__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, bool has, bool own, const Cons<double> &c,
+                                          double (&x)[3], int sweep, double cfm) {
+  double a[6], dx[3];
+  load6(ac, a);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double h = S.half_dot(r, a);
+    dx[r] = h + dpp_all<kQuadSwap>(h);   // the row sum, until the owner puts dx there
+  }
+  if (own) {
+    if (GENERAL && sweep == 0) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) dx[r] = x[r];
+    } else {
+      double res[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) res[r] = c.rhs[r] - tfma(cfm, x[r], dx[r]);
+      update_rows<double, METHOD, true, false>(c, res, x, dx);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) dx[r] = dpp_all<BCAST>(dx[r]);
+  if (has) {
+    S.acc_add(a, dx);
+    store6(ac, a);
+  }
+}
+
+// lambda and w = A x - rhs of a pair's constraint, written by its owner
+template <int HELD>
+__device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const PairSide<HELD> &S, unsigned ac, bool own,
+                                              int cidx, const Cons<double> &c, const double *x) {
+  double a[6];
+  load6(ac, a);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double h = S.half_dot(r, a);
+    const double ax = h + dpp_all<kQuadSwap>(h);
+    if (own) {
+      A.x[(size_t)cidx * 3 + r] = x[r];
+      A.wres[(size_t)cidx * 3 + r] = tfma(A.cfm, x[r], ax) - c.rhs[r];
+    }
+  }
+}
+
+template <int METHOD, bool STORE_SYSTEM>
+__device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsigned char *smem) {
+  constexpr int BLOCK = 256;
+  const int tid = (int)threadIdx.x, tile = blockIdx.x;
+  const int side = tid & 1, laneA = (tid & ~63) + ((tid & 63) >> 1), laneB = laneA + 32;
+  const bool ownA = side == 0, ownB = side == 1;
+  double *s_acc = reinterpret_cast<double *>(smem);
+  const int nslots = A.tile_nslots[tile];
+  const int32_t *slot_body = A.slot_body + A.tile_slot_off[tile];
+
+  const int P = A.tile_period[tile], depth = A.tile_depth[tile];
+  // the constraint this lane assembles and owns (A on the even lane, B on the odd one), and this lane's side of both;
+  // of the descriptors only that stays: the epilogue reads the constraint numbers again
+  const LaneDesc d = A.lanes[(size_t)tile * BLOCK + (side ? laneB : laneA)];
+  const bool active = d.cidx >= 0;
+  const bool has0 = active && d.slot0 != 0, has1 = active && d.slot1 != 0;
+  bool activeA, activeB;
+  unsigned acA, acB;
+  {
+    const LaneDesc o = A.lanes[(size_t)tile * BLOCK + (side ? laneA : laneB)];
+    const bool other = o.cidx >= 0;
+    const int mine = active ? (side ? d.slot1 : d.slot0) : 0, theirs = other ? (side ? o.slot1 : o.slot0) : 0;
+    activeA = side ? other : active;
+    activeB = side ? active : other;
+    acA = lds_addr(s_acc + (side ? theirs : mine) * 6);
+    acB = lds_addr(s_acc + (side ? mine : theirs) * 6);
+  }
+  const unsigned ac_world = lds_addr(s_acc);   // slot 0: no body on this side
+
+  Cons<double> c = {};
+  double x[3] = {0.0, 0.0, 0.0};
+  if (active) assemble_lane<STORE_SYSTEM>(A.assemble, d.cidx, c);
+  if constexpr (STORE_SYSTEM) {
+    stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
+    __syncthreads();   // every wavefront has read its staging area back
+  }
+  for (int s = tid; s < nslots; s += BLOCK) {   // a fresh solve: the accumulators start from zero
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = 0.0;
+  }
+  // D, inv and the weights from the whole constraint, as the one-lane form has them (no LINSYM rewrite: each side keeps
+  // its own linear block)
+  if (active) {
+    load_cons<double, true, false, true>(A, d.cidx, has0, has1, has0 ? slot_body[d.slot0] : 0, has1 ? slot_body[d.slot1] : 0, c);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) x[r] = c.rhs[r];
+  }
+  // the sides change hands once: the even lane gives A's side 1 for B's side 0
+  constexpr int HELD = pair_products<METHOD, STORE_SYSTEM>();
+  PairSide<HELD> SA, SB;
+#pragma unroll
+  for (int k = 0; k < 18; ++k) {
+    const double got = dpp_all<kQuadSwap>(side ? c.J0[k] : c.J1[k]);
+    SA.J[k] = side ? got : c.J0[k];
+    SB.J[k] = side ? c.J1[k] : got;
+  }
+  {
+    const double gl = dpp_all<kQuadSwap>(side ? c.wl0 : c.wl1), ga = dpp_all<kQuadSwap>(side ? c.wa0 : c.wa1);
+    SA.wl = side ? gl : c.wl0; SA.wa = side ? ga : c.wa0;
+    SB.wl = side ? c.wl1 : gl; SB.wa = side ? c.wa1 : ga;
+  }
+  SA.form();
+  SB.form();
+  int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, A.sweeps, 0));
+  __syncthreads();
+
+  // the timetable of step_solve_kernel, once per constraint of the pair (identical in both lanes); the levels are read
+  // here, behind the barrier, so that they occupy no register through the prologue
+  const int levelA = A.lane_level[(size_t)tile * BLOCK + laneA], levelB = A.lane_level[(size_t)tile * BLOCK + laneB];
+  int sweepA = 0, sweepB = 0;
+  const int t0 = METHOD == 2 ? depth : 0;
+  int dueA = (activeA && A.sweeps >= 0) ? levelA : 0x7fffffff, dueB = (activeB && A.sweeps >= 0) ? levelB : 0x7fffffff;
+  constexpr int grid_acc = METHOD == 1 ? 1 : 0;
+  int t_s = 0, t_e = 0;
+  const int Ps = __builtin_amdgcn_readfirstlane(P);
+  if (A.steady && Ps > 0) {
+    const int ds = __builtin_amdgcn_readfirstlane(depth), t0s = METHOD == 2 ? ds : 0;
+    t_s = grid_acc ? ds : t0s + ds - 1;
+    t_e = min(t0s + Ps * (A.sweeps + grid_acc), t_end);
+    if (t_e <= t_s) t_s = t_e = 0;
+  }
+  int t = 0, stop = t_e > t_s ? t_s : t_end;
+  for (;;) {
+    for (; t < stop; ++t) {
+      if (dueA == t) {
+        pair_pass<METHOD, kQuadEven, true>(SA, acA, acA != ac_world, ownA, c, x, sweepA, A.cfm);
+        dueA = (METHOD == 2 && sweepA == 0) ? t0 + (depth - 1 - levelA) : dueA + P;
+        if (++sweepA > A.sweeps) dueA = 0x7fffffff;
+      }
+      if (dueB == t) {   // after A's where both are due: they share no body then
+        pair_pass<METHOD, kQuadOdd, true>(SB, acB, acB != ac_world, ownB, c, x, sweepB, A.cfm);
+        dueB = (METHOD == 2 && sweepB == 0) ? t0 + (depth - 1 - levelB) : dueB + P;
+        if (++sweepB > A.sweeps) dueB = 0x7fffffff;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+    if (t >= t_end) break;
+    // steady: the two passes as two code copies, each behind one compare of the constraint's phase with the clock's
+    const int phaseA = activeA ? ((METHOD == 2) ? t0 + depth - 1 - levelA : levelA) % Ps : -1;
+    const int phaseB = activeB ? ((METHOD == 2) ? t0 + depth - 1 - levelB : levelB) % Ps : -1;
+    int tp = t % Ps;
+    for (; t < t_e; ++t) {
+      if (phaseA == tp) pair_pass<METHOD, kQuadEven, false>(SA, acA, acA != ac_world, ownA, c, x, 1, A.cfm);
+      if (phaseB == tp) pair_pass<METHOD, kQuadOdd, false>(SB, acB, acB != ac_world, ownB, c, x, 1, A.cfm);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      tp = tp + 1 == Ps ? 0 : tp + 1;
+    }
+    // drain: each constraint's next update at or after t_e, from its level (read again: not held through the window)
+    const int lvA = A.lane_level[(size_t)tile * BLOCK + laneA], lvB = A.lane_level[(size_t)tile * BLOCK + laneB];
+    const int bA = (METHOD == 2) ? t0 + depth - 1 - lvA : lvA, bB = (METHOD == 2) ? t0 + depth - 1 - lvB : lvB;
+    const int kA = t_e > bA ? (t_e - bA + Ps - 1) / Ps : 0, kB = t_e > bB ? (t_e - bB + Ps - 1) / Ps : 0;
+    sweepA = kA + 1 - grid_acc;
+    sweepB = kB + 1 - grid_acc;
+    dueA = (!activeA || sweepA > A.sweeps) ? 0x7fffffff : bA + P * kA;
+    dueB = (!activeB || sweepB > A.sweeps) ? 0x7fffffff : bB + P * kB;
+    stop = t_end;
+  }
+
+  const int cidx = A.lanes[(size_t)tile * BLOCK + (side ? laneB : laneA)].cidx;   // the owner's: the one that is used
+  if (activeA) pair_epilogue(A, SA, acA, ownA, cidx, c, x);
+  if (activeB) pair_epilogue(A, SB, acB, ownB, cidx, c, x);
+  for (int s = tid + 1; s < nslots; s += BLOCK) {
+    const int body = slot_body[s];
+    if (body < 0) continue;   // unused slot number
+#pragma unroll
+    for (int k = 0; k < 6; ++k) A.acc[(size_t)body * 6 + k] = s_acc[s * 6 + k];
+  }
+}
+
 // FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
 // ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
-          bool STORE_SYSTEM = true, bool FRIC = false>
+          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if constexpr (PAIR) {   // ASSEMBLE, fp64, 256-lane tiles (launch_step_solve_assemble)
+    pair_step_solve<METHOD, STORE_SYSTEM>(A, smem);
+    return;
+  }
   constexpr int WAVES = BLOCK / 64;
   const int sub = GROUP > 1 ? (int)threadIdx.x / BLOCK : 0;                 // wavefront-uniform
   const int phys = GROUP > 1 ? (int)threadIdx.x % BLOCK : (int)threadIdx.x;
@@ -455,13 +697,13 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 namespace {
-template <bool STORE_SYSTEM>
+template <bool STORE_SYSTEM, bool PAIR>
 void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
   // the accumulators; the storing form stages its blocks in the same LDS first
   size_t lds = (size_t)b.max_slots * 6 * sizeof(double);
   if (STORE_SYSTEM) lds = std::max(lds, (size_t)4 * kStageWave * sizeof(double));
-  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM>;
-  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM>;
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
@@ -469,11 +711,16 @@ void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_
 }
 }  // namespace
 
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, hipStream_t s) {
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, hipStream_t s) {
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
-  if (store_system) launch_step_solve_assemble_t<true>(b, method, n_tiles, s);
-  else launch_step_solve_assemble_t<false>(b, method, n_tiles, s);
+  if (store_system) {
+    if (pair) launch_step_solve_assemble_t<true, true>(b, method, n_tiles, s);
+    else launch_step_solve_assemble_t<true, false>(b, method, n_tiles, s);
+  } else {
+    if (pair) launch_step_solve_assemble_t<false, true>(b, method, n_tiles, s);
+    else launch_step_solve_assemble_t<false, false>(b, method, n_tiles, s);
+  }
 }
 
 template void launch_step_solve<double>(const SolveArgs<double> &, int, int, int, int, bool, hipStream_t);

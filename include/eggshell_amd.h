@@ -104,8 +104,12 @@ typedef enum {
                                       a step that does not fuse, the dense entries, and the residual -- so a step
                                       asked for statistics, or get_stats after one, pays for it too */
   EGS_SCHED_START = 1024,          /* the solve started from a given x0 (egs_problem_set_start), not from rhs */
-  EGS_SCHED_FRICTION = 2048        /* the launch ran the kernels' friction forms (egs_problem_set_friction,
+  EGS_SCHED_FRICTION = 2048,       /* the launch ran the kernels' friction forms (egs_problem_set_friction,
                                       egs_world_set_friction): tangential bounds +-mu x_n.  Clear with friction off */
+  EGS_SCHED_PAIR = 4096            /* the EGS_SCHED_FUSED_ASSEMBLY launch ran each update on a lane pair: two threads
+                                      hold one side each of two constraints (plans whose half-wavefronts each hold one
+                                      phase of the timetable, a pile of columns).  The same bits as one lane per
+                                      constraint; EGS_STEP_PAIR=0 switches it off */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -806,6 +810,12 @@ egs_status egs_debug_plan_slots(int32_t n_bodies, int32_t m, const int32_t *body
 egs_status egs_debug_plan_timetable(int32_t n_bodies, int32_t m, const int32_t *body0,
                                     const int32_t *body1, int32_t tile_size,
                                     int32_t *level, int32_t *period, int32_t *depth, int32_t *runs);
+
+/* Host only: *pairable = 1 if, in the 256-lane tile plan of the graph, every half-wavefront of lanes (32 consecutive
+ * lanes, aligned) is idle or holds constraints of one phase (level mod period) of its tile's timetable: what the fused
+ * step launch asks of a plan before it runs an update on a lane pair (EGS_SCHED_PAIR).                              */
+egs_status egs_debug_plan_pairable(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                   int32_t *pairable);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
