@@ -52,6 +52,8 @@ EXPORTS = [
     "egs_problem_set_start", "egs_match_contacts", "egs_world_set_warm_start", "egs_world_get_start",
     "egs_problem_set_friction", "egs_world_set_friction",
     "egs_update_contacts_shapes", "egs_world_set_shapes",
+    "egs_mixed_friction_solve_batch", "egs_problem_set_dense_friction", "egs_problem_dense_friction_info",
+    "egs_world_set_dense_friction", "egs_world_dense_friction_info",
 ]
 
 
@@ -89,6 +91,13 @@ def load():
             # ctx, count, n, A, b, C, lo, hi, use_bounds, max_pivots, x, w, ok, pivots
             _lib.egs_mixed_constraints_solve_batch.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] * 2 + [C.c_void_p] * 4
             _lib.egs_mixed_constraints_solve_batch.restype = C.c_int
+        if hasattr(_lib, "egs_mixed_friction_solve_batch"):
+            # ctx, count, n, A, b, C, lo, hi, normal_row, mu, max_pivots, max_outer, tol, x, w, beta, ok, pivots, outer, change
+            _lib.egs_mixed_friction_solve_batch.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] * 2 + [C.c_double]
+                                                            + [C.c_void_p] * 7)
+            _lib.egs_mixed_friction_solve_batch.restype = C.c_int
+            for name in ("egs_problem_set_dense_friction", "egs_world_set_dense_friction"):
+                getattr(_lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_double]
     return _lib
 
 
@@ -200,6 +209,27 @@ def check_mixed_batch(ns, A, b, C, lo, hi):
     if A.size != int((rows ** 2).sum()) or any(v.size != tot for v in (b, C, lo, hi)):
         raise ValueError("packed arrays do not match the sizes")
     return ns, A.reshape(-1), b.reshape(-1), C.reshape(-1), lo.reshape(-1), hi.reshape(-1)
+
+
+def check_mixed_friction_batch(ns, A, b, C, lo, hi, normal_row, mu, max_outer=32, tol=1e-10):
+    """The checks of Context.mixed_friction_solve_batch_packed that need no device: check_mixed_batch's, normal_row (integers)
+    and mu packed like the vectors, max_outer an integer >= 0 and tol >= 0 (not NaN).  Returns ns, A, b, C, lo, hi,
+    normal_row, mu as the C ABI takes them.  (What a normal_row may point at and the sign of mu are the library's to
+    refuse.)"""
+    ns, A, b, C, lo, hi = check_mixed_batch(ns, A, b, C, lo, hi)
+    if normal_row is None or mu is None:
+        raise ValueError("normal_row and mu are required")
+    nr = np.asarray(normal_row)
+    if nr.size and not np.issubdtype(nr.dtype, np.integer):
+        raise ValueError("normal_row: integer row indices (-1: a plain row)")
+    nr, mu = _i32(nr).reshape(-1), _f64(mu).reshape(-1)
+    if nr.size != b.size or mu.size != b.size:
+        raise ValueError("packed arrays do not match the sizes")
+    if int(max_outer) != max_outer or max_outer < 0:
+        raise ValueError("max_outer: an integer >= 0 (0: the default, 32)")
+    if not tol >= 0:
+        raise ValueError("tol must be >= 0")
+    return ns, A, b, C, lo, hi, nr, mu
 
 
 def params(method=GAUSS_SEIDEL, max_iters=500, tol=1e-9, cfm=0.0, omega=1.5, check_every=1):
@@ -373,6 +403,19 @@ class Context:
         ok, x, w, piv = self.mixed_constraints_solve_batch_packed(ns, A, b, Cp, lo, hi, use_bounds, max_pivots)
         xl, wl = unpack_lcp_batch(ns, None, x, w)
         return [bool(v) for v in ok], xl, wl, [int(v) for v in piv]
+
+    def mixed_friction_solve_batch_packed(self, ns, A, b, C, lo, hi, normal_row, mu, max_pivots=0, max_outer=32, tol=1e-10):
+        """egs_mixed_friction_solve_batch on packed arrays: a dict of ok [count] (bool), x, w, beta (packed), pivots, outer
+        [count], change [count] and converged = change <= tol.  A failed problem shows in ok[k], not as an exception."""
+        ns, A, b, c8, lo, hi, nr, mu = check_mixed_friction_batch(ns, A, b, C, lo, hi, normal_row, mu, max_outer, tol)
+        cnt = len(ns)
+        tot = int(np.maximum(ns, 0).sum())
+        x = np.zeros(tot); w = np.zeros(tot); beta = np.zeros(tot)
+        ok = np.zeros(cnt, np.int32); piv = np.zeros(cnt, np.int32); outer = np.zeros(cnt, np.int32); change = np.zeros(cnt)
+        self.check(load().egs_mixed_friction_solve_batch(self.h, cnt, _p(ns), _p(A), _p(b), _p(c8), _p(lo), _p(hi), _p(nr), _p(mu),
+                                                         int(max_pivots), int(max_outer), float(tol), _p(x), _p(w), _p(beta), _p(ok),
+                                                         _p(piv), _p(outer), _p(change)))
+        return dict(ok=ok.astype(bool), x=x, w=w, beta=beta, pivots=piv, outer=outer, change=change, converged=change <= tol)
 
     def dense_iterate(self, A, b, prm, Ceq=None, lo=None, hi=None):
         """sparse::{Jacobi,GaussSeidel,SOR}Iteration(A, b[, C, x_lo, x_hi]) on an explicit matrix: x, stats."""
@@ -644,6 +687,16 @@ class Problem:
         self.ctx.check(load().egs_problem_dense_condition(self.h, C.c_double(cfm), C.byref(est)))
         return est.value
 
+    def set_dense_friction(self, max_outer=32, tol=1e-10):
+        """egs_problem_set_dense_friction: max_outer > 0 lets step_dense solve the friction pyramid (0: it refuses)."""
+        self.ctx.check(load().egs_problem_set_dense_friction(self.h, int(max_outer), float(tol)))
+
+    def dense_friction_info(self):
+        """(outer, converged, change) of the last step_dense that solved the pyramid."""
+        outer, conv, change = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        self.ctx.check(load().egs_problem_dense_friction_info(self.h, C.byref(outer), C.byref(conv), C.byref(change)))
+        return outer.value, bool(conv.value), change.value
+
     def step_dense(self, dt, erp=0.2, cfm=0.0, use_bounds=0):
         """StepVelocities_ODE through the dense path: returns (ok, pivots)."""
         ok = C.c_int32(0); piv = C.c_int32(0)
@@ -863,6 +916,17 @@ class World:
         if st not in (OK, ERR_LCP_FAILED):
             self.ctx.check(st)
         return nf.value
+
+    def set_dense_friction(self, max_outer=32, tol=1e-10):
+        """egs_world_set_dense_friction: max_outer > 0 lets the dense steps solve the friction pyramid (0: they refuse)."""
+        self.ctx.check(load().egs_world_set_dense_friction(self.h, int(max_outer), float(tol)))
+
+    def dense_friction_info(self):
+        """Per-ensemble outcomes of the pyramid in the last dense step: outer, converged (bool), change [E]."""
+        E = self.n_ensembles
+        outer = np.zeros(E, np.int32); conv = np.zeros(E, np.int32); change = np.zeros(E)
+        self.ctx.check(load().egs_world_dense_friction_info(self.h, C.c_int32(E), _p(outer), _p(conv), _p(change)))
+        return outer, conv.astype(bool), change
 
     def dense_info(self):
         """Per-ensemble figures of the last step_dense: condition estimate, cfm added, pivots, ok [E]."""

@@ -157,7 +157,9 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
   if (!p) return EGS_ERR_INVALID;
   if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
-  if (p->friction) return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
+  if (p->friction && p->dense_fric_outer == 0)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
+  if (p->friction && use_bounds != 1) return fail(p->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
   if (ok) *ok = 0;
   return guarded(p->ctx, [&]() -> egs_status {
     egs_context *ctx = p->ctx;
@@ -184,10 +186,44 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
     const std::vector<double> &lo = p->h_rows_lo, &hi = p->h_rows_hi;
     int piv = 0;
     std::string msg;
-    // Lcp::MixedConstraintsSolver (ensembles.cc:531) on the device matrix; lambda lands in the problem's x
-    const bool good = dense_mixed_constraints_device(ctx->dense, (int)rows, p->dense_A.p, real<double>(p->rhs), C.data(),
-                                                     lo.data(), hi.data(), (use_bounds & 1) != 0, (use_bounds & 2) != 0, 0, 0.0,
-                                                     nullptr, nullptr, real<double>(p->x), &piv, &msg);
+    bool good;
+    p->dense_fric_valid = false;
+    if (p->friction) {
+      // the pyramid: the fixed-point iteration from the host on the matrix and right-hand side read back; rows 0 and 1
+      // of a constraint with mu >= 0 are pyramid rows of its row 2 (egs_problem_set_friction's meaning)
+      std::vector<double> hA(rows * rows), hb(rows), hmu((size_t)p->m), mu_row(rows), hx(rows), hw(rows);
+      std::vector<int32_t> nrow(rows, -1);
+      HIPCHK(hipMemcpyAsync(hA.data(), p->dense_A.p, rows * rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hb.data(), real<double>(p->rhs), rows * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hmu.data(), real<double>(p->mu), (size_t)p->m * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (size_t i = 1; i < rows; ++i)                     // the factorisations read the lower triangle: one matrix
+        for (size_t j = 0; j < i; ++j) hA[j * rows + i] = hA[i * rows + j];
+      for (size_t k = 0; k < rows; ++k) {
+        mu_row[k] = hmu[k / 3];
+        if (k % 3 < 2 && mu_row[k] >= 0.0) {
+          nrow[k] = (int32_t)(k - k % 3 + 2);
+          if (C[k - k % 3 + 2]) return fail(ctx, EGS_ERR_INVALID, "dense friction: the normal row of a pyramid constraint is an equality row");
+        }
+      }
+      int out = 0;
+      double change = 0.0;
+      good = mixed_friction_host(ctx->dense, (int)rows, hA.data(), hb.data(), C.data(), lo.data(), hi.data(), nrow.data(), mu_row.data(), 0,
+                                 p->dense_fric_outer, p->dense_fric_tol, hx.data(), hw.data(), nullptr, &piv, &out, &change, &msg);
+      p->dense_fric_valid = true;
+      p->dense_fric_solves = out;
+      p->dense_fric_change = change;
+      p->dense_fric_converged = (good && change <= p->dense_fric_tol) ? 1 : 0;
+      if (good) {
+        HIPCHK(hipMemcpyAsync(real<double>(p->x), hx.data(), rows * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                    // hx is this scope's
+      }
+    } else {
+      // Lcp::MixedConstraintsSolver (ensembles.cc:531) on the device matrix; lambda lands in the problem's x
+      good = dense_mixed_constraints_device(ctx->dense, (int)rows, p->dense_A.p, real<double>(p->rhs), C.data(), lo.data(), hi.data(),
+                                            (use_bounds & 1) != 0, (use_bounds & 2) != 0, 0, 0.0, nullptr, nullptr, real<double>(p->x),
+                                            &piv, &msg);
+    }
     if (pivots) *pivots = piv;
     if (!good) return fail(ctx, EGS_ERR_LCP_FAILED, msg.empty() ? "MixedConstraintsSolver did not reach a solution" : msg);
     if (ok) *ok = 1;
@@ -197,6 +233,24 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
     do_velocity(p, dt);                                       // ensembles.cc:535, 572
     return EGS_OK;
   });
+}
+
+egs_status egs_problem_set_dense_friction(egs_problem *p, int32_t max_outer, double tol) {
+  if (!p) return EGS_ERR_INVALID;
+  if (max_outer < 0) return fail(p->ctx, EGS_ERR_INVALID, "max_outer must be >= 0 (0: egs_problem_step_dense refuses friction)");
+  if (!(tol >= 0)) return fail(p->ctx, EGS_ERR_INVALID, "tol must be >= 0");
+  p->dense_fric_outer = max_outer;
+  p->dense_fric_tol = tol;
+  return EGS_OK;
+}
+
+egs_status egs_problem_dense_friction_info(egs_problem *p, int32_t *outer, int32_t *converged, double *change) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!p->dense_fric_valid) return fail(p->ctx, EGS_ERR_INVALID, "no egs_problem_step_dense with the friction pyramid yet");
+  if (outer) *outer = p->dense_fric_solves;
+  if (converged) *converged = p->dense_fric_converged;
+  if (change) *change = p->dense_fric_change;
+  return EGS_OK;
 }
 
 egs_status egs_mixed_constraints_solve(egs_context *ctx, int32_t N, const double *A, const double *b,
@@ -282,6 +336,90 @@ egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, co
                                                 0.0);
       ok[k] = good ? 1 : 0;
       if (pivots) pivots[k] = piv;
+    }
+    return EGS_OK;     // per-problem outcome in ok[]
+  });
+}
+
+egs_status egs_mixed_friction_solve_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A, const double *b,
+                                          const uint8_t *C, const double *lo, const double *hi, const int32_t *normal_row,
+                                          const double *mu, int32_t max_pivots, int32_t max_outer, double tol, double *x, double *w,
+                                          double *beta, int32_t *ok, int32_t *pivots, int32_t *outer, double *change) {
+  if (!ctx) return EGS_ERR_INVALID;
+  // everything is checked before anything is launched or written
+  if (count < 0) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: count < 0");
+  if (max_pivots < 0) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: max_pivots < 0");
+  if (max_outer < 0) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: max_outer < 0");
+  if (!(tol >= 0)) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: tol must be >= 0");
+  if (count == 0) return EGS_OK;
+  if (!n || !ok || !outer || !change) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  std::vector<int64_t> a_off(count), v_off(count);
+  std::vector<int32_t> fused, single;
+  int64_t at = 0, vt = 0;
+  for (int k = 0; k < count; ++k) {
+    const int nk = n[k];
+    if (nk < 0) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: n < 0, problem " + std::to_string(k));
+    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: n too large, problem " + std::to_string(k));
+    a_off[k] = at; v_off[k] = vt;
+    if (nk > 0) (nk <= kFusedDenseMax ? fused : single).push_back(k);
+    at += (int64_t)nk * nk; vt += nk;
+  }
+  if (vt > 0 && (!A || !b || !C || !lo || !hi || !normal_row || !mu || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  for (int k = 0; k < count; ++k) {
+    const int nk = n[k];
+    const int32_t *nr = normal_row + v_off[k];
+    const uint8_t *Ck = C + v_off[k];
+    for (int i = 0; i < nk; ++i) {
+      const int f = nr[i];
+      if (f == -1) continue;
+      if (f < -1 || f >= nk)
+        return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: normal_row out of range, problem " + std::to_string(k));
+      if (Ck[f] || nr[f] != -1)
+        return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: a normal row must be a plain inequality row, problem " + std::to_string(k));
+      if (!(mu[v_off[k] + i] >= 0))
+        return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: mu must be >= 0 on a pyramid row, problem " + std::to_string(k));
+    }
+    const double *Ak = A + a_off[k];     // the rule of the single entry's symmetry check (dense_lcp.hip)
+    double amax = 0.0, asym = 0.0;
+    for (int i = 1; i < nk; ++i)
+      for (int j = 0; j < i; ++j) {
+        const double v = Ak[(size_t)i * nk + j];
+        amax = std::fmax(amax, std::fabs(v));
+        asym = std::fmax(asym, std::fabs(v - Ak[(size_t)j * nk + i]));
+      }
+    if (asym > 1e-10 * std::max(amax, 1e-300))
+      return fail(ctx, EGS_ERR_INVALID, "A must be symmetric (J M^-1 J^T + cfm I is): problem " + std::to_string(k));
+  }
+  if (max_outer == 0) max_outer = 32;
+  for (int k = 0; k < count; ++k) {
+    ok[k] = n[k] == 0 ? 1 : 0;
+    if (pivots) pivots[k] = 0;
+    outer[k] = n[k] == 0 ? 1 : 0;
+    change[k] = 0.0;
+  }
+  return guarded(ctx, [&]() -> egs_status {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!fused.empty()) {
+      LaunchHooks hooks;
+      hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
+      hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
+      hooks.self = ctx;
+      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
+      ctx->pinned.reset();
+      const MixedFrictionBatch fr{normal_row, mu, max_outer, tol, beta, outer, change};
+      mixed_constraints_fused(ctx->dense, hooks, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo, hi,
+                              true, max_pivots, x, w, ok, pivots, &fr);
+    }
+    // beyond the fused size: the same iteration from the host, one problem after another
+    for (const int k : single) {
+      int piv = 0, out = 0;
+      const int64_t v = v_off[k];
+      const bool good = mixed_friction_host(ctx->dense, n[k], A + a_off[k], b + v, C + v, lo + v, hi + v, normal_row + v, mu + v,
+                                            max_pivots, max_outer, tol, x + v, w + v, beta ? beta + v : nullptr, &piv, &out, &change[k],
+                                            nullptr);
+      ok[k] = good ? 1 : 0;
+      if (pivots) pivots[k] = piv;
+      outer[k] = out;
     }
     return EGS_OK;     // per-problem outcome in ok[]
   });

@@ -96,10 +96,32 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
 // allocation, one upload, at most one launch per size class (32 / 64 / 112 rows), one read-back, one synchronisation.
 // use_bounds = false is the reference (quirk Q3); max_pivots > 0 tightens its cap min(1000, 2^n_i).  ok[k] = the
 // reference's bool, x / w of a failed problem are zero.  The matrices must already have passed the symmetry check.
+// fr != NULL: the pyramid form (egs_mixed_friction_solve_batch; mixed_solve_device.h).  normal_row / mu: packed like the
+// vectors, already validated (a normal row is a plain inequality row of the same problem, mu >= 0 on pyramid rows);
+// max_outer >= 1; beta (packed, may be NULL), outer / change (indexed like ok) receive each problem's outcome.  Solve
+// k + 1 starts its Murty set from solve k's final set.
+struct MixedFrictionBatch {
+  const int32_t *normal_row;
+  const double *mu;
+  int max_outer;
+  double tol;
+  double *beta;
+  int32_t *outer;
+  double *change;
+};
 void mixed_constraints_fused(DenseWorkspace &ws, const LaunchHooks &hooks, int count, const int32_t *sel, const int32_t *n,
                              const int64_t *a_off, const int64_t *v_off, const double *A, const double *b, const uint8_t *C,
                              const double *lo, const double *hi, bool use_bounds, int max_pivots, double *x, double *w, int32_t *ok,
-                             int32_t *pivots);
+                             int32_t *pivots, const MixedFrictionBatch *fr = nullptr);
+
+// One pyramid problem of any size by the same fixed-point iteration on the host (the route beyond kFusedDenseMax rows):
+// every outer solve is dense_mixed_constraints(use_bounds) on the problem WITHOUT its pinned rows, the pyramid rows as
+// inequality rows with bounds [-beta, +beta]; beta follows the read-back x.  Each solve starts its Murty set from
+// scratch.  A, b, C, lo, hi, normal_row, mu: host, validated as above.  x, w [N] out (w = A x - b on the pinned rows),
+// beta [N] (may be NULL), *pivots summed over the solves, *outer, *change.  Returns the inner solver's bool.
+bool mixed_friction_host(DenseWorkspace &ws, int N, const double *A, const double *b, const uint8_t *C, const double *lo,
+                         const double *hi, const int32_t *normal_row, const double *mu, int max_pivots, int max_outer, double tol,
+                         double *x, double *w, double *beta, int *pivots, int *outer, double *change, std::string *msg);
 
 // sparse::{Jacobi,GaussSeidel,SOR}Iteration on an explicit dense matrix (sparse_iterations.cc:72-144; dense_iter.hip):
 // A row-major n x n (n <= 1024), C / lo / hi as the reference's 5-argument overloads (all-equality for the 2-argument

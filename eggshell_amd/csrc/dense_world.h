@@ -22,6 +22,13 @@ struct DenseEnsStatus {
   int32_t pivots;     // principal pivots of the Murty loop
 };
 
+// What the pyramid form's fixed-point iteration leaves per ensemble (egs_world_dense_friction_info).
+struct DenseFrictionStatus {
+  double change;      // the last delta
+  int32_t outer;      // solves made
+  int32_t converged;  // change <= tol
+};
+
 // Per-ensemble workspace of an ensemble of N rows, in doubles from its offset:
 //   A [N][N] | Z [N][N] + N (A^-1, then L^-1 [A_ei | b_e]) | lhs [N][N] | b, lo, hi, C (0 / 1), x [N] each.
 inline size_t dense_ws_size(size_t N) { return 3 * N * N + 6 * N; }
@@ -42,11 +49,23 @@ struct DenseWorldArgs {
   int32_t use_bounds;
 };
 
+// The pyramid form's own arguments (egs_world_set_dense_friction): the world problem's per-constraint coefficients as
+// world_fill_friction leaves them (fp64; < 0: the constraint's rows stay as stored).
+struct DenseWorldFriction {
+  const double *mu;
+  DenseFrictionStatus *status;                  // [E]
+  double tol;
+  int32_t max_outer, pad;
+};
+
 // A_e = J M^-1 J^T of every ensemble (the operation order of dense_system_kernel, without the cfm) and its rows
 // gathered into the ensemble's workspace.  Grid: a workgroup row per ensemble, max_m^2 constraint pairs wide.
 void launch_dense_world_system(const DenseWorldArgs &a, int n_ens, int max_m, hipStream_t s);
 // The fused ComputeVDot of the `count` ensembles list[0 .. count) of size class cls (kDenseClassRows[cls]).
 void launch_dense_world_fused(const DenseWorldArgs &a, const int32_t *list, int count, int cls, hipStream_t s);
+// The same with the Coulomb pyramid solved by the stage's fixed-point iteration (mixed_solve_device.h); use_bounds is 1.
+void launch_dense_world_friction(const DenseWorldArgs &a, const DenseWorldFriction &fa, const int32_t *list, int count, int cls,
+                                 hipStream_t s);
 // A[i][i] += cfm, i < N
 void launch_dense_world_add_diag(double *A, int N, double cfm, hipStream_t s);
 // x[3 cons_e[i] + r] = xs[3 i + r]

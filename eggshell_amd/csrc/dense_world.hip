@@ -3,6 +3,8 @@
 // without the host: CheckMatrixCondition against kGoodConditionNumber = 1e7 (ensembles.cc:513-521), the Schur
 // complement over the equality rows (lcp.cc:286-294), the reference's Murty loop on the inequality rows
 // (lcp.cc:157-274, as murty_small_kernel in dense_lcp.hip) and x_e = A_ee^-1 (b_e - A_ei x_i) (lcp.cc:317).
+// dense_world_friction_kernel is the same body around the stage's pyramid form (egs_world_set_dense_friction): rows 0
+// and 1 of a constraint with mu >= 0 are pyramid rows of its row 2, mu read per gathered constraint.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -76,14 +78,13 @@ __global__ void __launch_bounds__(256) dense_world_system_kernel(DenseWorldArgs 
 // complement live in the ensemble's workspace (global memory, cache-resident at these sizes); the Cholesky factors
 // (packed lower triangle) and every vector live in LDS.  Every decision is the workgroup's alone, so an ensemble
 // gets the same bits whatever else the world holds.
-template <int MAXN, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs a, const int32_t *list) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
+struct NoWorldFriction {};
+
+template <int MAXN, int BLOCK, bool PYR, typename Friction>
+__device__ __forceinline__ void dense_world_body(double *sm, MixedSolveShared<MAXN> &sh, double (&s_diag)[2], double (&s_red)[BLOCK / 64][6],
+                                                 const DenseWorldArgs &a, const int32_t *list, const Friction &fa) {
   const MixedSolveLds L(sm, MAXN);                  // the packed triangle (Cholesky factors of A, A_ee, A(S,S)) and the vectors
   double *T = L.T, *x = L.x, *w = L.w, *r = L.r, *y = L.y, *y2 = L.y2;
-  __shared__ MixedSolveShared<MAXN> sh;
-  __shared__ double s_diag[2];
-  __shared__ double s_red[BLOCK / 64][6];
   const int tid = threadIdx.x;
   const int e = list[blockIdx.x];
   const int c0 = a.cstart[e];
@@ -92,6 +93,10 @@ __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs
   double *Z = A + (size_t)N * N;
   double *Lh = Z + (size_t)N * N + N;
   const double *vb = A + dense_ws_vec(N), *vlo = vb + N, *vhi = vb + 2 * N, *vc = vb + 3 * N;
+  if constexpr (PYR) {      // mu per row, in the workspace's x vector (free on the fused path); read after the barriers below
+    double *vmu = A + dense_ws_vec(N) + 4 * (size_t)N;
+    for (int i = tid; i < N; i += BLOCK) vmu[i] = fa.mu[a.cons[c0 + i / 3]];
+  }
 
   // K partial sums per thread -> the workgroup's sums, the same bits in every thread
   auto block_sum = [&](double *v, int K) {
@@ -187,8 +192,18 @@ __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs
   __syncthreads();   // (every thread has read sh.fail and A before they change)
 
   // ---- Lcp::MixedConstraintsSolver (lcp.cc:276-336): the stage mixed_batch_kernel shares (mixed_solve_device.h)
-  mixed_partition(sh, N, [&](int i) { return vc[i] != 0.0; });
-  const MixedSolveResult res = mixed_solve_stage<MAXN, BLOCK>(sh, L, A, N, vb, vlo, vhi, Z, Lh, a.use_bounds, 0);
+  MixedPyramid<PYR> pyr;
+  if constexpr (PYR) {
+    const double *vmu = vb + 4 * (size_t)N;
+    pyr.nrow = nullptr; pyr.mu = vmu;
+    pyr.max_outer = fa.max_outer; pyr.tol = fa.tol;
+    pyr.ext = sm + mixed_solve_lds_doubles(MAXN);
+    pyr.outer = 0; pyr.change = 0.0;
+    mixed_partition(sh, N, [&](int i) { return vc[i] != 0.0 && pyr.normal_of(i) < 0; });     // a pyramid row is an inequality row
+  } else {
+    mixed_partition(sh, N, [&](int i) { return vc[i] != 0.0; });
+  }
+  const MixedSolveResult res = mixed_solve_stage<MAXN, BLOCK, PYR>(sh, L, A, N, vb, vlo, vhi, Z, Lh, a.use_bounds, 0, pyr);
   const int ne = sh.ne, ni = sh.ni, solved = res.solved, pivots = res.pivots;
   const int *idxE = sh.idxE, *idxI = sh.idxI;
   if (solved) {     // lambda in the world's order
@@ -205,7 +220,32 @@ __global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs
     DenseEnsStatus st;
     st.condition = condition; st.cfm = cfm; st.ok = solved; st.pivots = pivots;
     a.status[e] = st;
+    if constexpr (PYR) {
+      DenseFrictionStatus fs;
+      fs.change = solved ? pyr.change : 0.0;
+      fs.outer = (solved && pyr.outer == 0) ? 1 : pyr.outer;
+      fs.converged = (solved && fs.change <= fa.tol) ? 1 : 0;
+      fa.status[e] = fs;
+    }
   }
+}
+
+template <int MAXN, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) dense_world_fused_kernel(DenseWorldArgs a, const int32_t *list) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ MixedSolveShared<MAXN> sh;
+  __shared__ double s_diag[2];
+  __shared__ double s_red[BLOCK / 64][6];
+  dense_world_body<MAXN, BLOCK, false>(sm, sh, s_diag, s_red, a, list, NoWorldFriction{});
+}
+
+template <int MAXN, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) dense_world_friction_kernel(DenseWorldArgs a, const int32_t *list, DenseWorldFriction fa) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ MixedSolveShared<MAXN> sh;
+  __shared__ double s_diag[2];
+  __shared__ double s_red[BLOCK / 64][6];
+  dense_world_body<MAXN, BLOCK, true>(sm, sh, s_diag, s_red, a, list, fa);
 }
 
 __global__ void add_diag_kernel(double *A, int N, double cfm) {
@@ -224,6 +264,12 @@ void launch_fused(const DenseWorldArgs &a, const int32_t *list, int count, hipSt
   hipLaunchKernelGGL((dense_world_fused_kernel<MAXN, BLOCK>), dim3(count), dim3(BLOCK), lds, s, a, list);
 }
 
+template <int MAXN, int BLOCK>
+void launch_friction(const DenseWorldArgs &a, const DenseWorldFriction &fa, const int32_t *list, int count, hipStream_t s) {
+  const size_t lds = mixed_pyramid_lds_doubles(MAXN) * sizeof(double);
+  hipLaunchKernelGGL((dense_world_friction_kernel<MAXN, BLOCK>), dim3(count), dim3(BLOCK), lds, s, a, list, fa);
+}
+
 }  // namespace
 
 void launch_dense_world_system(const DenseWorldArgs &a, int n_ens, int max_m, hipStream_t s) {
@@ -237,6 +283,14 @@ void launch_dense_world_fused(const DenseWorldArgs &a, const int32_t *list, int 
   if (cls == 0) launch_fused<32, 64>(a, list, count, s);
   else if (cls == 1) launch_fused<64, 64>(a, list, count, s);
   else launch_fused<112, 256>(a, list, count, s);
+}
+
+void launch_dense_world_friction(const DenseWorldArgs &a, const DenseWorldFriction &fa, const int32_t *list, int count, int cls,
+                                 hipStream_t s) {
+  if (count <= 0) return;
+  if (cls == 0) launch_friction<32, 64>(a, fa, list, count, s);
+  else if (cls == 1) launch_friction<64, 64>(a, fa, list, count, s);
+  else launch_friction<112, 256>(a, fa, list, count, s);
 }
 
 void launch_dense_world_add_diag(double *A, int N, double cfm, hipStream_t s) {

@@ -4,6 +4,14 @@
 // forward substitution, the Schur complement, the reference's Murty loop (lcp.cc:157-274, as murty_small_kernel in
 // dense_lcp.hip) and x_e = A_ee^-1 (b_e - A_ei x_i).  Every fused operation is an explicit fma: both kernels compute
 // the same bits from the same rows.
+//
+// The PYRAMID form (template flag PYR; egs_mixed_friction_solve_batch) wraps the Murty loop in the
+// Tresca fixed-point iteration on the bounds of the Coulomb pyramid's tangential rows: the partition and the Schur
+// complement run once (neither depends on the bounds), every outer solve is the box LCP with the pyramid rows bounded
+// by [-beta, +beta] (beta = 0: the row is PINNED, x = 0 and no condition on w), beta follows the normal rows' x after
+// each solve, and x_e is back-substituted once after the last.  Solve k + 1 starts its Murty set from solve k's final
+// set (rows at a bound move with it, a row released from the pin starts free).  The form with the flag off is the code
+// it was before the flag existed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,17 +108,47 @@ __device__ __forceinline__ void mixed_partition(MixedSolveShared<MAXN> &sh, int 
 
 struct MixedSolveResult {
   int solved;     // the reference's bool
-  int pivots;     // principal pivots of the Murty loop
+  int pivots;     // principal pivots of the Murty loop (the pyramid form: summed over its solves)
 };
+
+// What the pyramid form takes and reports beside the plain one; the plain form's is empty.
+//   nrow[i] (row i of the problem) = the row whose x bounds row i (a plain inequality row), or -1: a plain row;
+//   mu[i] >= 0 its coefficient; max_outer >= 1 solves at most; tol the stopping change.
+//   nrow == NULL: the rows come in triples (t, t, n) as a world's constraints do, and mu[i] >= 0 on rows 3c and 3c + 1
+//   makes them pyramid rows of row 3c + 2 (normal_of below; mu[i] < 0: plain rows).
+//   ext: one more LDS vector of MAXN doubles, behind mixed_solve_lds_doubles(MAXN) -- the normal row of every
+//   inequality row as its index among the inequality rows (MAXN ints), then the two words of the change reduction.
+//   On return: outer = solves made, change = the last delta; the bound of inequality row k stands in L.hi[k].
+template <bool PYR>
+struct MixedPyramid {};
+template <>
+struct MixedPyramid<true> {
+  const int32_t *nrow;
+  const double *mu;
+  int max_outer;
+  double tol;
+  double *ext;
+  int outer;
+  double change;
+  __device__ __forceinline__ int normal_of(int row) const {
+    if (nrow) return nrow[row];
+    const int r = row % 3;
+    return (r < 2 && mu[row] >= 0.0) ? row - r + 2 : -1;
+  }
+};
+constexpr size_t mixed_pyramid_lds_doubles(int maxn) { return mixed_solve_lds_doubles(maxn) + (size_t)maxn; }
 
 // The solve on the partition mixed_partition left in sh.  A: N x N row-major, symmetric; vb, vlo, vhi: the rows'
 // right-hand side and bounds (the bounds are read only with use_bounds).  Z (sh.ne x (sh.ni + 1) doubles) and Lh (sh.ni^2
 // doubles) are the caller's workspace, LDS or global.  max_pivots > 0 tightens the reference's cap min(1000, 2^ni).
 // On return, when solved: L.x[k] and L.w[k] belong to row sh.idxI[k], L.y2[k] to row sh.idxE[k] (whose w is 0).
-template <int MAXN, int BLOCK>
+// PYR: the pyramid form, with pyr as described above (the partition must then list every pyramid row as an inequality
+// row, and the dynamic LDS holds mixed_pyramid_lds_doubles(MAXN) doubles); without it pyr is empty and the code is the
+// plain solve.
+template <int MAXN, int BLOCK, bool PYR>
 __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<MAXN> &sh, const MixedSolveLds &L, const double *A, int N,
                                                                const double *vb, const double *vlo, const double *vhi, double *Z,
-                                                               double *Lh, int use_bounds, int max_pivots) {
+                                                               double *Lh, int use_bounds, int max_pivots, MixedPyramid<PYR> &pyr) {
   const int tid = threadIdx.x;
   const int NONE = 0x7fffffff;
   double *T = L.T, *x = L.x, *w = L.w, *r = L.r, *Cv = L.Cv, *lo = L.lo, *hi = L.hi, *b = L.b, *y = L.y, *bx = L.bx, *bw = L.bw,
@@ -155,7 +193,24 @@ __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<M
   }
   // the inequality rows' bounds: the reference calls the no-bounds overload (lcp.cc:298, quirk Q3)
   const bool box_fix = use_bounds != 0;
+  int *nloc = nullptr;                      // pyramid form: the normal row of inequality row k, among the inequality rows
+  unsigned long long *red = nullptr;        // and the two words of the change reduction
+  if constexpr (PYR) {
+    nloc = reinterpret_cast<int *>(pyr.ext);
+    red = reinterpret_cast<unsigned long long *>(nloc + MAXN);
+    for (int k = tid; k < ni; k += BLOCK) {
+      const int f = pyr.normal_of(idxI[k]);
+      int at = -1;
+      if (f >= 0)
+        for (int j = 0; j < ni; ++j) if (idxI[j] == f) at = j;
+      nloc[k] = at;
+    }
+    __syncthreads();
+  }
   for (int k = tid; k < ni; k += BLOCK) {
+    if constexpr (PYR) {
+      if (nloc[k] >= 0) { lo[k] = 0.0; hi[k] = 0.0; continue; }   // beta^0 = 0: pinned, outside the lo < hi rule
+    }
     lo[k] = box_fix ? vlo[idxI[k]] : 0.0;
     hi[k] = box_fix ? vhi[idxI[k]] : INFINITY;
     if (!(lo[k] < hi[k]) || !(lo[k] <= 0) || !(box_fix ? hi[k] >= 0 : hi[k] > 0)) sh.badb = 1;   // lcp.cc:161-164
@@ -174,6 +229,9 @@ __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<M
     if (max_pivots > 0 && max_pivots < max_iterations) max_iterations = max_pivots;   // the caller's own cap
     for (int i = tid; i < n; i += BLOCK) {
       S[i] = 1; Cv[i] = lo[i];
+      if constexpr (PYR) {
+        if (nloc[i] >= 0) S[i] = 0;             // a pinned row is clamped to 0 and never enters the set
+      }
       x[i] = 0.0; w[i] = -b[i]; r[i] = -b[i];   // lcp.cc:184-185
       bx[i] = 0.0; bw[i] = -b[i];
     }
@@ -183,6 +241,9 @@ __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<M
       __syncthreads();
       for (int i = tid; i < n; i += BLOCK) {
         const double xi = x[i], wi = w[i];
+        if constexpr (PYR) {
+          if (nloc[i] >= 0 && hi[i] == 0.0) continue;      // pinned: x = 0, its w carries no condition
+        }
         bool off;
         if (S[i]) off = (xi < lo[i]) || (xi > hi[i]);
         else off = (Cv[i] == lo[i] && wi < 0) || (Cv[i] == hi[i] && wi > 0);
@@ -230,68 +291,109 @@ __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<M
     check();
     if (tid == 0) sh.best = sh.good;
     __syncthreads();
-    int iter = 0;
-    bool force = box_fix;
-    while (iter < max_iterations) {
-      if (!force) {
-        if (is_solution(1e-9)) { if (tid == 0) sh.state = 1; __syncthreads(); break; }
-        if (tid == 0 && sh.first != NONE) {             // lcp.cc:36-62: flip the first offender
-          const int i = sh.first;
-          if (S[i]) { S[i] = 0; Cv[i] = (x[i] < lo[i]) ? lo[i] : hi[i]; }
-          else S[i] = 1;
+    int outer = 1;
+    bool again;
+    do {   // one pass; the pyramid form: the solves of the fixed-point iteration
+      again = false;
+      int iter = 0;
+      bool force = PYR ? (box_fix || outer > 1) : box_fix;
+      while (iter < max_iterations) {
+        if (!force) {
+          if (is_solution(1e-9)) { if (tid == 0) sh.state = 1; __syncthreads(); break; }
+          if (tid == 0 && sh.first != NONE) {             // lcp.cc:36-62: flip the first offender
+            const int i = sh.first;
+            if (S[i]) { S[i] = 0; Cv[i] = (x[i] < lo[i]) ? lo[i] : hi[i]; }
+            else S[i] = 1;
+          }
+          __syncthreads();
+        }
+        force = false;
+        if (tid == 0) {                                  // index list of S
+          int ns = 0;
+          for (int i = 0; i < n; ++i) if (S[i]) idx[ns++] = i;
+          sh.ns = ns;
+        }
+        for (int i = tid; i < n; i += BLOCK) x[i] = S[i] ? 0.0 : Cv[i];   // x = x_clamped
+        __syncthreads();
+        const int ns = sh.ns;
+        // right-hand side: b(S), minus M(S,!S) x(!S) for the true box problem (lcp.cc:199-216)
+        if (box_fix) {
+          residual_vector();                              // r = M x_clamped - b
+          for (int k = tid; k < ns; k += BLOCK) y[k] = -r[idx[k]];
+        } else {
+          for (int k = tid; k < ns; k += BLOCK) y[k] = b[idx[k]];
+        }
+        for (int q = tid; q < ns * ns; q += BLOCK) {      // gather M(S,S), lower triangle
+          const int rr = q / ns, cc = q - rr * ns;
+          if (cc <= rr) T[dtri(rr, cc)] = M[(size_t)idx[rr] * n + idx[cc]];
         }
         __syncthreads();
-      }
-      force = false;
-      if (tid == 0) {                                  // index list of S
-        int ns = 0;
-        for (int i = 0; i < n; ++i) if (S[i]) idx[ns++] = i;
-        sh.ns = ns;
-      }
-      for (int i = tid; i < n; i += BLOCK) x[i] = S[i] ? 0.0 : Cv[i];   // x = x_clamped
-      __syncthreads();
-      const int ns = sh.ns;
-      // right-hand side: b(S), minus M(S,!S) x(!S) for the true box problem (lcp.cc:199-216)
-      if (box_fix) {
-        residual_vector();                              // r = M x_clamped - b
-        for (int k = tid; k < ns; k += BLOCK) y[k] = -r[idx[k]];
-      } else {
-        for (int k = tid; k < ns; k += BLOCK) y[k] = b[idx[k]];
-      }
-      for (int q = tid; q < ns * ns; q += BLOCK) {      // gather M(S,S), lower triangle
-        const int rr = q / ns, cc = q - rr * ns;
-        if (cc <= rr) T[dtri(rr, cc)] = M[(size_t)idx[rr] * n + idx[cc]];
-      }
-      __syncthreads();
-      packed_cholesky<BLOCK>(T, ns, y, &sh.fail);
-      packed_back_solve(T, ns, y);
-      for (int k = tid; k < ns; k += BLOCK) x[idx[k]] = y[k];
-      __syncthreads();
-      residual_vector();                               // r = M x - b
-      for (int i = tid; i < n; i += BLOCK) w[i] = S[i] ? 0.0 : r[i];     // lcp.cc:219-223
-      __syncthreads();
-      ++pivots;
-      check();
-      if (sh.good > sh.best) {                         // lcp.cc:125-137 (uniform: shared value)
-        for (int i = tid; i < n; i += BLOCK) { bx[i] = x[i]; bw[i] = w[i]; }
+        packed_cholesky<BLOCK>(T, ns, y, &sh.fail);
+        packed_back_solve(T, ns, y);
+        for (int k = tid; k < ns; k += BLOCK) x[idx[k]] = y[k];
         __syncthreads();
-        if (tid == 0) sh.best = sh.good;
+        residual_vector();                               // r = M x - b
+        for (int i = tid; i < n; i += BLOCK) w[i] = S[i] ? 0.0 : r[i];     // lcp.cc:219-223
         __syncthreads();
+        ++pivots;
+        check();
+        if (sh.good > sh.best) {                         // lcp.cc:125-137 (uniform: shared value)
+          for (int i = tid; i < n; i += BLOCK) { bx[i] = x[i]; bw[i] = w[i]; }
+          __syncthreads();
+          if (tid == 0) sh.best = sh.good;
+          __syncthreads();
+        }
+        ++iter;
+        if (sh.fail) break;
       }
-      ++iter;
-      if (sh.fail) break;
-    }
-    solved = (sh.state == 1);
-    if (!solved && !sh.fail) {
-      // capped: the best-seen iterate (reference rule only), re-checked at the looser 1e-8 (lcp.cc:241-246)
-      if (!box_fix) {
-        for (int i = tid; i < n; i += BLOCK) { x[i] = bx[i]; w[i] = bw[i]; }
+      solved = (sh.state == 1);
+      if (!solved && !sh.fail) {
+        // capped: the best-seen iterate (reference rule only), re-checked at the looser 1e-8 (lcp.cc:241-246)
+        if (!box_fix) {
+          for (int i = tid; i < n; i += BLOCK) { x[i] = bx[i]; w[i] = bw[i]; }
+          __syncthreads();
+        }
+        residual_vector();
+        check();
+        solved = is_solution(1e-8) ? 1 : 0;
+      }
+      if constexpr (PYR) {
+        // beta^{k+1} from x^k, and delta_k = max |beta^{k+1} - beta^k| / max(1, max beta^{k+1}): both maxima of
+        // non-negative doubles, taken on their bit patterns
+        pyr.outer = outer;
+        if (!solved) break;
+        if (tid == 0) { red[0] = 0ull; red[1] = 0ull; }
         __syncthreads();
+        for (int i = tid; i < n; i += BLOCK) {
+          const int f = nloc[i];
+          if (f < 0) continue;
+          const double xf = x[f];
+          const double bn = xf > 0.0 ? pyr.mu[idxI[i]] * xf : 0.0;     // one rounding, as project_pyramid's
+          atomicMax(&red[0], (unsigned long long)__double_as_longlong(fabs(bn - hi[i])));
+          atomicMax(&red[1], (unsigned long long)__double_as_longlong(bn));
+        }
+        __syncthreads();
+        const double dmax = __longlong_as_double((long long)red[0]), bmax = __longlong_as_double((long long)red[1]);
+        pyr.change = dmax / (bmax > 1.0 ? bmax : 1.0);
+        if (pyr.change <= pyr.tol || outer >= pyr.max_outer) break;
+        // the next solve: the bounds move, rows at a bound move with them, the set stays
+        for (int i = tid; i < n; i += BLOCK) {
+          const int f = nloc[i];
+          if (f < 0) continue;
+          const double xf = x[f];
+          const double bn = xf > 0.0 ? pyr.mu[idxI[i]] * xf : 0.0;
+          const double old = hi[i];
+          if (bn == 0.0) { S[i] = 0; Cv[i] = 0.0; lo[i] = 0.0; hi[i] = 0.0; continue; }
+          if (old == 0.0) S[i] = 1;                        // released from the pin: 0 is strictly inside
+          else if (!S[i]) Cv[i] = Cv[i] < 0.0 ? -bn : bn;
+          lo[i] = -bn; hi[i] = bn;
+        }
+        if (tid == 0) sh.state = 0;
+        __syncthreads();
+        ++outer;
+        again = true;
       }
-      residual_vector();
-      check();
-      solved = is_solution(1e-8) ? 1 : 0;
-    }
+    } while (again);
   }
 
   // ---- x_e = A_ee^-1 (b_e - A_ei x_i)   (lcp.cc:317); the factor of A_ee once more (the loop above reused T)
@@ -313,6 +415,15 @@ __device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<M
   MixedSolveResult res;
   res.solved = solved; res.pivots = pivots;
   return res;
+}
+
+// the plain form
+template <int MAXN, int BLOCK>
+__device__ __forceinline__ MixedSolveResult mixed_solve_stage(MixedSolveShared<MAXN> &sh, const MixedSolveLds &L, const double *A, int N,
+                                                               const double *vb, const double *vlo, const double *vhi, double *Z,
+                                                               double *Lh, int use_bounds, int max_pivots) {
+  MixedPyramid<false> none;
+  return mixed_solve_stage<MAXN, BLOCK, false>(sh, L, A, N, vb, vlo, vhi, Z, Lh, use_bounds, max_pivots, none);
 }
 
 }  // namespace egs

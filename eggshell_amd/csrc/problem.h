@@ -132,6 +132,13 @@ struct egs_problem {
   // mu.  A new topology turns it off: the coefficients belong to the list they were given for.
   egs::DevBuf<unsigned char> mu;
   bool friction = false;
+  // egs_problem_set_dense_friction: max_outer > 0 makes egs_problem_step_dense solve the pyramid while friction is on
+  // (0: it refuses); the outcome of the last such step (egs_problem_dense_friction_info).
+  int dense_fric_outer = 0;
+  double dense_fric_tol = 0.0;
+  bool dense_fric_valid = false;
+  int dense_fric_solves = 0, dense_fric_converged = 0;
+  double dense_fric_change = 0.0;
   bool minv_iso = false;       // every M^-1 block is diag(a,a,a,b,b,b): the tile kernel keeps no B (EGS_ISO=0 disables)
   int last_iterations = 0;
   size_t real_size() const { return precision == EGS_F32 ? sizeof(float) : sizeof(double); }

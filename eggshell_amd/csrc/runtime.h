@@ -149,6 +149,7 @@ struct DenseWorkspace {
   // the kernels whose dynamic LDS limit has been raised on this context's device
   bool back_solve_lds = false, diag_lds = false, panel_lds = false;
   bool mixed_batch_lds[3] = {false, false, false};      // mixed_batch_kernel, one per size class
+  bool mixed_friction_lds[3] = {false, false, false};   // mixed_friction_batch_kernel, likewise
   // with the device set and both streams idle
   void release() {
     drop_blocks();

@@ -124,6 +124,15 @@ struct egs_world {
   // (world_fill_friction) before its solve.
   bool friction = false;
   DevBuf<double> d_fric;                 // [E]
+  std::vector<double> h_fric;            // [E], the host's copy (the dense step's ensembles above the fused cap)
+  // egs_world_set_dense_friction: max_outer > 0 makes the dense steps solve the pyramid (the fixed-point iteration of
+  // mixed_solve_device.h) while friction is on; 0: they refuse.  The outcomes of the last dense step, per ensemble.
+  int dense_fric_outer = 0;
+  double dense_fric_tol = 0.0;
+  DevBuf<DenseFrictionStatus> dn_fstatus;
+  DenseFrictionStatus *h_dn_fstatus = nullptr;
+  std::vector<DenseFrictionStatus> dn_finfo;   // [E] of the last dense step
+  std::vector<int32_t> dn_cons_host;     // dn_cons on the host
   bool lambda_stale = false;             // a stabilise call changed bodies / contacts since the last step's solve
   // EGS_WORLD_TRACE=1: host wall time per phase of egs_world_step, printed by egs_world_destroy
   bool trace = false;
@@ -234,11 +243,13 @@ void world_dense_plan(egs_world *w) {
   for (const auto &l : w->dn_class) lists.insert(lists.end(), l.begin(), l.end());
   if (lists.empty()) lists.push_back(0);
   stage(w->ctx, w->dn_cons, cons);
+  w->dn_cons_host = cons;
   stage(w->ctx, w->dn_cstart, w->dn_start);
   stage(w->ctx, w->dn_wsoff, w->dn_off);
   stage(w->ctx, w->dn_lists, lists);
   w->dn_ws.alloc((size_t)(off > 0 ? off : 1));
   w->dn_status.alloc((size_t)E);
+  w->dn_fstatus.alloc((size_t)E);
   w->dn_big_rows_valid = false;
   w->dense_plan_replans = w->replans;
 }
@@ -495,7 +506,10 @@ struct PhaseTimer {
 // egs_world_step_dense's ensembles above the fused cap: the multi-launch path on each ensemble's workspace slice, one
 // after another (row types and bounds read back once per re-plan).  x: the world problem's lambda.  The first
 // failure's message goes to big_msg.  dt_each [E] (host, may be NULL): an ensemble with dt 0 sits out, it is not solved.
-void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double *x, std::string &big_msg, const double *dt_each) {
+// pyramid: friction is on and egs_world_set_dense_friction allows it -- the fixed-point iteration from the host
+// (mixed_friction_host) on the ensemble's matrix and right-hand side read back, beta from the read-back x.
+void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double *x, std::string &big_msg, const double *dt_each,
+                     bool pyramid) {
   hipStream_t s = w->ctx->stream;
   auto rows_of = [&](int e) { return 3 * (w->dn_start[(size_t)e + 1] - w->dn_start[(size_t)e]); };
   if (!w->dn_big_rows_valid) {
@@ -536,9 +550,37 @@ void world_dense_big(egs_world *w, double cfm_coeff, int32_t use_bounds, double 
     if (st.cfm != 0.0) launch_dense_world_add_diag(A, N, st.cfm, s);
     int piv = 0;
     std::string msg;
-    const bool good = dense_mixed_constraints_device(w->ctx->dense, N, A, vb, w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
-                                                     w->dn_big_hi.data() + r0, use_bounds != 0, false, 0, 0.0, nullptr,
-                                                     nullptr, xs, &piv, &msg);
+    bool good;
+    if (pyramid) {
+      const size_t n = (size_t)N;
+      std::vector<double> hA(n * n), hb(n), hmu(n), hx(n), hw(n);
+      std::vector<int32_t> nrow(n, -1);
+      HIPCHK(hipMemcpyAsync(hA.data(), A, n * n * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(hb.data(), vb, n * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (size_t i = 1; i < n; ++i)                       // the factorisations read the lower triangle: one matrix
+        for (size_t j = 0; j < i; ++j) hA[j * n + i] = hA[i * n + j];
+      const int mj = (int)w->jb0.size();
+      for (size_t k = 0; k < n; ++k) {
+        const int c = w->dn_cons_host[(size_t)w->dn_start[(size_t)e] + k / 3];
+        hmu[k] = c < mj ? -1.0 : w->h_fric[(size_t)e];
+        if (k % 3 < 2 && hmu[k] >= 0.0) nrow[k] = (int32_t)(k - k % 3 + 2);
+      }
+      DenseFrictionStatus &fs = w->dn_finfo[(size_t)e];
+      int out = 0;
+      good = mixed_friction_host(w->ctx->dense, N, hA.data(), hb.data(), w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
+                                 w->dn_big_hi.data() + r0, nrow.data(), hmu.data(), 0, w->dense_fric_outer, w->dense_fric_tol, hx.data(),
+                                 hw.data(), nullptr, &piv, &out, &fs.change, &msg);
+      fs.outer = out;
+      fs.converged = (good && fs.change <= w->dense_fric_tol) ? 1 : 0;
+      if (good) {
+        HIPCHK(hipMemcpyAsync(xs, hx.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                   // hx is this scope's
+      }
+    } else {
+      good = dense_mixed_constraints_device(w->ctx->dense, N, A, vb, w->dn_big_C.data() + r0, w->dn_big_lo.data() + r0,
+                                            w->dn_big_hi.data() + r0, use_bounds != 0, false, 0, 0.0, nullptr, nullptr, xs, &piv, &msg);
+    }
     st.ok = good ? 1 : 0;
     st.pivots = piv;
     if (good) launch_dense_world_scatter(w->dn_cons.p + w->dn_start[(size_t)e], N, xs, x, s);
@@ -642,10 +684,15 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
     const int E = w->n_ens;
     if (!w->h_dn_status) w->h_dn_status = static_cast<DenseEnsStatus *>(w->dn_pinned.take((size_t)E * sizeof(DenseEnsStatus)));
     w->dn_info.assign((size_t)E, DenseEnsStatus{1.0, 0.0, 1, 0});   // contact-free ensembles: solved, no pivots
+    w->dn_finfo.assign((size_t)E, DenseFrictionStatus{0.0, 1, 1});  // (and without the pyramid: one solve)
+    const bool pyramid = w->friction && w->dense_fric_outer > 0;
+    if (pyramid && !w->h_dn_fstatus)
+      w->h_dn_fstatus = static_cast<DenseFrictionStatus *>(w->dn_pinned.take((size_t)E * sizeof(DenseFrictionStatus)));
     std::string big_msg;
     bool sits_out = false;
     for (int e = 0; dt_each && e < E; ++e) sits_out |= dt_each[e] == 0.0;
     w->last_warm = false;
+    if (pyramid) world_fill_friction(w);
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);                              // J, err, bounds, rhs (ensembles.cc:565-570)
       // the dense step takes no start; an ensemble sitting out keeps its history through the rows matched here
@@ -680,20 +727,31 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
         lists = w->dn_lists_step.p;
         HIPCHK(hipMemsetAsync(a.x, 0, (size_t)p->m * 3 * sizeof(double), s));
       }
+      DenseWorldFriction fa{};
+      if (pyramid) {
+        fa.mu = real<double>(p->mu); fa.status = w->dn_fstatus.p;
+        fa.tol = w->dense_fric_tol; fa.max_outer = w->dense_fric_outer;
+      }
       int at = 0;
       for (int c = 0; c < 3; ++c) {                                  // the rest of ComputeVDot, one workgroup each
-        launch_dense_world_fused(a, lists + at, count[c], c, s);
+        if (pyramid) launch_dense_world_friction(a, fa, lists + at, count[c], c, s);
+        else launch_dense_world_fused(a, lists + at, count[c], c, s);
         at += count[c];
       }
       HIPCHK(hipGetLastError());
-      if (!w->dn_big.empty()) world_dense_big(w, cfm_coeff, use_bounds, a.x, big_msg, dt_each);   // above the fused cap
+      if (!w->dn_big.empty()) world_dense_big(w, cfm_coeff, use_bounds, a.x, big_msg, dt_each, pyramid);   // above the fused cap
       // one read-back of the fused ensembles' figures
       if (at > 0) {
         HIPCHK(hipMemcpyAsync(w->h_dn_status, w->dn_status.p, (size_t)E * sizeof(DenseEnsStatus), hipMemcpyDeviceToHost, s));
+        if (pyramid)
+          HIPCHK(hipMemcpyAsync(w->h_dn_fstatus, w->dn_fstatus.p, (size_t)E * sizeof(DenseFrictionStatus), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         for (const auto &l : w->dn_class)
           for (int e : l)
-            if (!(dt_each && dt_each[e] == 0.0)) w->dn_info[(size_t)e] = w->h_dn_status[e];
+            if (!(dt_each && dt_each[e] == 0.0)) {
+              w->dn_info[(size_t)e] = w->h_dn_status[e];
+              if (pyramid) w->dn_finfo[(size_t)e] = w->h_dn_fstatus[e];
+            }
       }
     }
     int nf = 0, first = -1, max_piv = 0;
@@ -973,8 +1031,10 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
   if (!w) return EGS_ERR_INVALID;
   if (n_failed) *n_failed = 0;
   if (egs_status st = world_step_guard(w, dt, "the dense path is fp64 (the reference's is)")) return st;
-  if (w->friction) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
+  if (w->friction && w->dense_fric_outer == 0)
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
+  if (w->friction && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
   return world_step_direct(w, dt, erp, nullptr, nullptr, cfm_coeff, use_bounds, detect_contacts, n_failed);
 }
 
@@ -983,8 +1043,10 @@ egs_status egs_world_step_dense_each(egs_world *w, int32_t n_ensembles, const do
   if (!w) return EGS_ERR_INVALID;
   if (n_failed) *n_failed = 0;
   if (egs_status st = world_each_guard(w, n_ensembles, dt, erp, "the dense path is fp64 (the reference's is)")) return st;
-  if (w->friction) return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
+  if (w->friction && w->dense_fric_outer == 0)
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
+  if (w->friction && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
   return world_step_direct(w, 0.0, 0.0, dt, erp, cfm_coeff, use_bounds, detect_contacts, n_failed);
 }
 
@@ -999,6 +1061,28 @@ egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condi
     if (cfm) cfm[e] = st.cfm;
     if (pivots) pivots[e] = st.pivots;
     if (ok) ok[e] = st.ok;
+  }
+  return EGS_OK;
+}
+
+egs_status egs_world_set_dense_friction(egs_world *w, int32_t max_outer, double tol) {
+  if (!w) return EGS_ERR_INVALID;
+  if (max_outer < 0) return fail(w->ctx, EGS_ERR_INVALID, "max_outer must be >= 0 (0: the dense steps refuse friction)");
+  if (!(tol >= 0)) return fail(w->ctx, EGS_ERR_INVALID, "tol must be >= 0");
+  w->dense_fric_outer = max_outer;
+  w->dense_fric_tol = tol;
+  return EGS_OK;
+}
+
+egs_status egs_world_dense_friction_info(egs_world *w, int32_t n_ensembles, int32_t *outer, int32_t *converged, double *change) {
+  if (!w) return EGS_ERR_INVALID;
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  if (w->dn_finfo.size() != (size_t)w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "no egs_world_step_dense yet");
+  for (int e = 0; e < w->n_ens; ++e) {
+    const DenseFrictionStatus &fs = w->dn_finfo[(size_t)e];
+    if (outer) outer[e] = fs.outer;
+    if (converged) converged[e] = fs.converged;
+    if (change) change[e] = fs.change;
   }
   return EGS_OK;
 }
@@ -1064,6 +1148,7 @@ egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const doubl
     hipStream_t s = w->ctx->stream;
     HIPCHK(hipStreamSynchronize(s));   // a step in flight may still read the old table
     w->d_fric.alloc((size_t)n_ensembles);
+    w->h_fric.assign(mu, mu + n_ensembles);
     HIPCHK(hipMemcpyAsync(w->d_fric.p, mu, (size_t)n_ensembles * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));   // mu is the caller's
     w->friction = any;

@@ -542,6 +542,7 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
       problem_ = nullptr;
       egs::check(egs_problem_create(egs::DefaultContext(), n_, m, b0.data(), b1.data(), EGS_F64, &problem_));
       plan_b0_ = b0; plan_b1_ = b1;
+      problem_friction_ = false;
     }
     std::vector<double> pos((size_t)n_ * 3), R((size_t)n_ * 9), vl((size_t)n_ * 3), w((size_t)n_ * 3), Minv((size_t)n_ * 36);
     for (int i = 0; i < n_; ++i) {
@@ -554,13 +555,32 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
     egs::check(egs_problem_set_constraints(problem_, kind.data(), data.data()));
     egs_solve_stats st;
     if (use_dense_solver) {   // ComputeVDot (ensembles.cc:498-538) on the device
+      const bool pyramid = friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID;   // (Step let it through: SetDenseFriction)
+      if (pyramid) {   // every contact its coefficient, every joint -1
+        std::vector<double> mu((size_t)m);
+        for (int i = 0; i < m; ++i) mu[i] = dynamic_cast<const Contact *>(cs[i].get()) ? friction_mu_ : -1.0;
+        egs::check(egs_problem_set_friction(problem_, mu.data()));
+        problem_friction_ = true;
+      } else if (problem_friction_) {
+        egs::check(egs_problem_set_friction(problem_, nullptr));
+        problem_friction_ = false;
+      }
+      egs::check(egs_problem_set_dense_friction(problem_, dense_fric_outer_, dense_fric_tol_));
       egs::check(egs_problem_assemble(problem_, dt, erp));
       egs::check(egs_problem_dense_condition(problem_, 0.0, &last_condition_estimate));
       const double cfm = last_condition_estimate < 1e7 ? 0.0 : cfm_coeff;   // kGoodConditionNumber, constants.h:12
       int32_t ok = 0, pivots = 0;
-      egs_status rc = egs_problem_step_dense(problem_, dt, erp, cfm, /*use_bounds=*/0, &ok, &pivots);
+      egs_status rc = egs_problem_step_dense(problem_, dt, erp, cfm, /*use_bounds=*/dense_fric_outer_ > 0 ? 1 : 0, &ok, &pivots);
       if (rc != EGS_OK || !ok)   // the reference Panics here (ensembles.cc:531-534)
-        throw egs::Error(rc != EGS_OK ? rc : EGS_ERR_LCP_FAILED, "Lcp::MixedConstraintsSolver exited without reaching a solution.");
+        throw egs::Error(rc != EGS_OK ? rc : EGS_ERR_LCP_FAILED,
+                         rc == EGS_ERR_INVALID ? egs_last_error(egs::DefaultContext())
+                                               : "Lcp::MixedConstraintsSolver exited without reaching a solution.");
+      last_dense_outer = 1; last_dense_converged = true;
+      if (pyramid) {
+        int32_t outer = 0, conv = 0;
+        egs::check(egs_problem_dense_friction_info(problem_, &outer, &conv, nullptr));
+        last_dense_outer = outer; last_dense_converged = conv != 0;
+      }
     } else
     egs::check(egs_problem_step(problem_, dt, erp, &prm, &st));
     last_lambda.resize(3 * m);
@@ -739,6 +759,13 @@ void Ensemble::SetFriction(Contact::FrictionModel model, double mu) {
   friction_mu_ = model == Contact::FrictionModel::COULOMB_PYRAMID ? mu : 0.0;
 }
 
+void Ensemble::SetDenseFriction(int max_outer, double tol) {
+  if (max_outer < 0) throw egs::Error(EGS_ERR_INVALID, "SetDenseFriction: max_outer must be >= 0");
+  if (!(tol >= 0)) throw egs::Error(EGS_ERR_INVALID, "SetDenseFriction: tol must be >= 0");
+  dense_fric_outer_ = max_outer;
+  dense_fric_tol_ = max_outer > 0 ? tol : 0.0;
+}
+
 bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
@@ -844,9 +871,17 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
     throw egs::Error(EGS_ERR_UNSUPPORTED, "an ensemble with a Sphere steps on contacts the device detects: not with "
                                           "detect_contacts = false");
   if (StepOnDevice(dt)) return;   // collide -> solve -> integrate in one resident pipeline
-  if (friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID)
-    throw egs::Error(EGS_ERR_UNSUPPORTED, "COULOMB_PYRAMID steps on the device only: not with use_device_step = false, "
-                                          "use_dense_solver, caller-supplied contacts or a joint the device cannot take");
+  if (friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID) {
+    bool dense = use_dense_solver && dense_fric_outer_ > 0;      // SetDenseFriction: the dense step solves the pyramid
+    if (dense) {
+      int32_t kind = 0;
+      double d[7];
+      for (const auto &j : joints_) dense = dense && j->Describe(&kind, d);
+    }
+    if (!dense)
+      throw egs::Error(EGS_ERR_UNSUPPORTED, "COULOMB_PYRAMID steps on the device only: not with use_device_step = false, "
+                                            "use_dense_solver, caller-supplied contacts or a joint the device cannot take");
+  }
   const VectorXd v = GetVelocities();
   if (detect_contacts) UpdateContacts();
   CheckAndCorrectEnsembleState();   // ensembles.cc:394
@@ -875,6 +910,8 @@ EnsembleGroup::EnsembleGroup(std::vector<Ensemble *> members) : members_(std::mo
       throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in detect_contacts");
     if (m->warm_start_ != first->warm_start_ || m->warm_radius_ != first->warm_radius_)
       throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in SetWarmStart");
+    if (m->dense_fric_outer_ != first->dense_fric_outer_ || m->dense_fric_tol_ != first->dense_fric_tol_)
+      throw egs::Error(EGS_ERR_INVALID, who + " differs from member 0 in SetDenseFriction");
     int32_t kind = 0;
     double data[7];
     for (size_t j = 0; j < m->joints_.size(); ++j)
@@ -954,6 +991,9 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   for (size_t i = 1; i < E; ++i)   // (the constructor's check, again: SetWarmStart may have been called since)
     if (members_[i]->warm_start_ != lead->warm_start_ || members_[i]->warm_radius_ != lead->warm_radius_)
       throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " differs from member 0 in SetWarmStart");
+  for (size_t i = 1; i < E; ++i)
+    if (members_[i]->dense_fric_outer_ != lead->dense_fric_outer_ || members_[i]->dense_fric_tol_ != lead->dense_fric_tol_)
+      throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " differs from member 0 in SetDenseFriction");
   const bool warm = lead->warm_start_ && !lead->use_dense_solver;
   if (first || warm != world_warm_ || (warm && lead->warm_radius_ != world_warm_radius_)) {
     egs::check(egs_world_set_warm_start(world_, warm ? 1 : 0, lead->warm_radius_));
@@ -991,8 +1031,12 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   }
   const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
   if (lead->use_dense_solver) {
-    egs::check(egs_world_step_dense_each(world_, (int32_t)E, dt.data(), erp.data(), lead->cfm_coeff, /*use_bounds=*/0,
-                                         lead->detect_contacts ? 1 : 0, nullptr));
+    egs::check(egs_world_set_dense_friction(world_, lead->dense_fric_outer_, lead->dense_fric_tol_));
+    egs::check(egs_world_step_dense_each(world_, (int32_t)E, dt.data(), erp.data(), lead->cfm_coeff,
+                                         /*use_bounds=*/lead->dense_fric_outer_ > 0 ? 1 : 0, lead->detect_contacts ? 1 : 0, nullptr));
+    std::vector<int32_t> outer(E), conv(E);
+    egs::check(egs_world_dense_friction_info(world_, (int32_t)E, outer.data(), conv.data(), nullptr));
+    for (size_t i = 0; i < E; ++i) { members_[i]->last_dense_outer = outer[i]; members_[i]->last_dense_converged = conv[i] != 0; }
   } else {
     egs_solve_params prm = lead->solver_params;
     prm.cfm = lead->cfm_coeff;

@@ -334,8 +334,20 @@ class Ensemble {  // ensembles.h:25-186
   // reference's model; COULOMB_PYRAMID bounds every contact's two tangential multipliers by +-mu times its normal
   // multiplier in the device step's sweeps (egs_world_set_friction).  Throws egs::Error: EGS_ERR_UNSUPPORTED for
   // NO_FRICTION and INFINITE, EGS_ERR_INVALID for a pyramid with mu < 0 or NaN.  A pyramid ensemble steps on the
-  // device only: Step throws EGS_ERR_UNSUPPORTED where it would take the explicit or the dense path.
+  // device only: Step throws EGS_ERR_UNSUPPORTED where it would take the explicit or the dense path -- the dense path
+  // unless SetDenseFriction has allowed it.
   void SetFriction(Contact::FrictionModel model, double mu = 0);
+  // The pyramid on the dense direct solver, opt-in (egs_problem_set_dense_friction / egs_world_set_dense_friction):
+  // after SetDenseFriction(max_outer > 0, tol) a COULOMB_PYRAMID ensemble with use_dense_solver steps instead of
+  // throwing -- the fixed-point iteration on the tangential bounds, at most max_outer solves, stopping change tol --
+  // and this ensemble's dense steps honour the stored bounds (use_bounds = 1, which the pyramid needs), whatever its
+  // friction model.  last_dense_outer / last_dense_converged tell how the last such step ended; not converging is no
+  // error.  max_outer = 0 switches it off again.  Throws egs::Error(EGS_ERR_INVALID): max_outer < 0, tol < 0 or NaN.
+  void SetDenseFriction(int max_outer = 32, double tol = 1e-10);
+  int dense_friction_outer() const { return dense_fric_outer_; }
+  double dense_friction_tol() const { return dense_fric_tol_; }
+  int last_dense_outer = 0;
+  bool last_dense_converged = true;
   Contact::FrictionModel friction_model() const { return friction_model_; }
   double friction_mu() const { return friction_mu_; }
   bool warm_start() const { return warm_start_; }
@@ -381,6 +393,9 @@ class Ensemble {  // ensembles.h:25-186
   double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
   Contact::FrictionModel friction_model_ = Contact::FrictionModel::BOX;
   double friction_mu_ = 0.0, world_friction_ = -1.0;   // asked for; the coefficient the device world was last told (< 0: box)
+  int dense_fric_outer_ = 0;                     // SetDenseFriction (0: off)
+  double dense_fric_tol_ = 0.0;
+  bool problem_friction_ = false;                // the cached device problem holds friction coefficients
   double device_friction() const { return friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID ? friction_mu_ : -1.0; }
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last device step (warm start only)
   egs_problem *problem_ = nullptr;
@@ -414,7 +429,7 @@ class Cairn : public Ensemble {
 // member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
 // egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
 //   - The members may differ in SetFriction: member i's contacts take its model and coefficient (egs_world_set_friction).
-//   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts and SetWarmStart, and each must be able to
+//   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts, SetWarmStart and SetDenseFriction, and each must be able to
 //     take the device step (joints that Describe themselves, no caller-supplied contacts); the list may not be empty or
 //     hold a pointer twice: the constructor throws egs::Error(EGS_ERR_INVALID) naming the offending member.
 //   - The members are not owned and must outlive the group; Init() them before the first Step (M^-1, the external

@@ -8,6 +8,9 @@
 //   friction_demo --box      the same step with the reference's friction box: it saturates at 1 per contact
 //   friction_demo --refuse   SetFriction(NO_FRICTION), SetFriction(INFINITE), a negative mu and a pyramid ensemble
 //                            with use_dense_solver: prints the four refusals, exits 0 if all were refused
+//   friction_demo --dense    the cube at mu 0.2 and 0.8 with use_dense_solver after SetDenseFriction(32, 1e-10), cfm 0.01
+//                            (the four redundant contacts make J M^-1 J^T singular, so the cfm rule adds it): per mu one
+//                            JSON line with the velocity, Coulomb's, outer and converged
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -57,11 +60,34 @@ int refuse() {
   return refused == 4 ? 0 : 1;
 }
 
+int dense() {
+  const double depth = 1e-6;
+  for (const double mu : {0.2, 0.8}) {
+    TiltedCube cube(depth);
+    cube.Init();
+    cube.cfm_coeff = 0.01;
+    cube.use_dense_solver = true;
+    cube.SetFriction(Contact::FrictionModel::COULOMB_PYRAMID, mu);
+    cube.SetDenseFriction(32, 1e-10);
+    cube.Step(kDt);
+    const Body &b = *cube.components()[0];
+    const double th = std::atan(kTan), erp = 0.2;
+    const double normal = kG * std::cos(th) + erp * depth / (kDt * kDt);
+    const double slide = kDt * (kG * std::sin(th) - mu * normal);
+    std::printf("{\"mu\": %.17g, \"depth\": %.17g, \"contacts\": %d, \"v\": [%.17g, %.17g, %.17g], \"w\": [%.17g, %.17g, %.17g], "
+                "\"coulomb_vx\": %.17g, \"coulomb_vz\": %.17g, \"outer\": %d, \"converged\": %d}\n",
+                mu, depth, (int)cube.constraints().size(), b.v()[0], b.v()[1], b.v()[2], b.w_g()[0], b.w_g()[1], b.w_g()[2],
+                slide > 0 ? slide : 0.0, erp * depth / kDt, cube.last_dense_outer, cube.last_dense_converged ? 1 : 0);
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
   try {
     if (argc > 1 && std::strcmp(argv[1], "--refuse") == 0) return refuse();
+    if (argc > 1 && std::strcmp(argv[1], "--dense") == 0) return dense();
     const bool box = argc > 1 && std::strcmp(argv[1], "--box") == 0;
     if (box) { --argc; ++argv; }
     const double mu = argc > 1 ? std::atof(argv[1]) : 0.2;

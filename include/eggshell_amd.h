@@ -215,9 +215,23 @@ egs_status egs_problem_set_start(egs_problem *p, int32_t mode, const double *x0 
  *      forward sweep clamps against the previous x_n); b = 0 = x adds nothing.
  *      mu = NULL, or no coefficient >= 0, turns friction off: every result and schedule flag is then what it is
  *      without this call.  On, the launches report EGS_SCHED_FRICTION, egs_problem_step does not fuse the assembly
- *      (EGS_SCHED_FUSED_ASSEMBLY stays clear) and egs_problem_step_dense returns EGS_ERR_UNSUPPORTED.  Starts, mat-vec
- *      and get_wres work alongside as they are.  EGS_ERR_INVALID: a NaN coefficient (nothing changes).              */
+ *      (EGS_SCHED_FUSED_ASSEMBLY stays clear) and egs_problem_step_dense returns EGS_ERR_UNSUPPORTED unless
+ *      egs_problem_set_dense_friction has allowed it.  Starts, mat-vec and get_wres work alongside as they are.
+ *      EGS_ERR_INVALID: a NaN coefficient (nothing changes).                                                       */
 egs_status egs_problem_set_friction(egs_problem *p, const double *mu /*[m] or NULL*/);
+/* The friction pyramid on the dense direct solver, opt-in.  max_outer > 0: while friction is on, egs_problem_step_dense
+ * solves the pyramid by the fixed-point iteration of egs_mixed_friction_solve_batch (at most max_outer solves, stopping
+ * change tol; the reference values are 32 and 1e-10) instead of refusing: rows 0 and 1 of a constraint with mu >= 0 are
+ * pyramid rows whose normal row is its row 2.  The step runs the iteration from the host around the dense mixed solver
+ * (every solve on the problem without its pinned rows, its Murty set from scratch), whatever the size.  use_bounds
+ * must then be 1 (EGS_ERR_INVALID otherwise, also when a pyramid constraint's row 2 is an equality row).  Not converging
+ * within max_outer is no failure: the step integrates the last iterate; egs_problem_dense_friction_info tells.
+ * max_outer = 0 (the default) switches it off again: the step refuses as before.  The condition estimate, cfm,
+ * EGS_ERR_LCP_FAILED and integration are unchanged.  EGS_ERR_INVALID: max_outer < 0, tol < 0 or NaN.                */
+egs_status egs_problem_set_dense_friction(egs_problem *p, int32_t max_outer, double tol);
+/* The last egs_problem_step_dense that solved the pyramid (any pointer may be NULL): solves made, converged
+ * (change <= tol), the last change.  EGS_ERR_INVALID before the first such step.                                   */
+egs_status egs_problem_dense_friction_info(egs_problem *p, int32_t *outer, int32_t *converged, double *change);
 
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
@@ -337,6 +351,34 @@ egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, co
                                              const double *b, const uint8_t *C, const double *lo, const double *hi,
                                              int32_t use_bounds, int32_t max_pivots, double *x, double *w, int32_t *ok,
                                              int32_t *pivots);
+
+/* The Coulomb friction pyramid on the dense direct solver, for `count` independent problems on explicit matrices
+ * (packing, fusing and size classes of egs_mixed_constraints_solve_batch; plain rows always honour their bounds, the
+ * meaning of use_bounds bit 0).  Beside (A, b, C, lo, hi) a problem has, per row r, normal_row[r] (int32, an index
+ * within its own problem, or -1: a plain row) and mu[r] >= 0.  A row with normal_row[r] = f >= 0 is a PYRAMID row: an
+ * inequality row whatever C[r] says, bounded by [-beta_r, +beta_r] with beta_r following x_f; f must be a plain
+ * inequality row.  The solve is the fixed-point iteration on beta:
+ *   beta^0 = 0.  Solve k is the box LCP with the pyramid rows at [-beta^k, +beta^k]; a pyramid row with beta^k_r = 0
+ *   is PINNED: x_r = 0 exactly, its w_r carries no condition, it never enters the active set.
+ *   beta^{k+1}_r = x_f > 0 ? fl(mu_r x_f) : 0;  delta_k = max_r |beta^{k+1}_r - beta^k_r| / max(1, max_r beta^{k+1}_r).
+ *   Stop at the first k with delta_k <= tol, or after max_outer solves (0 = 32).
+ * x, w: the last solve's (w = 0 exactly on equality rows, A x - b on a pinned row); beta (may be NULL): the bounds x was
+ * solved under, 0 on plain rows; outer[k]: solves made; change[k]: the last delta, so the run converged iff
+ * change[k] <= tol; pivots[k] (may be NULL): Murty steps summed over the solves.  ok[k] = 0: an inner solve failed as
+ * egs_mixed_constraints_solve_batch's does.  NOT converging within max_outer is no failure: ok[k] = 1 and the last
+ * iterate is returned.  A problem without a pyramid row returns the bits of egs_mixed_constraints_solve_batch with
+ * use_bounds = 1, and outer = 1.
+ * Problems of n[k] <= 112 rows run fused, a workgroup each, the partition and the Schur complement once and every
+ * solve starting its Murty set from the previous solve's final set.  Larger ones run inside the call, one after
+ * another: the same iteration from the host around egs_mixed_constraints_solve's path, on the problem without its
+ * pinned rows, every solve starting its set from scratch.
+ * EGS_ERR_INVALID, with nothing launched and no output written: whatever egs_mixed_constraints_solve_batch refuses;
+ * a normal_row outside -1 .. n[k] - 1, or one pointing at an equality row or at another pyramid row; a NaN or negative
+ * mu on a pyramid row; max_outer < 0; tol < 0 or NaN. */
+egs_status egs_mixed_friction_solve_batch(egs_context *ctx, int32_t count, const int32_t *n, const double *A, const double *b,
+                                          const uint8_t *C, const double *lo, const double *hi, const int32_t *normal_row,
+                                          const double *mu, int32_t max_pivots, int32_t max_outer, double tol, double *x,
+                                          double *w, double *beta, int32_t *ok, int32_t *pivots, int32_t *outer, double *change);
 
 /* Replaces sparse::JacobiIteration / GaussSeidelIteration / SORIteration on an EXPLICIT matrix:
  *   VectorXd sparse::XIteration(const MatrixXd& A, const VectorXd& b)                                    sparse_iterations.h:13-24
@@ -529,8 +571,8 @@ egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_r
  * world's, 1 for a plain world).  Every contact of ensemble e takes mu[e], every joint -1; mu[e] < 0 keeps the
  * reference's friction box for that ensemble.  The per-constraint coefficients are filled on the device from the
  * current contact list at every step.  egs_world_step and egs_world_step_each solve with it; egs_world_step_dense and
- * egs_world_step_dense_each return EGS_ERR_UNSUPPORTED while any coefficient is >= 0.  Warm start and stabilisation are
- * untouched.  EGS_ERR_INVALID: mu NULL, a NaN, a wrong n_ensembles (nothing changes).                              */
+ * egs_world_step_dense_each return EGS_ERR_UNSUPPORTED while any coefficient is >= 0, unless
+ * egs_world_set_dense_friction has allowed it.  Warm start and stabilisation are untouched.  EGS_ERR_INVALID: mu NULL, a NaN, a wrong n_ensembles (nothing changes).                              */
 egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const double *mu /*[E]*/);
 egs_status egs_world_get_start(egs_world *w, int32_t max_rows, int32_t *rows_out, double *x0, int32_t *source /*[m] or NULL*/);
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans);
@@ -591,6 +633,22 @@ egs_status egs_world_step_dense(egs_world *w, double dt, double erp, double cfm_
  * and ok (1 = solved).  n_ensembles must be the world's; EGS_ERR_INVALID before the first dense step.    */
 egs_status egs_world_dense_info(egs_world *w, int32_t n_ensembles, double *condition, double *cfm,
                                 int32_t *pivots, int32_t *ok);
+/* The friction pyramid on the dense steps, opt-in (egs_problem_set_dense_friction for a world).  max_outer > 0: while
+ * egs_world_set_friction is on, egs_world_step_dense and egs_world_step_dense_each solve every ensemble's pyramid --
+ * every contact's rows 0 and 1 bounded by +-mu[e] x of its row 2, joints and ensembles with mu[e] < 0 as stored --
+ * by the fixed-point iteration of egs_mixed_friction_solve_batch.  Ensembles of at most 112 rows run it inside the fused
+ * kernel (its pyramid form: mu read per gathered constraint from the table the step fills; partition and Schur
+ * complement once; each solve starts its Murty set from the previous solve's); larger ones from the host around the
+ * multi-launch path (each solve from scratch).  use_bounds must be 1 while friction is on (EGS_ERR_INVALID otherwise).
+ * A world whose friction is off steps exactly as without this call.  Each ensemble of a batched world gets the bits of
+ * its own one-ensemble world.  Not converging within max_outer is no failure.  max_outer = 0 (the default): the dense
+ * steps refuse friction as before.  EGS_ERR_INVALID: max_outer < 0, tol < 0 or NaN.                                */
+egs_status egs_world_set_dense_friction(egs_world *w, int32_t max_outer, double tol);
+/* Per-ensemble outcomes of the pyramid in the last dense step ([E] each, any may be NULL): solves made, converged
+ * (change <= tol), the last change; an ensemble without constraints, sitting out, or stepped with friction off reports
+ * 1, 1, 0.  n_ensembles must be the world's; EGS_ERR_INVALID before the first dense step.                          */
+egs_status egs_world_dense_friction_info(egs_world *w, int32_t n_ensembles, int32_t *outer, int32_t *converged,
+                                         double *change);
 
 /* ---- a time step and an erp per ensemble -----------------------------------------------------------------------
  * The reference's frame steps its ensembles at different rates (model.cc:80, 108: the cairn with kSimTimeStep*5,
