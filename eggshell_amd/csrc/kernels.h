@@ -128,7 +128,10 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 // assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit.
 // store_system = false: J0, J1, rhs, lo, hi, err and is_eq are not written (the caller defers them: problem.h)
 // pair: the PAIR form, one update on a lane pair (step_solve.hip); the same bits on any plan, worth it on a pairable one
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, hipStream_t s);
+// chain (with pair, on a plan that is Plan::chained, a.steady on): the CHAIN form of its steady loop, the pair's
+// accumulators in registers between its two updates; the same bits
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
+                                hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);

@@ -354,7 +354,7 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
     plan = std::move(*recycle);
     plan.n_islands = plan.n_tiles = 0; plan.max_slots = 1; plan.max_cnt = 1;
     plan.lanes.clear(); plan.lane_level.clear(); plan.tile_period.clear(); plan.tile_depth.clear();
-    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false; plan.pairable = false;
+    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false; plan.pairable = false; plan.chained = false;
     plan.tile_nslots.clear(); plan.tile_slot_off.clear(); plan.slot_body.clear();
     plan.global.clear();
     plan.n_patch_tiles = 0; plan.patch_max_slots = 1; plan.n_shared_bodies = 0; plan.patch_runs = false;
@@ -755,6 +755,28 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
         else if (ph != phase) plan.pairable = false;
       }
     }
+  // chained (plan.h): the thread pair of the PAIR form that holds A = lane 64 w + l and B = lane 64 w + 32 + l runs two
+  // consecutive updates of the same two bodies.  The sweeps' grid of a fresh launch puts a constraint's updates at
+  // b + P k with b = level (forward) resp. b = 2 depth - 1 - level (backward SOR: the sweeps start at t0 = depth and
+  // mirror the levels).  With P even a time step's parity is its phase's, t mod P.  Forward: level[A] is even, so A,
+  // the first of the two, is due at even steps and B = A + 1 at the odd step that follows.  Backward: level[B] =
+  // level[A] + 1 is odd, so b[B] = 2 depth - 1 - level[B] is even whatever the depth: B, the first of the two there, is
+  // due at even steps and A, with b[A] = b[B] + 1, at the odd step that follows.  An A without a B is due at even steps
+  // forward and at odd steps backward.  So in both methods the pair's first update falls on an even step and its
+  // second on the next one, and the lanes due at steps 2 j and 2 j + 1 are the firsts and seconds of the same pairs.
+  plan.chained = plan.pairable;
+  for (int t = 0; t < plan.n_tiles && plan.chained; ++t) {
+    if (plan.tile_period[t] % 2 != 0) plan.chained = false;
+    for (int w = 0; w < block / 64 && plan.chained; ++w)
+      for (int l = 0; l < 32 && plan.chained; ++l) {
+        const size_t ia = (size_t)t * block + 64 * w + l, ib = ia + 32;
+        const LaneDesc &a = plan.lanes[ia], &b = plan.lanes[ib];
+        if (a.cidx < 0) { if (b.cidx >= 0) plan.chained = false; continue; }
+        if (plan.lane_level[ia] % 2 != 0) plan.chained = false;
+        else if (b.cidx >= 0 && (a.slot0 != b.slot0 || a.slot1 != b.slot1 || plan.lane_level[ib] != plan.lane_level[ia] + 1))
+          plan.chained = false;
+      }
+  }
   plan.slot_body.assign((size_t)off, -1);   // slot 0 of every tile = the world
   for (int b = 0; b < n_bodies; ++b)
     if (body_tile[b] >= 0) plan.slot_body[(size_t)plan.tile_slot_off[body_tile[b]] + body_slot[b]] = b;

@@ -62,6 +62,13 @@ struct Plan {
   // under the phase-major lane order.  That is where step_solve_kernel's PAIR form pays (step_solve.hip): it runs the
   // update of lane 64 w + j on the thread pair (2 j, 2 j + 1) of wavefront w, and then that of lane 64 w + 32 + j.
   bool pairable = false;
+  // A pairable plan in which the two constraints of every thread pair of that form, A = plan lane 64 w + l and
+  // B = plan lane 64 w + 32 + l (l < 32), are consecutive updates of the SAME two bodies: every tile's period is even, B
+  // is not active without A, level[A] is even, and where both are active slot0 and slot1 agree and level[B] =
+  // level[A] + 1 -- two neighbouring contact points of a box face, as the phase-major lane order of a pile lays them out.
+  // Then the pair's accumulators can stay in registers from the first of the two updates to the second (step_solve.hip:
+  // the CHAIN form; plan.cpp derives the parity of the first's time step where it sets the flag).
+  bool chained = false;
   std::vector<int32_t> tile_nslots;   // per tile, slots in use (slot 0 = world)
   std::vector<int32_t> tile_slot_off; // per tile, offset into slot_body
   std::vector<int32_t> slot_body;     // slot -> global body index (-1 for slot 0)

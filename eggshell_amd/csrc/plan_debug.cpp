@@ -155,4 +155,12 @@ egs_status egs_debug_plan_pairable(int32_t n, int32_t m, const int32_t *body0, c
   });
 }
 
+egs_status egs_debug_plan_chained(int32_t n, int32_t m, const int32_t *body0, const int32_t *body1, int32_t *chained) {
+  return plan_entry(n, m, body0, body1, [&]() -> egs_status {
+    const Plan pl = build_plan(n, m, body0, body1, 256);
+    if (chained) *chained = pl.chained ? 1 : 0;
+    return EGS_OK;
+  });
+}
+
 }  // extern "C"

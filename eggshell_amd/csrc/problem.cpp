@@ -761,6 +761,17 @@ egs_status egs_problem_get_stats(egs_problem *p, egs_solve_stats *stats) {
   });
 }
 
+egs_status egs_problem_get_schedule(egs_problem *p, int32_t *schedule) {
+  if (!p || !schedule) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    egs_solve_stats st;
+    std::memset(&st, 0, sizeof st);
+    fill_stats(p, &st);
+    *schedule = st.schedule | (int32_t)(p->last_sched & egs_problem::kSchedRefinements);
+    return EGS_OK;
+  });
+}
+
 egs_status egs_solve_blocks(egs_context *ctx, int32_t n, const double *Minv, int32_t m, const int32_t *body0,
                             const int32_t *body1, const double *J0, const double *J1, const uint8_t *is_eq,
                             const double *lo, const double *hi, const double *rhs, const egs_solve_params *params,

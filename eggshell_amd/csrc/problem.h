@@ -52,6 +52,9 @@ struct egs_problem {
   egs::Plan planq;
   bool use_quad = false;
   uint32_t last_sched = 0;     // SweepSchedule::flags() of the last solve launch
+  // ... of which egs_solve_stats.schedule leaves these out and egs_problem_get_schedule reports them: refinements of a
+  // form that is already reported.  Callers compare that field exactly between a form's switch on and off.
+  static constexpr uint32_t kSchedRefinements = EGS_SCHED_CHAIN;
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0

@@ -23,6 +23,7 @@ struct SweepSchedule {
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
   bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_solve.hip)
+  bool chain = false;       // ... whose steady loop keeps a pair's accumulators in registers between its two updates (CHAIN)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -31,7 +32,8 @@ struct SweepSchedule {
   uint32_t flags() const {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
-           (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0);
+           (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0) |
+           (chain ? EGS_SCHED_CHAIN : 0);
   }
 };
 
@@ -84,6 +86,11 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   // EGS_STEP_PAIR=0 keeps one lane per constraint.
   const char *pe = std::getenv("EGS_STEP_PAIR");
   s.pair = s.assemble && pl.pairable && !(pe && std::atoi(pe) == 0);
+  // ... with the accumulators of a pair in registers from the first of its two updates to the second, where the pair
+  // holds consecutive updates of the same two bodies (plan.h: chained).  The form is the PAIR kernel's steady loop, so
+  // it goes with that loop.  EGS_STEP_CHAIN=0 keeps the LDS round trip.
+  const char *ce = std::getenv("EGS_STEP_CHAIN");
+  s.chain = s.pair && pl.chained && s.steady && !(ce && std::atoi(ce) == 0);
   return s;
 }
 
@@ -171,7 +178,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, ctx->stream);
+          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, ctx->stream);
           // the system this launch assembled: stored, or the problem's to make on demand from the state it read
           p->sys_deferred = sc.defer;
           p->deferred_prev = false;
@@ -417,7 +424,7 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_tiles = pl.n_tiles;
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
-  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | p->last_sched;
+  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_sched & ~egs_problem::kSchedRefinements);
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;

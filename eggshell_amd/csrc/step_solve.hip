@@ -56,7 +56,8 @@
 // problem remembers that its system is not materialised (problem.h: ensure_system runs assemble_kernel on demand).
 //
 // PAIR (ASSEMBLE only): an update runs on a lane pair, each lane holding one side of two constraints; described where
-// it is written, before the kernel.
+// it is written, before the kernel.  CHAIN (PAIR only): where the pair's two constraints are consecutive updates of the
+// same two bodies, the steady loop hands their accumulators from the first update to the second in registers.
 #include <algorithm>
 
 #include "kernels.h"
@@ -222,8 +223,13 @@ __device__ __forceinline__ int timetable_end(int depth, int P, int sweeps, int r
 // by compiling every count.  Six spill 12 to 20 bytes in every one of the four.
 constexpr int kPairHeldFree[2] = {5, 5};    // store-free: GS, backward SOR
 constexpr int kPairHeldStore[2] = {5, 5};   // storing
-template <int METHOD, bool STORE_SYSTEM>
+// ... and in the CHAIN form (below), whose steady loop carries a pair's six accumulators across a barrier: five spill
+// 20 (GS) and 28 bytes (backward SOR), four 12 bytes in backward SOR
+constexpr int kPairHeldChainFree[2] = {4, 3};
+constexpr int kPairHeldChainStore[2] = {4, 3};
+template <int METHOD, bool STORE_SYSTEM, bool CHAIN>
 constexpr int pair_products() {
+  if (CHAIN) return STORE_SYSTEM ? kPairHeldChainStore[METHOD - 1] : kPairHeldChainFree[METHOD - 1];
   return STORE_SYSTEM ? kPairHeldStore[METHOD - 1] : kPairHeldFree[METHOD - 1];
 }
 
@@ -262,11 +268,13 @@ struct PairSide {
 
 // One update of a pair's constraint on both lanes.  own: this lane holds the constraint's scalars (c, x); BCAST: the
 // quad_perm that hands the owner's value to both; GENERAL: the update may be the accumulation (sweep 0: dx = x).
-template <int METHOD, int BCAST, bool GENERAL, int HELD>
-__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, bool has, bool own, const Cons<double> &c,
-                                          double (&x)[3], int sweep, double cfm) {
-  double a[6], dx[3];
-  load6(ac, a);
+// a: this lane's side's accumulator.  LOAD: read from LDS first; otherwise the caller hands it over in registers, as
+// the pair's previous update left it.  STORE: written back to LDS; otherwise it stays in a for the pair's next update.
+template <int METHOD, int BCAST, bool GENERAL, bool LOAD, bool STORE, int HELD>
+__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, double (&a)[6], bool has, bool own,
+                                          const Cons<double> &c, double (&x)[3], int sweep, double cfm) {
+  double dx[3];
+  if constexpr (LOAD) load6(ac, a);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     const double h = S.half_dot(r, a);
@@ -287,8 +295,15 @@ __device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, bool h
   for (int r = 0; r < 3; ++r) dx[r] = dpp_all<BCAST>(dx[r]);
   if (has) {
     S.acc_add(a, dx);
-    store6(ac, a);
+    if constexpr (STORE) store6(ac, a);
   }
+}
+// ... from LDS to LDS
+template <int METHOD, int BCAST, bool GENERAL, int HELD>
+__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, bool has, bool own, const Cons<double> &c,
+                                          double (&x)[3], int sweep, double cfm) {
+  double a[6];
+  pair_pass<METHOD, BCAST, GENERAL, true, true>(S, ac, a, has, own, c, x, sweep, cfm);
 }
 
 // lambda and w = A x - rhs of a pair's constraint, written by its owner
@@ -308,7 +323,17 @@ __device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const 
   }
 }
 
-template <int METHOD, bool STORE_SYSTEM>
+// CHAIN (plans that are Plan::chained, plan.h; solve.cpp launches it on no other): A and B of a thread pair are
+// consecutive updates of the same two bodies, so both lanes have ONE accumulator address for the two, and in the steady
+// window the pair's first update (A forward, B in backward SOR) is due at even steps and its second at the step after
+// (plan.cpp derives it).  The steady loop then walks two steps per iteration: the first's pass reads the accumulators
+// and stores nothing, the second's takes them from the first's registers and stores.  Nothing else in the tile touches
+// the two bodies in between (per body the timetable runs one update per step), so LDS holds the same doubles at every
+// point where another lane reads them: the same bits.  A pair with an A and no B reads and stores in A's own step.
+// The barrier between the two steps of an iteration stays, although on such a plan it orders nothing (the lanes due at
+// steps 2 j and 2 j + 1 are the firsts and seconds of the same pairs): without it the step measured no faster
+// (DESIGN.md section 5).
+template <int METHOD, bool STORE_SYSTEM, bool CHAIN>
 __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsigned char *smem) {
   constexpr int BLOCK = 256;
   const int tid = (int)threadIdx.x, tile = blockIdx.x;
@@ -334,6 +359,7 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
     activeB = side ? active : other;
     acA = lds_addr(s_acc + (side ? theirs : mine) * 6);
     acB = lds_addr(s_acc + (side ? mine : theirs) * 6);
+    if constexpr (CHAIN) acB = acA;   // the same two bodies wherever B is active, and unused where it is not
   }
   const unsigned ac_world = lds_addr(s_acc);   // slot 0: no body on this side
 
@@ -356,7 +382,7 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
     for (int r = 0; r < 3; ++r) x[r] = c.rhs[r];
   }
   // the sides change hands once: the even lane gives A's side 1 for B's side 0
-  constexpr int HELD = pair_products<METHOD, STORE_SYSTEM>();
+  constexpr int HELD = pair_products<METHOD, STORE_SYSTEM, CHAIN>();
   PairSide<HELD> SA, SB;
 #pragma unroll
   for (int k = 0; k < 18; ++k) {
@@ -387,6 +413,12 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
     const int ds = __builtin_amdgcn_readfirstlane(depth), t0s = METHOD == 2 ? ds : 0;
     t_s = grid_acc ? ds : t0s + ds - 1;
     t_e = min(t0s + Ps * (A.sweeps + grid_acc), t_end);
+    if constexpr (CHAIN) {
+      // whole pairs of steps from an even one (the period is even: a step's parity is its phase's): an odd t_s leaves
+      // one more step to the fill, an odd length one more to the drain -- both loops take any step of the timetable
+      t_s += t_s & 1;
+      t_e -= (t_e - t_s) & 1;
+    }
     if (t_e <= t_s) t_s = t_e = 0;
   }
   int t = 0, stop = t_e > t_s ? t_s : t_end;
@@ -406,16 +438,47 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
       __builtin_amdgcn_s_barrier();
     }
     if (t >= t_end) break;
-    // steady: the two passes as two code copies, each behind one compare of the constraint's phase with the clock's
-    const int phaseA = activeA ? ((METHOD == 2) ? t0 + depth - 1 - levelA : levelA) % Ps : -1;
-    const int phaseB = activeB ? ((METHOD == 2) ? t0 + depth - 1 - levelB : levelB) % Ps : -1;
-    int tp = t % Ps;
-    for (; t < t_e; ++t) {
-      if (phaseA == tp) pair_pass<METHOD, kQuadEven, false>(SA, acA, acA != ac_world, ownA, c, x, 1, A.cfm);
-      if (phaseB == tp) pair_pass<METHOD, kQuadOdd, false>(SB, acB, acB != ac_world, ownB, c, x, 1, A.cfm);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      tp = tp + 1 == Ps ? 0 : tp + 1;
+    if constexpr (CHAIN) {
+      // steady, two steps per iteration behind one compare: the even phase of the pair's first update with the clock's
+      const int bA = (METHOD == 2) ? t0 + depth - 1 - levelA : levelA;
+      const int phF = activeA ? (bA % Ps) & ~1 : -1;   // backward, A is the second: its phase is odd, B's one less
+      const bool has = acA != ac_world;
+      int tp = t % Ps;
+      double a[6];
+      for (; t < t_e; t += 2) {
+        const bool go = phF == tp;
+        if constexpr (METHOD == 1) {
+          if (go) {
+            pair_pass<METHOD, kQuadEven, false, true, false>(SA, acA, a, has, ownA, c, x, 1, A.cfm);
+            if (!activeB && has) store6(acA, a);   // an A without a B
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // that store
+          __builtin_amdgcn_s_barrier();
+          if (go && activeB) pair_pass<METHOD, kQuadOdd, false, false, true>(SB, acA, a, has, ownB, c, x, 1, A.cfm);
+        } else {
+          if (go && activeB) pair_pass<METHOD, kQuadOdd, false, true, false>(SB, acA, a, has, ownB, c, x, 1, A.cfm);
+          __builtin_amdgcn_s_barrier();   // nothing was stored in this step
+          if (go) {
+            if (!activeB) load6(acA, a);   // an A without a B
+            pair_pass<METHOD, kQuadEven, false, false, true>(SA, acA, a, has, ownA, c, x, 1, A.cfm);
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        tp = tp + 2 == Ps ? 0 : tp + 2;
+      }
+    } else {
+      // steady: the two passes as two code copies, each behind one compare of the constraint's phase with the clock's
+      const int phaseA = activeA ? ((METHOD == 2) ? t0 + depth - 1 - levelA : levelA) % Ps : -1;
+      const int phaseB = activeB ? ((METHOD == 2) ? t0 + depth - 1 - levelB : levelB) % Ps : -1;
+      int tp = t % Ps;
+      for (; t < t_e; ++t) {
+        if (phaseA == tp) pair_pass<METHOD, kQuadEven, false>(SA, acA, acA != ac_world, ownA, c, x, 1, A.cfm);
+        if (phaseB == tp) pair_pass<METHOD, kQuadOdd, false>(SB, acB, acB != ac_world, ownB, c, x, 1, A.cfm);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        tp = tp + 1 == Ps ? 0 : tp + 1;
+      }
     }
     // drain: each constraint's next update at or after t_e, from its level (read again: not held through the window)
     const int lvA = A.lane_level[(size_t)tile * BLOCK + laneA], lvB = A.lane_level[(size_t)tile * BLOCK + laneB];
@@ -442,11 +505,11 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
 // FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
 // ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
-          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false>
+          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false, bool CHAIN = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if constexpr (PAIR) {   // ASSEMBLE, fp64, 256-lane tiles (launch_step_solve_assemble)
-    pair_step_solve<METHOD, STORE_SYSTEM>(A, smem);
+    pair_step_solve<METHOD, STORE_SYSTEM, CHAIN>(A, smem);
     return;
   }
   constexpr int WAVES = BLOCK / 64;
@@ -697,13 +760,13 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 namespace {
-template <bool STORE_SYSTEM, bool PAIR>
+template <bool STORE_SYSTEM, bool PAIR, bool CHAIN = false>
 void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
   // the accumulators; the storing form stages its blocks in the same LDS first
   size_t lds = (size_t)b.max_slots * 6 * sizeof(double);
   if (STORE_SYSTEM) lds = std::max(lds, (size_t)4 * kStageWave * sizeof(double));
-  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR>;
-  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR>;
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
@@ -711,10 +774,14 @@ void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_
 }
 }  // namespace
 
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, hipStream_t s) {
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
+                                hipStream_t s) {
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
-  if (store_system) {
+  if (pair && chain) {
+    if (store_system) launch_step_solve_assemble_t<true, true, true>(b, method, n_tiles, s);
+    else launch_step_solve_assemble_t<false, true, true>(b, method, n_tiles, s);
+  } else if (store_system) {
     if (pair) launch_step_solve_assemble_t<true, true>(b, method, n_tiles, s);
     else launch_step_solve_assemble_t<true, false>(b, method, n_tiles, s);
   } else {

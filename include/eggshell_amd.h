@@ -106,10 +106,16 @@ typedef enum {
   EGS_SCHED_START = 1024,          /* the solve started from a given x0 (egs_problem_set_start), not from rhs */
   EGS_SCHED_FRICTION = 2048,       /* the launch ran the kernels' friction forms (egs_problem_set_friction,
                                       egs_world_set_friction): tangential bounds +-mu x_n.  Clear with friction off */
-  EGS_SCHED_PAIR = 4096            /* the EGS_SCHED_FUSED_ASSEMBLY launch ran each update on a lane pair: two threads
+  EGS_SCHED_PAIR = 4096,           /* the EGS_SCHED_FUSED_ASSEMBLY launch ran each update on a lane pair: two threads
                                       hold one side each of two constraints (plans whose half-wavefronts each hold one
                                       phase of the timetable, a pile of columns).  The same bits as one lane per
                                       constraint; EGS_STEP_PAIR=0 switches it off */
+  EGS_SCHED_CHAIN = 8192           /* ... whose steady loop (EGS_STEP_STEADY) keeps the pair's two bodies'
+                                      accumulators in registers from the first of the pair's two updates to the second
+                                      (plans whose pairs hold consecutive contacts of the same two bodies:
+                                      egs_debug_plan_chained).  The same bits; EGS_STEP_CHAIN=0 switches it off.
+                                      A refinement of EGS_SCHED_PAIR: egs_problem_get_schedule reports it,
+                                      egs_solve_stats.schedule does not (its bits stay those of the pair launch) */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -300,6 +306,9 @@ egs_status egs_problem_advance(egs_problem *p, double dt);
 egs_status egs_problem_get_state(egs_problem *p, double *pos, double *R, double *v, double *w);
 /* fills stats->residual/iterations of the last solve (synchronises) */
 egs_status egs_problem_get_stats(egs_problem *p, egs_solve_stats *stats);
+/* The egs_schedule_flags of the last GS / SOR solve: the bits of egs_solve_stats.schedule and, with them, the
+ * refinements that field leaves out (EGS_SCHED_CHAIN).  Host only: no synchronisation, no residual. */
+egs_status egs_problem_get_schedule(egs_problem *p, int32_t *schedule);
 
 /* ---- entry 3: replaces Lcp::MixedConstraintsSolver(A, b, C, x_lo, x_hi, x, w)
  *      lcp.h:21-23 / lcp.cc:276-336 (and Lcp::MurtyPrincipalPivot,
@@ -874,6 +883,14 @@ egs_status egs_debug_plan_timetable(int32_t n_bodies, int32_t m, const int32_t *
  * step launch asks of a plan before it runs an update on a lane pair (EGS_SCHED_PAIR).                              */
 egs_status egs_debug_plan_pairable(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
                                    int32_t *pairable);
+
+/* Host only: *chained = 1 if that plan is pairable, every tile's period is even, and the two constraints of every
+ * thread pair of the lane-pair form -- A = lane 64 w + l and B = lane 64 w + 32 + l of a tile, l < 32 -- are consecutive
+ * updates of the same two bodies: no B without an A, level[A] even, and where both exist the same two LDS slots and
+ * level[B] = level[A] + 1.  What the step launch asks before it keeps a pair's accumulators in registers from the
+ * first of the two updates to the second (EGS_SCHED_CHAIN).                                                        */
+egs_status egs_debug_plan_chained(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                  int32_t *chained);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
