@@ -55,6 +55,7 @@ EXPORTS = [
     "egs_update_contacts_shapes", "egs_world_set_shapes",
     "egs_mixed_friction_solve_batch", "egs_problem_set_dense_friction", "egs_problem_dense_friction_info",
     "egs_world_set_dense_friction", "egs_world_dense_friction_info",
+    "egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass",
 ]
 
 
@@ -99,6 +100,11 @@ def load():
             _lib.egs_mixed_friction_solve_batch.restype = C.c_int
             for name in ("egs_problem_set_dense_friction", "egs_world_set_dense_friction"):
                 getattr(_lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_double]
+        if hasattr(_lib, "egs_problem_set_live_inertia"):
+            # handle, inertia_body, torque / handle, Minv, f_ext
+            for name in ("egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass"):
+                getattr(_lib, name).argtypes = [C.c_void_p] * 3
+                getattr(_lib, name).restype = C.c_int
     return _lib
 
 
@@ -116,6 +122,16 @@ def _i32(a):
 
 def _u8(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _live_arrays(n, inertia_body, torque):
+    """The two pointers of the set_live_inertia entries, shapes checked: [n][9] (or [n][3][3]) and [n][3]."""
+    Ib, tq = _f64(inertia_body), _f64(torque)
+    if Ib is not None and Ib.size != 9 * n:
+        raise ValueError("inertia_body has %d entries for %d bodies" % (Ib.size, n))
+    if tq is not None and (Ib is None or tq.size != 3 * n):
+        raise ValueError("torque needs inertia_body and 3 entries for each of the %d bodies" % n)
+    return _p(Ib), _p(tq)
 
 
 def debug_plan_patches(n_bodies, body0, body1):
@@ -606,6 +622,18 @@ class Problem:
         a = [_f64(pos), _f64(R), _f64(v), _f64(w), _f64(Minv), _f64(f_ext)]
         self.ctx.check(load().egs_problem_set_state(self.h, *[_p(v_) for v_ in a]))
 
+    def set_live_inertia(self, inertia_body=None, torque=None):
+        """Live inertia (egs_problem_set_live_inertia): body-frame inertias [n][3][3] and an optional applied torque
+        [n][3]; every stepping entry then recomputes M^-1 and the gyroscopic torque of the bodies whose inertia is not
+        a multiple of the identity from the R and w the device holds.  None turns it off."""
+        self.ctx.check(load().egs_problem_set_live_inertia(self.h, *_live_arrays(self.n, inertia_body, torque)))
+
+    def mass(self):
+        """Minv [n][36] and f_ext [n][6] as the device holds them (egs_problem_get_mass)."""
+        Minv = np.zeros((self.n, 36)); f_ext = np.zeros((self.n, 6))
+        self.ctx.check(load().egs_problem_get_mass(self.h, _p(Minv), _p(f_ext)))
+        return Minv, f_ext
+
     def set_constraints(self, kind, data):
         kind, data = _i32(kind), _f64(data)
         self.ctx.check(load().egs_problem_set_constraints(self.h, _p(kind), _p(data)))
@@ -872,6 +900,17 @@ class World:
         side = _f64(np.tile([0.3, 0.3, 0.3], (self.n, 1)) if side is None else side)
         a = [_f64(pos), _f64(R), _f64(v), _f64(w), _f64(Minv), _f64(f_ext), side]
         self.ctx.check(load().egs_world_set_bodies(self.h, *[_p(x) for x in a]))
+
+    def set_live_inertia(self, inertia_body=None, torque=None):
+        """Live inertia (egs_world_set_live_inertia): as Problem.set_live_inertia, global body indices in a batched
+        world.  None turns it off."""
+        self.ctx.check(load().egs_world_set_live_inertia(self.h, *_live_arrays(self.n, inertia_body, torque)))
+
+    def mass(self):
+        """Minv [n][36] and f_ext [n][6] as the device holds them (egs_world_get_mass)."""
+        Minv = np.zeros((self.n, 36)); f_ext = np.zeros((self.n, 6))
+        self.ctx.check(load().egs_world_get_mass(self.h, _p(Minv), _p(f_ext)))
+        return Minv, f_ext
 
     def set_shapes(self, shape):
         """A shape per body, SHAPE_BOX / SHAPE_SPHERE [n] (egs_world_set_shapes); None switches back to boxes.  A

@@ -165,6 +165,7 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
     egs_context *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     if (stall_seen(p)) return report_stall(p);
+    refresh_live_mass(p);
     do_assemble(p, dt, erp);                                  // J, err, bounds, rhs (ensembles.cc:565-570)
     if (p->m == 0) {                                           // v_dot = M^-1 f (ensembles.cc:504-505)
       zero_accumulators(p);

@@ -112,9 +112,16 @@ struct GlobalArgs {
 };
 
 
-// Wf[b] = M_b^-1 f_ext,b: both frozen at Init (Q5), so assembly and the velocity update read
-// these 48 B per body instead of the 288 B block and the force (same expression, same bits).
+// Wf[b] = M_b^-1 f_ext,b: both frozen at Init (Q5) unless live inertia is on, so assembly and the velocity update
+// read these 48 B per body instead of the 288 B block and the force (same expression, same bits).
 void launch_mass_times_force(int n, const double *Minv, const double *f_ext, double *Wf, hipStream_t s);
+// Live inertia (egs_problem_set_live_inertia): for every body b with live_mask[b] != 0, from R [n][9], w [n][3] and
+// inertia_body [n][9], the angular 3x3 of Minv[b] (fp64) and of Minv_r[b] (its (REAL) conversion), f_ext[b][3:6] =
+// torque[b] + gyroscopic torque (torque NULL: the gyroscopic torque alone) and Wf[b], with the bits of
+// orc_minv_blocks / orc_external_force / mass_times_force_kernel.  Other bodies are neither read nor written.
+template <typename REAL>
+void launch_live_mass(int n, const double *R, const double *w, const double *inertia_body, const double *torque,
+                      const uint8_t *live_mask, double *Minv, REAL *Minv_r, double *f_ext, double *Wf, hipStream_t s);
 template <typename REAL>
 void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
                        int block, hipStream_t s);

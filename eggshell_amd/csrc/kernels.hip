@@ -480,6 +480,76 @@ __global__ void __launch_bounds__(256) mass_times_force_kernel(int n, const doub
   Wf[e] = ((((M[0] * f[0] + M[1] * f[1]) + M[2] * f[2]) + M[3] * f[3]) + M[4] * f[4]) + M[5] * f[5];
 }
 
+// Live inertia: what Ensemble::Init (ensembles.cc:202-222) would compute at the R and w the
+// device holds now, for every body the mask selects (inertia_body not a multiple of the identity).  One lane per body.
+// Operation order is that of orc_minv_blocks / orc_external_force (oracle/model.c) with mat3_inv (oracle/linalg.h):
+// I_g = (R I_b) R^T, its inverse by cofactors, the gyroscopic torque ((-[w]x) I_g) w.  The lane writes the angular
+// 3x3 of its fp64 block and of the working-precision one (the (REAL) of the fp64 value, as convert_kernel gives),
+// f_ext[3:6] (+ torque[b] where an applied torque is given) and its six rows of Wf in mass_times_force_kernel's
+// expression.  The linear rows of M^-1 and f_ext are read, never written.
+template <typename REAL>
+__global__ void __launch_bounds__(256) live_mass_kernel(int n, const double *R, const double *w, const double *inertia_body,
+                                                        const double *torque, const uint8_t *live_mask, double *Minv,
+                                                        REAL *Minv_r, double *f_ext, double *Wf) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n || !live_mask[b]) return;
+  double Rb[9], Ib[9], wb[3], RI[9], Rt[9], Ig[9], cm[9], t[9], tq[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { Rb[k] = R[(size_t)b * 9 + k]; Ib[k] = inertia_body[(size_t)b * 9 + k]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) wb[k] = w[(size_t)b * 3 + k];
+  mm3(Rb, Ib, RI);   // body.h:58: R I R^T
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rt[3 * i + j] = Rb[3 * j + i];
+  mm3(RI, Rt, Ig);
+  double *M = Minv + (size_t)b * 36;
+  REAL *Mr = Minv_r + (size_t)b * 36;
+  {  // mat3_inv
+    const double c00 = Ig[4] * Ig[8] - Ig[5] * Ig[7];
+    const double c10 = Ig[5] * Ig[6] - Ig[3] * Ig[8];
+    const double c20 = Ig[3] * Ig[7] - Ig[4] * Ig[6];
+    const double det = (Ig[0] * c00 + Ig[1] * c10) + Ig[2] * c20;
+    const double id = 1.0 / det;
+    double inv[9];
+    inv[0] = c00 * id;
+    inv[1] = (Ig[2] * Ig[7] - Ig[1] * Ig[8]) * id;
+    inv[2] = (Ig[1] * Ig[5] - Ig[2] * Ig[4]) * id;
+    inv[3] = c10 * id;
+    inv[4] = (Ig[0] * Ig[8] - Ig[2] * Ig[6]) * id;
+    inv[5] = (Ig[2] * Ig[3] - Ig[0] * Ig[5]) * id;
+    inv[6] = c20 * id;
+    inv[7] = (Ig[1] * Ig[6] - Ig[0] * Ig[7]) * id;
+    inv[8] = (Ig[0] * Ig[4] - Ig[1] * Ig[3]) * id;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        M[6 * (3 + r) + 3 + c] = inv[3 * r + c];
+        Mr[6 * (3 + r) + 3 + c] = (REAL)inv[3 * r + c];
+      }
+  }
+  crossmat(wb, cm);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cm[k] = -1.0 * cm[k];
+  mm3(cm, Ig, t);
+  mv3(t, wb, tq);
+  double f[6];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    f[k] = f_ext[(size_t)b * 6 + k];
+    f[3 + k] = torque ? torque[(size_t)b * 3 + k] + tq[k] : tq[k];
+    f_ext[(size_t)b * 6 + 3 + k] = f[3 + k];
+  }
+  // the block as it stands now: its own stores above are visible to the lane that made them
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double *Mrow = M + 6 * r;
+    Wf[(size_t)b * 6 + r] = ((((Mrow[0] * f[0] + Mrow[1] * f[1]) + Mrow[2] * f[2]) + Mrow[3] * f[3]) + Mrow[4] * f[4]) + Mrow[5] * f[5];
+  }
+}
+
 // StepPositions_ODE (ensembles.cc:577-591): p += dt (v + v_new)/2,
 // R = Q(dt (w + w_new)/2) R with Q = WtoQ (utils.cc:82-89); then the new
 // velocities become the body state for the next step.
@@ -993,6 +1063,14 @@ void launch_mass_times_force(int n, const double *Minv, const double *f_ext, dou
   hipLaunchKernelGGL(mass_times_force_kernel, dim3((6 * n + 255) / 256), dim3(256), 0, s, n, Minv, f_ext, Wf);
 }
 
+template <typename REAL>
+void launch_live_mass(int n, const double *R, const double *w, const double *inertia_body, const double *torque,
+                      const uint8_t *live_mask, double *Minv, REAL *Minv_r, double *f_ext, double *Wf, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL((live_mass_kernel<REAL>), dim3((n + 255) / 256), dim3(256), 0, s, n, R, w, inertia_body, torque,
+                     live_mask, Minv, Minv_r, f_ext, Wf);
+}
+
 void launch_advance(int n, const BodyState &in, const BodyState &out, const double *v6, double dt, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(advance_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, in, out, v6, dt);
@@ -1106,6 +1184,8 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_velocity_each<REAL>(int, const double *, const double *, const double *, const REAL *,      \
                                            const int32_t *, const double *, double *, hipStream_t);                 \
   template void launch_convert_minv<REAL>(int, const double *, REAL *, hipStream_t);                         \
+  template void launch_live_mass<REAL>(int, const double *, const double *, const double *, const double *,  \
+                                       const uint8_t *, double *, REAL *, double *, double *, hipStream_t);  \
   template void launch_fill_friction<REAL>(int, int, const int32_t *, const int32_t *, const int32_t *,      \
                                            const double *, REAL *, hipStream_t);                             \
   template void launch_minv_iso<REAL>(int, const REAL *, int *, hipStream_t);                               \

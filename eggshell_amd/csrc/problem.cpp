@@ -2,6 +2,7 @@
 // mass blocks, the sticky stall flag, assembly and velocity update, the stand-alone mat-vec, and the egs_problem_*
 // entries of the C ABI with the stateless egs_solve_blocks / egs_matvec_blocks on top of them.
 #include <chrono>
+#include <cmath>
 
 #include "matvec.h"
 #include "policy.h"
@@ -177,11 +178,74 @@ void ensure_minv_real(egs_problem *p) {
     with_real(p, [&](auto r) { using REAL = decltype(r); launch_minv_iso<REAL>(p->n, real<REAL>(p->Minv_r), scratch, s); });
     HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const bool iso = flag != 0;
+    // live inertia rewrites the angular blocks of its bodies every step: whatever the upload held, they are not isotropic
+    const bool iso = flag != 0 && !p->live_any;
     if (iso != p->minv_iso) p->tile_plan_ready = false;   // the preferred tile size depends on it
     p->minv_iso = iso;
   }
   decide_linsym_bodies(p);
+}
+
+void refresh_live_mass(egs_problem *p) {
+  if (!p->live_any || p->n <= 0) return;
+  ensure_system(p);      // a deferred system is made from the Wf of the state its step read: before that Wf changes
+  ensure_minv_real(p);   // an upload not converted yet (the one place with a read-back: once per upload, not per step)
+  ensure_wf(p);
+  record_kernel_event(p->ctx, true);
+  with_real(p, [&](auto r) {
+    using REAL = decltype(r);
+    launch_live_mass<REAL>(p->n, p->R.p, p->w.p, p->live_inertia.p, p->live_has_torque ? p->live_torque.p : nullptr,
+                           p->live_mask.p, p->Minv_d.p, real<REAL>(p->Minv_r), p->f_ext.p, p->Wf.p, p->ctx->stream);
+  });
+  record_kernel_event(p->ctx, false);
+  HIPCHK(hipGetLastError());
+}
+
+egs_status set_live_inertia(egs_problem *p, const double *inertia_body, const double *torque) {
+  egs_context *ctx = p->ctx;
+  const size_t n = (size_t)p->n;
+  std::vector<uint8_t> mask(n, 0);
+  bool any = false;
+  for (size_t b = 0; inertia_body && b < n; ++b) {
+    const double *I = inertia_body + 9 * b;
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(I[k])) return fail(ctx, EGS_ERR_INVALID, "body " + std::to_string(b) + ": non-finite inertia_body");
+    for (int k = 0; torque && k < 3; ++k)
+      if (!std::isfinite(torque[3 * b + k])) return fail(ctx, EGS_ERR_INVALID, "body " + std::to_string(b) + ": non-finite torque");
+    if (I[1] != I[3] || I[2] != I[6] || I[5] != I[7])
+      return fail(ctx, EGS_ERR_INVALID, "body " + std::to_string(b) + ": inertia_body is not symmetric");
+    // Sylvester: the three leading minors
+    const double m2 = I[0] * I[4] - I[1] * I[3];
+    const double m3 = (I[0] * (I[4] * I[8] - I[5] * I[7]) + I[1] * (I[5] * I[6] - I[3] * I[8])) + I[2] * (I[3] * I[7] - I[4] * I[6]);
+    if (!(I[0] > 0) || !(m2 > 0) || !(m3 > 0))
+      return fail(ctx, EGS_ERR_INVALID, "body " + std::to_string(b) + ": inertia_body is not positive definite");
+    const bool multiple = I[1] == 0 && I[2] == 0 && I[5] == 0 && I[0] == I[4] && I[0] == I[8];   // a I_3: skipped
+    mask[b] = multiple ? 0 : 1;
+    any |= !multiple;
+  }
+  return guarded(ctx, [&]() -> egs_status {
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));   // a step in flight may still read the old arrays
+    const bool was = p->live_any;
+    if (any) {
+      p->live_inertia.alloc(n * 9); p->live_mask.alloc(n);
+      upload(p->live_inertia, inertia_body, n * 9, s);
+      upload(p->live_mask, mask.data(), n, s);
+      if (torque) { p->live_torque.alloc(n * 3); upload(p->live_torque, torque, n * 3, s); }
+      p->live_has_torque = torque != nullptr;
+      p->live_any = true;
+      if (p->minv_iso) {   // once: the isotropic schedules are not for these blocks, and the tile size follows
+        p->minv_iso = false;
+        p->tile_plan_ready = false;
+        p->linsym_bodies = 0;
+      }
+    } else {
+      p->live_any = false;
+      p->live_has_torque = false;
+      if (was) p->minv_r_valid = false;   // the blocks stay what the last refresh left: the isotropy check decides again
+    }
+    return EGS_OK;
+  });
 }
 
 // Ball joints that join two bodies are assembled with +0 in J1_lin where J0_lin holds +0 (joints.cc:17-31): their
@@ -633,6 +697,24 @@ egs_status egs_problem_set_mass(egs_problem *p, const double *inv_mass, const do
   });
 }
 
+egs_status egs_problem_set_live_inertia(egs_problem *p, const double *inertia_body, const double *torque) {
+  if (!p) return EGS_ERR_INVALID;
+  return set_live_inertia(p, inertia_body, torque);
+}
+
+egs_status egs_problem_get_mass(egs_problem *p, double *Minv, double *f_ext) {
+  if (!p) return EGS_ERR_INVALID;
+  return guarded(p->ctx, [&]() -> egs_status {
+    const size_t n = (size_t)p->n;
+    hipStream_t s = p->ctx->stream;
+    if (p->have_state) refresh_live_mass(p);   // live inertia: the arrays of the state the device holds now
+    if (Minv && n) HIPCHK(hipMemcpyAsync(Minv, p->Minv_d.p, n * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (f_ext && n) HIPCHK(hipMemcpyAsync(f_ext, p->f_ext.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return EGS_OK;
+  });
+}
+
 egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, const double *data) {
   if (!p) return EGS_ERR_INVALID;
   if (p->m > 0 && (!kind || !data)) return fail(p->ctx, EGS_ERR_INVALID, "NULL constraint descriptors");
@@ -654,7 +736,7 @@ egs_status egs_problem_assemble(egs_problem *p, double dt, double erp) {
   if (!p) return EGS_ERR_INVALID;
   if (!p->have_state || !p->have_constraints) return fail(p->ctx, EGS_ERR_INVALID, "set_state and set_constraints first");
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
-  return guarded(p->ctx, [&]() -> egs_status { do_assemble(p, dt, erp); return EGS_OK; });
+  return guarded(p->ctx, [&]() -> egs_status { refresh_live_mass(p); do_assemble(p, dt, erp); return EGS_OK; });
 }
 
 egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_solve_params *params,
@@ -664,6 +746,7 @@ egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_sol
   if (!(dt > 0)) return fail(p->ctx, EGS_ERR_INVALID, "dt must be > 0");
   return guarded(p->ctx, [&]() -> egs_status {
     if (stall_seen(p)) return report_stall(p);   // an earlier (asynchronous) step timed out
+    refresh_live_mass(p);
     note_assembled(p);   // what choose_sweep reads of the blocks this step makes
     egs_status st;
     if (step_fuses_assembly(p, params)) {

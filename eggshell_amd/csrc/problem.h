@@ -142,6 +142,13 @@ struct egs_problem {
   bool dense_fric_valid = false;
   int dense_fric_solves = 0, dense_fric_converged = 0;
   double dense_fric_change = 0.0;
+  // Live inertia (egs_problem_set_live_inertia): inertia_body [n][9], the applied torque [n][3]
+  // (live_has_torque) and the mask [n] of the bodies whose inertia_body is not a multiple of the identity.  live_any:
+  // the mask selects some body -- then refresh_live_mass launches live_mass_kernel at the start of every stepping entry
+  // and minv_iso stays false (ensure_minv_real); without one the feature changes nothing at all.
+  egs::DevBuf<double> live_inertia, live_torque;
+  egs::DevBuf<uint8_t> live_mask;
+  bool live_any = false, live_has_torque = false;
   bool minv_iso = false;       // every M^-1 block is diag(a,a,a,b,b,b): the tile kernel keeps no B (EGS_ISO=0 disables)
   int last_iterations = 0;
   size_t real_size() const { return precision == EGS_F32 ? sizeof(float) : sizeof(double); }
@@ -166,6 +173,12 @@ egs_status check_topology(egs_context *ctx, int32_t n, int32_t m, const int32_t 
 void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const int32_t *body1, bool fresh = true);
 void ensure_tile_plan(egs_problem *p);
 void ensure_minv_real(egs_problem *p);
+// Live inertia: M^-1 (fp64 and working precision), f_ext and Wf of the masked bodies from the R and w the device holds
+// now.  One launch, no synchronisation while the caller's M^-1 / f_ext uploads are converted already; a no-op unless
+// live_any.  Every stepping entry calls it before anything reads those arrays.
+void refresh_live_mass(egs_problem *p);
+// the checks and the state change of egs_problem_set_live_inertia / egs_world_set_live_inertia
+egs_status set_live_inertia(egs_problem *p, const double *inertia_body, const double *torque);
 void note_kinds(egs_problem *p, const int32_t *kind);
 void note_assembled(egs_problem *p);
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp);

@@ -613,6 +613,7 @@ egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *
   return guarded(w->ctx, [&]() -> egs_status {
     hipStream_t s = w->ctx->stream;
     PhaseTimer lap{w, w->t_phase, /*sync=*/false};
+    refresh_live_mass(w->prob);   // live inertia: M^-1, f_ext and Wf of the state this step starts from (a free body reads Wf too)
     EnsembleRates rates;
     if (dt_each) rates = world_send_rates(w, dt_each, erp_each);
     const EnsembleRates *each = dt_each ? &rates : nullptr;
@@ -676,6 +677,7 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
   w->last_dense = false;
   return guarded(w->ctx, [&]() -> egs_status {
     hipStream_t s = w->ctx->stream;
+    refresh_live_mass(w->prob);   // as world_step_sweeps
     EnsembleRates rates;
     if (dt_each) rates = world_send_rates(w, dt_each, erp_each);
     const EnsembleRates *each = dt_each ? &rates : nullptr;
@@ -904,6 +906,22 @@ egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R
     w->have_bodies = true;
     return EGS_OK;
   });
+}
+
+egs_status egs_world_set_live_inertia(egs_world *w, const double *inertia_body, const double *torque) {
+  if (!w) return EGS_ERR_INVALID;
+  egs_status made = guarded(w->ctx, [&]() -> egs_status {   // valid before egs_world_set_bodies, as set_bodies itself is
+    if (!w->prob) world_make_problem(w, w->jb0.data(), w->jb1.data(), (int)w->jb0.size());
+    return EGS_OK;
+  });
+  if (made != EGS_OK) return made;
+  return set_live_inertia(w->prob, inertia_body, torque);
+}
+
+egs_status egs_world_get_mass(egs_world *w, double *Minv, double *f_ext) {
+  if (!w) return EGS_ERR_INVALID;
+  if (!w->have_bodies) return fail(w->ctx, EGS_ERR_INVALID, "egs_world_set_bodies first");
+  return egs_problem_get_mass(w->prob, Minv, f_ext);
 }
 
 egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape) {

@@ -445,6 +445,7 @@ Ensemble::~Ensemble() {
 }
 
 void Ensemble::Init() {  // ensembles.cc:24-29
+  if (live_world_ == world_) live_world_ = nullptr;
   if (world_) { egs_world_destroy(world_); world_ = nullptr; }   // M^-1 / f_ext are re-sent to a fresh world
   ConstructMassInertiaMatrixInverse();
   InitializeExternalForceTorqueVector();
@@ -476,6 +477,51 @@ void Ensemble::InitializeExternalForceTorqueVector() {  // ensembles.cc:214-222
       external_force_torque_(6 * i + 3 + k) = tq[k];
     }
   }
+}
+
+// ---- live inertia (SetLiveInertia) ------------------------------------------------------------------------------------
+bool Ensemble::IsMultipleOfIdentity(const Matrix3d &I) {   // the device's skip rule (egs_problem_set_live_inertia)
+  return I.d[1] == 0 && I.d[2] == 0 && I.d[3] == 0 && I.d[5] == 0 && I.d[6] == 0 && I.d[7] == 0 && I.d[0] == I.d[4] &&
+         I.d[0] == I.d[8];
+}
+
+std::vector<double> Ensemble::BodyInertias() const {
+  std::vector<double> Ib((size_t)n_ * 9);
+  for (int i = 0; i < n_; ++i)
+    for (int k = 0; k < 9; ++k) Ib[(size_t)i * 9 + k] = components_[i]->I_b().d[k];
+  return Ib;
+}
+
+void Ensemble::RefreshLiveMassOnHost() {   // what the device's refresh does, by the code of Init() (ensembles.cc:202-222)
+  for (int i = 0; i < n_; ++i) {
+    const auto &b = components_.at(i);
+    if (IsMultipleOfIdentity(b->I_b())) continue;
+    Matrix3d Iinv = b->I_g().inverse();
+    Vector3d tq = ((-1.0 * CrossMat(b->w_g())) * b->I_g()) * b->w_g();
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) M_inverse_(6 * i + 3 + r, 6 * i + 3 + c) = Iinv(r, c);
+      external_force_torque_(6 * i + 3 + r) = tq[r];
+    }
+  }
+}
+
+void Ensemble::PullLiveMass() const {
+  if (!live_inertia_ || !live_world_) return;
+  std::vector<double> Minv((size_t)live_total_ * 36), fext((size_t)live_total_ * 6);
+  egs::check(egs_world_get_mass(live_world_, Minv.data(), fext.data()));
+  for (int i = 0; i < n_; ++i) {
+    const size_t g = (size_t)(live_offset_ + i);
+    for (int r = 0; r < 6; ++r) {
+      for (int c = 0; c < 6; ++c) M_inverse_(6 * i + r, 6 * i + c) = Minv[g * 36 + 6 * r + c];
+      external_force_torque_(6 * i + r) = fext[g * 6 + r];
+    }
+  }
+}
+
+void Ensemble::SetLiveInertia(bool on) {
+  if (!on && live_inertia_) PullLiveMass();   // frozen from here on at what the last step used
+  live_inertia_ = on;
+  if (!on) live_world_ = nullptr;
 }
 
 ConstraintsList Ensemble::CombineConstraintsLists() const {  // ensembles.cc:234-239
@@ -809,6 +855,13 @@ bool Ensemble::StepOnDevice(double dt) {
   if (!(warm_start_ && egs::same_state(world_state_, pos, R, vl, w)))
     egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
                                     first ? external_force_torque_.data() : nullptr, first ? side.data() : nullptr));
+  if (first) world_live_ = false;   // a fresh world has live inertia off
+  if (live_inertia_ != world_live_) {
+    const std::vector<double> Ib = BodyInertias();
+    egs::check(egs_world_set_live_inertia(world_, live_inertia_ ? Ib.data() : nullptr, nullptr));
+    world_live_ = live_inertia_;
+  }
+  live_world_ = live_inertia_ ? world_ : nullptr; live_offset_ = 0; live_total_ = n_;
   if (first)
     if (const std::vector<int32_t> shape = Shapes(); !shape.empty()) egs::check(egs_world_set_shapes(world_, shape.data()));
   // joints are permanent in the reference (ensembles.cc:331-334); a caller that edits them all the same
@@ -882,6 +935,10 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
       throw egs::Error(EGS_ERR_UNSUPPORTED, "COULOMB_PYRAMID steps on the device only: not with use_device_step = false, "
                                             "use_dense_solver, caller-supplied contacts or a joint the device cannot take");
   }
+  if (live_inertia_) {   // the explicit paths read the host's arrays: bring them to the state this step starts from
+    live_world_ = nullptr;   // (no device world holds newer ones after this step)
+    RefreshLiveMassOnHost();
+  }
   const VectorXd v = GetVelocities();
   if (detect_contacts) UpdateContacts();
   CheckAndCorrectEnsembleState();   // ensembles.cc:394
@@ -923,6 +980,8 @@ EnsembleGroup::EnsembleGroup(std::vector<Ensemble *> members) : members_(std::mo
 }
 
 EnsembleGroup::~EnsembleGroup() {
+  for (Ensemble *m : members_)
+    if (world_ && m->live_world_ == world_) m->live_world_ = nullptr;
   if (world_) egs_world_destroy(world_);
 }
 
@@ -1014,6 +1073,28 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   if (!(warm && egs::same_state(world_state_, pos, R, vl, w)))
     egs::check(egs_world_set_bodies(world_, pos.data(), R.data(), vl.data(), w.data(), first ? Minv.data() : nullptr,
                                     first ? fext.data() : nullptr, first ? side.data() : nullptr));
+  {   // the members' live inertia, each its own: the bodies of a member with it off go as the identity, which is skipped
+    std::vector<char> live(E);
+    bool any = false;
+    for (size_t i = 0; i < E; ++i) { live[i] = members_[i]->live_inertia_ ? 1 : 0; any = any || live[i]; }
+    if (first) world_live_.assign(E, 0);
+    if (live != world_live_) {
+      std::vector<double> Ib(n * 9, 0.0);
+      for (size_t g = 0; g < n; ++g) Ib[9 * g] = Ib[9 * g + 4] = Ib[9 * g + 8] = 1.0;
+      for (size_t i = 0; i < E; ++i) {
+        if (!live[i]) continue;
+        const std::vector<double> own = members_[i]->BodyInertias();
+        std::copy(own.begin(), own.end(), Ib.begin() + 9 * (size_t)off_[i]);
+      }
+      egs::check(egs_world_set_live_inertia(world_, any ? Ib.data() : nullptr, nullptr));
+      world_live_ = live;
+    }
+    for (size_t i = 0; i < E; ++i) {
+      Ensemble *m = members_[i];
+      if (live[i]) { m->live_world_ = world_; m->live_offset_ = off_[i]; m->live_total_ = (int)n; }
+      else if (m->live_world_ == world_) m->live_world_ = nullptr;
+    }
+  }
   if (first) {   // the members' shapes, with the side lengths; none sent when every Body of every member is a box
     std::vector<int32_t> shape(n, EGS_SHAPE_BOX);
     bool any = false;

@@ -299,7 +299,18 @@ class Ensemble {  // ensembles.h:25-186
   enum struct RelaxationSolver { Sweep = 0, Direct };
   void SetRelaxationSolver(RelaxationSolver solver) { relaxation_solver_ = solver; }
   int last_relaxation_rank = -1;         // rank of the last Direct solve (-1: none yet)
-  const MatrixXd &M_inverse() const { return M_inverse_; }
+  // M^-1 and the external force / torque vector: as Init() left them (quirk Q5) -- with SetLiveInertia(true) and a
+  // device world, what the device holds for the bodies' current state, read back on demand.
+  const MatrixXd &M_inverse() const { PullLiveMass(); return M_inverse_; }
+  const VectorXd &external_force_torque() const { PullLiveMass(); return external_force_torque_; }
+  // Not in the reference, off by default (Q5 stays the default): M^-1's angular blocks and the gyroscopic torque follow
+  // the bodies (egs_world_set_live_inertia, with every Body's I_b()): each Step recomputes, from the R and w it starts
+  // from, what Init() would compute at that state, for every Body whose I_b() is not a multiple of the identity.  The
+  // device step does it on the device; the explicit paths (use_device_step = false, use_dense_solver, caller-supplied
+  // contacts) on the host before StepVelocities_ODE, by Init()'s own code.  Turning it off freezes both at the state of
+  // the last step.
+  void SetLiveInertia(bool on);
+  bool live_inertia() const { return live_inertia_; }
   const ConstraintsList constraints() const { return CombineConstraintsLists(); }
   const ComponentsList &components() const { return components_; }
   void SetContacts(const ContactsList &c) { contacts_ = c; }
@@ -361,11 +372,20 @@ class Ensemble {  // ensembles.h:25-186
   ComponentsList components_;
   JointsList joints_;
   ContactsList contacts_;
-  MatrixXd M_inverse_;
-  VectorXd external_force_torque_;
+  mutable MatrixXd M_inverse_;               // (mutable: PullLiveMass)
+  mutable VectorXd external_force_torque_;
 
  private:
   friend class EnsembleGroup;
+  // SetLiveInertia: asked for; what the device world was last told; the world that last stepped this ensemble with live
+  // inertia on (its own, or an EnsembleGroup's: not owned), the offset of its first body there and that world's bodies
+  bool live_inertia_ = false, world_live_ = false;
+  egs_world *live_world_ = nullptr;
+  int live_offset_ = 0, live_total_ = 0;
+  static bool IsMultipleOfIdentity(const Matrix3d &I);
+  std::vector<double> BodyInertias() const;       // [n][9], every Body's I_b()
+  void RefreshLiveMassOnHost();                   // Init()'s two arrays at the current state, skipped bodies left alone
+  void PullLiveMass() const;                      // live inertia on and a device world: both arrays from egs_world_get_mass
   void ConstructMassInertiaMatrixInverse();                              // ensembles.cc:202-212
   void InitializeExternalForceTorqueVector();                            // ensembles.cc:214-222
   ConstraintsList CombineConstraintsLists() const;                       // ensembles.cc:234-239
@@ -429,6 +449,8 @@ class Cairn : public Ensemble {
 // member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
 // egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
 //   - The members may differ in SetFriction: member i's contacts take its model and coefficient (egs_world_set_friction).
+//   - The members may differ in SetLiveInertia: the state is per body (egs_world_set_live_inertia; the bodies of a member
+//     with it off are sent as the identity, which the device skips).
 //   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts, SetWarmStart and SetDenseFriction, and each must be able to
 //     take the device step (joints that Describe themselves, no caller-supplied contacts); the list may not be empty or
 //     hold a pointer twice: the constructor throws egs::Error(EGS_ERR_INVALID) naming the offending member.
@@ -459,6 +481,7 @@ class EnsembleGroup {
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
   std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)
+  std::vector<char> world_live_;                 // ... and the members' SetLiveInertia (empty: never told, all off)
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last step (warm start only)
 };
 

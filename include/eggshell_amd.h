@@ -273,7 +273,8 @@ egs_status egs_matvec_blocks(egs_context *ctx, int32_t n_bodies, const double *M
  *      (ensembles.cc:569-570) and, after the solve, the velocity update
  *      (ensembles.cc:535, 572).  Body state and constraint descriptors:
  *   pos [n][3], R [n][9] row-major, v [n][3], w [n][3] (global frame),
- *   Minv [n][36], f_ext [n][6]  (ensembles.cc:202-222; frozen at Init, Q5)
+ *   Minv [n][36], f_ext [n][6]  (ensembles.cc:202-222; frozen at Init, Q5 --
+ *                unless egs_problem_set_live_inertia turns live inertia on)
  *   kind [m] (egs_constraint_kind),
  *   data [m][7]: joint   = c0(3), c1(3) (c1 = world point if body1 = -1), 0
  *                contact = position(3), normal(3), depth (collision.h:12-27) */
@@ -286,6 +287,33 @@ egs_status egs_problem_set_state(egs_problem *p, const double *pos,
  * (ensembles.cc:202-212) ever stores; the 6x6 blocks are built from it. */
 egs_status egs_problem_set_mass(egs_problem *p, const double *inv_mass,
                                 const double *inv_inertia);
+/* ---- live inertia: world-frame M^-1 and the gyroscopic torque follow the bodies.  Off by default: the reference
+ * computes both in Ensemble::Init and never again (quirk Q5), and so does this library unless told otherwise here.
+ *   inertia_body [n][9]  body-frame inertia, row-major; NULL turns live inertia off
+ *   torque       [n][3]  an applied torque, world frame; NULL = none
+ * With live inertia on, every stepping entry (egs_problem_assemble, egs_problem_step, egs_problem_step_dense, and
+ * through the world egs_world_step[_each] and egs_world_step_dense[_each]) first recomputes on the device, from the R
+ * and w the device holds AT THE START OF THAT STEP, what Ensemble::Init would compute at that state, for every body b
+ * whose inertia_body[b] is not exactly a I_3 (all off-diagonals exactly 0, the three diagonals equal):
+ *   I_g = (R I_b) R^T;   the angular 3x3 block of Minv[b] = I_g^-1 by cofactors;
+ *   f_ext[b][3:6] = torque[b] + ((-[w]x) I_g) w,
+ * in the operation order of ensembles.cc:202-222 (the bits of the CPU oracle's minv_blocks / external_force), and
+ * with them the device's derived copies (the working-precision M^-1, M^-1 f_ext).  One more launch per step; no
+ * synchronisation, read-back or upload.  The linear rows (1/m, f_ext[b][0:3]) are never touched: they stay the
+ * caller's.  A body whose inertia_body IS a I_3 is skipped -- its Minv and f_ext rows stay what the caller uploaded
+ * (rotation cannot change its world inertia, its gyroscopic torque vanishes) -- so a world of cubes or spheres with live
+ * inertia on is bit for bit the world with it off, on the same schedule.  The refresh depends on the state only: a step
+ * that fails, or an ensemble sitting a step out, leaves the arrays consistent with its unchanged bodies.
+ * While it is on, a later egs_problem_set_state / egs_world_set_bodies that passes Minv / f_ext keeps their linear
+ * rows; the angular parts of the bodies that are not skipped are overwritten at the next step.
+ * EGS_ERR_INVALID, with nothing changed: a non-finite entry, an inertia_body[b] that is not exactly symmetric or not
+ * positive definite (Sylvester's three leading minors).  Turning it off leaves the arrays what the last step made
+ * them. */
+egs_status egs_problem_set_live_inertia(egs_problem *p, const double *inertia_body /*[n][9] or NULL = off*/,
+                                        const double *torque /*[n][3] or NULL*/);
+/* Minv [n][36], f_ext [n][6] as the device holds them (fp64); either may be NULL.  With live inertia on they are first
+ * brought to the state the device holds now (the refresh is idempotent: a step would compute the same). */
+egs_status egs_problem_get_mass(egs_problem *p, double *Minv /*[n][36]*/, double *f_ext /*[n][6]*/);
 egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind,
                                        const double *data);
 /* J, err, bounds, rhs = -(erp/dt^2) err - J (v/dt + Minv f_ext) on device */
@@ -533,7 +561,9 @@ typedef struct egs_world egs_world;
 egs_status egs_world_create(egs_context *ctx, int32_t n_bodies, int32_t precision, egs_world **out);
 void egs_world_destroy(egs_world *w);
 /* pos [n][3], R [n][9], v, w [n][3], Minv [n][36], f_ext [n][6] (frozen as
- * Ensemble::Init leaves them, quirk Q5), side_lengths [n][3] (body.h:91).
+ * Ensemble::Init leaves them, quirk Q5, unless egs_world_set_live_inertia is
+ * on: then their angular parts follow the bodies and only the linear rows
+ * given here are kept), side_lengths [n][3] (body.h:91).
  * The first call needs every array; later calls may pass NULL for any of them
  * to keep what the device holds (typically Minv, f_ext, side_lengths). */
 egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R, const double *v,
@@ -555,6 +585,13 @@ egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v,
 egs_status egs_world_get_contacts(egs_world *w, int32_t max_contacts, int32_t *m_out, int32_t *body0,
                                   int32_t *body1, double *data);
 egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_out, double *lambda);
+/* Live inertia for the world's bodies: egs_problem_set_live_inertia / egs_problem_get_mass (above) with global body
+ * indices in a batched world.  The refresh is the first thing every egs_world_step[_each] and
+ * egs_world_step_dense[_each] enqueues; the stabilise entries work with M = I and do not refresh -- the step after
+ * them does, from the poses they left.  The state is per body, so each ensemble of a batched world holds the bits of
+ * a world created for it alone.  Valid any time after the world is created; get_mass after egs_world_set_bodies. */
+egs_status egs_world_set_live_inertia(egs_world *w, const double *inertia_body, const double *torque);
+egs_status egs_world_get_mass(egs_world *w, double *Minv, double *f_ext);
 
 /* ---- warm start: a step's solve starts from the previous step's lambda instead of rhs (quirk Q7).  Off by default;
  * off, nothing in a step changes.  On, egs_world_step and egs_world_step_each run
