@@ -56,6 +56,7 @@ EXPORTS = [
     "egs_mixed_friction_solve_batch", "egs_problem_set_dense_friction", "egs_problem_dense_friction_info",
     "egs_world_set_dense_friction", "egs_world_dense_friction_info",
     "egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass",
+    "egs_problem_set_restitution", "egs_world_set_restitution",
 ]
 
 
@@ -100,6 +101,9 @@ def load():
             _lib.egs_mixed_friction_solve_batch.restype = C.c_int
             for name in ("egs_problem_set_dense_friction", "egs_world_set_dense_friction"):
                 getattr(_lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_double]
+        if hasattr(_lib, "egs_problem_set_restitution"):
+            _lib.egs_problem_set_restitution.argtypes = [C.c_void_p, C.c_void_p, C.c_double]   # problem, rest, vth
+            _lib.egs_world_set_restitution.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double]   # world, E, rest, vth
         if hasattr(_lib, "egs_problem_set_live_inertia"):
             # handle, inertia_body, torque / handle, Minv, f_ext
             for name in ("egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass"):
@@ -691,6 +695,14 @@ class Problem:
             raise ValueError("mu: %d coefficients for %d constraints" % (mu.size, self.m))
         self.ctx.check(load().egs_problem_set_friction(self.h, _p(mu)))
 
+    def set_restitution(self, rest=None, vth=0.0):
+        """Restitution (egs_problem_set_restitution): one coefficient per constraint, >= 0: a contact approaching faster
+        than vth bounces with it, < 0: assembled as stored.  None, or no coefficient >= 0, turns it off."""
+        rest = _f64(rest)
+        if rest is not None and rest.size != self.m:
+            raise ValueError("rest: %d coefficients for %d constraints" % (rest.size, self.m))
+        self.ctx.check(load().egs_problem_set_restitution(self.h, _p(rest), float(vth)))
+
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
         w = np.zeros(3 * self.m)
@@ -1047,6 +1059,12 @@ class World:
         for a plain world), joints none; mu[e] < 0 keeps the reference's friction box."""
         mu = np.atleast_1d(_f64(mu))
         self.ctx.check(load().egs_world_set_friction(self.h, C.c_int32(mu.shape[0]), _p(mu)))
+
+    def set_restitution(self, rest, vth=0.0):
+        """Restitution per ensemble (egs_world_set_restitution): every contact of ensemble e takes rest[e] (a scalar for a
+        plain world), joints none; rest[e] < 0: that ensemble's contacts do not bounce."""
+        rest = None if rest is None else np.atleast_1d(_f64(rest))
+        self.ctx.check(load().egs_world_set_restitution(self.h, C.c_int32(0 if rest is None else rest.shape[0]), _p(rest), float(vth)))
 
     def set_warm_start(self, enable, match_radius=0.01):
         """Sweep steps start from the previous step's lambda (egs_world_set_warm_start): a contact takes the rows of the

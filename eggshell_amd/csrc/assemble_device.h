@@ -183,6 +183,38 @@ __device__ __forceinline__ double assemble_rhs_t(const AssembleArgs &A, double d
   const double ju = dot6p(j0 + 6 * r, u0) + dot6p(j1 + 6 * r, u1);
   return kk * e[r] - ju;
 }
+// Restitution (egs_problem_set_restitution): the normal row's target t = kk err[2] of contact i, raised to -rest vn / dt
+// where the contact approaches faster than vth.  vn: the separating speed of row 2 from the bodies' (v, w), zeros for
+// a world side.  A joint, a coefficient < 0 and a contact that does not trigger return t itself: the stored bits.
+template <bool EACH>
+__device__ __forceinline__ double restitution_target(const AssembleArgs &A, int i, double dt_each, const double *j0,
+                                                     const double *j1, double t) {
+  if (A.kind[i] == 0) return t;
+  const double rest = A.rest[i];
+  if (!(rest >= 0)) return t;
+  const int b0 = A.body0[i], b1 = A.body1[i];
+  double s0[6], s1[6];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    s0[r] = b0 >= 0 ? (r < 3 ? A.v[(size_t)b0 * 3 + r] : A.w[(size_t)b0 * 3 + r - 3]) : 0.0;
+    s1[r] = b1 >= 0 ? (r < 3 ? A.v[(size_t)b1 * 3 + r] : A.w[(size_t)b1 * 3 + r - 3]) : 0.0;
+  }
+  const double vn = dot6p(j0 + 12, s0) + dot6p(j1 + 12, s1);
+  if (vn < -A.vth) {
+    const double b = (-(rest * vn)) / (EACH ? dt_each : A.dt);
+    if (b > t) t = b;
+  }
+  return t;
+}
+// row 2 of constraint i with restitution (A.rest is set): assemble_rhs_t's, its target raised where the contact bounces
+template <bool EACH>
+__device__ __forceinline__ double assemble_rhs_bounce_t(const AssembleArgs &A, int i, double dt_each, double erp_each,
+                                                        const double *j0, const double *j1, const double *e, const double *u0,
+                                                        const double *u1) {
+  const double kk = EACH ? -erp_each / dt_each / dt_each : -A.erp / A.dt / A.dt;
+  const double ju = dot6p(j0 + 12, u0) + dot6p(j1 + 12, u1);
+  return restitution_target<EACH>(A, i, dt_each, j0, j1, kk * e[2]) - ju;
+}
 __device__ __forceinline__ double assemble_rhs(const AssembleArgs &A, const double *j0, const double *j1, const double *e,
                                                const double *u0, const double *u1, int r) {
   return assemble_rhs_t<false>(A, 0.0, 0.0, j0, j1, e, u0, u1, r);

@@ -3,12 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "plan.h"
 
 namespace egs {
 
-struct AssembleArgs {
+struct AssembleCore {
   int32_t n, m;
   const double *pos, *R, *v, *w;                 // body state, fp64
   const double *Wf;                              // [n][6] M^-1 f_ext (launch_mass_times_force)
@@ -18,6 +19,12 @@ struct AssembleArgs {
   void *J0, *J1, *lo, *hi, *rhs;                 // REAL outputs
   double *err;                                   // [3m] fp64
   uint8_t *is_eq;
+};
+struct AssembleArgs : AssembleCore {
+  // restitution (assemble_device.h: restitution_target): one coefficient per constraint [m], >= 0: a contact's normal
+  // row bounces above the approach speed vth, < 0: as stored.  NULL = off.
+  const double *rest = nullptr;
+  double vth = 0.0;
 };
 // Per-ensemble rates of a step (egs_world_step_each), device tables: body -> ensemble [n], dt [n_ens], erp [n_ens].
 // A constraint takes its first body's ensemble's pair instead of AssembleArgs' dt / erp, a body its ensemble's dt.
@@ -64,8 +71,10 @@ struct SolveArgs {
   int steady = 0;           // 1: step_solve_kernel (GROUP = 1, no snapshots) runs the steady-state loop between the
                             // fill and the drain of its timetable (step_solve.hip)
   // step_solve_kernel's ASSEMBLE form (launch_step_solve_assemble): every lane assembles its constraint from this
-  // body state in the prologue and also leaves the blocks where assemble_kernel would (J0 .. is_eq above point there)
-  AssembleArgs assemble{};
+  // body state in the prologue and also leaves the blocks where assemble_kernel would (J0 .. is_eq above point there).
+  // An fp64 launch only: the fp32 argument block keeps the core alone and with it its size (16 bytes more cost the
+  // fp32 Jacobi tile kernels two VGPRs and a wavefront of occupancy: DESIGN.md section 4j).
+  std::conditional_t<sizeof(REAL) == 8, AssembleArgs, AssembleCore> assemble{};
   // Per-sweep history (tolerance-terminated solves): x after sweep s and each body's
   // accumulator once its last constraint of sweep s has run, s = 1..sweeps of this launch.
   // hist_residual then evaluates the reference's per-iteration stopping test for the
@@ -131,7 +140,8 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles,
 // decides both (solve.cpp: choose_sweep).
 template <typename REAL>
 void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int block, int group, bool linsym, hipStream_t s);
-// the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles, no snapshots):
+// the LINSYM form with the assembly in its prologue (a.assemble; a fresh solve, 256-constraint tiles, no snapshots;
+// a.assemble.rest set: the restitution instantiations, the same sweep behind a prologue that bounces the normal rows):
 // assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit.
 // store_system = false: J0, J1, rhs, lo, hi, err and is_eq are not written (the caller defers them: problem.h)
 // pair: the PAIR form, one update on a lane pair (step_solve.hip); the same bits on any plan, worth it on a pairable one
@@ -228,7 +238,7 @@ void launch_seg_fixed(const EnsembleSegs &S, const EnsembleStop &T, const double
 
 // The per-constraint friction coefficients of a world's list (egs_world_set_friction): constraint i < mj is a joint and
 // gets -1, a contact gets mu_ens[ensemble of its first body] (body_ens == NULL: a plain world, ensemble 0), rounded to
-// REAL.
+// REAL.  The restitution table of egs_world_set_restitution is filled by the same kernel, REAL = double.
 template <typename REAL>
 void launch_fill_friction(int m, int mj, const int32_t *body0, const int32_t *body1, const int32_t *body_ens,
                           const double *mu_ens, REAL *mu, hipStream_t s);

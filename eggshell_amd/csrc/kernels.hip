@@ -639,8 +639,9 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
 // K1-K4 assembly: the per-constraint body lives in assemble_device.h.
 struct NoRates {};   // the scalar form's (empty) second argument
 // EACH: dt and erp per constraint from its ensemble's (T); an ensemble that sits the step out (dt 0) gets rhs rows of
-// exactly 0, its blocks, err, bounds and row types as always.
-template <typename REAL, bool EACH, typename RATES>
+// exactly 0, its blocks, err, bounds and row types as always.  REST: restitution on the normal rows (A.rest is set);
+// an instantiation of its own, so that the launches without it keep their registers.
+template <typename REAL, bool EACH, typename RATES, bool REST>
 __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
   // stores hit 64 lines per instruction; staged, the workgroup writes its 256 x 18 block contiguously
@@ -672,7 +673,10 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   if (!live) return;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_t<EACH>(A, dt, erp, j0, j1, e, u0, u1, r);
+    if (REST && r == 2)
+      rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_bounce_t<EACH>(A, i, dt, erp, j0, j1, e, u0, u1);
+    else
+      rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_t<EACH>(A, dt, erp, j0, j1, e, u0, u1, r);
     A.err[(size_t)i * 3 + r] = e[r];
     loo[(size_t)i * 3 + r] = (REAL)lo[r];
     hio[(size_t)i * 3 + r] = (REAL)hi[r];
@@ -996,13 +1000,17 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 template <typename REAL>
 void launch_assemble(const AssembleArgs &a, hipStream_t s) {
   if (a.m <= 0) return;
-  hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates>), dim3((a.m + 255) / 256), dim3(256), 0, s, a, NoRates{});
+  const dim3 g((a.m + 255) / 256), t(256);
+  if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true>), g, t, 0, s, a, NoRates{});
+  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false>), g, t, 0, s, a, NoRates{});
 }
 
 template <typename REAL>
 void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStream_t s) {
   if (a.m <= 0) return;
-  hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates>), dim3((a.m + 255) / 256), dim3(256), 0, s, a, t);
+  const dim3 g((a.m + 255) / 256), b(256);
+  if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true>), g, b, 0, s, a, t);
+  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false>), g, b, 0, s, a, t);
 }
 
 template <typename REAL>

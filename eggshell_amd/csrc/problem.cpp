@@ -289,6 +289,8 @@ AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
   a.dt = dt; a.erp = erp;
   a.J0 = p->J0.p; a.J1 = p->J1.p; a.lo = p->lo.p; a.hi = p->hi.p; a.rhs = p->rhs.p;
   a.err = p->err.p; a.is_eq = p->is_eq.p;
+  a.rest = p->restitution ? p->rest.p : nullptr;
+  a.vth = p->rest_vth;
   return a;
 }
 
@@ -429,6 +431,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->have_lambda = false;
   if (p->start_mode == EGS_START_GIVEN) p->start_mode = EGS_START_RHS;
   p->friction = false;   // the coefficients were those of the old list (the world refills them: world.cpp)
+  p->restitution = false;   // likewise
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
     const int force = env ? std::atoi(env) : -1;
@@ -641,6 +644,28 @@ egs_status egs_problem_set_friction(egs_problem *p, const double *mu) {
       upload_real(p, p->mu, mu, m);
     }
     p->friction = any;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_restitution(egs_problem *p, const double *rest, double vth) {
+  if (!p) return EGS_ERR_INVALID;
+  if (!(vth >= 0) || std::isinf(vth)) return fail(p->ctx, EGS_ERR_INVALID, "the restitution threshold must be finite and >= 0");
+  const size_t m = (size_t)p->m;
+  bool any = false;
+  for (size_t i = 0; rest && i < m; ++i) {
+    if (rest[i] != rest[i] || std::isinf(rest[i])) return fail(p->ctx, EGS_ERR_INVALID, "NaN or infinite restitution coefficient");
+    any |= rest[i] >= 0;
+  }
+  return guarded(p->ctx, [&]() -> egs_status {
+    ensure_system(p);   // a deferred system is the one of the table its step ran with
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));   // an assembly in flight may still read the old coefficients
+    if (any) {
+      p->rest.alloc(m);
+      upload(p->rest, rest, m, p->ctx->stream);
+    }
+    p->restitution = any;
+    p->rest_vth = vth;
     return EGS_OK;
   });
 }

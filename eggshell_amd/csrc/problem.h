@@ -135,6 +135,13 @@ struct egs_problem {
   // mu.  A new topology turns it off: the coefficients belong to the list they were given for.
   egs::DevBuf<unsigned char> mu;
   bool friction = false;
+  // Restitution (egs_problem_set_restitution, egs_world_set_restitution): rest [m] fp64, one coefficient per constraint,
+  // >= 0: a contact's normal row bounces above the approach speed rest_vth (assemble_device.h: restitution_target), < 0:
+  // assembled as stored.  restitution: some coefficient is >= 0 -- then every assembly takes the table (assemble_args);
+  // off, nothing reads it.  A new topology turns it off, as it does friction (the world refills both).
+  egs::DevBuf<double> rest;
+  bool restitution = false;
+  double rest_vth = 0.0;
   // egs_problem_set_dense_friction: max_outer > 0 makes egs_problem_step_dense solve the pyramid while friction is on
   // (0: it refuses); the outcome of the last such step (egs_problem_dense_friction_info).
   int dense_fric_outer = 0;

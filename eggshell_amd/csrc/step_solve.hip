@@ -151,14 +151,16 @@ __device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, con
 // err, lo, hi and is_eq to global memory where assemble_kernel puts them (24 B per lane and array: a few lines per
 // store instruction), rhs into c.  STORE = false: into c only.  The bounds do not go into c: the sweep of this form
 // projects with a contact's literals.
-template <bool STORE>
+template <bool STORE, bool REST>
 __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, Cons<double> &c) {
   double e[3], lo[3], hi[3], u0[6], u1[6];
   bool eq;
   assemble_one(G, cidx, c.J0, c.J1, e, lo, hi, eq, u0, u1);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    c.rhs[r] = assemble_rhs(G, c.J0, c.J1, e, u0, u1, r);
+    // REST: restitution on the normal row (G.rest is set), here in the prologue only
+    if (REST && r == 2) c.rhs[r] = assemble_rhs_bounce_t<false>(G, cidx, 0.0, 0.0, c.J0, c.J1, e, u0, u1);
+    else c.rhs[r] = assemble_rhs(G, c.J0, c.J1, e, u0, u1, r);
     if constexpr (STORE) {
       reinterpret_cast<double *>(G.rhs)[(size_t)cidx * 3 + r] = c.rhs[r];
       G.err[(size_t)cidx * 3 + r] = e[r];
@@ -333,7 +335,7 @@ __device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const 
 // The barrier between the two steps of an iteration stays, although on such a plan it orders nothing (the lanes due at
 // steps 2 j and 2 j + 1 are the firsts and seconds of the same pairs): without it the step measured no faster
 // (DESIGN.md section 5).
-template <int METHOD, bool STORE_SYSTEM, bool CHAIN>
+template <int METHOD, bool STORE_SYSTEM, bool CHAIN, bool REST>
 __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsigned char *smem) {
   constexpr int BLOCK = 256;
   const int tid = (int)threadIdx.x, tile = blockIdx.x;
@@ -365,7 +367,7 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
 
   Cons<double> c = {};
   double x[3] = {0.0, 0.0, 0.0};
-  if (active) assemble_lane<STORE_SYSTEM>(A.assemble, d.cidx, c);
+  if (active) assemble_lane<STORE_SYSTEM, REST>(A.assemble, d.cidx, c);
   if constexpr (STORE_SYSTEM) {
     stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
     __syncthreads();   // every wavefront has read its staging area back
@@ -505,11 +507,11 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
 // FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
 // ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
-          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false, bool CHAIN = false>
+          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false, bool CHAIN = false, bool REST = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if constexpr (PAIR) {   // ASSEMBLE, fp64, 256-lane tiles (launch_step_solve_assemble)
-    pair_step_solve<METHOD, STORE_SYSTEM, CHAIN>(A, smem);
+    pair_step_solve<METHOD, STORE_SYSTEM, CHAIN, REST>(A, smem);
     return;
   }
   constexpr int WAVES = BLOCK / 64;
@@ -545,7 +547,7 @@ __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(R
   // where x starts: the previous launch's x, a given start (A.x0), or NULL: rhs (Q7; always so in the ASSEMBLE form)
   const REAL *xs = ASSEMBLE ? nullptr : resume ? A.x : A.x0;
   if constexpr (ASSEMBLE) {
-    if (active) assemble_lane<STORE_SYSTEM>(A.assemble, d.cidx, c);
+    if (active) assemble_lane<STORE_SYSTEM, REST>(A.assemble, d.cidx, c);
     if constexpr (STORE_SYSTEM) {
       stage_blocks(A.assemble, reinterpret_cast<double *>(smem) + (tid >> 6) * kStageWave, tid & 63, d.cidx, active, c);
       __syncthreads();   // every wavefront has read its staging area back
@@ -760,17 +762,23 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 namespace {
-template <bool STORE_SYSTEM, bool PAIR, bool CHAIN = false>
-void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
+template <bool STORE_SYSTEM, bool PAIR, bool CHAIN, bool REST>
+void launch_step_solve_assemble_r(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
   // the accumulators; the storing form stages its blocks in the same LDS first
   size_t lds = (size_t)b.max_slots * 6 * sizeof(double);
   if (STORE_SYSTEM) lds = std::max(lds, (size_t)4 * kStageWave * sizeof(double));
-  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN>;
-  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN>;
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
   else hipLaunchKernelGGL(k2, dim3(n_tiles), dim3(256), lds, s, b);
+}
+// restitution (b.assemble.rest is set) has instantiations of its own: the launches without it run the code they ran
+template <bool STORE_SYSTEM, bool PAIR, bool CHAIN = false>
+void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
+  if (b.assemble.rest != nullptr) launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, true>(b, method, n_tiles, s);
+  else launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, false>(b, method, n_tiles, s);
 }
 }  // namespace
 

@@ -125,6 +125,12 @@ struct egs_world {
   bool friction = false;
   DevBuf<double> d_fric;                 // [E]
   std::vector<double> h_fric;            // [E], the host's copy (the dense step's ensembles above the fused cap)
+  // egs_world_set_restitution: one coefficient per ensemble (< 0: none) and the threshold speed.  restitution: some
+  // coefficient is >= 0; then every step fills the problem's per-constraint table from the current list
+  // (world_fill_restitution) before its assembly.
+  bool restitution = false;
+  DevBuf<double> d_rest;                 // [E]
+  double rest_vth = 0.0;
   // egs_world_set_dense_friction: max_outer > 0 makes the dense steps solve the pyramid (the fixed-point iteration of
   // mixed_solve_device.h) while friction is on; 0: they refuse.  The outcomes of the last dense step, per ensemble.
   int dense_fric_outer = 0;
@@ -606,6 +612,19 @@ void world_fill_friction(egs_world *w) {
   HIPCHK(hipGetLastError());
 }
 
+// The problem's restitution coefficients for the list about to be assembled, as world_fill_friction fills mu: joints
+// -1, every contact its ensemble's coefficient, in fp64 (the assembly's precision).
+void world_fill_restitution(egs_world *w) {
+  egs_problem *p = w->prob;
+  p->restitution = w->restitution && p->m > 0;
+  if (!p->restitution) return;
+  p->rest.alloc((size_t)p->m);
+  p->rest_vth = w->rest_vth;
+  launch_fill_friction<double>(p->m, (int)w->jb0.size(), p->body0.p, p->body1.p, w->n_ens > 1 ? w->d_ens.p : nullptr,
+                               w->d_rest.p, p->rest.p, w->ctx->stream);
+  HIPCHK(hipGetLastError());
+}
+
 // egs_world_step (dt_each == NULL) and egs_world_step_each (dt_each / erp_each [E], host, validated) after their guards
 egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *dt_each, const double *erp_each,
                              const egs_solve_params *params, int32_t detect_contacts, egs_solve_stats *stats) {
@@ -622,6 +641,7 @@ egs_status world_step_sweeps(egs_world *w, double dt, double erp, const double *
     const bool batched = w->n_ens > 1;
     w->last_warm = false;
     if (w->friction || p->friction) world_fill_friction(w);
+    if (w->restitution || p->restitution) world_fill_restitution(w);
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);
       // x0 from the history; an ensemble without one gets its rhs rows, the default start.  The problem takes the
@@ -695,6 +715,7 @@ egs_status world_step_direct(egs_world *w, double dt, double erp, const double *
     for (int e = 0; dt_each && e < E; ++e) sits_out |= dt_each[e] == 0.0;
     w->last_warm = false;
     if (pyramid) world_fill_friction(w);
+    if (w->restitution || p->restitution) world_fill_restitution(w);
     if (p->m > 0) {
       world_assemble(w, dt, erp, each);                              // J, err, bounds, rhs (ensembles.cc:565-570)
       // the dense step takes no start; an ensemble sitting out keeps its history through the rows matched here
@@ -1171,6 +1192,29 @@ egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const doubl
     HIPCHK(hipStreamSynchronize(s));   // mu is the caller's
     w->friction = any;
     if (!any && w->prob) w->prob->friction = false;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_restitution(egs_world *w, int32_t n_ensembles, const double *rest, double vth) {
+  if (!w) return EGS_ERR_INVALID;
+  if (!rest) return fail(w->ctx, EGS_ERR_INVALID, "NULL restitution table");
+  if (n_ensembles != w->n_ens) return fail(w->ctx, EGS_ERR_INVALID, "n_ensembles differs from the world's");
+  if (!(vth >= 0) || std::isinf(vth)) return fail(w->ctx, EGS_ERR_INVALID, "the restitution threshold must be finite and >= 0");
+  bool any = false;
+  for (int e = 0; e < n_ensembles; ++e) {
+    if (rest[e] != rest[e] || std::isinf(rest[e])) return fail(w->ctx, EGS_ERR_INVALID, "NaN or infinite restitution coefficient");
+    any |= rest[e] >= 0;
+  }
+  return guarded(w->ctx, [&]() -> egs_status {
+    hipStream_t s = w->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));   // a step in flight may still read the old table
+    w->d_rest.alloc((size_t)n_ensembles);
+    HIPCHK(hipMemcpyAsync(w->d_rest.p, rest, (size_t)n_ensembles * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));   // rest is the caller's
+    w->restitution = any;
+    w->rest_vth = vth;
+    if (!any && w->prob) w->prob->restitution = false;
     return EGS_OK;
   });
 }

@@ -589,6 +589,7 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
       egs::check(egs_problem_create(egs::DefaultContext(), n_, m, b0.data(), b1.data(), EGS_F64, &problem_));
       plan_b0_ = b0; plan_b1_ = b1;
       problem_friction_ = false;
+      problem_restitution_ = false;
     }
     std::vector<double> pos((size_t)n_ * 3), R((size_t)n_ * 9), vl((size_t)n_ * 3), w((size_t)n_ * 3), Minv((size_t)n_ * 36);
     for (int i = 0; i < n_; ++i) {
@@ -599,6 +600,15 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
     }
     egs::check(egs_problem_set_state(problem_, pos.data(), R.data(), vl.data(), w.data(), Minv.data(), external_force_torque_.data()));
     egs::check(egs_problem_set_constraints(problem_, kind.data(), data.data()));
+    if (restitution_ >= 0) {   // every contact the coefficient, every joint -1
+      std::vector<double> rest((size_t)m);
+      for (int i = 0; i < m; ++i) rest[i] = kind[i] == EGS_CONTACT_BOX ? restitution_ : -1.0;
+      egs::check(egs_problem_set_restitution(problem_, rest.data(), restitution_vth_));
+      problem_restitution_ = true;
+    } else if (problem_restitution_) {
+      egs::check(egs_problem_set_restitution(problem_, nullptr, 0.0));
+      problem_restitution_ = false;
+    }
     egs_solve_stats st;
     if (use_dense_solver) {   // ComputeVDot (ensembles.cc:498-538) on the device
       const bool pyramid = friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID;   // (Step let it through: SetDenseFriction)
@@ -633,6 +643,9 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
     egs::check(egs_problem_get_lambda(problem_, last_lambda.data()));
     egs::check(egs_problem_get_velocity(problem_, v_new.data()));
   } else {
+    if (restitution_ >= 0)
+      throw egs::Error(EGS_ERR_UNSUPPORTED, "SetRestitution takes effect where the device assembles: not with a "
+                                            "constraint the device cannot describe");
     Flat f = Flatten(cs, M_inverse_);
     VectorXd err = ComputePositionConstraintError();
     VectorXd rhs(3 * m);
@@ -805,6 +818,14 @@ void Ensemble::SetFriction(Contact::FrictionModel model, double mu) {
   friction_mu_ = model == Contact::FrictionModel::COULOMB_PYRAMID ? mu : 0.0;
 }
 
+void Ensemble::SetRestitution(double e, double threshold) {
+  if (e != e || std::isinf(e)) throw egs::Error(EGS_ERR_INVALID, "SetRestitution: e must be finite");
+  if (!(threshold >= 0) || std::isinf(threshold))
+    throw egs::Error(EGS_ERR_INVALID, "SetRestitution: threshold must be finite and >= 0");
+  restitution_ = e >= 0 ? e : -1.0;
+  restitution_vth_ = threshold;
+}
+
 void Ensemble::SetDenseFriction(int max_outer, double tol) {
   if (max_outer < 0) throw egs::Error(EGS_ERR_INVALID, "SetDenseFriction: max_outer must be >= 0");
   if (!(tol >= 0)) throw egs::Error(EGS_ERR_INVALID, "SetDenseFriction: tol must be >= 0");
@@ -849,6 +870,11 @@ bool Ensemble::StepOnDevice(double dt) {
   if (const double mu = device_friction(); mu != world_friction_) {
     egs::check(egs_world_set_friction(world_, 1, &mu));
     world_friction_ = mu;
+  }
+  if (first) { world_restitution_ = -1.0; world_restitution_vth_ = 0.0; }   // a fresh world has none
+  if (restitution_ != world_restitution_ || (restitution_ >= 0 && restitution_vth_ != world_restitution_vth_)) {
+    egs::check(egs_world_set_restitution(world_, 1, &restitution_, restitution_vth_));
+    world_restitution_ = restitution_; world_restitution_vth_ = restitution_vth_;
   }
   // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state
   // that is still what the last step left on the device is not pushed again: a push drops the world's history.
@@ -1066,6 +1092,24 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     if (mu != world_friction_) {
       egs::check(egs_world_set_friction(world_, (int32_t)E, mu.data()));
       world_friction_ = mu;
+    }
+  }
+  {   // the members' restitution: each its own coefficient, one threshold among those that have it on
+    std::vector<double> rest(E);
+    double vth = 0.0;
+    bool any = false;
+    for (size_t i = 0; i < E; ++i) {
+      rest[i] = members_[i]->restitution_;
+      if (rest[i] < 0) continue;
+      if (any && members_[i]->restitution_vth_ != vth)
+        throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " differs in SetRestitution's threshold");
+      vth = members_[i]->restitution_vth_;
+      any = true;
+    }
+    if (first) { world_restitution_.assign(E, -1.0); world_restitution_vth_ = 0.0; }
+    if (rest != world_restitution_ || (any && vth != world_restitution_vth_)) {
+      egs::check(egs_world_set_restitution(world_, (int32_t)E, rest.data(), vth));
+      world_restitution_ = rest; world_restitution_vth_ = vth;
     }
   }
   // M^-1, the external force and the box sizes are frozen at Init() (Q5): sent once.  With warm start on, a state

@@ -348,6 +348,16 @@ class Ensemble {  // ensembles.h:25-186
   // device only: Step throws EGS_ERR_UNSUPPORTED where it would take the explicit or the dense path -- the dense path
   // unless SetDenseFriction has allowed it.
   void SetFriction(Contact::FrictionModel model, double mu = 0);
+  // Not in the reference either, off by default: restitution (egs_world_set_restitution, egs_problem_set_restitution).
+  // A contact approaching faster than `threshold` (m/s, >= 0) separates at e times its approach speed, with the
+  // Baumgarte velocity as the floor; joints never bounce; e > 1 is allowed; e < 0 turns it off.  Takes effect in
+  // every step that assembles on the device (the device world, and the per-step device problem with or without
+  // use_dense_solver); a step whose rows the host assembles (a constraint the device cannot describe) throws
+  // egs::Error(EGS_ERR_UNSUPPORTED) while it is on.  Throws egs::Error(EGS_ERR_INVALID): e NaN or infinite, threshold
+  // < 0, NaN or infinite.
+  void SetRestitution(double e, double threshold = 0.0);
+  double restitution() const { return restitution_; }
+  double restitution_threshold() const { return restitution_vth_; }
   // The pyramid on the dense direct solver, opt-in (egs_problem_set_dense_friction / egs_world_set_dense_friction):
   // after SetDenseFriction(max_outer > 0, tol) a COULOMB_PYRAMID ensemble with use_dense_solver steps instead of
   // throwing -- the fixed-point iteration on the tangential bounds, at most max_outer solves, stopping change tol --
@@ -416,6 +426,9 @@ class Ensemble {  // ensembles.h:25-186
   int dense_fric_outer_ = 0;                     // SetDenseFriction (0: off)
   double dense_fric_tol_ = 0.0;
   bool problem_friction_ = false;                // the cached device problem holds friction coefficients
+  double restitution_ = -1.0, restitution_vth_ = 0.0;   // asked for (< 0: off) ...
+  double world_restitution_ = -1.0, world_restitution_vth_ = 0.0;   // ... and what the device world was last told
+  bool problem_restitution_ = false;             // the cached device problem holds restitution coefficients
   double device_friction() const { return friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID ? friction_mu_ : -1.0; }
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last device step (warm start only)
   egs_problem *problem_ = nullptr;
@@ -449,6 +462,8 @@ class Cairn : public Ensemble {
 // member's own Step(dt[i]) leaves (sweeps; the dense members: what a world of their own leaves after
 // egs_world_step_dense).  dt[i] = 0: member i sits the step out, nothing of it changes.
 //   - The members may differ in SetFriction: member i's contacts take its model and coefficient (egs_world_set_friction).
+//   - The members may differ in SetRestitution's coefficient (egs_world_set_restitution); those that have it on must
+//     agree in the threshold, of which the world has one.
 //   - The members may differ in SetLiveInertia: the state is per body (egs_world_set_live_inertia; the bodies of a member
 //     with it off are sent as the identity, which the device skips).
 //   - The members must agree in solver_params, cfm_coeff, use_dense_solver, detect_contacts, SetWarmStart and SetDenseFriction, and each must be able to
@@ -481,6 +496,8 @@ class EnsembleGroup {
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
   std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)
+  std::vector<double> world_restitution_;        // ... their restitution coefficients and the threshold
+  double world_restitution_vth_ = 0.0;
   std::vector<char> world_live_;                 // ... and the members' SetLiveInertia (empty: never told, all off)
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last step (warm start only)
 };

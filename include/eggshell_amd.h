@@ -239,6 +239,29 @@ egs_status egs_problem_set_dense_friction(egs_problem *p, int32_t max_outer, dou
  * (change <= tol), the last change.  EGS_ERR_INVALID before the first such step.                                   */
 egs_status egs_problem_dense_friction_info(egs_problem *p, int32_t *outer, int32_t *converged, double *change);
 
+/* ---- Restitution: contacts that bounce.  The reference has none: a contact's normal row asks only for
+ *      J v' >= erp depth / dt (ensembles.cc:569-570), so a dropped body stops dead.  This is Newton's law of restitution
+ *      with that Baumgarte term as the floor, off unless asked for.  rest holds one coefficient per constraint, fp64
+ *      whatever the problem's precision; vth >= 0 is one threshold speed.  Constraint c bounces only if its kind is
+ *      EGS_CONTACT_BOX, a table is set and rest[c] >= 0; joints never bounce, rest[c] < 0 is assembled as stored.  For
+ *      a bouncing contact the assembly forms row 2 of rhs in this order, in fp64 without contraction, and casts it:
+ *          s0 = (v, w) of body0, s1 = (v, w) of body1                  (six zeros for a world side)
+ *          vn = dot6p(J0 row 2, s0) + dot6p(J1 row 2, s1)              (the separating speed; approaching: vn < 0)
+ *          t  = kk err[2]                                              (kk = -erp/dt/dt; the ensemble's pair in _each)
+ *          if (vn < -vth) { b = (-(rest[c] vn)) / dt;  if (b > t) t = b; }
+ *          rhs[2] = t - ju                                             (ju = J (v/dt + M^-1 f) as always)
+ *      so that the normal row's complementarity becomes J v' >= max(erp depth / dt, -rest vn).  Rows 0 and 1, err, lo,
+ *      hi, is_eq, J0 and J1 are untouched; a contact that does not trigger (vn >= -vth, or b <= t) gets the bits it
+ *      gets without this call; an ensemble sitting a step out (dt[e] = 0) keeps rhs = 0 exactly.  Coefficients above 1
+ *      are allowed.  It takes effect wherever the rhs is made -- egs_problem_assemble, egs_problem_step (the fused
+ *      launch keeps the assembly in its prologue: EGS_SCHED_FUSED_ASSEMBLY, PAIR and CHAIN stay set, and a deferred
+ *      system materialised later carries the table its step ran with), egs_problem_step_dense -- and composes with
+ *      friction, dense friction, starts and live inertia, which read the restituted rhs where they read rhs.
+ *      rest = NULL, or no coefficient >= 0, turns it off: every result and schedule flag is then what it is without
+ *      this call.  A new topology turns it off (the coefficients belong to the list they were given for).
+ *      EGS_ERR_INVALID: a NaN or infinite coefficient, vth < 0, NaN or infinite (nothing changes).                   */
+egs_status egs_problem_set_restitution(egs_problem *p, const double *rest /*[m] or NULL = off*/, double vth);
+
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
  *      const VectorXd& x, double epsilon_diagonal, double scale_diagonal)
@@ -620,6 +643,15 @@ egs_status egs_world_set_warm_start(egs_world *w, int32_t enable, double match_r
  * egs_world_step_dense_each return EGS_ERR_UNSUPPORTED while any coefficient is >= 0, unless
  * egs_world_set_dense_friction has allowed it.  Warm start and stabilisation are untouched.  EGS_ERR_INVALID: mu NULL, a NaN, a wrong n_ensembles (nothing changes).                              */
 egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const double *mu /*[E]*/);
+/* Restitution (egs_problem_set_restitution) for a world: one coefficient per ensemble (n_ensembles must be the world's,
+ * 1 for a plain world) and one threshold speed.  Every contact of ensemble e takes rest[e], every joint -1; rest[e] < 0:
+ * that ensemble's contacts do not bounce and get the bits of a world without this call.  The per-constraint table is
+ * filled on the device from the current contact list at every step (no read-back, no upload), so the contacts of a
+ * re-planned list carry their ensemble's coefficient.  egs_world_step[_each] and egs_world_step_dense[_each] assemble
+ * with it; warm start matches and snapshots after the restituted solve; the stabilise entries work on positions and
+ * ignore it.  EGS_ERR_INVALID: rest NULL, a NaN or infinite coefficient, vth < 0, NaN or infinite, a wrong n_ensembles
+ * (nothing changes).                                                                                              */
+egs_status egs_world_set_restitution(egs_world *w, int32_t n_ensembles, const double *rest /*[E]*/, double vth);
 egs_status egs_world_get_start(egs_world *w, int32_t max_rows, int32_t *rows_out, double *x0, int32_t *source /*[m] or NULL*/);
 egs_status egs_world_info(egs_world *w, int32_t *n_constraints, int32_t *n_contacts, int32_t *replans);
 
