@@ -430,7 +430,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   // the rows changed: x holds no lambda of this list, and a GIVEN start has the wrong length
   p->have_lambda = false;
   if (p->start_mode == EGS_START_GIVEN) p->start_mode = EGS_START_RHS;
-  p->friction = false;   // the coefficients were those of the old list (the world refills them: world.cpp)
+  p->friction = false;   // the coefficients were those of the old list (the world refills them: world_step.cpp)
   p->restitution = false;   // likewise
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
