@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libeggshell_amd.so")
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STALL, ERR_UNSUPPORTED, ERR_LCP_FAILED, ERR_INTERNAL = range(8)
 JACOBI, GAUSS_SEIDEL, SOR = 0, 1, 2
 F64, F32 = 0, 1
-JOINT_BALL, CONTACT_BOX = 0, 1
+JOINT_BALL, CONTACT_BOX, JOINT_LOCK, JOINT_HINGE_AXIS = 0, 1, 2, 3
 SHAPE_BOX, SHAPE_SPHERE = 0, 1
 MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
@@ -57,6 +57,7 @@ EXPORTS = [
     "egs_world_set_dense_friction", "egs_world_dense_friction_info",
     "egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass",
     "egs_problem_set_restitution", "egs_world_set_restitution",
+    "egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks",
 ]
 
 
@@ -104,6 +105,13 @@ def load():
         if hasattr(_lib, "egs_problem_set_restitution"):
             _lib.egs_problem_set_restitution.argtypes = [C.c_void_p, C.c_void_p, C.c_double]   # problem, rest, vth
             _lib.egs_world_set_restitution.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double]   # world, E, rest, vth
+        if hasattr(_lib, "egs_problem_set_motors"):
+            _lib.egs_problem_set_motors.argtypes = [C.c_void_p, C.c_void_p]   # problem, motor
+            _lib.egs_world_set_joints_kinds.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4   # world, m, kind, b0, b1, data
+            _lib.egs_world_set_joint_motors.argtypes = [C.c_void_p, C.c_void_p]   # world, motor
+            _lib.egs_world_get_blocks.argtypes = [C.c_void_p] * 8   # world, J0, J1, is_eq, lo, hi, rhs, err
+            for name in ("egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks"):
+                getattr(_lib, name).restype = C.c_int
         if hasattr(_lib, "egs_problem_set_live_inertia"):
             # handle, inertia_body, torque / handle, Minv, f_ext
             for name in ("egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass"):
@@ -703,6 +711,14 @@ class Problem:
             raise ValueError("rest: %d coefficients for %d constraints" % (rest.size, self.m))
         self.ctx.check(load().egs_problem_set_restitution(self.h, _p(rest), float(vth)))
 
+    def set_motors(self, motor=None):
+        """Hinge motors (egs_problem_set_motors): [m][2] = (speed, tau) per constraint; a HINGE_AXIS constraint with
+        tau >= 0 is driven towards speed within +-tau, everything else is assembled as stored.  None turns it off."""
+        motor = _f64(motor)
+        if motor is not None and motor.size != 2 * self.m:
+            raise ValueError("motor: %d values for %d constraints" % (motor.size, self.m))
+        self.ctx.check(load().egs_problem_set_motors(self.h, _p(motor)))
+
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
         w = np.zeros(3 * self.m)
@@ -935,6 +951,27 @@ class World:
     def set_joints(self, body0, body1, data):
         body0, body1, data = _i32(body0), _i32(body1), _f64(data)
         self.ctx.check(load().egs_world_set_joints(self.h, C.c_int32(body0.shape[0]), _p(body0), _p(body1), _p(data)))
+
+    def set_joints_kinds(self, kind, body0, body1, data):
+        """Joints of any kind (egs_world_set_joints_kinds): JOINT_BALL, JOINT_LOCK, JOINT_HINGE_AXIS; kind None: all ball."""
+        kind, body0, body1, data = _i32(kind), _i32(body0), _i32(body1), _f64(data)
+        if kind is not None and kind.shape[0] != body0.shape[0]:
+            raise ValueError("kind: %d entries for %d joints" % (kind.shape[0], body0.shape[0]))
+        self.m_joints = int(body0.shape[0])
+        self.ctx.check(load().egs_world_set_joints_kinds(self.h, C.c_int32(body0.shape[0]), _p(kind), _p(body0), _p(body1), _p(data)))
+
+    def blocks(self):
+        """(J0, J1, is_eq, lo, hi, rhs, err) of the list the last step assembled (egs_world_get_blocks), joints first."""
+        m = self.info()["n_constraints"]
+        J0 = np.zeros((m, 18)); J1 = np.zeros((m, 18)); is_eq = np.zeros(3 * m, np.uint8)
+        lo = np.zeros(3 * m); hi = np.zeros(3 * m); rhs = np.zeros(3 * m); err = np.zeros(3 * m)
+        self.ctx.check(load().egs_world_get_blocks(self.h, _p(J0), _p(J1), _p(is_eq), _p(lo), _p(hi), _p(rhs), _p(err)))
+        return J0, J1, is_eq, lo, hi, rhs, err
+
+    def set_joint_motors(self, motor=None):
+        """Hinge motors of the world's joints (egs_world_set_joint_motors): [m_joints][2] = (speed, tau); None: off."""
+        motor = _f64(motor)
+        self.ctx.check(load().egs_world_set_joint_motors(self.h, _p(motor)))
 
     def step(self, dt, erp, prm, detect_contacts=True, want_stats=False):
         st = SolveStats()

@@ -73,20 +73,102 @@ __device__ __forceinline__ double dot6p(const double *a, const double *b) {
   return ((((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]) + a[4] * b[4]) + a[5] * b[5];
 }
 
-// Constraint i: j0 / j1 (3x6 row-major, zero for a world side), e = err, lo / hi, eq (every row of a joint is an
-// equality row, no row of a contact is) and per side u = v/dt + W f (zero for a world side), what the rhs needs.
+// The angular blocks (EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS; eggshell_amd.h has the derivation and DESIGN.md section
+// 4k the limits).  The linear columns stay exactly zero on both sides; err is (body0 quantity) - (body1 quantity) and
+// d err/dt = J0 s0 + J1 s1 at err = 0, as for the ball joint.  fp64, no contraction, no trigonometric function; the
+// operation order below is the one tests/joint_reference.py restates.
+//
+// LOCK, data = (qw, qx, qy, qz, 0, 0, 0), the unit quaternion of Rref = R0(0)^T R1(0) (R0(0)^T for a world side):
+//   Rq = quat_to_R(q);  T = mm3(R0, Rq);  E = mm3(T, R1^T) with R1^T formed by index (a world side: E = T)
+//   err = (0.5*(E[7]-E[5]), 0.5*(E[2]-E[6]), 0.5*(E[3]-E[1]))      the axial vector of E, sin(theta) n
+//   J0 = [0 | I3], J1 = [0 | -1.0*I3] (zero for a world side); three equality rows, lo = hi = 0
+__device__ __forceinline__ void lock_block(const AssembleArgs &A, int b0, int b1, const double *d, double *j0, double *j1,
+                                           double *e) {
+  double R0[9], Rq[9], T[9], E[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
+  quat_to_R(d[0], d[1], d[2], d[3], Rq);
+  mm3(R0, Rq, T);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) j0[6 * r + 3 + r] = 1.0;
+  if (b1 >= 0) {
+    double R1t[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) R1t[3 * r + c] = A.R[(size_t)b1 * 9 + 3 * c + r];
+    mm3(T, R1t, E);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) j1[6 * r + 3 + r] = -1.0 * 1.0;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = T[k];
+  }
+  e[0] = 0.5 * (E[7] - E[5]);
+  e[1] = 0.5 * (E[2] - E[6]);
+  e[2] = 0.5 * (E[3] - E[1]);
+}
+// HINGE_AXIS, data = (a0[3], a1[3], 0): a0 the unit axis in body0's frame, a1 in body1's (the world axis for a world side):
+//   s = mv3(R0, a0);  t = mv3(R1, a1) (a world side: a1);  Rn = align_to_z(s), rows (p, q, s^)
+//   c = t x s = (t1 s2 - t2 s1, t2 s0 - t0 s2, t0 s1 - t1 s0);  err = (d3(p, c), d3(q, c), 0)
+//   J0 = [0 | Rn], J1 = [0 | -1.0*Rn] (zero for a world side)
+// Rows 0 and 1 are equality rows; row 2, the axis row, is an inequality row with lo = hi = 0 (the multiplier pinned
+// at 0: the hinge turns freely) unless a motor opens its bounds (motor_row below).  t = -s is a false equilibrium
+// (c = 0 there too): the linearisation holds for axes less than a right angle apart.
+__device__ __forceinline__ void hinge_block(const AssembleArgs &A, int b0, int b1, const double *d, double *j0, double *j1,
+                                            double *e) {
+  double R0[9], s[3], t[3], Rn[9], c[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
+  mv3(R0, d, s);
+  if (b1 >= 0) {
+    double R1[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R1[k] = A.R[(size_t)b1 * 9 + k];
+    mv3(R1, d + 3, t);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = d[3 + k];
+  }
+  align_to_z(s, Rn);
+  c[0] = t[1] * s[2] - t[2] * s[1];
+  c[1] = t[2] * s[0] - t[0] * s[2];
+  c[2] = t[0] * s[1] - t[1] * s[0];
+  e[0] = d3(Rn, c);
+  e[1] = d3(Rn + 3, c);
+  e[2] = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      j0[6 * r + 3 + k] = Rn[3 * r + k];
+      if (b1 >= 0) j1[6 * r + 3 + k] = -1.0 * Rn[3 * r + k];
+    }
+}
+
+// Constraint i: j0 / j1 (3x6 row-major, zero for a world side), e = err, lo / hi, eq per row (every row of a ball joint
+// and of a lock is an equality row, no row of a contact is, a hinge's axis row is not) and per side u = v/dt + W f
+// (zero for a world side), what the rhs needs.
 // EACH: dt is the constraint's own time step, dt_each (constraint_rates); otherwise the launch's A.dt, read where the
-// scalar form has always read it
-template <bool EACH>
+// scalar form has always read it.  ANGULAR = false leaves the angular blocks out: the fused prologue of
+// step_solve_kernel, which choose_sweep offers lists of contacts only, keeps the code it had.
+template <bool EACH, bool ANGULAR = true>
 __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, double dt_each, double *j0, double *j1, double *e,
-                                               double *lo, double *hi, bool &eq, double *u0, double *u1) {
+                                               double *lo, double *hi, bool *eq, double *u0, double *u1) {
   const int b0 = A.body0[i], b1 = A.body1[i];
   double d[7];
 #pragma unroll
   for (int k = 0; k < 7; ++k) d[k] = A.data[(size_t)i * 7 + k];
 #pragma unroll
   for (int k = 0; k < 18; ++k) { j0[k] = 0.0; j1[k] = 0.0; }
-  if (A.kind[i] == 0) {  // joints.cc:3-35
+  const int kind = A.kind[i];
+  if (ANGULAR && kind >= 2) {
+    if (kind == 2) lock_block(A, b0, b1, d, j0, j1, e);
+    else hinge_block(A, b0, b1, d, j0, j1, e);
+    eq[0] = true; eq[1] = true; eq[2] = kind == 2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = 0.0; hi[k] = 0.0; }
+  } else if (kind == 0) {  // joints.cc:3-35
     double R0[9], rc0[3], cm[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
@@ -118,7 +200,7 @@ __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, dou
 #pragma unroll
       for (int k = 0; k < 3; ++k) e[k] = e[k] - d[3 + k];
     }
-    eq = true;
+    eq[0] = true; eq[1] = true; eq[2] = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { lo[k] = 0.0; hi[k] = 0.0; }
   } else {  // contact.cc:14-117, FrictionModel::BOX
@@ -149,7 +231,7 @@ __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, dou
         for (int c = 0; c < 3; ++c) { j1[6 * r + c] = Rn[3 * r + c]; j1[6 * r + 3 + c] = rw[3 * r + c]; }
     }
     e[0] = 0.0; e[1] = 0.0; e[2] = -d[6];
-    eq = false;
+    eq[0] = false; eq[1] = false; eq[2] = false;
     lo[0] = -1.0; lo[1] = -1.0; lo[2] = 0.0;
     hi[0] = 1.0; hi[1] = 1.0; hi[2] = INFINITY;
   }
@@ -171,9 +253,10 @@ __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, dou
     }
   }
 }
+template <bool ANGULAR = true>
 __device__ __forceinline__ void assemble_one(const AssembleArgs &A, int i, double *j0, double *j1, double *e, double *lo,
-                                             double *hi, bool &eq, double *u0, double *u1) {
-  assemble_one_t<false>(A, i, 0.0, j0, j1, e, lo, hi, eq, u0, u1);
+                                             double *hi, bool *eq, double *u0, double *u1) {
+  assemble_one_t<false, ANGULAR>(A, i, 0.0, j0, j1, e, lo, hi, eq, u0, u1);
 }
 // row r of rhs = -(erp/dt^2) err - J (v/dt + W f)      ensembles.cc:569-570
 template <bool EACH>
@@ -185,11 +268,12 @@ __device__ __forceinline__ double assemble_rhs_t(const AssembleArgs &A, double d
 }
 // Restitution (egs_problem_set_restitution): the normal row's target t = kk err[2] of contact i, raised to -rest vn / dt
 // where the contact approaches faster than vth.  vn: the separating speed of row 2 from the bodies' (v, w), zeros for
-// a world side.  A joint, a coefficient < 0 and a contact that does not trigger return t itself: the stored bits.
+// a world side.  Whatever is not a contact (the joints never bounce), a coefficient < 0 and a contact that does not
+// trigger return t itself: the stored bits.
 template <bool EACH>
 __device__ __forceinline__ double restitution_target(const AssembleArgs &A, int i, double dt_each, const double *j0,
                                                      const double *j1, double t) {
-  if (A.kind[i] == 0) return t;
+  if (A.kind[i] != 1) return t;
   const double rest = A.rest[i];
   if (!(rest >= 0)) return t;
   const int b0 = A.body0[i], b1 = A.body1[i];
@@ -214,6 +298,24 @@ __device__ __forceinline__ double assemble_rhs_bounce_t(const AssembleArgs &A, i
   const double kk = EACH ? -erp_each / dt_each / dt_each : -A.erp / A.dt / A.dt;
   const double ju = dot6p(j0 + 12, u0) + dot6p(j1 + 12, u1);
   return restitution_target<EACH>(A, i, dt_each, j0, j1, kk * e[2]) - ju;
+}
+// The motor table (egs_problem_set_motors), motor [m][2] = (speed, tau), not NULL: a HINGE_AXIS constraint i with
+// tau >= 0 (+inf allowed) gets lo[2] = -tau, hi[2] = +tau and the target t = speed / dt in place of kk err[2] (which
+// is 0 for it): rhs2 = t - ju, so that the solve asks for s^ . (w0' - w1') = speed within the torque limit.  Returns
+// whether it applied; tau < 0 and every other kind are left as assembled.
+template <bool EACH>
+__device__ __forceinline__ bool motor_row(const AssembleArgs &A, const double *motor, int i, double dt_each, const double *j0,
+                                          const double *j1, const double *u0, const double *u1, double *lo, double *hi,
+                                          double &rhs2) {
+  if (A.kind[i] != 3) return false;
+  const double speed = motor[(size_t)i * 2], tau = motor[(size_t)i * 2 + 1];
+  if (!(tau >= 0)) return false;
+  lo[2] = -tau;
+  hi[2] = tau;
+  const double t = speed / (EACH ? dt_each : A.dt);
+  const double ju = dot6p(j0 + 12, u0) + dot6p(j1 + 12, u1);
+  rhs2 = t - ju;
+  return true;
 }
 __device__ __forceinline__ double assemble_rhs(const AssembleArgs &A, const double *j0, const double *j1, const double *e,
                                                const double *u0, const double *u1, int r) {

@@ -160,6 +160,12 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
   if (p->friction && p->dense_fric_outer == 0)
     return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (p->friction && use_bounds != 1) return fail(p->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
+  // a hinge's axis row pinned at lo = hi = 0 does not meet Murty's preconditions (lcp.cc:161-164), and without the
+  // bounds a motored one would be solved as a lambda >= 0 row
+  if (p->hinges && (use_bounds & 1) == 0)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step takes a hinge axis row as a box row: a hinge needs use_bounds bit 0");
+  if (p->hinges_pinned)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   if (ok) *ok = 0;
   return guarded(p->ctx, [&]() -> egs_status {
     egs_context *ctx = p->ctx;

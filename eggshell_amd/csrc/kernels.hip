@@ -233,7 +233,9 @@ __global__ void __launch_bounds__(BLOCK, ISO ? (sizeof(REAL) == 4 ? 4 : 3) : 1) 
 
 // --------------------------------------------------------------------------
 // residual partial sums (sparse_iterations.cc:51-69): per block 4 sums of w^2
-// over {equality, at lo & w<0, at hi & w>0, strictly inside}.
+// over {equality, at lo & w<0, at hi & w>0, strictly inside}.  A row pinned by lo == hi (a free hinge's axis row) has
+// its multiplier fixed and w free of either sign: it violates nothing and is in none of the four (in all three kernels
+// below; a row with lo < hi is sorted as ever).
 // FRIC: rows 0 and 1 of a constraint with mu >= 0 by the pyramid's rule (solve_device.h: pyramid_residual), the
 // normal multiplier being row 3i + 2 of the same x.  Without FRIC mu is not read.
 template <typename REAL, bool FRIC = false>
@@ -248,8 +250,8 @@ __global__ void __launch_bounds__(256) residual_partials_kernel(int rows, const 
     if (FRIC && r % 3 < 2 && mu[r / 3] >= REAL(0)) pyramid_residual(xv, w, mu[r / 3], x[r - r % 3 + 2], a, b, c);
     else if (is_eq[r]) e += w * w;
     else {
-      if (xv == l && w < 0) a += w * w;
-      if (xv == h && w > 0) b += w * w;
+      if (xv == l && w < 0 && l != h) a += w * w;
+      if (xv == h && w > 0 && l != h) b += w * w;
       if (xv > l && xv < h) c += w * w;
     }
   }
@@ -312,8 +314,8 @@ __global__ void __launch_bounds__(256) hist_residual_kernel(const SolveArgs<REAL
         acc[g][1] += s_lo; acc[g][2] += s_hi; acc[g][3] += s_in;
       } else if (eq) acc[g][0] += w * w;
       else {
-        if (xv == l && w < 0) acc[g][1] += w * w;
-        if (xv == h && w > 0) acc[g][2] += w * w;
+        if (xv == l && w < 0 && l != h) acc[g][1] += w * w;
+        if (xv == h && w > 0 && l != h) acc[g][2] += w * w;
         if (xv > l && xv < h) acc[g][3] += w * w;
       }
     }
@@ -380,8 +382,8 @@ __global__ void __launch_bounds__(256) seg_residual_kernel(const SolveArgs<REAL>
         acc[1] += s_lo; acc[2] += s_hi; acc[3] += s_in;
       } else if (A.is_eq[r]) acc[0] += w * w;
       else {
-        if (xv == l && w < 0) acc[1] += w * w;
-        if (xv == h && w > 0) acc[2] += w * w;
+        if (xv == l && w < 0 && l != h) acc[1] += w * w;
+        if (xv == h && w > 0 && l != h) acc[2] += w * w;
         if (xv > l && xv < h) acc[3] += w * w;
       }
     }
@@ -640,9 +642,12 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
 struct NoRates {};   // the scalar form's (empty) second argument
 // EACH: dt and erp per constraint from its ensemble's (T); an ensemble that sits the step out (dt 0) gets rhs rows of
 // exactly 0, its blocks, err, bounds and row types as always.  REST: restitution on the normal rows (A.rest is set);
-// an instantiation of its own, so that the launches without it keep their registers.
-template <typename REAL, bool EACH, typename RATES, bool REST>
-__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T) {
+// an instantiation of its own, so that the launches without it keep their registers.  motor: the hinge motors'
+// table (assemble_device.h: motor_row), NULL = off; read by hinge-axis lanes only.  ANGULAR: the list holds an angular
+// block (LOCK, HINGE_AXIS); without one the launch runs the instantiation that leaves them and the motors out, with
+// the registers and the occupancy it had before they existed.
+template <typename REAL, bool EACH, typename RATES, bool REST, bool ANGULAR>
+__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T, const double *motor) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
   // stores hit 64 lines per instruction; staged, the workgroup writes its 256 x 18 block contiguously
   __shared__ REAL stage[256 * 19];   // row stride 19: conflict-free column walks
@@ -650,10 +655,10 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   const bool live = i_raw < A.m;
   const int i = live ? i_raw : A.m - 1;   // the tail lanes recompute the last constraint and store nothing
   double j0[18], j1[18], e[3], lo[3], hi[3], u0[6], u1[6];
-  bool eq;
+  bool eq[3];
   double dt = 0.0, erp = 0.0;   // EACH: the constraint's own; otherwise A.dt / A.erp where they are used
   if constexpr (EACH) constraint_rates(A, T, i, dt, erp);
-  assemble_one_t<EACH>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
+  assemble_one_t<EACH, ANGULAR>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
   REAL *J0o = reinterpret_cast<REAL *>(A.J0), *J1o = reinterpret_cast<REAL *>(A.J1);
   REAL *loo = reinterpret_cast<REAL *>(A.lo), *hio = reinterpret_cast<REAL *>(A.hi);
   REAL *rhso = reinterpret_cast<REAL *>(A.rhs);
@@ -671,16 +676,20 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
     for (int e = threadIdx.x; e < count * 18; e += 256) J1o[(size_t)first * 18 + e] = stage[(e / 18) * 19 + e % 18];
   }
   if (!live) return;
+  double motor_rhs = 0.0;
+  const bool motored = ANGULAR && motor != nullptr && motor_row<EACH>(A, motor, i, dt, j0, j1, u0, u1, lo, hi, motor_rhs);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    if (REST && r == 2)
+    if (r == 2 && motored)
+      rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)motor_rhs;
+    else if (REST && r == 2)
       rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_bounce_t<EACH>(A, i, dt, erp, j0, j1, e, u0, u1);
     else
       rhso[(size_t)i * 3 + r] = (EACH && dt == 0.0) ? REAL(0) : (REAL)assemble_rhs_t<EACH>(A, dt, erp, j0, j1, e, u0, u1, r);
     A.err[(size_t)i * 3 + r] = e[r];
     loo[(size_t)i * 3 + r] = (REAL)lo[r];
     hio[(size_t)i * 3 + r] = (REAL)hi[r];
-    A.is_eq[(size_t)i * 3 + r] = eq ? 1 : 0;
+    A.is_eq[(size_t)i * 3 + r] = eq[r] ? 1 : 0;
   }
 }
 
@@ -998,19 +1007,25 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 template <typename REAL>
-void launch_assemble(const AssembleArgs &a, hipStream_t s) {
+void launch_assemble(const AssembleArgs &a, bool angular, const double *motor, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), t(256);
-  if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true>), g, t, 0, s, a, NoRates{});
-  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false>), g, t, 0, s, a, NoRates{});
+  if (angular) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true>), g, t, 0, s, a, NoRates{}, motor);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true>), g, t, 0, s, a, NoRates{}, motor);
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, false>), g, t, 0, s, a, NoRates{}, nullptr);
+  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, false>), g, t, 0, s, a, NoRates{}, nullptr);
 }
 
 template <typename REAL>
-void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, hipStream_t s) {
+void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const double *motor, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), b(256);
-  if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true>), g, b, 0, s, a, t);
-  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false>), g, b, 0, s, a, t);
+  if (angular) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true>), g, b, 0, s, a, t, motor);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true>), g, b, 0, s, a, t, motor);
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, false>), g, b, 0, s, a, t, nullptr);
+  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, false>), g, b, 0, s, a, t, nullptr);
 }
 
 template <typename REAL>
@@ -1183,8 +1198,8 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_global_solve<REAL>(const GlobalArgs<REAL> &, int, hipStream_t);                            \
   template void launch_cons_prepare<REAL>(const SolveArgs<REAL> &, hipStream_t);                             \
   template void launch_global_wres<REAL>(const GlobalArgs<REAL> &, hipStream_t);                            \
-  template void launch_assemble<REAL>(const AssembleArgs &, hipStream_t);                                    \
-  template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, hipStream_t);        \
+  template void launch_assemble<REAL>(const AssembleArgs &, bool, const double *, hipStream_t);                                    \
+  template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, bool, const double *, hipStream_t);        \
   template void launch_residual_partials<REAL>(int, const REAL *, const REAL *, const REAL *, const REAL *,  \
                                                const uint8_t *, const REAL *, double *, int, hipStream_t);   \
   template void launch_velocity<REAL>(int, const double *, const double *, const double *, const REAL *, double,   \

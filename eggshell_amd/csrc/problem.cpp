@@ -252,14 +252,30 @@ egs_status set_live_inertia(egs_problem *p, const double *inertia_body, const do
 // J1_lin is -J0_lin in value but not in bits.  Contacts are [-Rn, ..] / [Rn, ..], negated bit for bit.
 // A list without any joint holds contacts only: the fused step's sweep takes their bounds as literals (solve.cpp:
 // choose_sweep).
+// The angular blocks (EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS) are joints here: one between two bodies counts as a two-body
+// ball joint (its J1 is -1.0 * J0 only in value where J0 holds +0, and the LINSYM forms keep one linear block, which
+// these do not have), so a list that holds one runs none of LINSYM, FUSED_ASSEMBLY, PAIR or CHAIN.
 void note_kinds(egs_problem *p, const int32_t *kind) {
   bool jp = false, joint = false;
-  for (int i = 0; i < p->m && !jp; ++i) {
-    joint = joint || kind[i] == EGS_JOINT_BALL;
-    jp = kind[i] == EGS_JOINT_BALL && p->h_body0[i] >= 0 && p->h_body1[i] >= 0;
+  p->angular = false;
+  for (int i = 0; i < p->m; ++i) {
+    joint = joint || kind[i] != EGS_CONTACT_BOX;
+    p->angular = p->angular || kind[i] == EGS_JOINT_LOCK || kind[i] == EGS_JOINT_HINGE_AXIS;
+    jp = jp || (kind[i] != EGS_CONTACT_BOX && p->h_body0[i] >= 0 && p->h_body1[i] >= 0);
   }
   p->joint_pairs = jp;
   p->contacts_only = !joint;
+  p->h_kind.assign(kind, kind + p->m);
+  note_hinges(p, nullptr);
+}
+
+void note_hinges(egs_problem *p, const double *motor) {
+  p->hinges = p->hinges_pinned = false;
+  for (int i = 0; i < p->m && i < (int)p->h_kind.size(); ++i) {
+    if (p->h_kind[i] != EGS_JOINT_HINGE_AXIS) continue;
+    p->hinges = true;
+    if (!motor || !(motor[2 * (size_t)i + 1] > 0)) p->hinges_pinned = true;
+  }
 }
 
 // ---- the sticky stall flag ---------------------------------------------------
@@ -276,6 +292,31 @@ egs_status report_stall(egs_problem *p) {
   *p->h_flag.p = 0;
   p->ctx->error = "device ordering wait timed out";
   return EGS_ERR_STALL;
+}
+
+// What is wrong with a list of kinds and descriptors (nothing: NULL): an unknown kind; for the angular blocks a side 0
+// without a body, non-finite data, a LOCK quaternion or a hinge axis whose squared norm is not within 1e-12 of 1.
+const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, const double *data) {
+  auto unit = [](const double *v, int k) {
+    double n = 0.0;
+    for (int q = 0; q < k; ++q) n += v[q] * v[q];
+    return std::fabs(n - 1.0) <= 1e-12;   // false for a NaN
+  };
+  for (int i = 0; i < m; ++i) {
+    const double *d = data + 7 * (size_t)i;
+    switch (kind[i]) {
+      case EGS_JOINT_BALL: case EGS_CONTACT_BOX: break;
+      case EGS_JOINT_LOCK: case EGS_JOINT_HINGE_AXIS:
+        if (body0[i] < 0) return "an angular joint needs a body on side 0";
+        for (int k = 0; k < 7; ++k)
+          if (!std::isfinite(d[k])) return "non-finite angular joint data";
+        if (kind[i] == EGS_JOINT_LOCK ? !unit(d, 4) : !(unit(d, 3) && unit(d + 3, 3)))
+          return kind[i] == EGS_JOINT_LOCK ? "the lock quaternion is not a unit quaternion" : "a hinge axis is not a unit vector";
+        break;
+      default: return "unknown constraint kind";
+    }
+  }
+  return nullptr;
 }
 
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
@@ -302,7 +343,7 @@ void note_assembled(egs_problem *p) {
 
 void do_assemble(egs_problem *p, double dt, double erp) {
   const AssembleArgs a = assemble_args(p, dt, erp);
-  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->ctx->stream); });
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, motor_table(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   note_assembled(p);
   p->sys_deferred = false;   // every array is written: a deferred system is superseded
@@ -310,7 +351,7 @@ void do_assemble(egs_problem *p, double dt, double erp) {
 
 void do_assemble_each(egs_problem *p, const EnsembleRates &r) {
   const AssembleArgs a = assemble_args(p, 0.0, 0.0);   // the scalar pair is not read
-  with_real(p, [&](auto t) { launch_assemble_each<decltype(t)>(a, r, p->ctx->stream); });
+  with_real(p, [&](auto t) { launch_assemble_each<decltype(t)>(a, r, p->angular, motor_table(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   note_assembled(p);
   p->sys_deferred = false;
@@ -321,7 +362,7 @@ void ensure_system(egs_problem *p) {
   if (!p->sys_deferred) return;
   AssembleArgs a = assemble_args(p, p->deferred_dt, p->deferred_erp);
   if (p->deferred_prev) { a.pos = p->prev_pos.p; a.R = p->prev_R.p; a.v = p->prev_v.p; a.w = p->prev_w.p; }
-  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->ctx->stream); });
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, motor_table(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   p->sys_deferred = false;
 }
@@ -432,6 +473,9 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   if (p->start_mode == EGS_START_GIVEN) p->start_mode = EGS_START_RHS;
   p->friction = false;   // the coefficients were those of the old list (the world refills them: world_step.cpp)
   p->restitution = false;   // likewise
+  p->motors = false;        // likewise
+  p->hinges = p->hinges_pinned = p->angular = false;
+  p->h_kind.clear();
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
     const int force = env ? std::atoi(env) : -1;
@@ -670,6 +714,30 @@ egs_status egs_problem_set_restitution(egs_problem *p, const double *rest, doubl
   });
 }
 
+egs_status egs_problem_set_motors(egs_problem *p, const double *motor) {
+  if (!p) return EGS_ERR_INVALID;
+  const size_t m = (size_t)p->m;
+  bool any = false;
+  for (size_t i = 0; motor && i < m; ++i) {
+    const double speed = motor[2 * i], tau = motor[2 * i + 1];
+    if (speed != speed || std::isinf(speed)) return fail(p->ctx, EGS_ERR_INVALID, "NaN or infinite motor speed");
+    if (tau != tau) return fail(p->ctx, EGS_ERR_INVALID, "NaN motor torque limit");
+    any |= tau >= 0 && i < p->h_kind.size() && p->h_kind[i] == EGS_JOINT_HINGE_AXIS;
+  }
+  return guarded(p->ctx, [&]() -> egs_status {
+    ensure_system(p);   // a deferred system is the one of the table its step ran with
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));   // an assembly in flight may still read the old table
+    if (any) {
+      p->motor.alloc(m * 2);
+      upload(p->motor, motor, m * 2, p->ctx->stream);
+    }
+    p->motors = any;
+    note_hinges(p, any ? motor : nullptr);
+    p->h_rows_valid = false;   // the axis rows' bounds follow the table
+    return EGS_OK;
+  });
+}
+
 egs_status egs_problem_get_lambda(egs_problem *p, double *x) {
   if (!p || !x) return EGS_ERR_INVALID;
   return guarded(p->ctx, [&]() -> egs_status {
@@ -743,14 +811,13 @@ egs_status egs_problem_get_mass(egs_problem *p, double *Minv, double *f_ext) {
 egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, const double *data) {
   if (!p) return EGS_ERR_INVALID;
   if (p->m > 0 && (!kind || !data)) return fail(p->ctx, EGS_ERR_INVALID, "NULL constraint descriptors");
-  for (int i = 0; i < p->m; ++i)
-    if (kind[i] != EGS_JOINT_BALL && kind[i] != EGS_CONTACT_BOX)
-      return fail(p->ctx, EGS_ERR_INVALID, "unknown constraint kind");
+  if (const char *fault = constraints_fault(p->m, kind, p->h_body0.data(), data)) return fail(p->ctx, EGS_ERR_INVALID, fault);
   return guarded(p->ctx, [&]() -> egs_status {
     ensure_system(p);   // before its inputs change
     upload(p->kind, kind, (size_t)p->m, p->ctx->stream);
     upload(p->data, data, (size_t)p->m * 7, p->ctx->stream);
     note_kinds(p, kind);
+    p->motors = false;   // the table was given for the kinds before these
     p->have_constraints = true;
     p->h_rows_valid = false;
     return EGS_OK;

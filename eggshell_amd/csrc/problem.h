@@ -142,6 +142,16 @@ struct egs_problem {
   egs::DevBuf<double> rest;
   bool restitution = false;
   double rest_vth = 0.0;
+  // Hinge motors (egs_problem_set_motors, egs_world_set_joint_motors): motor [m][2] fp64 = (speed, tau) per constraint;
+  // a HINGE_AXIS constraint with tau >= 0 gets +-tau on its axis row and speed / dt as its target (assemble_device.h:
+  // motor_row).  motors: some hinge has tau >= 0 -- then every assemble_kernel launch takes the table (motor_table);
+  // off, nothing reads it.  A new topology turns it off (the world refills it).  hinges / hinges_pinned: the kinds hold
+  // a HINGE_AXIS / one whose axis row stays pinned at lo = hi = 0 under the table in force (the dense steps refuse it).
+  egs::DevBuf<double> motor;
+  bool motors = false;
+  bool hinges = false, hinges_pinned = false;
+  bool angular = false;                // the kinds hold a LOCK or a HINGE_AXIS: the assembly launches their form (kernels.h)
+  std::vector<int32_t> h_kind;         // the kinds of the list (note_kinds)
   // egs_problem_set_dense_friction: max_outer > 0 makes egs_problem_step_dense solve the pyramid while friction is on
   // (0: it refuses); the outcome of the last such step (egs_problem_dense_friction_info).
   int dense_fric_outer = 0;
@@ -187,8 +197,14 @@ void refresh_live_mass(egs_problem *p);
 // the checks and the state change of egs_problem_set_live_inertia / egs_world_set_live_inertia
 egs_status set_live_inertia(egs_problem *p, const double *inertia_body, const double *torque);
 void note_kinds(egs_problem *p, const int32_t *kind);
+// what egs_problem_set_constraints refuses in a list of kinds and descriptors (NULL: nothing)
+const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, const double *data);
 void note_assembled(egs_problem *p);
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp);
+// the motor table the assembly launches take beside it: p->motor while motors are on, else NULL
+inline const double *motor_table(const egs_problem *p) { return p->motors ? p->motor.p : nullptr; }
+// hinges / hinges_pinned from the kinds and motor [m][2] (NULL: none): problem.h
+void note_hinges(egs_problem *p, const double *motor);
 void do_assemble(egs_problem *p, double dt, double erp);
 // J0, J1, rhs, lo, hi, err and is_eq are materialised after this (a no-op unless the last step deferred them)
 void ensure_system(egs_problem *p);

@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(NT) stab_direct_kernel(StabDirectArgs a, const
   for (;;) {
     for (int i = t; i < me; i += NT) {   // J and err at the current body state, assemble_kernel's operations
       double j0[18], j1[18], ev[3], lo[3], hi[3], u0[6], u1[6];
-      bool eq;
+      bool eq[3];
       assemble_one(a.as, a.cons[c0 + i], j0, j1, ev, lo, hi, eq, u0, u1);
 #pragma unroll
       for (int k = 0; k < 18; ++k) { M.J[36 * i + k] = j0[k]; M.J[36 * i + 18 + k] = j1[k]; }

@@ -154,8 +154,8 @@ __device__ __forceinline__ void linsym_acc_add(REAL *a, const Cons<REAL> &c, con
 template <bool STORE, bool REST>
 __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, Cons<double> &c) {
   double e[3], lo[3], hi[3], u0[6], u1[6];
-  bool eq;
-  assemble_one(G, cidx, c.J0, c.J1, e, lo, hi, eq, u0, u1);
+  bool eq[3];
+  assemble_one<false>(G, cidx, c.J0, c.J1, e, lo, hi, eq, u0, u1);   // contacts only (choose_sweep): no angular block
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     // REST: restitution on the normal row (G.rest is set), here in the prologue only
@@ -166,7 +166,7 @@ __device__ __forceinline__ void assemble_lane(const AssembleArgs &G, int cidx, C
       G.err[(size_t)cidx * 3 + r] = e[r];
       reinterpret_cast<double *>(G.lo)[(size_t)cidx * 3 + r] = lo[r];
       reinterpret_cast<double *>(G.hi)[(size_t)cidx * 3 + r] = hi[r];
-      G.is_eq[(size_t)cidx * 3 + r] = eq ? 1 : 0;
+      G.is_eq[(size_t)cidx * 3 + r] = eq[r] ? 1 : 0;
     }
   }
 }

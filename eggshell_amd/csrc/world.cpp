@@ -12,6 +12,8 @@ using namespace egs;
 
 namespace {
 
+void world_fill_motors(egs_world *w);
+
 void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int m) {
   hipStream_t s = w->ctx->stream;
   if (!w->prob) {
@@ -28,17 +30,38 @@ void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int 
   // constraint kinds: joints first, then contacts; joint descriptors are static
   std::vector<int32_t> kind((size_t)(m > 0 ? m : 1), EGS_CONTACT_BOX);
   const int mj = (int)w->jb0.size();
-  for (int i = 0; i < mj; ++i) kind[i] = EGS_JOINT_BALL;
+  for (int i = 0; i < mj; ++i) kind[i] = w->jkind[(size_t)i];
   if (m > 0) {
     kind.resize((size_t)m);
     stage(w->ctx, np->kind, kind);   // through the pinned arena (reset only after a synchronise): no wait here
     note_kinds(np, kind.data());
     if (mj > 0) upload(np->data, w->jdata.data(), (size_t)mj * 7, s);
   }
+  world_fill_motors(w);
   np->have_constraints = true;
   np->h_rows_valid = false;
   w->topo_b0.assign(b0, b0 + m); w->topo_b1.assign(b1, b1 + m);
   ++w->replans;
+}
+
+// The problem's motor table for its current list from the joints' (the joints come first; no contact row is read:
+// assemble_device.h, motor_row).  The new topology has turned the problem's table off.
+void world_fill_motors(egs_world *w) {
+  egs_problem *p = w->prob;
+  const size_t mj = w->jb0.size();
+  p->motors = false;
+  if (w->jmotor.empty() || p->m <= 0) { note_hinges(p, nullptr); return; }
+  std::vector<double> t((size_t)p->m * 2, -1.0);
+  std::copy(w->jmotor.begin(), w->jmotor.end(), t.begin());
+  bool any = false;
+  for (size_t i = 0; i < mj; ++i) any |= w->jkind[i] == EGS_JOINT_HINGE_AXIS && t[2 * i + 1] >= 0;
+  if (any) {
+    p->motor.alloc(t.size());
+    upload(p->motor, t.data(), t.size(), w->ctx->stream);
+    p->motors = true;
+  }
+  note_hinges(p, any ? t.data() : nullptr);
+  p->h_rows_valid = false;
 }
 
 // What is wrong with a shape array (nothing: an empty string): a value that is no egs_shape, or -- where the side lengths are
@@ -111,7 +134,8 @@ namespace egs {
 void world_update_contacts(egs_world *w, PhaseTimer *lap) {
   hipStream_t s = w->ctx->stream;
   const int mj = (int)w->jb0.size();
-  const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, mj, w->djb0.p, w->djb1.p, w->djdata.p,
+  // the pruning takes the ball joints alone
+  const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, w->mj_ball, w->djb0.p, w->djb1.p, w->djdata.p,
                             w->shapes ? w->dshape.p : nullptr);
   if (lap) (*lap)(0);
   const size_t mt = (size_t)mj + (size_t)mc;
@@ -297,9 +321,13 @@ egs_status egs_world_create_batch(egs_context *ctx, int32_t n_ensembles, const i
   return st;
 }
 
-egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
-                                const double *data) {
+egs_status egs_world_set_joints_kinds(egs_world *w, int32_t m_joints, const int32_t *kind, const int32_t *body0,
+                                      const int32_t *body1, const double *data) {
   if (!w || m_joints < 0 || (m_joints > 0 && (!body0 || !body1 || !data))) return EGS_ERR_INVALID;
+  for (int i = 0; kind && i < m_joints; ++i)
+    if (kind[i] == EGS_CONTACT_BOX) return fail(w->ctx, EGS_ERR_INVALID, "a contact is not a joint");
+  if (kind)
+    if (const char *fault = constraints_fault(m_joints, kind, body0, data)) return fail(w->ctx, EGS_ERR_INVALID, fault);
   EnsembleLayout &L = w->ens;
   std::vector<int32_t> joint_off;
   if (L.n_ens > 1) {   // every joint inside one ensemble, the joints grouped by ensemble (order within kept)
@@ -321,12 +349,25 @@ egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *b
   w->jb0.assign(body0, body0 + m_joints);
   w->jb1.assign(body1, body1 + m_joints);
   w->jdata.assign(data, data + (size_t)m_joints * 7);
+  if (kind) w->jkind.assign(kind, kind + m_joints);
+  else w->jkind.assign((size_t)m_joints, EGS_JOINT_BALL);
+  w->jmotor.clear();   // the motors were those of the old list
+  // the ball joints, in list order: what the collider prunes against
+  std::vector<int32_t> bb0, bb1;
+  std::vector<double> bd;
+  for (int i = 0; i < m_joints; ++i) {
+    if (w->jkind[(size_t)i] != EGS_JOINT_BALL) continue;
+    bb0.push_back(body0[i]); bb1.push_back(body1[i]);
+    bd.insert(bd.end(), data + 7 * (size_t)i, data + 7 * (size_t)i + 7);
+  }
+  const size_t mb = bb0.size();
+  w->mj_ball = (int)mb;
   return guarded(w->ctx, [&]() -> egs_status {
-    w->djb0.alloc((size_t)m_joints); w->djb1.alloc((size_t)m_joints); w->djdata.alloc((size_t)m_joints * 7);
-    if (m_joints > 0) {
-      upload(w->djb0, body0, (size_t)m_joints, w->ctx->stream);
-      upload(w->djb1, body1, (size_t)m_joints, w->ctx->stream);
-      upload(w->djdata, data, (size_t)m_joints * 7, w->ctx->stream);
+    w->djb0.alloc(mb); w->djb1.alloc(mb); w->djdata.alloc(mb * 7);
+    if (mb > 0) {
+      upload(w->djb0, bb0.data(), mb, w->ctx->stream);
+      upload(w->djb1, bb1.data(), mb, w->ctx->stream);
+      upload(w->djdata, bd.data(), mb * 7, w->ctx->stream);
     }
     world_make_problem(w, w->jb0.data(), w->jb1.data(), m_joints);   // contacts are re-detected by the next step
     w->m_contacts = 0;
@@ -338,6 +379,31 @@ egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *b
       HIPCHK(hipMemsetAsync(L.d_coff.p, 0, E1 * sizeof(int32_t), w->ctx->stream));
       L.batch.segs.mj = m_joints;
     }
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
+                                const double *data) {
+  return egs_world_set_joints_kinds(w, m_joints, nullptr, body0, body1, data);
+}
+
+egs_status egs_world_set_joint_motors(egs_world *w, const double *motor) {
+  if (!w) return EGS_ERR_INVALID;
+  const size_t mj = w->jb0.size();
+  for (size_t i = 0; motor && i < mj; ++i) {
+    const double speed = motor[2 * i], tau = motor[2 * i + 1];
+    if (speed != speed || std::isinf(speed)) return fail(w->ctx, EGS_ERR_INVALID, "NaN or infinite motor speed");
+    if (tau != tau) return fail(w->ctx, EGS_ERR_INVALID, "NaN motor torque limit");
+  }
+  return guarded(w->ctx, [&]() -> egs_status {
+    if (w->prob) {
+      ensure_system(w->prob);
+      HIPCHK(hipStreamSynchronize(w->ctx->stream));   // an assembly in flight may still read the old table
+    }
+    if (motor) w->jmotor.assign(motor, motor + 2 * mj);
+    else w->jmotor.clear();
+    if (w->prob) world_fill_motors(w);
     return EGS_OK;
   });
 }
@@ -371,6 +437,14 @@ egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_ou
   if (3 * w->prob->m > max_rows) return fail(w->ctx, EGS_ERR_INVALID, "max_rows too small");
   if (w->prob->m == 0) return EGS_OK;
   return egs_problem_get_lambda(w->prob, lambda);
+}
+
+egs_status egs_world_get_blocks(egs_world *w, double *J0, double *J1, uint8_t *is_eq, double *lo, double *hi, double *rhs,
+                                double *err) {
+  if (!w || !w->prob) return EGS_ERR_INVALID;
+  if (w->prob->m == 0) return EGS_OK;
+  if (!w->prob->have_blocks) return fail(w->ctx, EGS_ERR_INVALID, "no step has assembled the world's list yet");
+  return egs_problem_get_blocks(w->prob, J0, J1, is_eq, lo, hi, rhs, err);
 }
 
 egs_status egs_world_set_friction(egs_world *w, int32_t n_ensembles, const double *mu) {

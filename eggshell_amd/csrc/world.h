@@ -145,8 +145,11 @@ struct egs_world {
   egs::Collider col;
   std::vector<int32_t> jb0, jb1;       // permanent constraints (joints), listed first (ensembles.cc:234-239)
   std::vector<double> jdata;
-  egs::DevBuf<int32_t> djb0, djb1;     // the same on the device, for joint-vs-contact pruning
-  egs::DevBuf<double> djdata;
+  std::vector<int32_t> jkind;          // their kinds (egs_world_set_joints_kinds; all EGS_JOINT_BALL from egs_world_set_joints)
+  std::vector<double> jmotor;          // egs_world_set_joint_motors: [joints][2] = (speed, tau); empty: off
+  int mj_ball = 0;                     // how many of them are ball joints
+  egs::DevBuf<int32_t> djb0, djb1;     // the ball joints among them on the device, for joint-vs-contact pruning (an
+  egs::DevBuf<double> djdata;          // angular block has no position): mj_ball entries, in list order
   std::vector<int32_t> topo_b0, topo_b1;
   egs::PinnedArena topo_pinned;        // page-locked landing area for the contact topology
   int32_t *h_b0 = nullptr, *h_b1 = nullptr;

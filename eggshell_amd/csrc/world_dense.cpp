@@ -141,6 +141,17 @@ egs_status world_dense_guard(egs_world *w, int32_t use_bounds) {
     return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense solvers have no friction pyramid (turn friction off first)");
   if (use_bounds != 0 && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "use_bounds must be 0 or 1");
   if (w->friction.any && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
+  // as egs_problem_step_dense: a hinge's axis row is a box row, and one pinned at lo = hi = 0 is not Murty's to solve
+  bool hinges = false, pinned = false;
+  for (size_t i = 0; i < w->jkind.size(); ++i) {
+    if (w->jkind[i] != EGS_JOINT_HINGE_AXIS) continue;
+    hinges = true;
+    pinned = pinned || w->jmotor.empty() || !(w->jmotor[2 * i + 1] > 0);
+  }
+  if (hinges && use_bounds != 1)
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step takes a hinge axis row as a box row: a hinge needs use_bounds = 1");
+  if (pinned)
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   return EGS_OK;
 }
 

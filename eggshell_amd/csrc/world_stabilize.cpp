@@ -89,7 +89,7 @@ void world_relax_assemble(egs_world *w) {
   a.rhs = rx->wres.p;                  // scratch: the solve writes w there
   a.err = real<double>(rx->rhs);
   a.is_eq = w->rx.eq_scratch.p;
-  launch_assemble<double>(a, w->ctx->stream);
+  launch_assemble<double>(a, p->angular, nullptr, w->ctx->stream);   // no motor: the relaxation reads J and err only
   HIPCHK(hipGetLastError());
   rx->have_blocks = true;
   rx->lin_neg = !rx->joint_pairs;

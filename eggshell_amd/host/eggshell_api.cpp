@@ -132,6 +132,139 @@ Vector3d BallAndSocketJoint::GetConstraintPosition() const {  // joints.cc:57-75
   return (p0 + (b1_->p() + b1_->R() * c1_)) / 2;
 }
 
+// ---- the angular blocks (not in the reference; the device's operation order, assemble_device.h) --------------
+static Matrix3d QuatToR(const double q[4]) {   // utils.cc's quaternion matrix in the library's order (quat_to_R)
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  Matrix3d R;
+  R.d[0] = 1.0 - (tyy + tzz); R.d[1] = txy - twz;         R.d[2] = txz + twy;
+  R.d[3] = txy + twz;         R.d[4] = 1.0 - (txx + tzz); R.d[5] = tyz - twx;
+  R.d[6] = txz - twy;         R.d[7] = tyz + twx;         R.d[8] = 1.0 - (txx + tyy);
+  return R;
+}
+
+// a unit quaternion of the rotation matrix, by the largest of the four squared components
+static void RToQuat(const Matrix3d &R, double q[4]) {
+  const double t = R(0, 0) + R(1, 1) + R(2, 2);
+  const double c[4] = {1 + t, 1 + 2 * R(0, 0) - t, 1 + 2 * R(1, 1) - t, 1 + 2 * R(2, 2) - t};
+  int k = 0;
+  for (int i = 1; i < 4; ++i) if (c[i] > c[k]) k = i;
+  const double s = 2.0 * std::sqrt(c[k]);
+  if (k == 0) { q[0] = s / 4; q[1] = (R(2, 1) - R(1, 2)) / s; q[2] = (R(0, 2) - R(2, 0)) / s; q[3] = (R(1, 0) - R(0, 1)) / s; }
+  else if (k == 1) { q[0] = (R(2, 1) - R(1, 2)) / s; q[1] = s / 4; q[2] = (R(0, 1) + R(1, 0)) / s; q[3] = (R(0, 2) + R(2, 0)) / s; }
+  else if (k == 2) { q[0] = (R(0, 2) - R(2, 0)) / s; q[1] = (R(0, 1) + R(1, 0)) / s; q[2] = s / 4; q[3] = (R(1, 2) + R(2, 1)) / s; }
+  else { q[0] = (R(1, 0) - R(0, 1)) / s; q[1] = (R(0, 2) + R(2, 0)) / s; q[2] = (R(1, 2) + R(2, 1)) / s; q[3] = s / 4; }
+  const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int i = 0; i < 4; ++i) q[i] /= n;
+}
+
+static void AngularRows(ArrayXb *ct, VectorXd *lo, VectorXd *hi, bool axis_row_is_equality) {
+  ct->resize(3); lo->resize(3); hi->resize(3);
+  (*ct)(0) = 1; (*ct)(1) = 1; (*ct)(2) = axis_row_is_equality ? 1 : 0;
+}
+
+AngularLockJoint::AngularLockJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1)
+    : Joint(std::move(b0), i0, Vector3d::Zero(), std::move(b1), i1, Vector3d::Zero()) {
+  const Matrix3d R0t = b0_->R().transpose();
+  RToQuat(b1_ == nullptr ? R0t : R0t * b1_->R(), q_);
+}
+
+VectorXd AngularLockJoint::ComputeError() const {
+  const Matrix3d T = b0_->R() * QuatToR(q_);
+  const Matrix3d E = b1_ == nullptr ? T : T * b1_->R().transpose();
+  return ToX(Vector3d(0.5 * (E.d[7] - E.d[5]), 0.5 * (E.d[2] - E.d[6]), 0.5 * (E.d[3] - E.d[1])));
+}
+
+void AngularLockJoint::ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *ct, VectorXd *lo, VectorXd *hi) const {
+  SetBlock(J_b0, Matrix3d::Zero(), Matrix3d::Identity());
+  if (b1_ == nullptr) SetBlock(J_b1, Matrix3d::Zero(), Matrix3d::Zero());
+  else SetBlock(J_b1, Matrix3d::Zero(), -1.0 * Matrix3d::Identity());
+  AngularRows(ct, lo, hi, true);
+}
+
+bool AngularLockJoint::Describe(int32_t *kind, double data[7]) const {
+  *kind = EGS_JOINT_LOCK;
+  for (int k = 0; k < 4; ++k) data[k] = q_[k];
+  data[4] = data[5] = data[6] = 0;
+  return true;
+}
+
+HingeAxisJoint::HingeAxisJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world)
+    : Joint(std::move(b0), i0, Vector3d::Zero(), std::move(b1), i1, Vector3d::Zero()) {
+  if (!(axis_world.norm() > 0)) throw egs::Error(EGS_ERR_INVALID, "HingeAxisJoint: the axis must not vanish");
+  const Vector3d a = axis_world / axis_world.norm();
+  a0_ = b0_->R().transpose() * a;
+  a0_ = a0_ / a0_.norm();
+  a1_ = b1_ == nullptr ? a : b1_->R().transpose() * a;
+  a1_ = a1_ / a1_.norm();
+}
+
+VectorXd HingeAxisJoint::ComputeError() const {
+  const Vector3d s = b0_->R() * a0_;
+  const Vector3d t = b1_ == nullptr ? a1_ : b1_->R() * a1_;
+  const Matrix3d Rn = AlignVectors(s, Vector3d(0, 0, 1));
+  const Vector3d c = t.cross(s);
+  return ToX(Vector3d(Vector3d(Rn.d[0], Rn.d[1], Rn.d[2]).dot(c), Vector3d(Rn.d[3], Rn.d[4], Rn.d[5]).dot(c), 0.0));
+}
+
+void HingeAxisJoint::ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *ct, VectorXd *lo, VectorXd *hi) const {
+  const Matrix3d Rn = AlignVectors(b0_->R() * a0_, Vector3d(0, 0, 1));
+  SetBlock(J_b0, Matrix3d::Zero(), Rn);
+  if (b1_ == nullptr) SetBlock(J_b1, Matrix3d::Zero(), Matrix3d::Zero());
+  else SetBlock(J_b1, Matrix3d::Zero(), -1.0 * Rn);
+  AngularRows(ct, lo, hi, false);
+  if (tau_ >= 0) { (*lo)(2) = -tau_; (*hi)(2) = tau_; }
+}
+
+bool HingeAxisJoint::Describe(int32_t *kind, double data[7]) const {
+  *kind = EGS_JOINT_HINGE_AXIS;
+  for (int k = 0; k < 3; ++k) { data[k] = a0_[k]; data[3 + k] = a1_[k]; }
+  data[6] = 0;
+  return true;
+}
+
+// [joints][2] = (speed, tau) of a joint list, (0, -1) for whatever is no motored hinge; returns whether any hinge is driven
+static bool JointMotors(const JointsList &joints, std::vector<double> *motor) {
+  bool any = false;
+  motor->assign(2 * joints.size(), 0.0);
+  for (size_t j = 0; j < joints.size(); ++j) {
+    (*motor)[2 * j + 1] = -1.0;
+    const auto *h = dynamic_cast<const HingeAxisJoint *>(joints[j].get());
+    if (!h || !(h->motor_torque() >= 0)) continue;
+    (*motor)[2 * j] = h->motor_speed(); (*motor)[2 * j + 1] = h->motor_torque();
+    any = true;
+  }
+  return any;
+}
+
+int Ensemble::AddWeld(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world) {
+  const Vector3d c0 = b0->R().transpose() * (anchor_world - b0->p());
+  if (b1 == nullptr) joints_.push_back(std::make_shared<BallAndSocketJoint>(b0, i0, c0, anchor_world));
+  else joints_.push_back(std::make_shared<BallAndSocketJoint>(b0, i0, c0, b1, i1, b1->R().transpose() * (anchor_world - b1->p())));
+  joints_.push_back(std::make_shared<AngularLockJoint>(b0, i0, b1, i1));
+  return (int)joints_.size() - 1;
+}
+
+int Ensemble::AddHinge(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world,
+                       const Vector3d &axis_world) {
+  auto hinge = std::make_shared<HingeAxisJoint>(b0, i0, b1, i1, axis_world);   // (throws before anything is added)
+  const Vector3d c0 = b0->R().transpose() * (anchor_world - b0->p());
+  if (b1 == nullptr) joints_.push_back(std::make_shared<BallAndSocketJoint>(b0, i0, c0, anchor_world));
+  else joints_.push_back(std::make_shared<BallAndSocketJoint>(b0, i0, c0, b1, i1, b1->R().transpose() * (anchor_world - b1->p())));
+  joints_.push_back(hinge);
+  return (int)joints_.size() - 1;
+}
+
+void Ensemble::SetHingeMotor(int index, double speed, double max_torque) {
+  auto *h = index >= 0 && index < (int)joints_.size() ? dynamic_cast<HingeAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!h) throw egs::Error(EGS_ERR_INVALID, "SetHingeMotor: joint " + std::to_string(index) + " is not a hinge");
+  if (speed != speed || std::isinf(speed) || max_torque != max_torque)
+    throw egs::Error(EGS_ERR_INVALID, "SetHingeMotor: the speed must be finite and the torque limit a number");
+  h->SetMotor(speed, max_torque);
+}
+
 // ---- contact.cc ----------------------------------------------------------
 VectorXd Contact::ComputeError() const {  // contact.cc:14-22
   VectorXd e(3);
@@ -600,6 +733,15 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
     }
     egs::check(egs_problem_set_state(problem_, pos.data(), R.data(), vl.data(), w.data(), Minv.data(), external_force_torque_.data()));
     egs::check(egs_problem_set_constraints(problem_, kind.data(), data.data()));
+    bool hinges = false;
+    for (int i = 0; i < m; ++i) hinges = hinges || kind[i] == EGS_JOINT_HINGE_AXIS;
+    if (hinges) {   // the joints come first in cs: their motors, then no motor for the contacts
+      std::vector<double> motor;
+      if (JointMotors(joints_, &motor)) {
+        motor.resize(2 * (size_t)m, -1.0);
+        egs::check(egs_problem_set_motors(problem_, motor.data()));
+      }
+    }
     if (restitution_ >= 0) {   // every contact the coefficient, every joint -1
       std::vector<double> rest((size_t)m);
       for (int i = 0; i < m; ++i) rest[i] = kind[i] == EGS_CONTACT_BOX ? restitution_ : -1.0;
@@ -626,10 +768,11 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
       egs::check(egs_problem_dense_condition(problem_, 0.0, &last_condition_estimate));
       const double cfm = last_condition_estimate < 1e7 ? 0.0 : cfm_coeff;   // kGoodConditionNumber, constants.h:12
       int32_t ok = 0, pivots = 0;
-      egs_status rc = egs_problem_step_dense(problem_, dt, erp, cfm, /*use_bounds=*/dense_fric_outer_ > 0 ? 1 : 0, &ok, &pivots);
+      // a hinge's axis row is a box row: an ensemble that holds one steps with the stored bounds
+      egs_status rc = egs_problem_step_dense(problem_, dt, erp, cfm, /*use_bounds=*/dense_fric_outer_ > 0 || hinges ? 1 : 0, &ok, &pivots);
       if (rc != EGS_OK || !ok)   // the reference Panics here (ensembles.cc:531-534)
         throw egs::Error(rc != EGS_OK ? rc : EGS_ERR_LCP_FAILED,
-                         rc == EGS_ERR_INVALID ? egs_last_error(egs::DefaultContext())
+                         rc == EGS_ERR_INVALID || rc == EGS_ERR_UNSUPPORTED ? egs_last_error(egs::DefaultContext())
                                                : "Lcp::MixedConstraintsSolver exited without reaching a solution.");
       last_dense_outer = 1; last_dense_converged = true;
       if (pyramid) {
@@ -733,6 +876,7 @@ void Ensemble::UpdateContacts() {  // ensembles.cc:445-480 (+ :308-328)
   std::vector<std::shared_ptr<Joint>> host_joints;
   for (const auto &j : joints_) {
     if (j->i0_ < 0 || j->i1_ < 0) continue;   // the pair scan never visits the ground (quirk Q4)
+    if (!j->HasPosition()) continue;          // an angular block prunes nothing
     int32_t kind = 0;
     double d7[7];
     if (j->Describe(&kind, d7)) { jb0.push_back(j->i0_); jb1.push_back(j->i1_); jdata.insert(jdata.end(), d7, d7 + 7); }
@@ -764,6 +908,7 @@ void Ensemble::CheckAndCorrectEnsembleState() {
   if (external_force_torque_.size() != 6 * n_) throw egs::Error(EGS_ERR_INVALID, "external_force_torque_ dimensions are incorrect.");
   auto key_of = [](int a, int b) { return a < b ? std::make_pair(a, b) : std::make_pair(b, a); };
   auto close = [](const Constraint &c1, const Constraint &c2) {   // CheckConstraintPair, ensembles.cc:376-388
+    if (!c1.HasPosition() || !c2.HasPosition()) return false;      // an angular block is close to nothing
     return (c1.GetConstraintPosition() - c2.GetConstraintPosition()).norm() < 1e-6;
   };
   // joint vs joint: conflict or overconstraint -> the reference Panics (ensembles.cc:280-289)
@@ -836,12 +981,13 @@ void Ensemble::SetDenseFriction(int max_outer, double tol) {
 bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
-  std::vector<int32_t> jb0(mj), jb1(mj), kind(1);
-  std::vector<double> jdata((size_t)mj * 7);
+  std::vector<int32_t> jb0(mj), jb1(mj), jkind(mj);
+  std::vector<double> jdata((size_t)mj * 7), jmotor;
   for (int i = 0; i < mj; ++i) {
     jb0[i] = joints_[i]->i0_; jb1[i] = joints_[i]->i1_;
-    if (!joints_[i]->Describe(&kind[0], &jdata[(size_t)i * 7])) return false;
+    if (!joints_[i]->Describe(&jkind[i], &jdata[(size_t)i * 7])) return false;
   }
+  const bool motors = JointMotors(joints_, &jmotor);
   if (!detect_contacts && !contacts_.empty()) return false;   // caller-supplied contacts: use the explicit path
   egs_context *ctx = egs::DefaultContext();
   const bool first = !world_;
@@ -892,10 +1038,16 @@ bool Ensemble::StepOnDevice(double dt) {
     if (const std::vector<int32_t> shape = Shapes(); !shape.empty()) egs::check(egs_world_set_shapes(world_, shape.data()));
   // joints are permanent in the reference (ensembles.cc:331-334); a caller that edits them all the same
   // (same count, other bodies or anchors) must not step against the stale device copy
-  if (world_joints_ != mj || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {
-    egs::check(egs_world_set_joints(world_, mj, jb0.data(), jb1.data(), jdata.data()));
+  if (world_joints_ != mj || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_ || jkind != world_jkind_) {
+    egs::check(egs_world_set_joints_kinds(world_, mj, jkind.data(), jb0.data(), jb1.data(), jdata.data()));
     world_joints_ = mj;
-    world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata;
+    world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata; world_jkind_ = jkind;
+    world_jmotor_.assign(2 * (size_t)mj, 0.0);
+    for (int i = 0; i < mj; ++i) world_jmotor_[2 * (size_t)i + 1] = -1.0;
+  }
+  if (jmotor != world_jmotor_) {
+    egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
+    world_jmotor_ = jmotor;
   }
   egs_solve_params prm = solver_params;
   prm.cfm = cfm_coeff;
@@ -1036,8 +1188,11 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   const size_t n = (size_t)off_[E];
   std::vector<double> pos(n * 3), R(n * 9), vl(n * 3), w(n * 3), Minv(first ? n * 36 : 0), side(first ? n * 3 : 0),
       fext(first ? n * 6 : 0);
-  std::vector<int32_t> jb0, jb1;
-  std::vector<double> jdata;
+  std::vector<int32_t> jb0, jb1, jkind;
+  std::vector<double> jdata, jmotor;
+  bool motors = false, hinges = false;
+  for (size_t i = 0; i < E; ++i)
+    for (const auto &j : members_[i]->joints_) hinges = hinges || dynamic_cast<const HingeAxisJoint *>(j.get()) != nullptr;
   for (size_t i = 0; i < E; ++i) {
     const Ensemble *m = members_[i];
     const size_t o = (size_t)off_[i];
@@ -1070,7 +1225,11 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
       jb0.push_back(a >= 0 ? a + (int32_t)o : -1);
       jb1.push_back(b >= 0 ? b + (int32_t)o : -1);
       jdata.insert(jdata.end(), d, d + 7);
+      jkind.push_back(kind);
     }
+    std::vector<double> own;
+    motors = JointMotors(m->joints_, &own) || motors;
+    jmotor.insert(jmotor.end(), own.begin(), own.end());
   }
   const Ensemble *lead = members_[0];
   for (size_t i = 1; i < E; ++i)   // (the constructor's check, again: SetWarmStart may have been called since)
@@ -1149,16 +1308,22 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     if (any) egs::check(egs_world_set_shapes(world_, shape.data()));
   }
   world_state_.clear();
-  if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_) {   // re-sent when edited
-    egs::check(egs_world_set_joints(world_, (int32_t)jb0.size(), jb0.data(), jb1.data(), jdata.data()));
+  if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_ || jkind != world_jkind_) {   // re-sent when edited
+    egs::check(egs_world_set_joints_kinds(world_, (int32_t)jb0.size(), jkind.data(), jb0.data(), jb1.data(), jdata.data()));
     joints_sent_ = true;
-    world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata;
+    world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata; world_jkind_ = jkind;
+    world_jmotor_.assign(2 * jb0.size(), 0.0);   // a new joint list has no motors
+    for (size_t j = 0; j < jb0.size(); ++j) world_jmotor_[2 * j + 1] = -1.0;
+  }
+  if (jmotor != world_jmotor_) {   // ... and the motors with them
+    egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
+    world_jmotor_ = jmotor;
   }
   const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
   if (lead->use_dense_solver) {
     egs::check(egs_world_set_dense_friction(world_, lead->dense_fric_outer_, lead->dense_fric_tol_));
     egs::check(egs_world_step_dense_each(world_, (int32_t)E, dt.data(), erp.data(), lead->cfm_coeff,
-                                         /*use_bounds=*/lead->dense_fric_outer_ > 0 ? 1 : 0, lead->detect_contacts ? 1 : 0, nullptr));
+                                         /*use_bounds=*/lead->dense_fric_outer_ > 0 || hinges ? 1 : 0, lead->detect_contacts ? 1 : 0, nullptr));
     std::vector<int32_t> outer(E), conv(E);
     egs::check(egs_world_dense_friction_info(world_, (int32_t)E, outer.data(), conv.data(), nullptr));
     for (size_t i = 0; i < E; ++i) { members_[i]->last_dense_outer = outer[i]; members_[i]->last_dense_converged = conv[i] != 0; }

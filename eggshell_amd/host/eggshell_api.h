@@ -101,6 +101,9 @@ class Constraint {  // constraints.h:14-48
   virtual bool Describe(int32_t *kind, double data[7]) const { (void)kind; (void)data; return false; }
   // Get the global frame constraint position (constraints.h:38-39).
   virtual Vector3d GetConstraintPosition() const = 0;
+  // Not in the reference: false for a constraint that acts on orientations only (AngularLockJoint, HingeAxisJoint).
+  // It has no position, so the closeness scans (CheckAndCorrectEnsembleState, the contact pruning) pass it over.
+  virtual bool HasPosition() const { return true; }
   int i0_ = -1;
   int i1_ = -1;
 
@@ -128,6 +131,46 @@ class BallAndSocketJoint : public Joint {  // joints.h:31-50
                 VectorXd *constraint_hi) const override;                    // joints.cc:13-35
   bool Describe(int32_t *kind, double data[7]) const override;
   Vector3d GetConstraintPosition() const override;                          // joints.cc:57-75
+};
+
+// Not in the reference, whose joints.h announces a "library of all joint types" and holds the ball joint alone: the
+// two angular blocks of the library (EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS; include/eggshell_amd.h has the formulas).
+// Beside a BallAndSocketJoint on the same two bodies they make a weld and a hinge (Ensemble::AddWeld / AddHinge).
+// b1 = nullptr, i1 = -1: to the world.  ComputeError / ComputeJ follow the device's operation order.
+class AngularLockJoint : public Joint {
+ public:
+  // holds the relative orientation the two bodies have now
+  AngularLockJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1);
+  VectorXd ComputeError() const override;                                   // the axial vector of R0 Rq R1^T: sin(theta) n
+  void ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *constraint_type, VectorXd *constraint_lo,
+                VectorXd *constraint_hi) const override;                    // [0 | I], [0 | -I]; three equality rows
+  bool Describe(int32_t *kind, double data[7]) const override;
+  Vector3d GetConstraintPosition() const override { return Vector3d::Zero(); }
+  bool HasPosition() const override { return false; }
+
+ private:
+  double q_[4];   // (w, x, y, z) of R0(0)^T R1(0)
+};
+
+class HingeAxisJoint : public Joint {
+ public:
+  // axis_world: the hinge axis at the bodies' current pose (any length > 0)
+  HingeAxisJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world);
+  VectorXd ComputeError() const override;                                   // (p . c, q . c, 0), c = t x s
+  void ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *constraint_type, VectorXd *constraint_lo,
+                VectorXd *constraint_hi) const override;                    // [0 | Rn], [0 | -Rn]; the axis row an inequality row
+  bool Describe(int32_t *kind, double data[7]) const override;
+  Vector3d GetConstraintPosition() const override { return Vector3d::Zero(); }
+  bool HasPosition() const override { return false; }
+  // the motor (egs_problem_set_motors): the solve asks for axis . (w0' - w1') = speed within +-max_torque (+inf
+  // allowed); max_torque < 0: no motor, the hinge turns freely
+  void SetMotor(double speed, double max_torque) { speed_ = speed; tau_ = max_torque; }
+  double motor_speed() const { return speed_; }
+  double motor_torque() const { return tau_; }
+
+ private:
+  Vector3d a0_, a1_;   // the unit axis in body0's frame and in body1's (the world's for a world side)
+  double speed_ = 0.0, tau_ = -1.0;
 };
 
 struct ContactGeometry {  // collision.h:12-27
@@ -356,6 +399,18 @@ class Ensemble {  // ensembles.h:25-186
   // egs::Error(EGS_ERR_UNSUPPORTED) while it is on.  Throws egs::Error(EGS_ERR_INVALID): e NaN or infinite, threshold
   // < 0, NaN or infinite.
   void SetRestitution(double e, double threshold = 0.0);
+  // Not in the reference: a weld and a hinge between components b0 (index i0) and b1 (i1; nullptr and -1: the world),
+  // each a BallAndSocketJoint at anchor_world plus an angular block captured from the current pose (AngularLockJoint;
+  // HingeAxisJoint about axis_world).  Both return the index of the angular joint in the ensemble's joints; call them
+  // before Init().  SetHingeMotor drives the hinge at that index: speed rad/s about the axis (body0 relative to
+  // body1) within +-max_torque, +inf allowed; max_torque < 0 removes the motor.  Throws egs::Error(EGS_ERR_INVALID)
+  // for an index that is no hinge, a NaN or an infinite speed.  A hinge without a motor, or with max_torque = 0,
+  // steps through the sweeps only: with use_dense_solver the library's EGS_ERR_UNSUPPORTED is thrown.
+  int AddWeld(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world);
+  int AddHinge(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world,
+               const Vector3d &axis_world);
+  void SetHingeMotor(int index, double speed, double max_torque);
+  const JointsList &joints() const { return joints_; }
   double restitution() const { return restitution_; }
   double restitution_threshold() const { return restitution_vth_; }
   // The pyramid on the dense direct solver, opt-in (egs_problem_set_dense_friction / egs_world_set_dense_friction):
@@ -419,6 +474,8 @@ class Ensemble {  // ensembles.h:25-186
   int world_joints_ = -1;
   std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds
   std::vector<double> world_jdata_;
+  std::vector<int32_t> world_jkind_;             // ... their kinds and their motors ([joints][2], (0, -1): none)
+  std::vector<double> world_jmotor_;
   bool warm_start_ = false, world_warm_ = false;   // asked for; what the device world was last told
   double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
   Contact::FrictionModel friction_model_ = Contact::FrictionModel::BOX;
@@ -493,6 +550,8 @@ class EnsembleGroup {
   bool joints_sent_ = false;
   std::vector<int32_t> world_jb0_, world_jb1_;   // the joints the device world holds
   std::vector<double> world_jdata_;
+  std::vector<int32_t> world_jkind_;             // ... their kinds and their motors, re-sent with them
+  std::vector<double> world_jmotor_;
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
   std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)

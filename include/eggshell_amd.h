@@ -54,7 +54,7 @@ typedef enum {
 typedef enum { EGS_JACOBI = 0, EGS_GAUSS_SEIDEL = 1, EGS_SOR = 2 } egs_method;
 typedef enum { EGS_F64 = 0, EGS_F32 = 1 } egs_precision;
 /* constraint descriptor kinds for device-side assembly */
-typedef enum { EGS_JOINT_BALL = 0, EGS_CONTACT_BOX = 1 } egs_constraint_kind;
+typedef enum { EGS_JOINT_BALL = 0, EGS_CONTACT_BOX = 1, EGS_JOINT_LOCK = 2, EGS_JOINT_HINGE_AXIS = 3 } egs_constraint_kind;
 
 /* Runtime form of the reference's compile-time constants:
  *   omega = 1.5 and max_iters = 500 (sparse_iterations.cc:15-19),
@@ -261,6 +261,39 @@ egs_status egs_problem_dense_friction_info(egs_problem *p, int32_t *outer, int32
  *      this call.  A new topology turns it off (the coefficients belong to the list they were given for).
  *      EGS_ERR_INVALID: a NaN or infinite coefficient, vth < 0, NaN or infinite (nothing changes).                   */
 egs_status egs_problem_set_restitution(egs_problem *p, const double *rest /*[m] or NULL = off*/, double vth);
+
+/* ---- Angular joint blocks and the hinge motor.  The reference's joints.h has the ball joint alone.  Two angular 3x6
+ *      blocks stand beside it, so that weld = BALL + LOCK and hinge = BALL + HINGE_AXIS on the same two bodies.  Both are
+ *      joints in every sense: listed first in a world, never bouncing, friction coefficient -1, their own previous rows
+ *      in a warm start.  Their linear Jacobian columns are exactly zero; err is (body0 quantity) - (body1 quantity) and
+ *      d err/dt = J0 s0 + J1 s1 at err = 0, as for the ball joint.  body0 must be a body; body1 = -1 is the world.
+ *      Assembled in fp64 without contraction in this order (mv3, mm3, d3, quat_to_R, align_to_z: assemble_device.h):
+ *      EGS_JOINT_LOCK, data = (qw, qx, qy, qz, 0, 0, 0), the unit quaternion of Rref = R0(0)^T R1(0) (R0(0)^T, the
+ *      target orientation transposed, for a world side):
+ *          Rq = quat_to_R(q);  T = mm3(R0, Rq);  E = mm3(T, R1^T), R1^T formed by index     (a world side: E = T)
+ *          err = (0.5*(E[7]-E[5]), 0.5*(E[2]-E[6]), 0.5*(E[3]-E[1]))       row-major: the axial vector, sin(theta) n
+ *          J0 = [0 | I3], J1 = [0 | -1.0*I3] (zero for a world side); three equality rows, lo = hi = 0
+ *      EGS_JOINT_HINGE_AXIS, data = (a0[3], a1[3], 0): the unit axis in body0's frame and in body1's (the world axis for
+ *      a world side):
+ *          s = mv3(R0, a0);  t = mv3(R1, a1) (a world side: a1);  Rn = align_to_z(s), rows (p, q, s^)
+ *          c = t x s = (t1 s2 - t2 s1, t2 s0 - t0 s2, t0 s1 - t1 s0);  err = (d3(p, c), d3(q, c), 0)
+ *          J0 = [0 | Rn], J1 = [0 | -1.0*Rn] (zero for a world side)
+ *      Rows 0 and 1 are equality rows.  Row 2, the axis row, is an inequality row with lo = hi = 0: its multiplier is
+ *      pinned at 0 and the hinge turns freely.  Both linearise sin(theta): they hold for errors below a right angle, and
+ *      t = -s (the axes antiparallel) is a false equilibrium with err = 0.
+ *      egs_problem_set_motors: motor [m][2] = (speed, tau) per constraint.  For a HINGE_AXIS constraint with tau >= 0
+ *      (+inf allowed) the assembly sets lo[2] = -tau, hi[2] = +tau and rhs[2] = speed / dt - ju (the ensemble's dt in
+ *      the _each forms; an ensemble sitting a step out keeps rhs = 0), so the solve asks for s^ . (w0' - w1') = speed
+ *      within the torque limit.  tau < 0, and every other kind, is assembled as stored.  motor = NULL, or no hinge with
+ *      tau >= 0, turns it off: every result and schedule flag is then what it is without this call.  A new topology or
+ *      a new egs_problem_set_constraints turns it off.  EGS_ERR_INVALID: a NaN or infinite speed, a NaN tau (nothing
+ *      changes).
+ *      A list that holds one of these kinds never runs EGS_SCHED_LINSYM, FUSED_ASSEMBLY, PAIR or CHAIN; lists without
+ *      them keep their schedules and their bits.  The dense steps (egs_problem_step_dense, egs_world_step_dense[_each])
+ *      take LOCK rows as equality rows and a motored axis row with tau > 0 as a box row (use_bounds bit 0); an axis row
+ *      pinned at lo = hi = 0 (no motor, or tau = 0) does not meet Murty's preconditions (lcp.cc:161-164), so they return
+ *      EGS_ERR_UNSUPPORTED for it, and for any hinge when use_bounds bit 0 is clear.                                   */
+egs_status egs_problem_set_motors(egs_problem *p, const double *motor /*[m][2] or NULL = off*/);
 
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
@@ -602,12 +635,26 @@ egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape);
 /* ball joints: body0/body1 [m], data [m][7] = c0, c1 (world point if body1 = -1), 0 */
 egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
                                 const double *data);
+/* ... of any joint kind (EGS_JOINT_BALL, EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS; data as egs_problem_set_constraints
+ * takes it, checked the same way).  kind = NULL, or all EGS_JOINT_BALL, is egs_world_set_joints bit for bit.  Only the
+ * ball joints take part in the joint-versus-contact pruning of the collider: an angular block has no position.  The
+ * batch rules are those of egs_world_set_joints.  Drops the motors of an earlier list.                          */
+egs_status egs_world_set_joints_kinds(egs_world *w, int32_t m_joints, const int32_t *kind /*[m_joints] or NULL*/,
+                                      const int32_t *body0, const int32_t *body1, const double *data);
+/* egs_problem_set_motors for the world's joints: motor [m_joints][2] = (speed, tau), NULL = off.  Every step's
+ * assembly carries it, re-planned lists included; the stabilise entries work on positions and ignore it.
+ * EGS_ERR_INVALID as egs_problem_set_motors (nothing changes).                                                   */
+egs_status egs_world_set_joint_motors(egs_world *w, const double *motor /*[m_joints][2] or NULL = off*/);
 egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_params *params,
                           int32_t detect_contacts, egs_solve_stats *stats);
 egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v, double *w_ang);
 egs_status egs_world_get_contacts(egs_world *w, int32_t max_contacts, int32_t *m_out, int32_t *body0,
                                   int32_t *body1, double *data);
 egs_status egs_world_get_lambda(egs_world *w, int32_t max_rows, int32_t *rows_out, double *lambda);
+/* The system the last step assembled, as egs_problem_get_blocks returns it, joints first: m = egs_world_info's
+ * n_constraints, J0 / J1 [m][18], is_eq / lo / hi / rhs / err [3m]; any pointer may be NULL. */
+egs_status egs_world_get_blocks(egs_world *w, double *J0, double *J1, uint8_t *is_eq, double *lo, double *hi,
+                                double *rhs, double *err);
 /* Live inertia for the world's bodies: egs_problem_set_live_inertia / egs_problem_get_mass (above) with global body
  * indices in a batched world.  The refresh is the first thing every egs_world_step[_each] and
  * egs_world_step_dense[_each] enqueues; the stabilise entries work with M = I and do not refresh -- the step after
