@@ -27,6 +27,7 @@ SCHED_START = 1024
 SCHED_FRICTION = 2048
 SCHED_PAIR = 4096
 SCHED_CHAIN = 8192
+SCHED_SHARE = 16384
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
@@ -39,12 +40,12 @@ EXPORTS = [
     "egs_problem_set_state", "egs_problem_set_mass", "egs_problem_set_constraints", "egs_problem_assemble",
     "egs_problem_step", "egs_problem_get_blocks", "egs_problem_get_velocity",
     "egs_problem_advance", "egs_problem_get_state",
-    "egs_problem_get_stats", "egs_problem_get_schedule", "egs_mixed_constraints_solve", "egs_debug_plan", "egs_debug_plan_slots",
+    "egs_problem_get_stats", "egs_problem_get_schedule", "egs_problem_get_schedule_full", "egs_mixed_constraints_solve", "egs_debug_plan", "egs_debug_plan_slots",
     "egs_update_contacts", "egs_update_contacts_joints", "egs_world_create", "egs_world_destroy", "egs_world_set_bodies",
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
-    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
+    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
@@ -675,6 +676,12 @@ class Problem:
         self.ctx.check(load().egs_problem_get_schedule(self.h, C.byref(out)))
         return int(out.value)
 
+    def schedule_full(self):
+        """... and SCHED_SHARE with them (see egs_problem_get_schedule_full)."""
+        out = C.c_int32(0)
+        self.ctx.check(load().egs_problem_get_schedule_full(self.h, C.byref(out)))
+        return int(out.value)
+
     def lambda_(self):
         x = np.zeros(3 * self.m)
         self.ctx.check(load().egs_problem_get_lambda(self.h, _p(x)))
@@ -876,6 +883,19 @@ def debug_plan_chained(n_bodies, body0, body1):
     st = load().egs_debug_plan_chained(C.c_int32(n_bodies), C.c_int32(body0.shape[0]), _p(body0), _p(body1), C.byref(out))
     if st != OK:
         raise EgsError(st, "egs_debug_plan_chained failed")
+    return bool(out.value)
+
+
+def debug_plan_share(n_bodies, body0, body1, data):
+    """Host-only: is the plan chained, and do the two contacts of every thread pair carry the same normal bit for bit
+    (see egs_debug_plan_share)?  data: the constraint descriptors [m][7]."""
+    body0, body1 = _i32(body0), _i32(body1)
+    data = np.ascontiguousarray(data, dtype=np.float64).reshape(body0.shape[0], 7)
+    out = C.c_int32(0)
+    st = load().egs_debug_plan_share(C.c_int32(n_bodies), C.c_int32(body0.shape[0]), _p(body0), _p(body1), _p(data),
+                                     C.byref(out))
+    if st != OK:
+        raise EgsError(st, "egs_debug_plan_share failed")
     return bool(out.value)
 
 

@@ -147,8 +147,10 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 // pair: the PAIR form, one update on a lane pair (step_solve.hip); the same bits on any plan, worth it on a pairable one
 // chain (with pair, on a plan that is Plan::chained, a.steady on): the CHAIN form of its steady loop, the pair's
 // accumulators in registers between its two updates; the same bits
+// share (with chain, where the two contacts of every thread pair carry one normal: problem.h, share_normals): the SHARE
+// form, one linear block and one pair of weights per lane for both constraints; the same bits
 void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
-                                hipStream_t s);
+                                bool share, hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);
@@ -256,6 +258,9 @@ void launch_minv_iso(int n, const REAL *W, int *flag, hipStream_t s);
 // the same linear weight W[0] bit for bit (the body preconditions of step_solve_kernel's LINSYM form)
 template <typename REAL>
 void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, const REAL *W, int *flag, hipStream_t s);
+// plan_shares_normals (plan.h) on the device, for a chained plan of 256-lane tiles: *flag &= the two constraints of
+// every thread pair have the same three normal bit patterns in data [m][7]
+void launch_share_normals(int n_tiles, const LaneDesc *lanes, const double *data, int *flag, hipStream_t s);
 
 // A = J M^-1 J^T + cfm I, [3m][3m] row-major fp64 on the device (ensembles.cc:510, 513-521)
 void launch_dense_system(int m, const int32_t *body0, const int32_t *body1, const double *J0, const double *J1,

@@ -637,6 +637,17 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
   if (!ok) atomicAnd(flag, 0);
 }
 
+// thread i = pair l of wavefront w of tile t, i = (4 t + w) * 32 + l: plan lanes 64 w + l and 64 w + 32 + l
+__global__ void __launch_bounds__(256) share_normals_kernel(int n_pairs, const LaneDesc *lanes, const double *data, int *flag) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pairs) return;
+  const size_t ia = (size_t)(i >> 5) * 64 + (i & 31);
+  const int a = lanes[ia].cidx, b = lanes[ia + 32].cidx;
+  if (a < 0 || b < 0) return;
+  const double *na = data + (size_t)a * 7 + 3, *nb = data + (size_t)b * 7 + 3;
+  if (!(same_bits(na[0], nb[0]) && same_bits(na[1], nb[1]) && same_bits(na[2], nb[2]))) atomicAnd(flag, 0);
+}
+
 // --------------------------------------------------------------------------
 // K1-K4 assembly: the per-constraint body lives in assemble_device.h.
 struct NoRates {};   // the scalar form's (empty) second argument
@@ -1130,6 +1141,12 @@ void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, con
   hipLaunchKernelGGL((linsym_bodies_kernel<REAL>), dim3((m + 255) / 256), dim3(256), 0, s, m, body0, body1, W, flag);
 }
 
+
+void launch_share_normals(int n_tiles, const LaneDesc *lanes, const double *data, int *flag, hipStream_t s) {
+  if (n_tiles <= 0) return;
+  const int n_pairs = n_tiles * 128;
+  hipLaunchKernelGGL(share_normals_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, n_pairs, lanes, data, flag);
+}
 
 template <typename REAL>
 int occupancy_global_solve() {

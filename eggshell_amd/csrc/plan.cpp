@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <numeric>
 #include <stdexcept>
 #include <string>
@@ -805,6 +806,19 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
   }
   phase_clock.mark("patches");
   return plan;
+}
+
+bool plan_shares_normals(const Plan &plan, const double *data) {
+  if (!plan.chained) return false;
+  for (int t = 0; t < plan.n_tiles; ++t)
+    for (int w = 0; w < plan.block / 64; ++w)
+      for (int l = 0; l < 32; ++l) {
+        const size_t ia = (size_t)t * plan.block + 64 * w + l;
+        const int a = plan.lanes[ia].cidx, b = plan.lanes[ia + 32].cidx;
+        if (a < 0 || b < 0) continue;
+        if (std::memcmp(data + 7 * (size_t)a + 3, data + 7 * (size_t)b + 3, 3 * sizeof(double)) != 0) return false;
+      }
+  return true;
 }
 
 void set_patch_workgroups(int n) { if (n > 0) g_patch_workgroups = n; }

@@ -104,6 +104,12 @@ constexpr int kAutoQuadBlock = 0;
 Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
                 int block, Plan *recycle = nullptr, int max_run_tiles = 0);
 
+// What the SHARE form of the fused step launch (step_solve.hip) asks beyond a chained plan: the two constraints of every
+// thread pair, A = plan lane 64 w + l and B = plan lane 64 w + 32 + l, carry one contact normal -- data[7 i + 3 .. 5]
+// (the constraint descriptors, [m][7]) of A and of B are the same three bit patterns (-0.0 is not +0.0) wherever both
+// are active.  A pair with an A and no B asks nothing.  false on a plan that is not chained.
+bool plan_shares_normals(const Plan &plan, const double *data);
+
 // how many workgroups (CUs) an oversize island's patches may occupy at once: sizes the patches (plan.cpp::build_patches)
 void set_patch_workgroups(int n);
 

@@ -163,4 +163,14 @@ egs_status egs_debug_plan_chained(int32_t n, int32_t m, const int32_t *body0, co
   });
 }
 
+egs_status egs_debug_plan_share(int32_t n, int32_t m, const int32_t *body0, const int32_t *body1, const double *data,
+                                int32_t *share) {
+  if (m > 0 && !data) return EGS_ERR_INVALID;
+  return plan_entry(n, m, body0, body1, [&]() -> egs_status {
+    const Plan pl = build_plan(n, m, body0, body1, 256);
+    if (share) *share = plan_shares_normals(pl, data) ? 1 : 0;
+    return EGS_OK;
+  });
+}
+
 }  // extern "C"

@@ -54,6 +54,26 @@ void decide_linsym_bodies(egs_problem *p) {
   p->linsym_bodies = flag != 0 ? 1 : 0;
 }
 
+}  // namespace
+
+namespace egs {
+void decide_share_normals(egs_problem *p) {
+  if (p->share_normals != egs_problem::kShareUndecided) return;
+  p->share_normals = 0;
+  if (!p->tile_plan_ready || !p->plan.chained || p->plan.block != 256 || !p->have_constraints) return;
+  hipStream_t s = p->ctx->stream;
+  int one = 1, flag = 0;
+  int32_t *scratch = p->error_flag.p + 1;
+  HIPCHK(hipMemcpyAsync(scratch, &one, sizeof(int), hipMemcpyHostToDevice, s));
+  launch_share_normals(p->plan.n_tiles, p->tile.lanes.p, p->data.p, scratch, s);
+  HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  p->share_normals = flag != 0 ? 1 : 0;
+}
+}  // namespace egs
+
+namespace {
+
 // two device buffers change places (DevBuf owns its allocation: members, not objects, are exchanged)
 template <typename T>
 void swap_buffers(DevBuf<T> &a, DevBuf<T> &b) {
@@ -444,6 +464,7 @@ void ensure_tile_plan(egs_problem *p) {
   p->gden.alloc(mg * 3 * rsz); p->gdx.alloc(mg * 3 * rsz);
   HIPCHK(hipStreamSynchronize(s));
   p->tile_plan_ready = true;
+  if (p->share_normals >= 0) p->share_normals = egs_problem::kShareUndecided;   // the answer was the old plan's
 }
 
 // (Re)build everything that depends on the constraint topology.  Body state
@@ -460,6 +481,7 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->h_body1.assign(body1, body1 + m);
   p->tile_plan_ready = false;
   p->linsym_bodies = -1;
+  p->share_normals = egs_problem::kShareDeviceData;   // no descriptors yet: egs_problem_set_constraints brings them
   p->mv_ready = false;
   p->dense_cfm = -1.0;
   p->h_rows_valid = false;
@@ -817,6 +839,7 @@ egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, cons
     upload(p->kind, kind, (size_t)p->m, p->ctx->stream);
     upload(p->data, data, (size_t)p->m * 7, p->ctx->stream);
     note_kinds(p, kind);
+    p->share_normals = egs_problem::kShareUndecided;
     p->motors = false;   // the table was given for the kinds before these
     p->have_constraints = true;
     p->h_rows_valid = false;
@@ -945,6 +968,13 @@ egs_status egs_problem_get_schedule(egs_problem *p, int32_t *schedule) {
     *schedule = st.schedule | (int32_t)(p->last_sched & egs_problem::kSchedRefinements);
     return EGS_OK;
   });
+}
+
+egs_status egs_problem_get_schedule_full(egs_problem *p, int32_t *schedule) {
+  if (!p || !schedule) return EGS_ERR_INVALID;
+  const egs_status st = egs_problem_get_schedule(p, schedule);
+  if (st == EGS_OK) *schedule |= (int32_t)(p->last_sched & egs_problem::kSchedFullOnly);
+  return st;
 }
 
 egs_status egs_solve_blocks(egs_context *ctx, int32_t n, const double *Minv, int32_t m, const int32_t *body0,

@@ -55,11 +55,21 @@ struct egs_problem {
   // ... of which egs_solve_stats.schedule leaves these out and egs_problem_get_schedule reports them: refinements of a
   // form that is already reported.  Callers compare that field exactly between a form's switch on and off.
   static constexpr uint32_t kSchedRefinements = EGS_SCHED_CHAIN;
+  // ... and these are left out of egs_problem_get_schedule too, whose callers compare it with EGS_SCHED_CHAIN masked
+  // against the statistics: egs_problem_get_schedule_full alone reports them
+  static constexpr uint32_t kSchedFullOnly = EGS_SCHED_SHARE;
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
   bool contacts_only = false;  // no constraint is a joint (note_kinds): every row has a contact's bounds, (-1, -1, 0) .. (1, 1, +inf)
   int linsym_bodies = -1;      // LINSYM's body preconditions (launch_linsym_bodies) on the device, -1: not decided yet
+  // SHARE's precondition on the chained tile plan (plan.h: plan_shares_normals; launch_share_normals on the device):
+  // 1 / 0, kShareUndecided: data came from the host and nobody has looked yet (the first choose_sweep that offers the
+  // CHAIN form does: decide_share_normals, 4 bytes back), kShareDeviceData: data was, or will be, written on the device
+  // (a world's collider) or is not there yet -- "no" without a look, which would cost a synchronisation per step.
+  // Every writer of data sets one of the last two; a new tile plan turns a decided answer back to undecided.
+  static constexpr int kShareUndecided = -1, kShareDeviceData = -2;
+  int share_normals = kShareDeviceData;
   // which kernel takes the oversize islands of a GS / SOR solve (choose_oversize_schedule; EGS_PATCH=0
   // forces the all-global kernel, EGS_QUAD_PATCH=0 the 1-lane patches) and how many workgroups the
   // all-global kernel's persistent grid may have: both from the runtime's occupancy of the kernels
@@ -189,6 +199,8 @@ REAL *real(const DevBuf<unsigned char> &b) { return reinterpret_cast<REAL *>(b.p
 egs_status check_topology(egs_context *ctx, int32_t n, int32_t m, const int32_t *body0, const int32_t *body1);
 void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const int32_t *body1, bool fresh = true);
 void ensure_tile_plan(egs_problem *p);
+// share_normals of a problem whose tile plan is ready and chained, while it is kShareUndecided (synchronises once)
+void decide_share_normals(egs_problem *p);
 void ensure_minv_real(egs_problem *p);
 // Live inertia: M^-1 (fp64 and working precision), f_ext and Wf of the masked bodies from the R and w the device holds
 // now.  One launch, no synchronisation while the caller's M^-1 / f_ext uploads are converted already; a no-op unless

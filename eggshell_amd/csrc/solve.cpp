@@ -24,6 +24,7 @@ struct SweepSchedule {
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
   bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_solve.hip)
   bool chain = false;       // ... whose steady loop keeps a pair's accumulators in registers between its two updates (CHAIN)
+  bool share = false;       // ... and a thread one linear block and one pair of weights for both constraints (SHARE)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -33,7 +34,7 @@ struct SweepSchedule {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
            (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0) |
-           (chain ? EGS_SCHED_CHAIN : 0);
+           (chain ? EGS_SCHED_CHAIN : 0) | (share ? EGS_SCHED_SHARE : 0);
   }
 };
 
@@ -91,6 +92,12 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   // it goes with that loop.  EGS_STEP_CHAIN=0 keeps the LDS round trip.
   const char *ce = std::getenv("EGS_STEP_CHAIN");
   s.chain = s.pair && pl.chained && s.steady && !(ce && std::atoi(ce) == 0);
+  // ... and one linear block and one pair of weights per thread for both constraints of the pair, where the two have
+  // the same contact normal bit for bit (problem.h: share_normals, decided here once per constraint upload or plan,
+  // never for descriptors written on the device).  EGS_STEP_SHARE=0 keeps both copies.
+  const char *he = std::getenv("EGS_STEP_SHARE");
+  if (s.chain && p->share_normals == egs_problem::kShareUndecided) decide_share_normals(p);
+  s.share = s.chain && p->share_normals == 1 && !(he && std::atoi(he) == 0);
   return s;
 }
 
@@ -178,7 +185,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, ctx->stream);
+          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, sc.share, ctx->stream);
           // the system this launch assembled: stored, or the problem's to make on demand from the state it read
           p->sys_deferred = sc.defer;
           p->deferred_prev = false;
@@ -424,7 +431,7 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_tiles = pl.n_tiles;
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
-  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_sched & ~egs_problem::kSchedRefinements);
+  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_sched & ~(egs_problem::kSchedRefinements | egs_problem::kSchedFullOnly));
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;

@@ -57,7 +57,8 @@
 //
 // PAIR (ASSEMBLE only): an update runs on a lane pair, each lane holding one side of two constraints; described where
 // it is written, before the kernel.  CHAIN (PAIR only): where the pair's two constraints are consecutive updates of the
-// same two bodies, the steady loop hands their accumulators from the first update to the second in registers.
+// same two bodies, the steady loop hands their accumulators from the first update to the second in registers.  SHARE
+// (CHAIN only): where the two also have one contact normal, the lane keeps their linear block and weights once.
 #include <algorithm>
 
 #include "kernels.h"
@@ -268,12 +269,91 @@ struct PairSide {
   }
 };
 
+// SHARE (CHAIN only; solve.cpp takes it where problem.h: share_normals holds): A and B of a thread pair are contact
+// points of one face pair of the same two bodies, with one normal.  A contact's linear block is -+Rn, and Rn comes from
+// the normal alone (assemble_device.h: align_to_z(d + 3, Rn)), so on each side A's nine linear entries and B's are the
+// same bits, and so are the weights: the same body.  The lane keeps them ONCE (PairLin: A's), with the linear products
+// wl Jl, which then serve both constraints, and per constraint only the angular 3x3 with its held products (PairAng).
+// Every operand is the double the CHAIN form reads in its place, every multiply the one PairSide does: the same bits.
+// The registers that frees hold products: how many of the nine shared linear ones, and how many of the nine angular
+// ones per constraint, found as the counts above were: all nine linear ones fit everywhere; a
+// sixth angular one spills 12 (GS) or 20 bytes (backward SOR).
+constexpr int kShareLinFree[2] = {9, 9};    // store-free: GS, backward SOR
+constexpr int kShareLinStore[2] = {9, 9};   // storing
+constexpr int kShareAngFree[2] = {5, 5};
+constexpr int kShareAngStore[2] = {5, 5};
+template <int METHOD, bool STORE_SYSTEM>
+constexpr int share_lin_products() {
+  return STORE_SYSTEM ? kShareLinStore[METHOD - 1] : kShareLinFree[METHOD - 1];
+}
+template <int METHOD, bool STORE_SYSTEM>
+constexpr int share_ang_products() {
+  return STORE_SYSTEM ? kShareAngStore[METHOD - 1] : kShareAngFree[METHOD - 1];
+}
+
+// the linear part of one side, for both constraints of the lane
+template <int HELD>
+struct PairLin {
+  double J[9];    // the three rows' linear columns: PairSide's J[6 r + k] at 3 r + k
+  double wl, wa;
+  double p[HELD > 0 ? HELD : 1];   // product i = wl J[3 (i % 3) + i / 3]: PairSide's product i
+  __device__ __forceinline__ void form() {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      if (i < HELD) {
+        p[i] = wl * J[3 * (i % 3) + i / 3];
+        asm volatile("" : "+v"(p[i]));
+      }
+    }
+  }
+};
+// the angular part of one side of one constraint
+template <int HELD>
+struct PairAng {
+  double J[9];    // PairSide's J[6 r + 3 + k] at 3 r + k
+  double p[HELD > 0 ? HELD : 1];   // product i = wa J[3 (i % 3) + i / 3]: PairSide's product 9 + i
+  __device__ __forceinline__ void form(double wa) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      if (i < HELD) {
+        p[i] = wa * J[3 * (i % 3) + i / 3];
+        asm volatile("" : "+v"(p[i]));
+      }
+    }
+  }
+};
+// one side of one constraint as PairSide's users take it, from the two parts
+template <int LHELD, int AHELD>
+struct PairShared {
+  PairLin<LHELD> &L;
+  PairAng<AHELD> &G;
+  __device__ __forceinline__ void acc_add(double *a, const double *d) const {
+    if constexpr (LHELD < 9) asm volatile("" : "+v"(L.wl));
+    if constexpr (AHELD < 9) asm volatile("" : "+v"(L.wa));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double t = tfma(3 * k < LHELD ? L.p[3 * k] : L.wl * L.J[k], d[0], a[k]);
+      t = tfma(3 * k + 1 < LHELD ? L.p[3 * k + 1] : L.wl * L.J[3 + k], d[1], t);
+      a[k] = tfma(3 * k + 2 < LHELD ? L.p[3 * k + 2] : L.wl * L.J[6 + k], d[2], t);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double t = tfma(3 * k < AHELD ? G.p[3 * k] : L.wa * G.J[k], d[0], a[3 + k]);
+      t = tfma(3 * k + 1 < AHELD ? G.p[3 * k + 1] : L.wa * G.J[3 + k], d[1], t);
+      a[3 + k] = tfma(3 * k + 2 < AHELD ? G.p[3 * k + 2] : L.wa * G.J[6 + k], d[2], t);
+    }
+  }
+  __device__ __forceinline__ double half_dot(int r, const double *a) const {
+    return dot3h(L.J + 3 * r, a) + dot3h(G.J + 3 * r, a + 3);
+  }
+};
+
 // One update of a pair's constraint on both lanes.  own: this lane holds the constraint's scalars (c, x); BCAST: the
 // quad_perm that hands the owner's value to both; GENERAL: the update may be the accumulation (sweep 0: dx = x).
 // a: this lane's side's accumulator.  LOAD: read from LDS first; otherwise the caller hands it over in registers, as
 // the pair's previous update left it.  STORE: written back to LDS; otherwise it stays in a for the pair's next update.
-template <int METHOD, int BCAST, bool GENERAL, bool LOAD, bool STORE, int HELD>
-__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, double (&a)[6], bool has, bool own,
+template <int METHOD, int BCAST, bool GENERAL, bool LOAD, bool STORE, typename SIDE>
+__device__ __forceinline__ void pair_pass(SIDE &S, unsigned ac, double (&a)[6], bool has, bool own,
                                           const Cons<double> &c, double (&x)[3], int sweep, double cfm) {
   double dx[3];
   if constexpr (LOAD) load6(ac, a);
@@ -301,16 +381,16 @@ __device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, double
   }
 }
 // ... from LDS to LDS
-template <int METHOD, int BCAST, bool GENERAL, int HELD>
-__device__ __forceinline__ void pair_pass(PairSide<HELD> &S, unsigned ac, bool has, bool own, const Cons<double> &c,
+template <int METHOD, int BCAST, bool GENERAL, typename SIDE>
+__device__ __forceinline__ void pair_pass(SIDE &S, unsigned ac, bool has, bool own, const Cons<double> &c,
                                           double (&x)[3], int sweep, double cfm) {
   double a[6];
   pair_pass<METHOD, BCAST, GENERAL, true, true>(S, ac, a, has, own, c, x, sweep, cfm);
 }
 
 // lambda and w = A x - rhs of a pair's constraint, written by its owner
-template <int HELD>
-__device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const PairSide<HELD> &S, unsigned ac, bool own,
+template <typename SIDE>
+__device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const SIDE &S, unsigned ac, bool own,
                                               int cidx, const Cons<double> &c, const double *x) {
   double a[6];
   load6(ac, a);
@@ -325,6 +405,13 @@ __device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const 
   }
 }
 
+// a constraint's side as the loops take it: the PairSide, or (SHARE) the view of the shared parts
+template <bool SHARE, typename P, typename V>
+__device__ __forceinline__ auto &pair_side(P &p, V &v) {
+  if constexpr (SHARE) return v;
+  else return p;
+}
+
 // CHAIN (plans that are Plan::chained, plan.h; solve.cpp launches it on no other): A and B of a thread pair are
 // consecutive updates of the same two bodies, so both lanes have ONE accumulator address for the two, and in the steady
 // window the pair's first update (A forward, B in backward SOR) is due at even steps and its second at the step after
@@ -335,7 +422,7 @@ __device__ __forceinline__ void pair_epilogue(const SolveArgs<double> &A, const 
 // The barrier between the two steps of an iteration stays, although on such a plan it orders nothing (the lanes due at
 // steps 2 j and 2 j + 1 are the firsts and seconds of the same pairs): without it the step measured no faster
 // (DESIGN.md section 5).
-template <int METHOD, bool STORE_SYSTEM, bool CHAIN, bool REST>
+template <int METHOD, bool STORE_SYSTEM, bool CHAIN, bool REST, bool SHARE>
 __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsigned char *smem) {
   constexpr int BLOCK = 256;
   const int tid = (int)threadIdx.x, tile = blockIdx.x;
@@ -384,21 +471,49 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
     for (int r = 0; r < 3; ++r) x[r] = c.rhs[r];
   }
   // the sides change hands once: the even lane gives A's side 1 for B's side 0
+  static_assert(CHAIN || !SHARE, "SHARE is a form of the CHAIN kernel");
   constexpr int HELD = pair_products<METHOD, STORE_SYSTEM, CHAIN>();
-  PairSide<HELD> SA, SB;
+  constexpr int LHELD = share_lin_products<METHOD, STORE_SYSTEM>(), AHELD = share_ang_products<METHOD, STORE_SYSTEM>();
+  PairSide<HELD> PA, PB;        // not SHARE
+  PairLin<LHELD> L;             // SHARE: one linear part under two angular ones
+  PairAng<AHELD> GA, GB;
+  PairShared<LHELD, AHELD> VA{L, GA}, VB{L, GB};
+  auto &SA = pair_side<SHARE>(PA, VA);
+  auto &SB = pair_side<SHARE>(PB, VB);
+  if constexpr (SHARE) {
+    // the linear block and the weights move once, A's: B's are the same bits wherever B is active (solve.cpp)
 #pragma unroll
-  for (int k = 0; k < 18; ++k) {
-    const double got = dpp_all<kQuadSwap>(side ? c.J0[k] : c.J1[k]);
-    SA.J[k] = side ? got : c.J0[k];
-    SB.J[k] = side ? c.J1[k] : got;
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double gl = dpp_all<kQuadSwap>(c.J1[6 * r + k]);
+        const double ga = dpp_all<kQuadSwap>(side ? c.J0[6 * r + 3 + k] : c.J1[6 * r + 3 + k]);
+        L.J[3 * r + k] = side ? gl : c.J0[6 * r + k];
+        GA.J[3 * r + k] = side ? ga : c.J0[6 * r + 3 + k];
+        GB.J[3 * r + k] = side ? c.J1[6 * r + 3 + k] : ga;
+      }
+    }
+    const double gl = dpp_all<kQuadSwap>(c.wl1), ga = dpp_all<kQuadSwap>(c.wa1);
+    L.wl = side ? gl : c.wl0;
+    L.wa = side ? ga : c.wa0;
+    L.form();
+    GA.form(L.wa);
+    GB.form(L.wa);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+      const double got = dpp_all<kQuadSwap>(side ? c.J0[k] : c.J1[k]);
+      SA.J[k] = side ? got : c.J0[k];
+      SB.J[k] = side ? c.J1[k] : got;
+    }
+    {
+      const double gl = dpp_all<kQuadSwap>(side ? c.wl0 : c.wl1), ga = dpp_all<kQuadSwap>(side ? c.wa0 : c.wa1);
+      SA.wl = side ? gl : c.wl0; SA.wa = side ? ga : c.wa0;
+      SB.wl = side ? c.wl1 : gl; SB.wa = side ? c.wa1 : ga;
+    }
+    SA.form();
+    SB.form();
   }
-  {
-    const double gl = dpp_all<kQuadSwap>(side ? c.wl0 : c.wl1), ga = dpp_all<kQuadSwap>(side ? c.wa0 : c.wa1);
-    SA.wl = side ? gl : c.wl0; SA.wa = side ? ga : c.wa0;
-    SB.wl = side ? c.wl1 : gl; SB.wa = side ? c.wa1 : ga;
-  }
-  SA.form();
-  SB.form();
   int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, A.sweeps, 0));
   __syncthreads();
 
@@ -507,11 +622,11 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
 // FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
 // ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
-          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false, bool CHAIN = false, bool REST = false>
+          bool STORE_SYSTEM = true, bool FRIC = false, bool PAIR = false, bool CHAIN = false, bool REST = false, bool SHARE = false>
 __global__ void __launch_bounds__(BLOCK * GROUP, (ISO && GROUP == 1) ? (sizeof(REAL) == 4 ? 4 : 3) : 1) step_solve_kernel(const SolveArgs<REAL> A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if constexpr (PAIR) {   // ASSEMBLE, fp64, 256-lane tiles (launch_step_solve_assemble)
-    pair_step_solve<METHOD, STORE_SYSTEM, CHAIN, REST>(A, smem);
+    pair_step_solve<METHOD, STORE_SYSTEM, CHAIN, REST, SHARE>(A, smem);
     return;
   }
   constexpr int WAVES = BLOCK / 64;
@@ -762,31 +877,34 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 namespace {
-template <bool STORE_SYSTEM, bool PAIR, bool CHAIN, bool REST>
+template <bool STORE_SYSTEM, bool PAIR, bool CHAIN, bool REST, bool SHARE>
 void launch_step_solve_assemble_r(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
   // the accumulators; the storing form stages its blocks in the same LDS first
   size_t lds = (size_t)b.max_slots * 6 * sizeof(double);
   if (STORE_SYSTEM) lds = std::max(lds, (size_t)4 * kStageWave * sizeof(double));
-  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST>;
-  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST>;
+  auto k1 = step_solve_kernel<double, 256, 1, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST, SHARE>;
+  auto k2 = step_solve_kernel<double, 256, 2, true, 1, false, true, true, STORE_SYSTEM, false, PAIR, CHAIN, REST, SHARE>;
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(method == 1 ? k1 : k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (method == 1) hipLaunchKernelGGL(k1, dim3(n_tiles), dim3(256), lds, s, b);
   else hipLaunchKernelGGL(k2, dim3(n_tiles), dim3(256), lds, s, b);
 }
 // restitution (b.assemble.rest is set) has instantiations of its own: the launches without it run the code they ran
-template <bool STORE_SYSTEM, bool PAIR, bool CHAIN = false>
+template <bool STORE_SYSTEM, bool PAIR, bool CHAIN = false, bool SHARE = false>
 void launch_step_solve_assemble_t(const SolveArgs<double> &b, int method, int n_tiles, hipStream_t s) {
-  if (b.assemble.rest != nullptr) launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, true>(b, method, n_tiles, s);
-  else launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, false>(b, method, n_tiles, s);
+  if (b.assemble.rest != nullptr) launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, true, SHARE>(b, method, n_tiles, s);
+  else launch_step_solve_assemble_r<STORE_SYSTEM, PAIR, CHAIN, false, SHARE>(b, method, n_tiles, s);
 }
 }  // namespace
 
 void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
-                                hipStream_t s) {
+                                bool share, hipStream_t s) {
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
-  if (pair && chain) {
+  if (pair && chain && share) {
+    if (store_system) launch_step_solve_assemble_t<true, true, true, true>(b, method, n_tiles, s);
+    else launch_step_solve_assemble_t<false, true, true, true>(b, method, n_tiles, s);
+  } else if (pair && chain) {
     if (store_system) launch_step_solve_assemble_t<true, true, true>(b, method, n_tiles, s);
     else launch_step_solve_assemble_t<false, true, true>(b, method, n_tiles, s);
   } else if (store_system) {

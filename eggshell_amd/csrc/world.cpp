@@ -157,6 +157,7 @@ void world_update_contacts(egs_world *w, PhaseTimer *lap) {
   if (lap) (*lap)(1);
   if (changed) world_make_problem(w, w->h_b0, w->h_b1, (int)mt);  // host plan only on topology change
   if (lap) (*lap)(2);
+  w->prob->share_normals = egs_problem::kShareDeviceData;   // the contacts' descriptors are written on the device
   if (mc > 0)
     HIPCHK(hipMemcpyAsync(w->prob->data.p + (size_t)mj * 7, w->col.data(), (size_t)mc * 7 * sizeof(double),
                           hipMemcpyDeviceToDevice, s));

@@ -110,12 +110,20 @@ typedef enum {
                                       hold one side each of two constraints (plans whose half-wavefronts each hold one
                                       phase of the timetable, a pile of columns).  The same bits as one lane per
                                       constraint; EGS_STEP_PAIR=0 switches it off */
-  EGS_SCHED_CHAIN = 8192           /* ... whose steady loop (EGS_STEP_STEADY) keeps the pair's two bodies'
+  EGS_SCHED_CHAIN = 8192,          /* ... whose steady loop (EGS_STEP_STEADY) keeps the pair's two bodies'
                                       accumulators in registers from the first of the pair's two updates to the second
                                       (plans whose pairs hold consecutive contacts of the same two bodies:
                                       egs_debug_plan_chained).  The same bits; EGS_STEP_CHAIN=0 switches it off.
                                       A refinement of EGS_SCHED_PAIR: egs_problem_get_schedule reports it,
                                       egs_solve_stats.schedule does not (its bits stay those of the pair launch) */
+  EGS_SCHED_SHARE = 16384          /* ... in which a thread keeps ONE linear Jacobian block and one pair of weights for
+                                      its side of both constraints: the two contacts of every thread pair carry the
+                                      same normal, bit for bit (egs_debug_plan_share), decided once per
+                                      egs_problem_set_constraints.  The same bits; EGS_STEP_SHARE=0 switches it off.
+                                      A refinement of EGS_SCHED_CHAIN: only egs_problem_get_schedule_full reports it
+                                      (callers compare egs_problem_get_schedule with EGS_SCHED_CHAIN masked against
+                                      egs_solve_stats.schedule).  A world, whose collider writes the contacts on the
+                                      device, does not take the form */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -393,6 +401,8 @@ egs_status egs_problem_get_stats(egs_problem *p, egs_solve_stats *stats);
 /* The egs_schedule_flags of the last GS / SOR solve: the bits of egs_solve_stats.schedule and, with them, the
  * refinements that field leaves out (EGS_SCHED_CHAIN).  Host only: no synchronisation, no residual. */
 egs_status egs_problem_get_schedule(egs_problem *p, int32_t *schedule);
+/* ... and, with those, the refinements of a refinement (EGS_SCHED_SHARE).  Host only as well. */
+egs_status egs_problem_get_schedule_full(egs_problem *p, int32_t *schedule);
 
 /* ---- entry 3: replaces Lcp::MixedConstraintsSolver(A, b, C, x_lo, x_hi, x, w)
  *      lcp.h:21-23 / lcp.cc:276-336 (and Lcp::MurtyPrincipalPivot,
@@ -1007,6 +1017,14 @@ egs_status egs_debug_plan_pairable(int32_t n_bodies, int32_t m, const int32_t *b
  * first of the two updates to the second (EGS_SCHED_CHAIN).                                                        */
 egs_status egs_debug_plan_chained(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
                                   int32_t *chained);
+
+/* Host only: *share = 1 if that plan is chained and, with data the constraint descriptors [m][7] of
+ * egs_problem_set_constraints, the two constraints of every thread pair that holds an A and a B have the same contact
+ * normal as bit patterns: data[7 A + 3 .. 5] and data[7 B + 3 .. 5] compared as integers (-0.0 is not +0.0).  A pair
+ * with an A alone asks nothing.  What the step launch asks before a thread keeps one linear block for both
+ * (EGS_SCHED_SHARE).                                                                                               */
+egs_status egs_debug_plan_share(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                const double *data, int32_t *share);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
