@@ -19,6 +19,7 @@
 // box_schur_kernel below: lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747) fused into one launch for a batch of
 // problems of n <= 96 rows (egs_box_lcp_schur_batch).
 #include "dense_lcp.h"
+#include "packed_block.h"
 #include "runtime.h"
 
 #include <algorithm>
@@ -798,8 +799,6 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
                          int32_t *ok, int32_t *nub_out, int32_t *pivots) {
   if (algorithm != 0 && algorithm != 1) throw std::invalid_argument("SolveLCP_BoxSchur: algorithm 0 (Murty) or 1 (Cottle-Dantzig)");
   if (count <= 0) return;
-  // one packed block, the same layout on both sides:  x w perm res | A | b lo hi a_off v_off n nub
-  // read back: everything up to the end of A; uploaded: everything from A on
   size_t at = 0, vt = 0;
   int n_max = 0;
   for (int k = 0; k < count; ++k) {
@@ -807,34 +806,42 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
     if (nk < 1 || nk > kDantzigMaxRows) throw std::invalid_argument("SolveLCP_BoxSchur, fused: 1 <= n <= 96");
     at += (size_t)nk * nk; vt += nk; n_max = std::max(n_max, nk);
   }
-  const auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
-  const size_t o_x = 0, o_w = o_x + vt * 8, o_perm = o_w + vt * 8, o_res = up8(o_perm + vt * 4), o_A = o_res + (size_t)count * sizeof(LcpResult),
-               o_b = o_A + at * 8, o_lo = o_b + vt * 8, o_hi = o_lo + vt * 8, o_aoff = o_hi + vt * 8, o_voff = o_aoff + (size_t)count * 8,
-               o_n = o_voff + (size_t)count * 8, o_nub = o_n + (size_t)count * 4, total = o_nub + (size_t)count * 4;
-  char *h = static_cast<char *>(hooks.take(hooks.self, total));
-  double *hA = reinterpret_cast<double *>(h + o_A), *hb = reinterpret_cast<double *>(h + o_b), *hlo = reinterpret_cast<double *>(h + o_lo),
-         *hhi = reinterpret_cast<double *>(h + o_hi);
-  int64_t *haoff = reinterpret_cast<int64_t *>(h + o_aoff), *hvoff = reinterpret_cast<int64_t *>(h + o_voff);
-  int32_t *hn = reinterpret_cast<int32_t *>(h + o_n), *hnub = reinterpret_cast<int32_t *>(h + o_nub);
+  // one packed block, the same layout on both sides (packed_block.h).  read back: x w perm res A; uploaded: b lo hi
+  // a_off v_off n nub and, permuted in place by the device, A: the last section read back, so the upload starts there
+  const size_t nc = (size_t)count;
+  PackedBlock blk;
+  const auto s_x = blk.add<double>(Zone::Download, vt), s_w = blk.add<double>(Zone::Download, vt);
+  const auto s_perm = blk.add<int32_t>(Zone::Download, vt);
+  const auto s_res = blk.add<LcpResult>(Zone::Download, nc, 8);
+  const auto s_A = blk.add<double>(Zone::Download, at);
+  const auto s_b = blk.add<double>(Zone::Upload, vt), s_lo = blk.add<double>(Zone::Upload, vt), s_hi = blk.add<double>(Zone::Upload, vt);
+  const auto s_aoff = blk.add<int64_t>(Zone::Upload, nc), s_voff = blk.add<int64_t>(Zone::Upload, nc);
+  const auto s_n = blk.add<int32_t>(Zone::Upload, nc), s_nub = blk.add<int32_t>(Zone::Upload, nc);
+  char *h = static_cast<char *>(hooks.take(hooks.self, blk.host_bytes()));
+  ScopedDevBuf<char> d(blk.total_bytes());
+  blk.bind(h, d.p);
+  int64_t *haoff = blk.host(s_aoff), *hvoff = blk.host(s_voff);
   size_t ap = 0, vp = 0;
   for (int k = 0; k < count; ++k) {
     const int j = sel[k], nk = n[j];
-    std::memcpy(hA + ap, A + a_off[j], (size_t)nk * nk * sizeof(double));
-    std::memcpy(hb + vp, b + v_off[j], nk * sizeof(double));
-    std::memcpy(hlo + vp, lo + v_off[j], nk * sizeof(double));
-    std::memcpy(hhi + vp, hi + v_off[j], nk * sizeof(double));
-    haoff[k] = (int64_t)ap; hvoff[k] = (int64_t)vp; hn[k] = nk; hnub[k] = nub ? nub[j] : -1;
+    haoff[k] = (int64_t)ap; hvoff[k] = (int64_t)vp; blk.host(s_n)[k] = nk; blk.host(s_nub)[k] = nub ? nub[j] : -1;
     ap += (size_t)nk * nk; vp += nk;
   }
-  ScopedDevBuf<char> d(total);
-  HIPCHK(hipMemcpyAsync(d.p + o_A, h + o_A, total - o_A, hipMemcpyHostToDevice, stream));
+  const auto rows = [&](int k) { return (size_t)n[sel[k]]; };
+  const auto entries = [&](int k) { return (size_t)n[sel[k]] * (size_t)n[sel[k]]; };
+  const auto a_at = [&](int k) { return (size_t)haoff[k]; };
+  const auto v_at = [&](int k) { return (size_t)hvoff[k]; };
+  gather_ragged(blk.host(s_A), A, count, sel, a_off, entries, a_at);
+  gather_ragged(blk.host(s_b), b, count, sel, v_off, rows, v_at);
+  gather_ragged(blk.host(s_lo), lo, count, sel, v_off, rows, v_at);
+  gather_ragged(blk.host(s_hi), hi, count, sel, v_off, rows, v_at);
+  HIPCHK(hipMemcpyAsync(d.p + s_A.offset, h + s_A.offset, blk.upload_end() - s_A.offset, hipMemcpyHostToDevice, stream));
   SchurSet S{};
-  S.n = reinterpret_cast<int32_t *>(d.p + o_n); S.nub = reinterpret_cast<int32_t *>(d.p + o_nub);
-  S.a_off = reinterpret_cast<int64_t *>(d.p + o_aoff); S.v_off = reinterpret_cast<int64_t *>(d.p + o_voff);
-  S.A = reinterpret_cast<double *>(d.p + o_A); S.b = reinterpret_cast<double *>(d.p + o_b);
-  S.lo = reinterpret_cast<double *>(d.p + o_lo); S.hi = reinterpret_cast<double *>(d.p + o_hi);
-  S.x = reinterpret_cast<double *>(d.p + o_x); S.w = reinterpret_cast<double *>(d.p + o_w);
-  S.perm = reinterpret_cast<int32_t *>(d.p + o_perm); S.res = reinterpret_cast<LcpResult *>(d.p + o_res);
+  S.n = blk.device(s_n); S.nub = blk.device(s_nub);
+  S.a_off = blk.device(s_aoff); S.v_off = blk.device(s_voff);
+  S.A = blk.device(s_A); S.b = blk.device(s_b); S.lo = blk.device(s_lo); S.hi = blk.device(s_hi);
+  S.x = blk.device(s_x); S.w = blk.device(s_w);
+  S.perm = blk.device(s_perm); S.res = blk.device(s_res);
   S.q6 = q6 ? 1 : 0; S.max_steps = max_steps;
   S.max_ticks = max_seconds > 0 ? (long long)(max_seconds * 1e8) + 1 : 0;
   const size_t lds = schur_lds_bytes(n_max);
@@ -847,19 +854,17 @@ void box_lcp_schur_fused(hipStream_t stream, const LaunchHooks &hooks, int algor
   else hipLaunchKernelGGL(km, dim3(count), dim3(64), lds, stream, S);
   HIPCHK(hipGetLastError());
   if (hooks.mark) hooks.mark(hooks.self, false);
-  HIPCHK(hipMemcpyAsync(h, d.p, o_A + at * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(h, d.p, blk.download_bytes(), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
-  const double *hx = reinterpret_cast<double *>(h + o_x), *hw = reinterpret_cast<double *>(h + o_w);
-  const int32_t *hperm = reinterpret_cast<int32_t *>(h + o_perm);
-  const LcpResult *hres = reinterpret_cast<LcpResult *>(h + o_res);
+  scatter_ragged(x, blk.host(s_x), count, sel, v_off, rows, v_at);
+  scatter_ragged(w, blk.host(s_w), count, sel, v_off, rows, v_at);
+  if (perm) scatter_ragged(perm, blk.host(s_perm), count, sel, v_off, rows, v_at);
+  const LcpResult *hres = blk.host(s_res);
   for (int k = 0; k < count; ++k) {
     const int j = sel[k], nk = n[j];
     double *Ak = A + a_off[j];
-    const double *Hk = hA + haoff[k];
+    const double *Hk = blk.host(s_A) + haoff[k];
     for (int r = 0; r < nk; ++r) std::memcpy(Ak + (size_t)r * nk, Hk + (size_t)r * nk, (size_t)(r + 1) * sizeof(double));   // the lower triangle only
-    std::memcpy(x + v_off[j], hx + hvoff[k], nk * sizeof(double));
-    std::memcpy(w + v_off[j], hw + hvoff[k], nk * sizeof(double));
-    if (perm) std::memcpy(perm + v_off[j], hperm + hvoff[k], nk * sizeof(int32_t));
     ok[j] = hres[k].ok;
     if (nub_out) nub_out[j] = hres[k].pad;
     if (pivots) pivots[j] = hres[k].pivots;

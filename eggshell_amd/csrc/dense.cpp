@@ -52,6 +52,63 @@ egs_status box_lcp_incremental_entry(egs_context *ctx, int algorithm, int32_t n,
   });
 }
 
+// ---- the front end the batch entries share ----
+// page-locked staging from the context's arena, the launches bracketed for egs_kernel_time
+LaunchHooks context_hooks(egs_context *ctx) {
+  LaunchHooks hooks;
+  hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
+  hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
+  hooks.self = ctx;
+  return hooks;
+}
+
+void fresh_staging(egs_context *ctx) {
+  HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
+  ctx->pinned.reset();
+}
+
+// the rule of the single entry's symmetry check (dense_lcp.hip)
+bool symmetric_enough(const double *A, int n) {
+  double amax = 0.0, asym = 0.0;
+  for (int i = 1; i < n; ++i)
+    for (int j = 0; j < i; ++j) {
+      const double v = A[(size_t)i * n + j];
+      amax = std::fmax(amax, std::fabs(v));
+      asym = std::fmax(asym, std::fabs(v - A[(size_t)j * n + i]));
+    }
+  return !(asym > 1e-10 * std::max(amax, 1e-300));
+}
+
+// Problems packed one after another: problem k's matrix at a_off[k] doubles, its vectors at v_off[k] rows; those with
+// rows go to `fused` or `single`.
+struct RaggedBatch {
+  std::vector<int64_t> a_off, v_off;
+  std::vector<int32_t> fused, single;
+  int64_t at = 0, vt = 0;
+  // refuse(k, too_large) is the entry's own check of problem k, made once its offsets are known: the message to fail
+  // with, or an empty one; too_large: n[k]^2 is beyond int32.  Returns the first message, in problem order.
+  template <class Fuse, class Refuse>
+  std::string split(int count, const int32_t *n, Fuse fuse, Refuse refuse) {
+    a_off.resize(count); v_off.resize(count);
+    for (int k = 0; k < count; ++k) {
+      const int nk = n[k];
+      a_off[k] = at; v_off[k] = vt;
+      std::string msg = refuse(k, (int64_t)nk * nk > INT32_MAX);
+      if (!msg.empty()) return msg;
+      if (nk > 0) (fuse(nk) ? fused : single).push_back(k);
+      at += (int64_t)nk * nk; vt += nk;
+    }
+    return {};
+  }
+};
+
+// the size rule of the two mixed batch entries, in `what`'s name
+std::string mixed_size_refusal(const char *what, int nk, int k, bool too_large) {
+  if (nk < 0) return std::string(what) + ": n < 0, problem " + std::to_string(k);
+  if (too_large) return std::string(what) + ": n too large, problem " + std::to_string(k);
+  return {};
+}
+
 }  // namespace
 
 extern "C" {
@@ -121,16 +178,8 @@ egs_status egs_dense_iterate_batch(egs_context *ctx, int32_t count, const int32_
   if (rows > 0 && (C || lo || hi) && !(C && lo && hi)) return fail(ctx, EGS_ERR_INVALID, "C, lo and hi come together (or all NULL: every row an equality)");
   return guarded(ctx, [&]() -> egs_status {
     HIPCHK(hipSetDevice(ctx->device));
-    LaunchHooks hooks;
-    hooks.take = [](void *self, size_t bytes) {
-      egs_context *c = static_cast<egs_context *>(self);
-      HIPCHK(hipStreamSynchronize(c->stream));     // nothing may still be reading the staging memory
-      c->pinned.reset();
-      return c->pinned.take(bytes);
-    };
-    hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
-    hooks.self = ctx;
-    dense_iterate_batch(ctx->stream, hooks, count, n, A, b, C, lo, hi, params->method, params->omega, params->max_iters, params->tol, x,
+    fresh_staging(ctx);
+    dense_iterate_batch(ctx->stream, context_hooks(ctx), count, n, A, b, C, lo, hi, params->method, params->omega, params->max_iters, params->tol, x,
                         iterations, residual, residual_history);
     return EGS_OK;
   });
@@ -293,32 +342,17 @@ egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, co
   if (max_pivots < 0) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: max_pivots < 0");
   if (count == 0) return EGS_OK;
   if (!n || !ok) return fail(ctx, EGS_ERR_INVALID, "NULL array");
-  std::vector<int64_t> a_off(count), v_off(count);
-  std::vector<int32_t> fused, single;
   const bool block_pivoting = (use_bounds & 2) != 0;
-  int64_t at = 0, vt = 0;
-  for (int k = 0; k < count; ++k) {
-    const int nk = n[k];
-    if (nk < 0) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: n < 0, problem " + std::to_string(k));
-    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "mixed constraints batch: n too large, problem " + std::to_string(k));
-    a_off[k] = at; v_off[k] = vt;
-    if (nk > 0) (nk <= kFusedDenseMax && !block_pivoting ? fused : single).push_back(k);
-    at += (int64_t)nk * nk; vt += nk;
-  }
-  if (vt > 0 && (!A || !b || !C || !lo || !hi || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
-  for (int k = 0; k < count; ++k) {     // the rule of the single entry's symmetry check (dense_lcp.hip)
-    const int nk = n[k];
-    const double *Ak = A + a_off[k];
-    double amax = 0.0, asym = 0.0;
-    for (int i = 1; i < nk; ++i)
-      for (int j = 0; j < i; ++j) {
-        const double v = Ak[(size_t)i * nk + j];
-        amax = std::fmax(amax, std::fabs(v));
-        asym = std::fmax(asym, std::fabs(v - Ak[(size_t)j * nk + i]));
-      }
-    if (asym > 1e-10 * std::max(amax, 1e-300))
+  RaggedBatch batch;
+  const std::string refused = batch.split(count, n, [&](int nk) { return nk <= kFusedDenseMax && !block_pivoting; },
+                                          [&](int k, bool too_large) { return mixed_size_refusal("mixed constraints batch", n[k], k, too_large); });
+  if (!refused.empty()) return fail(ctx, EGS_ERR_INVALID, refused);
+  const std::vector<int64_t> &a_off = batch.a_off, &v_off = batch.v_off;
+  const std::vector<int32_t> &fused = batch.fused, &single = batch.single;
+  if (batch.vt > 0 && (!A || !b || !C || !lo || !hi || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  for (int k = 0; k < count; ++k)
+    if (!symmetric_enough(A + a_off[k], n[k]))
       return fail(ctx, EGS_ERR_INVALID, "A must be symmetric (J M^-1 J^T + cfm I is): problem " + std::to_string(k));
-  }
   for (int k = 0; k < count; ++k) {
     ok[k] = n[k] == 0 ? 1 : 0;
     if (pivots) pivots[k] = 0;
@@ -326,14 +360,9 @@ egs_status egs_mixed_constraints_solve_batch(egs_context *ctx, int32_t count, co
   return guarded(ctx, [&]() -> egs_status {
     HIPCHK(hipSetDevice(ctx->device));
     if (!fused.empty()) {
-      LaunchHooks hooks;
-      hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
-      hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
-      hooks.self = ctx;
-      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
-      ctx->pinned.reset();
-      mixed_constraints_fused(ctx->dense, hooks, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo, hi,
-                              (use_bounds & 1) != 0, max_pivots, x, w, ok, pivots);
+      fresh_staging(ctx);
+      mixed_constraints_fused(ctx->dense, context_hooks(ctx), (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo,
+                              hi, (use_bounds & 1) != 0, max_pivots, x, w, ok, pivots);
     }
     // beyond the fused size, or with block pivoting: the single-problem path, one problem after another
     for (const int k : single) {
@@ -360,18 +389,13 @@ egs_status egs_mixed_friction_solve_batch(egs_context *ctx, int32_t count, const
   if (!(tol >= 0)) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: tol must be >= 0");
   if (count == 0) return EGS_OK;
   if (!n || !ok || !outer || !change) return fail(ctx, EGS_ERR_INVALID, "NULL array");
-  std::vector<int64_t> a_off(count), v_off(count);
-  std::vector<int32_t> fused, single;
-  int64_t at = 0, vt = 0;
-  for (int k = 0; k < count; ++k) {
-    const int nk = n[k];
-    if (nk < 0) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: n < 0, problem " + std::to_string(k));
-    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: n too large, problem " + std::to_string(k));
-    a_off[k] = at; v_off[k] = vt;
-    if (nk > 0) (nk <= kFusedDenseMax ? fused : single).push_back(k);
-    at += (int64_t)nk * nk; vt += nk;
-  }
-  if (vt > 0 && (!A || !b || !C || !lo || !hi || !normal_row || !mu || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
+  RaggedBatch batch;
+  const std::string refused = batch.split(count, n, [](int nk) { return nk <= kFusedDenseMax; },
+                                          [&](int k, bool too_large) { return mixed_size_refusal("mixed friction batch", n[k], k, too_large); });
+  if (!refused.empty()) return fail(ctx, EGS_ERR_INVALID, refused);
+  const std::vector<int64_t> &a_off = batch.a_off, &v_off = batch.v_off;
+  const std::vector<int32_t> &fused = batch.fused, &single = batch.single;
+  if (batch.vt > 0 && (!A || !b || !C || !lo || !hi || !normal_row || !mu || !x || !w)) return fail(ctx, EGS_ERR_INVALID, "NULL array");
   for (int k = 0; k < count; ++k) {
     const int nk = n[k];
     const int32_t *nr = normal_row + v_off[k];
@@ -386,15 +410,7 @@ egs_status egs_mixed_friction_solve_batch(egs_context *ctx, int32_t count, const
       if (!(mu[v_off[k] + i] >= 0))
         return fail(ctx, EGS_ERR_INVALID, "mixed friction batch: mu must be >= 0 on a pyramid row, problem " + std::to_string(k));
     }
-    const double *Ak = A + a_off[k];     // the rule of the single entry's symmetry check (dense_lcp.hip)
-    double amax = 0.0, asym = 0.0;
-    for (int i = 1; i < nk; ++i)
-      for (int j = 0; j < i; ++j) {
-        const double v = Ak[(size_t)i * nk + j];
-        amax = std::fmax(amax, std::fabs(v));
-        asym = std::fmax(asym, std::fabs(v - Ak[(size_t)j * nk + i]));
-      }
-    if (asym > 1e-10 * std::max(amax, 1e-300))
+    if (!symmetric_enough(A + a_off[k], nk))
       return fail(ctx, EGS_ERR_INVALID, "A must be symmetric (J M^-1 J^T + cfm I is): problem " + std::to_string(k));
   }
   if (max_outer == 0) max_outer = 32;
@@ -407,14 +423,9 @@ egs_status egs_mixed_friction_solve_batch(egs_context *ctx, int32_t count, const
   return guarded(ctx, [&]() -> egs_status {
     HIPCHK(hipSetDevice(ctx->device));
     if (!fused.empty()) {
-      LaunchHooks hooks;
-      hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
-      hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
-      hooks.self = ctx;
-      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
-      ctx->pinned.reset();
+      fresh_staging(ctx);
       const MixedFrictionBatch fr{normal_row, mu, max_outer, tol, beta, outer, change};
-      mixed_constraints_fused(ctx->dense, hooks, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo, hi,
+      mixed_constraints_fused(ctx->dense, context_hooks(ctx), (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, C, lo, hi,
                               true, max_pivots, x, w, ok, pivots, &fr);
     }
     // beyond the fused size: the same iteration from the host, one problem after another
@@ -488,38 +499,34 @@ egs_status egs_box_lcp_schur_batch(egs_context *ctx, int32_t algorithm, int32_t 
   // everything is checked before anything is written
   const double big = std::numeric_limits<double>::max();
   const bool q6 = reference_quirks != 0;
-  std::vector<int64_t> a_off(count), v_off(count);
-  std::vector<int32_t> fused, single;
-  int64_t at = 0, vt = 0;
-  for (int k = 0; k < count; ++k) {
-    const int nk = n[k];
-    if (nk < 1 || (nub && nub[k] > nk)) return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: n >= 1, nub <= n");
-    if ((int64_t)nk * nk > INT32_MAX) return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: n too large");
-    a_off[k] = at; v_off[k] = vt;
-    const double *lk = lo + vt, *hk = hi + vt;
-    const int hook = nub ? nub[k] : -1;
-    for (int i = 0; i < nk; ++i) {
-      // the rows the partition leaves behind the unbounded ones (toolkit/lcp.cc:660-669) go to the inner solver
-      const bool bounded = hook >= 0 ? i >= hook : (q6 ? (lk[i] > -big || hk[i] < -big) : (lk[i] > -big || hk[i] < big));
-      if (!bounded) continue;
-      // lo <= 0 <= hi (toolkit/lcp.h:134); Dantzig also needs lo < hi (toolkit/lcp.cc:448-450)
-      if (!(lk[i] <= 0.0) || !(hk[i] >= 0.0) || (algorithm == 1 && !(lk[i] < hk[i])))
-        return fail(ctx, EGS_ERR_INVALID, "SolveLCP_BoxSchur: the bounded rows need lo <= 0 <= hi (and lo < hi for Cottle-Dantzig)");
-    }
-    (nk <= kDantzigMaxRows ? fused : single).push_back(k);
-    at += (int64_t)nk * nk; vt += nk;
-  }
+  RaggedBatch batch;
+  const std::string refused = batch.split(
+      count, n, [](int nk) { return nk <= kDantzigMaxRows; },
+      [&](int k, bool too_large) -> std::string {
+        const int nk = n[k];
+        if (nk < 1 || (nub && nub[k] > nk)) return "SolveLCP_BoxSchur: n >= 1, nub <= n";
+        if (too_large) return "SolveLCP_BoxSchur: n too large";
+        const double *lk = lo + batch.v_off[k], *hk = hi + batch.v_off[k];
+        const int hook = nub ? nub[k] : -1;
+        for (int i = 0; i < nk; ++i) {
+          // the rows the partition leaves behind the unbounded ones (toolkit/lcp.cc:660-669) go to the inner solver
+          const bool bounded = hook >= 0 ? i >= hook : (q6 ? (lk[i] > -big || hk[i] < -big) : (lk[i] > -big || hk[i] < big));
+          if (!bounded) continue;
+          // lo <= 0 <= hi (toolkit/lcp.h:134); Dantzig also needs lo < hi (toolkit/lcp.cc:448-450)
+          if (!(lk[i] <= 0.0) || !(hk[i] >= 0.0) || (algorithm == 1 && !(lk[i] < hk[i])))
+            return "SolveLCP_BoxSchur: the bounded rows need lo <= 0 <= hi (and lo < hi for Cottle-Dantzig)";
+        }
+        return {};
+      });
+  if (!refused.empty()) return fail(ctx, EGS_ERR_INVALID, refused);
+  const std::vector<int64_t> &a_off = batch.a_off, &v_off = batch.v_off;
+  const std::vector<int32_t> &fused = batch.fused, &single = batch.single;
   for (int k = 0; k < count; ++k) ok[k] = 0;
   return guarded(ctx, [&]() -> egs_status {
     HIPCHK(hipSetDevice(ctx->device));
-    LaunchHooks hooks;
-    hooks.take = [](void *self, size_t bytes) { return static_cast<egs_context *>(self)->pinned.take(bytes); };
-    hooks.mark = [](void *self, bool begin) { record_kernel_event(static_cast<egs_context *>(self), begin); };
-    hooks.self = ctx;
     if (!fused.empty()) {
-      HIPCHK(hipStreamSynchronize(ctx->stream));     // nothing may still be reading the staging memory
-      ctx->pinned.reset();
-      box_lcp_schur_fused(ctx->stream, hooks, algorithm, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, lo, hi,
+      fresh_staging(ctx);
+      box_lcp_schur_fused(ctx->stream, context_hooks(ctx), algorithm, (int)fused.size(), fused.data(), n, a_off.data(), v_off.data(), A, b, lo, hi,
                           nub, q6, max_iterations, max_seconds, x, w, perm, ok, nub_out, pivots);
     }
     // beyond the fused size: the single-problem path, one problem after another

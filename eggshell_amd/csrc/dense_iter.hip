@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "dense_lcp.h"
+#include "packed_block.h"
 #include "runtime.h"
 
 namespace egs {
@@ -393,18 +394,25 @@ void dense_iterate_batch(hipStream_t s, const LaunchHooks &hooks, int count, con
     }
     return;
   }
-  // one packed block, the same layout on both sides:  x out hist | A b lo hi prob sel C
-  // read back: everything before A; uploaded: everything from A on
-  const auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-  const size_t o_x = 0, o_out = o_x + vt * 8, o_hist = o_out + (size_t)count * sizeof(DenseIterOut),
-               o_A = up16(o_hist + (history ? (size_t)count * hlen * 8 : 0)), o_b = o_A + dat * 8, o_lo = o_b + vt * 8, o_hi = o_lo + vt * 8,
-               o_prob = o_hi + vt * 8, o_sel = o_prob + (size_t)count * sizeof(DenseIterProblem), o_C = o_sel + nsel * 4, total = o_C + vt;
-  char *h = static_cast<char *>(hooks.take(hooks.self, total));
-  double *hA = reinterpret_cast<double *>(h + o_A), *hb = reinterpret_cast<double *>(h + o_b), *hlo = reinterpret_cast<double *>(h + o_lo),
-         *hhi = reinterpret_cast<double *>(h + o_hi);
-  DenseIterProblem *hprob = reinterpret_cast<DenseIterProblem *>(h + o_prob);
-  int32_t *hsel = reinterpret_cast<int32_t *>(h + o_sel);
-  uint8_t *hC = reinterpret_cast<uint8_t *>(h + o_C);
+  // one packed block, the same layout on both sides (packed_block.h).  read back: x out [hist]; uploaded: A b lo hi
+  // prob sel C.  Every problem of the call is in it, in the caller's order, so only A (padded below) is copied piecewise.
+  const size_t nc = (size_t)count;
+  PackedBlock blk;
+  const auto s_x = blk.add<double>(Zone::Download, vt);
+  const auto s_out = blk.add<DenseIterOut>(Zone::Download, nc);
+  const auto s_hist = blk.add<double>(Zone::Download, history ? nc * hlen : 0);
+  const auto s_A = blk.add<double>(Zone::Upload, dat, 16), s_b = blk.add<double>(Zone::Upload, vt), s_lo = blk.add<double>(Zone::Upload, vt),
+             s_hi = blk.add<double>(Zone::Upload, vt);
+  const auto s_prob = blk.add<DenseIterProblem>(Zone::Upload, nc);
+  const auto s_sel = blk.add<int32_t>(Zone::Upload, nsel);
+  const auto s_C = blk.add<uint8_t>(Zone::Upload, vt);
+  char *h = static_cast<char *>(hooks.take(hooks.self, blk.host_bytes()));
+  ScopedDevBuf<char> d(blk.total_bytes());
+  blk.bind(h, d.p);
+  double *hA = blk.host(s_A), *hb = blk.host(s_b), *hlo = blk.host(s_lo), *hhi = blk.host(s_hi);
+  DenseIterProblem *hprob = blk.host(s_prob);
+  int32_t *hsel = blk.host(s_sel);
+  uint8_t *hC = blk.host(s_C);
   size_t ap = 0, vp = 0, dp = 0;
   for (int k = 0; k < count; ++k) {
     const size_t nk = (size_t)n[k];
@@ -420,36 +428,34 @@ void dense_iterate_batch(hipStream_t s, const LaunchHooks &hooks, int count, con
   }
   std::copy(small.begin(), small.end(), hsel);
   std::copy(medium.begin(), medium.end(), hsel + small.size());
-  ScopedDevBuf<char> d(total);
-  HIPCHK(hipMemcpyAsync(d.p + o_A, h + o_A, total - o_A, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d.p + blk.upload_begin(), h + blk.upload_begin(), blk.upload_end() - blk.upload_begin(), hipMemcpyHostToDevice, s));
   DenseIterSet S{};
-  S.prob = reinterpret_cast<DenseIterProblem *>(d.p + o_prob);
-  S.A = reinterpret_cast<double *>(d.p + o_A); S.b = reinterpret_cast<double *>(d.p + o_b);
-  S.lo = reinterpret_cast<double *>(d.p + o_lo); S.hi = reinterpret_cast<double *>(d.p + o_hi);
-  S.C = reinterpret_cast<uint8_t *>(d.p + o_C);
-  S.x = reinterpret_cast<double *>(d.p + o_x); S.out = reinterpret_cast<DenseIterOut *>(d.p + o_out);
-  S.hist = history ? reinterpret_cast<double *>(d.p + o_hist) : nullptr;
+  S.prob = blk.device(s_prob);
+  S.A = blk.device(s_A); S.b = blk.device(s_b); S.lo = blk.device(s_lo); S.hi = blk.device(s_hi);
+  S.C = blk.device(s_C);
+  S.x = blk.device(s_x); S.out = blk.device(s_out);
+  S.hist = history ? blk.device(s_hist) : nullptr;
   S.method = method; S.max_iters = max_iters; S.ksor = 1.0 / omega; S.tol = tol;
   if (hooks.mark) hooks.mark(hooks.self, true);
   if (!small.empty()) {
     const size_t lds = small_lds_bytes(n_small_max);
     if (lds > 48 * 1024)
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(dense_iterate_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    S.sel = reinterpret_cast<int32_t *>(d.p + o_sel);
+    S.sel = blk.device(s_sel);
     hipLaunchKernelGGL(dense_iterate_small_kernel, dim3((unsigned)small.size()), dim3(64), lds, s, S);
     HIPCHK(hipGetLastError());
   }
   if (!medium.empty()) {
-    S.sel = reinterpret_cast<int32_t *>(d.p + o_sel) + small.size();
+    S.sel = blk.device(s_sel) + small.size();
     hipLaunchKernelGGL(dense_iterate_medium_kernel, dim3((unsigned)medium.size()), dim3(1024), 0, s, S);
     HIPCHK(hipGetLastError());
   }
   if (hooks.mark) hooks.mark(hooks.self, false);
-  HIPCHK(hipMemcpyAsync(h, d.p, o_hist + (history ? (size_t)count * hlen * 8 : 0), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h, d.p, blk.download_bytes(), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (vt) std::memcpy(x, h + o_x, vt * sizeof(double));
-  const DenseIterOut *hout = reinterpret_cast<const DenseIterOut *>(h + o_out);
-  const double *hh = reinterpret_cast<const double *>(h + o_hist);
+  if (vt) std::memcpy(x, blk.host(s_x), vt * sizeof(double));
+  const DenseIterOut *hout = blk.host(s_out);
+  const double *hh = blk.host(s_hist);
   for (int k = 0; k < count; ++k) {
     const bool ran = n[k] > 0;          // a problem without rows was not launched (sparse_iterations.cc:79-81)
     if (iterations) iterations[k] = ran ? hout[k].iterations : 0;

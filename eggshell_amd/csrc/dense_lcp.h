@@ -78,6 +78,12 @@ bool box_lcp_schur(DenseWorkspace &ws, int n, double *A, const double *b, const 
 // that `hooks.take` hands out (valid until the call returns); hooks.mark(begin) brackets the launch for the caller's
 // kernel timer (may be NULL).  The bounds must already satisfy lo <= 0 <= hi on the bounded rows.  Problems with more
 // rows are NOT fused: they go through box_lcp_schur one at a time.
+//
+// The three fused pipelines below (this one, mixed_constraints_fused, dense_iterate_batch) lay their block out with
+// packed_block.h: the sections read back, the sections uploaded, then device-only scratch, the same offsets on both
+// sides; hooks.take is asked for the block's host_bytes().  host/packed_block_check.cpp runs their section lists on the
+// CPU under the sanitizers.  The caller (dense.cpp) makes the hooks from its context and empties the staging arena
+// before the call.
 struct LaunchHooks {
   void *(*take)(void *self, size_t bytes);
   void (*mark)(void *self, bool begin);

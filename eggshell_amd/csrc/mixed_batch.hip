@@ -14,6 +14,7 @@
 #include "dense_lcp.h"
 #include "dense_world.h"
 #include "mixed_solve_device.h"
+#include "packed_block.h"
 #include "runtime.h"
 
 namespace egs {
@@ -171,54 +172,53 @@ void mixed_constraints_fused(DenseWorkspace &ws, const LaunchHooks &hooks, int c
     at += nk * nk; vt += nk;
     if (cls == 2) wt += nk * nk;
   }
-  // one packed block, the same layout on both sides:  x w [beta fout] out | A b lo hi [mu] prob list [nrow] C | workspace
-  // (device only); read back: everything before A; uploaded: from A to the end of C.  [..]: the pyramid form only.
-  const auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-  const size_t fv = fr ? vt : 0, fc = fr ? (size_t)count : 0;
-  const size_t o_x = 0, o_w = o_x + vt * 8, o_beta = o_w + vt * 8, o_fout = o_beta + fv * 8, o_out = o_fout + fc * sizeof(MixedFrictionOut),
-               o_A = up16(o_out + (size_t)count * sizeof(MixedBatchOut)),
-               o_b = o_A + at * 8, o_lo = o_b + vt * 8, o_hi = o_lo + vt * 8, o_mu = o_hi + vt * 8, o_prob = o_mu + fv * 8,
-               o_list = o_prob + (size_t)count * sizeof(MixedBatchProblem), o_nrow = o_list + (size_t)count * 4, o_C = o_nrow + fv * 4,
-               o_end = o_C + vt, o_ws = up16(o_end), total = o_ws + wt * 8;
-  char *h = static_cast<char *>(hooks.take(hooks.self, o_end));
-  double *hA = reinterpret_cast<double *>(h + o_A), *hb = reinterpret_cast<double *>(h + o_b), *hlo = reinterpret_cast<double *>(h + o_lo),
-         *hhi = reinterpret_cast<double *>(h + o_hi);
-  int32_t *hlist = reinterpret_cast<int32_t *>(h + o_list);
-  uint8_t *hC = reinterpret_cast<uint8_t *>(h + o_C);
-  for (int f = 0; f < count; ++f) {
-    const int k = sel[f];
-    const size_t nk = (size_t)n[k];
-    std::memcpy(hA + prob[f].a_off, A + a_off[k], nk * nk * sizeof(double));
-    std::memcpy(hb + prob[f].v_off, b + v_off[k], nk * sizeof(double));
-    std::memcpy(hlo + prob[f].v_off, lo + v_off[k], nk * sizeof(double));
-    std::memcpy(hhi + prob[f].v_off, hi + v_off[k], nk * sizeof(double));
-    std::memcpy(hC + prob[f].v_off, C + v_off[k], nk);
-    if (fr) {
-      std::memcpy(reinterpret_cast<double *>(h + o_mu) + prob[f].v_off, fr->mu + v_off[k], nk * sizeof(double));
-      std::memcpy(reinterpret_cast<int32_t *>(h + o_nrow) + prob[f].v_off, fr->normal_row + v_off[k], nk * sizeof(int32_t));
-    }
+  // one packed block, the same layout on both sides (packed_block.h).  read back: x w [beta fout] out; uploaded: A b lo
+  // hi [mu] prob list [nrow] C; device only: the 112-row class's workspace.  [..]: the pyramid form only.
+  const size_t nc = (size_t)count, fv = fr ? vt : 0, fc = fr ? nc : 0;
+  PackedBlock blk;
+  const auto s_x = blk.add<double>(Zone::Download, vt), s_w = blk.add<double>(Zone::Download, vt), s_beta = blk.add<double>(Zone::Download, fv);
+  const auto s_fout = blk.add<MixedFrictionOut>(Zone::Download, fc);
+  const auto s_out = blk.add<MixedBatchOut>(Zone::Download, nc);
+  const auto s_A = blk.add<double>(Zone::Upload, at, 16), s_b = blk.add<double>(Zone::Upload, vt), s_lo = blk.add<double>(Zone::Upload, vt),
+             s_hi = blk.add<double>(Zone::Upload, vt), s_mu = blk.add<double>(Zone::Upload, fv);
+  const auto s_prob = blk.add<MixedBatchProblem>(Zone::Upload, nc);
+  const auto s_list = blk.add<int32_t>(Zone::Upload, nc), s_nrow = blk.add<int32_t>(Zone::Upload, fv);
+  const auto s_C = blk.add<uint8_t>(Zone::Upload, vt);
+  const auto s_ws = blk.add<double>(Zone::Scratch, wt, 16);
+  char *h = static_cast<char *>(hooks.take(hooks.self, blk.host_bytes()));
+  ScopedDevBuf<char> d(blk.total_bytes());
+  blk.bind(h, d.p);
+  const auto rows = [&](int f) { return (size_t)prob[f].n; };
+  const auto entries = [&](int f) { return (size_t)prob[f].n * (size_t)prob[f].n; };
+  const auto a_at = [&](int f) { return (size_t)prob[f].a_off; };
+  const auto v_at = [&](int f) { return (size_t)prob[f].v_off; };
+  gather_ragged(blk.host(s_A), A, count, sel, a_off, entries, a_at);
+  gather_ragged(blk.host(s_b), b, count, sel, v_off, rows, v_at);
+  gather_ragged(blk.host(s_lo), lo, count, sel, v_off, rows, v_at);
+  gather_ragged(blk.host(s_hi), hi, count, sel, v_off, rows, v_at);
+  gather_ragged(blk.host(s_C), C, count, sel, v_off, rows, v_at);
+  if (fr) {
+    gather_ragged(blk.host(s_mu), fr->mu, count, sel, v_off, rows, v_at);
+    gather_ragged(blk.host(s_nrow), fr->normal_row, count, sel, v_off, rows, v_at);
   }
-  std::memcpy(h + o_prob, prob.data(), (size_t)count * sizeof(MixedBatchProblem));
+  std::copy(prob.begin(), prob.end(), blk.host(s_prob));
   size_t lp = 0;
-  for (int c = 0; c < 3; ++c) { std::copy(cls_list[c].begin(), cls_list[c].end(), hlist + lp); lp += cls_list[c].size(); }
-  ScopedDevBuf<char> d(total);
-  HIPCHK(hipMemcpyAsync(d.p + o_A, h + o_A, o_end - o_A, hipMemcpyHostToDevice, s));
+  for (int c = 0; c < 3; ++c) { std::copy(cls_list[c].begin(), cls_list[c].end(), blk.host(s_list) + lp); lp += cls_list[c].size(); }
+  HIPCHK(hipMemcpyAsync(d.p + blk.upload_begin(), h + blk.upload_begin(), blk.upload_end() - blk.upload_begin(), hipMemcpyHostToDevice, s));
   MixedBatchArgs a{};
-  a.prob = reinterpret_cast<MixedBatchProblem *>(d.p + o_prob);
-  a.A = reinterpret_cast<double *>(d.p + o_A); a.b = reinterpret_cast<double *>(d.p + o_b);
-  a.lo = reinterpret_cast<double *>(d.p + o_lo); a.hi = reinterpret_cast<double *>(d.p + o_hi);
-  a.C = reinterpret_cast<uint8_t *>(d.p + o_C);
-  a.x = reinterpret_cast<double *>(d.p + o_x); a.w = reinterpret_cast<double *>(d.p + o_w);
-  a.out = reinterpret_cast<MixedBatchOut *>(d.p + o_out);
-  a.ws = reinterpret_cast<double *>(d.p + o_ws);
+  a.prob = blk.device(s_prob);
+  a.A = blk.device(s_A); a.b = blk.device(s_b); a.lo = blk.device(s_lo); a.hi = blk.device(s_hi);
+  a.C = blk.device(s_C);
+  a.x = blk.device(s_x); a.w = blk.device(s_w);
+  a.out = blk.device(s_out);
+  a.ws = blk.device(s_ws);
   a.use_bounds = use_bounds ? 1 : 0; a.max_pivots = max_pivots;
-  const int32_t *dlist = reinterpret_cast<int32_t *>(d.p + o_list);
+  const int32_t *dlist = blk.device(s_list);
   if (hooks.mark) hooks.mark(hooks.self, true);
   lp = 0;
   if (fr) {
     MixedFrictionArgs fa{};
-    fa.nrow = reinterpret_cast<int32_t *>(d.p + o_nrow); fa.mu = reinterpret_cast<double *>(d.p + o_mu);
-    fa.beta = reinterpret_cast<double *>(d.p + o_beta); fa.out = reinterpret_cast<MixedFrictionOut *>(d.p + o_fout);
+    fa.nrow = blk.device(s_nrow); fa.mu = blk.device(s_mu); fa.beta = blk.device(s_beta); fa.out = blk.device(s_fout);
     fa.tol = fr->tol; fa.max_outer = fr->max_outer;
     if (!cls_list[0].empty()) launch_mixed_friction_batch<32, 64, true>(a, fa, dlist + lp, (int)cls_list[0].size(), &ws.mixed_friction_lds[0], s);
     lp += cls_list[0].size();
@@ -233,23 +233,18 @@ void mixed_constraints_fused(DenseWorkspace &ws, const LaunchHooks &hooks, int c
     if (!cls_list[2].empty()) launch_mixed_batch<112, 256, false>(a, dlist + lp, (int)cls_list[2].size(), &ws.mixed_batch_lds[2], s);
   }
   if (hooks.mark) hooks.mark(hooks.self, false);
-  HIPCHK(hipMemcpyAsync(h, d.p, o_out + (size_t)count * sizeof(MixedBatchOut), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h, d.p, blk.download_bytes(), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  const double *hx = reinterpret_cast<const double *>(h + o_x), *hw = reinterpret_cast<const double *>(h + o_w);
-  const MixedBatchOut *hout = reinterpret_cast<const MixedBatchOut *>(h + o_out);
+  scatter_ragged(x, blk.host(s_x), count, sel, v_off, rows, v_at);
+  scatter_ragged(w, blk.host(s_w), count, sel, v_off, rows, v_at);
+  if (fr && fr->beta) scatter_ragged(fr->beta, blk.host(s_beta), count, sel, v_off, rows, v_at);
+  const MixedBatchOut *hout = blk.host(s_out);
+  const MixedFrictionOut *hf = blk.host(s_fout);
   for (int f = 0; f < count; ++f) {
     const int k = sel[f];
-    const size_t nk = (size_t)n[k];
-    std::memcpy(x + v_off[k], hx + prob[f].v_off, nk * sizeof(double));
-    std::memcpy(w + v_off[k], hw + prob[f].v_off, nk * sizeof(double));
     ok[k] = hout[f].ok;
     if (pivots) pivots[k] = hout[f].pivots;
-    if (fr) {
-      const MixedFrictionOut *hf = reinterpret_cast<const MixedFrictionOut *>(h + o_fout);
-      if (fr->beta) std::memcpy(fr->beta + v_off[k], reinterpret_cast<const double *>(h + o_beta) + prob[f].v_off, nk * sizeof(double));
-      fr->outer[k] = hf[f].outer;
-      fr->change[k] = hf[f].change;
-    }
+    if (fr) { fr->outer[k] = hf[f].outer; fr->change[k] = hf[f].change; }
   }
 }
 
