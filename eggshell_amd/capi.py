@@ -28,6 +28,7 @@ SCHED_FRICTION = 2048
 SCHED_PAIR = 4096
 SCHED_CHAIN = 8192
 SCHED_SHARE = 16384
+SCHED_FACE = 32768
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
@@ -40,12 +41,12 @@ EXPORTS = [
     "egs_problem_set_state", "egs_problem_set_mass", "egs_problem_set_constraints", "egs_problem_assemble",
     "egs_problem_step", "egs_problem_get_blocks", "egs_problem_get_velocity",
     "egs_problem_advance", "egs_problem_get_state",
-    "egs_problem_get_stats", "egs_problem_get_schedule", "egs_problem_get_schedule_full", "egs_mixed_constraints_solve", "egs_debug_plan", "egs_debug_plan_slots",
+    "egs_problem_get_stats", "egs_problem_get_schedule", "egs_problem_get_schedule_full", "egs_problem_get_schedule_forms", "egs_mixed_constraints_solve", "egs_debug_plan", "egs_debug_plan_slots",
     "egs_update_contacts", "egs_update_contacts_joints", "egs_world_create", "egs_world_destroy", "egs_world_set_bodies",
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
-    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
+    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_debug_plan_faced", "egs_debug_plan_face_normals", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
@@ -682,6 +683,12 @@ class Problem:
         self.ctx.check(load().egs_problem_get_schedule_full(self.h, C.byref(out)))
         return int(out.value)
 
+    def schedule_forms(self):
+        """... and SCHED_FACE with them (see egs_problem_get_schedule_forms)."""
+        out = C.c_int32(0)
+        self.ctx.check(load().egs_problem_get_schedule_forms(self.h, C.byref(out)))
+        return int(out.value)
+
     def lambda_(self):
         x = np.zeros(3 * self.m)
         self.ctx.check(load().egs_problem_get_lambda(self.h, _p(x)))
@@ -896,6 +903,30 @@ def debug_plan_share(n_bodies, body0, body1, data):
                                      C.byref(out))
     if st != OK:
         raise EgsError(st, "egs_debug_plan_share failed")
+    return bool(out.value)
+
+
+def debug_plan_faced(n_bodies, body0, body1):
+    """Host-only: do the thread pairs of the face form hold four consecutive updates of the same two bodies, alone on
+    those bodies within a block of four time steps (see egs_debug_plan_faced)?"""
+    body0, body1 = _i32(body0), _i32(body1)
+    out = C.c_int32(0)
+    st = load().egs_debug_plan_faced(C.c_int32(n_bodies), C.c_int32(body0.shape[0]), _p(body0), _p(body1), C.byref(out))
+    if st != OK:
+        raise EgsError(st, "egs_debug_plan_faced failed")
+    return bool(out.value)
+
+
+def debug_plan_face_normals(n_bodies, body0, body1, data):
+    """Host-only: is the plan faced, and do the contacts of every group of four carry one normal bit for bit (see
+    egs_debug_plan_face_normals)?  data: the constraint descriptors [m][7]."""
+    body0, body1 = _i32(body0), _i32(body1)
+    data = np.ascontiguousarray(data, dtype=np.float64).reshape(body0.shape[0], 7)
+    out = C.c_int32(0)
+    st = load().egs_debug_plan_face_normals(C.c_int32(n_bodies), C.c_int32(body0.shape[0]), _p(body0), _p(body1), _p(data),
+                                            C.byref(out))
+    if st != OK:
+        raise EgsError(st, "egs_debug_plan_face_normals failed")
     return bool(out.value)
 
 

@@ -151,6 +151,10 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 // form, one linear block and one pair of weights per lane for both constraints; the same bits
 void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
                                 bool share, hipStream_t s);
+// the FACE form of the share launch (step_solve.hip): GS, store-free, no restitution, on a plan that is Plan::faced whose
+// groups of four carry one normal (problem.h: face_normals), a.steady on; 128 threads per tile; the same bits.
+// tiles_per_cu: 3 or 4 resident tiles per CU (4: what the registers allow; 3: the launch asks for more LDS)
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);
@@ -259,7 +263,10 @@ void launch_minv_iso(int n, const REAL *W, int *flag, hipStream_t s);
 template <typename REAL>
 void launch_linsym_bodies(int m, const int32_t *body0, const int32_t *body1, const REAL *W, int *flag, hipStream_t s);
 // plan_shares_normals (plan.h) on the device, for a chained plan of 256-lane tiles: *flag &= the two constraints of
-// every thread pair have the same three normal bit patterns in data [m][7]
+// every thread pair have the same three normal bit patterns in data [m][7] (bit 0 of a flag that starts at 3: any
+// mismatch clears the whole flag), and plan_faces_normals with it: bit 1 stays set only if the first of every odd
+// wavefront's pair also has the normal of the pair 64 lanes below it, so that with bit 0 the four members of a group
+// carry one normal
 void launch_share_normals(int n_tiles, const LaneDesc *lanes, const double *data, int *flag, hipStream_t s);
 
 // A = J M^-1 J^T + cfm I, [3m][3m] row-major fp64 on the device (ensembles.cc:510, 513-521)

@@ -637,7 +637,9 @@ __global__ void __launch_bounds__(256) linsym_bodies_kernel(int m, const int32_t
   if (!ok) atomicAnd(flag, 0);
 }
 
-// thread i = pair l of wavefront w of tile t, i = (4 t + w) * 32 + l: plan lanes 64 w + l and 64 w + 32 + l
+// thread i = pair l of wavefront w of tile t, i = (4 t + w) * 32 + l: plan lanes 64 w + l and 64 w + 32 + l.
+// Bit 0 of *flag: every pair carries one normal (SHARE); bit 1, read with bit 0: the first of an odd w's pair also
+// carries that of the pair 64 lanes below, member 0 of its group of four (FACE: plan.h, plan_faces_normals).
 __global__ void __launch_bounds__(256) share_normals_kernel(int n_pairs, const LaneDesc *lanes, const double *data, int *flag) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_pairs) return;
@@ -646,6 +648,16 @@ __global__ void __launch_bounds__(256) share_normals_kernel(int n_pairs, const L
   if (a < 0 || b < 0) return;
   const double *na = data + (size_t)a * 7 + 3, *nb = data + (size_t)b * 7 + 3;
   if (!(same_bits(na[0], nb[0]) && same_bits(na[1], nb[1]) && same_bits(na[2], nb[2]))) atomicAnd(flag, 0);
+}
+// ... the pairs' firsts: a group's member 2 against its member 0 (a member 2 without a member 3 is no pair above)
+__global__ void __launch_bounds__(256) face_normals_kernel(int n_pairs, const LaneDesc *lanes, const double *data, int *flag) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_pairs || !((i >> 5) & 1)) return;
+  const size_t ic = (size_t)(i >> 5) * 64 + (i & 31);
+  const int a = lanes[ic - 64].cidx, c = lanes[ic].cidx;
+  if (a < 0 || c < 0) return;
+  const double *na = data + (size_t)a * 7 + 3, *nc = data + (size_t)c * 7 + 3;
+  if (!(same_bits(na[0], nc[0]) && same_bits(na[1], nc[1]) && same_bits(na[2], nc[2]))) atomicAnd(flag, ~2);
 }
 
 // --------------------------------------------------------------------------
@@ -1146,6 +1158,7 @@ void launch_share_normals(int n_tiles, const LaneDesc *lanes, const double *data
   if (n_tiles <= 0) return;
   const int n_pairs = n_tiles * 128;
   hipLaunchKernelGGL(share_normals_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, n_pairs, lanes, data, flag);
+  hipLaunchKernelGGL(face_normals_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, n_pairs, lanes, data, flag);
 }
 
 template <typename REAL>

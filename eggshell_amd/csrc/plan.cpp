@@ -355,7 +355,7 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
     plan = std::move(*recycle);
     plan.n_islands = plan.n_tiles = 0; plan.max_slots = 1; plan.max_cnt = 1;
     plan.lanes.clear(); plan.lane_level.clear(); plan.tile_period.clear(); plan.tile_depth.clear();
-    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false; plan.pairable = false; plan.chained = false;
+    plan.max_period = plan.max_depth = 1; plan.levels_ok = true; plan.runs = false; plan.pairable = false; plan.chained = false; plan.faced = false;
     plan.tile_nslots.clear(); plan.tile_slot_off.clear(); plan.slot_body.clear();
     plan.global.clear();
     plan.n_patch_tiles = 0; plan.patch_max_slots = 1; plan.n_shared_bodies = 0; plan.patch_runs = false;
@@ -778,6 +778,36 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
           plan.chained = false;
       }
   }
+  // faced (plan.h): the same for the four members of a group, 32 plan lanes apart in a 128-lane half of a tile, and no
+  // other group on a member's bodies inside a block of four steps.  Forward, member k is due at steps = level[0] + k
+  // (mod P), level[0] and P multiples of 4: a block of four steps from a step = 0 (mod 4) holds whole groups.
+  plan.faced = plan.chained;
+  std::vector<int32_t> slot_group;
+  for (int t = 0; t < plan.n_tiles && plan.faced; ++t) {
+    const int P = plan.tile_period[t];
+    if (P % 4 != 0) { plan.faced = false; break; }
+    slot_group.assign((size_t)(P / 4) * plan.tile_nslots[t], -1);
+    for (int g = 0; g < block / 4 && plan.faced; ++g) {   // group g: lanes 128 (g / 32) + 32 k + g % 32
+      const size_t i0 = (size_t)t * block + 128 * (g / 32) + g % 32;
+      const LaneDesc &a = plan.lanes[i0];
+      for (int k = 0; k < 4 && plan.faced; ++k) {
+        const LaneDesc &d = plan.lanes[i0 + 32 * k];
+        if (d.cidx < 0) continue;
+        if (a.cidx < 0 || plan.lanes[i0 + 32 * (k > 0 ? k - 1 : 0)].cidx < 0) plan.faced = false;
+        else if (plan.lane_level[i0] % 4 != 0 || d.slot0 != a.slot0 || d.slot1 != a.slot1 ||
+                 plan.lane_level[i0 + 32 * k] != plan.lane_level[i0] + k)
+          plan.faced = false;
+        if (!plan.faced) break;
+        const int blk = (plan.lane_level[i0] / 4) % (P / 4);
+        for (const int slot : {(int)d.slot0, (int)d.slot1}) {
+          if (slot == 0) continue;   // the world: no accumulator
+          int32_t &owner = slot_group[(size_t)blk * plan.tile_nslots[t] + slot];
+          if (owner < 0) owner = g;
+          else if (owner != g) plan.faced = false;
+        }
+      }
+    }
+  }
   plan.slot_body.assign((size_t)off, -1);   // slot 0 of every tile = the world
   for (int b = 0; b < n_bodies; ++b)
     if (body_tile[b] >= 0) plan.slot_body[(size_t)plan.tile_slot_off[body_tile[b]] + body_slot[b]] = b;
@@ -818,6 +848,21 @@ bool plan_shares_normals(const Plan &plan, const double *data) {
         if (a < 0 || b < 0) continue;
         if (std::memcmp(data + 7 * (size_t)a + 3, data + 7 * (size_t)b + 3, 3 * sizeof(double)) != 0) return false;
       }
+  return true;
+}
+
+bool plan_faces_normals(const Plan &plan, const double *data) {
+  if (!plan.faced) return false;
+  for (int t = 0; t < plan.n_tiles; ++t)
+    for (int g = 0; g < plan.block / 4; ++g) {
+      const size_t i0 = (size_t)t * plan.block + 128 * (g / 32) + g % 32;
+      const int a = plan.lanes[i0].cidx;
+      if (a < 0) continue;
+      for (int k = 1; k < 4; ++k) {
+        const int b = plan.lanes[i0 + 32 * k].cidx;
+        if (b >= 0 && std::memcmp(data + 7 * (size_t)a + 3, data + 7 * (size_t)b + 3, 3 * sizeof(double)) != 0) return false;
+      }
+    }
   return true;
 }
 

@@ -69,6 +69,15 @@ struct Plan {
   // Then the pair's accumulators can stay in registers from the first of the two updates to the second (step_solve.hip:
   // the CHAIN form; plan.cpp derives the parity of the first's time step where it sets the flag).
   bool chained = false;
+  // A chained plan in which the FOUR constraints of every thread pair of the FACE form, plan lanes 128 W + 32 k + l
+  // (k = 0 .. 3, l < 32) of each 128-lane half of a tile, are consecutive updates of the SAME two bodies -- the four
+  // contact points of a box face: every tile's period is a multiple of 4, member k is active only if member k - 1 is,
+  // level[member 0] is a multiple of 4, every active member has member 0's slot0 and slot1 and level = level[member 0]
+  // + k, and per tile, per block of four time steps ((level / 4) mod (P / 4)) and per LDS slot other than the world's,
+  // all constraints that use the slot belong to ONE group.  Then a group's accumulators can stay in registers through
+  // the four updates of a block, and nothing else in the tile reads or writes them inside the block: the three
+  // barriers inside it order nothing (step_solve.hip: the FACE form).
+  bool faced = false;
   std::vector<int32_t> tile_nslots;   // per tile, slots in use (slot 0 = world)
   std::vector<int32_t> tile_slot_off; // per tile, offset into slot_body
   std::vector<int32_t> slot_body;     // slot -> global body index (-1 for slot 0)
@@ -109,6 +118,9 @@ Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
 // (the constraint descriptors, [m][7]) of A and of B are the same three bit patterns (-0.0 is not +0.0) wherever both
 // are active.  A pair with an A and no B asks nothing.  false on a plan that is not chained.
 bool plan_shares_normals(const Plan &plan, const double *data);
+// ... and what the FACE form asks beyond a faced plan: all active members of every group of four (Plan::faced) carry
+// member 0's normal, bit for bit.  A group with one member asks nothing.  false on a plan that is not faced.
+bool plan_faces_normals(const Plan &plan, const double *data);
 
 // how many workgroups (CUs) an oversize island's patches may occupy at once: sizes the patches (plan.cpp::build_patches)
 void set_patch_workgroups(int n);

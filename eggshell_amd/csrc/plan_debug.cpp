@@ -173,4 +173,22 @@ egs_status egs_debug_plan_share(int32_t n, int32_t m, const int32_t *body0, cons
   });
 }
 
+egs_status egs_debug_plan_faced(int32_t n, int32_t m, const int32_t *body0, const int32_t *body1, int32_t *faced) {
+  return plan_entry(n, m, body0, body1, [&]() -> egs_status {
+    const Plan pl = build_plan(n, m, body0, body1, 256);
+    if (faced) *faced = pl.faced ? 1 : 0;
+    return EGS_OK;
+  });
+}
+
+egs_status egs_debug_plan_face_normals(int32_t n, int32_t m, const int32_t *body0, const int32_t *body1, const double *data,
+                                       int32_t *face) {
+  if (m > 0 && !data) return EGS_ERR_INVALID;
+  return plan_entry(n, m, body0, body1, [&]() -> egs_status {
+    const Plan pl = build_plan(n, m, body0, body1, 256);
+    if (face) *face = plan_faces_normals(pl, data) ? 1 : 0;
+    return EGS_OK;
+  });
+}
+
 }  // extern "C"

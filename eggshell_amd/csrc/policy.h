@@ -46,6 +46,11 @@ inline OversizeSchedule choose_oversize_schedule(int n_patch_tiles, int quad_per
   return kAllGlobal;
 }
 
+// The FACE form of the fused step launch (step_solve.hip) runs a 256-constraint tile on 128 threads at up to 256 VGPRs:
+// four tiles fit a CU.  Resident tiles per CU it asks for, 3 or 4 (3: by a larger LDS request); measured on MI355X,
+// 24 C3 piles (1 536 tiles on 256 CUs: 1 024 + 512 at four, 768 + 768 at three): DESIGN.md section 5.
+constexpr int kFaceTilesPerCu = 4;
+
 // Isotropic bodies, batched work: the register-light tile kernel (no stored B, three
 // 256-constraint tiles per CU in fp64, four in fp32) against the regular one (fp64:
 // 512-constraint tiles, one per CU; fp32: three 256-constraint tiles).

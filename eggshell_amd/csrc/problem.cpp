@@ -60,15 +60,17 @@ namespace egs {
 void decide_share_normals(egs_problem *p) {
   if (p->share_normals != egs_problem::kShareUndecided) return;
   p->share_normals = 0;
+  p->face_normals = false;
   if (!p->tile_plan_ready || !p->plan.chained || p->plan.block != 256 || !p->have_constraints) return;
   hipStream_t s = p->ctx->stream;
-  int one = 1, flag = 0;
+  int both = 3, flag = 0;   // bit 0: SHARE's answer, bit 1 with it: FACE's
   int32_t *scratch = p->error_flag.p + 1;
-  HIPCHK(hipMemcpyAsync(scratch, &one, sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(scratch, &both, sizeof(int), hipMemcpyHostToDevice, s));
   launch_share_normals(p->plan.n_tiles, p->tile.lanes.p, p->data.p, scratch, s);
   HIPCHK(hipMemcpyAsync(&flag, scratch, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  p->share_normals = flag != 0 ? 1 : 0;
+  p->share_normals = (flag & 1) ? 1 : 0;
+  p->face_normals = flag == 3 && p->plan.faced;
 }
 }  // namespace egs
 
@@ -974,6 +976,13 @@ egs_status egs_problem_get_schedule_full(egs_problem *p, int32_t *schedule) {
   if (!p || !schedule) return EGS_ERR_INVALID;
   const egs_status st = egs_problem_get_schedule(p, schedule);
   if (st == EGS_OK) *schedule |= (int32_t)(p->last_sched & egs_problem::kSchedFullOnly);
+  return st;
+}
+
+egs_status egs_problem_get_schedule_forms(egs_problem *p, int32_t *schedule) {
+  if (!p || !schedule) return EGS_ERR_INVALID;
+  const egs_status st = egs_problem_get_schedule_full(p, schedule);
+  if (st == EGS_OK) *schedule |= (int32_t)(p->last_sched & egs_problem::kSchedFormsOnly);
   return st;
 }
 

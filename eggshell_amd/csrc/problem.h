@@ -58,6 +58,9 @@ struct egs_problem {
   // ... and these are left out of egs_problem_get_schedule too, whose callers compare it with EGS_SCHED_CHAIN masked
   // against the statistics: egs_problem_get_schedule_full alone reports them
   static constexpr uint32_t kSchedFullOnly = EGS_SCHED_SHARE;
+  // ... and these out of that one as well, whose callers compare it exactly on scenes that take the form:
+  // egs_problem_get_schedule_forms alone reports them
+  static constexpr uint32_t kSchedFormsOnly = EGS_SCHED_FACE;
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
@@ -70,6 +73,9 @@ struct egs_problem {
   // Every writer of data sets one of the last two; a new tile plan turns a decided answer back to undecided.
   static constexpr int kShareUndecided = -1, kShareDeviceData = -2;
   int share_normals = kShareDeviceData;
+  // FACE's precondition on a faced tile plan (plan.h: plan_faces_normals), the second answer of the same look: valid
+  // while share_normals is 1, which it implies
+  bool face_normals = false;
   // which kernel takes the oversize islands of a GS / SOR solve (choose_oversize_schedule; EGS_PATCH=0
   // forces the all-global kernel, EGS_QUAD_PATCH=0 the 1-lane patches) and how many workgroups the
   // all-global kernel's persistent grid may have: both from the runtime's occupancy of the kernels

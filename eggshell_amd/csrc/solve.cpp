@@ -25,6 +25,8 @@ struct SweepSchedule {
   bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_solve.hip)
   bool chain = false;       // ... whose steady loop keeps a pair's accumulators in registers between its two updates (CHAIN)
   bool share = false;       // ... and a thread one linear block and one pair of weights for both constraints (SHARE)
+  bool face = false;        // ... on a thread pair per box face: four updates behind one barrier, 128 threads per tile (FACE)
+  int face_tiles = kFaceTilesPerCu;   // ... at this many resident tiles per CU (policy.h; EGS_STEP_FACE_TILES)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -34,7 +36,8 @@ struct SweepSchedule {
     return (iso ? EGS_SCHED_ISO : 0) | (timetable ? EGS_SCHED_STATIC : 0) | (linsym ? EGS_SCHED_LINSYM : 0) |
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
            (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0) |
-           (chain ? EGS_SCHED_CHAIN : 0) | (share ? EGS_SCHED_SHARE : 0);
+           (chain ? EGS_SCHED_CHAIN : 0) | (share ? EGS_SCHED_SHARE : 0) |
+           (face ? EGS_SCHED_FACE : 0);
   }
 };
 
@@ -98,6 +101,15 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   const char *he = std::getenv("EGS_STEP_SHARE");
   if (s.chain && p->share_normals == egs_problem::kShareUndecided) decide_share_normals(p);
   s.share = s.chain && p->share_normals == 1 && !(he && std::atoi(he) == 0);
+  // ... and the four contact points of a face on one thread pair, where the plan lays them 32 lanes apart with nothing
+  // else on their bodies inside a block of four steps (plan.h: faced) and all four carry one normal (problem.h:
+  // face_normals).  The form has the forward sweep of the store-free launch without restitution; backward SOR, the
+  // storing launch and the restitution twin keep SHARE.  EGS_STEP_FACE=0 keeps SHARE everywhere;
+  // EGS_STEP_FACE_TILES=3|4 sets the resident tiles per CU.
+  const char *ae = std::getenv("EGS_STEP_FACE"), *te = std::getenv("EGS_STEP_FACE_TILES");
+  s.face = s.share && pl.faced && p->face_normals && method == EGS_GAUSS_SEIDEL && s.defer && !p->restitution &&
+           !(ae && std::atoi(ae) == 0);
+  if (te && (std::atoi(te) == 3 || std::atoi(te) == 4)) s.face_tiles = std::atoi(te);
   return s;
 }
 
@@ -185,7 +197,8 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, sc.share, ctx->stream);
+          if (sc.face) launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, ctx->stream);
+          else launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, sc.share, ctx->stream);
           // the system this launch assembled: stored, or the problem's to make on demand from the state it read
           p->sys_deferred = sc.defer;
           p->deferred_prev = false;
@@ -431,7 +444,7 @@ void fill_stats(egs_problem *p, egs_solve_stats *st) {
   st->n_tiles = pl.n_tiles;
   st->n_global = (int32_t)pl.global.size();
   st->reserved = p->use_quad ? 1 : 0;  // 1: 4-lanes-per-constraint schedule for GS/SOR
-  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_sched & ~(egs_problem::kSchedRefinements | egs_problem::kSchedFullOnly));
+  st->schedule = (p->use_quad ? EGS_SCHED_QUAD : 0) | (p->last_sched & ~(egs_problem::kSchedRefinements | egs_problem::kSchedFullOnly | egs_problem::kSchedFormsOnly));
   if (!p->use_quad && !pl.global.empty())
     st->schedule |= p->oversize == kQuadPatches ? EGS_SCHED_QUAD_PATCHES : p->oversize == kLanePatches ? EGS_SCHED_LANE_PATCHES : EGS_SCHED_ALL_GLOBAL;
   st->tile_constraints = pl.block;

@@ -58,7 +58,9 @@
 // PAIR (ASSEMBLE only): an update runs on a lane pair, each lane holding one side of two constraints; described where
 // it is written, before the kernel.  CHAIN (PAIR only): where the pair's two constraints are consecutive updates of the
 // same two bodies, the steady loop hands their accumulators from the first update to the second in registers.  SHARE
-// (CHAIN only): where the two also have one contact normal, the lane keeps their linear block and weights once.
+// (CHAIN only): where the two also have one contact normal, the lane keeps their linear block and weights once.  FACE
+// (a kernel of its own, step_solve_face_kernel): where the plan lays the four contact points of a face 32 lanes apart,
+// a thread pair holds all four and runs their updates behind one barrier.
 #include <algorithm>
 
 #include "kernels.h"
@@ -619,6 +621,204 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
   }
 }
 
+// ---- FACE (a refinement of SHARE; GS, store-free, no restitution): four updates on a thread pair ------------------
+// A face pair of a pile has four contact points: four consecutive updates of the same two bodies, which the phase-major
+// plan lays 32 lanes apart (plan.h: Plan::faced).  CHAIN keeps points 0 and 1 on one thread pair and hands the
+// accumulators to points 2 and 3, in the next wavefront, through LDS and a barrier.  Here a tile's 256 plan lanes run on
+// 128 threads: thread l of wavefront W plays side s = l & 1 of the FOUR constraints at plan lanes 128 W + 32 k + (l >> 1),
+// k = 0 .. 3 (members A, B, C, D).  The even lane owns A and C (rhs, x, inv, D's off-diagonal), the odd lane B and D; the
+// lane holds ONE linear part (A's: all four carry one normal, problem.h: face_normals) and four angular ones.  The steady
+// loop walks four steps per iteration behind one compare: load, pass A, B, C, D on the same six registers, store, ONE
+// barrier.  Inside a block of four steps nothing else in the tile touches the group's two bodies (Plan::faced says so
+// per block and slot), so LDS holds the same doubles wherever another lane reads them, and the three barriers that
+// stood inside the block ordered nothing.  Every operand is the double the SHARE form reads in its place, every product
+// the multiply it does, in its order: the same bits.  A group with fewer than four members runs those it has.
+// The fill, the drain and the accumulation take the general loop, which walks blocks the same way with `due` and `sweep`
+// per group: right on any block of the timetable.
+// Registers: up to 256 VGPRs at two wavefronts per SIMD (four 128-thread tiles per CU).  Held products: all nine linear ones
+// and kFaceAng of the nine angular ones per member, the largest count that keeps scratch 0.
+#ifndef EGS_FACE_ANG_PRODUCTS
+#define EGS_FACE_ANG_PRODUCTS 6
+#endif
+constexpr int kFaceLin = 9, kFaceAng = EGS_FACE_ANG_PRODUCTS;
+constexpr int kFaceThreads = 128, kFaceLanes = 256;
+
+// the prologue of one owned constraint: assembled and finished as the one-lane form does (the same D, inv and rhs)
+__device__ __forceinline__ void face_load(const SolveArgs<double> &A, const LaneDesc &d, const int32_t *slot_body,
+                                          Cons<double> &c, double (&x)[3]) {
+  const bool active = d.cidx >= 0;
+  const bool has0 = active && d.slot0 != 0, has1 = active && d.slot1 != 0;
+  if (active) {
+    assemble_lane<false, false>(A.assemble, d.cidx, c);
+    load_cons<double, true, false, true>(A, d.cidx, has0, has1, has0 ? slot_body[d.slot0] : 0, has1 ? slot_body[d.slot1] : 0, c);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) x[r] = c.rhs[r];
+  }
+}
+// the sides of the pair's two owned constraints (the even lane's c is E's, the odd lane's O's) change hands once: this
+// lane's side of both; LIN: E's linear block and weights too
+template <bool LIN>
+__device__ __forceinline__ void face_sides(const Cons<double> &c, int side, PairLin<kFaceLin> &L, PairAng<kFaceAng> &GE,
+                                           PairAng<kFaceAng> &GO) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double ga = dpp_all<kQuadSwap>(side ? c.J0[6 * r + 3 + k] : c.J1[6 * r + 3 + k]);
+      GE.J[3 * r + k] = side ? ga : c.J0[6 * r + 3 + k];
+      GO.J[3 * r + k] = side ? c.J1[6 * r + 3 + k] : ga;
+      if constexpr (LIN) {
+        const double gl = dpp_all<kQuadSwap>(c.J1[6 * r + k]);
+        L.J[3 * r + k] = side ? gl : c.J0[6 * r + k];
+      }
+    }
+  }
+  if constexpr (LIN) {
+    const double gl = dpp_all<kQuadSwap>(c.wl1), ga = dpp_all<kQuadSwap>(c.wa1);
+    L.wl = side ? gl : c.wl0;
+    L.wa = side ? ga : c.wa0;
+  }
+}
+
+__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int METHOD = 1;
+  const int tid = (int)threadIdx.x, tile = blockIdx.x;
+  const int side = tid & 1;
+  const bool even = side == 0, odd = side == 1;
+  // member k of this thread pair's group: plan lane lane0 + 32 k
+  const size_t lane0 = (size_t)tile * kFaceLanes + (tid >> 6) * 128 + ((tid & 63) >> 1);
+  double *s_acc = reinterpret_cast<double *>(smem);
+  const int nslots = A.tile_nslots[tile];
+  const int32_t *slot_body = A.slot_body + A.tile_slot_off[tile];
+  const int P = A.tile_period[tile], depth = A.tile_depth[tile];
+
+  // how many members the group has (member k is not active without member k - 1), and this lane's side's accumulator:
+  // one address for all of them
+  int nm = 0;
+  unsigned ac;
+  {
+    const LaneDesc dA = A.lanes[lane0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (A.lanes[lane0 + 32 * k].cidx >= 0) nm = k + 1;
+    ac = lds_addr(s_acc + (dA.cidx >= 0 ? (side ? dA.slot1 : dA.slot0) : 0) * 6);
+  }
+  const bool has = ac != lds_addr(s_acc);   // slot 0, the world: no body on this side
+
+  // the two constraints this lane owns, one after the other: A then C on the even lane, B then D on the odd one.  The
+  // first's blocks wait in LDS (the accumulators' place, before they are set up; element e of thread i at e * 128 + i)
+  // while the second is assembled: the assembly has the registers the one-lane form gives it.
+  PairLin<kFaceLin> L;
+  PairAng<kFaceAng> GA, GB, GC, GD;
+  Cons<double> c0 = {}, c1 = {};
+  double x0[3] = {0.0, 0.0, 0.0}, x1[3] = {0.0, 0.0, 0.0};
+  face_load(A, A.lanes[lane0 + 32 * side], slot_body, c0, x0);
+  face_sides<true>(c0, side, L, GA, GB);
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    s_acc[e * kFaceThreads + tid] = L.J[e];
+    s_acc[(9 + e) * kFaceThreads + tid] = GA.J[e];
+    s_acc[(18 + e) * kFaceThreads + tid] = GB.J[e];
+  }
+  asm volatile("" ::: "memory");   // stored here, loaded below: not carried in registers
+  face_load(A, A.lanes[lane0 + 64 + 32 * side], slot_body, c1, x1);
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    L.J[e] = s_acc[e * kFaceThreads + tid];
+    GA.J[e] = s_acc[(9 + e) * kFaceThreads + tid];
+    GB.J[e] = s_acc[(18 + e) * kFaceThreads + tid];
+  }
+  face_sides<false>(c1, side, L, GC, GD);
+  __syncthreads();   // every thread has its blocks back
+  for (int s = tid; s < nslots; s += kFaceThreads) {   // a fresh solve: the accumulators start from zero
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = 0.0;
+  }
+  // the held products, formed behind both assemblies: fewer registers live through the second one
+  L.form();
+  GA.form(L.wa);
+  GB.form(L.wa);
+  GC.form(L.wa);
+  GD.form(L.wa);
+  PairShared<kFaceLin, kFaceAng> SA{L, GA}, SB{L, GB}, SC{L, GC}, SD{L, GD};
+  const int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, A.sweeps, 0));
+  __syncthreads();
+
+  // The timetable of step_solve_kernel per GROUP: member k's level is A's + k and the period a multiple of 4, so the
+  // four members are due at the four steps of one block, in one sweep (0: the accumulation), and the group's next
+  // block comes a period later.  Both loops walk a block per iteration behind ONE barrier: what holds for the steady
+  // window holds for the fill and the drain (Plan::faced is about every block), and a block past the timetable's end
+  // finds no group due.
+  const int levelA = A.lane_level[lane0];
+  int sweep = 0, due = (nm > 0 && A.sweeps >= 0) ? levelA : 0x7fffffff;
+  int t_s = 0, t_e = 0;
+  const int Ps = __builtin_amdgcn_readfirstlane(P);
+  if (A.steady && Ps > 0) {
+    // whole blocks from a step = 0 (mod 4): a step's residue is its phase's
+    t_s = (__builtin_amdgcn_readfirstlane(depth) + 3) & ~3;
+    t_e = min(Ps * (A.sweeps + 1), t_end);
+    t_e -= (t_e - t_s) & 3;
+    if (t_e <= t_s) t_s = t_e = 0;
+  }
+  int t = 0, stop = t_e > t_s ? t_s : t_end;
+  double a[6];
+  for (;;) {
+    for (; t < stop; t += 4) {
+      if (due == t) {
+        pair_pass<METHOD, kQuadEven, true, true, false>(SA, ac, a, has, even, c0, x0, sweep, A.cfm);
+        if (nm > 1) pair_pass<METHOD, kQuadOdd, true, false, false>(SB, ac, a, has, odd, c0, x0, sweep, A.cfm);
+        if (nm > 2) pair_pass<METHOD, kQuadEven, true, false, false>(SC, ac, a, has, even, c1, x1, sweep, A.cfm);
+        if (nm > 3) pair_pass<METHOD, kQuadOdd, true, false, false>(SD, ac, a, has, odd, c1, x1, sweep, A.cfm);
+        if (has) store6(ac, a);   // after the group's last active member
+        due += P;
+        if (++sweep > A.sweeps) due = 0x7fffffff;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    }
+    if (t >= t_end) break;
+    {
+      // steady: one compare of the phase of the group's first update with the clock's; no `due`, no `sweep`, no
+      // accumulation branch
+      const int phF = nm > 0 ? levelA % Ps : -1;
+      int tp = t % Ps;
+      for (; t < t_e; t += 4) {
+        if (phF == tp) {
+          pair_pass<METHOD, kQuadEven, false, true, false>(SA, ac, a, has, even, c0, x0, 1, A.cfm);
+          if (nm > 1) pair_pass<METHOD, kQuadOdd, false, false, false>(SB, ac, a, has, odd, c0, x0, 1, A.cfm);
+          if (nm > 2) pair_pass<METHOD, kQuadEven, false, false, false>(SC, ac, a, has, even, c1, x1, 1, A.cfm);
+          if (nm > 3) pair_pass<METHOD, kQuadOdd, false, false, false>(SD, ac, a, has, odd, c1, x1, 1, A.cfm);
+          if (has) store6(ac, a);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        tp = tp + 4 == Ps ? 0 : tp + 4;
+      }
+    }
+    // drain: the group's next block at or after t_e, from its level (read again: not held through the window)
+    const int lv = A.lane_level[lane0];
+    const int n = t_e > lv ? (t_e - lv + Ps - 1) / Ps : 0;
+    sweep = n;   // update n on a grid whose update 0 is the accumulation
+    due = (nm == 0 || n > A.sweeps) ? 0x7fffffff : lv + P * n;
+    stop = t_end;
+  }
+
+  // the owner's constraint numbers, read again: not held through the loops
+  const int cidx0 = A.lanes[lane0 + 32 * side].cidx, cidx1 = A.lanes[lane0 + 64 + 32 * side].cidx;
+  if (nm > 0) pair_epilogue(A, SA, ac, even, cidx0, c0, x0);
+  if (nm > 1) pair_epilogue(A, SB, ac, odd, cidx0, c0, x0);
+  if (nm > 2) pair_epilogue(A, SC, ac, even, cidx1, c1, x1);
+  if (nm > 3) pair_epilogue(A, SD, ac, odd, cidx1, c1, x1);
+  for (int s = tid + 1; s < nslots; s += kFaceThreads) {
+    const int body = slot_body[s];
+    if (body < 0) continue;   // unused slot number
+#pragma unroll
+    for (int k = 0; k < 6; ++k) A.acc[(size_t)body * 6 + k] = s_acc[s * 6 + k];
+  }
+}
+
 // FRIC: the Coulomb pyramid on the constraints with mu >= 0 (solve_device.h: project_pyramid), A.mu not NULL.  The
 // ASSEMBLE form has none (solve.cpp: choose_sweep).
 template <typename REAL, int BLOCK, int METHOD, bool ISO, int GROUP, bool HIST, bool LINSYM = false, bool ASSEMBLE = false,
@@ -914,6 +1114,20 @@ void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_ti
     if (pair) launch_step_solve_assemble_t<false, true>(b, method, n_tiles, s);
     else launch_step_solve_assemble_t<false, false>(b, method, n_tiles, s);
   }
+}
+
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, hipStream_t s) {
+  if (n_tiles <= 0) return;
+  SolveArgs<double> b = a;
+  b.n_tiles = n_tiles;
+  // the accumulators; the prologue keeps 27 doubles per thread in the same LDS first
+  size_t lds = std::max((size_t)b.max_slots * 6, (size_t)27 * kFaceThreads) * sizeof(double);
+  // the registers allow four tiles per CU; a request above a quarter of the CU's 160 KiB of LDS leaves room for three
+  constexpr size_t kQuarterLds = 160 * 1024 / 4;
+  if (tiles_per_cu == 3) lds = std::max(lds, kQuarterLds + 1024);
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(step_solve_face_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(step_solve_face_kernel, dim3(n_tiles), dim3(kFaceThreads), lds, s, b);
 }
 
 template void launch_step_solve<double>(const SolveArgs<double> &, int, int, int, int, bool, hipStream_t);

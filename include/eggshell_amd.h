@@ -116,7 +116,7 @@ typedef enum {
                                       egs_debug_plan_chained).  The same bits; EGS_STEP_CHAIN=0 switches it off.
                                       A refinement of EGS_SCHED_PAIR: egs_problem_get_schedule reports it,
                                       egs_solve_stats.schedule does not (its bits stay those of the pair launch) */
-  EGS_SCHED_SHARE = 16384          /* ... in which a thread keeps ONE linear Jacobian block and one pair of weights for
+  EGS_SCHED_SHARE = 16384,         /* ... in which a thread keeps ONE linear Jacobian block and one pair of weights for
                                       its side of both constraints: the two contacts of every thread pair carry the
                                       same normal, bit for bit (egs_debug_plan_share), decided once per
                                       egs_problem_set_constraints.  The same bits; EGS_STEP_SHARE=0 switches it off.
@@ -124,6 +124,13 @@ typedef enum {
                                       (callers compare egs_problem_get_schedule with EGS_SCHED_CHAIN masked against
                                       egs_solve_stats.schedule).  A world, whose collider writes the contacts on the
                                       device, does not take the form */
+  EGS_SCHED_FACE = 32768           /* ... in which a thread pair holds the FOUR contact points of a box face and runs
+                                      their four updates behind one barrier, the two bodies' accumulators in registers
+                                      from the first to the last (plans that are faced: egs_debug_plan_faced; one
+                                      normal per face: egs_debug_plan_face_normals; GS, the store-free launch, no
+                                      restitution).  128 threads per 256-constraint tile.  The same bits;
+                                      EGS_STEP_FACE=0 switches it off, EGS_STEP_FACE_TILES=3|4 sets the tiles per CU.
+                                      A refinement of EGS_SCHED_SHARE: only egs_problem_get_schedule_forms reports it */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -403,6 +410,9 @@ egs_status egs_problem_get_stats(egs_problem *p, egs_solve_stats *stats);
 egs_status egs_problem_get_schedule(egs_problem *p, int32_t *schedule);
 /* ... and, with those, the refinements of a refinement (EGS_SCHED_SHARE).  Host only as well. */
 egs_status egs_problem_get_schedule_full(egs_problem *p, int32_t *schedule);
+/* ... and, with those, the form of the EGS_SCHED_SHARE launch that ran (EGS_SCHED_FACE): the two entries above and
+ * egs_solve_stats.schedule keep the bits they have without it.  Host only as well. */
+egs_status egs_problem_get_schedule_forms(egs_problem *p, int32_t *schedule);
 
 /* ---- entry 3: replaces Lcp::MixedConstraintsSolver(A, b, C, x_lo, x_hi, x, w)
  *      lcp.h:21-23 / lcp.cc:276-336 (and Lcp::MurtyPrincipalPivot,
@@ -1025,6 +1035,20 @@ egs_status egs_debug_plan_chained(int32_t n_bodies, int32_t m, const int32_t *bo
  * (EGS_SCHED_SHARE).                                                                                               */
 egs_status egs_debug_plan_share(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
                                 const double *data, int32_t *share);
+
+/* Host only: *faced = 1 if that plan is chained and the four constraints of every thread pair of the face form -- plan
+ * lanes 128 W + 32 k + l of a tile, k = 0 .. 3, l < 32, W = 0, 1 -- are consecutive updates of the same two bodies: every
+ * tile's period is a multiple of 4, member k exists only if member k - 1 does, level[member 0] is a multiple of 4,
+ * every member has member 0's two LDS slots and level[member 0] + k, and per tile, per block of four time steps
+ * ((level / 4) mod (period / 4)) and per LDS slot other than the world's, all constraints that use the slot belong to
+ * one such group.  What the step launch asks before it runs a face's four updates behind one barrier (EGS_SCHED_FACE). */
+egs_status egs_debug_plan_faced(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                int32_t *faced);
+
+/* Host only: *face = 1 if that plan is faced and every member of every such group has member 0's contact normal as bit
+ * patterns (data as in egs_debug_plan_share).  A group with one member asks nothing.                               */
+egs_status egs_debug_plan_face_normals(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
+                                       const double *data, int32_t *face);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
