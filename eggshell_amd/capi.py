@@ -60,6 +60,7 @@ EXPORTS = [
     "egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass",
     "egs_problem_set_restitution", "egs_world_set_restitution",
     "egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks",
+    "egs_problem_set_hinge_limits", "egs_world_set_joint_limits",
 ]
 
 
@@ -113,6 +114,10 @@ def load():
             _lib.egs_world_set_joint_motors.argtypes = [C.c_void_p, C.c_void_p]   # world, motor
             _lib.egs_world_get_blocks.argtypes = [C.c_void_p] * 8   # world, J0, J1, is_eq, lo, hi, rhs, err
             for name in ("egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks"):
+                getattr(_lib, name).restype = C.c_int
+        if hasattr(_lib, "egs_problem_set_hinge_limits"):
+            for name in ("egs_problem_set_hinge_limits", "egs_world_set_joint_limits"):
+                getattr(_lib, name).argtypes = [C.c_void_p, C.c_void_p]   # problem / world, lim
                 getattr(_lib, name).restype = C.c_int
         if hasattr(_lib, "egs_problem_set_live_inertia"):
             # handle, inertia_body, torque / handle, Minv, f_ext
@@ -733,6 +738,15 @@ class Problem:
             raise ValueError("motor: %d values for %d constraints" % (motor.size, self.m))
         self.ctx.check(load().egs_problem_set_motors(self.h, _p(motor)))
 
+    def set_hinge_limits(self, lim=None):
+        """Hinge angle limits (egs_problem_set_hinge_limits): [m][8] = (qw, qx, qy, qz, sin lo, cos lo, sin hi, cos hi)
+        per constraint, q the quaternion of R0(0)^T R1(0); a (sin, cos) pair of (0, 0): no stop on that side.  A
+        HINGE_AXIS constraint past a stop gets the one-sided axis row of that stop.  None turns it off."""
+        lim = _f64(lim)
+        if lim is not None and lim.size != 8 * self.m:
+            raise ValueError("lim: %d values for %d constraints" % (lim.size, self.m))
+        self.ctx.check(load().egs_problem_set_hinge_limits(self.h, _p(lim)))
+
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
         w = np.zeros(3 * self.m)
@@ -1001,6 +1015,7 @@ class World:
 
     def set_joints(self, body0, body1, data):
         body0, body1, data = _i32(body0), _i32(body1), _f64(data)
+        self.m_joints = int(body0.shape[0])
         self.ctx.check(load().egs_world_set_joints(self.h, C.c_int32(body0.shape[0]), _p(body0), _p(body1), _p(data)))
 
     def set_joints_kinds(self, kind, body0, body1, data):
@@ -1023,6 +1038,15 @@ class World:
         """Hinge motors of the world's joints (egs_world_set_joint_motors): [m_joints][2] = (speed, tau); None: off."""
         motor = _f64(motor)
         self.ctx.check(load().egs_world_set_joint_motors(self.h, _p(motor)))
+
+    def set_joint_limits(self, lim=None):
+        """Hinge limits of the world's joints (egs_world_set_joint_limits): [m_joints][8] as Problem.set_hinge_limits;
+        None: off."""
+        lim = _f64(lim)
+        mj = getattr(self, "m_joints", None)
+        if lim is not None and mj is not None and lim.size != 8 * mj:
+            raise ValueError("lim: %d values for %d joints" % (lim.size, mj))
+        self.ctx.check(load().egs_world_set_joint_limits(self.h, _p(lim)))
 
     def step(self, dt, erp, prm, detect_contacts=True, want_stats=False):
         st = SolveStats()

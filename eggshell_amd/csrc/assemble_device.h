@@ -113,7 +113,7 @@ __device__ __forceinline__ void lock_block(const AssembleArgs &A, int b0, int b1
 //   c = t x s = (t1 s2 - t2 s1, t2 s0 - t0 s2, t0 s1 - t1 s0);  err = (d3(p, c), d3(q, c), 0)
 //   J0 = [0 | Rn], J1 = [0 | -1.0*Rn] (zero for a world side)
 // Rows 0 and 1 are equality rows; row 2, the axis row, is an inequality row with lo = hi = 0 (the multiplier pinned
-// at 0: the hinge turns freely) unless a motor opens its bounds (motor_row below).  t = -s is a false equilibrium
+// at 0: the hinge turns freely) unless a motor opens its bounds (motor_row below) or a stop is active (limit_row).  t = -s is a false equilibrium
 // (c = 0 there too): the linearisation holds for axes less than a right angle apart.
 __device__ __forceinline__ void hinge_block(const AssembleArgs &A, int b0, int b1, const double *d, double *j0, double *j1,
                                             double *e) {
@@ -302,7 +302,8 @@ __device__ __forceinline__ double assemble_rhs_bounce_t(const AssembleArgs &A, i
 // The motor table (egs_problem_set_motors), motor [m][2] = (speed, tau), not NULL: a HINGE_AXIS constraint i with
 // tau >= 0 (+inf allowed) gets lo[2] = -tau, hi[2] = +tau and the target t = speed / dt in place of kk err[2] (which
 // is 0 for it): rhs2 = t - ju, so that the solve asks for s^ . (w0' - w1') = speed within the torque limit.  Returns
-// whether it applied; tau < 0 and every other kind are left as assembled.
+// whether it applied; tau < 0 and every other kind are left as assembled.  A hinge whose stop is active this step
+// (limit_row below) is not handed to it: motor and limit share the axis row, and the row is the limit's then.
 template <bool EACH>
 __device__ __forceinline__ bool motor_row(const AssembleArgs &A, const double *motor, int i, double dt_each, const double *j0,
                                           const double *j1, const double *u0, const double *u1, double *lo, double *hi,
@@ -316,6 +317,60 @@ __device__ __forceinline__ bool motor_row(const AssembleArgs &A, const double *m
   const double ju = dot6p(j0 + 12, u0) + dot6p(j1 + 12, u1);
   rhs2 = t - ju;
   return true;
+}
+// The limit table (egs_problem_set_hinge_limits), lim [m][8] = (qw, qx, qy, qz, sin lo, cos lo, sin hi, cos hi), not
+// NULL: a HINGE_AXIS constraint i with a stop (a (sin, cos) pair that is not (0, 0)) has its angle read as the lock
+// reads its error -- q is the unit quaternion of Rref = R0(0)^T R1(0), which fixes theta = 0 -- and, past a stop, its
+// axis row made the one-sided row of that stop.  After the block (s, Rn, err[0..1], J keep their bits):
+//   Rq = quat_to_R(q);  T = mm3(R0, Rq);  E = mm3(T, R1^T) with R1^T formed by index (a world side: E = T)
+//   ax = (0.5*(E[7]-E[5]), 0.5*(E[2]-E[6]), 0.5*(E[3]-E[1]));  sn = d3(s, ax), s = mv3(R0, a0);  cs = 0.5*(((E[0]+E[4])+E[8]) - 1.0)
+//   upper set and sn*(1.0+chi) > shi*(1.0+cs):       err[2] = sn*chi - cs*shi, lo[2] = -inf, hi[2] = 0
+//   else lower set and sn*(1.0+clo) < slo*(1.0+cs):  err[2] = sn*clo - cs*slo, lo[2] = 0, hi[2] = +inf
+// The comparisons are tan(theta/2) against tan(limit/2), cross-multiplied; err[2] = sin(theta - limit).  The rhs row is
+// the ordinary kk err[2] - ju.  err2 / lo2 / hi2: row 2 of err, lo and hi, written only then.  Returns whether a stop is active; then motor_row leaves the row alone for this step.
+// Every other kind, a row without a stop and a hinge inside its range are left as assembled.
+__device__ __forceinline__ bool limit_row(const AssembleArgs &A, const double *lim, int i, double &err2, double &lo2, double &hi2) {
+  if (A.kind[i] != 3) return false;
+  const double *L = lim + (size_t)i * 8;
+  const double slo = L[4], clo = L[5], shi = L[6], chi = L[7];
+  const bool lower = slo != 0.0 || clo != 0.0, upper = shi != 0.0 || chi != 0.0;
+  if (!lower && !upper) return false;
+  const int b0 = A.body0[i], b1 = A.body1[i];
+  double R0[9], a0[3], s[3], Rq[9], T[9], E[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a0[k] = A.data[(size_t)i * 7 + k];
+  mv3(R0, a0, s);
+  quat_to_R(L[0], L[1], L[2], L[3], Rq);
+  mm3(R0, Rq, T);
+  if (b1 >= 0) {
+    double R1t[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) R1t[3 * r + c] = A.R[(size_t)b1 * 9 + 3 * c + r];
+    mm3(T, R1t, E);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = T[k];
+  }
+  const double ax[3] = {0.5 * (E[7] - E[5]), 0.5 * (E[2] - E[6]), 0.5 * (E[3] - E[1])};
+  const double sn = d3(s, ax);
+  const double cs = 0.5 * (((E[0] + E[4]) + E[8]) - 1.0);
+  if (upper && sn * (1.0 + chi) > shi * (1.0 + cs)) {
+    err2 = sn * chi - cs * shi;
+    lo2 = -INFINITY;
+    hi2 = 0.0;
+    return true;
+  }
+  if (lower && sn * (1.0 + clo) < slo * (1.0 + cs)) {
+    err2 = sn * clo - cs * slo;
+    lo2 = 0.0;
+    hi2 = INFINITY;
+    return true;
+  }
+  return false;
 }
 __device__ __forceinline__ double assemble_rhs(const AssembleArgs &A, const double *j0, const double *j1, const double *e,
                                                const double *u0, const double *u1, int r) {

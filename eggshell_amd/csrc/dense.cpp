@@ -213,6 +213,10 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
   // bounds a motored one would be solved as a lambda >= 0 row
   if (p->hinges && (use_bounds & 1) == 0)
     return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step takes a hinge axis row as a box row: a hinge needs use_bounds bit 0");
+  // whether a limited hinge's axis row is pinned or one-sided is decided on the device (limit_row): the host cannot tell
+  if (p->limits)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no hinge limits: hinge constraint " + std::to_string(p->limited_hinge) +
+                                                 " has a stop (take the table away, or use the sweeps)");
   if (p->hinges_pinned)
     return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   if (ok) *ok = 0;

@@ -186,11 +186,16 @@ void launch_quad_patch_solve(const SolveArgs<REAL> &a, int method, int n_tiles, 
 // which is part of SolveArgs<double>: the solve launches keep their kernel arguments, and the fused prologue of
 // step_solve_kernel never sees a hinge (solve.cpp: choose_sweep).  angular: the list holds an EGS_JOINT_LOCK or an
 // EGS_JOINT_HINGE_AXIS; false launches the form without them (and without the motors), the code of the lists before them.
+// limit [m][8] or NULL: the hinge limits (egs_problem_set_hinge_limits), travelling the same way; with a table the
+// angular form's instantiation with limit_row runs, without one the kernel the lists ran before the limits.
+struct HingeTables {
+  const double *motor = nullptr, *limit = nullptr;
+};
 template <typename REAL>
-void launch_assemble(const AssembleArgs &a, bool angular, const double *motor, hipStream_t s);
+void launch_assemble(const AssembleArgs &a, bool angular, const HingeTables &h, hipStream_t s);
 // ... with every constraint on its ensemble's rates (a.dt and a.erp are not read)
 template <typename REAL>
-void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const double *motor, hipStream_t s);
+void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const HingeTables &h, hipStream_t s);
 // partial sums of squares by row category: out[4*blocks].  mu [rows / 3] (may be NULL: off): rows 0 and 1 of a
 // constraint with mu >= 0 are sorted by the pyramid's bounds, as in the kernels below that
 // take the coefficients from SolveArgs::mu.

@@ -668,9 +668,12 @@ struct NoRates {};   // the scalar form's (empty) second argument
 // an instantiation of its own, so that the launches without it keep their registers.  motor: the hinge motors'
 // table (assemble_device.h: motor_row), NULL = off; read by hinge-axis lanes only.  ANGULAR: the list holds an angular
 // block (LOCK, HINGE_AXIS); without one the launch runs the instantiation that leaves them and the motors out, with
-// the registers and the occupancy it had before they existed.
-template <typename REAL, bool EACH, typename RATES, bool REST, bool ANGULAR>
-__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T, const double *motor) {
+// the registers and the occupancy it had before they existed.  LIMITS: the hinge limits' table (assemble_device.h:
+// limit_row) is set; an instantiation of the ANGULAR form of its own, so that the lists without a stop run the code
+// they ran before the limits.  A row whose stop is active is the limit's for the step: the motor leaves it alone.
+template <typename REAL, bool EACH, typename RATES, bool REST, bool ANGULAR, bool LIMITS = false>
+__global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T, const double *motor,
+                                                       const double *limit) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
   // stores hit 64 lines per instruction; staged, the workgroup writes its 256 x 18 block contiguously
   __shared__ REAL stage[256 * 19];   // row stride 19: conflict-free column walks
@@ -681,7 +684,12 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   bool eq[3];
   double dt = 0.0, erp = 0.0;   // EACH: the constraint's own; otherwise A.dt / A.erp where they are used
   if constexpr (EACH) constraint_rates(A, T, i, dt, erp);
+  // the stop's row first, while nothing else is live: three values and a flag wait for the block
+  bool stopped = false;
+  double stop_err = 0.0, stop_lo = 0.0, stop_hi = 0.0;
+  if constexpr (LIMITS) stopped = limit_row(A, limit, i, stop_err, stop_lo, stop_hi);
   assemble_one_t<EACH, ANGULAR>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
+  if (LIMITS && stopped) { e[2] = stop_err; lo[2] = stop_lo; hi[2] = stop_hi; }
   REAL *J0o = reinterpret_cast<REAL *>(A.J0), *J1o = reinterpret_cast<REAL *>(A.J1);
   REAL *loo = reinterpret_cast<REAL *>(A.lo), *hio = reinterpret_cast<REAL *>(A.hi);
   REAL *rhso = reinterpret_cast<REAL *>(A.rhs);
@@ -700,7 +708,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   }
   if (!live) return;
   double motor_rhs = 0.0;
-  const bool motored = ANGULAR && motor != nullptr && motor_row<EACH>(A, motor, i, dt, j0, j1, u0, u1, lo, hi, motor_rhs);
+  const bool motored = ANGULAR && !stopped && motor != nullptr && motor_row<EACH>(A, motor, i, dt, j0, j1, u0, u1, lo, hi, motor_rhs);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     if (r == 2 && motored)
@@ -1030,25 +1038,31 @@ void launch_tile_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 }
 
 template <typename REAL>
-void launch_assemble(const AssembleArgs &a, bool angular, const double *motor, hipStream_t s) {
+void launch_assemble(const AssembleArgs &a, bool angular, const HingeTables &h, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), t(256);
-  if (angular) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true>), g, t, 0, s, a, NoRates{}, motor);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true>), g, t, 0, s, a, NoRates{}, motor);
-  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, false>), g, t, 0, s, a, NoRates{}, nullptr);
-  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, false>), g, t, 0, s, a, NoRates{}, nullptr);
+  if (angular && h.limit) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit);
+  } else if (angular) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr);
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr);
+  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr);
 }
 
 template <typename REAL>
-void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const double *motor, hipStream_t s) {
+void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const HingeTables &h, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), b(256);
-  if (angular) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true>), g, b, 0, s, a, t, motor);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true>), g, b, 0, s, a, t, motor);
-  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, false>), g, b, 0, s, a, t, nullptr);
-  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, false>), g, b, 0, s, a, t, nullptr);
+  if (angular && h.limit) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true, true>), g, b, 0, s, a, t, h.motor, h.limit);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true, true>), g, b, 0, s, a, t, h.motor, h.limit);
+  } else if (angular) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true>), g, b, 0, s, a, t, h.motor, nullptr);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true>), g, b, 0, s, a, t, h.motor, nullptr);
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, false>), g, b, 0, s, a, t, nullptr, nullptr);
+  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, false>), g, b, 0, s, a, t, nullptr, nullptr);
 }
 
 template <typename REAL>
@@ -1228,8 +1242,8 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_global_solve<REAL>(const GlobalArgs<REAL> &, int, hipStream_t);                            \
   template void launch_cons_prepare<REAL>(const SolveArgs<REAL> &, hipStream_t);                             \
   template void launch_global_wres<REAL>(const GlobalArgs<REAL> &, hipStream_t);                            \
-  template void launch_assemble<REAL>(const AssembleArgs &, bool, const double *, hipStream_t);                                    \
-  template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, bool, const double *, hipStream_t);        \
+  template void launch_assemble<REAL>(const AssembleArgs &, bool, const HingeTables &, hipStream_t);                               \
+  template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, bool, const HingeTables &, hipStream_t);   \
   template void launch_residual_partials<REAL>(int, const REAL *, const REAL *, const REAL *, const REAL *,  \
                                                const uint8_t *, const REAL *, double *, int, hipStream_t);   \
   template void launch_velocity<REAL>(int, const double *, const double *, const double *, const REAL *, double,   \

@@ -341,6 +341,32 @@ const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, 
   return nullptr;
 }
 
+// What is wrong with a limit table: a non-finite entry anywhere; on a HINGE_AXIS row with a stop a q that is not a unit
+// quaternion within 1e-12 (constraints_fault's bound), a (sin, cos) pair that is neither (0, 0) nor on the unit circle
+// within 1e-12, a stop at +-pi (1 + cos <= 0: tan(limit / 2) has no value there), or lo above hi in the half-angle order
+// tan(lo / 2) > tan(hi / 2), cross-multiplied as limit_row compares.
+const char *limits_fault(size_t m, const int32_t *kind, const double *lim, int *first) {
+  *first = -1;
+  for (size_t i = 0; lim && i < m; ++i) {
+    const double *L = lim + 8 * i;
+    for (int k = 0; k < 8; ++k)
+      if (!std::isfinite(L[k])) return "non-finite hinge limit entry";
+    if (kind[i] != EGS_JOINT_HINGE_AXIS) continue;
+    const bool lower = L[4] != 0.0 || L[5] != 0.0, upper = L[6] != 0.0 || L[7] != 0.0;
+    if (!lower && !upper) continue;
+    if (!(std::fabs(((L[0] * L[0] + L[1] * L[1]) + L[2] * L[2]) + L[3] * L[3] - 1.0) <= 1e-12))
+      return "the hinge limit's reference quaternion is not a unit quaternion";
+    for (int k = 4; k < 8; k += 2) {
+      if (L[k] == 0.0 && L[k + 1] == 0.0) continue;
+      if (!(std::fabs(L[k] * L[k] + L[k + 1] * L[k + 1] - 1.0) <= 1e-12)) return "a hinge limit's (sin, cos) pair is not on the unit circle";
+      if (1.0 + L[k + 1] <= 0.0) return "a hinge limit at +-pi";
+    }
+    if (lower && upper && L[4] * (1.0 + L[7]) > L[6] * (1.0 + L[5])) return "a hinge's lower limit is above its upper limit";
+    if (*first < 0) *first = (int)i;
+  }
+  return nullptr;
+}
+
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp) {
   AssembleArgs a;
   a.n = p->n; a.m = p->m;
@@ -365,7 +391,7 @@ void note_assembled(egs_problem *p) {
 
 void do_assemble(egs_problem *p, double dt, double erp) {
   const AssembleArgs a = assemble_args(p, dt, erp);
-  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, motor_table(p), p->ctx->stream); });
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, hinge_tables(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   note_assembled(p);
   p->sys_deferred = false;   // every array is written: a deferred system is superseded
@@ -373,7 +399,7 @@ void do_assemble(egs_problem *p, double dt, double erp) {
 
 void do_assemble_each(egs_problem *p, const EnsembleRates &r) {
   const AssembleArgs a = assemble_args(p, 0.0, 0.0);   // the scalar pair is not read
-  with_real(p, [&](auto t) { launch_assemble_each<decltype(t)>(a, r, p->angular, motor_table(p), p->ctx->stream); });
+  with_real(p, [&](auto t) { launch_assemble_each<decltype(t)>(a, r, p->angular, hinge_tables(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   note_assembled(p);
   p->sys_deferred = false;
@@ -384,7 +410,7 @@ void ensure_system(egs_problem *p) {
   if (!p->sys_deferred) return;
   AssembleArgs a = assemble_args(p, p->deferred_dt, p->deferred_erp);
   if (p->deferred_prev) { a.pos = p->prev_pos.p; a.R = p->prev_R.p; a.v = p->prev_v.p; a.w = p->prev_w.p; }
-  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, motor_table(p), p->ctx->stream); });
+  with_real(p, [&](auto r) { launch_assemble<decltype(r)>(a, p->angular, hinge_tables(p), p->ctx->stream); });
   HIPCHK(hipGetLastError());
   p->sys_deferred = false;
 }
@@ -498,6 +524,8 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->friction = false;   // the coefficients were those of the old list (the world refills them: world_step.cpp)
   p->restitution = false;   // likewise
   p->motors = false;        // likewise
+  p->limits = false;        // likewise
+  p->limited_hinge = -1;
   p->hinges = p->hinges_pinned = p->angular = false;
   p->h_kind.clear();
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
@@ -762,6 +790,27 @@ egs_status egs_problem_set_motors(egs_problem *p, const double *motor) {
   });
 }
 
+egs_status egs_problem_set_hinge_limits(egs_problem *p, const double *lim) {
+  if (!p) return EGS_ERR_INVALID;
+  const size_t m = (size_t)p->m;
+  int first = -1;
+  if (lim && p->h_kind.size() != m) return fail(p->ctx, EGS_ERR_INVALID, "egs_problem_set_constraints first: the limits go with its kinds");
+  if (lim)
+    if (const char *fault = limits_fault(m, p->h_kind.data(), lim, &first)) return fail(p->ctx, EGS_ERR_INVALID, fault);
+  return guarded(p->ctx, [&]() -> egs_status {
+    ensure_system(p);   // a deferred system is the one of the table its step ran with
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));   // an assembly in flight may still read the old table
+    if (first >= 0) {
+      p->limit.alloc(m * 8);
+      upload(p->limit, lim, m * 8, p->ctx->stream);
+    }
+    p->limits = first >= 0;
+    p->limited_hinge = first;
+    p->h_rows_valid = false;   // the axis rows' bounds follow the table
+    return EGS_OK;
+  });
+}
+
 egs_status egs_problem_get_lambda(egs_problem *p, double *x) {
   if (!p || !x) return EGS_ERR_INVALID;
   return guarded(p->ctx, [&]() -> egs_status {
@@ -843,6 +892,8 @@ egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, cons
     note_kinds(p, kind);
     p->share_normals = egs_problem::kShareUndecided;
     p->motors = false;   // the table was given for the kinds before these
+    p->limits = false;   // likewise
+    p->limited_hinge = -1;
     p->have_constraints = true;
     p->h_rows_valid = false;
     return EGS_OK;

@@ -166,7 +166,14 @@ struct egs_problem {
   egs::DevBuf<double> motor;
   bool motors = false;
   bool hinges = false, hinges_pinned = false;
-  bool angular = false;                // the kinds hold a LOCK or a HINGE_AXIS: the assembly launches their form (kernels.h)
+  // Hinge limits (egs_problem_set_hinge_limits, egs_world_set_joint_limits): limit [m][8] fp64 = (q, sin lo, cos lo,
+  // sin hi, cos hi) per constraint (assemble_device.h: limit_row).  limits: some hinge has a stop -- then every
+  // assemble_kernel launch takes the table (hinge_tables) and the dense steps refuse, naming limited_hinge (the first
+  // such constraint); off, nothing reads it.  A new topology or new constraints turn it off (the world refills it).
+  egs::DevBuf<double> limit;
+  bool limits = false;
+  int limited_hinge = -1;
+  bool angular = false;               // the kinds hold a LOCK or a HINGE_AXIS: the assembly launches their form (kernels.h)
   std::vector<int32_t> h_kind;         // the kinds of the list (note_kinds)
   // egs_problem_set_dense_friction: max_outer > 0 makes egs_problem_step_dense solve the pyramid while friction is on
   // (0: it refuses); the outcome of the last such step (egs_problem_dense_friction_info).
@@ -219,8 +226,13 @@ void note_kinds(egs_problem *p, const int32_t *kind);
 const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, const double *data);
 void note_assembled(egs_problem *p);
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp);
-// the motor table the assembly launches take beside it: p->motor while motors are on, else NULL
-inline const double *motor_table(const egs_problem *p) { return p->motors ? p->motor.p : nullptr; }
+// the motor and limit tables the assembly launches take beside it: p->motor / p->limit while they are on, else NULL
+inline egs::HingeTables hinge_tables(const egs_problem *p) {
+  return egs::HingeTables{p->motors ? p->motor.p : nullptr, p->limits ? p->limit.p : nullptr};
+}
+// What is wrong with a limit table lim [m][8] for the kinds given (nothing: NULL; rows of other kinds are not read),
+// and in *first the first HINGE_AXIS constraint with a stop (-1: none).
+const char *limits_fault(size_t m, const int32_t *kind, const double *lim, int *first);
 // hinges / hinges_pinned from the kinds and motor [m][2] (NULL: none): problem.h
 void note_hinges(egs_problem *p, const double *motor);
 void do_assemble(egs_problem *p, double dt, double erp);

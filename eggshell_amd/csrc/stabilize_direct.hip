@@ -256,6 +256,11 @@ __global__ void __launch_bounds__(NT) stab_direct_kernel(StabDirectArgs a, const
 #pragma unroll
       for (int k = 0; k < 3; ++k) M.b[3 * i + k] = ev[k];
     }
+    if (a.limit)   // an active stop: err[2] = sin(theta - limit); a pass of its own, so that the blocks above keep their registers
+      for (int i = t; i < me; i += NT) {
+        double err2, lo2, hi2;
+        if (limit_row(a.as, a.limit, a.cons[c0 + i], err2, lo2, hi2)) M.b[3 * i + 2] = err2;
+      }
     __syncthreads();
     err_sq = direct_err_sq(M, N, t);
     go = err_sq > a.threshold && steps < a.max_steps;   // ensembles.cc:610, 632 (NaN stops)

@@ -13,6 +13,7 @@ using namespace egs;
 namespace {
 
 void world_fill_motors(egs_world *w);
+void world_fill_limits(egs_world *w);
 
 void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int m) {
   hipStream_t s = w->ctx->stream;
@@ -38,6 +39,7 @@ void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int 
     if (mj > 0) upload(np->data, w->jdata.data(), (size_t)mj * 7, s);
   }
   world_fill_motors(w);
+  world_fill_limits(w);
   np->have_constraints = true;
   np->h_rows_valid = false;
   w->topo_b0.assign(b0, b0 + m); w->topo_b1.assign(b1, b1 + m);
@@ -61,6 +63,27 @@ void world_fill_motors(egs_world *w) {
     p->motors = true;
   }
   note_hinges(p, any ? t.data() : nullptr);
+  p->h_rows_valid = false;
+}
+
+// The problem's limit table for its current list from the joints' (the joints come first; the contacts' rows are
+// zeros, which limit_row never reads: it returns on the kind).  The new topology has turned the problem's table off.
+void world_fill_limits(egs_world *w) {
+  egs_problem *p = w->prob;
+  const size_t mj = w->jb0.size();
+  p->limits = false;
+  p->limited_hinge = -1;
+  if (w->jlimit.empty() || p->m <= 0) return;
+  std::vector<double> t((size_t)p->m * 8, 0.0);
+  std::copy(w->jlimit.begin(), w->jlimit.end(), t.begin());
+  int first = -1;
+  limits_fault(mj, w->jkind.data(), w->jlimit.data(), &first);   // validated when it was set: the first stop only
+  if (first >= 0) {
+    p->limit.alloc(t.size());
+    upload(p->limit, t.data(), t.size(), w->ctx->stream);
+    p->limits = true;
+    p->limited_hinge = first;
+  }
   p->h_rows_valid = false;
 }
 
@@ -353,6 +376,7 @@ egs_status egs_world_set_joints_kinds(egs_world *w, int32_t m_joints, const int3
   if (kind) w->jkind.assign(kind, kind + m_joints);
   else w->jkind.assign((size_t)m_joints, EGS_JOINT_BALL);
   w->jmotor.clear();   // the motors were those of the old list
+  w->jlimit.clear();   // and the limits
   // the ball joints, in list order: what the collider prunes against
   std::vector<int32_t> bb0, bb1;
   std::vector<double> bd;
@@ -405,6 +429,23 @@ egs_status egs_world_set_joint_motors(egs_world *w, const double *motor) {
     if (motor) w->jmotor.assign(motor, motor + 2 * mj);
     else w->jmotor.clear();
     if (w->prob) world_fill_motors(w);
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_joint_limits(egs_world *w, const double *lim) {
+  if (!w) return EGS_ERR_INVALID;
+  const size_t mj = w->jb0.size();
+  int first = -1;
+  if (const char *fault = limits_fault(mj, w->jkind.data(), lim, &first)) return fail(w->ctx, EGS_ERR_INVALID, fault);
+  return guarded(w->ctx, [&]() -> egs_status {
+    if (w->prob) {
+      ensure_system(w->prob);
+      HIPCHK(hipStreamSynchronize(w->ctx->stream));   // an assembly in flight may still read the old table
+    }
+    if (lim && first >= 0) w->jlimit.assign(lim, lim + 8 * mj);
+    else w->jlimit.clear();
+    if (w->prob) world_fill_limits(w);
     return EGS_OK;
   });
 }

@@ -150,6 +150,12 @@ egs_status world_dense_guard(egs_world *w, int32_t use_bounds) {
   }
   if (hinges && use_bounds != 1)
     return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step takes a hinge axis row as a box row: a hinge needs use_bounds = 1");
+  if (!w->jlimit.empty()) {   // (kept only while a hinge has a stop) pinned or one-sided is decided on the device: the host cannot tell
+    int first = -1;
+    limits_fault(w->jkind.size(), w->jkind.data(), w->jlimit.data(), &first);
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no hinge limits: hinge joint " + std::to_string(first) +
+                                                 " has a stop (take the table away, or use the sweeps)");
+  }
   if (pinned)
     return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   return EGS_OK;

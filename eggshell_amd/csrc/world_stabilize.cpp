@@ -89,7 +89,9 @@ void world_relax_assemble(egs_world *w) {
   a.rhs = rx->wres.p;                  // scratch: the solve writes w there
   a.err = real<double>(rx->rhs);
   a.is_eq = w->rx.eq_scratch.p;
-  launch_assemble<double>(a, p->angular, nullptr, w->ctx->stream);   // no motor: the relaxation reads J and err only
+  // no motor: the relaxation reads J and err only.  The limits stay: an active stop's err[2] = sin(theta - limit) is a
+  // row of (J J^T) y = err, an inactive one's is 0 as a free hinge's
+  launch_assemble<double>(a, p->angular, HingeTables{nullptr, hinge_tables(p).limit}, w->ctx->stream);
   HIPCHK(hipGetLastError());
   rx->have_blocks = true;
   rx->lin_neg = !rx->joint_pairs;
@@ -270,6 +272,7 @@ egs_status egs_world_stabilize_direct(egs_world *w, int32_t mode, int32_t max_st
       }
       egs_problem *p = w->prob;
       a.as = assemble_args(p, 1.0, 0.2);
+      a.limit = hinge_tables(p).limit;
       a.pos = p->pos.p; a.R = p->R.p; a.v = p->v.p; a.w = p->w.p;
       a.cons = d.cons.p; a.cstart = d.cstart.p;
       a.bo = E > 1 ? w->ens.d_boff.p : nullptr;

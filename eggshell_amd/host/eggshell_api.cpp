@@ -199,6 +199,44 @@ HingeAxisJoint::HingeAxisJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr
   a0_ = a0_ / a0_.norm();
   a1_ = b1_ == nullptr ? a : b1_->R().transpose() * a;
   a1_ = a1_ / a1_.norm();
+  const Matrix3d R0t = b0_->R().transpose();
+  RToQuat(b1_ == nullptr ? R0t : R0t * b1_->R(), q_);
+}
+
+void HingeAxisJoint::SinCos(double *sn, double *cs) const {
+  const Vector3d s = b0_->R() * a0_;
+  const Matrix3d T = b0_->R() * QuatToR(q_);
+  const Matrix3d E = b1_ == nullptr ? T : T * b1_->R().transpose();
+  const Vector3d ax(0.5 * (E.d[7] - E.d[5]), 0.5 * (E.d[2] - E.d[6]), 0.5 * (E.d[3] - E.d[1]));
+  *sn = s.dot(ax);
+  *cs = 0.5 * (((E.d[0] + E.d[4]) + E.d[8]) - 1.0);
+}
+
+void HingeAxisJoint::LimitRow(double row[8]) const {
+  for (int k = 0; k < 4; ++k) row[k] = q_[k];
+  row[4] = std::isfinite(limit_lo_) ? std::sin(limit_lo_) : 0.0;
+  row[5] = std::isfinite(limit_lo_) ? std::cos(limit_lo_) : 0.0;
+  row[6] = std::isfinite(limit_hi_) ? std::sin(limit_hi_) : 0.0;
+  row[7] = std::isfinite(limit_hi_) ? std::cos(limit_hi_) : 0.0;
+}
+
+double HingeAxisJoint::Angle() const {
+  double sn, cs;
+  SinCos(&sn, &cs);
+  return std::atan2(sn, cs);
+}
+
+int HingeAxisJoint::ActiveStop(double *err2) const {
+  *err2 = 0.0;
+  if (!has_limits()) return 0;
+  double L[8], sn, cs;
+  LimitRow(L);
+  SinCos(&sn, &cs);
+  const double slo = L[4], clo = L[5], shi = L[6], chi = L[7];
+  const bool lower = slo != 0.0 || clo != 0.0, upper = shi != 0.0 || chi != 0.0;
+  if (upper && sn * (1.0 + chi) > shi * (1.0 + cs)) { *err2 = sn * chi - cs * shi; return 1; }
+  if (lower && sn * (1.0 + clo) < slo * (1.0 + cs)) { *err2 = sn * clo - cs * slo; return -1; }
+  return 0;
 }
 
 VectorXd HingeAxisJoint::ComputeError() const {
@@ -206,7 +244,9 @@ VectorXd HingeAxisJoint::ComputeError() const {
   const Vector3d t = b1_ == nullptr ? a1_ : b1_->R() * a1_;
   const Matrix3d Rn = AlignVectors(s, Vector3d(0, 0, 1));
   const Vector3d c = t.cross(s);
-  return ToX(Vector3d(Vector3d(Rn.d[0], Rn.d[1], Rn.d[2]).dot(c), Vector3d(Rn.d[3], Rn.d[4], Rn.d[5]).dot(c), 0.0));
+  double err2;
+  ActiveStop(&err2);   // 0 unless a stop is active: then sin(theta - limit)
+  return ToX(Vector3d(Vector3d(Rn.d[0], Rn.d[1], Rn.d[2]).dot(c), Vector3d(Rn.d[3], Rn.d[4], Rn.d[5]).dot(c), err2));
 }
 
 void HingeAxisJoint::ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *ct, VectorXd *lo, VectorXd *hi) const {
@@ -215,7 +255,11 @@ void HingeAxisJoint::ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *ct, Vecto
   if (b1_ == nullptr) SetBlock(J_b1, Matrix3d::Zero(), Matrix3d::Zero());
   else SetBlock(J_b1, Matrix3d::Zero(), -1.0 * Rn);
   AngularRows(ct, lo, hi, false);
-  if (tau_ >= 0) { (*lo)(2) = -tau_; (*hi)(2) = tau_; }
+  double err2;
+  const int stop = ActiveStop(&err2);   // an active stop's row is the limit's for the step: the motor leaves it alone
+  if (stop > 0) { (*lo)(2) = -INFINITY; (*hi)(2) = 0.0; }
+  else if (stop < 0) { (*lo)(2) = 0.0; (*hi)(2) = INFINITY; }
+  else if (tau_ >= 0) { (*lo)(2) = -tau_; (*hi)(2) = tau_; }
 }
 
 bool HingeAxisJoint::Describe(int32_t *kind, double data[7]) const {
@@ -234,6 +278,19 @@ static bool JointMotors(const JointsList &joints, std::vector<double> *motor) {
     const auto *h = dynamic_cast<const HingeAxisJoint *>(joints[j].get());
     if (!h || !(h->motor_torque() >= 0)) continue;
     (*motor)[2 * j] = h->motor_speed(); (*motor)[2 * j + 1] = h->motor_torque();
+    any = true;
+  }
+  return any;
+}
+
+// [joints][8], the limit rows of a joint list, zeros for whatever is no limited hinge; returns whether any hinge has a stop
+static bool JointLimits(const JointsList &joints, std::vector<double> *lim) {
+  bool any = false;
+  lim->assign(8 * joints.size(), 0.0);
+  for (size_t j = 0; j < joints.size(); ++j) {
+    const auto *h = dynamic_cast<const HingeAxisJoint *>(joints[j].get());
+    if (!h || !h->has_limits()) continue;
+    h->LimitRow(lim->data() + 8 * j);
     any = true;
   }
   return any;
@@ -263,6 +320,22 @@ void Ensemble::SetHingeMotor(int index, double speed, double max_torque) {
   if (speed != speed || std::isinf(speed) || max_torque != max_torque)
     throw egs::Error(EGS_ERR_INVALID, "SetHingeMotor: the speed must be finite and the torque limit a number");
   h->SetMotor(speed, max_torque);
+}
+
+void Ensemble::SetHingeLimits(int index, double lo, double hi) {
+  auto *h = index >= 0 && index < (int)joints_.size() ? dynamic_cast<HingeAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!h) throw egs::Error(EGS_ERR_INVALID, "SetHingeLimits: joint " + std::to_string(index) + " is not a hinge");
+  if (lo != lo || hi != hi || lo > hi) throw egs::Error(EGS_ERR_INVALID, "SetHingeLimits: the limits must be numbers with lo <= hi");
+  const double pi = 3.14159265358979323846;
+  if ((std::isfinite(lo) && std::fabs(lo) >= pi) || (std::isfinite(hi) && std::fabs(hi) >= pi) || lo == INFINITY || hi == -INFINITY)
+    throw egs::Error(EGS_ERR_INVALID, "SetHingeLimits: a finite limit lies inside (-pi, pi); -INFINITY / +INFINITY mean no stop");
+  h->SetLimits(lo, hi);
+}
+
+double Ensemble::HingeAngle(int index) const {
+  const auto *h = index >= 0 && index < (int)joints_.size() ? dynamic_cast<const HingeAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!h) throw egs::Error(EGS_ERR_INVALID, "HingeAngle: joint " + std::to_string(index) + " is not a hinge");
+  return h->Angle();
 }
 
 // ---- contact.cc ----------------------------------------------------------
@@ -741,6 +814,11 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
         motor.resize(2 * (size_t)m, -1.0);
         egs::check(egs_problem_set_motors(problem_, motor.data()));
       }
+      std::vector<double> lim;
+      if (JointLimits(joints_, &lim)) {   // likewise their limit rows, zeros for the contacts
+        lim.resize(8 * (size_t)m, 0.0);
+        egs::check(egs_problem_set_hinge_limits(problem_, lim.data()));
+      }
     }
     if (restitution_ >= 0) {   // every contact the coefficient, every joint -1
       std::vector<double> rest((size_t)m);
@@ -982,12 +1060,13 @@ bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
   std::vector<int32_t> jb0(mj), jb1(mj), jkind(mj);
-  std::vector<double> jdata((size_t)mj * 7), jmotor;
+  std::vector<double> jdata((size_t)mj * 7), jmotor, jlimit;
   for (int i = 0; i < mj; ++i) {
     jb0[i] = joints_[i]->i0_; jb1[i] = joints_[i]->i1_;
     if (!joints_[i]->Describe(&jkind[i], &jdata[(size_t)i * 7])) return false;
   }
   const bool motors = JointMotors(joints_, &jmotor);
+  if (!JointLimits(joints_, &jlimit)) jlimit.clear();
   if (!detect_contacts && !contacts_.empty()) return false;   // caller-supplied contacts: use the explicit path
   egs_context *ctx = egs::DefaultContext();
   const bool first = !world_;
@@ -1044,10 +1123,15 @@ bool Ensemble::StepOnDevice(double dt) {
     world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata; world_jkind_ = jkind;
     world_jmotor_.assign(2 * (size_t)mj, 0.0);
     for (int i = 0; i < mj; ++i) world_jmotor_[2 * (size_t)i + 1] = -1.0;
+    world_jlimit_.clear();   // ... and no limits
   }
   if (jmotor != world_jmotor_) {
     egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
     world_jmotor_ = jmotor;
+  }
+  if (jlimit != world_jlimit_) {
+    egs::check(egs_world_set_joint_limits(world_, jlimit.empty() ? nullptr : jlimit.data()));
+    world_jlimit_ = jlimit;
   }
   egs_solve_params prm = solver_params;
   prm.cfm = cfm_coeff;
@@ -1189,8 +1273,8 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   std::vector<double> pos(n * 3), R(n * 9), vl(n * 3), w(n * 3), Minv(first ? n * 36 : 0), side(first ? n * 3 : 0),
       fext(first ? n * 6 : 0);
   std::vector<int32_t> jb0, jb1, jkind;
-  std::vector<double> jdata, jmotor;
-  bool motors = false, hinges = false;
+  std::vector<double> jdata, jmotor, jlimit;
+  bool motors = false, hinges = false, limits = false;
   for (size_t i = 0; i < E; ++i)
     for (const auto &j : members_[i]->joints_) hinges = hinges || dynamic_cast<const HingeAxisJoint *>(j.get()) != nullptr;
   for (size_t i = 0; i < E; ++i) {
@@ -1230,7 +1314,10 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     std::vector<double> own;
     motors = JointMotors(m->joints_, &own) || motors;
     jmotor.insert(jmotor.end(), own.begin(), own.end());
+    limits = JointLimits(m->joints_, &own) || limits;
+    jlimit.insert(jlimit.end(), own.begin(), own.end());
   }
+  if (!limits) jlimit.clear();
   const Ensemble *lead = members_[0];
   for (size_t i = 1; i < E; ++i)   // (the constructor's check, again: SetWarmStart may have been called since)
     if (members_[i]->warm_start_ != lead->warm_start_ || members_[i]->warm_radius_ != lead->warm_radius_)
@@ -1314,10 +1401,15 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     world_jb0_ = jb0; world_jb1_ = jb1; world_jdata_ = jdata; world_jkind_ = jkind;
     world_jmotor_.assign(2 * jb0.size(), 0.0);   // a new joint list has no motors
     for (size_t j = 0; j < jb0.size(); ++j) world_jmotor_[2 * j + 1] = -1.0;
+    world_jlimit_.clear();   // ... and no limits
   }
   if (jmotor != world_jmotor_) {   // ... and the motors with them
     egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
     world_jmotor_ = jmotor;
+  }
+  if (jlimit != world_jlimit_) {   // ... and the limits
+    egs::check(egs_world_set_joint_limits(world_, jlimit.empty() ? nullptr : jlimit.data()));
+    world_jlimit_ = jlimit;
   }
   const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
   if (lead->use_dense_solver) {

@@ -19,6 +19,7 @@
 #define EGGSHELL_API_H
 
 #include <array>
+#include <cmath>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -167,10 +168,28 @@ class HingeAxisJoint : public Joint {
   void SetMotor(double speed, double max_torque) { speed_ = speed; tau_ = max_torque; }
   double motor_speed() const { return speed_; }
   double motor_torque() const { return tau_; }
+  // The angle limits (egs_problem_set_hinge_limits), in radians: theta, body0's turn relative to body1 about the axis
+  // since the joint was built, is kept within [lo, hi]; -INFINITY / +INFINITY: no stop on that side.  Past a stop the
+  // axis row is that stop's one-sided row for the step and the motor leaves it alone.  lo <= hi, a finite limit inside
+  // (-pi, pi): Ensemble::SetHingeLimits checks them.
+  void SetLimits(double lo, double hi) { limit_lo_ = lo; limit_hi_ = hi; }
+  double limit_lo() const { return limit_lo_; }
+  double limit_hi() const { return limit_hi_; }
+  bool has_limits() const { return std::isfinite(limit_lo_) || std::isfinite(limit_hi_); }
+  // the row of the limit table: (qw, qx, qy, qz, sin lo, cos lo, sin hi, cos hi), a missing stop as (0, 0)
+  void LimitRow(double row[8]) const;
+  // theta now, by atan2 on the host from the sine and cosine the device forms: for read-out only
+  double Angle() const;
 
  private:
+  // (sin theta, cos theta) in the device's operation order (assemble_device.h: limit_row)
+  void SinCos(double *sn, double *cs) const;
+  // +1: past the upper stop, -1: past the lower, 0: neither, by the device's half-angle comparison; *err2 = sin(theta - limit)
+  int ActiveStop(double *err2) const;
   Vector3d a0_, a1_;   // the unit axis in body0's frame and in body1's (the world's for a world side)
+  double q_[4];        // (w, x, y, z) of R0(0)^T R1(0): theta = 0
   double speed_ = 0.0, tau_ = -1.0;
+  double limit_lo_ = -INFINITY, limit_hi_ = INFINITY;
 };
 
 struct ContactGeometry {  // collision.h:12-27
@@ -410,6 +429,12 @@ class Ensemble {  // ensembles.h:25-186
   int AddHinge(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world,
                const Vector3d &axis_world);
   void SetHingeMotor(int index, double speed, double max_torque);
+  // Angle limits of the hinge at that index (HingeAxisJoint::SetLimits): lo <= theta <= hi in radians, -INFINITY /
+  // +INFINITY for no stop; they reach the device with the next step.  Throws egs::Error(EGS_ERR_INVALID) for an index
+  // that is no hinge, a NaN, lo > hi, or a finite |angle| >= pi.  An ensemble with a limited hinge does not step with
+  // use_dense_solver (EGS_ERR_UNSUPPORTED from the library).  HingeAngle: theta of that hinge now (host, atan2).
+  void SetHingeLimits(int index, double lo, double hi);
+  double HingeAngle(int index) const;
   const JointsList &joints() const { return joints_; }
   double restitution() const { return restitution_; }
   double restitution_threshold() const { return restitution_vth_; }
@@ -476,6 +501,7 @@ class Ensemble {  // ensembles.h:25-186
   std::vector<double> world_jdata_;
   std::vector<int32_t> world_jkind_;             // ... their kinds and their motors ([joints][2], (0, -1): none)
   std::vector<double> world_jmotor_;
+  std::vector<double> world_jlimit_;             // ... and their limit rows ([joints][8]; empty: none sent)
   bool warm_start_ = false, world_warm_ = false;   // asked for; what the device world was last told
   double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
   Contact::FrictionModel friction_model_ = Contact::FrictionModel::BOX;
@@ -552,6 +578,7 @@ class EnsembleGroup {
   std::vector<double> world_jdata_;
   std::vector<int32_t> world_jkind_;             // ... their kinds and their motors, re-sent with them
   std::vector<double> world_jmotor_;
+  std::vector<double> world_jlimit_;             // ... and their limit rows ([joints][8]; empty: none sent)
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
   std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)

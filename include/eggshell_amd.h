@@ -310,6 +310,36 @@ egs_status egs_problem_set_restitution(egs_problem *p, const double *rest /*[m] 
  *      EGS_ERR_UNSUPPORTED for it, and for any hinge when use_bounds bit 0 is clear.                                   */
 egs_status egs_problem_set_motors(egs_problem *p, const double *motor /*[m][2] or NULL = off*/);
 
+/* ---- Hinge angle limits: a per-constraint table on the EGS_JOINT_HINGE_AXIS block (no constraint kind of its own).
+ *      lim [m][8] = (qw, qx, qy, qz, sin lo, cos lo, sin hi, cos hi), fp64 whatever the problem's precision.  q is the
+ *      unit quaternion of Rref = R0(0)^T R1(0) (R0(0)^T for a world side), the EGS_JOINT_LOCK convention: it fixes
+ *      theta = 0, and theta is body0's turn relative to body1 about s = R0 a0.  A (sin, cos) pair of (0, 0) means "no
+ *      stop on that side"; a row with both pairs (0, 0), and any row of a constraint that is not HINGE_AXIS, is ignored.
+ *      The table holds sines and cosines, so the device code uses no trigonometric function.  For a HINGE_AXIS
+ *      constraint with a stop the assembly forms the block as above (s, t, Rn, c, err[0..1], J0, J1 keep their bits),
+ *      then, in fp64 without contraction:
+ *          Rq = quat_to_R(q);  T = mm3(R0, Rq);  E = mm3(T, R1^T), R1^T formed by index     (a world side: E = T)
+ *          ax = (0.5*(E[7]-E[5]), 0.5*(E[2]-E[6]), 0.5*(E[3]-E[1]))
+ *          sn = d3(s, ax)                                  sin(theta)
+ *          cs = 0.5*(((E[0]+E[4])+E[8]) - 1.0)             cos(theta)
+ *          upper set and sn*(1.0+chi) > shi*(1.0+cs):       err[2] = sn*chi - cs*shi;  lo[2] = -inf;  hi[2] = 0
+ *          else lower set and sn*(1.0+clo) < slo*(1.0+cs):  err[2] = sn*clo - cs*slo;  lo[2] = 0;  hi[2] = +inf
+ *          else: row 2 as without the table (err 0, lo = hi = 0)
+ *      The comparison is tan(theta/2) against tan(limit/2), cross-multiplied: monotone in theta on (-pi, pi), no
+ *      division.  err[2] = sin(theta - limit) in both cases, and rhs[2] is the ordinary kk err[2] - ju, so the solve asks
+ *      for s^ . (w0' - w1') <= -erp sin(theta - hi) / dt with lambda <= 0 at the upper stop, the mirror image at the
+ *      lower.  is_eq[2] stays 0.  Like the other angular errors this one linearises a sine, and the read-out wraps at
+ *      +-pi: a hinge that overshoots a stop by more than pi - |limit| is seen on the other side.
+ *      Motor and limit share the axis row: while a stop is active the row is the limit's and the motor leaves it alone for
+ *      that step (the motor applies only when lo[2] == hi[2] after the block); inside the range the motor works as above.
+ *      lim = NULL, or no hinge with a stop, turns limits off: every result and schedule flag is then what it is without
+ *      this call.  A new topology or a new egs_problem_set_constraints turns them off.  The stabilise passes of a world
+ *      take an active stop as one more row of (J J^T) y = err.  The dense steps return EGS_ERR_UNSUPPORTED while a hinge
+ *      has a stop (whether its row is pinned is decided on the device).  EGS_ERR_INVALID (nothing changes): a non-finite
+ *      entry; for a hinge with a stop a q that is not a unit quaternion within 1e-12, a pair that is neither (0, 0) nor on
+ *      the unit circle within 1e-12, a stop at +-pi (1 + cos <= 0), lo above hi in the half-angle order.              */
+egs_status egs_problem_set_hinge_limits(egs_problem *p, const double *lim /*[m][8] or NULL = off*/);
+
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
  *      const VectorXd& x, double epsilon_diagonal, double scale_diagonal)
@@ -665,6 +695,11 @@ egs_status egs_world_set_joints_kinds(egs_world *w, int32_t m_joints, const int3
  * assembly carries it, re-planned lists included; the stabilise entries work on positions and ignore it.
  * EGS_ERR_INVALID as egs_problem_set_motors (nothing changes).                                                   */
 egs_status egs_world_set_joint_motors(egs_world *w, const double *motor /*[m_joints][2] or NULL = off*/);
+/* egs_problem_set_hinge_limits for the world's joints: lim [m_joints][8], NULL = off.  Every step's assembly carries
+ * it, re-planned lists included, each ensemble of a batch its own rows; the stabilise entries take an active stop as a
+ * row of their system; the dense steps return EGS_ERR_UNSUPPORTED while a hinge has a stop.  egs_world_set_joints[_kinds]
+ * drops it.  EGS_ERR_INVALID as egs_problem_set_hinge_limits (nothing changes).                                  */
+egs_status egs_world_set_joint_limits(egs_world *w, const double *lim /*[m_joints][8] or NULL = off*/);
 egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_params *params,
                           int32_t detect_contacts, egs_solve_stats *stats);
 egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v, double *w_ang);
