@@ -146,6 +146,50 @@ __device__ __forceinline__ void hinge_block(const AssembleArgs &A, int b0, int b
     }
 }
 
+// A contact's blocks (contact.cc:14-117, FrictionModel::BOX) as functions of values: no loads.  d = the descriptor
+// (point[3], normal[3], depth).  contact_frame: Rn from the normal.  contact_side: side SIDE's block j (all 18 entries)
+// from Rn, the point and the body's position.  contact_err: e = err.  contact_blocks: the three together, j0 / j1 zero
+// for a side without a body (pos0 / pos1 not read there).  assemble_one_t's contact branch calls the parts where it had
+// their code, each side's behind that side's load of pos; the staged prologue of step_solve_face_kernel
+// (step_solve.hip), which has the values in registers, calls contact_blocks: the same operations in the same order,
+// the same bits.
+__device__ __forceinline__ void contact_frame(const double *d, double *Rn) { align_to_z(d + 3, Rn); }
+template <int SIDE>
+__device__ __forceinline__ void contact_side(const double *d, const double *Rn, const double *pos, double *j) {
+  double rel[3], cm[9], rw[9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) rel[k] = d[k] - pos[k];
+  crossmat(rel, cm);
+  if (SIDE == 1) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) cm[k] = -1.0 * cm[k];
+  }
+  mm3(Rn, cm, rw);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { j[6 * r + c] = SIDE == 1 ? Rn[3 * r + c] : -Rn[3 * r + c]; j[6 * r + 3 + c] = rw[3 * r + c]; }
+}
+__device__ __forceinline__ void contact_err(const double *d, double *e) { e[0] = 0.0; e[1] = 0.0; e[2] = -d[6]; }
+__device__ __forceinline__ void contact_blocks(const double *d, const double *pos0, const double *pos1, bool has0, bool has1,
+                                               double *j0, double *j1, double *e) {
+  double Rn[9];
+  contact_frame(d, Rn);
+#pragma unroll
+  for (int k = 0; k < 18; ++k) { j0[k] = 0.0; j1[k] = 0.0; }
+  if (has0) contact_side<0>(d, Rn, pos0, j0);
+  if (has1) contact_side<1>(d, Rn, pos1, j1);
+  contact_err(d, e);
+}
+// One side's u = v/dt + W f (ensembles.cc:569-570) from values: vw = (v, w) of the body, wf = its M^-1 f_ext.  The
+// expression of assemble_one_t's last lines, which keep it in place between their loads (v, the quotient, W f, the
+// sum): with W f loaded ahead of the division assemble_kernel<double> takes 132 VGPRs instead of 128 and loses a
+// wavefront per SIMD.  tests/test_gpu_step_face_prologue.py holds the two to the same bits.
+__device__ __forceinline__ void side_u(const double *vw, const double *wf, double dt, double *u) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r) u[r] = vw[r] / dt + wf[r];
+}
+
 // Constraint i: j0 / j1 (3x6 row-major, zero for a world side), e = err, lo / hi, eq per row (every row of a ball joint
 // and of a lock is an equality row, no row of a contact is, a hinge's axis row is not) and per side u = v/dt + W f
 // (zero for a world side), what the rhs needs.
@@ -205,32 +249,20 @@ __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, dou
     for (int k = 0; k < 3; ++k) { lo[k] = 0.0; hi[k] = 0.0; }
   } else {  // contact.cc:14-117, FrictionModel::BOX
     double Rn[9];
-    align_to_z(d + 3, Rn);
+    contact_frame(d, Rn);
     if (b0 >= 0) {
-      double rel[3], cm[9], rw[9];
+      double p[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) rel[k] = d[k] - A.pos[(size_t)b0 * 3 + k];
-      crossmat(rel, cm);
-      mm3(Rn, cm, rw);
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { j0[6 * r + c] = -Rn[3 * r + c]; j0[6 * r + 3 + c] = rw[3 * r + c]; }
+      for (int k = 0; k < 3; ++k) p[k] = A.pos[(size_t)b0 * 3 + k];
+      contact_side<0>(d, Rn, p, j0);
     }
     if (b1 >= 0) {
-      double rel[3], cm[9], rw[9];
+      double p[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) rel[k] = d[k] - A.pos[(size_t)b1 * 3 + k];
-      crossmat(rel, cm);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) cm[k] = -1.0 * cm[k];
-      mm3(Rn, cm, rw);
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { j1[6 * r + c] = Rn[3 * r + c]; j1[6 * r + 3 + c] = rw[3 * r + c]; }
+      for (int k = 0; k < 3; ++k) p[k] = A.pos[(size_t)b1 * 3 + k];
+      contact_side<1>(d, Rn, p, j1);
     }
-    e[0] = 0.0; e[1] = 0.0; e[2] = -d[6];
+    contact_err(d, e);
     eq[0] = false; eq[1] = false; eq[2] = false;
     lo[0] = -1.0; lo[1] = -1.0; lo[2] = 0.0;
     hi[0] = 1.0; hi[1] = 1.0; hi[2] = INFINITY;

@@ -148,7 +148,9 @@ __device__ __forceinline__ void acc_add_side1(REAL *a, const Cons<REAL> &c, cons
 // only what is derived from them is formed here.  Every lane of that form is a contact (solve.cpp: choose_sweep), whose
 // bounds are literals in the sweep (project_contact): c.lo, c.hi and c.eq are not used.
 // FRIC: the lane also takes its friction coefficient (A.mu, not NULL in a friction launch).
-template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false, bool FRIC = false>
+// WEIGHTED (ISO): the bodies' weights are in c.wl0 .. c.wa1 already, loaded by the caller with its other loads (the
+// staged prologue of step_solve_face_kernel); a side without a body gets the same zeros.  body0 / body1 are not read.
+template <typename REAL, bool ISO = false, bool LINSYM = false, bool ASSEMBLED = false, bool FRIC = false, bool WEIGHTED = false>
 __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bool has0, bool has1,
                                           int body0, int body1, Cons<REAL> &c) {
 #pragma unroll
@@ -156,11 +158,18 @@ __device__ __forceinline__ void load_cons(const SolveArgs<REAL> &A, int cidx, bo
     c.J0[k] = has0 ? (ASSEMBLED ? c.J0[k] : A.J0[(size_t)cidx * 18 + k]) : REAL(0);
     c.J1[k] = has1 ? (ASSEMBLED ? c.J1[k] : A.J1[(size_t)cidx * 18 + k]) : REAL(0);
   }
-  c.wl0 = c.wa0 = c.wl1 = c.wa1 = REAL(0);
+  if (ISO && WEIGHTED) {
+    c.wl0 = has0 ? c.wl0 : REAL(0); c.wa0 = has0 ? c.wa0 : REAL(0);
+    c.wl1 = has1 ? c.wl1 : REAL(0); c.wa1 = has1 ? c.wa1 : REAL(0);
+  } else {
+    c.wl0 = c.wa0 = c.wl1 = c.wa1 = REAL(0);
+  }
   if (ISO) {
     // B[k][q] = w_k J[q][k] is formed where it is needed; D = J0 B0 + J1 B1 in the stored-B order
-    if (has0) { c.wl0 = A.Minv[(size_t)body0 * 36]; c.wa0 = A.Minv[(size_t)body0 * 36 + 21]; }
-    if (has1) { c.wl1 = A.Minv[(size_t)body1 * 36]; c.wa1 = A.Minv[(size_t)body1 * 36 + 21]; }
+    if (!WEIGHTED) {
+      if (has0) { c.wl0 = A.Minv[(size_t)body0 * 36]; c.wa0 = A.Minv[(size_t)body0 * 36 + 21]; }
+      if (has1) { c.wl1 = A.Minv[(size_t)body1 * 36]; c.wa1 = A.Minv[(size_t)body1 * 36 + 21]; }
+    }
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll

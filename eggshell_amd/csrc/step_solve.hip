@@ -643,17 +643,75 @@ __device__ __forceinline__ void pair_step_solve(const SolveArgs<double> &A, unsi
 constexpr int kFaceLin = 9, kFaceAng = EGS_FACE_ANG_PRODUCTS;
 constexpr int kFaceThreads = 128, kFaceLanes = 256;
 
-// the prologue of one owned constraint: assembled and finished as the one-lane form does (the same D, inv and rhs)
-__device__ __forceinline__ void face_load(const SolveArgs<double> &A, const LaneDesc &d, const int32_t *slot_body,
-                                          Cons<double> &c, double (&x)[3]) {
-  const bool active = d.cidx >= 0;
-  const bool has0 = active && d.slot0 != 0, has1 = active && d.slot1 != 0;
-  if (active) {
-    assemble_lane<false, false>(A.assemble, d.cidx, c);
-    load_cons<double, true, false, true>(A, d.cidx, has0, has1, has0 ? slot_body[d.slot0] : 0, has1 ? slot_body[d.slot1] : 0, c);
+// The prologue in stages: each stage's loads are issued together, branch-free, and waited for once.
+//   1. the four members' descriptors and member 0's level;
+//   2. data[7] of both owned constraints and the group's two body numbers, taken ONCE, from member 0's slots through
+//      slot_body (every active member of a faced plan has member 0's slots: plan.h, Plan::faced) -- neither body0 /
+//      body1 nor kind is read: the launch is contacts only (solve.cpp: choose_sweep);
+//   3. the two bodies' state once per lane: pos, v, w, Wf, Minv[0], Minv[21] of each side;
+//   4. u0 and u1 once, then the two assemblies from those values (assemble_device.h: contact_blocks, side_u,
+//      assemble_rhs -- the operations of assemble_one in their order) and load_cons for D and inv.
+// An index that would not be valid is clamped to one that is (body 0 for a world side, constraint 0 for an idle
+// member) and the value selected away afterwards: a world side gets the zeros it always got, an idle member zeros
+// throughout.
+struct FaceBodies {
+  double pos0[3], pos1[3];
+  double u0[6], u1[6];     // v/dt + W f per side, zeros for a world side
+  double wl0, wa0, wl1, wa1;
+  bool has0, has1;         // the group's: member 0 is active and has a body on the side
+};
+// stage 3 and the first half of stage 4; b0 / b1: the sides' body numbers, negative where there is none
+__device__ __forceinline__ void face_bodies(const SolveArgs<double> &A, int b0, int b1, FaceBodies &B) {
+  const AssembleArgs &G = A.assemble;
+  const size_t i0 = (size_t)max(b0, 0), i1 = (size_t)max(b1, 0);
+  double vw0[6], vw1[6], wf0[6], wf1[6];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) x[r] = c.rhs[r];
+  for (int k = 0; k < 3; ++k) {
+    B.pos0[k] = G.pos[i0 * 3 + k];
+    B.pos1[k] = G.pos[i1 * 3 + k];
+    vw0[k] = G.v[i0 * 3 + k];
+    vw1[k] = G.v[i1 * 3 + k];
+    vw0[3 + k] = G.w[i0 * 3 + k];
+    vw1[3 + k] = G.w[i1 * 3 + k];
   }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    wf0[k] = G.Wf[i0 * 6 + k];
+    wf1[k] = G.Wf[i1 * 6 + k];
+  }
+  B.wl0 = A.Minv[i0 * 36];
+  B.wa0 = A.Minv[i0 * 36 + 21];
+  B.wl1 = A.Minv[i1 * 36];
+  B.wa1 = A.Minv[i1 * 36 + 21];
+  __builtin_amdgcn_sched_barrier(0);   // every load above is issued before the first use below
+  side_u(vw0, wf0, G.dt, B.u0);
+  side_u(vw1, wf1, G.dt, B.u1);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    B.u0[k] = B.has0 ? B.u0[k] : 0.0;
+    B.u1[k] = B.has1 ? B.u1[k] : 0.0;
+  }
+}
+// one owned constraint from its descriptor d and the bodies' values: assembled and finished as the one-lane form does
+// (the same J, rhs, D and inv); idle: zeros
+__device__ __forceinline__ void face_assemble(const SolveArgs<double> &A, const double (&d)[7], const FaceBodies &B, bool active,
+                                              Cons<double> &c, double (&x)[3]) {
+  const bool has0 = active && B.has0, has1 = active && B.has1;
+  double e[3];
+  contact_blocks(d, B.pos0, B.pos1, has0, has1, c.J0, c.J1, e);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) c.rhs[r] = assemble_rhs(A.assemble, c.J0, c.J1, e, B.u0, B.u1, r);
+  c.wl0 = B.wl0; c.wa0 = B.wa0; c.wl1 = B.wl1; c.wa1 = B.wa1;
+  load_cons<double, true, false, true, false, true>(A, 0, has0, has1, 0, 0, c);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    c.rhs[r] = active ? c.rhs[r] : 0.0;
+    c.inv[r] = active ? c.inv[r] : 0.0;
+    // opaque: formed here, in the prologue, as when loads pinned the assembly -- not sunk to the loops that use them
+    asm volatile("" : "+v"(c.rhs[r]), "+v"(c.inv[r]));
+    x[r] = c.rhs[r];
+  }
+  asm volatile("" : "+v"(c.D[3]), "+v"(c.D[6]), "+v"(c.D[7]));   // the off-diagonal entries a forward update takes
 }
 // the sides of the pair's two owned constraints (the even lane's c is E's, the odd lane's O's) change hands once: this
 // lane's side of both; LIN: E's linear block and weights too
@@ -693,27 +751,44 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
   const int32_t *slot_body = A.slot_body + A.tile_slot_off[tile];
   const int P = A.tile_period[tile], depth = A.tile_depth[tile];
 
-  // how many members the group has (member k is not active without member k - 1), and this lane's side's accumulator:
-  // one address for all of them
-  int nm = 0;
-  unsigned ac;
-  {
-    const LaneDesc dA = A.lanes[lane0];
+  // stage 1: the four members' descriptors and the group's level.  How many members the group has (member k is not
+  // active without member k - 1), and this lane's side's accumulator: one address for all of them
+  LaneDesc dm[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (A.lanes[lane0 + 32 * k].cidx >= 0) nm = k + 1;
-    ac = lds_addr(s_acc + (dA.cidx >= 0 ? (side ? dA.slot1 : dA.slot0) : 0) * 6);
-  }
+  for (int k = 0; k < 4; ++k) dm[k] = A.lanes[lane0 + 32 * k];
+  const int levelA = A.lane_level[lane0];
+  int nm = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (dm[k].cidx >= 0) nm = k + 1;
+  const int slot0 = dm[0].cidx >= 0 ? dm[0].slot0 : 0, slot1 = dm[0].cidx >= 0 ? dm[0].slot1 : 0;
+  const unsigned ac = lds_addr(s_acc + (side ? slot1 : slot0) * 6);
   const bool has = ac != lds_addr(s_acc);   // slot 0, the world: no body on this side
 
-  // the two constraints this lane owns, one after the other: A then C on the even lane, B then D on the odd one.  The
-  // first's blocks wait in LDS (the accumulators' place, before they are set up; element e of thread i at e * 128 + i)
-  // while the second is assembled: the assembly has the registers the one-lane form gives it.
+  // the two constraints this lane owns: A and C on the even lane, B and D on the odd one
+  const int own0 = side ? dm[1].cidx : dm[0].cidx, own1 = side ? dm[3].cidx : dm[2].cidx;
+  // stage 2: their descriptors and the group's bodies (slot 0 holds -1)
+  double d0[7], d1[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    d0[k] = A.assemble.data[(size_t)max(own0, 0) * 7 + k];
+    d1[k] = A.assemble.data[(size_t)max(own1, 0) * 7 + k];
+  }
+  const int body0 = slot_body[slot0], body1 = slot_body[slot1];
+  __builtin_amdgcn_sched_barrier(0);   // issued together, before the first wait
+  // stage 3: the bodies' state, once per lane
+  FaceBodies B;
+  B.has0 = slot0 != 0;
+  B.has1 = slot1 != 0;
+  face_bodies(A, body0, body1, B);
+
+  // stage 4: one assembly after the other.  The first's blocks wait in LDS (the accumulators' place, before they are
+  // set up; element e of thread i at e * 128 + i) while the second is assembled from the same body values.
   PairLin<kFaceLin> L;
   PairAng<kFaceAng> GA, GB, GC, GD;
   Cons<double> c0 = {}, c1 = {};
-  double x0[3] = {0.0, 0.0, 0.0}, x1[3] = {0.0, 0.0, 0.0};
-  face_load(A, A.lanes[lane0 + 32 * side], slot_body, c0, x0);
+  double x0[3], x1[3];
+  face_assemble(A, d0, B, own0 >= 0, c0, x0);
   face_sides<true>(c0, side, L, GA, GB);
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
@@ -722,7 +797,10 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
     s_acc[(18 + e) * kFaceThreads + tid] = GB.J[e];
   }
   asm volatile("" ::: "memory");   // stored here, loaded below: not carried in registers
-  face_load(A, A.lanes[lane0 + 64 + 32 * side], slot_body, c1, x1);
+  // ... and the second assembly, which no longer loads, is not scheduled into the first: one at a time in the registers
+  __builtin_amdgcn_sched_barrier(0);
+  face_assemble(A, d1, B, own1 >= 0, c1, x1);
+  __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
@@ -751,7 +829,6 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
   // block comes a period later.  Both loops walk a block per iteration behind ONE barrier: what holds for the steady
   // window holds for the fill and the drain (Plan::faced is about every block), and a block past the timetable's end
   // finds no group due.
-  const int levelA = A.lane_level[lane0];
   int sweep = 0, due = (nm > 0 && A.sweeps >= 0) ? levelA : 0x7fffffff;
   int t_s = 0, t_e = 0;
   const int Ps = __builtin_amdgcn_readfirstlane(P);
