@@ -29,6 +29,7 @@ SCHED_PAIR = 4096
 SCHED_CHAIN = 8192
 SCHED_SHARE = 16384
 SCHED_FACE = 32768
+SCHED_FACE_SPLIT = 65536
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
@@ -46,7 +47,7 @@ EXPORTS = [
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
-    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_debug_plan_faced", "egs_debug_plan_face_normals", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
+    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_debug_plan_faced", "egs_debug_plan_face_normals", "egs_debug_face_split", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
@@ -929,6 +930,21 @@ def debug_plan_faced(n_bodies, body0, body1):
     if st != OK:
         raise EgsError(st, "egs_debug_plan_faced failed")
     return bool(out.value)
+
+
+def debug_face_split(n_tiles, slots, depth, period, sweeps, force=None):
+    """Host-only: the split of the FACE launch in time (see egs_debug_face_split) for n_tiles tiles on `slots` resident
+    slots.  force: None, the policy decides; (h, s1), the last h tiles after s1 sweeps.  Returns (split tiles, s1, pieces):
+    pieces int32 [n][4] in ticket order, per piece tile, resume, sweeps, kind (0 whole, 1 first part, 2 second part)."""
+    h, s1 = (-1, 0) if force is None else force
+    tiles, cut, n = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    pieces = np.zeros((2 * max(int(n_tiles), 0) + 1, 4), dtype=np.int32)
+    st = load().egs_debug_face_split(C.c_int32(n_tiles), C.c_int32(slots), C.c_int32(depth), C.c_int32(period),
+                                     C.c_int32(sweeps), C.c_int32(h), C.c_int32(s1), C.byref(tiles), C.byref(cut),
+                                     _p(pieces), C.byref(n))
+    if st != OK:
+        raise EgsError(st, "egs_debug_face_split failed")
+    return tiles.value, cut.value, pieces[:n.value].copy()
 
 
 def debug_plan_face_normals(n_bodies, body0, body1, data):

@@ -154,7 +154,19 @@ void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_ti
 // the FACE form of the share launch (step_solve.hip): GS, store-free, no restitution, on a plan that is Plan::faced whose
 // groups of four carry one normal (problem.h: face_normals), a.steady on; 128 threads per tile; the same bits.
 // tiles_per_cu: 3 or 4 resident tiles per CU (4: what the registers allow; 3: the launch asks for more LDS)
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, hipStream_t s);
+// w (NULL: one workgroup per tile, blockIdx = tile): the launch split in time.  w->n_workgroups persistent workgroups
+// take the pieces of w->pieces (policy.h: face_piece_list) by ticket; a split tile's first part hands lambda and the
+// accumulators to its second part through a.x / a.acc and flags[tile]; the same bits.
+struct FacePiece;
+struct FaceWork {
+  const FacePiece *pieces;   // [n_pieces]
+  uint32_t *counter;         // the problem's ticket counter: never reset, ticket = the value drawn - ticket_base
+  uint32_t *flags;           // [n_tiles] the epoch of the launch whose first part of the tile has been stored
+  uint32_t ticket_base, epoch;
+  int32_t n_pieces;
+  int32_t n_workgroups;      // the grid: min(pieces, resident slots); every workgroup draws tickets until one is past the list
+};
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork *w, hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);

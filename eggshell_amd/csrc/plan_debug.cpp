@@ -1,5 +1,5 @@
 // plan_debug.cpp -- the plan-inspection entries of the C ABI (egs_debug_plan*, egs_debug_matvec_plan,
-// egs_debug_choose_oversize_schedule): what the host planners (plan.h, matvec_plan.h) and the schedule policy
+// egs_debug_choose_oversize_schedule, egs_debug_face_split): what the host planners (plan.h, matvec_plan.h) and the schedule policy
 // (policy.h) decide for a constraint graph, per constraint.  Host code only: no HIP call, no context, no device.
 #include <exception>
 
@@ -189,6 +189,29 @@ egs_status egs_debug_plan_face_normals(int32_t n, int32_t m, const int32_t *body
     if (face) *face = plan_faces_normals(pl, data) ? 1 : 0;
     return EGS_OK;
   });
+}
+
+egs_status egs_debug_face_split(int32_t n_tiles, int32_t slots, int32_t depth, int32_t period, int32_t sweeps,
+                                int32_t force_tiles, int32_t force_s1, int32_t *split_tiles, int32_t *s1, int32_t *pieces,
+                                int32_t *n_pieces) {
+  if (n_tiles < 0 || slots <= 0 || sweeps < 0) return EGS_ERR_INVALID;
+  try {
+    const FaceSplit f = force_tiles >= 0 ? face_split_forced(n_tiles, force_tiles, force_s1, sweeps)
+                                         : face_split_policy(n_tiles, slots, depth, period, sweeps);
+    if (split_tiles) *split_tiles = f.tiles;
+    if (s1) *s1 = f.s1;
+    std::vector<FacePiece> list;
+    face_piece_list(n_tiles, slots, f, sweeps, list);
+    if (n_pieces) *n_pieces = (int32_t)list.size();
+    if (pieces)
+      for (size_t i = 0; i < list.size(); ++i) {
+        pieces[4 * i] = list[i].tile; pieces[4 * i + 1] = list[i].resume;
+        pieces[4 * i + 2] = list[i].sweeps; pieces[4 * i + 3] = list[i].kind;
+      }
+    return EGS_OK;
+  } catch (const std::exception &) {
+    return EGS_ERR_INVALID;
+  }
 }
 
 }  // extern "C"

@@ -48,8 +48,90 @@ inline OversizeSchedule choose_oversize_schedule(int n_patch_tiles, int quad_per
 
 // The FACE form of the fused step launch (step_solve.hip) runs a 256-constraint tile on 128 threads at up to 256 VGPRs:
 // four tiles fit a CU.  Resident tiles per CU it asks for, 3 or 4 (3: by a larger LDS request); measured on MI355X,
-// 24 C3 piles (1 536 tiles on 256 CUs: 1 024 + 512 at four, 768 + 768 at three): DESIGN.md section 5.
+// 24 C3 piles (1 536 tiles on 256 CUs: 1 024 + 512 at four, 768 + 768 at three): DESIGN.md section 5.  Measured again
+// with the launch split in time (below): at four the 512 are split and the step runs at 52 230 pile-steps/s, at three
+// there is no remainder to split and it stays at 48 025.  Four.
 constexpr int kFaceTilesPerCu = 4;
+
+// The FACE launch split in time (step_solve.hip: pieces).  With n_tiles = k x slots + R, 0 < R <= slots / 2, the last
+// round keeps half the resident slots empty or more.  R tiles are then cut after sweep s1: a slot runs
+//     a first part (accumulation + sweeps 1 .. s1), then a whole tile        depth + P s1  +  depth + P S   steps
+//     a whole tile, then a second part (sweeps s1 + 1 .. S, resumed)         depth + P S   +  depth + P (S - s1 - 1)
+// where two rounds walk 2 (depth + P S).  s1 = S / 2 makes the two sequences equal to within one period.  Per slot the
+// split saves P (S - s1) steps and adds a second fill (depth) and what a second prologue, the hand-over and tiles that
+// no longer walk in step on a CU cost, kFaceSplitPrologueSteps.  Measured on MI355X, 24 C3 piles (depth 64, P 8; a
+// block of 4 steps is about 1 us): a prologue and an epilogue take about 25 us (100 steps), and at 100 and at 50 sweeps
+// the split launch came out 27 and 28 us (about 110 steps) behind what that alone predicts -- 0.442 against 0.475 ms at
+// 100 sweeps, 0.294 against 0.275 at 50.  260 steps with a margin: the split starts at 81 sweeps on such a tile, where
+// the saving is 328 steps against 324.  At the headline it is 400, half of P S, against 324.
+constexpr int kFaceSplitPrologueSteps = 260;
+struct FaceSplit {
+  int tiles = 0;   // H: the LAST H tiles of the plan are split; 0: no split
+  int s1 = 0;      // ... after this many sweeps, 1 .. S - 1
+};
+inline FaceSplit face_split_policy(long n_tiles, long slots, int depth, int P, int S) {
+  FaceSplit f;
+  if (slots <= 0 || n_tiles <= slots || S < 2 || P <= 0) return f;
+  const long R = n_tiles % slots;
+  if (R == 0 || 2 * R > slots) return f;
+  const int s1 = S / 2;
+  if ((long)P * (S - s1) <= (long)depth + kFaceSplitPrologueSteps) return f;
+  f.tiles = (int)R;
+  f.s1 = s1;
+  return f;
+}
+
+// EGS_STEP_FACE_SPLIT_FORCE=h,s1: the last h tiles (clamped to the tile count) after s1 sweeps, whatever the policy says
+inline FaceSplit face_split_forced(long n_tiles, long h, long s1, int S) {
+  FaceSplit f;
+  if (h <= 0 || s1 < 1 || s1 > S - 1) return f;
+  f.tiles = (int)std::min(h, n_tiles);
+  f.s1 = (int)s1;
+  return f;
+}
+
+// One piece of work in the split FACE launch.  Workgroups take pieces in list order (by ticket), so a second part
+// comes after its first part in the list.
+struct FacePiece {
+  int32_t tile, resume, sweeps, kind;   // kind: kFaceWhole, kFaceFirst (publishes the tile), kFaceSecond (waits for it)
+};
+enum { kFaceWhole = 0, kFaceFirst = 1, kFaceSecond = 2 };
+// The list for n_tiles tiles of which the last f.tiles are split after f.s1 of S sweeps: the whole tiles of the full
+// rounds; then the first parts spread evenly among the whole tiles that fill the resident slots with them; then the
+// remaining whole tiles, which follow the first parts; then the second parts, which follow the first group's tiles.
+template <typename VEC>
+inline void face_piece_list(int n_tiles, long slots, FaceSplit f, int S, VEC &out) {
+  out.clear();
+  const int H = std::min(std::max(f.tiles, 0), n_tiles), whole = n_tiles - H;
+  const bool split = H > 0 && f.s1 >= 1 && f.s1 < S;
+  if (!split) {
+    for (int t = 0; t < n_tiles; ++t) out.push_back(FacePiece{t, 0, S, kFaceWhole});
+    return;
+  }
+  // whole tiles that run beside the first parts: what is left of the slots, as far as there are tiles; those before
+  // them are the full rounds, those after them follow the first parts
+  const long beside = std::min<long>(whole, std::max<long>(slots - H, 0));
+  const long later = std::min<long>(whole - beside, H);
+  const int lead = (int)(whole - beside - later);
+  int t = 0;
+  for (; t < lead; ++t) out.push_back(FacePiece{t, 0, S, kFaceWhole});
+  // first parts and the `beside` whole tiles, interleaved evenly (whichever dispatch order the slots fill in, a CU gets
+  // its share of both)
+  long done_f = 0, done_w = 0;
+  const long total = H + beside;
+  for (long i = 0; i < total; ++i) {
+    // first part number done_f is due once (done_f + 1) / H <= (i + 1) / total
+    if (done_f < H && (done_w >= beside || done_f * total <= i * (long)H)) {
+      out.push_back(FacePiece{whole + (int)done_f, 0, f.s1, kFaceFirst});
+      ++done_f;
+    } else {
+      out.push_back(FacePiece{t++, 0, S, kFaceWhole});
+      ++done_w;
+    }
+  }
+  for (; t < whole; ++t) out.push_back(FacePiece{t, 0, S, kFaceWhole});
+  for (int h = 0; h < H; ++h) out.push_back(FacePiece{whole + h, 1, S - f.s1, kFaceSecond});
+}
 
 // Isotropic bodies, batched work: the register-light tile kernel (no stored B, three
 // 256-constraint tiles per CU in fp64, four in fp32) against the regular one (fp64:

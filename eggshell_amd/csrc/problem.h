@@ -6,6 +6,7 @@
 #include "kernels.h"
 #include "matvec_plan.h"
 #include "plan.h"
+#include "policy.h"
 #include "runtime.h"
 
 namespace egs {
@@ -60,7 +61,7 @@ struct egs_problem {
   static constexpr uint32_t kSchedFullOnly = EGS_SCHED_SHARE;
   // ... and these out of that one as well, whose callers compare it exactly on scenes that take the form:
   // egs_problem_get_schedule_forms alone reports them
-  static constexpr uint32_t kSchedFormsOnly = EGS_SCHED_FACE;
+  static constexpr uint32_t kSchedFormsOnly = EGS_SCHED_FACE | EGS_SCHED_FACE_SPLIT;
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0
@@ -89,6 +90,15 @@ struct egs_problem {
   int trace_sweeps = 0;
   egs::DevBuf<unsigned char> ggran;   // [n][6] x 16 B: data-tagged granules of the 4-lane body patches (quad_solve.hip)
   uint32_t gran_epoch = 0;
+  // The FACE launch split in time (solve.cpp: face_work; step_solve.hip).  The piece list is a function of
+  // face_key = {tiles, resident slots, split tiles, s1, sweeps} alone: built and uploaded when that changes, never
+  // inside a step otherwise.  face_sync: [0] the ticket counter, which only grows (face_ticket_base is what it stands
+  // at before the next launch), [1 + tile] the launch epoch of the tile's last published first part.
+  std::vector<egs::FacePiece> h_face_pieces;
+  egs::DevBuf<egs::FacePiece> face_pieces;
+  long face_key[5] = {-1, -1, -1, -1, -1};
+  egs::DevBuf<uint32_t> face_sync;
+  uint32_t face_ticket_base = 0, face_epoch = 0;
   // oversize islands as body patches (GS/SOR): LDS for private bodies, global for shared
   egs::DevicePatches patch;
   // topology + state (fp64)

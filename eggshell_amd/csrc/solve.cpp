@@ -2,7 +2,9 @@
 // (SweepSchedule / choose_sweep, applying policy.h), the launch itself, the residual metric, the fixed-count and
 // tolerance-terminated loops of the reference (do_solve) and their per-ensemble form for batched worlds
 // (do_solve_batch).  No extern "C" entry lives here.
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <limits>
 
 #include "policy.h"
@@ -27,6 +29,7 @@ struct SweepSchedule {
   bool share = false;       // ... and a thread one linear block and one pair of weights for both constraints (SHARE)
   bool face = false;        // ... on a thread pair per box face: four updates behind one barrier, 128 threads per tile (FACE)
   int face_tiles = kFaceTilesPerCu;   // ... at this many resident tiles per CU (policy.h; EGS_STEP_FACE_TILES)
+  FaceSplit split;          // ... with the last split.tiles tiles cut after sweep split.s1 (policy.h: face_split_policy)
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -37,7 +40,7 @@ struct SweepSchedule {
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
            (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0) |
            (chain ? EGS_SCHED_CHAIN : 0) | (share ? EGS_SCHED_SHARE : 0) |
-           (face ? EGS_SCHED_FACE : 0);
+           (face ? EGS_SCHED_FACE : 0) | (split.tiles > 0 ? EGS_SCHED_FACE_SPLIT : 0);
   }
 };
 
@@ -110,6 +113,15 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   s.face = s.share && pl.faced && p->face_normals && method == EGS_GAUSS_SEIDEL && s.defer && !p->restitution &&
            !(ae && std::atoi(ae) == 0);
   if (te && (std::atoi(te) == 3 || std::atoi(te) == 4)) s.face_tiles = std::atoi(te);
+  // ... split in time where the last round would leave half the resident slots empty or more (policy.h).
+  // EGS_STEP_FACE_SPLIT=0 keeps one workgroup per tile; EGS_STEP_FACE_SPLIT_FORCE=h,s1 splits the last h tiles after s1
+  // sweeps whatever the policy says (tests, experiments).
+  const char *xe = std::getenv("EGS_STEP_FACE_SPLIT"), *xf = std::getenv("EGS_STEP_FACE_SPLIT_FORCE");
+  if (s.face && !(xe && std::atoi(xe) == 0)) {
+    long h = 0, s1 = 0;
+    if (xf && std::sscanf(xf, "%ld,%ld", &h, &s1) == 2) s.split = face_split_forced(pl.n_tiles, h, s1, sweeps);
+    else if (!xf) s.split = face_split_policy(pl.n_tiles, (long)p->ctx->cu_count * s.face_tiles, pl.max_depth, pl.max_period, sweeps);
+  }
   return s;
 }
 
@@ -152,6 +164,45 @@ GlobalArgs<REAL> global_args(const egs_problem *p, REAL cfm, bool hist) {
   g.dx = real<REAL>(p->gdx);
   g.tickets = p->gtickets.p;
   return g;
+}
+
+// The work of a split FACE launch: the piece list (built and uploaded when its key changes: never inside a step
+// otherwise), the ticket counter and the tiles' flags.  Neither is reset between launches: the counter only grows and
+// the kernel subtracts what it stood at, the flags carry the launch's epoch (on a wrap they are cleared, as the
+// granules' tags are).
+FaceWork face_work(egs_problem *p, int n_tiles, long slots, FaceSplit f, int sweeps) {
+  hipStream_t st = p->ctx->stream;
+  const long key[5] = {n_tiles, slots, f.tiles, f.s1, sweeps};
+  if (!std::equal(key, key + 5, p->face_key)) {
+    face_piece_list(n_tiles, slots, f, sweeps, p->h_face_pieces);
+    p->face_pieces.alloc(p->h_face_pieces.size());
+    HIPCHK(hipMemcpyAsync(p->face_pieces.p, p->h_face_pieces.data(), p->h_face_pieces.size() * sizeof(FacePiece),
+                          hipMemcpyHostToDevice, st));
+    std::copy(key, key + 5, p->face_key);
+  }
+  const size_t words = 1 + (size_t)n_tiles;
+  if (p->face_sync.cap < words) {
+    p->face_sync.alloc(words);
+    HIPCHK(hipMemsetAsync(p->face_sync.p, 0, p->face_sync.cap * sizeof(uint32_t), st));
+    p->face_ticket_base = 0;
+    p->face_epoch = 0;
+  }
+  if (++p->face_epoch == 0) {   // the epoch wrapped: old flags could match again
+    HIPCHK(hipMemsetAsync(p->face_sync.p + 1, 0, (p->face_sync.cap - 1) * sizeof(uint32_t), st));
+    p->face_epoch = 1;
+  }
+  FaceWork w{};
+  w.pieces = p->face_pieces.p;
+  w.counter = p->face_sync.p;
+  w.flags = p->face_sync.p + 1;
+  w.ticket_base = p->face_ticket_base;
+  w.epoch = p->face_epoch;
+  w.n_pieces = (int32_t)p->h_face_pieces.size();
+  w.n_workgroups = (int32_t)std::min<long>(w.n_pieces, slots);
+  // every piece is drawn once, and every workgroup draws one ticket past the list before it ends (modulo 2^32, as the
+  // counter itself)
+  p->face_ticket_base += (uint32_t)w.n_pieces + (uint32_t)w.n_workgroups;
+  return w;
 }
 
 template <typename REAL>
@@ -197,7 +248,10 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.assemble) {
         if constexpr (sizeof(REAL) == 8) {
           a.assemble = *assemble;
-          if (sc.face) launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, ctx->stream);
+          if (sc.face && sc.split.tiles > 0) {
+            const FaceWork w = face_work(p, pl.n_tiles, (long)ctx->cu_count * sc.face_tiles, sc.split, sweeps);
+            launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, &w, ctx->stream);
+          } else if (sc.face) launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, nullptr, ctx->stream);
           else launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, sc.share, ctx->stream);
           // the system this launch assembled: stored, or the problem's to make on demand from the state it read
           p->sys_deferred = sc.defer;

@@ -60,10 +60,13 @@
 // same two bodies, the steady loop hands their accumulators from the first update to the second in registers.  SHARE
 // (CHAIN only): where the two also have one contact normal, the lane keeps their linear block and weights once.  FACE
 // (a kernel of its own, step_solve_face_kernel): where the plan lays the four contact points of a face 32 lanes apart,
-// a thread pair holds all four and runs their updates behind one barrier.
+// a thread pair holds all four and runs their updates behind one barrier.  Where its tiles leave the last round of
+// resident slots half empty or emptier, that launch is split in time (step_solve_face_pieces_kernel: a tile as two
+// pieces, sweeps 1 .. s1 and s1 + 1 .. S, taken by ticket on persistent workgroups; policy.h: face_split_policy).
 #include <algorithm>
 
 #include "kernels.h"
+#include "policy.h"
 #include "solve_device.h"
 #include "assemble_device.h"
 
@@ -738,10 +741,41 @@ __device__ __forceinline__ void face_sides(const Cons<double> &c, int side, Pair
   }
 }
 
-__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+//
+// PIECES: the launch split in time (policy.h: face_split_policy).  A workgroup is not a tile but a PIECE of the list W.pieces:
+// a whole tile, or the first or the second part of a tile cut after sweep s1.  A first part runs the accumulation and
+// sweeps 1 .. s1, stores lambda and the accumulators where the epilogue stores them anyway, and publishes the tile:
+// every thread's stores, an agent-scope release, then one store of the launch's epoch to W.flags[tile].  A second part
+// runs the same prologue (the same J, rhs, inv), then one thread waits for the flag (agent-scope acquire loads, a
+// sleep between them, at most A.spin_limit of them: on overrun the workgroup sets A.error_flag and returns), and it
+// resumes as step_solve_kernel resumes: x from A.x, the accumulators from A.acc, sweep 1 first, no accumulation, on the
+// timetable of a resumed launch of S - s1 sweeps.  Each body's accumulator sees the same updates in the same order:
+// the same bits.  Pieces are taken by ticket (one atomicAdd per piece on a counter that is never reset: the host
+// passes what it stood at), not by blockIdx: a second part stands behind its first part in the list, so whoever holds
+// the first part's ticket is already running and waits for nothing -- whatever order the workgroups are dispatched in.
+// The workgroups are persistent: as many as the GPU holds at once (or as there are pieces), each taking piece after
+// piece until a ticket is past the list.  With one workgroup per piece the hardware refilled the freed slots late and
+// unevenly (a tenth of them stood empty while workgroups were pending) and the launch was no shorter than the unsplit
+// one.
+// Only the prologue, the loop bounds and the epilogue differ from the unsplit kernel: n_sweeps and resume are scalar.
+// Returns false once the list is exhausted: the workgroup is done.
+template <bool PIECES>
+__device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const FaceWork &W, unsigned char *smem, const int tid) {
   constexpr int METHOD = 1;
-  const int tid = (int)threadIdx.x, tile = blockIdx.x;
+  int tile = blockIdx.x, n_sweeps = A.sweeps, resume = 0, kind = kFaceWhole;
+  if constexpr (PIECES) {
+    unsigned *s_word = reinterpret_cast<unsigned *>(smem);
+    if (tid == 0) *s_word = atomicAdd(W.counter, 1u) - W.ticket_base;
+    __syncthreads();
+    const unsigned ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)*s_word);
+    __syncthreads();   // read by everyone before the prologue takes this LDS
+    if (ticket >= (unsigned)W.n_pieces) return false;   // no piece left; nothing is read past the list
+    const FacePiece pc = W.pieces[ticket];
+    tile = __builtin_amdgcn_readfirstlane(pc.tile);
+    resume = __builtin_amdgcn_readfirstlane(pc.resume);
+    n_sweeps = __builtin_amdgcn_readfirstlane(pc.sweeps);
+    kind = __builtin_amdgcn_readfirstlane(pc.kind);
+  }
   const int side = tid & 1;
   const bool even = side == 0, odd = side == 1;
   // member k of this thread pair's group: plan lane lane0 + 32 k
@@ -810,9 +844,43 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
   }
   face_sides<false>(c1, side, L, GC, GD);
   __syncthreads();   // every thread has its blocks back
-  for (int s = tid; s < nslots; s += kFaceThreads) {   // a fresh solve: the accumulators start from zero
+  if (PIECES && resume) {
+    // the second part of a split tile: behind both assemblies, so whatever waiting there is overlaps the prologue
+    unsigned *s_word = reinterpret_cast<unsigned *>(smem);
+    if (tid == 0) {
+      uint32_t spins = 0;
+      unsigned ok = 1;
+      while (__hip_atomic_load(W.flags + tile, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != W.epoch) {
+        if (++spins > A.spin_limit) { ok = 0; break; }
+        __builtin_amdgcn_s_sleep(8);
+      }
+      *s_word = ok;
+    }
+    __syncthreads();
+    const bool ok = __builtin_amdgcn_readfirstlane((int)*s_word) != 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every thread reads what the first part stored
+    __syncthreads();   // the word is read before the accumulators take its place
+    if (!ok) {
+      // the piece is given up and the launch reports a stall; the workgroup goes on drawing, so that the counter ends
+      // where the host expects it whatever happened
+      if (tid == 0) atomicOr(A.error_flag, 1);
+      return true;
+    }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = 0.0;
+    for (int r = 0; r < 3; ++r) {
+      if (own0 >= 0) x0[r] = A.x[(size_t)own0 * 3 + r];
+      if (own1 >= 0) x1[r] = A.x[(size_t)own1 * 3 + r];
+    }
+    for (int s = tid; s < nslots; s += kFaceThreads) {
+      const int body = slot_body[s];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = body >= 0 ? A.acc[(size_t)body * 6 + k] : 0.0;
+    }
+  } else {
+    for (int s = tid; s < nslots; s += kFaceThreads) {   // a fresh solve: the accumulators start from zero
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_acc[s * 6 + k] = 0.0;
+    }
   }
   // the held products, formed behind both assemblies: fewer registers live through the second one
   L.form();
@@ -821,7 +889,7 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
   GC.form(L.wa);
   GD.form(L.wa);
   PairShared<kFaceLin, kFaceAng> SA{L, GA}, SB{L, GB}, SC{L, GC}, SD{L, GD};
-  const int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, A.sweeps, 0));
+  const int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, n_sweeps, resume));
   __syncthreads();
 
   // The timetable of step_solve_kernel per GROUP: member k's level is A's + k and the period a multiple of 4, so the
@@ -829,13 +897,14 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
   // block comes a period later.  Both loops walk a block per iteration behind ONE barrier: what holds for the steady
   // window holds for the fill and the drain (Plan::faced is about every block), and a block past the timetable's end
   // finds no group due.
-  int sweep = 0, due = (nm > 0 && A.sweeps >= 0) ? levelA : 0x7fffffff;
+  // (a resumed piece starts at sweep 1: its grid has no accumulation, one update less)
+  int sweep = resume, due = (nm > 0 && n_sweeps >= resume) ? levelA : 0x7fffffff;
   int t_s = 0, t_e = 0;
   const int Ps = __builtin_amdgcn_readfirstlane(P);
   if (A.steady && Ps > 0) {
     // whole blocks from a step = 0 (mod 4): a step's residue is its phase's
     t_s = (__builtin_amdgcn_readfirstlane(depth) + 3) & ~3;
-    t_e = min(Ps * (A.sweeps + 1), t_end);
+    t_e = min(Ps * (n_sweeps + 1 - resume), t_end);
     t_e -= (t_e - t_s) & 3;
     if (t_e <= t_s) t_s = t_e = 0;
   }
@@ -850,7 +919,7 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
         if (nm > 3) pair_pass<METHOD, kQuadOdd, true, false, false>(SD, ac, a, has, odd, c1, x1, sweep, A.cfm);
         if (has) store6(ac, a);   // after the group's last active member
         due += P;
-        if (++sweep > A.sweeps) due = 0x7fffffff;
+        if (++sweep > n_sweeps) due = 0x7fffffff;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -877,8 +946,8 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
     // drain: the group's next block at or after t_e, from its level (read again: not held through the window)
     const int lv = A.lane_level[lane0];
     const int n = t_e > lv ? (t_e - lv + Ps - 1) / Ps : 0;
-    sweep = n;   // update n on a grid whose update 0 is the accumulation
-    due = (nm == 0 || n > A.sweeps) ? 0x7fffffff : lv + P * n;
+    sweep = n + resume;   // update n on a grid whose update 0 is the accumulation, or (resumed) sweep 1
+    due = (nm == 0 || sweep > n_sweeps) ? 0x7fffffff : lv + P * n;
     stop = t_end;
   }
 
@@ -893,6 +962,31 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const 
     if (body < 0) continue;   // unused slot number
 #pragma unroll
     for (int k = 0; k < 6; ++k) A.acc[(size_t)body * 6 + k] = s_acc[s * 6 + k];
+  }
+  if (PIECES && kind == kFaceFirst) {
+    // publish: this thread's stores of lambda and the accumulators, released to the agent, before the tile's flag
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(W.flags + tile, W.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return true;
+}
+
+__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  face_step<false>(A, FaceWork{}, smem, (int)threadIdx.x);
+}
+// ... persistent workgroups, as many as the GPU holds at once: each takes piece after piece until the list is exhausted
+__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_pieces_kernel(const SolveArgs<double> A, const FaceWork W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int tid = (int)threadIdx.x;
+  for (;;) {
+    // A piece is compiled as the unsplit kernel's body is: the thread number and the launch's scalars are opaque per
+    // piece, so nothing formed from them is carried in registers from one piece to the next (scratch stays 0).
+    SolveArgs<double> B = A;
+    asm volatile("" : "+v"(tid), "+s"(B.assemble.dt), "+s"(B.assemble.erp), "+s"(B.cfm));
+    if (!face_step<true>(B, W, smem, tid)) break;
+    __syncthreads();   // the epilogue has read the accumulators before the next ticket lands there
   }
 }
 
@@ -1193,7 +1287,7 @@ void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_ti
   }
 }
 
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, hipStream_t s) {
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork *w, hipStream_t s) {
   if (n_tiles <= 0) return;
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
@@ -1202,6 +1296,12 @@ void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_p
   // the registers allow four tiles per CU; a request above a quarter of the CU's 160 KiB of LDS leaves room for three
   constexpr size_t kQuarterLds = 160 * 1024 / 4;
   if (tiles_per_cu == 3) lds = std::max(lds, kQuarterLds + 1024);
+  if (w) {   // split in time: persistent workgroups that take the pieces by ticket
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(step_solve_face_pieces_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(step_solve_face_pieces_kernel, dim3(w->n_workgroups), dim3(kFaceThreads), lds, s, b, *w);
+    return;
+  }
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(step_solve_face_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(step_solve_face_kernel, dim3(n_tiles), dim3(kFaceThreads), lds, s, b);

@@ -124,13 +124,20 @@ typedef enum {
                                       (callers compare egs_problem_get_schedule with EGS_SCHED_CHAIN masked against
                                       egs_solve_stats.schedule).  A world, whose collider writes the contacts on the
                                       device, does not take the form */
-  EGS_SCHED_FACE = 32768           /* ... in which a thread pair holds the FOUR contact points of a box face and runs
+  EGS_SCHED_FACE = 32768,          /* ... in which a thread pair holds the FOUR contact points of a box face and runs
                                       their four updates behind one barrier, the two bodies' accumulators in registers
                                       from the first to the last (plans that are faced: egs_debug_plan_faced; one
                                       normal per face: egs_debug_plan_face_normals; GS, the store-free launch, no
                                       restitution).  128 threads per 256-constraint tile.  The same bits;
                                       EGS_STEP_FACE=0 switches it off, EGS_STEP_FACE_TILES=3|4 sets the tiles per CU.
                                       A refinement of EGS_SCHED_SHARE: only egs_problem_get_schedule_forms reports it */
+  EGS_SCHED_FACE_SPLIT = 65536     /* ... whose launch is split in time: where the tiles fill the resident slots once
+                                      or more and leave a remainder of at most half of them, that many tiles run as
+                                      two workgroups, sweeps 1 .. s1 and s1 + 1 .. S, so that the last round keeps
+                                      every slot busy (egs_debug_face_split).  The same bits; EGS_STEP_FACE_SPLIT=0
+                                      switches it off, EGS_STEP_FACE_SPLIT_FORCE=h,s1 splits the last h tiles after
+                                      s1 sweeps whatever the policy says.  Only egs_problem_get_schedule_forms
+                                      reports it */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -1084,6 +1091,16 @@ egs_status egs_debug_plan_faced(int32_t n_bodies, int32_t m, const int32_t *body
  * patterns (data as in egs_debug_plan_share).  A group with one member asks nothing.                               */
 egs_status egs_debug_plan_face_normals(int32_t n_bodies, int32_t m, const int32_t *body0, const int32_t *body1,
                                        const double *data, int32_t *face);
+
+/* Host only: the split of the FACE launch in time (EGS_SCHED_FACE_SPLIT) for n_tiles tiles on `slots` resident slots
+ * (CUs x tiles per CU) whose timetable has the given depth and period, at `sweeps` sweeps -- the policy the library
+ * itself applies.  force_tiles < 0: the policy decides; otherwise the last force_tiles tiles (clamped to n_tiles) are
+ * split after force_s1 sweeps (outside 1 .. sweeps - 1: no split).  *split_tiles and *s1: the answer, 0 and 0 for no
+ * split.  pieces (NULL, or room for 4 x (n_tiles + n_tiles) values): the launch's work list in ticket order, per
+ * piece {tile, resume, sweeps of the piece, kind: 0 whole, 1 first part, 2 second part}; *n_pieces its length.     */
+egs_status egs_debug_face_split(int32_t n_tiles, int32_t slots, int32_t depth, int32_t period, int32_t sweeps,
+                                int32_t force_tiles, int32_t force_s1, int32_t *split_tiles, int32_t *s1,
+                                int32_t *pieces, int32_t *n_pieces);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
