@@ -151,7 +151,7 @@ __device__ __forceinline__ void hinge_block(const AssembleArgs &A, int b0, int b
 // from Rn, the point and the body's position.  contact_err: e = err.  contact_blocks: the three together, j0 / j1 zero
 // for a side without a body (pos0 / pos1 not read there).  assemble_one_t's contact branch calls the parts where it had
 // their code, each side's behind that side's load of pos; the staged prologue of step_solve_face_kernel
-// (step_solve.hip), which has the values in registers, calls contact_blocks: the same operations in the same order,
+// (step_face.hip), which has the values in registers, calls contact_blocks: the same operations in the same order,
 // the same bits.
 __device__ __forceinline__ void contact_frame(const double *d, double *Rn) { align_to_z(d + 3, Rn); }
 template <int SIDE>

@@ -58,7 +58,7 @@ struct SolveArgs {
   REAL cfm, kscale;
   int32_t sweeps, resume, max_slots;
   uint32_t spin_limit;
-  // static timetable of the same sweep (step_solve.hip, plan.h): per lane its level, per tile the
+  // static timetable of the same sweep (step_device.h, plan.h): per lane its level, per tile the
   // period P and the depth of the level DAG
   const uint16_t *lane_level = nullptr;
   const int32_t *tile_period = nullptr, *tile_depth = nullptr;
@@ -69,7 +69,7 @@ struct SolveArgs {
   int linsym = 0;           // 1 (with iso, fp64, GROUP = 1): J1_lin = -J0_lin and wl0 = wl1 bit for bit on every
                             // two-body constraint: step_solve_kernel keeps one linear block (step_solve.hip: LINSYM)
   int steady = 0;           // 1: step_solve_kernel (GROUP = 1, no snapshots) runs the steady-state loop between the
-                            // fill and the drain of its timetable (step_solve.hip)
+                            // fill and the drain of its timetable (step_device.h)
   // step_solve_kernel's ASSEMBLE form (launch_step_solve_assemble): every lane assembles its constraint from this
   // body state in the prologue and also leaves the blocks where assemble_kernel would (J0 .. is_eq above point there).
   // An fp64 launch only: the fp32 argument block keeps the core alone and with it its size (16 bytes more cost the
@@ -144,14 +144,17 @@ void launch_step_solve(const SolveArgs<REAL> &a, int method, int n_tiles, int bl
 // a.assemble.rest set: the restitution instantiations, the same sweep behind a prologue that bounces the normal rows):
 // assemble_kernel and this launch in one, with the blocks, lambda, w and the accumulators of both, bit for bit.
 // store_system = false: J0, J1, rhs, lo, hi, err and is_eq are not written (the caller defers them: problem.h)
-// pair: the PAIR form, one update on a lane pair (step_solve.hip); the same bits on any plan, worth it on a pairable one
-// chain (with pair, on a plan that is Plan::chained, a.steady on): the CHAIN form of its steady loop, the pair's
-// accumulators in registers between its two updates; the same bits
+void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, hipStream_t s);
+// the PAIR form of that launch, one update on a lane pair (step_pair.hip): the same arguments, the same bits on any plan,
+// worth it on a pairable one
+// chain (on a plan that is Plan::chained, a.steady on): the CHAIN form of its steady loop, the pair's accumulators in
+// registers between its two updates; the same bits
 // share (with chain, where the two contacts of every thread pair carry one normal: problem.h, share_normals): the SHARE
-// form, one linear block and one pair of weights per lane for both constraints; the same bits
-void launch_step_solve_assemble(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool pair, bool chain,
-                                bool share, hipStream_t s);
-// the FACE form of the share launch (step_solve.hip): GS, store-free, no restitution, on a plan that is Plan::faced whose
+// form, one linear block and one pair of weights per lane for both constraints; the same bits.  share without chain
+// is no form: std::logic_error
+void launch_step_solve_pair(const SolveArgs<double> &a, int method, int n_tiles, bool store_system, bool chain, bool share,
+                            hipStream_t s);
+// the FACE form of the share launch (step_face.hip): GS, store-free, no restitution, on a plan that is Plan::faced whose
 // groups of four carry one normal (problem.h: face_normals), a.steady on; 128 threads per tile; the same bits.
 // tiles_per_cu: 3 or 4 resident tiles per CU (4: what the registers allow; 3: the launch asks for more LDS)
 // w (NULL: one workgroup per tile, blockIdx = tile): the launch split in time.  w->n_workgroups persistent workgroups

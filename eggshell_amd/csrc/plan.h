@@ -38,7 +38,7 @@ struct Plan {
   int n_islands = 0, n_tiles = 0, max_slots = 1;
   int max_cnt = 1;                    // largest per-body constraint count (ticket period)
   std::vector<LaneDesc> lanes;        // n_tiles * block
-  // Static time-stepped schedule of the same sweep (step_solve.hip).  level = depth of the constraint in
+  // Static time-stepped schedule of the same sweep (step_device.h).  level = depth of the constraint in
   // the list-order dependency DAG of one sweep (a constraint comes after the previous constraint of each
   // of its bodies).  With P >= every body's level span (last level - first level + 1) the update of
   // sweep s may run at time level + P * (s - 1): per body the times increase in list order and the next
@@ -59,14 +59,14 @@ struct Plan {
   bool runs = false;
   // Every half-wavefront of plan lanes (lanes 32 h .. 32 h + 31 of a 256-lane tile) is idle or holds constraints of
   // ONE phase (level mod the tile's period): a time step's due lanes fill half-wavefronts, as in a pile of columns
-  // under the phase-major lane order.  That is where step_solve_kernel's PAIR form pays (step_solve.hip): it runs the
+  // under the phase-major lane order.  That is where step_solve_kernel's PAIR form pays (step_pair.hip): it runs the
   // update of lane 64 w + j on the thread pair (2 j, 2 j + 1) of wavefront w, and then that of lane 64 w + 32 + j.
   bool pairable = false;
   // A pairable plan in which the two constraints of every thread pair of that form, A = plan lane 64 w + l and
   // B = plan lane 64 w + 32 + l (l < 32), are consecutive updates of the SAME two bodies: every tile's period is even, B
   // is not active without A, level[A] is even, and where both are active slot0 and slot1 agree and level[B] =
   // level[A] + 1 -- two neighbouring contact points of a box face, as the phase-major lane order of a pile lays them out.
-  // Then the pair's accumulators can stay in registers from the first of the two updates to the second (step_solve.hip:
+  // Then the pair's accumulators can stay in registers from the first of the two updates to the second (step_pair.hip:
   // the CHAIN form; plan.cpp derives the parity of the first's time step where it sets the flag).
   bool chained = false;
   // A chained plan in which the FOUR constraints of every thread pair of the FACE form, plan lanes 128 W + 32 k + l
@@ -76,7 +76,7 @@ struct Plan {
   // + k, and per tile, per block of four time steps ((level / 4) mod (P / 4)) and per LDS slot other than the world's,
   // all constraints that use the slot belong to ONE group.  Then a group's accumulators can stay in registers through
   // the four updates of a block, and nothing else in the tile reads or writes them inside the block: the three
-  // barriers inside it order nothing (step_solve.hip: the FACE form).
+  // barriers inside it order nothing (step_face.hip).
   bool faced = false;
   std::vector<int32_t> tile_nslots;   // per tile, slots in use (slot 0 = world)
   std::vector<int32_t> tile_slot_off; // per tile, offset into slot_body
@@ -113,7 +113,7 @@ constexpr int kAutoQuadBlock = 0;
 Plan build_plan(int n_bodies, int m, const int32_t *body0, const int32_t *body1,
                 int block, Plan *recycle = nullptr, int max_run_tiles = 0);
 
-// What the SHARE form of the fused step launch (step_solve.hip) asks beyond a chained plan: the two constraints of every
+// What the SHARE form of the fused step launch (step_pair.hip) asks beyond a chained plan: the two constraints of every
 // thread pair, A = plan lane 64 w + l and B = plan lane 64 w + 32 + l, carry one contact normal -- data[7 i + 3 .. 5]
 // (the constraint descriptors, [m][7]) of A and of B are the same three bit patterns (-0.0 is not +0.0) wherever both
 // are active.  A pair with an A and no B asks nothing.  false on a plan that is not chained.

@@ -17,7 +17,7 @@ namespace egs {
 // tiles per CU.
 inline int quad_tiles_per_cu_max(int precision) { return precision == EGS_F32 ? 8 : 5; }
 constexpr int kBigTileMinConstraints = 196608;   // 768 tiles of 256: from here 512-constraint tiles
-// The tile plan's GS / SOR sweep on its static timetable (step_solve.hip) or on tickets
+// The tile plan's GS / SOR sweep on its static timetable (step_device.h) or on tickets
 // (tile_solve_kernel)?  The timetable takes depth + P x sweeps barrier steps, P = the largest level
 // span of a body in a tile; the ticket sweep follows the true dependency chains, about
 // depth + (largest per-body count) x sweeps updates long.  Regular islands (piles of columns) have
@@ -46,14 +46,14 @@ inline OversizeSchedule choose_oversize_schedule(int n_patch_tiles, int quad_per
   return kAllGlobal;
 }
 
-// The FACE form of the fused step launch (step_solve.hip) runs a 256-constraint tile on 128 threads at up to 256 VGPRs:
+// The FACE form of the fused step launch (step_face.hip) runs a 256-constraint tile on 128 threads at up to 256 VGPRs:
 // four tiles fit a CU.  Resident tiles per CU it asks for, 3 or 4 (3: by a larger LDS request); measured on MI355X,
 // 24 C3 piles (1 536 tiles on 256 CUs: 1 024 + 512 at four, 768 + 768 at three): DESIGN.md section 5.  Measured again
 // with the launch split in time (below): at four the 512 are split and the step runs at 52 230 pile-steps/s, at three
 // there is no remainder to split and it stays at 48 025.  Four.
 constexpr int kFaceTilesPerCu = 4;
 
-// The FACE launch split in time (step_solve.hip: pieces).  With n_tiles = k x slots + R, 0 < R <= slots / 2, the last
+// The FACE launch split in time (step_face.hip: pieces).  With n_tiles = k x slots + R, 0 < R <= slots / 2, the last
 // round keeps half the resident slots empty or more.  R tiles are then cut after sweep s1: a slot runs
 //     a first part (accumulation + sweeps 1 .. s1), then a whole tile        depth + P s1  +  depth + P S   steps
 //     a whole tile, then a second part (sweeps s1 + 1 .. S, resumed)         depth + P S   +  depth + P (S - s1 - 1)

@@ -90,7 +90,7 @@ struct egs_problem {
   int trace_sweeps = 0;
   egs::DevBuf<unsigned char> ggran;   // [n][6] x 16 B: data-tagged granules of the 4-lane body patches (quad_solve.hip)
   uint32_t gran_epoch = 0;
-  // The FACE launch split in time (solve.cpp: face_work; step_solve.hip).  The piece list is a function of
+  // The FACE launch split in time (solve.cpp: face_work; step_face.hip).  The piece list is a function of
   // face_key = {tiles, resident slots, split tiles, s1, sweeps} alone: built and uploaded when that changes, never
   // inside a step otherwise.  face_sync: [0] the ticket counter, which only grows (face_ticket_base is what it stands
   // at before the next launch), [1 + tile] the launch epoch of the tile's last published first part.

@@ -550,7 +550,7 @@ __device__ __forceinline__ void load3(unsigned acc_addr, float (&a)[3]) {
       : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]) : "v"(acc_addr) : "memory");
 }
 
-// The 4-lanes-per-constraint sweep on the STATIC TIMETABLE of step_solve.hip (plan.h: level, period,
+// The 4-lanes-per-constraint sweep on the STATIC TIMETABLE of step_device.h (plan.h: level, period,
 // depth): constraint c runs its update of sweep s at time step level(c) + P * s, one workgroup barrier
 // per step, no tickets and no polling.  Same lane layout, same arithmetic and same bits as
 // quad_solve_kernel; what goes away is the ticket round trip through LDS on the critical path of a
@@ -621,7 +621,7 @@ __global__ void __launch_bounds__(4 * QT) step_quad_kernel(const SolveArgs<REAL>
       if (pyr) lo[0] = mu;
     }
   }
-  // length of the tile's timetable (step_solve.hip: timetable_end)
+  // length of the tile's timetable (step_device.h: timetable_end)
   int t_end;
   if (METHOD == 2) t_end = (A.resume ? 0 : depth) + (A.sweeps >= 1 ? depth + P * (A.sweeps - 1) : 0);
   else { const int n_phases = A.sweeps + (A.resume ? 0 : 1); t_end = n_phases >= 1 ? depth + P * (n_phases - 1) : 0; }

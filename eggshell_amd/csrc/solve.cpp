@@ -18,13 +18,13 @@ namespace {
 // them between calls in one process), and nowhere else; launch_solve_t dispatches on the answer.
 struct SweepSchedule {
   bool quad = false;        // 4 lanes per constraint (planq) instead of 1 (plan)
-  bool timetable = false;   // the plan's static timetable (step_solve.hip, quad_solve.hip) instead of tickets
+  bool timetable = false;   // the plan's static timetable (step_device.h, quad_solve.hip) instead of tickets
   int iso = 0;              // SolveArgs::iso: the isotropic-body variant of the 1-lane tile kernels
   int group = 1;            // tiles per workgroup of step_solve_kernel
   bool linsym = false;      // step_solve_kernel's LINSYM form
   bool assemble = false;    // ... with the assembly in its prologue (egs_problem_step)
   bool defer = false;       // ... which stores no system: the problem defers it (problem.h: ensure_system)
-  bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_solve.hip)
+  bool pair = false;        // ... in its PAIR form: one update on a lane pair (step_pair.hip)
   bool chain = false;       // ... whose steady loop keeps a pair's accumulators in registers between its two updates (CHAIN)
   bool share = false;       // ... and a thread one linear block and one pair of weights for both constraints (SHARE)
   bool face = false;        // ... on a thread pair per box face: four updates behind one barrier, 128 threads per tile (FACE)
@@ -205,6 +205,33 @@ FaceWork face_work(egs_problem *p, int n_tiles, long slots, FaceSplit f, int swe
   return w;
 }
 
+// The timetable sweep of the one-lane plan: exactly one of the four launchers of the step units (kernels.h), as the
+// schedule says.  An assembling launch (sc.assemble: fp64, `assemble` given) also leaves the problem's record of the
+// system it assembled.
+template <typename REAL>
+void launch_timetable(egs_problem *p, const SweepSchedule &sc, SolveArgs<REAL> &a, int method, int sweeps,
+                      const AssembleArgs *assemble) {
+  const int n_tiles = p->plan.n_tiles;
+  hipStream_t st = p->ctx->stream;
+  if (!sc.assemble) {
+    launch_step_solve<REAL>(a, method, n_tiles, p->plan.block, sc.group, sc.linsym, st);
+    return;
+  }
+  if constexpr (sizeof(REAL) == 8) {
+    a.assemble = *assemble;
+    if (sc.face && sc.split.tiles > 0) {
+      const FaceWork w = face_work(p, n_tiles, (long)p->ctx->cu_count * sc.face_tiles, sc.split, sweeps);
+      launch_step_solve_face(a, n_tiles, sc.face_tiles, &w, st);
+    } else if (sc.face) launch_step_solve_face(a, n_tiles, sc.face_tiles, nullptr, st);
+    else if (sc.pair) launch_step_solve_pair(a, method, n_tiles, !sc.defer, sc.chain, sc.share, st);
+    else launch_step_solve_assemble(a, method, n_tiles, !sc.defer, st);
+    // the system this launch assembled: stored, or the problem's to make on demand from the state it read
+    p->sys_deferred = sc.defer;
+    p->deferred_prev = false;
+    p->deferred_dt = assemble->dt; p->deferred_erp = assemble->erp;
+  }
+}
+
 template <typename REAL>
 void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweeps, int resume, const AssembleArgs *assemble) {
   egs_context *ctx = p->ctx;
@@ -245,22 +272,7 @@ void launch_solve_t(egs_problem *p, int method, REAL cfm, REAL kscale, int sweep
       if (sc.timetable) launch_step_quad<REAL>(a, method, pl.n_tiles, pl.block, ctx->stream);
       else launch_quad_solve<REAL>(a, method, pl.n_tiles, pl.block, ctx->stream);
     } else if (sc.timetable) {
-      if (sc.assemble) {
-        if constexpr (sizeof(REAL) == 8) {
-          a.assemble = *assemble;
-          if (sc.face && sc.split.tiles > 0) {
-            const FaceWork w = face_work(p, pl.n_tiles, (long)ctx->cu_count * sc.face_tiles, sc.split, sweeps);
-            launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, &w, ctx->stream);
-          } else if (sc.face) launch_step_solve_face(a, pl.n_tiles, sc.face_tiles, nullptr, ctx->stream);
-          else launch_step_solve_assemble(a, method, pl.n_tiles, !sc.defer, sc.pair, sc.chain, sc.share, ctx->stream);
-          // the system this launch assembled: stored, or the problem's to make on demand from the state it read
-          p->sys_deferred = sc.defer;
-          p->deferred_prev = false;
-          p->deferred_dt = assemble->dt; p->deferred_erp = assemble->erp;
-        }
-      } else {
-        launch_step_solve<REAL>(a, method, pl.n_tiles, pl.block, sc.group, sc.linsym, ctx->stream);
-      }
+      launch_timetable(p, sc, a, method, sweeps, assemble);
     } else {
       launch_tile_solve<REAL>(a, method, pl.n_tiles, pl.block, ctx->stream);
     }
@@ -524,7 +536,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     // tickets are 32-bit counters that advance by cnt per sweep: very long runs
     // are cut into resumed launches so they cannot wrap
     // ... and the static timetable counts time steps in a 32-bit int (t_end = depth + period x sweeps,
-    // step_solve.hip / quad_solve.hip): the chunk also keeps that below INT_MAX.  64-bit arithmetic, then the clamp.
+    // step_device.h / quad_solve.hip): the chunk also keeps that below INT_MAX.  64-bit arithmetic, then the clamp.
     const int chunk_max = fixed_chunk_max(p->use_quad ? p->planq : p->plan);
     int done = 0;
     do {

@@ -359,7 +359,7 @@ __device__ __forceinline__ void load12(unsigned ac0, unsigned ac1, float (&a0)[6
   a0[0] = u0.x; a0[1] = u0.y; a0[2] = u1.x; a0[3] = u1.y; a0[4] = u2.x; a0[5] = u2.y;
   a1[0] = v0.x; a1[1] = v0.y; a1[2] = v1.x; a1[3] = v1.y; a1[4] = v2.x; a1[5] = v2.y;
 }
-// one body's accumulator (step_solve.hip: the PAIR form, a lane holds one side of a constraint)
+// one body's accumulator (step_pair_device.h: the PAIR form, a lane holds one side of a constraint)
 __device__ __forceinline__ void load6(unsigned ac, double (&a)[6]) {
   d2_t u0, u1, u2;
   asm volatile(

@@ -1041,7 +1041,7 @@ egs_status egs_debug_plan_slots(int32_t n_bodies, int32_t m, const int32_t *body
                                 int32_t *lane, int32_t *slot0, int32_t *slot1,
                                 int32_t *tile_nslots);
 
-/* The static timetable of the same schedule (step_solve.hip): constraint c
+/* The static timetable of the same schedule (step_device.h): constraint c
  * runs its update of sweep s at time step level[c] + period * s of its tile, level = depth in the
  * list-order dependency DAG of one sweep (sparse_iterations_utils.cc:159-243: a constraint reads
  * what the previous constraint of each of its bodies wrote), period = the largest level span of a

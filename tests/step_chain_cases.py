@@ -38,7 +38,7 @@ def scene(name):
 
 
 def steady_window(method, depth, period, sweeps):
-    """[t_s, t_e) of a fresh launch's steady window as step_solve.hip sets it before the CHAIN form trims it, and the
+    """[t_s, t_e) of a fresh launch's steady window as step_pair.hip sets it before the CHAIN form trims it, and the
     timetable's end; method "gs" or "sor"."""
     if method == "sor":
         t_end = depth + (depth + period * (sweeps - 1) if sweeps >= 1 else 0)

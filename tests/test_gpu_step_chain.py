@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the CHAIN form of step_solve_kernel's lane-pair launch (EGS_STEP_CHAIN; step_solve.hip).  In the
+"""GPU (-m gpu): the CHAIN form of the lane-pair launch (EGS_STEP_CHAIN; step_pair.hip).  In the
 steady part of the timetable a thread pair keeps its two bodies' accumulators in registers from the first of its two
 updates to the second: the same doubles travel by register instead of through LDS, so lambda, w, the accumulators and
 the velocities of a step must keep every bit of

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the FACE form of the fused step launch (EGS_STEP_FACE; step_solve.hip).  Where the plan lays the four
+"""GPU (-m gpu): the FACE form of the fused step launch (EGS_STEP_FACE; step_face.hip).  Where the plan lays the four
 contact points of every box face 32 lanes apart (Plan::faced) and the four carry one normal, a tile runs on 128 threads,
 a thread pair holds the four constraints, and the steady loop runs their four updates on one set of accumulator
 registers behind one barrier.  The same doubles, the same multiplies, the same order: lambda, w, the accumulators and

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the staged prologue of the FACE form (step_solve.hip: step_solve_face_kernel).  The kernel loads the
+"""GPU (-m gpu): the staged prologue of the FACE form (step_face.hip: step_solve_face_kernel).  The kernel loads the
 four members' descriptors, then data[7] of both owned constraints with the group's two body numbers, then the two
 bodies' state ONCE per lane, and assembles both constraints from those values (assemble_device.h: contact_blocks,
 side_u) where it used to run the one-lane assembly twice behind its own loads.  Nothing it computes may move by a bit.

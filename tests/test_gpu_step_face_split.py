@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the FACE launch split in time (EGS_STEP_FACE_SPLIT; step_solve.hip, policy.h).  A split tile runs as
+"""GPU (-m gpu): the FACE launch split in time (EGS_STEP_FACE_SPLIT; step_face.hip, policy.h).  A split tile runs as
 two workgroups: the first part walks the accumulation and sweeps 1 .. s1, stores lambda and the accumulators and
 publishes the tile; the second part waits for it and resumes with sweeps s1 + 1 .. S.  Every body's accumulator sees the
 same updates in the same order, so lambda, w, the accumulators, the velocities and the blocks of a step must keep every

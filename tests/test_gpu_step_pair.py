@@ -1,4 +1,4 @@
-"""GPU (-m gpu): step_solve_kernel's PAIR form (one update on a lane pair, EGS_STEP_PAIR; step_solve.hip).  It changes
+"""GPU (-m gpu): the PAIR form of the fused step launch (one update on a lane pair, EGS_STEP_PAIR; step_pair.hip).  It changes
 which thread forms which product and no rounding, so lambda, w, the accumulators and the velocities of a step must keep
 every bit of
 

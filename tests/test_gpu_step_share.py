@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the SHARE form of step_solve_kernel's CHAIN launch (EGS_STEP_SHARE; step_solve.hip).  Where the two
+"""GPU (-m gpu): the SHARE form of the CHAIN launch (EGS_STEP_SHARE; step_pair.hip).  Where the two
 contacts of every thread pair carry one normal, a thread keeps the linear Jacobian block, the weights and the linear
 products of its side once for both constraints: the same doubles in fewer registers, the same multiplies, so lambda, w,
 the accumulators and the velocities of a step must keep every bit of

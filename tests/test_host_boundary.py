@@ -220,7 +220,7 @@ def _chunk_places(body0, body1):
 
 
 def _timetable_is_list_order(body0, body1, tt, sweeps=3):
-    """Replay the timetable of step_solve.hip on the host: at time step level + period * s the
+    """Replay the timetable of step_device.h on the host: at time step level + period * s the
     constraint runs sweep s.  Per body, the (sweep, list index) pairs must come in exactly the
     order of the sequential list-order sweeps, with no two of them in one time step."""
     m = body0.shape[0]

@@ -1,5 +1,5 @@
 """CPU: Plan::faced (plan.h) and plan_faces_normals, what the fused step launch asks before a thread pair runs the four
-contact points of a box face behind one barrier (step_solve.hip: the FACE form).  The flag against its definition,
+contact points of a box face behind one barrier (step_face.hip).  The flag against its definition,
 recomputed here from the planner's own tables (tile, lane, slots, level, period), on the chained scenes of
 test_gpu_step_chain.py, on one C3 pile, on a pile with two contact points per face (chained, not faced) and on the lists
 that are not chained; the normals' answer beside SHARE's; and which steady windows the cases of test_gpu_step_face.py

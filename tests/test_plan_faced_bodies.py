@@ -1,4 +1,4 @@
-"""CPU: what the staged prologue of the FACE form (step_solve.hip: step_solve_face_kernel) relies on.  It takes the two
+"""CPU: what the staged prologue of the FACE form (step_face.hip: step_solve_face_kernel) relies on.  It takes the two
 body numbers of a thread pair's group ONCE, from member A's slots, and loads those bodies' state once for both
 constraints the lane owns.  That is right only if every member of every group has A's body0 and A's body1, side for
 side -- which Plan::faced promises through the slots.  Here it is read off the planner's debug tables alone (tile and

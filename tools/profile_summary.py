@@ -19,7 +19,7 @@ import re
 import shutil
 import sys
 
-MAIN = ("step_solve_kernel", "step_quad_kernel", "tile_solve_kernel", "quad_solve_kernel", "patch_solve_kernel", "global_solve_kernel",
+MAIN = ("step_solve_", "step_quad_kernel", "tile_solve_kernel", "quad_solve_kernel", "patch_solve_kernel", "global_solve_kernel",
         "matvec_tile_kernel", "pair_solve_kernel", "duo_solve_kernel", "chol_", "box_dantzig_kernel", "box_murty_kernel")
 
 
