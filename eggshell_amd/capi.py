@@ -17,6 +17,7 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_STALL, ERR_UNSUPPORTED, ERR_LCP_FAI
 JACOBI, GAUSS_SEIDEL, SOR = 0, 1, 2
 F64, F32 = 0, 1
 JOINT_BALL, CONTACT_BOX, JOINT_LOCK, JOINT_HINGE_AXIS = 0, 1, 2, 3
+JOINT_SLIDER_AXIS = 5   # 4 is no kind (it stays invalid)
 SHAPE_BOX, SHAPE_SPHERE = 0, 1
 MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
@@ -62,6 +63,7 @@ EXPORTS = [
     "egs_problem_set_restitution", "egs_world_set_restitution",
     "egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks",
     "egs_problem_set_hinge_limits", "egs_world_set_joint_limits",
+    "egs_problem_set_slider_limits", "egs_world_set_slider_limits",
 ]
 
 
@@ -118,6 +120,10 @@ def load():
                 getattr(_lib, name).restype = C.c_int
         if hasattr(_lib, "egs_problem_set_hinge_limits"):
             for name in ("egs_problem_set_hinge_limits", "egs_world_set_joint_limits"):
+                getattr(_lib, name).argtypes = [C.c_void_p, C.c_void_p]   # problem / world, lim
+                getattr(_lib, name).restype = C.c_int
+        if hasattr(_lib, "egs_problem_set_slider_limits"):
+            for name in ("egs_problem_set_slider_limits", "egs_world_set_slider_limits"):
                 getattr(_lib, name).argtypes = [C.c_void_p, C.c_void_p]   # problem / world, lim
                 getattr(_lib, name).restype = C.c_int
         if hasattr(_lib, "egs_problem_set_live_inertia"):
@@ -748,6 +754,14 @@ class Problem:
             raise ValueError("lim: %d values for %d constraints" % (lim.size, self.m))
         self.ctx.check(load().egs_problem_set_hinge_limits(self.h, _p(lim)))
 
+    def set_slider_limits(self, lim=None):
+        """Slider travel stops (egs_problem_set_slider_limits): [m][2] = (xlo, xhi) per constraint, -inf / +inf: no stop
+        on that side.  A SLIDER_AXIS constraint past a stop gets the one-sided rail row of that stop.  None turns it off."""
+        lim = _f64(lim)
+        if lim is not None and lim.size != 2 * self.m:
+            raise ValueError("lim: %d values for %d constraints" % (lim.size, self.m))
+        self.ctx.check(load().egs_problem_set_slider_limits(self.h, _p(lim)))
+
     def wres(self):
         """w = A lambda - rhs of the last solve (the solve kernels' epilogue)."""
         w = np.zeros(3 * self.m)
@@ -1035,7 +1049,7 @@ class World:
         self.ctx.check(load().egs_world_set_joints(self.h, C.c_int32(body0.shape[0]), _p(body0), _p(body1), _p(data)))
 
     def set_joints_kinds(self, kind, body0, body1, data):
-        """Joints of any kind (egs_world_set_joints_kinds): JOINT_BALL, JOINT_LOCK, JOINT_HINGE_AXIS; kind None: all ball."""
+        """Joints of any kind (egs_world_set_joints_kinds): JOINT_BALL, JOINT_LOCK, JOINT_HINGE_AXIS, JOINT_SLIDER_AXIS; kind None: all ball."""
         kind, body0, body1, data = _i32(kind), _i32(body0), _i32(body1), _f64(data)
         if kind is not None and kind.shape[0] != body0.shape[0]:
             raise ValueError("kind: %d entries for %d joints" % (kind.shape[0], body0.shape[0]))
@@ -1063,6 +1077,15 @@ class World:
         if lim is not None and mj is not None and lim.size != 8 * mj:
             raise ValueError("lim: %d values for %d joints" % (lim.size, mj))
         self.ctx.check(load().egs_world_set_joint_limits(self.h, _p(lim)))
+
+    def set_slider_limits(self, lim=None):
+        """Travel stops of the world's sliders (egs_world_set_slider_limits): [m_joints][2] as
+        Problem.set_slider_limits; None: off."""
+        lim = _f64(lim)
+        mj = getattr(self, "m_joints", None)
+        if lim is not None and mj is not None and lim.size != 2 * mj:
+            raise ValueError("lim: %d values for %d joints" % (lim.size, mj))
+        self.ctx.check(load().egs_world_set_slider_limits(self.h, _p(lim)))
 
     def step(self, dt, erp, prm, detect_contacts=True, want_stats=False):
         st = SolveStats()

@@ -146,6 +146,65 @@ __device__ __forceinline__ void hinge_block(const AssembleArgs &A, int b0, int b
     }
 }
 
+// SLIDER_AXIS (EGS_JOINT_SLIDER_AXIS = 5; a slider is LOCK + SLIDER_AXIS as a hinge is BALL + HINGE_AXIS), data =
+// (a0[3], c[3], 0): a0 the unit rail direction in body0's frame; with body1 a body c is a point of the rail in body0's
+// frame and the rail's target point is body1's centre, P1 = pos[b1]; with a world side c is the world point the rail
+// passes through, P1 = c, and the rail passes through body0's centre.
+//   s = mv3(R0, a0);  Rn = align_to_z(s), rows (p, q, s^)
+//   two bodies:  ro = mv3(R0, c);  D[k] = (p0[k] + ro[k]) - P1[k]
+//   world side:                    D[k] =  p0[k] - c[k]
+//   rel[k] = p0[k] - P1[k];  rw = mm3(Rn, crossmat(rel))         row r is (P1 - p0) x Rn_r: the lever arm is body0's alone
+//   J0 = [Rn | rw], J1 = [-1.0*Rn | 0] (all zero for a world side);  err = (d3(p, D), d3(q, D), 0)
+// Rows 0 and 1 are equality rows; row 2, the rail row, is an inequality row with lo = hi = 0 (the multiplier pinned at
+// 0: the slider runs freely) unless a motor opens its bounds (motor_row) or a travel stop is active (slider_stop_row).
+// The travel is x = d3(s^, D): d x/dt = row 2 of J0 s0 + J1 s1 at every pose (s is rigid in body0, body1 enters
+// through its centre only); rows 0 and 1 are exact at err = 0, as the ball's and the hinge's.
+// slider_frame: Rn and D, the part slider_stop_row shares with the block, operation for operation.
+__device__ __forceinline__ void slider_frame(const AssembleArgs &A, int b0, int b1, const double *d, double *Rn, double *D,
+                                             double *rel) {
+  double R0[9], s[3], p0[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R0[k] = A.R[(size_t)b0 * 9 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p0[k] = A.pos[(size_t)b0 * 3 + k];
+  mv3(R0, d, s);
+  align_to_z(s, Rn);
+  if (b1 >= 0) {
+    double ro[3];
+    mv3(R0, d + 3, ro);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double P1 = A.pos[(size_t)b1 * 3 + k];
+      D[k] = (p0[k] + ro[k]) - P1;
+      rel[k] = p0[k] - P1;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      D[k] = p0[k] - d[3 + k];
+      rel[k] = p0[k] - d[3 + k];
+    }
+  }
+}
+__device__ __forceinline__ void slider_block(const AssembleArgs &A, int b0, int b1, const double *d, double *j0, double *j1,
+                                             double *e) {
+  double Rn[9], D[3], rel[3], cm[9], rw[9];
+  slider_frame(A, b0, b1, d, Rn, D, rel);
+  crossmat(rel, cm);
+  mm3(Rn, cm, rw);
+  e[0] = d3(Rn, D);
+  e[1] = d3(Rn + 3, D);
+  e[2] = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      j0[6 * r + k] = Rn[3 * r + k];
+      j0[6 * r + 3 + k] = rw[3 * r + k];
+      if (b1 >= 0) j1[6 * r + k] = -1.0 * Rn[3 * r + k];
+    }
+}
+
 // A contact's blocks (contact.cc:14-117, FrictionModel::BOX) as functions of values: no loads.  d = the descriptor
 // (point[3], normal[3], depth).  contact_frame: Rn from the normal.  contact_side: side SIDE's block j (all 18 entries)
 // from Rn, the point and the body's position.  contact_err: e = err.  contact_blocks: the three together, j0 / j1 zero
@@ -191,12 +250,13 @@ __device__ __forceinline__ void side_u(const double *vw, const double *wf, doubl
 }
 
 // Constraint i: j0 / j1 (3x6 row-major, zero for a world side), e = err, lo / hi, eq per row (every row of a ball joint
-// and of a lock is an equality row, no row of a contact is, a hinge's axis row is not) and per side u = v/dt + W f
+// and of a lock is an equality row, no row of a contact is, a hinge's axis row and a slider's rail row are not) and per side u = v/dt + W f
 // (zero for a world side), what the rhs needs.
 // EACH: dt is the constraint's own time step, dt_each (constraint_rates); otherwise the launch's A.dt, read where the
 // scalar form has always read it.  ANGULAR = false leaves the angular blocks out: the fused prologue of
-// step_solve_kernel, which choose_sweep offers lists of contacts only, keeps the code it had.
-template <bool EACH, bool ANGULAR = true>
+// step_solve_kernel, which choose_sweep offers lists of contacts only, keeps the code it had.  SLIDER = true adds the
+// slider block (kind 5): the forms launched only for a list that holds one, so that every other list runs the code it ran.
+template <bool EACH, bool ANGULAR = true, bool SLIDER = false>
 __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, double dt_each, double *j0, double *j1, double *e,
                                                double *lo, double *hi, bool *eq, double *u0, double *u1) {
   const int b0 = A.body0[i], b1 = A.body1[i];
@@ -208,6 +268,7 @@ __device__ __forceinline__ void assemble_one_t(const AssembleArgs &A, int i, dou
   const int kind = A.kind[i];
   if (ANGULAR && kind >= 2) {
     if (kind == 2) lock_block(A, b0, b1, d, j0, j1, e);
+    else if (SLIDER && kind == 5) slider_block(A, b0, b1, d, j0, j1, e);
     else hinge_block(A, b0, b1, d, j0, j1, e);
     eq[0] = true; eq[1] = true; eq[2] = kind == 2;
 #pragma unroll
@@ -336,11 +397,13 @@ __device__ __forceinline__ double assemble_rhs_bounce_t(const AssembleArgs &A, i
 // is 0 for it): rhs2 = t - ju, so that the solve asks for s^ . (w0' - w1') = speed within the torque limit.  Returns
 // whether it applied; tau < 0 and every other kind are left as assembled.  A hinge whose stop is active this step
 // (limit_row below) is not handed to it: motor and limit share the axis row, and the row is the limit's then.
-template <bool EACH>
+// SLIDER: a SLIDER_AXIS constraint's rail row likewise, (speed, f) with f the force limit and speed = dx/dt, body0's
+// travel relative to body1 along s^; a slider whose travel stop is active (slider_stop_row) is not handed to it.
+template <bool EACH, bool SLIDER = false>
 __device__ __forceinline__ bool motor_row(const AssembleArgs &A, const double *motor, int i, double dt_each, const double *j0,
                                           const double *j1, const double *u0, const double *u1, double *lo, double *hi,
                                           double &rhs2) {
-  if (A.kind[i] != 3) return false;
+  if (SLIDER ? (A.kind[i] != 3 && A.kind[i] != 5) : A.kind[i] != 3) return false;
   const double speed = motor[(size_t)i * 2], tau = motor[(size_t)i * 2 + 1];
   if (!(tau >= 0)) return false;
   lo[2] = -tau;
@@ -398,6 +461,38 @@ __device__ __forceinline__ bool limit_row(const AssembleArgs &A, const double *l
   }
   if (lower && sn * (1.0 + clo) < slo * (1.0 + cs)) {
     err2 = sn * clo - cs * slo;
+    lo2 = 0.0;
+    hi2 = INFINITY;
+    return true;
+  }
+  return false;
+}
+// The travel table (egs_problem_set_slider_limits), lim [m][2] = (xlo, xhi), -inf / +inf: no stop on that side, not
+// NULL: a SLIDER_AXIS constraint i has its travel x = d3(s^, D) read with the block's own operations (slider_frame) and,
+// past a stop, its rail row made the one-sided row of that stop:
+//   xhi finite and x > xhi:       err[2] = x - xhi, lo[2] = -inf, hi[2] = 0
+//   else xlo finite and x < xlo:  err[2] = x - xlo, lo[2] = 0,    hi[2] = +inf
+// The rhs row is the ordinary kk err[2] - ju.  err2 / lo2 / hi2 are written only then.  Returns whether a stop is
+// active; then motor_row leaves the row alone for this step.  Every other kind is left as assembled.
+__device__ __forceinline__ bool slider_stop_row(const AssembleArgs &A, const double *lim, int i, double &err2, double &lo2,
+                                                double &hi2) {
+  if (A.kind[i] != 5) return false;
+  const double xlo = lim[(size_t)i * 2], xhi = lim[(size_t)i * 2 + 1];
+  const bool lower = xlo > -INFINITY, upper = xhi < INFINITY;
+  if (!lower && !upper) return false;
+  double d[6], Rn[9], D[3], rel[3];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) d[k] = A.data[(size_t)i * 7 + k];
+  slider_frame(A, A.body0[i], A.body1[i], d, Rn, D, rel);
+  const double x = d3(Rn + 6, D);
+  if (upper && x > xhi) {
+    err2 = x - xhi;
+    lo2 = -INFINITY;
+    hi2 = 0.0;
+    return true;
+  }
+  if (lower && x < xlo) {
+    err2 = x - xlo;
     lo2 = 0.0;
     hi2 = INFINITY;
     return true;

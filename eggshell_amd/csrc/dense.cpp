@@ -217,6 +217,12 @@ egs_status egs_problem_step_dense(egs_problem *p, double dt, double erp, double 
   if (p->limits)
     return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no hinge limits: hinge constraint " + std::to_string(p->limited_hinge) +
                                                  " has a stop (take the table away, or use the sweeps)");
+  if (p->travels)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no travel stops: slider constraint " + std::to_string(p->stopped_slider) +
+                                                 " has a stop (take the table away, or use the sweeps)");
+  if (p->pinned_slider >= 0)
+    return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free slider's rail row at lo = hi = 0: slider constraint " +
+                                                 std::to_string(p->pinned_slider) + " (give it a motor with a force > 0, or use the sweeps)");
   if (p->hinges_pinned)
     return fail(p->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   if (ok) *ok = 0;

@@ -203,14 +203,24 @@ void launch_quad_patch_solve(const SolveArgs<REAL> &a, int method, int n_tiles, 
 // EGS_JOINT_HINGE_AXIS; false launches the form without them (and without the motors), the code of the lists before them.
 // limit [m][8] or NULL: the hinge limits (egs_problem_set_hinge_limits), travelling the same way; with a table the
 // angular form's instantiation with limit_row runs, without one the kernel the lists ran before the limits.
+// slider: the list holds an EGS_JOINT_SLIDER_AXIS; then the slider form runs, with motor, limit and travel [m][2] (the
+// sliders' travel stops, egs_problem_set_slider_limits) as run-time pointers, NULL = off.  Without a slider no launch
+// reads travel, and every list runs the kernel it ran before the sliders.
 struct HingeTables {
-  const double *motor = nullptr, *limit = nullptr;
+  const double *motor = nullptr, *limit = nullptr, *travel = nullptr;
+  bool slider = false;
 };
 template <typename REAL>
 void launch_assemble(const AssembleArgs &a, bool angular, const HingeTables &h, hipStream_t s);
 // ... with every constraint on its ensemble's rates (a.dt and a.erp are not read)
 template <typename REAL>
 void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const HingeTables &h, hipStream_t s);
+// dst[r] = the bound lo[r] of a slider's pinned rail row (kind 5, row 2, lo == hi), src[r] of every other row; dst may
+// be src.  What a tolerance-terminated solve of a list with a slider starts from (solve.cpp: StartScope): the stopping
+// test leaves pinned rows out, so the start must hold them at their bound already.  The rows of every other kind keep
+// their start, so an ensemble without a slider in a batch that holds one starts as its own world does.
+template <typename REAL>
+void launch_pin_start(int rows, const REAL *src, const int32_t *kind, const REAL *lo, const REAL *hi, REAL *dst, hipStream_t s);
 // partial sums of squares by row category: out[4*blocks].  mu [rows / 3] (may be NULL: off): rows 0 and 1 of a
 // constraint with mu >= 0 are sorted by the pyramid's bounds, as in the kernels below that
 // take the coefficients from SolveArgs::mu.

@@ -671,9 +671,15 @@ struct NoRates {};   // the scalar form's (empty) second argument
 // the registers and the occupancy it had before they existed.  LIMITS: the hinge limits' table (assemble_device.h:
 // limit_row) is set; an instantiation of the ANGULAR form of its own, so that the lists without a stop run the code
 // they ran before the limits.  A row whose stop is active is the limit's for the step: the motor leaves it alone.
-template <typename REAL, bool EACH, typename RATES, bool REST, bool ANGULAR, bool LIMITS = false>
+// SLIDER: the list holds an EGS_JOINT_SLIDER_AXIS; the form with the slider block beside every other, launched for such
+// a list only.  Its tables are run-time pointers, NULL = off: motor (hinges and sliders), limit (the hinge limits) and
+// travel (the sliders' stops, assemble_device.h: slider_stop_row), the last an argument of this form alone (SliderArg).
+struct NoTravel {};
+template <bool SLIDER> struct SliderArg { using type = NoTravel; };
+template <> struct SliderArg<true> { using type = const double *; };
+template <typename REAL, bool EACH, typename RATES, bool REST, bool ANGULAR, bool LIMITS = false, bool SLIDER = false>
 __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, const RATES T, const double *motor,
-                                                       const double *limit) {
+                                                       const double *limit, const typename SliderArg<SLIDER>::type travel) {
   // J blocks leave through LDS: a lane's 18 values are 144 B apart from its neighbour's, so direct
   // stores hit 64 lines per instruction; staged, the workgroup writes its 256 x 18 block contiguously
   __shared__ REAL stage[256 * 19];   // row stride 19: conflict-free column walks
@@ -688,8 +694,12 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   bool stopped = false;
   double stop_err = 0.0, stop_lo = 0.0, stop_hi = 0.0;
   if constexpr (LIMITS) stopped = limit_row(A, limit, i, stop_err, stop_lo, stop_hi);
-  assemble_one_t<EACH, ANGULAR>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
-  if (LIMITS && stopped) { e[2] = stop_err; lo[2] = stop_lo; hi[2] = stop_hi; }
+  if constexpr (SLIDER) {
+    if (limit != nullptr) stopped = limit_row(A, limit, i, stop_err, stop_lo, stop_hi);
+    if (travel != nullptr && !stopped) stopped = slider_stop_row(A, travel, i, stop_err, stop_lo, stop_hi);
+  }
+  assemble_one_t<EACH, ANGULAR, SLIDER>(A, i, dt, j0, j1, e, lo, hi, eq, u0, u1);
+  if ((LIMITS || SLIDER) && stopped) { e[2] = stop_err; lo[2] = stop_lo; hi[2] = stop_hi; }
   REAL *J0o = reinterpret_cast<REAL *>(A.J0), *J1o = reinterpret_cast<REAL *>(A.J1);
   REAL *loo = reinterpret_cast<REAL *>(A.lo), *hio = reinterpret_cast<REAL *>(A.hi);
   REAL *rhso = reinterpret_cast<REAL *>(A.rhs);
@@ -708,7 +718,7 @@ __global__ void __launch_bounds__(256) assemble_kernel(const AssembleArgs A, con
   }
   if (!live) return;
   double motor_rhs = 0.0;
-  const bool motored = ANGULAR && !stopped && motor != nullptr && motor_row<EACH>(A, motor, i, dt, j0, j1, u0, u1, lo, hi, motor_rhs);
+  const bool motored = ANGULAR && !stopped && motor != nullptr && motor_row<EACH, SLIDER>(A, motor, i, dt, j0, j1, u0, u1, lo, hi, motor_rhs);
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     if (r == 2 && motored)
@@ -1041,28 +1051,49 @@ template <typename REAL>
 void launch_assemble(const AssembleArgs &a, bool angular, const HingeTables &h, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), t(256);
-  if (angular && h.limit) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit);
+  if (h.slider) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true, false, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit, h.travel);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true, false, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit, h.travel);
+  } else if (angular && h.limit) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit, NoTravel{});
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true, true>), g, t, 0, s, a, NoRates{}, h.motor, h.limit, NoTravel{});
   } else if (angular) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr);
-  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr);
-  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr);
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr, NoTravel{});
+    else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, true>), g, t, 0, s, a, NoRates{}, h.motor, nullptr, NoTravel{});
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, true, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr, NoTravel{});
+  else hipLaunchKernelGGL((assemble_kernel<REAL, false, NoRates, false, false>), g, t, 0, s, a, NoRates{}, nullptr, nullptr, NoTravel{});
 }
 
 template <typename REAL>
 void launch_assemble_each(const AssembleArgs &a, const EnsembleRates &t, bool angular, const HingeTables &h, hipStream_t s) {
   if (a.m <= 0) return;
   const dim3 g((a.m + 255) / 256), b(256);
-  if (angular && h.limit) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true, true>), g, b, 0, s, a, t, h.motor, h.limit);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true, true>), g, b, 0, s, a, t, h.motor, h.limit);
+  if (h.slider) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true, false, true>), g, b, 0, s, a, t, h.motor, h.limit, h.travel);
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true, false, true>), g, b, 0, s, a, t, h.motor, h.limit, h.travel);
+  } else if (angular && h.limit) {
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true, true>), g, b, 0, s, a, t, h.motor, h.limit, NoTravel{});
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true, true>), g, b, 0, s, a, t, h.motor, h.limit, NoTravel{});
   } else if (angular) {
-    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true>), g, b, 0, s, a, t, h.motor, nullptr);
-    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true>), g, b, 0, s, a, t, h.motor, nullptr);
-  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, false>), g, b, 0, s, a, t, nullptr, nullptr);
-  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, false>), g, b, 0, s, a, t, nullptr, nullptr);
+    if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, true>), g, b, 0, s, a, t, h.motor, nullptr, NoTravel{});
+    else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, true>), g, b, 0, s, a, t, h.motor, nullptr, NoTravel{});
+  } else if (a.rest) hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, true, false>), g, b, 0, s, a, t, nullptr, nullptr, NoTravel{});
+  else hipLaunchKernelGGL((assemble_kernel<REAL, true, EnsembleRates, false, false>), g, b, 0, s, a, t, nullptr, nullptr, NoTravel{});
+}
+
+template <typename REAL>
+__global__ void __launch_bounds__(256) pin_start_kernel(int rows, const REAL *src, const int32_t *kind, const REAL *lo,
+                                                        const REAL *hi, REAL *dst) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const REAL l = lo[r];
+  dst[r] = (r % 3 == 2 && kind[r / 3] == 5 && l == hi[r]) ? l : src[r];
+}
+
+template <typename REAL>
+void launch_pin_start(int rows, const REAL *src, const int32_t *kind, const REAL *lo, const REAL *hi, REAL *dst, hipStream_t s) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL((pin_start_kernel<REAL>), dim3((rows + 255) / 256), dim3(256), 0, s, rows, src, kind, lo, hi, dst);
 }
 
 template <typename REAL>
@@ -1244,6 +1275,7 @@ void launch_cons_prepare(const SolveArgs<REAL> &a, hipStream_t s) {
   template void launch_global_wres<REAL>(const GlobalArgs<REAL> &, hipStream_t);                            \
   template void launch_assemble<REAL>(const AssembleArgs &, bool, const HingeTables &, hipStream_t);                               \
   template void launch_assemble_each<REAL>(const AssembleArgs &, const EnsembleRates &, bool, const HingeTables &, hipStream_t);   \
+  template void launch_pin_start<REAL>(int, const REAL *, const int32_t *, const REAL *, const REAL *, REAL *, hipStream_t);  \
   template void launch_residual_partials<REAL>(int, const REAL *, const REAL *, const REAL *, const REAL *,  \
                                                const uint8_t *, const REAL *, double *, int, hipStream_t);   \
   template void launch_velocity<REAL>(int, const double *, const double *, const double *, const REAL *, double,   \

@@ -277,13 +277,17 @@ egs_status set_live_inertia(egs_problem *p, const double *inertia_body, const do
 // The angular blocks (EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS) are joints here: one between two bodies counts as a two-body
 // ball joint (its J1 is -1.0 * J0 only in value where J0 holds +0, and the LINSYM forms keep one linear block, which
 // these do not have), so a list that holds one runs none of LINSYM, FUSED_ASSEMBLY, PAIR or CHAIN.
+// A slider (EGS_JOINT_SLIDER_AXIS) has a lever arm on body0 alone, J1 = [-Rn | 0]: whichever sides it joins, the list
+// that holds one counts as holding a two-body joint, and none of LINSYM, FUSED_ASSEMBLY, PAIR, CHAIN, SHARE, FACE runs.
 void note_kinds(egs_problem *p, const int32_t *kind) {
   bool jp = false, joint = false;
   p->angular = false;
+  p->sliders = false;
   for (int i = 0; i < p->m; ++i) {
     joint = joint || kind[i] != EGS_CONTACT_BOX;
     p->angular = p->angular || kind[i] == EGS_JOINT_LOCK || kind[i] == EGS_JOINT_HINGE_AXIS;
-    jp = jp || (kind[i] != EGS_CONTACT_BOX && p->h_body0[i] >= 0 && p->h_body1[i] >= 0);
+    p->sliders = p->sliders || kind[i] == EGS_JOINT_SLIDER_AXIS;
+    jp = jp || (kind[i] != EGS_CONTACT_BOX && p->h_body0[i] >= 0 && p->h_body1[i] >= 0) || kind[i] == EGS_JOINT_SLIDER_AXIS;
   }
   p->joint_pairs = jp;
   p->contacts_only = !joint;
@@ -293,7 +297,13 @@ void note_kinds(egs_problem *p, const int32_t *kind) {
 
 void note_hinges(egs_problem *p, const double *motor) {
   p->hinges = p->hinges_pinned = false;
+  p->pinned_slider = -1;
   for (int i = 0; i < p->m && i < (int)p->h_kind.size(); ++i) {
+    if (p->h_kind[i] == EGS_JOINT_SLIDER_AXIS) {   // its rail row is a box row of the dense steps, as a hinge's axis row
+      p->hinges = true;
+      if ((!motor || !(motor[2 * (size_t)i + 1] > 0)) && p->pinned_slider < 0) p->pinned_slider = i;
+      continue;
+    }
     if (p->h_kind[i] != EGS_JOINT_HINGE_AXIS) continue;
     p->hinges = true;
     if (!motor || !(motor[2 * (size_t)i + 1] > 0)) p->hinges_pinned = true;
@@ -317,7 +327,8 @@ egs_status report_stall(egs_problem *p) {
 }
 
 // What is wrong with a list of kinds and descriptors (nothing: NULL): an unknown kind; for the angular blocks a side 0
-// without a body, non-finite data, a LOCK quaternion or a hinge axis whose squared norm is not within 1e-12 of 1.
+// without a body, non-finite data, a LOCK quaternion or a hinge axis whose squared norm is not within 1e-12 of 1; for
+// a slider a side 0 without a body, non-finite data, a rail direction a0 that is no unit vector within 1e-12.
 const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, const double *data) {
   auto unit = [](const double *v, int k) {
     double n = 0.0;
@@ -334,6 +345,12 @@ const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, 
           if (!std::isfinite(d[k])) return "non-finite angular joint data";
         if (kind[i] == EGS_JOINT_LOCK ? !unit(d, 4) : !(unit(d, 3) && unit(d + 3, 3)))
           return kind[i] == EGS_JOINT_LOCK ? "the lock quaternion is not a unit quaternion" : "a hinge axis is not a unit vector";
+        break;
+      case EGS_JOINT_SLIDER_AXIS:
+        if (body0[i] < 0) return "a slider needs a body on side 0";
+        for (int k = 0; k < 7; ++k)
+          if (!std::isfinite(d[k])) return "non-finite slider data";
+        if (!unit(d, 3)) return "a slider's rail direction is not a unit vector";
         break;
       default: return "unknown constraint kind";
     }
@@ -363,6 +380,19 @@ const char *limits_fault(size_t m, const int32_t *kind, const double *lim, int *
     }
     if (lower && upper && L[4] * (1.0 + L[7]) > L[6] * (1.0 + L[5])) return "a hinge's lower limit is above its upper limit";
     if (*first < 0) *first = (int)i;
+  }
+  return nullptr;
+}
+
+const char *travel_fault(size_t m, const int32_t *kind, const double *lim, int *first) {
+  *first = -1;
+  for (size_t i = 0; lim && i < m; ++i) {
+    const double xlo = lim[2 * i], xhi = lim[2 * i + 1];
+    if (xlo != xlo || xhi != xhi) return "NaN slider limit entry";
+    if (kind[i] != EGS_JOINT_SLIDER_AXIS) continue;
+    if (xlo == INFINITY || xhi == -INFINITY) return "a slider's lower limit is +inf or its upper limit -inf";
+    if (xlo > xhi) return "a slider's lower limit is above its upper limit";
+    if (*first < 0 && (std::isfinite(xlo) || std::isfinite(xhi))) *first = (int)i;
   }
   return nullptr;
 }
@@ -526,7 +556,10 @@ void problem_set_topology(egs_problem *p, int32_t m, const int32_t *body0, const
   p->motors = false;        // likewise
   p->limits = false;        // likewise
   p->limited_hinge = -1;
-  p->hinges = p->hinges_pinned = p->angular = false;
+  p->travels = false;       // likewise
+  p->stopped_slider = -1;
+  p->hinges = p->hinges_pinned = p->angular = p->sliders = false;
+  p->pinned_slider = -1;
   p->h_kind.clear();
   {  // quad schedule: small problems whose islands all fit 64-constraint tiles
     const char *env = std::getenv("EGS_QUAD");
@@ -774,7 +807,7 @@ egs_status egs_problem_set_motors(egs_problem *p, const double *motor) {
     const double speed = motor[2 * i], tau = motor[2 * i + 1];
     if (speed != speed || std::isinf(speed)) return fail(p->ctx, EGS_ERR_INVALID, "NaN or infinite motor speed");
     if (tau != tau) return fail(p->ctx, EGS_ERR_INVALID, "NaN motor torque limit");
-    any |= tau >= 0 && i < p->h_kind.size() && p->h_kind[i] == EGS_JOINT_HINGE_AXIS;
+    any |= tau >= 0 && i < p->h_kind.size() && (p->h_kind[i] == EGS_JOINT_HINGE_AXIS || p->h_kind[i] == EGS_JOINT_SLIDER_AXIS);
   }
   return guarded(p->ctx, [&]() -> egs_status {
     ensure_system(p);   // a deferred system is the one of the table its step ran with
@@ -807,6 +840,27 @@ egs_status egs_problem_set_hinge_limits(egs_problem *p, const double *lim) {
     p->limits = first >= 0;
     p->limited_hinge = first;
     p->h_rows_valid = false;   // the axis rows' bounds follow the table
+    return EGS_OK;
+  });
+}
+
+egs_status egs_problem_set_slider_limits(egs_problem *p, const double *lim) {
+  if (!p) return EGS_ERR_INVALID;
+  const size_t m = (size_t)p->m;
+  int first = -1;
+  if (lim && p->h_kind.size() != m) return fail(p->ctx, EGS_ERR_INVALID, "egs_problem_set_constraints first: the limits go with its kinds");
+  if (lim)
+    if (const char *fault = travel_fault(m, p->h_kind.data(), lim, &first)) return fail(p->ctx, EGS_ERR_INVALID, fault);
+  return guarded(p->ctx, [&]() -> egs_status {
+    ensure_system(p);   // a deferred system is the one of the table its step ran with
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));   // an assembly in flight may still read the old table
+    if (first >= 0) {
+      p->travel.alloc(m * 2);
+      upload(p->travel, lim, m * 2, p->ctx->stream);
+    }
+    p->travels = first >= 0;
+    p->stopped_slider = first;
+    p->h_rows_valid = false;   // the rail rows' bounds follow the table
     return EGS_OK;
   });
 }
@@ -894,6 +948,8 @@ egs_status egs_problem_set_constraints(egs_problem *p, const int32_t *kind, cons
     p->motors = false;   // the table was given for the kinds before these
     p->limits = false;   // likewise
     p->limited_hinge = -1;
+    p->travels = false;  // likewise
+    p->stopped_slider = -1;
     p->have_constraints = true;
     p->h_rows_valid = false;
     return EGS_OK;

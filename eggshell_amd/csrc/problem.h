@@ -184,6 +184,18 @@ struct egs_problem {
   bool limits = false;
   int limited_hinge = -1;
   bool angular = false;               // the kinds hold a LOCK or a HINGE_AXIS: the assembly launches their form (kernels.h)
+  // Sliders (EGS_JOINT_SLIDER_AXIS).  sliders: the kinds hold one -- then every assemble_kernel launch runs the slider
+  // form (hinge_tables) and no LINSYM schedule runs (note_kinds); pinned_slider: the first whose rail row stays pinned at
+  // lo = hi = 0 under the motor table in force (-1: none; the dense steps refuse it by name).  Travel stops
+  // (egs_problem_set_slider_limits, egs_world_set_slider_limits): travel [m][2] fp64 = (xlo, xhi) per constraint
+  // (assemble_device.h: slider_stop_row).  travels: some slider has a finite stop -- then the slider form takes the
+  // table and the dense steps refuse, naming stopped_slider (the first such); off, nothing reads it.  A new topology or
+  // new constraints turn it off (the world refills it).
+  bool sliders = false;
+  int pinned_slider = -1;
+  egs::DevBuf<double> travel;
+  bool travels = false;
+  int stopped_slider = -1;
   std::vector<int32_t> h_kind;         // the kinds of the list (note_kinds)
   // egs_problem_set_dense_friction: max_outer > 0 makes egs_problem_step_dense solve the pyramid while friction is on
   // (0: it refuses); the outcome of the last such step (egs_problem_dense_friction_info).
@@ -236,14 +248,19 @@ void note_kinds(egs_problem *p, const int32_t *kind);
 const char *constraints_fault(int m, const int32_t *kind, const int32_t *body0, const double *data);
 void note_assembled(egs_problem *p);
 AssembleArgs assemble_args(egs_problem *p, double dt, double erp);
-// the motor and limit tables the assembly launches take beside it: p->motor / p->limit while they are on, else NULL
+// the motor, limit and travel tables the assembly launches take beside it: p->motor / p->limit / p->travel while they
+// are on, else NULL, and whether the list holds a slider
 inline egs::HingeTables hinge_tables(const egs_problem *p) {
-  return egs::HingeTables{p->motors ? p->motor.p : nullptr, p->limits ? p->limit.p : nullptr};
+  return egs::HingeTables{p->motors ? p->motor.p : nullptr, p->limits ? p->limit.p : nullptr,
+                          p->sliders && p->travels ? p->travel.p : nullptr, p->sliders};
 }
+// What is wrong with a travel table lim [m][2] for the kinds given (nothing: NULL): a NaN anywhere; on a SLIDER_AXIS
+// row xlo = +inf, xhi = -inf or xlo > xhi.  *first: the first SLIDER_AXIS constraint with a finite stop (-1: none).
+const char *travel_fault(size_t m, const int32_t *kind, const double *lim, int *first);
 // What is wrong with a limit table lim [m][8] for the kinds given (nothing: NULL; rows of other kinds are not read),
 // and in *first the first HINGE_AXIS constraint with a stop (-1: none).
 const char *limits_fault(size_t m, const int32_t *kind, const double *lim, int *first);
-// hinges / hinges_pinned from the kinds and motor [m][2] (NULL: none): problem.h
+// hinges / hinges_pinned / pinned_slider from the kinds and motor [m][2] (NULL: none): problem.h
 void note_hinges(egs_problem *p, const double *motor);
 void do_assemble(egs_problem *p, double dt, double erp);
 // J0, J1, rhs, lo, hi, err and is_eq are materialised after this (a no-op unless the last step deferred them)

@@ -407,14 +407,29 @@ void release_large_history(egs_problem *p) {
 // One solve's start (egs_problem_set_start): decided before the first launch, in force until the solve returns.
 // PREVIOUS takes its copy of x here, so x0 never aliases x; a problem without a lambda for its constraint list starts
 // from rhs.  Launches outside a solve (accumulators_from_lambda) never see a start.
+// pin: a tolerance-terminated solve of a list that holds a slider.  Its stopping test is first made on the start, and it
+// leaves pinned rows (lo == hi, no equality row) out; a free slider's rail row is such a row, and where the start
+// satisfies every other row (a world-side slider on a vertical rail: only the rail row has a right-hand side) the solve
+// would return lambda_rail = rhs != 0 without a sweep.  So that solve always takes a start, rhs if it has no other, with
+// every pinned rail row at its bound (launch_pin_start), the value the first sweep would give it.  The system is stored by
+// then (tol > 0 never fuses the assembly).  Lists without a slider start as they always have.
 struct StartScope {
   egs_problem *p;
-  explicit StartScope(egs_problem *q) : p(q) {
-    const bool take = p->m > 0 && solve_takes_start(p);
+  explicit StartScope(egs_problem *q, bool pin = false) : p(q) {
+    bool take = p->m > 0 && solve_takes_start(p);
+    const size_t bytes = (size_t)p->m * 3 * p->real_size();
     if (take && p->start_mode == EGS_START_PREVIOUS) {
-      const size_t bytes = (size_t)p->m * 3 * p->real_size();
       p->start.alloc(bytes);
       HIPCHK(hipMemcpyAsync(p->start.p, p->x.p, bytes, hipMemcpyDeviceToDevice, p->ctx->stream));
+    }
+    if (pin && p->m > 0) {
+      if (!take) p->start.alloc(bytes);
+      with_real(p, [&](auto r) {
+        using REAL = decltype(r);
+        launch_pin_start<REAL>(3 * p->m, take ? real<REAL>(p->start) : real<REAL>(p->rhs), p->kind.p, real<REAL>(p->lo),
+                               real<REAL>(p->hi), real<REAL>(p->start), p->ctx->stream);
+      });
+      take = true;
     }
     p->start_active = take;
   }
@@ -531,7 +546,7 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
   ensure_minv_real(p);   // also decides the isotropic fast path, hence the tile size
   if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
   if (stall_seen(p)) return report_stall(p);   // an earlier asynchronous solve timed out
-  const StartScope start(p);
+  const StartScope start(p, prm->tol > 0 && p->sliders);
   if (!(prm->tol > 0)) {
     // tickets are 32-bit counters that advance by cnt per sweep: very long runs
     // are cut into resumed launches so they cannot wrap
@@ -704,7 +719,7 @@ egs_status do_solve_batch(egs_problem *p, const egs_solve_params *prm, BatchSolv
   ensure_minv_real(p);
   if (!p->use_quad || prm->method == EGS_JACOBI) ensure_tile_plan(p);
   if (stall_seen(p)) return report_stall(p);
-  const StartScope start(p);
+  const StartScope start(p, p->sliders);   // (tol > 0 here)
   // the schedule of do_solve: same recorded-chunk decision, chunk sizes and deferred residual of x0
   const bool defer_first = defer_first_residual(prm);
   const bool history = use_history(p, prm);

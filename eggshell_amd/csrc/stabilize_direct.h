@@ -38,6 +38,8 @@ inline size_t direct_ws_size(size_t rows) {
 struct StabDirectArgs {
   AssembleArgs as{};                             // the world problem's body state and constraint list (outputs unused)
   const double *limit = nullptr;                 // the hinge limits' table [as.m][8] (assemble_device.h: limit_row); NULL: off
+  bool slider = false;                           // the list holds an EGS_JOINT_SLIDER_AXIS: its blocks get a pass of their own
+  const double *travel = nullptr;                // the sliders' travel stops [as.m][2] (assemble_device.h: slider_stop_row); NULL: off
   double *pos = nullptr, *R = nullptr, *v = nullptr, *w = nullptr;   // the same body state, to be moved
   const int32_t *cons = nullptr, *cstart = nullptr;   // ensemble e's constraints, in its own order: cons[cstart[e] .. cstart[e+1])
   const int32_t *bo = nullptr;                   // body offsets [E + 1]; NULL: one ensemble of as.n bodies

@@ -248,6 +248,7 @@ __global__ void __launch_bounds__(NT) stab_direct_kernel(StabDirectArgs a, const
   bool go;
   for (;;) {
     for (int i = t; i < me; i += NT) {   // J and err at the current body state, assemble_kernel's operations
+      if (a.slider && a.as.kind[a.cons[c0 + i]] == 5) continue;   // a slider's block: the pass below
       double j0[18], j1[18], ev[3], lo[3], hi[3], u0[6], u1[6];
       bool eq[3];
       assemble_one(a.as, a.cons[c0 + i], j0, j1, ev, lo, hi, eq, u0, u1);
@@ -260,6 +261,23 @@ __global__ void __launch_bounds__(NT) stab_direct_kernel(StabDirectArgs a, const
       for (int i = t; i < me; i += NT) {
         double err2, lo2, hi2;
         if (limit_row(a.as, a.limit, a.cons[c0 + i], err2, lo2, hi2)) M.b[3 * i + 2] = err2;
+      }
+    if (a.slider)   // the slider blocks, and an active travel stop's err[2] = x - limit: a pass of its own for the same reason
+      for (int i = t; i < me; i += NT) {
+        const int c = a.cons[c0 + i];
+        if (a.as.kind[c] != 5) continue;
+        double d[7], j0[18], j1[18], ev[3];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) d[k] = a.as.data[(size_t)c * 7 + k];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) { j0[k] = 0.0; j1[k] = 0.0; }
+        slider_block(a.as, a.as.body0[c], a.as.body1[c], d, j0, j1, ev);
+        double lo2, hi2;
+        if (a.travel) slider_stop_row(a.as, a.travel, c, ev[2], lo2, hi2);
+#pragma unroll
+        for (int k = 0; k < 18; ++k) { M.J[36 * i + k] = j0[k]; M.J[36 * i + 18 + k] = j1[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) M.b[3 * i + k] = ev[k];
       }
     __syncthreads();
     err_sq = direct_err_sq(M, N, t);

@@ -14,6 +14,7 @@ namespace {
 
 void world_fill_motors(egs_world *w);
 void world_fill_limits(egs_world *w);
+void world_fill_travel(egs_world *w);
 
 void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int m) {
   hipStream_t s = w->ctx->stream;
@@ -40,6 +41,7 @@ void world_make_problem(egs_world *w, const int32_t *b0, const int32_t *b1, int 
   }
   world_fill_motors(w);
   world_fill_limits(w);
+  world_fill_travel(w);
   np->have_constraints = true;
   np->h_rows_valid = false;
   w->topo_b0.assign(b0, b0 + m); w->topo_b1.assign(b1, b1 + m);
@@ -56,7 +58,7 @@ void world_fill_motors(egs_world *w) {
   std::vector<double> t((size_t)p->m * 2, -1.0);
   std::copy(w->jmotor.begin(), w->jmotor.end(), t.begin());
   bool any = false;
-  for (size_t i = 0; i < mj; ++i) any |= w->jkind[i] == EGS_JOINT_HINGE_AXIS && t[2 * i + 1] >= 0;
+  for (size_t i = 0; i < mj; ++i) any |= (w->jkind[i] == EGS_JOINT_HINGE_AXIS || w->jkind[i] == EGS_JOINT_SLIDER_AXIS) && t[2 * i + 1] >= 0;
   if (any) {
     p->motor.alloc(t.size());
     upload(p->motor, t.data(), t.size(), w->ctx->stream);
@@ -83,6 +85,29 @@ void world_fill_limits(egs_world *w) {
     upload(p->limit, t.data(), t.size(), w->ctx->stream);
     p->limits = true;
     p->limited_hinge = first;
+  }
+  p->h_rows_valid = false;
+}
+
+// The problem's travel table for its current list from the joints' (the joints come first; the contacts' rows are
+// (-inf, +inf), which slider_stop_row never reads: it returns on the kind).  The new topology has turned the problem's
+// table off.
+void world_fill_travel(egs_world *w) {
+  egs_problem *p = w->prob;
+  const size_t mj = w->jb0.size();
+  p->travels = false;
+  p->stopped_slider = -1;
+  if (w->jtravel.empty() || p->m <= 0) return;
+  std::vector<double> t((size_t)p->m * 2);
+  for (size_t i = 0; i < t.size(); ++i) t[i] = i % 2 ? INFINITY : -INFINITY;
+  std::copy(w->jtravel.begin(), w->jtravel.end(), t.begin());
+  int first = -1;
+  travel_fault(mj, w->jkind.data(), w->jtravel.data(), &first);   // validated when it was set: the first stop only
+  if (first >= 0) {
+    p->travel.alloc(t.size());
+    upload(p->travel, t.data(), t.size(), w->ctx->stream);
+    p->travels = true;
+    p->stopped_slider = first;
   }
   p->h_rows_valid = false;
 }
@@ -377,6 +402,7 @@ egs_status egs_world_set_joints_kinds(egs_world *w, int32_t m_joints, const int3
   else w->jkind.assign((size_t)m_joints, EGS_JOINT_BALL);
   w->jmotor.clear();   // the motors were those of the old list
   w->jlimit.clear();   // and the limits
+  w->jtravel.clear();  // and the sliders' travel stops
   // the ball joints, in list order: what the collider prunes against
   std::vector<int32_t> bb0, bb1;
   std::vector<double> bd;
@@ -446,6 +472,23 @@ egs_status egs_world_set_joint_limits(egs_world *w, const double *lim) {
     if (lim && first >= 0) w->jlimit.assign(lim, lim + 8 * mj);
     else w->jlimit.clear();
     if (w->prob) world_fill_limits(w);
+    return EGS_OK;
+  });
+}
+
+egs_status egs_world_set_slider_limits(egs_world *w, const double *lim) {
+  if (!w) return EGS_ERR_INVALID;
+  const size_t mj = w->jb0.size();
+  int first = -1;
+  if (const char *fault = travel_fault(mj, w->jkind.data(), lim, &first)) return fail(w->ctx, EGS_ERR_INVALID, fault);
+  return guarded(w->ctx, [&]() -> egs_status {
+    if (w->prob) {
+      ensure_system(w->prob);
+      HIPCHK(hipStreamSynchronize(w->ctx->stream));   // an assembly in flight may still read the old table
+    }
+    if (lim && first >= 0) w->jtravel.assign(lim, lim + 2 * mj);
+    else w->jtravel.clear();
+    if (w->prob) world_fill_travel(w);
     return EGS_OK;
   });
 }

@@ -147,6 +147,7 @@ struct egs_world {
   std::vector<double> jdata;
   std::vector<int32_t> jkind;          // their kinds (egs_world_set_joints_kinds; all EGS_JOINT_BALL from egs_world_set_joints)
   std::vector<double> jmotor;          // egs_world_set_joint_motors: [joints][2] = (speed, tau); empty: off
+  std::vector<double> jtravel;         // egs_world_set_slider_limits: [joints][2] = (xlo, xhi); empty: off (kept only while a slider has a finite stop)
   std::vector<double> jlimit;          // egs_world_set_joint_limits: [joints][8] = (q, sin lo, cos lo, sin hi, cos hi); empty: off
   int mj_ball = 0;                     // how many of them are ball joints
   egs::DevBuf<int32_t> djb0, djb1;     // the ball joints among them on the device, for joint-vs-contact pruning (an

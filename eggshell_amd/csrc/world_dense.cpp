@@ -143,7 +143,13 @@ egs_status world_dense_guard(egs_world *w, int32_t use_bounds) {
   if (w->friction.any && use_bounds != 1) return fail(w->ctx, EGS_ERR_INVALID, "the dense friction pyramid needs use_bounds = 1");
   // as egs_problem_step_dense: a hinge's axis row is a box row, and one pinned at lo = hi = 0 is not Murty's to solve
   bool hinges = false, pinned = false;
+  int pinned_slider = -1;
   for (size_t i = 0; i < w->jkind.size(); ++i) {
+    if (w->jkind[i] == EGS_JOINT_SLIDER_AXIS) {   // a slider's rail row likewise
+      hinges = true;
+      if (pinned_slider < 0 && (w->jmotor.empty() || !(w->jmotor[2 * i + 1] > 0))) pinned_slider = (int)i;
+      continue;
+    }
     if (w->jkind[i] != EGS_JOINT_HINGE_AXIS) continue;
     hinges = true;
     pinned = pinned || w->jmotor.empty() || !(w->jmotor[2 * i + 1] > 0);
@@ -156,6 +162,15 @@ egs_status world_dense_guard(egs_world *w, int32_t use_bounds) {
     return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no hinge limits: hinge joint " + std::to_string(first) +
                                                  " has a stop (take the table away, or use the sweeps)");
   }
+  if (!w->jtravel.empty()) {   // (kept only while a slider has a finite stop) likewise
+    int first = -1;
+    travel_fault(w->jkind.size(), w->jkind.data(), w->jtravel.data(), &first);
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step has no travel stops: slider joint " + std::to_string(first) +
+                                                 " has a stop (take the table away, or use the sweeps)");
+  }
+  if (pinned_slider >= 0)
+    return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free slider's rail row at lo = hi = 0: slider joint " +
+                                                 std::to_string(pinned_slider) + " (give it a motor with a force > 0, or use the sweeps)");
   if (pinned)
     return fail(w->ctx, EGS_ERR_UNSUPPORTED, "the dense step cannot pin a free hinge's axis row at lo = hi = 0 (give the hinge a motor with tau > 0, or use the sweeps)");
   return EGS_OK;

@@ -91,7 +91,10 @@ void world_relax_assemble(egs_world *w) {
   a.is_eq = w->rx.eq_scratch.p;
   // no motor: the relaxation reads J and err only.  The limits stay: an active stop's err[2] = sin(theta - limit) is a
   // row of (J J^T) y = err, an inactive one's is 0 as a free hinge's
-  launch_assemble<double>(a, p->angular, HingeTables{nullptr, hinge_tables(p).limit}, w->ctx->stream);
+  // Likewise a slider's travel stop: err[2] = x - limit while it is active, 0 as a free hinge's axis row otherwise
+  HingeTables tables = hinge_tables(p);
+  tables.motor = nullptr;
+  launch_assemble<double>(a, p->angular, tables, w->ctx->stream);
   HIPCHK(hipGetLastError());
   rx->have_blocks = true;
   rx->lin_neg = !rx->joint_pairs;
@@ -273,6 +276,8 @@ egs_status egs_world_stabilize_direct(egs_world *w, int32_t mode, int32_t max_st
       egs_problem *p = w->prob;
       a.as = assemble_args(p, 1.0, 0.2);
       a.limit = hinge_tables(p).limit;
+      a.slider = p->sliders;
+      a.travel = hinge_tables(p).travel;
       a.pos = p->pos.p; a.R = p->R.p; a.v = p->v.p; a.w = p->w.p;
       a.cons = d.cons.p; a.cstart = d.cstart.p;
       a.bo = E > 1 ? w->ens.d_boff.p : nullptr;

@@ -269,12 +269,87 @@ bool HingeAxisJoint::Describe(int32_t *kind, double data[7]) const {
   return true;
 }
 
-// [joints][2] = (speed, tau) of a joint list, (0, -1) for whatever is no motored hinge; returns whether any hinge is driven
+SliderAxisJoint::SliderAxisJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world)
+    : Joint(std::move(b0), i0, Vector3d::Zero(), std::move(b1), i1, Vector3d::Zero()) {
+  if (!(axis_world.norm() > 0)) throw egs::Error(EGS_ERR_INVALID, "SliderAxisJoint: the rail direction must not vanish");
+  const Vector3d a = axis_world / axis_world.norm();
+  a0_ = b0_->R().transpose() * a;
+  a0_ = a0_ / a0_.norm();
+  // x = 0 now: the rail's point is body1's centre (in body0's frame), or body0's own centre for a world side
+  c_ = b1_ == nullptr ? b0_->p() : b0_->R().transpose() * (b1_->p() - b0_->p());
+}
+
+void SliderAxisJoint::Frame(Matrix3d *Rn, Vector3d *D, Vector3d *rel) const {
+  const Vector3d s = b0_->R() * a0_;
+  *Rn = AlignVectors(s, Vector3d(0, 0, 1));
+  const Vector3d p0 = b0_->p();
+  if (b1_ != nullptr) {
+    const Vector3d ro = b0_->R() * c_, P1 = b1_->p();
+    for (int k = 0; k < 3; ++k) { (*D)[k] = (p0[k] + ro[k]) - P1[k]; (*rel)[k] = p0[k] - P1[k]; }
+  } else {
+    for (int k = 0; k < 3; ++k) { (*D)[k] = p0[k] - c_[k]; (*rel)[k] = p0[k] - c_[k]; }
+  }
+}
+
+double SliderAxisJoint::Position() const {
+  Matrix3d Rn;
+  Vector3d D, rel;
+  Frame(&Rn, &D, &rel);
+  return Vector3d(Rn.d[6], Rn.d[7], Rn.d[8]).dot(D);
+}
+
+int SliderAxisJoint::ActiveStop(double *err2) const {
+  *err2 = 0.0;
+  if (!has_limits()) return 0;
+  const double x = Position();
+  if (limit_hi_ < INFINITY && x > limit_hi_) { *err2 = x - limit_hi_; return 1; }
+  if (limit_lo_ > -INFINITY && x < limit_lo_) { *err2 = x - limit_lo_; return -1; }
+  return 0;
+}
+
+VectorXd SliderAxisJoint::ComputeError() const {
+  Matrix3d Rn;
+  Vector3d D, rel;
+  Frame(&Rn, &D, &rel);
+  double err2;
+  ActiveStop(&err2);   // 0 unless a stop is active: then x - stop
+  return ToX(Vector3d(Vector3d(Rn.d[0], Rn.d[1], Rn.d[2]).dot(D), Vector3d(Rn.d[3], Rn.d[4], Rn.d[5]).dot(D), err2));
+}
+
+void SliderAxisJoint::ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *ct, VectorXd *lo, VectorXd *hi) const {
+  Matrix3d Rn;
+  Vector3d D, rel;
+  Frame(&Rn, &D, &rel);
+  SetBlock(J_b0, Rn, Rn * CrossMat(rel));   // row r of the angular part: (P1 - p0) x Rn_r, the lever arm on body0 alone
+  if (b1_ == nullptr) SetBlock(J_b1, Matrix3d::Zero(), Matrix3d::Zero());
+  else SetBlock(J_b1, -1.0 * Rn, Matrix3d::Zero());
+  AngularRows(ct, lo, hi, false);
+  double err2;
+  const int stop = ActiveStop(&err2);   // an active stop's row is the stop's for the step: the motor leaves it alone
+  if (stop > 0) { (*lo)(2) = -INFINITY; (*hi)(2) = 0.0; }
+  else if (stop < 0) { (*lo)(2) = 0.0; (*hi)(2) = INFINITY; }
+  else if (force_ >= 0) { (*lo)(2) = -force_; (*hi)(2) = force_; }
+}
+
+bool SliderAxisJoint::Describe(int32_t *kind, double data[7]) const {
+  *kind = EGS_JOINT_SLIDER_AXIS;
+  for (int k = 0; k < 3; ++k) { data[k] = a0_[k]; data[3 + k] = c_[k]; }
+  data[6] = 0;
+  return true;
+}
+
+// [joints][2] = (speed, tau) of a joint list, (0, -1) for whatever is no motored hinge or slider; returns whether any is driven
 static bool JointMotors(const JointsList &joints, std::vector<double> *motor) {
   bool any = false;
   motor->assign(2 * joints.size(), 0.0);
   for (size_t j = 0; j < joints.size(); ++j) {
     (*motor)[2 * j + 1] = -1.0;
+    if (const auto *sl = dynamic_cast<const SliderAxisJoint *>(joints[j].get())) {
+      if (!(sl->motor_force() >= 0)) continue;
+      (*motor)[2 * j] = sl->motor_speed(); (*motor)[2 * j + 1] = sl->motor_force();
+      any = true;
+      continue;
+    }
     const auto *h = dynamic_cast<const HingeAxisJoint *>(joints[j].get());
     if (!h || !(h->motor_torque() >= 0)) continue;
     (*motor)[2 * j] = h->motor_speed(); (*motor)[2 * j + 1] = h->motor_torque();
@@ -294,6 +369,49 @@ static bool JointLimits(const JointsList &joints, std::vector<double> *lim) {
     any = true;
   }
   return any;
+}
+
+// [joints][2], the travel stops of a joint list, (-inf, +inf) for whatever is no limited slider; returns whether any slider has a stop
+static bool JointTravel(const JointsList &joints, std::vector<double> *lim) {
+  bool any = false;
+  lim->assign(2 * joints.size(), INFINITY);
+  for (size_t j = 0; j < joints.size(); ++j) {
+    (*lim)[2 * j] = -INFINITY;
+    const auto *sl = dynamic_cast<const SliderAxisJoint *>(joints[j].get());
+    if (!sl || !sl->has_limits()) continue;
+    (*lim)[2 * j] = sl->limit_lo(); (*lim)[2 * j + 1] = sl->limit_hi();
+    any = true;
+  }
+  return any;
+}
+
+int Ensemble::AddSlider(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world) {
+  auto slider = std::make_shared<SliderAxisJoint>(b0, i0, b1, i1, axis_world);   // (throws before anything is added)
+  joints_.push_back(std::make_shared<AngularLockJoint>(b0, i0, b1, i1));
+  joints_.push_back(slider);
+  return (int)joints_.size() - 1;
+}
+
+void Ensemble::SetSliderMotor(int index, double speed, double max_force) {
+  auto *s = index >= 0 && index < (int)joints_.size() ? dynamic_cast<SliderAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!s) throw egs::Error(EGS_ERR_INVALID, "SetSliderMotor: joint " + std::to_string(index) + " is not a slider");
+  if (speed != speed || std::isinf(speed) || max_force != max_force)
+    throw egs::Error(EGS_ERR_INVALID, "SetSliderMotor: the speed must be finite and the force limit a number");
+  s->SetMotor(speed, max_force);
+}
+
+void Ensemble::SetSliderLimits(int index, double lo, double hi) {
+  auto *s = index >= 0 && index < (int)joints_.size() ? dynamic_cast<SliderAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!s) throw egs::Error(EGS_ERR_INVALID, "SetSliderLimits: joint " + std::to_string(index) + " is not a slider");
+  if (lo != lo || hi != hi || lo > hi || lo == INFINITY || hi == -INFINITY)
+    throw egs::Error(EGS_ERR_INVALID, "SetSliderLimits: the limits must be numbers with lo <= hi; -INFINITY / +INFINITY mean no stop");
+  s->SetLimits(lo, hi);
+}
+
+double Ensemble::SliderPosition(int index) const {
+  const auto *s = index >= 0 && index < (int)joints_.size() ? dynamic_cast<const SliderAxisJoint *>(joints_[index].get()) : nullptr;
+  if (!s) throw egs::Error(EGS_ERR_INVALID, "SliderPosition: joint " + std::to_string(index) + " is not a slider");
+  return s->Position();
 }
 
 int Ensemble::AddWeld(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &anchor_world) {
@@ -807,7 +925,7 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
     egs::check(egs_problem_set_state(problem_, pos.data(), R.data(), vl.data(), w.data(), Minv.data(), external_force_torque_.data()));
     egs::check(egs_problem_set_constraints(problem_, kind.data(), data.data()));
     bool hinges = false;
-    for (int i = 0; i < m; ++i) hinges = hinges || kind[i] == EGS_JOINT_HINGE_AXIS;
+    for (int i = 0; i < m; ++i) hinges = hinges || kind[i] == EGS_JOINT_HINGE_AXIS || kind[i] == EGS_JOINT_SLIDER_AXIS;   // (a slider's rail row likewise)
     if (hinges) {   // the joints come first in cs: their motors, then no motor for the contacts
       std::vector<double> motor;
       if (JointMotors(joints_, &motor)) {
@@ -818,6 +936,12 @@ VectorXd Ensemble::StepVelocities_ODE(double dt, const VectorXd &v, double erp) 
       if (JointLimits(joints_, &lim)) {   // likewise their limit rows, zeros for the contacts
         lim.resize(8 * (size_t)m, 0.0);
         egs::check(egs_problem_set_hinge_limits(problem_, lim.data()));
+      }
+      std::vector<double> travel;
+      if (JointTravel(joints_, &travel)) {   // ... and the sliders' stops, (-inf, +inf) for the contacts
+        travel.resize(2 * (size_t)m, INFINITY);
+        for (size_t i = joints_.size(); i < (size_t)m; ++i) travel[2 * i] = -INFINITY;
+        egs::check(egs_problem_set_slider_limits(problem_, travel.data()));
       }
     }
     if (restitution_ >= 0) {   // every contact the coefficient, every joint -1
@@ -1060,13 +1184,14 @@ bool Ensemble::StepOnDevice(double dt) {
   if (!use_device_step || use_dense_solver) return false;
   const int mj = (int)joints_.size();
   std::vector<int32_t> jb0(mj), jb1(mj), jkind(mj);
-  std::vector<double> jdata((size_t)mj * 7), jmotor, jlimit;
+  std::vector<double> jdata((size_t)mj * 7), jmotor, jlimit, jtravel;
   for (int i = 0; i < mj; ++i) {
     jb0[i] = joints_[i]->i0_; jb1[i] = joints_[i]->i1_;
     if (!joints_[i]->Describe(&jkind[i], &jdata[(size_t)i * 7])) return false;
   }
   const bool motors = JointMotors(joints_, &jmotor);
   if (!JointLimits(joints_, &jlimit)) jlimit.clear();
+  if (!JointTravel(joints_, &jtravel)) jtravel.clear();
   if (!detect_contacts && !contacts_.empty()) return false;   // caller-supplied contacts: use the explicit path
   egs_context *ctx = egs::DefaultContext();
   const bool first = !world_;
@@ -1124,6 +1249,7 @@ bool Ensemble::StepOnDevice(double dt) {
     world_jmotor_.assign(2 * (size_t)mj, 0.0);
     for (int i = 0; i < mj; ++i) world_jmotor_[2 * (size_t)i + 1] = -1.0;
     world_jlimit_.clear();   // ... and no limits
+    world_jtravel_.clear();
   }
   if (jmotor != world_jmotor_) {
     egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
@@ -1132,6 +1258,10 @@ bool Ensemble::StepOnDevice(double dt) {
   if (jlimit != world_jlimit_) {
     egs::check(egs_world_set_joint_limits(world_, jlimit.empty() ? nullptr : jlimit.data()));
     world_jlimit_ = jlimit;
+  }
+  if (jtravel != world_jtravel_) {
+    egs::check(egs_world_set_slider_limits(world_, jtravel.empty() ? nullptr : jtravel.data()));
+    world_jtravel_ = jtravel;
   }
   egs_solve_params prm = solver_params;
   prm.cfm = cfm_coeff;
@@ -1273,10 +1403,10 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   std::vector<double> pos(n * 3), R(n * 9), vl(n * 3), w(n * 3), Minv(first ? n * 36 : 0), side(first ? n * 3 : 0),
       fext(first ? n * 6 : 0);
   std::vector<int32_t> jb0, jb1, jkind;
-  std::vector<double> jdata, jmotor, jlimit;
-  bool motors = false, hinges = false, limits = false;
+  std::vector<double> jdata, jmotor, jlimit, jtravel;
+  bool motors = false, hinges = false, limits = false, travels = false;
   for (size_t i = 0; i < E; ++i)
-    for (const auto &j : members_[i]->joints_) hinges = hinges || dynamic_cast<const HingeAxisJoint *>(j.get()) != nullptr;
+    for (const auto &j : members_[i]->joints_) hinges = hinges || dynamic_cast<const HingeAxisJoint *>(j.get()) != nullptr || dynamic_cast<const SliderAxisJoint *>(j.get()) != nullptr;
   for (size_t i = 0; i < E; ++i) {
     const Ensemble *m = members_[i];
     const size_t o = (size_t)off_[i];
@@ -1316,8 +1446,11 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     jmotor.insert(jmotor.end(), own.begin(), own.end());
     limits = JointLimits(m->joints_, &own) || limits;
     jlimit.insert(jlimit.end(), own.begin(), own.end());
+    travels = JointTravel(m->joints_, &own) || travels;
+    jtravel.insert(jtravel.end(), own.begin(), own.end());
   }
   if (!limits) jlimit.clear();
+  if (!travels) jtravel.clear();
   const Ensemble *lead = members_[0];
   for (size_t i = 1; i < E; ++i)   // (the constructor's check, again: SetWarmStart may have been called since)
     if (members_[i]->warm_start_ != lead->warm_start_ || members_[i]->warm_radius_ != lead->warm_radius_)
@@ -1402,6 +1535,7 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     world_jmotor_.assign(2 * jb0.size(), 0.0);   // a new joint list has no motors
     for (size_t j = 0; j < jb0.size(); ++j) world_jmotor_[2 * j + 1] = -1.0;
     world_jlimit_.clear();   // ... and no limits
+    world_jtravel_.clear();
   }
   if (jmotor != world_jmotor_) {   // ... and the motors with them
     egs::check(egs_world_set_joint_motors(world_, motors ? jmotor.data() : nullptr));
@@ -1410,6 +1544,10 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   if (jlimit != world_jlimit_) {   // ... and the limits
     egs::check(egs_world_set_joint_limits(world_, jlimit.empty() ? nullptr : jlimit.data()));
     world_jlimit_ = jlimit;
+  }
+  if (jtravel != world_jtravel_) {   // ... and the sliders' stops
+    egs::check(egs_world_set_slider_limits(world_, jtravel.empty() ? nullptr : jtravel.data()));
+    world_jtravel_ = jtravel;
   }
   const std::vector<double> erp(E, 0.2);   // error_reduction_param of StepVelocities_ODE, as in Ensemble::Step
   if (lead->use_dense_solver) {

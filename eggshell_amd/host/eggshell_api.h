@@ -192,6 +192,44 @@ class HingeAxisJoint : public Joint {
   double limit_lo_ = -INFINITY, limit_hi_ = INFINITY;
 };
 
+// The slider block of the library (EGS_JOINT_SLIDER_AXIS; include/eggshell_amd.h has the formulas).  Beside an
+// AngularLockJoint on the same two bodies it makes a slider, a general prismatic joint (Ensemble::AddSlider).  The rail
+// is rigid in body0; with a body on side 1 it is held to body1's centre, to the world it passes through body0's
+// centre and the world point c.  ComputeError / ComputeJ follow the device's operation order.
+class SliderAxisJoint : public Joint {
+ public:
+  // axis_world: the rail direction at the bodies' current pose (any length > 0); the travel x is 0 now
+  SliderAxisJoint(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world);
+  VectorXd ComputeError() const override;                                   // (p . D, q . D, 0 or x - stop)
+  void ComputeJ(MatrixXd *J_b0, MatrixXd *J_b1, ArrayXb *constraint_type, VectorXd *constraint_lo,
+                VectorXd *constraint_hi) const override;                    // [Rn | rw], [-Rn | 0]; the rail row an inequality row
+  bool Describe(int32_t *kind, double data[7]) const override;
+  Vector3d GetConstraintPosition() const override { return Vector3d::Zero(); }
+  bool HasPosition() const override { return false; }                       // pruning stays with the ball joints
+  // the motor (egs_problem_set_motors): the solve asks for dx/dt = speed within +-max_force (+inf allowed);
+  // max_force < 0: no motor, the slider runs freely
+  void SetMotor(double speed, double max_force) { speed_ = speed; force_ = max_force; }
+  double motor_speed() const { return speed_; }
+  double motor_force() const { return force_; }
+  // The travel stops (egs_problem_set_slider_limits): x is kept within [lo, hi]; -INFINITY / +INFINITY: no stop on that
+  // side.  Past a stop the rail row is that stop's one-sided row for the step and the motor leaves it alone.
+  void SetLimits(double lo, double hi) { limit_lo_ = lo; limit_hi_ = hi; }
+  double limit_lo() const { return limit_lo_; }
+  double limit_hi() const { return limit_hi_; }
+  bool has_limits() const { return std::isfinite(limit_lo_) || std::isfinite(limit_hi_); }
+  // x now: body0's travel relative to body1 along the rail, 0 where the joint was built (the device's operations)
+  double Position() const;
+
+ private:
+  // Rn (rows p, q, s^), D and rel = p0 - P1 in the device's operation order (assemble_device.h: slider_frame)
+  void Frame(Matrix3d *Rn, Vector3d *D, Vector3d *rel) const;
+  // +1: past the upper stop, -1: past the lower, 0: neither; *err2 = x - stop
+  int ActiveStop(double *err2) const;
+  Vector3d a0_, c_;   // the unit rail direction in body0's frame; the rail's point (body0's frame; the world's for a world side)
+  double speed_ = 0.0, force_ = -1.0;
+  double limit_lo_ = -INFINITY, limit_hi_ = INFINITY;
+};
+
 struct ContactGeometry {  // collision.h:12-27
   Vector3d position, normal;
   double depth = 0;
@@ -435,6 +473,17 @@ class Ensemble {  // ensembles.h:25-186
   // use_dense_solver (EGS_ERR_UNSUPPORTED from the library).  HingeAngle: theta of that hinge now (host, atan2).
   void SetHingeLimits(int index, double lo, double hi);
   double HingeAngle(int index) const;
+  // A slider between b0 and b1 (nullptr, -1: the world) along axis_world at the current pose: an AngularLockJoint plus
+  // a SliderAxisJoint whose rail point is chosen so that the travel x is 0 now.  Returns the slider's index; call it
+  // before Init.  SetSliderMotor: dx/dt = speed within +-max_force (< 0: off).  SetSliderLimits: lo <= x <= hi,
+  // -INFINITY / +INFINITY for no stop; both reach the device with the next step and throw egs::Error(EGS_ERR_INVALID)
+  // for an index that is no slider, a NaN, an infinite speed, lo > hi, lo = +INFINITY or hi = -INFINITY.  An ensemble
+  // with a free or a stopped slider does not step with use_dense_solver (EGS_ERR_UNSUPPORTED from the library).
+  // SliderPosition: x of that slider now (host).
+  int AddSlider(std::shared_ptr<Body> b0, int i0, std::shared_ptr<Body> b1, int i1, const Vector3d &axis_world);
+  void SetSliderMotor(int index, double speed, double max_force);
+  void SetSliderLimits(int index, double lo, double hi);
+  double SliderPosition(int index) const;
   const JointsList &joints() const { return joints_; }
   double restitution() const { return restitution_; }
   double restitution_threshold() const { return restitution_vth_; }
@@ -502,6 +551,7 @@ class Ensemble {  // ensembles.h:25-186
   std::vector<int32_t> world_jkind_;             // ... their kinds and their motors ([joints][2], (0, -1): none)
   std::vector<double> world_jmotor_;
   std::vector<double> world_jlimit_;             // ... and their limit rows ([joints][8]; empty: none sent)
+  std::vector<double> world_jtravel_;            // ... and the sliders' travel stops ([joints][2]; empty: none sent)
   bool warm_start_ = false, world_warm_ = false;   // asked for; what the device world was last told
   double warm_radius_ = 0.0, world_warm_radius_ = 0.0;
   Contact::FrictionModel friction_model_ = Contact::FrictionModel::BOX;
@@ -579,6 +629,7 @@ class EnsembleGroup {
   std::vector<int32_t> world_jkind_;             // ... their kinds and their motors, re-sent with them
   std::vector<double> world_jmotor_;
   std::vector<double> world_jlimit_;             // ... and their limit rows ([joints][8]; empty: none sent)
+  std::vector<double> world_jtravel_;            // ... and the sliders' travel stops ([joints][2]; empty: none sent)
   bool world_warm_ = false;                      // what the device world was last told (the members' SetWarmStart)
   double world_warm_radius_ = 0.0;
   std::vector<double> world_friction_;           // ... and the members' friction coefficients (empty: never told)

@@ -55,6 +55,10 @@ typedef enum { EGS_JACOBI = 0, EGS_GAUSS_SEIDEL = 1, EGS_SOR = 2 } egs_method;
 typedef enum { EGS_F64 = 0, EGS_F32 = 1 } egs_precision;
 /* constraint descriptor kinds for device-side assembly */
 typedef enum { EGS_JOINT_BALL = 0, EGS_CONTACT_BOX = 1, EGS_JOINT_LOCK = 2, EGS_JOINT_HINGE_AXIS = 3 } egs_constraint_kind;
+/* ... and the slider block, a constraint kind like those four (the kind arrays are int32_t, not the enum type).  It is
+ * 5: kind 4 is no kind and never will be, it stays EGS_ERR_INVALID for ever.  The value stands beside the enum, whose
+ * four members are pinned as they are. */
+enum { EGS_JOINT_SLIDER_AXIS = 5 };
 
 /* Runtime form of the reference's compile-time constants:
  *   omega = 1.5 and max_iters = 500 (sparse_iterations.cc:15-19),
@@ -346,6 +350,43 @@ egs_status egs_problem_set_motors(egs_problem *p, const double *motor /*[m][2] o
  *      entry; for a hinge with a stop a q that is not a unit quaternion within 1e-12, a pair that is neither (0, 0) nor on
  *      the unit circle within 1e-12, a stop at +-pi (1 + cos <= 0), lo above hi in the half-angle order.              */
 egs_status egs_problem_set_hinge_limits(egs_problem *p, const double *lim /*[m][8] or NULL = off*/);
+
+/* ---- Slider joints: EGS_JOINT_SLIDER_AXIS = 5 (4 stays invalid for ever).  A slider is LOCK + SLIDER_AXIS on the same
+ *      two bodies, as a hinge is BALL + HINGE_AXIS; with the lock holding the relative orientation it is a general
+ *      prismatic joint.  data = (a0[3], c[3], 0): a0 the unit rail direction in body0's frame; body0 must be a body.
+ *      With body1 a body, c is a point of the rail in body0's frame and the rail's target point is body1's centre,
+ *      P1 = pos[b1].  With body1 = -1 (the world), c is the world point the rail passes through, P1 = c, and the rail
+ *      passes through body0's centre.  Assembled in fp64 without contraction and without a trigonometric function, in
+ *      this order (mv3, align_to_z, crossmat, mm3, d3: assemble_device.h):
+ *          s = mv3(R0, a0);  Rn = align_to_z(s), rows (p, q, s^)
+ *          two bodies:  ro = mv3(R0, c);  D[k] = (p0[k] + ro[k]) - P1[k]
+ *          world side:                    D[k] =  p0[k] - c[k]
+ *          rel[k] = p0[k] - P1[k];  rw = mm3(Rn, crossmat(rel))             row r is (P1 - p0) x Rn_r
+ *          J0 = [Rn | rw],  J1 = [-1.0*Rn | 0] (all zero for a world side)
+ *          err = (d3(p, D), d3(q, D), 0)
+ *      Rows 0 and 1 are equality rows.  Row 2, the rail row, is an inequality row with lo = hi = 0: its multiplier is
+ *      pinned at 0 and the slider runs freely, as a free hinge's axis row.  d err/dt = J0 s0 + J1 s1 at err = 0 for rows 0
+ *      and 1; for the travel x = d3(s^, D) it holds at every pose (s is rigid in body0 and body1 enters through its
+ *      centre only).  The lever arm sits on body0 alone: J0^T lambda and J1^T lambda carry no net force and no net torque.
+ *      Motor: egs_problem_set_motors applies to the rail row as to a hinge's axis row: (speed, f) with f >= 0 gives
+ *      lo[2] = -f, hi[2] = +f, rhs[2] = speed / dt - ju, speed = dx/dt, body0's travel relative to body1 along s^.
+ *      Travel stops: lim [m][2] = (xlo, xhi), fp64, -inf / +inf: no stop on that side; rows of other kinds are ignored.
+ *      After the block is formed, its bits kept:
+ *          xhi finite and x > xhi:       err[2] = x - xhi;  lo[2] = -inf;  hi[2] = 0
+ *          else xlo finite and x < xlo:  err[2] = x - xlo;  lo[2] = 0;     hi[2] = +inf
+ *          else: row 2 as without the table
+ *      rhs[2] stays the ordinary kk err[2] - ju and is_eq[2] stays 0: the sign convention of the hinge stops, lambda <= 0
+ *      at the upper stop.  While a stop is active the motor leaves the row alone for that step.  lim = NULL, or no slider
+ *      with a finite stop, turns the stops off: every result and schedule flag is then what it is without this call.  A
+ *      new topology or a new egs_problem_set_constraints turns them off.  EGS_ERR_INVALID (nothing changes): a NaN
+ *      anywhere in the table; on a slider row xlo = +inf, xhi = -inf or xlo > xhi.  egs_problem_set_constraints refuses
+ *      a slider with body0 < 0, a non-finite number among its seven, or an a0 that is no unit vector within 1e-12.
+ *      A list that holds a slider runs none of EGS_SCHED_LINSYM, FUSED_ASSEMBLY, PAIR, CHAIN, SHARE, FACE (its J1 is not
+ *      -J0); friction (coefficient -1), restitution and warm start treat it as any joint.  The stabilise passes of a
+ *      world take an active stop as one more row of (J J^T) y = err and an inactive rail row as a free hinge's axis row.
+ *      The dense steps take a motored rail row with f > 0 as a box row (use_bounds bit 0) and return
+ *      EGS_ERR_UNSUPPORTED, naming the constraint, for a free slider (pinned row) and for any slider with a finite stop. */
+egs_status egs_problem_set_slider_limits(egs_problem *p, const double *lim /*[m][2] or NULL = off*/);
 
 /* ---- the matrix-free products: replace sparse::CalculateSparse{JMJtX,Lx,Ux,
  *      LxUx,Dx,UxDx,LxDx}(const ConstraintsList&, const MatrixXd& M_inverse,
@@ -692,7 +733,7 @@ egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape);
 /* ball joints: body0/body1 [m], data [m][7] = c0, c1 (world point if body1 = -1), 0 */
 egs_status egs_world_set_joints(egs_world *w, int32_t m_joints, const int32_t *body0, const int32_t *body1,
                                 const double *data);
-/* ... of any joint kind (EGS_JOINT_BALL, EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS; data as egs_problem_set_constraints
+/* ... of any joint kind (EGS_JOINT_BALL, EGS_JOINT_LOCK, EGS_JOINT_HINGE_AXIS, EGS_JOINT_SLIDER_AXIS; data as egs_problem_set_constraints
  * takes it, checked the same way).  kind = NULL, or all EGS_JOINT_BALL, is egs_world_set_joints bit for bit.  Only the
  * ball joints take part in the joint-versus-contact pruning of the collider: an angular block has no position.  The
  * batch rules are those of egs_world_set_joints.  Drops the motors of an earlier list.                          */
@@ -707,6 +748,11 @@ egs_status egs_world_set_joint_motors(egs_world *w, const double *motor /*[m_joi
  * row of their system; the dense steps return EGS_ERR_UNSUPPORTED while a hinge has a stop.  egs_world_set_joints[_kinds]
  * drops it.  EGS_ERR_INVALID as egs_problem_set_hinge_limits (nothing changes).                                  */
 egs_status egs_world_set_joint_limits(egs_world *w, const double *lim /*[m_joints][8] or NULL = off*/);
+/* egs_problem_set_slider_limits for the world's joints: lim [m_joints][2] = (xlo, xhi), NULL = off.  Every step's
+ * assembly carries it, re-planned lists included; the stabilise entries take an active stop as a row of their system;
+ * the dense steps return EGS_ERR_UNSUPPORTED while a slider has a finite stop.  egs_world_set_joints[_kinds] drops it.
+ * EGS_ERR_INVALID as egs_problem_set_slider_limits (nothing changes).                                            */
+egs_status egs_world_set_slider_limits(egs_world *w, const double *lim /*[m_joints][2] or NULL = off*/);
 egs_status egs_world_step(egs_world *w, double dt, double erp, const egs_solve_params *params,
                           int32_t detect_contacts, egs_solve_stats *stats);
 egs_status egs_world_get_bodies(egs_world *w, double *pos, double *R, double *v, double *w_ang);
