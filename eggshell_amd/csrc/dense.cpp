@@ -67,7 +67,7 @@ void fresh_staging(egs_context *ctx) {
   ctx->pinned.reset();
 }
 
-// the rule of the single entry's symmetry check (dense_lcp.hip)
+// the rule of the single entry's symmetry check (dense_mixed_impl, dense_lcp.hip)
 bool symmetric_enough(const double *A, int n) {
   double amax = 0.0, asym = 0.0;
   for (int i = 1; i < n; ++i)

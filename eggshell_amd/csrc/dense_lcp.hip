@@ -1,480 +1,25 @@
-// dense_lcp.hip -- dense direct LCP for gfx950: the reference's
-// Lcp::MixedConstraintsSolver (lcp.cc:276-336) and Lcp::MurtyPrincipalPivot
-// (lcp.cc:157-274) with the O(n^3) pieces on the GPU.
-//
-// Structure (all matrices row-major fp64, resident in HBM for the whole call):
-//   * One routine does every factorisation: a blocked right-looking Cholesky of
-//     the first `nf` columns of a lower-trapezoid T (extra rows below the square
-//     part ride along).  Per 64-column block: chol_diag_kernel (diagonal block
-//     and its inverse, in registers), chol_trsm_kernel (panel below = B L11^-T
-//     as a matrix product) and chol_update_kernel (trailing T -= P P^T), the
-//     last two on the fp64 matrix cores (v_mfma_f64_16x16x4_f64).
-//   * MixedConstraintsSolver: permute to [E | I], append b as a last row and
-//     factor only the E columns: the trailing block IS the Schur complement
-//     A_ii - A_ie A_ee^-1 A_ei, the trailing part of the b row IS
-//     b_i - A_ie A_ee^-1 b_e, and the b row's E part is L^-1 b_e (lcp.cc:286-294).
-//   * Murty: the reference's single-index principal pivoting verbatim -- S
-//     starts all-true, x = 0, w = -b; each iteration flips the FIRST offending
-//     index (lcp.cc:36-62) and re-solves A(S,S) x_S = b_S from scratch
-//     (lcp.cc:202-203): gather + Cholesky + back substitution on the device;
-//     the flip decision, best-solution memory (lcp.cc:105-137) and the
-//     iteration cap min(1000, 2^dim) (lcp.cc:168) are evaluated per pivot from
-//     a 64-byte record read back from the device.  Up to 112 rows the whole
-//     loop runs in one workgroup instead (murty_small_kernel).
-// The reference factors with Eigen's pivoted LDLT / LU inverse; A is required
-// to be symmetric with positive definite A_ee and A(S,S) (true for J M^-1 J^T
-// + cfm I and for the reference's own tests); otherwise the call reports
-// failure instead of a wrong answer.
-#include "dense_lcp.h"
-#include "runtime.h"
+// dense_lcp.hip -- the two dense direct solvers of the reference with the O(n^3) pieces on the GPU:
+// Lcp::MixedConstraintsSolver (lcp.cc:276-336) and lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747).  All matrices
+// row-major fp64, resident in HBM for the whole call.
+//   * Both permute to [E | I], append b as a last row and factor only the E columns (SchurStage): the trailing block IS
+//     the Schur complement A_ii - A_ie A_ee^-1 A_ei, the trailing part of the b row IS b_i - A_ie A_ee^-1 b_e, and the
+//     b row's E part is L^-1 b_e (lcp.cc:286-294).
+//   * The factorisation and the solves with its factor are dense_factor.hip's; the reduced LCP goes to the Murty pivot
+//     loop of dense_murty.hip or, in SolveLCP_BoxSchur up to kIncrementalMaxRows bounded rows, to dantzig.hip.
+// The reference factors with Eigen's pivoted LDLT / LU inverse; A is required to be symmetric with positive definite
+// A_ee and A(S,S) (true for J M^-1 J^T + cfm I and for the reference's own tests); otherwise the call reports failure
+// instead of a wrong answer.
+#include "dense_internal.h"
 
 #include <algorithm>
 #include <chrono>
-#include <cmath>
-#include <cstdlib>
 #include <cstdio>
-#include <cstring>
-#include <functional>
 #include <limits>
 #include <stdexcept>
-#include <string>
-#include <vector>
 
 namespace egs {
 
 namespace {
-
-constexpr int NB = 64;    // block size = wavefront size
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// ---- blocked Cholesky ------------------------------------------------------
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-
-// 1 / sqrt(d) to within an ulp or two: hardware estimate y, e = 1 - d y^2, then
-// y (1 + e/2 + 3 e^2 / 8) (cubic convergence, one short dependent chain).
-__device__ __forceinline__ double rsqrt_refined(double d) {
-  const double y = __builtin_amdgcn_rsq(d);
-  const double e = __builtin_fma(-d * y, y, 1.0);
-  const double t = __builtin_fma(0.375, e, 0.5) * e;
-  return __builtin_fma(y, t, y);
-}
-
-// Workgroup barrier that orders LDS traffic only (__syncthreads() also drains vmcnt, i.e. waits for the
-// acknowledgement of the global stores in flight; the column loop below stores one finished column per
-// step and has no reason to wait for it).
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// ---- the diagonal tile ------------------------------------------------------------------------------------
-// L11 = chol(tile) and its inverse for a 64 x 64 tile staged in LDS, one workgroup of five wavefronts.  This is the
-// latency chain of the whole factorisation (one tile per 64 columns, nothing else can start before it ends), so it is
-// built for few dependent steps rather than for throughput (tools/diag_bench.hip times the variants: 23.4 us for the
-// round-2 routine -- one barrier per column, the inverse accumulated by a fifth wavefront with 63 - j multiply-adds
-// per column -- against 12.9 us for this one):
-//   * wavefronts 0..3, lane i = row i; wavefront w holds the four-column groups g = 4 m + w (16 registers).  The
-//     owner of group g reads the 4 x 4 diagonal mini-block out of its lanes once (readlane -> scalar registers),
-//     factors it redundantly in every lane and solves its own row against it: no cross-lane traffic inside the four
-//     columns.  The four columns go to LDS (column-major sL, every column in its own place: no double buffer), ONE
-//     barrier per group, and every wavefront applies the rank-4 update to the groups it holds -- the factored ones too
-//     (dead registers; the code stays free of wavefront-dependent branches).  Entries above the diagonal are scratch:
-//     nothing masks them and nothing reads them.
-//   * wavefront 4, lane c < 16 = column c of the inverse of the current 16 x 16 diagonal block: forward substitution
-//     row by row as the columns appear (15 - r multiply-adds per row, in the shadow of the column chain).
-//   * afterwards the rest of the inverse by products on the fp64 matrix cores: X(2p+1, 2p) = -X(2p+1, 2p+1) L(2p+1, 2p)
-//     X(2p, 2p) for the two 32 x 32 diagonal blocks, then the 32 x 32 block below them the same way.
-//   * L (lower triangle) and the inverse (all of it: zero above the diagonal) go to memory at the end, rows coalesced.
-// The inverse turns the panel's triangular solve and the diagonal steps of the back substitution into matrix
-// products (chol_trsm_kernel, chol_panel_kernel, back_solve_kernel).
-constexpr int kTileLs = NB + 2;      // column stride of sL / row stride of sX (doubles)
-constexpr int kTileQs = 34;          // row stride of the 32 x 32 scratch
-constexpr int kTileLdsDoubles = 2 * NB * kTileLs + 32 * kTileQs + NB;      // sL, sX, sQ, sRv
-
-__device__ __forceinline__ double4_t mfma_f64(double a, double b, double4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-
-// sB: the tile, row-major with row stride ldb.  sL, sX: NB * kTileLs doubles each; sQ: 32 * kTileQs; sRv: NB.
-// Tout / inv: where L (row stride ld, tile origin already applied) and the inverse (64 x 64, dense) go.
-__device__ __forceinline__ void chol_diag_tile(const double *sB, int ldb, double *sL, double *sX, double *sQ, double *sRv, double *Tout,
-                                               int ld, double *inv, int *fail) {
-  constexpr int GW = 4, NG = NB / GW, MG = NG / 4, LS = kTileLs, XS = kTileLs, QS = kTileQs;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < NB * XS; i += blockDim.x) sX[i] = 0.0;      // the inverse is zero above its diagonal blocks
-  if (wave < 4) {
-    double a[MG][GW];
-#pragma unroll
-    for (int m = 0; m < MG; ++m)
-#pragma unroll
-      for (int q = 0; q < GW; ++q) a[m][q] = sB[lane * ldb + GW * (4 * m + wave) + q];
-    bool bad = false;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int mo = g >> 2, c0 = GW * g;
-      if (wave == (g & 3)) {
-        // the mini-block's lower triangle, m[r][c] from lane c0 + r
-        const double m00 = readlane_f64(a[mo][0], c0);
-        const double m10 = readlane_f64(a[mo][0], c0 + 1), m11 = readlane_f64(a[mo][1], c0 + 1);
-        const double m20 = readlane_f64(a[mo][0], c0 + 2), m21 = readlane_f64(a[mo][1], c0 + 2), m22 = readlane_f64(a[mo][2], c0 + 2);
-        const double m30 = readlane_f64(a[mo][0], c0 + 3), m31 = readlane_f64(a[mo][1], c0 + 3), m32 = readlane_f64(a[mo][2], c0 + 3),
-                     m33 = readlane_f64(a[mo][3], c0 + 3);
-        const double r0 = rsqrt_refined(m00);
-        const double x0 = a[mo][0] * r0;
-        const double l10 = m10 * r0, l20 = m20 * r0, l30 = m30 * r0;
-        const double d1 = __builtin_fma(-l10, l10, m11);
-        const double r1 = rsqrt_refined(d1);
-        const double x1 = __builtin_fma(-x0, l10, a[mo][1]) * r1;
-        const double l21 = __builtin_fma(-l20, l10, m21) * r1, l31 = __builtin_fma(-l30, l10, m31) * r1;
-        const double d2 = __builtin_fma(-l21, l21, __builtin_fma(-l20, l20, m22));
-        const double r2 = rsqrt_refined(d2);
-        const double x2 = __builtin_fma(-x1, l21, __builtin_fma(-x0, l20, a[mo][2])) * r2;
-        const double l32 = __builtin_fma(-l31, l21, __builtin_fma(-l30, l20, m32)) * r2;
-        const double d3 = __builtin_fma(-l32, l32, __builtin_fma(-l31, l31, __builtin_fma(-l30, l30, m33)));
-        const double r3 = rsqrt_refined(d3);
-        const double x3 = __builtin_fma(-x2, l32, __builtin_fma(-x1, l31, __builtin_fma(-x0, l30, a[mo][3]))) * r3;
-        bad |= !(m00 > 0.0) | !(d1 > 0.0) | !(d2 > 0.0) | !(d3 > 0.0);
-        sL[(c0 + 0) * LS + lane] = x0; sL[(c0 + 1) * LS + lane] = x1; sL[(c0 + 2) * LS + lane] = x2; sL[(c0 + 3) * LS + lane] = x3;
-        if (lane == 0) { sRv[c0] = r0; sRv[c0 + 1] = r1; sRv[c0 + 2] = r2; sRv[c0 + 3] = r3; }
-      }
-      lds_barrier();
-      if (g + 1 < NG) {
-        double lrow[GW];
-#pragma unroll
-        for (int q = 0; q < GW; ++q) lrow[q] = sL[(c0 + q) * LS + lane];
-#pragma unroll
-        for (int m = mo; m < MG; ++m) {
-          const int cg = GW * (4 * m + wave);
-#pragma unroll
-          for (int q2 = 0; q2 < GW; ++q2) {
-            double acc = a[m][q2];
-#pragma unroll
-            for (int q = 0; q < GW; ++q) acc = __builtin_fma(-lrow[q], sL[(c0 + q) * LS + cg + q2], acc);
-            a[m][q2] = acc;
-          }
-        }
-      }
-    }
-    if (bad && lane == 0) atomicOr(fail, 1);
-  } else {
-    double acc[16];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      lds_barrier();
-#pragma unroll
-      for (int q = 0; q < GW; ++q) {
-        const int R = GW * g + q, b = R >> 4, r = R & 15;
-        if (r == 0) {
-#pragma unroll
-          for (int k = 0; k < 16; ++k) acc[k] = 0.0;
-        }
-        if (lane < 16) {
-          const double x = (((lane == r) ? 1.0 : 0.0) - acc[r]) * sRv[R];      // lanes c > r: exactly 0
-          sX[R * XS + 16 * b + lane] = x;
-#pragma unroll
-          for (int k2 = r + 1; k2 < 16; ++k2) acc[k2] = __builtin_fma(sL[R * LS + 16 * b + k2], x, acc[k2]);
-        }
-      }
-    }
-  }
-  lds_barrier();
-  // v_mfma_f64_16x16x4_f64 operand maps: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15]; D: col = lane&15, row = (lane>>4) + 4 reg
-  const int li = lane & 15, lk = lane >> 4;
-  if (wave < 2) {      // X(2p+1, 2p) = -X(2p+1, 2p+1) (L(2p+1, 2p) X(2p, 2p)), p = wave
-    const int o = 32 * wave;
-    double4_t P = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) P = mfma_f64(sL[(o + 4 * kk + lk) * LS + o + 16 + li], sX[(o + 4 * kk + lk) * XS + o + li], P);
-    double *sP = sQ + wave * 16 * QS;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) sP[(lk + 4 * reg) * QS + li] = P[reg];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    double4_t D = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) D = mfma_f64(sX[(o + 16 + li) * XS + o + 16 + 4 * kk + lk], sP[(4 * kk + lk) * QS + li], D);
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) sX[(o + 16 + lk + 4 * reg) * XS + o + li] = -D[reg];
-  }
-  lds_barrier();
-  // X_BL = -X_BR (L_BL X_TL) on the 32 x 32 blocks, one 16 x 16 tile per wavefront
-  if (wave < 4) {
-    const int ti = wave >> 1, tj = wave & 1;
-    double4_t Q = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) Q = mfma_f64(sL[(4 * kk + lk) * LS + 32 + 16 * ti + li], sX[(4 * kk + lk) * XS + 16 * tj + li], Q);
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) sQ[(16 * ti + lk + 4 * reg) * QS + 16 * tj + li] = Q[reg];
-  }
-  lds_barrier();
-  if (wave < 4) {
-    const int ti = wave >> 1, tj = wave & 1;
-    double4_t D = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) D = mfma_f64(sX[(32 + 16 * ti + li) * XS + 32 + 4 * kk + lk], sQ[(4 * kk + lk) * QS + 16 * tj + li], D);
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) sX[(32 + 16 * ti + lk + 4 * reg) * XS + 16 * tj + li] = -D[reg];
-  }
-  lds_barrier();
-  for (int i = threadIdx.x; i < NB * NB; i += blockDim.x) {
-    const int r = i >> 6, c = i & 63;
-    inv[i] = sX[r * XS + c];
-    if (c <= r) Tout[(size_t)r * ld + c] = sL[c * LS + r];
-  }
-}
-
-constexpr int kDiagThreads = 320;
-constexpr size_t kDiagLdsBytes = (size_t)(NB * (NB + 2) + kTileLdsDoubles) * sizeof(double);
-
-// The tile at (k0, k0) of T: L to Tout (same place), the inverse to inv.
-__global__ void __launch_bounds__(kDiagThreads) chol_diag_kernel(const double *T, double *Tout, int ld, int k0, double *inv, int *fail) {
-  extern __shared__ __attribute__((aligned(16))) double smem_d[];
-  double *sB = smem_d, *sL = sB + NB * (NB + 2), *sX = sL + NB * kTileLs, *sQ = sX + NB * kTileLs, *sRv = sQ + 32 * kTileQs;
-  for (int i = threadIdx.x; i < NB * NB; i += blockDim.x) {
-    const int r = i >> 6, c = i & 63;
-    sB[r * (NB + 2) + c] = T[(size_t)(k0 + r) * ld + k0 + c];
-  }
-  __syncthreads();
-  chol_diag_tile(sB, NB + 2, sL, sX, sQ, sRv, Tout + (size_t)k0 * ld + k0, ld, inv, fail);
-}
-
-// A 64 x 64 block of doubles from global memory (row stride ld) into LDS (row stride kStageLd) with 16-byte loads, all
-// of a thread's eight loads in flight at once: one memory round trip per operand instead of one per k-step of the MFMA
-// loop.  Rows at or beyond `nrows` read as zero.  Threads 0..255: thread t takes row t / 4, columns 16 (t % 4) .. + 15.
-constexpr int kStageLd = NB + 2;     // doubles; keeps 16-byte alignment of every row start
-typedef double double2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void stage_block(const double *src, int ld, int row0, int nrows, double *dst) {
-  if (threadIdx.x >= 256) return;
-  const int r = threadIdx.x >> 2, c = (threadIdx.x & 3) * 16;
-  const bool ok = row0 + r < nrows;
-  const double *p = src + (size_t)(ok ? row0 + r : 0) * ld + c;
-  double v[16];
-  if ((((size_t)p) & 15) == 0) {
-    double2_t q[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) q[k] = ok ? *reinterpret_cast<const double2_t *>(p + 2 * k) : (double2_t){0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[2 * k] = q[k].x; v[2 * k + 1] = q[k].y; }
-  } else {          // an odd leading dimension leaves rows 8-byte aligned only
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = ok ? p[k] : 0.0;
-  }
-  double *d = dst + r * kStageLd + c;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) *reinterpret_cast<double2_t *>(d + 2 * k) = (double2_t){v[2 * k], v[2 * k + 1]};
-}
-
-// acc[ti][tj] += (rows lr.. of sA) (rows lc.. of sB)^T over K = 64: the 32 x 32 quadrant of one wavefront.
-// v_mfma_f64_16x16x4_f64 operand maps: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15];
-// D: col = lane&15, row = (lane>>4) + 4*reg.
-__device__ __forceinline__ void mfma_quadrant(const double *sA, const double *sB, int lr, int lc, double4_t (&acc)[2][2]) {
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-  for (int kk = 0; kk < NB / 4; ++kk) {
-    double a[2], b[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      a[t] = sA[(lr + 16 * t + li) * kStageLd + 4 * kk + lk];
-      b[t] = sB[(lc + 16 * t + li) * kStageLd + 4 * kk + lk];
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-        acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[tj], acc[ti][tj], 0, 0, 0);
-  }
-}
-
-// Panel below the diagonal block: X = B L11^-T = B (L11^-1)^T on the fp64 matrix
-// cores, X[r][c] = sum_k B[r][k] Linv[c][k].  One workgroup per 64-row slab,
-// each wavefront a 32x32 quadrant; both operands staged in LDS.  B is read from T, X goes to Tout (may be T).
-__global__ void __launch_bounds__(256) chol_trsm_kernel(const double *T, double *Tout, int ld, int nrows, int k0, const double *inv, int ibase, int iend) {
-  __shared__ __attribute__((aligned(16))) double sA[NB * kStageLd], sBm[NB * kStageLd];
-  const int r0 = k0 + NB + blockIdx.x * NB;
-  if (r0 >= ibase && r0 < iend && r0 - ibase >= k0 + NB) return;      // identity rows that no panel has reached yet (see factor())
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int lr = (wave >> 1) * 32, lc = (wave & 1) * 32;
-  const int li = lane & 15, lk = lane >> 4;
-  stage_block(T + k0, ld, r0, nrows, sA);
-  stage_block(inv, NB, 0, NB, sBm);
-  double4_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  __syncthreads();
-  mfma_quadrant(sA, sBm, lr, lc, acc);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = r0 + lr + 16 * ti + lk + 4 * reg, c = lc + 16 * tj + li;
-        if (r < nrows) Tout[(size_t)r * ld + k0 + c] = acc[ti][tj][reg];
-      }
-}
-
-// Trailing update on the fp64 matrix cores: for rows r >= k0+64 and columns
-// c in [k0+64, ld) with c <= r (lower trapezoid),  T[r][c] -= sum_k P[r][k] P[c][k],
-// P = T[:, k0..k0+64).  One workgroup (4 wavefronts) per 64x64 tile; each
-// wavefront owns a 32x32 quadrant = 2x2 MFMA tiles, K = 64 in 16 steps of 4; the two 64 x 64 pieces of the panel are
-// staged in LDS first (stage_block).
-__global__ void __launch_bounds__(256) chol_update_kernel(double *T, int ld, int nrows, int k0) {
-  __shared__ __attribute__((aligned(16))) double sA[NB * kStageLd], sBm[NB * kStageLd];
-  const int r0 = k0 + NB + blockIdx.y * NB;
-  const int c0 = k0 + NB + blockIdx.x * NB;
-  if (c0 > r0 + NB - 1) return;  // tile entirely above the diagonal
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int lr = (wave >> 1) * 32, lc = (wave & 1) * 32;
-  const int qr = r0 + lr, qc = c0 + lc;
-  const int li = lane & 15, lk = lane >> 4;
-  double4_t acc[2][2], told[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  // the tile's old values, requested before the operands: the final T -= acc costs no second round trip
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = qr + 16 * ti + lk + 4 * reg, c = qc + 16 * tj + li;
-        told[ti][tj][reg] = (r < nrows && c < ld && c <= r) ? T[(size_t)r * ld + c] : 0.0;
-      }
-  const bool diag = r0 == c0;
-  stage_block(T + k0, ld, r0, nrows, sA);
-  if (!diag) stage_block(T + k0, ld, c0, nrows < ld ? nrows : ld, sBm);     // rows of the panel that are columns of the tile
-  __syncthreads();
-  mfma_quadrant(sA, diag ? sA : sBm, lr, lc, acc);
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int r = qr + 16 * ti + lk + 4 * reg, c = qc + 16 * tj + li;
-        if (r < nrows && c < ld && c <= r) T[(size_t)r * ld + c] = told[ti][tj][reg] - acc[ti][tj][reg];
-      }
-}
-
-// Solve L^T x = y in one workgroup: L = T[0..nf)[0..nf) lower, y = T[yrow][0..nf),
-// inv = the L_kk^-1 blocks chol_diag_kernel left behind.  Blocks from the last to
-// the first: x_k = L_kk^-T t_k is a 64x64 product with the stored inverse, then
-// the 64-row strip L[k-block][0..k) (contiguous rows, coalesced) is subtracted
-// from the remaining right-hand side.
-// x is written to out[map ? map[i] : i] for i < nreal (padding rows dropped).
-// XS_LDS: the running right-hand side lives in LDS (nf <= kBackSolveLdsRows) instead of global scratch -- every block
-// step reads and rewrites it, and a workgroup-visible global round trip costs a microsecond each way.
-constexpr int kBackSolveLdsRows = 16384;
-template <bool XS_LDS>
-__global__ void __launch_bounds__(1024) back_solve_kernel(const double *T, int ld, int nf, int yrow, int nreal,
-                                                          const int *map, double *out, double *xs_global /*[nf] scratch*/,
-                                                          const double *inv) {
-  extern __shared__ __attribute__((aligned(16))) double xs_lds[];
-  double *xs = XS_LDS ? xs_lds : xs_global;
-  __shared__ double sx[NB];
-  __shared__ double red[16][NB];
-  __shared__ double redB[1024];
-  const int tid = threadIdx.x;
-  // with the right-hand side in LDS nothing a step exchanges goes through memory: a barrier that orders LDS only lets
-  // the loads requested ahead (next strip, next inverse block) stay in flight across it
-  auto step_barrier = [] { if (XS_LDS) lds_barrier(); else __syncthreads(); };
-  for (int i = tid; i < nf; i += 1024) xs[i] = T[(size_t)yrow * ld + i];
-  __syncthreads();
-  // thread (i, part) of the 64 x 16 layout multiplies rows part, part+16, ... of the inverse block;
-  // its four entries for the NEXT block are requested before this block's strip update
-  const int i = tid & 63, part = tid >> 6;
-  double li[4];
-  {
-    const double *Li = inv + (size_t)((nf - NB) / NB) * NB * NB;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) li[q] = nf >= NB ? Li[(part + 16 * q) * NB + i] : 0.0;
-  }
-  for (int kb = nf - NB; kb >= 0; kb -= NB) {
-    // The strip L[kb .. kb+64)[0 .. kb) is subtracted from the kb open entries by P threads per column (P rows-parts of
-    // R = 64 / P rows, as many as 1024 threads allow); its entries do not depend on x_k, so they are requested now and
-    // arrive while x_k = L_kk^-T t_k is formed.
-    int P = kb > 0 ? 1024 / kb : 0;      // (0 only for kb = 0: more than 1024 open columns is P = 1 plus the tail loop below)
-    P = P >= 16 ? 16 : P >= 8 ? 8 : P >= 4 ? 4 : P >= 2 ? 2 : (kb > 0 ? 1 : 0);
-    const int R = P ? NB / P : 0;
-    const bool active = P > 0 && tid < P * kb;
-    const int c = active ? tid % kb : 0, rp = active ? tid / kb : 0;
-    double lv[32];
-    const double *strip = T + (size_t)(kb + rp * R) * ld + c;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) lv[j] = (active && j < R) ? strip[(size_t)j * ld] : 0.0;
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s = __builtin_fma(li[q], xs[kb + part + 16 * q], s);   // Linv[r][i] = 0 for i > r
-    red[part][i] = s;
-    if (kb >= NB) {
-      const double *Ln = inv + (size_t)(kb / NB - 1) * NB * NB;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) li[q] = Ln[(part + 16 * q) * NB + i];
-    }
-    step_barrier();
-    if (tid < NB) {
-      double x = 0.0;
-#pragma unroll
-      for (int p = 0; p < 16; ++p) x += red[p][tid];
-      sx[tid] = x;
-      xs[kb + tid] = x;
-    }
-    step_barrier();
-    if (P == 0) continue;      // (kb == 0: nothing left to update; uniform)
-    double u = 0.0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) if (j < R) u = __builtin_fma(lv[j], sx[rp * R + j], u);
-    if (P == 1) {             // more than 512 open columns: one thread per column, the second half of its 64 rows now
-      if (active) {
-#pragma unroll
-        for (int j = 0; j < 32; ++j) lv[j] = strip[(size_t)(32 + j) * ld];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) u = __builtin_fma(lv[j], sx[32 + j], u);
-        xs[c] -= u;
-      }
-      for (int c2 = tid + 1024; c2 < kb; c2 += 1024) {      // (more than 1024 open columns)
-        double y = 0.0;
-#pragma unroll 32
-        for (int r = 0; r < NB; ++r) y = __builtin_fma(T[(size_t)(kb + r) * ld + c2], sx[r], y);
-        xs[c2] -= y;
-      }
-    } else {
-      if (active) redB[rp * kb + c] = u;
-      step_barrier();
-      if (tid < kb) {
-        double y = 0.0;
-        for (int p = 0; p < P; ++p) y += redB[p * kb + tid];
-        xs[tid] -= y;
-      }
-    }
-    step_barrier();
-  }
-  for (int i = tid; i < nreal; i += 1024) out[map ? map[i] : i] = xs[i];
-}
-
-void launch_back_solve(DenseWorkspace &ws, const double *T, int ld, int nf, int yrow, int nreal, const int *map, double *out, double *xs,
-                       const double *inv) {
-  hipStream_t s = ws.stream;
-  if (nf <= kBackSolveLdsRows) {
-    if (!ws.back_solve_lds) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(back_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(kBackSolveLdsRows * sizeof(double))));
-      ws.back_solve_lds = true;
-    }
-    hipLaunchKernelGGL(back_solve_kernel<true>, dim3(1), dim3(1024), (size_t)nf * sizeof(double), s, T, ld, nf, yrow, nreal, map, out, xs, inv);
-  } else {
-    hipLaunchKernelGGL(back_solve_kernel<false>, dim3(1), dim3(1024), 0, s, T, ld, nf, yrow, nreal, map, out, xs, inv);
-  }
-}
 
 // max |a_ij| and max |a_ij - a_ji| over i > j (non-negative doubles order like
 // their bit patterns, so an integer atomicMax does the reduction).
@@ -548,59 +93,6 @@ __global__ void extract_schur_kernel(const double *T, int nepad, int ni, double 
   }
 }
 
-// Pivot trapezoid: A(S,S) padded with an identity block; then nspad identity rows (they become L^-T, see factor());
-// b_eff(S) as last row.
-__global__ void build_pivot_kernel(const double *lhs, int n, const int *S, int ns, int nspad, const double *beff,
-                                   double *T, int identity_rows, int *pos0, int *idx0) {
-  const int ld = nspad, ib = identity_rows ? nspad : 0, rows = nspad + ib + 1;
-  if (pos0) {      // this set becomes the base of the bordered pivots (murty_advance_kernel validates pos0 through idx0)
-    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < (size_t)ns) { pos0[S[k]] = (int)k; idx0[k] = S[k]; }
-  }
-  const size_t total = (size_t)rows * ld;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(idx / ld), c = (int)(idx % ld);
-    double v = 0.0;
-    if (r < ns) { if (c < ns) v = lhs[(size_t)S[r] * n + S[c]]; }
-    else if (r < nspad) v = (c == r) ? 1.0 : 0.0;
-    else if (r < nspad + ib) v = (c == r - nspad) ? 1.0 : 0.0;
-    else { if (c < ns) v = beff[S[c]]; }
-    T[idx] = v;
-  }
-}
-
-// x = L^-T z from the rows the factorisation turned into L^-T (factor(), ibase): x_i = sum_{c >= i} Linvt[i][c] z[c],
-// z = L^-1 b.  One wavefront per row; x goes to out[map ? map[i] : i] for i < nreal.
-// keep: rows whose map[row] has keep == 0 are not written (indexes that left the set since the factorisation).
-__global__ void __launch_bounds__(256) inverse_rows_solve_kernel(const double *T, int ld, int nf, int ibase, const double *z, int nreal,
-                                                                 const int *map, double *out, const uint8_t *keep) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= nreal) return;
-  if (keep && !keep[map[row]]) return;
-  const double *Li = T + (size_t)(ibase + row) * ld;
-  double s0 = 0.0, s1 = 0.0;
-  int c = (row & ~63) + lane;      // whole 64-column groups from the one that holds the diagonal
-  for (; c + 64 < nf; c += 128) {
-    s0 = __builtin_fma(c >= row ? Li[c] : 0.0, z[c], s0);
-    s1 = __builtin_fma(Li[c + 64], z[c + 64], s1);
-  }
-  if (c < nf) s0 = __builtin_fma(c >= row ? Li[c] : 0.0, z[c], s0);
-  double sum = s0 + s1;
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-  if (lane == 0) out[map ? map[row] : row] = sum;
-}
-
-// out = M v - sub  (row-major M n x n): one wavefront per row.
-__global__ void __launch_bounds__(256) gemv_minus_kernel(const double *M, int n, const double *v, const double *sub,
-                                                         double *out) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  double s = 0.0;
-  for (int c = lane; c < n; c += 64) s = __builtin_fma(M[(size_t)row * n + c], v[c], s);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  if (lane == 0) out[row] = s - sub[row];
-}
-
 // t_k = T[last][k] - sum_j T[nepad+j][k] xi[j]   (k < nepad), in place.  One workgroup per 64
 // columns; 16 row groups each sum every 16th row (row reads stay contiguous), then one LDS pass.
 __global__ void __launch_bounds__(1024) xe_rhs_kernel(double *T, int nepad, int ni, const double *xi) {
@@ -625,1045 +117,125 @@ __global__ void __launch_bounds__(1024) xe_rhs_kernel(double *T, int nepad, int 
   }
 }
 
-// ---- Murty bookkeeping -------------------------------------------------------
-struct MurtyRecord {      // written by murty_check_kernel, read by the host each pivot
-  int first_offender;     // lowest index that must flip, or INT_MAX
-  int out_of_bounds;      // any x < lo or x > hi            (lcp.cc:66)
-  int w_bad;              // any w < 0 at x == lo or w > 0 at x == hi  (lcp.cc:72-76)
-  int pad;
-  double resid2;          // || A x - (b + w) ||^2           (lcp.cc:81-83)
-  double goodness;        // sum of the non-positive x and w (lcp.cc:107-113)
-};
-
-// x(!S) = C (the clamped bound); beff = b - A(:, !S) x(!S) is formed by the
-// caller with gemv_minus on x_clamped.  This kernel prepares x_clamped.
-__global__ void clamp_x_kernel(int n, const uint8_t *S, const double *Cb, double *xc) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) xc[i] = S[i] ? 0.0 : Cb[i];
-}
-__global__ void negate_kernel(int n, const double *a, double *o) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) o[i] = -a[i];
-}
-// w = S ? 0 : r   (lcp.cc:219-223), r = A x - b
-__global__ void set_w_kernel(int n, const uint8_t *S, const double *r, double *w) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) w[i] = S[i] ? 0.0 : r[i];
-}
-__global__ void fill_x_clamped_kernel(int n, const uint8_t *S, const double *Cb, double *x) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n && !S[i]) x[i] = Cb[i];
+__global__ void scatter_kernel(int n, const int *idx, const double *src, double *dst) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) dst[idx[k]] = src[k];
 }
 
-// CheckMurtySolution, lcp.cc:20-103 (single workgroup; n <= a few thousand).
-__global__ void __launch_bounds__(1024) murty_check_kernel(int n, const double *x, const double *w, const double *r,
-                                                           const uint8_t *S, const double *Cb, const double *lo,
-                                                           const double *hi, MurtyRecord *rec) {
-  __shared__ int s_first, s_oob, s_wbad;
-  __shared__ double s_res[1024], s_good[1024];
-  if (threadIdx.x == 0) { s_first = 0x7fffffff; s_oob = 0; s_wbad = 0; }
-  __syncthreads();
-  double res = 0.0, good = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) {
-    const double xi = x[i], wi = w[i];
-    bool off;
-    if (S[i]) off = (xi < lo[i]) || (xi > hi[i]);
-    else off = (Cb[i] == lo[i] && wi < 0) || (Cb[i] == hi[i] && wi > 0);
-    if (off) atomicMin(&s_first, i);
-    if (xi < lo[i] || xi > hi[i]) s_oob = 1;
-    if ((xi == lo[i] && wi < 0) || (xi == hi[i] && wi > 0)) s_wbad = 1;
-    const double d = r[i] - wi;   // (A x - b) - w
-    res += d * d;
-    if (!(xi > 0)) good += xi;
-    if (!(wi > 0)) good += wi;
-  }
-  s_res[threadIdx.x] = res; s_good[threadIdx.x] = good;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { s_res[threadIdx.x] += s_res[threadIdx.x + s]; s_good[threadIdx.x] += s_good[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    rec->first_offender = s_first; rec->out_of_bounds = s_oob; rec->w_bad = s_wbad; rec->pad = 0;
-    rec->resid2 = s_res[0]; rec->goodness = s_good[0];
-  }
-}
-
-// ---- the pivot loop's state lives on the device ----------------------------------------------------------
-// Round 2's loop downloaded x and w, chose the flips on the host and uploaded S, C and the index list again: seven
-// small pageable copies per pivot, ~0.1 ms of the 0.37 ms a pivot of the N = 2048 problem took.  Now the host sees one
-// 64-byte record per pivot (written straight into pinned host memory) and everything else stays where it is:
-//   murty_init_kernel     S = 1, C = lo, x = 0, w = r = -b (lcp.cc:184-185), best-iterate memory
-//   murty_prep_kernel     x(!S) = C and b_eff = b - A(:, !S) x(!S)
-//   murty_resid_kernel    r = A x - b, w = S ? 0 : r (lcp.cc:219-223)
-//   murty_advance_kernel  CheckMurtySolution (lcp.cc:20-103) + best-iterate memory (lcp.cc:125-137) + the flips of the
-//                         NEXT pivot (single index, lcp.cc:36-62, or the block rule) + the ascending index list of S
-struct MurtyStep {        // one per pivot, read by the host after the synchronisation
-  int first_offender;     // lowest index that must flip, or INT_MAX
-  int out_of_bounds;      // any x < lo or x > hi            (lcp.cc:66)
-  int w_bad;              // any w < 0 at x == lo or w > 0 at x == hi  (lcp.cc:72-76)
-  int fail;               // a factorisation met a non-positive pivot
-  double resid2;          // || A x - (b + w) ||^2           (lcp.cc:81-83)
-  double goodness;        // sum of the non-positive x and w (lcp.cc:107-113)
-  int ns;                 // |S| after the flips: the size of the next pivot's system
-  int ninf;               // number of infeasible indexes before the flips
-  int flipped;
-  int nd, nr;             // |S \ S0| and |S0 \ S| against the factored base set S0 (-1: not tracked)
-  int seq;                // the launch's sequence number, stored last (system scope): the host polls it instead of
-                          // waiting for the stream (a completion signal costs ~15 us of host latency per pivot)
-};
-struct MurtyState {       // block-rule and best-iterate memory, device resident
-  int best_ninf, patience;
-  double best_good;
-  int have_best, pad;
-};
-
-// guess: the block rule may start from any set.  A row whose bound is 0 on the side b points away from (lo = 0 and
-// b <= 0: x = 0, w = -b >= 0 is consistent on its own) starts outside S at that bound instead of inside: on the N = 2048
-// problem the first system has 470 rows instead of 985 and the rule needs 6 pivots instead of 8.
-__global__ void murty_init_kernel(int n, const double *b, const double *lo, const double *hi, int guess, uint8_t *S, double *Cb, double *x,
-                                  double *w, double *r, double *bx, double *bw, MurtyState *st) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) { st->best_ninf = n + 1; st->patience = 10; st->best_good = 0.0; st->have_best = 0; st->pad = 0; }
-  if (i < n) {
-    const double nb = -b[i];
-    const bool at_lo = guess && lo[i] == 0.0 && b[i] <= 0.0, at_hi = guess && !at_lo && hi[i] == 0.0 && b[i] >= 0.0;
-    S[i] = (at_lo || at_hi) ? 0 : 1; Cb[i] = at_hi ? hi[i] : lo[i]; x[i] = 0.0; w[i] = nb; r[i] = nb; bx[i] = 0.0; bw[i] = nb;
-  }
-}
-
-// one wavefront per row: beff = b - A xc (box problems; the reference's own loop drops the term, lcp.cc:199-216),
-// x = xc, xc = S ? 0 : C
-__global__ void __launch_bounds__(256) murty_prep_kernel(const double *M, int n, const double *b, const uint8_t *S,
-                                                         const double *Cb, int box_fix, double *beff, double *x) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  double s = 0.0;
-  if (box_fix) {
-    for (int c = lane; c < n; c += 64) s = __builtin_fma(M[(size_t)row * n + c], S[c] ? 0.0 : Cb[c], s);
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  }
-  if (lane == 0) {
-    beff[row] = box_fix ? -(s - b[row]) : b[row];
-    x[row] = S[row] ? 0.0 : Cb[row];
-  }
-}
-
-__global__ void __launch_bounds__(256) murty_resid_kernel(const double *M, int n, const double *x, const double *b,
-                                                          const uint8_t *S, double *r, double *w) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  double s = 0.0;
-  for (int c = lane; c < n; c += 64) s = __builtin_fma(M[(size_t)row * n + c], x[c], s);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  if (lane == 0) {
-    const double rr = s - b[row];
-    r[row] = rr;
-    w[row] = S[row] ? 0.0 : rr;
-  }
-}
-
-// mode 0: check only; 1: flip the first offender (the reference's rule); 2: the block rule.  Single workgroup.
-__global__ void __launch_bounds__(1024) murty_advance_kernel(int n, const double *x, const double *w, const double *r, uint8_t *S,
-                                                             double *Cb, const double *lo, const double *hi, int mode, double tol,
-                                                             int keep_best, MurtyState *st, double *bx, double *bw, int *idx,
-                                                             const int *fail_a, const int *fail_b, MurtyStep *out,
-                                                             const int *pos0, const int *idx0, int n0, int *Dl, int *Rl, int list_cap, int seq) {
-  __shared__ int s_first, s_last, s_ninf, s_oob, s_wbad, s_improved, s_all, s_flip, s_flipped;
-  __shared__ double s_res[1024], s_good[1024];
-  __shared__ unsigned long long s_wave[16];
-  const int tid = threadIdx.x;
-  if (tid == 0) { s_first = 0x7fffffff; s_last = -1; s_ninf = 0; s_oob = 0; s_wbad = 0; s_flipped = 0; }
-  __syncthreads();
-  auto offender = [&](int i, double xi, double wi) {
-    if (S[i]) return (xi < lo[i]) || (xi > hi[i]);
-    return (Cb[i] == lo[i] && wi < 0) || (Cb[i] == hi[i] && wi > 0);
-  };
-  double res = 0.0, good = 0.0;
-  for (int i = tid; i < n; i += 1024) {
-    const double xi = x[i], wi = w[i];
-    if (offender(i, xi, wi)) { atomicMin(&s_first, i); atomicMax(&s_last, i); atomicAdd(&s_ninf, 1); }
-    if (xi < lo[i] || xi > hi[i]) s_oob = 1;
-    if ((xi == lo[i] && wi < 0) || (xi == hi[i] && wi > 0)) s_wbad = 1;
-    const double d = r[i] - wi;   // (A x - b) - w
-    res += d * d;
-    if (!(xi > 0)) good += xi;
-    if (!(wi > 0)) good += wi;
-  }
-  s_res[tid] = res; s_good[tid] = good;
-  __syncthreads();
-  for (int k = 512; k > 0; k >>= 1) {
-    if (tid < k) { s_res[tid] += s_res[tid + k]; s_good[tid] += s_good[tid + k]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const bool solution = s_first == 0x7fffffff && !s_oob && !s_wbad && sqrt(s_res[0]) <= tol;
-    s_improved = keep_best && (!st->have_best || s_good[0] > st->best_good);
-    if (s_improved) { st->best_good = s_good[0]; st->have_best = 1; }
-    bool all = true;
-    int flip = 0;
-    if (mode != 0 && !solution && s_first != 0x7fffffff) {
-      flip = 1;
-      if (mode == 2) {      // every infeasible index while their number keeps falling, else the largest one
-        if (s_ninf < st->best_ninf) { st->best_ninf = s_ninf; st->patience = 10; }
-        else if (st->patience > 0) --st->patience;
-        else all = false;
-      }
-    }
-    s_flip = flip; s_all = all ? 1 : 0;
-  }
-  __syncthreads();
-  if (s_improved) for (int i = tid; i < n; i += 1024) { bx[i] = x[i]; bw[i] = w[i]; }
-  if (s_flip) {
-    const int one = (mode == 1) ? s_first : (s_all ? -1 : s_last);
-    for (int i = tid; i < n; i += 1024) {
-      const double xi = x[i];
-      const bool mine = one >= 0 ? (i == one) : offender(i, xi, w[i]);
-      if (mine) {
-        if (S[i]) { S[i] = 0; Cb[i] = (xi < lo[i]) ? lo[i] : hi[i]; }   // lcp.cc:36-62
-        else S[i] = 1;
-        atomicAdd(&s_flipped, 1);
-      }
-    }
-  }
-  __syncthreads();
-  // the ascending index list of S, and the difference against the factored base set S0 = idx0[0 .. n0): D = S \ S0,
-  // R = S0 \ S, ascending.  Thread t owns a run of consecutive indexes; ONE scan over the packed counts (|S| in the low
-  // word, |D| and |R| in 16 bits each: n < 32768 when the base is tracked), inside the wavefronts by shuffles, across them
-  // through LDS.  pos0 is never cleared: an entry counts only if idx0 points back at it.
-  auto in_base = [&](int i) { const int q = pos0[i]; return q >= 0 && q < n0 && idx0[q] == i; };
-  const int per = (n + 1023) / 1024, i0 = tid * per, i1 = min(n, i0 + per);
-  unsigned long long mine = 0;
-  for (int i = i0; i < i1; ++i) {
-    const bool in_s = S[i] != 0;
-    mine += in_s ? 1ull : 0ull;
-    if (pos0) {
-      const bool in0 = in_base(i);
-      if (in_s && !in0) mine += 1ull << 32;
-      if (!in_s && in0) mine += 1ull << 48;
-    }
-  }
-  unsigned long long incl = mine, total = 0;
-  {
-    const int lane = tid & 63;
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (int k = 0; k < 16; ++k) { if (k < (tid >> 6)) before += s_wave[k]; total += s_wave[k]; }
-    incl += before;
-  }
-  const unsigned long long excl = incl - mine;
-  const int ns_total = (int)(total & 0xffffffffull);
-  int nd_total = -1, nr_total = -1;
-  {
-    int pos = (int)(excl & 0xffffffffull);
-    for (int i = i0; i < i1; ++i) if (S[i]) idx[pos++] = i;
-  }
-  if (pos0) {
-    nd_total = (int)((total >> 32) & 0xffff); nr_total = (int)(total >> 48);
-    if (nd_total + nr_total <= list_cap) {
-      int pd = (int)((excl >> 32) & 0xffff), pr = (int)(excl >> 48);
-      for (int i = i0; i < i1; ++i) {
-        const bool in0 = in_base(i);
-        if (S[i] && !in0) Dl[pd++] = i;
-        if (!S[i] && in0) Rl[pr++] = i;
-      }
-    }
-  }
-  if (tid == 0) {
-    out->first_offender = s_first; out->out_of_bounds = s_oob; out->w_bad = s_wbad;
-    out->fail = (fail_a ? *fail_a : 0) | (fail_b ? *fail_b : 0);
-    out->resid2 = s_res[0]; out->goodness = s_good[0];
-    out->ns = ns_total; out->ninf = s_ninf; out->flipped = s_flipped; out->nd = nd_total; out->nr = nr_total;
-    __threadfence_system();
-    __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// ---- pivots that differ little from a factored one ---------------------------------------------------------
-// Block pivoting ends with a few small corrections of S (the N = 2048 problem: 486, 440, 226, 121, 40, 11, 2 flips), the
-// reference's single-index rule changes one index per pivot -- and a fresh factorisation costs the same 64-column
-// latency chain every time.  With S0 the set of the last factorisation (L and W = L^-T in T, see factor()), D = S \ S0
-// and R = S0 \ S, m = |D| + |R| <= 64, the new x solves the bordered system
-//     [A00  A0D  E_R] [x0]   [b0]
-//     [AD0  ADD   0 ] [xD] = [bD]          (the multipliers mu pin x_R = 0)
-//     [E_R'  0    0 ] [mu]   [0 ]
-// by block elimination on the old factor:  Y = L^-1 [A0D E_R],  z0 = L^-1 b0,  C = [ADD 0; 0 0] - Y'Y (quasi-definite:
-// no pivoting needed),  C zz = [bD; 0] - Y'z0,  x0 = W (z0 - Y zz): two products with W (parallel over all CUs), one
-// m x m elimination in one workgroup -- no panel chain.
-constexpr int kBorderMax = 64;            // m
-constexpr int kBorderStride = 68;         // row stride of U and Y: m + 1 columns (the last is b0 / z0), padded
-
-// U (n0pad x kBorderStride): columns A(S0, D), E_R, b0; rows beyond n0 zero
-__global__ void border_build_kernel(const double *A, int n, const double *beff, const int *idx0, int n0, int n0pad, const int *pos0,
-                                    const int *Dl, int nd, const int *Rl, int nr, double *U) {
-  const int m = nd + nr;
-  const size_t total = (size_t)n0pad * kBorderStride;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int k = (int)(e / kBorderStride), j = (int)(e % kBorderStride);
-    double v = 0.0;
-    if (k < n0) {
-      if (j < nd) v = A[(size_t)idx0[k] * n + Dl[j]];
-      else if (j < m) v = (pos0[Rl[j - nd]] == k) ? 1.0 : 0.0;
-      else if (j == m) v = beff[idx0[k]];
-    }
-    U[e] = v;
-  }
-}
-
-// Y = L^-1 U = W'U (W[k][c] = T[ibase + k][c], zero for k > c) in 64 x 64 tiles of W: workgroup (tile (cb, kb <= cb), column
-// quarter jq) forms Yp[kb][cb 64 + c][j] = sum over the tile's k of W[k][c] U[k][j] for 17 columns j.  Both operands are
-// read along k-major rows and staged in LDS; lane = c, wavefront w takes the columns jq 17 + w, + 4, ... (its U reads are
-// wavefront-uniform broadcasts).
-constexpr int kBorderJ = kBorderStride / 4;      // 17 columns per quarter
-__global__ void __launch_bounds__(256) border_forward_kernel(const double *T, int ld, int ibase, int n0, const double *U, double *Yp,
-                                                             int n0pad) {
-  __shared__ double sW[NB][NB + 1], sU[NB][kBorderJ + 1];
-  int cbi = 0, t = blockIdx.x;      // tile index -> (cb, kb), kb <= cb
-  while (t > cbi) { t -= cbi + 1; ++cbi; }
-  const int kbi = t, cb = cbi * NB, kb = kbi * NB, j0 = blockIdx.y * kBorderJ;
-  for (int e = threadIdx.x; e < NB * NB; e += 256) {
-    const int k = e >> 6, c = e & 63;
-    sW[k][c] = (kb + k < n0 && kb + k <= cb + c) ? T[(size_t)(ibase + kb + k) * ld + cb + c] : 0.0;
-  }
-  for (int e = threadIdx.x; e < NB * kBorderJ; e += 256) {
-    const int k = e / kBorderJ, j = e % kBorderJ;
-    sU[k][j] = U[(size_t)(kb + k) * kBorderStride + j0 + j];
-  }
-  __syncthreads();
-  const int c = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int NJ = (kBorderJ + 3) / 4;      // 5 columns per wavefront (the last wavefronts have 4)
-  double acc[NJ];
-#pragma unroll
-  for (int b = 0; b < NJ; ++b) acc[b] = 0.0;
-#pragma unroll 8
-  for (int k = 0; k < NB; ++k) {
-    const double wv = sW[k][c];
-#pragma unroll
-    for (int b = 0; b < NJ; ++b) if (w + 4 * b < kBorderJ) acc[b] = __builtin_fma(wv, sU[k][w + 4 * b], acc[b]);
-  }
-  // out through LDS: a row's 17 columns are contiguous in Yp, a lane's are not
-  __syncthreads();
-#pragma unroll
-  for (int b = 0; b < NJ; ++b) if (w + 4 * b < kBorderJ) sU[c][w + 4 * b] = acc[b];
-  __syncthreads();
-  double *out = Yp + ((size_t)kbi * n0pad + cb) * kBorderStride + j0;
-  for (int e = threadIdx.x; e < NB * kBorderJ; e += 256) {
-    const int r = e / kBorderJ, j = e % kBorderJ;
-    out[(size_t)r * kBorderStride + j] = sU[r][j];
-  }
-}
-
-// Y = the sum of its tiles' shares for one 64-row block per workgroup, and the block's share of Y'Y (all m + 1 columns:
-// the last row is Y'z0), lower triangle.
-__global__ void __launch_bounds__(256) border_gram_kernel(const double *Yp, int n0pad, int n0, int m1, double *Y, double *Cpart) {
-  __shared__ double sY[NB][kBorderStride + 1];
-  const int cbi = blockIdx.x, cb = cbi * NB;
-  {
-    // the block's NB x kBorderStride entries are contiguous in every partial copy: element e of thread t is t + 256 i
-    constexpr int PER = NB * kBorderStride / 256;      // 17
-    double v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) v[i] = 0.0;
-    for (int kbi = 0; kbi <= cbi; ++kbi) {
-      const double *src = Yp + ((size_t)kbi * n0pad + cb) * kBorderStride;
-      double ld_[PER];
-#pragma unroll
-      for (int i = 0; i < PER; ++i) ld_[i] = src[threadIdx.x + 256 * i];
-#pragma unroll
-      for (int i = 0; i < PER; ++i) v[i] += ld_[i];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int e = threadIdx.x + 256 * i, c = e / kBorderStride, j = e % kBorderStride;
-      const double val = (cb + c < n0 && j < m1) ? v[i] : 0.0;
-      Y[(size_t)(cb + c) * kBorderStride + j] = val;
-      sY[c][j] = val;
-    }
-  }
-  __syncthreads();
-  double *Cp = Cpart + (size_t)cbi * kBorderStride * kBorderStride;
-  for (int e = threadIdx.x; e < m1 * m1; e += 256) {
-    const int j1 = e / m1, j2 = e % m1;
-    double sacc = 0.0;
-    if (j2 <= j1) {
-#pragma unroll 16
-      for (int r = 0; r < NB; ++r) sacc = __builtin_fma(sY[r][j1], sY[r][j2], sacc);
-    }
-    Cp[j1 * kBorderStride + j2] = sacc;
-  }
-}
-
-// C zz = g in one workgroup: C = [A(D,D) 0; 0 0] - sum of the blocks' Y'Y, g = [b(D); 0] - Y'z0; symmetric elimination
-// without pivoting (C is quasi-definite: the D block positive, the R block negative definite).
-__global__ void __launch_bounds__(256) border_small_kernel(const double *Cpart, int nblocks, const double *A, int n, const double *beff,
-                                                           const int *Dl, int nd, int m, double *zz, int *fail) {
-  __shared__ double M[kBorderMax][kBorderMax + 2];      // augmented with g
-  const int tid = threadIdx.x, m1 = m + 1;
-  for (int e = tid; e < m * m1; e += 256) {
-    const int j1 = e / m1, j2 = e % m1;
-    const int hi = j2 == m ? m : (j1 > j2 ? j1 : j2), lo = j2 == m ? j1 : (j1 > j2 ? j2 : j1);      // Cpart holds the lower triangle
-    const double *src = Cpart + hi * kBorderStride + lo;
-    double sum = 0.0;
-    int b = 0;
-    for (; b + 4 <= nblocks; b += 4) {
-      const double a0 = src[(size_t)b * kBorderStride * kBorderStride], a1 = src[(size_t)(b + 1) * kBorderStride * kBorderStride],
-                   a2 = src[(size_t)(b + 2) * kBorderStride * kBorderStride], a3 = src[(size_t)(b + 3) * kBorderStride * kBorderStride];
-      sum += a0; sum += a1; sum += a2; sum += a3;
-    }
-    for (; b < nblocks; ++b) sum += src[(size_t)b * kBorderStride * kBorderStride];
-    double c0 = 0.0;
-    if (j2 == m) c0 = j1 < nd ? beff[Dl[j1]] : 0.0;
-    else if (j1 < nd && j2 < nd) c0 = A[(size_t)Dl[j1] * n + Dl[j2]];
-    M[j1][j2] = c0 - sum;
-  }
-  __syncthreads();
-  // Gauss-Jordan: step k clears column k in every other row, so the solution is M[i][m] / M[i][i] at the end.  Row k and
-  // column k are only read in step k and every other entry has one writer: in place, one barrier per step.  Thread
-  // (i = tid / 4, q = tid % 4) owns the columns j = q, q + 4, ... of row i.
-  const int i = tid >> 2, q = tid & 3;
-  for (int k = 0; k < m; ++k) {
-    const double piv = M[k][k];
-    if (tid == 0 && !(fabs(piv) > 0.0)) atomicOr(fail, 1);
-    if (i < m && i != k) {
-      double rp = __builtin_amdgcn_rcp(piv);      // 1 / piv: hardware estimate + two Newton steps
-      rp = __builtin_fma(__builtin_fma(-piv, rp, 1.0), rp, rp);
-      rp = __builtin_fma(__builtin_fma(-piv, rp, 1.0), rp, rp);
-      const double f = -M[i][k] * rp;
-      for (int j = k + 1 + ((q - (k + 1)) & 3); j < m1; j += 4) M[i][j] = __builtin_fma(f, M[k][j], M[i][j]);
-    }
-    __syncthreads();
-  }
-  if (tid < m) zz[tid] = M[tid][m] / M[tid][tid];
-}
-
-// v = z0 - Y zz (the right-hand side of the product with W), one wavefront per row, and x_D = zz[0 .. nd) into x
-__global__ void __launch_bounds__(256) border_v_kernel(const double *Y, int n0pad, int m, const double *zz, double *v, const int *Dl, int nd, double *x) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (blockIdx.x == 0 && threadIdx.x < nd) x[Dl[threadIdx.x]] = zz[threadIdx.x];      // nd <= kBorderMax <= 256
-  if (row >= n0pad) return;
-  const double *y = Y + (size_t)row * kBorderStride;
-  double sum = lane < m ? -y[lane] * zz[lane] : 0.0;      // m <= 64
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-  if (lane == 0) v[row] = y[m] + sum;
-}
-
-
-
-// ---- small problems: the whole pivot loop in ONE workgroup ----------------------
-// The reference's own ensembles give the dense solver a few dozen rows (Cairn(4): 3 rows per
-// contact), where a launch and a read-back per pivot dwarf the arithmetic.  For n <= 112 the
-// principal submatrix A(S,S) fits LDS in packed lower-triangular form, so one 256-thread
-// workgroup runs the reference's complete loop (lcp.cc:157-274: flip the first offender,
-// factor A(S,S) afresh, solve, w, CheckMurtySolution, best-solution memory, iteration cap and
-// the final looser check) without the host.  Same decisions as murty_device below.
-constexpr int kSmallMurtyMax = 112;
-
-struct SmallMurtyResult {   // written by thread 0 at the end
-  int solved;               // a solution at 1e-9 (lcp.cc:196) or, when capped, at 1e-8 (lcp.cc:244-246)
-  int pivots;
-  int not_spd;              // a principal submatrix had a non-positive pivot
-  int pad;
-};
-
-__device__ __forceinline__ int tri(int r, int c) { return r * (r + 1) / 2 + c; }   // c <= r
-
-__global__ void __launch_bounds__(256) murty_small_kernel(int n, const double *A, const double *bvec, const double *lo_g,
-                                                          const double *hi_g, int box_fix, int max_iterations,
-                                                          double *x_out, double *w_out, SmallMurtyResult *res) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  double *T = sm;                                   // packed lower triangle of A(S,S), then its Cholesky factor
-  double *x = T + kSmallMurtyMax * (kSmallMurtyMax + 1) / 2;
-  double *w = x + kSmallMurtyMax, *r = w + kSmallMurtyMax, *Cv = r + kSmallMurtyMax, *lo = Cv + kSmallMurtyMax;
-  double *hi = lo + kSmallMurtyMax, *b = hi + kSmallMurtyMax, *y = b + kSmallMurtyMax, *bx = y + kSmallMurtyMax;
-  double *bw = bx + kSmallMurtyMax, *y2 = bw + kSmallMurtyMax;
-  __shared__ int idx[kSmallMurtyMax];
-  __shared__ unsigned char S[kSmallMurtyMax];
-  __shared__ int s_first, s_oob, s_wbad, s_ns, s_state, s_fail;   // s_state: 0 run, 1 solved, 2 capped
-  __shared__ double s_resid2, s_good, s_best;
-  const int tid = threadIdx.x;
-  const int NONE = 0x7fffffff;
-
-  for (int i = tid; i < n; i += 256) {
-    S[i] = 1; lo[i] = lo_g[i]; hi[i] = hi_g[i]; Cv[i] = lo_g[i]; b[i] = bvec[i];
-    x[i] = 0.0; w[i] = -bvec[i]; r[i] = -bvec[i];   // lcp.cc:184-185
-    bx[i] = 0.0; bw[i] = -bvec[i];
-  }
-  if (tid == 0) { s_state = 0; s_fail = 0; }
-  __syncthreads();
-
-  // CheckMurtySolution (lcp.cc:20-103) + goodness (lcp.cc:107-113) of the current x, w, r
-  auto check = [&]() {
-    if (tid == 0) { s_first = NONE; s_oob = 0; s_wbad = 0; }
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-      const double xi = x[i], wi = w[i];
-      bool off;
-      if (S[i]) off = (xi < lo[i]) || (xi > hi[i]);
-      else off = (Cv[i] == lo[i] && wi < 0) || (Cv[i] == hi[i] && wi > 0);
-      if (off) atomicMin(&s_first, i);
-      if (xi < lo[i] || xi > hi[i]) s_oob = 1;
-      if ((xi == lo[i] && wi < 0) || (xi == hi[i] && wi > 0)) s_wbad = 1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double res2 = 0.0, good = 0.0;
-      for (int i = 0; i < n; ++i) {
-        const double d = r[i] - w[i];
-        res2 += d * d;
-        if (!(x[i] > 0)) good += x[i];
-        if (!(w[i] > 0)) good += w[i];
-      }
-      s_resid2 = res2; s_good = good;
-    }
-    __syncthreads();
-  };
-  auto is_solution = [&](double tol) { return s_first == NONE && !s_oob && !s_wbad && sqrt(s_resid2) <= tol; };
-  // (A x)_i with two threads per row (even / odd columns) and four independent chains each;
-  // the pair is combined through LDS by the caller
-  auto row_times_x = [&](int i, int half) {
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-    const double *row = A + (size_t)i * n;
-    int c = half;
-    for (; c + 6 < n; c += 8) {
-      p0 = __builtin_fma(row[c], x[c], p0);
-      p1 = __builtin_fma(row[c + 2], x[c + 2], p1);
-      p2 = __builtin_fma(row[c + 4], x[c + 4], p2);
-      p3 = __builtin_fma(row[c + 6], x[c + 6], p3);
-    }
-    for (; c < n; c += 2) p0 = __builtin_fma(row[c], x[c], p0);
-    return (p0 + p1) + (p2 + p3);
-  };
-  // r = A x - b
-  auto residual_vector = [&]() {
-    const int i = tid >> 1, half = tid & 1;
-    double part = 0.0;
-    if (i < n) part = row_times_x(i, half);
-    if (i < n && half == 1) y2[i] = part;
-    __syncthreads();
-    if (i < n && half == 0) r[i] = (part + y2[i]) - b[i];
-    __syncthreads();
-  };
-
-  check();
-  if (tid == 0) s_best = s_good;
-  __syncthreads();
-
-  int iter = 0, pivots = 0;
-  bool force = box_fix != 0;
-  while (iter < max_iterations) {
-    if (!force) {
-      if (is_solution(1e-9)) { if (tid == 0) s_state = 1; __syncthreads(); break; }
-      if (tid == 0 && s_first != NONE) {             // lcp.cc:36-62: flip the first offender
-        const int i = s_first;
-        if (S[i]) { S[i] = 0; Cv[i] = (x[i] < lo[i]) ? lo[i] : hi[i]; }
-        else S[i] = 1;
-      }
-      __syncthreads();
-    }
-    force = false;
-    if (tid == 0) {                                  // index list of S
-      int ns = 0;
-      for (int i = 0; i < n; ++i) if (S[i]) idx[ns++] = i;
-      s_ns = ns;
-    }
-    for (int i = tid; i < n; i += 256) x[i] = S[i] ? 0.0 : Cv[i];   // x = x_clamped
-    __syncthreads();
-    const int ns = s_ns;
-    // right-hand side: b(S), minus A(S,!S) x(!S) for the true box problem (lcp.cc:199-216)
-    if (box_fix) {
-      residual_vector();                              // r = A x_clamped - b
-      for (int k = tid; k < ns; k += 256) y[k] = -r[idx[k]];
-    } else {
-      for (int k = tid; k < ns; k += 256) y[k] = b[idx[k]];
-    }
-    for (int e = tid; e < ns * (ns + 1) / 2; e += 256) {             // gather A(S,S), lower triangle
-      int rr = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-      while (tri(rr + 1, 0) <= e) ++rr;
-      while (tri(rr, 0) > e) --rr;
-      const int cc = e - tri(rr, 0);
-      T[e] = A[(size_t)idx[rr] * n + idx[cc]];
-    }
-    __syncthreads();
-    // Cholesky, right-looking, in place; y rides along as an extra row, so L z = y is solved by
-    // the same column steps.  Two barriers per column: every thread takes the square root of the
-    // (not yet overwritten) pivot itself.
-    for (int j = 0; j < ns; ++j) {
-      const double d = T[tri(j, j)];
-      if (!(d > 0.0)) { if (tid == 0) s_fail = 1; }
-      const double rt = sqrt(d > 0.0 ? d : 1.0);
-      for (int i = j + 1 + tid; i < ns; i += 256) T[tri(i, j)] /= rt;
-      if (tid == 255) y[j] /= rt;
-      __syncthreads();
-      if (tid == 0) T[tri(j, j)] = rt;
-      const int tx = tid & 15, ty = tid >> 4;
-      for (int i = j + 1 + ty; i < ns; i += 16) {
-        const double lij = T[tri(i, j)];
-        for (int k = j + 1 + tx; k <= i; k += 16) T[tri(i, k)] = __builtin_fma(-lij, T[tri(k, j)], T[tri(i, k)]);
-      }
-      {
-        const double yj = y[j];
-        for (int i = j + 1 + tid; i < ns; i += 256) y[i] = __builtin_fma(-T[tri(i, j)], yj, y[i]);
-      }
-      __syncthreads();
-    }
-    // L^T v = z in ONE wavefront (two unknowns per lane), no workgroup barrier per step
-    if (tid < 64) {
-      for (int j = ns - 1; j >= 0; --j) {
-        if (tid == (j & 63)) y[j] = y[j] / T[tri(j, j)];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double yj = y[j];
-        for (int i = tid; i < j; i += 64) y[i] = __builtin_fma(-T[tri(j, i)], yj, y[i]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-    }
-    __syncthreads();
-    for (int k = tid; k < ns; k += 256) x[idx[k]] = y[k];
-    __syncthreads();
-    residual_vector();                               // r = A x - b
-    for (int i = tid; i < n; i += 256) w[i] = S[i] ? 0.0 : r[i];     // lcp.cc:219-223
-    __syncthreads();
-    ++pivots;
-    check();
-    if (s_good > s_best) {                           // lcp.cc:125-137 (uniform: shared value)
-      for (int i = tid; i < n; i += 256) { bx[i] = x[i]; bw[i] = w[i]; }
-      __syncthreads();
-      if (tid == 0) s_best = s_good;
-      __syncthreads();
-    }
-    ++iter;
-    if (s_fail) break;
-  }
-  int solved = (s_state == 1);
-  if (!solved && !s_fail) {
-    // capped: the best-seen iterate (reference rule only), re-checked at the looser 1e-8 (lcp.cc:241-246)
-    if (!box_fix) {
-      for (int i = tid; i < n; i += 256) { x[i] = bx[i]; w[i] = bw[i]; }
-      __syncthreads();
-    }
-    residual_vector();
-    check();
-    solved = is_solution(1e-8) ? 1 : 0;
-  }
-  for (int i = tid; i < n; i += 256) { x_out[i] = x[i]; w_out[i] = w[i]; }
-  if (tid == 0) { res->solved = solved; res->pivots = pivots; res->not_spd = s_fail; res->pad = 0; }
-}
-
-// A block of the workspace's cache (DenseWorkspace::take, runtime.h), rounded up to 256 bytes.
-template <typename T>
-struct Buf {
+// What both solvers share: the trapezoid [A_ee A_ei; A_ie A_ii; b^T] over E (padded to nepad) and I, its scratch and the
+// two runs of launches on it.  Uploads, the reset and read-back of `fail_d` and every synchronisation are the caller's.
+struct SchurStage {
   DenseWorkspace &ws;
-  T *p = nullptr;
-  size_t bytes = 0;
-  Buf(DenseWorkspace &w, size_t n) : ws(w) {
-    if (n) { bytes = ((n * sizeof(T) + 255) / 256) * 256; p = static_cast<T *>(ws.take(bytes)); }
+  const int ne, ni, nepad, ld, rows;
+  Buf<double> T, lhs, rhs, xi, wi, xe, xs, dinv;      // lhs, rhs: the reduced LCP; xi, wi: its solution; xe: the E part of x
+  Buf<int> fail_d;
+  SchurStage(DenseWorkspace &w, int ne_, int ni_)
+      : ws(w), ne(ne_), ni(ni_), nepad((ne_ + NB - 1) / NB * NB), ld(nepad + ni_), rows(ld + 1),
+        T(w, (size_t)rows * (ld > 0 ? ld : 1)), lhs(w, (size_t)ni_ * ni_), rhs(w, ni_), xi(w, ni_), wi(w, ni_), xe(w, ne_), xs(w, nepad),
+        dinv(w, (size_t)nepad * NB), fail_d(w, 1) {}
+  // Factor the E columns (lcp.cc:286-294; toolkit/lcp.cc: L L' = Z, Q = L^-1 B'): the trailing block becomes the Schur
+  // complement A_ii - A_ie A_ee^-1 A_ei (lhs), the trailing part of the b row b_i - A_ie A_ee^-1 b_e (rhs).
+  void eliminate(const double *dA, const double *db, int N, const int *dE, const int *dI, int lower_only) {
+    hipStream_t s = ws.stream;
+    hipLaunchKernelGGL(build_schur_kernel, dim3(grid1((size_t)rows * ld)), dim3(256), 0, s, dA, db, N, dE, ne, nepad, dI, ni, T.p, lower_only);
+    factor(ws, T.p, ld, rows, nepad, fail_d.p, dinv.p);
+    if (ni) hipLaunchKernelGGL(extract_schur_kernel, dim3(grid1((size_t)ni * ni)), dim3(256), 0, s, T.p, nepad, ni, lhs.p, rhs.p);
   }
-  // a block goes back to the cache while kernels that use it may still be queued: the next taker enqueues on the same
-  // context's stream, so the stream's order keeps them apart
-  ~Buf() { if (p) ws.give(p, bytes); }
-  Buf(const Buf &) = delete;
-  Buf &operator=(const Buf &) = delete;
+  // xe = A_ee^-1 (b_e - A_ei x_i) = L^-T (L^-1 b_e - (L^-1 A_ei) x_i) from xi   (lcp.cc:317); needs ne > 0
+  void back_substitute() {
+    hipLaunchKernelGGL(xe_rhs_kernel, dim3(nepad / NB), dim3(1024), 0, ws.stream, T.p, nepad, ni, xi.p);
+    launch_back_solve(ws, T.p, ld, nepad, nepad + ni, ne, nullptr, xe.p, xs.p, dinv.p);
+  }
 };
 
-inline int grid1(size_t n, int block = 256) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
-
-// ---- one launch per panel -------------------------------------------------------------------------------
-// The three launches of a panel step (diagonal block -> panel solve -> trailing update) run one after the other and
-// the first, a 64-column latency chain in ONE workgroup, takes 20 of the 37 us.  chol_panel_kernel does the panel
-// solve AND the trailing update of panel k in one launch, and the workgroup that finishes the NEXT diagonal tile
-// factors it on the spot (chol_diag_tile, the algorithm of chol_diag_kernel on a tile staged in LDS), while the other
-// workgroups are still updating: per panel one launch whose length is that one workgroup's (update + 20 us).
-//   * Every workgroup needs X_r = B_r L^-T and X_c = B_c L^-T of its tile's row blocks; it computes them itself from the
-//     unsolved panel (two extra 64^3 MFMA products per tile: the matrix cores are idle anyway) instead of waiting for a
-//     panel-solve launch.
-//   * Nobody may overwrite the panel while others still read it, so the solved panel X, the factored diagonal blocks
-//     and nothing else go to a second array (Tl, same shape); T keeps taking the trailing updates.  After the last panel
-//     merge_factor_kernel copies the factored columns back, so every consumer finds L where it always was.
-constexpr int kPanelThreads = 320;     // four MFMA wavefronts + the inverse wavefront of the diagonal tile
-
-// grid (tc, tr) over the 64 x 64 tiles of the trailing trapezoid of panel k0 (as chol_update_kernel).
-// factor_next: the tile (k0 + 64, k0 + 64) is the next diagonal block to factor (k0 + 64 < nf).
-__global__ void __launch_bounds__(kPanelThreads) chol_panel_kernel(double *T, double *Tl, int ld, int nrows, int k0, const double *inv_k,
-                                                                   double *inv_next, int *fail, int factor_next, int ibase, int iend) {
-  extern __shared__ __attribute__((aligned(16))) double smem_d[];
-  double *sA = smem_d, *sBm = sA + NB * kStageLd, *sI = sBm + NB * kStageLd;
-  double *sQ = sI + NB * kStageLd, *sRv = sQ + 32 * kTileQs;      // scratch of the diagonal tile (with sA and sI)
-  const int r0 = k0 + NB + blockIdx.y * NB;
-  const int c0 = k0 + NB + blockIdx.x * NB;
-  if (c0 > r0 + NB - 1) return;  // tile entirely above the diagonal
-  if (r0 >= ibase && r0 < iend && r0 - ibase >= k0 + NB) return;      // identity rows that no panel has reached yet
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool mm = wave < 4;      // the MFMA wavefronts
-  const int lr = (wave >> 1) * 32, lc = (wave & 1) * 32;
-  const int qr = r0 + lr, qc = c0 + lc;
-  const int li = lane & 15, lk = lane >> 4;
-  const bool diag = r0 == c0;
-  double4_t told[2][2], xr[2][2], xc[2][2], acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      xr[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0}; xc[a][b] = xr[a][b]; acc[a][b] = xr[a][b]; told[a][b] = xr[a][b];
-    }
-  if (mm) {
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int r = qr + 16 * ti + lk + 4 * reg, c = qc + 16 * tj + li;
-          told[ti][tj][reg] = (r < nrows && c < ld && c <= r) ? T[(size_t)r * ld + c] : 0.0;
-        }
-  }
-  stage_block(T + k0, ld, r0, nrows, sA);
-  if (!diag) stage_block(T + k0, ld, c0, nrows < ld ? nrows : ld, sBm);
-  stage_block(inv_k, NB, 0, NB, sI);
-  __syncthreads();
-  // the solved panel rows of this tile: X = B L^-T, X[r][c] = sum_k B[r][k] Linv[c][k]
-  if (mm) {
-    mfma_quadrant(sA, sI, lr, lc, xr);
-    if (!diag) mfma_quadrant(sBm, sI, lr, lc, xc);
-  }
-  __syncthreads();
-  if (mm) {
-    // back into LDS as operands of the update; the first tile of every row block also files its X rows in Tl
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int rr = lr + 16 * ti + lk + 4 * reg, cc = lc + 16 * tj + li;
-          sA[rr * kStageLd + cc] = xr[ti][tj][reg];
-          if (!diag) sBm[rr * kStageLd + cc] = xc[ti][tj][reg];
-          if (blockIdx.x == 0 && r0 + rr < nrows) Tl[(size_t)(r0 + rr) * ld + k0 + cc] = xr[ti][tj][reg];
-        }
-  }
-  __syncthreads();
-  if (mm) mfma_quadrant(sA, diag ? sA : sBm, lr, lc, acc);
-  const bool factor_here = factor_next && diag && blockIdx.x == 0;      // uniform
-  if (!factor_here) {
-    if (mm) {
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            const int r = qr + 16 * ti + lk + 4 * reg, c = qc + 16 * tj + li;
-            if (r < nrows && c < ld && c <= r) T[(size_t)r * ld + c] = told[ti][tj][reg] - acc[ti][tj][reg];
-          }
-    }
-    return;
-  }
-  // the next diagonal block: updated tile -> LDS -> L and its inverse
-  __syncthreads();
-  if (mm) {
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int rr = lr + 16 * ti + lk + 4 * reg, cc = lc + 16 * tj + li;
-          sBm[rr * kStageLd + cc] = told[ti][tj][reg] - acc[ti][tj][reg];
-        }
-  }
-  __syncthreads();
-  chol_diag_tile(sBm, kStageLd, sA, sI, sQ, sRv, Tl + (size_t)r0 * ld + r0, ld, inv_next, fail);
-}
-
-// the factored columns (and the solved rows below them) back from Tl into T
-__global__ void merge_factor_kernel(double *T, const double *Tl, int ld, int nrows, int nf) {
-  const size_t total = (size_t)nrows * nf;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(idx / nf), c = (int)(idx % nf);
-    if (r >= c) T[(size_t)r * ld + c] = Tl[(size_t)r * ld + c];
-  }
-}
-
-// the diagonal-tile kernel needs 110 KB of LDS: opt in once
-void launch_diag(DenseWorkspace &ws, const double *T, double *Tout, int ld, int k0, double *inv, int *fail) {
-  if (!ws.diag_lds) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(chol_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDiagLdsBytes));
-    ws.diag_lds = true;
-  }
-  hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(kDiagThreads), kDiagLdsBytes, ws.stream, T, Tout, ld, k0, inv, fail);
-}
-
-// Blocked Cholesky of the first nf (multiple of 64) columns of T; inv receives
-// the nf/64 inverted diagonal blocks (64x64 each).
-void factor_launches(DenseWorkspace &ws, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase) {
-  hipStream_t s = ws.stream;
-  const int iend = ibase >= 0 ? ibase + nf : -1;
-  if (ibase < 0) ibase = 1 << 30;
-  for (int k0 = 0; k0 < nf; k0 += NB) {
-    double *inv_k = inv + (size_t)(k0 / NB) * NB * NB;
-    launch_diag(ws, T, T, ld, k0, inv_k, fail);
-    const int slabs = (nrows - (k0 + NB) + NB - 1) / NB;
-    if (slabs > 0) hipLaunchKernelGGL(chol_trsm_kernel, dim3(slabs), dim3(256), 0, s, T, T, ld, nrows, k0, inv_k, ibase, iend);
-    const int tr = (nrows - (k0 + NB) + NB - 1) / NB, tc = (ld - (k0 + NB) + NB - 1) / NB;
-    if (tr > 0 && tc > 0) hipLaunchKernelGGL(chol_update_kernel, dim3(tc, tr), dim3(256), 0, s, T, ld, nrows, k0);
-  }
-}
-
-// ibase >= 0: rows [ibase, ibase + nf) of T hold an identity block (ibase a multiple of 64, at or below nf).  The panel
-// solves turn it into L^-T row by row -- row i is zero left of column i, so a 64-row block of it is skipped until the
-// panels reach its columns -- and a solve with the factor becomes ONE matrix-vector product with those rows
-// (inverse_rows_solve_kernel) instead of a block-by-block back substitution in a single workgroup, which one CU's
-// memory bandwidth bounds (the strips of L are n^2 / 2 doubles: 34 us at n = 512, 105 us at n = 1088).  The extra
-// tiles run on other CUs in the shadow of the diagonal tile's chain.
-void factor(DenseWorkspace &ws, double *T, int ld, int nrows, int nf, int *fail, double *inv, int ibase = -1) {
-  if (nf <= 0) return;
-  hipStream_t s = ws.stream;
-  static const bool fused = [] { const char *e = std::getenv("EGS_CHOL_FUSED"); return !(e && std::atoi(e) == 0); }();
-  if (!fused || nf <= NB) { factor_launches(ws, T, ld, nrows, nf, fail, inv, ibase); return; }
-  const int iend = ibase >= 0 ? ibase + nf : -1;
-  if (ibase < 0) ibase = 1 << 30;
-  const size_t need = (size_t)nrows * ld;
-  if (ws.factor_work.cap < need) {      // the second array: grow-only, a quarter of head-room from the start
-    if (ws.factor_work.p) HIPCHK(hipStreamSynchronize(s));
-    ws.factor_work.release();
-    ws.factor_work.alloc(need + need / 4);
-  }
-  double *Tl = ws.factor_work.p;
-  const size_t lds = (size_t)(3 * NB * kStageLd + 32 * kTileQs + NB) * sizeof(double);
-  if (!ws.panel_lds) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(chol_panel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ws.panel_lds = true;
-  }
-  // the first diagonal block has no update before it
-  launch_diag(ws, T, Tl, ld, 0, inv, fail);
-  for (int k0 = 0; k0 < nf; k0 += NB) {
-    double *inv_k = inv + (size_t)(k0 / NB) * NB * NB;
-    const int tr = (nrows - (k0 + NB) + NB - 1) / NB, tc = (ld - (k0 + NB) + NB - 1) / NB;
-    if (tr > 0 && tc > 0) {
-      const int factor_next = (k0 + NB < nf) ? 1 : 0;
-      hipLaunchKernelGGL(chol_panel_kernel, dim3(tc, tr), dim3(kPanelThreads), lds, s, T, Tl, ld, nrows, k0, inv_k, inv_k + NB * NB, fail, factor_next, ibase, iend);
-    } else {
-      // nothing to the right of this panel: only the rows below it are left to solve (k0 + 64 == nf here)
-      const int slabs = (nrows - (k0 + NB) + NB - 1) / NB;
-      if (slabs > 0) hipLaunchKernelGGL(chol_trsm_kernel, dim3(slabs), dim3(256), 0, s, T, Tl, ld, nrows, k0, inv_k, ibase, iend);
-    }
-  }
-  hipLaunchKernelGGL(merge_factor_kernel, dim3(grid1((size_t)nrows * nf)), dim3(256), 0, s, T, Tl, ld, nrows, nf);
-}
-
-}  // namespace
-
-// The workspace's page-locked records: murty_advance_kernel writes `step` and the host reads it after the sync;
-// `words` is the landing area of the deferred checks (a line of its own: the host polls step.seq while copies land here).
-struct HostWords { unsigned long long sym[2]; int fail; int pad; };
-struct DensePinned { alignas(64) MurtyStep step; alignas(64) HostWords words; };
-
-namespace {
-
-DensePinned *pinned_records(DenseWorkspace &ws) {
-  if (!ws.pinned.p) {
-    ws.pinned.alloc(1);
-    std::memset(ws.pinned.p, 0, sizeof(DensePinned));
-  }
-  return ws.pinned.p;
-}
-
-// Murty on (A n x n device, b device).  Mirrors lcp.cc:157-274; box_fix as in
-// the oracle (true box problem: solve once before the first check).
-//
-// block = true is NOT the reference's pivot rule: block principal pivoting
-// (Judice & Pires): every infeasible index flips at once while the number of
-// infeasibilities keeps falling, with single-index steps (largest index) as the
-// safeguard that guarantees termination.  Same unique solution for SPD A, in
-// tens of factorisations instead of hundreds -- and no min(1000, 2^n) cap, which
-// the reference's single-index rule exhausts for n >~ 600.
-// extra_fail: a device flag of the caller's own factorisation, folded into the record's `fail`; after_first_sync: run
-// once after the first synchronisation (the caller's deferred checks ride on it instead of synchronising themselves).
-bool murty_device(DenseWorkspace &ws, int n, const double *dA, const double *db, const std::vector<double> &lo,
-                  const std::vector<double> &hi, bool box_fix, bool block, int max_pivots, double max_seconds, double *dx,
-                  double *dw, int *pivots_out, std::string *msg, const int *extra_fail = nullptr,
-                  const std::function<void()> *after_first_sync = nullptr) {
-  hipStream_t s = ws.stream;
-  const auto t_start = std::chrono::steady_clock::now();
-  for (int i = 0; i < n; ++i)   // lcp.cc:161-164; the box variant also admits hi == 0 (toolkit/lcp.h:129)
-    if (!(lo[i] < hi[i]) || !(lo[i] <= 0) || !(box_fix ? hi[i] >= 0 : hi[i] > 0)) { if (msg) *msg = "bounds must satisfy lo <= 0 < hi (lcp.cc:161-164)"; return false; }
-  *pivots_out = 0;
-  if (n == 0) return true;
-  const double p2 = std::pow(2.0, n);
-  int max_iterations = block ? 4 * n + 100 : (p2 > 1000 ? 1000 : (int)p2);  // lcp.cc:168
-  // the caller's own cap (lcp::Settings::max_iterations, toolkit/lcp.h:161-164): give up and return false
-  if (max_pivots > 0 && max_pivots < max_iterations) max_iterations = max_pivots;
-  if (n <= kSmallMurtyMax && !block) {   // the whole loop in one workgroup, one read-back
-    Buf<double> lo_s(ws, n), hi_s(ws, n);
-    Buf<SmallMurtyResult> res_d(ws, 1);
-    SmallMurtyResult res{};
-    HIPCHK(hipMemcpyAsync(lo_s.p, lo.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(hi_s.p, hi.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
-    const size_t lds = (size_t)(kSmallMurtyMax * (kSmallMurtyMax + 1) / 2 + 11 * kSmallMurtyMax) * sizeof(double);
-    hipLaunchKernelGGL(murty_small_kernel, dim3(1), dim3(256), lds, s, n, dA, db, lo_s.p, hi_s.p, box_fix ? 1 : 0,
-                       max_iterations, dx, dw, res_d.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&res, res_d.p, sizeof res, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    *pivots_out = res.pivots;
-    if (res.not_spd) { if (msg) *msg = "a principal submatrix A(S,S) is not positive definite"; return false; }
-    if (!res.solved && msg) *msg = "MurtyPrincipalPivot: iteration cap reached without a sensible solution (lcp.cc:250-252)";
-    return res.solved != 0;
-  }
-  const int npad_max = (n + NB - 1) / NB * NB;
-  Buf<double> T(ws, (size_t)(2 * npad_max + 1) * npad_max), lohi_d(ws, 2 * (size_t)n), Cb(ws, n), beff(ws, n), r(ws, n), bx(ws, n), bw(ws, n), xs(ws, npad_max), dinv(ws, (size_t)npad_max * NB);
-  Buf<uint8_t> S_d(ws, n);
-  Buf<int> idx_d(ws, n), fail_d(ws, 1);
-  Buf<MurtyState> st_d(ws, 1);
-  // bordered pivots (see border_* kernels): the base set of the last factorisation and the work arrays
-  static const bool border_on = [] { const char *e = std::getenv("EGS_DENSE_BORDER"); return !(e && std::atoi(e) == 0); }();
-  static const bool start_guess = [] { const char *e = std::getenv("EGS_DENSE_GUESS"); return !(e && std::atoi(e) == 0); }();
-  const bool track_base = border_on && n <= 2048;      // (the forward product keeps n / 64 partial copies of Y)
-  Buf<int> pos0(ws, track_base ? n : 0), idx0(ws, track_base ? npad_max : 0), Dl(ws, track_base ? kBorderMax : 0), Rl(ws, track_base ? kBorderMax : 0);
-  Buf<double> Um(ws, track_base ? (size_t)npad_max * kBorderStride : 0), Ym(ws, track_base ? (size_t)npad_max * kBorderStride : 0),
-      Cpart(ws, track_base ? (size_t)(npad_max / NB) * kBorderStride * kBorderStride : 0), zz(ws, track_base ? kBorderStride : 0), vv(ws, track_base ? npad_max : 0),
-      Yp(ws, track_base ? (size_t)(npad_max / NB) * npad_max * kBorderStride : 0);
-  int base_n0 = -1;      // |S0|, or -1 while nothing is factored
-  if (track_base) HIPCHK(hipMemsetAsync(pos0.p, 0xff, (size_t)n * sizeof(int), s));
-  const double *lo_d = lohi_d.p, *hi_d = lohi_d.p + n;
-  MurtyStep *rec = &pinned_records(ws)->step;
-  int seq = rec->seq;      // continues across calls (the record is the workspace's)
-  {
-    std::vector<double> lohi(2 * (size_t)n);
-    std::copy(lo.begin(), lo.end(), lohi.begin());
-    std::copy(hi.begin(), hi.end(), lohi.begin() + n);
-    HIPCHK(hipMemcpyAsync(lohi_d.p, lohi.data(), 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
-  // x = 0, w = -b, r = A x - b = -b   (lcp.cc:184-185); S = everything, C = lo
-  hipLaunchKernelGGL(murty_init_kernel, dim3(grid1(n)), dim3(256), 0, s, n, db, lo_d, hi_d, (block && start_guess) ? 1 : 0, S_d.p, Cb.p, dx,
-                     dw, r.p, bx.p, bw.p, st_d.p);
-  const int flip_mode = block ? 2 : 1;
-  // check the iterate on the device, flip for the next pivot there too, and read the 64-byte record
-  auto advance = [&](int mode, double tol, int keep_best) {
-    hipLaunchKernelGGL(murty_advance_kernel, dim3(1), dim3(1024), 0, s, n, dx, dw, r.p, S_d.p, Cb.p, lo_d, hi_d, mode, tol, keep_best,
-                       st_d.p, bx.p, bw.p, idx_d.p, fail_d.p, extra_fail, rec, track_base ? pos0.p : (const int *)nullptr, idx0.p, base_n0 > 0 ? base_n0 : 0,
-                       Dl.p, Rl.p, kBorderMax, ++seq);
-    HIPCHK(hipGetLastError());
-    // the record is in host-coherent memory and its sequence number is written last: poll it (every later launch is
-    // ordered by the stream anyway); fall back to the stream's own completion if it does not show up
-    const auto t_poll = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; __atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) != seq; ++spins) {
-      if ((spins & 0xfff) == 0xfff && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count() > 0.05) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (__atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE) != seq) throw std::runtime_error("dense LCP: the pivot record did not arrive");
-        break;
-      }
-    }
-  };
-  auto is_solution = [&](double tol) {
-    return rec->first_offender == 0x7fffffff && !rec->out_of_bounds && !rec->w_bad && std::sqrt(rec->resid2) <= tol;
-  };
-  int iter = 0, pivots = 0, bordered = 0;
-  bool last_bordered = false, polished = false;
-  bool force = box_fix, solved = false, timed_out = false;
-  // the start iterate: its goodness opens the best-solution memory; a box problem solves once before the first flip,
-  // the reference's loop (lcp.cc:196-198) checks and flips first
-  advance(force ? 0 : flip_mode, 1e-9, 1);
-  if (after_first_sync) (*after_first_sync)();
-  const bool trace = std::getenv("EGS_DENSE_TRACE") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  while (iter < max_iterations && !rec->fail) {
-    if (max_seconds > 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > max_seconds) {
-      timed_out = true;   // lcp::Settings::max_time (toolkit/lcp.h:166-167)
-      break;
-    }
-    // The reference's rule starts from S = everything and moves one index per pivot, so its bordered pivots all stand on
-    // the factor of the FIRST set: an accepted x then carries the conditioning of that set (often the whole matrix), not
-    // of its own A(S,S) -- on a C5-recipe matrix of 113 rows a backward error of 112 u where a factorisation of the final
-    // set gives 1 u.  Such an iterate is solved once more on a fresh factor of its own set before
-    // it is accepted; that is no pivot of the rule (S does not change) and is not counted as one.  The block rule's
-    // bases lie next to its final set and measure like fresh factors, so it keeps its last bordered pivot.
-    const bool polish = !force && !block && last_bordered && !polished && is_solution(1e-9);
-    if (!force && !polish && is_solution(1e-9)) { solved = true; break; }
-    // (no index to flip but not a solution -- residual / sign checks failed: the reference recomputes with unchanged S,
-    //  and so does this)
-    force = false;
-    polished = polished || polish;
-    // new candidate: x(S) = A(S,S)^-1 (b(S) [- A(S,!S) x(!S)])   lcp.cc:199-216
-    const int ns = rec->ns;
-    const int nspad = (ns + NB - 1) / NB * NB;
-    hipLaunchKernelGGL(murty_prep_kernel, dim3((n + 3) / 4), dim3(256), 0, s, dA, n, db, S_d.p, Cb.p, box_fix ? 1 : 0, beff.p, dx);
-    const int nd = rec->nd, nr = rec->nr, mb = nd + nr;
-    if (track_base && base_n0 > 0 && nd >= 0 && mb <= kBorderMax && ns > 0 && !polish) {
-      // a few indexes away from the factored set: the bordered system on the old factor
-      const int n0 = base_n0, n0pad = (n0 + NB - 1) / NB * NB, nblocks = n0pad / NB;
-      hipLaunchKernelGGL(border_build_kernel, dim3(grid1((size_t)n0pad * kBorderStride)), dim3(256), 0, s, dA, n, beff.p, idx0.p, n0, n0pad,
-                         pos0.p, Dl.p, nd, Rl.p, nr, Um.p);
-      hipLaunchKernelGGL(border_forward_kernel, dim3(nblocks * (nblocks + 1) / 2, 4), dim3(256), 0, s, T.p, n0pad, n0pad, n0, Um.p, Yp.p, n0pad);
-      hipLaunchKernelGGL(border_gram_kernel, dim3(nblocks), dim3(256), 0, s, Yp.p, n0pad, n0, mb + 1, Ym.p, Cpart.p);
-      if (mb > 0)
-        hipLaunchKernelGGL(border_small_kernel, dim3(1), dim3(256), 0, s, Cpart.p, nblocks, dA, n, beff.p, Dl.p, nd, mb, zz.p, fail_d.p);
-      hipLaunchKernelGGL(border_v_kernel, dim3(n0pad / 4), dim3(256), 0, s, Ym.p, n0pad, mb, zz.p, vv.p, Dl.p, nd, dx);
-      hipLaunchKernelGGL(inverse_rows_solve_kernel, dim3((n0 + 3) / 4), dim3(256), 0, s, T.p, n0pad, n0pad, n0pad, vv.p, n0, idx0.p, dx, S_d.p);
-      ++bordered;
-      last_bordered = true;
-    } else if (ns > 0) {
-      last_bordered = false;
-      hipLaunchKernelGGL(build_pivot_kernel, dim3(grid1((size_t)(2 * nspad + 1) * nspad)), dim3(256), 0, s, dA, n, idx_d.p, ns,
-                         nspad, beff.p, T.p, 1, track_base ? pos0.p : (int *)nullptr, idx0.p);
-      factor(ws, T.p, nspad, 2 * nspad + 1, nspad, fail_d.p, dinv.p, nspad);
-      hipLaunchKernelGGL(inverse_rows_solve_kernel, dim3((ns + 3) / 4), dim3(256), 0, s, T.p, nspad, nspad, nspad,
-                         T.p + (size_t)2 * nspad * nspad, ns, idx_d.p, dx, (const uint8_t *)nullptr);
-      if (track_base) base_n0 = ns;      // (build_pivot_kernel recorded the set: the base of the bordered pivots that may follow)
-    }
-    // r = A x - b; w(!S) = r.  (The reference, lcp.cc:219-221, uses x(S) only: x(!S) = lo = 0 there, so A x(S) == A x.)
-    hipLaunchKernelGGL(murty_resid_kernel, dim3((n + 3) / 4), dim3(256), 0, s, dA, n, dx, db, S_d.p, r.p, dw);
-    if (!polish) ++pivots;
-    advance(flip_mode, 1e-9, 1);     // lcp.cc:125-137: the best iterate by "goodness" is kept by the kernel
-    // resid2 is the squared residual of A(S,S) x(S) = b(S) (w is zero on S, r - w off it): a bordered solve that misses
-    // the tolerance a solution must meet anyway is not built upon -- the next pivot factors afresh
-    if (last_bordered && !(std::sqrt(rec->resid2) <= 1e-10)) base_n0 = -1;
-    if (trace) {
-      const auto t_now = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "dense trace pivot %d: ns %d of %d (%s, +%d -%d against the factored set), %.3f ms, residual on S %.1e; then %d infeasible, %d flipped\n",
-                   pivots, ns, n, polish ? "accepted set factored afresh" : last_bordered ? "bordered" : "factored", nd, nr,
-                   std::chrono::duration<double, std::milli>(t_now - t_prev).count(), std::sqrt(rec->resid2), rec->ninf, rec->flipped);
-      t_prev = t_now;
-    }
-    if (!polish) ++iter;
-  }
-  if (!solved && iter < max_iterations && !timed_out && !rec->fail) solved = is_solution(1e-9);
-  if (trace) std::fprintf(stderr, "dense trace: %d pivots, %d of them bordered\n", pivots, bordered);
-  *pivots_out = pivots;
-  if (rec->fail) { if (msg) *msg = "a principal submatrix A(S,S) is not positive definite"; return false; }
-  if (solved) return true;  // x, w hold the solution iterate (== best, see lcp.cc:241)
-  // capped: return the best-seen iterate and re-check it with the looser 1e-8 (lcp.cc:241-246)
-  if (!box_fix && !block) {
-    HIPCHK(hipMemcpyAsync(dx, bx.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(dw, bw.p, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  }
-  hipLaunchKernelGGL(gemv_minus_kernel, dim3((n + 3) / 4), dim3(256), 0, s, dA, n, dx, db, r.p);
-  advance(0, 1e-8, 0);
-  const bool ok = is_solution(1e-8);
-  if (!ok && msg) *msg = "MurtyPrincipalPivot: iteration cap reached without a sensible solution (lcp.cc:250-252)";
-  return ok;
-}
-
-}  // namespace
-
-namespace {
 // The host entry uploads the lower block trapezoids of A first and hands the rest over as `upload_rest`: the Schur stage
 // (which reads the lower triangle only) is enqueued before the host pushes the remainder on a second stream, where the
 // symmetry check then runs; `side` is that stream.
 bool dense_mixed_impl(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
                       bool use_bounds, bool block_pivoting, int max_pivots, double max_seconds, double *x, double *w, double *dx_out,
-                      int *pivots, std::string *msg, const std::function<void()> *upload_rest, hipStream_t side);
+                      int *pivots, std::string *msg, const std::function<void()> *upload_rest, hipStream_t side) {
+  if (pivots) *pivots = 0;
+  if (N == 0) return true;
+  hipStream_t s = ws.stream;
+  const auto t_dev0 = std::chrono::steady_clock::now();
+  std::vector<int> E, I;
+  for (int i = 0; i < N; ++i) (C[i] ? E : I).push_back(i);
+  const int ne = (int)E.size(), ni = (int)I.size();
+  SchurStage st(ws, ne, ni);
+  Buf<int> dEI(ws, N);
+  int *const dE_p = dEI.p, *const dI_p = dEI.p + ne;
+  struct { const double *p; } dA{dA_in}, db{db_in};
+  {
+    std::vector<int> EI(E);
+    EI.insert(EI.end(), I.begin(), I.end());
+    HIPCHK(hipMemcpyAsync(dEI.p, EI.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(hipMemsetAsync(st.fail_d.p, 0, sizeof(int), s));
+  // A must be symmetric: the factorisations read its lower triangle only.  The verdict (and the Schur factorisation's
+  // failure flag) is read at the first synchronisation the pivot loop makes anyway, not at one of its own.
+  Buf<unsigned long long> sym_d(ws, 2);
+  HostWords *host = &pinned_records(ws)->words;
+  auto check_symmetry = [&](hipStream_t q) {
+    HIPCHK(hipMemsetAsync(sym_d.p, 0, 2 * sizeof(unsigned long long), q));
+    hipLaunchKernelGGL(symmetry_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, q, dA.p, N, sym_d.p);
+    HIPCHK(hipMemcpyAsync(host->sym, sym_d.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
+  };
+  if (!upload_rest) check_symmetry(s);
+  st.eliminate(dA.p, db.p, N, dE_p, dI_p, upload_rest ? 1 : 0);
+  HIPCHK(hipMemcpyAsync(&host->fail, st.fail_d.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (upload_rest) {      // the device is busy with the Schur stage: now the rest of A, then the symmetry check, on the side stream
+    (*upload_rest)();
+    check_symmetry(side);
+  }
+  bool schur_failed = false;
+  const std::function<void()> deferred = [&]() {     // after any synchronisation that follows the copies above
+    if (upload_rest) HIPCHK(hipStreamSynchronize(side));
+    double amax, asym;
+    std::memcpy(&amax, &host->sym[0], sizeof amax);
+    std::memcpy(&asym, &host->sym[1], sizeof asym);
+    if (asym > 1e-10 * std::max(amax, 1e-300)) throw std::invalid_argument("A must be symmetric (J M^-1 J^T + cfm I is)");
+    if (host->fail) schur_failed = true;
+    if (dense_trace())
+      std::fprintf(stderr, "dense trace schur: ne %d ni %d, symmetry + factor + first check %.3f ms\n", ne, ni,
+                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dev0).count());
+  };
+  // (no inequality rows: nothing synchronises before the final read-back, the checks run there)
+  // Murty on the inequality part; the reference calls the no-bounds overload (lcp.cc:298)
+  std::vector<double> l2(ni), h2(ni);
+  for (int k = 0; k < ni; ++k) { l2[k] = use_bounds ? lo[I[k]] : 0.0; h2[k] = use_bounds ? hi[I[k]] : std::numeric_limits<double>::infinity(); }
+  int piv = 0;
+  bool deferred_ran = false;
+  const std::function<void()> once = [&]() { if (!deferred_ran) { deferred_ran = true; deferred(); } };
+  bool ok = true;
+  if (ni > 0) {
+    ok = murty_device(ws, ni, st.lhs.p, st.rhs.p, l2, h2, use_bounds, block_pivoting, max_pivots, max_seconds, st.xi.p, st.wi.p, &piv, msg,
+                      st.fail_d.p, &once);
+    once();     // (paths of the pivot loop that return without its first synchronisation hook have synchronised all the same)
+    if (schur_failed) { if (msg) *msg = "A_ee is not positive definite"; return false; }
+  }
+  if (pivots) *pivots = piv;
+  if (!ok) return false;
+  Buf<double> xw(ws, (size_t)2 * N);      // x and w in the caller's order: one copy back
+  std::vector<double> xwh((size_t)2 * N);
+  HIPCHK(hipMemsetAsync(xw.p, 0, (size_t)2 * N * sizeof(double), s));     // w = 0 on the equality rows, lcp.cc:332-333
+  if (ne) {
+    st.back_substitute();
+    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ne)), dim3(256), 0, s, ne, dE_p, st.xe.p, xw.p);
+  }
+  if (ni) {
+    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ni)), dim3(256), 0, s, ni, dI_p, st.xi.p, xw.p);
+    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ni)), dim3(256), 0, s, ni, dI_p, st.wi.p, xw.p + N);
+  }
+  HIPCHK(hipMemcpyAsync(xwh.data(), xw.p, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (dx_out) HIPCHK(hipMemcpyAsync(dx_out, xw.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));   // stays on the device too
+  HIPCHK(hipStreamSynchronize(s));
+  once();
+  if (schur_failed) { if (msg) *msg = "A_ee is not positive definite"; return false; }
+  if (x) std::memcpy(x, xwh.data(), (size_t)N * sizeof(double));
+  if (w) std::memcpy(w, xwh.data() + N, (size_t)N * sizeof(double));
+  return true;
+}
+
 }  // namespace
 
 bool dense_mixed_constraints(DenseWorkspace &ws, int N, const double *A, const double *b, const uint8_t *C, const double *lo,
@@ -1672,7 +244,7 @@ bool dense_mixed_constraints(DenseWorkspace &ws, int N, const double *A, const d
   if (pivots) *pivots = 0;
   if (N == 0) return true;
   hipStream_t s = ws.stream;
-  const bool trace = std::getenv("EGS_DENSE_TRACE") != nullptr;
+  const bool trace = dense_trace();
   const auto t_a = std::chrono::steady_clock::now();
   Buf<double> dA(ws, (size_t)N * N), db(ws, N);
   const auto t_b = std::chrono::steady_clock::now();
@@ -1718,273 +290,12 @@ bool dense_mixed_constraints(DenseWorkspace &ws, int N, const double *A, const d
                           chunk ? &rest : nullptr, side);
 }
 
-__global__ void scatter_kernel(int n, const int *idx, const double *src, double *dst) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) dst[idx[k]] = src[k];
-}
-
-// max and min of the diagonal of the factor held in T (the first n columns)
-__global__ void __launch_bounds__(256) diag_minmax_kernel(const double *T, int ld, int n, double *out) {
-  __shared__ double smax[256], smin[256];
-  double mx = 0.0, mn = 1e300;
-  for (int k = threadIdx.x; k < n; k += 256) {
-    const double d = T[(size_t)k * ld + k];
-    mx = d > mx ? d : mx;
-    mn = d < mn ? d : mn;
-  }
-  smax[threadIdx.x] = mx; smin[threadIdx.x] = mn;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      smax[threadIdx.x] = smax[threadIdx.x + o] > smax[threadIdx.x] ? smax[threadIdx.x + o] : smax[threadIdx.x];
-      smin[threadIdx.x] = smin[threadIdx.x + o] < smin[threadIdx.x] ? smin[threadIdx.x + o] : smin[threadIdx.x];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[0] = smax[0]; out[1] = smin[0]; }
-}
-
-// lambda_max(A) by power iteration and 1 / lambda_min(A) by inverse iteration with the blocked Cholesky factor held in
-// T (ld = npad, identity padding) and its inverted diagonal blocks: cond_2(A) = lambda_max / lambda_min for a symmetric
-// positive definite A -- what the reference reads off a JacobiSVD (utils.cc:256-261: sigma_max / sigma_min).  One
-// workgroup, N <= 1024: every vector in LDS, a thread per row for the products, 64-row block steps for the two
-// triangular solves.  out[0] = lambda_max estimate, out[1] = 1 / lambda_min estimate (Rayleigh quotients, both from below).
-constexpr int kCondMaxRows = 1024;
-__global__ void __launch_bounds__(1024) cond_iterations_kernel(const double *A, int N, const double *T, int ld, int npad, const double *inv,
-                                                               int iters, double *out) {
-  __shared__ double v[kCondMaxRows], u[kCondMaxRows], red[1024], part[16][NB], blk[NB];
-  const int tid = threadIdx.x;
-  auto dot = [&](const double *a, const double *b) {
-    double sacc = 0.0;
-    for (int i = tid; i < N; i += 1024) sacc = __builtin_fma(a[i], b[i], sacc);
-    red[tid] = sacc;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-  };
-  auto start = [&]() {     // a start vector with a component along every eigenvector one can reasonably expect
-    for (int i = tid; i < npad; i += 1024) v[i] = i < N ? 1.0 + 0.37 * (double)((unsigned)(i * 2654435761u) >> 22) / 1024.0 : 0.0;
-    __syncthreads();
-  };
-  // ---- lambda_max
-  start();
-  double lmax = 0.0;
-  for (int it = 0; it < iters; ++it) {
-    for (int r = tid; r < N; r += 1024) {
-      double sacc = 0.0;
-      const double *row = A + (size_t)r * N;
-      for (int c = 0; c < N; ++c) sacc = __builtin_fma(row[c], v[c], sacc);
-      u[r] = sacc;
-    }
-    __syncthreads();
-    const double vv = dot(v, v), vu = dot(v, u), uu = dot(u, u);
-    lmax = vu / vv;
-    const double sc = uu > 0.0 ? 1.0 / sqrt(uu) : 0.0;
-    for (int i = tid; i < N; i += 1024) v[i] = u[i] * sc;
-    __syncthreads();
-  }
-  // ---- 1 / lambda_min: z = A^-1 v = L^-T L^-1 v
-  start();
-  double mu = 0.0;
-  const int i64 = tid & 63, p16 = tid >> 6;
-  for (int it = 0; it < iters; ++it) {
-    for (int i = tid; i < npad; i += 1024) u[i] = v[i];
-    __syncthreads();
-    for (int kb = 0; kb < npad; kb += NB) {            // L y = u, block by block: y_kb = Linv_kb u_kb, then the strip below
-      const double *Li = inv + (size_t)(kb / NB) * NB * NB;
-      double sacc = 0.0;
-      for (int c = p16; c < NB; c += 16) sacc = __builtin_fma(Li[i64 * NB + c], u[kb + c], sacc);     // Linv[r][c] = 0 for c > r
-      part[p16][i64] = sacc;
-      __syncthreads();
-      if (tid < NB) {
-        double y = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) y += part[q][tid];
-        blk[tid] = y;
-        u[kb + tid] = y;
-      }
-      __syncthreads();
-      for (int i = kb + NB + tid; i < npad; i += 1024) {
-        double y = u[i];
-        const double *row = T + (size_t)i * ld + kb;
-#pragma unroll 16
-        for (int c = 0; c < NB; ++c) y = __builtin_fma(-row[c], blk[c], y);
-        u[i] = y;
-      }
-      __syncthreads();
-    }
-    for (int kb = npad - NB; kb >= 0; kb -= NB) {      // L^T z = y: z_kb = Linv_kb^T y_kb, then the strip to its left
-      const double *Li = inv + (size_t)(kb / NB) * NB * NB;
-      double sacc = 0.0;
-      for (int r = p16; r < NB; r += 16) sacc = __builtin_fma(Li[r * NB + i64], u[kb + r], sacc);
-      part[p16][i64] = sacc;
-      __syncthreads();
-      if (tid < NB) {
-        double z = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) z += part[q][tid];
-        blk[tid] = z;
-        u[kb + tid] = z;
-      }
-      __syncthreads();
-      for (int c = tid; c < kb; c += 1024) {
-        double y = u[c];
-#pragma unroll 16
-        for (int r = 0; r < NB; ++r) y = __builtin_fma(-T[(size_t)(kb + r) * ld + c], blk[r], y);
-        u[c] = y;
-      }
-      __syncthreads();
-    }
-    const double vv = dot(v, v), vu = dot(v, u), uu = dot(u, u);
-    mu = vu / vv;
-    const double sc = uu > 0.0 ? 1.0 / sqrt(uu) : 0.0;
-    for (int i = tid; i < npad; i += 1024) v[i] = i < N ? u[i] * sc : 0.0;
-    __syncthreads();
-  }
-  if (tid == 0) { out[0] = lmax; out[1] = mu; }
-}
-
-double dense_condition_estimate(DenseWorkspace &ws, int N, const double *dA, bool *spd, double *pivot_bound) {
-  if (spd) *spd = true;
-  if (pivot_bound) *pivot_bound = 1.0;
-  if (N == 0) return 1.0;
-  hipStream_t s = ws.stream;
-  const int npad = (N + NB - 1) / NB * NB;
-  Buf<double> T(ws, (size_t)(npad + 1) * npad), dinv(ws, (size_t)npad * NB), zero(ws, N), mm(ws, 4);
-  Buf<int> idx_d(ws, N), fail_d(ws, 1);
-  std::vector<int> idx(N);
-  for (int i = 0; i < N; ++i) idx[i] = i;
-  HIPCHK(hipMemcpyAsync(idx_d.p, idx.data(), N * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(zero.p, 0, N * sizeof(double), s));
-  HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(build_pivot_kernel, dim3(grid1((size_t)(npad + 1) * npad)), dim3(256), 0, s, dA, N, idx_d.p, N, npad, zero.p, T.p, 0, (int *)nullptr, (int *)nullptr);
-  factor(ws, T.p, npad, npad + 1, npad, fail_d.p, dinv.p);
-  hipLaunchKernelGGL(diag_minmax_kernel, dim3(1), dim3(256), 0, s, T.p, npad, N, mm.p);
-  double h[4] = {1, 1, 0, 0};
-  int fail = 0;
-  HIPCHK(hipMemcpyAsync(h, mm.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&fail, fail_d.p, sizeof fail, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (fail || !(h[1] > 0)) { if (spd) *spd = false; return std::numeric_limits<double>::infinity(); }
-  const double r = h[0] / h[1];
-  if (pivot_bound) *pivot_bound = r * r;
-  if (N > kCondMaxRows) return r * r;      // beyond one workgroup's vectors: the pivot bound (a LOWER bound) is all there is
-  // 60 iterations each: the Rayleigh quotients converge like (lambda_2 / lambda_1)^(2k); both approach from below
-  hipLaunchKernelGGL(cond_iterations_kernel, dim3(1), dim3(1024), 0, s, dA, N, T.p, npad, npad, dinv.p, 60, mm.p + 2);
-  HIPCHK(hipMemcpyAsync(h + 2, mm.p + 2, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const double est = h[2] * h[3];
-  return est > r * r ? est : r * r;          // two lower bounds: the larger one
-}
-
 bool dense_mixed_constraints_device(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C,
                                     const double *lo, const double *hi, bool use_bounds, bool block_pivoting, int max_pivots,
                                     double max_seconds, double *x, double *w, double *dx_out, int *pivots, std::string *msg) {
   return dense_mixed_impl(ws, N, dA_in, db_in, C, lo, hi, use_bounds, block_pivoting, max_pivots, max_seconds, x, w, dx_out, pivots, msg,
                           nullptr, nullptr);
 }
-
-namespace {
-bool dense_mixed_impl(DenseWorkspace &ws, int N, const double *dA_in, const double *db_in, const uint8_t *C, const double *lo, const double *hi,
-                      bool use_bounds, bool block_pivoting, int max_pivots, double max_seconds, double *x, double *w, double *dx_out,
-                      int *pivots, std::string *msg, const std::function<void()> *upload_rest, hipStream_t side) {
-  if (pivots) *pivots = 0;
-  if (N == 0) return true;
-  hipStream_t s = ws.stream;
-  const auto t_dev0 = std::chrono::steady_clock::now();
-  std::vector<int> E, I;
-  for (int i = 0; i < N; ++i) (C[i] ? E : I).push_back(i);
-  const int ne = (int)E.size(), ni = (int)I.size();
-  const int nepad = (ne + NB - 1) / NB * NB;
-  const int ld = nepad + ni, rows = nepad + ni + 1;
-  Buf<double> T(ws, (size_t)rows * (ld > 0 ? ld : 1)), lhs(ws, (size_t)ni * ni), rhs(ws, ni), xi(ws, ni), wi(ws, ni), xe(ws, ne), xs(ws, nepad), dinv(ws, (size_t)nepad * NB);
-  Buf<int> dEI(ws, N), fail_d(ws, 1);
-  int *const dE_p = dEI.p, *const dI_p = dEI.p + ne;
-  struct { const double *p; } dA{dA_in}, db{db_in};
-  {
-    std::vector<int> EI(E);
-    EI.insert(EI.end(), I.begin(), I.end());
-    HIPCHK(hipMemcpyAsync(dEI.p, EI.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
-  }
-  HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
-  // A must be symmetric: the factorisations read its lower triangle only.  The verdict (and the Schur factorisation's
-  // failure flag) is read at the first synchronisation the pivot loop makes anyway, not at one of its own.
-  Buf<unsigned long long> sym_d(ws, 2);
-  HostWords *host = &pinned_records(ws)->words;
-  auto check_symmetry = [&](hipStream_t q) {
-    HIPCHK(hipMemsetAsync(sym_d.p, 0, 2 * sizeof(unsigned long long), q));
-    hipLaunchKernelGGL(symmetry_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, q, dA.p, N, sym_d.p);
-    HIPCHK(hipMemcpyAsync(host->sym, sym_d.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, q));
-  };
-  if (!upload_rest) check_symmetry(s);
-  // Schur stage: factor the E columns of [A_ee A_ei; A_ie A_ii; b^T]   (lcp.cc:286-294)
-  hipLaunchKernelGGL(build_schur_kernel, dim3(grid1((size_t)rows * ld)), dim3(256), 0, s, dA.p, db.p, N, dE_p, ne, nepad, dI_p, ni, T.p,
-                     upload_rest ? 1 : 0);
-  factor(ws, T.p, ld, rows, nepad, fail_d.p, dinv.p);
-  if (ni) hipLaunchKernelGGL(extract_schur_kernel, dim3(grid1((size_t)ni * ni)), dim3(256), 0, s, T.p, nepad, ni, lhs.p, rhs.p);
-  HIPCHK(hipMemcpyAsync(&host->fail, fail_d.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (upload_rest) {      // the device is busy with the Schur stage: now the rest of A, then the symmetry check, on the side stream
-    (*upload_rest)();
-    check_symmetry(side);
-  }
-  bool schur_failed = false;
-  const std::function<void()> deferred = [&]() {     // after any synchronisation that follows the copies above
-    if (upload_rest) HIPCHK(hipStreamSynchronize(side));
-    double amax, asym;
-    std::memcpy(&amax, &host->sym[0], sizeof amax);
-    std::memcpy(&asym, &host->sym[1], sizeof asym);
-    if (asym > 1e-10 * std::max(amax, 1e-300)) throw std::invalid_argument("A must be symmetric (J M^-1 J^T + cfm I is)");
-    if (host->fail) schur_failed = true;
-    if (std::getenv("EGS_DENSE_TRACE"))
-      std::fprintf(stderr, "dense trace schur: ne %d ni %d, symmetry + factor + first check %.3f ms\n", ne, ni,
-                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dev0).count());
-  };
-  // (no inequality rows: nothing synchronises before the final read-back, the checks run there)
-  // Murty on the inequality part; the reference calls the no-bounds overload (lcp.cc:298)
-  std::vector<double> l2(ni), h2(ni);
-  for (int k = 0; k < ni; ++k) { l2[k] = use_bounds ? lo[I[k]] : 0.0; h2[k] = use_bounds ? hi[I[k]] : std::numeric_limits<double>::infinity(); }
-  int piv = 0;
-  bool deferred_ran = false;
-  const std::function<void()> once = [&]() { if (!deferred_ran) { deferred_ran = true; deferred(); } };
-  bool ok = true;
-  if (ni > 0) {
-    ok = murty_device(ws, ni, lhs.p, rhs.p, l2, h2, use_bounds, block_pivoting, max_pivots, max_seconds, xi.p, wi.p, &piv, msg, fail_d.p, &once);
-    once();     // (paths of the pivot loop that return without its first synchronisation hook have synchronised all the same)
-    if (schur_failed) { if (msg) *msg = "A_ee is not positive definite"; return false; }
-  }
-  if (pivots) *pivots = piv;
-  if (!ok) return false;
-  // x_e = A_ee^-1 (b_e - A_ei x_i) = L^-T (L^-1 b_e - (L^-1 A_ei) x_i)   (lcp.cc:317)
-  Buf<double> xw(ws, (size_t)2 * N);      // x and w in the caller's order: one copy back
-  std::vector<double> xwh((size_t)2 * N);
-  HIPCHK(hipMemsetAsync(xw.p, 0, (size_t)2 * N * sizeof(double), s));     // w = 0 on the equality rows, lcp.cc:332-333
-  if (ne) {
-    hipLaunchKernelGGL(xe_rhs_kernel, dim3(nepad / NB), dim3(1024), 0, s, T.p, nepad, ni, xi.p);
-    launch_back_solve(ws, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p,
-                       dinv.p);
-    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ne)), dim3(256), 0, s, ne, dE_p, xe.p, xw.p);
-  }
-  if (ni) {
-    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ni)), dim3(256), 0, s, ni, dI_p, xi.p, xw.p);
-    hipLaunchKernelGGL(scatter_kernel, dim3(grid1(ni)), dim3(256), 0, s, ni, dI_p, wi.p, xw.p + N);
-  }
-  HIPCHK(hipMemcpyAsync(xwh.data(), xw.p, (size_t)2 * N * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (dx_out) HIPCHK(hipMemcpyAsync(dx_out, xw.p, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));   // stays on the device too
-  HIPCHK(hipStreamSynchronize(s));
-  once();
-  if (schur_failed) { if (msg) *msg = "A_ee is not positive definite"; return false; }
-  if (x) std::memcpy(x, xwh.data(), (size_t)N * sizeof(double));
-  if (w) std::memcpy(w, xwh.data() + N, (size_t)N * sizeof(double));
-  return true;
-}
-
-}  // namespace
-
 
 // ---- lcp::SolveLCP_BoxSchur (toolkit/lcp.cc:627-747) -------------------------------------------------
 namespace {
@@ -2066,20 +377,17 @@ bool box_lcp_schur(DenseWorkspace &ws, int n, double *A, const double *b_arg, co
   // Schur stage on the caller's matrix (lower triangle) read through the permutation: E = perm[0, nub), I = the rest
   HIPCHK(hipMemcpyAsync(dA.p, A, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(db.p, b_arg, n * sizeof(double), hipMemcpyHostToDevice, s));
-  const int nepad = (ne + NB - 1) / NB * NB;
-  const int ld = nepad + ni, rows = nepad + ni + 1;
-  Buf<double> T(ws, (size_t)rows * ld), lhs(ws, (size_t)ni * ni), rhs(ws, ni), xi(ws, ni), wi(ws, ni), xe(ws, ne), xs(ws, nepad), dinv(ws, (size_t)nepad * NB), dl2(ws, ni), dh2(ws, ni);
-  Buf<int> dE(ws, ne), dI(ws, ni), fail_d(ws, 1);
+  SchurStage st(ws, ne, ni);
+  Buf<double> dl2(ws, ni), dh2(ws, ni);
+  Buf<int> dE(ws, ne), dI(ws, ni);
   HIPCHK(hipMemcpyAsync(dE.p, perm.data(), ne * sizeof(int), hipMemcpyHostToDevice, s));
   if (ni) HIPCHK(hipMemcpyAsync(dI.p, perm.data() + ne, ni * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(fail_d.p, 0, sizeof(int), s));
-  hipLaunchKernelGGL(build_schur_kernel, dim3(grid1((size_t)rows * ld)), dim3(256), 0, s, dA.p, db.p, n, dE.p, ne, nepad, dI.p, ni, T.p, 1);
-  factor(ws, T.p, ld, rows, nepad, fail_d.p, dinv.p);            // L L' = Z, Q = L^-1 B', R = C - Q'Q, rhs = d - B Z^-1 c
-  if (ni) hipLaunchKernelGGL(extract_schur_kernel, dim3(grid1((size_t)ni * ni)), dim3(256), 0, s, T.p, nepad, ni, lhs.p, rhs.p);
+  HIPCHK(hipMemsetAsync(st.fail_d.p, 0, sizeof(int), s));
+  st.eliminate(dA.p, db.p, n, dE.p, dI.p, 1);            // L L' = Z, Q = L^-1 B', R = C - Q'Q, rhs = d - B Z^-1 c
   // meanwhile the host applies the partition to the caller's lower triangle, as the reference leaves it
   for (const auto &sw : swaps) swap_rows_and_columns_lower(A, n, sw.first, sw.second);
   int fail = 0;
-  HIPCHK(hipMemcpyAsync(&fail, fail_d.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&fail, st.fail_d.p, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (fail) { if (msg) *msg = "the unbounded block Z is not positive definite"; return false; }
   if (ni) {
@@ -2088,21 +396,21 @@ bool box_lcp_schur(DenseWorkspace &ws, int n, double *A, const double *b_arg, co
     if (ni <= kIncrementalMaxRows) {
       HIPCHK(hipMemcpyAsync(dl2.p, l2.data(), ni * sizeof(double), hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(dh2.p, h2.data(), ni * sizeof(double), hipMemcpyHostToDevice, s));
-      good = box_lcp_incremental_device(s, algorithm, ni, lhs.p, rhs.p, dl2.p, dh2.p, l2.data(), h2.data(), max_steps, max_seconds, xi.p, wi.p, &piv, msg);
+      good = box_lcp_incremental_device(s, algorithm, ni, st.lhs.p, st.rhs.p, dl2.p, dh2.p, l2.data(), h2.data(), max_steps, max_seconds,
+                                        st.xi.p, st.wi.p, &piv, msg);
     } else {
-      good = murty_device(ws, ni, lhs.p, rhs.p, l2, h2, true, true, max_steps, max_seconds, xi.p, wi.p, &piv, msg);
+      good = murty_device(ws, ni, st.lhs.p, st.rhs.p, l2, h2, true, true, max_steps, max_seconds, st.xi.p, st.wi.p, &piv, msg);
     }
     if (pivots) *pivots = piv;
     if (!good) return false;
   }
   // y = Z^-1 (c - B' z) = L^-T (L^-1 c - Q z)
   std::vector<double> xih(ni), wih(ni), xeh(ne);
-  hipLaunchKernelGGL(xe_rhs_kernel, dim3(nepad / NB), dim3(1024), 0, s, T.p, nepad, ni, xi.p);
-  launch_back_solve(ws, T.p, ld, nepad, nepad + ni, ne, (const int *)nullptr, xe.p, xs.p, dinv.p);
-  HIPCHK(hipMemcpyAsync(xeh.data(), xe.p, ne * sizeof(double), hipMemcpyDeviceToHost, s));
+  st.back_substitute();
+  HIPCHK(hipMemcpyAsync(xeh.data(), st.xe.p, ne * sizeof(double), hipMemcpyDeviceToHost, s));
   if (ni) {
-    HIPCHK(hipMemcpyAsync(xih.data(), xi.p, ni * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(wih.data(), wi.p, ni * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(xih.data(), st.xi.p, ni * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(wih.data(), st.wi.p, ni * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   HIPCHK(hipStreamSynchronize(s));
   for (int k = 0; k < ne; ++k) { x[perm[k]] = xeh[k]; w[perm[k]] = 0.0; }          // Unpermute (:741-744)

@@ -9,8 +9,8 @@
 namespace egs {
 
 // Ensembles of at most this many rows (3 per constraint) are solved by the fused kernel, one workgroup each;
-// larger ones go through the multi-launch path of dense_lcp.hip.  Size classes: <= 32 and <= 64 rows run on one
-// wavefront, <= 112 on four.
+// larger ones go through the multi-launch path (dense_mixed_constraints_device, dense_lcp.hip).  Size classes: <= 32 and <= 64 rows run on
+// one wavefront, <= 112 on four.
 constexpr int kDenseClassRows[3] = {32, 64, 112};
 constexpr int kFusedDenseMax = 112;
 

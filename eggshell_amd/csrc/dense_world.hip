@@ -2,7 +2,7 @@
 // (egs_world_step_dense): the dense J M^-1 J^T of each ensemble, then ONE workgroup per ensemble runs the rest
 // without the host: CheckMatrixCondition against kGoodConditionNumber = 1e7 (ensembles.cc:513-521), the Schur
 // complement over the equality rows (lcp.cc:286-294), the reference's Murty loop on the inequality rows
-// (lcp.cc:157-274, as murty_small_kernel in dense_lcp.hip) and x_e = A_ee^-1 (b_e - A_ei x_i) (lcp.cc:317).
+// (lcp.cc:157-274, as murty_small_kernel in dense_murty.hip) and x_e = A_ee^-1 (b_e - A_ei x_i) (lcp.cc:317).
 // dense_world_friction_kernel is the same body around the stage's pyramid form (egs_world_set_dense_friction): rows 0
 // and 1 of a constraint with mu >= 0 are pyramid rows of its row 2, mu read per gathered constraint.
 #include <hip/hip_runtime.h>
@@ -153,7 +153,7 @@ __device__ __forceinline__ void dense_world_body(double *sm, MixedSolveShared<MA
       __syncthreads();
     }
     // lambda_max by power iteration on A, 1 / lambda_min by power iteration on A^-1, side by side: the start vector
-    // and the 60 iterations of dense_condition_estimate (dense_lcp.hip); Rayleigh quotients, both from below
+    // and the 60 iterations of dense_condition_estimate (dense_factor.hip); Rayleigh quotients, both from below
     double *v1 = x, *u1 = w, *v2 = r, *u2 = y;
     for (int i = tid; i < N; i += BLOCK) {
       const double s0 = 1.0 + 0.37 * (double)((unsigned)(i * 2654435761u) >> 22) / 1024.0;

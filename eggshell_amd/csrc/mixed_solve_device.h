@@ -2,7 +2,7 @@
 // dense_world_fused_kernel (dense_world.hip, a world's ensembles) and mixed_batch_kernel (mixed_batch.hip, a caller's
 // packed matrices) share: partition by C, packed right-looking Cholesky of A_ee with [A_ei | b_e] riding through the
 // forward substitution, the Schur complement, the reference's Murty loop (lcp.cc:157-274, as murty_small_kernel in
-// dense_lcp.hip) and x_e = A_ee^-1 (b_e - A_ei x_i).  Every fused operation is an explicit fma: both kernels compute
+// dense_murty.hip) and x_e = A_ee^-1 (b_e - A_ei x_i).  Every fused operation is an explicit fma: both kernels compute
 // the same bits from the same rows.
 //
 // The PYRAMID form (template flag PYR; egs_mixed_friction_solve_batch) wraps the Murty loop in the

@@ -92,9 +92,10 @@ struct PinnedBuf {
   ~PinnedBuf() { release(); }
 };
 
-// What the dense solvers (dense_lcp.hip) keep between calls.  A context owns one: everything in it is used only by
-// work enqueued on that context's stream, under that context's device, and all of it is created on first use.
-struct DensePinned;      // dense_lcp.hip: the records the device writes for the host (pivot step, deferred checks)
+// What the dense solvers (dense_lcp.hip, dense_factor.hip, dense_murty.hip) keep between calls.  A context owns one:
+// everything in it is used only by work enqueued on that context's stream, under that context's device, and all of it
+// is created on first use.
+struct DensePinned;      // dense_internal.h: the records the device writes for the host (pivot step, deferred checks)
 struct DenseWorkspace {
   hipStream_t stream = nullptr;      // the owning context's
   // Device scratch.  A solve takes some twenty-five buffers; hipMalloc + hipFree for each of them (hipFree synchronises

@@ -1,6 +1,7 @@
-"""The mixed box LCP as mathematics: a CERTIFIED reference for the dense direct solvers (dense_lcp.hip, dantzig.hip,
-mixed_solve_device.h / mixed_batch.hip, the fused solve of dense_world.hip).  numpy and math.fsum only; nothing from
-oracle/ takes part in a reference value, and no pivot rule is restated.
+"""The mixed box LCP as mathematics: a CERTIFIED reference for the dense direct solvers (dense_lcp.hip on
+dense_factor.hip and dense_murty.hip, dantzig.hip, mixed_solve_device.h / mixed_batch.hip, the fused solve of
+dense_world.hip).  numpy and math.fsum only; nothing from oracle/ takes part in a reference value, and no pivot rule is
+restated.
 
   find x, w = A x - b with     w_r = 0                    on an equality row (x_r free)
                                lo_r <= x_r <= hi_r and    w_r = 0 inside, w_r >= 0 on lo_r, w_r <= 0 on hi_r   otherwise

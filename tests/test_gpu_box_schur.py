@@ -116,3 +116,33 @@ def test_limits_and_refusals(ctx):
     assert e.value.status == capi.ERR_INVALID
     Abad = A.copy(); Abad[0, 0] = -1.0        # Z not positive definite
     assert not ctx.box_lcp_schur(np.tril(Abad), b, lo, hi)[0]
+
+
+@pytest.mark.parametrize("n,unbounded", [(1100, 0.0), (1200, 0.05)])
+def test_block_rule_beyond_the_incremental_solver(ctx, n, unbounded):
+    """More bounded rows than the incremental-factor solver takes (1 024): the box LCP goes to the pivot loop with the
+    block rule, on the matrix itself when every row is bounded (n = 1 100) and on the Schur complement otherwise
+    (n = 1 200, 62 unbounded and 1 138 bounded rows).  The recipe of
+    test_gpu_dense_block.py::test_block_rule_between_the_round_sizes and its flat tolerances.  Seed n + 1: in float64 on
+    the host (tests/lcp_reference.py: find_set) both problems are solvable and no bounded row has |x - bound| and |w|
+    below 1.5e-4; seed n = 1 100 has one at 8e-6."""
+    rng = np.random.default_rng(n + 1)
+    M = rng.uniform(-1, 1, (n, n))
+    A = M.T @ M + 1e-2 * np.eye(n)
+    b = rng.uniform(-1, 1, n) * 3.0
+    lo = np.where(rng.uniform(size=n) < 0.5, -0.2, 0.0)
+    hi = np.where(rng.uniform(size=n) < 0.5, 0.3, np.inf)
+    free = rng.uniform(size=n) < unbounded
+    lo[free] = -BIG; hi[free] = BIG
+    ok, x, w, Ap, perm, nub, piv = ctx.box_lcp_schur(np.tril(A), b, lo, hi)
+    assert ok
+    assert nub == free.sum() and np.array_equal(np.sort(perm), np.arange(n))
+    assert np.linalg.norm(A @ x - b - w) <= 1e-6 * max(1.0, np.linalg.norm(A @ x))
+    assert not w[free].any()
+    xi, wi, li, hi_i = x[~free], w[~free], lo[~free], hi[~free]
+    tol = 1e-7
+    assert (xi >= li - tol).all() and (xi <= hi_i + tol).all()
+    inside = (xi > li + tol) & (xi < hi_i - tol)
+    assert np.abs(wi[inside]).max(initial=0.0) < 1e-6
+    assert (wi[np.abs(xi - li) <= tol] >= -1e-6).all() and (wi[np.abs(xi - hi_i) <= tol] <= 1e-6).all()
+    # (flat and loose on purpose: the measured bounds in units of u are test_gpu_lcp_reference.py's, DESIGN 7d)

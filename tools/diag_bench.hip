@@ -1,4 +1,4 @@
-// Micro-benchmark of the 64 x 64 diagonal-tile factorisation (chol_diag_tile of eggshell_amd/csrc/dense_lcp.hip):
+// Micro-benchmark of the 64 x 64 diagonal-tile factorisation (chol_diag_tile of eggshell_amd/csrc/dense_factor.hip):
 // the latency chain that bounds every panel step of the blocked Cholesky.  Variants are timed inside one launch
 // (reps repetitions on a tile staged in LDS) and checked against a host Cholesky + inverse.
 //   hipcc -O3 --offload-arch=gfx950 -o diag_bench diag_bench.hip && ./diag_bench
