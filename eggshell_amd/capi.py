@@ -18,7 +18,7 @@ JACOBI, GAUSS_SEIDEL, SOR = 0, 1, 2
 F64, F32 = 0, 1
 JOINT_BALL, CONTACT_BOX, JOINT_LOCK, JOINT_HINGE_AXIS = 0, 1, 2, 3
 JOINT_SLIDER_AXIS = 5   # 4 is no kind (it stays invalid)
-SHAPE_BOX, SHAPE_SPHERE = 0, 1
+SHAPE_BOX, SHAPE_SPHERE, SHAPE_CAPSULE = 0, 1, 2
 MV_LOWER, MV_UPPER, MV_DIAG, MV_FULL = 1, 2, 4, 8
 SCHED_QUAD, SCHED_ISO, SCHED_QUAD_PATCHES, SCHED_LANE_PATCHES, SCHED_ALL_GLOBAL, SCHED_STATIC, SCHED_LEAN = 1, 2, 4, 8, 16, 32, 64   # SCHED_LEAN: reserved, never reported
 SCHED_LINSYM = 128
@@ -370,8 +370,9 @@ class Context:
         return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
 
     def update_contacts_shapes(self, pos, R, side, shape=None, max_contacts=None, joints=None):
-        """update_contacts with a shape per body (egs_update_contacts_shapes): SHAPE_BOX / SHAPE_SPHERE [n], a sphere's
-        side row being (d, d, d); shape None = all boxes.  joints as in update_contacts."""
+        """update_contacts with a shape per body (egs_update_contacts_shapes): SHAPE_BOX / SHAPE_SPHERE /
+        SHAPE_CAPSULE [n], a sphere's side row being (d, d, d) and a capsule's (d, d, l) with l > d, its axis column 2 of
+        R; shape None = all boxes.  joints as in update_contacts."""
         pos, R, side, shape = _f64(pos), _f64(R), _f64(side), _i32(shape)
         n = pos.reshape(-1, 3).shape[0]
         jb0, jb1, jd = (_i32(joints[0]), _i32(joints[1]), _f64(joints[2])) if joints is not None else (None, None, None)
@@ -1036,8 +1037,9 @@ class World:
         return Minv, f_ext
 
     def set_shapes(self, shape):
-        """A shape per body, SHAPE_BOX / SHAPE_SPHERE [n] (egs_world_set_shapes); None switches back to boxes.  A
-        sphere's side row is (d, d, d); its inertia is the caller's Minv."""
+        """A shape per body, SHAPE_BOX / SHAPE_SPHERE / SHAPE_CAPSULE [n] (egs_world_set_shapes); None switches back to
+        boxes.  A sphere's side row is (d, d, d), a capsule's (d, d, l) with l > d (diameter, tip-to-tip length; the axis
+        is column 2 of R); the inertia is the caller's Minv."""
         shape = _i32(shape)
         if shape is not None and shape.shape != (self.n,):
             raise ValueError("shape has shape %s: the world has %d bodies" % (shape.shape, self.n))

@@ -17,8 +17,9 @@
 //   2. flatten candidates (scan)      -> pair list in (i, j) order
 //   3. narrow_kernel<false, .>        per pair: SAT + clipping, count kept contacts
 //   4. scan, narrow_kernel<true, .> + ground emit  -> final arrays
-// With a shape array (egs_shape per body) the same pipeline runs the SHAPES = true instantiations, which
-// add sphere-ground, sphere-sphere and sphere-box beside the box code (collide.h has the geometry).
+// With a shape array (egs_shape per body) the same pipeline runs the SHAPES = 1 instantiations, which
+// add sphere-ground, sphere-sphere and sphere-box beside the box code, or -- where the array holds a capsule --
+// the SHAPES = 2 instantiations, which add the four capsule cases (collide.h has the geometry).
 // Arithmetic follows oracle/collision.c operation by operation (fp64,
 // -ffp-contract=off), so the contact set is bit-identical to the CPU oracle's.
 #include <hip/hip_runtime.h>
@@ -388,14 +389,216 @@ __device__ int collide_sphere_box(const double *cS, const double *sideS, const d
   return 1;
 }
 
+// ---- capsules (collide.h states the geometry) ---------------------------------
+// A capsule is a body whose side row is (d, d, l), l > d: r = side[0] * 0.5, e = (side[2] - side[0]) * 0.5, axis
+// u = (R[2], R[5], R[8]); the ball at t is centred at c_k + t * u_k (one product, one sum).  Every contact is a sphere
+// rule applied to such a ball, so the sphere functions above are called with the capsule's own side row (they read
+// side[0] alone).  One operation order each, restated in numpy by tests/capsule_twin.py.
+constexpr int kShapeCapsule = 2;   // EGS_SHAPE_CAPSULE
+constexpr double kFlat = 1e-9;     // the flat rule: an interior candidate this close (centre distance) to an emitted end is dropped
+
+struct Capsule { double e; double u[3]; };
+__device__ __forceinline__ Capsule capsule_of(const double *R, const double *side) {
+  return Capsule{(side[2] - side[0]) * 0.5, {R[2], R[5], R[8]}};
+}
+__device__ __forceinline__ void ball_at(const double *c, const double *u, double t, double *b) {
+  b[0] = c[0] + t * u[0]; b[1] = c[1] + t * u[1]; b[2] = c[2] + t * u[2];
+}
+
+// collide_spheres with the centre distance L reported (written whether or not there is a contact)
+__device__ int collide_balls(const double *ci, const double *si, const double *cj, const double *sj, double *out, double *Lout) {
+  const double ri = si[0] * 0.5, rj = sj[0] * 0.5;
+  const double d[3] = {cj[0] - ci[0], cj[1] - ci[1], cj[2] - ci[2]};
+  const double L = sqrt(dot3(d, d));
+  *Lout = L;
+  const double s = L - (ri + rj);
+  if (s > 0) return 0;
+  double n[3] = {0, 0, 1};
+  if (L != 0) { n[0] = d[0] / L; n[1] = d[1] / L; n[2] = d[2] / L; }
+  const double t = ((ri + L) - rj) * 0.5;
+  for (int k = 0; k < 3; ++k) { out[k] = ci[k] + n[k] * t; out[3 + k] = n[k]; }
+  out[6] = -s;
+  return 1;
+}
+
+// ground_sphere on the ball at -e, then on the ball at +e
+__device__ int ground_capsule(const double *c, const double *R, const double *side, double *out) {
+  const Capsule C = capsule_of(R, side);
+  double b[3];
+  ball_at(c, C.u, -C.e, b);
+  int n = ground_sphere(b, side, out);
+  ball_at(c, C.u, C.e, b);
+  n += ground_sphere(b, side, out ? out + 7 * n : nullptr);
+  return n;
+}
+
+// t = min(max(dot3(cS - cC, u), -e), e): the parameter of the capsule's ball nearest the point cS
+__device__ __forceinline__ double capsule_nearest(const double *cC, const Capsule &C, const double *cS) {
+  const double w[3] = {cS[0] - cC[0], cS[1] - cC[1], cS[2] - cC[2]};
+  return fmin(fmax(dot3(w, C.u), -C.e), C.e);
+}
+
+// The capsule's ball nearest the sphere's centre against the sphere, in the pair's order (first = the capsule is body0).
+__device__ int collide_capsule_sphere(const double *cC, const double *RC, const double *sideC, const double *cS,
+                                      const double *sideS, bool first, double *out) {
+  const Capsule C = capsule_of(RC, sideC);
+  double b[3];
+  ball_at(cC, C.u, capsule_nearest(cC, C, cS), b);
+  return first ? collide_spheres(b, sideC, cS, sideS, out) : collide_spheres(cS, sideS, b, sideC, out);
+}
+
+// Capsules i < j.  Candidates in order: end 0 of i, end 1 of i (each against j's nearest ball), end 0 of j, end 1 of j
+// (each against i's nearest ball), then the interior pair:
+//   w = cj - ci;  A = ui.ui;  B = uj.uj;  a = ui.uj;  p = ui.w;  q = uj.w;  det = A * B - a * a
+//   s = (p * B - a * q) / det;  t = (a * p - A * q) / det;  exists iff det != 0, -ei < s < ei and -ej < t < ej
+// (two capsules with the same R bits have A = B = a, det = 0 exactly).  The interior pair is dropped if an emitted end
+// candidate's centre distance L is within kFlat of its own.  Every candidate is collide_balls(ball of i, ball of j).
+__device__ int collide_capsules(const double *ci, const double *Ri, const double *si, const double *cj, const double *Rj,
+                                const double *sj, double *out) {
+  const Capsule Ci = capsule_of(Ri, si), Cj = capsule_of(Rj, sj);
+  int n = 0;
+  double Lend[4], L, bi[3], bj[3];
+  bool hit[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double te = (q & 1) ? 1.0 : -1.0;
+    if (q < 2) { ball_at(ci, Ci.u, te * Ci.e, bi); ball_at(cj, Cj.u, capsule_nearest(cj, Cj, bi), bj); }
+    else       { ball_at(cj, Cj.u, te * Cj.e, bj); ball_at(ci, Ci.u, capsule_nearest(ci, Ci, bj), bi); }
+    const int c = collide_balls(bi, si, bj, sj, out + 7 * n, &L);
+    hit[q] = c != 0; Lend[q] = L;
+    n += c;
+  }
+  const double w[3] = {cj[0] - ci[0], cj[1] - ci[1], cj[2] - ci[2]};
+  const double A = dot3(Ci.u, Ci.u), B = dot3(Cj.u, Cj.u), a = dot3(Ci.u, Cj.u), p = dot3(Ci.u, w), q = dot3(Cj.u, w);
+  const double det = A * B - a * a;
+  if (det != 0) {
+    const double s = (p * B - a * q) / det, t = (a * p - A * q) / det;
+    if (s > -Ci.e && s < Ci.e && t > -Cj.e && t < Cj.e) {
+      double row[7];
+      ball_at(ci, Ci.u, s, bi); ball_at(cj, Cj.u, t, bj);
+      const int c = collide_balls(bi, si, bj, sj, row, &L);
+      bool flat = false;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) flat |= hit[k] && fabs(Lend[k] - L) <= kFlat;
+      if (c && !flat) { for (int k = 0; k < 7; ++k) out[7 * n + k] = row[k]; ++n; }
+    }
+  }
+  return n;
+}
+
+// dist(t)^2 of the capsule axis in the box frame: p_k = p0_k + t * ub_k;  q_k = min(max(p_k, -h_k), h_k);  e = p - q;  e.e
+__device__ __forceinline__ double axis_dist2(const double *p0, const double *ub, const double *h, double t) {
+  double e[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double p = p0[k] + t * ub[k];
+    e[k] = p - fmin(fmax(p, -h[k]), h[k]);
+  }
+  return dot3(e, e);
+}
+
+#define EGS_CSWAP(a, b) { const double lo_ = fmin(a, b), hi_ = fmax(a, b); a = lo_; b = hi_; }
+
+// Capsule C against box B; flip = the capsule is body0.  Candidates: the ball at -e, the ball at +e, the ball at t*,
+// each through collide_sphere_box.  In the box frame the axis is p0 + t ub:
+//   dc = cC - cB;  p0_k = (R[k] dc0 + R[3 + k] dc1) + R[6 + k] dc2;  ub_k = (R[k] u0 + R[3 + k] u1) + R[6 + k] u2;  h_k = sideB[k] * 0.5
+//   breakpoints x_{2k} = (-h_k - p0_k) / ub_k, x_{2k+1} = (h_k - p0_k) / ub_k  (ub_k == 0: both +inf)
+//   clip: lo = max(-e, min(x_{2k}, x_{2k+1}) over k), hi = min(e, max(x_{2k}, x_{2k+1}) over k); a k with ub_k == 0 and
+//   |p0_k| > h_k empties it.  lo <= hi (the axis enters the box): t* = (lo + hi) * 0.5.
+//   Otherwise tau_0 = -e, tau_1..6 = the breakpoints clamped to [-e, e] and sorted (a fixed network), tau_7 = e; for
+//   piece i = 0..6: m = (tau_i + tau_{i+1}) * 0.5, sg_k = +1 if p_k(m) > h_k, -1 if p_k(m) < -h_k, else 0 (inactive),
+//   num = sum over active k of ub_k * (p0_k - sg_k h_k), den = sum over active k of ub_k * ub_k (k ascending, from 0),
+//   s_i = min(max(-num / den, tau_i), tau_{i+1}) if den > 0.  t* = the candidate with the lowest axis_dist2 among
+//   tau_0, s_0, tau_1, s_1, ..., s_6, tau_7 in this order, the first on a tie.
+//   t* counts iff -e < t* < e;  D(t) = sqrt(axis_dist2(t));  the interior candidate is dropped if an emitted end's D is
+//   within kFlat of D(t*).
+__device__ int collide_capsule_box(const double *cC, const double *RC, const double *sideC, const double *cB,
+                                   const double *RB, const double *sideB, bool flip, double *out) {
+  const Capsule C = capsule_of(RC, sideC);
+  const double dc[3] = {cC[0] - cB[0], cC[1] - cB[1], cC[2] - cB[2]};
+  double p0[3], ub[3], h[3], x0, x1, x2, x3, x4, x5;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p0[k] = (RB[k] * dc[0] + RB[3 + k] * dc[1]) + RB[6 + k] * dc[2];
+    ub[k] = (RB[k] * C.u[0] + RB[3 + k] * C.u[1]) + RB[6 + k] * C.u[2];
+    h[k] = sideB[k] * 0.5;
+  }
+  double lo = -C.e, hi = C.e;
+#define EGS_SLAB(k, xa, xb)                                                      \
+  if (ub[k] != 0) {                                                              \
+    xa = (-h[k] - p0[k]) / ub[k]; xb = (h[k] - p0[k]) / ub[k];                   \
+    lo = fmax(lo, fmin(xa, xb)); hi = fmin(hi, fmax(xa, xb));                    \
+  } else {                                                                       \
+    xa = INFINITY; xb = INFINITY;                                                \
+    if (fabs(p0[k]) > h[k]) hi = -INFINITY;                                      \
+  }
+  EGS_SLAB(0, x0, x1) EGS_SLAB(1, x2, x3) EGS_SLAB(2, x4, x5)
+#undef EGS_SLAB
+  double ts;
+  if (lo <= hi) {
+    ts = (lo + hi) * 0.5;
+  } else {
+    x0 = fmin(fmax(x0, -C.e), C.e); x1 = fmin(fmax(x1, -C.e), C.e); x2 = fmin(fmax(x2, -C.e), C.e);
+    x3 = fmin(fmax(x3, -C.e), C.e); x4 = fmin(fmax(x4, -C.e), C.e); x5 = fmin(fmax(x5, -C.e), C.e);
+    EGS_CSWAP(x0, x5) EGS_CSWAP(x1, x3) EGS_CSWAP(x2, x4)
+    EGS_CSWAP(x1, x2) EGS_CSWAP(x3, x4)
+    EGS_CSWAP(x0, x3) EGS_CSWAP(x2, x5)
+    EGS_CSWAP(x0, x1) EGS_CSWAP(x2, x3) EGS_CSWAP(x4, x5)
+    EGS_CSWAP(x1, x2) EGS_CSWAP(x3, x4)
+    const double tau[8] = {-C.e, x0, x1, x2, x3, x4, x5, C.e};
+    ts = tau[0];
+    double best = axis_dist2(p0, ub, h, ts);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const double m = (tau[i] + tau[i + 1]) * 0.5;
+      double num = 0, den = 0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double p = p0[k] + m * ub[k];
+        const double sg = p > h[k] ? 1.0 : (p < -h[k] ? -1.0 : 0.0);
+        if (sg != 0) { num = num + ub[k] * (p0[k] - sg * h[k]); den = den + ub[k] * ub[k]; }
+      }
+      if (den > 0) {
+        const double s = fmin(fmax(-num / den, tau[i]), tau[i + 1]);
+        const double f = axis_dist2(p0, ub, h, s);
+        if (f < best) { best = f; ts = s; }
+      }
+      const double f = axis_dist2(p0, ub, h, tau[i + 1]);
+      if (f < best) { best = f; ts = tau[i + 1]; }
+    }
+  }
+  int n = 0;
+  double b[3];
+  ball_at(cC, C.u, -C.e, b);
+  const int n0 = collide_sphere_box(b, sideC, cB, RB, sideB, flip, out);
+  n += n0;
+  ball_at(cC, C.u, C.e, b);
+  const int n1 = collide_sphere_box(b, sideC, cB, RB, sideB, flip, out + 7 * n);
+  n += n1;
+  if (ts > -C.e && ts < C.e) {
+    const double Ds = sqrt(axis_dist2(p0, ub, h, ts));
+    bool flat = false;
+    if (n0) flat |= fabs(sqrt(axis_dist2(p0, ub, h, -C.e)) - Ds) <= kFlat;
+    if (n1) flat |= fabs(sqrt(axis_dist2(p0, ub, h, C.e)) - Ds) <= kFlat;
+    if (!flat) {
+      ball_at(cC, C.u, ts, b);
+      n += collide_sphere_box(b, sideC, cB, RB, sideB, flip, out + 7 * n);
+    }
+  }
+  return n;
+}
+#undef EGS_CSWAP
+
 // ---- kernels ---------------------------------------------------------------
-// SHAPES = false is the all-box code, launched whenever no shape array is set; SHAPES = true reads
-// shape [n] (egs_shape) and dispatches per lane.  The broad phase below does not look at shapes: its
-// bounding radius 0.5 |side| is (sqrt(3) / 2) d >= r for a (d, d, d) sphere, so the candidate ball
-// contains the sphere and the candidate order (ascending j) is the box scene's.
+// SHAPES = 0 is the all-box code, launched whenever no shape array is set; SHAPES = 1 reads shape [n] (egs_shape) and
+// dispatches boxes and spheres per lane; SHAPES = 2 dispatches capsules as well and is launched only when the shape
+// array holds one, so a scene without capsules runs the kernels it ran before there were any.  The broad phase below
+// does not look at shapes: its bounding radius 0.5 |side| is (sqrt(3) / 2) d >= r for a (d, d, d) sphere and
+// 0.5 sqrt(2 d^2 + l^2) >= l / 2 for a (d, d, l) capsule, so the candidate ball contains the body and the candidate
+// order (ascending j) is the box scene's.
 // Batched worlds (ens != NULL): body b's ground contacts follow the pair contacts of the ensembles before
 // its own, ebase[2e] of them (ens_base_kernel).
-template <bool SHAPES>
+template <int SHAPES>
 __global__ void __launch_bounds__(256) ground_kernel(int n, const double *pos, const double *R, const double *side,
                                                      const int *off, int *count, int *b0, int *b1, double *data,
                                                      const int *ens = nullptr, const int *ebase = nullptr,
@@ -404,7 +607,9 @@ __global__ void __launch_bounds__(256) ground_kernel(int n, const double *pos, c
   if (b >= n) return;
   double buf[8 * 7];
   int c;
-  if (SHAPES && shape[b] == kShapeSphere)
+  if (SHAPES == 2 && shape[b] == kShapeCapsule)
+    c = ground_capsule(pos + 3 * (size_t)b, R + 9 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
+  else if (SHAPES && shape[b] == kShapeSphere)
     c = ground_sphere(pos + 3 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
   else
     c = ground_contacts(pos + 3 * (size_t)b, R + 9 * (size_t)b, side + 3 * (size_t)b, off ? buf : nullptr);
@@ -593,7 +798,7 @@ __global__ void __launch_bounds__(256) flatten_kernel(int n, const int *cand, co
 // position (ensembles.cc:296-306; Joint::GetConstraintPosition, joints.cc:57-75).
 struct JointList { int mj; const int *b0, *b1; const double *data; };
 
-template <bool EMIT, bool SHAPES>
+template <bool EMIT, int SHAPES>
 __global__ void __launch_bounds__(64) narrow_kernel(int npairs, const int *pi, const int *pj, const double *pos,
                                                     const double *R, const double *side, const int *off, int base,
                                                     int *count, int *b0, int *b1, double *data, JointList jl,
@@ -605,7 +810,16 @@ __global__ void __launch_bounds__(64) narrow_kernel(int npairs, const int *pi, c
   double cs[MAXC * 7];
   int nc;
   const bool si = SHAPES && shape[i] == kShapeSphere, sj = SHAPES && shape[j] == kShapeSphere;
-  if (si && sj)   // a sphere pair or sphere-box pair has one contact: only the joint test below can drop it
+  const bool ki = SHAPES == 2 && shape[i] == kShapeCapsule, kj = SHAPES == 2 && shape[j] == kShapeCapsule;
+  if (ki || kj) {   // the capsule's partner: a capsule, a sphere (si / sj) or a box
+    const double *ci = pos + 3 * (size_t)i, *Ri = R + 9 * (size_t)i, *di = side + 3 * (size_t)i;
+    const double *cj = pos + 3 * (size_t)j, *Rj = R + 9 * (size_t)j, *dj = side + 3 * (size_t)j;
+    if (ki && kj) nc = collide_capsules(ci, Ri, di, cj, Rj, dj, cs);
+    else if (ki && sj) nc = collide_capsule_sphere(ci, Ri, di, cj, dj, /*first=*/true, cs);
+    else if (kj && si) nc = collide_capsule_sphere(cj, Rj, dj, ci, di, /*first=*/false, cs);
+    else if (ki) nc = collide_capsule_box(ci, Ri, di, cj, Rj, dj, /*flip=*/true, cs);
+    else nc = collide_capsule_box(cj, Rj, dj, ci, Ri, di, /*flip=*/false, cs);
+  } else if (si && sj)   // a sphere pair or sphere-box pair has one contact: only the joint test below can drop it
     nc = collide_spheres(pos + 3 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j, side + 3 * (size_t)j, cs);
   else if (si)
     nc = collide_sphere_box(pos + 3 * (size_t)i, side + 3 * (size_t)i, pos + 3 * (size_t)j, R + 9 * (size_t)j,
@@ -778,7 +992,7 @@ void Collider::set_ensembles(int n_ens, const int32_t *ens, const int32_t *eoff,
 }
 
 int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, const double *dside, int mj,
-                  const int32_t *djb0, const int32_t *djb1, const double *djdata, const int32_t *dshape) {
+                  const int32_t *djb0, const int32_t *djb1, const double *djdata, const int32_t *dshape, bool capsules) {
   const JointList jl{mj, djb0, djb1, djdata};
   Impl &I = *impl_;
   n_ground_ = 0; n_pairs_ = 0;
@@ -793,12 +1007,16 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   // flags: [0] candidate overflow, [1] ground contacts, [2] candidate pairs, [3] pair contacts
   HIPCHK(hipMemsetAsync(I.flags.p, 0, 4 * sizeof(int), s));
   const int gb = (n + 255) / 256;
-  // dshape == NULL: every body a box, the SHAPES = false instantiations (the launches of a world without shapes)
-  if (dshape)
-    hipLaunchKernelGGL((ground_kernel<true>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
+  // dshape == NULL: every body a box, the SHAPES = 0 instantiations (the launches of a world without shapes)
+  // the SHAPES = 2 forms only where the caller's shape array holds a capsule
+  if (dshape && capsules)
+    hipLaunchKernelGGL((ground_kernel<2>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
+                       (int *)nullptr, (int *)nullptr, (double *)nullptr, (const int *)nullptr, (const int *)nullptr, dshape);
+  else if (dshape)
+    hipLaunchKernelGGL((ground_kernel<1>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
                        (int *)nullptr, (int *)nullptr, (double *)nullptr, (const int *)nullptr, (const int *)nullptr, dshape);
   else
-  hipLaunchKernelGGL((ground_kernel<false>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
+  hipLaunchKernelGGL((ground_kernel<0>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, (const int *)nullptr, I.gcount.p,
                      (int *)nullptr, (int *)nullptr, (double *)nullptr);
   exclusive_scan_async(s, n, I.gcount.p, I.goff.p, I.blocks.p, I.flags.p + 1);
   if (use_grid(n)) {
@@ -836,12 +1054,16 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
                                   ens, eoff);
     else
     hipLaunchKernelGGL(flatten_kernel, dim3(gb), dim3(256), 0, s, n, I.cand.p, I.ccount.p, I.coff.p, I.pi.p, I.pj.p);
-    if (dshape)
-      hipLaunchKernelGGL((narrow_kernel<false, true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+    if (dshape && capsules)
+      hipLaunchKernelGGL((narrow_kernel<false, 2>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+                         (const int *)nullptr, 0, I.pcount.p, (int *)nullptr, (int *)nullptr, (double *)nullptr, jl,
+                         (const int *)nullptr, (const int *)nullptr, dshape);
+    else if (dshape)
+      hipLaunchKernelGGL((narrow_kernel<false, 1>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                          (const int *)nullptr, 0, I.pcount.p, (int *)nullptr, (int *)nullptr, (double *)nullptr, jl,
                          (const int *)nullptr, (const int *)nullptr, dshape);
     else
-    hipLaunchKernelGGL((narrow_kernel<false, false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+    hipLaunchKernelGGL((narrow_kernel<false, 0>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                        (const int *)nullptr, 0, I.pcount.p, (int *)nullptr, (int *)nullptr, (double *)nullptr, jl);
     P = exclusive_scan(s, C, I.pcount.p, I.poff.p, I.blocks2.p, I.flags.p + 3);
   }
@@ -854,17 +1076,23 @@ int Collider::run(hipStream_t s, int n, const double *dpos, const double *dR, co
   }
   if (m == 0) return 0;
   I.b0.alloc(m); I.b1.alloc(m); I.data.alloc((size_t)m * 7);
-  if (dshape)
-    hipLaunchKernelGGL((ground_kernel<true>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
+  if (dshape && capsules)
+    hipLaunchKernelGGL((ground_kernel<2>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
+                       I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr, dshape);
+  else if (dshape)
+    hipLaunchKernelGGL((ground_kernel<1>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
                        I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr, dshape);
   else
-  hipLaunchKernelGGL((ground_kernel<false>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
+  hipLaunchKernelGGL((ground_kernel<0>), dim3(gb), dim3(256), 0, s, n, dpos, dR, dside, I.goff.p, (int *)nullptr, I.b0.p,
                      I.b1.p, I.data.p, ens, ens ? I.ebase.p : nullptr);
-  if (C > 0 && dshape)
-    hipLaunchKernelGGL((narrow_kernel<true, true>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+  if (C > 0 && dshape && capsules)
+    hipLaunchKernelGGL((narrow_kernel<true, 2>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+                       I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr, dshape);
+  else if (C > 0 && dshape)
+    hipLaunchKernelGGL((narrow_kernel<true, 1>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                        I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr, dshape);
   else if (C > 0)
-    hipLaunchKernelGGL((narrow_kernel<true, false>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
+    hipLaunchKernelGGL((narrow_kernel<true, 0>), dim3((C + 63) / 64), dim3(64), 0, s, C, I.pi.p, I.pj.p, dpos, dR, dside,
                        I.poff.p, G, (int *)nullptr, I.b0.p, I.b1.p, I.data.p, jl, ens, ens ? I.ebase.p : nullptr);
   HIPCHK(hipGetLastError());
   return m;
@@ -897,8 +1125,10 @@ int update_contacts(hipStream_t s, int n, const double *pos, const double *R, co
   }
   ScopedDevBuf<int> dshape(shape ? nn : 0);
   if (shape) HIPCHK(hipMemcpyAsync(dshape.p, shape, nn * sizeof(int), hipMemcpyHostToDevice, s));
+  bool capsules = false;
+  for (size_t b = 0; shape && b < nn; ++b) capsules |= shape[b] == kShapeCapsule;
   Collider col;
-  const int m = col.run(s, n, dpos.p, dR.p, dside.p, mj, djb0.p, djb1.p, djdata.p, shape ? dshape.p : nullptr);
+  const int m = col.run(s, n, dpos.p, dR.p, dside.p, mj, djb0.p, djb1.p, djdata.p, shape ? dshape.p : nullptr, capsules);
   if (n_ground) *n_ground = col.n_ground();
   if (n_pairs) *n_pairs = col.n_pairs();
   if (m > max_contacts) throw std::invalid_argument("update_contacts: max_contacts too small (" + std::to_string(m) + " needed)");

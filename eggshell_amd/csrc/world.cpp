@@ -113,17 +113,28 @@ void world_fill_travel(egs_world *w) {
 }
 
 // What is wrong with a shape array (nothing: an empty string): a value that is no egs_shape, or -- where the side lengths are
-// known (side != NULL) -- a sphere whose side row is not three equal positive numbers.
+// known (side != NULL) -- a sphere whose side row is not three equal positive numbers, a capsule whose side row is not
+// (d, d, l) with 0 < d < l, both finite.
 std::string shapes_fault(int n, const int32_t *shape, const double *side) {
   for (int b = 0; b < n; ++b) {
-    if (shape[b] != EGS_SHAPE_BOX && shape[b] != EGS_SHAPE_SPHERE)
+    if (shape[b] != EGS_SHAPE_BOX && shape[b] != EGS_SHAPE_SPHERE && shape[b] != EGS_SHAPE_CAPSULE)
       return "body " + std::to_string(b) + ": unknown shape " + std::to_string(shape[b]);
-    if (shape[b] != EGS_SHAPE_SPHERE || !side) continue;
+    if (shape[b] == EGS_SHAPE_BOX || !side) continue;
     const double *d = side + 3 * (size_t)b;
-    if (!(d[0] > 0) || d[1] != d[0] || d[2] != d[0])
-      return "body " + std::to_string(b) + ": a sphere's side_lengths must be (d, d, d) with d > 0";
+    if (shape[b] == EGS_SHAPE_SPHERE) {
+      if (!(d[0] > 0) || d[1] != d[0] || d[2] != d[0])
+        return "body " + std::to_string(b) + ": a sphere's side_lengths must be (d, d, d) with d > 0";
+    } else if (!(d[0] > 0) || d[1] != d[0] || !(d[2] > d[0]) || !std::isfinite(d[0]) || !std::isfinite(d[2])) {
+      return "body " + std::to_string(b) + ": a capsule's side_lengths must be (d, d, l) with 0 < d < l, both finite" +
+             (d[2] == d[0] ? " (l == d is a sphere: use EGS_SHAPE_SPHERE)" : "");
+    }
   }
   return std::string();
+}
+
+bool holds_capsule(const std::vector<int32_t> &shape) {
+  for (int32_t v : shape) if (v == EGS_SHAPE_CAPSULE) return true;
+  return false;
 }
 
 egs_status update_contacts_entry(egs_context *ctx, int32_t n, const double *pos, const double *R, const double *side,
@@ -184,7 +195,7 @@ void world_update_contacts(egs_world *w, PhaseTimer *lap) {
   const int mj = (int)w->jb0.size();
   // the pruning takes the ball joints alone
   const int mc = w->col.run(s, w->n, w->prob->pos.p, w->prob->R.p, w->dside.p, w->mj_ball, w->djb0.p, w->djb1.p, w->djdata.p,
-                            w->shapes ? w->dshape.p : nullptr);
+                            w->shapes ? w->dshape.p : nullptr, w->shapes && w->capsules);
   if (lap) (*lap)(0);
   const size_t mt = (size_t)mj + (size_t)mc;
   if (mt > w->h_cap) {   // grow-only; the stream is idle here (col.run synchronised)
@@ -324,6 +335,7 @@ egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape) {
     }
     w->shapes = shape && w->n > 0;
     if (!w->shapes) w->h_shape.clear();
+    w->capsules = holds_capsule(w->h_shape);
     world_drop_history(w);
     return EGS_OK;
   });

@@ -138,7 +138,8 @@ struct egs_world {
   egs::DevBuf<double> dside;
   // egs_world_set_shapes: egs_shape per body on the device, handed to every Collider::run (shapes = false: NULL, the
   // all-box launches); host copies of the shapes and the side lengths, for the check that a sphere's sides are (d, d, d)
-  bool shapes = false;
+  // capsules: h_shape holds an EGS_SHAPE_CAPSULE, so the collider launches its capsule instantiations
+  bool shapes = false, capsules = false;
   egs::DevBuf<int32_t> dshape;
   std::vector<int32_t> h_shape;
   std::vector<double> h_side;

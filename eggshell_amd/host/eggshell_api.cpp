@@ -97,6 +97,25 @@ Matrix3d Body::CalculateInertia(double m) const {  // body.cc:19-36
   return I;
 }
 
+// Not in the reference.  A uniform solid capsule about its centre, axis z: the cylinder (m_c) and the two
+// hemispheres (m_s together) share the mass by volume, pi r^2 H : (4/3) pi r^3.
+Body Body::Capsule(const Vector3d &p, const Vector3d &v, double radius, double length, double m) {
+  if (!(radius > 0) || !(length > 2 * radius) || !std::isfinite(length))
+    throw egs::Error(EGS_ERR_INVALID, "Body::Capsule: length is tip to tip and must exceed 2 radius > 0 (a capsule "
+                                      "with length == 2 radius is a Body::Sphere)");
+  const double r = radius, H = length - 2 * radius;
+  const double vc = M_PI * r * r * H, vs = 4.0 / 3.0 * M_PI * r * r * r;
+  const double mc = m * vc / (vc + vs), ms = m * vs / (vc + vs);
+  Matrix3d I = Matrix3d::Identity();
+  I(0, 0) = I(1, 1) = mc * (H * H / 12 + r * r / 4) + ms * (0.4 * r * r + H * H / 4 + 0.375 * H * r);
+  I(2, 2) = mc * r * r / 2 + 0.4 * ms * r * r;
+  Body b(p, v, m, Matrix3d::Identity(), Vector3d::Zero(), I);
+  b.type_ = BodyType::Capsule;
+  b.radius_ = radius;
+  b.length_ = length;
+  return b;
+}
+
 // ---- joints.cc -----------------------------------------------------------
 static VectorXd ToX(const Vector3d &v) { VectorXd x(3); for (int k = 0; k < 3; ++k) x(k) = v[k]; return x; }
 
@@ -1050,9 +1069,9 @@ void Ensemble::StepPositions_ODE(double dt, const VectorXd &v, const VectorXd &v
 std::vector<int32_t> Ensemble::Shapes() const {
   std::vector<int32_t> shape;
   for (int i = 0; i < n_; ++i)
-    if (components_[i]->type() == Body::BodyType::Sphere) {
+    if (components_[i]->type() != Body::BodyType::Box) {
       if (shape.empty()) shape.assign((size_t)n_, EGS_SHAPE_BOX);
-      shape[(size_t)i] = EGS_SHAPE_SPHERE;
+      shape[(size_t)i] = components_[i]->type() == Body::BodyType::Sphere ? EGS_SHAPE_SPHERE : EGS_SHAPE_CAPSULE;
     }
   return shape;
 }
@@ -1313,7 +1332,7 @@ void Ensemble::Step(double dt, Integrator g) {  // ensembles.cc:390-427
                      "Integrator::EXPLICIT_EULER panics in the reference (ComputeJDotV_Joints, ensembles.cc:94-97); "
                      "only Integrator::OPEN_DYNAMICS_ENGINE completes a step");
   if (!detect_contacts && !Shapes().empty())
-    throw egs::Error(EGS_ERR_UNSUPPORTED, "an ensemble with a Sphere steps on contacts the device detects: not with "
+    throw egs::Error(EGS_ERR_UNSUPPORTED, "an ensemble with a Sphere or a Capsule steps on contacts the device detects: not with "
                                           "detect_contacts = false");
   if (StepOnDevice(dt)) return;   // collide -> solve -> integrate in one resident pipeline
   if (friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID) {
@@ -1413,7 +1432,7 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     if (m->n_ != off_[i + 1] - off_[i])
       throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup: member " + std::to_string(i) + " changed its number of bodies");
     if (!m->detect_contacts && !m->Shapes().empty())
-      throw egs::Error(EGS_ERR_UNSUPPORTED, "EnsembleGroup: member " + std::to_string(i) + " holds a Sphere and steps on contacts "
+      throw egs::Error(EGS_ERR_UNSUPPORTED, "EnsembleGroup: member " + std::to_string(i) + " holds a Sphere or a Capsule and steps on contacts "
                                                 "the device detects: not with detect_contacts = false");
     for (int b = 0; b < m->n_; ++b) {
       const Body &body = *m->components_[b];

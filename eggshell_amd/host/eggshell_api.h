@@ -64,16 +64,27 @@ class Body {  // body.h:13-96
   // body.h:60: `enum struct BodyType { Box = 0 }` with the TODO "move this to a subclass when there are different
   // types of Bodies".  Sphere is not in the reference: a ball of the given radius and mass, I = (2/5) m r^2 * 1,
   // collided as a sphere on the device (EGS_SHAPE_SPHERE; its side lengths are the diameter three times).
-  enum struct BodyType { Box = 0, Sphere };
+  // Capsule is not in the reference either: radius, tip-to-tip length > 2 radius, its axis the body's z axis (column 2
+  // of R), collided as a capsule on the device (EGS_SHAPE_CAPSULE; side lengths (2 radius, 2 radius, length)).  It has
+  // a uniform solid capsule's inertia: a cylinder of height H = length - 2 radius and two hemispheres, the mass split
+  // by volume into m_c and m_s,  I_zz = m_c r^2 / 2 + (2/5) m_s r^2,
+  // I_xx = I_yy = m_c (H^2 / 12 + r^2 / 4) + m_s (2 r^2 / 5 + H^2 / 4 + 3 H r / 8).
+  // That is not a multiple of the identity: under the default frozen inertia (quirk Q5: M^-1 and the external force
+  // are taken at Init() and kept) a tumbling capsule keeps the world-frame inertia it had at Init().
+  // Ensemble::SetLiveInertia(true) is the remedy: M^-1 and the gyroscopic torque then follow the body.
+  enum struct BodyType { Box = 0, Sphere, Capsule };
   static Body Sphere(const Vector3d &p, const Vector3d &v, double radius, double m = 1.0) {
     Body b(p, v, m, Matrix3d::Identity(), Vector3d::Zero(), Matrix3d::Identity() * (0.4 * m * radius * radius));
     b.type_ = BodyType::Sphere;
     b.radius_ = radius;
     return b;
   }
+  static Body Capsule(const Vector3d &p, const Vector3d &v, double radius, double length, double m = 1.0);
   BodyType type() const { return type_; }
   double radius() const { return radius_; }   // 0 for a box
+  double length() const { return length_; }   // tip to tip; 0 unless a capsule
   Vector3d GetSideLengths() const {           // body.h:91 for a box
+    if (type_ == BodyType::Capsule) return Vector3d(2 * radius_, 2 * radius_, length_);
     return type_ == BodyType::Sphere ? Vector3d(2 * radius_, 2 * radius_, 2 * radius_) : Vector3d(0.3, 0.3, 0.3);
   }
 
@@ -84,7 +95,7 @@ class Body {  // body.h:13-96
   Vector3d w_;
   Matrix3d I_;
   BodyType type_ = BodyType::Box;
-  double radius_ = 0.0;
+  double radius_ = 0.0, length_ = 0.0;
   Matrix3d CalculateInertia(double m) const;  // body.cc:19-36
 };
 
@@ -533,7 +544,7 @@ class Ensemble {  // ensembles.h:25-186
   void StepPositions_ODE(double dt, const VectorXd &v, const VectorXd &v_new);                    // :577-591
   bool StepOnDevice(double dt);
   // egs_shape per component; empty when every Body is a box (the library then takes its all-box launches).  Shapes
-  // go to the device with the side lengths (frozen at Init(), Q5) and with every UpdateContacts().  A sphere ensemble
+  // go to the device with the side lengths (frozen at Init(), Q5) and with every UpdateContacts().  An ensemble with a sphere or a capsule
   // needs the device's detection: Step throws egs::Error(EGS_ERR_UNSUPPORTED) with detect_contacts = false.
   std::vector<int32_t> Shapes() const;
   // -step_scale * J^T (J J^T)^-1 err (ensembles.cc:659-666); the SPD(-semidefinite)

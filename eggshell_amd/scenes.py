@@ -183,6 +183,42 @@ def ball_pile(nx, ny, nz, radius=0.15, sink=1e-3, gap=1e-2, mass=1.0, origin=(0.
                 side=np.full((n, 3), d), shape=np.ones(n, np.int32))
 
 
+def capsule_inertia(mass, radius, length):
+    """(I_xx = I_yy, I_zz) about the centre of a uniform solid capsule along its z axis: a cylinder of height
+    H = length - 2 radius and two hemispheres, the mass split by volume (m_c : m_s = pi r^2 H : (4/3) pi r^3).
+    I_zz = m_c r^2 / 2 + (2/5) m_s r^2;  I_xx = m_c (H^2 / 12 + r^2 / 4) + m_s (2 r^2 / 5 + H^2 / 4 + 3 H r / 8)."""
+    r, H = float(radius), float(length) - 2.0 * float(radius)
+    vc, vs = math.pi * r * r * H, 4.0 / 3.0 * math.pi * r ** 3
+    mc, ms = mass * vc / (vc + vs), mass * vs / (vc + vs)
+    izz = mc * r * r / 2 + 0.4 * ms * r * r
+    ixx = mc * (H * H / 12 + r * r / 4) + ms * (0.4 * r * r + H * H / 4 + 0.375 * H * r)
+    return ixx, izz
+
+
+def log_pile(nx, ny, nz=1, radius=0.1, length=0.6, sink=1e-3, gap=1e-2, mass=1.0, origin=(0.0, 0.0)):
+    """nz layers of nx x ny logs (capsules: radius, tip-to-tip length, mass, a solid capsule's inertia), nx end to end
+    and ny side by side, `gap` apart within a layer.  Even layers lie along x, odd layers along y (the grid turned with
+    them), each layer `sink` into the one below and the lowest `sink` into the ground: logs on a plate for nz = 1, a
+    crib for nx = 1.  Bodies only, with side = (2r, 2r, length) and shape = 2 (capi.SHAPE_CAPSULE) per log, the axis
+    column 2 of R; the contacts come from the device (Context.update_contacts_shapes or a world step)."""
+    d = 2.0 * radius
+    along_x = np.array([0.0, 0.0, 1.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0])
+    along_y = np.array([1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, 0.0])
+    p, R = [], []
+    for k in range(nz):
+        for i in range(nx):
+            for j in range(ny):
+                a, b = (i - (nx - 1) / 2) * (length + gap), (j - (ny - 1) / 2) * (d + gap)   # about the origin
+                x, y = (a, b) if k % 2 == 0 else (b, a)
+                p.append([origin[0] + x, origin[1] + y, (radius - sink) + k * (d - sink)])
+                R.append(along_x if k % 2 == 0 else along_y)
+    n = len(p)
+    ixx, izz = capsule_inertia(mass, radius, length)
+    return dict(p=np.array(p).reshape(-1, 3), R=np.array(R).reshape(-1, 9), v=np.zeros((n, 3)), w=np.zeros((n, 3)),
+                mass=np.full(n, float(mass)), I_body=np.tile(np.diag([ixx, ixx, izz]).reshape(9), (n, 1)),
+                side=np.tile([d, d, float(length)], (n, 1)), shape=np.full(n, 2, np.int32))
+
+
 def concat(scenes):
     """Batch independent ensembles into one system (body indices offset)."""
     out = {}

@@ -670,12 +670,42 @@ egs_status egs_update_contacts_joints(egs_context *ctx, int32_t n_bodies,
  *     sgn(0) = +1, depth = (h_k - |p_k|) + r, box point = the centre moved onto that face.  Sphere point
  *     c_S - r n_BS; position = the midpoint of the two points; the normal is n_BS if the box is body0, else -n_BS.
  * A pair with a sphere has at most one contact; the joint-vs-contact pruning applies to it unchanged.  The list order
- * is unchanged and box-box pairs emit what they emit without shapes.  Inertia stays the caller's (Minv).           */
-typedef enum { EGS_SHAPE_BOX = 0, EGS_SHAPE_SPHERE = 1 } egs_shape;
+ * is unchanged and box-box pairs emit what they emit without shapes.  Inertia stays the caller's (Minv).
+ *
+ * A capsule (EGS_SHAPE_CAPSULE = 2) is a body whose side_lengths row is (d, d, l) with d > 0 and l > d strictly, both
+ * finite (l == d is a sphere and is refused: use EGS_SHAPE_SPHERE).  r = d / 2, half axis e = (l - d) / 2 > 0, axis u =
+ * column 2 of R (R[2], R[5], R[8]); "the ball at t" is the sphere of diameter d centred at c + t u, t in [-e, e];
+ * end 0 is t = -e, end 1 is t = +e.  The conventions are the ones above, and every rule is one of the three sphere
+ * rules applied to balls of the capsule:
+ *   capsule - ground: the sphere - ground rule on the ball at end 0, then at end 1: at most 2 contacts, in that order.
+ *   capsule - sphere: t = clamp((c_S - c) . u, -e, e); the sphere - sphere rule between the ball at t and the sphere,
+ *     in the pair's (i, j) order: at most 1 contact.
+ *   capsule i - capsule j: candidates in this order: end 0 of i against capsule j, end 1 of i against j, end 0 of j
+ *     against capsule i, end 1 of j against i (each by the capsule - sphere rule, normal always i -> j), then the
+ *     interior pair: the balls at the axes' common-perpendicular parameters (s, t), which exists only where s and t lie
+ *     strictly inside both segments and the 2 x 2 determinant (u_i.u_i)(u_j.u_j) - (u_i.u_j)^2 is non-zero in the
+ *     device's arithmetic.  Whenever the closest pair of the two segments involves an end it is one of the four end
+ *     candidates, so parallel axes need no special case.  At most 5 contacts.
+ *   capsule - box: dist(t) = the L of the sphere - box rule for a centre at c + t u (0 inside the box).  Candidates:
+ *     end 0, end 1, then the interior point t*, each by the sphere - box rule.  t* is the lowest minimiser of dist on
+ *     [-e, e] and counts only when strictly inside; if the axis enters the box (minimum 0) t* is the midpoint of the
+ *     stretch of axis inside the box (the segment clipped against the three slabs).  dist^2 is a convex piecewise
+ *     quadratic in t with at most 6 breakpoints (a box-frame coordinate of the axis crossing +-h_k); the minimiser is
+ *     found exactly up to rounding from the ends, the breakpoints and each piece's stationary point.  At most 3.
+ *   A candidate is emitted iff its sphere rule says contact.
+ *   Flat rule (capsule - capsule and capsule - box): the interior candidate is dropped if an EMITTED end candidate's
+ *   centre distance (for a box: its dist) is within 1e-9 of its own; 1e-9 is absolute, in metres, a constant of the
+ *   kind of the collider's 1e-6.  So a log flat on a plate and two logs side by side get 2 contacts, a capsule bridging
+ *   two boxes one per box; a crossed pair, a capsule see-sawing on a box edge and a capsule lying across a box narrower
+ *   than itself get 1.  In that last case dist is constant along the stretch above the box up to rounding, and the
+ *   contact's position ALONG that flat stretch is unspecified within the stretch.
+ * The same-pair 1e-6 pruning and the joint-vs-contact pruning then run unchanged.  List order and the output of
+ * box - box pairs and of spheres are unchanged.  A scene without a capsule launches the kernels it launched before.  */
+typedef enum { EGS_SHAPE_BOX = 0, EGS_SHAPE_SPHERE = 1, EGS_SHAPE_CAPSULE = 2 } egs_shape;
 
 /* egs_update_contacts_joints with shape [n_bodies] (egs_shape values) or NULL.  NULL, or all EGS_SHAPE_BOX, gives the
  * result of egs_update_contacts_joints bit for bit.  EGS_ERR_INVALID: an unknown shape value, a sphere whose
- * side_lengths row is not three equal positive numbers.                                                           */
+ * side_lengths row is not three equal positive numbers, a capsule whose row is not (d, d, l) with 0 < d < l, finite. */
 egs_status egs_update_contacts_shapes(egs_context *ctx, int32_t n_bodies,
                                       const double *pos, const double *R,
                                       const double *side_lengths, int32_t m_joints,
@@ -727,7 +757,7 @@ egs_status egs_world_set_bodies(egs_world *w, const double *pos, const double *R
  * egs_world_step[_each], egs_world_step_dense[_each], egs_world_stabilize[_direct] with detect_contacts = 1.  NULL
  * switches back to boxes.  Valid any time after the world is created; drops the warm-start history as
  * egs_world_set_bodies does.  EGS_ERR_INVALID, with nothing changed: an unknown value; a sphere whose side_lengths row
- * is not three equal positive numbers -- checked when both are known, i.e. here if egs_world_set_bodies has given the
+ * is not three equal positive numbers, a capsule whose row is not (d, d, l) with 0 < d < l -- checked when both are known, i.e. here if egs_world_set_bodies has given the
  * side lengths and in egs_world_set_bodies whenever it is given side_lengths while shapes are set.             */
 egs_status egs_world_set_shapes(egs_world *w, const int32_t *shape);
 /* ball joints: body0/body1 [m], data [m][7] = c0, c1 (world point if body1 = -1), 0 */
