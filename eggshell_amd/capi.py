@@ -64,6 +64,7 @@ EXPORTS = [
     "egs_problem_set_motors", "egs_world_set_joints_kinds", "egs_world_set_joint_motors", "egs_world_get_blocks",
     "egs_problem_set_hinge_limits", "egs_world_set_joint_limits",
     "egs_problem_set_slider_limits", "egs_world_set_slider_limits",
+    "egs_cast_rays", "egs_world_set_rays", "egs_world_cast_rays",
 ]
 
 
@@ -131,6 +132,13 @@ def load():
             for name in ("egs_problem_set_live_inertia", "egs_problem_get_mass", "egs_world_set_live_inertia", "egs_world_get_mass"):
                 getattr(_lib, name).argtypes = [C.c_void_p] * 3
                 getattr(_lib, name).restype = C.c_int
+        if hasattr(_lib, "egs_cast_rays"):
+            # ctx, n, pos, R, side, shape, n_rays, ray_body, origin, dir, tmax, hit, t, normal
+            _lib.egs_cast_rays.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 7
+            _lib.egs_world_set_rays.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5   # world, n_rays, ens, body, o, d, tmax
+            _lib.egs_world_cast_rays.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4   # world, max_rays, n_out, hit, t, normal
+            for name in ("egs_cast_rays", "egs_world_set_rays", "egs_world_cast_rays"):
+                getattr(_lib, name).restype = C.c_int
     return _lib
 
 
@@ -148,6 +156,17 @@ def _i32(a):
 
 def _u8(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _ray_arrays(origin, dir, tmax, ray_body):
+    """(origin, dir, n_rays, tmax, ray_body) of the ray entries: contiguous, tmax None = +inf, shapes checked."""
+    origin, dir = _f64(origin).reshape(-1, 3), _f64(dir).reshape(-1, 3)
+    nr = origin.shape[0]
+    tmax = np.full(nr, np.inf) if tmax is None else _f64(tmax).reshape(-1)
+    ray_body = _i32(ray_body)
+    if dir.shape[0] != nr or tmax.shape[0] != nr or (ray_body is not None and ray_body.shape != (nr,)):
+        raise ValueError("origin, dir, tmax and ray_body must describe the same %d rays" % nr)
+    return origin, dir, nr, tmax, ray_body
 
 
 def _live_arrays(n, inertia_body, torque):
@@ -384,6 +403,20 @@ class Context:
                                                      _p(jb0), _p(jb1), _p(jd), _p(shape), C.c_int32(cap), C.byref(m),
                                                      _p(b0), _p(b1), _p(data)))
         return b0[:m.value].copy(), b1[:m.value].copy(), data[:m.value].copy()
+
+    def cast_rays(self, pos, R, side, shape, origin, dir, tmax=None, ray_body=None, out=None):
+        """Rays against the ground and one ensemble's bodies (egs_cast_rays; the rules are in eggshell_amd.h): origin,
+        dir [n_rays][3] (dir is not normalised: t is in its units), tmax [n_rays] (None = +inf), ray_body [n_rays] (-1 =
+        world frame; otherwise origin and dir are in that body's frame and it is not tested) or None.  Returns (hit_body
+        [n_rays] int32: -2 none, -1 the ground, else the body; t [n_rays]; normal [n_rays][3]).  out = (hit_body, t,
+        normal): arrays to write into."""
+        pos, R, side, shape = _f64(pos), _f64(R), _f64(side), _i32(shape)
+        n = pos.reshape(-1, 3).shape[0]
+        origin, dir, nr, tmax, ray_body = _ray_arrays(origin, dir, tmax, ray_body)
+        hit, t, normal = out if out is not None else (np.full(nr, -2, np.int32), np.zeros(nr), np.zeros((nr, 3)))
+        self.check(load().egs_cast_rays(self.h, C.c_int32(n), _p(pos), _p(R), _p(side), _p(shape), C.c_int32(nr),
+                                        _p(ray_body), _p(origin), _p(dir), _p(tmax), _p(hit), _p(t), _p(normal)))
+        return hit, t, normal
 
     def match_contacts(self, old_b0, old_b1, old_pos, old_lambda, old_off, valid, new_b0, new_b1, new_pos, new_rhs,
                        new_off, radius):
@@ -1044,6 +1077,27 @@ class World:
         if shape is not None and shape.shape != (self.n,):
             raise ValueError("shape has shape %s: the world has %d bodies" % (shape.shape, self.n))
         self.ctx.check(load().egs_world_set_shapes(self.h, _p(shape)))
+
+    def set_rays(self, origin, dir, tmax=None, ray_body=None, ray_ens=None):
+        """The world's ray table (egs_world_set_rays), kept on the device until the next call: arrays as
+        Context.cast_rays takes them, ray_body in global body indices, ray_ens [n_rays] non-decreasing in a batched
+        world.  No rays (an empty origin) drops the table."""
+        origin, dir, nr, tmax, ray_body = _ray_arrays(origin, dir, tmax, ray_body)
+        ray_ens = _i32(ray_ens)
+        if ray_ens is not None and ray_ens.shape != (nr,):
+            raise ValueError("ray_ens has shape %s for %d rays" % (ray_ens.shape, nr))
+        self.ctx.check(load().egs_world_set_rays(self.h, C.c_int32(nr), _p(ray_ens), _p(ray_body), _p(origin), _p(dir),
+                                                 _p(tmax)))
+        self.n_rays = nr
+
+    def cast_rays(self, out=None):
+        """The table's rays against the state the device holds now (egs_world_cast_rays): (hit_body, t, normal) as
+        Context.cast_rays returns them, hit_body in global body indices."""
+        nr = getattr(self, "n_rays", 0)
+        hit, t, normal = out if out is not None else (np.full(nr, -2, np.int32), np.zeros(nr), np.zeros((nr, 3)))
+        got = C.c_int32(0)
+        self.ctx.check(load().egs_world_cast_rays(self.h, C.c_int32(hit.shape[0]), C.byref(got), _p(hit), _p(t), _p(normal)))
+        return hit, t, normal
 
     def set_joints(self, body0, body1, data):
         body0, body1, data = _i32(body0), _i32(body1), _f64(data)

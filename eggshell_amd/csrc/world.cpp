@@ -112,26 +112,6 @@ void world_fill_travel(egs_world *w) {
   p->h_rows_valid = false;
 }
 
-// What is wrong with a shape array (nothing: an empty string): a value that is no egs_shape, or -- where the side lengths are
-// known (side != NULL) -- a sphere whose side row is not three equal positive numbers, a capsule whose side row is not
-// (d, d, l) with 0 < d < l, both finite.
-std::string shapes_fault(int n, const int32_t *shape, const double *side) {
-  for (int b = 0; b < n; ++b) {
-    if (shape[b] != EGS_SHAPE_BOX && shape[b] != EGS_SHAPE_SPHERE && shape[b] != EGS_SHAPE_CAPSULE)
-      return "body " + std::to_string(b) + ": unknown shape " + std::to_string(shape[b]);
-    if (shape[b] == EGS_SHAPE_BOX || !side) continue;
-    const double *d = side + 3 * (size_t)b;
-    if (shape[b] == EGS_SHAPE_SPHERE) {
-      if (!(d[0] > 0) || d[1] != d[0] || d[2] != d[0])
-        return "body " + std::to_string(b) + ": a sphere's side_lengths must be (d, d, d) with d > 0";
-    } else if (!(d[0] > 0) || d[1] != d[0] || !(d[2] > d[0]) || !std::isfinite(d[0]) || !std::isfinite(d[2])) {
-      return "body " + std::to_string(b) + ": a capsule's side_lengths must be (d, d, l) with 0 < d < l, both finite" +
-             (d[2] == d[0] ? " (l == d is a sphere: use EGS_SHAPE_SPHERE)" : "");
-    }
-  }
-  return std::string();
-}
-
 bool holds_capsule(const std::vector<int32_t> &shape) {
   for (int32_t v : shape) if (v == EGS_SHAPE_CAPSULE) return true;
   return false;
@@ -189,6 +169,26 @@ egs_status world_set_table(egs_world *w, CoeffTable &t, int32_t n_ensembles, con
 }  // namespace
 
 namespace egs {
+
+// What is wrong with a shape array (nothing: an empty string): a value that is no egs_shape, or -- where the side lengths are
+// known (side != NULL) -- a sphere whose side row is not three equal positive numbers, a capsule whose side row is not
+// (d, d, l) with 0 < d < l, both finite.
+std::string shapes_fault(int n, const int32_t *shape, const double *side) {
+  for (int b = 0; b < n; ++b) {
+    if (shape[b] != EGS_SHAPE_BOX && shape[b] != EGS_SHAPE_SPHERE && shape[b] != EGS_SHAPE_CAPSULE)
+      return "body " + std::to_string(b) + ": unknown shape " + std::to_string(shape[b]);
+    if (shape[b] == EGS_SHAPE_BOX || !side) continue;
+    const double *d = side + 3 * (size_t)b;
+    if (shape[b] == EGS_SHAPE_SPHERE) {
+      if (!(d[0] > 0) || d[1] != d[0] || d[2] != d[0])
+        return "body " + std::to_string(b) + ": a sphere's side_lengths must be (d, d, d) with d > 0";
+    } else if (!(d[0] > 0) || d[1] != d[0] || !(d[2] > d[0]) || !std::isfinite(d[0]) || !std::isfinite(d[2])) {
+      return "body " + std::to_string(b) + ": a capsule's side_lengths must be (d, d, l) with 0 < d < l, both finite" +
+             (d[2] == d[0] ? " (l == d is a sphere: use EGS_SHAPE_SPHERE)" : "");
+    }
+  }
+  return std::string();
+}
 
 void world_update_contacts(egs_world *w, PhaseTimer *lap) {
   hipStream_t s = w->ctx->stream;

@@ -1,5 +1,5 @@
 // world.h -- struct egs_world, one member struct per feature, and the handful of functions that cross the world units
-// (world.cpp, world_step.cpp, world_dense.cpp, world_stabilize.cpp).  Included by those four only; the world works on
+// (world.cpp, world_step.cpp, world_dense.cpp, world_stabilize.cpp, rays.cpp).  Included by those five only; the world works on
 // its egs_problem through problem.h.
 #pragma once
 
@@ -9,6 +9,7 @@
 #include "dense_world.h"
 #include "ensemble_rows.h"
 #include "problem.h"
+#include "raycast.h"
 #include "stabilize_direct.h"
 
 namespace egs {
@@ -124,6 +125,18 @@ struct CoeffTable {
   std::vector<double> h;                 // [E], the host's copy (friction: read for the dense step's ensembles above the fused cap)
 };
 
+// egs_world_set_rays: the ray table on the device (n = 0: none), kept until the next egs_world_set_rays -- nothing a
+// step, a re-plan, a stabilise call or egs_world_set_bodies writes is in here, and nothing in here is read by them.
+// egs_world_cast_rays writes out = t [n] | normal [n][3] | hit [n] (int32) and reads it back in one copy through h.
+struct RayTable {
+  int n = 0;
+  bool attached = false, grouped = false;   // some ray rides on a body; the rays name ensembles (batched world)
+  DevBuf<int32_t> ens, body;
+  DevBuf<double> geom;                   // origin [n][3] | dir [n][3] | tmax [n]
+  DevBuf<unsigned char> out;
+  PinnedBuf<unsigned char> h;
+};
+
 }  // namespace egs
 
 // ---------------------------------------------------------------------------
@@ -176,6 +189,7 @@ struct egs_world {
   egs::WarmStart ws;
   egs::CoeffTable friction, restitution;
   double rest_vth = 0.0;               // the restitution threshold speed
+  egs::RayTable rays;
   ~egs_world() { if (prob) egs_problem_destroy(prob); }
 };
 
@@ -204,6 +218,8 @@ inline egs_status world_check_ensembles(egs_world *w, int32_t n_ensembles) {
 }
 
 // ---- world.cpp -----------------------------------------------------------------------------------------------------
+// What is wrong with a shape array (nothing: an empty string); side = NULL: the side lengths are not known yet
+std::string shapes_fault(int n, const int32_t *shape, const double *side);
 // UpdateContacts + pruning on the device (ensembles.cc:393-394), the topology read-back, and a re-plan only when the
 // constraint topology changed: the front of every stepping entry and of the detecting stabilise passes.  lap (may be
 // NULL) takes laps 0 .. 2: collide, topology, re-plan.

@@ -790,6 +790,7 @@ Ensemble::~Ensemble() {
 void Ensemble::Init() {  // ensembles.cc:24-29
   if (live_world_ == world_) live_world_ = nullptr;
   if (world_) { egs_world_destroy(world_); world_ = nullptr; }   // M^-1 / f_ext are re-sent to a fresh world
+  ray_pose_.clear(); world_rays_.clear();                        // ... which holds no rays and no poses yet
   ConstructMassInertiaMatrixInverse();
   InitializeExternalForceTorqueVector();
   VectorXd err = ComputePositionConstraintError();  // CheckInitialConditions, :224-232
@@ -1121,6 +1122,111 @@ void Ensemble::UpdateContacts() {  // ensembles.cc:445-480 (+ :308-328)
   }
 }
 
+namespace {
+
+// pos [n][3] | R [n][9] of the components, the layout of ray_pose_
+void AppendPose(const ComponentsList &cs, std::vector<double> *pos, std::vector<double> *R) {
+  for (const auto &c : cs) {
+    for (int k = 0; k < 3; ++k) pos->push_back(c->p()[k]);
+    for (int k = 0; k < 9; ++k) R->push_back(c->R().d[k]);
+  }
+}
+
+bool SamePose(const std::vector<double> &kept, const std::vector<double> &pos, const std::vector<double> &R) {
+  return !kept.empty() && kept.size() == pos.size() + R.size() &&
+         std::memcmp(kept.data(), pos.data(), pos.size() * sizeof(double)) == 0 &&
+         std::memcmp(kept.data() + pos.size(), R.data(), R.size() * sizeof(double)) == 0;
+}
+
+// the arrays of the ray entries; body_offset shifts the attached rays' indices (a group's world)
+struct RayArrays {
+  std::vector<double> origin, dir, tmax;
+  std::vector<int32_t> body;
+  void Add(const Ray &r, int body_offset) {
+    for (int k = 0; k < 3; ++k) { origin.push_back(r.origin[k]); dir.push_back(r.dir[k]); }
+    tmax.push_back(r.tmax);
+    body.push_back(r.body >= 0 ? r.body + body_offset : r.body);
+  }
+  // one flat key: the table a world holds is sent again only when this changes
+  std::vector<double> Key(const std::vector<int32_t> *ens = nullptr) const {
+    std::vector<double> k(origin);
+    k.insert(k.end(), dir.begin(), dir.end());
+    k.insert(k.end(), tmax.begin(), tmax.end());
+    k.insert(k.end(), body.begin(), body.end());
+    if (ens) k.insert(k.end(), ens->begin(), ens->end());
+    return k;
+  }
+};
+
+bool SameKey(const std::vector<double> &a, const std::vector<double> &b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0);
+}
+
+// The hit of ray r in its ensemble's numbering; the point from the world-frame ray, formed as the device forms it.
+RayHit MakeHit(const Ray &r, const ComponentsList &cs, int32_t body, int body_offset, double t, const double *n) {
+  Vector3d o = r.origin, d = r.dir;
+  if (r.body >= 0) {
+    const Matrix3d &R = cs[(size_t)r.body]->R();
+    const Vector3d c = cs[(size_t)r.body]->p();
+    o = Vector3d(c[0] + ((R.d[0] * r.origin[0] + R.d[1] * r.origin[1]) + R.d[2] * r.origin[2]),
+                 c[1] + ((R.d[3] * r.origin[0] + R.d[4] * r.origin[1]) + R.d[5] * r.origin[2]),
+                 c[2] + ((R.d[6] * r.origin[0] + R.d[7] * r.origin[1]) + R.d[8] * r.origin[2]));
+    d = Vector3d((R.d[0] * r.dir[0] + R.d[1] * r.dir[1]) + R.d[2] * r.dir[2], (R.d[3] * r.dir[0] + R.d[4] * r.dir[1]) + R.d[5] * r.dir[2],
+                 (R.d[6] * r.dir[0] + R.d[7] * r.dir[1]) + R.d[8] * r.dir[2]);
+  }
+  RayHit h;
+  h.body = body >= 0 ? body - body_offset : body;
+  h.t = t;
+  h.normal = Vector3d(n[0], n[1], n[2]);
+  h.point = body == -2 ? o : Vector3d(o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]);
+  return h;
+}
+
+}  // namespace
+
+std::vector<RayHit> Ensemble::CastRays(const std::vector<Ray> &rays) {
+  const size_t nr = rays.size();
+  std::vector<RayHit> out;
+  if (nr == 0) return out;
+  RayArrays a;
+  for (const Ray &r : rays) {
+    if (r.body < -1 || r.body >= n_) throw egs::Error(EGS_ERR_INVALID, "Ensemble::CastRays: a ray's body is not a component");
+    a.Add(r, 0);
+  }
+  std::vector<double> pos, R;
+  AppendPose(components_, &pos, &R);
+  std::vector<int32_t> hit(nr);
+  std::vector<double> t(nr), normal(3 * nr);
+  if (world_ && SamePose(ray_pose_, pos, R)) {   // the device holds these very poses: nothing but the rays goes up
+    const std::vector<double> key = a.Key();
+    if (!SameKey(key, world_rays_)) {
+      world_rays_.clear();
+      egs::check(egs_world_set_rays(world_, (int32_t)nr, nullptr, a.body.data(), a.origin.data(), a.dir.data(), a.tmax.data()));
+      world_rays_ = key;
+    }
+    int32_t got = 0;
+    egs::check(egs_world_cast_rays(world_, (int32_t)nr, &got, hit.data(), t.data(), normal.data()));
+  } else {
+    std::vector<double> side;
+    for (const auto &c : components_) {
+      const Vector3d sl = c->GetSideLengths();
+      for (int k = 0; k < 3; ++k) side.push_back(sl[k]);
+    }
+    const std::vector<int32_t> shape = Shapes();
+    egs::check(egs_cast_rays(egs::DefaultContext(), n_, pos.data(), R.data(), side.data(), shape.empty() ? nullptr : shape.data(),
+                             (int32_t)nr, a.body.data(), a.origin.data(), a.dir.data(), a.tmax.data(), hit.data(), t.data(),
+                             normal.data()));
+  }
+  for (size_t i = 0; i < nr; ++i) out.push_back(MakeHit(rays[i], components_, hit[i], 0, t[i], &normal[3 * i]));
+  return out;
+}
+
+RayHit Ensemble::CastRay(const Vector3d &origin, const Vector3d &dir, double tmax) {
+  Ray r;
+  r.origin = origin; r.dir = dir; r.tmax = tmax;
+  return CastRays({r})[0];
+}
+
 // ensembles.cc:241-329.  UpdateContacts already returns a pruned contact list (the device does the
 // contact-vs-contact and joint-vs-contact passes in the reference's order), so what is left for
 // caller-supplied contacts (SetContacts) is the same scan on the host, and the joint-vs-joint check.
@@ -1286,9 +1392,12 @@ bool Ensemble::StepOnDevice(double dt) {
   prm.cfm = cfm_coeff;
   egs_solve_stats st;
   world_state_.clear();   // (a step that throws leaves no state to trust)
+  ray_pose_.clear();
   egs::check(egs_world_step(world_, dt, /*erp=*/0.2, &prm, detect_contacts ? 1 : 0, &st));
   egs::check(egs_world_get_bodies(world_, pos.data(), R.data(), vl.data(), w.data()));
   if (warm_start_) egs::keep_state(world_state_, pos, R, vl, w);
+  ray_pose_ = pos;
+  ray_pose_.insert(ray_pose_.end(), R.begin(), R.end());
   for (int i = 0; i < n_; ++i) {
     components_[i]->SetP(Vector3d(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]));
     components_[i]->SetV(Vector3d(vl[3 * i], vl[3 * i + 1], vl[3 * i + 2]));
@@ -1547,6 +1656,7 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     if (any) egs::check(egs_world_set_shapes(world_, shape.data()));
   }
   world_state_.clear();
+  ray_pose_.clear();
   if (!joints_sent_ || jb0 != world_jb0_ || jb1 != world_jb1_ || jdata != world_jdata_ || jkind != world_jkind_) {   // re-sent when edited
     egs::check(egs_world_set_joints_kinds(world_, (int32_t)jb0.size(), jkind.data(), jb0.data(), jb1.data(), jdata.data()));
     joints_sent_ = true;
@@ -1584,6 +1694,8 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
   }
   egs::check(egs_world_get_bodies(world_, pos.data(), R.data(), vl.data(), w.data()));
   if (warm) egs::keep_state(world_state_, pos, R, vl, w);
+  ray_pose_ = pos;
+  ray_pose_.insert(ray_pose_.end(), R.begin(), R.end());
   int32_t mcons = 0, mc = 0, replans = 0;
   egs::check(egs_world_info(world_, &mcons, &mc, &replans));
   std::vector<int32_t> jo(E + 1), co(E + 1), cb0((size_t)mc), cb1((size_t)mc);
@@ -1624,6 +1736,48 @@ void EnsembleGroup::Step(const std::vector<double> &dt) {
     for (int r = 0; r < rj; ++r) m->last_lambda(r) = lambda[(size_t)(3 * jo[i] + r)];
     for (int r = 0; r < rc; ++r) m->last_lambda(rj + r) = lambda[(size_t)(3 * (mj + co[i]) + r)];
   }
+}
+
+std::vector<std::vector<RayHit>> EnsembleGroup::CastRays(const std::vector<std::vector<Ray>> &rays) {
+  const size_t E = members_.size();
+  if (rays.size() != E)
+    throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup::CastRays: " + std::to_string(rays.size()) + " ray lists for " +
+                                          std::to_string(E) + " members");
+  std::vector<std::vector<RayHit>> out(E);
+  std::vector<double> pos, R;
+  for (const Ensemble *m : members_) AppendPose(m->components_, &pos, &R);
+  if (!world_ || !SamePose(ray_pose_, pos, R)) {   // the world does not hold these poses: each member for itself
+    for (size_t i = 0; i < E; ++i) out[i] = members_[i]->CastRays(rays[i]);
+    return out;
+  }
+  RayArrays a;
+  std::vector<int32_t> ens;
+  for (size_t i = 0; i < E; ++i)
+    for (const Ray &r : rays[i]) {
+      if (r.body < -1 || r.body >= members_[i]->n_)
+        throw egs::Error(EGS_ERR_INVALID, "EnsembleGroup::CastRays: a ray's body is not a component of member " + std::to_string(i));
+      a.Add(r, off_[i]);
+      ens.push_back((int32_t)i);
+    }
+  const size_t nr = ens.size();
+  if (nr == 0) return out;
+  const std::vector<double> key = a.Key(&ens);
+  if (!SameKey(key, world_rays_)) {
+    world_rays_.clear();
+    egs::check(egs_world_set_rays(world_, (int32_t)nr, ens.data(), a.body.data(), a.origin.data(), a.dir.data(), a.tmax.data()));
+    world_rays_ = key;
+  }
+  std::vector<int32_t> hit(nr);
+  std::vector<double> t(nr), normal(3 * nr);
+  int32_t got = 0;
+  egs::check(egs_world_cast_rays(world_, (int32_t)nr, &got, hit.data(), t.data(), normal.data()));
+  size_t at = 0;
+  for (size_t i = 0; i < E; ++i)
+    for (const Ray &r : rays[i]) {
+      out[i].push_back(MakeHit(r, members_[i]->components_, hit[at], off_[i], t[at], &normal[3 * at]));
+      ++at;
+    }
+  return out;
 }
 
 Chain::Chain(int num_links, const Vector3d &anchor) {  // ensembles.cc:668-707

@@ -389,6 +389,23 @@ std::vector<bool> SolveLCPBatch(const Settings &settings, std::vector<MatrixXd> 
                                 std::vector<VectorXd> *w);
 }  // namespace lcp
 
+// Not in the reference: ray casts against the ground and the bodies (egs_cast_rays; the rules are stated above it in
+// eggshell_amd.h).  dir is not normalised: t is in its units.  body >= 0 attaches the ray to that component of its
+// ensemble: origin and dir are then in the component's frame and the component itself is not tested.
+struct Ray {
+  Vector3d origin, dir;
+  double tmax = std::numeric_limits<double>::infinity();
+  int body = -1;
+};
+// body: -2 no hit, -1 the ground, else the component's index in its ensemble.  t = tmax on a miss; normal = 0 on a miss
+// and where the origin is inside the solid (t = 0).  point = the world-frame origin + t x the world-frame dir, the
+// origin itself on a miss.
+struct RayHit {
+  int body;
+  double t;
+  Vector3d normal, point;
+};
+
 class Ensemble {  // ensembles.h:25-186
  public:
   virtual ~Ensemble();
@@ -429,6 +446,14 @@ class Ensemble {  // ensembles.h:25-186
   // update contacts_ (ensembles.cc:445-480), then drop contacts closer than
   // 1e-6 to an earlier contact of the same pair (ensembles.cc:308-328): on the GPU.
   void UpdateContacts();
+  // Rays against the ground and the components as they are now.  While the ensemble steps on the device and the Body
+  // objects still hold what the last step left there, the table goes to the device world and is cast against the state
+  // it holds (egs_world_set_rays, sent again only when the rays change; egs_world_cast_rays): no body state crosses.
+  // Otherwise -- before the first Step, on the explicit paths, after a Body was edited -- the stateless entry on the
+  // components' current poses (egs_cast_rays).  Both give the same bits.  Throws egs::Error(EGS_ERR_INVALID) as the
+  // entries refuse: a non-finite or zero ray, tmax < 0, a body index out of range.
+  std::vector<RayHit> CastRays(const std::vector<Ray> &rays);
+  RayHit CastRay(const Vector3d &origin, const Vector3d &dir, double tmax = std::numeric_limits<double>::infinity());
   // Check whether there exist constraint pairs that are too close to each other (ensembles.cc:241-329):
   // conflicting joints between one pair of components are an error (the reference Panics; here
   // egs::Error with EGS_ERR_INVALID), a contact closer than 1e-6 to a joint or to an earlier contact
@@ -575,6 +600,8 @@ class Ensemble {  // ensembles.h:25-186
   bool problem_restitution_ = false;             // the cached device problem holds restitution coefficients
   double device_friction() const { return friction_model_ == Contact::FrictionModel::COULOMB_PYRAMID ? friction_mu_ : -1.0; }
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last device step (warm start only)
+  std::vector<double> ray_pose_;                 // pos, R as pulled after the last device step: what the world's rays would see
+  std::vector<double> world_rays_;               // the ray table the device world holds (origin, dir, tmax, body per ray)
   egs_problem *problem_ = nullptr;
   std::vector<int32_t> plan_b0_, plan_b1_;   // topology the cached device problem was planned for
 };
@@ -628,6 +655,10 @@ class EnsembleGroup {
   // how many ensembles the group's device world holds (0 before the first Step) and how many worlds it has made
   int world_ensembles() const;
   int worlds_created() const { return worlds_created_; }
+  // rays[i]: member i's rays, body indices in member i's own numbering; the result likewise.  One table and one launch on
+  // the group's world while every member's Body objects hold what the last group Step left there; otherwise each member
+  // casts for itself (Ensemble::CastRays).
+  std::vector<std::vector<RayHit>> CastRays(const std::vector<std::vector<Ray>> &rays);
 
  private:
   std::vector<Ensemble *> members_;
@@ -648,6 +679,8 @@ class EnsembleGroup {
   double world_restitution_vth_ = 0.0;
   std::vector<char> world_live_;                 // ... and the members' SetLiveInertia (empty: never told, all off)
   std::vector<double> world_state_;              // pos, R, v, w as pulled after the last step (warm start only)
+  std::vector<double> ray_pose_;                 // pos, R as pulled after the last step: what the world's rays would see
+  std::vector<double> world_rays_;               // the ray table the world holds (origin, dir, tmax, body, ensemble per ray)
 };
 
 #endif

@@ -1196,6 +1196,78 @@ egs_status egs_debug_matvec_plan(int32_t n_bodies, int32_t m, const int32_t *bod
                                  int32_t *n_islands, int32_t *n_shared_bodies,
                                  int32_t *n_boundary, int32_t *cons_tile, int32_t *cons_lane);
 
+/* ---- ray casts: a question put to the solids the collider knows -- the ground and the three shapes of egs_shape.
+ * Ray.  Origin o[3] and direction d[3] are finite and d != 0.  d is not normalised by the library: t is in units of d,
+ *   so a unit d gives metres.  tmax >= 0, +inf allowed.  The ray is the set o + t d, 0 <= t <= tmax.
+ * Result per ray.  body (int32): -2 no hit, -1 the ground, otherwise the global body index.  t (fp64): tmax on a miss.
+ *   normal[3]: the unit outward normal of the surface at the hit; (0, 0, 0) on a miss and where the origin is inside the
+ *   solid (then t = 0).
+ * Solids.  The collider's conventions; R is taken as orthonormal and is not renormalised.  All of it runs in fp64 on
+ *   the fp64 pos / R / side / shape arrays the collider reads, whatever the world's solve precision, without fused
+ *   multiply-adds, a . b = (a0 b0 + a1 b1) + a2 b2.
+ *   Entering root of |w + t d|^2 = r^2 (used for every ball and, in the perpendicular components, for the capsule's
+ *     side): the perpendicular-offset form, which does not cancel for a far origin.  s = (w . d) / (d . d),
+ *     m = w - s d, disc = r^2 - m . m; no root unless disc >= 0; t = -s - sqrt(disc / (d . d)); it counts iff t >= 0.
+ *   Ground: the half space z < 0.  Origin inside iff o_z < 0 strictly.  Otherwise a hit iff d_z < 0, at
+ *     t = o_z / (-d_z), normal (0, 0, 1).  A level ray (d_z == 0) never hits, at any height.
+ *   Sphere: side row (d, d, d), r = d / 2, R not read.  w = o - c.  Inside iff w . w < r^2.  Otherwise the entering
+ *     root; normal = (w + t d) normalised.
+ *   Box: the slab test in the box frame, p = R^T (o - c), q = R^T d, h = side / 2.  An axis with q_k == 0 exactly
+ *     rejects iff |p_k| > h_k; otherwise its roots are (-h_k - p_k) / q_k and (h_k - p_k) / q_k.  t_in = the largest
+ *     near root, t_out = the smallest far root.  A hit iff t_in <= t_out and t_out > 0.  t_in < 0: the origin is inside.
+ *     Otherwise t = t_in, normal = -sgn(q_k) (column k of R) for the axis k that gave t_in (lowest k on a tie).
+ *   Capsule: side row (d, d, l), u = column 2 of R, r = d / 2, e = (l - d) / 2: the union of the cylinder
+ *     {|s| <= e, rho <= r} and the balls at c -+ e u.  w = o - c.  Inside iff |w - s u|^2 < r^2 with
+ *     s = min(max(w . u, -e), e), the collider's clamp.  Otherwise the smallest of three candidates' t, compared with
+ *     strict < in this order: the side, the ball at end 0 (c - e u), the ball at end 1.  Side: w' = w - (w . u) u,
+ *     d' = d - (d . u) u, the entering root of |w' + t d'|^2 = r^2 with d' . d' in the place of d . d; it does not
+ *     exist when d' . d' == 0 exactly, and counts only when t >= 0 and (w . u) + t (d . u) lies in [-e, e]; normal =
+ *     (w' + t d') normalised.  A ball: the sphere's entering root and normal about its centre.
+ * Choosing among solids.  The smallest computed t with t <= tmax; a tie goes to the ground first, then to the lowest
+ *   body index; a solid that holds the origin counts with t = 0, so an origin inside several reports the first of them
+ *   in that order.  The answer therefore does not depend on the order in which bodies are visited.
+ * On a surface, along a face, through an edge -- each falls the way the comparisons above say, in fp64:
+ *   origin on the ground plane (o_z == 0): not inside; looking down it hits at t = 0, level or up it misses.
+ *   origin on a sphere (w . w == r^2 in fp64): not inside; it hits only if the rounded root is >= 0, so a ray leaving
+ *     outwards misses and one heading inwards hits at t = 0 or misses by the last bit -- a root of -1 ulp is a miss.
+ *   origin on a box face: t_in == 0 is a hit at t = 0 with that face's normal, whether the ray heads in or runs along
+ *     the face inside the other two slabs (q_k == 0 and |p_k| == h_k is not rejected); leaving outwards t_out == 0 misses.
+ *   a ray through a box edge or corner: two or three near roots tie, the lowest axis gives the normal; if rounding
+ *     makes t_in > t_out the ray misses.
+ *   a grazing ray (disc == 0) hits; the seam of a capsule: side and ball give the same point, the side wins a tie;
+ *   a ray exactly along a capsule's axis has no side candidate and hits an end ball at its pole.
+ *   t == tmax is a hit.  A hit at t = -0.0 (a root (0) / (negative)) is reported as computed.
+ * A bounding-sphere rejection may run before the exact tests and never changes a result (its bound is inflated beyond
+ *   the rounding of the tests); by default it runs where an ensemble holds more than 128 bodies on average, and
+ *   EGS_RAY_CULL=0 / 1 in the environment forces it off / on.
+ * Frames.  A ray may be attached to a body b of its own ensemble (ray_body[i] = b, -1 = world frame): o, d are then in
+ *   b's frame, the device forms o_w = c_b + R_b o (each component c + ((R0 o0 + R1 o1) + R2 o2)) and d_w = R_b d from
+ *   the state it holds at that moment, and body b is not tested: a sensor follows its carrier with no read-back and
+ *   never sees its own hull.
+ * Ensembles.  In a batched world every ray names its ensemble; it sees that ensemble's bodies and the ground, nothing else.
+ *
+ * egs_cast_rays: host arrays, one ensemble, as egs_update_contacts_shapes takes them (shape NULL = boxes; shapes and
+ *   sides checked by the same rules).  ray_body [n_rays] or NULL = world frame; normal [n_rays][3] or NULL.
+ *   n_rays = 0 is EGS_OK.
+ * egs_world_set_rays: stores the table on the device; n_rays = 0 drops it.  ray_ens [n_rays], non-decreasing, is
+ *   required in a batched world and may be NULL in a plain one; ray_body holds global body indices.  The table
+ *   survives egs_world_set_bodies, steps, re-plans and the stabilise entries.
+ * egs_world_cast_rays: one launch on the world's stream against the state the device holds now, one read-back, one
+ *   synchronise; *n_out (may be NULL) = the table's size.  Valid after egs_world_set_bodies.  Casting reads the world
+ *   and writes nothing the steps read.
+ * EGS_ERR_INVALID, with nothing changed and no output written: a required array NULL; a non-finite o or d, a zero d; a
+ *   negative or NaN tmax; a ray_ens out of range or not non-decreasing; a ray_body out of range or outside the ray's
+ *   ensemble; max_rays smaller than the table; a cast with no table.                                               */
+egs_status egs_cast_rays(egs_context *ctx, int32_t n_bodies, const double *pos, const double *R,
+                         const double *side_lengths, const int32_t *shape /*or NULL = boxes*/,
+                         int32_t n_rays, const int32_t *ray_body /*[n_rays] or NULL = world frame*/,
+                         const double *origin, const double *dir, const double *tmax,
+                         int32_t *hit_body, double *t, double *normal /*[n_rays][3] or NULL*/);
+egs_status egs_world_set_rays(egs_world *w, int32_t n_rays, const int32_t *ray_ens /*NULL: plain world*/,
+                              const int32_t *ray_body, const double *origin, const double *dir, const double *tmax);
+egs_status egs_world_cast_rays(egs_world *w, int32_t max_rays, int32_t *n_out,
+                               int32_t *hit_body, double *t, double *normal);
+
 #ifdef __cplusplus
 }
 #endif
