@@ -17,6 +17,15 @@ The step of one ensemble (tests/world_combo_cases.py: a Scene with one ensemble)
              box form, sweep_reference.sweeps)
   v', p', R' model_reference.velocity_reference / position_reference
 
+The scenes of world_combo_cases.PLUS_TABLE add four features, again from their own modules unchanged:
+
+  contacts   capsule_twin / capsule_reference for a pair with a capsule (capsule_twin is sphere_twin on a list without one)
+  assembly   slider_reference's twin and reference for a slider's rows, travel stop included; limit_reference's for the
+             axis row of a hinge past a stop (err[2], its tolerance, the one-sided bounds; the motor leaves the row alone);
+             every other row from joint_reference as before (the modules agree bit for bit on those: asserted)
+  residual   a row pinned by lo == hi is in none of the residual's sums: check_solution
+  rays       after the step, ray_twin and ray_reference on the poses it left
+
 Every reference takes the exact fp64 values handed to the code under test, as its own module says: the lambda
 reference the blocks and rhs that code assembled, the velocity reference its lambda.  So one wrong stage shows at that
 stage and is not smeared over the ones that follow.
@@ -31,14 +40,20 @@ import types
 import mpmath as mp
 import numpy as np
 
+import capsule_reference as capref
+import capsule_twin
 import collision_reference as cref
 import friction_port
 import friction_reference as fr
 import inertia_reference as ir
 import joint_reference as jr
+import limit_reference as lr
 import live_inertia_cases as lic
 import model_reference as mr
+import ray_reference as rayref
+import ray_twin
 import restitution_reference as rr
+import slider_reference as sr
 import sphere_reference as sref
 import sphere_twin
 import sweep_reference as sw
@@ -65,8 +80,9 @@ def joints_of(e):
 
 def full_case(sc, state, mass, contacts, dt, erp):
     """The list a world step solves -- joints first, then the contacts -- as a model_reference case, with the
-    per-constraint tables the world must have filled in: (case, motor, mu, rest), tables None where the scene never
-    sets them."""
+    per-constraint tables the world must have filled in: (case, motor, mu, rest, hinge limits [m][8], travel stops
+    [m][2]), tables None where the scene never sets them.  A contact's rows of the two stop tables are zeros (no stop)
+    and (-inf, +inf)."""
     e = sc.ens[0]
     kind, b0, b1, data, motor = joints_of(e)
     c0, c1, cd = contacts
@@ -78,7 +94,9 @@ def full_case(sc, state, mass, contacts, dt, erp):
                 data=np.concatenate([data, np.asarray(cd, np.float64).reshape(-1, 7)]), dt=float(dt), erp=float(erp))
     table = lambda t: None if t is None else np.concatenate([np.full(mj, -1.0), np.full(mc, float(t[0]))])
     full_motor = np.concatenate([motor, np.tile([0.0, -1.0], (mc, 1))]) if sc.kinds and mj else None
-    return case, full_motor, table(sc.mu), table(sc.rest)
+    lim = np.concatenate([e["limits"], np.zeros((mc, 8))]) if sc.limits and e.get("limits") is not None else None
+    travel = np.concatenate([e["travel"], np.tile([-np.inf, np.inf], (mc, 1))]) if sc.travel and e.get("travel") is not None else None
+    return case, full_motor, table(sc.mu), table(sc.rest), lim, travel
 
 
 class _Listed:
@@ -117,20 +135,38 @@ def twin_mass(sc, state, mass):
 def twin_detect(sc, state):
     e = sc.ens[0]
     shape = e["shape"] if sc.shapes else np.zeros(len(e["shape"]), np.int32)
+    if sc.capsules:
+        if not (shape == wc.CAPSULE).any():      # on a list without capsules the capsule twin is the sphere twin
+            a, b = capsule_twin.contacts(state[0], state[1], e["side"], shape), sphere_twin.contacts(state[0], state[1], e["side"], shape)
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+        return capsule_twin.contacts(state[0], state[1], e["side"], shape)
     return sphere_twin.contacts(state[0], state[1], e["side"], shape)
 
 
 def twin_assemble(sc, state, mass, contacts, dt, erp):
     """The system of the step in fp64: joint_reference's twin for the blocks and the joints' rows, restitution_reference's
     for the contacts' rows.  Returns (case, tables, dict J0, J1, err, lo, hi, is_eq, rhs, what, margin)."""
-    case, motor, mu, rest = full_case(sc, state, mass, contacts, dt, erp)
-    tw = jr.twin_assemble(case, motor)
+    case, motor, mu, rest, lim, travel = full_case(sc, state, mass, contacts, dt, erp)
+    if (case["kind"] == sr.SLIDER).any() or lim is not None:
+        # slider_reference's twin takes the sliders' rows and hands the others to limit_reference's, which takes the stopped
+        # hinges' axis rows and hands the others to joint_reference's
+        tw = sr.twin_assemble(case, motor, travel, hinge_lim=lim if lim is not None else np.zeros((case["kind"].shape[0], 8)))
+        old, sub = sr._others(case)
+        plain = jr.twin_assemble(sub, None if motor is None else motor[old])
+        for i, k in enumerate(old):      # the three modules agree bit for bit on every row that none of them changes
+            rows = slice(3 * k, 3 * k + (2 if tw["active"][k] else 3))
+            for name in ("err", "lo", "hi", "rhs"):
+                assert jr.bits_equal(tw[name][rows], plain[name][3 * i:3 * i + rows.stop - rows.start]), (k, name)
+            assert jr.bits_equal(tw["J0"][k], plain["J0"][i]) and jr.bits_equal(tw["J1"][k], plain["J1"][i])
+    else:
+        tw = jr.twin_assemble(case, motor)
+        tw["active"] = np.zeros(case["kind"].shape[0], np.int32)
     rhs_c, what, margin = rr.twin_rhs(case, tw["J0"], tw["J1"], tw["err"], rest, sc.vth)
     contact = np.repeat(case["kind"] == jr.CONTACT, 3)
     ball = np.repeat(case["kind"] == jr.BALL, 3)
     assert np.array_equal(rhs_c[ball], tw["rhs"][ball])      # both twins restate the same rows
     tw["rhs"] = np.where(contact, rhs_c, tw["rhs"])
-    tw.update(what=what, margin=margin)
+    tw.update(what=what, margin=margin, lim=lim, travel=travel)
     return case, (motor, mu, rest), tw
 
 
@@ -144,7 +180,7 @@ def twin_step(sc, state, mass, prev, dt, erp, dense=False):
     m, mj = case["kind"].shape[0], len(joints_of(e)[0])
     s = flat(case, tw["J0"], tw["J1"], tw["is_eq"], tw["lo"], tw["hi"])
     rec = dict(state=state, mass_in=mass, mass=(Minv, f_ext), contacts=contacts, case=case, motor=motor, mu=mu, rest=rest,
-               tw=tw, what=tw["what"], margin=tw["margin"], prev=prev, dt=dt, erp=erp, dense=dense, x0=None, src=None, cond=None)
+               tw=tw, what=tw["what"], margin=tw["margin"], lim=tw["lim"], travel=tw["travel"], prev=prev, dt=dt, erp=erp, dense=dense, x0=None, src=None, cond=None)
     muf = np.full(m, -1.0) if mu is None else mu
     if dense:
         A0 = dense_numpy(s, 0.0)[0]
@@ -157,10 +193,15 @@ def twin_step(sc, state, mass, prev, dt, erp, dense=False):
             rec["x0"], rec["src"] = expected_x0(prev, contacts, mj, tw["rhs"])
         p = sc.prm
         lam, acc, wres, res = friction_port.sweeps(s, tw["rhs"], p["cfm"], muf, p["method"], p["omega"], p["max_iters"], False, rec["x0"])
+        pinned = pinned_rows(tw["is_eq"], tw["lo"], tw["hi"])
+        if pinned.any():      # the port's residual is the rule from before pinned rows: they are in none of the sums
+            res = friction_port.residual(lam, np.where(pinned, 0.0, wres), tw["is_eq"], tw["lo"], tw["hi"], muf)
         rec.update(acc=acc, wres=wres, res=res)
     v6 = orc.velocity_update(state[2], state[3], Minv, f_ext, case["body0"], case["body1"], tw["J0"], tw["J1"], lam, dt)
     p1, R1 = orc.position_update(state[0], state[1], np.concatenate([state[2], state[3]], axis=1), v6, dt)
     rec.update(lam=lam, v6=v6, after=(p1, R1, v6[:, :3].copy(), v6[:, 3:].copy()))
+    if sc.rays:
+        rec["rays"] = twin_rays(sc, rec["after"])
     rec["left_out"] = left_out(sc, rec)
     return rec
 
@@ -174,7 +215,8 @@ def twin_run(sc):
     out = []
     for k, (dt, erp) in enumerate(sc.rates):
         if dt[0] == 0.0:
-            out.append(dict(dt=0.0, left_out={}, contacts=twin_detect(sc, state), src=None, what=[]))
+            out.append(dict(dt=0.0, left_out={}, contacts=twin_detect(sc, state), src=None, what=[],
+                            rays=twin_rays(sc, state) if sc.rays else None))
             continue
         dense = sc.entry == "dense" and k % 2 == 1
         rec = twin_step(sc, state, mass, prev if sc.warm else None, dt[0], erp[0], dense)
@@ -197,10 +239,12 @@ def collision_left_out(sc, state, contacts):
     for k in range(len(b0)):
         rows.setdefault((int(b0[k]), int(b1[k])), []).append(np.asarray(data[k]))
     tally, balls = cref.Tally(), {}
-    radius = np.where(shape == wc.SPHERE, 0.5 * side[:, 0], 0.5 * np.linalg.norm(side, axis=1))
+    radius = np.where(shape == wc.SPHERE, 0.5 * side[:, 0], np.where(shape == wc.CAPSULE, 0.5 * side[:, 2], 0.5 * np.linalg.norm(side, axis=1)))
     for b in range(n):
         got = rows.pop((-1, b), [])
-        if shape[b] == wc.SPHERE:
+        if shape[b] == wc.CAPSULE:
+            capref.compare(capref.capsule_ground(p[b], R[b], side[b]), got, balls, ground=True)
+        elif shape[b] == wc.SPHERE:
             g = sref.sphere_ground(p[b], side[b][0])
             g["guard_n"] = False
             sref.compare(g, got, balls)
@@ -211,6 +255,8 @@ def collision_left_out(sc, state, contacts):
             got = rows.pop((i, j), [])
             if np.linalg.norm(p[i] - p[j]) > (radius[i] + radius[j]) * (1 + 1e-9):
                 assert not got, "contacts between bodies %d and %d, whose bounding spheres are apart" % (i, j)
+            elif shape[i] == wc.CAPSULE or shape[j] == wc.CAPSULE:
+                capref.compare(capref.pair(p, R, side, shape, i, j), got, balls)
             elif shape[i] == wc.SPHERE or shape[j] == wc.SPHERE:
                 sref.compare(sref.pair(p, R, side, shape, i, j), got, balls)
             else:
@@ -247,7 +293,120 @@ def left_out(sc, rec):
             warm += int(any(abs(x - r2) < 1e-9 * r2 for x in d2) or (len(d2) > 1 and d2[0] <= r2 and d2[1] - d2[0] < 1e-9 * r2))
     out["warm"] = warm
     out["dense"] = int(rec["cond"] is not None and DENSE_COND / 10 < rec["cond"] < DENSE_COND * 10)
+    if sc.limits or sc.travel:
+        _, dist = stop_reference(case, rec.get("lim"), rec.get("travel"))
+        out["limit"] = sum(1 for i, d in enumerate(dist) if d is not None and case["kind"][i] == jr.HINGE and d <= lr.MARGIN)
+        out["travel"] = sum(1 for i, d in enumerate(dist) if d is not None and case["kind"][i] == sr.SLIDER and d <= sr.MARGIN)
+    if sc.rays and rec.get("after") is not None:
+        out["rays"] = sum(1 for r in reference_rays(sc, rec["after"]) if r[0] is None)
     return out
+
+
+# ---- stops and rays -----------------------------------------------------------------------------------------------------------
+def stop_reference(case, lim, travel):
+    """Per constraint, by the references' own decisions (atan2 for a hinge, the 50-digit travel for a slider): (active
+    [m]: +1 upper, -1 lower, 0; the distance from the nearest stop set, in tan(theta / 2) or in metres, None where no
+    table applies)."""
+    m = case["kind"].shape[0]
+    active, dist = np.zeros(m, np.int32), [None] * m
+    if lim is not None:
+        with mp.workdps(mr.DPS):
+            for i, r in enumerate(lr.case_reference(case, lim)):
+                if r is not None:
+                    active[i], dist[i] = r[0], float(r[3])
+    if travel is not None:
+        with mp.workdps(mr.DPS):
+            p, R = [mr._v(x) for x in case["p"]], [mr._m3(x) for x in case["R"]]
+            for i in np.nonzero(case["kind"] == sr.SLIDER)[0]:
+                d, b1 = mr._v(case["data"][i]), int(case["body1"][i])
+                ref = sr.slider_reference(p[int(case["body0"][i])], R[int(case["body0"][i])], p[b1] if b1 >= 0 else None, d[0:3], d[3:6])
+                act, _, _, ds = sr.stop_reference(ref["x"], ref["dx"], float(travel[i][0]), float(travel[i][1]))
+                assert ref["dx"] < sr.MARGIN
+                active[i], dist[i] = act, (float(ds) if ds != mp.inf else None)
+    return active, dist
+
+
+def _rays_of(sc, state):
+    """The ensemble's rays in the world frame at the pose given: (origins, directions, tmax, carrier)."""
+    r = sc.ens[0]["rays"]
+    o, d = [], []
+    for k in range(len(r["body"])):
+        b = int(r["body"][k])
+        ow, dw = (r["origin"][k], r["dir"][k]) if b < 0 else ray_twin.world_frame(state[0][b], state[1][b], r["origin"][k], r["dir"][k])
+        o.append(ow); d.append(dw)
+    return np.array(o, np.float64), np.array(d, np.float64), r["tmax"], r["body"]
+
+
+def twin_rays(sc, state):
+    """(hit_body, t, normal) of the ensemble's ray table against the state given, by ray_twin."""
+    e = sc.ens[0]
+    r = e["rays"]
+    shape = e["shape"] if sc.shapes else None
+    return ray_twin.cast(state[0], state[1], e["side"], shape, r["origin"], r["dir"], r["tmax"], r["body"])
+
+
+@functools.lru_cache(maxsize=256)
+def _reference_rays(key):
+    pos, R, side, shape, o, d, tmax, body = (np.frombuffer(b, t).reshape(s) for b, t, s in key)
+    return [rayref.cast_one(pos, R, side, shape, o[k], d[k], tmax[k], int(body[k])) for k in range(len(body))]
+
+
+def reference_rays(sc, state):
+    """[(kind, body, t, normal)] per ray by ray_reference, on the world-frame rays the twin's fp64 frame change gives (a
+    carried ray's origin and direction are inputs of the reference, as every ray's are; the frame change itself is held
+    to 50 digits by frame_change_error).  Cached by the bits of its
+    inputs: the CPU test and left_out ask for the same casts."""
+    e = sc.ens[0]
+    o, d, tmax, body = _rays_of(sc, state)
+    shape = e["shape"] if sc.shapes else np.zeros(len(e["shape"]), np.int32)
+    arrs = (np.asarray(state[0], np.float64), np.asarray(state[1], np.float64), e["side"], shape, o, d, tmax, body)
+    return _reference_rays(tuple((np.ascontiguousarray(a).tobytes(), a.dtype.str, a.shape) for a in arrs))
+
+
+def frame_change_error(sc, state, o, d):
+    """The fp64 frame change of the carried rays (ray_twin.world_frame, which the device mirrors bit for bit) against
+    o_w = c + R o, d_w = R d at 50 digits: the worst error over its tolerance, 5u of the magnitude sum per component (a
+    three-term product sum, one addition for the origin).  ray_reference rounds its inputs to fp64, so it is handed the
+    fp64 world-frame ray; this is the independent check of the step before it."""
+    r = sc.ens[0]["rays"]
+    worst = 0.0
+    with mp.workdps(rayref.DPS):
+        for k in range(len(r["body"])):
+            b = int(r["body"][k])
+            if b < 0:
+                continue
+            c, R = mr._v(state[0][b]), mr._m3(state[1][b])
+            lo, ld = mr._v(r["origin"][k]), mr._v(r["dir"][k])
+            for j in range(3):
+                for base, loc, got in ((c[j], lo, o[k][j]), (mp.mpf(0), ld, d[k][j])):
+                    want = base + sum(R[j][i] * loc[i] for i in range(3))
+                    mag = abs(base) + sum(abs(R[j][i] * loc[i]) for i in range(3))
+                    if mag > 0:
+                        worst = max(worst, float(abs(mp.mpf(float(got)) - want) / (5 * mr.U * mag)))
+                    else:
+                        assert float(got) == 0.0
+    return worst
+
+
+def check_rays(sc, state, got):
+    """got = (hit_body, t, normal) against reference_rays: the body of every decided ray; t |d| and the normal within
+    ray_reference's bound for scenes of a metre or two (collision_reference.TOL).  Returns the worst error / bound."""
+    hit, t, normal = got
+    o, d, tmax, body = _rays_of(sc, state)
+    assert frame_change_error(sc, state, o, d) <= 1.0
+    worst = 0.0
+    with mp.workdps(rayref.DPS):
+        for k, (kind, rb, rt, rn) in enumerate(reference_rays(sc, state)):
+            if kind is None:
+                continue
+            assert int(hit[k]) == rb, ("ray %d: body %d, the reference says %s %d" % (k, hit[k], kind, rb))
+            if kind != "hit":
+                assert t[k] == (0.0 if kind == "inside" else tmax[k]) and not normal[k].any(), (k, kind, t[k])
+                continue
+            dn = mp.sqrt(sum(mp.mpf(float(x)) ** 2 for x in d[k]))
+            err = max([abs(mp.mpf(float(t[k])) - rt) * dn] + [abs(mp.mpf(float(normal[k][j])) - rn[j]) for j in range(3)])
+            worst = max(worst, float(err / rayref.TOL))
+    return worst
 
 
 # ---- the composed reference -----------------------------------------------------------------------------------------------------
@@ -281,8 +440,17 @@ def inertia_agrees(sc, state):
 
 
 def rhs_reference(case, asm, motor, rest, vth):
-    """The composed rhs as Checked, the restitution decisions, and (lo, hi) with the motors' limits."""
-    rj = jr.rhs_reference(case, asm, motor)
+    """The composed rhs as Checked, the restitution decisions, and (lo, hi) with the motors' limits.  An asm of
+    stops_assembly_reference (it has `active`) takes the joints' rows and the bounds from slider_reference, which leaves
+    the motor off a row whose stop is active."""
+    if "active" in asm:
+        idle = motor
+        if motor is not None:      # the motor leaves an active hinge stop's row alone, as it does a slider's
+            idle = motor.copy()
+            idle[(asm["active"] != 0) & (case["kind"] == jr.HINGE)] = (0.0, -1.0)
+        rj = sr.rhs_reference(case, asm, idle)
+    else:
+        rj = jr.rhs_reference(case, asm, motor)
     rc, what = rr.rhs_reference(case, asm, rest, vth)
     m = case["kind"].shape[0]
     out = mr.Checked(3 * m)
@@ -292,7 +460,7 @@ def rhs_reference(case, asm, motor, rest, vth):
             if case["kind"][i] == jr.BALL:      # neither reference changes a ball joint's rows
                 assert rj.val[k] == rc.val[k] and rj.tol[k] == rc.tol[k]
             out.put(k, src.val[k], src.mag[k], src.tol[k])
-    return out, what, jr.motor_bounds(case, asm, motor)
+    return out, what, (sr.bounds_reference(case, asm, idle) if "active" in asm else jr.motor_bounds(case, asm, motor))
 
 
 def rhs_each_reference(cases, asms, motors, rests, vth):
@@ -310,11 +478,31 @@ def rhs_each_reference(cases, asms, motors, rests, vth):
     return out
 
 
+def stops_assembly_reference(case, lim, travel):
+    """The assembly of a list that may hold sliders and stopped hinges: slider_reference.assemble_reference (the sliders
+    from it with an active travel stop in place, every other row from joint_reference), then on a hinge whose stop
+    limit_reference finds active, err[2] with its tolerance and the one-sided bounds."""
+    asm = sr.assemble_reference(case, travel)
+    if lim is not None:
+        with mp.workdps(mr.DPS):
+            for i, r in enumerate(lr.case_reference(case, lim)):
+                if r is None or not r[0]:
+                    continue
+                act, err, tol = r[0], r[1], r[2]
+                asm["active"][i] = act
+                asm["err"].put(3 * i + 2, err, abs(err), tol)
+                asm["lo"][3 * i + 2], asm["hi"][3 * i + 2] = (-np.inf, 0.0) if act > 0 else (0.0, np.inf)
+    return asm
+
+
 def assembly_reference(sc, state, mass, contacts, dt, erp):
-    case, motor, mu, rest = full_case(sc, state, mass, contacts, dt, erp)
-    asm = jr.assemble_reference(case)
+    case, motor, mu, rest, lim, travel = full_case(sc, state, mass, contacts, dt, erp)
+    if (case["kind"] == sr.SLIDER).any() or lim is not None:
+        asm = stops_assembly_reference(case, lim, travel)
+    else:
+        asm = jr.assemble_reference(case)
     rhs, what, (lo, hi) = rhs_reference(case, asm, motor, rest, sc.vth)
-    return dict(case=case, motor=motor, mu=mu, rest=rest, asm=asm, rhs=rhs, what=what, lo=lo, hi=hi)
+    return dict(case=case, motor=motor, mu=mu, rest=rest, lim=lim, travel=travel, asm=asm, rhs=rhs, what=what, lo=lo, hi=hi)
 
 
 def worst(checked, got, f32=False, rows=None):
@@ -355,7 +543,24 @@ def lambda_reference(sc, case, blocks, mu, x0):
 def check_solution(A, muf, blocks, x_ref, lam, acc=None, wres=None, res=None):
     """friction_reference.measure: {x, a, w, r} ratios in units of u max(1, |ref|) etc. (sweep_reference)."""
     _, _, is_eq, lo, hi, rhs, _ = blocks
-    return fr.measure(A, rhs, is_eq, lo, hi, muf, x_ref, lam, acc, wres, res)
+    out = fr.measure(A, rhs, is_eq, lo, hi, muf, x_ref, lam, acc, wres, res)
+    pinned = pinned_rows(is_eq, lo, hi)
+    if res is not None and pinned.any():
+        # DESIGN.md section 4k: a row pinned by lo == hi violates nothing whatever the sign of its w, and the residual
+        # kernels leave it out of all four sums.  friction_reference's rule is the one from before pinned rows existed, so
+        # it is handed w = 0 on them, which puts a row in none of its sums, and no magnitude for them either.
+        with mp.workdps(sw.DPS):
+            w, mag = sw.wres(A, rhs, lam)
+            w = [mp.mpf(0) if pinned[r] else w[r] for r in range(len(w))]
+            mag = [mp.mpf(0) if pinned[r] else mag[r] for r in range(len(mag))]
+            want, scale = fr.residual_pyramid(A, rhs, lam, is_eq, lo, hi, muf, w=(w, mag))
+        out["r"] = sw.err_scalar(res, want, scale, A.f32)
+    return out
+
+
+def pinned_rows(is_eq, lo, hi):
+    """[3m] bool: the inequality rows with lo == hi (a free hinge's axis row, a free slider's rail row)."""
+    return (np.asarray(is_eq) == 0) & (np.asarray(lo) == np.asarray(hi))
 
 
 def carried_sweeps(s, rhs, cfm, mu, method, omega, K, x0=None, f32=False):

@@ -67,12 +67,98 @@ def test_nothing_is_left_out_and_the_seed_is_the_first_accepted(name):
     assert wc.redraw(name) == wc.SEEDS[name]
 
 
+# ---- the scenes with hinge stops, sliders, capsules and rays ------------------------------------------------------------------
+def test_the_plus_table_is_what_the_scenes_are_built_from():
+    for name in wc.PLUS_NAMES:
+        sc = wc.scene(name)
+        on = wc.PLUS_TABLE[name][0]
+        assert (sc.mu is not None) == ("P" in on) and (sc.rest is not None) == ("R" in on) and sc.warm == ("W" in on)
+        assert sc.live == ("L" in on) and sc.shapes == ("S" in on) and sc.kinds == ("K" in on) and sc.f32 == ("32" in on)
+        assert (sc.entry == "step_each") == ("E" in on) and {"S", "L", "W"} <= set(on)
+        e = sc.ens[0]
+        dense = sc.entry == "dense"
+        assert (e["kinds"] is not None) == ("K" in on)
+        kinds = e["kinds"] if e["kinds"] is not None else np.zeros(len(e["joints"][0]), np.int32)
+        assert (e["limits"] is not None) == ("H" in on) == sc.limits and (e["travel"] is not None) == ("D" in on) == sc.travel
+        assert (kinds == wc.SLIDER).any() == ("D" in on or dense) and (e["shape"] == wc.CAPSULE).any() == ("C" in on) == sc.capsules
+        assert (e["rays"] is not None) == ("Y" in on) == sc.rays
+        if "H" in on:      # a motor and both stops on the door's axis row
+            door = int(np.nonzero(e["limits"][:, 4:8].any(axis=1))[0][0])
+            assert e["kinds"][door] == jr.HINGE and e["joints"][1][door] == -1 and e["motors"][door][1] > 0 and e["limits"][door, 4:8].all()
+        if "D" in on:      # a motored slider between two bodies with both stops, one to the world with a lower stop only
+            t, k = e["travel"], e["kinds"] == wc.SLIDER
+            both = np.nonzero(k & np.isfinite(t).all(axis=1))[0]
+            lower = np.nonzero(k & np.isfinite(t[:, 0]) & np.isinf(t[:, 1]))[0]
+            assert len(both) == 1 and e["joints"][1][both[0]] >= 0 and e["motors"][both[0]][1] > 0
+            assert len(lower) == 1 and e["joints"][1][lower[0]] == -1 and e["motors"][lower[0]][1] < 0
+        if dense:          # motored, and no finite stop anywhere
+            assert all(e["motors"][i][1] > 0 for i in np.nonzero((kinds == wc.SLIDER) | (kinds == jr.HINGE))[0])
+        if "C" in on:      # box-shaped inertias: live inertia follows every capsule
+            assert not cr.lic.is_skipped(e["I_body"][e["shape"] == wc.CAPSULE]).any()
+        if "Y" in on:
+            assert 14 <= len(e["rays"]["body"]) <= 20 and (e["rays"]["body"] >= 0).sum() >= 3 and (e["rays"]["body"] < 0).sum() >= 3
+        assert len(sc.rates) == wc.STEPS and all(x["p"].shape[0] <= 18 for x in sc.ens)
+    sc = wc.scene("BATCH+")
+    assert len(sc.ens) == 3 and sc.ens[1]["joints"] is None and (sc.ens[1]["shape"] == wc.CAPSULE).any()
+    assert sc.ens[2]["limits"] is not None and sc.ens[2]["travel"] is not None and sc.rates == wc.BATCH_RATES
+    assert all(len(r["contacts"][0]) == 0 for r in cr.twin_runs("BATCH+")[2])
+
+
+@pytest.mark.parametrize("name", wc.PLUS_NAMES)
+def test_nothing_is_left_out_of_the_plus_scenes_and_the_seed_is_the_first_accepted(name):
+    sc = wc.scene(name)
+    runs = cr.twin_runs(name)
+    for e, run in enumerate(runs):
+        assert len(run) == wc.STEPS
+        for k, rec in enumerate(run):
+            assert all(v == 0 for v in rec["left_out"].values()), (name, e, k, rec["left_out"])
+            if rec["dt"] != 0.0:
+                want = {"collision", "restitution", "branch", "warm", "dense"} | ({"limit", "travel"} if sc.limits or sc.travel else set()) | \
+                       ({"rays"} if sc.rays else set())
+                assert set(rec["left_out"]) == want
+            assert len(rec["contacts"][0]) + (0 if sc.ens[e]["joints"] is None else len(sc.ens[e]["joints"][0])) <= 48
+    assert wc.accepts(sc.single(0) if len(sc.ens) > 1 else sc, runs) == []
+    assert wc.redraw(name) == wc.SEEDS[name]
+
+
+@pytest.mark.parametrize("name", [n for n in wc.PLUS_NAMES if "32" not in n])
+def test_stop_decisions_and_rays_of_the_twins(name):
+    """Every step of every ensemble: the twin's stop decisions (the half-angle comparison, the fp64 travel) are the
+    references' (atan2, the 50-digit travel), the reference's stop rows carry the one-sided bounds, and the ray twin's
+    hits on the poses the step left are ray_reference's bodies, its t and normal within ray_reference's bound."""
+    sc0 = wc.scene(name)
+    acts, worst = set(), 0.0
+    for e, run in enumerate(cr.twin_runs(name)):
+        sc = sc0.single(e) if len(sc0.ens) > 1 else sc0
+        for k, rec in enumerate(run):
+            if rec["dt"] == 0.0:
+                if sc.rays:      # nothing moved: the hits of the step before
+                    assert all(np.array_equal(a, b) for a, b in zip(rec["rays"], run[k - 1]["rays"]))
+                continue
+            active, dist = cr.stop_reference(rec["case"], rec["lim"], rec["travel"])
+            assert np.array_equal(active, rec["tw"]["active"]), (name, e, k)
+            for i in np.nonzero(active)[0]:
+                r = 3 * i + 2
+                acts.add((int(rec["case"]["kind"][i]), int(active[i])))
+                assert (rec["tw"]["lo"][r], rec["tw"]["hi"][r]) == ((-np.inf, 0.0) if active[i] > 0 else (0.0, np.inf))
+                assert rec["tw"]["err"][r] != 0.0 and (rec["tw"]["err"][r] > 0) == (active[i] > 0)
+            if sc.rays:
+                worst = max(worst, cr.check_rays(sc, rec["after"], rec["rays"]))
+    if sc0.limits:
+        assert (jr.HINGE, 1) in acts
+    if sc0.travel:
+        assert {(wc.SLIDER, 1), (wc.SLIDER, -1)} <= acts
+    if sc0.rays:
+        print("%s: ray twin against ray_reference, worst error / bound %.3g" % (name, worst))
+        assert worst <= 1.0
+
+
 def test_all_replans_under_joints():
     counts = [len(r["contacts"][0]) for r in cr.twin_runs("ALL")[0]]
     assert any(a != b for a, b in zip(counts, counts[1:])), counts
 
 
-@pytest.mark.parametrize("name", [n for n in wc.NAMES if "32" not in n])
+@pytest.mark.parametrize("name", [n for n in wc.NAMES + wc.PLUS_NAMES if "32" not in n])
 def test_twins_meet_the_composed_reference(name):
     """Every stage of every step: the mass refresh, the assembly, the rhs with its decisions, lambda with its
     accumulators, w and residual, the velocities and the poses."""
@@ -111,7 +197,7 @@ def test_twins_meet_the_composed_reference(name):
     print("%s: twin against the composition, worst ratio to bound: %s" % (name, " ".join("%s=%.3g" % kv for kv in sorted(worst.items()))))
 
 
-@pytest.mark.parametrize("name", wc.NAMES)
+@pytest.mark.parametrize("name", wc.NAMES + wc.PLUS_NAMES)
 def test_the_carried_twin_finds_the_references_lambda(name):
     """combo_reference.carried_sweeps, whose a and w ratios stand behind the GPU test's bounds where the class constants
     do not reach: its lambda is the reference's within the class bound, and the figures are printed for DESIGN.md."""
@@ -201,3 +287,67 @@ def test_live_inertia_alone_is_the_mass_references():
     assert list(live) == list((e["shape"] == wc.BOX) & ~cube) and live.sum() >= 6 and cr.inertia_agrees(sc, state) < 1e-30
     im, jf = cr.mass_entries(live)
     assert M.worst(e["Minv"], im)[0] <= 1.0 and f.worst(e["f_ext"], jf)[0] <= 1.0
+
+
+def test_hinge_limits_alone_are_limit_reference():
+    """A list with hinge stops and nothing else on: every row but an active stop's is joint_reference's, value and
+    tolerance; an active stop's err[2], tolerance and bounds are limit_reference's, and its motor is off the row."""
+    case, motor, asm0, _, _ = jr.generated("n4m8-b")
+    lim = cr.lr.make_limits(case, 0)
+    asm = cr.stops_assembly_reference(case, lim, None)
+    rhs, what, (lo, hi) = cr.rhs_reference(case, asm, motor, None, 0.0)
+    rhs0 = jr.rhs_reference(case, asm0, motor)
+    lo0, hi0 = jr.motor_bounds(case, asm0, motor)
+    ref = cr.lr.case_reference(case, lim)
+    seen = 0
+    for i in range(case["kind"].shape[0]):
+        act = ref[i][0] if ref[i] is not None else 0
+        assert asm["active"][i] == act
+        for k in range(3 * i, 3 * i + (2 if act else 3)):
+            assert asm["err"].val[k] == asm0["err"].val[k] and asm["err"].tol[k] == asm0["err"].tol[k]
+            assert rhs.val[k] == rhs0.val[k] and rhs.tol[k] == rhs0.tol[k] and (lo[k], hi[k]) == (lo0[k], hi0[k])
+        assert asm["J0"].val[18 * i:18 * i + 18] == asm0["J0"].val[18 * i:18 * i + 18]
+        if act:
+            seen += 1
+            k = 3 * i + 2
+            assert asm["err"].val[k] == ref[i][1] and asm["err"].tol[k] == ref[i][2]
+            assert (lo[k], hi[k]) == ((-np.inf, 0.0) if act > 0 else (0.0, np.inf))
+            if jr.motor_applies(case, motor, i):      # the motor's target is not in the row: it is kk err[2] - J u
+                assert rhs.val[k] != rhs0.val[k]
+    assert seen > 0
+    tw = cr.lr.twin_assemble(case, motor, lim)
+    assert rhs.worst(tw["rhs"])[0] <= 1.0 and asm["err"].worst(tw["err"])[0] <= 1.0
+    assert np.array_equal(tw["lo"], lo) and np.array_equal(tw["hi"], hi)
+
+
+def test_sliders_alone_are_slider_reference():
+    case, motor = cr.sr.generated("n4m8-b")
+    travel = cr.sr.make_travel(case, "mixed")
+    asm, asm0 = cr.stops_assembly_reference(case, None, travel), cr.sr.assemble_reference(case, travel)
+    assert same(asm["err"], asm0["err"]) and same(asm["J0"], asm0["J0"]) and same(asm["J1"], asm0["J1"])
+    assert np.array_equal(asm["active"], asm0["active"]) and asm["active"].any()
+    rhs, what, (lo, hi) = cr.rhs_reference(case, asm, motor, None, 0.0)
+    assert same(rhs, cr.sr.rhs_reference(case, asm0, motor))
+    lo0, hi0 = cr.sr.bounds_reference(case, asm0, motor)
+    assert np.array_equal(lo, lo0) and np.array_equal(hi, hi0)
+
+
+def test_a_pinned_row_is_in_none_of_the_residuals_sums():
+    """Free hinges (no motor): their axis rows are pinned by lo == hi == 0 and carry w != 0.  friction_port's residual
+    sorts such a row as 'on lo with w < 0' or 'on hi with w > 0'; the kernels leave it out.
+    check_solution holds a reported residual to the second rule: the port's own value misses it by the pinned rows' w,
+    the value with those rows left out meets the class bound."""
+    case, _, _, plain, _ = jr.generated("n4m8-b")
+    s = cr.flat(case, plain["J0"], plain["J1"], plain["is_eq"], plain["lo"], plain["hi"])
+    pinned = cr.pinned_rows(plain["is_eq"], plain["lo"], plain["hi"])
+    assert pinned.any() and list(np.nonzero(pinned)[0] % 3) == [2] * int(pinned.sum())
+    mu = np.full(s.m, -1.0)
+    lam, acc, wres, res = cr.friction_port.sweeps(s, plain["rhs"], 0.01, mu, sw.GAUSS_SEIDEL, 1.0, 12)
+    assert np.abs(wres[pinned]).max() > 1e-3 and (lam[pinned] == 0.0).all()
+    left_out = cr.friction_port.residual(lam, np.where(pinned, 0.0, wres), plain["is_eq"], plain["lo"], plain["hi"], mu)
+    assert res - left_out > 1e-3
+    blocks = (plain["J0"], plain["J1"], plain["is_eq"], plain["lo"], plain["hi"], plain["rhs"], plain["err"])
+    A = sw.system(s, 0.01, False)
+    bound = fr.BOUNDS[(CLASS, False)]["r"]
+    assert cr.check_solution(A, mu, blocks, lam, lam, acc, wres, left_out)["r"] <= bound
+    assert cr.check_solution(A, mu, blocks, lam, lam, acc, wres, res)["r"] > 1e6 * bound
