@@ -157,9 +157,12 @@ void launch_step_solve_pair(const SolveArgs<double> &a, int method, int n_tiles,
 // the FACE form of the share launch (step_face.hip): GS, store-free, no restitution, on a plan that is Plan::faced whose
 // groups of four carry one normal (problem.h: face_normals), a.steady on; 128 threads per tile; the same bits.
 // tiles_per_cu: 3 or 4 resident tiles per CU (4: what the registers allow; 3: the launch asks for more LDS)
-// w (NULL: one workgroup per tile, blockIdx = tile): the launch split in time.  w->n_workgroups persistent workgroups
-// take the pieces of w->pieces (policy.h: face_piece_list) by ticket; a split tile's first part hands lambda and the
-// accumulators to its second part through a.x / a.acc and flags[tile]; the same bits.
+// w.pieces NULL: one workgroup per tile, blockIdx = tile.  Otherwise the persistent form (the launch split in time, or
+// more tiles than resident slots): w.n_workgroups workgroups take the pieces of w.pieces (policy.h: face_piece_list) by
+// ticket; a split tile's first part hands lambda and the accumulators to its second part through a.x / a.acc and
+// flags[tile]; the same bits.
+// w.v6 (NULL: off): the epilogue also writes the step's velocities of the bodies of its tile, velocity_kernel's
+// expression on the accumulator it has just stored (a first part does not: its accumulators are not final).
 struct FacePiece;
 struct FaceWork {
   const FacePiece *pieces;   // [n_pieces]
@@ -168,8 +171,10 @@ struct FaceWork {
   uint32_t ticket_base, epoch;
   int32_t n_pieces;
   int32_t n_workgroups;      // the grid: min(pieces, resident slots); every workgroup draws tickets until one is past the list
+  double *v6;                // [n][6] the velocities egs_problem_step leaves (problem.h: v6), or NULL
+  int32_t *host_stall;       // the device address of the problem's page-locked stall word: a wait that overran stores 1
 };
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork *w, hipStream_t s);
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork &w, hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);

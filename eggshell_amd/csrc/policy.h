@@ -133,6 +133,11 @@ inline void face_piece_list(int n_tiles, long slots, FaceSplit f, int S, VEC &ou
   for (int h = 0; h < H; ++h) out.push_back(FacePiece{whole + h, 1, S - f.s1, kFaceSecond});
 }
 
+// The persistent FACE launch without a split: wherever the tiles take more than one round of the resident slots.  With a
+// workgroup per tile the hardware refills freed slots late (32 C3 piles: 0.600 ms where two rounds of 0.237 ms are
+// 0.474); `slots` persistent workgroups on the whole-tile list refill themselves.
+inline bool face_persist_pays(long n_tiles, long slots) { return slots > 0 && n_tiles > slots; }
+
 // Isotropic bodies, batched work: the register-light tile kernel (no stored B, three
 // 256-constraint tiles per CU in fp64, four in fp32) against the regular one (fp64:
 // 512-constraint tiles, one per CU; fp32: three 256-constraint tiles).

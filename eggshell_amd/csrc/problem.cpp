@@ -493,6 +493,12 @@ void ensure_tile_plan(egs_problem *p) {
     }
   }
   const Plan &pl = p->plan;
+  {
+    std::vector<char> in_tile((size_t)(n > 0 ? n : 1), 0);
+    for (const int32_t b : pl.slot_body)
+      if (b >= 0) in_tile[(size_t)b] = 1;
+    p->plan_covers_bodies = n > 0 && std::count(in_tile.begin(), in_tile.end(), 1) == n;
+  }
   p->tile.stage(p->ctx, pl);
   stage(p->ctx, p->gcons, pl.global);
   if (pl.n_patch_tiles > 0) p->patch.stage(p->ctx, pl);
@@ -647,6 +653,7 @@ egs_status egs_problem_create(egs_context *ctx, int32_t n, int32_t m, const int3
     HIPCHK(hipMemsetAsync(p->error_flag.p, 0, 2 * sizeof(int32_t), ctx->stream));
     p->h_flag.alloc(16);   // 64 bytes
     *p->h_flag.p = 0;
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&p->h_flag_dev), p->h_flag.p, 0));
     problem_set_topology(p, m, body0, body1);
     return EGS_OK;
   });
@@ -973,15 +980,22 @@ egs_status egs_problem_step(egs_problem *p, double dt, double erp, const egs_sol
     refresh_live_mass(p);
     note_assembled(p);   // what choose_sweep reads of the blocks this step makes
     egs_status st;
+    // the solve's launch may write the velocities itself (problem.h: step_velocity); whatever happens in the solve, the
+    // offer ends with it
+    struct Offer {
+      egs_problem *p;
+      ~Offer() { p->step_velocity = egs_problem::kVelocityNone; }
+    } offer{p};
     if (step_fuses_assembly(p, params)) {
       const AssembleArgs a = assemble_args(p, dt, erp);
+      p->step_velocity = egs_problem::kVelocityOffered;
       st = do_solve(p, params, stats, &a);
     } else {
       do_assemble(p, dt, erp);
       st = do_solve(p, params, stats);
     }
     if (st != EGS_OK) return st;
-    do_velocity(p, dt);
+    if (p->step_velocity != egs_problem::kVelocityWritten) do_velocity(p, dt);
     return EGS_OK;
   });
 }

@@ -123,7 +123,16 @@ struct egs_problem {
   // it and only reporting it clears it, so a stall in any step of an asynchronous run is seen.
   // [1]: scratch word of the isotropy check.
   egs::DevBuf<int32_t> error_flag;
-  egs::PinnedBuf<int32_t> h_flag;   // page-locked copy of [0] (64 bytes), refreshed by an async copy after every solve
+  // page-locked copy of [0] (64 bytes), refreshed by an async copy after every solve -- except one that was a FACE launch
+  // alone, whose kernel stores to it through h_flag_dev where a wait overruns (step_face.hip)
+  egs::PinnedBuf<int32_t> h_flag;
+  int32_t *h_flag_dev = nullptr;    // its device address (hipHostGetDevicePointer, once per problem)
+  // egs_problem_step's velocities.  The step offers them to its solve; a FACE launch that is the whole solve, on a plan
+  // whose tiles hold every body (plan_covers_bodies: a body in no tile still moves by dt W f), writes them in its
+  // epilogue and says so, and the step then skips velocity_kernel.
+  enum { kVelocityNone = 0, kVelocityOffered = 1, kVelocityWritten = 2 };
+  int step_velocity = kVelocityNone;
+  bool plan_covers_bodies = false;  // of the tile plan: every body 0 .. n - 1 is a slot of some tile
   egs::PinnedBuf<double> h_hist;    // page-locked landing area of the stopping loop's per-sweep residual sums (+ the flag)
   // per-sweep history of a chunk of sweeps (tolerance-terminated solves, see kernels.h)
   egs::DevBuf<unsigned char> hist_x, hist_acc;

@@ -30,6 +30,8 @@ struct SweepSchedule {
   bool face = false;        // ... on a thread pair per box face: four updates behind one barrier, 128 threads per tile (FACE)
   int face_tiles = kFaceTilesPerCu;   // ... at this many resident tiles per CU (policy.h; EGS_STEP_FACE_TILES)
   FaceSplit split;          // ... with the last split.tiles tiles cut after sweep split.s1 (policy.h: face_split_policy)
+  long face_slots = 0;      // ... the workgroups of that launch the GPU holds at once (EGS_STEP_FACE_SLOTS)
+  bool face_persistent = false;   // ... on that many persistent workgroups that take pieces: split, or more tiles than slots
   bool started = false;     // the solve starts from a given x0 (problem.h: start_active), not from rhs
   bool friction = false;    // the kernels' friction forms: SolveArgs::mu is the problem's (problem.h: friction)
   int steady = 0;           // SolveArgs::steady: step_solve_kernel's steady-state loop (it applies at group 1, no snapshots)
@@ -115,12 +117,20 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   if (te && (std::atoi(te) == 3 || std::atoi(te) == 4)) s.face_tiles = std::atoi(te);
   // ... split in time where the last round would leave half the resident slots empty or more (policy.h).
   // EGS_STEP_FACE_SPLIT=0 keeps one workgroup per tile; EGS_STEP_FACE_SPLIT_FORCE=h,s1 splits the last h tiles after s1
-  // sweeps whatever the policy says (tests, experiments).
+  // sweeps whatever the policy says (tests, experiments).  EGS_STEP_FACE_SLOTS=k stands for the resident slots, in the
+  // policy and as the grid of the persistent launch (tests: no small scene has more tiles than the GPU has slots).
   const char *xe = std::getenv("EGS_STEP_FACE_SPLIT"), *xf = std::getenv("EGS_STEP_FACE_SPLIT_FORCE");
+  const char *ke = std::getenv("EGS_STEP_FACE_SLOTS");
+  s.face_slots = ke && std::atol(ke) > 0 ? std::atol(ke) : (long)p->ctx->cu_count * s.face_tiles;
   if (s.face && !(xe && std::atoi(xe) == 0)) {
     long h = 0, s1 = 0;
     if (xf && std::sscanf(xf, "%ld,%ld", &h, &s1) == 2) s.split = face_split_forced(pl.n_tiles, h, s1, sweeps);
-    else if (!xf) s.split = face_split_policy(pl.n_tiles, (long)p->ctx->cu_count * s.face_tiles, pl.max_depth, pl.max_period, sweeps);
+    else if (!xf) s.split = face_split_policy(pl.n_tiles, s.face_slots, pl.max_depth, pl.max_period, sweeps);
+    // ... and persistent workgroups on the whole-tile list wherever the tiles take more than one round: with a
+    // workgroup per tile the hardware refills freed slots late.  EGS_STEP_FACE_PERSIST=0 keeps
+    // the persistent form for split launches alone.
+    const char *re = std::getenv("EGS_STEP_FACE_PERSIST");
+    s.face_persistent = s.split.tiles > 0 || (face_persist_pays(pl.n_tiles, s.face_slots) && !(re && std::atoi(re) == 0));
   }
   return s;
 }
@@ -166,7 +176,7 @@ GlobalArgs<REAL> global_args(const egs_problem *p, REAL cfm, bool hist) {
   return g;
 }
 
-// The work of a split FACE launch: the piece list (built and uploaded when its key changes: never inside a step
+// The work of a persistent FACE launch: the piece list (built and uploaded when its key changes: never inside a step
 // otherwise), the ticket counter and the tiles' flags.  Neither is reset between launches: the counter only grows and
 // the kernel subtracts what it stood at, the flags carry the launch's epoch (on a wrap they are cleared, as the
 // granules' tags are).
@@ -219,11 +229,18 @@ void launch_timetable(egs_problem *p, const SweepSchedule &sc, SolveArgs<REAL> &
   }
   if constexpr (sizeof(REAL) == 8) {
     a.assemble = *assemble;
-    if (sc.face && sc.split.tiles > 0) {
-      const FaceWork w = face_work(p, n_tiles, (long)p->ctx->cu_count * sc.face_tiles, sc.split, sweeps);
-      launch_step_solve_face(a, n_tiles, sc.face_tiles, &w, st);
-    } else if (sc.face) launch_step_solve_face(a, n_tiles, sc.face_tiles, nullptr, st);
-    else if (sc.pair) launch_step_solve_pair(a, method, n_tiles, !sc.defer, sc.chain, sc.share, st);
+    if (sc.face) {
+      FaceWork w = sc.face_persistent ? face_work(p, n_tiles, sc.face_slots, sc.split, sweeps) : FaceWork{};
+      w.host_stall = p->h_flag_dev;
+      // the step's velocities from the epilogue, where egs_problem_step offers them and every body is in some tile (one
+      // in none still moves by dt W f: velocity_kernel's).  EGS_STEP_FACE_VELOCITY=0 keeps velocity_kernel.
+      const char *ve = std::getenv("EGS_STEP_FACE_VELOCITY");
+      if (p->step_velocity == egs_problem::kVelocityOffered && p->plan_covers_bodies && !(ve && std::atoi(ve) == 0)) {
+        w.v6 = p->v6.p;
+        p->step_velocity = egs_problem::kVelocityWritten;
+      }
+      launch_step_solve_face(a, n_tiles, sc.face_tiles, w, st);
+    } else if (sc.pair) launch_step_solve_pair(a, method, n_tiles, !sc.defer, sc.chain, sc.share, st);
     else launch_step_solve_assemble(a, method, n_tiles, !sc.defer, st);
     // the system this launch assembled: stored, or the problem's to make on demand from the state it read
     p->sys_deferred = sc.defer;
@@ -562,7 +579,10 @@ egs_status do_solve(egs_problem *p, const egs_solve_params *prm, egs_solve_stats
     p->last_iterations = prm->max_iters;
     p->have_lambda = true;
     p->residual_pending = !stats;   // nobody is looking: the reduction runs when egs_problem_get_stats asks
-    if (!stats) post_flag_copy(p);  // ... and a stall shows up at the next call or the next synchronising getter
+    // ... and a stall shows up at the next call or the next synchronising getter.  A solve that was one FACE launch
+    // posts no copy: its kernel stores to the page-locked word itself (step_face.hip; the unsplit form has no wait)
+    const bool face_alone = prm->max_iters <= chunk_max && (p->last_sched & EGS_SCHED_FACE) != 0;
+    if (!stats && !face_alone) post_flag_copy(p);
     if (stats) {
       int flag = 0;
       launch_residual(p);

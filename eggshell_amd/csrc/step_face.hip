@@ -148,7 +148,9 @@ __device__ __forceinline__ void face_sides(const Cons<double> &c, int side, Pair
 // The workgroups are persistent: as many as the GPU holds at once (or as there are pieces), each taking piece after
 // piece until a ticket is past the list.  With one workgroup per piece the hardware refilled the freed slots late and
 // unevenly (a tenth of them stood empty while workgroups were pending) and the launch was no shorter than the unsplit
-// one.
+// one.  Nor does workgroup k start with piece k to save its first draw: measured, the headline's
+// launch then took 461 us where it takes 444 (supposedly the list's even mix of first parts and
+// whole tiles no longer reaches every CU once the hardware's placement of workgroup numbers decides who gets which).
 // Only the prologue, the loop bounds and the epilogue differ from the unsplit kernel: n_sweeps and resume are scalar.
 // Returns false once the list is exhausted: the workgroup is done.
 template <bool PIECES>
@@ -254,8 +256,12 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
     __syncthreads();   // the word is read before the accumulators take its place
     if (!ok) {
       // the piece is given up and the launch reports a stall; the workgroup goes on drawing, so that the counter ends
-      // where the host expects it whatever happened
-      if (tid == 0) atomicOr(A.error_flag, 1);
+      // where the host expects it whatever happened.  The host's page-locked copy of the flag is set from here (no copy
+      // is posted behind a FACE launch): system scope, so the host sees it once the launch has ended at the latest
+      if (tid == 0) {
+        atomicOr(A.error_flag, 1);
+        __hip_atomic_store(W.host_stall, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
       return true;
     }
 #pragma unroll
@@ -352,8 +358,19 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
   for (int s = tid + 1; s < nslots; s += kFaceThreads) {
     const int body = slot_body[s];
     if (body < 0) continue;   // unused slot number
+    double acc[6];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) A.acc[(size_t)body * 6 + k] = s_acc[s * 6 + k];
+    for (int k = 0; k < 6; ++k) A.acc[(size_t)body * 6 + k] = acc[k] = s_acc[s * 6 + k];
+    // the step's velocity of the body, velocity_kernel's expression (kernels.hip) on the accumulator just stored: the
+    // same bits.  A first part's accumulators are not the step's: its tile's second part writes.
+    if (W.v6 && kind != kFaceFirst) {
+      const AssembleArgs &G = A.assemble;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const double vel = k < 3 ? G.v[(size_t)body * 3 + k] : G.w[(size_t)body * 3 + k - 3];
+        W.v6[(size_t)body * 6 + k] = vel + G.dt * (G.Wf[(size_t)body * 6 + k] + acc[k]);
+      }
+    }
   }
   if (PIECES && kind == kFaceFirst) {
     // publish: this thread's stores of lambda and the accumulators, released to the agent, before the tile's flag
@@ -364,9 +381,10 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
   return true;
 }
 
-__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A) {
+// (W: the velocity pointer alone is read)
+__global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A, const FaceWork W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  face_step<false>(A, FaceWork{}, smem, (int)threadIdx.x);
+  face_step<false>(A, W, smem, (int)threadIdx.x);
 }
 // ... persistent workgroups, as many as the GPU holds at once: each takes piece after piece until the list is exhausted
 __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_pieces_kernel(const SolveArgs<double> A, const FaceWork W) {
@@ -384,7 +402,7 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_pieces_kernel
 
 }  // namespace
 
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork *w, hipStream_t s) {
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork &w, hipStream_t s) {
   if (n_tiles <= 0) return;
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
@@ -393,9 +411,9 @@ void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_p
   // the registers allow four tiles per CU; a request above a quarter of the CU's 160 KiB of LDS leaves room for three
   constexpr size_t kQuarterLds = 160 * 1024 / 4;
   if (tiles_per_cu == 3) lds = std::max(lds, kQuarterLds + 1024);
-  // split in time: persistent workgroups that take the pieces by ticket
-  if (w) launch_lds(step_solve_face_pieces_kernel, dim3(w->n_workgroups), dim3(kFaceThreads), lds, s, b, *w);
-  else launch_lds(step_solve_face_kernel, dim3(n_tiles), dim3(kFaceThreads), lds, s, b);
+  // a piece list: persistent workgroups that take its pieces
+  if (w.pieces) launch_lds(step_solve_face_pieces_kernel, dim3(w.n_workgroups), dim3(kFaceThreads), lds, s, b, w);
+  else launch_lds(step_solve_face_kernel, dim3(n_tiles), dim3(kFaceThreads), lds, s, b, w);
 }
 
 }  // namespace egs

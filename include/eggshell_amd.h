@@ -134,6 +134,11 @@ typedef enum {
                                       normal per face: egs_debug_plan_face_normals; GS, the store-free launch, no
                                       restitution).  128 threads per 256-constraint tile.  The same bits;
                                       EGS_STEP_FACE=0 switches it off, EGS_STEP_FACE_TILES=3|4 sets the tiles per CU.
+                                      In egs_problem_step the launch also writes the velocities where every body is
+                                      in some tile, and no velocity kernel runs (EGS_STEP_FACE_VELOCITY=0: it does).
+                                      With more tiles than resident slots, that many persistent workgroups take the
+                                      tiles (EGS_STEP_FACE_PERSIST=0: a workgroup per tile; EGS_STEP_FACE_SLOTS=k
+                                      stands for the slot count, for tests).
                                       A refinement of EGS_SCHED_SHARE: only egs_problem_get_schedule_forms reports it */
   EGS_SCHED_FACE_SPLIT = 65536     /* ... whose launch is split in time: where the tiles fill the resident slots once
                                       or more and leave a remainder of at most half of them, that many tiles run as
