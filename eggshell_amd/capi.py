@@ -31,13 +31,14 @@ SCHED_CHAIN = 8192
 SCHED_SHARE = 16384
 SCHED_FACE = 32768
 SCHED_FACE_SPLIT = 65536
+SCHED_FACE_LEAN = 131072
 START_RHS, START_GIVEN, START_PREVIOUS = 0, 1, 2
 STABILIZE_INIT, STABILIZE_POST = 0, 1
 
 # every symbol include/eggshell_amd.h declares
 EXPORTS = [
     "egs_default_params", "egs_context_create", "egs_context_destroy", "egs_last_error",
-    "egs_context_synchronize", "egs_timer_start", "egs_timer_stop", "egs_kernel_time",
+    "egs_context_synchronize", "egs_context_cu_count", "egs_timer_start", "egs_timer_stop", "egs_kernel_time",
     "egs_solve_blocks", "egs_problem_create", "egs_problem_create_batch", "egs_problem_destroy", "egs_problem_set_blocks",
     "egs_problem_solve", "egs_problem_get_lambda", "egs_problem_get_accumulators",
     "egs_problem_set_state", "egs_problem_set_mass", "egs_problem_set_constraints", "egs_problem_assemble",
@@ -48,7 +49,7 @@ EXPORTS = [
     "egs_world_set_joints", "egs_world_step", "egs_world_get_bodies", "egs_world_get_contacts",
     "egs_world_get_lambda", "egs_world_info", "egs_world_create_batch", "egs_world_batch_info",
     "egs_problem_matvec", "egs_problem_get_matvec", "egs_problem_get_wres", "egs_matvec_blocks",
-    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_debug_plan_faced", "egs_debug_plan_face_normals", "egs_debug_face_split", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
+    "egs_debug_matvec_plan", "egs_debug_choose_oversize_schedule", "egs_debug_plan_timetable", "egs_debug_plan_pairable", "egs_debug_plan_chained", "egs_debug_plan_share", "egs_debug_plan_faced", "egs_debug_plan_face_normals", "egs_debug_face_split", "egs_debug_face_form", "egs_box_lcp_dantzig", "egs_box_lcp_murty",
     "egs_box_lcp_batch", "egs_box_lcp_schur", "egs_box_lcp_schur_batch", "egs_dense_condition", "egs_dense_iterate", "egs_dense_iterate_batch", "egs_debug_plan_patches", "egs_problem_debug_trace",
     "egs_mixed_constraints_solve_limits", "egs_mixed_constraints_solve_batch", "egs_problem_dense_system", "egs_problem_dense_condition", "egs_problem_step_dense",
     "egs_world_step_dense", "egs_world_dense_info", "egs_world_stabilize", "egs_world_stabilize_info",
@@ -326,6 +327,11 @@ class Context:
 
     def synchronize(self):
         self.check(load().egs_context_synchronize(self.h))
+
+    def cu_count(self):
+        n = C.c_int32(0)
+        self.check(load().egs_context_cu_count(self.h, C.byref(n)))
+        return n.value
 
     def timer_start(self):
         self.check(load().egs_timer_start(self.h))
@@ -993,6 +999,23 @@ def debug_face_split(n_tiles, slots, depth, period, sweeps, force=None):
     if st != OK:
         raise EgsError(st, "egs_debug_face_split failed")
     return tiles.value, cut.value, pieces[:n.value].copy()
+
+
+def debug_face_form(n_tiles, cus, depth, period, sweeps, max_slots=0):
+    """Host-only: the form of the FACE launch (see egs_debug_face_form) for n_tiles tiles on `cus` CUs.  Returns a dict:
+    lean (bool), us (the predicted launch of the present and of the lean form, microseconds), split (per form: split
+    tiles, s1) and lds_bytes (a lean tile's LDS request at six tiles per CU for max_slots body slots; 0: it does not fit,
+    or max_slots was not given)."""
+    lean, lds = C.c_int32(0), C.c_int64(0)
+    us, split = np.zeros(2, dtype=np.float64), np.zeros((2, 2), dtype=np.int32)
+    lib = load()
+    lib.egs_debug_face_form.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 4
+    st = lib.egs_debug_face_form(n_tiles, cus, depth, period, sweeps, max_slots, C.addressof(lean), us.ctypes.data,
+                                 split.ctypes.data, C.addressof(lds))
+    if st != OK:
+        raise EgsError(st, "egs_debug_face_form failed")
+    return {"lean": bool(lean.value), "us": (float(us[0]), float(us[1])),
+            "split": (tuple(int(v) for v in split[0]), tuple(int(v) for v in split[1])), "lds_bytes": int(lds.value)}
 
 
 def debug_plan_face_normals(n_bodies, body0, body1, data):

@@ -71,6 +71,12 @@ egs_status egs_context_synchronize(egs_context *ctx) {
   return guarded(ctx, [&]() -> egs_status { HIPCHK(hipStreamSynchronize(ctx->stream)); return EGS_OK; });
 }
 
+egs_status egs_context_cu_count(const egs_context *ctx, int32_t *cus) {
+  if (!ctx || !cus) return EGS_ERR_INVALID;
+  *cus = ctx->cu_count;
+  return EGS_OK;
+}
+
 egs_status egs_timer_start(egs_context *ctx) {
   if (!ctx) return EGS_ERR_INVALID;
   return guarded(ctx, [&]() -> egs_status { HIPCHK(hipEventRecord(ctx->t0, ctx->stream)); return EGS_OK; });

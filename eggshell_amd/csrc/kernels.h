@@ -174,7 +174,11 @@ struct FaceWork {
   double *v6;                // [n][6] the velocities egs_problem_step leaves (problem.h: v6), or NULL
   int32_t *host_stall;       // the device address of the problem's page-locked stall word: a wait that overran stores 1
 };
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork &w, hipStream_t s);
+// lean: the LEAN twins (linear held products alone, 168 VGPRs, six tiles per CU; tiles_per_cu may then be 6 too); the same bits.
+// Where a lean tile's LDS request does not fit (policy.h: face_lds_bytes returns 0) the caller keeps the present form:
+// asked for all the same, std::logic_error.
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, bool lean, const FaceWork &w,
+                            hipStream_t s);
 // ... and the 4-lanes-per-constraint schedule on the same timetable (quad_solve.hip)
 template <typename REAL>
 void launch_step_quad(const SolveArgs<REAL> &a, int method, int n_tiles, int tile_size, hipStream_t s);

@@ -1,5 +1,5 @@
 // plan_debug.cpp -- the plan-inspection entries of the C ABI (egs_debug_plan*, egs_debug_matvec_plan,
-// egs_debug_choose_oversize_schedule, egs_debug_face_split): what the host planners (plan.h, matvec_plan.h) and the schedule policy
+// egs_debug_choose_oversize_schedule, egs_debug_face_split, egs_debug_face_form): what the host planners (plan.h, matvec_plan.h) and the schedule policy
 // (policy.h) decide for a constraint graph, per constraint.  Host code only: no HIP call, no context, no device.
 #include <exception>
 
@@ -212,6 +212,18 @@ egs_status egs_debug_face_split(int32_t n_tiles, int32_t slots, int32_t depth, i
   } catch (const std::exception &) {
     return EGS_ERR_INVALID;
   }
+}
+
+egs_status egs_debug_face_form(int32_t n_tiles, int32_t cus, int32_t depth, int32_t period, int32_t sweeps,
+                               int32_t max_slots, int32_t *lean, double *us, int32_t *split, int64_t *lds_bytes) {
+  if (n_tiles < 0 || cus <= 0 || sweeps < 0) return EGS_ERR_INVALID;
+  const FaceForm f = face_form_policy(n_tiles, cus, depth, period, sweeps);
+  if (lean) *lean = f.lean ? 1 : 0;
+  if (us) { us[0] = f.us[0]; us[1] = f.us[1]; }
+  if (split)
+    for (int k = 0; k < 2; ++k) { split[2 * k] = f.split[k].tiles; split[2 * k + 1] = f.split[k].s1; }
+  if (lds_bytes) *lds_bytes = max_slots > 0 ? (int64_t)face_lds_bytes(max_slots, true, kFaceLeanTilesPerCu) : 0;
+  return EGS_OK;
 }
 
 }  // extern "C"

@@ -53,6 +53,26 @@ inline OversizeSchedule choose_oversize_schedule(int n_patch_tiles, int quad_per
 // there is no remainder to split and it stays at 48 025.  Four.
 constexpr int kFaceTilesPerCu = 4;
 
+// The LEAN form of the same kernels holds the linear w J products alone (step_face.hip: kFaceLeanLin), fits 168 VGPRs and
+// so three wavefronts per SIMD: six tiles per CU.  Six tiles share the CU's 160 KiB of LDS, so a tile may ask for 26 KiB
+// at most.  A tile's request (bytes): the accumulators (max_slots x 6 doubles) and, lean, behind them the owner's scalars the loops would otherwise reload from
+// scratch (kFaceLeanParked doubles per thread, element e of thread i at e x 128 + i); before either, the prologue keeps
+// blocks of the first assembly there while the second runs: 27 doubles per thread, lean 26 (one stays in its
+// register).  tiles_per_cu 3 / 4 below the form's own count: the request is padded past a quarter resp. a fifth of the
+// CU's LDS.  0: a lean tile of that many slots does not fit six to a CU -- the launch keeps the present kernel.
+constexpr int kFaceLeanTilesPerCu = 6;
+constexpr int kFaceTileThreads = 128;
+constexpr int kFaceStaged = 27, kFaceLeanStaged = 26, kFaceLeanParked = 18;
+constexpr size_t kCuLdsBytes = 160 * 1024, kFaceLeanLdsMax = 26 * 1024;
+inline size_t face_lds_bytes(int max_slots, bool lean, int tiles_per_cu) {
+  const size_t acc = (size_t)max_slots * 6, th = kFaceTileThreads;
+  size_t lds = (lean ? std::max(acc + kFaceLeanParked * th, kFaceLeanStaged * th) : std::max(acc, kFaceStaged * th)) * sizeof(double);
+  if (lean && lds > kFaceLeanLdsMax) return 0;
+  if (tiles_per_cu == 3) lds = std::max(lds, kCuLdsBytes / 4 + 1024);
+  else if (lean && tiles_per_cu == 4) lds = std::max(lds, kCuLdsBytes / 5 + 1024);
+  return lds;
+}
+
 // The FACE launch split in time (step_face.hip: pieces).  With n_tiles = k x slots + R, 0 < R <= slots / 2, the last
 // round keeps half the resident slots empty or more.  R tiles are then cut after sweep s1: a slot runs
 //     a first part (accumulation + sweeps 1 .. s1), then a whole tile        depth + P s1  +  depth + P S   steps
@@ -137,6 +157,51 @@ inline void face_piece_list(int n_tiles, long slots, FaceSplit f, int S, VEC &ou
 // workgroup per tile the hardware refills freed slots late (32 C3 piles: 0.600 ms where two rounds of 0.237 ms are
 // 0.474); `slots` persistent workgroups on the whole-tile list refill themselves.
 inline bool face_persist_pays(long n_tiles, long slots) { return slots > 0 && n_tiles > slots; }
+
+// Which FACE form takes a launch: the present kernels on 4 x CUs resident slots or the lean ones on 6 x CUs, each with
+// the split (face_split_policy) and the persistence rule applied to its own slot count.  A launch is predicted as the
+// busiest slot's work: per piece a fixed part (prologue, epilogue, refill), per block of four steps the form's block
+// time with every slot taken, and for a split its kFaceSplitPrologueSteps.  Six lean tiles keep a CU's SIMDs busier than
+// four present ones, but not by half: a lean block takes 1.65 times a present one, so the lean form pays only where it
+// saves a round (or the split's half round).  At and below 4 x CUs tiles the present form is kept without a prediction.
+// The constants (microseconds; MI355X, C3 piles, depth 64, period 8: a tile walks 16 + 2 S blocks), from the `fixed_us`
+// and `us_per_sweep` columns of profiles/lean/step1.json:
+//   present, 16 piles (four tiles per CU): 1.875 per sweep, 43.1 fixed  ->  0.93 per block, 28 per piece;
+//   lean, 24 piles (six tiles per CU):     3.059 per sweep, 71.7 fixed  ->  1.53 per block, 47 per piece.
+// Checked against rows of that file it was not fitted to, at 100 sweeps: present, 32 piles (two rounds) 458 predicted,
+// 468 .. 486 measured; present, 24 piles (split) 425 and 424 .. 432; lean, 24 piles 377 and 377 .. 393.
+// Nobody has measured another depth, period or CU count: there the per-piece part (which holds the prologue's and the
+// epilogue's share of a tile of THIS depth) and the block time are an extrapolation.  The guard on 4 x CUs tiles and the
+// round arithmetic keep a wrong constant from doing more than choosing the slower of two correct launches.
+constexpr double kFaceBlockUs = 0.93, kFacePieceUs = 28.0;
+constexpr double kFaceLeanBlockUs = 1.53, kFaceLeanPieceUs = 47.0;
+struct FaceForm {
+  bool lean = false;
+  double us[2] = {0.0, 0.0};   // the predicted launch, present and lean
+  FaceSplit split[2];          // ... and the split each form would take
+};
+inline double face_launch_us(long n_tiles, long slots, int depth, int P, int S, double block_us, double piece_us, FaceSplit &f) {
+  f = face_split_policy(n_tiles, slots, depth, P, S);
+  if (n_tiles <= 0 || slots <= 0) return 0.0;
+  const double tile = (double)depth + (double)P * S;
+  const long full = n_tiles / slots, rest = n_tiles % slots;
+  double steps = full * tile, pieces = (double)full;
+  if (f.tiles > 0) {   // the remainder as half tiles on every slot: the longer half, a second fill and the hand-over
+    steps += (double)depth + (double)P * std::max(f.s1, S - f.s1) + kFaceSplitPrologueSteps;
+    pieces += 1;
+  } else if (rest > 0) {
+    steps += tile;
+    pieces += 1;
+  }
+  return pieces * piece_us + steps / 4 * block_us;
+}
+inline FaceForm face_form_policy(long n_tiles, int cus, int depth, int P, int S) {
+  FaceForm r;
+  r.us[0] = face_launch_us(n_tiles, (long)cus * kFaceTilesPerCu, depth, P, S, kFaceBlockUs, kFacePieceUs, r.split[0]);
+  r.us[1] = face_launch_us(n_tiles, (long)cus * kFaceLeanTilesPerCu, depth, P, S, kFaceLeanBlockUs, kFaceLeanPieceUs, r.split[1]);
+  r.lean = n_tiles > (long)cus * kFaceTilesPerCu && r.us[1] < r.us[0];
+  return r;
+}
 
 // Isotropic bodies, batched work: the register-light tile kernel (no stored B, three
 // 256-constraint tiles per CU in fp64, four in fp32) against the regular one (fp64:

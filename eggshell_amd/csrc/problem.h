@@ -61,7 +61,7 @@ struct egs_problem {
   static constexpr uint32_t kSchedFullOnly = EGS_SCHED_SHARE;
   // ... and these out of that one as well, whose callers compare it exactly on scenes that take the form:
   // egs_problem_get_schedule_forms alone reports them
-  static constexpr uint32_t kSchedFormsOnly = EGS_SCHED_FACE | EGS_SCHED_FACE_SPLIT;
+  static constexpr uint32_t kSchedFormsOnly = EGS_SCHED_FACE | EGS_SCHED_FACE_SPLIT | EGS_SCHED_FACE_LEAN;
   bool lin_neg = false;        // J1_lin == -J0_lin on every two-body constraint, in value and bit for bit, signed zeros
                                // included (device assembly: contacts only, note_kinds; egs_problem_set_blocks: checked)
   bool joint_pairs = false;    // a ball joint joins two bodies: its assembled J1_lin holds +0 where J0_lin holds +0

@@ -28,6 +28,7 @@ struct SweepSchedule {
   bool chain = false;       // ... whose steady loop keeps a pair's accumulators in registers between its two updates (CHAIN)
   bool share = false;       // ... and a thread one linear block and one pair of weights for both constraints (SHARE)
   bool face = false;        // ... on a thread pair per box face: four updates behind one barrier, 128 threads per tile (FACE)
+  bool face_lean = false;   // ... in its LEAN form: fewer held products, 168 VGPRs, six tiles per CU (policy.h: face_form_policy)
   int face_tiles = kFaceTilesPerCu;   // ... at this many resident tiles per CU (policy.h; EGS_STEP_FACE_TILES)
   FaceSplit split;          // ... with the last split.tiles tiles cut after sweep split.s1 (policy.h: face_split_policy)
   long face_slots = 0;      // ... the workgroups of that launch the GPU holds at once (EGS_STEP_FACE_SLOTS)
@@ -42,7 +43,8 @@ struct SweepSchedule {
            (assemble ? EGS_SCHED_FUSED_ASSEMBLY : 0) | (defer ? EGS_SCHED_DEFERRED_SYSTEM : 0) |
            (started ? EGS_SCHED_START : 0) | (friction ? EGS_SCHED_FRICTION : 0) | (pair ? EGS_SCHED_PAIR : 0) |
            (chain ? EGS_SCHED_CHAIN : 0) | (share ? EGS_SCHED_SHARE : 0) |
-           (face ? EGS_SCHED_FACE : 0) | (split.tiles > 0 ? EGS_SCHED_FACE_SPLIT : 0);
+           (face ? EGS_SCHED_FACE : 0) | (split.tiles > 0 ? EGS_SCHED_FACE_SPLIT : 0) |
+           (face_lean ? EGS_SCHED_FACE_LEAN : 0);
   }
 };
 
@@ -114,13 +116,24 @@ SweepSchedule choose_sweep(egs_problem *p, int method, int sweeps, bool hist, bo
   const char *ae = std::getenv("EGS_STEP_FACE"), *te = std::getenv("EGS_STEP_FACE_TILES");
   s.face = s.share && pl.faced && p->face_normals && method == EGS_GAUSS_SEIDEL && s.defer && !p->restitution &&
            !(ae && std::atoi(ae) == 0);
-  if (te && (std::atoi(te) == 3 || std::atoi(te) == 4)) s.face_tiles = std::atoi(te);
+  // ... in its LEAN form (six tiles per CU) where the policy predicts the shorter launch for it and a tile's LDS request
+  // fits six to a CU.  EGS_STEP_FACE_LEAN=0 keeps the present kernels everywhere, =1 takes the lean ones wherever FACE
+  // holds and the request fits; EGS_STEP_FACE_TILES=6 asks for the lean form too.  Where the tiles per CU or the slot
+  // count are given, the policy (which compares the two forms at their own slot counts) is not asked.
+  const char *ne = std::getenv("EGS_STEP_FACE_LEAN"), *ke = std::getenv("EGS_STEP_FACE_SLOTS");
+  const int tiles_env = te ? std::atoi(te) : 0, lean_env = ne ? std::atoi(ne) : -1;
+  if (s.face && lean_env != 0 && face_lds_bytes(pl.max_slots, true, kFaceLeanTilesPerCu) != 0) {
+    if (lean_env == 1 || tiles_env == kFaceLeanTilesPerCu) s.face_lean = true;
+    else if (lean_env < 0 && !te && !ke)
+      s.face_lean = face_form_policy(pl.n_tiles, p->ctx->cu_count, pl.max_depth, pl.max_period, sweeps).lean;
+  }
+  if (s.face_lean) s.face_tiles = kFaceLeanTilesPerCu;
+  if (tiles_env == 3 || tiles_env == 4) s.face_tiles = tiles_env;
   // ... split in time where the last round would leave half the resident slots empty or more (policy.h).
   // EGS_STEP_FACE_SPLIT=0 keeps one workgroup per tile; EGS_STEP_FACE_SPLIT_FORCE=h,s1 splits the last h tiles after s1
   // sweeps whatever the policy says (tests, experiments).  EGS_STEP_FACE_SLOTS=k stands for the resident slots, in the
   // policy and as the grid of the persistent launch (tests: no small scene has more tiles than the GPU has slots).
   const char *xe = std::getenv("EGS_STEP_FACE_SPLIT"), *xf = std::getenv("EGS_STEP_FACE_SPLIT_FORCE");
-  const char *ke = std::getenv("EGS_STEP_FACE_SLOTS");
   s.face_slots = ke && std::atol(ke) > 0 ? std::atol(ke) : (long)p->ctx->cu_count * s.face_tiles;
   if (s.face && !(xe && std::atoi(xe) == 0)) {
     long h = 0, s1 = 0;
@@ -239,7 +252,7 @@ void launch_timetable(egs_problem *p, const SweepSchedule &sc, SolveArgs<REAL> &
         w.v6 = p->v6.p;
         p->step_velocity = egs_problem::kVelocityWritten;
       }
-      launch_step_solve_face(a, n_tiles, sc.face_tiles, w, st);
+      launch_step_solve_face(a, n_tiles, sc.face_tiles, sc.face_lean, w, st);
     } else if (sc.pair) launch_step_solve_pair(a, method, n_tiles, !sc.defer, sc.chain, sc.share, st);
     else launch_step_solve_assemble(a, method, n_tiles, !sc.defer, st);
     // the system this launch assembled: stored, or the problem's to make on demand from the state it read

@@ -5,7 +5,11 @@
 // a thread pair holds all four and runs their updates behind one barrier.  Where its tiles leave the last round of
 // resident slots half empty or emptier, that launch is split in time (step_solve_face_pieces_kernel: a tile as two
 // pieces, sweeps 1 .. s1 and s1 + 1 .. S, taken by ticket on persistent workgroups; policy.h: face_split_policy).
+// Both kernels have a LEAN twin from the same source (step_solve_face_lean_kernel, ..._lean_pieces_kernel): fewer held
+// products and the owner's scalars in LDS, 168 VGPRs, six tiles per CU instead of four -- slower blocks, taken where six
+// tiles per CU save a round (policy.h: face_form_policy).
 #include <algorithm>
+#include <stdexcept>
 
 #include "kernels.h"
 #include "policy.h"
@@ -37,6 +41,10 @@ namespace {
 #endif
 constexpr int kFaceLin = 9, kFaceAng = EGS_FACE_ANG_PRODUCTS;
 constexpr int kFaceThreads = 128, kFaceLanes = 256;
+// LEAN (168 VGPRs, three wavefronts per SIMD, six tiles per CU): no angular products and as many of the nine linear ones,
+// which serve all four members, as keep scratch out of the timetable loops with the owner's scalars parked in LDS
+// (face_park): all nine in the unsplit kernel, six in the pieces kernel (nine reload two doubles per block there).
+constexpr int kFaceLeanLin = 9, kFaceLeanLinPieces = 6;
 
 // The prologue in stages: each stage's loads are issued together, branch-free, and waited for once.
 //   1. the four members' descriptors and member 0's level;
@@ -110,9 +118,8 @@ __device__ __forceinline__ void face_assemble(const SolveArgs<double> &A, const 
 }
 // the sides of the pair's two owned constraints (the even lane's c is E's, the odd lane's O's) change hands once: this
 // lane's side of both; LIN: E's linear block and weights too
-template <bool LIN>
-__device__ __forceinline__ void face_sides(const Cons<double> &c, int side, PairLin<kFaceLin> &L, PairAng<kFaceAng> &GE,
-                                           PairAng<kFaceAng> &GO) {
+template <bool LIN, int NL, int NA>
+__device__ __forceinline__ void face_sides(const Cons<double> &c, int side, PairLin<NL> &L, PairAng<NA> &GE, PairAng<NA> &GO) {
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -130,6 +137,31 @@ __device__ __forceinline__ void face_sides(const Cons<double> &c, int side, Pair
     const double gl = dpp_all<kQuadSwap>(c.wl1), ga = dpp_all<kQuadSwap>(c.wa1);
     L.wl = side ? gl : c.wl0;
     L.wa = side ? ga : c.wa0;
+  }
+}
+
+constexpr int kFaceOff[3] = {3, 6, 7};   // D's off-diagonal entries that a forward update takes
+// LEAN: the parked values of owned constraint K (0, 1), to LDS and back (element e of this thread at park[e * 128])
+template <bool LEAN, int K>
+__device__ __forceinline__ void face_park(double *park, const Cons<double> &c) {
+  if constexpr (LEAN) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      park[(9 * K + r) * kFaceThreads] = c.rhs[r];
+      park[(9 * K + 3 + r) * kFaceThreads] = c.D[kFaceOff[r]];
+      park[(9 * K + 6 + r) * kFaceThreads] = c.inv[r];
+    }
+  }
+}
+template <bool LEAN, int K>
+__device__ __forceinline__ void face_unpark(const double *park, Cons<double> &c) {
+  if constexpr (LEAN) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      c.rhs[r] = park[(9 * K + r) * kFaceThreads];
+      c.D[kFaceOff[r]] = park[(9 * K + 3 + r) * kFaceThreads];
+      c.inv[r] = park[(9 * K + 6 + r) * kFaceThreads];
+    }
   }
 }
 
@@ -153,9 +185,10 @@ __device__ __forceinline__ void face_sides(const Cons<double> &c, int side, Pair
 // whole tiles no longer reaches every CU once the hardware's placement of workgroup numbers decides who gets which).
 // Only the prologue, the loop bounds and the epilogue differ from the unsplit kernel: n_sweeps and resume are scalar.
 // Returns false once the list is exhausted: the workgroup is done.
-template <bool PIECES>
+template <bool PIECES, bool LEAN>
 __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const FaceWork &W, unsigned char *smem, const int tid) {
   constexpr int METHOD = 1;
+  constexpr int NL = LEAN ? (PIECES ? kFaceLeanLinPieces : kFaceLeanLin) : kFaceLin, NA = LEAN ? 0 : kFaceAng;
   int tile = blockIdx.x, n_sweeps = A.sweeps, resume = 0, kind = kFaceWhole;
   if constexpr (PIECES) {
     unsigned *s_word = reinterpret_cast<unsigned *>(smem);
@@ -212,17 +245,21 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
 
   // stage 4: one assembly after the other.  The first's blocks wait in LDS (the accumulators' place, before they are
   // set up; element e of thread i at e * 128 + i) while the second is assembled from the same body values.
-  PairLin<kFaceLin> L;
-  PairAng<kFaceAng> GA, GB, GC, GD;
+  PairLin<NL> L;
+  PairAng<NA> GA, GB, GC, GD;
   Cons<double> c0 = {}, c1 = {};
   double x0[3], x1[3];
   face_assemble(A, d0, B, own0 >= 0, c0, x0);
   face_sides<true>(c0, side, L, GA, GB);
+  // (LEAN: the last linear entry stays in its register, so that six tiles' staging fits a CU: 26 doubles per thread are
+  // the 26 KiB a tile may ask for -- policy.h: face_lds_bytes)
+  constexpr int SL = LEAN ? 8 : 9;
+  static_assert(SL + 18 == (LEAN ? kFaceLeanStaged : kFaceStaged), "policy.h sizes the staging");
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
-    s_acc[e * kFaceThreads + tid] = L.J[e];
-    s_acc[(9 + e) * kFaceThreads + tid] = GA.J[e];
-    s_acc[(18 + e) * kFaceThreads + tid] = GB.J[e];
+    if (e < SL) s_acc[e * kFaceThreads + tid] = L.J[e];
+    s_acc[(SL + e) * kFaceThreads + tid] = GA.J[e];
+    s_acc[(SL + 9 + e) * kFaceThreads + tid] = GB.J[e];
   }
   asm volatile("" ::: "memory");   // stored here, loaded below: not carried in registers
   // ... and the second assembly, which no longer loads, is not scheduled into the first: one at a time in the registers
@@ -232,12 +269,22 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
   asm volatile("" ::: "memory");
 #pragma unroll
   for (int e = 0; e < 9; ++e) {
-    L.J[e] = s_acc[e * kFaceThreads + tid];
-    GA.J[e] = s_acc[(9 + e) * kFaceThreads + tid];
-    GB.J[e] = s_acc[(18 + e) * kFaceThreads + tid];
+    if (e < SL) L.J[e] = s_acc[e * kFaceThreads + tid];
+    GA.J[e] = s_acc[(SL + e) * kFaceThreads + tid];
+    GB.J[e] = s_acc[(SL + 9 + e) * kFaceThreads + tid];
   }
   face_sides<false>(c1, side, L, GC, GD);
   __syncthreads();   // every thread has its blocks back
+  // LEAN: the owner's rhs, D's off-diagonals and inv of both constraints, which the loops would otherwise reload from
+  // scratch, are parked in LDS behind the accumulators (element e of thread i at e * 128 + i) and read in the block, each
+  // constraint's ahead of its two passes
+  static_assert(kFaceLeanParked == 18, "policy.h sizes the parked values");
+  double *s_park = nullptr;
+  if constexpr (LEAN) {
+    s_park = s_acc + (size_t)A.max_slots * 6 + tid;
+    face_park<LEAN, 0>(s_park, c0);
+    face_park<LEAN, 1>(s_park, c1);
+  }
   if (PIECES && resume) {
     // the second part of a split tile: behind both assemblies, so whatever waiting there is overlaps the prologue
     unsigned *s_word = reinterpret_cast<unsigned *>(smem);
@@ -286,7 +333,7 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
   GB.form(L.wa);
   GC.form(L.wa);
   GD.form(L.wa);
-  PairShared<kFaceLin, kFaceAng> SA{L, GA}, SB{L, GB}, SC{L, GC}, SD{L, GD};
+  PairShared<NL, NA> SA{L, GA}, SB{L, GB}, SC{L, GC}, SD{L, GD};
   const int t_end = __builtin_amdgcn_readfirstlane(timetable_end<METHOD>(depth, P, n_sweeps, resume));
   __syncthreads();
 
@@ -311,8 +358,10 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
   for (;;) {
     for (; t < stop; t += 4) {
       if (due == t) {
+        face_unpark<LEAN, 0>(s_park, c0);
         pair_pass<METHOD, kQuadEven, true, true, false>(SA, ac, a, has, even, c0, x0, sweep, A.cfm);
         if (nm > 1) pair_pass<METHOD, kQuadOdd, true, false, false>(SB, ac, a, has, odd, c0, x0, sweep, A.cfm);
+        face_unpark<LEAN, 1>(s_park, c1);
         if (nm > 2) pair_pass<METHOD, kQuadEven, true, false, false>(SC, ac, a, has, even, c1, x1, sweep, A.cfm);
         if (nm > 3) pair_pass<METHOD, kQuadOdd, true, false, false>(SD, ac, a, has, odd, c1, x1, sweep, A.cfm);
         if (has) store6(ac, a);   // after the group's last active member
@@ -330,8 +379,10 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
       int tp = t % Ps;
       for (; t < t_e; t += 4) {
         if (phF == tp) {
+          face_unpark<LEAN, 0>(s_park, c0);
           pair_pass<METHOD, kQuadEven, false, true, false>(SA, ac, a, has, even, c0, x0, 1, A.cfm);
           if (nm > 1) pair_pass<METHOD, kQuadOdd, false, false, false>(SB, ac, a, has, odd, c0, x0, 1, A.cfm);
+          face_unpark<LEAN, 1>(s_park, c1);
           if (nm > 2) pair_pass<METHOD, kQuadEven, false, false, false>(SC, ac, a, has, even, c1, x1, 1, A.cfm);
           if (nm > 3) pair_pass<METHOD, kQuadOdd, false, false, false>(SD, ac, a, has, odd, c1, x1, 1, A.cfm);
           if (has) store6(ac, a);
@@ -351,6 +402,8 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
 
   // the owner's constraint numbers, read again: not held through the loops
   const int cidx0 = A.lanes[lane0 + 32 * side].cidx, cidx1 = A.lanes[lane0 + 64 + 32 * side].cidx;
+  face_unpark<LEAN, 0>(s_park, c0);
+  face_unpark<LEAN, 1>(s_park, c1);
   if (nm > 0) pair_epilogue(A, SA, ac, even, cidx0, c0, x0);
   if (nm > 1) pair_epilogue(A, SB, ac, odd, cidx0, c0, x0);
   if (nm > 2) pair_epilogue(A, SC, ac, even, cidx1, c1, x1);
@@ -384,7 +437,7 @@ __device__ __forceinline__ bool face_step(const SolveArgs<double> &A, const Face
 // (W: the velocity pointer alone is read)
 __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_kernel(const SolveArgs<double> A, const FaceWork W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  face_step<false>(A, W, smem, (int)threadIdx.x);
+  face_step<false, false>(A, W, smem, (int)threadIdx.x);
 }
 // ... persistent workgroups, as many as the GPU holds at once: each takes piece after piece until the list is exhausted
 __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_pieces_kernel(const SolveArgs<double> A, const FaceWork W) {
@@ -395,25 +448,44 @@ __global__ void __launch_bounds__(kFaceThreads, 2) step_solve_face_pieces_kernel
     // piece, so nothing formed from them is carried in registers from one piece to the next (scratch stays 0).
     SolveArgs<double> B = A;
     asm volatile("" : "+v"(tid), "+s"(B.assemble.dt), "+s"(B.assemble.erp), "+s"(B.cfm));
-    if (!face_step<true>(B, W, smem, tid)) break;
+    if (!face_step<true, false>(B, W, smem, tid)) break;
     __syncthreads();   // the epilogue has read the accumulators before the next ticket lands there
+  }
+}
+// the LEAN twins: the same source at three wavefronts per SIMD (six tiles per CU)
+__global__ void __launch_bounds__(kFaceThreads, 3) step_solve_face_lean_kernel(const SolveArgs<double> A, const FaceWork W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  face_step<false, true>(A, W, smem, (int)threadIdx.x);
+}
+__global__ void __launch_bounds__(kFaceThreads, 3) step_solve_face_lean_pieces_kernel(const SolveArgs<double> A, const FaceWork W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int tid = (int)threadIdx.x;
+  for (;;) {
+    SolveArgs<double> B = A;
+    asm volatile("" : "+v"(tid), "+s"(B.assemble.dt), "+s"(B.assemble.erp), "+s"(B.cfm));
+    if (!face_step<true, true>(B, W, smem, tid)) break;
+    __syncthreads();
   }
 }
 
 }  // namespace
 
-void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, const FaceWork &w, hipStream_t s) {
+void launch_step_solve_face(const SolveArgs<double> &a, int n_tiles, int tiles_per_cu, bool lean, const FaceWork &w,
+                            hipStream_t s) {
   if (n_tiles <= 0) return;
   SolveArgs<double> b = a;
   b.n_tiles = n_tiles;
-  // the accumulators; the prologue keeps 27 doubles per thread in the same LDS first
-  size_t lds = std::max((size_t)b.max_slots * 6, (size_t)27 * kFaceThreads) * sizeof(double);
-  // the registers allow four tiles per CU; a request above a quarter of the CU's 160 KiB of LDS leaves room for three
-  constexpr size_t kQuarterLds = 160 * 1024 / 4;
-  if (tiles_per_cu == 3) lds = std::max(lds, kQuarterLds + 1024);
+  // the accumulators, the lean form's parked values behind them; the prologue keeps its blocks in the same LDS first
+  // (policy.h: face_lds_bytes).  A lean tile whose request does not fit six to a CU is the caller's to refuse (solve.cpp:
+  // choose_sweep asks face_lds_bytes before it sizes the slots, the split and the grid for the form): no falling back
+  // here, where the work list is already the lean form's
+  static_assert(kFaceThreads == kFaceTileThreads, "policy.h sizes the LDS request for this many threads");
+  const size_t lds = face_lds_bytes(b.max_slots, lean, tiles_per_cu);
+  if (lds == 0) throw std::logic_error("a lean FACE launch asked for where a tile's LDS request does not fit");
   // a piece list: persistent workgroups that take its pieces
-  if (w.pieces) launch_lds(step_solve_face_pieces_kernel, dim3(w.n_workgroups), dim3(kFaceThreads), lds, s, b, w);
-  else launch_lds(step_solve_face_kernel, dim3(n_tiles), dim3(kFaceThreads), lds, s, b, w);
+  auto *kernel = w.pieces ? (lean ? step_solve_face_lean_pieces_kernel : step_solve_face_pieces_kernel)
+                          : (lean ? step_solve_face_lean_kernel : step_solve_face_kernel);
+  launch_lds(kernel, w.pieces ? dim3(w.n_workgroups) : dim3(n_tiles), dim3(kFaceThreads), lds, s, b, w);
 }
 
 }  // namespace egs

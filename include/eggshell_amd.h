@@ -140,13 +140,18 @@ typedef enum {
                                       tiles (EGS_STEP_FACE_PERSIST=0: a workgroup per tile; EGS_STEP_FACE_SLOTS=k
                                       stands for the slot count, for tests).
                                       A refinement of EGS_SCHED_SHARE: only egs_problem_get_schedule_forms reports it */
-  EGS_SCHED_FACE_SPLIT = 65536     /* ... whose launch is split in time: where the tiles fill the resident slots once
+  EGS_SCHED_FACE_SPLIT = 65536,    /* ... whose launch is split in time: where the tiles fill the resident slots once
                                       or more and leave a remainder of at most half of them, that many tiles run as
                                       two workgroups, sweeps 1 .. s1 and s1 + 1 .. S, so that the last round keeps
                                       every slot busy (egs_debug_face_split).  The same bits; EGS_STEP_FACE_SPLIT=0
                                       switches it off, EGS_STEP_FACE_SPLIT_FORCE=h,s1 splits the last h tiles after
                                       s1 sweeps whatever the policy says.  Only egs_problem_get_schedule_forms
                                       reports it */
+  EGS_SCHED_FACE_LEAN = 131072     /* ... on the LEAN kernels: fewer held products, 168 VGPRs, six tiles per CU instead
+                                      of four, where that is predicted to shorten the launch (egs_debug_face_form).
+                                      The same bits; EGS_STEP_FACE_LEAN=0 keeps the four-tile kernels everywhere, =1
+                                      takes the lean ones wherever the form holds, EGS_STEP_FACE_TILES also accepts 6.
+                                      Only egs_problem_get_schedule_forms reports it */
 } egs_schedule_flags;
 
 void egs_default_params(egs_solve_params *p); /* GS, 500, 1, omega 1.5, cfm 0, tol 1e-9 */
@@ -156,6 +161,8 @@ egs_status egs_context_create(int device_index, egs_context **out);
 void egs_context_destroy(egs_context *ctx);
 const char *egs_last_error(const egs_context *ctx);
 egs_status egs_context_synchronize(egs_context *ctx);
+/* The device's compute units, as the schedule policies count them (resident slots = CUs x tiles per CU). */
+egs_status egs_context_cu_count(const egs_context *ctx, int32_t *cus);
 /* hipEvent pair on the context's stream (the stream every kernel below is
  * launched on).  stop() synchronises and returns elapsed milliseconds. */
 egs_status egs_timer_start(egs_context *ctx);
@@ -1182,6 +1189,16 @@ egs_status egs_debug_plan_face_normals(int32_t n_bodies, int32_t m, const int32_
 egs_status egs_debug_face_split(int32_t n_tiles, int32_t slots, int32_t depth, int32_t period, int32_t sweeps,
                                 int32_t force_tiles, int32_t force_s1, int32_t *split_tiles, int32_t *s1,
                                 int32_t *pieces, int32_t *n_pieces);
+
+/* Host only: the form of the FACE launch (EGS_SCHED_FACE_LEAN) for n_tiles tiles on a GPU of `cus` CUs whose timetable
+ * has the given depth and period, at `sweeps` sweeps -- the policy the library itself applies: the present kernels on
+ * 4 x cus resident slots against the lean ones on 6 x cus, each with the split and persistence rules applied to its own
+ * slot count.  *lean: 1 where the lean form is predicted shorter; us[0], us[1] (NULL, or room for two): the predicted
+ * launch times of the present and the lean form in microseconds; split[0..1], split[2..3] (NULL, or room for four):
+ * each form's split tiles and s1.  max_slots > 0: *lds_bytes (NULL: not asked) is the LDS a lean tile with that many
+ * body slots asks for at six tiles per CU, 0 where it does not fit (the launch then keeps the present kernels).   */
+egs_status egs_debug_face_form(int32_t n_tiles, int32_t cus, int32_t depth, int32_t period, int32_t sweeps,
+                               int32_t max_slots, int32_t *lean, double *us, int32_t *split, int64_t *lds_bytes);
 
 /* Which kernel takes islands larger than a workgroup in a GS / SOR solve (host only, the
  * chooser the library itself uses): 0 = body patches on the 4-lanes-per-constraint kernel,
